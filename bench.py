@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W          (N >= 1: for N > 1 this process starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W   (the same ranks, started by torchrun)
+    python bench.py ... --dump-outputs DIR   (also: the last timed step's results as DIR/{ids,distances,counts}.npy, float64)
 
 One "step" = one batch of B synthetic queries through the library: hash -> walk -> sweep -> select -> final, plus,
 for N > 1, the RCCL all-gather of every rank's packed top-k and the merge kernel (zh_shard_search_*: the exchange is
@@ -228,7 +229,13 @@ def parse():
     ap.add_argument("--profile-run", action="store_true",
                     help="profiling: nothing but full windows of the bench workload (warm-up rounded up to whole windows, no R_unique "
                          "pass, no host-buffer leg, no recall): every launch of the sweep kernel in the process is comparable")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: write what the last timed step returned to the caller (ids, distances, counts of the bench "
+                         "line's workload) as DIR/<name>.npy in float64, so that two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def make_metric(za, name, parity=True):
@@ -550,8 +557,11 @@ def run_workload(env, name, S, rank, steps, warmup, exchange, recall=False, M_ov
         env.dist.all_reduce(t, op=env.dist.ReduceOp.MAX)
         elapsed = float(t.item())
     st = ix.stats()
-    last = slots[((steps + WIN - 1) // WIN - 1) % (NS + LA if look["ahead"] else NS)]["res"][(steps - 1) % WIN] if pipelined else r0
-    last_host = (last["h_ids"].numpy().copy(), last["h_counts"].numpy().copy())
+    if not pipelined:
+        last = r0
+    else:  # (--serial-windows runs every window in slot 0)
+        last = slots[0 if args.serial_windows else ((steps + WIN - 1) // WIN - 1) % (NS + LA if look["ahead"] else NS)]["res"][(steps - 1) % WIN]
+    last_host = (last["h_ids"].numpy().copy(), last["h_counts"].numpy().copy(), last["h_keys"].numpy().copy())
 
     # ---- untimed: R_unique of the timed batches (per internal batch = per window: a row shared by two batches of a window
     # counts once, so `achieved` never exceeds what the kernel really moved) ---------------------------------------
@@ -708,6 +718,8 @@ def run_workload(env, name, S, rank, steps, warmup, exchange, recall=False, M_ov
         "visits_per_batch": st["visits"] / max(st["window_batches"], 1), "rows_scored_per_batch": st["rows_scored"] / max(st["window_batches"], 1),
         "window_batches": WIN,
         "setup_s": {"fill": t_fill, "build": t_build},
+        # what the caller received from the last timed step (query batch warmup + steps - 1): main() writes it out for --dump-outputs
+        "last_step": {"ids": last_host[0], "keys": last_host[2], "counts": last_host[1], "query_batch": warmup + steps - 1},
     }
     if st.get("approx_batches_accum"):
         # the table scan read half-width (fp16) copies of the queries; what the intervals left for the exact passes (last internal batch)
@@ -1113,6 +1125,33 @@ def write_detail(full):
     return doc, where
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0x5EB2A004
+
+
+def dump_outputs(last, dname, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the last timed step's results as the caller received them, in float64 -- ids.npy (global row ids, -1 past a
+    query's count), distances.npy (the f64 each key is the bit pattern of, +inf past a query's count), counts.npy.  Over `limit` bytes
+    in all: the rows of a fixed, seeded sample of the queries, whose indices go to query_rows.npy.  Returns the names written."""
+    ids = np.ascontiguousarray(last["ids"]).view(np.uint64)
+    keys = np.ascontiguousarray(last["keys"]).view(np.uint64)
+    counts = np.asarray(last["counts"]).astype(np.int64)
+    b, k = ids.shape
+    valid = np.arange(k)[None, :] < counts[:, None]
+    out = {"ids": np.where(valid, ids.astype(np.float64), -1.0),
+           "distances": np.where(valid, keys.view(np.float64), np.inf),
+           "counts": counts.astype(np.float64)}
+    if 8 * (2 * k + 1) * b > limit:
+        n = max(1, (limit - 4096) // (8 * (2 * k + 2)))  # (4 KB: the .npy headers)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(b, size=n, replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+        out["query_rows"] = rows.astype(np.float64)
+    os.makedirs(dname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dname, name + ".npy"), a)
+    return sorted(out)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:  # no launcher: be one
@@ -1132,6 +1171,11 @@ def main():
     res, ix, group, wl, M_shard = run_workload(env, name, S, env.rank if not emu else 0, args.steps, args.warmup, exchange=S > 1,
                                                recall=main_recall, M_override=args.max_node_size,
                                                rows_override=args.rows, batch_override=args.batch, kind_override=kind)
+    last_step = res.pop("last_step")
+    if args.dump_outputs and env.rank == 0:
+        names = dump_outputs(last_step, args.dump_outputs)
+        print("bench.py: query batch %d (the last timed step) -> %s in %s" % (last_step["query_batch"], ", ".join(names), args.dump_outputs),
+              file=sys.stderr)
     if args.data == "iid":  # (the committed counters are those of the iid command)
         pmc_traffic(args, name, S, res["roofline"])
     cpu = None

@@ -163,8 +163,7 @@ ZF_EXPORT void zf_search_batch(const int32_t *plane, const int32_t *left, const 
     Forest f{plane, left, right, roots, planes, consts, leaf_ids, d, T};
     uint64_t rows = 0;
 #ifdef _OPENMP
-    if (nthreads > 0) omp_set_num_threads(nthreads);
-#pragma omp parallel reduction(+ : rows)
+#pragma omp parallel num_threads(nthreads > 0 ? nthreads : omp_get_max_threads()) reduction(+ : rows)
 #endif
     {
         Ctx c;

@@ -878,8 +878,7 @@ ZO_EXPORT void zo_search_batch(const zo_forest *f, const float *X, const float *
                                zo_stats *st) {
     uint64_t rs = 0, pe = 0, lv = 0, cd = 0;
 #ifdef _OPENMP
-    if (nthreads > 0) omp_set_num_threads(nthreads);
-#pragma omp parallel reduction(+ : rs, pe, lv, cd)
+#pragma omp parallel num_threads(nthreads > 0 ? nthreads : omp_get_max_threads()) reduction(+ : rs, pe, lv, cd)
 #endif
     {
         zo_ctx c; ctx_init(&c, f, X, metric, mode);
@@ -905,8 +904,7 @@ ZO_EXPORT void zo_search_batch_synth(const zo_forest *f, uint64_t seed_rows, uin
                                      uint32_t *out_counts, int nthreads, zo_stats *st) {
     uint64_t rs = 0, pe = 0, lv = 0, cd = 0;
 #ifdef _OPENMP
-    if (nthreads > 0) omp_set_num_threads(nthreads);
-#pragma omp parallel reduction(+ : rs, pe, lv, cd)
+#pragma omp parallel num_threads(nthreads > 0 ? nthreads : omp_get_max_threads()) reduction(+ : rs, pe, lv, cd)
 #endif
     {
         zo_ctx c; ctx_init_synth(&c, f, seed_rows, first_row, kind, metric, mode);

@@ -1,9 +1,12 @@
 """The line the driver parses (round 4's final stdout line was 25.9 KB and BENCH_r04.json has `parsed: null`).
 bench.compact_line on a canned full record -- round 4's own 25.9-KB record, committed under profiles/ -- must give one
-strictly-JSON object below the limit that still carries the contract's keys, `roofline` and `cpu_baseline`.  CPU only."""
+strictly-JSON object below the limit that still carries the contract's keys, `roofline` and `cpu_baseline`.
+Also the --dump-outputs writer (bench.dump_outputs).  CPU only."""
 import json
 import os
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -68,3 +71,43 @@ def test_detail_record_is_strict_json(tmp_path, monkeypatch):
     assert "NaN" not in doc and json.loads(doc)["x"] is None
     assert sorted(where) == ["bench_detail.json", os.path.join("gpurun_out", "bench_detail.json")]
     assert json.load(open(tmp_path / "gpurun_out" / "bench_detail.json"))["value"] > 0
+
+
+def _last_step(b, k, rng):
+    ids = rng.integers(0, 1 << 40, size=(b, k)).astype(np.int64)
+    keys = np.sort(rng.random((b, k)) * 100.0, axis=1).view(np.int64)  # a key is the bit pattern of its f64 distance
+    counts = rng.integers(1, k + 1, size=b).astype(np.int32)
+    past = np.arange(k)[None, :] >= counts[:, None]
+    ids[past] = -1  # UINT64_MAX past a query's count, as the library leaves it
+    keys[past] = -1
+    return {"ids": ids, "keys": keys, "counts": counts, "query_batch": 7}
+
+
+def test_dump_outputs_writes_the_callers_arrays_in_float64(tmp_path):
+    import bench
+    last = _last_step(16, 10, np.random.default_rng(1))
+    names = bench.dump_outputs(last, str(tmp_path / "out"))
+    assert names == ["counts", "distances", "ids"]
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert (got["counts"] == last["counts"]).all()
+    for b in range(16):
+        c = int(last["counts"][b])
+        assert (got["ids"][b, :c] == last["ids"][b, :c]).all() and (got["ids"][b, c:] == -1).all()
+        assert (got["distances"][b, :c] == last["keys"][b, :c].view(np.float64)).all() and np.isinf(got["distances"][b, c:]).all()
+
+
+def test_dump_outputs_samples_a_fixed_set_of_queries_over_the_limit(tmp_path):
+    import bench
+    last = _last_step(4096, 100, np.random.default_rng(2))
+    limit = 1 << 20
+    for run in ("a", "b"):
+        names = bench.dump_outputs(last, str(tmp_path / run), limit=limit)
+        assert names == ["counts", "distances", "ids", "query_rows"]
+        assert sum(os.path.getsize(tmp_path / run / (n + ".npy")) for n in names) <= limit
+    rows = np.load(tmp_path / "a" / "query_rows.npy")
+    assert (rows == np.load(tmp_path / "b" / "query_rows.npy")).all() and 0 < len(rows) < 4096
+    ids = np.load(tmp_path / "a" / "ids.npy")
+    r = rows.astype(np.int64)
+    assert ids.shape == (len(rows), 100) and (ids[:, 0] == last["ids"][r, 0]).all()
+    assert (np.load(tmp_path / "a" / "counts.npy") == last["counts"][r]).all()

@@ -28,3 +28,20 @@ def test_fast_port_matches_the_oracle_within_summation_order(n, d, M, T, k, kind
             else:
                 assert len(set(oi[b, :c].tolist()) & set(fi[b, :c].tolist())) >= c - 2
     assert zf.isa() in ("avx2", "avx512")
+
+
+def test_an_explicit_thread_count_does_not_outlive_the_call():
+    """nthreads > 0 sizes that one call's parallel region only: the process's default (what later calls with nthreads = 0 use, e.g. every
+    oracle check of the GPU tests that run after this file in the same process) stays as it was"""
+    X = zo.synth_rows(2000, 32)
+    f = zo.Forest.build(X, 50, 3)
+    ff = zf.FastForest(X, f.arrays())
+    Q = zo.synth_queries(8, 32, 2000)
+    before = (zo.num_threads(), zf.num_threads())
+    want = f.search_batch(Q, 10, zo.L2SQ, 0)
+    ff.search_batch(Q, 10, zf.L2SQ, 0, nthreads=1)
+    got = f.search_batch(Q, 10, zo.L2SQ, 0, nthreads=1)
+    fs = zo.Forest.borrow_synth(2000, 32, 50, f.arrays())  # (synth_rows' default generator: the same rows as X)
+    got_synth = fs.search_batch_synth(Q, 10, zo.L2SQ, 0, nthreads=1)
+    assert (zo.num_threads(), zf.num_threads()) == before
+    assert all((a == b).all() and (a == c).all() for a, b, c in zip(want, got, got_synth))

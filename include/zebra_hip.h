@@ -501,10 +501,8 @@ ZH_API int zh_set_hash_mode(zh_index *idx, int mode);
 
 ZH_API const char *zh_last_error(void);
 ZH_API const char *zh_version(void);
-/* Device memory.  With ZH_POOL=1 in the environment, blocks of 32 MiB and more that an index or a search context lets go of are kept by the library
- * (a process-wide cache keyed by size) and handed to the next buffer of a fitting size instead of going back to the driver ("order
- * effect": worth ~5 % on an index created late in a process; off by default).  hipMalloc failing empties the cache by itself; this call empties it
- * on request (e.g. before another library needs the memory).  Without ZH_POOL=1 it does nothing. */
+/* Device memory.  The library caches no device memory: every buffer an index or a search context lets go of goes back to the driver.  This call
+ * does nothing and returns ZH_OK; it stays in the ABI for callers that already use it. */
 ZH_API int zh_trim_device_memory(void);
 
 #ifdef __cplusplus

@@ -16,7 +16,6 @@
 #include <new>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include "zh_internal.h"
@@ -60,194 +59,6 @@ extern "C" const char *zh_version(void) { return "zebra-hip 0.1 (gfx950)"; }
 // ------------------------------------------------------------------------------------------------
 // growable device buffer
 // ------------------------------------------------------------------------------------------------
-// Device memory for the library's buffers.  Default: hipMalloc.  ZH_VMM=1 (read once; an experiment for the "order effect", DESIGN.md s9: an index
-// whose buffers are allocated after another library has churned device memory scans 25-40 % slower): allocations of 2 MiB and more are made through
-// the virtual-memory API instead -- an address range reserved, physical memory created in chunks of ZH_VMM_CHUNK_MB (default 256) and mapped -- so
-// that what backs a buffer is a handful of large physical allocations whatever state hipMalloc's pool is in.
-struct VmmRec { size_t size; std::vector<hipMemGenericAllocationHandle_t> handles; std::vector<size_t> sizes; };
-static std::mutex g_vmm_mu;
-static std::unordered_map<void *, VmmRec> g_vmm;
-static int vmm_mode() {
-    static const int m = [] { const char *e = getenv("ZH_VMM"); return e ? atoi(e) : 0; }();
-    return m;
-}
-// ---- the block cache (round 6; the "order effect"), OPT-IN: ZH_POOL=1.  How a buffer is MAPPED decides how fast the matrix-core scan
-// runs over it: the same cfg3 launch takes 3.2 ms on hipMalloc'd buffers of a fresh process and on ranges of the virtual-memory API aligned to 2 MiB
-// and backed by 256-MiB chunks, 3.7 ms on ranges aligned to 4 KiB, 3.4-4.8 on ranges made of 2-MiB chunks (profiles/r06_order_effect.txt; ZH_VMM above
-// is that experiment) -- and 3.6-3.8 on the hipMalloc'd buffers of the second / third index a process creates.  With the cache, large blocks are not
-// handed back to the driver when an index or a context lets go of them: they wait here, keyed by size, and the next buffer of a fitting size takes
-// one (what a framework's caching allocator does); hipMalloc is asked only for what no cached block serves, and when it fails the cache is emptied
-// and it is asked again.  Measured: the late index's launch 3.77 -> 3.59 ms (cfg4 shard), 0.99 -> 0.93 (cfg2) -- a twentieth, not the effect: buffers
-// that are NEW late in a process are slow whether or not anything was freed before them.  Off by default (held memory is invisible to other
-// libraries' allocators); zh_trim_device_memory() empties it; blocks below 32 MiB are not kept.
-struct PoolBlock { void *p; size_t cap; int dev; };
-static std::mutex g_pool_mu;
-static std::vector<PoolBlock> g_pool;
-static std::unordered_map<void *, size_t> g_pool_caps;  // every live block of 32 MiB and more this library allocated: its capacity
-static size_t g_pool_bytes = 0;
-static bool pool_on() {
-    static const bool on = [] { const char *e = getenv("ZH_POOL"); return e && e[0] == '1'; }();
-    return on;
-}
-static const size_t POOL_MIN = size_t(32) << 20;
-static void zh_dev_free_raw(void *p);
-static size_t pool_cached_bytes(int dev) {
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    size_t n = 0;
-    for (const PoolBlock &b : g_pool) if (b.dev == dev) n += b.cap;
-    return n;
-}
-static void pool_trim() {
-    std::vector<PoolBlock> gone;
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mu);
-        gone.swap(g_pool);
-        g_pool_bytes = 0;
-    }
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (const PoolBlock &b : gone) {
-        { std::lock_guard<std::mutex> lk(g_pool_mu); g_pool_caps.erase(b.p); }
-        (void)hipSetDevice(b.dev);
-        zh_dev_free_raw(b.p);
-    }
-    (void)hipSetDevice(cur);
-}
-// free device memory as the library's own headroom rules should see it: what the driver reports plus what the block cache would give back
-static hipError_t zh_mem_info(size_t *mem_free, size_t *mem_total) {
-    hipError_t e = hipMemGetInfo(mem_free, mem_total);
-    if (e != hipSuccess) return e;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) *mem_free += pool_cached_bytes(dev);
-    return hipSuccess;
-}
-static hipError_t zh_dev_alloc_raw(void **out, size_t bytes);
-static hipError_t zh_dev_alloc(void **out, size_t bytes) {
-    if (pool_on() && bytes >= POOL_MIN) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        {
-            std::lock_guard<std::mutex> lk(g_pool_mu);
-            size_t best = (size_t)-1;
-            for (size_t i = 0; i < g_pool.size(); i++)  // best fit, at most half as much again as asked for
-                if (g_pool[i].dev == dev && g_pool[i].cap >= bytes && g_pool[i].cap <= bytes + bytes / 2 && (best == (size_t)-1 || g_pool[i].cap < g_pool[best].cap)) best = i;
-            if (best != (size_t)-1) {
-                *out = g_pool[best].p;
-                g_pool_bytes -= g_pool[best].cap;
-                g_pool[best] = g_pool.back();
-                g_pool.pop_back();
-            } else
-                *out = nullptr;
-        }
-        if (*out) {
-            // hipFree would have waited for everything queued on the device before the block could be handed out again: so does a hit (rare: an
-            // index or a context being set up)
-            (void)hipDeviceSynchronize();
-            return hipSuccess;
-        }
-        hipError_t e = zh_dev_alloc_raw(out, bytes);
-        if (e != hipSuccess) {  // out of memory with blocks in the cache: give them back and ask again
-            (void)hipGetLastError();
-            pool_trim();
-            e = zh_dev_alloc_raw(out, bytes);
-        }
-        if (e == hipSuccess) {
-            std::lock_guard<std::mutex> lk(g_pool_mu);
-            g_pool_caps[*out] = bytes;
-        }
-        return e;
-    }
-    hipError_t e = zh_dev_alloc_raw(out, bytes);
-    if (e != hipSuccess && pool_on() && g_pool_bytes) {
-        (void)hipGetLastError();
-        pool_trim();
-        e = zh_dev_alloc_raw(out, bytes);
-    }
-    return e;
-}
-static void zh_dev_free_raw(void *p);
-static void zh_dev_free(void *p) {
-    if (!p) return;
-    if (pool_on()) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        std::lock_guard<std::mutex> lk(g_pool_mu);
-        auto it = g_pool_caps.find(p);
-        if (it != g_pool_caps.end()) {  // (a block of this library's, 32 MiB or more: it stays mapped; nothing reads it once a later user's work is queued behind this call in host order -- hipFree's own rule for the caller)
-            g_pool.push_back(PoolBlock{p, it->second, dev});
-            g_pool_bytes += it->second;
-            return;
-        }
-    }
-    zh_dev_free_raw(p);
-}
-static hipError_t zh_dev_alloc_raw(void **out, size_t bytes) {
-    if (vmm_mode() <= 0 || bytes < (size_t(2) << 20)) return hipMalloc(out, bytes);
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    hipMemAllocationProp prop{};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = dev;
-    size_t gran = 0;
-    if ((e = hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended)) != hipSuccess || gran == 0) return hipMalloc(out, bytes);
-    static const size_t chunk_mb = [] { const char *c = getenv("ZH_VMM_CHUNK_MB"); return (size_t)(c ? atoi(c) : 256); }();
-    // the reported granularity is 4 KiB on this platform (profiles/micro/vmm_probe.hip): the range's ALIGNMENT and the chunks' sizes are what let the
-    // page tables use large fragments -- ZH_VMM_ALIGN_MB (default 2; 0 = the reported granularity, for the experiment's control)
-    static const size_t align_mb = [] { const char *c = getenv("ZH_VMM_ALIGN_MB"); return (size_t)(c ? atoi(c) : 2); }();
-    if (align_mb) gran = std::max<size_t>(gran, align_mb << 20);
-    const size_t chunk = std::max<size_t>(gran, (chunk_mb << 20) / gran * gran);
-    const size_t total = (bytes + gran - 1) / gran * gran;
-    void *va = nullptr;
-    if ((e = hipMemAddressReserve(&va, total, gran, nullptr, 0)) != hipSuccess) return e;
-    VmmRec rec;
-    rec.size = total;
-    size_t off = 0;
-    while (off < total) {
-        const size_t sz = std::min(chunk, total - off);
-        hipMemGenericAllocationHandle_t h;
-        if ((e = hipMemCreate(&h, sz, &prop, 0)) != hipSuccess) break;
-        if ((e = hipMemMap((char *)va + off, sz, 0, h, 0)) != hipSuccess) { hipMemRelease(h); break; }
-        rec.handles.push_back(h); rec.sizes.push_back(sz);
-        off += sz;
-    }
-    if (e == hipSuccess) {
-        hipMemAccessDesc acc{};
-        acc.location = prop.location;
-        acc.flags = hipMemAccessFlagsProtReadWrite;
-        e = hipMemSetAccess(va, total, &acc, 1);
-    }
-    if (e != hipSuccess) {
-        size_t o2 = 0;
-        for (size_t i = 0; i < rec.handles.size(); i++) { hipMemUnmap((char *)va + o2, rec.sizes[i]); hipMemRelease(rec.handles[i]); o2 += rec.sizes[i]; }
-        hipMemAddressFree(va, total);
-        (void)hipGetLastError();
-        return e;
-    }
-    {
-        std::lock_guard<std::mutex> lk(g_vmm_mu);
-        g_vmm.emplace(va, std::move(rec));
-    }
-    *out = va;
-    return hipSuccess;
-}
-static void zh_dev_free_raw(void *p) {
-    if (!p) return;
-    VmmRec rec;
-    bool mine = false;
-    {
-        std::lock_guard<std::mutex> lk(g_vmm_mu);
-        auto it = g_vmm.find(p);
-        if (it != g_vmm.end()) { rec = std::move(it->second); g_vmm.erase(it); mine = true; }
-    }
-    if (!mine) { hipFree(p); return; }
-    hipDeviceSynchronize();  // (hipFree's guarantee: nothing in flight still uses the range)
-    size_t off = 0;
-    for (size_t i = 0; i < rec.handles.size(); i++) { hipMemUnmap((char *)p + off, rec.sizes[i]); hipMemRelease(rec.handles[i]); off += rec.sizes[i]; }
-    hipMemAddressFree(p, rec.size);
-}
-
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
@@ -265,32 +76,32 @@ struct DevBuf {
         if (bytes <= cap) return ZH_OK;
         if (defer) bytes += bytes / 8;
         if (defer && old_bytes + cap > (size_t(2) << 30)) {
-            for (void *o : old) zh_dev_free(o);
+            for (void *o : old) hipFree(o);
             old.clear();
             old_bytes = 0;
         }
         size_t ncap = std::max(bytes, cap + cap / 2);
         ncap = (ncap + 255) & ~size_t(255);
         void *np = nullptr;
-        hipError_t e = zh_dev_alloc(&np, ncap);
+        hipError_t e = hipMalloc(&np, ncap);
         if (e != hipSuccess) {
             ncap = (bytes + 255) & ~size_t(255);
-            e = zh_dev_alloc(&np, ncap);
+            e = hipMalloc(&np, ncap);
         }
         if (e != hipSuccess) return fail(ZH_ENOMEM, "hipMalloc(%zu bytes): %s", ncap, hipGetErrorString(e));
         if (keep && p && cap) {
             e = hipMemcpyAsync(np, p, cap, hipMemcpyDeviceToDevice, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) { zh_dev_free(np); return fail(ZH_EHIP, "grow copy: %s", hipGetErrorString(e)); }
+            if (e != hipSuccess) { hipFree(np); return fail(ZH_EHIP, "grow copy: %s", hipGetErrorString(e)); }
         }
-        if (p) { if (defer) { old.push_back(p); old_bytes += cap; } else zh_dev_free(p); }
+        if (p) { if (defer) { old.push_back(p); old_bytes += cap; } else hipFree(p); }
         p = np;
         cap = ncap;
         return ZH_OK;
     }
     void release() {
-        if (p) zh_dev_free(p);
-        for (void *o : old) zh_dev_free(o);
+        if (p) hipFree(p);
+        for (void *o : old) hipFree(o);
         old.clear();
         old_bytes = 0;
         p = nullptr;
@@ -1583,7 +1394,6 @@ static int build_blocks_inner(zh_index *ix) {
     ix->blocks_valid = true;
     ix->blocks_inner = true;
     ix->blk_recs_b = n_inner_recs;
-    if (getenv("ZH_DEBUG_BLOCKS")) fprintf(stderr, "zebra_hip: blocked view (inner-node blocks): %u blocks, %u upper nodes, %zu inner records\n", n_blocks, ix->n_upper, n_inner_recs);
     return ZH_OK;
 }
 
@@ -1677,7 +1487,6 @@ static int build_blocks(zh_index *ix) {
     ix->n_blocks = n_blocks;
     ix->n_upper = (uint32_t)(upper.size() / 2);
     ix->blocks_valid = true;
-    if (getenv("ZH_DEBUG_BLOCKS")) fprintf(stderr, "zebra_hip: blocked view (round-2 blocks): %u blocks, %u upper nodes\n", n_blocks, ix->n_upper);
     return ZH_OK;
 }
 
@@ -1719,13 +1528,13 @@ static int build_row_leaf(zh_index *ix) {
 // perm_rows = 0: id order (it won, there is no table, the order is switched off, or there is no room for the sort).  ZH_ROW_ORDER=0|2|3 forces one.
 static int build_scan_perm(zh_index *ix) {
     const char *env_o = getenv("ZH_ROW_ORDER");  // (read when a copy is made: tests and A/B switch it)
-    const int forced = env_o ? atoi(env_o) : (getenv("ZH_NO_ROW_ORDER") ? 0 : -1);
+    const int forced = env_o ? atoi(env_o) : -1;
     ix->perm_rows = 0;
     ix->perm_gen++;
     ix->order_keys = 0;
     if (forced == 0 || ix->row_order_off || !ix->row_leaf_valid || ix->row_leaf_rows != ix->n_rows || ix->n_rows < 32 || ix->n_rows > 0x7FFFFFF0ull) return ZH_OK;
     size_t mem_free = 0, mem_total = 0;  // the sort's scratch: ~28 bytes per row, released before the copy is made
-    if (zh_mem_info(&mem_free, &mem_total) != hipSuccess || mem_free < ix->n_rows * 48 + mem_total / 16) return ZH_OK;
+    if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess || mem_free < ix->n_rows * 48 + mem_total / 16) return ZH_OK;
     DevBuf cand, dsum;
     if (ix->scan_perm.ensure(ix->n_rows * 4) || cand.ensure(ix->n_rows * 4) || dsum.ensure(8)) { cand.release(); dsum.release(); return ZH_OK; }
     const uint2 *rl = ix->row_leaf.as<uint2>();
@@ -1773,7 +1582,7 @@ static int ensure_row_leaf_p(zh_index *ix) {
     // the same headroom rule as the copies themselves: a sixteenth of the device stays free for the batches' scratch
     const uint64_t want_p = std::max<uint64_t>(ix->n_rows * T, 1) * sizeof(uint2);
     size_t mem_free = 0, mem_total = 0;
-    if (want_p > ix->row_leaf_p.cap && (zh_mem_info(&mem_free, &mem_total) != hipSuccess || mem_free < want_p + mem_total / 16)) { ix->perm_rows = 0; return ZH_OK; }
+    if (want_p > ix->row_leaf_p.cap && (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess || mem_free < want_p + mem_total / 16)) { ix->perm_rows = 0; return ZH_OK; }
     int rc = quiesce_before_rewrite();
     if (rc) return rc;
     rc = ix->row_leaf_p.ensure(want_p);
@@ -1797,7 +1606,7 @@ static int ensure_row_half(zh_index *ix, bool *ok) {
     size_t mem_free = 0, mem_total = 0;
     const uint64_t want = std::max<uint64_t>(tiles, 1) * 16 * (d * 2 + sizeof(float2));
     const bool room = want <= ix->row_half.cap + ix->row_meta.cap ||
-                      (zh_mem_info(&mem_free, &mem_total) == hipSuccess && mem_free >= want + want / 2 + mem_total / 16);
+                      (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_free >= want + want / 2 + mem_total / 16);
     // No room for the copy (64M x 768 on one GPU: 196 GB of rows + 98 GB), or ZH_ROW_HALF_META_ONLY=1 (tests; read per call): the per-row scales and
     // norms alone (8 bytes per row) -- scan_mfma_kernel<D, true> then converts the f32 rows itself, to the bits the copy would hold (round 6: the
     // same matrix-core scan at every N of the series)
@@ -1805,7 +1614,7 @@ static int ensure_row_half(zh_index *ix, bool *ok) {
     const bool meta_only = !room || (mo_e && mo_e[0] == '1');
     if (meta_only) {
         const uint64_t want_meta = std::max<uint64_t>(tiles, 1) * 16 * sizeof(float2);
-        const bool room_meta = want_meta <= ix->row_meta.cap || (zh_mem_info(&mem_free, &mem_total) == hipSuccess && mem_free >= want_meta + mem_total / 16);
+        const bool room_meta = want_meta <= ix->row_meta.cap || (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_free >= want_meta + mem_total / 16);
         ix->row_half.release();
         if (!room_meta || ix->row_meta.ensure(want_meta, false, ix->stream) != ZH_OK || ix->row_rho_dev.ensure(4) != ZH_OK) {
             ix->row_meta.release();
@@ -1872,7 +1681,7 @@ static int ensure_row_half128(zh_index *ix, bool *ok, bool want_bytes) {
     ix->h128_failed = false;
     size_t mem_free = 0, mem_total = 0;
     const uint64_t want = std::max<uint64_t>(ix->n_rows, 1) * (bytes ? 128 : 256);
-    const bool room = want <= ix->row_half128.cap || (zh_mem_info(&mem_free, &mem_total) == hipSuccess && mem_free >= want + want / 2 + mem_total / 16);
+    const bool room = want <= ix->row_half128.cap || (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_free >= want + want / 2 + mem_total / 16);
     if (!room || ix->row_half128.ensure(want, true, ix->stream) != ZH_OK || ix->row_rho_dev.ensure(12) != ZH_OK) {
         ix->row_half128.release();
         ix->h128_failed = true; ix->h128_bytes = false;
@@ -1936,10 +1745,9 @@ static int ensure_row_half128(zh_index *ix, bool *ok, bool want_bytes) {
 // longer fit beside the stream in the 8 x 4 MB of L2.  zh_set_sweep_mode / ZH_SWEEP_MODE=leaf|scan force one of them.
 static bool use_approx(const zh_index *ix, const ZhTotals &tot, size_t B, size_t k, int metric);
 // The half-width scan on the matrix cores (scan_mfma_kernel) where it has a kernel and the index can keep an fp16 copy of its rows
-// (+50 % of the row table; ensure_row_half): mode 5 / ZH_NO_MFMA=1 keep the VALU kernel, which reads the f32 rows.
+// (+50 % of the row table; ensure_row_half): mode 5 keeps the VALU kernel, which reads the f32 rows.
 static bool mfma_wanted(const zh_index *ix) {
-    static const bool off = getenv("ZH_NO_MFMA") != nullptr;
-    return !off && ix->sweep_mode != 5 && zh_scan_mfma_supported(ix->opt.dim, ix->n_trees) && !ix->mfma_f32_off &&
+    return ix->sweep_mode != 5 && zh_scan_mfma_supported(ix->opt.dim, ix->n_trees) && !ix->mfma_f32_off &&
            !(ix->row_half_failed && ix->scale_gen == ix->rows_gen && ix->scale_rows == ix->n_rows);
 }
 static bool choose_scan(const zh_index *ix, const ZhTotals &tot, int metric, size_t B, size_t k) {
@@ -1972,11 +1780,10 @@ static bool choose_scan(const zh_index *ix, const ZhTotals &tot, int metric, siz
 // lists fit the per-query sort.  ZH_SWEEP_MODE=scan / zh_set_sweep_mode(2) keep the f32 scan; =approx / mode 4 say so explicitly.
 static bool use_approx(const zh_index *ix, const ZhTotals &tot, size_t B, size_t k, int metric) {
     static const int forced = [] { const char *e = getenv("ZH_SWEEP_MODE"); return !e ? 0 : (e[0] == 's' ? 2 : (e[0] == 'a' ? 4 : 1)); }();
-    static const bool off = getenv("ZH_NO_APPROX") != nullptr;
     const int sm_ = ix->sweep_mode.load();
     int mode = sm_ == 3 ? forced : (sm_ ? sm_ : forced);
     if (mode == 5) mode = 4;
-    if (off || mode == 2 || mode == 1 || mode == 6) return false;
+    if (mode == 2 || mode == 1 || mode == 6) return false;
     if (!zh_scan_approx_supported(ix->opt.dim, ix->n_trees, metric) || k > 256 || B == 0 || B >= (1u << 24)) return false;  // (24 bits of a packed pair record)
     if (tot.takes > 2048ull * B || tot.visits > 8ull * B * ix->n_trees) return false;
     // by itself only where it pays: per pair it moves half the bytes, but a window of ONE cfg3 batch (4.3 pairs per stored row) gains 4 % on
@@ -1991,11 +1798,10 @@ static bool use_approx(const zh_index *ix, const ZhTotals &tot, size_t B, size_t
 
 // The leaf-major sweep of a d = 128 table at half width (sweep128h_kernel)?  Where the f32 sweep is what HBM gives random 512-byte rows: long
 // leaves, many scored rows; the same list limits as the half-width scan.  zh_set_sweep_mode(6) asks for it wherever it is implemented,
-// (1) keeps the f32 sweep; ZH_NO_LEAF_HALF=1 switches it off.
+// (1) keeps the f32 sweep.
 static bool use_approx_leaf(const zh_index *ix, const ZhTotals &tot, size_t B, size_t k, int metric) {
-    static const bool off = getenv("ZH_NO_LEAF_HALF") != nullptr || getenv("ZH_NO_APPROX") != nullptr;
     static const bool env_sweep = getenv("ZH_SWEEP_MODE") != nullptr;
-    if (off || ix->opt.dim != 128 || !zh_sweep_has_predicate(128, metric)) return false;
+    if (ix->opt.dim != 128 || !zh_sweep_has_predicate(128, metric)) return false;
     if (ix->sweep_mode != 6 && (env_sweep || (ix->sweep_mode != 0 && ix->sweep_mode != 3))) return false;
     if (k > 256 || B == 0 || B >= (1u << 24) || tot.takes > 2048ull * B || tot.visits > 8ull * B * ix->n_trees) return false;
     if (ix->h128_failed && ix->h128_gen == ix->rows_gen && ix->h128_rows == ix->n_rows) return false;
@@ -2128,10 +1934,9 @@ int ctx_wait(zh_search_ctx *c);
 // A batch hashed from row scores can pick its candidates from them (zh_search.hip, "Prefilter"): for the metrics the scores
 // determine, leaves short enough for the per-lane selection, and forests this library built (a row is in one leaf per tree).
 static bool use_prefilter(const zh_index *ix, const zh_search_ctx *c, size_t k, int metric) {
-    static const bool off = getenv("ZH_NO_PREFILTER") != nullptr;  // A/B: sweep + select for every batch
     // (mode 3 keeps trying past two strikes -- a caller who knows the overflows are rare -- but not past eight in a row: every one is a batch computed twice)
     const uint32_t strikes = ix->prefilter_strikes.load();
-    if (off || !c->score_hash || c->prefilter_off_once || c->stream_ordered || (strikes >= 2 && ix->sweep_mode != 3) || strikes >= 8) return false;
+    if (!c->score_hash || c->prefilter_off_once || c->stream_ordered || (strikes >= 2 && ix->sweep_mode != 3) || strikes >= 8) return false;
     static const bool env_sweep = getenv("ZH_SWEEP_MODE") != nullptr;
     if ((ix->sweep_mode != 0 && ix->sweep_mode != 3) || (env_sweep && ix->sweep_mode != 3)) return false;  // a sweep was asked for
     if (metric != ZH_L2SQ && metric != ZH_L2 && metric != ZH_COSINE) return false;
@@ -2231,10 +2036,8 @@ static int ctx_begin(zh_search_ctx *c, const float *const *dQs, size_t nwin, siz
     ZhForestDev f = forest_dev(ix);
     HIPCHK(hipEventRecord(c->ev[0], s));
     if (metric == ZH_COSINE) HIPCHK(zh_launch_qnorm(dQ, (uint32_t)B, d, c->wQQ.as<float>(), s));
-    static const bool no_blocks = getenv("ZH_WALK_NO_BLOCKS") != nullptr;  // A/B: the pointer walk for all-dense signs too
-    const bool blocked = c->P_dense >= ix->n_planes && ix->n_planes && ix->blocks_valid && !no_blocks;
-    static const bool eager_fix = getenv("ZH_EAGER_FIXUPS") != nullptr;  // A/B: every uncertain sign recomputed before the walk
-    c->lazy_fix = c->score_hash && blocked && !eager_fix && ((B + 3) & ~(size_t)3) != 4 && d % 4 == 0;  // (plane_above_wave's shape)
+    const bool blocked = c->P_dense >= ix->n_planes && ix->n_planes && ix->blocks_valid;
+    c->lazy_fix = c->score_hash && blocked && ((B + 3) & ~(size_t)3) != 4 && d % 4 == 0;  // (plane_above_wave's shape)
     if (c->lazy_fix && (rc = c->wUnc.ensure(std::max<size_t>((size_t)B * c->wpq * 4, 4)))) return rc;
     if (c->score_hash) {
         if ((rc = launch_score_hash(c, dQ, B, c->lazy_fix, s))) return rc;
@@ -2372,8 +2175,7 @@ static int ctx_finish(zh_search_ctx *c, uint64_t *const *outIds, uint64_t *const
     if ((rc = c->wVisits.ensure(std::max<uint64_t>(tot.visits, 1) * sizeof(ZhVisit)))) return rc;
     if ((rc = c->wGroups.ensure(std::max<uint64_t>(tot.groups, 1) * sizeof(ZhGroup)))) return rc;
     if ((rc = c->wGroupRowOff.ensure(std::max<uint64_t>(tot.groups, 1) * 8))) return rc;
-    static const bool no_wave_table = getenv("ZH_NO_WAVE_TABLE") != nullptr;  // A/B: per-lane binary search over all groups
-    if (!no_wave_table && (rc = c->wWaveGroup.ensure((tot.group_rows / 64 + 2) * 4))) return rc;
+    if ((rc = c->wWaveGroup.ensure((tot.group_rows / 64 + 2) * 4))) return rc;
     if ((rc = c->wKeys.ensure(std::max<uint64_t>(tot.rows, 1) * 8))) return rc;
     if ((rc = c->wCandKeys.ensure(std::max<uint64_t>(tot.takes, 1) * 8))) return rc;
     if ((rc = c->wCandIds.ensure(std::max<uint64_t>(tot.takes, 1) * 4))) return rc;
@@ -2416,11 +2218,11 @@ static int ctx_finish(zh_search_ctx *c, uint64_t *const *outIds, uint64_t *const
         HIPCHK(zh_launch_node_visits(c->wLeafCount.as<uint32_t>(), c->wGroupBase.as<uint32_t>(), c->wGroups.as<ZhGroup>(), ix->n_nodes,
                                      c->wVisitBits.as<uint32_t>(), c->wNodeVisit.as<uint4>(), s));
     }
-    if (!no_wave_table && !c->scan)
+    if (!c->scan)
         HIPCHK(zh_launch_wave_groups(c->wGroups.as<ZhGroup>(), c->wGroupRowOff.as<uint64_t>(), tot.groups, c->wWaveGroup.as<uint32_t>(), s));
     c->approx = c->scan && use_approx(ix, tot, B, k, c->metric);
     c->approx_leaf = false; c->approx_bytes = false;
-    if (!c->scan && !no_wave_table && use_approx_leaf(ix, tot, B, k, c->metric)) {
+    if (!c->scan && use_approx_leaf(ix, tot, B, k, c->metric)) {
         bool ok = false;
         // rows of bytes (integers 0 .. 255: SIFT descriptors) are copied as bytes -- half the sweep's bytes, no rounding -- for the lean kernels;
         // ZH_S128H_BYTES=0 (read per batch: tests) keeps the copy of halves
@@ -2514,8 +2316,8 @@ static int ctx_finish(zh_search_ctx *c, uint64_t *const *outIds, uint64_t *const
                                     c->metric, c->mode, c->wKeys.as<uint64_t>(), nullptr, hs));
     else
         HIPCHK(zh_launch_sweep(ix->X.as<float>(), d, c->dQ, c->wQQ.as<float>(), c->wGroups.as<ZhGroup>(),
-                               c->wGroupRowOff.as<uint64_t>(), tot.groups, no_wave_table ? nullptr : c->wWaveGroup.as<uint32_t>(), f.leaf_ids,
-                               tot.group_rows, c->metric, c->mode, c->wKeys.as<uint64_t>(), f.group, hs));
+                               c->wGroupRowOff.as<uint64_t>(), tot.groups, c->wWaveGroup.as<uint32_t>(), f.leaf_ids,
+                               tot.group_rows, c->metric, c->mode, c->wKeys.as<uint64_t>(), hs));
     HIPCHK(hipEventRecord(c->ev_sw1, hs));
     if (hs != s) HIPCHK(hipStreamWaitEvent(s, c->ev_sw1, 0));
     HIPCHK(hipEventRecord(c->ev[3], s));
@@ -2541,7 +2343,7 @@ static int ctx_finish(zh_search_ctx *c, uint64_t *const *outIds, uint64_t *const
         run_if = ap.ctl + 1;
         if (c->approx_leaf)
             HIPCHK(zh_launch_sweep(ix->X.as<float>(), d, c->dQ, c->wQQ.as<float>(), c->wGroups.as<ZhGroup>(), c->wGroupRowOff.as<uint64_t>(), tot.groups,
-                                   c->wWaveGroup.as<uint32_t>(), f.leaf_ids, tot.group_rows, c->metric, c->mode, c->wKeys.as<uint64_t>(), f.group, s, run_if));
+                                   c->wWaveGroup.as<uint32_t>(), f.leaf_ids, tot.group_rows, c->metric, c->mode, c->wKeys.as<uint64_t>(), s, run_if));
         else
             HIPCHK(zh_launch_scan_sweep(ix->X.as<float>(), d, ix->n_rows, c->dQ, c->wQQ.as<float>(), ix->row_leaf.as<uint2>(), T,
                                         c->wVisitBits.as<uint32_t>(), c->wNodeVisit.as<uint4>(), c->wGroups.as<ZhGroup>(), f.group,
@@ -2787,8 +2589,7 @@ extern "C" int zh_search_wait(zh_search_ctx *c) {
 
 // ---- test / debug access (include/zebra_hip.h, "test / debug access") ----
 extern "C" int zh_trim_device_memory(void) {
-    pool_trim();
-    return ZH_OK;
+    return ZH_OK;  // (the library caches no device memory: every buffer goes back to the driver when it is freed)
 }
 
 extern "C" int zh_debug_keep_raw(zh_index *ix, int on) {

@@ -265,11 +265,7 @@ void scan_approx_kernel(const float *__restrict__ X, const uint4 *__restrict__ Q
                                                            uint32_t GRP, uint64_t row_begin, uint64_t row_end, float Kc,
                                                            uint64_t *__restrict__ iv) {
     constexpr int LG = 64 / G, NH = D * G / 512, NR = 2 * NH;  // lanes per group; dwordx4 of halves per pair; float4 registers per row
-#ifdef ZH_APX_RB
-    constexpr int RB = ZH_APX_RB;
-#else
     constexpr int RB = NR <= 6 ? 4 : 2;                         // rows per HBM round trip
-#endif
     static_assert(D * G % 512 == 0 && NH >= 1, "a lane's share of a query is whole 16-byte loads");
     __shared__ uint4 pair_list[4][ZH_APX_CAP];  // {row of the wave's RW, query, interval slot lo, hi}
     __shared__ uint32_t row_start[4][20];
@@ -302,9 +298,6 @@ void scan_approx_kernel(const float *__restrict__ X, const uint4 *__restrict__ Q
         nst = 0;
     };
     auto load_q = [&](uint32_t b, uint4 *hq) {
-#ifdef ZH_APX_EXP_Q_L1   // timing experiment (results invalid): eight queries only -> the query loads hit the vector L1
-        b &= 7u;
-#endif
         const uint4 *qp = Qh + (size_t)b * (D / 8) + l;
 #pragma unroll
         for (int i = 0; i < NH; i++) hq[i] = qp[i * LG];
@@ -327,11 +320,7 @@ void scan_approx_kernel(const float *__restrict__ X, const uint4 *__restrict__ Q
                 v[2 * j + 1] = make_float4(__uint_as_float(sx[1]), __uint_as_float(sy[1]), __uint_as_float(sz[1]), __uint_as_float(sw[1]));
             }
         } else {
-#ifdef ZH_APX_EXP_ROWS_L2   // timing experiment (results invalid): every row from a 3-MB region -> L2 hits instead of HBM reads
-            const float4 *r4 = X4 + (size_t)(row & 1023) * (D / 4) + l;
-#else
             const float4 *r4 = X4 + (size_t)row * (D / 4) + l;
-#endif
 #pragma unroll
             for (int j = 0; j < NR; j++) v[j] = ld16<true>(r4 + LG * j);
         }
@@ -414,7 +403,6 @@ void scan_approx_kernel(const float *__restrict__ X, const uint4 *__restrict__ Q
                 if (rid[r] == 0xFFFFFFFFu) continue;
                 const uint32_t pb = (uint32_t)__builtin_amdgcn_readfirstlane((int)rstart[rid[r] + 1]);
                 const float a2 = row_sumsq(v[r]);
-#ifndef ZH_APX_NO_PINGPONG
                 // two steps per trip, the two query buffers swapping roles: no register copies except after a row's odd last step
                 uint4 recn, hqn[NH];
                 auto one = [&](const uint4 &ru, const uint4 *hu, uint4 &rp, uint4 *hp) {
@@ -434,20 +422,6 @@ void scan_approx_kernel(const float *__restrict__ X, const uint4 *__restrict__ Q
                         for (int i = 0; i < NH; i++) hq[i] = hqn[i];
                     }
                 }
-#else
-                while (p < pb) {
-                    const uint32_t pn = p + G < pb ? p + G : pb;
-                    const uint4 recn = list[pn + g < P ? pn + g : P - 1];
-                    uint4 hqn[NH];
-                    load_q(recn.y, hqn);
-                    const float s = dot_h(v[r], hq);
-                    stash(s, a2, rec.y, ((uint64_t)rec.w << 32) | rec.z, p + g < pb);
-                    rec = recn;
-#pragma unroll
-                    for (int i = 0; i < NH; i++) hq[i] = hqn[i];
-                    p = pn;
-                }
-#endif
             }
         }
     } else {
@@ -486,7 +460,7 @@ void scan_approx_kernel(const float *__restrict__ X, const uint4 *__restrict__ Q
 }
 
 // ---- the table scan on the matrix cores (round 4, second half; reworked in round 5) -- THE DEFAULT half-width scan with up to 16 trees at
-// d = 256 / 384 / 512 / 768 / 1024 (zh_api.hip mfma_wanted; zh_set_sweep_mode(5) / ZH_NO_MFMA keep the VALU kernel above, which needs no copy of
+// d = 256 / 384 / 512 / 768 / 1024 (zh_api.hip mfma_wanted; zh_set_sweep_mode(5) keeps the VALU kernel above, which needs no copy of
 // the rows) ----
 // The VALU scan spends 36 vector instructions per pair (profiles/r04_pmc_scan_mix.txt): a 32-lane fma column, its reduce, its record and its
 // stash.  Here a wave's 16 stored rows are the A operand of v_mfma_f32_16x16x32_f16, loaded from the index's fp16 copy of the rows
@@ -587,9 +561,6 @@ hipError_t zh_launch_permute_row_leaf(const uint2 *dRowLeaf, const uint32_t *dPe
     return hipGetLastError();
 }
 
-#ifndef ZH_MFMA_EXP
-#define ZH_MFMA_EXP 0   // timing experiments of scan_mfma_kernel (diagnostic builds, results invalid): 1 no MFMA, 2 queries from L1, 3 no LDS staging writes, 4 no result stores, 5 no tile loop, 6 result stores into an L2-resident region
-#endif
 #ifndef ZH_MFMA_CL
 #define ZH_MFMA_CL 0   // A/B: 128-byte query lines per column and chunk (0: by dimension)
 #endif
@@ -749,35 +720,21 @@ void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ X
     const uint32_t rd1 = (c16 >> 3) * 64u + (c16 & 7u) * 8u + (((4u + h) ^ (c16 >> 1)) & 7u);
     auto issue = [&](uint32_t bA, uint32_t bB, int chunk, u32x4v *dst) {
         if (!ZH_GUARD(bA < nq && bB < nq, 1u)) { bA = 0; bB = 0; }
-#if ZH_MFMA_EXP == 2   // timing experiment (results invalid): eight queries only -> the query lines hit the vector L1
-        bA &= 7u; bB &= 7u;
-#endif
         const u32x4v *qa = Qv + (size_t)bA * (D / 8) + (size_t)(chunk * CL * 8) + (pc ^ swA);
         const u32x4v *qb = Qv + (size_t)bB * (D / 8) + (size_t)(chunk * CL * 8) + (pc ^ swB);
 #pragma unroll
         for (int i = 0; i < CL; i++) { dst[2 * i] = qa[8 * i]; dst[2 * i + 1] = qb[8 * i]; }
     };
     auto to_lds = [&](const u32x4v *src) {
-#if ZH_MFMA_EXP == 3   // timing experiment (results invalid): the staged lines are not written to LDS (one word keeps the loads alive)
-        u32x4v f = src[0];
-#pragma unroll
-        for (int i = 1; i < 2 * CL; i++) f ^= src[i];
-        if (f[0] == 0x12345678u) stg[lane] = f;
-#else
 #pragma unroll
         for (int i = 0; i < 2 * CL; i++) stg[64 * i + lane] = src[i];
-#endif
     };
     auto mfma_chunk = [&](int chunk, f32x4v *acc) {
 #pragma unroll
         for (int i = 0; i < 2 * CL; i++) {  // step 2 CL chunk + i: line i / 2 of the chunk
             const u32x4v v = stg[128 * (i / 2) + ((i & 1) ? rd1 : rd0)];
             const int st = chunk * 2 * CL + i;
-#if ZH_MFMA_EXP == 1   // timing experiment (results invalid): no MFMA
-            acc[st & 3] += __builtin_bit_cast(f32x4v, v) + __builtin_bit_cast(f32x4v, __builtin_shufflevector(A[st], A[st], 0, 1, 2, 3, 4, 5, 6, 7));
-#else
             acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, v), acc[st & 3], 0, 0, 0);
-#endif
         }
     };
     auto emit = [&](const f32x4v *acc, uint32_t rl, uint64_t slot, bool valid) {  // column c16 wants row rl: lane (c16, rl >> 2), register rl & 3
@@ -878,12 +835,7 @@ void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ X
         __builtin_amdgcn_wave_barrier();
         // the wave's distinct queries sixteen at a time; the next chunk of query lines is requested before the current one is multiplied,
         // across tile boundaries
-#if ZH_MFMA_EXP == 5   // timing experiment (results invalid): no tile loop -- phase 1, pair list, column pass and the rows' tile loads only
-        const uint32_t nt = (nd + 15) / 16 > 4096u ? 1u : 0u;
-        if (lane == 0 && __builtin_bit_cast(u32x4v, A[NS - 1])[0] == 0x12345678u) iv[0] = 0;
-#else
         const uint32_t nt = (nd + 15) / 16;
-#endif
         SP(const uint64_t sp3 = clock64();)
         // what the sharing is worth (zh_stats_t::approx_columns / approx_column_pairs): every 64th wave reports -- same-address atomics from all
         // 200k waves of a launch serialise in one L2 channel (measured: 3.6 -> 5.5 ms per launch)
@@ -919,15 +871,8 @@ void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ X
                 const uint32_t rl = (uint32_t)(rec >> 60), col = (uint32_t)(rec >> 36) & 15u;
                 const float sv = reinterpret_cast<const float *>(al)[col * 16 + rl];
                 const float2 rm = rmeta[rl];
-#if ZH_MFMA_EXP == 4   // timing experiment (results invalid): one pair in 64 stores its result
-                if ((rec & 63u) == 0u)
-#endif
-#if ZH_MFMA_EXP == 6   // timing experiment (results invalid): every result store lands in 2 MiB that stay in the L2s (the stores' issue and acknowledgement without their HBM side)
-                __builtin_nontemporal_store(((uint64_t)__float_as_uint(rm.x) << 32) | __float_as_uint(sv * rm.y), iv + ((wave & 4095u) * 64u + lane));
-#else
                 if (ZH_GUARD((rec & 0xFFFFFFFFFull) < iv_cap, 2u))
                     __builtin_nontemporal_store(((uint64_t)__float_as_uint(rm.x) << 32) | __float_as_uint(sv * rm.y), iv + (rec & 0xFFFFFFFFFull));
-#endif
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -1555,17 +1500,10 @@ __device__ __forceinline__ uint32_t row_newbcast(uint32_t v) {  // every lane: t
 // the four row-load instructions of tile T of a chunk whose ids the lanes hold as lane (h, c) = flat row 4 c + h: instruction i = rows 4 (4 T + i) + h
 template <int T>
 __device__ __forceinline__ void issue_lean_tile(const u32x4v *__restrict__ Xh, uint32_t ids, uint32_t c16, u32x4v (&R)[4]) {
-#if defined(ZH_S128L_EXP) && ZH_S128L_EXP == 3  // plain (temporal) row loads
-    R[0] = Xh[(size_t)row_newbcast<4 * T + 0>(ids) * 16 + c16];
-    R[1] = Xh[(size_t)row_newbcast<4 * T + 1>(ids) * 16 + c16];
-    R[2] = Xh[(size_t)row_newbcast<4 * T + 2>(ids) * 16 + c16];
-    R[3] = Xh[(size_t)row_newbcast<4 * T + 3>(ids) * 16 + c16];
-#else
     R[0] = __builtin_nontemporal_load(Xh + (size_t)row_newbcast<4 * T + 0>(ids) * 16 + c16);
     R[1] = __builtin_nontemporal_load(Xh + (size_t)row_newbcast<4 * T + 1>(ids) * 16 + c16);
     R[2] = __builtin_nontemporal_load(Xh + (size_t)row_newbcast<4 * T + 2>(ids) * 16 + c16);
     R[3] = __builtin_nontemporal_load(Xh + (size_t)row_newbcast<4 * T + 3>(ids) * 16 + c16);
-#endif
 }
 // The chunk of flat rows r0 .. r0 + cnt - 1 (r0 a multiple of 64, cnt <= 64: the batch's last chunk is short) as at most TWO SEGMENTS, each inside one
 // group: cntA rows of group g from its row within0 and -- where a group ends inside the chunk -- cntB rows from the first row of group g + 1.
@@ -1587,9 +1525,6 @@ __device__ __forceinline__ bool chunk_segments(uint64_t r0, uint32_t cnt, const 
     cntA = (uint32_t)(nxt - r0); cntB = (uint32_t)(end - nxt);
     return true;
 }
-#ifndef ZH_S128L_EXP
-#define ZH_S128L_EXP 0     // timing experiments on the lean kernel (profiles/r06_sweep128h_experiments.txt); 0 = the shipped form
-#endif
 #ifndef ZH_S128L_WAVES
 #define ZH_S128L_WAVES 5   // waves per SIMD the register allocation is held to (A/B)
 #endif
@@ -1713,17 +1648,7 @@ void sweep128h_lean_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restri
             for (int j = 0; j < 4; j++)
                 if ((uint32_t)j < gsize && lane < cnt) {
                     const uint64_t v = ((uint64_t)a2b << 32) | __float_as_uint(res[j] * inv);
-#if ZH_S128L_EXP == 1    // timing experiment (results invalid): no result stores
-                    if (res_a2 == 123456.789f) dst[gr->key_off[j]] = v;
-#elif ZH_S128L_EXP == 2  // plain (write-back) stores
-                    dst[gr->key_off[j]] = v;
-#elif ZH_S128L_EXP == 7  // timing experiment (results invalid): every run starts on a 128-byte line
-                    __builtin_nontemporal_store(v, iv + ((gr->key_off[j] + within0) & ~15ull) + lane);
-#elif ZH_S128L_EXP == 8  // timing experiment (results invalid): the runs land in 512 KiB that stay in the L2s
-                    __builtin_nontemporal_store(v, iv + (wave & 1023u) * 64 + lane);
-#else
                     __builtin_nontemporal_store(v, dst + gr->key_off[j]);
-#endif
                 }
         } else {
             // ---- the fused sweep: lane l holds flat row l of the chunk against every slot.  Per slot: the interval (select_tau_kernel's arithmetic), the
@@ -1777,9 +1702,6 @@ __device__ __forceinline__ void issue_byte_tile(const u32x4v *__restrict__ Xb, u
 }
 #ifndef ZH_S128B_WAVES
 #define ZH_S128B_WAVES 4   // waves per SIMD the byte kernel's register allocation is held to (A/B)
-#endif
-#ifndef ZH_S128B_EXP
-#define ZH_S128B_EXP 0     // timing experiments on the byte kernel (profiles/r06_sweep128b_experiments.txt), results INVALID: 1 no conversion, 2 no epilogue, 3 no Gram; valid: 4 no pre-test
 #endif
 template <int CH, int FUSE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ZH_S128B_WAVES, ZH_S128B_WAVES)))
@@ -1876,20 +1798,12 @@ void sweep128b_lean_kernel(const u32x4v *__restrict__ Xb, const u32x4v *__restri
 #pragma unroll
             for (int m = 0; m < 2; m++) {
                 const u32x4v v0 = m ? v10 : v00, v1 = m ? v11 : v01;
-#if ZH_S128B_EXP == 1
-                const f16x8 Bf[4] = {__builtin_bit_cast(f16x8, v0), __builtin_bit_cast(f16x8, v1), __builtin_bit_cast(f16x8, v0), __builtin_bit_cast(f16x8, v1)};
-#else
                 const f16x8 Bf[4] = {bytes8_to_f16(v0[0], v0[1]), bytes8_to_f16(v0[2], v0[3]), bytes8_to_f16(v1[0], v1[1]), bytes8_to_f16(v1[2], v1[3])};
-#endif
                 f32x4v dsum = {0.f, 0.f, 0.f, 0.f}, gram = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int st = 0; st < 4; st++) {
                     dsum = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[st], Bf[st], dsum, 0, 0, 0);
-#if ZH_S128B_EXP != 3
                     gram = __builtin_amdgcn_mfma_f32_16x16x32_f16(Bf[st], Bf[st], gram, 0, 0, 0);
-#else
-                    gram = dsum;
-#endif
                 }
                 const float dg_lo = c_odd ? gram[1] : gram[0], dg_hi = c_odd ? gram[3] : gram[2], dg = c_up ? dg_hi : dg_lo;
                 const float a2 = __int_as_float(__builtin_amdgcn_ds_bpermute((int)diag_src, __float_as_int(dg)));
@@ -1912,9 +1826,9 @@ void sweep128b_lean_kernel(const u32x4v *__restrict__ Xb, const u32x4v *__restri
             const uint32_t take4 = gr->take4;
 #pragma unroll
             for (int j = 0; j < 4; j++)
-                if ((uint32_t)j < gsize && (ZH_S128B_EXP != 2 || res[j] == 123456.789f)) {
+                if ((uint32_t)j < gsize) {
                     const uint32_t take = (take4 >> (8 * j)) & 255u;
-                    if constexpr (FUSE == 0 && ZH_S128B_EXP != 4) {
+                    if constexpr (FUSE == 0) {
                         if (!(take < glen && take < k_top)) {  // (the exact path's visits keep every interval)
                             const uint32_t t_w = take < glen ? (uint32_t)__builtin_amdgcn_readlane((int)topv[j], (int)(take - 1)) : 0xFFFFFFFFu;
                             const uint32_t t_q = (uint32_t)__builtin_amdgcn_readfirstlane((int)tau_pre[j]);
@@ -2158,13 +2072,11 @@ static void launch_sweep128h_lean(const void *dXh, const void *dQh, float inv, c
             hipLaunchKernelGGL((sweep128h_lean_kernel<CHL, FUSE>), dim3((uint32_t)((wl + 3) / 4)), dim3(256), 0, s, (const u32x4v *)dXh,
                                (const u32x4v *)dQh, inv, dGroups, dGroupRowOff, n_groups, dWaveGroup, dLeafIds, r, r_end, dIv, ap, k_top, Kc);
     }
-#if ZH_S128L_EXP != 5    // (5: timing experiment without the boundary kernel, results invalid)
     // the chunks of three or more groups, of the WHOLE batch in one launch (a launch of its own per 25M rows was 0.04-0.06 ms each): a wave
     // looks at 64 chunks.  Chunk boundaries are absolute (every launch above starts on a multiple of 256 rows), so both kernels see the same chunks
     const uint64_t bw = ((R_grouped + 63) / 64 + 63) / 64, bb = (bw + 3) / 4;
     hipLaunchKernelGGL((sweep128h_boundary_kernel<FUSE, BYTES>), dim3((uint32_t)bb), dim3(256), 0, s, (const u32x4v *)dXh, (const u32x4v *)dQh, inv, dGroups,
                        dGroupRowOff, n_groups, dWaveGroup, dLeafIds, (uint64_t)0, R_grouped, dIv, ap, k_top, Kc);
-#endif
 }
 // fuse: null = the raw pairs go to dIv for select_tau_kernel / select_emit_kernel; else the FUSED sweep (intervals, bounds and the queries' lists
 // inside the sweep; exact_register_kernel instead of the select pass): `fuse_kinda` = approx_interval's kind, k_top <= 64

@@ -257,8 +257,7 @@ hipError_t zh_launch_classify(const float *dX, uint32_t d, const uint32_t *dPerm
                               const ZhBuildChunk *dChunks, uint32_t n_chunks, const float *dPlanes,
                               const float *dConsts, uint8_t *dFlags, uint32_t *dChunkAbove, hipStream_t s) {
     if (!n_chunks) return hipSuccess;
-    static const int variant = [] { const char *e = getenv("ZH_CLASSIFY_VARIANT"); return e ? atoi(e) : 0; }();
-    if ((d & 3u) == 0 && d >= 64 && variant != 1) {
+    if ((d & 3u) == 0 && d >= 64) {
         ZH_SLICED(classify_lds_kernel, n_chunks, 256, 0, s, dX, d, dPerm, dNodes, dChunks, dPlanes, dConsts, dFlags, dChunkAbove)
         return hipGetLastError();
     }

@@ -30,8 +30,8 @@ struct ZhVisit {
     uint32_t pad;
 };
 
-// Visits of one leaf by different queries of the batch (or window) are swept together, `group` at a time (2 or 4, chosen
-// per index by zh_group_size): the leaf's rows cross HBM once per group instead of once per query.
+// Visits of one leaf by different queries of the batch (or window) are swept together, `group` at a time (zh_group_size):
+// the leaf's rows cross HBM once per group instead of once per query.
 #define ZH_GROUP_MAX 4
 struct ZhGroup {
     uint32_t leaf_off, len, gsize;
@@ -39,7 +39,7 @@ struct ZhGroup {
     uint32_t b[ZH_GROUP_MAX];
     uint64_t key_off[ZH_GROUP_MAX];  // the member visits' row_off (slice of the key scratch)
 };
-// 4 queries per group (ZH_GROUP=2|4 forces; A/B in profiles/).
+// 4 queries per group (2 measured no better, profiles/r02_ab_sweep128.txt); the sweep kernels take groups of up to 4.
 uint32_t zh_group_size(uint32_t dim);
 
 // per (query, tree) pair counts produced by the walk's first pass, then their exclusive scans
@@ -135,7 +135,6 @@ __device__ __forceinline__ bool zh_plane_above(const float *__restrict__ w, floa
 }
 #endif
 
-#define ZH_SORT_N 4096        // entries of the LDS sort buffer of the select / final kernels
 #define ZH_INLINE_VISITS 32    // visits a pair may record in the walk's first pass
 
 // ---- launchers (zh_search.hip) ---------------------------------------------------------------
@@ -178,7 +177,7 @@ hipError_t zh_launch_walk_emit(ZhForestDev f, const float *dQ, uint32_t B, uint3
 hipError_t zh_launch_sweep(const float *dX, uint32_t d, const float *dQ, const float *dQQ, const ZhGroup *dGroups,
                            const uint64_t *dGroupRowOff, uint64_t n_groups, const uint32_t *dWaveGroup,
                            const uint32_t *dLeafIds, uint64_t R_grouped, int metric, int mode, uint64_t *dKeys,
-                           uint32_t group, hipStream_t s, const uint32_t *dRunIf = nullptr);
+                           hipStream_t s, const uint32_t *dRunIf = nullptr);
 bool zh_sweep_has_predicate(uint32_t d, int metric);
 // waveGroup[w] = group of flat row 64 w, for every wave start of [0, R_grouped)
 hipError_t zh_launch_wave_groups(const ZhGroup *dGroups, const uint64_t *dGroupRowOff, uint64_t n_groups, uint32_t *dWaveGroup,

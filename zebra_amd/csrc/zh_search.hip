@@ -192,8 +192,7 @@ hipError_t zh_launch_hash_dense(const float *dQ, uint32_t B, const float *dPlane
                                 uint32_t P, uint32_t d, uint32_t *dBits, uint32_t words_per_q, float *dDots,
                                 hipStream_t s) {
     if (B == 0 || P == 0) return hipSuccess;
-    static const int variant = [] { const char *e = getenv("ZH_HASH_VARIANT"); return e ? atoi(e) : 0; }();  // 1: small tiles only
-    if ((d & 3u) == 0 && B >= 128 && (uint64_t)P * B >= (1ull << 22) && variant != 1) {
+    if ((d & 3u) == 0 && B >= 128 && (uint64_t)P * B >= (1ull << 22)) {
         dim3 grid((P + 127) / 128, (B + 127) / 128);
         if (dDots)
             hipLaunchKernelGGL(hash_dense_big_kernel<true>, grid, dim3(256), 0, s, dQ, B, dPlanes, dConsts, P, d, dBits,
@@ -1004,7 +1003,6 @@ __global__ __launch_bounds__(64) void walk_blocked_inner_kernel(ZhForestDev f, Z
         // arithmetic, for every flagged node of the block the walk enters -- not when the walk steps on it: the DFS below then has no flag to test
         // (its loop is bound by the SIMD's scalar issue slot: every scalar instruction per step counts; ~4x the exact chains of the lazy scheme,
         // < 1 % of a pair's cycles)
-#ifndef ZH_PROBE_NO_EAGER_FLAGS  // (timing probe only: results are wrong without it)
         WP(p_flags += (uint32_t)__builtin_popcountll(__ballot(ub != 0));)
         for (unsigned long long um = __ballot(ub != 0); um; um &= um - 1) {
             const int j = __builtin_ctzll(um);
@@ -1012,7 +1010,6 @@ __global__ __launch_bounds__(64) void walk_blocked_inner_kernel(ZhForestDev f, Z
             const bool ab = plane_above_wave(f.planes + (size_t)p_ * d, f.consts[p_], Q + (size_t)b * d, d, lane);
             if ((int)lane == j) sgn = ab ? 1 : 0;
         }
-#endif
         // one word per inner node: main child's code | backup child's code << 8 (lsh.rs:335-338: above -> right is main)
         uint32_t pk;
         {
@@ -1393,11 +1390,9 @@ __device__ __forceinline__ void row_sums_group(const float4 *v, const float4 (*q
     }
 }
 
-// D > 0: compile-time dimension (multiple of 4); D == 0: runtime d, any value (slow path)
-// QLDS (A/B only, ZH_SWEEP_QLDS=1): the group's queries staged in LDS (one member's float4s in registers at a time) instead of
-// all G members in registers -- the north_star's "LDS-staged query tiles" taken literally; measured equal (62.2 k against 61.7 k QPS at cfg3:
-// the kernel is HBM-bound either way, profiles/r02_ab_query_staging.txt), registers kept.
-template <int D, int KIND, int G, int SWEEP_RG = 4, bool NT = false, bool QLDS = false>
+// D > 0: compile-time dimension (multiple of 4); D == 0: runtime d, any value (slow path).  Rows are streamed once per
+// batch: non-temporal loads (+1.3 % measured, profiles/).  Rows in flight (2/4/8) made no measurable difference at d = 768: 4.
+template <int D, int KIND, int G, int SWEEP_RG = 4>
 __global__ __launch_bounds__(256) void sweep_kernel(const float *__restrict__ X, uint32_t d,
                                                      const float *__restrict__ Q, const float *__restrict__ QQ,
                                                      const ZhGroup *__restrict__ groups,
@@ -1420,9 +1415,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const float *__restrict__ X,
     if (D > 0) {
         constexpr int DD = (D > 0 ? D : 4);
         constexpr int NV = RowVec<DD>::NV;
-        float4 q[QLDS ? 1 : G][NV];
-        __shared__ float4 qs[QLDS ? 4 : 1][QLDS ? G : 1][QLDS ? NV : 1][QLDS ? 64 : 1];
-        const uint32_t wq = (threadIdx.x >> 6) & 3;
+        float4 q[G][NV];
         uint32_t cur_g = 0xFFFFFFFFu, gsize = 0;
         for (uint32_t i0 = 0; i0 < cnt; i0 += SWEEP_RG) {
             float4 v[SWEEP_RG][NV];
@@ -1430,7 +1423,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const float *__restrict__ X,
             for (int r = 0; r < SWEEP_RG; r++) {
                 uint32_t i = i0 + r < cnt ? i0 + r : cnt - 1;
                 uint32_t id = __builtin_amdgcn_readlane(my_id, i);
-                load_row<DD, NT>(X + (size_t)id * DD, lane, v[r]);
+                load_row<DD, true>(X + (size_t)id * DD, lane, v[r]);
             }
 #pragma unroll
             for (int r = 0; r < SWEEP_RG; r++) {
@@ -1442,31 +1435,12 @@ __global__ __launch_bounds__(256) void sweep_kernel(const float *__restrict__ X,
                         gsize = groups[g].gsize;
 #pragma unroll
                         for (int m = 0; m < G; m++)
-                            if ((uint32_t)m < gsize) {
-                                if constexpr (QLDS) {
-                                    load_row<DD>(Q + (size_t)groups[g].b[m] * DD, lane, q[0]);
-#pragma unroll
-                                    for (int j = 0; j < NV; j++) qs[wq][m][j][lane] = q[0][j];
-                                } else
-                                    load_row<DD>(Q + (size_t)groups[g].b[m] * DD, lane, q[m]);
-                            }
+                            if ((uint32_t)m < gsize) load_row<DD>(Q + (size_t)groups[g].b[m] * DD, lane, q[m]);
                     }
                     float s0[G], s1[G];
 #pragma unroll
                     for (int m = 0; m < G; m++) { s0[m] = 0.f; s1[m] = 0.f; }
-                    if constexpr (QLDS) {
-#pragma unroll
-                        for (int m = 0; m < G; m++)
-                            if ((uint32_t)m < gsize) {
-#pragma unroll
-                                for (int j = 0; j < NV; j++) q[0][j] = qs[wq][m][j][lane];
-                                float t0[1] = {0.f}, t1[1] = {0.f};
-                                row_sums_group<DD, KIND, 1>(v[r], q, 1, lane, param, t0, t1);
-                                s0[m] = t0[0]; s1[m] = t1[0];
-                                if (KIND == K_COS) s1[0] = t1[0];
-                            }
-                    } else
-                        row_sums_group<DD, KIND, G>(v[r], q, gsize, lane, param, s0, s1);
+                    row_sums_group<DD, KIND, G>(v[r], q, gsize, lane, param, s0, s1);
                     if (lane == i) {
 #pragma unroll
                         for (int m = 0; m < G; m++) { mine0[m] = s0[m]; mine1[m] = KIND == K_COS ? s1[0] : s1[m]; }
@@ -1518,7 +1492,7 @@ __device__ __forceinline__ float half_sum_canonical(float s) {
 // streams 32 KB (profiles/micro/gather512.hip: the bare gather of random 512-byte rows runs at 6.55 TB/s, this kernel with
 // one chunk per wave at 5.3-5.5).  Chunks after the first usually continue in the group the previous chunk ended in (leaves
 // hold thousands of rows): their ids are then ONE independent load, issued before the current chunk is streamed.
-template <int KIND, int G, int RG, bool NT, int CH>
+template <int KIND, int G, int RG, int CH>
 __global__ __launch_bounds__(256) void sweep128_kernel(const float *__restrict__ X, const float *__restrict__ Q,
                                                         const float *__restrict__ QQ, const ZhGroup *__restrict__ groups,
                                                         const uint64_t *__restrict__ groupRowOff, uint64_t n_groups,
@@ -1572,7 +1546,7 @@ __global__ __launch_bounds__(256) void sweep128_kernel(const float *__restrict__
                 const uint32_t j = j0 + r < npair ? j0 + r : npair - 1;
                 const uint32_t jh = j + 32 < cnt ? j + 32 : cnt - 1;
                 const uint32_t idl = __builtin_amdgcn_readlane(my_id, j), idh = __builtin_amdgcn_readlane(my_id, jh);
-                v[r] = ld16<NT>(X4 + (size_t)(up ? idh : idl) * 32 + hl);
+                v[r] = ld16<true>(X4 + (size_t)(up ? idh : idl) * 32 + hl);
             }
 #pragma unroll
             for (int r = 0; r < RG; r++) {
@@ -1637,7 +1611,7 @@ __global__ __launch_bounds__(256) void sweep128_kernel(const float *__restrict__
 }
 
 uint64_t zh_sweep_rows_per_launch(uint32_t d) {
-    static const uint64_t launch_bytes = [] { const char *e = getenv("ZH_SWEEP_LAUNCH_MB"); return (uint64_t)(e ? atoi(e) : 12288) << 20; }();
+    const uint64_t launch_bytes = (uint64_t)12288 << 20;
     uint64_t rows = launch_bytes / ((uint64_t)4 * (d ? d : 1));
     rows = (rows + 255) / 256 * 256;
     return rows < 65536 ? 65536 : rows;
@@ -1647,18 +1621,15 @@ struct SweepArgs {
     const float *dX; uint32_t d; const float *dQ, *dQQ;
     const ZhGroup *dGroups; const uint64_t *dGroupRowOff; uint64_t n_groups;
     const uint32_t *dWaveGroup;  // wave-start table (zh_launch_wave_groups) or nullptr: full binary search per lane
-    const uint32_t *dLeafIds; uint64_t R_grouped; int metric, param; uint64_t *dKeys; uint32_t group; hipStream_t s;
+    const uint32_t *dLeafIds; uint64_t R_grouped; int metric, param; uint64_t *dKeys; hipStream_t s;
     const uint32_t *dRunIf;  // a predicate on the device (d = 128 half-wave kernel only): the launch returns at once when it is zero
 };
 
-template <int D, int KIND, int G>
-static hipError_t launch_sweep_g(const SweepArgs &a) {
-    // rows are streamed once per batch: non-temporal loads (+1.3 % measured, profiles/); ZH_SWEEP_VARIANT=1
-    // switches them off for A/B runs.  Rows in flight (2/4/8) made no measurable difference at d = 768: 4.
-    static const int variant = [] { const char *e = getenv("ZH_SWEEP_VARIANT"); return e ? atoi(e) : 0; }();
-    // d = 128: the half-wave kernel, RG load instructions = 2 RG rows in flight (ZH_SWEEP128=0: the generic kernel; A/B)
-    static const int v128 = [] { const char *e = getenv("ZH_SWEEP128"); return e ? atoi(e) : 8; }();
-    // One batch is issued as several launches of ~ZH_SWEEP_LAUNCH_BYTES each (about 2 ms of HBM time): a single
+// groups of up to 4 queries (zh_group_size); a group of fewer members runs the same kernel
+template <int D, int KIND>
+static hipError_t launch_sweep_k(const SweepArgs &a) {
+    constexpr int G = 4;
+    // One batch is issued as several launches of ~12 GiB of rows each (about 2 ms of HBM time): a single
     // 18-ms dispatch keeps its dispatch pipe busy until its last workgroup is issued, and kernels of other
     // queues that share the pipe (the next batch's hash / walk, RCCL) would wait that long.
     // (a PREDICATED sweep -- the redo behind a half-width sweep, all but never run -- is ONE launch of a small striding grid for the whole batch)
@@ -1668,45 +1639,19 @@ static hipError_t launch_sweep_g(const SweepArgs &a) {
         uint64_t waves = (r_end - r + 63) / 64;
         uint64_t blocks = (waves + 3) / 4;
         if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-        const dim3 grid((uint32_t)blocks), blk(256);
         if constexpr (D == 128 && (KIND == K_L2 || KIND == K_COS)) {
-            if (v128 > 0) {
-                // ZH_SWEEP128_CHUNKS (A/B): 64-row chunks per wave, 1 = the round-2 kernel's shape
-                static const int ch128 = [] { const char *e = getenv("ZH_SWEEP128_CHUNKS"); return e ? atoi(e) : 4; }();
-#define ZH_S128(RG_, CH_) do { const uint64_t w_ = (r_end - r + 64 * CH_ - 1) / (64 * CH_), b_ = (w_ + 3) / 4;                        \
-                               hipLaunchKernelGGL((sweep128_kernel<KIND, G, RG_, true, CH_>), dim3((uint32_t)(a.dRunIf && b_ > 2048 ? 2048 : b_)), blk, 0, a.s, a.dX, a.dQ, a.dQQ, \
-                                                  a.dGroups, a.dGroupRowOff, a.n_groups, a.dWaveGroup, a.dLeafIds, r, r_end, a.metric, a.param, a.dKeys, a.dRunIf); } while (0)
-                if (ch128 == 1) ZH_S128(8, 1);
-                else if (ch128 == 8) ZH_S128(8, 8);
-                else if (v128 == 4) ZH_S128(4, 4);
-                else if (v128 == 16) ZH_S128(16, 4);
-                else ZH_S128(8, 4);
-#undef ZH_S128
-                continue;
-            }
-        }
-        if constexpr (D == 768 && KIND == K_L2 && G == 4) {
-            static const bool qlds = getenv("ZH_SWEEP_QLDS") != nullptr;
-            if (qlds) {
-                hipLaunchKernelGGL((sweep_kernel<D, KIND, G, 4, true, true>), grid, blk, 0, a.s, a.dX, a.d, a.dQ, a.dQQ, a.dGroups,
-                                   a.dGroupRowOff, a.n_groups, a.dWaveGroup, a.dLeafIds, r, r_end, a.metric, a.param, a.dKeys);
-                continue;
-            }
-        }
-        if (variant == 1)
-            hipLaunchKernelGGL((sweep_kernel<D, KIND, G, 4, false>), grid, blk, 0, a.s, a.dX, a.d, a.dQ, a.dQQ, a.dGroups,
+            // d = 128: the half-wave kernel, 8 load instructions = 16 rows in flight, 4 consecutive 64-row chunks per wave
+            constexpr int RG = 8, CH = 4;
+            const uint64_t w = (r_end - r + 64 * CH - 1) / (64 * CH), b = (w + 3) / 4;
+            hipLaunchKernelGGL((sweep128_kernel<KIND, G, RG, CH>), dim3((uint32_t)(a.dRunIf && b > 2048 ? 2048 : b)), dim3(256), 0,
+                               a.s, a.dX, a.dQ, a.dQQ, a.dGroups, a.dGroupRowOff, a.n_groups, a.dWaveGroup, a.dLeafIds, r, r_end,
+                               a.metric, a.param, a.dKeys, a.dRunIf);
+        } else {
+            hipLaunchKernelGGL((sweep_kernel<D, KIND, G>), dim3((uint32_t)blocks), dim3(256), 0, a.s, a.dX, a.d, a.dQ, a.dQQ, a.dGroups,
                                a.dGroupRowOff, a.n_groups, a.dWaveGroup, a.dLeafIds, r, r_end, a.metric, a.param, a.dKeys);
-        else
-            hipLaunchKernelGGL((sweep_kernel<D, KIND, G, 4, true>), grid, blk, 0, a.s, a.dX, a.d, a.dQ, a.dQQ, a.dGroups,
-                               a.dGroupRowOff, a.n_groups, a.dWaveGroup, a.dLeafIds, r, r_end, a.metric, a.param, a.dKeys);
+        }
     }
     return hipGetLastError();
-}
-
-template <int D, int KIND>
-static hipError_t launch_sweep_k(const SweepArgs &a) {
-    if (a.group == 4) return launch_sweep_g<D, KIND, 4>(a);
-    return launch_sweep_g<D, KIND, 2>(a);
 }
 
 // the two simsimd-path kinds get every specialised dimension; the ten `distances`-path kinds the three
@@ -1733,27 +1678,23 @@ static hipError_t launch_sweep_kind(const SweepArgs &a) {
 #undef ZH_SWEEP_CASE
 }
 
-// the leaf-major sweep that takes a device-side predicate: the d = 128 half-wave kernel of the two simsimd-path kinds (not under ZH_SWEEP128=0)
+// the leaf-major sweep that takes a device-side predicate: the d = 128 half-wave kernel of the two simsimd-path kinds
 bool zh_sweep_has_predicate(uint32_t d, int metric) {
-    static const int v128 = [] { const char *e = getenv("ZH_SWEEP128"); return e ? atoi(e) : 8; }();
     const int kind = zh_kind_of(metric);
-    return d == 128 && v128 > 0 && (kind == K_L2 || kind == K_COS);
+    return d == 128 && (kind == K_L2 || kind == K_COS);
 }
 
 uint32_t zh_group_size(uint32_t dim) {
-    static const int forced = [] { const char *e = getenv("ZH_GROUP"); return e ? atoi(e) : 0; }();
-    if (forced == 2 || forced == 4) return (uint32_t)forced;
     return 4u;  // (d = 128 with the half-wave kernel: 4 measures equal or better than 2, profiles/r02_ab_sweep128.txt)
 }
 
 hipError_t zh_launch_sweep(const float *dX, uint32_t d, const float *dQ, const float *dQQ, const ZhGroup *dGroups,
                            const uint64_t *dGroupRowOff, uint64_t n_groups, const uint32_t *dWaveGroup,
                            const uint32_t *dLeafIds, uint64_t R_grouped, int metric, int param, uint64_t *dKeys,
-                           uint32_t group, hipStream_t s, const uint32_t *dRunIf) {
+                           hipStream_t s, const uint32_t *dRunIf) {
     if (R_grouped == 0 || n_groups == 0) return hipSuccess;
     if (dRunIf && !zh_sweep_has_predicate(d, metric)) return hipErrorInvalidValue;
-    const SweepArgs a{dX, d, dQ, dQQ, dGroups, dGroupRowOff, n_groups, dWaveGroup, dLeafIds, R_grouped, metric, param, dKeys,
-                      group == 4 ? 4u : 2u, s, dRunIf};
+    const SweepArgs a{dX, d, dQ, dQQ, dGroups, dGroupRowOff, n_groups, dWaveGroup, dLeafIds, R_grouped, metric, param, dKeys, s, dRunIf};
 #define ZH_KIND_CASE(K) case K: return launch_sweep_kind<K>(a)
     switch (zh_kind_of(metric)) {
         ZH_KIND_CASE(K_COS);
@@ -1839,26 +1780,6 @@ hipError_t zh_launch_node_visits(const uint32_t *dLeafCount, const uint32_t *dGr
     if (!words) return hipSuccess;
     hipLaunchKernelGGL(node_visit_kernel, dim3((words + 255) / 256), dim3(256), 0, s, dLeafCount, dGroupBase, dGroups, n_nodes, dBits, dNodeVisit);
     return hipGetLastError();
-}
-
-// A stored row of the table scan: streamed exactly once per batch window.  ZH_SCAN_ROWPOL (build-time, A/B) picks the cache
-// policy of these loads: 0 = global_load ... nt; n > 0 = buffer_load with aux bits n (1 = sc0, 2 = nt, 16 = sc1).
-#ifndef ZH_SCAN_ROWPOL
-#define ZH_SCAN_ROWPOL 0
-#endif
-template <int D>
-__device__ __forceinline__ void load_row_stream(const float *__restrict__ row, uint32_t lane, float4 *v) {
-#if ZH_SCAN_ROWPOL == 0
-    load_row<D, true>(row, lane, v);
-#else
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(row), 0, D * 4, 0x00020000);
-#pragma unroll
-    for (int j = 0; j < RowVec<D>::NV; j++) {
-        const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rs, (lane + 64 * j) * 16, 0, ZH_SCAN_ROWPOL);  // out of range -> 0
-        v[j] = make_float4(__uint_as_float(t.x), __uint_as_float(t.y), __uint_as_float(t.z), __uint_as_float(t.w));
-    }
-#endif
 }
 
 #define ZH_SCAN_CAP 256  // pair records of a wave's LDS list (16 bytes each); a wave with more pairs takes the slow path
@@ -2011,10 +1932,10 @@ __global__ __launch_bounds__(256) void scan_sweep_kernel(const float *__restrict
                 rowmask &= rowmask - 1;  // (0 & anything stays 0)
             }
             float4 v0[NV], v1[NV], v2[NV], v3[NV];
-            load_row_stream<D>(X + (size_t)(r0 + rid[0]) * D, lane, v0);
-            if (rid[1] != 0xFFFFFFFFu) load_row_stream<D>(X + (size_t)(r0 + rid[1]) * D, lane, v1);
-            if (rid[2] != 0xFFFFFFFFu) load_row_stream<D>(X + (size_t)(r0 + rid[2]) * D, lane, v2);
-            if (rid[3] != 0xFFFFFFFFu) load_row_stream<D>(X + (size_t)(r0 + rid[3]) * D, lane, v3);
+            load_row<D, true>(X + (size_t)(r0 + rid[0]) * D, lane, v0);
+            if (rid[1] != 0xFFFFFFFFu) load_row<D, true>(X + (size_t)(r0 + rid[1]) * D, lane, v1);
+            if (rid[2] != 0xFFFFFFFFu) load_row<D, true>(X + (size_t)(r0 + rid[2]) * D, lane, v2);
+            if (rid[3] != 0xFFFFFFFFu) load_row<D, true>(X + (size_t)(r0 + rid[3]) * D, lane, v3);
             segment(v0, KIND == K_COS ? row_norm(v0) : 0.f, rid[0]);
             if (rid[1] != 0xFFFFFFFFu) segment(v1, KIND == K_COS ? row_norm(v1) : 0.f, rid[1]);
             if (rid[2] != 0xFFFFFFFFu) segment(v2, KIND == K_COS ? row_norm(v2) : 0.f, rid[2]);
@@ -2261,16 +2182,12 @@ static hipError_t launch_scan_dk(const float *dX, uint64_t n_rows, const float *
         const uint64_t r_end = r + rows_per_launch < n_rows ? r + rows_per_launch : n_rows;
         const uint64_t waves = (r_end - r + RW - 1) / RW, blocks = (waves + 3) / 4;
         if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-        if constexpr (D == 128 && (KIND == K_L2 || KIND == K_COS)) {
-            static const bool paired = getenv("ZH_SCAN128_GENERIC") == nullptr;  // A/B: the generic kernel at d = 128
-            if (paired) {
-                hipLaunchKernelGGL((scan128_sweep_kernel<KIND>), dim3((uint32_t)blocks), dim3(256), 0, s, dX, dQ, dQQ, dRowLeaf, T, RW,
-                                   dVisitBits, dNodeVisit, dGroups, group, r, r_end, metric, param, dKeys, dRunIf);
-                continue;
-            }
-        }
-        hipLaunchKernelGGL((scan_sweep_kernel<D, KIND>), dim3((uint32_t)blocks), dim3(256), 0, s, dX, dQ, dQQ, dRowLeaf, T, RW,
-                           dVisitBits, dNodeVisit, dGroups, group, r, r_end, metric, param, dKeys, dRunIf);
+        if constexpr (D == 128 && (KIND == K_L2 || KIND == K_COS))
+            hipLaunchKernelGGL((scan128_sweep_kernel<KIND>), dim3((uint32_t)blocks), dim3(256), 0, s, dX, dQ, dQQ, dRowLeaf, T, RW,
+                               dVisitBits, dNodeVisit, dGroups, group, r, r_end, metric, param, dKeys, dRunIf);
+        else
+            hipLaunchKernelGGL((scan_sweep_kernel<D, KIND>), dim3((uint32_t)blocks), dim3(256), 0, s, dX, dQ, dQQ, dRowLeaf, T, RW,
+                               dVisitBits, dNodeVisit, dGroups, group, r, r_end, metric, param, dKeys, dRunIf);
     }
     return hipGetLastError();
 }
@@ -2329,7 +2246,7 @@ hipError_t zh_launch_distance_rows(const float *dX, uint64_t n, uint32_t d, cons
     float *dqq = reinterpret_cast<float *>(dro + 1);
     hipLaunchKernelGGL(one_group_kernel, dim3(1), dim3(1), 0, s, dg, dro, n);
     hipError_t e = zh_launch_qnorm(dq, 1, d, dqq, s);
-    if (e == hipSuccess) e = zh_launch_sweep(dX, d, dq, dqq, dg, dro, 1, nullptr, nullptr, n, metric, mode, dKeys, 2, s);
+    if (e == hipSuccess) e = zh_launch_sweep(dX, d, dq, dqq, dg, dro, 1, nullptr, nullptr, n, metric, mode, dKeys, s);
     return e;
 }
 
@@ -2420,9 +2337,6 @@ hipError_t zh_launch_select(const ZhVisit *dVisits, uint64_t n_visits, const uin
     const uint64_t blocks = (n_visits + chunk - 1) / chunk;  // <= 2^23: 2^31 threads
     if (max_leaf_len <= 1024)
         hipLaunchKernelGGL(select_kernel<1024>, dim3((uint32_t)blocks), dim3(256), 0, s, dVisits, n_visits, (uint32_t)chunk,
-                           dLeafIds, dKeys, dCandKeys, dCandIds, dRunIf);
-    else if (getenv("ZH_SELECT_4096") != nullptr)  // A/B: the round-1 LDS footprint (48 KB per block)
-        hipLaunchKernelGGL(select_kernel<ZH_SORT_N>, dim3((uint32_t)blocks), dim3(256), 0, s, dVisits, n_visits, (uint32_t)chunk,
                            dLeafIds, dKeys, dCandKeys, dCandIds, dRunIf);
     else  // Leaves longer than the LDS buffer re-read their keys from the L2-resident scratch per histogram round.  Small buffers win:
           // 2048 entries (24 KB per block, six blocks per CU) against 4096: 0.33 / 0.46 ms alone at cfg3, 0.4 / 3.8 ms beside the sweep;

@@ -470,7 +470,7 @@ def synth_queries_device(device, d_out, n_rows, b, dim, b0=0, seed_rows=0x5EB2A0
 
 # ------------------------------------------------------------------------ src/database/core.rs
 def trim_device_memory():
-    """zh_trim_device_memory: hand the library's cached device blocks (32 MiB and more, kept when an index or context lets go of them) back to the driver"""
+    """zh_trim_device_memory: does nothing (the library caches no device memory; freed buffers go back to the driver at once)"""
     check(lib().zh_trim_device_memory())
 
 

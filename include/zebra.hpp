@@ -205,6 +205,25 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
             for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * top_k + j], keys[i * top_k + j]);
         return out;
     }
+    // exact k nearest neighbours over every live stored row (zh_search_exact_batch): same keys and order as search_batch, no forest needed
+    template <class Met>
+    std::vector<std::pair<Id, DistanceUnit>> search_exact(const Embedding<N> &query, std::size_t top_k, const Met &metric) const {
+        return std::move(search_exact_batch(std::vector<Embedding<N>>{query}, top_k, metric)[0]);
+    }
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> search_exact_batch(const std::vector<Embedding<N>> &queries,
+                                                                               std::size_t top_k, const Met &metric) const {
+        const std::size_t b = queries.size();
+        std::vector<Id> ids(b * top_k);
+        std::vector<DistanceUnit> keys(b * top_k);
+        std::vector<std::uint32_t> counts(b);
+        check(zh_search_exact_batch(h_.get(), b ? queries[0].data() : nullptr, b, top_k, Met::metric, metric.mode(), ids.data(),
+                                    keys.data(), counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(b);
+        for (std::size_t i = 0; i < b; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * top_k + j], keys[i * top_k + j]);
+        return out;
+    }
     zh_index *handle() const { return h_.get(); }
 
   private:

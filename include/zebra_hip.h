@@ -22,6 +22,7 @@
  *                                        whose rows are sharded across GPUs (README.md:31 "can be sharded"): local search on
  *                                        this rank's shard, ONE RCCL all-gather of the packed top-k, merge on every rank
  *   zh_merge_topk_device                 (new) the shard merge alone
+ *   zh_search_exact_batch[_device]       (new) exact top-k over every live row under the same keys: recall ground truth
  *
  * Conventions
  *   - Every function returns ZH_OK (0) or a negative zh_status; zh_last_error() gives the message
@@ -249,6 +250,33 @@ ZH_API int zh_search_batch(zh_index *idx, const float *q, size_t b, size_t k, in
  * `stream` (a hipStream_t; NULL = the index's own stream) and have completed on return. */
 ZH_API int zh_search_batch_device(zh_index *idx, const float *d_q, size_t b, size_t k, int metric, int cosine_mode,
                            uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream);
+
+/* EXACT top-k over every live stored row (rows removed by zh_index_remove / zh_index_deduplicate excluded); no forest needed: an index
+ * filled by zh_index_append and never built is served.  Same arguments, limits, key arithmetic and output convention as zh_search_batch:
+ * ids = id_base + row, ascending by (key, id), out_counts[i] = min(k, live rows), entries past it UINT64_MAX; k = 0 gives counts of 0.
+ * Every key is the one zh_distance_batch returns for that (row, query) pair, for every metric, power and cosine mode, so the answer
+ * is the ground truth of a recall measurement under the library's own keys.  Thread-safe against concurrent searches on the same
+ * index (it serialises on the index's internal lock); never concurrent with add / build / remove / clear.  It does not join the
+ * combining front end of zh_search_batch and leaves zh_stats_t alone: zh_search_exact_info describes the most recent call.
+ * Two paths, same answers: path 2 (ZH_L2SQ, ZH_L2, ZH_COSINE at dim 256 / 384 / 512 / 768 / 1024, at least max(k, 8192) live rows, room for the
+ * index's fp16 row copy: + 2 * dim + 8 bytes per stored row, kept and shared with the search) scans on the matrix cores for an interval per pair
+ * and gives only the rows the intervals cannot rule out the canonical key; everything else, and an internal batch whose per-query lists run over,
+ * takes path 1 (canonical sums for every pair).  Device scratch is allocated per call and released before it returns: at 1024 queries up to
+ * ~1.1 GiB (path 1) or (16384 + 8 k) * 44 bytes per query (path 2). */
+ZH_API int zh_search_exact_batch(zh_index *idx, const float *q, size_t b, size_t k, int metric, int cosine_mode,
+                                 uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts);
+/* The same with queries and results in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_search_exact_batch_device(zh_index *idx, const float *d_q, size_t b, size_t k, int metric, int cosine_mode,
+                                        uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream);
+typedef struct zh_exact_info {  /* the most recent zh_search_exact_* call on this index */
+    uint64_t batch;       /* queries */
+    uint64_t rows_live;   /* rows ranked */
+    uint32_t path;        /* 1: canonical sums for every pair; 2: matrix-core intervals, canonical keys for the survivors only */
+    uint32_t redone;      /* path-2 internal batches whose lists ran over and were answered by path 1 instead */
+    uint64_t survivors;   /* path 2: (row, query) pairs that got the canonical key, over all queries */
+    uint64_t launches;    /* row-chunk launches of the scan */
+} zh_exact_info;
+ZH_API int zh_search_exact_info(const zh_index *idx, zh_exact_info *out);
 
 /* Pipelined form of zh_search_batch_device (new; the reference has one blocking search per query): a context
  * is one in-flight batch with its own scratch.  The context calls do NOT take the index's internal lock (the blocking

@@ -97,6 +97,17 @@ pub mod ffi {
         pub reserve_rows: u64,
     }
 
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
+    pub struct zh_exact_info {
+        pub batch: u64,
+        pub rows_live: u64,
+        pub path: u32,
+        pub redone: u32,
+        pub survivors: u64,
+        pub launches: u64,
+    }
+
     pub const ZH_COSINE: c_int = 0;
     pub const ZH_L2SQ: c_int = 1;
     pub const ZH_L2: c_int = 2;
@@ -125,6 +136,11 @@ pub mod ffi {
         pub fn zh_index_num_trees(idx: *const zh_index) -> u32;
         pub fn zh_search_batch(idx: *mut zh_index, q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
                                out_ids: *mut u64, out_keys: *mut u64, out_counts: *mut u32) -> c_int;
+        pub fn zh_search_exact_batch(idx: *mut zh_index, q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
+                                     out_ids: *mut u64, out_keys: *mut u64, out_counts: *mut u32) -> c_int;
+        pub fn zh_search_exact_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
+                                            d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_search_exact_info(idx: *const zh_index, out: *mut zh_exact_info) -> c_int;
         pub fn zh_search_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
                                       d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_distance_pair(metric: c_int, cosine_mode: c_int, a: *const f32, b: *const f32, dim: usize, out_key: *mut u64,
@@ -344,6 +360,23 @@ impl<const N: usize> LSHIndex<N> {
         check(unsafe {
             ffi::zh_search_batch(self.hip.0, queries.as_ptr() as *const f32, b, top_k, Met::METRIC, metric.param(), ids.as_mut_ptr(),
                                  keys.as_mut_ptr(), counts.as_mut_ptr())
+        })?;
+        let t = self.ids.read().unwrap();
+        Ok((0..b).map(|i| (0..counts[i] as usize).map(|j| (t.of_row[ids[i * top_k + j] as usize], keys[i * top_k + j])).collect()).collect())
+    }
+
+    /// exact k nearest neighbours over every live stored row (zh_search_exact_batch): same keys and order as search_batch
+    pub fn search_exact_batch<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        queries: &[Embedding<N>],
+        top_k: usize,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<Vec<(Uuid, DistanceUnit)>>> {
+        let b = queries.len();
+        let (mut ids, mut keys, mut counts) = (vec![0u64; b * top_k], vec![0u64; b * top_k], vec![0u32; b]);
+        check(unsafe {
+            ffi::zh_search_exact_batch(self.hip.0, queries.as_ptr() as *const f32, b, top_k, Met::METRIC, metric.param(), ids.as_mut_ptr(),
+                                       keys.as_mut_ptr(), counts.as_mut_ptr())
         })?;
         let t = self.ids.read().unwrap();
         Ok((0..b).map(|i| (0..counts[i] as usize).map(|j| (t.of_row[ids[i * top_k + j] as usize], keys[i * top_k + j])).collect()).collect())

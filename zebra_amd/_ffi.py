@@ -77,6 +77,14 @@ class DebugScanInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ExactInfo(C.Structure):
+    _fields_ = [("batch", C.c_uint64), ("rows_live", C.c_uint64), ("path", C.c_uint32), ("redone", C.c_uint32), ("survivors", C.c_uint64),
+                ("launches", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/zebra_hip.h declares: (name, restype, argtypes)
 _vp, _u64, _u32, _sz, _i = C.c_void_p, C.c_uint64, C.c_uint32, C.c_size_t, C.c_int
 SYMBOLS = [
@@ -105,6 +113,9 @@ SYMBOLS = [
     ("zh_hash_signs", _i, [_vp, _vp, _sz, _vp, _vp]),
     ("zh_search_batch", _i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_search_batch_device", _i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    ("zh_search_exact_batch", _i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _vp, _vp]),
+    ("zh_search_exact_batch_device", _i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    ("zh_search_exact_info", _i, [_vp, _vp]),
     ("zh_search_ctx_create", _i, [_vp, _vp]),
     ("zh_search_ctx_destroy", None, [_vp]),
     ("zh_search_begin", _i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),

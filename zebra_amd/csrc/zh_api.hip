@@ -252,6 +252,12 @@ struct zh_index {
     // the blocking entry points run on this context (under `mu`); staging buffers of the host-pointer variant
     zh_search_ctx dctx;
     DevBuf wQ, wOutIds, wOutKeys, wOutCounts;
+    // the exact search (zh_search_exact_*, zh_exact.hip): scratch of its own, so that pipelined search contexts are never touched; the
+    // ascending live rows on the device for (ex_live_rows, ex_live_gen) = (n_rows, dead_gen) -- removed rows are never scored
+    DevBuf ex_live, ex_bits, ex_QQ, ex_keys, ex_visits, ex_cbase, ex_ckeys, ex_cids, ex_run_ids, ex_run_keys, ex_run_counts, ex_Q, ex_ids, ex_kout, ex_counts,
+        ex_Qh, ex_qmeta, ex_tau, ex_cnt, ex_lid, ex_llo, ex_lhi, ex_scr, ex_over;
+    uint64_t ex_live_rows = ~0ull, ex_live_gen = ~0ull, ex_n_live = 0;
+    zh_exact_info ex_info{};  // (stats_mu)
 
     bool broken = false;  // an incremental add failed half way: trees are stale until zh_index_build
     int dense_levels = -1;
@@ -465,6 +471,7 @@ static void free_forest(zh_index *ix) {
     }
 }
 
+static void exact_release_scratch(zh_index *ix);
 extern "C" void zh_index_destroy(zh_index *ix) {
     if (ix)
         for (auto &ln : ix->lanes) {
@@ -489,7 +496,10 @@ extern "C" void zh_index_destroy(zh_index *ix) {
     ix->row_hn2.release(); ix->row_norm.release(); ix->row_half.release(); ix->row_meta.release(); ix->row_rho_dev.release(); ix->row_half128.release();
     ix->scan_perm.release(); ix->row_leaf_p.release();
     ix->dctx.release_all();
-    DevBuf *ws[] = {&ix->wQ, &ix->wOutIds, &ix->wOutKeys, &ix->wOutCounts};
+    DevBuf *ws[] = {&ix->wQ, &ix->wOutIds, &ix->wOutKeys, &ix->wOutCounts, &ix->ex_live, &ix->ex_QQ, &ix->ex_keys, &ix->ex_visits, &ix->ex_cbase,
+                    &ix->ex_ckeys, &ix->ex_cids, &ix->ex_run_ids, &ix->ex_run_keys, &ix->ex_run_counts, &ix->ex_Q, &ix->ex_ids, &ix->ex_kout, &ix->ex_counts,
+                    &ix->ex_bits};
+    exact_release_scratch(ix);
     for (DevBuf *b : ws) b->release();
     if (ix->sweep_stream) hipStreamDestroy(ix->sweep_stream);
     if (ix->stream) hipStreamDestroy(ix->stream);
@@ -2994,6 +3004,244 @@ extern "C" int zh_search_batch(zh_index *ix, const float *q, size_t b, size_t k,
         break;
     }
     if (me.rc) return fail(me.rc, "%s", me.err.empty() ? "zh_search_batch: out of host memory" : me.err.c_str());
+    return ZH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// exact search (zh_exact.hip): every live row against every query, canonical keys, top_k by (key, id)
+// ------------------------------------------------------------------------------------------------
+#define ZH_EXACT_BATCH 1024u             // queries per internal batch
+#define ZH_EXACT_KEY_BYTES (size_t(1) << 30)  // key scratch of one row chunk: queries x rows x 8 bytes
+
+// the ascending live rows (path 1) and the live-row bitmap (path 2) on the device (under mu, exclusive), rebuilt when rows were appended or
+// removed since
+static int exact_live_rows(zh_index *ix) {
+    if (ix->ex_live_rows == ix->n_rows && ix->ex_live_gen == ix->dead_gen) return ZH_OK;
+    std::vector<uint32_t> live;
+    live.reserve(ix->n_rows - ix->n_dead);
+    for (uint64_t r = 0; r < ix->n_rows; r++)
+        if (!(r < ix->h_dead.size() && ix->h_dead[r])) live.push_back((uint32_t)r);
+    int rc = ix->ex_live.ensure(std::max<size_t>(live.size(), 1) * 4);
+    if (rc) return rc;
+    if (!live.empty()) HIPCHK(hipMemcpy(ix->ex_live.p, live.data(), live.size() * 4, hipMemcpyHostToDevice));
+    std::vector<uint32_t> bits((ix->n_rows + 31) / 32 + 1, 0u);
+    for (uint32_t r : live) bits[r >> 5] |= 1u << (r & 31);
+    if ((rc = ix->ex_bits.ensure(bits.size() * 4))) return rc;
+    HIPCHK(hipMemcpy(ix->ex_bits.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
+    ix->ex_n_live = live.size();
+    ix->ex_live_rows = ix->n_rows;
+    ix->ex_live_gen = ix->dead_gen;
+    return ZH_OK;
+}
+
+// one internal batch (B <= ZH_EXACT_BATCH) on device pointers, enqueued on s.  Row chunk after row chunk: keys of all queries into the
+// scratch, each query's top_k of every sub-chunk of L positions (select_kernel), a query's sub-chunks merged (final_kernel), the chunk's
+// answer merged into the running one (the caller's outputs) -- merge_wave_kernel / final_kernel<true>.
+static int exact_batch(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys,
+                       uint32_t *dCounts, hipStream_t s, uint64_t *launches) {
+    const uint32_t d = ix->opt.dim;
+    const uint64_t n_live = ix->ex_n_live;
+    if (k == 0) { HIPCHK(hipMemsetAsync(dCounts, 0, (size_t)B * 4, s)); return ZH_OK; }
+    if (n_live == 0) { HIPCHK(zh_launch_exact_empty(B, k, dIds, dKeys, dCounts, s)); return ZH_OK; }
+    const uint32_t L = k <= 512 ? 2048u : 4096u, kk = std::min(k, L);
+    uint64_t rc_rows = std::max<uint64_t>(L, ZH_EXACT_KEY_BYTES / 8 / B / L * L);
+    rc_rows = std::min<uint64_t>(rc_rows, (n_live + L - 1) / L * L);
+    const uint32_t nsub_max = (uint32_t)(rc_rows / L);
+    int rc;
+    if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_keys.ensure((size_t)B * rc_rows * 8)) ||
+        (rc = ix->ex_visits.ensure((size_t)B * nsub_max * sizeof(ZhVisit))) || (rc = ix->ex_cbase.ensure(((size_t)B * nsub_max + 1) * 8)) ||
+        (rc = ix->ex_ckeys.ensure((size_t)B * nsub_max * kk * 8)) || (rc = ix->ex_cids.ensure((size_t)B * nsub_max * kk * 4)) ||
+        (rc = ix->ex_run_ids.ensure((size_t)2 * B * k * 8)) || (rc = ix->ex_run_keys.ensure((size_t)2 * B * k * 8)) ||
+        (rc = ix->ex_run_counts.ensure((size_t)2 * B * 4)))
+        return rc;
+    const int param = metric == ZH_COSINE ? mode : ((metric == ZH_MINKOWSKI || metric == ZH_PNORM) ? mode : 0);
+    const uint32_t *dLive = ix->ex_live.as<uint32_t>();
+    uint64_t *runIds = ix->ex_run_ids.as<uint64_t>(), *runKeys = ix->ex_run_keys.as<uint64_t>();
+    uint32_t *runCounts = ix->ex_run_counts.as<uint32_t>();
+    HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
+    for (uint64_t p0 = 0; p0 < n_live; p0 += rc_rows) {
+        const uint32_t nr = (uint32_t)std::min<uint64_t>(rc_rows, n_live - p0), nsub = (nr + L - 1) / L;
+        HIPCHK(zh_launch_exact_score(ix->X.as<float>(), d, dLive, p0, nr, dQ, ix->ex_QQ.as<float>(), B, metric, param, ix->ex_keys.as<uint64_t>(),
+                                     rc_rows, s));
+        HIPCHK(zh_launch_exact_visits(B, nsub, nr, L, k, p0, rc_rows, ix->ex_visits.as<ZhVisit>(), ix->ex_cbase.as<uint64_t>(), s));
+        HIPCHK(zh_launch_select(ix->ex_visits.as<ZhVisit>(), (uint64_t)B * nsub, dLive, ix->ex_keys.as<uint64_t>(), ix->ex_ckeys.as<uint64_t>(),
+                                ix->ex_cids.as<uint32_t>(), L, nullptr, s));
+        if (p0 == 0) {
+            HIPCHK(zh_launch_final(ix->ex_cbase.as<uint64_t>(), B, nsub, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), ix->opt.id_base,
+                                   dIds, dKeys, dCounts, nullptr, s));
+        } else {  // this chunk's answer into slot 1, the running one (the outputs) into slot 0, both merged back into the outputs
+            HIPCHK(zh_launch_final(ix->ex_cbase.as<uint64_t>(), B, nsub, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), ix->opt.id_base,
+                                   runIds + (size_t)B * k, runKeys + (size_t)B * k, runCounts + B, nullptr, s));
+            HIPCHK(hipMemcpyAsync(runIds, dIds, (size_t)B * k * 8, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(runKeys, dKeys, (size_t)B * k * 8, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(runCounts, dCounts, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+            HIPCHK(zh_launch_merge(2, B, k, runIds, runKeys, runCounts, dIds, dKeys, dCounts, 0, 0, s));
+        }
+        (*launches)++;
+    }
+    return ZH_OK;
+}
+
+// Path 2 of one internal batch: the matrix-core interval scan in geometrically growing row chunks, a per-query tau and list, canonical keys for
+// the survivors, final_kernel's (key, id) top_k.  *used = false: path 2 does not serve this index / batch (path 1 answers); *overflowed: a list
+// ran over and the outputs are not valid (the caller answers the batch by path 1).
+#define ZH_EXACT_GROWTH 4
+static int exact_batch2(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts,
+                        hipStream_t s, bool *used, bool *overflowed, uint64_t *survivors, uint64_t *launches) {
+    *used = false; *overflowed = false;
+    const uint32_t d = ix->opt.dim;
+    if (k == 0 || !zh_exact_mfma_supported(d, metric) || ix->ex_n_live < std::max<uint64_t>(k, 8192)) return ZH_OK;
+    int rc;
+    const void *Xh;
+    const float2 *rowMeta;
+    const uint32_t *perm;
+    uint64_t perm_rows;
+    float rho;
+    {
+        std::lock_guard<std::mutex> lb(ix->blk_mu);
+        bool ok = false;
+        if ((rc = ensure_row_half(ix, &ok))) return rc;
+        if (!ok || !ix->row_half.p) return ZH_OK;  // no room for the fp16 copy: path 1
+        Xh = ix->row_half.p; rowMeta = ix->row_meta.as<float2>(); rho = ix->row_rho;
+        perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr; perm_rows = ix->perm_rows;
+    }
+    const uint32_t cap = 16384 + 8 * k;  // first chunk (<= max(k, 4096) rows, all listed) + a few growth steps' worth of k
+    if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_Qh.ensure((size_t)B * d * 2)) || (rc = ix->ex_qmeta.ensure((size_t)B * 16)) ||
+        (rc = ix->ex_tau.ensure((size_t)B * 4)) || (rc = ix->ex_cnt.ensure((size_t)B * 4)) || (rc = ix->ex_lid.ensure((size_t)B * cap * 4)) ||
+        (rc = ix->ex_llo.ensure((size_t)B * cap * 4)) || (rc = ix->ex_lhi.ensure((size_t)B * cap * 4)) || (rc = ix->ex_scr.ensure((size_t)B * cap * 12)) ||
+        (rc = ix->ex_over.ensure(4)) || (rc = ix->ex_ckeys.ensure((size_t)B * cap * 8)) || (rc = ix->ex_cids.ensure((size_t)B * cap * 4)) ||
+        (rc = ix->ex_cbase.ensure(((size_t)B + 1) * 8)))
+        return rc;
+    ZhExact2 e{Xh, rowMeta, perm, perm_rows, ix->ex_bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B, zh_approx_bound(metric, d, 1), rho,
+               ix->ex_tau.as<uint32_t>(), ix->ex_cnt.as<uint32_t>(), ix->ex_lid.as<uint32_t>(), ix->ex_llo.as<uint32_t>(), ix->ex_lhi.as<uint32_t>(), cap,
+               ix->ex_over.as<uint32_t>()};
+    HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
+    HIPCHK(zh_launch_qhalf(dQ, B, d, ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), 1, s));
+    HIPCHK(hipMemsetAsync(e.tau, 0xFF, (size_t)B * 4, s));
+    HIPCHK(hipMemsetAsync(e.cnt, 0, (size_t)B * 4, s));
+    HIPCHK(hipMemsetAsync(e.over, 0, 4, s));
+    std::vector<uint64_t> cb(B + 1);
+    for (uint32_t b = 0; b <= B; b++) cb[b] = (uint64_t)b * cap;
+    HIPCHK(hipMemcpyAsync(ix->ex_cbase.p, cb.data(), cb.size() * 8, hipMemcpyHostToDevice, s));
+    const uint64_t n = ix->n_rows;  // positions of the copy; removed rows are masked by the bitmap
+    uint64_t chunk = (std::max<uint64_t>(k, 4096) + 15) / 16 * 16;
+    for (uint64_t p0 = 0; p0 < n; p0 += chunk, chunk *= ZH_EXACT_GROWTH) {
+        const uint64_t p1 = std::min(n, p0 + chunk);
+        HIPCHK(zh_launch_exact_mfma(d, metric, mode, e, p0, p1, s));
+        HIPCHK(zh_launch_exact_prune(e, k, ix->ex_scr.as<uint32_t>(), s));
+        (*launches)++;
+    }
+    HIPCHK(zh_launch_exact_survivor_keys(ix->X.as<float>(), d, dQ, ix->ex_QQ.as<float>(), metric, mode, e, ix->ex_ckeys.as<uint64_t>(),
+                                         ix->ex_cids.as<uint32_t>(), s));
+    HIPCHK(zh_launch_final(ix->ex_cbase.as<uint64_t>(), B, 1, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), ix->opt.id_base, dIds, dKeys,
+                           dCounts, nullptr, s));
+    std::vector<uint32_t> h_cnt(B + 1);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), e.cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_cnt.data() + B, e.over, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *used = true;
+    *overflowed = h_cnt[B] != 0;
+    if (!*overflowed)
+        for (uint32_t b = 0; b < B; b++) *survivors += h_cnt[b];
+    return ZH_OK;
+}
+
+static void exact_release_scratch(zh_index *ix) {  // the per-call scratch goes back to the driver: an idle index holds only the live-row views
+    DevBuf *bs[] = {&ix->ex_QQ, &ix->ex_keys, &ix->ex_visits, &ix->ex_cbase, &ix->ex_ckeys, &ix->ex_cids, &ix->ex_run_ids, &ix->ex_run_keys,
+                    &ix->ex_run_counts, &ix->ex_Q, &ix->ex_ids, &ix->ex_kout, &ix->ex_counts, &ix->ex_Qh, &ix->ex_qmeta, &ix->ex_tau, &ix->ex_cnt,
+                    &ix->ex_lid, &ix->ex_llo, &ix->ex_lhi, &ix->ex_scr, &ix->ex_over};
+    for (DevBuf *b : bs) b->release();
+}
+
+// one internal batch: path 2 where it serves, path 1 otherwise and for a batch whose path-2 lists ran over
+static int exact_one(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts,
+                     hipStream_t s, zh_exact_info *inf) {
+    bool used = false, overflowed = false;
+    int rc = exact_batch2(ix, dQ, B, k, metric, mode, dIds, dKeys, dCounts, s, &used, &overflowed, &inf->survivors, &inf->launches);
+    if (rc) return rc;
+    if (used) inf->path = 2;
+    if (used && !overflowed) return ZH_OK;
+    if (overflowed) inf->redone++;
+    return exact_batch(ix, dQ, B, k, metric, mode, dIds, dKeys, dCounts, s, &inf->launches);
+}
+
+static int exact_args(zh_index *ix, const float *q, size_t b, size_t k, int metric, int mode, const void *ids, const void *keys,
+                      const void *counts, const char *who) {
+    if (!ix || (b && (!q || !counts || (k && (!ids || !keys))))) return fail(ZH_EINVAL, "%s: null argument", who);
+    if (k > ZH_MAX_TOPK) return fail(ZH_ELIMIT, "top_k %zu > ZH_MAX_TOPK (%u)", k, ZH_MAX_TOPK);
+    return check_metric(metric, mode);
+}
+
+static void exact_record(zh_index *ix, size_t b, zh_exact_info inf) {
+    exact_release_scratch(ix);
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    inf.batch = b;
+    inf.rows_live = ix->ex_n_live;
+    ix->ex_info = inf;
+}
+
+extern "C" int zh_search_exact_batch_device(zh_index *ix, const float *d_q, size_t b, size_t k, int metric, int mode, uint64_t *d_out_ids,
+                                            uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
+    int rc = exact_args(ix, d_q, b, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_search_exact_batch_device");
+    if (rc) return rc;
+    if (b == 0) return ZH_OK;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    const uint32_t d = ix->opt.dim;
+    zh_exact_info inf{};
+    inf.path = 1;
+    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
+        if ((rc = exact_one(ix, d_q + b0 * d, nb, (uint32_t)k, metric, mode, d_out_ids + b0 * k, d_out_keys + b0 * k, d_out_counts + b0, s, &inf))) {
+            exact_release_scratch(ix);
+            return rc;
+        }
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    exact_record(ix, b, inf);
+    return ZH_OK;
+}
+
+extern "C" int zh_search_exact_batch(zh_index *ix, const float *q, size_t b, size_t k, int metric, int mode, uint64_t *out_ids,
+                                     uint64_t *out_keys, uint32_t *out_counts) {
+    int rc = exact_args(ix, q, b, k, metric, mode, out_ids, out_keys, out_counts, "zh_search_exact_batch");
+    if (rc) return rc;
+    if (b == 0) return ZH_OK;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    const hipStream_t s = ix->stream;
+    const uint32_t d = ix->opt.dim;
+    const size_t nb_max = std::min<size_t>(ZH_EXACT_BATCH, b);
+    if ((rc = ix->ex_Q.ensure(nb_max * d * 4)) || (rc = ix->ex_ids.ensure(std::max<size_t>(nb_max * k, 1) * 8)) ||
+        (rc = ix->ex_kout.ensure(std::max<size_t>(nb_max * k, 1) * 8)) || (rc = ix->ex_counts.ensure(nb_max * 4)))
+        return rc;
+    zh_exact_info inf{};
+    inf.path = 1;
+    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
+        HIPCHK(hipMemcpyAsync(ix->ex_Q.p, q + b0 * d, (size_t)nb * d * 4, hipMemcpyHostToDevice, s));
+        if ((rc = exact_one(ix, ix->ex_Q.as<float>(), nb, (uint32_t)k, metric, mode, ix->ex_ids.as<uint64_t>(), ix->ex_kout.as<uint64_t>(),
+                            ix->ex_counts.as<uint32_t>(), s, &inf))) {
+            exact_release_scratch(ix);
+            return rc;
+        }
+        if (k) {
+            HIPCHK(hipMemcpyAsync(out_ids + b0 * k, ix->ex_ids.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_keys + b0 * k, ix->ex_kout.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipMemcpyAsync(out_counts + b0, ix->ex_counts.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    exact_record(ix, b, inf);
+    return ZH_OK;
+}
+
+extern "C" int zh_search_exact_info(const zh_index *ix, zh_exact_info *out) {
+    if (!ix || !out) return fail(ZH_EINVAL, "zh_search_exact_info: null argument");
+    zh_index *m = const_cast<zh_index *>(ix);
+    std::lock_guard<std::mutex> lk(m->stats_mu);
+    *out = m->ex_info;
     return ZH_OK;
 }
 

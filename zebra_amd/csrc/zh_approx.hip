@@ -155,48 +155,7 @@ __device__ __forceinline__ float group_sum(float s) {
     return s;
 }
 
-// The L2 family's interval is V -+ E: V from the pair's sums, E from the norms.  Both as functions of their own, because the fused sweep's pre-test
-// (fused_pretest) evaluates V the same way and E at an upper bound of nx: every operation of l2_E is non-decreasing in nx >= 0 (all factors are
-// non-negative) and so is its rounded result -- E(nx_max) >= E(nx) in f32, whatever the roundings.
-__device__ __forceinline__ float l2_V(float s, float a2, const float4 qm) {
-    const float sh = s * qm.x, sum = a2 + qm.y;
-    return sum - 2.0f * sh;
-}
-__device__ __forceinline__ float l2_E(float nx, const float4 qm, float Kc, float rho, float rho_n) {
-    const float nn = nx + qm.z;
-    // |s / sigma - x.q| <= |x| dq + |x - x'| (|q| + dq), |x - x'| <= rho |x| (rho = 0: the scan multiplied the f32 row)
-    return Kc * nn * nn + 2.02f * nx * (qm.w + rho * (qm.z + qm.w)) + 2.2f * rho_n * nx * nx;
-}
-// the interval of one (row, query) pair from its sums: sortable lo | sortable hi << 32; (0, all ones) = nothing certain
-template <int KINDA>
-__device__ __forceinline__ uint64_t approx_interval(float s, float a2, const float4 qm, float Kc, float rho, float rho_n) {
-    uint32_t lo_s = 0u, hi_s = 0xFFFFFFFFu;
-    const float sh = s * qm.x;
-    if (KINDA == 0) {
-        // rho_n != 0: a2 is the ROUNDED row's |x'|^2 (sweep128h_kernel): |x| <= |x'| (1 + 2 rho_n), ||x'|^2 - |x|^2| <= 2.2 rho_n |x'|^2
-        const float nx = sqrtf(a2) * (1.0f + 1e-5f) * (1.0f + 2.0f * rho_n), nn = nx + qm.z, sum = a2 + qm.y;
-        const float V = l2_V(s, a2, qm);
-        const float E = l2_E(nx, qm, Kc, rho, rho_n);
-        if ((V - V == 0.f) && (E - E == 0.f) && nn > 1e-12f && sum < 1e37f) { lo_s = f32_sortable(V - E); hi_s = f32_sortable(V + E); }
-    } else {
-        const float nx = sqrtf(a2), nq = sqrtf(qm.y);
-        if (nx > 1e-12f && nq > 1e-12f && (sh - sh == 0.f) && (nx - nx == 0.f) && (nq - nq == 0.f)) {
-            float r = 1.0f - sh / (nx * nq);
-            r = r > 0.f ? r : 0.f;
-            const float dqr = qm.w / nq;
-            const float e = Kc + 1.01f * (dqr + rho * (1.0f + dqr) + rho_n);
-            float v = r;
-            bool ok = true;
-            if (KINDA == 2) {  // ZH_COSINE_PARITY keys compare as the bits of 1 - distance: as pf_value<2>
-                const float key = 1.0f - r;
-                ok = fabsf(key) > e;
-                v = key > 0.f ? key : 2.0f - key;
-            }
-            if (ok && (v - v == 0.f) && (e - e == 0.f)) { lo_s = f32_sortable(v - e); hi_s = f32_sortable(v + e); }
-        }
-    }
-    return ((uint64_t)hi_s << 32) | lo_s;
-}
+// (l2_V, l2_E and approx_interval live in zh_device.h: the exact search (zh_exact.hip) forms the same intervals)
 
 // Phase 1 of a table-scan wave: its nr * T (row, tree) entries -> which leaves this batch visits, by which query, where the result
 // goes, and the exclusive scan of the visit counts (= positions in the wave's pair list).  Three dependent fetches per entry -- the

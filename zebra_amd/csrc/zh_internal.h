@@ -287,6 +287,29 @@ hipError_t zh_launch_final_interval(const ZhVisit *dVisits, const float *dX, uin
                                     uint32_t k, const uint32_t *dLeafIds, int metric, int mode, uint64_t id_base, ZhApprox ap,
                                     uint64_t *dOutIds, uint64_t *dOutKeys, uint32_t *dOutCounts, uint32_t max_leaf_len, hipStream_t s);
 
+// ---- the exact search (zh_exact.hip): keys of every (live row, query) pair of a row chunk, the per-(query, sub-chunk) visits for select /
+// final, and the answer of a batch with no live rows
+// keys[b * ld + (p - p0)] = key of (stored row dLive[p], query b), p in [p0, p0 + nr)
+hipError_t zh_launch_exact_score(const float *dX, uint32_t d, const uint32_t *dLive, uint64_t p0, uint32_t nr, const float *dQ,
+                                 const float *dQQ, uint32_t B, int metric, int param, uint64_t *dKeys, uint64_t ld, hipStream_t s);
+// visit b * nsub + j = positions [p0 + j L, p0 + min((j + 1) L, nr)) for query b, take min(k, len); dCandBase: B * nsub + 1 entries
+hipError_t zh_launch_exact_visits(uint32_t B, uint32_t nsub, uint32_t nr, uint32_t L, uint32_t k, uint64_t p0, uint64_t ld, ZhVisit *dVisits,
+                                  uint64_t *dCandBase, hipStream_t s);
+// path 2 (L2SQ, L2, cosine at d = 256 .. 1024): the matrix-core scan's view of one internal batch -- the index's fp16 row copy, the queries' fp16 copy,
+// and per query tau (sortable f32, starts at ~0), a list of cap (row, lo, hi) entries and its count; *over != 0: a list ran over (path 1 answers)
+struct ZhExact2 {
+    const void *Xh; const float2 *rowMeta; const uint32_t *perm; uint64_t perm_rows; const uint32_t *liveBits;
+    const void *Qh; const float4 *qmeta; uint32_t B; float Kc, rho;
+    uint32_t *tau, *cnt, *lid, *llo, *lhi; uint32_t cap; uint32_t *over;
+};
+bool zh_exact_mfma_supported(uint32_t d, int metric);
+hipError_t zh_launch_exact_mfma(uint32_t d, int metric, int mode, const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, hipStream_t s);
+// dScratch: 3 * B * cap words
+hipError_t zh_launch_exact_prune(const ZhExact2 &e, uint32_t k, uint32_t *dScratch, hipStream_t s);
+hipError_t zh_launch_exact_survivor_keys(const float *dX, uint32_t d, const float *dQ, const float *dQQ, int metric, int mode, const ZhExact2 &e,
+                                         uint64_t *dCKeys, uint32_t *dCIds, hipStream_t s);
+hipError_t zh_launch_exact_empty(uint32_t B, uint32_t k, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts, hipStream_t s);
+
 // ---- launchers (zh_score.hip): every sign of a forest built from stored rows, from N row scores per query --------
 // Prefilter (zh_search.hip, "Prefilter"): a batch hashed from row scores picks the rows that can be among a pair's k best from
 // those scores; only they are scored with the reference's arithmetic.  Lists: one per (tree, query), `cap` slots, list (t, b) at

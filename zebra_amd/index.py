@@ -263,6 +263,34 @@ class LSHIndex:
         check(lib().zh_search_batch_device(self._h, d_q_ptr, b, top_k, metric.metric, metric.mode, d_ids_ptr,
                                            d_keys_ptr, d_counts_ptr, stream))
 
+    def search_exact_batch(self, queries, top_k, metric):
+        """EXACT top_k over every live stored row under the same keys as search_batch (no forest needed; removed rows excluded):
+        (ids [b,k] u64, keys [b,k] u64, counts [b] u32); entries past counts[i] are 2^64-1.  The ground truth for recall."""
+        q = _f32(queries, self.dim)
+        b = q.shape[0]
+        ids = np.empty((b, top_k), np.uint64)
+        keys = np.empty((b, top_k), np.uint64)
+        counts = np.zeros(b, np.uint32)
+        check(lib().zh_search_exact_batch(self._h, _p(q), b, top_k, metric.metric, metric.mode, _p(ids), _p(keys), _p(counts)))
+        return ids, keys, counts
+
+    def search_exact(self, query, top_k, metric):
+        """the exact top_k of one query -> list of (id, distance key), ascending"""
+        ids, keys, counts = self.search_exact_batch(_f32(query).reshape(1, -1), top_k, metric)
+        n = int(counts[0])
+        return list(zip(ids[0, :n].tolist(), keys[0, :n].tolist()))
+
+    def search_exact_batch_device(self, d_q_ptr, b, top_k, metric, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream=None):
+        """search_exact_batch with queries and results already in device memory (raw pointers, e.g. torch .data_ptr())."""
+        check(lib().zh_search_exact_batch_device(self._h, d_q_ptr, b, top_k, metric.metric, metric.mode, d_ids_ptr,
+                                                 d_keys_ptr, d_counts_ptr, stream))
+
+    def exact_info(self):
+        """what the most recent exact search on this index did (zh_search_exact_info): batch, rows_live, path, redone, survivors, launches"""
+        info = _ffi.ExactInfo()
+        check(lib().zh_search_exact_info(self._h, C.byref(info)))
+        return info.as_dict()
+
     def debug_keep_raw(self, on=True):
         """tests: half-width batches keep a copy of the scan's raw pairs (zh_debug_keep_raw)"""
         check(lib().zh_debug_keep_raw(self._h, 1 if on else 0))

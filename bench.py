@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W          (N >= 1: for N > 1 this process starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W   (the same ranks, started by torchrun)
     python bench.py ... --dump-outputs DIR   (also: the last timed step's results as DIR/{ids,distances,counts}.npy, float64)
+    python bench.py ... --full               (also everything beside the headline figure: see "A plain run and --full" below)
 
 One "step" = one batch of B synthetic queries through the library: hash -> walk -> sweep -> select -> final, plus,
 for N > 1, the RCCL all-gather of every rank's packed top-k and the merge kernel (zh_shard_search_*: the exchange is
@@ -27,7 +28,15 @@ Workloads (BASELINE.json `configs`; index options from BASELINE.md s3):
   --emulate-ranks N on ONE GPU: rank 0's shard of an N-rank run (rows / N, max_node_size / N) with the exchange step
             on a one-rank RCCL communicator in the loop: the per-rank work of a series point ("per-rank, emulated").
 Batches are software-pipelined two deep: the small latency-bound kernels of batch i+1 run beside the HBM-bound sweep of
-batch i.  --no-pipeline times the blocking call.  Prints ONE JSON line on rank 0.
+batch i.  --no-pipeline times the blocking call.
+
+A plain run and --full.  A plain run does what its headline figure needs: it builds the index, warms up, times the steps, writes
+--dump-outputs and prints ONE JSON line on rank 0.  Beside `value` that line carries only what the timed steps measured themselves
+(stage times, window latency, the sweep's launch time and the roofline figures that follow from it; `unique_row_fraction` and the
+figures that need it are null).  --full adds, after the timed steps: the R_unique pass (rows a launch really loads), the planted-
+neighbour / brute-force recall runs, the host-buffer entry point, the CPU baselines, the other configurations of an N = 1 run, and
+the full record (bench_detail.json and the stdout line before the compact one).  --no-recall, --no-main-recall, --cpu-seconds,
+--recall-queries, --no-other-configs, --only-other and --sleep-before-other shape what --full adds.
 """
 import argparse
 import ctypes
@@ -194,6 +203,9 @@ def parse():
     ap.add_argument("--rows", type=int, default=None, help="override total rows (debug)")
     ap.add_argument("--max-node-size", type=int, default=None, help="override max_node_size (debug)")
     ap.add_argument("--batch", type=int, default=None, help="override the query batch (debug)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (R_unique pass, recall, host-buffer entry point, CPU "
+                         "baselines, other configurations) and write the full record; a plain run does only the timed steps")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of EACH CPU baseline leg (0 = skip)")
     ap.add_argument("--recall-queries", type=int, default=256)
     ap.add_argument("--no-recall", action="store_true")
@@ -235,6 +247,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full and (args.only_other or args.sleep_before_other):
+        ap.error("--only-other and --sleep-before-other shape the other configurations, which only --full runs")
     return args
 
 
@@ -563,23 +577,26 @@ def run_workload(env, name, S, rank, steps, warmup, exchange, recall=False, M_ov
         last = slots[0 if args.serial_windows else ((steps + WIN - 1) // WIN - 1) % (NS + LA if look["ahead"] else NS)]["res"][(steps - 1) % WIN]
     last_host = (last["h_ids"].numpy().copy(), last["h_counts"].numpy().copy(), last["h_keys"].numpy().copy())
 
-    # ---- untimed: R_unique of the timed batches (per internal batch = per window: a row shared by two batches of a window
-    # counts once, so `achieved` never exceeds what the kernel really moved) ---------------------------------------
-    ix.set_profiling(2)
-    uniq = tot = 0
-    for i in range(0 if args.profile_run else max(1, min(steps // WIN, 4))):
-        ix.stats(reset=True)
-        if pipelined:
-            begin(slots[0], warmup + i * WIN, min(WIN, steps - i * WIN))
-            finish(slots[0])
-            drain(slots[0])
-        else:
-            blocking(warmup + i)
-            torch.cuda.synchronize()
-        s2 = ix.stats()
-        uniq += s2["rows_unique"]
-        tot += s2["rows_scored"]
-    uniq_frac = uniq / max(tot, 1) if tot else 1.0
+    # ---- untimed, --full only: R_unique of the timed batches (per internal batch = per window: a row shared by two batches of a
+    # window counts once, so `achieved` never exceeds what the kernel really moved) -------------------------------------
+    # A plain run does not measure it: NaN carries through every figure that needs it, and the JSON writers print those as null.
+    uniq_frac = float("nan")
+    if args.full:
+        ix.set_profiling(2)
+        uniq = tot = 0
+        for i in range(0 if args.profile_run else max(1, min(steps // WIN, 4))):
+            ix.stats(reset=True)
+            if pipelined:
+                begin(slots[0], warmup + i * WIN, min(WIN, steps - i * WIN))
+                finish(slots[0])
+                drain(slots[0])
+            else:
+                blocking(warmup + i)
+                torch.cuda.synchronize()
+            s2 = ix.stats()
+            uniq += s2["rows_unique"]
+            tot += s2["rows_scored"]
+        uniq_frac = uniq / max(tot, 1) if tot else 1.0
     ix.set_profiling(0)
 
     # one batch's sweep is issued as several launches of the same kernel (~12 GB each): per-launch figures
@@ -817,8 +834,8 @@ def run_workload(env, name, S, rank, steps, warmup, exchange, recall=False, M_ov
 
     # sanity of the last timed batch as it arrived on the host
     assert (last_host[1] <= k).all() and (last_host[1] > 0).all(), "empty results in the last timed batch"
-    # PCIe-inclusive rate through the host-buffer entry point: reported beside, never as, `value`
-    if group is None and S == 1 and not args.profile_run:
+    # PCIe-inclusive rate through the host-buffer entry point (--full): reported beside, never as, `value`
+    if args.full and group is None and S == 1 and not args.profile_run:
         # zh_search_batch (HOST pointers, blocking: what the shim's search_batch / Database::query_vectors reaches, core.rs:290-313) with a batch of
         # four API batches' worth of host-resident queries (4096 at cfg3): the library cuts it into windows over two contexts, copies beside the
         # kernels (zh_api.hip, search_host_windows).  PCIe inclusive, pageable memory on both sides.
@@ -1062,7 +1079,7 @@ def compact_line(full, limit=LINE_LIMIT):
             "iid": _pick(rc.get("bench_data_iid") or {}, (f"recall_at_{k}", "planted_neighbour_hit_rate"))}
     if rc.get("at_this_point"):
         rsum["at_this_point"] = _pick(rc["at_this_point"], ("max_node_size_per_shard", f"recall_at_{k}", f"recall_at_{k}_reference_key", "planted_neighbour_hit_rate"))
-    optional.append(("recall", rsum))
+    optional.append(("recall", rsum if rc else None))  # (a plain run measures no recall)
     oc = {}
     for key, v in (full.get("other_configs") or {}).items():
         r = v.get("roofline") or {}
@@ -1162,12 +1179,12 @@ def main():
     S = emu or env.world
     name = args.workload or ("cfg3" if S == 1 else "scale64m")
     kind = {"clustered": 2, "clustered-shuffled": 3}.get(args.data) if WORKLOADS[name]["kind"] == 0 else None
-    will_run_others = S == 1 and env.world == 1 and not args.no_other_configs and name == "cfg3" and not args.rows
+    will_run_others = args.full and S == 1 and env.world == 1 and not args.no_other_configs and name == "cfg3" and not args.rows
     # The order of things ("order effect"): an index whose device buffers are allocated after torch's brute-force recall ran in this
     # process scans up to a third slower (the matrix-core scan; not clocks, not the TLB, not the L2 hit rate: profiles/r05_order_effect*.txt).  So the
     # TIMED runs come first -- the bench line's own workload, then the other configurations, each with only the planted-neighbour check -- and the
     # brute-force recall runs (which rebuild their small / medium indexes) after all of them.  --no-other-configs: the recall in place, as before.
-    main_recall = False if (args.no_recall or args.no_main_recall) else ("planted" if will_run_others else True)
+    main_recall = False if (not args.full or args.no_recall or args.no_main_recall) else ("planted" if will_run_others else True)
     res, ix, group, wl, M_shard = run_workload(env, name, S, env.rank if not emu else 0, args.steps, args.warmup, exchange=S > 1,
                                                recall=main_recall, M_override=args.max_node_size,
                                                rows_override=args.rows, batch_override=args.batch, kind_override=kind)
@@ -1179,7 +1196,7 @@ def main():
     if args.data == "iid":  # (the committed counters are those of the iid command)
         pmc_traffic(args, name, S, res["roofline"])
     cpu = None
-    if env.rank == 0 and S == 1 and args.cpu_seconds > 0:
+    if args.full and env.rank == 0 and S == 1 and args.cpu_seconds > 0:
         cpu = cpu_baselines(env, ix, wl, M_shard, args.cpu_seconds)
     if group is not None:
         group.close()
@@ -1288,7 +1305,7 @@ def main():
             "config": res["config"],
             "latency_ms": res.get("latency_ms"),
             "half_width_scan": res.get("half_width_scan"),
-            "recall": None,  # filled below
+            "recall": None,  # filled below (--full)
             f"recall_at_{k}": res.get(f"recall_at_{k}"), f"recall_at_{k}_reference_key": res.get(f"recall_at_{k}_reference_key"),
             "planted_neighbour_hit_rate": res.get("planted_neighbour_hit_rate"),
             "roofline": res["roofline"], "cpu_baseline": cpu[1] if cpu else None, "cpu_baseline_bitexact": cpu[0] if cpu else None,
@@ -1308,30 +1325,31 @@ def main():
             out["preflight"] = res["preflight"]
         if other is not None:
             out["other_configs"] = other
-        # BASELINE's metric is "queries/sec + recall@k": the recall that says something first.  On the bench line's iid ~N(0,1)
-        # rows in 768-d every non-planted neighbour is indistinguishable from a random row, so recall@k against brute force is
-        # ~(rows scanned / rows) for ANY index -- the planted neighbour (query = stored row + 0.3 noise) is the informative part
-        # there; on clustered rows (same shape, same speed) recall@k itself is informative.
-        rc = (other or {}).get("recall_clustered") or {}
-        cos_literal = wl["metric"] == "cosine"
-        out["recall"] = {
-            "informative": {"data": "clustered rows (128 consecutive rows share a centre), cfg3 shape", f"recall_at_{k}": rc.get("recall_at_100") if k == 100 else None,
-                            "planted_neighbour_hit_rate": rc.get("planted_neighbour_hit_rate"), "queries_per_s": rc.get("queries_per_s_this_gpu")}
-            if rc else None,
-            "bench_data_iid": {f"recall_at_{k}": res.get(f"recall_at_{k}"), "planted_neighbour_hit_rate": res.get("planted_neighbour_hit_rate"),
-                               "note": "iid Gaussian rows: recall@k vs brute force is uninformative by construction (see comment in bench.py); "
-                                       "the planted neighbour is what an index can find"},
-            "cosine_key_note": ("this workload's metric is cosine with the reference's LITERAL key (distance.rs:23-25 sorts by similarity, SURVEY F4): "
-                                f"recall_at_{k}_reference_key is ~0 by construction; recall_at_{k} is measured with the corrected key, same cost")
-            if cos_literal else ("the bench line's own workload is L2; the metric's cosine top-10 shape is measured under both keys in "
-                                 "other_configs.cfg4_one_of_8_shards.recall_at_10 and other_configs.scale64m_n1.recall_at_10 (corrected key: cosine "
-                                 "distance; reference key: distance.rs:23-25 sorts by SIMILARITY, recall ~0 by construction, SURVEY F4)"),
-        }
-        if S > 1 or emu:
-            out["recall"]["at_this_point"] = {"max_node_size_per_shard": M_shard, f"recall_at_{k}": res.get(f"recall_at_{k}"),
-                                              f"recall_at_{k}_reference_key": res.get(f"recall_at_{k}_reference_key"),
-                                              "planted_neighbour_hit_rate": res.get("planted_neighbour_hit_rate"), "data": args.data,
-                                              "note": res.get("recall_note")}
+        if args.full:  # (a plain run measures no recall)
+            # BASELINE's metric is "queries/sec + recall@k": the recall that says something first.  On the bench line's iid ~N(0,1)
+            # rows in 768-d every non-planted neighbour is indistinguishable from a random row, so recall@k against brute force is
+            # ~(rows scanned / rows) for ANY index -- the planted neighbour (query = stored row + 0.3 noise) is the informative part
+            # there; on clustered rows (same shape, same speed) recall@k itself is informative.
+            rc = (other or {}).get("recall_clustered") or {}
+            cos_literal = wl["metric"] == "cosine"
+            out["recall"] = {
+                "informative": {"data": "clustered rows (128 consecutive rows share a centre), cfg3 shape", f"recall_at_{k}": rc.get("recall_at_100") if k == 100 else None,
+                                "planted_neighbour_hit_rate": rc.get("planted_neighbour_hit_rate"), "queries_per_s": rc.get("queries_per_s_this_gpu")}
+                if rc else None,
+                "bench_data_iid": {f"recall_at_{k}": res.get(f"recall_at_{k}"), "planted_neighbour_hit_rate": res.get("planted_neighbour_hit_rate"),
+                                   "note": "iid Gaussian rows: recall@k vs brute force is uninformative by construction (see comment in bench.py); "
+                                           "the planted neighbour is what an index can find"},
+                "cosine_key_note": ("this workload's metric is cosine with the reference's LITERAL key (distance.rs:23-25 sorts by similarity, SURVEY F4): "
+                                    f"recall_at_{k}_reference_key is ~0 by construction; recall_at_{k} is measured with the corrected key, same cost")
+                if cos_literal else ("the bench line's own workload is L2; the metric's cosine top-10 shape is measured under both keys in "
+                                     "other_configs.cfg4_one_of_8_shards.recall_at_10 and other_configs.scale64m_n1.recall_at_10 (corrected key: cosine "
+                                     "distance; reference key: distance.rs:23-25 sorts by SIMILARITY, recall ~0 by construction, SURVEY F4)"),
+            }
+            if S > 1 or emu:
+                out["recall"]["at_this_point"] = {"max_node_size_per_shard": M_shard, f"recall_at_{k}": res.get(f"recall_at_{k}"),
+                                                  f"recall_at_{k}_reference_key": res.get(f"recall_at_{k}_reference_key"),
+                                                  "planted_neighbour_hit_rate": res.get("planted_neighbour_hit_rate"), "data": args.data,
+                                                  "note": res.get("recall_note")}
     # RCCL writes a version banner through C stdio: every rank flushes it before the last barrier, so that rank 0's JSON
     # line is the LAST line of the job's stdout
     sys.stdout.flush()
@@ -1342,10 +1360,11 @@ def main():
         ctypes.CDLL(None).fflush(None)
     if env.rank == 0:
         out["prefilter_dtype"] = prefilter_dtype_of(out["roofline"])
-        doc, where = write_detail(out)
-        out["detail"] = ", ".join(where) + "; also the stdout line before this one"
-        # the full record first (one line, any length), the COMPACT record last: the driver parses the last line of stdout
-        print(json.dumps({"bench_detail": json.loads(doc)}, allow_nan=False), flush=True)
+        if args.full:
+            doc, where = write_detail(out)
+            out["detail"] = ", ".join(where) + "; also the stdout line before this one"
+            # the full record first (one line, any length), the COMPACT record last: the driver parses the last line of stdout
+            print(json.dumps({"bench_detail": json.loads(doc)}, allow_nan=False), flush=True)
         print(compact_line(out), flush=True)
 
 

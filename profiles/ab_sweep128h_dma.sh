@@ -5,5 +5,5 @@ fmt='import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r
 for v in 0 1 0 1; do
   if [ $v = 1 ]; then export ZH_S128H_DMA=1; else unset ZH_S128H_DMA; fi
   echo -n "ZH_S128H_DMA=$v: "
-  python bench.py --workload cfg5 --emulate-ranks 8 --steps 8 --cpu-seconds 0 --no-recall --no-other-configs 2>/dev/null | python -c "$fmt"
+  python bench.py --full --workload cfg5 --emulate-ranks 8 --steps 8 --cpu-seconds 0 --no-recall --no-other-configs 2>/dev/null | python -c "$fmt"
 done

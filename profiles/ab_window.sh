@@ -7,7 +7,7 @@ for g in g2 g4; do
   cp gpurun_ab/libzebra_hip_$g.so zebra_amd/lib/libzebra_hip.so
   for w in 1 2 4; do
     echo -n "$wl $g window $w: "
-    python bench.py --workload $wl --window $w --steps 24 --warmup 4 --cpu-seconds 0 --no-recall --no-other-configs 2>/dev/null | python -c "$fmt"
+    python bench.py --full --workload $wl --window $w --steps 24 --warmup 4 --cpu-seconds 0 --no-recall --no-other-configs 2>/dev/null | python -c "$fmt"
   done
 done; done
 cp gpurun_ab/libzebra_hip_g4.so zebra_amd/lib/libzebra_hip.so

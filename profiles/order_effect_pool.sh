@@ -13,7 +13,7 @@ out=gpurun_out/order_effect_pool.txt
 for pool in 1 0 1 0; do
   for order in cfg2,cfg4_one_of_8_shards cfg4_one_of_8_shards,cfg2; do
     echo "== ZH_POOL=$pool  main cfg3, then $order (no recall runs)" | tee -a $out
-    ZH_POOL=$pool bash profiles/run_checked.sh gpurun_out/order_pool timeout -k 10 300 python bench.py --steps 4 --warmup 2 --cpu-seconds 0 --no-recall --only-other $order || { echo FAILED | tee -a $out; tail -3 gpurun_out/order_pool.err | tee -a $out; exit 1; }
-    python3 -c "$fmt" < gpurun_out/order_pool.out 2>&1 | tee -a $out
+    ZH_POOL=$pool bash profiles/run_checked.sh "${out%.txt}_run" timeout -k 10 300 python bench.py --full --steps 4 --warmup 2 --cpu-seconds 0 --no-recall --only-other $order || { echo FAILED | tee -a $out; tail -3 "${out%.txt}_run.err" | tee -a $out; exit 1; }
+    python3 -c "$fmt" < "${out%.txt}_run.out" 2>&1 | tee -a $out
   done
 done

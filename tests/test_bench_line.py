@@ -1,7 +1,7 @@
 """The line the driver parses (round 4's final stdout line was 25.9 KB and BENCH_r04.json has `parsed: null`).
 bench.compact_line on a canned full record -- round 4's own 25.9-KB record, committed under profiles/ -- must give one
 strictly-JSON object below the limit that still carries the contract's keys, `roofline` and `cpu_baseline`.
-Also the --dump-outputs writer (bench.dump_outputs).  CPU only."""
+Also the line of a plain run (no --full), the option checks and the --dump-outputs writer (bench.dump_outputs).  CPU only."""
 import json
 import os
 import sys
@@ -60,6 +60,36 @@ def test_non_finite_values_and_oversized_parts():
     assert j["roofline"]["frac"] is None and j["roofline"]["traffic"] is None
     assert "other_configs" in j["dropped_for_length"] and "other_configs" not in j
     assert len(j["cpu_baseline"]["sample"]) <= 400
+
+
+def test_compact_line_of_a_plain_run():
+    """a run without --full: no R_unique pass (NaN through the figures that need it), no recall, CPU baselines, host-buffer leg or
+    other configurations -- the line still carries the contract's keys, the timed run's own roofline figures, and no empty parts"""
+    import bench
+    full = _canned()
+    for key in ("other_configs", "recall", "host_buffers", "host_buffers_qps", "cpu_baseline_bitexact", "detail"):
+        full.pop(key, None)
+    full["cpu_baseline"] = None
+    full["roofline"]["unique_row_fraction"] = float("nan")
+    full["roofline"]["s8d_equivalent_GBps"] = float("nan")
+    j = _check(bench.compact_line(full))
+    assert j["value"] == float("%.6g" % full["value"]) and j["ms_per_step"] == float("%.6g" % full["ms_per_step"])
+    assert j["roofline"]["unique_row_fraction"] is None and j["roofline"]["launch_ms"] > 0 and j["roofline"]["frac"] > 0
+    assert j["cpu_baseline"] is None and j["host_buffers_qps"] is None
+    assert "recall" not in j and "other_configs" not in j and "dropped_for_length" not in j
+
+
+def test_full_is_off_by_default_and_other_configs_need_it(monkeypatch):
+    import pytest
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "4", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--only-other", "cfg2"])
+    assert bench.parse().full is True
+    for extra in (["--only-other", "cfg2"], ["--sleep-before-other", "5"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + extra)
+        with pytest.raises(SystemExit):
+            bench.parse()
 
 
 def test_detail_record_is_strict_json(tmp_path, monkeypatch):

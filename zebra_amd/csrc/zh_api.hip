@@ -1645,6 +1645,8 @@ static int ensure_row_half(zh_index *ix, bool *ok) {
         *ok = true;
         return ZH_OK;
     }
+    // a copy that was released (the meta-only state, or no room at all) holds none of the rows scale_rows speaks of: made again from row 0
+    const bool had_copy = ix->row_half.p && ix->row_meta.p;
     if (ix->row_half.ensure(std::max<uint64_t>(tiles, 1) * 16 * d * 2, true, ix->stream) != ZH_OK ||
         ix->row_meta.ensure(std::max<uint64_t>(tiles, 1) * 16 * sizeof(float2), true, ix->stream) != ZH_OK || ix->row_rho_dev.ensure(4) != ZH_OK) {
         ix->row_half.release(); ix->row_meta.release();
@@ -1660,7 +1662,7 @@ static int ensure_row_half(zh_index *ix, bool *ok) {
     // rows appended since the order was made keep position = id and share no tile with their leaf mates: once they are a quarter of the table
     // the copy is made again, in an order measured on all of it
     const bool stale_order = ix->perm_rows && ix->n_rows - ix->perm_rows > ix->perm_rows / 4;
-    if (ix->scale_gen != ix->rows_gen || from > ix->n_rows || stale_order) {
+    if (!had_copy || ix->scale_gen != ix->rows_gen || from > ix->n_rows || stale_order) {
         from = 0;
         HIPCHK(hipMemsetAsync(ix->row_rho_dev.p, 0, 4, ix->stream));
     }

@@ -1,4 +1,4 @@
-/* Plain C99 user of the C ABI (include/zebra_hip.h): insert vectors, search a batch, grow the index, remove.
+/* Plain C99 user of the C ABI (include/zebra_hip.h): insert vectors, search a batch, grow the index, remove, compact.
  *   gcc -std=c99 -Iinclude examples/search_example.c -Lzebra_amd/lib -lzebra_hip -Wl,-rpath,$PWD/zebra_amd/lib -o /tmp/ex && /tmp/ex
  * Mirrors what Database::insert_records / query_vectors do in the reference (src/database/core.rs:245-254, 290-313). */
 #include <stdio.h>
@@ -47,6 +47,26 @@ int main(void) {
     printf("deduplicate removed %zu, remove found [%d %d], %llu vectors left\n", removed, found[0], found[1],
            (unsigned long long)zh_index_count(idx));
     int ok = hits == B && removed == 100 && found[0] == 1 && found[1] == 0 && zh_index_count(idx) == (uint64_t)N - 1;
+
+    /* the 101 removed vectors still occupy device memory: compact, and the neighbours' ids follow the returned old -> new map */
+    uint64_t ids2[B * K], keys2[B * K];
+    uint32_t counts2[B];
+    CHECK(zh_search_batch(idx, q, B, K, ZH_L2SQ, 0, ids, keys, counts));
+    uint64_t stored = zh_index_stored_rows(idx);
+    uint64_t *new_ids = malloc(sizeof(uint64_t) * stored);
+    zh_compact_info ci;
+    CHECK(zh_index_compact(idx, new_ids, stored, &ci));
+    CHECK(zh_search_batch(idx, q, B, K, ZH_L2SQ, 0, ids2, keys2, counts2));
+    int follow = 1;
+    for (int b = 0; b < B; b++) {
+        follow &= counts2[b] == counts[b];
+        for (uint32_t j = 0; j < counts[b] && follow; j++) follow &= ids2[b * K + j] == new_ids[ids[b * K + j]] && keys2[b * K + j] == keys[b * K + j];
+    }
+    printf("compact: %llu -> %llu stored rows, %llu moved in %.3f ms; neighbours %s the id map\n", (unsigned long long)ci.rows_before,
+           (unsigned long long)ci.rows_after, (unsigned long long)ci.rows_moved, ci.ms, follow ? "follow" : "DO NOT follow");
+    ok = ok && follow && ci.rows_before == (uint64_t)N + 100 && ci.rows_after == (uint64_t)N - 1 && zh_index_stored_rows(idx) == (uint64_t)N - 1 &&
+         new_ids[997] == UINT64_MAX && new_ids[998] == 997;
+    free(new_ids);
     zh_index_destroy(idx);
     free(rows);
     free(q);

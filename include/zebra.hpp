@@ -184,6 +184,13 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         out.resize(n < out.size() ? n : out.size());
         return out;
     }
+    // (new) zh_index_compact: the device memory of removed vectors is reclaimed in place -> for every OLD local row its new id, or
+    // UINT64_MAX for a removed one (stable: strictly increasing on the live rows); every later call answers as before under that map
+    std::vector<Id> compact(zh_compact_info *info = nullptr) const {
+        std::vector<Id> new_ids(zh_index_stored_rows(h_.get()));
+        check(zh_index_compact(h_.get(), new_ids.data(), new_ids.size(), info));
+        return new_ids;
+    }
 
     // lsh.rs:544-565: approximate k nearest neighbours, ascending by (distance key, id)
     template <class Met>
@@ -248,6 +255,16 @@ class Database {
     }
     void deduplicate() {
         for (Id i : index.deduplicate()) documents_.erase(i);
+    }
+    // (new) compact the index and re-key the documents with the old -> new id map
+    void compact() {
+        const Id base = zh_index_id_base(index.handle());
+        const std::vector<Id> new_ids = index.compact();
+        std::map<Id, std::string> docs;
+        for (auto &kv : documents_)
+            if (kv.first >= base && kv.first - base < new_ids.size() && new_ids[kv.first - base] != ~Id(0))
+                docs[new_ids[kv.first - base]] = std::move(kv.second);
+        documents_.swap(docs);
     }
     void clear_database() {
         index.clear();

@@ -18,6 +18,8 @@
  *   zh_index_count / zh_index_num_trees  LSHIndex::no_vectors / no_trees / is_empty  lsh.rs:389-409
  *   zh_index_clear                       LSHIndex::clear          src/database/index/lsh.rs:506-529
  *   zh_index_remove / zh_index_deduplicate  LSHIndex::remove / deduplicate  src/database/index/lsh.rs:473-503, 270-288
+ *   zh_index_compact                     (new) what the reference's store does by itself after lsh.rs:495: the device memory of removed
+ *                                        rows is reclaimed in place, ids are renumbered under a returned old -> new map
  *   zh_shard_group_* / zh_shard_search_* (new) the loop of Database::query_vectors (src/database/core.rs:299-303) over an index
  *                                        whose rows are sharded across GPUs (README.md:31 "can be sharded"): local search on
  *                                        this rank's shard, ONE RCCL all-gather of the packed top-k, merge on every rank
@@ -214,6 +216,47 @@ ZH_API int zh_index_build(zh_index *idx); /* (re)build all trees on the GPU */
 ZH_API int zh_index_remove(zh_index *idx, const uint64_t *ids, size_t n, uint8_t *out_found, size_t *out_n_removed);
 ZH_API int zh_index_deduplicate(zh_index *idx, uint64_t *out_ids, size_t cap, size_t *out_n_removed);
 
+/* Compaction (new; the reference's store deletes a removed embedding, lsh.rs:495, and compacts by itself): remove / deduplicate only take ids
+ * out of the trees -- the vectors stay in device memory, and every kernel that streams the table by position still streams them.  This call
+ * moves the live rows down over the removed ones, IN PLACE and in their order (stable), renumbers the forest's leaf ids, and makes the live
+ * count the stored count.  Rows keep their relative order, so the old -> new map is strictly increasing on the live rows: a compacted index
+ * answers every later call as the uncompacted one would, under that map -- ids, keys, counts, later splits and rebuilds (the hyperplane sampler
+ * draws the i-th LIVE row, which is new row i).  Nothing compacts by itself.
+ *   - Needs external exclusion like add / build / remove; pipelined contexts must be idle.  Contexts and shard groups made before the call
+ *     stay usable.  ZH_ESTATE on an index whose last add failed half way.  With nothing removed: a no-op that returns the identity map and
+ *     releases nothing.
+ *   - The f32 table keeps its capacity (capacity_rows): later appends reuse the freed tail.  The derived copies of the rows (the fp16 tiles and
+ *     their per-row scales, the 128-d half / byte copy, the scan's row order and row -> leaf tables) are released and re-made at the new size
+ *     by the next batch that wants them.
+ *   - Rows move in stream-ordered chunks: a chunk whose destination ends at or before its source begins is copied directly, any other one
+ *     through a bounce buffer.  Device scratch (released before return): scratch_bytes <= ZH_COMPACT_BOUNCE_BYTES + 4.25 * rows_before + 4096
+ *     -- the bounce buffer, 4 bytes per stored row for the ranks, a bit per row, block sums.  ZH_COMPACT_CHUNK_ROWS (environment, read per
+ *     call; tests) sets the rows per chunk, at most what the bounce buffer holds.
+ *   - A forest injected with zh_index_set_forest that lists a row twice in one tree may still list a removed row: ZH_EUNSUPPORTED (rebuild it).
+ *   - A device failure after rows have begun to move leaves the table inconsistent: every call that reads or adds rows (add / append* /
+ *     build / remove / deduplicate / read_rows / hash_signs / search / exact search / compact) then fails with ZH_ESTATE until zh_index_clear.
+ *   - Speed of later searches: answers are the same, the path to them may not be.  A forest whose plane was made from a row that has been
+ *     removed loses the row-score hash and the prefilter on top of it (zh_set_hash_mode / zh_set_sweep_mode) when it is compacted -- the
+ *     sample row's score no longer exists -- and hashes with one dot product per plane until zh_index_build; zh_stats_t::hash_from_scores
+ *     shows it.  The table scans and sweeps get shorter by the removed share.
+ *   - info->ms is the device work only; the call also spends host time proportional to the stored rows (the live bitmap, the chunk plan,
+ *     and, when out_new_ids is given, 4 bytes per row back from the device).
+ * out_new_ids (may be NULL; else cap >= rows_before, ZH_EINVAL otherwise): for every OLD local row r, out_new_ids[r] = id_base + new row, or
+ * UINT64_MAX if r had been removed.  info may be NULL. */
+#define ZH_COMPACT_BOUNCE_BYTES (256u << 20)
+typedef struct zh_compact_info {
+    uint64_t rows_before;     /* stored rows (live + removed) before the call */
+    uint64_t rows_after;      /* = live rows = zh_index_count, before and after */
+    uint64_t rows_moved;      /* live rows whose position changed (0: nothing was removed, or only a tail) */
+    uint64_t bytes_moved;     /* bytes the move read + wrote in device memory (bounce copies counted) */
+    uint64_t scratch_bytes;   /* peak device scratch the call allocated (released before it returns) */
+    uint64_t capacity_rows;   /* rows the f32 table has room for after the call (kept: later appends reuse it) */
+    uint64_t copy_bytes_released; /* zh_stats_t::row_copy_bytes before the call: the fp16 / byte copies and the scan's order, let go and re-made at
+                                   * the new size on next use (the smaller per-row tables -- norms, row -> leaf, live lists -- go too, uncounted) */
+    double   ms;              /* hipEvent time of the device work, on the index's stream */
+} zh_compact_info;
+ZH_API int zh_index_compact(zh_index *idx, uint64_t *out_new_ids, size_t cap, zh_compact_info *info);
+
 /* ---- forest exchange (parity tests inject / extract the exact same forest) ----------------- */
 ZH_API int zh_index_set_forest(zh_index *idx, const zh_forest_view *forest);
 ZH_API int zh_index_forest_sizes(zh_index *idx, zh_forest_sizes *out);
@@ -224,6 +267,8 @@ ZH_API int zh_index_get_forest(zh_index *idx, int32_t *plane, int32_t *left, int
 /* ---- queries -------------------------------------------------------------------------------- */
 ZH_API uint64_t zh_index_count(const zh_index *idx);     /* stored vectors (0 <=> no_vectors) */
 ZH_API uint32_t zh_index_num_trees(const zh_index *idx); /* built trees    (0 <=> no_trees)   */
+ZH_API uint64_t zh_index_stored_rows(const zh_index *idx); /* rows the table holds, live + removed (= zh_index_count after zh_index_compact):
+                                                            * the next row's local number, and the length of zh_index_compact's map */
 ZH_API uint32_t zh_index_dim(const zh_index *idx);
 ZH_API int32_t zh_index_device(const zh_index *idx);     /* HIP device ordinal the index lives on */
 ZH_API uint64_t zh_index_id_base(const zh_index *idx);

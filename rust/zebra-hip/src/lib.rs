@@ -108,6 +108,19 @@ pub mod ffi {
         pub launches: u64,
     }
 
+    #[repr(C)]
+    #[derive(Default, Clone, Copy, Debug)]
+    pub struct zh_compact_info {
+        pub rows_before: u64,
+        pub rows_after: u64,
+        pub rows_moved: u64,
+        pub bytes_moved: u64,
+        pub scratch_bytes: u64,
+        pub capacity_rows: u64,
+        pub copy_bytes_released: u64,
+        pub ms: f64,
+    }
+
     pub const ZH_COSINE: c_int = 0;
     pub const ZH_L2SQ: c_int = 1;
     pub const ZH_L2: c_int = 2;
@@ -132,7 +145,9 @@ pub mod ffi {
         pub fn zh_index_build(idx: *mut zh_index) -> c_int;
         pub fn zh_index_remove(idx: *mut zh_index, ids: *const u64, n: usize, out_found: *mut u8, out_n_removed: *mut usize) -> c_int;
         pub fn zh_index_deduplicate(idx: *mut zh_index, out_ids: *mut u64, cap: usize, out_n_removed: *mut usize) -> c_int;
+        pub fn zh_index_compact(idx: *mut zh_index, out_new_ids: *mut u64, cap: usize, info: *mut zh_compact_info) -> c_int;
         pub fn zh_index_count(idx: *const zh_index) -> u64;
+        pub fn zh_index_stored_rows(idx: *const zh_index) -> u64;
         pub fn zh_index_num_trees(idx: *const zh_index) -> u32;
         pub fn zh_search_batch(idx: *mut zh_index, q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
                                out_ids: *mut u64, out_keys: *mut u64, out_counts: *mut u32) -> c_int;
@@ -406,6 +421,29 @@ impl<const N: usize> LSHIndex<N> {
         Ok(out[..n.min(cap)].iter().map(|r| t.of_row[*r as usize]).collect())
     }
 
+    /// (new) zh_index_compact: the device memory of removed vectors is reclaimed in place.  The library renumbers its rows (stable: live
+    /// rows keep their order) and returns old row -> new row; the row <-> Uuid table is rewritten with it, so Uuids never change and every
+    /// later call answers as before.  Removed vectors' Uuids leave the table.  Needs the exclusion of `add`.
+    pub fn compact(&self) -> anyhow::Result<ffi::zh_compact_info> {
+        let mut t = self.ids.write().unwrap(); // rows are renumbered: hold the table across the call
+        let n = unsafe { ffi::zh_index_stored_rows(self.hip.0) } as usize;
+        let mut new_ids = vec![u64::MAX; n];
+        let mut info = unsafe { std::mem::zeroed::<ffi::zh_compact_info>() };
+        check(unsafe { ffi::zh_index_compact(self.hip.0, new_ids.as_mut_ptr(), n, &mut info) })?;
+        let mut of_row = Vec::with_capacity(info.rows_after as usize);
+        let mut row_of = HashMap::with_capacity(info.rows_after as usize);
+        for (old, new) in new_ids.iter().enumerate() {
+            if *new != u64::MAX {
+                debug_assert_eq!(*new as usize, of_row.len()); // the map is strictly increasing on live rows (id_base is 0 here)
+                row_of.insert(t.of_row[old], *new);
+                of_row.push(t.of_row[old]);
+            }
+        }
+        t.of_row = of_row;
+        t.row_of = row_of;
+        Ok(info)
+    }
+
     /// lsh.rs:506-529
     pub fn clear(&self) -> anyhow::Result<()> {
         let mut t = self.ids.write().unwrap();
@@ -471,6 +509,11 @@ impl<
             results.insert(idx, docs);
         }
         Ok(results)
+    }
+
+    /// (new) reclaim the device memory of removed vectors; documents are keyed by Uuid and stay as they are
+    pub fn compact(&self) -> anyhow::Result<()> {
+        self.index.compact().map(|_| ())
     }
 
     /// core.rs:205-214

@@ -85,6 +85,16 @@ class ExactInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CompactInfo(C.Structure):
+    _fields_ = [("rows_before", C.c_uint64), ("rows_after", C.c_uint64), ("rows_moved", C.c_uint64), ("bytes_moved", C.c_uint64),
+                ("scratch_bytes", C.c_uint64), ("capacity_rows", C.c_uint64), ("copy_bytes_released", C.c_uint64), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+COMPACT_BOUNCE_BYTES = 256 << 20  # ZH_COMPACT_BOUNCE_BYTES
+
 # every symbol include/zebra_hip.h declares: (name, restype, argtypes)
 _vp, _u64, _u32, _sz, _i = C.c_void_p, C.c_uint64, C.c_uint32, C.c_size_t, C.c_int
 SYMBOLS = [
@@ -99,11 +109,13 @@ SYMBOLS = [
     ("zh_index_build", _i, [_vp]),
     ("zh_index_remove", _i, [_vp, _vp, _sz, _vp, _vp]),
     ("zh_index_deduplicate", _i, [_vp, _vp, _sz, _vp]),
+    ("zh_index_compact", _i, [_vp, _vp, _sz, _vp]),
     ("zh_index_set_forest", _i, [_vp, _vp]),
     ("zh_index_forest_sizes", _i, [_vp, _vp]),
     ("zh_index_get_forest", _i, [_vp] * 8),
     ("zh_index_count", _u64, [_vp]),
     ("zh_index_num_trees", _u32, [_vp]),
+    ("zh_index_stored_rows", _u64, [_vp]),
     ("zh_index_dim", _u32, [_vp]),
     ("zh_index_device", C.c_int32, [_vp]),
     ("zh_index_id_base", _u64, [_vp]),

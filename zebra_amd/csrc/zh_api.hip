@@ -260,6 +260,7 @@ struct zh_index {
     zh_exact_info ex_info{};  // (stats_mu)
 
     bool broken = false;  // an incremental add failed half way: trees are stale until zh_index_build
+    bool rows_torn = false;  // ... or a compaction failed after rows had begun to move (set with broken): the TABLE is inconsistent until zh_index_clear
     int dense_levels = -1;
     bool debug_keep_raw = false;  // zh_debug_keep_raw
     std::atomic<int> sweep_mode{0};  // zh_set_sweep_mode (atomic: set by one thread while pipelined contexts read it per batch): 0 cost model (prefilter where the batch has row scores), 1 leaf-major, 2 table scan (exact), 3 = 0, 4 table scan with half-width queries wherever it applies, 5 = 4 with the VALU kernel only (no fp16 copy of the rows)
@@ -343,6 +344,8 @@ struct zh_index {
     Lane lanes[1];
 };
 
+static const char *const k_torn_msg = "an earlier zh_index_compact failed after rows had begun to move: the stored rows are inconsistent; "
+                                      "zh_index_clear the index and store them again";
 static int set_device(const zh_index *ix) {
     hipError_t e = hipSetDevice(ix->device);
     if (e != hipSuccess) return fail(ZH_EHIP, "hipSetDevice(%d): %s", ix->device, hipGetErrorString(e));
@@ -513,7 +516,7 @@ extern "C" int zh_index_clear(zh_index *ix) {
     if (rc) return rc;
     hipStreamSynchronize(ix->stream);
     free_forest(ix);
-    ix->broken = false;
+    ix->broken = false; ix->rows_torn = false;
     ix->n_rows = 0;
     ix->h_dead.clear();
     ix->n_dead = 0;
@@ -534,6 +537,7 @@ extern "C" int zh_index_clear(zh_index *ix) {
 
 extern "C" uint64_t zh_index_count(const zh_index *ix) { return ix ? ix->n_rows - ix->n_dead : 0; }
 extern "C" uint32_t zh_index_num_trees(const zh_index *ix) { return ix ? ix->n_trees : 0; }
+extern "C" uint64_t zh_index_stored_rows(const zh_index *ix) { return ix ? ix->n_rows : 0; }
 extern "C" uint32_t zh_index_dim(const zh_index *ix) { return ix ? ix->opt.dim : 0; }
 extern "C" int32_t zh_index_device(const zh_index *ix) { return ix ? ix->device : -1; }
 extern "C" uint64_t zh_index_id_base(const zh_index *ix) { return ix ? ix->opt.id_base : 0; }
@@ -552,6 +556,7 @@ static int grow_rows(zh_index *ix, size_t n_more) {
 static int append_locked(zh_index *ix, const float *rows, size_t n, uint64_t *out_ids) {
     int rc = set_device(ix);
     if (rc) return rc;
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
     if ((rc = grow_rows(ix, n))) return rc;
     if (n) {
         HIPCHK(hipMemcpyAsync(ix->X.as<float>() + (size_t)ix->n_rows * ix->opt.dim, rows,
@@ -573,6 +578,7 @@ extern "C" int zh_index_read_rows(zh_index *ix, uint64_t first, size_t n, float 
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     int rc = set_device(ix);
     if (rc) return rc;
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
     if (first + n > ix->n_rows) return fail(ZH_EINVAL, "zh_index_read_rows: rows [%llu, %llu) out of range (%llu stored)",
                                             (unsigned long long)first, (unsigned long long)(first + n), (unsigned long long)ix->n_rows);
     if (n) HIPCHK(hipMemcpy(out, ix->X.as<float>() + (size_t)first * ix->opt.dim, n * ix->opt.dim * sizeof(float), hipMemcpyDeviceToHost));
@@ -584,6 +590,7 @@ extern "C" int zh_index_append_device(zh_index *ix, const float *d_rows, size_t 
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     int rc = set_device(ix);
     if (rc) return rc;
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
     if ((rc = grow_rows(ix, n))) return rc;
     if (n) {
         HIPCHK(hipMemcpyAsync(ix->X.as<float>() + (size_t)ix->n_rows * ix->opt.dim, d_rows,
@@ -599,6 +606,7 @@ extern "C" int zh_index_append_synthetic(zh_index *ix, size_t n, uint64_t seed, 
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     int rc = set_device(ix);
     if (rc) return rc;
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
     if ((rc = grow_rows(ix, n))) return rc;
     HIPCHK(zh_launch_synth_rows(ix->X.as<float>() + (size_t)ix->n_rows * ix->opt.dim, n, ix->opt.dim, seed, first_row,
                                 kind, ix->stream));
@@ -1054,6 +1062,7 @@ extern "C" int zh_index_build(zh_index *ix) {
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     int rc = set_device(ix);
     if (rc) return rc;
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
     return build_forest_locked(ix);
 }
 
@@ -1061,6 +1070,7 @@ extern "C" int zh_index_add(zh_index *ix, const float *rows, size_t n, uint64_t 
     if (!ix || (!rows && n)) return fail(ZH_EINVAL, "zh_index_add: null argument");
     if (ix->opt.max_node_size == 0) return fail(ZH_EINVAL, "max_node_size must be >= 1");
     std::unique_lock<std::shared_mutex> lk(ix->mu);  // one critical section: state is read, rows stored and trees updated under it
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
     if (ix->broken) return fail(ZH_ESTATE, "an earlier add failed half way: call zh_index_build before adding or searching");
     const bool had_trees = ix->n_trees != 0;  // lsh.rs:441: no_trees() decides between build_index and insert
     const uint64_t n_prev = ix->n_rows;
@@ -1155,6 +1165,7 @@ extern "C" int zh_index_remove(zh_index *ix, const uint64_t *ids, size_t n, uint
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     int rc = set_device(ix);
     if (rc) return rc;
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
     std::vector<uint32_t> rows;
     std::vector<size_t> where;
     std::vector<uint8_t> seen(ix->n_rows, 0);
@@ -1183,6 +1194,7 @@ extern "C" int zh_index_deduplicate(zh_index *ix, uint64_t *out_ids, size_t cap,
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     int rc = set_device(ix);
     if (rc) return rc;
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
     const uint64_t N = ix->n_rows;
     const uint32_t d = ix->opt.dim;
     if (out_n_removed) *out_n_removed = 0;
@@ -1246,6 +1258,159 @@ extern "C" int zh_index_deduplicate(zh_index *ix, uint64_t *out_ids, size_t cap,
         cnt++;
     }
     if (out_n_removed) *out_n_removed = cnt;
+    return ZH_OK;
+}
+
+// zh_index_compact: the live rows move down over the removed ones, in place and in their order; everything that names a row is renumbered.
+// Steps: (1) rank -- new_row[r] for every old row, from the live bitmap (zh_compact.hip); (2) the move, in stream-ordered chunks of old rows
+// [a, b): the chunk's live rows go to [new(a), new(b)).  new(r) <= r, so a chunk whose destination ends at or before its source begins
+// (new(b) <= a) is one launch that reads and writes disjoint ranges; any other chunk is gathered into the bounce buffer first and copied to its
+// destination by a second launch.  Either way a chunk writes below new(b) <= b only: never into the source of a LATER chunk, and the stream
+// runs the chunks in order.  Rows before the first removed row stay where they are.  (3) leaf_ids and the planes' sample rows through new_row.
+// (4) the host's view: counts, generations, and every derived copy of the rows let go (re-made at the new size by the batch that next wants it).
+extern "C" int zh_index_compact(zh_index *ix, uint64_t *out_new_ids, size_t cap, zh_compact_info *info) {
+    if (!ix) return fail(ZH_EINVAL, "null index");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc = set_device(ix);
+    if (rc) return rc;
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
+    if (ix->broken) return fail(ZH_ESTATE, "an earlier add failed half way: call zh_index_build before compacting");
+    const uint64_t N = ix->n_rows, NL = N - ix->n_dead, id_base = ix->opt.id_base;
+    const uint32_t d = ix->opt.dim;
+    const size_t row_bytes = (size_t)d * sizeof(float);
+    if (out_new_ids && cap < N)
+        return fail(ZH_EINVAL, "zh_index_compact: out_new_ids holds %zu entries, %llu rows are stored", cap, (unsigned long long)N);
+    zh_compact_info ci{};
+    ci.rows_before = N; ci.rows_after = NL; ci.capacity_rows = ix->X.cap / row_bytes;
+    if (ix->n_dead == 0) {  // nothing to reclaim: no generation moves, no copy is released
+        if (out_new_ids) for (uint64_t r = 0; r < N; r++) out_new_ids[r] = id_base + r;
+        if (info) *info = ci;
+        return ZH_OK;
+    }
+    if (ix->scan_unsafe)
+        return fail(ZH_EUNSUPPORTED, "zh_index_compact: the injected forest lists a row twice in one tree and may still list a removed row; rebuild it first");
+    HIPCHK(hipDeviceSynchronize());  // nothing of an earlier batch is left reading the rows or the copies
+    hipStream_t s = ix->stream;
+    if (ix->h_dead.size() < N) ix->h_dead.resize(N, 0);
+
+    // the live bitmap; the chunks of old rows from the first removed row on, with their live counts
+    std::vector<uint32_t> bits((N + 31) / 32 + 1, 0u);
+    uint64_t first_dead = N;
+    for (uint64_t r = 0; r < N; r++) {
+        if (!ix->h_dead[r]) bits[r >> 5] |= 1u << (r & 31);
+        else if (first_dead == N) first_dead = r;
+    }
+    const uint64_t chunk_max = std::max<uint64_t>(1, ZH_COMPACT_BOUNCE_BYTES / row_bytes);  // what the bounce buffer holds
+    uint64_t chunk_rows = chunk_max;
+    if (const char *e = getenv("ZH_COMPACT_CHUNK_ROWS")) {
+        const long long v = atoll(e);
+        if (v > 0) chunk_rows = std::min<uint64_t>((uint64_t)v, chunk_max);
+    }
+    struct Chunk { uint64_t a, n, to, live; bool direct; };
+    std::vector<Chunk> chunks;
+    uint64_t bounce_rows = 0;
+    {
+        uint64_t to = first_dead;  // = new(first_dead): every row before it is live
+        for (uint64_t a = first_dead; a < N; a += chunk_rows) {
+            const uint64_t n = std::min(chunk_rows, N - a);
+            uint64_t live = 0;
+            for (uint64_t r = a; r < a + n; r++) live += !ix->h_dead[r];
+            if (live) {
+                const bool direct = to + live <= a;
+                chunks.push_back({a, n, to, live, direct});
+                if (!direct) bounce_rows = std::max(bounce_rows, live);
+                ci.rows_moved += live;
+                ci.bytes_moved += (direct ? 2 : 4) * live * (uint64_t)row_bytes;
+            }
+            to += live;
+        }
+    }
+
+    const uint64_t nb = (N + ZH_COMPACT_RANK_ROWS - 1) / ZH_COMPACT_RANK_ROWS;
+    DevBuf dBits, dNew, dCount, dExcl, dTmp, dFlag, dBounce;
+    struct G { std::vector<DevBuf *> v; ~G() { for (auto *b : v) b->release(); } } g;
+    g.v = {&dBits, &dNew, &dCount, &dExcl, &dTmp, &dFlag, &dBounce};
+    if ((rc = dBits.ensure(bits.size() * 4)) || (rc = dNew.ensure(N * 4)) || (rc = dCount.ensure(nb * 4)) || (rc = dExcl.ensure((nb + 1) * 4)) ||
+        (rc = dTmp.ensure((nb / 1024 + 4) * 4)) || (rc = dFlag.ensure(4)) || (bounce_rows && (rc = dBounce.ensure(bounce_rows * row_bytes))))
+        return rc;
+    for (DevBuf *b : g.v) ci.scratch_bytes += b->cap;
+    std::vector<uint32_t> h_new;
+    const bool want_host_map = out_new_ids != nullptr;  // (4 bytes per stored row back over PCIe: only for a caller who wants the map)
+    if (want_host_map) h_new.resize(N);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    HIPCHK(hipEventCreate(&ev0));
+    if (hipEventCreate(&ev1) != hipSuccess) { hipEventDestroy(ev0); return fail(ZH_EHIP, "hipEventCreate failed"); }
+    struct GE { hipEvent_t a, b; ~GE() { hipEventDestroy(a); hipEventDestroy(b); } } ge{ev0, ev1};
+
+    // (1) rank: nothing of the index has changed yet
+    HIPCHK(hipMemcpyAsync(dBits.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(dFlag.p, 0, 4, s));
+    HIPCHK(hipEventRecord(ev0, s));
+    HIPCHK(zh_launch_compact_rank(dBits.as<uint32_t>(), N, dCount.as<uint32_t>(), dExcl.as<uint32_t>(), dTmp.as<uint32_t>(), dNew.as<uint32_t>(), s));
+    HIPCHK(hipStreamSynchronize(s));
+
+    // (2) + (3): from here on a failure leaves rows half moved
+    float *X = ix->X.as<float>();
+    const uint32_t *dMap = dNew.as<uint32_t>();
+    hipError_t e = hipSuccess;
+    for (size_t c = 0; c < chunks.size() && e == hipSuccess; c++) {
+        const Chunk &ch = chunks[c];
+        if (ch.direct) {
+            e = zh_launch_move_rows(X, X, d, dMap, ch.a, ch.n, 0, s);
+        } else {
+            e = zh_launch_move_rows(X, dBounce.as<float>(), d, dMap, ch.a, ch.n, ch.to, s);
+            if (e == hipSuccess) e = zh_launch_move_rows(dBounce.as<float>(), X + ch.to * d, d, nullptr, 0, ch.live, 0, s);
+        }
+    }
+    if (e == hipSuccess) e = zh_launch_renumber_ids(ix->leaf_ids.as<uint32_t>(), ix->n_leaf_ids, dMap, N, s);
+    const bool had_samples = ix->samples_valid && ix->n_planes && ix->plane_samples.cap >= (size_t)ix->n_planes * sizeof(uint2);
+    if (e == hipSuccess && had_samples) e = zh_launch_renumber_samples(ix->plane_samples.as<uint2>(), ix->n_planes, dMap, N, dFlag.as<uint32_t>(), s);
+    if (e == hipSuccess) e = hipEventRecord(ev1, s);
+    uint32_t lost_sample = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&lost_sample, dFlag.p, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && want_host_map) e = hipMemcpyAsync(h_new.data(), dNew.p, N * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        ix->broken = true; ix->rows_torn = true;
+        return fail(ZH_EHIP, "zh_index_compact failed after rows had begun to move (%s): the stored rows are inconsistent; zh_index_clear the index and store them again",
+                    hipGetErrorString(e));
+    }
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) ci.ms = ms;
+
+    // (4) the host's view
+    if (out_new_ids)
+        for (uint64_t r = 0; r < N; r++) out_new_ids[r] = h_new[r] == 0xFFFFFFFFu ? ~0ull : id_base + h_new[r];
+    if (want_host_map && ix->n_leaf_ids && ix->h_leaf_ids.size() == ix->n_leaf_ids) {
+        for (uint32_t &v : ix->h_leaf_ids)
+            if (v < N) v = h_new[v] == 0xFFFFFFFFu ? 0u : h_new[v];
+    } else {
+        ix->h_leaf_ids.clear();  // (the next incremental add or remove reads the mirror back from the device)
+    }
+    ix->n_rows = NL;
+    ix->h_dead.clear();
+    ix->n_dead = 0;
+    ix->rows_gen++; ix->dead_gen++;
+    ix->h_live.clear(); ix->h_live.shrink_to_fit();
+    ix->h_live_rows = ix->h_live_dead = ix->h_live_gen = ~0ull;
+    ix->ex_live_rows = ix->ex_live_gen = ~0ull;
+    ix->ex_live.release(); ix->ex_bits.release();  // (sized by the old row count; re-made by the next exact search)
+    ix->norm_rows = 0; ix->norm_gen = 0;
+    ix->row_hn2.release(); ix->row_norm.release();
+    ix->hab_planes = 0; ix->hab_rows = 0; ix->hab_gen = 0;
+    if (lost_sample) ix->samples_valid = false;  // (a plane's sample row is gone: no row scores for its sign until the forest is rebuilt)
+    ix->leaf_meta.release(); ix->leaf_meta_valid = false;
+    ix->row_leaf.release(); ix->row_leaf_valid = false; ix->row_leaf_failed = false; ix->row_leaf_rows = 0;
+    {
+        std::lock_guard<std::mutex> lb(ix->blk_mu);  // (the fp16 copies' state is blk_mu's: zh_stats reads it under that lock)
+        ix->blocks_valid = false;
+        ci.copy_bytes_released = ix->row_half.cap + ix->row_meta.cap + ix->row_half128.cap + ix->scan_perm.cap + ix->row_leaf_p.cap;
+        ix->scale_rows = 0; ix->scale_gen = 0; ix->row_rho = 0.f; ix->row_half.release(); ix->row_meta.release(); ix->row_half_failed = false;
+        ix->perm_rows = 0; ix->perm_gen++; ix->scan_perm.release(); ix->row_leaf_p.release();
+        ix->h128_rows = 0; ix->h128_gen = 0; ix->h128_rho = 0.f; ix->row_half128.release(); ix->h128_failed = false;
+        ix->h128_bytes = false;  // (h128_not_bytes stays: a table with a row that is not of bytes still has one, or lost it and finds out when the copy is next made)
+    }
+    if (info) *info = ci;
     return ZH_OK;
 }
 
@@ -1988,6 +2153,7 @@ static int ctx_begin(zh_search_ctx *c, const float *const *dQs, size_t nwin, siz
     const float *dQ = dQs[0];
     int rc;
     if (c->state == 1) return fail(ZH_ESTATE, "zh_search_begin: the context already has a batch begun; finish it first");
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
     if (ix->broken) return fail(ZH_ESTATE, "an earlier zh_index_add failed half way: call zh_index_build before searching");
     if (c->state == 2 && (rc = ctx_wait(c))) return rc;  // the previous batch was never waited for: retire it
     c->dQ = dQ; c->B = B; c->k = k; c->metric = metric; c->mode = mode; c->s = s;
@@ -3018,6 +3184,7 @@ extern "C" int zh_search_batch(zh_index *ix, const float *q, size_t b, size_t k,
 // the ascending live rows (path 1) and the live-row bitmap (path 2) on the device (under mu, exclusive), rebuilt when rows were appended or
 // removed since
 static int exact_live_rows(zh_index *ix) {
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
     if (ix->ex_live_rows == ix->n_rows && ix->ex_live_gen == ix->dead_gen) return ZH_OK;
     std::vector<uint32_t> live;
     live.reserve(ix->n_rows - ix->n_dead);
@@ -3252,6 +3419,7 @@ extern "C" int zh_hash_signs(zh_index *ix, const float *q, size_t b, uint32_t *o
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     int rc = set_device(ix);
     if (rc) return rc;
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
     const uint32_t P = ix->n_planes, d = ix->opt.dim;
     if (!b || !P) return ZH_OK;
     hipStream_t s = ix->stream;

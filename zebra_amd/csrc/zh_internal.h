@@ -397,3 +397,15 @@ hipError_t zh_launch_scan_u32(const uint32_t *dIn, uint32_t *dOut /* n+1 */, uin
 hipError_t zh_launch_scatter(const uint32_t *dPermIn, uint32_t *dPermOut, const ZhBuildNode *dNodes,
                              const ZhBuildChunk *dChunks, uint32_t n_chunks, const uint8_t *dFlags,
                              const uint32_t *dChunkScan, uint32_t *dNodeAbove, hipStream_t s);
+
+// ---- launchers (zh_compact.hip): zh_index_compact ---------------------------------------------------------------------------------
+#define ZH_COMPACT_RANK_ROWS 8192u  // rows per block of the rank pass (256 words of the live bitmap)
+// dNewRow[r] = live rows before r, or UINT32_MAX for a removed row, from the live bitmap (bits at and past n_rows zero).  dBlockCount: n_blocks
+// entries, dBlockExcl: n_blocks + 1, dScanTmp: n_blocks / 1024 + 2, for n_blocks = ceil(n_rows / ZH_COMPACT_RANK_ROWS)
+hipError_t zh_launch_compact_rank(const uint32_t *dLiveBits, uint64_t n_rows, uint32_t *dBlockCount, uint32_t *dBlockExcl, uint32_t *dScanTmp,
+                                  uint32_t *dNewRow, hipStream_t s);
+// rows [r0, r0 + n) of dSrc -> row (dMap ? dMap[r] : r) - sub of dDst (a UINT32_MAX entry: not moved); source and destination must not overlap
+hipError_t zh_launch_move_rows(const float *dSrc, float *dDst, uint32_t d, const uint32_t *dMap, uint64_t r0, uint64_t n, uint64_t sub, hipStream_t s);
+hipError_t zh_launch_renumber_ids(uint32_t *dIds, uint64_t n, const uint32_t *dNewRow, uint64_t rows_before, hipStream_t s);
+// *dFlag |= 1 when a sample row was removed
+hipError_t zh_launch_renumber_samples(uint2 *dSamples, uint32_t n, const uint32_t *dNewRow, uint64_t rows_before, uint32_t *dFlag, hipStream_t s);

@@ -173,6 +173,10 @@ class LSHIndex:
     def __len__(self):
         return int(lib().zh_index_count(self._h))
 
+    def stored_rows(self):
+        """rows the table holds, live + removed (zh_index_stored_rows); equals len() after compact()"""
+        return int(lib().zh_index_stored_rows(self._h))
+
     def add(self, embeddings):
         """lsh.rs:440-466: returns the ids of the added vectors (dense row ids, not Uuids)."""
         e = _f32(embeddings, self.dim)
@@ -209,6 +213,16 @@ class LSHIndex:
         n = C.c_size_t()
         check(lib().zh_index_deduplicate(self._h, _p(out), out.size, C.byref(n)))
         return out[:n.value]
+
+    def compact(self):
+        """zh_index_compact: the live rows move down over the removed ones on the device, in their order; the forest's leaf ids follow.
+        -> (new_ids [rows_before] u64: id_base + new row of every OLD local row, 2^64-1 for a removed one; info dict of zh_compact_info).
+        Every later call answers as the uncompacted index would, under that map.  With nothing removed: the identity, nothing released."""
+        n = self.stored_rows()
+        new_ids = np.empty(n, np.uint64)
+        info = _ffi.CompactInfo()
+        check(lib().zh_index_compact(self._h, _p(new_ids), n, C.byref(info)))
+        return new_ids, info.as_dict()
 
     def set_forest(self, arrays):
         a = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
@@ -527,6 +541,18 @@ class Database:
         """core.rs:216-225"""
         for i in self.index.deduplicate().tolist():
             self._documents.pop(i, None)
+
+    def compact(self):
+        """reclaim the device memory of removed vectors (LSHIndex.compact) and re-key the documents with the old -> new id map"""
+        new_ids, info = self.index.compact()
+        base, gone = self.index.id_base, np.uint64(0xFFFFFFFFFFFFFFFF)
+        docs = {}
+        for i, doc in self._documents.items():
+            r = i - base
+            if 0 <= r < new_ids.size and new_ids[r] != gone:
+                docs[int(new_ids[r])] = doc
+        self._documents = docs
+        return info
 
     def clear_database(self):
         """core.rs:194-198"""

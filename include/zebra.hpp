@@ -154,7 +154,24 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_index_create(&o, &h));
         h_.reset(h, zh_index_destroy);
     }
-    void save() const {}  // persistence is out of scope (lsh.rs:170-172)
+    void save() const {}  // the crate's own persistence goes through fjall (lsh.rs:170-172): not this path; snapshots are below
+    // (new) zh_index_save: the index as ONE snapshot file -- rows (removed ones included), removals, forest, the planes' sample rows -- written
+    // beside `path` first and renamed over it.  Needs the exclusion of add.
+    zh_snapshot_info save(const std::string &path) const {
+        zh_snapshot_info info;
+        check(zh_index_save(h_.get(), path.c_str(), &info));
+        return info;
+    }
+    // (new) zh_index_load: a new index from a snapshot, indistinguishable from the saved one for every later call (N must be the file's dim)
+    static LSHIndex load(const std::string &path, int device = -1, std::uint64_t reserve_rows = 0, zh_snapshot_info *info = nullptr) {
+        zh_snapshot_info seen;
+        check(zh_snapshot_inspect(path.c_str(), 0, &seen));
+        if (seen.dim != N) throw Error(ZH_EINVAL, "zebra: snapshot " + path + " holds vectors of another dimension");
+        zh_index *h = nullptr;
+        check(zh_index_load(path.c_str(), device, reserve_rows, &h, info));
+        LSHIndex out(Adopt{}, h);
+        return out;
+    }
 
     bool no_vectors() const { return zh_index_count(h_.get()) == 0; }     // lsh.rs:398-400
     bool no_trees() const { return zh_index_num_trees(h_.get()) == 0; }   // lsh.rs:407-409
@@ -234,6 +251,8 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
     zh_index *handle() const { return h_.get(); }
 
   private:
+    struct Adopt {};
+    LSHIndex(Adopt, zh_index *h) { h_.reset(h, zh_index_destroy); }
     std::shared_ptr<zh_index> h_;
 };
 

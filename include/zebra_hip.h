@@ -25,6 +25,8 @@
  *                                        this rank's shard, ONE RCCL all-gather of the packed top-k, merge on every rank
  *   zh_merge_topk_device                 (new) the shard merge alone
  *   zh_search_exact_batch[_device]       (new) exact top-k over every live row under the same keys: recall ground truth
+ *   zh_index_save / zh_index_load        (new) a snapshot of an index in ONE file of this library's own format (the reference persists through
+ *                                        fjall, lsh.rs:62-120, whose files are not read here): rows, removals, forest and the planes' sample rows
  *
  * Conventions
  *   - Every function returns ZH_OK (0) or a negative zh_status; zh_last_error() gives the message
@@ -66,8 +68,10 @@ typedef enum zh_status {
     ZH_ESTATE = -4,       /* call not valid in the index's current state */
     ZH_ELIMIT = -5,       /* a documented limit was exceeded (e.g. top_k > ZH_MAX_TOPK) */
     ZH_EUNSUPPORTED = -6,
-    ZH_EPEER = -7         /* sharded search: ANOTHER rank of the group failed its part of the batch (or died); the exchange
+    ZH_EPEER = -7,        /* sharded search: ANOTHER rank of the group failed its part of the batch (or died); the exchange
                            * completed (or was aborted after a timeout), the batch's results are not valid on any rank */
+    ZH_EIO = -8,          /* snapshots: the operating system refused an open, read, write, rename or fsync (the message carries strerror) */
+    ZH_ECORRUPT = -9      /* snapshots: the file is not a snapshot, is truncated, or fails a size, range or checksum test */
 } zh_status;
 
 /* the 13 metric structs of src/distance.rs.  0-2 are the simsimd path (key = f64 bits); 3-11 the `distances`
@@ -256,6 +260,52 @@ typedef struct zh_compact_info {
     double   ms;              /* hipEvent time of the device work, on the index's stream */
 } zh_compact_info;
 ZH_API int zh_index_compact(zh_index *idx, uint64_t *out_new_ids, size_t cap, zh_compact_info *info);
+
+/* ---- snapshots (new): an index saved to ONE file and loaded back ------------------------------------------------------------------
+ * A loaded index is indistinguishable from the saved one for every later call: ids, keys and counts of every search, zh_hash_signs,
+ * zh_index_read_rows, zh_index_get_forest, the counts, which path a batch takes where that depends on index state (zh_stats_t::hash_from_scores,
+ * prefiltered), and the effect of every later add / append / build / remove / deduplicate / compact.  Saved: the options, the f32 rows (removed
+ * ones included: ids are row numbers), the removed-row set, the forest arrays in the index's own numbering, the planes' sample rows and whether
+ * they are valid (zh_index_set_forest could not restore them: the row-score hash and the prefilter survive a snapshot), scan_unsafe, the levels
+ * of the built forest.  NOT saved: everything derived from those (the fp16 / byte copies of the rows, norms, row -> leaf tables, the scan order, the
+ * blocked view, exact-search scratch: re-made on first use, as after zh_index_compact) and the tuning state (sweep / hash mode, dense levels,
+ * strikes, statistics, profiling: a loaded index starts with the defaults).
+ * The file (byte for byte): little endian; a 4096-byte header block -- magic, version, the fields of zh_snapshot_info, a table of
+ * {kind, offset, length, checksum} per section, the block's own checksum last --, then the sections, each on a 4096-byte boundary, padding zero.
+ * A section's checksum is the sum mod 2^64 over its 8-byte words w_i (zero padded) of mix(w_i + 0x9E3779B97F4A7C15 (i + 1)), mix the splitmix64
+ * finaliser: computable in any order and in pieces, on the GPU and on the host alike.
+ * ZH_EIO: the operating system refused an open / read / write / rename / fsync; ZH_ECORRUPT: not a snapshot, truncated, or a size, range, padding
+ * or checksum test failed; ZH_EUNSUPPORTED: a version newer than ZH_SNAPSHOT_VERSION. */
+#define ZH_SNAPSHOT_VERSION 1u
+typedef struct zh_snapshot_info {
+    uint32_t version, dim, max_node_size, num_trees_option;
+    uint64_t seed, id_base;
+    uint64_t stored_rows, live_rows;          /* zh_index_stored_rows / zh_index_count */
+    uint32_t n_trees, n_nodes, n_planes, flags; /* flags: 1 plane samples present (row-score hash survives), 2 scan_unsafe forest */
+    uint64_t n_leaf_ids;
+    uint64_t file_bytes, row_bytes;
+    uint32_t n_sections, verified;            /* verified: 1 when every section checksum was recomputed and matched */
+    double   ms, ms_device;                   /* wall time of the call; hipEvent time of its device work (0 for inspect) */
+} zh_snapshot_info;
+/* Writes the index to `path`: to path + ".zhtmp" in the same directory first, fsync, then rename over path -- a failed save leaves no file at
+ * the temporary name and an older file at path intact.  The rows are never staged whole on the host: chunks of ZH_SNAPSHOT_CHUNK_BYTES
+ * (environment, read per call, rounded down to a multiple of 8; default 64 MiB) go device -> host through two pinned buffers on a stream of the
+ * call's own, the host writes chunk i while chunk i + 1 is in flight, and a gfx950 kernel sums each chunk on the device before it leaves: the
+ * rows' checksum vouches for what was in device memory.  The file does not depend on the chunk size.  Holds the index lock exclusively
+ * (searches wait) and needs the same external exclusion as zh_index_add; pipelined contexts must be idle.  ZH_ESTATE on an index whose last add
+ * or compaction failed half way.  An empty index, one filled by zh_index_append and never built, and one with an injected forest all save.
+ * info may be NULL. */
+ZH_API int zh_index_save(zh_index *idx, const char *path, zh_snapshot_info *info);
+/* Makes a new index from the file at `path` on `device` (-1: the calling thread's current device); reserve_rows is zh_options::reserve_rows.
+ * Every size in the header is tested against the file's length and the ABI's limits (ZH_MAX_DIM, 2^32-1 rows and leaf entries) before anything
+ * is allocated; the rows go up through the same two pinned buffers and the checksum kernel runs on what ARRIVED in device memory, so the
+ * comparison with the table vouches for the bytes the GPU will read.  The forest passes the tests of zh_index_set_forest (and its planes keep
+ * their numbering and their sample rows) before the index is handed out.  On any failure *out is NULL and everything allocated is released.
+ * info may be NULL.  Loading one file twice gives two independent indexes. */
+ZH_API int zh_index_load(const char *path, int32_t device, uint64_t reserve_rows, zh_index **out, zh_snapshot_info *info);
+/* Host code only (no GPU needed): the header of the file at `path`, after every test zh_index_load applies to the header block, the section
+ * table and the padding; verify != 0: every section's checksum is recomputed on the host as well (info->verified = 1). */
+ZH_API int zh_snapshot_inspect(const char *path, int verify, zh_snapshot_info *info);
 
 /* ---- forest exchange (parity tests inject / extract the exact same forest) ----------------- */
 ZH_API int zh_index_set_forest(zh_index *idx, const zh_forest_view *forest);

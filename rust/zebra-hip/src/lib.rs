@@ -121,6 +121,30 @@ pub mod ffi {
         pub ms: f64,
     }
 
+    #[repr(C)]
+    #[derive(Default, Clone, Copy, Debug)]
+    pub struct zh_snapshot_info {
+        pub version: u32,
+        pub dim: u32,
+        pub max_node_size: u32,
+        pub num_trees_option: u32,
+        pub seed: u64,
+        pub id_base: u64,
+        pub stored_rows: u64,
+        pub live_rows: u64,
+        pub n_trees: u32,
+        pub n_nodes: u32,
+        pub n_planes: u32,
+        pub flags: u32,
+        pub n_leaf_ids: u64,
+        pub file_bytes: u64,
+        pub row_bytes: u64,
+        pub n_sections: u32,
+        pub verified: u32,
+        pub ms: f64,
+        pub ms_device: f64,
+    }
+
     pub const ZH_COSINE: c_int = 0;
     pub const ZH_L2SQ: c_int = 1;
     pub const ZH_L2: c_int = 2;
@@ -146,6 +170,9 @@ pub mod ffi {
         pub fn zh_index_remove(idx: *mut zh_index, ids: *const u64, n: usize, out_found: *mut u8, out_n_removed: *mut usize) -> c_int;
         pub fn zh_index_deduplicate(idx: *mut zh_index, out_ids: *mut u64, cap: usize, out_n_removed: *mut usize) -> c_int;
         pub fn zh_index_compact(idx: *mut zh_index, out_new_ids: *mut u64, cap: usize, info: *mut zh_compact_info) -> c_int;
+        pub fn zh_index_save(idx: *mut zh_index, path: *const std::os::raw::c_char, info: *mut zh_snapshot_info) -> c_int;
+        pub fn zh_index_load(path: *const std::os::raw::c_char, device: i32, reserve_rows: u64, out: *mut *mut zh_index,
+                             info: *mut zh_snapshot_info) -> c_int;
         pub fn zh_index_count(idx: *const zh_index) -> u64;
         pub fn zh_index_stored_rows(idx: *const zh_index) -> u64;
         pub fn zh_index_num_trees(idx: *const zh_index) -> u32;
@@ -322,6 +349,44 @@ impl<const N: usize> LSHIndex<N> {
     }
     pub fn save(&self) -> anyhow::Result<()> {
         Ok(())
+    }
+    /// (new) zh_index_save: the index as ONE snapshot file (rows, removals, forest, the planes' sample rows), and the row -> Uuid table --
+    /// which the library does not know -- beside it as `<path>.ids` (16 bytes per stored row, in row order; written to a temporary name and
+    /// renamed, like the snapshot).  Holds the table across both, so the two files describe the same rows.  Needs the exclusion of `add`.
+    pub fn save_snapshot(&self, path: &str) -> anyhow::Result<ffi::zh_snapshot_info> {
+        let t = self.ids.write().unwrap();
+        let c_path = std::ffi::CString::new(path)?;
+        let mut info = ffi::zh_snapshot_info::default();
+        check(unsafe { ffi::zh_index_save(self.hip.0, c_path.as_ptr(), &mut info) })?;
+        anyhow::ensure!(info.stored_rows as usize == t.of_row.len(), "row table and snapshot disagree on the stored rows");
+        let mut bytes = Vec::with_capacity(16 * t.of_row.len());
+        for u in &t.of_row {
+            bytes.extend_from_slice(u.as_bytes());
+        }
+        let tmp = format!("{path}.ids.tmp");
+        std::fs::write(&tmp, &bytes)?;
+        std::fs::File::open(&tmp)?.sync_all()?;
+        std::fs::rename(&tmp, format!("{path}.ids"))?;
+        Ok(info)
+    }
+    /// (new) zh_index_load + the row -> Uuid table written by `save_snapshot`: the saved index, for every later call.  Rows removed before the
+    /// save keep their slot in the table (ids are row numbers) and stay unknown to `row_of`'s users exactly as before: the library refuses them.
+    pub fn load(path: &str) -> anyhow::Result<Self> {
+        let c_path = std::ffi::CString::new(path)?;
+        let mut info = ffi::zh_snapshot_info::default();
+        let mut h = std::ptr::null_mut();
+        check(unsafe { ffi::zh_index_load(c_path.as_ptr(), -1, 0, &mut h, &mut info) })?;
+        let hip = Arc::new(HipIndex(h)); // (dropped, and the index destroyed, on every early return below)
+        anyhow::ensure!(info.dim as usize == N, "snapshot holds vectors of dimension {}, not {}", info.dim, N);
+        let bytes = std::fs::read(format!("{path}.ids"))?;
+        anyhow::ensure!(bytes.len() as u64 == 16 * info.stored_rows, "{path}.ids does not hold {} ids", info.stored_rows);
+        let mut t = IdTable::default();
+        for (row, b) in bytes.chunks_exact(16).enumerate() {
+            let u = Uuid::from_slice(b)?;
+            t.row_of.insert(u, row as u64);
+            t.of_row.push(u);
+        }
+        Ok(Self { hip, ids: Arc::new(RwLock::new(t)) })
     }
     pub fn no_vectors(&self) -> bool {
         unsafe { ffi::zh_index_count(self.hip.0) == 0 }

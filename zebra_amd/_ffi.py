@@ -8,6 +8,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libzebra_hip.so")
 
 ZH_OK = 0
 ZH_EINVAL, ZH_ENOMEM, ZH_EHIP, ZH_ESTATE, ZH_ELIMIT, ZH_EUNSUPPORTED, ZH_EPEER = -1, -2, -3, -4, -5, -6, -7
+ZH_EIO, ZH_ECORRUPT = -8, -9  # snapshots: the operating system refused; not a snapshot / truncated / a size, range or checksum test failed
 COSINE, L2SQ, L2 = 0, 1, 2
 CHEBYSHEV, CANBERRA, BRAY_CURTIS, MANHATTAN, L3, L4, HAMMING, MINKOWSKI, PNORM = 3, 4, 5, 6, 7, 8, 9, 10, 11
 COSINE_PARITY, COSINE_CORRECTED = 0, 1
@@ -15,6 +16,8 @@ MAX_TOPK = 1024
 
 
 class ZhError(RuntimeError):
+    EIO, ECORRUPT = ZH_EIO, ZH_ECORRUPT
+
     def __init__(self, code, msg):
         super().__init__(f"zebra_hip error {code}: {msg}")
         self.code = code
@@ -95,6 +98,20 @@ class CompactInfo(C.Structure):
 
 COMPACT_BOUNCE_BYTES = 256 << 20  # ZH_COMPACT_BOUNCE_BYTES
 
+
+class SnapshotInfo(C.Structure):
+    _fields_ = [("version", C.c_uint32), ("dim", C.c_uint32), ("max_node_size", C.c_uint32), ("num_trees_option", C.c_uint32),
+                ("seed", C.c_uint64), ("id_base", C.c_uint64), ("stored_rows", C.c_uint64), ("live_rows", C.c_uint64),
+                ("n_trees", C.c_uint32), ("n_nodes", C.c_uint32), ("n_planes", C.c_uint32), ("flags", C.c_uint32),
+                ("n_leaf_ids", C.c_uint64), ("file_bytes", C.c_uint64), ("row_bytes", C.c_uint64),
+                ("n_sections", C.c_uint32), ("verified", C.c_uint32), ("ms", C.c_double), ("ms_device", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+SNAPSHOT_VERSION = 1  # ZH_SNAPSHOT_VERSION
+
 # every symbol include/zebra_hip.h declares: (name, restype, argtypes)
 _vp, _u64, _u32, _sz, _i = C.c_void_p, C.c_uint64, C.c_uint32, C.c_size_t, C.c_int
 SYMBOLS = [
@@ -110,6 +127,9 @@ SYMBOLS = [
     ("zh_index_remove", _i, [_vp, _vp, _sz, _vp, _vp]),
     ("zh_index_deduplicate", _i, [_vp, _vp, _sz, _vp]),
     ("zh_index_compact", _i, [_vp, _vp, _sz, _vp]),
+    ("zh_index_save", _i, [_vp, C.c_char_p, _vp]),
+    ("zh_index_load", _i, [C.c_char_p, C.c_int32, _u64, _vp, _vp]),
+    ("zh_snapshot_inspect", _i, [C.c_char_p, _i, _vp]),
     ("zh_index_set_forest", _i, [_vp, _vp]),
     ("zh_index_forest_sizes", _i, [_vp, _vp]),
     ("zh_index_get_forest", _i, [_vp] * 8),

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "zh_internal.h"
+#include "zh_snapfile.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -649,20 +650,26 @@ static int upload_nodes(zh_index *ix) {
     return ZH_OK;
 }
 
-extern "C" int zh_index_set_forest(zh_index *ix, const zh_forest_view *fv) {
-    if (!ix || !fv) return fail(ZH_EINVAL, "zh_index_set_forest: null argument");
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    int rc = set_device(ix);
-    if (rc) return rc;
-    const uint32_t nn = fv->n_nodes, np = fv->n_planes, nt = fv->n_trees, d = ix->opt.dim;
+// What zh_index_set_forest requires of a forest over n_rows stored rows (zh_index_load applies the same tests to a snapshot's forest): every
+// node reachable once, indices and leaf ranges in bounds, leaf ids below the stored rows, at most 63 levels.  Leaves behind the level of every
+// node, the inner nodes per level, and whether a tree lists a row twice.
+struct ForestCheck {
+    std::vector<int32_t> level;
+    std::vector<std::vector<uint32_t>> by_level;
+    bool dup_in_tree = false;
+};
+static int check_forest(const zh_forest_view *fv, uint64_t n_rows, ForestCheck &fc) {
+    const uint32_t nn = fv->n_nodes, np = fv->n_planes, nt = fv->n_trees;
+    std::vector<int32_t> &level = fc.level;
+    std::vector<std::vector<uint32_t>> &by_level = fc.by_level;
+    bool &dup_in_tree = fc.dup_in_tree;
     if (nt && (!fv->roots || !fv->plane || !fv->left || !fv->right)) return fail(ZH_EINVAL, "set_forest: null arrays");
     if (np && (!fv->planes || !fv->consts)) return fail(ZH_EINVAL, "set_forest: null plane arrays");
     if (fv->n_leaf_ids && !fv->leaf_ids) return fail(ZH_EINVAL, "set_forest: null leaf_ids");
     if (fv->n_leaf_ids > 0xFFFFFFFFull) return fail(ZH_ELIMIT, "set_forest: more than 2^32-1 leaf entries");
     // validate + level of every node (BFS per tree)
-    std::vector<int32_t> level(nn, -1);
-    std::vector<uint32_t> order;  // inner nodes in (level, tree, bfs) order
-    std::vector<std::vector<uint32_t>> by_level;
+    level.assign(nn, -1);
+    by_level.clear();
     std::vector<std::pair<uint32_t, uint32_t>> tree_leaves;  // (tree, leaf node)
     for (uint32_t t = 0; t < nt; t++) {
         if (fv->roots[t] >= nn) return fail(ZH_EINVAL, "set_forest: root %u out of range", t);
@@ -693,13 +700,13 @@ extern "C" int zh_index_set_forest(zh_index *ix, const zh_forest_view *fv) {
         }
     }
     for (uint64_t i = 0; i < fv->n_leaf_ids; i++)
-        if (fv->leaf_ids[i] >= ix->n_rows) return fail(ZH_EINVAL, "set_forest: leaf id %u >= stored rows %llu", fv->leaf_ids[i], (unsigned long long)ix->n_rows);
+        if (fv->leaf_ids[i] >= n_rows) return fail(ZH_EINVAL, "set_forest: leaf id %u >= stored rows %llu", fv->leaf_ids[i], (unsigned long long)n_rows);
     // A row listed twice inside ONE tree (a repeated id, or two leaves of a tree over the same leaf_ids range) is legal input --
     // the leaf-major sweep scores every listed occurrence -- but the table scan keeps one {leaf, position} per (row, tree): such
     // a forest is served leaf by leaf only, whatever the cost model or zh_set_sweep_mode say, so results never depend on the sweep.
-    bool dup_in_tree = false;
+    dup_in_tree = false;
     {
-        std::vector<uint32_t> stamp(ix->n_rows, 0xFFFFFFFFu);
+        std::vector<uint32_t> stamp(n_rows, 0xFFFFFFFFu);
         for (size_t i = 0; i < tree_leaves.size() && !dup_in_tree; i++) {
             const uint32_t t = tree_leaves[i].first, n = tree_leaves[i].second;
             const uint32_t off = (uint32_t)fv->left[n], len = (uint32_t)fv->right[n];
@@ -710,6 +717,20 @@ extern "C" int zh_index_set_forest(zh_index *ix, const zh_forest_view *fv) {
             }
         }
     }
+    return ZH_OK;
+}
+
+extern "C" int zh_index_set_forest(zh_index *ix, const zh_forest_view *fv) {
+    if (!ix || !fv) return fail(ZH_EINVAL, "zh_index_set_forest: null argument");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc = set_device(ix);
+    if (rc) return rc;
+    const uint32_t nn = fv->n_nodes, np = fv->n_planes, nt = fv->n_trees, d = ix->opt.dim;
+    ForestCheck fc;
+    if ((rc = check_forest(fv, ix->n_rows, fc))) return rc;
+    const std::vector<int32_t> &level = fc.level;
+    const std::vector<std::vector<uint32_t>> &by_level = fc.by_level;
+    const bool dup_in_tree = fc.dup_in_tree;
     // renumber planes level-major
     std::vector<int32_t> new_of_old(np, -1);
     std::vector<uint32_t> old_of_new;
@@ -1411,6 +1432,224 @@ extern "C" int zh_index_compact(zh_index *ix, uint64_t *out_new_ids, size_t cap,
         ix->h128_bytes = false;  // (h128_not_bytes stays: a table with a row that is not of bytes still has one, or lost it and finds out when the copy is next made)
     }
     if (info) *info = ci;
+    return ZH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// snapshots: zh_index_save / zh_index_load (the file: zh_snapfile.cpp; the row pipeline and the checksum kernel: zh_snapshot.hip)
+// ------------------------------------------------------------------------------------------------
+static int no_device_for_snapshot(const char *who) {
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev == 0)
+        return fail(ZH_EHIP, "%s: no usable HIP device (%s); this library has no CPU fallback", who, e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+    return ZH_OK;
+}
+static double wall_ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+extern "C" int zh_index_save(zh_index *ix, const char *path, zh_snapshot_info *info) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (info) memset(info, 0, sizeof *info);
+    int rc = no_device_for_snapshot("zh_index_save");
+    if (rc) return rc;
+    if (!ix || !path || !*path) return fail(ZH_EINVAL, "zh_index_save: null argument");
+    if (strlen(path) > 4000) return fail(ZH_EINVAL, "zh_index_save: path longer than 4000 bytes");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix))) return rc;
+    if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
+    if (ix->broken) return fail(ZH_ESTATE, "an earlier add failed half way: call zh_index_build before saving");
+    HIPCHK(hipStreamSynchronize(ix->stream));
+    const uint64_t N = ix->n_rows;
+    const uint32_t d = ix->opt.dim, np = ix->n_planes;
+    ZhSnapHeader h{};
+    zh_snapshot_info &f = h.info;
+    f.version = ZH_SNAPSHOT_VERSION; f.dim = d; f.max_node_size = ix->opt.max_node_size; f.num_trees_option = ix->opt.num_trees;
+    f.seed = ix->opt.seed; f.id_base = ix->opt.id_base; f.stored_rows = N; f.live_rows = N - ix->n_dead;
+    f.n_trees = ix->n_trees; f.n_nodes = ix->n_nodes; f.n_planes = np; f.n_leaf_ids = ix->n_leaf_ids;
+    f.flags = (ix->samples_valid ? 1u : 0u) | (ix->scan_unsafe ? 2u : 0u);
+    h.max_leaf_len = ix->max_leaf_len;
+    h.n_levels = (uint32_t)ix->planes_below_level.size();
+    if (h.n_levels > ZH_SNAP_MAX_LEVELS) return fail(ZH_ELIMIT, "zh_index_save: %u forest levels", h.n_levels);
+    zh_snap_plan(&h);
+
+    // the small sections, through the host
+    std::vector<uint8_t> removed((N + 7) / 8, 0);
+    for (uint64_t r = 0; r < N && r < ix->h_dead.size(); r++)
+        if (ix->h_dead[r]) removed[r >> 3] |= (uint8_t)(1u << (r & 7));
+    std::vector<float> hp((size_t)np * d), hc(np);
+    std::vector<uint32_t> hl(ix->n_leaf_ids), hs(f.flags & 1u ? (size_t)np * 2 : 0);
+    if (np) {
+        HIPCHK(hipMemcpy(hp.data(), ix->planes.p, hp.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hc.data(), ix->consts.p, hc.size() * 4, hipMemcpyDeviceToHost));
+    }
+    if (!hl.empty()) HIPCHK(hipMemcpy(hl.data(), ix->leaf_ids.p, hl.size() * 4, hipMemcpyDeviceToHost));
+    if (!hs.empty()) {
+        if (ix->plane_samples.cap < hs.size() * 4) return fail(ZH_ESTATE, "zh_index_save: the planes' sample rows are incomplete");
+        HIPCHK(hipMemcpy(hs.data(), ix->plane_samples.p, hs.size() * 4, hipMemcpyDeviceToHost));
+    }
+    const void *small[ZH_SNAP_MAX_SECTIONS] = {};
+    small[ZH_SEC_REMOVED] = removed.data(); small[ZH_SEC_NODE_PLANE] = ix->h_plane.data(); small[ZH_SEC_NODE_LEFT] = ix->h_left.data();
+    small[ZH_SEC_NODE_RIGHT] = ix->h_right.data(); small[ZH_SEC_ROOTS] = ix->h_roots.data(); small[ZH_SEC_PLANES] = hp.data();
+    small[ZH_SEC_CONSTS] = hc.data(); small[ZH_SEC_LEAF_IDS] = hl.data(); small[ZH_SEC_LEVELS] = ix->planes_below_level.data();
+    small[ZH_SEC_SAMPLES] = hs.data();
+    if (ix->h_plane.size() != ix->n_nodes || ix->h_roots.size() != ix->n_trees) return fail(ZH_ESTATE, "zh_index_save: the forest's host mirror is stale");
+
+    std::vector<char> tmp(strlen(path) + 16);
+    int fd;
+    if ((rc = zh_snap_create(path, f.file_bytes, tmp.data(), &fd))) return rc;
+    double ms_device = 0;
+    for (uint32_t i = 0; i < f.n_sections && !rc; i++) {
+        ZhSnapSection &s = h.sec[i];
+        if (s.kind == ZH_SEC_ROWS) {
+            rc = zh_snap_rows_out(fd, tmp.data(), s.offset, ix->X.p, s.length, &s.checksum, &ms_device);
+        } else {
+            s.checksum = zh_snap_sum(small[s.kind], s.length, 0);
+            if (s.length) rc = zh_snap_pwrite(fd, small[s.kind], s.length, s.offset, tmp.data());
+        }
+    }
+    if (!rc) {
+        uint8_t block[ZH_SNAP_BLOCK];
+        zh_snap_encode(&h, block);
+        rc = zh_snap_pwrite(fd, block, ZH_SNAP_BLOCK, 0, tmp.data());
+    }
+    if (rc) { zh_snap_abort(fd, tmp.data()); return rc; }
+    if ((rc = zh_snap_commit(fd, tmp.data(), path))) return rc;
+    if (info) {
+        *info = f;
+        info->verified = 1;  // every checksum in the table was computed from the index's own memory by this call
+        info->ms_device = ms_device;
+        info->ms = wall_ms_since(t_begin);
+    }
+    return ZH_OK;
+}
+
+// everything of a snapshot but the rows, read into host memory and tested; then installed into a fresh index
+static int load_forest(zh_index *ix, int fd, const ZhSnapHeader &h) {
+    const zh_snapshot_info &f = h.info;
+    const uint64_t N = f.stored_rows;
+    const uint32_t nn = f.n_nodes, np = f.n_planes, nt = f.n_trees, d = f.dim;
+    int rc;
+    auto corrupt = [&](const char *what) { return fail(ZH_ECORRUPT, "zh_index_load: %s", what); };
+    // removed rows
+    std::vector<uint8_t> removed((N + 7) / 8);
+    if ((rc = zh_snap_read_section(fd, zh_snap_find(&h, ZH_SEC_REMOVED), removed.data()))) return rc;
+    uint64_t n_dead = 0;
+    for (uint8_t b : removed) n_dead += (uint64_t)__builtin_popcount(b);
+    if ((N & 7) && (removed.back() >> (N & 7))) return corrupt("the removed-row bitmap names rows past the stored ones");
+    if (n_dead != N - f.live_rows) return corrupt("the removed-row bitmap does not match the live count");
+    // forest
+    std::vector<int32_t> plane(nn), left(nn), right(nn);
+    std::vector<uint32_t> roots(nt), leaf_ids(f.n_leaf_ids), levels(h.n_levels), samples(f.flags & 1u ? (size_t)np * 2 : 0);
+    std::vector<float> planes((size_t)np * d), consts(np);
+    if ((rc = zh_snap_read_section(fd, zh_snap_find(&h, ZH_SEC_NODE_PLANE), plane.data())) ||
+        (rc = zh_snap_read_section(fd, zh_snap_find(&h, ZH_SEC_NODE_LEFT), left.data())) ||
+        (rc = zh_snap_read_section(fd, zh_snap_find(&h, ZH_SEC_NODE_RIGHT), right.data())) ||
+        (rc = zh_snap_read_section(fd, zh_snap_find(&h, ZH_SEC_ROOTS), roots.data())) ||
+        (rc = zh_snap_read_section(fd, zh_snap_find(&h, ZH_SEC_PLANES), planes.data())) ||
+        (rc = zh_snap_read_section(fd, zh_snap_find(&h, ZH_SEC_CONSTS), consts.data())) ||
+        (rc = zh_snap_read_section(fd, zh_snap_find(&h, ZH_SEC_LEAF_IDS), leaf_ids.data())) ||
+        (rc = zh_snap_read_section(fd, zh_snap_find(&h, ZH_SEC_LEVELS), levels.data())))
+        return rc;
+    if ((f.flags & 1u) && (rc = zh_snap_read_section(fd, zh_snap_find(&h, ZH_SEC_SAMPLES), samples.data()))) return rc;
+    zh_forest_view fv{};
+    fv.n_nodes = nn; fv.n_planes = np; fv.n_trees = nt; fv.n_leaf_ids = f.n_leaf_ids;
+    fv.plane = plane.data(); fv.left = left.data(); fv.right = right.data(); fv.roots = roots.data();
+    fv.planes = planes.data(); fv.consts = consts.data(); fv.leaf_ids = leaf_ids.data();
+    ForestCheck fc;
+    if (check_forest(&fv, N, fc)) {
+        const std::string why = g_err;
+        return fail(ZH_ECORRUPT, "zh_index_load: the forest fails zh_index_set_forest's tests (%s)", why.c_str());
+    }
+    uint32_t max_leaf_len = 0;
+    for (uint32_t n = 0; n < nn; n++) {
+        // (set_forest's tests cover the nodes a root reaches; pack_nodes and the leaf-length pass read EVERY record)
+        if (plane[n] >= 0 && (uint32_t)plane[n] >= std::max(np, 1u)) return corrupt("a node names a plane past the last one");
+        if (plane[n] < -1) return corrupt("a node record is neither inner nor leaf");
+        if (plane[n] < 0) max_leaf_len = std::max(max_leaf_len, (uint32_t)right[n]);
+    }
+    if (max_leaf_len != h.max_leaf_len) return corrupt("max_leaf_len does not match the leaves");
+    for (uint32_t l = 0; l < h.n_levels; l++)
+        if (levels[l] > np || (l && levels[l] < levels[l - 1]) || (!l && levels[0] != 0)) return corrupt("the forest's level table is not 0 <= ... <= n_planes, ascending");
+    for (uint32_t v : samples)
+        if (v != 0xFFFFFFFFu && v >= N) return corrupt("a plane's sample row is past the stored rows");
+    if (nt == 0 && (nn || np || f.n_leaf_ids || h.n_levels || (f.flags & 3u))) return corrupt("forest arrays without trees");
+
+    // install: what build / insert / set_forest leave behind, with the planes in the file's numbering
+    if (n_dead) {
+        ix->h_dead.assign(N, 0);
+        for (uint64_t r = 0; r < N; r++) ix->h_dead[r] = (removed[r >> 3] >> (r & 7)) & 1u;
+    }
+    ix->n_dead = n_dead;
+    if (nt == 0) return ZH_OK;  // rows only: appended and never built, or empty
+    ix->h_plane.swap(plane); ix->h_left.swap(left); ix->h_right.swap(right); ix->h_roots.swap(roots);
+    if ((rc = ix->planes.ensure((size_t)std::max(np, 1u) * d * 4)) || (rc = ix->consts.ensure((size_t)std::max(np, 1u) * 4)) ||
+        (rc = ix->leaf_ids.ensure(std::max<uint64_t>(f.n_leaf_ids, 1) * 4)))
+        return rc;
+    if (np) {
+        HIPCHK(hipMemcpyAsync(ix->planes.p, planes.data(), planes.size() * 4, hipMemcpyHostToDevice, ix->stream));
+        HIPCHK(hipMemcpyAsync(ix->consts.p, consts.data(), consts.size() * 4, hipMemcpyHostToDevice, ix->stream));
+    }
+    if (f.n_leaf_ids) HIPCHK(hipMemcpyAsync(ix->leaf_ids.p, leaf_ids.data(), leaf_ids.size() * 4, hipMemcpyHostToDevice, ix->stream));
+    if (f.flags & 1u) {
+        if ((rc = ix->plane_samples.ensure((size_t)std::max(np, 1u) * sizeof(uint2)))) return rc;
+        if (np) HIPCHK(hipMemcpyAsync(ix->plane_samples.p, samples.data(), samples.size() * 4, hipMemcpyHostToDevice, ix->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ix->stream));
+    ix->n_planes = np;
+    ix->n_leaf_ids = f.n_leaf_ids;
+    ix->planes_below_level.swap(levels);
+    ix->samples_valid = (f.flags & 1u) != 0;
+    rc = upload_nodes(ix);
+    ix->scan_unsafe = (f.flags & 2u) != 0 || fc.dup_in_tree;
+    return rc;
+}
+
+extern "C" int zh_index_load(const char *path, int32_t device, uint64_t reserve_rows, zh_index **out, zh_snapshot_info *info) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (out) *out = nullptr;
+    if (info) memset(info, 0, sizeof *info);
+    int rc = no_device_for_snapshot("zh_index_load");
+    if (rc) return rc;
+    if (!path || !out) return fail(ZH_EINVAL, "zh_index_load: null argument");
+    ZhSnapHeader h;
+    int fd;
+    if ((rc = zh_snap_open(path, &fd, &h))) return rc;  // every size tested against the file's length and the limits: nothing allocated yet
+    struct FdGuard { int fd; ~FdGuard() { zh_snap_close(fd); } } fg{fd};
+    const zh_snapshot_info &f = h.info;
+    zh_options opt;
+    zh_options_default(&opt);
+    opt.dim = f.dim; opt.max_node_size = f.max_node_size; opt.num_trees = f.num_trees_option; opt.seed = f.seed; opt.id_base = f.id_base;
+    opt.device = device;
+    opt.reserve_rows = std::max<uint64_t>(reserve_rows, f.stored_rows);
+    zh_index *ix = nullptr;
+    if ((rc = zh_index_create(&opt, &ix))) return rc;
+    opt.reserve_rows = reserve_rows;
+    ix->opt.reserve_rows = reserve_rows;
+    double ms_device = 0;
+    uint64_t sum = 0;
+    const ZhSnapSection *rows = zh_snap_find(&h, ZH_SEC_ROWS);
+    rc = zh_snap_rows_in(fd, rows->offset, ix->X.p, rows->length, &sum, &ms_device);
+    if (!rc && sum != rows->checksum)
+        rc = fail(ZH_ECORRUPT, "zh_index_load: checksum mismatch in the rows as they arrived in device memory (section %u)", rows->kind);
+    if (!rc) {
+        ix->n_rows = f.stored_rows;
+        rc = load_forest(ix, fd, h);
+    }
+    if (rc) {
+        const std::string why = g_err;  // (destroy may overwrite the message)
+        zh_index_destroy(ix);
+        g_err = why;
+        return rc;
+    }
+    *out = ix;
+    if (info) {
+        *info = f;
+        info->verified = 1;
+        info->ms_device = ms_device;
+        info->ms = wall_ms_since(t_begin);
+    }
     return ZH_OK;
 }
 

@@ -409,3 +409,11 @@ hipError_t zh_launch_move_rows(const float *dSrc, float *dDst, uint32_t d, const
 hipError_t zh_launch_renumber_ids(uint32_t *dIds, uint64_t n, const uint32_t *dNewRow, uint64_t rows_before, hipStream_t s);
 // *dFlag |= 1 when a sample row was removed
 hipError_t zh_launch_renumber_samples(uint2 *dSamples, uint32_t n, const uint32_t *dNewRow, uint64_t rows_before, uint32_t *dFlag, hipStream_t s);
+
+// ---- snapshots (zh_snapshot.hip): zh_index_save / zh_index_load ----------------------------------------------------------------------
+// *dSum += the section checksum's terms (zh_snapfile.h) of the n_bytes at dBytes (8-byte aligned), whose first word is word `word0` of its section
+hipError_t zh_launch_snap_sum(const void *dBytes, uint64_t n_bytes, uint64_t word0, uint64_t *dSum, hipStream_t s);
+// the row table between device memory and the file, in chunks of ZH_SNAPSHOT_CHUNK_BYTES through two pinned buffers on a stream of the call's
+// own; *out_sum = the checksum of the bytes as they were (out) / arrived (in) in DEVICE memory, *ms_device the hipEvent time of the device work
+int zh_snap_rows_out(int fd, const char *path, uint64_t file_off, const void *dSrc, uint64_t n_bytes, uint64_t *out_sum, double *ms_device);
+int zh_snap_rows_in(int fd, uint64_t file_off, void *dDst, uint64_t n_bytes, uint64_t *out_sum, double *ms_device);

@@ -3,6 +3,7 @@
 Names, argument meaning and error behaviour follow the reference (file:line in each docstring);
 all arithmetic happens in libzebra_hip.so on the GPU."""
 import ctypes as C
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -122,6 +123,14 @@ class PNormDistance(_Metric):
         self.power = self.mode = int(power)
 
 
+def snapshot_info(path, verify=False):
+    """zh_snapshot_inspect (host code only, no GPU needed): the header of a snapshot file after every test a load applies to the header block,
+    the section table and the padding; verify=True recomputes every section's checksum on the host as well."""
+    info = _ffi.SnapshotInfo()
+    check(lib().zh_snapshot_inspect(os.fsencode(path), 1 if verify else 0, C.byref(info)))
+    return info.as_dict()
+
+
 # ------------------------------------------------------------------- src/database/index/lsh.rs
 @dataclass
 class LSHIndexOptions:
@@ -223,6 +232,27 @@ class LSHIndex:
         info = _ffi.CompactInfo()
         check(lib().zh_index_compact(self._h, _p(new_ids), n, C.byref(info)))
         return new_ids, info.as_dict()
+
+    def save(self, path):
+        """zh_index_save: the index as ONE snapshot file at `path` (written beside it first, then renamed over it) -> dict of zh_snapshot_info.
+        Rows (removed ones included), removals, the forest and the planes' sample rows are saved; derived copies and tuning state are not."""
+        info = _ffi.SnapshotInfo()
+        check(lib().zh_index_save(self._h, os.fsencode(path), C.byref(info)))
+        return info.as_dict()
+
+    @classmethod
+    def load(cls, path, device=-1, reserve_rows=0):
+        """zh_index_load: a new index from a snapshot file, indistinguishable from the saved one for every later call (its options come
+        from the file).  The dict of zh_snapshot_info is kept as .snapshot."""
+        info = _ffi.SnapshotInfo()
+        h = C.c_void_p()
+        check(lib().zh_index_load(os.fsencode(path), device, reserve_rows, C.byref(h), C.byref(info)))
+        self = cls.__new__(cls)
+        self._h = h
+        self.dim, self.id_base = int(info.dim), int(info.id_base)
+        self.options = LSHIndexOptions(int(info.max_node_size), int(info.num_trees_option))
+        self.snapshot = info.as_dict()
+        return self
 
     def set_forest(self, arrays):
         a = {k: np.ascontiguousarray(v) for k, v in arrays.items()}

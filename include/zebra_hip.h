@@ -425,7 +425,17 @@ ZH_API int zh_distance_pair(int metric, int cosine_mode, const float *a, const f
 
 /* Shard merge: S lists of b x k (ids, keys) with counts S x b, all in device memory (e.g. the
  * output of an RCCL all-gather of every rank's zh_search_batch_device result) -> b x k merged.
- * The kernel is enqueued on `stream` and the call returns; synchronise the stream before reading. */
+ * The kernel is enqueued on `stream` and the call returns; synchronise the stream before reading.
+ * The contract, per query, of this call and of zh_merge_topk_packed_device:
+ *   - list s contributes its entries j < min(d_counts[s*b + q], k).  Slots past a list's count are never read,
+ *     whatever they hold, and a count above k is treated as k;
+ *   - the answer is the k smallest of those entries by (key, id) as unsigned 64-bit pairs; identical (key, id)
+ *     pairs from different lists appear once (a repeated id is expected to carry the same key, as one row does);
+ *   - d_out_counts[q] is the number of entries kept; output slots past it are UINT64_MAX in ids and in keys;
+ *   - an entry whose key AND id are both UINT64_MAX is that marker of an empty slot and is dropped;
+ *   - the inputs are not written, and nothing outside the b*k ids, b*k keys and b counts of the outputs is.
+ * top_k outside 1..1024 is ZH_ELIMIT, n_shards outside 1..1024 and a null pointer with b > 0 are ZH_EINVAL, all judged
+ * before a device is touched; b = 0 is ZH_OK and launches nothing. */
 ZH_API int zh_merge_topk_device(int device, uint32_t n_shards, size_t b, size_t k, const uint64_t *d_ids,
                          const uint64_t *d_keys, const uint32_t *d_counts, uint64_t *d_out_ids,
                          uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream);

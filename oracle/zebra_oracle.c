@@ -1050,26 +1050,35 @@ ZO_EXPORT void zo_hash_signs(const zo_forest *f, const float *q, uint8_t *out_si
 }
 
 /* S-shard merge: per query, S lists of <= k (key,id) pairs sorted or not; keep the k
- * smallest by (key,id).  lists are [S][b][k] with counts [S][b]. */
+ * smallest DISTINCT by (key,id), the contract of the device's merge kernels: a list's slots past its count are
+ * never read, a count above k is taken as k, and of a run of equal ids in the sorted order (the same (key, id)
+ * arriving from several lists) only the first is kept.  lists are [S][b][k] with counts [S][b]; the output's
+ * slots past out_counts are left as they were. */
 ZO_EXPORT void zo_merge_topk(uint32_t S, uint64_t b, uint32_t k, const uint64_t *ids, const uint64_t *keys,
                              const uint32_t *counts, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts) {
     typedef struct { uint64_t id, key; } mp;
     mp *buf = malloc((size_t)S * k * sizeof(mp) + 16);
     for (uint64_t q = 0; q < b; q++) {
         uint32_t n = 0;
-        for (uint32_t s = 0; s < S; s++)
-            for (uint32_t i = 0; i < counts[s * b + q]; i++) {
+        for (uint32_t s = 0; s < S; s++) {
+            uint32_t c = counts[s * b + q] < k ? counts[s * b + q] : k;
+            for (uint32_t i = 0; i < c; i++) {
                 buf[n].id = ids[((size_t)s * b + q) * k + i];
                 buf[n].key = keys[((size_t)s * b + q) * k + i];
                 n++;
             }
+        }
         for (uint32_t i = 1; i < n; i++) { /* insertion sort: S*k is small */
             mp v = buf[i]; int64_t j = (int64_t)i - 1;
             while (j >= 0 && (buf[j].key > v.key || (buf[j].key == v.key && buf[j].id > v.id))) { buf[j + 1] = buf[j]; j--; }
             buf[j + 1] = v;
         }
-        uint32_t m = n < k ? n : k;
-        for (uint32_t i = 0; i < m; i++) { out_ids[q * k + i] = buf[i].id; out_keys[q * k + i] = buf[i].key; }
+        uint32_t m = 0;
+        for (uint32_t i = 0; i < n && m < k; i++) {
+            if (i && buf[i].id == buf[i - 1].id) continue; /* the same row from another list */
+            out_ids[q * k + m] = buf[i].id; out_keys[q * k + m] = buf[i].key;
+            m++;
+        }
         out_counts[q] = m;
     }
     free(buf);

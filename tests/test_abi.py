@@ -79,6 +79,33 @@ def test_no_cpu_fallback_without_gpu():
         zebra_amd.L2SquaredDistance().distance([1, 2, 3, 4], [1, 2, 3, 5])
 
 
+def test_merge_refuses_bad_arguments_before_touching_a_device():
+    """zh_merge_topk_device / zh_merge_topk_packed_device check their arguments before they pick a device: the refusals need no
+    GPU.  A null pointer is judged first, then top_k, then the shard count.  The limits are tried on an empty batch only (b = 0,
+    with and without pointers): if one of them were lost, the call would launch nothing and fail its assertion.  "Any one null
+    pointer with b > 0" cannot be tried that way: those calls rest on the null check itself, the first line of either function."""
+    from zebra_amd import _ffi
+    L = _ffi.lib()
+    p = ctypes.c_void_p(0x1000)  # never followed: b = 0 wherever every pointer is set
+
+    def plain(S, b, k, ptrs):
+        return L.zh_merge_topk_device(0, S, b, k, *ptrs, None)
+
+    def packed(S, b, k, ptrs):
+        return L.zh_merge_topk_packed_device(0, S, b, k, *ptrs, None)
+
+    for call, n_ptrs in ((plain, 6), (packed, 4)):
+        for ptrs in ((None,) * n_ptrs, (p,) * n_ptrs):
+            assert call(4, 0, 0, ptrs) == _ffi.ZH_ELIMIT and b"top_k" in L.zh_last_error()
+            assert call(4, 0, 1025, ptrs) == _ffi.ZH_ELIMIT
+            assert call(0, 0, 10, ptrs) == _ffi.ZH_EINVAL and b"n_shards" in L.zh_last_error()
+            assert call(1025, 0, 10, ptrs) == _ffi.ZH_EINVAL
+        for i in range(n_ptrs):  # any one null pointer with b > 0
+            ptrs = tuple(None if j == i else p for j in range(n_ptrs))
+            assert call(4, 5, 10, ptrs) == _ffi.ZH_EINVAL and b"null" in L.zh_last_error(), i
+        assert call(4, 5, 0, (None,) * n_ptrs) == _ffi.ZH_EINVAL  # (the null pointer is judged before top_k)
+
+
 def test_product_does_not_import_the_oracle():
     """only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may touch oracle/"""
     pkg = os.path.join(ROOT, "zebra_amd")

@@ -174,6 +174,81 @@ def test_a_list_that_runs_over_sends_the_batch_to_the_sweep(za):
     ix.close()
 
 
+def _rows_with_a_crowded_leaf(n_close):
+    """9000 random rows, n_close of them within 1e-3 per column of row 4000, and a batch whose last two queries sit among those.
+
+    A plane is made of two rows drawn from the whole set (lsh.rs:197-201), so it never passes between rows this close: every tree
+    keeps them in ONE leaf of n_close rows.  With n_close below k the walk of such a query takes that leaf whole and wanders on
+    through the rest of the tree.  The leaf is longer than the 8 rows a lane judges, so its visit takes the exact path: its rows
+    join the pair's list beside the k nearest of the other rows (they are nearer than all of those) without moving the list's
+    threshold.  Each of the T lists of these two queries then holds n_close + k entries (the oracle's walk, replayed with
+    zh_prefilter_bound's half-widths, gives exactly that; the other queries' lists hold k, one of them k + 1 once), the SAME
+    n_close + k rows in every tree, since every walk here sees nearly the whole tree."""
+    n, d, B = 9000, 128, 16
+    rng = np.random.default_rng(7)
+    X = zo.synth_rows(n, d)
+    X[4000:4000 + n_close] = X[4000] + rng.standard_normal((n_close, d)).astype(np.float32) * np.float32(1e-3)
+    Q = np.concatenate([zo.synth_queries(B - 2, d, n), X[[4000]], X[[4001]] + np.float32(1e-3)])
+    return X, Q, zo.synth_queries(B, d, n, b0=B)
+
+
+# Both cases below: 15 trees, k = 40, lists of cap = 256 slots (the library's own choice for k > 32).  T * cap = 3840 <= 4096 and
+# T * k = 600 <= 768, so zh_launch_final_lists hands them to merge_wave_kernel with L = 256 != k, which sorts at most 1024 entries.
+def test_lists_of_repeated_rows_that_fit_the_final_sort(za):
+    """20 close rows: the two queries among them bring 15 lists of 60 entries, 900 <= 1024, every row 15 times over"""
+    M, T, k = 5, 15, 40
+    X, Q, _ = _rows_with_a_crowded_leaf(20)
+    ix = _index(za, X, M, T)
+    fo = ix.get_forest()
+    assert fo["right"][fo["plane"] < 0].max() == 20
+    f = zo.Forest.from_arrays(X, M, fo)
+    for metric in ("l2sq", "l2"):
+        m, om, omode = _metric(za, metric)
+        oi, ok, oc = f.search_batch(Q, k, om, omode)
+        assert (oc == k).all() and np.isin(np.arange(4000, 4020), oi[-1]).all() and np.isin(np.arange(4000, 4020), oi[-2]).all()
+        ix.search_batch(Q, k, m)  # (an index's first wandering batch may outgrow the visit log and be swept)
+        for _ in range(2):
+            ids, keys, counts = ix.search_batch(Q, k, m)
+            st = ix.stats()
+            assert st["prefiltered"] == 1, (metric, st["prefilter_last_overflow"])
+            # the lists of the batch: 15 * k for every query, 15 * 20 more for the two among the close rows, a few that the bound
+            # cannot rule out.  This pins that the wave kernel really got lists of 60 of 256 slots; the window comes from a replay
+            # of the oracle's walk with zh_prefilter_bound's half-widths, so a change to that bound may legitimately move it
+            assert 16 * T * k + 2 * T * 20 <= st["prefilter_exact_rows"] <= 16 * T * k + 2 * T * 20 + 16 * T, st["prefilter_exact_rows"]
+            _same(ids, keys, counts, oi, ok, oc, metric)
+            assert (ids[np.arange(k)[None, :] >= counts[:, None]] == np.uint64(0xFFFFFFFFFFFFFFFF)).all()
+    assert ix.stats()["prefilter_fallbacks_accum"] == 0
+    ix.close()
+
+
+def test_lists_that_overflow_the_final_sort_send_the_batch_to_the_sweep(za):
+    """38 close rows: 15 lists of 78 entries, 1170 > 1024.  No list runs over its 256 slots (bits 1 and 2) and the table of
+    ambiguous visits holds them all (bit 4): the merge alone reports it, bit 16, and the batch is redone with the sweep"""
+    M, T, k = 5, 15, 40
+    X, Q, Q_plain = _rows_with_a_crowded_leaf(38)
+    ix = _index(za, X, M, T)
+    fo = ix.get_forest()
+    assert fo["right"][fo["plane"] < 0].max() == 38
+    f = zo.Forest.from_arrays(X, M, fo)
+    m = za.L2SquaredDistance()
+    ix.search_batch(Q_plain, k, m)  # (the first wandering batch may be swept)
+    ids, keys, counts = ix.search_batch(Q_plain, k, m)
+    st = ix.stats()
+    assert st["prefiltered"] == 1 and st["prefilter_fallbacks_accum"] == 0, st  # the index is one the prefilter serves
+    _same(ids, keys, counts, *f.search_batch(Q_plain, k, zo.L2SQ, 0), "random queries")
+    oi, ok, oc = f.search_batch(Q, k, zo.L2SQ, 0)
+    ids, keys, counts = ix.search_batch(Q, k, m)
+    st = ix.stats()
+    assert st["prefilter_last_overflow"] & 16, st["prefilter_last_overflow"]
+    assert st["prefilter_last_overflow"] == 16, st["prefilter_last_overflow"]
+    assert st["prefilter_fallbacks_accum"] == 1 and st["prefiltered"] == 0, st
+    _same(ids, keys, counts, oi, ok, oc, "redone with the sweep")
+    ids, keys, counts = ix.search_batch(Q_plain, k, m)  # one strike does not switch the prefilter off
+    assert ix.stats()["prefiltered"] == 1 and ix.stats()["prefilter_fallbacks_accum"] == 1
+    _same(ids, keys, counts, *f.search_batch(Q_plain, k, zo.L2SQ, 0), "afterwards")
+    ix.close()
+
+
 def test_prefilter_follows_inserts_and_removals(za):
     n0, n1, d, M, T, k, B = 12000, 3000, 256, 5, 4, 10, 16
     X = zo.synth_rows(n0 + n1, d)

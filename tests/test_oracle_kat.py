@@ -225,6 +225,32 @@ def test_shard_merge_property(S):
         assert [(int(ok[q, i]), int(oi[q, i])) for i in range(oc[q])] == pool
 
 
+def test_shard_merge_keeps_one_of_identical_pairs():
+    """the same (key, id) arriving from several lists is one answer, as on the device (the prefilter's per-tree lists hold the same
+    row many times); slots past a count are not read and a count above k reads k"""
+    k = 4
+    #                 list 0                              list 1                              list 2
+    ids = np.array([[[10, 11, 12, 13]], [[10, 20, 12, 21]], [[10, 11, 30, 99]]], np.uint64)
+    keys = np.array([[[5, 6, 7, 9]], [[5, 6, 7, 8]], [[5, 6, 1, 0]]], np.uint64)  # id 10 three times, 11 and 12 twice
+    counts = np.array([[4], [4], [3]], np.uint32)                                    # (key 0, id 99) lies past list 2's count
+    oi, ok, oc = zo.merge_topk(ids, keys, counts, k)
+    assert oc.tolist() == [4]
+    assert list(zip(ok[0].tolist(), oi[0].tolist())) == [(1, 30), (5, 10), (6, 11), (6, 20)]
+    # every list the same list: the answer is that list, sorted
+    same = np.repeat(np.array([[[7, 3, 9]]], np.uint64), 5, axis=0)
+    skeys = np.repeat(np.array([[[70, 30, 30]]], np.uint64), 5, axis=0)
+    oi, ok, oc = zo.merge_topk(same, skeys, np.full((5, 1), 3, np.uint32), 3)
+    assert oc.tolist() == [3] and list(zip(ok[0].tolist(), oi[0].tolist())) == [(30, 3), (30, 9), (70, 7)]
+    # fewer distinct entries than k: the count says so
+    oi, ok, oc = zo.merge_topk(same[:2, :, :2], skeys[:2, :, :2], np.full((2, 1), 2, np.uint32), 2)
+    assert oc.tolist() == [2] and oi[0].tolist() == [3, 7]
+    oi, ok, oc = zo.merge_topk(np.array([[[4, 4]]], np.uint64), np.array([[[1, 1]]], np.uint64), np.array([[2]], np.uint32), 2)
+    assert oc.tolist() == [1] and (int(ok[0, 0]), int(oi[0, 0])) == (1, 4)
+    # a count above k is k
+    oi, ok, oc = zo.merge_topk(ids, keys, np.array([[11], [4], [0]], np.uint32), k)
+    assert list(zip(ok[0, :oc[0]].tolist(), oi[0, :oc[0]].tolist())) == [(5, 10), (6, 11), (6, 20), (7, 12)]
+
+
 def test_search_matches_definition_and_recall():
     """search == sort(union of per-tree candidates) and finds planted neighbours (L2 and corrected cosine);
     literal cosine returns the LEAST similar candidates."""

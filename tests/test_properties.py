@@ -1,5 +1,6 @@
 """Property tests (hypothesis) of the invariants the design leans on, on the oracle:
-  * S-shard merge == global top-k of the union (SURVEY s8e parity definition), any counts / ties;
+  * S-shard merge == global top-k of the union (SURVEY s8e parity definition), any counts / ties, the union taken as a SET:
+    the same (key, id) from several lists is one entry;
   * union of per-leaf top-k == top-k of the union of the leaves' rows when every take equals k
     (why the distances need not be recomputed in the rerank);
   * the walk's control flow depends only on signs, leaf lengths and n: two metrics give the same visit list."""
@@ -20,6 +21,15 @@ def test_merge_is_topk_of_union(S, b, k, seed):
     oi, ok, oc = zo.merge_topk(ids, keys, counts, k)
     for q in range(b):
         pool = sorted((int(keys[s, q, i]), int(ids[s, q, i])) for s in range(S) for i in range(counts[s, q]))[:k]
+        assert [(int(ok[q, i]), int(oi[q, i])) for i in range(oc[q])] == pool
+    # the same with rows that several lists hold: ids drawn with repeats, a row's key a function of (query, id)
+    ids = rng.integers(0, max(2, S * k // 2), (S, b, k)).astype(np.uint64)
+    row_keys = rng.integers(0, 20, (b, int(ids.max()) + 1)).astype(np.uint64)
+    keys = np.stack([np.take_along_axis(row_keys, ids[s].astype(np.int64), 1) for s in range(S)])
+    oi, ok, oc = zo.merge_topk(ids, keys, counts, k)
+    for q in range(b):
+        pool = sorted({(int(keys[s, q, i]), int(ids[s, q, i])) for s in range(S) for i in range(counts[s, q])})[:k]
+        assert oc[q] == len(pool)
         assert [(int(ok[q, i]), int(oi[q, i])) for i in range(oc[q])] == pool
 
 

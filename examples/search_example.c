@@ -67,6 +67,21 @@ int main(void) {
     ok = ok && follow && ci.rows_before == (uint64_t)N + 100 && ci.rows_after == (uint64_t)N - 1 && zh_index_stored_rows(idx) == (uint64_t)N - 1 &&
          new_ids[997] == UINT64_MAX && new_ids[998] == 997;
     free(new_ids);
+
+    /* filtered search: the exact nearest neighbours among the even stored rows only (one bit per stored row, set = allowed) */
+    stored = zh_index_stored_rows(idx);
+    uint32_t *filter = calloc((stored + 31) / 32, sizeof(uint32_t));
+    for (uint64_t r = 0; r < stored; r += 2) filter[r >> 5] |= 1u << (r & 31);
+    CHECK(zh_search_exact_filtered_batch(idx, q, B, K, ZH_L2SQ, 0, filter, stored, ids, keys, counts));
+    zh_filtered_info fi;
+    CHECK(zh_search_filtered_info(idx, &fi));
+    int even = fi.rows_allowed == (stored + 1) / 2;
+    for (int b = 0; b < B; b++)
+        for (uint32_t j = 0; j < counts[b]; j++) even &= ids[b * K + j] % 2 == 0;
+    printf("filtered: %llu of %llu rows allowed, path %u; neighbours %s\n", (unsigned long long)fi.rows_allowed,
+           (unsigned long long)fi.rows_live, fi.path, even ? "all allowed" : "NOT all allowed");
+    ok = ok && even;
+    free(filter);
     zh_index_destroy(idx);
     free(rows);
     free(q);

@@ -248,6 +248,30 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
             for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * top_k + j], keys[i * top_k + j]);
         return out;
     }
+    // the exact k nearest neighbours among the live rows a bitmap allows (zh_search_exact_filtered_batch): bit r & 31 of filter_words[r >> 5]
+    // set = stored row r may be returned; n_bits rows are spoken for, rows past them are not allowed.  One filter for the whole batch.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> search_exact_filtered_batch(const std::vector<Embedding<N>> &queries, std::size_t top_k,
+                                                                                        const Met &metric,
+                                                                                        const std::vector<std::uint32_t> &filter_words,
+                                                                                        std::uint64_t n_bits) const {
+        const std::size_t b = queries.size();
+        if (filter_words.size() < (n_bits + 31) / 32) throw std::invalid_argument("search_exact_filtered_batch: filter shorter than n_bits");
+        std::vector<Id> ids(b * top_k);
+        std::vector<DistanceUnit> keys(b * top_k);
+        std::vector<std::uint32_t> counts(b);
+        check(zh_search_exact_filtered_batch(h_.get(), b ? queries[0].data() : nullptr, b, top_k, Met::metric, metric.mode(),
+                                             n_bits ? filter_words.data() : nullptr, n_bits, ids.data(), keys.data(), counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(b);
+        for (std::size_t i = 0; i < b; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * top_k + j], keys[i * top_k + j]);
+        return out;
+    }
+    zh_filtered_info filtered_info() const {
+        zh_filtered_info info{};
+        check(zh_search_filtered_info(h_.get(), &info));
+        return info;
+    }
     zh_index *handle() const { return h_.get(); }
 
   private:

@@ -25,6 +25,7 @@
  *                                        this rank's shard, ONE RCCL all-gather of the packed top-k, merge on every rank
  *   zh_merge_topk_device                 (new) the shard merge alone
  *   zh_search_exact_batch[_device]       (new) exact top-k over every live row under the same keys: recall ground truth
+ *   zh_search_exact_filtered_batch[_device] (new) the exact top-k among the live rows a caller's bitmap allows
  *   zh_index_save / zh_index_load        (new) a snapshot of an index in ONE file of this library's own format (the reference persists through
  *                                        fjall, lsh.rs:62-120, whose files are not read here): rows, removals, forest and the planes' sample rows
  *
@@ -372,6 +373,39 @@ typedef struct zh_exact_info {  /* the most recent zh_search_exact_* call on thi
     uint64_t launches;    /* row-chunk launches of the scan */
 } zh_exact_info;
 ZH_API int zh_search_exact_info(const zh_index *idx, zh_exact_info *out);
+
+/* Filtered exact search (new; the reference has no filter): zh_search_exact_batch over the rows a bitmap allows.  Bit r of the filter is bit
+ * r & 31 of filter_words[r >> 5]; set: stored row r (id zh_index_id_base + r) may be returned.  n_bits is how many rows the bitmap speaks for:
+ * rows at and past it are not allowed (a filter made before a later append stays valid), bits of the last word past it are ignored, and
+ * n_bits > zh_index_stored_rows is ZH_EINVAL (a bitmap made for another table, for instance before zh_index_compact renumbered the rows).  A NULL
+ * filter with n_bits > 0 is ZH_EINVAL.  The answer is exactly what zh_search_exact_batch gives on an index that holds only the rows that are both
+ * allowed and live: the same ids, canonical keys and (key, id) order for every metric, power and cosine mode; out_counts[i] = min(k, allowed live
+ * rows), entries past it UINT64_MAX; k = 0, an empty filter and an empty index give counts of 0; k > ZH_MAX_TOPK is ZH_ELIMIT; no forest needed.
+ * One filter serves the whole batch.  Locking as for the exact search; zh_stats_t and zh_exact_info are left alone (zh_search_filtered_info
+ * describes the most recent filtered call), and so are the index's cached live-row views.
+ * The filter pass runs on the device (allowed AND live, counted, ranked into the ascending list of allowed live rows): nothing is uploaded
+ * but the filter itself.  Path 1 scores that list, so its cost follows the allowed rows.  Path 2 (same dims and metrics as the exact search, at
+ * least max(k, 8192) allowed live rows) scans the fp16 copy in chunks placed by the cumulative count of ALLOWED rows, and a 16-row tile with no
+ * allowed row is skipped before it is loaded; it is taken when the tiles it would load cost less than gathering the allowed rows (the measured
+ * rule: DESIGN.md s13).  Same answers either way. */
+ZH_API int zh_search_exact_filtered_batch(zh_index *idx, const float *q, size_t b, size_t k, int metric, int cosine_mode,
+                                          const uint32_t *filter_words, uint64_t n_bits, uint64_t *out_ids, uint64_t *out_keys,
+                                          uint32_t *out_counts);
+/* The same with queries, filter and results in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_search_exact_filtered_batch_device(zh_index *idx, const float *d_q, size_t b, size_t k, int metric, int cosine_mode,
+                                                 const uint32_t *d_filter_words, uint64_t n_bits, uint64_t *d_out_ids,
+                                                 uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream);
+typedef struct zh_filtered_info {  /* the most recent zh_search_exact_filtered_* call on this index */
+    uint64_t batch;         /* queries */
+    uint64_t rows_live;     /* live rows of the index */
+    uint64_t rows_allowed;  /* ... of them allowed by the filter: the rows ranked */
+    uint32_t path;          /* 1: canonical sums for every (allowed row, query) pair; 2: matrix-core intervals over the table, masked */
+    uint32_t redone;        /* path-2 internal batches whose lists ran over and were answered by path 1 instead */
+    uint64_t survivors;     /* path 2: (row, query) pairs that got the canonical key, over all queries */
+    uint64_t launches;      /* row-chunk launches of the scan */
+    uint64_t tiles_skipped; /* path 2: 16-row tiles with no allowed row, returned from before they were loaded (over all internal batches) */
+} zh_filtered_info;
+ZH_API int zh_search_filtered_info(const zh_index *idx, zh_filtered_info *out);
 
 /* Pipelined form of zh_search_batch_device (new; the reference has one blocking search per query): a context
  * is one in-flight batch with its own scratch.  The context calls do NOT take the index's internal lock (the blocking

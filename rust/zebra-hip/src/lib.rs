@@ -109,6 +109,19 @@ pub mod ffi {
     }
 
     #[repr(C)]
+    #[derive(Default, Clone, Copy)]
+    pub struct zh_filtered_info {
+        pub batch: u64,
+        pub rows_live: u64,
+        pub rows_allowed: u64,
+        pub path: u32,
+        pub redone: u32,
+        pub survivors: u64,
+        pub launches: u64,
+        pub tiles_skipped: u64,
+    }
+
+    #[repr(C)]
     #[derive(Default, Clone, Copy, Debug)]
     pub struct zh_compact_info {
         pub rows_before: u64,
@@ -183,6 +196,13 @@ pub mod ffi {
         pub fn zh_search_exact_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
                                             d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_search_exact_info(idx: *const zh_index, out: *mut zh_exact_info) -> c_int;
+        pub fn zh_search_exact_filtered_batch(idx: *mut zh_index, q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
+                                              filter_words: *const u32, n_bits: u64, out_ids: *mut u64, out_keys: *mut u64,
+                                              out_counts: *mut u32) -> c_int;
+        pub fn zh_search_exact_filtered_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
+                                                     d_filter_words: *const u32, n_bits: u64, d_out_ids: *mut u64, d_out_keys: *mut u64,
+                                                     d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_search_filtered_info(idx: *const zh_index, out: *mut zh_filtered_info) -> c_int;
         pub fn zh_search_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
                                       d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_distance_pair(metric: c_int, cosine_mode: c_int, a: *const f32, b: *const f32, dim: usize, out_key: *mut u64,
@@ -460,6 +480,38 @@ impl<const N: usize> LSHIndex<N> {
         })?;
         let t = self.ids.read().unwrap();
         Ok((0..b).map(|i| (0..counts[i] as usize).map(|j| (t.of_row[ids[i * top_k + j] as usize], keys[i * top_k + j])).collect()).collect())
+    }
+
+    /// (new) the exact k nearest neighbours among the vectors `allowed` names (zh_search_exact_filtered_batch): the answer of an index that
+    /// held only those.  Unknown Uuids allow nothing; removed vectors are never returned.
+    pub fn search_exact_filtered_batch<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        queries: &[Embedding<N>],
+        top_k: usize,
+        metric: &Met,
+        allowed: &[Uuid],
+    ) -> anyhow::Result<Vec<Vec<(Uuid, DistanceUnit)>>> {
+        let b = queries.len();
+        let t = self.ids.read().unwrap();
+        let n_bits = unsafe { ffi::zh_index_stored_rows(self.hip.0) };
+        let mut words = vec![0u32; ((n_bits + 31) / 32) as usize];
+        for row in allowed.iter().filter_map(|u| t.row_of.get(u).copied()).filter(|r| *r < n_bits) {
+            words[(row >> 5) as usize] |= 1u32 << (row & 31);
+        }
+        let (mut ids, mut keys, mut counts) = (vec![0u64; b * top_k], vec![0u64; b * top_k], vec![0u32; b]);
+        check(unsafe {
+            ffi::zh_search_exact_filtered_batch(self.hip.0, queries.as_ptr() as *const f32, b, top_k, Met::METRIC, metric.param(),
+                                                if n_bits > 0 { words.as_ptr() } else { std::ptr::null() }, n_bits, ids.as_mut_ptr(),
+                                                keys.as_mut_ptr(), counts.as_mut_ptr())
+        })?;
+        Ok((0..b).map(|i| (0..counts[i] as usize).map(|j| (t.of_row[ids[i * top_k + j] as usize], keys[i * top_k + j])).collect()).collect())
+    }
+
+    /// what the most recent filtered search did (zh_search_filtered_info)
+    pub fn filtered_info(&self) -> anyhow::Result<ffi::zh_filtered_info> {
+        let mut info = ffi::zh_filtered_info::default();
+        check(unsafe { ffi::zh_search_filtered_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// lsh.rs:473-503 (as intended: the ids leave every tree)

@@ -259,6 +259,10 @@ struct zh_index {
         ex_Qh, ex_qmeta, ex_tau, ex_cnt, ex_lid, ex_llo, ex_lhi, ex_scr, ex_over;
     uint64_t ex_live_rows = ~0ull, ex_live_gen = ~0ull, ex_n_live = 0;
     zh_exact_info ex_info{};  // (stats_mu)
+    // the filtered exact search's per-call scratch (all released before the call returns): the caller's filter, allowed AND live by row and by
+    // position of the scan's row order, the blocks' counts and their exclusive sums, the ascending list of allowed live rows
+    DevBuf fl_filter, fl_bits, fl_pos, fl_bcount, fl_bexcl, fl_tmp, fl_list;
+    zh_filtered_info fl_info{};  // (stats_mu)
 
     bool broken = false;  // an incremental add failed half way: trees are stale until zh_index_build
     bool rows_torn = false;  // ... or a compaction failed after rows had begun to move (set with broken): the TABLE is inconsistent until zh_index_clear
@@ -3445,10 +3449,9 @@ static int exact_live_rows(zh_index *ix) {
 // one internal batch (B <= ZH_EXACT_BATCH) on device pointers, enqueued on s.  Row chunk after row chunk: keys of all queries into the
 // scratch, each query's top_k of every sub-chunk of L positions (select_kernel), a query's sub-chunks merged (final_kernel), the chunk's
 // answer merged into the running one (the caller's outputs) -- merge_wave_kernel / final_kernel<true>.
-static int exact_batch(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys,
-                       uint32_t *dCounts, hipStream_t s, uint64_t *launches) {
+static int exact_batch(zh_index *ix, const uint32_t *dLive, uint64_t n_live, const float *dQ, uint32_t B, uint32_t k, int metric, int mode,
+                       uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts, hipStream_t s, uint64_t *launches) {
     const uint32_t d = ix->opt.dim;
-    const uint64_t n_live = ix->ex_n_live;
     if (k == 0) { HIPCHK(hipMemsetAsync(dCounts, 0, (size_t)B * 4, s)); return ZH_OK; }
     if (n_live == 0) { HIPCHK(zh_launch_exact_empty(B, k, dIds, dKeys, dCounts, s)); return ZH_OK; }
     const uint32_t L = k <= 512 ? 2048u : 4096u, kk = std::min(k, L);
@@ -3463,7 +3466,6 @@ static int exact_batch(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, in
         (rc = ix->ex_run_counts.ensure((size_t)2 * B * 4)))
         return rc;
     const int param = metric == ZH_COSINE ? mode : ((metric == ZH_MINKOWSKI || metric == ZH_PNORM) ? mode : 0);
-    const uint32_t *dLive = ix->ex_live.as<uint32_t>();
     uint64_t *runIds = ix->ex_run_ids.as<uint64_t>(), *runKeys = ix->ex_run_keys.as<uint64_t>();
     uint32_t *runCounts = ix->ex_run_counts.as<uint32_t>();
     HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
@@ -3493,12 +3495,27 @@ static int exact_batch(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, in
 // Path 2 of one internal batch: the matrix-core interval scan in geometrically growing row chunks, a per-query tau and list, canonical keys for
 // the survivors, final_kernel's (key, id) top_k.  *used = false: path 2 does not serve this index / batch (path 1 answers); *overflowed: a list
 // ran over and the outputs are not valid (the caller answers the batch by path 1).
+// Under a filter (f; filter_prepare below) the scan reads f->dPos, the allowed-and-live bitmap by position, in place of the live bitmap, and the
+// chunks are placed by the cumulative count of ALLOWED rows (f->cum, per ZH_FILTER_BLOCK_ROWS positions): the first one ends where max(k, 4096) of
+// them have been seen, each later one holds ZH_EXACT_GROWTH times as many -- wherever in the table they sit, every query has its tau before a
+// large chunk arrives, exactly as without a filter.
 #define ZH_EXACT_GROWTH 4
+struct ExactFilter {
+    uint64_t n_allowed = 0;           // rows allowed and live
+    uint64_t tiles = 0;               // 16-position tiles of the scan that hold one (by position under a row order)
+    const uint32_t *dList = nullptr;  // ... ascending, for path 1 (made when path 1 is first needed: filter_list)
+    bool path2 = false;               // the path rule chose path 2 and the fp16 copy is there
+    const uint32_t *dPos = nullptr;   // path 2: the bitmap by position, made for this row order:
+    const uint32_t *perm = nullptr;
+    uint64_t perm_rows = 0;
+    std::vector<uint32_t> cum;        // exclusive sums of the allowed rows per block of positions (blocks + 1 entries)
+};
 static int exact_batch2(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts,
-                        hipStream_t s, bool *used, bool *overflowed, uint64_t *survivors, uint64_t *launches) {
+                        hipStream_t s, bool *used, bool *overflowed, uint64_t *survivors, uint64_t *launches, const ExactFilter *f = nullptr,
+                        uint64_t *tiles_skipped = nullptr) {
     *used = false; *overflowed = false;
     const uint32_t d = ix->opt.dim;
-    if (k == 0 || !zh_exact_mfma_supported(d, metric) || ix->ex_n_live < std::max<uint64_t>(k, 8192)) return ZH_OK;
+    if (k == 0 || !zh_exact_mfma_supported(d, metric) || (f ? f->n_allowed : ix->ex_n_live) < std::max<uint64_t>(k, 8192)) return ZH_OK;
     int rc;
     const void *Xh;
     const float2 *rowMeta;
@@ -3513,42 +3530,56 @@ static int exact_batch2(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, i
         Xh = ix->row_half.p; rowMeta = ix->row_meta.as<float2>(); rho = ix->row_rho;
         perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr; perm_rows = ix->perm_rows;
     }
+    if (f && (perm != f->perm || perm_rows != f->perm_rows)) return ZH_OK;  // (the row order changed since f->dPos was made: path 1)
     const uint32_t cap = 16384 + 8 * k;  // first chunk (<= max(k, 4096) rows, all listed) + a few growth steps' worth of k
     if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_Qh.ensure((size_t)B * d * 2)) || (rc = ix->ex_qmeta.ensure((size_t)B * 16)) ||
         (rc = ix->ex_tau.ensure((size_t)B * 4)) || (rc = ix->ex_cnt.ensure((size_t)B * 4)) || (rc = ix->ex_lid.ensure((size_t)B * cap * 4)) ||
         (rc = ix->ex_llo.ensure((size_t)B * cap * 4)) || (rc = ix->ex_lhi.ensure((size_t)B * cap * 4)) || (rc = ix->ex_scr.ensure((size_t)B * cap * 12)) ||
-        (rc = ix->ex_over.ensure(4)) || (rc = ix->ex_ckeys.ensure((size_t)B * cap * 8)) || (rc = ix->ex_cids.ensure((size_t)B * cap * 4)) ||
+        (rc = ix->ex_over.ensure(8)) || (rc = ix->ex_ckeys.ensure((size_t)B * cap * 8)) || (rc = ix->ex_cids.ensure((size_t)B * cap * 4)) ||
         (rc = ix->ex_cbase.ensure(((size_t)B + 1) * 8)))
         return rc;
-    ZhExact2 e{Xh, rowMeta, perm, perm_rows, ix->ex_bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B, zh_approx_bound(metric, d, 1), rho,
+    ZhExact2 e{Xh, rowMeta, perm, perm_rows, f ? f->dPos : ix->ex_bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B, zh_approx_bound(metric, d, 1), rho,
                ix->ex_tau.as<uint32_t>(), ix->ex_cnt.as<uint32_t>(), ix->ex_lid.as<uint32_t>(), ix->ex_llo.as<uint32_t>(), ix->ex_lhi.as<uint32_t>(), cap,
                ix->ex_over.as<uint32_t>()};
     HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
     HIPCHK(zh_launch_qhalf(dQ, B, d, ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), 1, s));
     HIPCHK(hipMemsetAsync(e.tau, 0xFF, (size_t)B * 4, s));
     HIPCHK(hipMemsetAsync(e.cnt, 0, (size_t)B * 4, s));
-    HIPCHK(hipMemsetAsync(e.over, 0, 4, s));
+    HIPCHK(hipMemsetAsync(e.over, 0, 8, s));  // (word 1: the filtered scan's skipped tiles)
     std::vector<uint64_t> cb(B + 1);
     for (uint32_t b = 0; b <= B; b++) cb[b] = (uint64_t)b * cap;
     HIPCHK(hipMemcpyAsync(ix->ex_cbase.p, cb.data(), cb.size() * 8, hipMemcpyHostToDevice, s));
     const uint64_t n = ix->n_rows;  // positions of the copy; removed rows are masked by the bitmap
     uint64_t chunk = (std::max<uint64_t>(k, 4096) + 15) / 16 * 16;
-    for (uint64_t p0 = 0; p0 < n; p0 += chunk, chunk *= ZH_EXACT_GROWTH) {
+    for (uint64_t p0 = 0; p0 < n && !f; p0 += chunk, chunk *= ZH_EXACT_GROWTH) {
         const uint64_t p1 = std::min(n, p0 + chunk);
         HIPCHK(zh_launch_exact_mfma(d, metric, mode, e, p0, p1, s));
         HIPCHK(zh_launch_exact_prune(e, k, ix->ex_scr.as<uint32_t>(), s));
         (*launches)++;
     }
+    if (f) {  // chunks of whole blocks, ended by the allowed rows seen (the first lists at most its target + a block's rows: below cap)
+        const size_t nb = f->cum.size() - 1;
+        uint64_t target = std::max<uint64_t>(k, 4096);
+        for (size_t j0 = 0; j0 < nb; target *= ZH_EXACT_GROWTH) {
+            size_t j1 = j0 + 1;
+            while (j1 < nb && f->cum[j1] - f->cum[j0] < target) j1++;
+            HIPCHK(zh_launch_exact_mfma(d, metric, mode, e, (uint64_t)j0 * ZH_FILTER_BLOCK_ROWS, std::min<uint64_t>(n, (uint64_t)j1 * ZH_FILTER_BLOCK_ROWS), s, true));
+            HIPCHK(zh_launch_exact_prune(e, k, ix->ex_scr.as<uint32_t>(), s));
+            (*launches)++;
+            j0 = j1;
+        }
+    }
     HIPCHK(zh_launch_exact_survivor_keys(ix->X.as<float>(), d, dQ, ix->ex_QQ.as<float>(), metric, mode, e, ix->ex_ckeys.as<uint64_t>(),
                                          ix->ex_cids.as<uint32_t>(), s));
     HIPCHK(zh_launch_final(ix->ex_cbase.as<uint64_t>(), B, 1, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), ix->opt.id_base, dIds, dKeys,
                            dCounts, nullptr, s));
-    std::vector<uint32_t> h_cnt(B + 1);
+    std::vector<uint32_t> h_cnt(B + 2);
     HIPCHK(hipMemcpyAsync(h_cnt.data(), e.cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h_cnt.data() + B, e.over, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_cnt.data() + B, e.over, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     *used = true;
     *overflowed = h_cnt[B] != 0;
+    if (tiles_skipped) *tiles_skipped += h_cnt[B + 1];
     if (!*overflowed)
         for (uint32_t b = 0; b < B; b++) *survivors += h_cnt[b];
     return ZH_OK;
@@ -3570,7 +3601,7 @@ static int exact_one(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, int 
     if (used) inf->path = 2;
     if (used && !overflowed) return ZH_OK;
     if (overflowed) inf->redone++;
-    return exact_batch(ix, dQ, B, k, metric, mode, dIds, dKeys, dCounts, s, &inf->launches);
+    return exact_batch(ix, ix->ex_live.as<uint32_t>(), ix->ex_n_live, dQ, B, k, metric, mode, dIds, dKeys, dCounts, s, &inf->launches);
 }
 
 static int exact_args(zh_index *ix, const float *q, size_t b, size_t k, int metric, int mode, const void *ids, const void *keys,
@@ -3650,6 +3681,196 @@ extern "C" int zh_search_exact_info(const zh_index *ix, zh_exact_info *out) {
     zh_index *m = const_cast<zh_index *>(ix);
     std::lock_guard<std::mutex> lk(m->stats_mu);
     *out = m->ex_info;
+    return ZH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// filtered exact search (zh_filter.hip + the exact search's two paths): only the rows a caller's bitmap allows are ranked
+// ------------------------------------------------------------------------------------------------
+// The path rule.  Path 1 gathers the allowed rows alone: its cost follows the allowed rows.  Path 2 streams every 16-row tile of the fp16 copy that
+// holds an allowed row and skips the others: its cost follows the rows of the tiles it loads, plus about one row's worth per skipped tile.  Per
+// row, path 1 costs ZH_FILTER_PATH1_ROW_COST times what path 2 does, so path 2 is taken when
+//     16 * loaded tiles + skipped tiles <= ZH_FILTER_PATH1_ROW_COST * allowed rows.
+// Measured with tests/probes/filter_probe.py on one MI355X at 10M x 768, 1024 queries, k = 100, L2SQ (table: DESIGN.md s13): all rows allowed,
+// path 1 633.3 ms against path 2 109.9 ms = 5.76; a skipped tile 7 - 18 ns against 11.0 ns per loaded row.  A random tenth of the rows leaves
+// few tiles empty and goes to path 1 (64.8 ms against 88.9); a contiguous tenth goes to path 2 (21.2 ms against 64.6).
+#define ZH_FILTER_PATH1_ROW_COST 5.75
+
+static void filter_release_scratch(zh_index *ix) {
+    exact_release_scratch(ix);
+    DevBuf *bs[] = {&ix->fl_filter, &ix->fl_bits, &ix->fl_pos, &ix->fl_bcount, &ix->fl_bexcl, &ix->fl_tmp, &ix->fl_list};
+    for (DevBuf *b : bs) b->release();
+}
+struct FilterScratchGuard {
+    zh_index *ix;
+    ~FilterScratchGuard() { filter_release_scratch(ix); }
+};
+
+// the ascending list of allowed live rows, from the row bitmap and the blocks' exclusive sums filter_prepare left
+static int filter_list(zh_index *ix, ExactFilter *f, hipStream_t s) {
+    int rc = ix->fl_list.ensure(std::max<uint64_t>(f->n_allowed, 1) * 4);
+    if (rc) return rc;
+    HIPCHK(zh_launch_filter_list(ix->fl_bits.as<uint32_t>(), ix->n_rows, ix->fl_bexcl.as<uint32_t>(), ix->fl_list.as<uint32_t>(), s));
+    f->dList = ix->fl_list.as<uint32_t>();
+    return ZH_OK;
+}
+
+// The filter pass of one call (under mu, exclusive; exact_live_rows has run): allowed AND live and its count, the path, and what that path reads --
+// the list (path 1), or the bitmap by position and the blocks' sums the chunks are placed by (path 2).  dFilter: n_bits bits in device memory.
+// Nothing comes from the host but the call's arguments; two small copies come back (the blocks' sums).  ZH_FILTER_PATH=1|2 (probes and tests,
+// read per call) forces a path where it can serve.
+static int filter_prepare(zh_index *ix, const uint32_t *dFilter, uint64_t n_bits, uint32_t k, int metric, hipStream_t s, ExactFilter *f) {
+    const uint64_t n = ix->n_rows;
+    if (!n) return ZH_OK;
+    const size_t nb = (size_t)((n + ZH_FILTER_BLOCK_ROWS - 1) / ZH_FILTER_BLOCK_ROWS);
+    int rc;
+    if ((rc = ix->fl_bits.ensure((n + 63) / 64 * 8)) || (rc = ix->fl_bcount.ensure(nb * 4)) || (rc = ix->fl_bexcl.ensure((2 * (nb + 1) + 1) * 4)) ||
+        (rc = ix->fl_tmp.ensure((nb / 1024 + 2) * 4)))
+        return rc;
+    uint32_t *excl = ix->fl_bexcl.as<uint32_t>();  // [0, nb]: by row; [nb + 1, 2 nb + 1]: by position under a row order; then the tile count
+    uint32_t *dTiles = excl + 2 * (nb + 1), h_tiles = 0;
+    HIPCHK(zh_launch_filter_and(dFilter, n_bits, ix->ex_bits.as<uint32_t>(), n, ix->fl_bits.as<uint32_t>(), ix->fl_bcount.as<uint32_t>(), excl,
+                                ix->fl_tmp.as<uint32_t>(), dTiles, s));
+    f->cum.resize(nb + 1);
+    HIPCHK(hipMemcpyAsync(f->cum.data(), excl, (nb + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&h_tiles, dTiles, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    f->n_allowed = f->cum[nb];
+    f->tiles = h_tiles;
+    const char *env_p = getenv("ZH_FILTER_PATH");
+    const int forced = env_p ? atoi(env_p) : 0;
+    f->path2 = forced != 1 && k && zh_exact_mfma_supported(ix->opt.dim, metric) && f->n_allowed >= std::max<uint64_t>(k, 8192);
+    if (f->path2) {
+        std::lock_guard<std::mutex> lb(ix->blk_mu);
+        bool ok = false;
+        if ((rc = ensure_row_half(ix, &ok))) return rc;
+        f->path2 = ok && ix->row_half.p;
+        f->perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr;
+        f->perm_rows = ix->perm_rows;
+    }
+    f->dPos = ix->fl_bits.as<uint32_t>();
+    if (f->path2 && f->perm) {  // position p holds row perm[p]: the mask once per call in that order, counted per block of positions
+        if ((rc = ix->fl_pos.ensure((n + 63) / 64 * 8))) return rc;
+        HIPCHK(zh_launch_filter_permute(ix->fl_bits.as<uint32_t>(), f->perm, f->perm_rows, n, ix->fl_pos.as<uint32_t>(), ix->fl_bcount.as<uint32_t>(),
+                                        excl + nb + 1, ix->fl_tmp.as<uint32_t>(), dTiles, s));
+        HIPCHK(hipMemcpyAsync(f->cum.data(), excl + nb + 1, (nb + 1) * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&h_tiles, dTiles, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        f->tiles = h_tiles;
+        f->dPos = ix->fl_pos.as<uint32_t>();
+    }
+    if (f->path2 && forced != 2) {
+        const uint64_t all_tiles = (n + 15) / 16;
+        f->path2 = (double)(16 * f->tiles + (all_tiles - f->tiles)) <= ZH_FILTER_PATH1_ROW_COST * (double)f->n_allowed;
+    }
+    return f->path2 ? ZH_OK : filter_list(ix, f, s);
+}
+
+// one internal batch under a filter: path 2 where the rule chose it, path 1 over the list otherwise and for a batch whose path-2 lists ran over
+static int filtered_one(zh_index *ix, ExactFilter *f, const float *dQ, uint32_t B, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys,
+                        uint32_t *dCounts, hipStream_t s, zh_filtered_info *inf) {
+    int rc;
+    if (f->path2) {
+        bool used = false, overflowed = false;
+        if ((rc = exact_batch2(ix, dQ, B, k, metric, mode, dIds, dKeys, dCounts, s, &used, &overflowed, &inf->survivors, &inf->launches, f,
+                               &inf->tiles_skipped)))
+            return rc;
+        if (used) inf->path = 2;
+        if (used && !overflowed) return ZH_OK;
+        if (overflowed) inf->redone++;
+        if (!f->dList && (rc = filter_list(ix, f, s))) return rc;
+    }
+    return exact_batch(ix, f->dList, f->n_allowed, dQ, B, k, metric, mode, dIds, dKeys, dCounts, s, &inf->launches);
+}
+
+static int filtered_args(zh_index *ix, const float *q, size_t b, size_t k, int metric, int mode, const uint32_t *filter, uint64_t n_bits, const void *ids,
+                         const void *keys, const void *counts, const char *who) {
+    int rc = exact_args(ix, q, b, k, metric, mode, ids, keys, counts, who);
+    if (rc) return rc;
+    if (n_bits && !filter) return fail(ZH_EINVAL, "%s: null filter for %llu rows", who, (unsigned long long)n_bits);
+    return ZH_OK;
+}
+
+static int filtered_bits_fit(zh_index *ix, uint64_t n_bits) {
+    if (n_bits > ix->n_rows)
+        return fail(ZH_EINVAL, "filter of %llu rows for a table of %llu: made for another table?", (unsigned long long)n_bits, (unsigned long long)ix->n_rows);
+    return ZH_OK;
+}
+
+static void filtered_record(zh_index *ix, size_t b, const ExactFilter &f, zh_filtered_info inf) {
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    inf.batch = b;
+    inf.rows_live = ix->ex_n_live;
+    inf.rows_allowed = f.n_allowed;
+    ix->fl_info = inf;
+}
+
+extern "C" int zh_search_exact_filtered_batch_device(zh_index *ix, const float *d_q, size_t b, size_t k, int metric, int mode, const uint32_t *d_filter,
+                                                     uint64_t n_bits, uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
+    int rc = filtered_args(ix, d_q, b, k, metric, mode, d_filter, n_bits, d_out_ids, d_out_keys, d_out_counts, "zh_search_exact_filtered_batch_device");
+    if (rc) return rc;
+    if (b == 0) return ZH_OK;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = filtered_bits_fit(ix, n_bits))) return rc;
+    FilterScratchGuard guard{ix};
+    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    const uint32_t d = ix->opt.dim;
+    ExactFilter f;
+    if ((rc = filter_prepare(ix, d_filter, n_bits, (uint32_t)k, metric, s, &f))) return rc;
+    zh_filtered_info inf{};
+    inf.path = 1;
+    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
+        if ((rc = filtered_one(ix, &f, d_q + b0 * d, nb, (uint32_t)k, metric, mode, d_out_ids + b0 * k, d_out_keys + b0 * k, d_out_counts + b0, s, &inf)))
+            return rc;
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    filtered_record(ix, b, f, inf);
+    return ZH_OK;
+}
+
+extern "C" int zh_search_exact_filtered_batch(zh_index *ix, const float *q, size_t b, size_t k, int metric, int mode, const uint32_t *filter,
+                                              uint64_t n_bits, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts) {
+    int rc = filtered_args(ix, q, b, k, metric, mode, filter, n_bits, out_ids, out_keys, out_counts, "zh_search_exact_filtered_batch");
+    if (rc) return rc;
+    if (b == 0) return ZH_OK;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = filtered_bits_fit(ix, n_bits))) return rc;
+    FilterScratchGuard guard{ix};
+    const hipStream_t s = ix->stream;
+    const uint32_t d = ix->opt.dim;
+    const size_t nb_max = std::min<size_t>(ZH_EXACT_BATCH, b), fwords = (size_t)((n_bits + 31) / 32);
+    if ((rc = ix->ex_Q.ensure(nb_max * d * 4)) || (rc = ix->ex_ids.ensure(std::max<size_t>(nb_max * k, 1) * 8)) ||
+        (rc = ix->ex_kout.ensure(std::max<size_t>(nb_max * k, 1) * 8)) || (rc = ix->ex_counts.ensure(nb_max * 4)) ||
+        (rc = ix->fl_filter.ensure(std::max<size_t>(fwords, 1) * 4)))
+        return rc;
+    if (fwords) HIPCHK(hipMemcpyAsync(ix->fl_filter.p, filter, fwords * 4, hipMemcpyHostToDevice, s));  // the call's only upload besides the queries
+    ExactFilter f;
+    if ((rc = filter_prepare(ix, ix->fl_filter.as<uint32_t>(), n_bits, (uint32_t)k, metric, s, &f))) return rc;
+    zh_filtered_info inf{};
+    inf.path = 1;
+    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
+        HIPCHK(hipMemcpyAsync(ix->ex_Q.p, q + b0 * d, (size_t)nb * d * 4, hipMemcpyHostToDevice, s));
+        if ((rc = filtered_one(ix, &f, ix->ex_Q.as<float>(), nb, (uint32_t)k, metric, mode, ix->ex_ids.as<uint64_t>(), ix->ex_kout.as<uint64_t>(),
+                               ix->ex_counts.as<uint32_t>(), s, &inf)))
+            return rc;
+        if (k) {
+            HIPCHK(hipMemcpyAsync(out_ids + b0 * k, ix->ex_ids.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_keys + b0 * k, ix->ex_kout.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipMemcpyAsync(out_counts + b0, ix->ex_counts.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    filtered_record(ix, b, f, inf);
+    return ZH_OK;
+}
+
+extern "C" int zh_search_filtered_info(const zh_index *ix, zh_filtered_info *out) {
+    if (!ix || !out) return fail(ZH_EINVAL, "zh_search_filtered_info: null argument");
+    zh_index *m = const_cast<zh_index *>(ix);
+    std::lock_guard<std::mutex> lk(m->stats_mu);
+    *out = m->fl_info;
     return ZH_OK;
 }
 

@@ -203,7 +203,9 @@ typedef uint32_t u32x4e __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ bool exact_live(const uint32_t *__restrict__ bits, uint32_t id) { return (bits[id >> 5] >> (id & 31)) & 1u; }
 
-template <int D, int KINDA>
+// FILT (the filtered search): liveBits is the allowed-and-live bitmap by POSITION (a tile's 16 positions are half a word of it), and a wave whose
+// tile is masked whole returns before it loads anything and counts itself in over[1]
+template <int D, int KINDA, bool FILT>
 __global__ __launch_bounds__(256) void exact_mfma_kernel(const u32x4e *__restrict__ Xh, const float2 *__restrict__ rowMeta,
                                                          const uint32_t *__restrict__ perm, uint64_t perm_rows, const uint32_t *__restrict__ liveBits,
                                                          uint64_t p_begin, uint64_t p_end, const u32x4e *__restrict__ Qh,
@@ -216,6 +218,12 @@ __global__ __launch_bounds__(256) void exact_mfma_kernel(const u32x4e *__restric
     const uint64_t tile = p_begin / 16 + (uint64_t)blockIdx.x * 4 + wid;
     const uint64_t p0 = tile * 16;
     if (p0 >= p_end) return;
+    if (FILT) {
+        if (((liveBits[p0 >> 5] >> (p0 & 31)) & 0xFFFFu) == 0u) {
+            if (lane == 0) atomicAdd(over + 1, 1u);
+            return;
+        }
+    }
     f16x8e A[NS];
     const u32x4e *tp = Xh + (size_t)tile * (NS * 64) + lane;
 #pragma unroll
@@ -229,7 +237,7 @@ __global__ __launch_bounds__(256) void exact_mfma_kernel(const u32x4e *__restric
         const uint64_t p = p0 + 4 * h + i;
         valid[i] = p < p_end;
         id[i] = valid[i] ? (perm && p < perm_rows ? perm[p] : (uint32_t)p) : 0u;
-        valid[i] = valid[i] && exact_live(liveBits, id[i]);
+        valid[i] = valid[i] && (FILT ? ((liveBits[p >> 5] >> (p & 31)) & 1u) != 0u : exact_live(liveBits, id[i]));
         meta[i] = valid[i] ? rowMeta[p] : make_float2(0.f, 0.f);
     }
     for (uint32_t q0 = 0; q0 < B; q0 += 16) {
@@ -351,32 +359,37 @@ bool zh_exact_mfma_supported(uint32_t d, int metric) {
     return (d == 256 || d == 384 || d == 512 || d == 768 || d == 1024) && (metric == ZH_L2SQ || metric == ZH_L2 || metric == ZH_COSINE);
 }
 
-template <int D, int KINDA>
+template <int D, int KINDA, bool FILT>
 static void launch_mfma_d(const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, hipStream_t s) {
     const uint64_t tiles = (p_end - p_begin + 15) / 16, blocks = (tiles + 3) / 4;
-    hipLaunchKernelGGL((exact_mfma_kernel<D, KINDA>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4e *)e.Xh, e.rowMeta, e.perm, e.perm_rows,
+    hipLaunchKernelGGL((exact_mfma_kernel<D, KINDA, FILT>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4e *)e.Xh, e.rowMeta, e.perm, e.perm_rows,
                        e.liveBits, p_begin, p_end, (const u32x4e *)e.Qh, e.qmeta, e.B, e.Kc, e.rho, e.tau, e.cnt, e.lid, e.llo, e.lhi, e.cap, e.over);
 }
 
-template <int KINDA>
+template <int KINDA, bool FILT>
 static hipError_t launch_mfma_kinda(uint32_t d, const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, hipStream_t s) {
     switch (d) {
-    case 256: launch_mfma_d<256, KINDA>(e, p_begin, p_end, s); break;
-    case 384: launch_mfma_d<384, KINDA>(e, p_begin, p_end, s); break;
-    case 512: launch_mfma_d<512, KINDA>(e, p_begin, p_end, s); break;
-    case 768: launch_mfma_d<768, KINDA>(e, p_begin, p_end, s); break;
-    case 1024: launch_mfma_d<1024, KINDA>(e, p_begin, p_end, s); break;
+    case 256: launch_mfma_d<256, KINDA, FILT>(e, p_begin, p_end, s); break;
+    case 384: launch_mfma_d<384, KINDA, FILT>(e, p_begin, p_end, s); break;
+    case 512: launch_mfma_d<512, KINDA, FILT>(e, p_begin, p_end, s); break;
+    case 768: launch_mfma_d<768, KINDA, FILT>(e, p_begin, p_end, s); break;
+    case 1024: launch_mfma_d<1024, KINDA, FILT>(e, p_begin, p_end, s); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
-hipError_t zh_launch_exact_mfma(uint32_t d, int metric, int mode, const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, hipStream_t s) {
+template <bool FILT>
+static hipError_t launch_mfma_filt(uint32_t d, int metric, int mode, const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, hipStream_t s) {
+    if (metric != ZH_COSINE) return launch_mfma_kinda<0, FILT>(d, e, p_begin, p_end, s);
+    if (mode == ZH_COSINE_PARITY) return launch_mfma_kinda<2, FILT>(d, e, p_begin, p_end, s);
+    return launch_mfma_kinda<1, FILT>(d, e, p_begin, p_end, s);
+}
+
+hipError_t zh_launch_exact_mfma(uint32_t d, int metric, int mode, const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, hipStream_t s, bool filtered) {
     if (p_begin >= p_end || !e.B) return hipSuccess;
     if (p_begin % 16) return hipErrorInvalidValue;
-    if (metric != ZH_COSINE) return launch_mfma_kinda<0>(d, e, p_begin, p_end, s);
-    if (mode == ZH_COSINE_PARITY) return launch_mfma_kinda<2>(d, e, p_begin, p_end, s);
-    return launch_mfma_kinda<1>(d, e, p_begin, p_end, s);
+    return filtered ? launch_mfma_filt<true>(d, metric, mode, e, p_begin, p_end, s) : launch_mfma_filt<false>(d, metric, mode, e, p_begin, p_end, s);
 }
 
 hipError_t zh_launch_exact_prune(const ZhExact2 &e, uint32_t k, uint32_t *dScratch, hipStream_t s) {

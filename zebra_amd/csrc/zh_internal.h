@@ -303,12 +303,28 @@ struct ZhExact2 {
     uint32_t *tau, *cnt, *lid, *llo, *lhi; uint32_t cap; uint32_t *over;
 };
 bool zh_exact_mfma_supported(uint32_t d, int metric);
-hipError_t zh_launch_exact_mfma(uint32_t d, int metric, int mode, const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, hipStream_t s);
+// filtered (zh_search_exact_filtered_batch): e.liveBits is the allowed-and-live bitmap BY POSITION (zh_launch_filter_permute under a row order), a
+// wave whose 16 positions are all masked returns before it loads its tile and counts itself in e.over[1]
+hipError_t zh_launch_exact_mfma(uint32_t d, int metric, int mode, const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, hipStream_t s,
+                                bool filtered = false);
 // dScratch: 3 * B * cap words
 hipError_t zh_launch_exact_prune(const ZhExact2 &e, uint32_t k, uint32_t *dScratch, hipStream_t s);
 hipError_t zh_launch_exact_survivor_keys(const float *dX, uint32_t d, const float *dQ, const float *dQQ, int metric, int mode, const ZhExact2 &e,
                                          uint64_t *dCKeys, uint32_t *dCIds, hipStream_t s);
 hipError_t zh_launch_exact_empty(uint32_t B, uint32_t k, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts, hipStream_t s);
+
+// ---- the filter pass of the filtered exact search (zh_filter.hip).  Bitmaps: bit r % 32 of word r / 32; n_blocks = ceil(n_rows / ZH_FILTER_BLOCK_ROWS);
+// dBlockCount: n_blocks entries, dBlockExcl: n_blocks + 1 (the last one the total), dScanTmp: n_blocks / 1024 + 2; *dTiles = 16-row tiles (of
+// rows, or of positions) that hold a set bit
+#define ZH_FILTER_BLOCK_ROWS 8192u
+// dOut = dFilter (n_bits bits, rows past them not allowed; may be null for n_bits = 0) AND dLiveBits, ceil(n_rows / 32) words
+hipError_t zh_launch_filter_and(const uint32_t *dFilter, uint64_t n_bits, const uint32_t *dLiveBits, uint64_t n_rows, uint32_t *dOut,
+                                uint32_t *dBlockCount, uint32_t *dBlockExcl, uint32_t *dScanTmp, uint32_t *dTiles, hipStream_t s);
+// bit p of dOut = bit (p < perm_rows ? dPerm[p] : p) of dBits; dOut: 8-byte aligned, ceil(n_rows / 64) * 2 words
+hipError_t zh_launch_filter_permute(const uint32_t *dBits, const uint32_t *dPerm, uint64_t perm_rows, uint64_t n_rows, uint32_t *dOut,
+                                    uint32_t *dBlockCount, uint32_t *dBlockExcl, uint32_t *dScanTmp, uint32_t *dTiles, hipStream_t s);
+// dList = the set bits of dBits, ascending (dBlockExcl as zh_launch_filter_and left it)
+hipError_t zh_launch_filter_list(const uint32_t *dBits, uint64_t n_rows, const uint32_t *dBlockExcl, uint32_t *dList, hipStream_t s);
 
 // ---- launchers (zh_score.hip): every sign of a forest built from stored rows, from N row scores per query --------
 // Prefilter (zh_search.hip, "Prefilter"): a batch hashed from row scores picks the rows that can be among a pair's k best from

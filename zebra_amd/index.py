@@ -335,6 +335,54 @@ class LSHIndex:
         check(lib().zh_search_exact_info(self._h, C.byref(info)))
         return info.as_dict()
 
+    def filter_bitmap(self, allowed):
+        """a filter for the filtered searches from a boolean mask over the stored rows (length up to stored_rows(); rows past it are not
+        allowed) or an integer array of ids -> (words u32, n_bits): bit r & 31 of word r >> 5 set = stored row r (id id_base + r) allowed"""
+        a = np.asarray(allowed)
+        if a.dtype == np.bool_:
+            mask = a.reshape(-1)
+        else:
+            rows = a.reshape(-1).astype(np.uint64) - np.uint64(self.id_base)
+            stored = self.stored_rows()
+            if rows.size and int(rows.max()) >= stored:
+                raise ValueError("an allowed id is outside this index's %d stored rows" % stored)
+            mask = np.zeros(stored, np.bool_)
+            mask[rows.astype(np.int64)] = True
+        words = np.packbits(mask, bitorder="little")
+        words = np.concatenate([words, np.zeros(-words.size % 4, np.uint8)]).view(np.uint32)
+        return np.ascontiguousarray(words), int(mask.size)
+
+    def search_exact_filtered_batch(self, queries, top_k, metric, allowed):
+        """search_exact_batch among the live rows `allowed` names (a boolean mask over the stored rows, or an array of ids): exactly the
+        answer of an index that held only those rows.  One filter for the whole batch; no forest needed."""
+        q = _f32(queries, self.dim)
+        b = q.shape[0]
+        words, n_bits = self.filter_bitmap(allowed)
+        ids = np.empty((b, top_k), np.uint64)
+        keys = np.empty((b, top_k), np.uint64)
+        counts = np.zeros(b, np.uint32)
+        check(lib().zh_search_exact_filtered_batch(self._h, _p(q), b, top_k, metric.metric, metric.mode, _p(words) if n_bits else None, n_bits,
+                                                   _p(ids), _p(keys), _p(counts)))
+        return ids, keys, counts
+
+    def search_exact_filtered(self, query, top_k, metric, allowed):
+        """the exact top_k of one query among the allowed rows -> list of (id, distance key), ascending"""
+        ids, keys, counts = self.search_exact_filtered_batch(_f32(query).reshape(1, -1), top_k, metric, allowed)
+        n = int(counts[0])
+        return list(zip(ids[0, :n].tolist(), keys[0, :n].tolist()))
+
+    def search_exact_filtered_batch_device(self, d_q_ptr, b, top_k, metric, d_filter_ptr, n_bits, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream=None):
+        """search_exact_filtered_batch with queries, the filter's u32 words (filter_bitmap's layout) and results already in device memory"""
+        check(lib().zh_search_exact_filtered_batch_device(self._h, d_q_ptr, b, top_k, metric.metric, metric.mode, d_filter_ptr, n_bits, d_ids_ptr,
+                                                          d_keys_ptr, d_counts_ptr, stream))
+
+    def filtered_info(self):
+        """what the most recent filtered exact search on this index did (zh_search_filtered_info): batch, rows_live, rows_allowed, path,
+        redone, survivors, launches, tiles_skipped"""
+        info = _ffi.FilteredInfo()
+        check(lib().zh_search_filtered_info(self._h, C.byref(info)))
+        return info.as_dict()
+
     def debug_keep_raw(self, on=True):
         """tests: half-width batches keep a copy of the scan's raw pairs (zh_debug_keep_raw)"""
         check(lib().zh_debug_keep_raw(self._h, 1 if on else 0))
@@ -594,4 +642,13 @@ class Database:
         if self.index.no_vectors():
             return {}
         ids, _, counts = self.index.search_batch(vectors, number_of_results, self.metric)
+        return {b: {int(i): self._documents.get(int(i)) for i in ids[b, :counts[b]]} for b in range(ids.shape[0])}
+
+    def query_vectors_where(self, vectors, number_of_results, predicate):
+        """query_vectors among the records whose document satisfies predicate(document): the exact nearest neighbours of every query among
+        them (LSHIndex.search_exact_filtered_batch) -> {query index: {id: document}}"""
+        if self.index.no_vectors():
+            return {}
+        allowed = np.fromiter((i for i, doc in self._documents.items() if predicate(doc)), np.uint64)
+        ids, _, counts = self.index.search_exact_filtered_batch(vectors, number_of_results, self.metric, allowed)
         return {b: {int(i): self._documents.get(int(i)) for i in ids[b, :counts[b]]} for b in range(ids.shape[0])}

@@ -1,8 +1,9 @@
-/* Plain C99 user of the C ABI (include/zebra_hip.h): insert vectors, search a batch, grow the index, remove, compact.
+/* Plain C99 user of the C ABI (include/zebra_hip.h): insert vectors, search a batch, grow the index, remove, compact, filter, range.
  *   gcc -std=c99 -Iinclude examples/search_example.c -Lzebra_amd/lib -lzebra_hip -Wl,-rpath,$PWD/zebra_amd/lib -o /tmp/ex && /tmp/ex
  * Mirrors what Database::insert_records / query_vectors do in the reference (src/database/core.rs:245-254, 290-313). */
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "zebra_hip.h"
 
@@ -82,6 +83,23 @@ int main(void) {
            (unsigned long long)fi.rows_live, fi.path, even ? "all allowed" : "NOT all allowed");
     ok = ok && even;
     free(filter);
+
+    /* range search, a near-duplicate pass: every live row within L2^2 <= 1.0 of a query, however many there are.  A threshold is a KEY (for L2^2
+     * the bits of the f64 distance); a first call with capacity 0 counts, the second one fetches.  Deduplicating a whole table is this loop over
+     * batches of its own rows. */
+    const double radius = 1.0;
+    uint64_t max_keys[B], offsets[B + 1], total = 0;
+    for (int b = 0; b < B; b++) memcpy(&max_keys[b], &radius, sizeof radius);
+    int rc = zh_search_range_batch(idx, q, B, max_keys, ZH_L2SQ, 0, 0, offsets, NULL, NULL, &total);
+    if (rc != ZH_OK && rc != ZH_ELIMIT) { fprintf(stderr, "zh_search_range_batch failed (%d): %s\n", rc, zh_last_error()); return 1; }
+    uint64_t *near_ids = malloc(sizeof(uint64_t) * (total + 1)), *near_keys = malloc(sizeof(uint64_t) * (total + 1));
+    CHECK(zh_search_range_batch(idx, q, B, max_keys, ZH_L2SQ, 0, total, offsets, near_ids, near_keys, &total));
+    int near = total >= 1 && total <= (uint64_t)B && offsets[0] == 0 && offsets[B] == total;
+    for (uint64_t i = 0; i < total; i++) near &= near_keys[i] <= max_keys[0];
+    printf("range: %llu rows within L2^2 <= %.1f of the %d queries; %s\n", (unsigned long long)total, radius, B, near ? "as planted" : "NOT as planted");
+    ok = ok && near;
+    free(near_ids);
+    free(near_keys);
     zh_index_destroy(idx);
     free(rows);
     free(q);

@@ -272,6 +272,33 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_search_filtered_info(h_.get(), &info));
         return info;
     }
+    // every live row whose key is <= the query's threshold key (zh_search_range_batch), ascending by (key, id): one call that counts, one that
+    // fetches.  max_keys: one key per query (~0 = every live row); for L2 squared, L2 and cosine a key is the f64 bit pattern of the distance.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> search_range_batch(const std::vector<Embedding<N>> &queries,
+                                                                               const std::vector<DistanceUnit> &max_keys, const Met &metric) const {
+        const std::size_t b = queries.size();
+        if (max_keys.size() != b) throw std::invalid_argument("search_range_batch: one threshold key per query");
+        std::vector<std::uint64_t> offsets(b + 1);
+        std::uint64_t total = 0;
+        const int rc = zh_search_range_batch(h_.get(), b ? queries[0].data() : nullptr, b, max_keys.data(), Met::metric, metric.mode(), 0,
+                                             offsets.data(), nullptr, nullptr, &total);
+        if (rc != ZH_ELIMIT) check(rc);
+        std::vector<Id> ids(total + 1);
+        std::vector<DistanceUnit> keys(total + 1);
+        if (total)
+            check(zh_search_range_batch(h_.get(), queries[0].data(), b, max_keys.data(), Met::metric, metric.mode(), total, offsets.data(), ids.data(),
+                                        keys.data(), &total));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(b);
+        for (std::size_t i = 0; i < b; i++)
+            for (std::uint64_t j = offsets[i]; j < offsets[i + 1]; j++) out[i].emplace_back(ids[j], keys[j]);
+        return out;
+    }
+    zh_range_info range_info() const {
+        zh_range_info info{};
+        check(zh_search_range_info(h_.get(), &info));
+        return info;
+    }
     zh_index *handle() const { return h_.get(); }
 
   private:
@@ -327,6 +354,22 @@ class Database {
             for (auto &p : nb[i]) {
                 auto it = documents_.find(p.first);
                 m[p.first] = it == documents_.end() ? std::string() : it->second;
+            }
+        }
+        return results;
+    }
+
+    // (new) every record whose key is <= max_key for each query (LSHIndex::search_range_batch): query index -> its records, nearest first
+    std::map<std::size_t, std::vector<std::pair<Id, std::string>>> query_vectors_within(const std::vector<Embedding<N>> &vectors,
+                                                                                        DistanceUnit max_key) const {
+        std::map<std::size_t, std::vector<std::pair<Id, std::string>>> results;
+        if (index.no_vectors()) return results;
+        const auto hits = index.search_range_batch(vectors, std::vector<DistanceUnit>(vectors.size(), max_key), metric_);
+        for (std::size_t i = 0; i < hits.size(); i++) {
+            auto &v = results[i];
+            for (auto &p : hits[i]) {
+                auto it = documents_.find(p.first);
+                v.emplace_back(p.first, it == documents_.end() ? std::string() : it->second);
             }
         }
         return results;

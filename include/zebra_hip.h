@@ -26,6 +26,7 @@
  *   zh_merge_topk_device                 (new) the shard merge alone
  *   zh_search_exact_batch[_device]       (new) exact top-k over every live row under the same keys: recall ground truth
  *   zh_search_exact_filtered_batch[_device] (new) the exact top-k among the live rows a caller's bitmap allows
+ *   zh_search_range_batch[_device]       (new) every live row whose key is at or below a per-query threshold key, as a CSR
  *   zh_index_save / zh_index_load        (new) a snapshot of an index in ONE file of this library's own format (the reference persists through
  *                                        fjall, lsh.rs:62-120, whose files are not read here): rows, removals, forest and the planes' sample rows
  *
@@ -406,6 +407,47 @@ typedef struct zh_filtered_info {  /* the most recent zh_search_exact_filtered_*
     uint64_t tiles_skipped; /* path 2: 16-row tiles with no allowed row, returned from before they were loaded (over all internal batches) */
 } zh_filtered_info;
 ZH_API int zh_search_filtered_info(const zh_index *idx, zh_filtered_info *out);
+
+/* Exact RANGE search (new; the reference has none): every live stored row within a radius of each query, however many there are.  The hits of query
+ * i are the live rows (rows removed by zh_index_remove / zh_index_deduplicate excluded; no forest needed) whose key is <= max_keys[i], where the
+ * key is the one zh_distance_batch returns for that (row, query) pair and keys compare as everywhere in this library: the u64 bit pattern,
+ * unsigned.  A row is in exactly when zh_search_exact_batch would rank it at or before a row with key max_keys[i].  The threshold is a KEY, one per
+ * query (zebra_amd.radius_key turns a distance into one); UINT64_MAX returns every live row.  For the parity cosine key (ZH_COSINE_PARITY: the bits
+ * of the similarity 1 - distance, which may be negative) the unsigned order is the definition: non-negative similarities ascending, then the
+ * negative ones by magnitude.
+ * The result is a CSR: the hits of query i are out_ids / out_keys [out_offsets[i], out_offsets[i + 1]), ascending by (key, id), ids = id_base +
+ * row; out_offsets[0] = 0 and *out_total = out_offsets[b].  out_offsets (b + 1 entries) and out_total must not be NULL.  If the hits exceed
+ * `capacity` (the entries out_ids and out_keys have room for) the call returns ZH_ELIMIT: *out_total and ALL of out_offsets are still exact -- allocate
+ * *out_total entries and call again -- and out_ids / out_keys are unspecified.  capacity = 0 with NULL out_ids / out_keys is the supported way to
+ * count only.  b = 0, an empty index and an index of removed rows only give all-zero offsets and ZH_OK.  A NULL index, q or max_keys with b > 0,
+ * NULL out_ids / out_keys with capacity > 0 and an unknown metric are refused before any device is touched.  All 13 metric / mode / power
+ * combinations and every dimension are served.  Locking and thread-safety as for zh_search_exact_batch; zh_stats_t, zh_exact_info,
+ * zh_filtered_info and the index's cached live-row views are left alone: zh_search_range_info describes the most recent call.
+ * Internal batches of 1024 queries, two paths, same answers.  Path 1 keys every pair with the canonical sums, row chunk by row chunk, and collects
+ * the keys at or below the threshold.  Path 2 (ZH_L2SQ, ZH_L2, ZH_COSINE at dim 256 / 384 / 512 / 768 / 1024, at least 8192 live rows, the fp16 row
+ * copy present) scans on the matrix cores for an interval per pair, takes the pairs whose interval reaches down to the threshold as candidates, and
+ * gives only them the canonical key; a batch whose candidates outgrow their pool is answered by path 1 (`redone`).  ZH_RANGE_PATH=1 in the
+ * environment (read per call) keeps every batch on path 1.
+ * Device scratch is allocated per call and released before it returns.  Per internal batch, with P = min(capacity left, queries x live rows) hit
+ * slots: 32 P bytes of hit pool and sort buffers + the sort's temporary storage (a few MiB), 8 bytes per candidate slot on path 2 (max(1.25 P,
+ * 4096 per query) of them), up to 1 GiB of key scratch on path 1, and for the host call 16 bytes per hit of the batch as staging. */
+ZH_API int zh_search_range_batch(zh_index *idx, const float *q, size_t b, const uint64_t *max_keys, int metric, int cosine_mode, uint64_t capacity,
+                                 uint64_t *out_offsets, uint64_t *out_ids, uint64_t *out_keys, uint64_t *out_total);
+/* The same with queries, thresholds and every output (out_total included) in device memory; enqueued on `stream` (NULL = the index's own stream),
+ * complete on return. */
+ZH_API int zh_search_range_batch_device(zh_index *idx, const float *d_q, size_t b, const uint64_t *d_max_keys, int metric, int cosine_mode,
+                                        uint64_t capacity, uint64_t *d_out_offsets, uint64_t *d_out_ids, uint64_t *d_out_keys, uint64_t *d_out_total,
+                                        void *stream);
+typedef struct zh_range_info {  /* the most recent zh_search_range_* call on this index */
+    uint64_t batch;       /* queries */
+    uint64_t rows_live;   /* live rows of the index */
+    uint64_t hits;        /* (row, query) pairs within their query's threshold, over all queries (exact whatever the capacity) */
+    uint32_t path;        /* 1: canonical sums for every pair; 2: matrix-core intervals, canonical keys for the candidates only */
+    uint32_t redone;      /* path-2 internal batches whose candidate pool ran over and were answered by path 1 instead */
+    uint64_t candidates;  /* path 2: (row, query) pairs that got the canonical key, over all internal batches path 2 completed */
+    uint64_t launches;    /* launches of the scan (row chunks on path 1, one per internal batch on path 2) */
+} zh_range_info;
+ZH_API int zh_search_range_info(const zh_index *idx, zh_range_info *out);
 
 /* Pipelined form of zh_search_batch_device (new; the reference has one blocking search per query): a context
  * is one in-flight batch with its own scratch.  The context calls do NOT take the index's internal lock (the blocking

@@ -110,6 +110,18 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_range_info {
+        pub batch: u64,
+        pub rows_live: u64,
+        pub hits: u64,
+        pub path: u32,
+        pub redone: u32,
+        pub candidates: u64,
+        pub launches: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_filtered_info {
         pub batch: u64,
         pub rows_live: u64,
@@ -203,6 +215,12 @@ pub mod ffi {
                                                      d_filter_words: *const u32, n_bits: u64, d_out_ids: *mut u64, d_out_keys: *mut u64,
                                                      d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_search_filtered_info(idx: *const zh_index, out: *mut zh_filtered_info) -> c_int;
+        pub fn zh_search_range_batch(idx: *mut zh_index, q: *const f32, b: usize, max_keys: *const u64, metric: c_int, cosine_mode: c_int,
+                                     capacity: u64, out_offsets: *mut u64, out_ids: *mut u64, out_keys: *mut u64, out_total: *mut u64) -> c_int;
+        pub fn zh_search_range_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, d_max_keys: *const u64, metric: c_int, cosine_mode: c_int,
+                                            capacity: u64, d_out_offsets: *mut u64, d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_total: *mut u64,
+                                            stream: *mut c_void) -> c_int;
+        pub fn zh_search_range_info(idx: *const zh_index, out: *mut zh_range_info) -> c_int;
         pub fn zh_search_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
                                       d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_distance_pair(metric: c_int, cosine_mode: c_int, a: *const f32, b: *const f32, dim: usize, out_key: *mut u64,
@@ -507,6 +525,42 @@ impl<const N: usize> LSHIndex<N> {
         Ok((0..b).map(|i| (0..counts[i] as usize).map(|j| (t.of_row[ids[i * top_k + j] as usize], keys[i * top_k + j])).collect()).collect())
     }
 
+    /// (new) every live vector whose key is <= the query's threshold key (zh_search_range_batch), ascending by (key, id): one call that
+    /// counts (capacity 0), one that fetches.  `max_keys`: one DistanceUnit per query (u64::MAX = every live vector).
+    pub fn search_range_batch<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        queries: &[Embedding<N>],
+        max_keys: &[DistanceUnit],
+        metric: &Met,
+    ) -> anyhow::Result<Vec<Vec<(Uuid, DistanceUnit)>>> {
+        let b = queries.len();
+        anyhow::ensure!(max_keys.len() == b, "search_range_batch: one threshold key per query");
+        let t = self.ids.read().unwrap();
+        let (mut offsets, mut total) = (vec![0u64; b + 1], 0u64);
+        let rc = unsafe {
+            ffi::zh_search_range_batch(self.hip.0, queries.as_ptr() as *const f32, b, max_keys.as_ptr(), Met::METRIC, metric.param(), 0,
+                                       offsets.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), &mut total)
+        };
+        if rc != -5 {
+            check(rc)?; // (-5 = ZH_ELIMIT: the hits exceed capacity 0; offsets and total are exact)
+        }
+        let (mut ids, mut keys) = (vec![0u64; total as usize + 1], vec![0u64; total as usize + 1]);
+        if total > 0 {
+            check(unsafe {
+                ffi::zh_search_range_batch(self.hip.0, queries.as_ptr() as *const f32, b, max_keys.as_ptr(), Met::METRIC, metric.param(), total,
+                                           offsets.as_mut_ptr(), ids.as_mut_ptr(), keys.as_mut_ptr(), &mut total)
+            })?;
+        }
+        Ok((0..b).map(|i| (offsets[i] as usize..offsets[i + 1] as usize).map(|j| (t.of_row[ids[j] as usize], keys[j])).collect()).collect())
+    }
+
+    /// what the most recent range search did (zh_search_range_info)
+    pub fn range_info(&self) -> anyhow::Result<ffi::zh_range_info> {
+        let mut info = ffi::zh_range_info::default();
+        check(unsafe { ffi::zh_search_range_info(self.hip.0, &mut info) })?;
+        Ok(info)
+    }
+
     /// what the most recent filtered search did (zh_search_filtered_info)
     pub fn filtered_info(&self) -> anyhow::Result<ffi::zh_filtered_info> {
         let mut info = ffi::zh_filtered_info::default();
@@ -608,6 +662,15 @@ impl<
             self.documents.insert(*id, doc.clone());
         }
         Ok(())
+    }
+
+    /// (new) every record whose key is <= `max_key` for each query (LSHIndex::search_range_batch): query index -> its records, nearest first
+    pub fn query_vectors_within(&self, vectors: &Vec<Embedding<N>>, max_key: DistanceUnit) -> anyhow::Result<Vec<Vec<(Uuid, Vec<u8>)>>> {
+        if self.index.no_vectors() {
+            return Ok(Vec::new());
+        }
+        let hits = self.index.search_range_batch(vectors, &vec![max_key; vectors.len()], &self.metric)?;
+        Ok(hits.into_iter().map(|h| h.into_iter().map(|(id, _)| (id, self.documents.get(&id).map(|d| d.clone()).unwrap_or_default())).collect()).collect())
     }
 
     /// core.rs:290-313: the rayon loop over queries (core.rs:299-303) is ONE batched call; order and distances are

@@ -263,6 +263,10 @@ struct zh_index {
     // position of the scan's row order, the blocks' counts and their exclusive sums, the ascending list of allowed live rows
     DevBuf fl_filter, fl_bits, fl_pos, fl_bcount, fl_bexcl, fl_tmp, fl_list;
     zh_filtered_info fl_info{};  // (stats_mu)
+    // the range search's per-call scratch (all released before the call returns): thresholds, counts per query, {hit, candidate} counters, the hit
+    // pool and its sort partner (v and key), path 2's candidate pool, the sort's temporary storage, offsets and outputs staged for the host call
+    DevBuf rg_maxk, rg_cnt, rg_ctr, rg_pv0, rg_pv1, rg_pk0, rg_pk1, rg_cand, rg_tmp, rg_off, rg_oids, rg_okeys;
+    zh_range_info rg_info{};  // (stats_mu)
 
     bool broken = false;  // an incremental add failed half way: trees are stale until zh_index_build
     bool rows_torn = false;  // ... or a compaction failed after rows had begun to move (set with broken): the TABLE is inconsistent until zh_index_clear
@@ -3871,6 +3875,232 @@ extern "C" int zh_search_filtered_info(const zh_index *ix, zh_filtered_info *out
     zh_index *m = const_cast<zh_index *>(ix);
     std::lock_guard<std::mutex> lk(m->stats_mu);
     *out = m->fl_info;
+    return ZH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// exact range search (zh_range.hip + the exact search's scan kernels): every live row with key <= a per-query threshold key, as a CSR
+// ------------------------------------------------------------------------------------------------
+#define ZH_RANGE_CAND_FLOOR 4096u  // path 2: candidate slots per query that are there whatever the capacity (a count-only call still lists candidates)
+
+static void range_release_scratch(zh_index *ix) {
+    exact_release_scratch(ix);
+    DevBuf *bs[] = {&ix->rg_maxk, &ix->rg_cnt, &ix->rg_ctr, &ix->rg_pv0, &ix->rg_pv1, &ix->rg_pk0, &ix->rg_pk1, &ix->rg_cand, &ix->rg_tmp, &ix->rg_off,
+                    &ix->rg_oids, &ix->rg_okeys};
+    for (DevBuf *b : bs) b->release();
+}
+struct RangeScratchGuard {
+    zh_index *ix;
+    ~RangeScratchGuard() { range_release_scratch(ix); }
+};
+struct RangeRun {
+    uint64_t capacity = 0;
+    uint64_t total = 0;  // hits of the internal batches so far
+    bool over = false;   // they passed the capacity: the batches after count only
+};
+
+// path 1 of one internal batch: row chunk after row chunk, exact_score_kernel's keys into the key scratch, range_collect_kernel over them
+static int range_batch1(zh_index *ix, const float *dQ, uint32_t B, const uint64_t *dMaxK, int metric, int mode, uint64_t pool_cap, hipStream_t s,
+                        uint64_t *launches) {
+    const uint32_t d = ix->opt.dim;
+    const uint64_t n_live = ix->ex_n_live;
+    const uint64_t rc_rows = std::min<uint64_t>(std::max<uint64_t>(256, ZH_EXACT_KEY_BYTES / 8 / B), n_live);
+    int rc;
+    if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_keys.ensure((size_t)B * rc_rows * 8))) return rc;
+    const int param = metric == ZH_COSINE ? mode : ((metric == ZH_MINKOWSKI || metric == ZH_PNORM) ? mode : 0);
+    HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
+    HIPCHK(hipMemsetAsync(ix->rg_cnt.p, 0, (size_t)B * 4, s));
+    HIPCHK(hipMemsetAsync(ix->rg_ctr.p, 0, 16, s));
+    for (uint64_t p0 = 0; p0 < n_live; p0 += rc_rows) {
+        const uint32_t nr = (uint32_t)std::min<uint64_t>(rc_rows, n_live - p0);
+        HIPCHK(zh_launch_exact_score(ix->X.as<float>(), d, ix->ex_live.as<uint32_t>(), p0, nr, dQ, ix->ex_QQ.as<float>(), B, metric, param,
+                                     ix->ex_keys.as<uint64_t>(), rc_rows, s));
+        HIPCHK(zh_launch_range_collect(ix->ex_keys.as<uint64_t>(), rc_rows, ix->ex_live.as<uint32_t>(), p0, nr, B, dMaxK, ix->rg_cnt.as<uint32_t>(),
+                                       ix->rg_ctr.as<unsigned long long>(), ix->rg_pv0.as<uint64_t>(), ix->rg_pk0.as<uint64_t>(), pool_cap, s));
+        (*launches)++;
+    }
+    return ZH_OK;
+}
+
+// Path 2 of one internal batch: the thresholds as fixed bounds, ONE matrix-core scan of the whole table into the candidate pool, canonical keys and
+// the judgement for the candidates.  *used = false: path 2 does not serve this index (path 1 answers).  On return with *used the stream has been
+// waited for and h_ctr = {hits, candidates}; candidates > cand_cap: the pool ran over and nothing was counted (path 1 answers).
+static int range_batch2(zh_index *ix, const float *dQ, uint32_t B, const uint64_t *dMaxK, int metric, int mode, uint64_t pool_cap, uint64_t cand_cap,
+                        hipStream_t s, bool *used, unsigned long long h_ctr[2], uint64_t *launches) {
+    *used = false;
+    const uint32_t d = ix->opt.dim;
+    if (!zh_exact_mfma_supported(d, metric) || ix->ex_n_live < 8192) return ZH_OK;
+    int rc;
+    const void *Xh;
+    const float2 *rowMeta;
+    const uint32_t *perm;
+    uint64_t perm_rows;
+    float rho;
+    {
+        std::lock_guard<std::mutex> lb(ix->blk_mu);
+        bool ok = false;
+        if ((rc = ensure_row_half(ix, &ok))) return rc;
+        if (!ok || !ix->row_half.p) return ZH_OK;  // no room for the fp16 copy: path 1
+        Xh = ix->row_half.p; rowMeta = ix->row_meta.as<float2>(); rho = ix->row_rho;
+        perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr; perm_rows = ix->perm_rows;
+    }
+    if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_Qh.ensure((size_t)B * d * 2)) || (rc = ix->ex_qmeta.ensure((size_t)B * 16)) ||
+        (rc = ix->ex_tau.ensure((size_t)B * 4)) || (rc = ix->rg_cand.ensure(cand_cap * 8)))
+        return rc;
+    ZhExact2 e{Xh, rowMeta, perm, perm_rows, ix->ex_bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B, zh_approx_bound(metric, d, 1), rho,
+               ix->ex_tau.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr, 0, nullptr};
+    unsigned long long *ctr = ix->rg_ctr.as<unsigned long long>();
+    HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
+    HIPCHK(zh_launch_qhalf(dQ, B, d, ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), 1, s));
+    HIPCHK(zh_launch_range_tau(dMaxK, B, metric, mode, e.tau, s));
+    HIPCHK(hipMemsetAsync(ix->rg_cnt.p, 0, (size_t)B * 4, s));
+    HIPCHK(hipMemsetAsync(ctr, 0, 16, s));
+    HIPCHK(zh_launch_range_mfma(d, metric, mode, e, 0, ix->n_rows, ix->rg_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
+    (*launches)++;
+    HIPCHK(zh_launch_range_survivors(ix->X.as<float>(), d, dQ, ix->ex_QQ.as<float>(), metric, mode, ix->rg_cand.as<uint64_t>(), ctr + 1, cand_cap, dMaxK,
+                                     ix->rg_cnt.as<uint32_t>(), ctr, ix->rg_pv0.as<uint64_t>(), ix->rg_pk0.as<uint64_t>(), pool_cap, s));
+    HIPCHK(hipMemcpyAsync(h_ctr, ctr, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *used = true;
+    return ZH_OK;
+}
+
+// One internal batch (B <= ZH_EXACT_BATCH) on device pointers: its hits counted and pooled by path 2 where it serves, by path 1 otherwise and
+// when path 2's candidates ran over; dOff[0 .. B] = run->total + the exclusive sums of the counts; and, while the capacity holds, the pool
+// ordered by (query, key, id) into dIds / dKeys at run->total (host_out: into staging and from there to the HOST arrays dIds / dKeys).
+static int range_one(zh_index *ix, const float *dQ, uint32_t B, const uint64_t *dMaxK, int metric, int mode, RangeRun *run, uint64_t *dOff,
+                     uint64_t *dIds, uint64_t *dKeys, bool host_out, hipStream_t s, zh_range_info *inf) {
+    const uint64_t n_live = ix->ex_n_live, pairs = (uint64_t)B * n_live;
+    const uint64_t pool_cap = run->over ? 0 : std::min<uint64_t>(run->capacity - run->total, pairs);
+    int rc;
+    if ((rc = ix->rg_cnt.ensure((size_t)B * 4)) || (rc = ix->rg_ctr.ensure(16)) || (rc = ix->rg_pv0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)) ||
+        (rc = ix->rg_pk0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)))
+        return rc;
+    unsigned long long h_ctr[2] = {0, 0};
+    if (n_live == 0) HIPCHK(hipMemsetAsync(ix->rg_cnt.p, 0, (size_t)B * 4, s));
+    else {
+        const char *env_p = getenv("ZH_RANGE_PATH");
+        bool done = false;
+        if (!(env_p && atoi(env_p) == 1)) {
+            const uint64_t cand_cap = std::min<uint64_t>(pairs, std::max<uint64_t>(pool_cap + pool_cap / 4, (uint64_t)ZH_RANGE_CAND_FLOOR * B));
+            bool used = false;
+            if ((rc = range_batch2(ix, dQ, B, dMaxK, metric, mode, pool_cap, cand_cap, s, &used, h_ctr, &inf->launches))) return rc;
+            if (used) {
+                inf->path = 2;
+                if (h_ctr[1] > cand_cap) inf->redone++;
+                else { inf->candidates += h_ctr[1]; done = true; }
+            }
+        }
+        if (!done) {
+            if ((rc = range_batch1(ix, dQ, B, dMaxK, metric, mode, pool_cap, s, &inf->launches))) return rc;
+            HIPCHK(hipMemcpyAsync(h_ctr, ix->rg_ctr.p, 16, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+    }
+    const uint64_t hits = h_ctr[0];
+    HIPCHK(zh_launch_range_offsets(ix->rg_cnt.as<uint32_t>(), B, run->total, dOff, s));
+    if (!run->over && hits > pool_cap) run->over = true;  // (pool_cap = the capacity left, or every pair there is)
+    if (!run->over && hits) {
+        uint64_t *dV[2] = {nullptr, nullptr}, *dK[2] = {nullptr, nullptr};
+        size_t tmp_bytes = 0;
+        HIPCHK(zh_launch_range_sort(dV, dK, hits, ix->n_rows, B, nullptr, &tmp_bytes, 0, nullptr, nullptr, s));
+        if ((rc = ix->rg_pv1.ensure(hits * 8)) || (rc = ix->rg_pk1.ensure(hits * 8)) || (rc = ix->rg_tmp.ensure(tmp_bytes))) return rc;
+        if (host_out && ((rc = ix->rg_oids.ensure(hits * 8)) || (rc = ix->rg_okeys.ensure(hits * 8)))) return rc;
+        dV[0] = ix->rg_pv0.as<uint64_t>(); dV[1] = ix->rg_pv1.as<uint64_t>();
+        dK[0] = ix->rg_pk0.as<uint64_t>(); dK[1] = ix->rg_pk1.as<uint64_t>();
+        uint64_t *oi = host_out ? ix->rg_oids.as<uint64_t>() : dIds + run->total, *ok = host_out ? ix->rg_okeys.as<uint64_t>() : dKeys + run->total;
+        HIPCHK(zh_launch_range_sort(dV, dK, hits, ix->n_rows, B, ix->rg_tmp.p, &tmp_bytes, ix->opt.id_base, oi, ok, s));
+        if (host_out) {
+            HIPCHK(hipMemcpyAsync(dIds + run->total, oi, hits * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(dKeys + run->total, ok, hits * 8, hipMemcpyDeviceToHost, s));
+        }
+    }
+    run->total += hits;
+    inf->hits += hits;
+    return ZH_OK;
+}
+
+static int range_args(zh_index *ix, const float *q, size_t b, const uint64_t *max_keys, int metric, int mode, uint64_t capacity, const void *offsets,
+                      const void *ids, const void *keys, const void *total, const char *who) {
+    int rc = exact_args(ix, q, b, capacity ? 1 : 0, metric, mode, ids, keys, offsets, who);
+    if (rc) return rc;
+    if (!offsets || !total || (b && !max_keys) || (capacity && (!ids || !keys))) return fail(ZH_EINVAL, "%s: null argument", who);
+    return ZH_OK;
+}
+
+static int range_finish(zh_index *ix, size_t b, const RangeRun &run, zh_range_info inf, const char *who) {
+    {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        inf.batch = b;
+        inf.rows_live = ix->ex_n_live;
+        ix->rg_info = inf;
+    }
+    if (run.over)
+        return fail(ZH_ELIMIT, "%s: %llu hits exceed the capacity of %llu; out_total and the offsets are exact, call again with that capacity", who,
+                    (unsigned long long)run.total, (unsigned long long)run.capacity);
+    return ZH_OK;
+}
+
+extern "C" int zh_search_range_batch_device(zh_index *ix, const float *d_q, size_t b, const uint64_t *d_max_keys, int metric, int mode, uint64_t capacity,
+                                            uint64_t *d_out_offsets, uint64_t *d_out_ids, uint64_t *d_out_keys, uint64_t *d_out_total, void *stream) {
+    int rc = range_args(ix, d_q, b, d_max_keys, metric, mode, capacity, d_out_offsets, d_out_ids, d_out_keys, d_out_total, "zh_search_range_batch_device");
+    if (rc) return rc;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    RangeScratchGuard guard{ix};
+    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    const uint32_t d = ix->opt.dim;
+    RangeRun run;
+    run.capacity = capacity;
+    zh_range_info inf{};
+    inf.path = 1;
+    HIPCHK(hipMemsetAsync(d_out_offsets, 0, 8, s));
+    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
+        if ((rc = range_one(ix, d_q + b0 * d, nb, d_max_keys + b0, metric, mode, &run, d_out_offsets + b0, d_out_ids, d_out_keys, false, s, &inf))) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(d_out_total, &run.total, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return range_finish(ix, b, run, inf, "zh_search_range_batch_device");
+}
+
+extern "C" int zh_search_range_batch(zh_index *ix, const float *q, size_t b, const uint64_t *max_keys, int metric, int mode, uint64_t capacity,
+                                     uint64_t *out_offsets, uint64_t *out_ids, uint64_t *out_keys, uint64_t *out_total) {
+    int rc = range_args(ix, q, b, max_keys, metric, mode, capacity, out_offsets, out_ids, out_keys, out_total, "zh_search_range_batch");
+    if (rc) return rc;
+    out_offsets[0] = 0;
+    *out_total = 0;
+    if (b == 0) return ZH_OK;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    RangeScratchGuard guard{ix};
+    const hipStream_t s = ix->stream;
+    const uint32_t d = ix->opt.dim;
+    const size_t nb_max = std::min<size_t>(ZH_EXACT_BATCH, b);
+    if ((rc = ix->ex_Q.ensure(nb_max * d * 4)) || (rc = ix->rg_maxk.ensure(nb_max * 8)) || (rc = ix->rg_off.ensure((nb_max + 1) * 8))) return rc;
+    RangeRun run;
+    run.capacity = capacity;
+    zh_range_info inf{};
+    inf.path = 1;
+    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
+        HIPCHK(hipMemcpyAsync(ix->ex_Q.p, q + b0 * d, (size_t)nb * d * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(ix->rg_maxk.p, max_keys + b0, (size_t)nb * 8, hipMemcpyHostToDevice, s));
+        if ((rc = range_one(ix, ix->ex_Q.as<float>(), nb, ix->rg_maxk.as<uint64_t>(), metric, mode, &run, ix->rg_off.as<uint64_t>(), out_ids, out_keys, true,
+                            s, &inf)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(out_offsets + b0, ix->rg_off.p, ((size_t)nb + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    *out_total = run.total;
+    return range_finish(ix, b, run, inf, "zh_search_range_batch");
+}
+
+extern "C" int zh_search_range_info(const zh_index *ix, zh_range_info *out) {
+    if (!ix || !out) return fail(ZH_EINVAL, "zh_search_range_info: null argument");
+    zh_index *m = const_cast<zh_index *>(ix);
+    std::lock_guard<std::mutex> lk(m->stats_mu);
+    *out = m->rg_info;
     return ZH_OK;
 }
 

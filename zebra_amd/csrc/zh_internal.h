@@ -326,6 +326,28 @@ hipError_t zh_launch_filter_permute(const uint32_t *dBits, const uint32_t *dPerm
 // dList = the set bits of dBits, ascending (dBlockExcl as zh_launch_filter_and left it)
 hipError_t zh_launch_filter_list(const uint32_t *dBits, uint64_t n_rows, const uint32_t *dBlockExcl, uint32_t *dList, hipStream_t s);
 
+// ---- the exact range search (zh_range.hip): every live row with key <= a per-query threshold key.  A hit pool is two u64 arrays, v = query << 32 | row
+// and the key; dCnt: the hits per query of the internal batch, counted whether or not the pool has room; *dHitCtr: all of them
+hipError_t zh_launch_range_collect(const uint64_t *dKeys, uint64_t ld, const uint32_t *dLive, uint64_t p0, uint32_t nr, uint32_t B,
+                                   const uint64_t *dMaxKeys, uint32_t *dCnt, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK,
+                                   uint64_t pool_cap, hipStream_t s);
+// path 2: dTau[b] = the threshold key of query b in approx_interval's sortable-f32 domain, rounded towards admitting more
+hipError_t zh_launch_range_tau(const uint64_t *dMaxKeys, uint32_t B, int metric, int mode, uint32_t *dTau, hipStream_t s);
+// exact_mfma_kernel's scan against e.tau (fixed); pairs with lo <= tau to dCand as query << 32 | row; *dCandCtr counts all of them (> cand_cap: ran over).
+// Of e it reads Xh, rowMeta, perm, perm_rows, liveBits, Qh, qmeta, B, Kc, rho, tau.
+hipError_t zh_launch_range_mfma(uint32_t d, int metric, int mode, const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, uint64_t *dCand, uint64_t cand_cap,
+                                unsigned long long *dCandCtr, hipStream_t s);
+// the candidates' canonical keys, judged against the thresholds, counted and appended to the hit pool (nothing when the candidate pool ran over)
+hipError_t zh_launch_range_survivors(const float *dX, uint32_t d, const float *dQ, const float *dQQ, int metric, int mode, const uint64_t *dCand,
+                                     const unsigned long long *dCandCtr, uint64_t cand_cap, const uint64_t *dMaxKeys, uint32_t *dCnt,
+                                     unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
+// dOff[i] = base + hits of the queries before i, i <= B (B <= 1024)
+hipError_t zh_launch_range_offsets(const uint32_t *dCnt, uint32_t B, uint64_t base, uint64_t *dOff, hipStream_t s);
+// the pool's n entries ordered by (query, key, row) and written out as ids (id_base + row) and keys; dV / dK: the pool and a second buffer of the
+// same size each.  dTmp == nullptr: only *tmp_bytes is set, to what the sorts of n entries need
+hipError_t zh_launch_range_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows, uint32_t B, void *dTmp, size_t *tmp_bytes, uint64_t id_base,
+                                uint64_t *dOutIds, uint64_t *dOutKeys, hipStream_t s);
+
 // ---- launchers (zh_score.hip): every sign of a forest built from stored rows, from N row scores per query --------
 // Prefilter (zh_search.hip, "Prefilter"): a batch hashed from row scores picks the rows that can be among a pair's k best from
 // those scores; only they are scored with the reference's arithmetic.  Lists: one per (tree, query), `cap` slots, list (t, b) at

@@ -123,6 +123,32 @@ class PNormDistance(_Metric):
         self.power = self.mode = int(power)
 
 
+_F64_KEYED = (_ffi.COSINE, _ffi.L2SQ, _ffi.L2)  # key = the f64 bit pattern (key_cosine / key_l2); HAMMING: the integer count; the rest: f32 bits widened
+
+
+def radius_key(metric, radius):
+    """The largest key that means "distance <= radius" under `metric` (a metric object or a ZH_* metric number), for the range searches'
+    max_keys: the f64 bit pattern of the radius for cosine, L2 squared and L2, the bits of the largest f32 at or below it for the metrics whose
+    key is an f32 widened to 64 bits, floor(radius) for Hamming's integer count.  `radius` may be a scalar or one value per query (-> a
+    uint64 array); NaN or a negative radius raises ValueError.  The radius is compared with the VALUE THE KEY HOLDS: for the parity cosine key
+    (CosineDistance(parity=True)) that value is the similarity 1 - distance and keys compare as unsigned bit patterns, so the hits of a
+    non-negative radius r are the rows with 0 <= similarity <= r."""
+    m = getattr(metric, "metric", metric)
+    r = np.asarray(radius, dtype=np.float64) + 0.0  # (-0.0 -> +0.0)
+    if np.isnan(r).any() or (r < 0).any():
+        raise ValueError("a radius must be a non-negative number")
+    if m in _F64_KEYED:
+        out = r.view(np.uint64) if r.ndim else np.float64(r).reshape(1).view(np.uint64)[0]
+    elif m == _ffi.HAMMING:
+        out = np.floor(np.minimum(r, 1.8e19)).astype(np.uint64)
+    else:
+        with np.errstate(over="ignore"):
+            f = r.astype(np.float32)
+        f = np.where(f.astype(np.float64) > r, np.nextafter(f, np.float32(-np.inf)), f).astype(np.float32)
+        out = f.reshape(-1).view(np.uint32).astype(np.uint64).reshape(f.shape)
+    return np.ascontiguousarray(out) if r.ndim else np.uint64(out)
+
+
 def snapshot_info(path, verify=False):
     """zh_snapshot_inspect (host code only, no GPU needed): the header of a snapshot file after every test a load applies to the header block,
     the section table and the padding; verify=True recomputes every section's checksum on the host as well."""
@@ -381,6 +407,69 @@ class LSHIndex:
         redone, survivors, launches, tiles_skipped"""
         info = _ffi.FilteredInfo()
         check(lib().zh_search_filtered_info(self._h, C.byref(info)))
+        return info.as_dict()
+
+    def _range_keys(self, b, radius, metric, max_keys):
+        if (radius is None) == (max_keys is None):
+            raise ValueError("give either a radius or max_keys")
+        mk = np.asarray(radius_key(metric, radius) if max_keys is None else max_keys, dtype=np.uint64)
+        mk = np.ascontiguousarray(np.broadcast_to(mk, (b,)) if mk.ndim == 0 else mk.reshape(-1))
+        if mk.size != b:
+            raise ValueError("expected one threshold per query (%d), got %d" % (b, mk.size))
+        return mk
+
+    def search_range_batch(self, queries, radius=None, metric=None, max_keys=None, capacity=None):
+        """EXACT range search: every live stored row whose key is <= the query's threshold, under the same keys as search_exact_batch (no
+        forest needed; removed rows excluded).  The threshold is `radius` (a scalar or one per query, turned into keys by radius_key) or
+        `max_keys` (u64 keys, one per query; 2^64-1 = every live row).  -> (offsets [b + 1] u64, ids u64, keys u64): the hits of query i are
+        ids / keys [offsets[i], offsets[i + 1]), ascending by (key, id).  One call with a guessed capacity; when the hits exceed it, one more
+        with the exact total the first call reported."""
+        q = _f32(queries, self.dim)
+        b = q.shape[0]
+        mk = self._range_keys(b, radius, metric, max_keys)
+        cap = int(capacity) if capacity is not None else max(1024, 64 * b)
+        offsets = np.zeros(b + 1, np.uint64)
+        total = C.c_uint64(0)
+        for attempt in range(2):
+            ids = np.empty(max(cap, 1), np.uint64)
+            keys = np.empty(max(cap, 1), np.uint64)
+            rc = lib().zh_search_range_batch(self._h, _p(q), b, _p(mk), metric.metric, metric.mode, cap, _p(offsets), _p(ids), _p(keys), C.byref(total))
+            if rc == _ffi.ZH_ELIMIT and attempt == 0 and total.value > cap:
+                cap = int(total.value)
+                continue
+            check(rc)
+            break
+        n = int(total.value)
+        return offsets, ids[:n], keys[:n]
+
+    def search_range(self, query, radius=None, metric=None, max_keys=None):
+        """the hits of one query -> list of (id, distance key), ascending"""
+        _, ids, keys = self.search_range_batch(_f32(query).reshape(1, -1), radius, metric, max_keys)
+        return list(zip(ids.tolist(), keys.tolist()))
+
+    def range_count_batch(self, queries, radius=None, metric=None, max_keys=None):
+        """how many hits search_range_batch would return for every query (a call with capacity 0: nothing is ordered or written) -> [b] u64"""
+        q = _f32(queries, self.dim)
+        b = q.shape[0]
+        mk = self._range_keys(b, radius, metric, max_keys)
+        offsets = np.zeros(b + 1, np.uint64)
+        total = C.c_uint64(0)
+        rc = lib().zh_search_range_batch(self._h, _p(q), b, _p(mk), metric.metric, metric.mode, 0, _p(offsets), None, None, C.byref(total))
+        if rc != _ffi.ZH_ELIMIT:
+            check(rc)
+        return np.diff(offsets)
+
+    def search_range_batch_device(self, d_q_ptr, b, d_max_keys_ptr, metric, capacity, d_offsets_ptr, d_ids_ptr, d_keys_ptr, d_total_ptr, stream=None):
+        """search_range_batch with queries, threshold keys, offsets (b + 1), ids / keys (`capacity` each) and the total (one u64) in device
+        memory (raw pointers, e.g. torch .data_ptr()).  Hits beyond the capacity raise ZhError with code ZH_ELIMIT; the offsets and the total
+        are exact even then."""
+        check(lib().zh_search_range_batch_device(self._h, d_q_ptr, b, d_max_keys_ptr, metric.metric, metric.mode, capacity, d_offsets_ptr, d_ids_ptr,
+                                                 d_keys_ptr, d_total_ptr, stream))
+
+    def range_info(self):
+        """what the most recent range search on this index did (zh_search_range_info): batch, rows_live, hits, path, redone, candidates, launches"""
+        info = _ffi.RangeInfo()
+        check(lib().zh_search_range_info(self._h, C.byref(info)))
         return info.as_dict()
 
     def debug_keep_raw(self, on=True):
@@ -652,3 +741,11 @@ class Database:
         allowed = np.fromiter((i for i, doc in self._documents.items() if predicate(doc)), np.uint64)
         ids, _, counts = self.index.search_exact_filtered_batch(vectors, number_of_results, self.metric, allowed)
         return {b: {int(i): self._documents.get(int(i)) for i in ids[b, :counts[b]]} for b in range(ids.shape[0])}
+
+    def query_vectors_within(self, vectors, radius):
+        """every record within `radius` of each query (LSHIndex.search_range_batch: exact, however many there are)
+        -> {query index: {id: document}}, each query's records in ascending (key, id) order"""
+        if self.index.no_vectors():
+            return {}
+        offsets, ids, _ = self.index.search_range_batch(vectors, radius, self.metric)
+        return {b: {int(i): self._documents.get(int(i)) for i in ids[int(offsets[b]):int(offsets[b + 1])]} for b in range(offsets.size - 1)}

@@ -1,4 +1,4 @@
-/* Plain C99 user of the C ABI (include/zebra_hip.h): insert vectors, search a batch, grow the index, remove, compact, filter, range.
+/* Plain C99 user of the C ABI (include/zebra_hip.h): insert vectors, search a batch, grow the index, remove, compact, filter, range, self-join.
  *   gcc -std=c99 -Iinclude examples/search_example.c -Lzebra_amd/lib -lzebra_hip -Wl,-rpath,$PWD/zebra_amd/lib -o /tmp/ex && /tmp/ex
  * Mirrors what Database::insert_records / query_vectors do in the reference (src/database/core.rs:245-254, 290-313). */
 #include <stdio.h>
@@ -100,6 +100,25 @@ int main(void) {
     ok = ok && near;
     free(near_ids);
     free(near_keys);
+
+    /* self-join: the near-duplicate pass over the whole table as ONE call -- every pair of live rows (a, b), a < b, within the same radius, each
+     * pair once and no row against itself.  One threshold key for the call; capacity 0 counts, the second call fetches. */
+    uint64_t join_key, n_pairs = 0;
+    memcpy(&join_key, &radius, sizeof radius);
+    rc = zh_self_join(idx, join_key, ZH_L2SQ, 0, 0, NULL, NULL, NULL, &n_pairs);
+    if (rc != ZH_OK && rc != ZH_ELIMIT) { fprintf(stderr, "zh_self_join failed (%d): %s\n", rc, zh_last_error()); return 1; }
+    uint64_t *pa = malloc(sizeof(uint64_t) * (n_pairs + 1)), *pb = malloc(sizeof(uint64_t) * (n_pairs + 1)), *pk = malloc(sizeof(uint64_t) * (n_pairs + 1));
+    CHECK(zh_self_join(idx, join_key, ZH_L2SQ, 0, n_pairs, pa, pb, pk, &n_pairs));
+    zh_join_info ji;
+    CHECK(zh_self_join_info(idx, &ji));
+    int joined = ji.pairs == n_pairs;
+    for (uint64_t i = 0; i < n_pairs; i++) joined &= pa[i] < pb[i] && pk[i] <= join_key && (i == 0 || pa[i - 1] <= pa[i]);
+    printf("self-join: %llu pairs within L2^2 <= %.1f among %llu live rows, path %u; %s\n", (unsigned long long)n_pairs, radius,
+           (unsigned long long)ji.rows_live, ji.path, joined ? "ordered and within the radius" : "NOT as specified");
+    ok = ok && joined;
+    free(pa);
+    free(pb);
+    free(pk);
     zh_index_destroy(idx);
     free(rows);
     free(q);

@@ -299,6 +299,29 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_search_range_info(h_.get(), &info));
         return info;
     }
+    // every pair of distinct live rows (a, b), a < b, whose key (stored row b against a query equal to row a) is <= max_key (zh_self_join),
+    // ascending by (a, key, b): one call that counts, one that fetches.  max_key: ~0 = every pair.
+    struct JoinedPair {
+        Id a, b;
+        DistanceUnit key;
+    };
+    template <class Met>
+    std::vector<JoinedPair> self_join(DistanceUnit max_key, const Met &metric) const {
+        std::uint64_t total = 0;
+        const int rc = zh_self_join(h_.get(), max_key, Met::metric, metric.mode(), 0, nullptr, nullptr, nullptr, &total);
+        if (rc != ZH_ELIMIT) check(rc);
+        std::vector<Id> a(total + 1), b(total + 1);
+        std::vector<DistanceUnit> keys(total + 1);
+        if (total) check(zh_self_join(h_.get(), max_key, Met::metric, metric.mode(), total, a.data(), b.data(), keys.data(), &total));
+        std::vector<JoinedPair> out(total);
+        for (std::uint64_t i = 0; i < total; i++) out[i] = JoinedPair{a[i], b[i], keys[i]};
+        return out;
+    }
+    zh_join_info join_info() const {
+        zh_join_info info{};
+        check(zh_self_join_info(h_.get(), &info));
+        return info;
+    }
     zh_index *handle() const { return h_.get(); }
 
   private:

@@ -27,6 +27,7 @@
  *   zh_search_exact_batch[_device]       (new) exact top-k over every live row under the same keys: recall ground truth
  *   zh_search_exact_filtered_batch[_device] (new) the exact top-k among the live rows a caller's bitmap allows
  *   zh_search_range_batch[_device]       (new) every live row whose key is at or below a per-query threshold key, as a CSR
+ *   zh_self_join[_device]                (new) every pair of live rows whose key is at or below one threshold key, each pair once
  *   zh_index_save / zh_index_load        (new) a snapshot of an index in ONE file of this library's own format (the reference persists through
  *                                        fjall, lsh.rs:62-120, whose files are not read here): rows, removals, forest and the planes' sample rows
  *
@@ -448,6 +449,47 @@ typedef struct zh_range_info {  /* the most recent zh_search_range_* call on thi
     uint64_t launches;    /* launches of the scan (row chunks on path 1, one per internal batch on path 2) */
 } zh_range_info;
 ZH_API int zh_search_range_info(const zh_index *idx, zh_range_info *out);
+
+/* Exact SELF-JOIN (new; the reference's deduplicate removes bit-identical rows only): every unordered pair of distinct live stored rows (a, b),
+ * a < b by row number, whose key is <= max_key.  Rows removed by zh_index_remove / zh_index_deduplicate are excluded; no forest is needed.
+ * The key of a pair is the key zh_distance_batch gives for stored row b against a query equal to the f32 values of row a: the pairs starting at a
+ * are exactly the hits of zh_search_range_batch(rows[a], max_keys = {max_key}) with id > a.  That orientation is the definition; nothing relies on
+ * the key being the same with the roles swapped (DESIGN.md s15 says, metric by metric, that the canonical sums do give the same bits).  ONE
+ * threshold key for the whole call, a key as for the range search: zebra_amd.radius_key gives it, UINT64_MAX returns all L (L - 1) / 2 pairs of L
+ * live rows, and the parity cosine key's unsigned order is the definition.
+ * The result is three parallel arrays out_a, out_b, out_keys of *out_total entries, ids = id_base + row, ascending by (a, key, b).  If the pairs
+ * exceed `capacity` (the entries each array has room for) the call returns ZH_ELIMIT with *out_total exact -- allocate that many and call again --
+ * and the arrays unspecified.  capacity = 0 with NULL arrays is the supported way to count only.  An empty index, one live row and removed rows only
+ * give *out_total = 0 and ZH_OK.  A NULL index or out_total, NULL arrays with capacity > 0 and an unknown metric are refused before any device is
+ * touched.  All 13 metric / mode / power combinations and every dimension are served.  Locking and thread-safety as for zh_search_range_batch;
+ * zh_stats_t, zh_exact_info, zh_filtered_info, zh_range_info and the index's cached live-row views are left alone: zh_self_join_info describes the
+ * most recent call.
+ * Two paths, same answers.  Path 1 gathers panels of up to 1024 live rows as queries, keys the row chunks from the panel's first row on with the
+ * canonical sums and collects the keys at or below the threshold whose row is above the query row.  Path 2 (ZH_L2SQ, ZH_L2, ZH_COSINE at dim 256 /
+ * 384 / 512 / 768 / 1024, at least 8192 live rows, the fp16 row copy present) multiplies tiles of the fp16 row copy by each other on the matrix
+ * cores, the blocks on or above the diagonal only, for an interval per pair; the pairs whose interval reaches down to the threshold are candidates
+ * and only they get the canonical key.  The copy is scanned in panels of 16384 rows; a panel whose candidates outgrow their pool is answered by
+ * path 1 alone (`redone`); under a scan order that is not id order the first such panel sends the whole call to path 1.  ZH_JOIN_PATH=1 in the
+ * environment (read per call) keeps every panel on path 1.
+ * Device scratch is allocated per call and released before it returns.  With P = min(capacity, L (L - 1) / 2) hit slots: 32 P bytes of hit pool and
+ * sort buffers + the sort's temporary storage; on path 2 20 bytes per stored row and 8 bytes per candidate slot of one panel (max(1.25 x the
+ * capacity left, 256 per row of the panel) of them, never more than the panel's pairs); on path 1 the panel's rows and up to 1 GiB of key scratch;
+ * for the host call 24 bytes per pair as staging. */
+ZH_API int zh_self_join(zh_index *idx, uint64_t max_key, int metric, int cosine_mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b,
+                        uint64_t *out_keys, uint64_t *out_total);
+/* The same with every output (out_total included) in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_self_join_device(zh_index *idx, uint64_t max_key, int metric, int cosine_mode, uint64_t capacity, uint64_t *d_out_a, uint64_t *d_out_b,
+                               uint64_t *d_out_keys, uint64_t *d_out_total, void *stream);
+typedef struct zh_join_info {  /* the most recent zh_self_join* call on this index */
+    uint64_t rows_live;   /* live rows of the index */
+    uint64_t pairs;       /* pairs within the threshold (exact whatever the capacity) */
+    uint32_t path;        /* 1: canonical sums for every pair; 2: matrix-core intervals, canonical keys for the candidates only */
+    uint32_t redone;      /* path-2 panels whose candidate pool ran over and were answered by path 1 instead */
+    uint64_t candidates;  /* path 2: pairs that got the canonical key, over all panels path 2 completed */
+    uint64_t launches;    /* launches of the scan (row chunks on path 1, one per panel on path 2) */
+    uint64_t tiles;       /* path 2: 16 x 16 tile products issued, from the launch geometry (T (T + 1) / 2 for T tiles: nothing below the diagonal) */
+} zh_join_info;
+ZH_API int zh_self_join_info(const zh_index *idx, zh_join_info *out);
 
 /* Pipelined form of zh_search_batch_device (new; the reference has one blocking search per query): a context
  * is one in-flight batch with its own scratch.  The context calls do NOT take the index's internal lock (the blocking

@@ -104,6 +104,14 @@ class RangeInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class JoinInfo(C.Structure):
+    _fields_ = [("rows_live", C.c_uint64), ("pairs", C.c_uint64), ("path", C.c_uint32), ("redone", C.c_uint32), ("candidates", C.c_uint64),
+                ("launches", C.c_uint64), ("tiles", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CompactInfo(C.Structure):
     _fields_ = [("rows_before", C.c_uint64), ("rows_after", C.c_uint64), ("rows_moved", C.c_uint64), ("bytes_moved", C.c_uint64),
                 ("scratch_bytes", C.c_uint64), ("capacity_rows", C.c_uint64), ("copy_bytes_released", C.c_uint64), ("ms", C.c_double)]
@@ -170,6 +178,9 @@ SYMBOLS = [
     ("zh_search_range_batch", _i, [_vp, _vp, _sz, _vp, _i, _i, _u64, _vp, _vp, _vp, _vp]),
     ("zh_search_range_batch_device", _i, [_vp, _vp, _sz, _vp, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("zh_search_range_info", _i, [_vp, _vp]),
+    ("zh_self_join", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
+    ("zh_self_join_device", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
+    ("zh_self_join_info", _i, [_vp, _vp]),
     ("zh_search_ctx_create", _i, [_vp, _vp]),
     ("zh_search_ctx_destroy", None, [_vp]),
     ("zh_search_begin", _i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),

@@ -267,6 +267,11 @@ struct zh_index {
     // pool and its sort partner (v and key), path 2's candidate pool, the sort's temporary storage, offsets and outputs staged for the host call
     DevBuf rg_maxk, rg_cnt, rg_ctr, rg_pv0, rg_pv1, rg_pk0, rg_pk1, rg_cand, rg_tmp, rg_off, rg_oids, rg_okeys;
     zh_range_info rg_info{};  // (stats_mu)
+    // the self-join's per-call scratch (all released before the call returns): {hit, candidate, panel-row} counters, the threshold's bound, the hit
+    // pool and its sort partner, path 2's per-position views, block table and candidate pool, a redone panel's row list, the sort's temporary storage
+    // and the outputs staged for the host call
+    DevBuf jn_ctr, jn_maxk, jn_tau, jn_pv0, jn_pv1, jn_pk0, jn_pk1, jn_qm, jn_cid, jn_first, jn_cand, jn_rows, jn_tmp, jn_oa, jn_ob, jn_okeys;
+    zh_join_info jn_info{};  // (stats_mu)
 
     bool broken = false;  // an incremental add failed half way: trees are stale until zh_index_build
     bool rows_torn = false;  // ... or a compaction failed after rows had begun to move (set with broken): the TABLE is inconsistent until zh_index_clear
@@ -4101,6 +4106,244 @@ extern "C" int zh_search_range_info(const zh_index *ix, zh_range_info *out) {
     zh_index *m = const_cast<zh_index *>(ix);
     std::lock_guard<std::mutex> lk(m->stats_mu);
     *out = m->rg_info;
+    return ZH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// exact self-join (zh_join.hip + the exact search's score kernel): every pair of live rows a < b with key(stored b, query a) <= one threshold key,
+// as three arrays ascending by (a, key, b).  DESIGN.md s15
+// ------------------------------------------------------------------------------------------------
+#define ZH_JOIN_CAND_FLOOR 256u  // path 2: candidate slots per held row of a panel that are there whatever the capacity (a count-only call still lists candidates)
+
+static void join_release_scratch(zh_index *ix) {
+    exact_release_scratch(ix);
+    DevBuf *bs[] = {&ix->jn_ctr, &ix->jn_maxk, &ix->jn_tau, &ix->jn_pv0, &ix->jn_pv1, &ix->jn_pk0, &ix->jn_pk1, &ix->jn_qm, &ix->jn_cid, &ix->jn_first,
+                    &ix->jn_cand, &ix->jn_rows, &ix->jn_tmp, &ix->jn_oa, &ix->jn_ob, &ix->jn_okeys};
+    for (DevBuf *b : bs) b->release();
+}
+struct JoinScratchGuard {
+    zh_index *ix;
+    ~JoinScratchGuard() { join_release_scratch(ix); }
+};
+
+// Path 1 for the B <= ZH_EXACT_BATCH query rows dQRows (row numbers, device): gathered into the query buffer, exact_score_kernel's keys of the live
+// rows from position p_from of the ascending live list on (no live row before it is above any of the query rows), join_collect_kernel over them.
+// Hits are counted in jn_ctr[0] and pooled while the pool has room.
+static int join_batch1(zh_index *ix, const uint32_t *dQRows, uint32_t B, uint64_t p_from, uint64_t max_key, int metric, int mode, uint64_t pool_cap,
+                       hipStream_t s, uint64_t *launches) {
+    const uint32_t d = ix->opt.dim;
+    const uint64_t n_live = ix->ex_n_live;
+    if (!B || p_from >= n_live) return ZH_OK;
+    const uint64_t rc_rows = std::min<uint64_t>(std::max<uint64_t>(256, ZH_EXACT_KEY_BYTES / 8 / B), n_live - p_from);
+    int rc;
+    if ((rc = ix->ex_Q.ensure((size_t)B * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_keys.ensure((size_t)B * rc_rows * 8))) return rc;
+    const int param = metric == ZH_COSINE ? mode : ((metric == ZH_MINKOWSKI || metric == ZH_PNORM) ? mode : 0);
+    HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dQRows, B, ix->ex_Q.as<float>(), s));
+    HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), B, d, ix->ex_QQ.as<float>(), s));
+    for (uint64_t p0 = p_from; p0 < n_live; p0 += rc_rows) {
+        const uint32_t nr = (uint32_t)std::min<uint64_t>(rc_rows, n_live - p0);
+        HIPCHK(zh_launch_exact_score(ix->X.as<float>(), d, ix->ex_live.as<uint32_t>(), p0, nr, ix->ex_Q.as<float>(), ix->ex_QQ.as<float>(), B, metric, param,
+                                     ix->ex_keys.as<uint64_t>(), rc_rows, s));
+        HIPCHK(zh_launch_join_collect(ix->ex_keys.as<uint64_t>(), rc_rows, ix->ex_live.as<uint32_t>(), p0, nr, dQRows, B, max_key,
+                                      ix->jn_ctr.as<unsigned long long>(), ix->jn_pv0.as<uint64_t>(), ix->jn_pk0.as<uint64_t>(), pool_cap, s));
+        (*launches)++;
+    }
+    return ZH_OK;
+}
+
+// Path 2 of the whole call: the threshold as a fixed bound, the copy's rows as approx_interval's queries, then panel after panel of
+// ZH_JOIN_PANEL_ROWS held positions: one matrix-core launch over the panel's blocks on or above the diagonal, canonical keys and the judgement for
+// its candidates.  A panel whose candidates outgrow the pool (nothing of it was counted) is answered by path 1 from its rows' list -- in id order;
+// under a row order the first such panel ends path 2 and the whole call is answered by path 1.  *used = false: path 2 does not serve this index,
+// or was given up (inf->path says 2 then): nothing is counted or pooled and path 1 answers everything.  *hits = jn_ctr[0] on return with *used.
+static int join_path2(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t pool_cap, hipStream_t s, zh_join_info *inf, bool *used, uint64_t *hits) {
+    *used = false;
+    const uint32_t d = ix->opt.dim;
+    if (!zh_exact_mfma_supported(d, metric) || ix->ex_n_live < 8192) return ZH_OK;
+    int rc;
+    const void *Xh;
+    const float2 *rowMeta;
+    const uint32_t *perm;
+    uint64_t perm_rows;
+    float rho;
+    {
+        std::lock_guard<std::mutex> lb(ix->blk_mu);
+        bool ok = false;
+        if ((rc = ensure_row_half(ix, &ok))) return rc;
+        if (!ok || !ix->row_half.p) return ZH_OK;  // no room for the fp16 copy: path 1
+        Xh = ix->row_half.p; rowMeta = ix->row_meta.as<float2>(); rho = ix->row_rho;
+        perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr; perm_rows = ix->perm_rows;
+    }
+    const uint64_t n = ix->n_rows, T = (n + 15) / 16, n_pos = T * 16;
+    const uint32_t n_ab_max = ZH_JOIN_PANEL_ROWS / 64;
+    if ((rc = ix->jn_qm.ensure(n_pos * 16)) || (rc = ix->jn_cid.ensure(n_pos * 4)) || (rc = ix->jn_tau.ensure(4)) || (rc = ix->jn_maxk.ensure(8)) ||
+        (rc = ix->jn_first.ensure((n_ab_max + 1) * 4)))
+        return rc;
+    unsigned long long *ctr = ix->jn_ctr.as<unsigned long long>();  // {hits, the panel's candidates, a redone panel's rows}
+    HIPCHK(hipMemcpyAsync(ix->jn_maxk.p, &max_key, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(zh_launch_range_tau(ix->jn_maxk.as<uint64_t>(), 1, metric, mode, ix->jn_tau.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_prep(rowMeta, perm, perm_rows, ix->ex_bits.as<uint32_t>(), n, rho, ix->jn_qm.as<float4>(), ix->jn_cid.as<uint32_t>(), s));
+    HIPCHK(hipStreamSynchronize(s));  // (max_key is the caller's stack)
+    *used = true;
+    inf->path = 2;
+    const float Kc = zh_approx_bound(metric, d, 1);
+    std::vector<uint32_t> first(n_ab_max + 1);
+    uint64_t rank_row = 0, rank = 0;  // live rows before row rank_row (id order: a redone panel's first chunk)
+    for (uint64_t P0 = 0; P0 < n; P0 += ZH_JOIN_PANEL_ROWS) {
+        const uint64_t P1 = std::min<uint64_t>(n, P0 + ZH_JOIN_PANEL_ROWS), tileA0 = P0 / 16, tileA1 = (P1 + 15) / 16;
+        const uint32_t n_ab = (uint32_t)((tileA1 - tileA0 + 3) / 4);
+        const uint64_t products = zh_join_geometry(T, tileA0, tileA1, first.data());
+        const uint64_t panel_rows = P1 - P0, pairs_bound = panel_rows * (n - P0), pool_left = pool_cap > *hits ? pool_cap - *hits : 0;
+        const uint64_t cand_cap = std::min<uint64_t>(pairs_bound, std::max<uint64_t>(pool_left + pool_left / 4, (uint64_t)ZH_JOIN_CAND_FLOOR * panel_rows));
+        if ((rc = ix->jn_cand.ensure(cand_cap * 8))) return rc;
+        HIPCHK(hipMemcpyAsync(ix->jn_first.p, first.data(), ((size_t)n_ab + 1) * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(ctr + 1, 0, 16, s));
+        HIPCHK(zh_launch_join_mfma(d, metric, mode, Xh, rowMeta, ix->jn_qm.as<float4>(), ix->jn_cid.as<uint32_t>(), n, tileA0, ix->jn_first.as<uint32_t>(), n_ab,
+                                   first[n_ab], Kc, rho, ix->jn_tau.as<uint32_t>(), ix->jn_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
+        inf->launches++;
+        inf->tiles += products;
+        HIPCHK(zh_launch_join_survivors(ix->X.as<float>(), d, metric, mode, ix->jn_cand.as<uint64_t>(), ctr + 1, cand_cap, max_key, ctr,
+                                        ix->jn_pv0.as<uint64_t>(), ix->jn_pk0.as<uint64_t>(), pool_cap, s));
+        unsigned long long h_ctr[3] = {0, 0, 0};
+        HIPCHK(hipMemcpyAsync(h_ctr, ctr, 24, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (h_ctr[1] <= cand_cap) {
+            inf->candidates += h_ctr[1];
+            *hits = h_ctr[0];
+            continue;
+        }
+        inf->redone++;
+        if (perm_rows) {
+            // Under a row order a panel owns its pairs by POSITION (the lower position lies in it), and path 1 owns pairs by row number: the
+            // redo below would count a different set.  So nothing of path 2 is kept: counters and pool rewound, the whole call answered by path 1.
+            HIPCHK(hipMemsetAsync(ctr, 0, 32, s));
+            inf->candidates = 0;
+            *hits = 0;
+            *used = false;
+            return ZH_OK;
+        }
+        if ((rc = ix->jn_rows.ensure(panel_rows * 4))) return rc;
+        HIPCHK(zh_launch_join_panel_rows(ix->jn_cid.as<uint32_t>(), P0, P1, ix->jn_rows.as<uint32_t>(), ctr + 2, s));
+        HIPCHK(hipMemcpyAsync(h_ctr, ctr, 24, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        // positions are row numbers here: the panel's pairs by position are its pairs by row number, and the live rows before the panel are
+        // below every row of it
+        for (; rank_row < P0; rank_row++) rank += !(rank_row < ix->h_dead.size() && ix->h_dead[rank_row]);
+        const uint64_t p_from = rank;
+        for (uint64_t b0 = 0; b0 < h_ctr[2]; b0 += ZH_EXACT_BATCH) {
+            const uint32_t nb = (uint32_t)std::min<uint64_t>(ZH_EXACT_BATCH, h_ctr[2] - b0);
+            if ((rc = join_batch1(ix, ix->jn_rows.as<uint32_t>() + b0, nb, p_from, max_key, metric, mode, pool_cap, s, &inf->launches))) return rc;
+        }
+        HIPCHK(hipMemcpyAsync(h_ctr, ctr, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        *hits = h_ctr[0];
+    }
+    return ZH_OK;
+}
+
+static int join_args(zh_index *ix, int metric, int mode, uint64_t capacity, const void *a, const void *b, const void *keys, const void *total,
+                     const char *who) {
+    if (!ix || !total || (capacity && (!a || !b || !keys))) return fail(ZH_EINVAL, "%s: null argument", who);
+    return check_metric(metric, mode);
+}
+
+// The call on the index's device (under mu, exclusive; exact_live_rows has run).  host_out: outA / outB / outKeys are HOST arrays, filled through
+// staging; otherwise device arrays.  *total = the pairs, exact whatever the capacity.
+static int join_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *outA, uint64_t *outB, uint64_t *outKeys, bool host_out,
+                    hipStream_t s, uint64_t *total, const char *who) {
+    zh_join_info inf{};
+    inf.path = 1;
+    inf.rows_live = ix->ex_n_live;
+    const uint64_t n_live = ix->ex_n_live;
+    uint64_t hits = 0;
+    int rc;
+    if (n_live >= 2) {
+        const uint64_t pool_cap = std::min<uint64_t>(capacity, n_live * (n_live - 1) / 2);
+        if ((rc = ix->jn_ctr.ensure(32)) || (rc = ix->jn_pv0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)) ||
+            (rc = ix->jn_pk0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)))
+            return rc;
+        HIPCHK(hipMemsetAsync(ix->jn_ctr.p, 0, 32, s));
+        const char *env_p = getenv("ZH_JOIN_PATH");
+        bool used = false;
+        if (!(env_p && atoi(env_p) == 1) && (rc = join_path2(ix, max_key, metric, mode, pool_cap, s, &inf, &used, &hits))) return rc;
+        if (!used) {  // panels of the ascending live list: panel [a0, a0 + B) against the live rows from a0 on
+            for (uint64_t a0 = 0; a0 + 1 < n_live; a0 += ZH_EXACT_BATCH) {
+                const uint32_t B = (uint32_t)std::min<uint64_t>(ZH_EXACT_BATCH, n_live - a0);
+                if ((rc = join_batch1(ix, ix->ex_live.as<uint32_t>() + a0, B, a0, max_key, metric, mode, pool_cap, s, &inf.launches))) return rc;
+            }
+            unsigned long long h = 0;
+            HIPCHK(hipMemcpyAsync(&h, ix->jn_ctr.p, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            hits = h;
+        }
+    }
+    *total = hits;
+    inf.pairs = hits;
+    const bool over = hits > capacity;
+    if (!over && hits) {
+        uint64_t *dV[2] = {nullptr, nullptr}, *dK[2] = {nullptr, nullptr};
+        size_t tmp_bytes = 0;
+        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, nullptr, &tmp_bytes, 0, nullptr, nullptr, nullptr, s));
+        if ((rc = ix->jn_pv1.ensure(hits * 8)) || (rc = ix->jn_pk1.ensure(hits * 8)) || (rc = ix->jn_tmp.ensure(tmp_bytes))) return rc;
+        if (host_out && ((rc = ix->jn_oa.ensure(hits * 8)) || (rc = ix->jn_ob.ensure(hits * 8)) || (rc = ix->jn_okeys.ensure(hits * 8)))) return rc;
+        dV[0] = ix->jn_pv0.as<uint64_t>(); dV[1] = ix->jn_pv1.as<uint64_t>();
+        dK[0] = ix->jn_pk0.as<uint64_t>(); dK[1] = ix->jn_pk1.as<uint64_t>();
+        uint64_t *oa = host_out ? ix->jn_oa.as<uint64_t>() : outA, *ob = host_out ? ix->jn_ob.as<uint64_t>() : outB;
+        uint64_t *ok = host_out ? ix->jn_okeys.as<uint64_t>() : outKeys;
+        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, ix->jn_tmp.p, &tmp_bytes, ix->opt.id_base, oa, ob, ok, s));
+        if (host_out) {
+            HIPCHK(hipMemcpyAsync(outA, oa, hits * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(outB, ob, hits * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(outKeys, ok, hits * 8, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        ix->jn_info = inf;
+    }
+    if (over)
+        return fail(ZH_ELIMIT, "%s: %llu pairs exceed the capacity of %llu; out_total is exact, call again with that capacity", who,
+                    (unsigned long long)hits, (unsigned long long)capacity);
+    return ZH_OK;
+}
+
+extern "C" int zh_self_join_device(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *d_out_a, uint64_t *d_out_b,
+                                   uint64_t *d_out_keys, uint64_t *d_out_total, void *stream) {
+    int rc = join_args(ix, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, d_out_total, "zh_self_join_device");
+    if (rc) return rc;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    JoinScratchGuard guard{ix};
+    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    uint64_t total = 0;
+    rc = join_run(ix, max_key, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, false, s, &total, "zh_self_join_device");
+    if (rc && rc != ZH_ELIMIT) return rc;
+    HIPCHK(hipMemcpyAsync(d_out_total, &total, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return rc;
+}
+
+extern "C" int zh_self_join(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b, uint64_t *out_keys,
+                            uint64_t *out_total) {
+    int rc = join_args(ix, metric, mode, capacity, out_a, out_b, out_keys, out_total, "zh_self_join");
+    if (rc) return rc;
+    *out_total = 0;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    JoinScratchGuard guard{ix};
+    uint64_t total = 0;
+    rc = join_run(ix, max_key, metric, mode, capacity, out_a, out_b, out_keys, true, ix->stream, &total, "zh_self_join");
+    if (rc && rc != ZH_ELIMIT) return rc;
+    *out_total = total;
+    return rc;
+}
+
+extern "C" int zh_self_join_info(const zh_index *ix, zh_join_info *out) {
+    if (!ix || !out) return fail(ZH_EINVAL, "zh_self_join_info: null argument");
+    zh_index *m = const_cast<zh_index *>(ix);
+    std::lock_guard<std::mutex> lk(m->stats_mu);
+    *out = m->jn_info;
     return ZH_OK;
 }
 

@@ -348,6 +348,38 @@ hipError_t zh_launch_range_offsets(const uint32_t *dCnt, uint32_t B, uint64_t ba
 hipError_t zh_launch_range_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows, uint32_t B, void *dTmp, size_t *tmp_bytes, uint64_t id_base,
                                 uint64_t *dOutIds, uint64_t *dOutKeys, hipStream_t s);
 
+// ---- the exact self-join (zh_join.hip): every pair of live rows a < b with key(stored b, query a) <= one threshold key.  A hit pool is two u64
+// arrays, v = a << 32 | b (row numbers) and the key; *dHitCtr counts every hit whether or not the pool has room
+#define ZH_JOIN_CHUNK 64u          // tiles J one block of the matrix-core scan walks
+#define ZH_JOIN_PANEL_ROWS 16384u  // positions of the copy one launch holds (256 blocks of four tiles); a panel is the unit path 1 redoes
+// path 1: dQ[b] = the f32 row dRows[b]
+hipError_t zh_launch_join_gather(const float *dX, uint32_t d, const uint32_t *dRows, uint32_t B, float *dQ, hipStream_t s);
+// ... and of the keys [b][p - p0] (zh_launch_exact_score) those <= max_key whose row dLive[p] is above the query row dQRows[b]
+hipError_t zh_launch_join_collect(const uint64_t *dKeys, uint64_t ld, const uint32_t *dLive, uint64_t p0, uint32_t nr, const uint32_t *dQRows, uint32_t B,
+                                  uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
+// path 2: per position of the fp16 copy (ceil(n_rows / 16) * 16 of them) dQm = the row as approx_interval's query, dCid = its row number or
+// UINT32_MAX (removed, or past the table)
+hipError_t zh_launch_join_prep(const float2 *dRowMeta, const uint32_t *dPerm, uint64_t perm_rows, const uint32_t *dLiveBits, uint64_t n_rows, float rho,
+                               float4 *dQm, uint32_t *dCid, hipStream_t s);
+// the blocks of a panel of held tiles [tileA0, tileA1) of T: first[ab] = blocks before held block ab (n_ab + 1 entries, caller's array); returns the
+// 16 x 16 tile products the panel issues
+uint64_t zh_join_geometry(uint64_t T, uint64_t tileA0, uint64_t tileA1, uint32_t *first);
+// the scan of one panel against *dTau (zh_launch_range_tau of the one threshold); pairs with lo <= tau to dCand as min(row) << 32 | max(row);
+// *dCandCtr counts all of them (> cand_cap: ran over)
+hipError_t zh_launch_join_mfma(uint32_t d, int metric, int mode, const void *dXh, const float2 *dRowMeta, const float4 *dQm, const uint32_t *dCid,
+                               uint64_t n_rows, uint64_t tileA0, const uint32_t *dFirst, uint32_t n_ab, uint32_t blocks, float Kc, float rho,
+                               const uint32_t *dTau, uint64_t *dCand, uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s);
+// the candidates' canonical keys, judged, counted and appended to the hit pool (nothing when the candidate pool ran over)
+hipError_t zh_launch_join_survivors(const float *dX, uint32_t d, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr,
+                                    uint64_t cand_cap, uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap,
+                                    hipStream_t s);
+// dList = the live rows at positions [p_begin, p_end), any order; *dCount += their number
+hipError_t zh_launch_join_panel_rows(const uint32_t *dCid, uint64_t p_begin, uint64_t p_end, uint32_t *dList, unsigned long long *dCount, hipStream_t s);
+// the pool's n entries ordered by (a, key, b) and written out as ids (id_base + row) and keys; dV / dK: the pool and a second buffer of the same size
+// each.  dTmp == nullptr: only *tmp_bytes is set, to what the sorts of n entries need
+hipError_t zh_launch_join_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows, void *dTmp, size_t *tmp_bytes, uint64_t id_base, uint64_t *dOutA,
+                               uint64_t *dOutB, uint64_t *dOutKeys, hipStream_t s);
+
 // ---- launchers (zh_score.hip): every sign of a forest built from stored rows, from N row scores per query --------
 // Prefilter (zh_search.hip, "Prefilter"): a batch hashed from row scores picks the rows that can be among a pair's k best from
 // those scores; only they are scored with the reference's arithmetic.  Lists: one per (tree, query), `cap` slots, list (t, b) at

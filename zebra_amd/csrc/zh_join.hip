@@ -1,0 +1,415 @@
+// zh_join.hip -- exact self-join (zh_self_join, driver in zh_api.hip): every unordered pair of distinct live stored rows (a, b), a < b by row number,
+// whose key is <= ONE threshold key.  The key of a pair is the key zh_distance_batch gives for stored row b against a query equal to the f32 values
+// of row a; that orientation is the definition, and every key below is computed in it.  The answer is three parallel arrays ascending by
+// (a, key, b), ids = id_base + row.  DESIGN.md s15.
+//
+// A hit is (a, b, key).  Both paths append hits to ONE pool per call -- v = a << 32 | b and the key, two u64 arrays -- and count them in *ctr whether
+// or not the pool still has room: the total stays exact when the caller's capacity is too small (or 0: count only).  A pool slot is taken with one
+// atomic per WAVE (range_wave_slots's pattern, restated here: zh_range.hip is left alone).
+//   path 1  a panel of up to 1024 live rows is gathered device-to-device into a query buffer (join_gather_kernel), exact_score_kernel (zh_exact.hip)
+//           keys the row chunks from the panel's first row on into the key scratch [query][position], join_collect_kernel takes the keys <= max_key
+//           whose row number is greater than the query row's.
+//   path 2  join_mfma_kernel: BOTH operands of v_mfma_f32_16x16x32_f16 are tiles of the index's fp16 row copy (the A and the B operand have the same
+//           per-lane layout: lane l holds line l % 16, k-chunk l / 16), so a 16 x 16 block of the table's Gram matrix needs no conversion, and only
+//           the blocks on or above the diagonal are computed.  A wave holds its 16-row tile I in registers; the four waves of a block hold four
+//           consecutive tiles and share every tile J >= I through LDS (two buffers of 32 d bytes: 64 KiB at d = 1024), so a tile crosses L2 -> CU
+//           once per 64 held rows.  LDS holds a tile exactly as global memory does -- lane l reads the 16 bytes at 16 l of a 1-KiB step, which puts
+//           each of ds_read_b128's four 16-lane groups on 16 distinct 16-byte slots of the 256-byte bank row: no conflict, no padding.  The sum is
+//           (acc0 + acc1) + (acc2 + acc3) as in range_mfma_kernel: zh_approx_bound(metric, d, 1) stays the accumulation bound.  approx_interval
+//           (unchanged) gives the pair's interval: the held row is its "stored row", the LDS row its "query", whose qm = {scale, |x|^2, an upper
+//           bound of |x|, dq = rho times that bound rounded up} comes from the row's rowMeta entry (join_prep_kernel).  Pairs with lo <= tau go to a
+//           candidate pool as min(id) << 32 | max(id) (positions are not ids under a row order); join_survivors_kernel gives every candidate the
+//           canonical key of (row b, query = f32 row a), both rows read from the f32 table, judges key <= max_key, counts and compacts.
+// Then, while the capacity holds, the pool is ordered by (a, key, b) with three stable LSD radix sorts (b bits, then the key, then the a bits;
+// rocPRIM through hipCUB) and join_emit_kernel writes the three arrays.
+// Scratch (all per call, released before return): path 2 holds 20 bytes per position (qm and the id-or-masked word), 8 bytes per candidate slot of
+// one panel (at most max(1.25 x the capacity left, 256 per held row) and never more than the panel's pairs) and a block table of 4 bytes per 64 held
+// rows; path 1 the exact search's query buffer and key scratch (<= 1 GiB); both 16 bytes per hit-pool slot (<= the capacity), and for the order as
+// much again plus hipCUB's temporary storage, and 24 bytes per hit of staging for the host call.
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+
+#include "zh_internal.h"
+#include "zh_device.h"
+
+typedef _Float16 f16x8j __attribute__((ext_vector_type(8)));
+typedef float f32x4j __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4j __attribute__((ext_vector_type(4)));
+
+// the lanes of `m` (a ballot) get consecutive pool slots: one atomic for the wave, taken by lane 0 (every lane of the wave is active at the call)
+__device__ __forceinline__ unsigned long long join_wave_slots(unsigned long long *__restrict__ ctr, uint64_t m, uint32_t lane) {
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(ctr, (unsigned long long)__popcll(m));
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
+    return (((unsigned long long)hi << 32) | lo) + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+}
+
+// ---- path 1: the panel's rows as queries.  One wave per row ----
+__global__ __launch_bounds__(256) void join_gather_kernel(const float *__restrict__ X, uint32_t d, const uint32_t *__restrict__ rows, uint32_t B,
+                                                          float *__restrict__ Q) {
+    const uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= B) return;
+    const float *x = X + (size_t)rows[b] * d;
+    float *q = Q + (size_t)b * d;
+    for (uint32_t e = lane; e < d; e += 64) q[e] = x[e];
+}
+
+hipError_t zh_launch_join_gather(const float *dX, uint32_t d, const uint32_t *dRows, uint32_t B, float *dQ, hipStream_t s) {
+    if (!B) return hipSuccess;
+    hipLaunchKernelGGL(join_gather_kernel, dim3((B + 3) / 4), dim3(256), 0, s, dX, d, dRows, B, dQ);
+    return hipGetLastError();
+}
+
+// the hits of a keyed row chunk: key <= max_key and the stored row's number above the query row's.  grid (ceil(nr / 256), B)
+__global__ __launch_bounds__(256) void join_collect_kernel(const uint64_t *__restrict__ keys, uint64_t ld, const uint32_t *__restrict__ live, uint64_t p0,
+                                                           uint32_t nr, const uint32_t *__restrict__ qrows, uint64_t max_key,
+                                                           unsigned long long *__restrict__ ctr, uint64_t *__restrict__ pv, uint64_t *__restrict__ pk,
+                                                           uint64_t cap) {
+    const uint32_t b = blockIdx.y, lane = threadIdx.x & 63;
+    const uint32_t rl = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t a = qrows[b];
+    uint64_t key = 0;
+    uint32_t row = 0;
+    bool hit = false;
+    if (rl < nr) {
+        row = live[p0 + rl];
+        key = keys[(size_t)b * ld + rl];
+        hit = row > a && key <= max_key;
+    }
+    const uint64_t m = __ballot(hit);
+    if (!m) return;  // (wave-uniform)
+    const unsigned long long slot = join_wave_slots(ctr, m, lane);  // always: the count stays exact when the pool is full
+    if (hit && slot < cap) {
+        pv[slot] = ((uint64_t)a << 32) | row;
+        pk[slot] = key;
+    }
+}
+
+hipError_t zh_launch_join_collect(const uint64_t *dKeys, uint64_t ld, const uint32_t *dLive, uint64_t p0, uint32_t nr, const uint32_t *dQRows, uint32_t B,
+                                  uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s) {
+    if (!nr || !B) return hipSuccess;
+    hipLaunchKernelGGL(join_collect_kernel, dim3((nr + 255) / 256, B), dim3(256), 0, s, dKeys, ld, dLive, p0, nr, dQRows, max_key, dHitCtr, dPoolV, dPoolK,
+                       pool_cap);
+    return hipGetLastError();
+}
+
+// ---- path 2: what the scan reads per POSITION of the copy (ceil(n / 16) * 16 of them).  cid = the row's number, or UINT32_MAX for a removed row
+// and for the tail of the last tile.  qm = approx_interval's view of the row as a query: {1 / sigma, f32 |x|^2, nq >= |x|, dq >= |x - x'|}, x' the
+// copy's row: l2_E's comment gives |x - x'| <= rho |x| for every usable row of the copy, so dq = rho * nq rounded up.  The tests are qhalf_kernel's:
+// a scale outside 2^-104 .. 2^76 (an exponent outside -90 .. 90), a row that is not usable or a norm that is no finite number leaves all four NaN --
+// nothing certain, every pair of the row a candidate. ----
+__global__ __launch_bounds__(256) void join_prep_kernel(const float2 *__restrict__ rowMeta, const uint32_t *__restrict__ perm, uint64_t perm_rows,
+                                                        const uint32_t *__restrict__ liveBits, uint64_t n_rows, uint64_t n_pos, float rho,
+                                                        float4 *__restrict__ qm, uint32_t *__restrict__ cid) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n_pos) return;
+    uint32_t id = 0xFFFFFFFFu;
+    float4 o = make_float4(NAN, NAN, NAN, NAN);
+    if (p < n_rows) {
+        const uint32_t r = perm && p < perm_rows ? perm[p] : (uint32_t)p;
+        if ((liveBits[r >> 5] >> (r & 31)) & 1u) id = r;
+        const float2 rm = rowMeta[p];
+        if (rm.y >= 4.930380657631324e-32f && rm.y <= 7.555786372591432e+22f && (rm.x - rm.x == 0.f)) {  // 2^-104, 2^76
+            const float nq = sqrtf(rm.x) * (1.0f + 1e-5f);
+            o = make_float4(rm.y, rm.x, nq, (rho * nq) * 1.0000005f);  // (two roundings of 2^-24 each, under the factor's 2^-21)
+        }
+    }
+    qm[p] = o;
+    cid[p] = id;
+}
+
+hipError_t zh_launch_join_prep(const float2 *dRowMeta, const uint32_t *dPerm, uint64_t perm_rows, const uint32_t *dLiveBits, uint64_t n_rows, float rho,
+                               float4 *dQm, uint32_t *dCid, hipStream_t s) {
+    const uint64_t n_pos = (n_rows + 15) / 16 * 16;
+    if (!n_pos) return hipSuccess;
+    hipLaunchKernelGGL(join_prep_kernel, dim3((uint32_t)((n_pos + 255) / 256)), dim3(256), 0, s, dRowMeta, dPerm, perm_rows, dLiveBits, n_rows, n_pos, rho, dQm,
+                       dCid);
+    return hipGetLastError();
+}
+
+// The launch geometry of a panel of held tiles [tileA0, tileA1) of T (tileA0 a multiple of 4; tileA1 one too, or T).  A block holds four consecutive
+// tiles from I0 = tileA0 + 4 ab and walks ONE chunk of ZH_JOIN_CHUNK tiles J, chunk c = [I0 + c CH, min(T, I0 + (c + 1) CH)): chunks are counted from
+// the block's own diagonal, so none lies wholly below it and none is launched that would.  first[ab] = the panel's blocks before held block ab
+// (first[n_ab] = all of them).  A wave skips the tiles J < I of the first chunk, and a block's chunks cover [I0, T) once: wave I issues T - I tile
+// products.  Returns their sum over the panel -- the `tiles` of zh_join_info, from the geometry alone.
+uint64_t zh_join_geometry(uint64_t T, uint64_t tileA0, uint64_t tileA1, uint32_t *first) {
+    const uint64_t n_ab = (tileA1 - tileA0 + 3) / 4;
+    uint64_t blocks = 0, products = 0;
+    for (uint64_t ab = 0; ab < n_ab; ab++) {
+        const uint64_t I0 = tileA0 + 4 * ab;
+        first[ab] = (uint32_t)blocks;
+        blocks += (T - I0 + ZH_JOIN_CHUNK - 1) / ZH_JOIN_CHUNK;
+        for (uint64_t I = I0; I < I0 + 4 && I < T; I++) products += T - I;
+    }
+    first[n_ab] = (uint32_t)blocks;
+    return products;
+}
+
+template <int D, int KINDA>
+__global__ __launch_bounds__(256) void join_mfma_kernel(const u32x4j *__restrict__ Xh, const float2 *__restrict__ rowMeta, const float4 *__restrict__ qm,
+                                                        const uint32_t *__restrict__ cid, uint64_t T, uint64_t tileA0, const uint32_t *__restrict__ first,
+                                                        uint32_t n_ab, float Kc, float rho, const uint32_t *__restrict__ tau, uint64_t *__restrict__ cand,
+                                                        uint64_t cap, unsigned long long *__restrict__ ctr) {
+    constexpr int NS = D / 32;        // MFMA steps of a tile (K = 32 each) = its KiB
+    constexpr int PIECES = NS * 64;   // 16-byte pieces of a tile
+    constexpr int PT = PIECES / 256;  // ... per thread of the block
+    __shared__ u32x4j sB[2][PIECES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, h = lane >> 4;
+    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    // the held block: the last ab with first[ab] <= blockIdx.x (block-uniform)
+    uint32_t lo = 0, hi = n_ab;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first[mid] <= blockIdx.x) lo = mid; else hi = mid;
+    }
+    const uint64_t I0 = tileA0 + 4ull * lo, I = I0 + wid;
+    const uint64_t Jb = I0 + (uint64_t)(blockIdx.x - first[lo]) * ZH_JOIN_CHUNK, Je = Jb + ZH_JOIN_CHUNK < T ? Jb + ZH_JOIN_CHUNK : T;
+    const bool active = I < T;  // (wave-uniform; an idle wave of the table's last block still moves tiles and meets the barriers)
+    f16x8j A[NS];
+    uint32_t id[4];
+    float2 meta[4];
+    if (active) {
+        const u32x4j *tp = Xh + (size_t)I * PIECES + lane;
+#pragma unroll
+        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8j, tp[64 * st]);
+        // this lane's outputs: rows 4 h + i of the held tile (register i), column c16 = row c16 of tile J
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint64_t p = I * 16 + 4 * h + i;
+            id[i] = cid[p];
+            meta[i] = id[i] != 0xFFFFFFFFu ? rowMeta[p] : make_float2(0.f, 0.f);
+        }
+    } else {
+#pragma unroll
+        for (int st = 0; st < NS; st++) A[st] = f16x8j{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 4; i++) { id[i] = 0xFFFFFFFFu; meta[i] = make_float2(0.f, 0.f); }
+    }
+    const uint32_t tq = tau[0];
+    {
+        const u32x4j *src = Xh + (size_t)Jb * PIECES + tid;
+#pragma unroll
+        for (int k = 0; k < PT; k++) sB[0][k * 256 + tid] = src[k * 256];
+    }
+    // the column rows' id-or-masked word and qm travel one tile ahead, like the tile itself: nothing of tile J is fetched in its compute phase
+    uint32_t cb_next = cid[Jb * 16 + c16];
+    float4 qb_next = qm[Jb * 16 + c16];
+    __syncthreads();
+    for (uint64_t J = Jb; J < Je; J++) {
+        const uint32_t cur = (uint32_t)(J - Jb) & 1u;
+        const bool more = J + 1 < Je;  // (block-uniform)
+        const uint32_t cb = cb_next;
+        const float4 qb = qb_next;
+        u32x4j pf[PT];
+        if (more) {
+            const u32x4j *src = Xh + (size_t)(J + 1) * PIECES + tid;
+#pragma unroll
+            for (int k = 0; k < PT; k++) pf[k] = src[k * 256];
+            cb_next = cid[(J + 1) * 16 + c16];
+            qb_next = qm[(J + 1) * 16 + c16];
+        }
+        if (active && J >= I) {  // (wave-uniform)
+            const u32x4j *bp = &sB[cur][lane];
+            f32x4j acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+            for (int st = 0; st < NS; st++)
+                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8j, bp[64 * st]), acc[st & 3], 0, 0, 0);
+            const f32x4j t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+            const bool diag = J == I;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                bool pass = false;
+                // in a diagonal tile only p_a < p_b: held row 4 h + i before column row c16
+                if (id[i] != 0xFFFFFFFFu && cb != 0xFFFFFFFFu && (!diag || 4 * h + i < c16))
+                    pass = (uint32_t)approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qb, Kc, rho, 0.f) <= tq;
+                const uint64_t m = __ballot(pass);
+                if (m) {  // (wave-uniform)
+                    const unsigned long long slot = join_wave_slots(ctr, m, lane);
+                    if (pass && slot < cap) {
+                        const uint32_t a = id[i] < cb ? id[i] : cb, b = id[i] < cb ? cb : id[i];
+                        cand[slot] = ((uint64_t)a << 32) | b;
+                    }
+                }
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int k = 0; k < PT; k++) sB[cur ^ 1][k * 256 + tid] = pf[k];
+        }
+        __syncthreads();  // buffer cur ^ 1 was last read in the step before, which every wave left through this barrier
+    }
+}
+
+template <int KINDA>
+static hipError_t launch_join_mfma_kinda(uint32_t d, const void *Xh, const float2 *rowMeta, const float4 *qm, const uint32_t *cid, uint64_t T, uint64_t tileA0,
+                                         const uint32_t *dFirst, uint32_t n_ab, uint32_t blocks, float Kc, float rho, const uint32_t *dTau, uint64_t *dCand,
+                                         uint64_t cap, unsigned long long *dCtr, hipStream_t s) {
+#define ZH_JN_CASE(DD)                                                                                                                                 \
+    case DD:                                                                                                                                            \
+        hipLaunchKernelGGL((join_mfma_kernel<DD, KINDA>), dim3(blocks), dim3(256), 0, s, (const u32x4j *)Xh, rowMeta, qm, cid, T, tileA0, dFirst, n_ab, Kc, rho, \
+                           dTau, dCand, cap, dCtr);                                                                                                     \
+        break
+    switch (d) {
+        ZH_JN_CASE(256);
+        ZH_JN_CASE(384);
+        ZH_JN_CASE(512);
+        ZH_JN_CASE(768);
+        ZH_JN_CASE(1024);
+    default: return hipErrorInvalidValue;
+    }
+#undef ZH_JN_CASE
+    return hipGetLastError();
+}
+
+hipError_t zh_launch_join_mfma(uint32_t d, int metric, int mode, const void *dXh, const float2 *dRowMeta, const float4 *dQm, const uint32_t *dCid,
+                               uint64_t n_rows, uint64_t tileA0, const uint32_t *dFirst, uint32_t n_ab, uint32_t blocks, float Kc, float rho,
+                               const uint32_t *dTau, uint64_t *dCand, uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s) {
+    const uint64_t T = (n_rows + 15) / 16;
+    if (!blocks || !n_ab) return hipSuccess;
+    if (tileA0 % 4 || tileA0 >= T) return hipErrorInvalidValue;
+    if (metric != ZH_COSINE) return launch_join_mfma_kinda<0>(d, dXh, dRowMeta, dQm, dCid, T, tileA0, dFirst, n_ab, blocks, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
+    if (mode == ZH_COSINE_PARITY)
+        return launch_join_mfma_kinda<2>(d, dXh, dRowMeta, dQm, dCid, T, tileA0, dFirst, n_ab, blocks, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
+    return launch_join_mfma_kinda<1>(d, dXh, dRowMeta, dQm, dCid, T, tileA0, dFirst, n_ab, blocks, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
+}
+
+// The candidates' canonical keys, in the manner of range_survivors_kernel -- and their judgement.  A candidate is a << 32 | b, a < b: the key is that
+// of STORED row b against the QUERY row a, both read from the f32 table; the cosine's query norm is qnorm_kernel's sum (the canonical one) of row a.
+// A wave takes 64 candidates at a time: pair j's sums wait in lane j, so that key_of, the comparison and the pool's atomic run once for all 64.
+template <int D, int KIND>
+__global__ __launch_bounds__(256) void join_survivors_kernel(const float *__restrict__ X, int metric, int param, const uint64_t *__restrict__ cand,
+                                                             const unsigned long long *__restrict__ candCtr, uint64_t cand_cap, uint64_t max_key,
+                                                             unsigned long long *__restrict__ ctr, uint64_t *__restrict__ pv, uint64_t *__restrict__ pk,
+                                                             uint64_t cap) {
+    constexpr int NV = RowVec<D>::NV;
+    const uint64_t n = *candCtr;
+    if (n > cand_cap) return;  // (the pool ran over: the panel is answered by path 1)
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
+    for (uint64_t g = wave * 64; g < n; g += n_waves * 64) {
+        const uint32_t m = n - g < 64 ? (uint32_t)(n - g) : 64u;
+        const uint64_t mine = lane < m ? cand[g + lane] : 0ull;
+        const uint32_t my_b = (uint32_t)mine, my_a = (uint32_t)(mine >> 32);
+        float m0 = 0.f, m1 = 0.f, mq = 0.f;
+        for (uint32_t j = 0; j < m; j++) {
+            const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)my_b, (int)j), qrow = (uint32_t)__builtin_amdgcn_readlane((int)my_a, (int)j);
+            float4 v[NV], q[NV];
+            load_row<D>(X + (size_t)row * D, lane, v);
+            load_row<D>(X + (size_t)qrow * D, lane, q);
+            float s0 = 0.f, s1 = 0.f, qq = 0.f;
+            row_pair_sums<D, KIND>(v, q, lane, param, s0, s1);
+            if (KIND == K_COS) {
+                float4 c = make_float4(0.f, 0.f, 0.f, 0.f), cq = c;
+#pragma unroll
+                for (int jj = 0; jj < NV; jj++) {
+                    const bool act = (jj < RowVec<D>::NJ) || (lane < (uint32_t)RowVec<D>::REM4);
+                    if (act) { sq4(v[jj], c); sq4(q[jj], cq); }
+                }
+                s1 = wave_sum_canonical((c.x + c.y) + (c.z + c.w));
+                qq = wave_sum_canonical((cq.x + cq.y) + (cq.z + cq.w));
+            }
+            if (lane == j) { m0 = s0; m1 = s1; mq = qq; }
+        }
+        uint64_t key = 0;
+        bool hit = false;
+        if (lane < m) {
+            key = key_of(metric, param, m0, m1, mq);
+            hit = key <= max_key;
+        }
+        const uint64_t hm = __ballot(hit);
+        if (hm) {  // (wave-uniform)
+            const unsigned long long slot = join_wave_slots(ctr, hm, lane);
+            if (hit && slot < cap) { pv[slot] = mine; pk[slot] = key; }
+        }
+    }
+}
+
+template <int D>
+static void launch_join_surv_d(const float *dX, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr, uint64_t cand_cap,
+                               uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, uint32_t blocks,
+                               hipStream_t s) {
+    if (metric == ZH_COSINE)
+        hipLaunchKernelGGL((join_survivors_kernel<D, K_COS>), dim3(blocks), dim3(256), 0, s, dX, metric, mode, dCand, dCandCtr, cand_cap, max_key, dHitCtr, dPoolV,
+                           dPoolK, pool_cap);
+    else
+        hipLaunchKernelGGL((join_survivors_kernel<D, K_L2>), dim3(blocks), dim3(256), 0, s, dX, metric, mode, dCand, dCandCtr, cand_cap, max_key, dHitCtr, dPoolV,
+                           dPoolK, pool_cap);
+}
+
+hipError_t zh_launch_join_survivors(const float *dX, uint32_t d, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr,
+                                    uint64_t cand_cap, uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap,
+                                    hipStream_t s) {
+    // the candidate count is known on the device only: enough waves for 64 candidates each up to the pool's size, at most 4096 of them
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (cand_cap + 255) / 256));
+#define ZH_JN_SURV(DD) case DD: launch_join_surv_d<DD>(dX, metric, mode, dCand, dCandCtr, cand_cap, max_key, dHitCtr, dPoolV, dPoolK, pool_cap, blocks, s); break
+    switch (d) {
+        ZH_JN_SURV(256);
+        ZH_JN_SURV(384);
+        ZH_JN_SURV(512);
+        ZH_JN_SURV(768);
+        ZH_JN_SURV(1024);
+    default: return hipErrorInvalidValue;
+    }
+#undef ZH_JN_SURV
+    return hipGetLastError();
+}
+
+// a panel whose candidates ran over: its live rows (positions [p_begin, p_end) of the copy, any order) as path 1's query rows; *dCount += their number
+__global__ __launch_bounds__(256) void join_panel_rows_kernel(const uint32_t *__restrict__ cid, uint64_t p_begin, uint64_t p_end, uint32_t *__restrict__ list,
+                                                              unsigned long long *__restrict__ count) {
+    const uint64_t p = p_begin + (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t id = p < p_end ? cid[p] : 0xFFFFFFFFu;
+    const bool on = id != 0xFFFFFFFFu;
+    const uint64_t m = __ballot(on);
+    if (!m) return;  // (wave-uniform)
+    const unsigned long long slot = join_wave_slots(count, m, lane);
+    if (on) list[slot] = id;
+}
+
+hipError_t zh_launch_join_panel_rows(const uint32_t *dCid, uint64_t p_begin, uint64_t p_end, uint32_t *dList, unsigned long long *dCount, hipStream_t s) {
+    if (p_begin >= p_end) return hipSuccess;
+    hipLaunchKernelGGL(join_panel_rows_kernel, dim3((uint32_t)((p_end - p_begin + 255) / 256)), dim3(256), 0, s, dCid, p_begin, p_end, dList, dCount);
+    return hipGetLastError();
+}
+
+// ---- both paths: the order.  Three stable LSD sorts of the pool: by the b bits of v, by the key, by the a bits of v -> (a, key, b) ----
+__global__ __launch_bounds__(256) void join_emit_kernel(const uint64_t *__restrict__ v, const uint64_t *__restrict__ k, uint64_t n, uint64_t id_base,
+                                                        uint64_t *__restrict__ out_a, uint64_t *__restrict__ out_b, uint64_t *__restrict__ keys) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { out_a[i] = id_base + (v[i] >> 32); out_b[i] = id_base + (v[i] & 0xFFFFFFFFull); keys[i] = k[i]; }
+}
+
+static int join_bits(uint64_t values) {  // bits that hold 0 .. values - 1
+    int b = 1;
+    while (b < 32 && (1ull << b) < values) b++;
+    return b;
+}
+
+// dTmp == nullptr: *tmp_bytes = what the three sorts of n entries need at most
+hipError_t zh_launch_join_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows, void *dTmp, size_t *tmp_bytes, uint64_t id_base, uint64_t *dOutA,
+                               uint64_t *dOutB, uint64_t *dOutKeys, hipStream_t s) {
+    hipcub::DoubleBuffer<uint64_t> v(dV[0], dV[1]), k(dK[0], dK[1]);
+    const int rb = join_bits(n_rows);
+    hipError_t e;
+    if (!dTmp) {
+        size_t a = 0, b = 0, c = 0;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, a, v, k, n, 0, rb, s)) != hipSuccess) return e;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, b, k, v, n, 0, 64, s)) != hipSuccess) return e;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, c, v, k, n, 32, 32 + rb, s)) != hipSuccess) return e;
+        *tmp_bytes = std::max<size_t>(std::max(a, b), std::max<size_t>(c, 1));
+        return hipSuccess;
+    }
+    if (!n) return hipSuccess;
+    size_t bytes = *tmp_bytes;
+    if ((e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, v, k, n, 0, rb, s)) != hipSuccess) return e;
+    bytes = *tmp_bytes;
+    if ((e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, k, v, n, 0, 64, s)) != hipSuccess) return e;
+    bytes = *tmp_bytes;
+    if ((e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, v, k, n, 32, 32 + rb, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(join_emit_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const uint64_t *)v.Current(), (const uint64_t *)k.Current(), n,
+                       id_base, dOutA, dOutB, dOutKeys);
+    return hipGetLastError();
+}

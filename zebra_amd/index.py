@@ -472,6 +472,66 @@ class LSHIndex:
         check(lib().zh_search_range_info(self._h, C.byref(info)))
         return info.as_dict()
 
+    def _join_key(self, radius, metric, max_key):
+        if metric is None:
+            raise ValueError("the self-join needs a metric")
+        if (radius is None) == (max_key is None):
+            raise ValueError("give either a radius or max_key")
+        mk = np.asarray(radius_key(metric, radius) if max_key is None else max_key, dtype=np.uint64)
+        if mk.size != 1:
+            raise ValueError("the self-join takes one threshold for the whole call, got %d" % mk.size)
+        return int(mk.reshape(-1)[0])
+
+    def self_join(self, radius=None, metric=None, max_key=None, capacity=None):
+        """EXACT self-join: every pair of distinct live stored rows (a, b), a < b, whose key is <= ONE threshold -- `radius` (turned into a
+        key by radius_key) or `max_key` (a u64 key; 2^64-1 = every pair).  The key of a pair is search_range_batch's for stored row b against
+        a query equal to row a.  -> (a u64, b u64, keys u64), ascending by (a, key, b).  One call with a guessed capacity; when the pairs
+        exceed it, one more with the exact total the first call reported."""
+        mk = self._join_key(radius, metric, max_key)
+        cap = int(capacity) if capacity is not None else max(1024, 16 * len(self))
+        total = C.c_uint64(0)
+        for attempt in range(2):
+            a = np.empty(max(cap, 1), np.uint64)
+            b = np.empty(max(cap, 1), np.uint64)
+            keys = np.empty(max(cap, 1), np.uint64)
+            rc = lib().zh_self_join(self._h, mk, metric.metric, metric.mode, cap, _p(a), _p(b), _p(keys), C.byref(total))
+            if rc == _ffi.ZH_ELIMIT and attempt == 0 and total.value > cap:
+                cap = int(total.value)
+                continue
+            check(rc)
+            break
+        n = int(total.value)
+        return a[:n], b[:n], keys[:n]
+
+    def self_join_count(self, radius=None, metric=None, max_key=None):
+        """how many pairs self_join would return (a call with capacity 0: nothing is ordered or written)"""
+        mk = self._join_key(radius, metric, max_key)
+        total = C.c_uint64(0)
+        rc = lib().zh_self_join(self._h, mk, metric.metric, metric.mode, 0, None, None, None, C.byref(total))
+        if rc != _ffi.ZH_ELIMIT:
+            check(rc)
+        return int(total.value)
+
+    def self_join_device(self, max_key, metric, capacity, d_a_ptr, d_b_ptr, d_keys_ptr, d_total_ptr, stream=None):
+        """self_join with a, b, keys (`capacity` each) and the total (one u64) in device memory (raw pointers, e.g. torch .data_ptr()).
+        Pairs beyond the capacity raise ZhError with code ZH_ELIMIT; the total is exact even then."""
+        check(lib().zh_self_join_device(self._h, int(max_key), metric.metric, metric.mode, capacity, d_a_ptr, d_b_ptr, d_keys_ptr, d_total_ptr, stream))
+
+    def join_info(self):
+        """what the most recent self-join on this index did (zh_self_join_info): rows_live, pairs, path, redone, candidates, launches, tiles"""
+        info = _ffi.JoinInfo()
+        check(lib().zh_self_join_info(self._h, C.byref(info)))
+        return info.as_dict()
+
+    def deduplicate_within(self, radius, metric):
+        """near-duplicate removal: rows are taken in ascending id, and row b is removed exactly when some KEPT row a < b forms a joined pair
+        with it (self_join at `radius`).  Decided on the host from the sorted pair list, then passed to remove -> the removed ids, ascending."""
+        a, b, _ = self.self_join(radius, metric)
+        removed = dedup_rule(a, b)
+        if removed.size:
+            self.remove(removed)
+        return removed
+
     def debug_keep_raw(self, on=True):
         """tests: half-width batches keep a copy of the scan's raw pairs (zh_debug_keep_raw)"""
         check(lib().zh_debug_keep_raw(self._h, 1 if on else 0))
@@ -683,6 +743,16 @@ def trim_device_memory():
     check(lib().zh_trim_device_memory())
 
 
+def dedup_rule(a, b):
+    """deduplicate_within's rule on a pair list sorted by a (self_join's order): b is removed exactly when a kept a < b is paired with it.
+    Every pair has a < b, so when the pairs of a are reached, whether a is kept is already final -> the removed ids (u64), ascending."""
+    removed = set()
+    for x, y in zip(np.asarray(a).tolist(), np.asarray(b).tolist()):
+        if x not in removed:
+            removed.add(y)
+    return np.array(sorted(removed), np.uint64)
+
+
 class Database:
     """Database<N, Met, Mod> restricted to the two calls on the hot path: insert_records
     (core.rs:245-254) and query_vectors (core.rs:290-313).  Documents are kept in memory (the lz4
@@ -749,3 +819,22 @@ class Database:
             return {}
         offsets, ids, _ = self.index.search_range_batch(vectors, radius, self.metric)
         return {b: {int(i): self._documents.get(int(i)) for i in ids[int(offsets[b]):int(offsets[b + 1])]} for b in range(offsets.size - 1)}
+
+    def near_duplicates(self, radius):
+        """every pair of records within `radius` of each other (LSHIndex.self_join: exact) -> [(document_a, document_b, distance)], in
+        ascending (id a, key, id b) order.  The distance is the number the key holds (for the parity cosine key: the similarity)."""
+        a, b, keys = self.index.self_join(radius, self.metric)
+        if self.metric.metric in _F64_KEYED:
+            dist = keys.view(np.float64)
+        elif self.metric.metric == _ffi.HAMMING:
+            dist = keys.astype(np.float64)
+        else:
+            dist = keys.astype(np.uint32).view(np.float32).astype(np.float64)
+        return [(self._documents.get(x), self._documents.get(y), float(v)) for x, y, v in zip(a.tolist(), b.tolist(), dist.tolist())]
+
+    def deduplicate_within(self, radius):
+        """LSHIndex.deduplicate_within, then the removed ids' documents go too -> the removed ids"""
+        removed = self.index.deduplicate_within(radius, self.metric)
+        for i in removed.tolist():
+            self._documents.pop(i, None)
+        return removed

@@ -322,6 +322,28 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_self_join_info(h_.get(), &info));
         return info;
     }
+    // the exact k-NN graph of the slab of stored rows [first_row, first_row + n) (zh_knn_graph): element i = the k nearest OTHER live rows of stored
+    // row first_row + i by (key, id), the key that of the neighbour against a query equal to the row; empty for a removed row.  k <= ZH_MAX_TOPK - 1.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> knn_graph(std::size_t k, const Met &metric, std::uint64_t first_row, std::uint64_t n) const {
+        std::vector<Id> ids(n * k + 1);
+        std::vector<DistanceUnit> keys(n * k + 1);
+        std::vector<std::uint32_t> counts(n + 1);
+        check(zh_knn_graph(h_.get(), first_row, n, k, Met::metric, metric.mode(), ids.data(), keys.data(), counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(n);
+        for (std::uint64_t i = 0; i < n; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * k + j], keys[i * k + j]);
+        return out;
+    }
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> knn_graph(std::size_t k, const Met &metric) const {
+        return knn_graph(k, metric, 0, zh_index_stored_rows(h_.get()));
+    }
+    zh_knn_info knn_info() const {
+        zh_knn_info info{};
+        check(zh_knn_graph_info(h_.get(), &info));
+        return info;
+    }
     zh_index *handle() const { return h_.get(); }
 
   private:

@@ -28,6 +28,7 @@
  *   zh_search_exact_filtered_batch[_device] (new) the exact top-k among the live rows a caller's bitmap allows
  *   zh_search_range_batch[_device]       (new) every live row whose key is at or below a per-query threshold key, as a CSR
  *   zh_self_join[_device]                (new) every pair of live rows whose key is at or below one threshold key, each pair once
+ *   zh_knn_graph[_device]                (new) every live row's exact k nearest OTHER live rows, slab by slab
  *   zh_index_save / zh_index_load        (new) a snapshot of an index in ONE file of this library's own format (the reference persists through
  *                                        fjall, lsh.rs:62-120, whose files are not read here): rows, removals, forest and the planes' sample rows
  *
@@ -490,6 +491,50 @@ typedef struct zh_join_info {  /* the most recent zh_self_join* call on this ind
     uint64_t tiles;       /* path 2: 16 x 16 tile products issued, from the launch geometry (T (T + 1) / 2 for T tiles: nothing below the diagonal) */
 } zh_join_info;
 ZH_API int zh_self_join_info(const zh_index *idx, zh_join_info *out);
+
+/* Exact k-NN GRAPH (new; the reference has no such call): for every live stored row a of the slab [first_row, first_row + n) its exact top-k by
+ * (key, id) over every live row EXCEPT a itself.  It replaces the loop "zh_index_read_rows back to the host, zh_search_exact_batch with k + 1,
+ * 1024 rows at a time, find and drop self on the host": that loop converts every batch of rows to fp16 again although the index's fp16 copy holds
+ * them, and "drop the first result" is wrong when a row has bit-identical duplicates with smaller ids, and wrong again under the parity cosine
+ * key, where self has the LARGEST key.
+ * The key of (a, b) is the key zh_distance_batch gives for stored row b against a query equal to the f32 values of row a (zh_self_join's
+ * orientation); the line of a equals zh_search_exact_filtered_batch(rows[a], k, allowed = every row but a).  Only the row with the same row number
+ * is excluded: bit-identical duplicates are ordinary neighbours, ties order by id.
+ * Output line i belongs to STORED row first_row + i, 0 <= i < n: out_ids / out_keys are [n][k] u64, out_counts [n] u32; ids = id_base + row;
+ * out_counts[i] = min(k, live rows - 1); entries past the count are UINT64_MAX in both arrays; a removed row's line has count 0 and is filled the
+ * same way.  The interface is a slab on purpose (10M rows x k = 32 are 5 GB of output): call it slab after slab.  first_row + n > stored rows is
+ * ZH_EINVAL; n = 0 is ZH_OK; k = 0 zeroes the counts and touches nothing else; k > ZH_MAX_TOPK - 1 is ZH_ELIMIT (one slot is kept so that path 1
+ * may ask the exact search for k + 1).  A NULL index, NULL outputs for a non-empty request, an unknown metric and the k limit are refused before
+ * any device is touched.  All 13 metric / mode / power combinations and every dimension are served.  Locking and thread-safety as for
+ * zh_search_exact_batch_device; zh_stats_t, zh_exact_info, zh_filtered_info, zh_range_info, zh_join_info and the index's cached live-row views are
+ * left alone: zh_knn_graph_info describes the most recent call.
+ * The work goes panel by panel (up to 1024 live rows of the slab, ascending).  Two paths, same answers.  Path 1 gathers the panel as queries,
+ * asks the exact search's path 1 for k + 1 and writes each line's first k entries that are not the line's own id.  Path 2 (ZH_L2SQ, ZH_L2,
+ * ZH_COSINE at dim 256 / 384 / 512 / 768 / 1024, at least max(k + 1, 8192) live rows, the fp16 row copy present) gathers the panel's tiles out of
+ * the fp16 copy and multiplies them by every tile of the copy on the matrix cores for an interval per pair, with a falling bound per line as in
+ * the exact search; only the survivors get the canonical key.  A panel whose candidate list runs over is answered by path 1 (`redone`).
+ * ZH_KNN_PATH=1 in the environment (read per call) keeps every panel on path 1; ZH_KNN_LIST_CAP=n (read per call; tests) lowers the list capacity.
+ * Device scratch is allocated per call and released before it returns: on path 2 20 bytes per stored row (24 under a scan order that is not id
+ * order) and per panel of P <= 1024 lines P (6 dim + 12) bytes of rows and 36 P (16384 + 8 k) bytes of lists; on path 1 the panel's rows and up
+ * to 1 GiB of key scratch; both 16 P (k + 1) bytes of panel answer; for the host call 16 k + 4 bytes per line of a sub-slab of 65536 lines. */
+ZH_API int zh_knn_graph(zh_index *idx, uint64_t first_row, uint64_t n, size_t k, int metric, int cosine_mode, uint64_t *out_ids, uint64_t *out_keys,
+                        uint32_t *out_counts);
+/* The same with every output in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return.  It replaces the same
+ * loop run on the device: zh_search_exact_batch_device over the index's own rows with k + 1 and a kernel of the caller's that drops self. */
+ZH_API int zh_knn_graph_device(zh_index *idx, uint64_t first_row, uint64_t n, size_t k, int metric, int cosine_mode, uint64_t *d_out_ids,
+                               uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream);
+typedef struct zh_knn_info {  /* the most recent zh_knn_graph* call on this index */
+    uint64_t rows_live;   /* live rows of the index */
+    uint64_t lines;       /* live rows answered (the slab's live rows) */
+    uint32_t k;
+    uint32_t path;        /* 1: the exact search's path 1 with k + 1; 2: matrix-core intervals, canonical keys for the survivors only */
+    uint32_t redone;      /* path 2: panels whose list ran over and that path 1 answered again */
+    uint64_t survivors;   /* path 2: pairs that got the canonical key, over the panels path 2 completed */
+    uint64_t launches;    /* launches of the scan (row chunks on path 1, column chunks on path 2) */
+    uint64_t tiles;       /* path 2: 16 x 16 tile products issued, from the launch geometry (panel tiles x column tiles: the full rectangle) */
+} zh_knn_info;
+/* What the host loop that zh_knn_graph replaces could only count by hand. */
+ZH_API int zh_knn_graph_info(const zh_index *idx, zh_knn_info *out);
 
 /* Pipelined form of zh_search_batch_device (new; the reference has one blocking search per query): a context
  * is one in-flight batch with its own scratch.  The context calls do NOT take the index's internal lock (the blocking

@@ -134,6 +134,19 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_knn_info {
+        pub rows_live: u64,
+        pub lines: u64,
+        pub k: u32,
+        pub path: u32,
+        pub redone: u32,
+        pub survivors: u64,
+        pub launches: u64,
+        pub tiles: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_filtered_info {
         pub batch: u64,
         pub rows_live: u64,
@@ -238,6 +251,11 @@ pub mod ffi {
         pub fn zh_self_join_device(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, d_out_a: *mut u64,
                                    d_out_b: *mut u64, d_out_keys: *mut u64, d_out_total: *mut u64, stream: *mut c_void) -> c_int;
         pub fn zh_self_join_info(idx: *const zh_index, out: *mut zh_join_info) -> c_int;
+        pub fn zh_knn_graph(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int, out_ids: *mut u64,
+                            out_keys: *mut u64, out_counts: *mut u32) -> c_int;
+        pub fn zh_knn_graph_device(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64,
+                                   d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_knn_graph_info(idx: *const zh_index, out: *mut zh_knn_info) -> c_int;
         pub fn zh_search_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
                                       d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_distance_pair(metric: c_int, cosine_mode: c_int, a: *const f32, b: *const f32, dim: usize, out_key: *mut u64,
@@ -595,6 +613,40 @@ impl<const N: usize> LSHIndex<N> {
             })?;
         }
         Ok((0..total as usize).map(|i| (t.of_row[a[i] as usize], t.of_row[b[i] as usize], keys[i])).collect())
+    }
+
+    /// (new) the exact k-NN graph (zh_knn_graph): per stored vector, in row order, its `k` nearest OTHER live vectors by (key, row), the key that
+    /// of the neighbour against a query equal to the vector; a removed vector's list is empty.  Fetched in slabs of 65536 rows.
+    pub fn knn_graph<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        k: usize,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<(Uuid, Vec<(Uuid, DistanceUnit)>)>> {
+        const SLAB: u64 = 65536;
+        let t = self.ids.read().unwrap();
+        let stored = t.of_row.len() as u64;
+        let mut out = Vec::with_capacity(stored as usize);
+        let (mut ids, mut keys, mut counts) = (vec![0u64; SLAB as usize * k + 1], vec![0u64; SLAB as usize * k + 1], vec![0u32; SLAB as usize]);
+        let mut first = 0u64;
+        while first < stored {
+            let n = SLAB.min(stored - first);
+            check(unsafe {
+                ffi::zh_knn_graph(self.hip.0, first, n, k, Met::METRIC, metric.param(), ids.as_mut_ptr(), keys.as_mut_ptr(), counts.as_mut_ptr())
+            })?;
+            for i in 0..n as usize {
+                let line = (0..counts[i] as usize).map(|j| (t.of_row[ids[i * k + j] as usize], keys[i * k + j])).collect();
+                out.push((t.of_row[first as usize + i], line));
+            }
+            first += n;
+        }
+        Ok(out)
+    }
+
+    /// what the most recent k-NN graph call did (zh_knn_graph_info)
+    pub fn knn_info(&self) -> anyhow::Result<ffi::zh_knn_info> {
+        let mut info = ffi::zh_knn_info::default();
+        check(unsafe { ffi::zh_knn_graph_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// what the most recent self-join did (zh_self_join_info)

@@ -112,6 +112,14 @@ class JoinInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KnnInfo(C.Structure):
+    _fields_ = [("rows_live", C.c_uint64), ("lines", C.c_uint64), ("k", C.c_uint32), ("path", C.c_uint32), ("redone", C.c_uint32),
+                ("survivors", C.c_uint64), ("launches", C.c_uint64), ("tiles", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CompactInfo(C.Structure):
     _fields_ = [("rows_before", C.c_uint64), ("rows_after", C.c_uint64), ("rows_moved", C.c_uint64), ("bytes_moved", C.c_uint64),
                 ("scratch_bytes", C.c_uint64), ("capacity_rows", C.c_uint64), ("copy_bytes_released", C.c_uint64), ("ms", C.c_double)]
@@ -181,6 +189,9 @@ SYMBOLS = [
     ("zh_self_join", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
     ("zh_self_join_device", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("zh_self_join_info", _i, [_vp, _vp]),
+    ("zh_knn_graph", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
+    ("zh_knn_graph_device", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    ("zh_knn_graph_info", _i, [_vp, _vp]),
     ("zh_search_ctx_create", _i, [_vp, _vp]),
     ("zh_search_ctx_destroy", None, [_vp]),
     ("zh_search_begin", _i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),

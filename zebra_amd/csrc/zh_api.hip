@@ -272,6 +272,10 @@ struct zh_index {
     // and the outputs staged for the host call
     DevBuf jn_ctr, jn_maxk, jn_tau, jn_pv0, jn_pv1, jn_pk0, jn_pk1, jn_qm, jn_cid, jn_first, jn_cand, jn_rows, jn_tmp, jn_oa, jn_ob, jn_okeys;
     zh_join_info jn_info{};  // (stats_mu)
+    // the k-NN graph's per-call scratch (all released before the call returns): path 2's per-position views and row -> position map, one panel's
+    // tiles, rowMeta and row numbers, the lists' bases, the panel's answer, and the outputs staged for the host call
+    DevBuf kn_qm, kn_cid, kn_pos, kn_A, kn_pmeta, kn_pid, kn_cbase, kn_pids, kn_pkeys, kn_pcounts, kn_oids, kn_okeys, kn_ocounts;
+    zh_knn_info kn_info{};  // (stats_mu)
 
     bool broken = false;  // an incremental add failed half way: trees are stale until zh_index_build
     bool rows_torn = false;  // ... or a compaction failed after rows had begun to move (set with broken): the TABLE is inconsistent until zh_index_clear
@@ -4344,6 +4348,243 @@ extern "C" int zh_self_join_info(const zh_index *ix, zh_join_info *out) {
     zh_index *m = const_cast<zh_index *>(ix);
     std::lock_guard<std::mutex> lk(m->stats_mu);
     *out = m->jn_info;
+    return ZH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// exact k-NN graph (zh_knn.hip + the exact search's two paths): each live row's k nearest OTHER live rows, slab by slab.  DESIGN.md s16
+// ------------------------------------------------------------------------------------------------
+#define ZH_KNN_HOST_SLAB 65536u  // lines the host call stages at a time
+
+static void knn_release_scratch(zh_index *ix) {
+    exact_release_scratch(ix);
+    DevBuf *bs[] = {&ix->kn_qm, &ix->kn_cid, &ix->kn_pos, &ix->kn_A, &ix->kn_pmeta, &ix->kn_pid, &ix->kn_cbase, &ix->kn_pids, &ix->kn_pkeys, &ix->kn_pcounts,
+                    &ix->kn_oids, &ix->kn_okeys, &ix->kn_ocounts};
+    for (DevBuf *b : bs) b->release();
+}
+struct KnnScratchGuard {
+    zh_index *ix;
+    ~KnnScratchGuard() { knn_release_scratch(ix); }
+};
+
+struct KnnRun {  // what a call settles once, before its slabs
+    bool path2 = false;
+    const void *Xh = nullptr;
+    const float2 *rowMeta = nullptr;
+    const uint32_t *pos = nullptr;  // row -> position under a row order, else null
+    float rho = 0.f, Kc = 0.f;
+    uint32_t cap = 0;               // list slots per line
+    uint64_t rank_row = 0, rank = 0;  // live rows before stored row rank_row (the slabs of a call ascend)
+};
+
+// The gate of path 2 and its per-call views: the copy's rows as approx_interval's queries (zh_launch_join_prep), the row -> position map under a
+// row order, the lists' bases.
+static int knn_setup(zh_index *ix, uint32_t k, int metric, int mode, hipStream_t s, KnnRun *run) {
+    const uint32_t d = ix->opt.dim;
+    const char *env_p = getenv("ZH_KNN_PATH");
+    if (env_p && atoi(env_p) == 1) return ZH_OK;
+    if (!zh_exact_mfma_supported(d, metric) || ix->ex_n_live < std::max<uint64_t>((uint64_t)k + 1, 8192)) return ZH_OK;
+    int rc;
+    const uint32_t *perm;
+    uint64_t perm_rows;
+    {
+        std::lock_guard<std::mutex> lb(ix->blk_mu);
+        bool ok = false;
+        if ((rc = ensure_row_half(ix, &ok))) return rc;
+        if (!ok || !ix->row_half.p) return ZH_OK;  // no copy (no room, or the per-row scales alone): path 1
+        run->Xh = ix->row_half.p; run->rowMeta = ix->row_meta.as<float2>(); run->rho = ix->row_rho;
+        perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr; perm_rows = ix->perm_rows;
+    }
+    const uint64_t n = ix->n_rows, n_pos = (n + 15) / 16 * 16;
+    run->cap = 16384 + 8 * k;
+    const char *env_c = getenv("ZH_KNN_LIST_CAP");
+    if (env_c && atoi(env_c) > 0) run->cap = std::min<uint32_t>(run->cap, (uint32_t)atoi(env_c));
+    if ((rc = ix->kn_qm.ensure(n_pos * 16)) || (rc = ix->kn_cid.ensure(n_pos * 4)) || (rc = ix->kn_cbase.ensure((ZH_KNN_PANEL_ROWS + 1) * 8))) return rc;
+    HIPCHK(zh_launch_join_prep(run->rowMeta, perm, perm_rows, ix->ex_bits.as<uint32_t>(), n, run->rho, ix->kn_qm.as<float4>(), ix->kn_cid.as<uint32_t>(), s));
+    if (perm_rows) {
+        if ((rc = ix->kn_pos.ensure(n * 4))) return rc;
+        HIPCHK(zh_launch_knn_rowpos(ix->kn_cid.as<uint32_t>(), n_pos, ix->kn_pos.as<uint32_t>(), s));
+        run->pos = ix->kn_pos.as<uint32_t>();
+    }
+    std::vector<uint64_t> cb(ZH_KNN_PANEL_ROWS + 1);
+    for (uint32_t b = 0; b <= ZH_KNN_PANEL_ROWS; b++) cb[b] = (uint64_t)b * run->cap;
+    HIPCHK(hipMemcpyAsync(ix->kn_cbase.p, cb.data(), cb.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));  // (cb is this frame's)
+    run->Kc = zh_approx_bound(metric, d, 1);
+    run->path2 = true;
+    return ZH_OK;
+}
+
+// Path 2 of one panel (the B live rows dRows, ascending): its answer [B][k] into kn_pids / kn_pkeys / kn_pcounts.  *overflowed: a line's list ran
+// over and the answer is not valid (the caller answers the panel by path 1).
+static int knn_panel2(zh_index *ix, const KnnRun &run, const uint32_t *dRows, uint32_t B, uint32_t k, int metric, int mode, hipStream_t s, bool *overflowed,
+                      zh_knn_info *inf) {
+    const uint32_t d = ix->opt.dim, cap = run.cap, PT = (B + 15) / 16;
+    int rc;
+    if ((rc = ix->kn_A.ensure((size_t)PT * 16 * d * 2)) || (rc = ix->kn_pmeta.ensure((size_t)PT * 16 * 8)) || (rc = ix->kn_pid.ensure((size_t)PT * 16 * 4)) ||
+        (rc = ix->ex_Q.ensure((size_t)B * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_tau.ensure((size_t)B * 4)) ||
+        (rc = ix->ex_cnt.ensure((size_t)B * 4)) || (rc = ix->ex_lid.ensure((size_t)B * cap * 4)) || (rc = ix->ex_llo.ensure((size_t)B * cap * 4)) ||
+        (rc = ix->ex_lhi.ensure((size_t)B * cap * 4)) || (rc = ix->ex_scr.ensure((size_t)B * cap * 12)) || (rc = ix->ex_over.ensure(8)) ||
+        (rc = ix->ex_ckeys.ensure((size_t)B * cap * 8)) || (rc = ix->ex_cids.ensure((size_t)B * cap * 4)))
+        return rc;
+    ZhExact2 e{run.Xh, run.rowMeta, nullptr, 0, ix->ex_bits.as<uint32_t>(), nullptr, nullptr, B, run.Kc, run.rho,
+               ix->ex_tau.as<uint32_t>(), ix->ex_cnt.as<uint32_t>(), ix->ex_lid.as<uint32_t>(), ix->ex_llo.as<uint32_t>(), ix->ex_lhi.as<uint32_t>(), cap,
+               ix->ex_over.as<uint32_t>()};
+    HIPCHK(zh_launch_knn_panel(d, run.Xh, run.rowMeta, run.pos, dRows, B, ix->kn_A.p, ix->kn_pmeta.as<float2>(), ix->kn_pid.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dRows, B, ix->ex_Q.as<float>(), s));
+    HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), B, d, ix->ex_QQ.as<float>(), s));
+    HIPCHK(hipMemsetAsync(e.tau, 0xFF, (size_t)B * 4, s));
+    HIPCHK(hipMemsetAsync(e.cnt, 0, (size_t)B * 4, s));
+    HIPCHK(hipMemsetAsync(e.over, 0, 8, s));
+    const uint64_t n = ix->n_rows;  // positions of the copy; removed rows are masked by the id word
+    uint64_t chunk = (std::max<uint64_t>((uint64_t)k + 1, 4096) + 15) / 16 * 16;
+    for (uint64_t p0 = 0; p0 < n; p0 += chunk, chunk *= ZH_EXACT_GROWTH) {
+        const uint64_t p1 = std::min(n, p0 + chunk);
+        HIPCHK(zh_launch_knn_mfma(d, metric, mode, e, ix->kn_qm.as<float4>(), ix->kn_cid.as<uint32_t>(), p0, p1, ix->kn_A.p, ix->kn_pmeta.as<float2>(),
+                                  ix->kn_pid.as<uint32_t>(), s));
+        HIPCHK(zh_launch_exact_prune(e, k, ix->ex_scr.as<uint32_t>(), s));
+        inf->launches++;
+        inf->tiles += (uint64_t)PT * ((p1 + 15) / 16 - p0 / 16);
+    }
+    HIPCHK(zh_launch_exact_survivor_keys(ix->X.as<float>(), d, ix->ex_Q.as<float>(), ix->ex_QQ.as<float>(), metric, mode, e, ix->ex_ckeys.as<uint64_t>(),
+                                         ix->ex_cids.as<uint32_t>(), s));
+    HIPCHK(zh_launch_final(ix->kn_cbase.as<uint64_t>(), B, 1, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), ix->opt.id_base,
+                           ix->kn_pids.as<uint64_t>(), ix->kn_pkeys.as<uint64_t>(), ix->kn_pcounts.as<uint32_t>(), nullptr, s));
+    std::vector<uint32_t> h_cnt(B + 2);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), e.cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_cnt.data() + B, e.over, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *overflowed = h_cnt[B] != 0;
+    if (!*overflowed)
+        for (uint32_t b = 0; b < B; b++) inf->survivors += h_cnt[b];
+    return ZH_OK;
+}
+
+// One slab on device outputs (under mu, exclusive; exact_live_rows and knn_setup have run; k > 0, n > 0): every line filled as "no neighbours", then
+// panel after panel of the slab's live rows.
+static int knn_slab(zh_index *ix, KnnRun *run, uint64_t first_row, uint64_t n, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys,
+                    uint32_t *dCounts, hipStream_t s, zh_knn_info *inf) {
+    const uint32_t d = ix->opt.dim;
+    int rc;
+    HIPCHK(zh_launch_exact_empty((uint32_t)n, k, dIds, dKeys, dCounts, s));
+    auto live_before = [&](uint64_t row) {
+        if (row < run->rank_row) { run->rank_row = 0; run->rank = 0; }
+        for (; run->rank_row < row; run->rank_row++) run->rank += !(run->rank_row < ix->h_dead.size() && ix->h_dead[run->rank_row]);
+        return run->rank;
+    };
+    const uint64_t lo = live_before(first_row), hi = live_before(first_row + n);
+    inf->lines += hi - lo;
+    if ((rc = ix->kn_pids.ensure((size_t)ZH_KNN_PANEL_ROWS * (k + 1) * 8)) || (rc = ix->kn_pkeys.ensure((size_t)ZH_KNN_PANEL_ROWS * (k + 1) * 8)) ||
+        (rc = ix->kn_pcounts.ensure((size_t)ZH_KNN_PANEL_ROWS * 4)))
+        return rc;
+    for (uint64_t a0 = lo; a0 < hi; a0 += ZH_KNN_PANEL_ROWS) {
+        const uint32_t B = (uint32_t)std::min<uint64_t>(ZH_KNN_PANEL_ROWS, hi - a0);
+        const uint32_t *dRows = ix->ex_live.as<uint32_t>() + a0;
+        if (run->path2) {
+            bool overflowed = false;
+            if ((rc = knn_panel2(ix, *run, dRows, B, k, metric, mode, s, &overflowed, inf))) return rc;
+            if (!overflowed) {
+                HIPCHK(zh_launch_knn_emit(ix->kn_pids.as<uint64_t>(), ix->kn_pkeys.as<uint64_t>(), ix->kn_pcounts.as<uint32_t>(), k, dRows, B, ix->opt.id_base,
+                                          first_row, k, dIds, dKeys, dCounts, s));
+                continue;
+            }
+            inf->redone++;
+        }
+        // path 1: the panel as queries, k + 1 over the live list, self taken out of each line
+        if ((rc = ix->ex_Q.ensure((size_t)B * d * 4))) return rc;
+        HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dRows, B, ix->ex_Q.as<float>(), s));
+        if ((rc = exact_batch(ix, ix->ex_live.as<uint32_t>(), ix->ex_n_live, ix->ex_Q.as<float>(), B, k + 1, metric, mode, ix->kn_pids.as<uint64_t>(),
+                              ix->kn_pkeys.as<uint64_t>(), ix->kn_pcounts.as<uint32_t>(), s, &inf->launches)))
+            return rc;
+        HIPCHK(zh_launch_knn_emit(ix->kn_pids.as<uint64_t>(), ix->kn_pkeys.as<uint64_t>(), ix->kn_pcounts.as<uint32_t>(), k + 1, dRows, B, ix->opt.id_base,
+                                  first_row, k, dIds, dKeys, dCounts, s));
+    }
+    return ZH_OK;
+}
+
+static int knn_args(zh_index *ix, uint64_t n, size_t k, int metric, int mode, const void *ids, const void *keys, const void *counts, const char *who) {
+    if (!ix || (n && (!counts || (k && (!ids || !keys))))) return fail(ZH_EINVAL, "%s: null argument", who);
+    if (k > ZH_MAX_TOPK - 1) return fail(ZH_ELIMIT, "%s: k %zu > ZH_MAX_TOPK - 1 (%u)", who, k, ZH_MAX_TOPK - 1);
+    return check_metric(metric, mode);
+}
+
+static int knn_range(zh_index *ix, uint64_t first_row, uint64_t n, const char *who) {
+    if (first_row > ix->n_rows || n > ix->n_rows - first_row)
+        return fail(ZH_EINVAL, "%s: rows [%llu, %llu + %llu) pass the %llu stored rows", who, (unsigned long long)first_row, (unsigned long long)first_row,
+                    (unsigned long long)n, (unsigned long long)ix->n_rows);
+    return ZH_OK;
+}
+
+static void knn_record(zh_index *ix, uint32_t k, zh_knn_info inf) {
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    inf.k = k;
+    inf.rows_live = ix->ex_n_live;
+    ix->kn_info = inf;
+}
+
+extern "C" int zh_knn_graph_device(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys,
+                                   uint32_t *d_out_counts, void *stream) {
+    int rc = knn_args(ix, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_device");
+    if (rc) return rc;
+    if (n == 0) return ZH_OK;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph_device"))) return rc;
+    KnnScratchGuard guard{ix};
+    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    zh_knn_info inf{};
+    inf.path = 1;
+    if (k == 0) {
+        HIPCHK(hipMemsetAsync(d_out_counts, 0, n * 4, s));
+    } else {
+        KnnRun run;
+        if ((rc = knn_setup(ix, (uint32_t)k, metric, mode, s, &run))) return rc;
+        if (run.path2) inf.path = 2;
+        if ((rc = knn_slab(ix, &run, first_row, n, (uint32_t)k, metric, mode, d_out_ids, d_out_keys, d_out_counts, s, &inf))) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    knn_record(ix, (uint32_t)k, inf);
+    return ZH_OK;
+}
+
+extern "C" int zh_knn_graph(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys,
+                            uint32_t *out_counts) {
+    int rc = knn_args(ix, n, k, metric, mode, out_ids, out_keys, out_counts, "zh_knn_graph");
+    if (rc) return rc;
+    if (n == 0) return ZH_OK;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph"))) return rc;
+    KnnScratchGuard guard{ix};
+    const hipStream_t s = ix->stream;
+    zh_knn_info inf{};
+    inf.path = 1;
+    if (k == 0) {
+        memset(out_counts, 0, n * 4);
+    } else {
+        KnnRun run;
+        if ((rc = knn_setup(ix, (uint32_t)k, metric, mode, s, &run))) return rc;
+        if (run.path2) inf.path = 2;
+        const uint64_t m_max = std::min<uint64_t>(n, ZH_KNN_HOST_SLAB);
+        if ((rc = ix->kn_oids.ensure(m_max * k * 8)) || (rc = ix->kn_okeys.ensure(m_max * k * 8)) || (rc = ix->kn_ocounts.ensure(m_max * 4))) return rc;
+        for (uint64_t r0 = 0; r0 < n; r0 += ZH_KNN_HOST_SLAB) {
+            const uint64_t m = std::min<uint64_t>(ZH_KNN_HOST_SLAB, n - r0);
+            if ((rc = knn_slab(ix, &run, first_row + r0, m, (uint32_t)k, metric, mode, ix->kn_oids.as<uint64_t>(), ix->kn_okeys.as<uint64_t>(),
+                               ix->kn_ocounts.as<uint32_t>(), s, &inf)))
+                return rc;
+            HIPCHK(hipMemcpyAsync(out_ids + r0 * k, ix->kn_oids.p, m * k * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_keys + r0 * k, ix->kn_okeys.p, m * k * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_counts + r0, ix->kn_ocounts.p, m * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+    }
+    knn_record(ix, (uint32_t)k, inf);
+    return ZH_OK;
+}
+
+extern "C" int zh_knn_graph_info(const zh_index *ix, zh_knn_info *out) {
+    if (!ix || !out) return fail(ZH_EINVAL, "zh_knn_graph_info: null argument");
+    zh_index *m = const_cast<zh_index *>(ix);
+    std::lock_guard<std::mutex> lk(m->stats_mu);
+    *out = m->kn_info;
     return ZH_OK;
 }
 

@@ -380,6 +380,26 @@ hipError_t zh_launch_join_panel_rows(const uint32_t *dCid, uint64_t p_begin, uin
 hipError_t zh_launch_join_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows, void *dTmp, size_t *tmp_bytes, uint64_t id_base, uint64_t *dOutA,
                                uint64_t *dOutB, uint64_t *dOutKeys, hipStream_t s);
 
+// ---- the exact k-NN graph (zh_knn.hip): each live row's k nearest other live rows, panel by panel
+#define ZH_KNN_PANEL_ROWS 1024u  // live rows one panel holds (= the exact search's internal batch: every reused launcher sees a batch it already serves)
+#define ZH_KNN_CHUNK 64u         // column tiles one block of the matrix-core scan walks at most
+static_assert(ZH_KNN_PANEL_ROWS % 64 == 0, "a held block is four tiles of 16 lines");
+// under a row order: dPos[row] = the position of live row `row` (dCid: zh_launch_join_prep's id-or-masked word per position)
+hipError_t zh_launch_knn_rowpos(const uint32_t *dCid, uint64_t n_pos, uint32_t *dPos, hipStream_t s);
+// the panel's tiles (ceil(B / 16) of them, 32 d bytes each) gathered out of the fp16 copy in the MFMA operand's order, with per line the position's
+// rowMeta and the row number (UINT32_MAX past B); dRows: the panel's B live rows; dPos: null in id order
+hipError_t zh_launch_knn_panel(uint32_t d, const void *dXh, const float2 *dRowMeta, const uint32_t *dPos, const uint32_t *dRows, uint32_t B, void *dA,
+                               float2 *dPMeta, uint32_t *dPid, hipStream_t s);
+// column tiles per block of a launch over `tiles` column tiles and n_ab held blocks
+uint32_t zh_knn_chunk(uint64_t tiles, uint32_t n_ab);
+// the scan of the panel (e.B lines; e.tau / cnt / lid / llo / lhi / cap / over per LINE) against positions [p_begin, p_end) of the copy (e.Xh); self is
+// excluded by row number.  Of e it reads Xh, B, Kc, rho and the lists
+hipError_t zh_launch_knn_mfma(uint32_t d, int metric, int mode, const ZhExact2 &e, const float4 *dQm, const uint32_t *dCid, uint64_t p_begin, uint64_t p_end,
+                              const void *dA, const float2 *dPMeta, const uint32_t *dPid, hipStream_t s);
+// a panel's answer [B][w] (zh_launch_final's) to the lines' places: line dRows[b] - first_row gets the first k entries that are not its own id
+hipError_t zh_launch_knn_emit(const uint64_t *dInIds, const uint64_t *dInKeys, const uint32_t *dInCounts, uint32_t w, const uint32_t *dRows, uint32_t B,
+                              uint64_t id_base, uint64_t first_row, uint32_t k, uint64_t *dOutIds, uint64_t *dOutKeys, uint32_t *dOutCounts, hipStream_t s);
+
 // ---- launchers (zh_score.hip): every sign of a forest built from stored rows, from N row scores per query --------
 // Prefilter (zh_search.hip, "Prefilter"): a batch hashed from row scores picks the rows that can be among a pair's k best from
 // those scores; only they are scored with the reference's arithmetic.  Lists: one per (tree, query), `cap` slots, list (t, b) at

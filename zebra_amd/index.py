@@ -523,6 +523,29 @@ class LSHIndex:
         check(lib().zh_self_join_info(self._h, C.byref(info)))
         return info.as_dict()
 
+    def knn_graph(self, k, metric, first_row=0, n=None):
+        """EXACT k-NN graph of the slab of stored rows [first_row, first_row + n) (default: from first_row to the last stored row): line i holds the
+        k nearest OTHER live rows of stored row first_row + i by (key, id) -- the key search_exact_batch gives for that row's f32 values as the
+        query; only the row itself is excluded, a bit-identical duplicate is a neighbour.  -> (ids [n,k] u64, keys [n,k] u64, counts [n] u32);
+        counts = min(k, live rows - 1), 0 for a removed row; entries past the count are 2^64-1."""
+        stored = self.stored_rows()
+        n = max(stored - first_row, 0) if n is None else int(n)
+        ids = np.empty((n, k), np.uint64)
+        keys = np.empty((n, k), np.uint64)
+        counts = np.zeros(n, np.uint32)
+        check(lib().zh_knn_graph(self._h, int(first_row), n, k, metric.metric, metric.mode, _p(ids), _p(keys), _p(counts)))
+        return ids, keys, counts
+
+    def knn_graph_device(self, k, metric, first_row, n, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream=None):
+        """knn_graph with the outputs ([n,k] u64 twice, [n] u32) already in device memory (raw pointers, e.g. torch .data_ptr())."""
+        check(lib().zh_knn_graph_device(self._h, int(first_row), int(n), k, metric.metric, metric.mode, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream))
+
+    def knn_info(self):
+        """what the most recent k-NN graph call on this index did (zh_knn_graph_info): rows_live, lines, k, path, redone, survivors, launches, tiles"""
+        info = _ffi.KnnInfo()
+        check(lib().zh_knn_graph_info(self._h, C.byref(info)))
+        return info.as_dict()
+
     def deduplicate_within(self, radius, metric):
         """near-duplicate removal: rows are taken in ascending id, and row b is removed exactly when some KEPT row a < b forms a joined pair
         with it (self_join at `radius`).  Decided on the host from the sorted pair list, then passed to remove -> the removed ids, ascending."""
@@ -824,13 +847,30 @@ class Database:
         """every pair of records within `radius` of each other (LSHIndex.self_join: exact) -> [(document_a, document_b, distance)], in
         ascending (id a, key, id b) order.  The distance is the number the key holds (for the parity cosine key: the similarity)."""
         a, b, keys = self.index.self_join(radius, self.metric)
-        if self.metric.metric in _F64_KEYED:
-            dist = keys.view(np.float64)
-        elif self.metric.metric == _ffi.HAMMING:
-            dist = keys.astype(np.float64)
-        else:
-            dist = keys.astype(np.uint32).view(np.float32).astype(np.float64)
+        dist = self._key_numbers(keys)
         return [(self._documents.get(x), self._documents.get(y), float(v)) for x, y, v in zip(a.tolist(), b.tolist(), dist.tolist())]
+
+    def _key_numbers(self, keys):
+        """the number each key holds, as f64 (for the parity cosine key: the similarity)"""
+        if self.metric.metric in _F64_KEYED:
+            return keys.view(np.float64)
+        if self.metric.metric == _ffi.HAMMING:
+            return keys.astype(np.float64)
+        return keys.astype(np.uint32).view(np.float32).astype(np.float64)
+
+    def knn_graph(self, k):
+        """every record's k nearest other records (LSHIndex.knn_graph: exact) -> {document: [(neighbour document, distance)], nearest first},
+        one entry per live record.  The distance is the number the key holds, as in near_duplicates."""
+        ids, keys, counts = self.index.knn_graph(k, self.metric)
+        dist = self._key_numbers(np.ascontiguousarray(keys)).reshape(keys.shape)
+        base = self.index.id_base
+        out = {}
+        for r in range(ids.shape[0]):
+            if (base + r) not in self._documents:
+                continue  # a removed row's line
+            c = int(counts[r])
+            out[self._documents[base + r]] = [(self._documents.get(i), float(v)) for i, v in zip(ids[r, :c].tolist(), dist[r, :c].tolist())]
+        return out
 
     def deduplicate_within(self, radius):
         """LSHIndex.deduplicate_within, then the removed ids' documents go too -> the removed ids"""

@@ -344,6 +344,28 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_knn_graph_info(h_.get(), &info));
         return info;
     }
+    // the forest k-NN graph of the slab (zh_knn_graph_forest): knn_graph's shape, the candidates of a row being the rows that share a leaf with it
+    // in some tree; empty for a removed row and for a row no tree holds.  Needs a built forest.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> knn_graph_forest(std::size_t k, const Met &metric, std::uint64_t first_row, std::uint64_t n) const {
+        std::vector<Id> ids(n * k + 1);
+        std::vector<DistanceUnit> keys(n * k + 1);
+        std::vector<std::uint32_t> counts(n + 1);
+        check(zh_knn_graph_forest(h_.get(), first_row, n, k, Met::metric, metric.mode(), ids.data(), keys.data(), counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(n);
+        for (std::uint64_t i = 0; i < n; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * k + j], keys[i * k + j]);
+        return out;
+    }
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> knn_graph_forest(std::size_t k, const Met &metric) const {
+        return knn_graph_forest(k, metric, 0, zh_index_stored_rows(h_.get()));
+    }
+    zh_knn_forest_info knn_forest_info() const {
+        zh_knn_forest_info info{};
+        check(zh_knn_graph_forest_info(h_.get(), &info));
+        return info;
+    }
     zh_index *handle() const { return h_.get(); }
 
   private:

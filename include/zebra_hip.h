@@ -29,6 +29,7 @@
  *   zh_search_range_batch[_device]       (new) every live row whose key is at or below a per-query threshold key, as a CSR
  *   zh_self_join[_device]                (new) every pair of live rows whose key is at or below one threshold key, each pair once
  *   zh_knn_graph[_device]                (new) every live row's exact k nearest OTHER live rows, slab by slab
+ *   zh_knn_graph_forest[_device]         (new) every row's k nearest rows among its leaf-mates in the forest: exact keys, approximate candidates
  *   zh_index_save / zh_index_load        (new) a snapshot of an index in ONE file of this library's own format (the reference persists through
  *                                        fjall, lsh.rs:62-120, whose files are not read here): rows, removals, forest and the planes' sample rows
  *
@@ -535,6 +536,53 @@ typedef struct zh_knn_info {  /* the most recent zh_knn_graph* call on this inde
 } zh_knn_info;
 /* What the host loop that zh_knn_graph replaces could only count by hand. */
 ZH_API int zh_knn_graph_info(const zh_index *idx, zh_knn_info *out);
+
+/* ---- forest k-NN graph (new): each stored row's k nearest rows AMONG ITS LEAF-MATES -------------------------------------------------------
+ * zh_knn_graph multiplies every row by every row; this call multiplies a row only by the rows the random-projection forest puts beside it.
+ * Arguments, output layout, slab meaning, ids, keys, tails and refusals are zh_knn_graph's.  The candidates of stored row a are
+ *   C(a) = the union, over all trees, of the members of the leaf that holds a in that tree, minus a itself,
+ * with membership as zh_index_get_forest's leaf_ids has it at the time of the call: removed rows have left every tree, rows appended since the
+ * last build are in none.  Only the row with the same row number is excluded; a pair that shares leaves in several trees counts once.  Line i is
+ * the first k of C(first_row + i) by (key, id), out_counts[i] = min(k, |C(a)|); a removed row and a live row that no tree holds have count 0.
+ * Every id, key and count is bit for bit what that definition gives with zh_distance_batch's keys, for all 13 metric / mode / power combinations,
+ * whatever the path, the slabs, the scan's row order or the run: what is approximate is the candidate set, never the arithmetic.  On a forest of
+ * ONE tree whose root is a leaf the answer is zh_knn_graph's.  Compared line by line with zh_knn_graph it is the recall of a forest setting on
+ * the index's own rows.
+ * An index without trees is ZH_ESTATE for a request with n > 0 and k > 0; the other refusals, n = 0 and k = 0 as for zh_knn_graph, judged in the
+ * same order.  Locking as zh_knn_graph_device; zh_stats_t, the five sibling info structs (zh_knn_info included) and the cached live-row views
+ * are left alone: zh_knn_graph_forest_info describes the most recent call.
+ * Path 1 (every metric, dimension and leaf shape): a line's visits are its own leaf in each tree; the leaf-major f32 sweep keys them, each
+ * visit's first k + 1 are merged by (key, id) with duplicates dropped by id, and self is taken out.  Path 2 (ZH_L2SQ, ZH_L2, ZH_COSINE at dim
+ * 256 / 384 / 512 / 768 / 1024, the fp16 row copy present, zh_options.max_node_size >= 64): tree by tree, batches of leaves are gathered out of the
+ * copy and ONE launch multiplies many leaves by themselves on the matrix cores for an interval per pair; a line's bound comes from its running
+ * answer after the earlier trees and from the current tree's list alone (DESIGN.md s17 has the argument); survivors get the canonical key and are
+ * merged into the running answer with duplicates dropped by id.  A batch whose list runs over has its sub-slabs of 65536 lines answered again by
+ * path 1 (`redone`).  ZH_FKNN_PATH=1 in the environment (read per call) forces path 1; ZH_FKNN_LIST_CAP=n (read per call; tests) lowers the list
+ * capacity.  Path 2 serves a slab at the cost of every leaf that holds one of its rows: few large slabs are cheaper than many small ones.
+ * Device scratch is per call, released before return, and bounded whatever the table's size except where stated: 4 bytes per tree node (the
+ * node -> tree map); per sub-slab of 65536 lines 8 trees + 12 bytes per line; path 1 per panel of P <= 1024 lines 4 P dim bytes of rows, 104 bytes
+ * per (line, tree), 8 bytes per key of at most max(2^25, trees x longest leaf) keys and 16 P (k + 1) of answer; path 2 per batch of at most 4096
+ * held lines and max(2048 tiles, the longest leaf) of columns 2 dim + 28 bytes per column row, 6 dim + 24 per held line and 36 bytes per list
+ * slot of (longest leaf of the batch + k, at most 16384 + 8 k; after the first tree at most 1024 + 4 k) slots per line, plus 4 bytes per stored
+ * row under a scan order that is not id order; for the host call 16 k + 4 bytes per line of a sub-slab of at most max(65536, 2^25 / k) lines. */
+ZH_API int zh_knn_graph_forest(zh_index *idx, uint64_t first_row, uint64_t n, size_t k, int metric, int cosine_mode, uint64_t *out_ids,
+                               uint64_t *out_keys, uint32_t *out_counts);
+/* The same with every output in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_knn_graph_forest_device(zh_index *idx, uint64_t first_row, uint64_t n, size_t k, int metric, int cosine_mode, uint64_t *d_out_ids,
+                                      uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream);
+typedef struct zh_knn_forest_info {  /* the most recent zh_knn_graph_forest* call on this index */
+    uint64_t rows_live;   /* live rows of the index */
+    uint64_t lines;       /* the slab's rows that some tree holds */
+    uint32_t k;
+    uint32_t path;        /* 1: the f32 leaf sweep over each line's own leaves; 2: matrix-core intervals leaf by leaf, canonical keys for survivors */
+    uint32_t trees;
+    uint64_t pairs;       /* sum over the trees and over the slab's lines of (length of the line's leaf - 1): from the forest, not from the answer */
+    uint64_t survivors;   /* path 2: pairs that got the canonical key, over the batches path 2 completed */
+    uint32_t redone;      /* path 2: sub-slabs that path 1 answered again because a list ran over */
+    uint64_t launches;    /* path 1: panels swept; path 2: batches (one matrix-core launch each) */
+    uint64_t tiles;       /* path 2: 16 x 16 tile products issued, from the launch geometry (held tiles in use x the leaf's column tiles); 0 on path 1 */
+} zh_knn_forest_info;
+ZH_API int zh_knn_graph_forest_info(const zh_index *idx, zh_knn_forest_info *out);
 
 /* Pipelined form of zh_search_batch_device (new; the reference has one blocking search per query): a context
  * is one in-flight batch with its own scratch.  The context calls do NOT take the index's internal lock (the blocking

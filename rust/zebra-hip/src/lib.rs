@@ -147,6 +147,21 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_knn_forest_info {
+        pub rows_live: u64,
+        pub lines: u64,
+        pub k: u32,
+        pub path: u32,
+        pub trees: u32,
+        pub pairs: u64,
+        pub survivors: u64,
+        pub redone: u32,
+        pub launches: u64,
+        pub tiles: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_filtered_info {
         pub batch: u64,
         pub rows_live: u64,
@@ -256,6 +271,11 @@ pub mod ffi {
         pub fn zh_knn_graph_device(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64,
                                    d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_knn_graph_info(idx: *const zh_index, out: *mut zh_knn_info) -> c_int;
+        pub fn zh_knn_graph_forest(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int, out_ids: *mut u64,
+                                   out_keys: *mut u64, out_counts: *mut u32) -> c_int;
+        pub fn zh_knn_graph_forest_device(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int,
+                                          d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_knn_graph_forest_info(idx: *const zh_index, out: *mut zh_knn_forest_info) -> c_int;
         pub fn zh_search_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
                                       d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_distance_pair(metric: c_int, cosine_mode: c_int, a: *const f32, b: *const f32, dim: usize, out_key: *mut u64,
@@ -640,6 +660,41 @@ impl<const N: usize> LSHIndex<N> {
             first += n;
         }
         Ok(out)
+    }
+
+    /// (new) the forest k-NN graph (zh_knn_graph_forest): knn_graph's shape, a vector's candidates being the vectors that share a leaf with it in
+    /// some tree; a removed vector's list and that of a vector no tree holds are empty.  Fetched in slabs of 1 048 576 rows.
+    pub fn knn_graph_forest<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        k: usize,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<(Uuid, Vec<(Uuid, DistanceUnit)>)>> {
+        const SLAB: u64 = 1 << 20;
+        let t = self.ids.read().unwrap();
+        let stored = t.of_row.len() as u64;
+        let mut out = Vec::with_capacity(stored as usize);
+        let cap = SLAB.min(stored) as usize;
+        let (mut ids, mut keys, mut counts) = (vec![0u64; cap * k + 1], vec![0u64; cap * k + 1], vec![0u32; cap + 1]);
+        let mut first = 0u64;
+        while first < stored {
+            let n = SLAB.min(stored - first);
+            check(unsafe {
+                ffi::zh_knn_graph_forest(self.hip.0, first, n, k, Met::METRIC, metric.param(), ids.as_mut_ptr(), keys.as_mut_ptr(), counts.as_mut_ptr())
+            })?;
+            for i in 0..n as usize {
+                let line = (0..counts[i] as usize).map(|j| (t.of_row[ids[i * k + j] as usize], keys[i * k + j])).collect();
+                out.push((t.of_row[first as usize + i], line));
+            }
+            first += n;
+        }
+        Ok(out)
+    }
+
+    /// what the most recent forest k-NN graph call did (zh_knn_graph_forest_info)
+    pub fn knn_forest_info(&self) -> anyhow::Result<ffi::zh_knn_forest_info> {
+        let mut info = ffi::zh_knn_forest_info::default();
+        check(unsafe { ffi::zh_knn_graph_forest_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// what the most recent k-NN graph call did (zh_knn_graph_info)

@@ -1,0 +1,103 @@
+"""The forest k-NN graph's C ABI (zh_knn_graph_forest*): declared in the header, exported under SYMBOLS, zh_knn_forest_info's layout mirrored by ctypes, the sibling
+info structs unchanged, the argument checks that are judged before any device is touched, and the C example.  No GPU needed."""
+import ctypes
+import os
+import re
+import subprocess
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KNN = ("zh_knn_graph_forest", "zh_knn_graph_forest_device", "zh_knn_graph_forest_info")
+FIELDS = ("rows_live", "lines", "k", "path", "trees", "pairs", "survivors", "redone", "launches", "tiles")
+
+
+def test_header_declares_the_forest_graph():
+    h = open(os.path.join(ROOT, "include", "zebra_hip.h")).read()
+    for name in KNN:
+        assert re.search(r"ZH_API\s+int\s+%s\s*\(" % name, h), name
+    assert "typedef struct zh_knn_forest_info" in h
+    # the device form takes a stream as its last argument, like its siblings
+    assert re.search(r"zh_knn_graph_forest_device\s*\([^;]*void\s*\*\s*stream\s*\)\s*;", h)
+
+
+def test_symbols_list_the_forest_graph():
+    from zebra_amd import _ffi
+    names = {n for n, _, _ in _ffi.SYMBOLS}
+    for name in KNN:
+        assert name in names, name
+    lib = ctypes.CDLL(_ffi.LIB_PATH)
+    for name in KNN:
+        assert hasattr(lib, name), name
+    assert [f for f, _ in _ffi.KnnForestInfo._fields_] == list(FIELDS)
+
+
+def test_forest_info_layout_matches_header():
+    from zebra_amd import _ffi
+    src = r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "zebra_hip.h"
+int main(void){
+  printf("%%zu", sizeof(zh_knn_forest_info));
+%s
+  printf("\n");
+  return 0; }''' % "\n".join('  printf(" %%zu", offsetof(zh_knn_forest_info, %s));' % f for f in FIELDS)
+    with tempfile.TemporaryDirectory() as td:
+        c = os.path.join(td, "t.c")
+        open(c, "w").write(src)
+        exe = os.path.join(td, "t")
+        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
+        got = [int(x) for x in subprocess.check_output([exe], text=True).split()]
+    F = _ffi.KnnForestInfo
+    assert got == [ctypes.sizeof(F)] + [getattr(F, f).offset for f in FIELDS]
+
+
+def test_sibling_info_structs_are_unchanged():
+    from zebra_amd import _ffi
+    assert [f for f, _ in _ffi.ExactInfo._fields_] == ["batch", "rows_live", "path", "redone", "survivors", "launches"]
+    assert [f for f, _ in _ffi.FilteredInfo._fields_] == ["batch", "rows_live", "rows_allowed", "path", "redone", "survivors", "launches",
+                                                          "tiles_skipped"]
+    assert [f for f, _ in _ffi.RangeInfo._fields_] == ["batch", "rows_live", "hits", "path", "redone", "candidates", "launches"]
+    assert [f for f, _ in _ffi.JoinInfo._fields_] == ["rows_live", "pairs", "path", "redone", "candidates", "launches", "tiles"]
+    assert [f for f, _ in _ffi.KnnInfo._fields_] == ["rows_live", "lines", "k", "path", "redone", "survivors", "launches", "tiles"]
+
+
+def test_arguments_are_judged_before_any_device():
+    """A null index, null outputs for a non-empty request, an unknown metric and the k limit are refused by the first lines of either entry
+    point.  The calls that pass a (never dereferenced) stand-in for the index must fail: were a check lost, the call would go on to lock that
+    stand-in and reach for a device."""
+    from zebra_amd import _ffi
+    L = _ffi.lib()
+    fake = ctypes.create_string_buffer(64)
+    idx = ctypes.cast(fake, ctypes.c_void_p)
+    ids, keys, counts = (ctypes.c_uint64 * 8)(), (ctypes.c_uint64 * 8)(), (ctypes.c_uint32 * 2)()
+    P = lambda x: ctypes.cast(x, ctypes.c_void_p)  # noqa: E731
+
+    def host(ix, n, k, metric, ip, kp, cp):
+        return L.zh_knn_graph_forest(ix, 0, n, k, metric, 0, ip, kp, cp)
+
+    def dev(ix, n, k, metric, ip, kp, cp):
+        return L.zh_knn_graph_forest_device(ix, 0, n, k, metric, 0, ip, kp, cp, None)
+
+    for call in (host, dev):
+        assert call(None, 2, 4, 1, P(ids), P(keys), P(counts)) == _ffi.ZH_EINVAL and b"null" in L.zh_last_error()
+        assert call(None, 0, 4, 1, P(ids), P(keys), P(counts)) == _ffi.ZH_EINVAL  # (a null index is refused even for an empty request)
+        assert call(idx, 2, 4, 1, None, P(keys), P(counts)) == _ffi.ZH_EINVAL and b"null" in L.zh_last_error()
+        assert call(idx, 2, 4, 1, P(ids), None, P(counts)) == _ffi.ZH_EINVAL
+        assert call(idx, 2, 4, 1, P(ids), P(keys), None) == _ffi.ZH_EINVAL
+        assert call(idx, 2, 0, 1, None, None, None) == _ffi.ZH_EINVAL  # k = 0 still writes the counts
+        assert call(idx, 2, 4, 99, P(ids), P(keys), P(counts)) == _ffi.ZH_EINVAL  # no such metric
+        assert call(idx, 0, 4, 99, None, None, None) == _ffi.ZH_EINVAL
+        assert call(idx, 2, 1024, 1, P(ids), P(keys), P(counts)) == _ffi.ZH_ELIMIT and b"ZH_MAX_TOPK" in L.zh_last_error()
+        assert call(idx, 0, 1024, 1, None, None, None) == _ffi.ZH_ELIMIT
+        assert call(idx, 2, 1024, 99, P(ids), P(keys), P(counts)) == _ffi.ZH_EINVAL  # the metric is judged before the limit
+        assert call(idx, 0, 1023, 1, None, None, None) == _ffi.ZH_OK  # an empty request: nothing to do, nothing touched
+    info = _ffi.KnnForestInfo()
+    assert L.zh_knn_graph_forest_info(None, ctypes.byref(info)) == _ffi.ZH_EINVAL
+    assert L.zh_knn_graph_forest_info(idx, None) == _ffi.ZH_EINVAL
+
+
+def test_example_compiles_as_c99():
+    with tempfile.TemporaryDirectory() as td:
+        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-c", "-I", os.path.join(ROOT, "include"),
+                               os.path.join(ROOT, "examples", "knn_forest_example.c"), "-o", os.path.join(td, "e.o")])

@@ -120,6 +120,14 @@ class KnnInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KnnForestInfo(C.Structure):
+    _fields_ = [("rows_live", C.c_uint64), ("lines", C.c_uint64), ("k", C.c_uint32), ("path", C.c_uint32), ("trees", C.c_uint32),
+                ("pairs", C.c_uint64), ("survivors", C.c_uint64), ("redone", C.c_uint32), ("launches", C.c_uint64), ("tiles", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CompactInfo(C.Structure):
     _fields_ = [("rows_before", C.c_uint64), ("rows_after", C.c_uint64), ("rows_moved", C.c_uint64), ("bytes_moved", C.c_uint64),
                 ("scratch_bytes", C.c_uint64), ("capacity_rows", C.c_uint64), ("copy_bytes_released", C.c_uint64), ("ms", C.c_double)]
@@ -192,6 +200,9 @@ SYMBOLS = [
     ("zh_knn_graph", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_knn_graph_device", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_knn_graph_info", _i, [_vp, _vp]),
+    ("zh_knn_graph_forest", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
+    ("zh_knn_graph_forest_device", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    ("zh_knn_graph_forest_info", _i, [_vp, _vp]),
     ("zh_search_ctx_create", _i, [_vp, _vp]),
     ("zh_search_ctx_destroy", None, [_vp]),
     ("zh_search_begin", _i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),

@@ -276,6 +276,13 @@ struct zh_index {
     // tiles, rowMeta and row numbers, the lists' bases, the panel's answer, and the outputs staged for the host call
     DevBuf kn_qm, kn_cid, kn_pos, kn_A, kn_pmeta, kn_pid, kn_cbase, kn_pids, kn_pkeys, kn_pcounts, kn_oids, kn_okeys, kn_ocounts;
     zh_knn_info kn_info{};  // (stats_mu)
+    // the forest k-NN graph's per-call scratch (all released before the call returns): the node -> tree map, a sub-slab's row -> leaf table, line
+    // flags, their exclusive sums and the lines, {pairs, tiles} counters, a path-1 panel's visit sizes, bases, groups and their row offsets, and
+    // path 2's batch: segments, column sources, column and held rows, held counts, both sides' tiles, rowMeta and queries, the lines' rows and
+    // bounds, the sub-slabs to redo, the row -> position map
+    DevBuf fk_ntree, fk_rl, fk_flag, fk_excl, fk_tmp, fk_rows, fk_ctr, fk_lens, fk_takes, fk_rbase, fk_cbase, fk_groups, fk_groff, fk_segs, fk_colsrc, fk_crow,
+        fk_hrow, fk_held, fk_CA, fk_cmeta, fk_cqm, fk_HA, fk_hmeta, fk_qrow, fk_maxk, fk_redo, fk_pos;
+    zh_knn_forest_info fk_info{};  // (stats_mu)
 
     bool broken = false;  // an incremental add failed half way: trees are stale until zh_index_build
     bool rows_torn = false;  // ... or a compaction failed after rows had begun to move (set with broken): the TABLE is inconsistent until zh_index_clear
@@ -4585,6 +4592,383 @@ extern "C" int zh_knn_graph_info(const zh_index *ix, zh_knn_info *out) {
     zh_index *m = const_cast<zh_index *>(ix);
     std::lock_guard<std::mutex> lk(m->stats_mu);
     *out = m->kn_info;
+    return ZH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// forest k-NN graph (zh_fknn.hip): each row's k nearest rows among its leaf-mates over all trees.  DESIGN.md s17
+// ------------------------------------------------------------------------------------------------
+#define ZH_FKNN_KEY_BUDGET (uint64_t(1) << 25)  // keys one path-1 panel's sweep may write (256 MiB), unless one line's leaves alone hold more
+
+static void fknn_release_scratch(zh_index *ix) {
+    knn_release_scratch(ix);
+    DevBuf *bs[] = {&ix->fk_ntree, &ix->fk_rl, &ix->fk_flag, &ix->fk_excl, &ix->fk_tmp, &ix->fk_rows, &ix->fk_ctr, &ix->fk_lens, &ix->fk_takes, &ix->fk_rbase,
+                    &ix->fk_cbase, &ix->fk_groups, &ix->fk_groff, &ix->fk_segs, &ix->fk_colsrc, &ix->fk_crow, &ix->fk_hrow, &ix->fk_held, &ix->fk_CA,
+                    &ix->fk_cmeta, &ix->fk_cqm, &ix->fk_HA, &ix->fk_hmeta, &ix->fk_qrow, &ix->fk_maxk, &ix->fk_redo, &ix->fk_pos};
+    for (DevBuf *b : bs) b->release();
+}
+struct FknnScratchGuard {
+    zh_index *ix;
+    ~FknnScratchGuard() { fknn_release_scratch(ix); }
+};
+
+struct FknnRun {  // what a call settles once
+    uint32_t T = 0;
+    bool path2 = false;
+    const void *Xh = nullptr;
+    const float2 *rowMeta = nullptr;
+    const uint32_t *pos = nullptr;  // row -> position under a row order, else null
+    float rho = 0.f, Kc = 0.f;
+    uint32_t env_cap = 0;           // ZH_FKNN_LIST_CAP (0: not set)
+    std::vector<std::vector<uint2>> leaves;  // per tree the non-empty leaves {offset into leaf_ids, length}, in the host mirror's order (path 2)
+};
+
+// The node -> tree map on the device (both paths' row -> leaf table), the path rule, and path 2's per-call views.
+static int fknn_setup(zh_index *ix, uint32_t k, int metric, int mode, hipStream_t s, FknnRun *run) {
+    const uint32_t d = ix->opt.dim, T = (uint32_t)ix->h_roots.size();
+    const size_t nn = ix->h_plane.size();
+    run->T = T;
+    const char *env_p = getenv("ZH_FKNN_PATH");
+    bool want2 = !(env_p && atoi(env_p) == 1) && zh_exact_mfma_supported(d, metric) && ix->opt.max_node_size >= 64;
+    int rc;
+    if (want2) {
+        std::lock_guard<std::mutex> lb(ix->blk_mu);
+        bool ok = false;
+        if ((rc = ensure_row_half(ix, &ok))) return rc;
+        if (!ok || !ix->row_half.p) want2 = false;  // no copy (no room, or the per-row scales alone): path 1
+        else {
+            run->Xh = ix->row_half.p; run->rowMeta = ix->row_meta.as<float2>(); run->rho = ix->row_rho;
+            if (ix->perm_rows) {
+                if ((rc = ix->fk_pos.ensure(ix->n_rows * 4))) return rc;
+                HIPCHK(zh_launch_fknn_rowpos(ix->scan_perm.as<uint32_t>(), ix->perm_rows, ix->n_rows, ix->fk_pos.as<uint32_t>(), s));
+                HIPCHK(hipStreamSynchronize(s));  // (scan_perm is read under blk_mu only)
+                run->pos = ix->fk_pos.as<uint32_t>();
+            }
+        }
+    }
+    std::vector<uint32_t> node_tree(std::max<size_t>(nn, 1), 0xFFFFFFFFu), st;
+    if (want2) run->leaves.resize(T);
+    for (uint32_t t = 0; t < T; t++) {
+        st.assign(1, ix->h_roots[t]);
+        while (!st.empty()) {
+            const uint32_t nd = st.back(); st.pop_back();
+            node_tree[nd] = t;
+            if (ix->h_plane[nd] >= 0) { st.push_back((uint32_t)ix->h_right[nd]); st.push_back((uint32_t)ix->h_left[nd]); }
+            else if (want2 && ix->h_right[nd] > 0) run->leaves[t].push_back(make_uint2((uint32_t)ix->h_left[nd], (uint32_t)ix->h_right[nd]));
+        }
+    }
+    if ((rc = ix->fk_ntree.ensure(node_tree.size() * 4)) || (rc = ix->fk_ctr.ensure(32))) return rc;
+    HIPCHK(hipMemcpyAsync(ix->fk_ntree.p, node_tree.data(), node_tree.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(ix->fk_ctr.p, 0, 32, s));
+    HIPCHK(hipStreamSynchronize(s));  // (node_tree is this frame's)
+    const char *env_c = getenv("ZH_FKNN_LIST_CAP");
+    if (env_c && atoi(env_c) > 0) run->env_cap = (uint32_t)atoi(env_c);
+    if (want2) { run->Kc = zh_approx_bound(metric, d, 1); run->path2 = true; }
+    return ZH_OK;
+}
+
+// Path 1 of one panel: the B lines dRows (rows of the sub-slab [r0, ...) that some tree holds) -> their lines of the outputs.
+static int fknn_panel1(zh_index *ix, const FknnRun &run, uint64_t r0, const uint32_t *dRows, uint32_t B, uint32_t k, int metric, int mode, uint64_t first_row,
+                       uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts, hipStream_t s, zh_knn_forest_info *inf) {
+    const uint32_t d = ix->opt.dim, T = run.T, w = k + 1;
+    const size_t V = (size_t)B * T;
+    const uint2 *rl = ix->fk_rl.as<uint2>();
+    int rc;
+    if ((rc = ix->fk_lens.ensure(V * 4)) || (rc = ix->fk_takes.ensure(V * 4)) || (rc = ix->fk_rbase.ensure((V + 1) * 4)) || (rc = ix->fk_cbase.ensure((V + 1) * 4)) ||
+        (rc = ix->fk_tmp.ensure((V / 1024 + 2) * 4)) || (rc = ix->ex_visits.ensure(V * sizeof(ZhVisit))) || (rc = ix->fk_groups.ensure(V * sizeof(ZhGroup))) ||
+        (rc = ix->fk_groff.ensure(V * 8)) || (rc = ix->ex_cbase.ensure((V + 1) * 8)) || (rc = ix->ex_Q.ensure((size_t)B * d * 4)) ||
+        (rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->kn_pids.ensure((size_t)B * w * 8)) || (rc = ix->kn_pkeys.ensure((size_t)B * w * 8)) ||
+        (rc = ix->kn_pcounts.ensure((size_t)B * 4)))
+        return rc;
+    HIPCHK(zh_launch_fknn_visit_sizes(rl, T, r0, dRows, B, w, ix->fk_lens.as<uint32_t>(), ix->fk_takes.as<uint32_t>(), s));
+    HIPCHK(zh_launch_scan_u32(ix->fk_lens.as<uint32_t>(), ix->fk_rbase.as<uint32_t>(), V, ix->fk_tmp.as<uint32_t>(), s));
+    HIPCHK(zh_launch_scan_u32(ix->fk_takes.as<uint32_t>(), ix->fk_cbase.as<uint32_t>(), V, ix->fk_tmp.as<uint32_t>(), s));
+    HIPCHK(zh_launch_fknn_visits(rl, T, r0, dRows, B, w, ix->fk_rbase.as<uint32_t>(), ix->fk_cbase.as<uint32_t>(), ix->ex_visits.as<ZhVisit>(),
+                                 ix->fk_groups.as<ZhGroup>(), ix->fk_groff.as<uint64_t>(), ix->ex_cbase.as<uint64_t>(), s));
+    uint32_t tot[2] = {0, 0};  // keys the sweep writes, candidates select keeps
+    HIPCHK(hipMemcpyAsync(&tot[0], ix->fk_rbase.as<uint32_t>() + V, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&tot[1], ix->fk_cbase.as<uint32_t>() + V, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = ix->ex_keys.ensure(std::max<size_t>(tot[0], 1) * 8)) || (rc = ix->ex_ckeys.ensure(std::max<size_t>(tot[1], 1) * 8)) ||
+        (rc = ix->ex_cids.ensure(std::max<size_t>(tot[1], 1) * 4)))
+        return rc;
+    const int param = metric == ZH_COSINE ? mode : ((metric == ZH_MINKOWSKI || metric == ZH_PNORM) ? mode : 0);
+    HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dRows, B, ix->ex_Q.as<float>(), s));
+    HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), B, d, ix->ex_QQ.as<float>(), s));
+    HIPCHK(zh_launch_sweep(ix->X.as<float>(), d, ix->ex_Q.as<float>(), ix->ex_QQ.as<float>(), ix->fk_groups.as<ZhGroup>(), ix->fk_groff.as<uint64_t>(), V, nullptr,
+                           ix->leaf_ids.as<uint32_t>(), tot[0], metric, param, ix->ex_keys.as<uint64_t>(), s));
+    HIPCHK(zh_launch_select(ix->ex_visits.as<ZhVisit>(), V, ix->leaf_ids.as<uint32_t>(), ix->ex_keys.as<uint64_t>(), ix->ex_ckeys.as<uint64_t>(),
+                            ix->ex_cids.as<uint32_t>(), ix->max_leaf_len, nullptr, s));
+    HIPCHK(zh_launch_final(ix->ex_cbase.as<uint64_t>(), B, T, w, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), ix->opt.id_base,
+                           ix->kn_pids.as<uint64_t>(), ix->kn_pkeys.as<uint64_t>(), ix->kn_pcounts.as<uint32_t>(), nullptr, s));
+    HIPCHK(zh_launch_knn_emit(ix->kn_pids.as<uint64_t>(), ix->kn_pkeys.as<uint64_t>(), ix->kn_pcounts.as<uint32_t>(), w, dRows, B, ix->opt.id_base, first_row, k,
+                              dIds, dKeys, dCounts, s));
+    inf->launches++;
+    return ZH_OK;
+}
+
+// One sub-slab [r0, r0 + m) of the slab that starts at first_row: its row -> leaf table and lines (count: into lines / pairs of the info), and
+// (answer) its lines by path 1, panel after panel.
+static int fknn_subslab(zh_index *ix, const FknnRun &run, uint64_t r0, uint32_t m, bool count, bool answer, uint32_t k, int metric, int mode,
+                        uint64_t first_row, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts, hipStream_t s, zh_knn_forest_info *inf) {
+    const uint32_t T = run.T;
+    int rc;
+    if ((rc = ix->fk_rl.ensure((size_t)m * T * sizeof(uint2))) || (rc = ix->fk_flag.ensure((size_t)m * 4)) || (rc = ix->fk_excl.ensure(((size_t)m + 1) * 4)) ||
+        (rc = ix->fk_tmp.ensure(((size_t)m / 1024 + 2) * 4)) || (rc = ix->fk_rows.ensure((size_t)m * 4)))
+        return rc;
+    unsigned long long *ctr = ix->fk_ctr.as<unsigned long long>();
+    HIPCHK(zh_launch_fknn_rowleaf(ix->node_pack.as<int4>(), ix->fk_ntree.as<uint32_t>(), ix->n_nodes, ix->leaf_ids.as<uint32_t>(), T, r0, m, ix->fk_rl.as<uint2>(), s));
+    HIPCHK(zh_launch_fknn_lines(ix->fk_rl.as<uint2>(), T, r0, m, ix->fk_flag.as<uint32_t>(), ix->fk_excl.as<uint32_t>(), ix->fk_tmp.as<uint32_t>(),
+                                ix->fk_rows.as<uint32_t>(), count ? ctr : ctr + 2, s));
+    uint32_t L = 0;
+    HIPCHK(hipMemcpyAsync(&L, ix->fk_excl.as<uint32_t>() + m, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (count) inf->lines += L;
+    if (!answer || !L) return ZH_OK;
+    // lines per panel: their T leaves' keys within the budget (a line's own leaves are the least a panel can hold)
+    const uint64_t per_line = (uint64_t)T * std::max<uint32_t>(ix->max_leaf_len, 1);
+    const uint32_t P = (uint32_t)std::min<uint64_t>(ZH_KNN_PANEL_ROWS, std::max<uint64_t>(1, ZH_FKNN_KEY_BUDGET / per_line));
+    for (uint32_t a0 = 0; a0 < L; a0 += P) {
+        const uint32_t B = std::min(P, L - a0);
+        if ((rc = fknn_panel1(ix, run, r0, ix->fk_rows.as<uint32_t>() + a0, B, k, metric, mode, first_row, dIds, dKeys, dCounts, s, inf))) return rc;
+    }
+    return ZH_OK;
+}
+
+// Path 2 of one batch of segments of one tree (first: no line has a running answer from an earlier tree yet, so the lists hold whole leaves).
+// *overflowed: a list ran over; the batch changed nothing and its lines' sub-slabs are marked in fk_redo.
+static int fknn_batch2(zh_index *ix, const FknnRun &run, std::vector<ZhFknnSeg> &segs, const std::vector<uint2> &colsrc, uint32_t held_tiles, uint32_t longest,
+                       bool first, uint64_t first_row, uint64_t n, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts,
+                       hipStream_t s, bool *overflowed, zh_knn_forest_info *inf) {
+    const uint32_t d = ix->opt.dim, NT = (uint32_t)colsrc.size(), HB = held_tiles * 16, n_segs = (uint32_t)segs.size();
+    // column tiles per block: ZH_FKNN_CHUNK, fewer while the launch would not fill the device (about 1024 blocks), never under 8
+    uint32_t ch = ZH_FKNN_CHUNK, n_blocks = 0;
+    for (;;) {
+        n_blocks = 0;
+        for (ZhFknnSeg &sg : segs) { sg.first_block = n_blocks; n_blocks += (sg.held_tiles + 3) / 4 * ((sg.ct + ch - 1) / ch); }
+        if (n_blocks >= 1024 || ch <= 8) break;
+        ch /= 2;
+    }
+    // list slots per line: a line lists at most its leaf-mates (longest - 1 <= lim): only the ceilings and the test switch can make a list run over
+    uint32_t cap = std::min<uint32_t>(longest + k, first ? 16384 + 8 * k : 1024 + 4 * k), lim = cap - k;
+    if (run.env_cap) { lim = std::min(lim, run.env_cap); cap = lim + k; }
+    int rc;
+    if ((rc = ix->fk_segs.ensure((size_t)n_segs * sizeof(ZhFknnSeg))) || (rc = ix->fk_colsrc.ensure((size_t)NT * 8)) || (rc = ix->fk_crow.ensure((size_t)NT * 64)) ||
+        (rc = ix->fk_hrow.ensure((size_t)HB * 4)) || (rc = ix->fk_held.ensure((size_t)n_segs * 4)) || (rc = ix->fk_CA.ensure((size_t)NT * 32 * d)) ||
+        (rc = ix->fk_cmeta.ensure((size_t)NT * 128)) || (rc = ix->fk_cqm.ensure((size_t)NT * 256)) || (rc = ix->fk_HA.ensure((size_t)HB * 2 * d)) ||
+        (rc = ix->fk_hmeta.ensure((size_t)HB * 8)) || (rc = ix->fk_qrow.ensure((size_t)HB * 4)) || (rc = ix->fk_maxk.ensure((size_t)HB * 8)) ||
+        (rc = ix->ex_Q.ensure((size_t)HB * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)HB * 4)) || (rc = ix->ex_tau.ensure((size_t)HB * 4)) ||
+        (rc = ix->ex_cnt.ensure((size_t)HB * 4)) || (rc = ix->ex_lid.ensure((size_t)HB * cap * 4)) || (rc = ix->ex_llo.ensure((size_t)HB * cap * 4)) ||
+        (rc = ix->ex_lhi.ensure((size_t)HB * cap * 4)) || (rc = ix->ex_scr.ensure((size_t)HB * cap * 12)) || (rc = ix->ex_over.ensure(8)) ||
+        (rc = ix->ex_ckeys.ensure((size_t)HB * cap * 8)) || (rc = ix->ex_cids.ensure((size_t)HB * cap * 4)) || (rc = ix->ex_cbase.ensure(((size_t)HB + 1) * 8)) ||
+        (rc = ix->kn_pids.ensure((size_t)HB * k * 8)) || (rc = ix->kn_pkeys.ensure((size_t)HB * k * 8)) || (rc = ix->kn_pcounts.ensure((size_t)HB * 4)))
+        return rc;
+    ZhExact2 e{run.Xh, run.rowMeta, nullptr, 0, ix->ex_bits.as<uint32_t>(), nullptr, nullptr, HB, run.Kc, run.rho,
+               ix->ex_tau.as<uint32_t>(), ix->ex_cnt.as<uint32_t>(), ix->ex_lid.as<uint32_t>(), ix->ex_llo.as<uint32_t>(), ix->ex_lhi.as<uint32_t>(), cap,
+               ix->ex_over.as<uint32_t>()};
+    std::vector<uint64_t> cb((size_t)HB + 1);
+    for (uint32_t b = 0; b <= HB; b++) cb[b] = (uint64_t)b * cap;
+    const ZhFknnSeg *dSegs = ix->fk_segs.as<ZhFknnSeg>();
+    uint32_t *crow = ix->fk_crow.as<uint32_t>(), *hrow = ix->fk_hrow.as<uint32_t>(), *held = ix->fk_held.as<uint32_t>();
+    unsigned long long *ctr = ix->fk_ctr.as<unsigned long long>();
+    HIPCHK(hipMemcpyAsync(ix->fk_segs.p, segs.data(), (size_t)n_segs * sizeof(ZhFknnSeg), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ix->fk_colsrc.p, colsrc.data(), (size_t)NT * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ix->ex_cbase.p, cb.data(), cb.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(zh_launch_fknn_cols(ix->fk_colsrc.as<uint2>(), NT, ix->leaf_ids.as<uint32_t>(), ix->n_rows, crow, s));
+    HIPCHK(zh_launch_fknn_held(dSegs, n_segs, ix->leaf_ids.as<uint32_t>(), first_row, n, hrow, held, ctr + 1, s));
+    HIPCHK(zh_launch_fknn_gather(d, run.Xh, run.rowMeta, run.pos, crow, NT, run.rho, ix->fk_CA.p, ix->fk_cmeta.as<float2>(), ix->fk_cqm.as<float4>(), s));
+    HIPCHK(zh_launch_fknn_gather(d, run.Xh, run.rowMeta, run.pos, hrow, held_tiles, run.rho, ix->fk_HA.p, ix->fk_hmeta.as<float2>(), nullptr, s));
+    HIPCHK(zh_launch_fknn_bound(hrow, HB, first_row, k, dKeys, dCounts, ix->fk_qrow.as<uint32_t>(), ix->fk_maxk.as<uint64_t>(), s));
+    HIPCHK(zh_launch_range_tau(ix->fk_maxk.as<uint64_t>(), HB, metric, mode, e.tau, s));
+    HIPCHK(hipMemsetAsync(e.cnt, 0, (size_t)HB * 4, s));
+    HIPCHK(hipMemsetAsync(e.over, 0, 8, s));
+    HIPCHK(zh_launch_fknn_mfma(d, metric, mode, dSegs, n_segs, n_blocks, held, ch, ix->fk_CA.p, ix->fk_cqm.as<float4>(), crow, ix->fk_HA.p,
+                               ix->fk_hmeta.as<float2>(), hrow, e, lim, s));
+    HIPCHK(zh_launch_exact_prune(e, k, ix->ex_scr.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, ix->fk_qrow.as<uint32_t>(), HB, ix->ex_Q.as<float>(), s));
+    HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), HB, d, ix->ex_QQ.as<float>(), s));
+    HIPCHK(zh_launch_exact_survivor_keys(ix->X.as<float>(), d, ix->ex_Q.as<float>(), ix->ex_QQ.as<float>(), metric, mode, e, ix->ex_ckeys.as<uint64_t>(),
+                                         ix->ex_cids.as<uint32_t>(), s));
+    HIPCHK(zh_launch_fknn_seed(hrow, HB, first_row, ix->opt.id_base, k, dIds, dKeys, dCounts, e, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), s));
+    HIPCHK(zh_launch_final(ix->ex_cbase.as<uint64_t>(), HB, 1, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), ix->opt.id_base,
+                           ix->kn_pids.as<uint64_t>(), ix->kn_pkeys.as<uint64_t>(), ix->kn_pcounts.as<uint32_t>(), nullptr, s));
+    HIPCHK(zh_launch_fknn_store(hrow, HB, first_row, ix->opt.id_base, k, ix->kn_pids.as<uint64_t>(), ix->kn_pkeys.as<uint64_t>(), dIds, dKeys, dCounts,
+                                e.over, s));
+    std::vector<uint32_t> h_cnt((size_t)HB + 2);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), e.cnt, (size_t)HB * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_cnt.data() + HB, e.over, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // (segs, colsrc and cb are the caller's and this frame's)
+    inf->launches++;
+    *overflowed = h_cnt[HB] != 0;
+    if (*overflowed) HIPCHK(zh_launch_fknn_mark(hrow, HB, first_row, ix->fk_redo.as<uint32_t>(), s));
+    else
+        for (uint32_t b = 0; b < HB; b++) inf->survivors += h_cnt[b];
+    return ZH_OK;
+}
+
+// Path 2 of the slab: tree after tree, a tree's leaves in batches of segments (at most ZH_FKNN_HELD_ROWS held lines and ZH_FKNN_COL_TILES column
+// tiles, or ONE longer leaf's); then the sub-slabs of the batches whose lists ran over, by path 1.
+static int fknn_path2(zh_index *ix, const FknnRun &run, uint64_t first_row, uint64_t n, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys,
+                      uint32_t *dCounts, hipStream_t s, zh_knn_forest_info *inf) {
+    const uint32_t n_sub = (uint32_t)((n + ZH_FKNN_SLAB - 1) / ZH_FKNN_SLAB), HT_MAX = ZH_FKNN_HELD_ROWS / 16;
+    int rc;
+    if ((rc = ix->fk_redo.ensure((size_t)n_sub * 4))) return rc;
+    HIPCHK(hipMemsetAsync(ix->fk_redo.p, 0, (size_t)n_sub * 4, s));
+    std::vector<ZhFknnSeg> segs;
+    std::vector<uint2> colsrc;
+    uint32_t held_tiles = 0, longest = 0;
+    bool any_over = false;
+    auto flush = [&](bool first) -> int {
+        if (segs.empty()) return ZH_OK;
+        bool over = false;
+        const int r = fknn_batch2(ix, run, segs, colsrc, held_tiles, longest, first, first_row, n, k, metric, mode, dIds, dKeys, dCounts, s, &over, inf);
+        any_over = any_over || over;
+        segs.clear(); colsrc.clear(); held_tiles = 0; longest = 0;
+        return r;
+    };
+    for (uint32_t t = 0; t < run.T; t++) {
+        for (const uint2 leaf : run.leaves[t]) {
+            const uint32_t off = leaf.x, len = leaf.y, ct = (len + 15) / 16;
+            uint32_t col0 = 0xFFFFFFFFu;  // the leaf's columns in the batch being filled (none yet)
+            for (uint32_t w0 = 0; w0 < len; w0 += ZH_FKNN_HELD_ROWS) {
+                const uint32_t hl = std::min<uint32_t>(ZH_FKNN_HELD_ROWS, len - w0), ht = (hl + 15) / 16;
+                if (!segs.empty() && (held_tiles + ht > HT_MAX || (col0 == 0xFFFFFFFFu && colsrc.size() + ct > ZH_FKNN_COL_TILES))) {
+                    if ((rc = flush(t == 0))) return rc;
+                    col0 = 0xFFFFFFFFu;
+                }
+                if (col0 == 0xFFFFFFFFu) {
+                    col0 = (uint32_t)colsrc.size();
+                    for (uint32_t c = 0; c < ct; c++) colsrc.push_back(make_uint2(off + 16 * c, std::min<uint32_t>(16, len - 16 * c)));
+                }
+                segs.push_back(ZhFknnSeg{col0, ct, off + w0, hl, held_tiles * 16, ht, 0, 0});
+                held_tiles += ht;
+                longest = std::max(longest, len);
+            }
+        }
+        if ((rc = flush(t == 0))) return rc;  // (a batch holds one tree's leaves: a line is in it once)
+    }
+    if (!any_over) return ZH_OK;
+    std::vector<uint32_t> redo(n_sub);
+    HIPCHK(hipMemcpyAsync(redo.data(), ix->fk_redo.p, (size_t)n_sub * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t j = 0; j < n_sub; j++) {
+        if (!redo[j]) continue;
+        const uint64_t r0 = first_row + (uint64_t)j * ZH_FKNN_SLAB;
+        const uint32_t m = (uint32_t)std::min<uint64_t>(ZH_FKNN_SLAB, first_row + n - r0);
+        inf->redone++;
+        if ((rc = fknn_subslab(ix, run, r0, m, false, true, k, metric, mode, first_row, dIds, dKeys, dCounts, s, inf))) return rc;
+    }
+    return ZH_OK;
+}
+
+// One slab on device outputs (under mu, exclusive; fknn_setup has run; k > 0, n > 0): every line filled as "no neighbours", the sub-slabs' lines
+// and pairs counted, and the lines answered -- sub-slab by sub-slab on path 1, leaf-major over the whole slab on path 2.
+static int fknn_slab(zh_index *ix, const FknnRun &run, uint64_t first_row, uint64_t n, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys,
+                     uint32_t *dCounts, hipStream_t s, zh_knn_forest_info *inf) {
+    int rc;
+    HIPCHK(zh_launch_exact_empty((uint32_t)n, k, dIds, dKeys, dCounts, s));
+    for (uint64_t r0 = first_row; r0 < first_row + n; r0 += ZH_FKNN_SLAB) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(ZH_FKNN_SLAB, first_row + n - r0);
+        if ((rc = fknn_subslab(ix, run, r0, m, true, !run.path2, k, metric, mode, first_row, dIds, dKeys, dCounts, s, inf))) return rc;
+    }
+    if (run.path2 && (rc = fknn_path2(ix, run, first_row, n, k, metric, mode, dIds, dKeys, dCounts, s, inf))) return rc;
+    return ZH_OK;
+}
+
+static int fknn_finish(zh_index *ix, uint32_t k, zh_knn_forest_info inf, hipStream_t s) {
+    unsigned long long ctr[2] = {0, 0};
+    if (ix->fk_ctr.p) {
+        HIPCHK(hipMemcpyAsync(ctr, ix->fk_ctr.p, 16, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    inf.k = k;
+    inf.rows_live = ix->ex_n_live;
+    inf.trees = ix->n_trees;
+    inf.pairs = ctr[0];
+    inf.tiles = ctr[1];
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    ix->fk_info = inf;
+    return ZH_OK;
+}
+
+// judged before any device is touched, in this order of kinds: null index (even for n = 0), null outputs of a non-empty request, the metric, the k limit
+static int fknn_args(zh_index *ix, uint64_t n, size_t k, int metric, int mode, const void *ids, const void *keys, const void *counts, const char *who) {
+    if (!ix || (n && (!counts || (k && (!ids || !keys))))) return fail(ZH_EINVAL, "%s: null argument", who);
+    const int rc = check_metric(metric, mode);
+    if (rc) return rc;
+    if (k > ZH_MAX_TOPK - 1) return fail(ZH_ELIMIT, "%s: k %zu > ZH_MAX_TOPK - 1 (%u)", who, k, ZH_MAX_TOPK - 1);
+    return ZH_OK;
+}
+
+// the state checks both entry points share once the index is locked and the range has been judged (n > 0, k > 0)
+static int fknn_state(zh_index *ix, const char *who) {
+    if (ix->broken) return fail(ZH_ESTATE, "%s: an incremental add failed: the trees are stale until zh_index_build", who);
+    if (!ix->n_trees || ix->h_roots.empty()) return fail(ZH_ESTATE, "%s: the index has no trees (zh_index_build)", who);
+    return ZH_OK;
+}
+
+extern "C" int zh_knn_graph_forest_device(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *d_out_ids,
+                                          uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
+    int rc = fknn_args(ix, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_forest_device");
+    if (rc) return rc;
+    if (n == 0) return ZH_OK;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph_forest_device"))) return rc;
+    FknnScratchGuard guard{ix};
+    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    zh_knn_forest_info inf{};
+    inf.path = 1;
+    FknnRun run;
+    if (k == 0) {
+        HIPCHK(hipMemsetAsync(d_out_counts, 0, n * 4, s));
+    } else {
+        if ((rc = fknn_state(ix, "zh_knn_graph_forest_device")) || (rc = fknn_setup(ix, (uint32_t)k, metric, mode, s, &run))) return rc;
+        if (run.path2) inf.path = 2;
+        if ((rc = fknn_slab(ix, run, first_row, n, (uint32_t)k, metric, mode, d_out_ids, d_out_keys, d_out_counts, s, &inf))) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return fknn_finish(ix, (uint32_t)k, inf, s);
+}
+
+extern "C" int zh_knn_graph_forest(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys,
+                                   uint32_t *out_counts) {
+    int rc = fknn_args(ix, n, k, metric, mode, out_ids, out_keys, out_counts, "zh_knn_graph_forest");
+    if (rc) return rc;
+    if (n == 0) return ZH_OK;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph_forest"))) return rc;
+    FknnScratchGuard guard{ix};
+    const hipStream_t s = ix->stream;
+    zh_knn_forest_info inf{};
+    inf.path = 1;
+    FknnRun run;
+    if (k == 0) {
+        memset(out_counts, 0, n * 4);
+    } else {
+        if ((rc = fknn_state(ix, "zh_knn_graph_forest")) || (rc = fknn_setup(ix, (uint32_t)k, metric, mode, s, &run))) return rc;
+        if (run.path2) inf.path = 2;
+        // the staged sub-slab: large, because path 2 serves a slab at the cost of every leaf that holds one of its rows
+        const uint64_t host_slab = std::max<uint64_t>(ZH_FKNN_SLAB, (uint64_t(1) << 25) / k / ZH_FKNN_SLAB * ZH_FKNN_SLAB), m_max = std::min(n, host_slab);
+        if ((rc = ix->kn_oids.ensure(m_max * k * 8)) || (rc = ix->kn_okeys.ensure(m_max * k * 8)) || (rc = ix->kn_ocounts.ensure(m_max * 4))) return rc;
+        for (uint64_t r0 = 0; r0 < n; r0 += host_slab) {
+            const uint64_t m = std::min(host_slab, n - r0);
+            if ((rc = fknn_slab(ix, run, first_row + r0, m, (uint32_t)k, metric, mode, ix->kn_oids.as<uint64_t>(), ix->kn_okeys.as<uint64_t>(),
+                                ix->kn_ocounts.as<uint32_t>(), s, &inf)))
+                return rc;
+            HIPCHK(hipMemcpyAsync(out_ids + r0 * k, ix->kn_oids.p, m * k * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_keys + r0 * k, ix->kn_okeys.p, m * k * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_counts + r0, ix->kn_ocounts.p, m * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+    }
+    return fknn_finish(ix, (uint32_t)k, inf, s);
+}
+
+extern "C" int zh_knn_graph_forest_info(const zh_index *ix, zh_knn_forest_info *out) {
+    if (!ix || !out) return fail(ZH_EINVAL, "zh_knn_graph_forest_info: null argument");
+    zh_index *m = const_cast<zh_index *>(ix);
+    std::lock_guard<std::mutex> lk(m->stats_mu);
+    *out = m->fk_info;
     return ZH_OK;
 }
 

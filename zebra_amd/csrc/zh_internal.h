@@ -400,6 +400,62 @@ hipError_t zh_launch_knn_mfma(uint32_t d, int metric, int mode, const ZhExact2 &
 hipError_t zh_launch_knn_emit(const uint64_t *dInIds, const uint64_t *dInKeys, const uint32_t *dInCounts, uint32_t w, const uint32_t *dRows, uint32_t B,
                               uint64_t id_base, uint64_t first_row, uint32_t k, uint64_t *dOutIds, uint64_t *dOutKeys, uint32_t *dOutCounts, hipStream_t s);
 
+// ---- the forest k-NN graph (zh_fknn.hip): each row's k nearest rows among its leaf-mates over all trees
+#define ZH_FKNN_SLAB 65536u       // lines of a sub-slab: the unit of the row -> leaf table, of path 1 and of a redo
+#define ZH_FKNN_HELD_ROWS 4096u   // path 2: members of one leaf a segment holds at most; held lines of a batch (256 tiles)
+#define ZH_FKNN_COL_TILES 2048u   // path 2: column tiles a batch gathers (more only for ONE leaf that is longer)
+#define ZH_FKNN_CHUNK 64u         // path 2: column tiles one block walks at most
+static_assert(ZH_FKNN_HELD_ROWS % 64 == 0, "a held block is four tiles of 16 lines");
+// one segment of a path-2 batch: members [held_off, held_off + held_len) of leaf_ids (one leaf's, or a window of them) as candidates for held rows,
+// against the whole leaf as columns
+struct ZhFknnSeg {
+    uint32_t col0, ct;             // the leaf's column tiles in the batch's column scratch
+    uint32_t held_off, held_len;   // the window of leaf_ids the held rows come from
+    uint32_t line0, held_tiles;    // its lines in the batch: [line0, line0 + 16 * held_tiles), line0 % 16 == 0, held_tiles = ceil(held_len / 16)
+    uint32_t first_block, pad;     // blocks of the launch before this segment's ceil(held_tiles / 4) * ceil(ct / ch)
+};
+// dRl[(r - r0) * T + t] = {offset into leaf_ids, length} of the leaf of row r in tree t, {UINT32_MAX, UINT32_MAX} for none; r in [r0, r0 + m)
+hipError_t zh_launch_fknn_rowleaf(const int4 *dNodePack, const uint32_t *dNodeTree, uint32_t n_nodes, const uint32_t *dLeafIds, uint32_t T, uint64_t r0,
+                                  uint32_t m, uint2 *dRl, hipStream_t s);
+// dRows = the sub-slab's rows that some tree holds, ascending (dExcl[m] = their number; dFlag m, dExcl m + 1, dScanTmp m / 1024 + 2 words);
+// *dPairs += the sum over them and over their trees of (leaf length - 1)
+hipError_t zh_launch_fknn_lines(const uint2 *dRl, uint32_t T, uint64_t r0, uint32_t m, uint32_t *dFlag, uint32_t *dExcl, uint32_t *dScanTmp, uint32_t *dRows,
+                                unsigned long long *dPairs, hipStream_t s);
+// path 1: visit b * T + t = line dRows[b]'s leaf in tree t; sizes first (for the two exclusive scans), then the visits, their one-member groups,
+// the groups' flat row offsets and the candidate bases (B * T + 1 entries), w = entries a visit takes at most
+hipError_t zh_launch_fknn_visit_sizes(const uint2 *dRl, uint32_t T, uint64_t r0, const uint32_t *dRows, uint32_t B, uint32_t w, uint32_t *dLens,
+                                      uint32_t *dTakes, hipStream_t s);
+hipError_t zh_launch_fknn_visits(const uint2 *dRl, uint32_t T, uint64_t r0, const uint32_t *dRows, uint32_t B, uint32_t w, const uint32_t *dRowBase,
+                                 const uint32_t *dCandBase, ZhVisit *dVisits, ZhGroup *dGroups, uint64_t *dGroupRowOff, uint64_t *dCandBase64, hipStream_t s);
+// path 2.  dPos[row] = the row's position in the fp16 copy under a row order
+hipError_t zh_launch_fknn_rowpos(const uint32_t *dPerm, uint64_t perm_rows, uint64_t n_rows, uint32_t *dPos, hipStream_t s);
+// dCRow[16 c + j] = leaf_ids[dSrc[c].x + j] for j < dSrc[c].y, else UINT32_MAX
+hipError_t zh_launch_fknn_cols(const uint2 *dSrc, uint32_t n_tiles, const uint32_t *dLeafIds, uint64_t n_rows, uint32_t *dCRow, hipStream_t s);
+// per segment its members inside [first_row, first_row + n) as held rows (dHRow, UINT32_MAX past them), dHeld[seg] their number; *dTiles += the
+// 16 x 16 tile products its blocks issue
+hipError_t zh_launch_fknn_held(const ZhFknnSeg *dSegs, uint32_t n_segs, const uint32_t *dLeafIds, uint64_t first_row, uint64_t n, uint32_t *dHRow,
+                               uint32_t *dHeld, unsigned long long *dTiles, hipStream_t s);
+// the tiles of a row list (16 n_tiles entries, UINT32_MAX = none) out of the fp16 copy in the MFMA operand's order, their rowMeta, and (dQm not null)
+// the rows as approx_interval's queries
+hipError_t zh_launch_fknn_gather(uint32_t d, const void *dXh, const float2 *dRowMeta, const uint32_t *dPos, const uint32_t *dRows, uint32_t n_tiles, float rho,
+                                 void *dA, float2 *dMeta, float4 *dQm, hipStream_t s);
+// per held line: dQRow = its row (0 for none), dMaxK = the k-th key of its running answer (the outputs), all ones while that holds fewer than k
+hipError_t zh_launch_fknn_bound(const uint32_t *dHRow, uint32_t B, uint64_t first_row, uint32_t k, const uint64_t *dOutKeys, const uint32_t *dOutCounts,
+                                uint32_t *dQRow, uint64_t *dMaxK, hipStream_t s);
+// every segment of a batch in one launch of n_blocks blocks; lists per held LINE in e (stride e.cap, at most lim entries each); of e it reads Kc, rho
+// and the lists
+hipError_t zh_launch_fknn_mfma(uint32_t d, int metric, int mode, const ZhFknnSeg *dSegs, uint32_t n_segs, uint32_t n_blocks, const uint32_t *dHeld, uint32_t ch,
+                               const void *dCA, const float4 *dCQm, const uint32_t *dCRow, const void *dHA, const float2 *dHMeta, const uint32_t *dHRow,
+                               const ZhExact2 &e, uint32_t lim, hipStream_t s);
+// the lines' running answers appended to their survivors' candidate slots; the batch's answer [B][k] written back as the running answer (an entry
+// whose id is id_base + UINT32_MAX is final_kernel's reading of an empty slot: not counted)
+hipError_t zh_launch_fknn_seed(const uint32_t *dHRow, uint32_t B, uint64_t first_row, uint64_t id_base, uint32_t k, const uint64_t *dOutIds,
+                               const uint64_t *dOutKeys, const uint32_t *dOutCounts, const ZhExact2 &e, uint64_t *dCKeys, uint32_t *dCIds, hipStream_t s);
+hipError_t zh_launch_fknn_store(const uint32_t *dHRow, uint32_t B, uint64_t first_row, uint64_t id_base, uint32_t k, const uint64_t *dInIds,
+                                const uint64_t *dInKeys, uint64_t *dOutIds, uint64_t *dOutKeys, uint32_t *dOutCounts, const uint32_t *dOver, hipStream_t s);
+// dRedo[(row - first_row) / ZH_FKNN_SLAB] = 1 for every held row of a batch whose lists ran over
+hipError_t zh_launch_fknn_mark(const uint32_t *dHRow, uint32_t B, uint64_t first_row, uint32_t *dRedo, hipStream_t s);
+
 // ---- launchers (zh_score.hip): every sign of a forest built from stored rows, from N row scores per query --------
 // Prefilter (zh_search.hip, "Prefilter"): a batch hashed from row scores picks the rows that can be among a pair's k best from
 // those scores; only they are scored with the reference's arithmetic.  Lists: one per (tree, query), `cap` slots, list (t, b) at

@@ -546,6 +546,32 @@ class LSHIndex:
         check(lib().zh_knn_graph_info(self._h, C.byref(info)))
         return info.as_dict()
 
+    def knn_graph_forest(self, k, metric, first_row=0, n=None):
+        """FOREST k-NN graph of the slab of stored rows [first_row, first_row + n) (default: from first_row to the last stored row): line i holds the
+        first k by (key, id) of the rows that share a leaf with stored row first_row + i in some tree (get_forest()'s leaf_ids), the row itself
+        excluded -- knn_graph's keys, ids and layout, exact arithmetic on an approximate candidate set.  -> (ids [n,k] u64, keys [n,k] u64,
+        counts [n] u32); counts = min(k, leaf-mates), 0 for a removed row and for a row no tree holds (appended since the last build); entries
+        past the count are 2^64-1.  Needs a built forest."""
+        stored = self.stored_rows()
+        n = max(stored - first_row, 0) if n is None else int(n)
+        ids = np.empty((n, k), np.uint64)
+        keys = np.empty((n, k), np.uint64)
+        counts = np.zeros(n, np.uint32)
+        check(lib().zh_knn_graph_forest(self._h, int(first_row), n, k, metric.metric, metric.mode, _p(ids), _p(keys), _p(counts)))
+        return ids, keys, counts
+
+    def knn_graph_forest_device(self, k, metric, first_row, n, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream=None):
+        """knn_graph_forest with the outputs ([n,k] u64 twice, [n] u32) already in device memory (raw pointers, e.g. torch .data_ptr())."""
+        check(lib().zh_knn_graph_forest_device(self._h, int(first_row), int(n), k, metric.metric, metric.mode, d_ids_ptr, d_keys_ptr, d_counts_ptr,
+                                               stream))
+
+    def knn_forest_info(self):
+        """what the most recent forest k-NN graph call on this index did (zh_knn_graph_forest_info): rows_live, lines, k, path, trees, pairs,
+        survivors, redone, launches, tiles"""
+        info = _ffi.KnnForestInfo()
+        check(lib().zh_knn_graph_forest_info(self._h, C.byref(info)))
+        return info.as_dict()
+
     def deduplicate_within(self, radius, metric):
         """near-duplicate removal: rows are taken in ascending id, and row b is removed exactly when some KEPT row a < b forms a joined pair
         with it (self_join at `radius`).  Decided on the host from the sorted pair list, then passed to remove -> the removed ids, ascending."""
@@ -861,7 +887,16 @@ class Database:
     def knn_graph(self, k):
         """every record's k nearest other records (LSHIndex.knn_graph: exact) -> {document: [(neighbour document, distance)], nearest first},
         one entry per live record.  The distance is the number the key holds, as in near_duplicates."""
-        ids, keys, counts = self.index.knn_graph(k, self.metric)
+        return self._graph_documents(*self.index.knn_graph(k, self.metric))
+
+    def knn_graph_forest(self, k):
+        """every record's k nearest records among those that share a leaf of the forest with it (LSHIndex.knn_graph_forest) -> what knn_graph
+        returns"""
+        if self.index.no_vectors():
+            return {}
+        return self._graph_documents(*self.index.knn_graph_forest(k, self.metric))
+
+    def _graph_documents(self, ids, keys, counts):
         dist = self._key_numbers(np.ascontiguousarray(keys)).reshape(keys.shape)
         base = self.index.id_base
         out = {}

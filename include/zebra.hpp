@@ -366,6 +366,25 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_knn_graph_forest_info(h_.get(), &info));
         return info;
     }
+    // the forest self-join (zh_self_join_forest): self_join's pairs among the rows that share a leaf in at least one tree, each pair once; exact
+    // keys on an approximate candidate set.  One call that counts, one that fetches.  Needs a built forest.
+    template <class Met>
+    std::vector<JoinedPair> self_join_forest(DistanceUnit max_key, const Met &metric) const {
+        std::uint64_t total = 0;
+        const int rc = zh_self_join_forest(h_.get(), max_key, Met::metric, metric.mode(), 0, nullptr, nullptr, nullptr, &total);
+        if (rc != ZH_ELIMIT) check(rc);
+        std::vector<Id> a(total + 1), b(total + 1);
+        std::vector<DistanceUnit> keys(total + 1);
+        if (total) check(zh_self_join_forest(h_.get(), max_key, Met::metric, metric.mode(), total, a.data(), b.data(), keys.data(), &total));
+        std::vector<JoinedPair> out(total);
+        for (std::uint64_t i = 0; i < total; i++) out[i] = JoinedPair{a[i], b[i], keys[i]};
+        return out;
+    }
+    zh_join_forest_info join_forest_info() const {
+        zh_join_forest_info info{};
+        check(zh_self_join_forest_info(h_.get(), &info));
+        return info;
+    }
     zh_index *handle() const { return h_.get(); }
 
   private:

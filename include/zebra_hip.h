@@ -30,6 +30,8 @@
  *   zh_self_join[_device]                (new) every pair of live rows whose key is at or below one threshold key, each pair once
  *   zh_knn_graph[_device]                (new) every live row's exact k nearest OTHER live rows, slab by slab
  *   zh_knn_graph_forest[_device]         (new) every row's k nearest rows among its leaf-mates in the forest: exact keys, approximate candidates
+ *   zh_self_join_forest[_device]         (new) every pair of leaf-mates whose key is at or below one threshold key, each pair once: exact keys,
+ *                                        approximate candidates
  *   zh_index_save / zh_index_load        (new) a snapshot of an index in ONE file of this library's own format (the reference persists through
  *                                        fjall, lsh.rs:62-120, whose files are not read here): rows, removals, forest and the planes' sample rows
  *
@@ -583,6 +585,61 @@ typedef struct zh_knn_forest_info {  /* the most recent zh_knn_graph_forest* cal
     uint64_t tiles;       /* path 2: 16 x 16 tile products issued, from the launch geometry (held tiles in use x the leaf's column tiles); 0 on path 1 */
 } zh_knn_forest_info;
 ZH_API int zh_knn_graph_forest_info(const zh_index *idx, zh_knn_forest_info *out);
+
+/* ---- forest self-join (new): all near-duplicate pairs AMONG LEAF-MATES ---------------------------------------------------------------------
+ * zh_self_join multiplies every tile of the table by every tile at or above it; this call multiplies a leaf only by itself.  Arguments, key,
+ * orientation, threshold, output arrays, order, ids and the capacity contract are zh_self_join's.  Let
+ *   F = the unordered pairs {a, b} of distinct stored rows that are members of the SAME leaf in at least one tree,
+ * with membership as zh_index_get_forest's leaf_ids has it at the time of the call: removed rows have left every tree, rows appended since the
+ * last build are in none.  The answer is every pair of F whose key is <= max_key, EACH PAIR ONCE however many trees put the two rows together:
+ * three parallel arrays out_a, out_b, out_keys of *out_total entries, a < b by row number, ids = id_base + row, ascending by (a, key, b).  The
+ * key of (a, b) is the key zh_distance_batch gives for stored row b against a query equal to the f32 values of row a.  ONE threshold key per
+ * call (zebra_amd.radius_key); UINT64_MAX returns all of F; the parity cosine key's unsigned order is the definition.
+ * Only the candidate set is approximate: ids, keys, order and total are bit for bit what that definition gives with zh_distance_batch's keys, for
+ * all 13 metric / mode / power combinations, whatever the path, the scan's row order or the run.  On a forest of ONE tree whose root is a leaf
+ * the answer is zh_self_join's; for any forest it is the subset of zh_self_join's pairs that lie in F, and the quotient of the two totals is the
+ * pair recall of the forest setting.
+ * More pairs than `capacity`: ZH_ELIMIT with *out_total EXACT (a pair that several trees repeat is counted once) and the arrays unspecified;
+ * capacity = 0 with NULL arrays counts only.  A NULL index or out_total, NULL arrays with capacity > 0 and an unknown metric are refused before
+ * any device is touched; after them an index without live rows has no pair (*out_total = 0, ZH_OK), and one with live rows and no trees, or
+ * with trees an interrupted insert left stale, is ZH_ESTATE, as for zh_knn_graph_forest.  A forest whose leaves all hold fewer than two rows
+ * gives *out_total = 0 and ZH_OK.  Locking as zh_self_join_device;
+ * zh_stats_t, the six sibling info structs and the cached live-row views are left alone: zh_self_join_forest_info describes the most recent call.
+ * Each pair once: the call builds leaf_of[row][tree], the row's leaf in that tree, on the device, and a pair met in tree t is kept only if the
+ * two rows share no leaf in any tree t' < t -- the first tree that puts them together owns the pair.  The rule is paid only by
+ * candidates (path 2) or by keys already at or below the threshold (path 1).
+ * Both paths work tree after tree into ONE hit pool.  Path 1 (every metric, dimension and leaf shape): the rows a tree holds are lines, each
+ * visits its own leaf in that tree; the leaf-major f32 sweep keys the leaf's rows against the line and the keys <= max_key whose row number is
+ * above the line's and that pass the rule are hits.  Path 2 (ZH_L2SQ, ZH_L2, ZH_COSINE at dim 256 / 384 / 512 / 768 / 1024, the fp16 row copy
+ * present, zh_options.max_node_size >= 64): a tree's non-empty leaves are cut into batches of at most 2048 tiles of 16 rows (or one longer leaf
+ * alone), a batch is gathered once out of the copy and ONE launch multiplies every leaf of it by itself on the matrix cores, the tiles on or
+ * above each leaf's diagonal only, for an interval per pair; pairs whose interval reaches down to the threshold are candidates, and those the
+ * rule leaves get the canonical key.  A batch whose candidates outgrow their pool has nothing counted and its leaves are answered by path 1
+ * (`redone`).  ZH_FJOIN_PATH=1 in the environment (read per call) forces path 1; ZH_FJOIN_CAND_CAP=n (read per call; tests) sets the candidate
+ * pool's slots per batch.
+ * Device scratch is per call and released before return: 4 bytes per (stored row, tree) of leaf_of -- 4 N T, 600 MB at 10M rows x 15 trees, not
+ * chunked -- and 4 bytes per tree node; with P = min(capacity, the forest's leaf pairs) hit slots 32 P bytes of hit pool and sort buffers + the
+ * sort's temporary storage; path 2 per batch 2 dim + 28 bytes per gathered row (at most max(32768, the longest leaf padded to tiles)), 16 bytes
+ * per 64 gathered rows of segments and 8 bytes per candidate slot (max(1.25 x the capacity left, 256 per gathered row), never more than the
+ * batch's leaf pairs), plus 4 bytes per stored row under a scan order that is not id order; path 1 per panel of at most 16384 lines 4 dim + 24
+ * bytes per line, 56 bytes per 4 lines and 8 bytes per key of at most max(2^25, the longest leaf) keys; for the host call 24 bytes per pair. */
+ZH_API int zh_self_join_forest(zh_index *idx, uint64_t max_key, int metric, int cosine_mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b,
+                               uint64_t *out_keys, uint64_t *out_total);
+/* The same with every output (out_total included) in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_self_join_forest_device(zh_index *idx, uint64_t max_key, int metric, int cosine_mode, uint64_t capacity, uint64_t *d_out_a,
+                                      uint64_t *d_out_b, uint64_t *d_out_keys, uint64_t *d_out_total, void *stream);
+typedef struct zh_join_forest_info {  /* the most recent zh_self_join_forest* call on this index */
+    uint64_t rows_live;   /* live rows of the index */
+    uint32_t trees;       /* trees of the forest */
+    uint32_t path;        /* 1: the f32 leaf sweep, each line over its own leaf; 2: matrix-core intervals leaf by leaf, canonical keys for candidates */
+    uint64_t leaf_pairs;  /* sum over all trees' leaves of len (len - 1) / 2, counted from the forest on the device: repeats across trees included */
+    uint64_t pairs;       /* pairs within the threshold, each once (exact whatever the capacity) */
+    uint64_t candidates;  /* path 2: pairs that got the canonical key, over the batches path 2 completed */
+    uint64_t launches;    /* launches of the scan (panels swept on path 1, one matrix-core launch per batch on path 2) */
+    uint64_t tiles;       /* path 2: 16 x 16 tile products issued, from the launch geometry (t (t + 1) / 2 per leaf of t tiles); 0 on path 1 */
+    uint32_t redone;      /* path-2 batches whose candidate pool ran over and were answered by path 1 */
+} zh_join_forest_info;
+ZH_API int zh_self_join_forest_info(const zh_index *idx, zh_join_forest_info *out);
 
 /* Pipelined form of zh_search_batch_device (new; the reference has one blocking search per query): a context
  * is one in-flight batch with its own scratch.  The context calls do NOT take the index's internal lock (the blocking

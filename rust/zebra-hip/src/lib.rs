@@ -162,6 +162,20 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_join_forest_info {
+        pub rows_live: u64,
+        pub trees: u32,
+        pub path: u32,
+        pub leaf_pairs: u64,
+        pub pairs: u64,
+        pub candidates: u64,
+        pub launches: u64,
+        pub tiles: u64,
+        pub redone: u32,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_filtered_info {
         pub batch: u64,
         pub rows_live: u64,
@@ -276,6 +290,11 @@ pub mod ffi {
         pub fn zh_knn_graph_forest_device(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int,
                                           d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_knn_graph_forest_info(idx: *const zh_index, out: *mut zh_knn_forest_info) -> c_int;
+        pub fn zh_self_join_forest(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, out_a: *mut u64,
+                                   out_b: *mut u64, out_keys: *mut u64, out_total: *mut u64) -> c_int;
+        pub fn zh_self_join_forest_device(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, d_out_a: *mut u64,
+                                          d_out_b: *mut u64, d_out_keys: *mut u64, d_out_total: *mut u64, stream: *mut c_void) -> c_int;
+        pub fn zh_self_join_forest_info(idx: *const zh_index, out: *mut zh_join_forest_info) -> c_int;
         pub fn zh_search_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
                                       d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_distance_pair(metric: c_int, cosine_mode: c_int, a: *const f32, b: *const f32, dim: usize, out_key: *mut u64,
@@ -688,6 +707,40 @@ impl<const N: usize> LSHIndex<N> {
             first += n;
         }
         Ok(out)
+    }
+
+    /// (new) the forest self-join (zh_self_join_forest): self_join's pairs among the vectors that share a leaf in at least one tree, each pair
+    /// once, ascending by (a, key, b); exact keys on an approximate candidate set.  One call that counts (capacity 0), one that fetches.
+    pub fn self_join_forest<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        max_key: DistanceUnit,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<(Uuid, Uuid, DistanceUnit)>> {
+        let t = self.ids.read().unwrap();
+        let mut total = 0u64;
+        let rc = unsafe {
+            ffi::zh_self_join_forest(self.hip.0, max_key, Met::METRIC, metric.param(), 0, std::ptr::null_mut(), std::ptr::null_mut(),
+                                     std::ptr::null_mut(), &mut total)
+        };
+        if rc != -5 {
+            check(rc)?;
+        }
+        let n = total as usize + 1;
+        let (mut a, mut b, mut keys) = (vec![0u64; n], vec![0u64; n], vec![0u64; n]);
+        if total > 0 {
+            check(unsafe {
+                ffi::zh_self_join_forest(self.hip.0, max_key, Met::METRIC, metric.param(), total, a.as_mut_ptr(), b.as_mut_ptr(), keys.as_mut_ptr(),
+                                         &mut total)
+            })?;
+        }
+        Ok((0..total as usize).map(|i| (t.of_row[a[i] as usize], t.of_row[b[i] as usize], keys[i])).collect())
+    }
+
+    /// what the most recent forest self-join did (zh_self_join_forest_info)
+    pub fn join_forest_info(&self) -> anyhow::Result<ffi::zh_join_forest_info> {
+        let mut info = ffi::zh_join_forest_info::default();
+        check(unsafe { ffi::zh_self_join_forest_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// what the most recent forest k-NN graph call did (zh_knn_graph_forest_info)

@@ -128,6 +128,14 @@ class KnnForestInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class JoinForestInfo(C.Structure):
+    _fields_ = [("rows_live", C.c_uint64), ("trees", C.c_uint32), ("path", C.c_uint32), ("leaf_pairs", C.c_uint64), ("pairs", C.c_uint64),
+                ("candidates", C.c_uint64), ("launches", C.c_uint64), ("tiles", C.c_uint64), ("redone", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CompactInfo(C.Structure):
     _fields_ = [("rows_before", C.c_uint64), ("rows_after", C.c_uint64), ("rows_moved", C.c_uint64), ("bytes_moved", C.c_uint64),
                 ("scratch_bytes", C.c_uint64), ("capacity_rows", C.c_uint64), ("copy_bytes_released", C.c_uint64), ("ms", C.c_double)]
@@ -203,6 +211,9 @@ SYMBOLS = [
     ("zh_knn_graph_forest", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_knn_graph_forest_device", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_knn_graph_forest_info", _i, [_vp, _vp]),
+    ("zh_self_join_forest", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
+    ("zh_self_join_forest_device", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
+    ("zh_self_join_forest_info", _i, [_vp, _vp]),
     ("zh_search_ctx_create", _i, [_vp, _vp]),
     ("zh_search_ctx_destroy", None, [_vp]),
     ("zh_search_begin", _i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),

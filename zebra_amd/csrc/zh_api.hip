@@ -283,6 +283,10 @@ struct zh_index {
     DevBuf fk_ntree, fk_rl, fk_flag, fk_excl, fk_tmp, fk_rows, fk_ctr, fk_lens, fk_takes, fk_rbase, fk_cbase, fk_groups, fk_groff, fk_segs, fk_colsrc, fk_crow,
         fk_hrow, fk_held, fk_CA, fk_cmeta, fk_cqm, fk_HA, fk_hmeta, fk_qrow, fk_maxk, fk_redo, fk_pos;
     zh_knn_forest_info fk_info{};  // (stats_mu)
+    // the forest self-join's per-call scratch beside the self-join's and the forest graph's (all released before the call returns): leaf_of, a path-1
+    // panel's pieces and per-line {leaf, key offset}, path 2's segments and candidate pool
+    DevBuf fj_leafof, fj_pieces, fj_linel, fj_linek, fj_segs, fj_cand;
+    zh_join_forest_info fj_info{};  // (stats_mu)
 
     bool broken = false;  // an incremental add failed half way: trees are stale until zh_index_build
     bool rows_torn = false;  // ... or a compaction failed after rows had begun to move (set with broken): the TABLE is inconsistent until zh_index_clear
@@ -4969,6 +4973,352 @@ extern "C" int zh_knn_graph_forest_info(const zh_index *ix, zh_knn_forest_info *
     zh_index *m = const_cast<zh_index *>(ix);
     std::lock_guard<std::mutex> lk(m->stats_mu);
     *out = m->fk_info;
+    return ZH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// forest self-join (zh_fjoin.hip): every pair of leaf-mates whose key is <= one threshold key, each pair once.  DESIGN.md s18
+// ------------------------------------------------------------------------------------------------
+#define ZH_FJOIN_CAND_FLOOR 256u  // path 2: candidate slots per gathered row of a batch that are there whatever the capacity
+
+static void fjoin_release_scratch(zh_index *ix) {
+    join_release_scratch(ix);
+    fknn_release_scratch(ix);
+    DevBuf *bs[] = {&ix->fj_leafof, &ix->fj_pieces, &ix->fj_linel, &ix->fj_linek, &ix->fj_segs, &ix->fj_cand};
+    for (DevBuf *b : bs) b->release();
+}
+struct FjoinScratchGuard {
+    zh_index *ix;
+    ~FjoinScratchGuard() { fjoin_release_scratch(ix); }
+};
+
+struct FjoinRun {  // what a call settles once
+    uint32_t T = 0;
+    int metric = 0, mode = 0;
+    uint64_t max_key = 0, pool_cap = 0;
+    bool path2 = false;
+    const void *Xh = nullptr;
+    const float2 *rowMeta = nullptr;
+    const uint32_t *pos = nullptr;  // row -> position under a row order, else null
+    float rho = 0.f, Kc = 0.f;
+    bool env_cand = false;          // ZH_FJOIN_CAND_CAP is set ...
+    uint64_t env_cand_cap = 0;      // ... to this
+    std::vector<std::vector<uint2>> leaves;  // per tree the non-empty leaves {offset into leaf_ids, length}, in the host mirror's order
+};
+
+// jn_ctr: {hits, the batch's candidates, the forest's leaf pairs, candidates that got a key}
+static int fjoin_setup(zh_index *ix, int metric, int mode, hipStream_t s, FjoinRun *run) {
+    const uint32_t d = ix->opt.dim, T = (uint32_t)ix->h_roots.size();
+    const size_t nn = ix->h_plane.size();
+    run->T = T;
+    const char *env_p = getenv("ZH_FJOIN_PATH");
+    bool want2 = !(env_p && atoi(env_p) == 1) && zh_exact_mfma_supported(d, metric) && ix->opt.max_node_size >= 64;
+    int rc;
+    if (want2) {
+        std::lock_guard<std::mutex> lb(ix->blk_mu);
+        bool ok = false;
+        if ((rc = ensure_row_half(ix, &ok))) return rc;
+        if (!ok || !ix->row_half.p) want2 = false;  // no copy (no room, or the per-row scales alone): path 1
+        else {
+            run->Xh = ix->row_half.p; run->rowMeta = ix->row_meta.as<float2>(); run->rho = ix->row_rho;
+            if (ix->perm_rows) {
+                if ((rc = ix->fk_pos.ensure(ix->n_rows * 4))) return rc;
+                HIPCHK(zh_launch_fknn_rowpos(ix->scan_perm.as<uint32_t>(), ix->perm_rows, ix->n_rows, ix->fk_pos.as<uint32_t>(), s));
+                HIPCHK(hipStreamSynchronize(s));  // (scan_perm is read under blk_mu only)
+                run->pos = ix->fk_pos.as<uint32_t>();
+            }
+        }
+    }
+    std::vector<uint32_t> node_tree(std::max<size_t>(nn, 1), 0xFFFFFFFFu), st;
+    run->leaves.resize(T);
+    for (uint32_t t = 0; t < T; t++) {
+        st.assign(1, ix->h_roots[t]);
+        while (!st.empty()) {
+            const uint32_t nd = st.back(); st.pop_back();
+            node_tree[nd] = t;
+            if (ix->h_plane[nd] >= 0) { st.push_back((uint32_t)ix->h_right[nd]); st.push_back((uint32_t)ix->h_left[nd]); }
+            else if (ix->h_right[nd] > 0) run->leaves[t].push_back(make_uint2((uint32_t)ix->h_left[nd], (uint32_t)ix->h_right[nd]));
+        }
+    }
+    if ((rc = ix->fk_ntree.ensure(node_tree.size() * 4)) || (rc = ix->jn_ctr.ensure(32)) ||
+        (rc = ix->fj_leafof.ensure(std::max<size_t>((size_t)ix->n_rows * T * 4, 4))))
+        return rc;
+    HIPCHK(hipMemcpyAsync(ix->fk_ntree.p, node_tree.data(), node_tree.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(ix->jn_ctr.p, 0, 32, s));
+    HIPCHK(zh_launch_fjoin_rowleaf(ix->node_pack.as<int4>(), ix->fk_ntree.as<uint32_t>(), ix->n_nodes, ix->leaf_ids.as<uint32_t>(), T, ix->n_rows,
+                                   ix->fj_leafof.as<uint32_t>(), ix->jn_ctr.as<unsigned long long>() + 2, s));
+    HIPCHK(hipStreamSynchronize(s));  // (node_tree is this frame's)
+    const char *env_c = getenv("ZH_FJOIN_CAND_CAP");
+    if (env_c && atoll(env_c) > 0) { run->env_cand = true; run->env_cand_cap = (uint64_t)atoll(env_c); }
+    if (want2) { run->Kc = zh_approx_bound(metric, d, 1); run->path2 = true; }
+    return ZH_OK;
+}
+
+// Path 1 of one panel: its pieces' lines against their leaves.
+static int fjoin_panel1(zh_index *ix, const FjoinRun &run, uint32_t t, const std::vector<ZhFjoinPiece> &pieces, uint32_t lines, uint32_t groups, uint64_t flat,
+                        uint64_t keys, hipStream_t s, zh_join_forest_info *inf) {
+    const uint32_t d = ix->opt.dim;
+    int rc;
+    if ((rc = ix->fj_pieces.ensure(pieces.size() * sizeof(ZhFjoinPiece))) || (rc = ix->fk_rows.ensure((size_t)lines * 4)) ||
+        (rc = ix->fj_linel.ensure((size_t)lines * 8)) || (rc = ix->fj_linek.ensure((size_t)lines * 8)) ||
+        (rc = ix->fk_groups.ensure((size_t)groups * sizeof(ZhGroup))) || (rc = ix->fk_groff.ensure((size_t)groups * 8)) ||
+        (rc = ix->ex_Q.ensure((size_t)lines * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)lines * 4)) || (rc = ix->ex_keys.ensure(std::max<uint64_t>(keys, 1) * 8)))
+        return rc;
+    const int param = run.metric == ZH_COSINE ? run.mode : ((run.metric == ZH_MINKOWSKI || run.metric == ZH_PNORM) ? run.mode : 0);
+    HIPCHK(hipMemcpyAsync(ix->fj_pieces.p, pieces.data(), pieces.size() * sizeof(ZhFjoinPiece), hipMemcpyHostToDevice, s));
+    HIPCHK(zh_launch_fjoin_groups(ix->fj_pieces.as<ZhFjoinPiece>(), (uint32_t)pieces.size(), groups, ix->leaf_ids.as<uint32_t>(), ix->n_rows,
+                                  ix->fk_rows.as<uint32_t>(), ix->fj_linel.as<uint2>(), ix->fj_linek.as<uint64_t>(), ix->fk_groups.as<ZhGroup>(),
+                                  ix->fk_groff.as<uint64_t>(), s));
+    HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, ix->fk_rows.as<uint32_t>(), lines, ix->ex_Q.as<float>(), s));
+    HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), lines, d, ix->ex_QQ.as<float>(), s));
+    HIPCHK(zh_launch_sweep(ix->X.as<float>(), d, ix->ex_Q.as<float>(), ix->ex_QQ.as<float>(), ix->fk_groups.as<ZhGroup>(), ix->fk_groff.as<uint64_t>(), groups,
+                           nullptr, ix->leaf_ids.as<uint32_t>(), flat, run.metric, param, ix->ex_keys.as<uint64_t>(), s));
+    HIPCHK(zh_launch_fjoin_collect(ix->ex_keys.as<uint64_t>(), ix->fk_rows.as<uint32_t>(), ix->fj_linel.as<uint2>(), ix->fj_linek.as<uint64_t>(), lines,
+                                   ix->leaf_ids.as<uint32_t>(), ix->n_rows, ix->fj_leafof.as<uint32_t>(), run.T, t, run.max_key,
+                                   ix->jn_ctr.as<unsigned long long>(), ix->jn_pv0.as<uint64_t>(), ix->jn_pk0.as<uint64_t>(), run.pool_cap, s));
+    HIPCHK(hipStreamSynchronize(s));  // (pieces is the caller's)
+    inf->launches++;
+    return ZH_OK;
+}
+
+// Path 1 for n leaves of tree t: every member of a leaf of two or more rows is a line that visits that leaf; panels of at most ZH_FJOIN_PANEL_LINES
+// lines and ZH_FKNN_KEY_BUDGET keys (a longer leaf's lines are spread over panels; one line's leaf is the least a panel can hold).
+static int fjoin_leaves1(zh_index *ix, const FjoinRun &run, uint32_t t, const uint2 *leaves, size_t n, hipStream_t s, zh_join_forest_info *inf) {
+    std::vector<ZhFjoinPiece> pieces;
+    uint32_t lines = 0, groups = 0;
+    uint64_t flat = 0, keys = 0;
+    int rc;
+    auto flush = [&]() -> int {
+        if (pieces.empty()) return ZH_OK;
+        const int r = fjoin_panel1(ix, run, t, pieces, lines, groups, flat, keys, s, inf);
+        pieces.clear(); lines = 0; groups = 0; flat = 0; keys = 0;
+        return r;
+    };
+    for (size_t l = 0; l < n; l++) {
+        const uint32_t off = leaves[l].x, len = leaves[l].y;
+        if (len < 2) continue;
+        for (uint32_t i0 = 0; i0 < len;) {
+            uint64_t room = std::min<uint64_t>(ZH_FJOIN_PANEL_LINES - lines, (ZH_FKNN_KEY_BUDGET - std::min<uint64_t>(keys, ZH_FKNN_KEY_BUDGET)) / len);
+            if (!room) {
+                if (!pieces.empty()) { if ((rc = flush())) return rc; continue; }
+                room = 1;
+            }
+            const uint32_t nl = (uint32_t)std::min<uint64_t>(len - i0, room), ng = (nl + ZH_GROUP_MAX - 1) / ZH_GROUP_MAX;
+            pieces.push_back(ZhFjoinPiece{off, len, i0, nl, lines, groups, flat, keys});
+            lines += nl; groups += ng; flat += (uint64_t)ng * len; keys += (uint64_t)nl * len;
+            i0 += nl;
+        }
+    }
+    return flush();
+}
+
+// Path 2 of one batch of leaves of tree t (leaves[l] at column tile col0[l] of the batch's NT tiles).  *hits = jn_ctr[0] afterwards.
+static int fjoin_batch2(zh_index *ix, const FjoinRun &run, uint32_t t, const std::vector<uint2> &leaves, const std::vector<uint2> &colsrc, hipStream_t s,
+                        zh_join_forest_info *inf, uint64_t *hits) {
+    const uint32_t d = ix->opt.dim, NT = (uint32_t)colsrc.size();
+    // tiles per chunk: ZH_FKNN_CHUNK, fewer while the launch would not fill the device (about 1024 blocks), never under 8.  A leaf of ct tiles gives one
+    // segment per held block I0 = 0, 4, ... < ct with ceil((ct - I0) / ch) blocks: chunks are counted from the held block's own diagonal
+    uint32_t ch = ZH_FKNN_CHUNK, n_blocks = 0;
+    for (;;) {
+        n_blocks = 0;
+        for (const uint2 lf : leaves) {
+            const uint32_t ct = (lf.y + 15) / 16;
+            for (uint32_t I0 = 0; I0 < ct; I0 += 4) n_blocks += (ct - I0 + ch - 1) / ch;
+        }
+        if (n_blocks >= 1024 || ch <= 8) break;
+        ch /= 2;
+    }
+    std::vector<ZhFjoinSeg> segs;
+    uint64_t products = 0, batch_pairs = 0;
+    uint32_t col0 = 0, blocks = 0;
+    for (const uint2 lf : leaves) {
+        const uint32_t ct = (lf.y + 15) / 16;
+        for (uint32_t I0 = 0; I0 < ct; I0 += 4) {
+            segs.push_back(ZhFjoinSeg{col0, ct, I0, blocks});
+            blocks += (ct - I0 + ch - 1) / ch;
+        }
+        products += (uint64_t)ct * (ct + 1) / 2;  // wave I issues ct - I
+        batch_pairs += (uint64_t)lf.y * (lf.y - 1) / 2;
+        col0 += ct;
+    }
+    const uint64_t pool_left = run.pool_cap > *hits ? run.pool_cap - *hits : 0;
+    uint64_t cand_cap = std::min<uint64_t>(batch_pairs, std::max<uint64_t>(pool_left + pool_left / 4, (uint64_t)ZH_FJOIN_CAND_FLOOR * NT * 16));
+    if (run.env_cand) cand_cap = run.env_cand_cap;
+    int rc;
+    if ((rc = ix->fj_segs.ensure(segs.size() * sizeof(ZhFjoinSeg))) || (rc = ix->fk_colsrc.ensure((size_t)NT * 8)) || (rc = ix->fk_crow.ensure((size_t)NT * 64)) ||
+        (rc = ix->fk_CA.ensure((size_t)NT * 32 * d)) || (rc = ix->fk_cmeta.ensure((size_t)NT * 128)) || (rc = ix->fk_cqm.ensure((size_t)NT * 256)) ||
+        (rc = ix->fj_cand.ensure(std::max<uint64_t>(cand_cap, 1) * 8)))
+        return rc;
+    unsigned long long *ctr = ix->jn_ctr.as<unsigned long long>();
+    uint32_t *crow = ix->fk_crow.as<uint32_t>();
+    HIPCHK(hipMemcpyAsync(ix->fj_segs.p, segs.data(), segs.size() * sizeof(ZhFjoinSeg), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ix->fk_colsrc.p, colsrc.data(), (size_t)NT * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(zh_launch_fknn_cols(ix->fk_colsrc.as<uint2>(), NT, ix->leaf_ids.as<uint32_t>(), ix->n_rows, crow, s));
+    HIPCHK(zh_launch_fknn_gather(d, run.Xh, run.rowMeta, run.pos, crow, NT, run.rho, ix->fk_CA.p, ix->fk_cmeta.as<float2>(), ix->fk_cqm.as<float4>(), s));
+    HIPCHK(hipMemsetAsync(ctr + 1, 0, 8, s));
+    HIPCHK(zh_launch_fjoin_mfma(d, run.metric, run.mode, ix->fj_segs.as<ZhFjoinSeg>(), (uint32_t)segs.size(), blocks, ch, ix->fk_CA.p, ix->fk_cmeta.as<float2>(),
+                                ix->fk_cqm.as<float4>(), crow, run.Kc, run.rho, ix->jn_tau.as<uint32_t>(), ix->fj_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
+    inf->launches++;
+    inf->tiles += products;
+    HIPCHK(zh_launch_fjoin_survivors(ix->X.as<float>(), d, run.metric, run.mode, ix->fj_cand.as<uint64_t>(), ctr + 1, cand_cap, ix->fj_leafof.as<uint32_t>(), run.T,
+                                     t, run.max_key, ctr, ctr + 3, ix->jn_pv0.as<uint64_t>(), ix->jn_pk0.as<uint64_t>(), run.pool_cap, s));
+    unsigned long long h_ctr[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(h_ctr, ctr, 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // (segs and colsrc are this frame's and the caller's)
+    if (h_ctr[1] <= cand_cap) {
+        inf->candidates = h_ctr[3];
+        *hits = h_ctr[0];
+        return ZH_OK;
+    }
+    // the pool ran over: nothing of the batch was counted (fjoin_survivors_kernel left at once); ownership does not depend on the path, so path 1
+    // over the same leaves counts exactly the batch's pairs
+    inf->redone++;
+    if ((rc = fjoin_leaves1(ix, run, t, leaves.data(), leaves.size(), s, inf))) return rc;
+    HIPCHK(hipMemcpyAsync(h_ctr, ctr, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *hits = h_ctr[0];
+    return ZH_OK;
+}
+
+// Path 2 of one tree: its non-empty leaves, in the host mirror's order, in batches of at most ZH_FKNN_COL_TILES tiles, or ONE longer leaf alone.
+static int fjoin_tree2(zh_index *ix, const FjoinRun &run, uint32_t t, hipStream_t s, zh_join_forest_info *inf, uint64_t *hits) {
+    std::vector<uint2> leaves, colsrc;
+    int rc;
+    for (const uint2 leaf : run.leaves[t]) {
+        const uint32_t ct = (leaf.y + 15) / 16;
+        if (!leaves.empty() && colsrc.size() + ct > ZH_FKNN_COL_TILES) {
+            if ((rc = fjoin_batch2(ix, run, t, leaves, colsrc, s, inf, hits))) return rc;
+            leaves.clear(); colsrc.clear();
+        }
+        leaves.push_back(leaf);
+        for (uint32_t c = 0; c < ct; c++) colsrc.push_back(make_uint2(leaf.x + 16 * c, std::min<uint32_t>(16, leaf.y - 16 * c)));
+    }
+    if (!leaves.empty() && (rc = fjoin_batch2(ix, run, t, leaves, colsrc, s, inf, hits))) return rc;
+    return ZH_OK;
+}
+
+// The call on the index's device (under mu, exclusive; exact_live_rows has run; the index has live rows and trees).  host_out as join_run.
+static int fjoin_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *outA, uint64_t *outB, uint64_t *outKeys, bool host_out,
+                     hipStream_t s, uint64_t *total, const char *who) {
+    zh_join_forest_info inf{};
+    inf.path = 1;
+    inf.rows_live = ix->ex_n_live;
+    inf.trees = ix->n_trees;
+    FjoinRun run;
+    run.metric = metric; run.mode = mode; run.max_key = max_key;
+    int rc;
+    if ((rc = fjoin_setup(ix, metric, mode, s, &run))) return rc;
+    unsigned long long *ctr = ix->jn_ctr.as<unsigned long long>();
+    unsigned long long h_ctr[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(h_ctr, ctr, 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    inf.leaf_pairs = h_ctr[2];
+    uint64_t hits = 0;
+    if (inf.leaf_pairs) {
+        run.pool_cap = std::min<uint64_t>(capacity, inf.leaf_pairs);
+        if ((rc = ix->jn_pv0.ensure(std::max<uint64_t>(run.pool_cap, 1) * 8)) || (rc = ix->jn_pk0.ensure(std::max<uint64_t>(run.pool_cap, 1) * 8))) return rc;
+        if (run.path2) {
+            inf.path = 2;
+            if ((rc = ix->jn_tau.ensure(4)) || (rc = ix->jn_maxk.ensure(8))) return rc;
+            HIPCHK(hipMemcpyAsync(ix->jn_maxk.p, &max_key, 8, hipMemcpyHostToDevice, s));
+            HIPCHK(zh_launch_range_tau(ix->jn_maxk.as<uint64_t>(), 1, metric, mode, ix->jn_tau.as<uint32_t>(), s));
+            HIPCHK(hipStreamSynchronize(s));  // (max_key is this frame's)
+        }
+        for (uint32_t t = 0; t < run.T; t++) {
+            if (run.path2) { if ((rc = fjoin_tree2(ix, run, t, s, &inf, &hits))) return rc; }
+            else if ((rc = fjoin_leaves1(ix, run, t, run.leaves[t].data(), run.leaves[t].size(), s, &inf))) return rc;
+        }
+        HIPCHK(hipMemcpyAsync(h_ctr, ctr, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        hits = h_ctr[0];
+    }
+    *total = hits;
+    inf.pairs = hits;
+    const bool over = hits > capacity;
+    if (!over && hits) {  // the order and the outputs, as join_run
+        uint64_t *dV[2] = {nullptr, nullptr}, *dK[2] = {nullptr, nullptr};
+        size_t tmp_bytes = 0;
+        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, nullptr, &tmp_bytes, 0, nullptr, nullptr, nullptr, s));
+        if ((rc = ix->jn_pv1.ensure(hits * 8)) || (rc = ix->jn_pk1.ensure(hits * 8)) || (rc = ix->jn_tmp.ensure(tmp_bytes))) return rc;
+        if (host_out && ((rc = ix->jn_oa.ensure(hits * 8)) || (rc = ix->jn_ob.ensure(hits * 8)) || (rc = ix->jn_okeys.ensure(hits * 8)))) return rc;
+        dV[0] = ix->jn_pv0.as<uint64_t>(); dV[1] = ix->jn_pv1.as<uint64_t>();
+        dK[0] = ix->jn_pk0.as<uint64_t>(); dK[1] = ix->jn_pk1.as<uint64_t>();
+        uint64_t *oa = host_out ? ix->jn_oa.as<uint64_t>() : outA, *ob = host_out ? ix->jn_ob.as<uint64_t>() : outB;
+        uint64_t *ok = host_out ? ix->jn_okeys.as<uint64_t>() : outKeys;
+        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, ix->jn_tmp.p, &tmp_bytes, ix->opt.id_base, oa, ob, ok, s));
+        if (host_out) {
+            HIPCHK(hipMemcpyAsync(outA, oa, hits * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(outB, ob, hits * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(outKeys, ok, hits * 8, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        ix->fj_info = inf;
+    }
+    if (over)
+        return fail(ZH_ELIMIT, "%s: %llu pairs exceed the capacity of %llu; out_total is exact, call again with that capacity", who,
+                    (unsigned long long)hits, (unsigned long long)capacity);
+    return ZH_OK;
+}
+
+// an index without live rows has no pair: total 0 (and the info says so) whatever its trees; otherwise the forest graph's state checks
+static int fjoin_state(zh_index *ix, bool *empty, const char *who) {
+    *empty = ix->ex_n_live == 0;
+    if (*empty) {
+        zh_join_forest_info inf{};
+        inf.path = 1;
+        inf.trees = ix->n_trees;
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        ix->fj_info = inf;
+        return ZH_OK;
+    }
+    return fknn_state(ix, who);
+}
+
+extern "C" int zh_self_join_forest_device(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *d_out_a, uint64_t *d_out_b,
+                                          uint64_t *d_out_keys, uint64_t *d_out_total, void *stream) {
+    int rc = join_args(ix, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, d_out_total, "zh_self_join_forest_device");
+    if (rc) return rc;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    bool empty = false;
+    if ((rc = fjoin_state(ix, &empty, "zh_self_join_forest_device"))) return rc;
+    FjoinScratchGuard guard{ix};
+    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    uint64_t total = 0;
+    if (!empty) {
+        rc = fjoin_run(ix, max_key, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, false, s, &total, "zh_self_join_forest_device");
+        if (rc && rc != ZH_ELIMIT) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(d_out_total, &total, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return rc;
+}
+
+extern "C" int zh_self_join_forest(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b, uint64_t *out_keys,
+                                   uint64_t *out_total) {
+    int rc = join_args(ix, metric, mode, capacity, out_a, out_b, out_keys, out_total, "zh_self_join_forest");
+    if (rc) return rc;
+    *out_total = 0;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    bool empty = false;
+    if ((rc = fjoin_state(ix, &empty, "zh_self_join_forest")) || empty) return rc;
+    FjoinScratchGuard guard{ix};
+    uint64_t total = 0;
+    rc = fjoin_run(ix, max_key, metric, mode, capacity, out_a, out_b, out_keys, true, ix->stream, &total, "zh_self_join_forest");
+    if (rc && rc != ZH_ELIMIT) return rc;
+    *out_total = total;
+    return rc;
+}
+
+extern "C" int zh_self_join_forest_info(const zh_index *ix, zh_join_forest_info *out) {
+    if (!ix || !out) return fail(ZH_EINVAL, "zh_self_join_forest_info: null argument");
+    zh_index *m = const_cast<zh_index *>(ix);
+    std::lock_guard<std::mutex> lk(m->stats_mu);
+    *out = m->fj_info;
     return ZH_OK;
 }
 

@@ -1,0 +1,395 @@
+// zh_fjoin.hip -- forest self-join (zh_self_join_forest, driver in zh_api.hip): every unordered pair of distinct stored rows (a, b), a < b by row
+// number, that are members of the SAME leaf in at least one tree and whose key is <= ONE threshold key, each pair once however many trees put the
+// two rows together.  Key, orientation, order, threshold and output are zh_join.hip's: the key of (a, b) is that of stored row b
+// against a query equal to the f32 row a, hits go to ONE pool per call (v = a << 32 | b and the key) and are counted whether or not the pool has
+// room, zh_launch_join_sort orders the pool by (a, key, b).  What is approximate is the candidate set, never the arithmetic.  DESIGN.md s18.
+//
+// Each pair once: leaf_of[row][tree] = the offset into leaf_ids of the row's leaf in that tree (UINT32_MAX: the tree does not hold the row), built
+// once per call by fjoin_rowleaf_kernel.  A pair met in tree t is kept only if leaf_of[a][t'] != leaf_of[b][t'] for every t' < t: the FIRST tree
+// that puts the two rows together owns the pair.  Ownership depends on the forest alone -- not on a path, a batch or a position of the scan's row
+// order -- so any set of leaves may be answered by either path and the hit counter may run on past the pool.  The comparisons (at most T - 1) are
+// paid by candidates (path 2) or by keys already at or below the threshold (path 1), never per product.
+//
+//   path 1  every metric, dimension and leaf shape, and the redo of a path-2 batch whose candidate pool ran over.  A panel is a list of pieces
+//           {leaf, a range of its members as lines}: fjoin_groups_kernel writes the lines' rows and groups of up to ZH_GROUP_MAX lines that visit
+//           the one leaf, join_gather_kernel gathers the lines' f32 rows as queries, the leaf-major f32 sweep keys the leaf's rows against them,
+//           fjoin_collect_kernel takes the keys <= max_key whose row number is above the line's and that pass the first-tree rule.
+//   path 2  a batch of one tree's leaves, each padded to whole tiles by masked rows, is gathered ONCE out of the fp16 copy (zh_fknn.hip's cols /
+//           gather kernels).  fjoin_mfma_kernel is join_mfma_kernel's triangle over MANY leaves in one launch: a block finds its segment (a leaf's
+//           four held tiles from I0) by binary search over the segments' first blocks, holds tiles I0 .. I0 + 3 of that leaf in registers, one per
+//           wave, and walks ONE chunk of the leaf's tiles counted from its own diagonal through two LDS buffers; a gathered tile serves as either
+//           MFMA operand (s15).  The sum is (acc0 + acc1) + (acc2 + acc3), approx_interval's bound zh_approx_bound(metric, d, 1), the held row its
+//           "stored row", the LDS row its "query": s15's argument for two rounded operands applies word for word.  Pairs with lo <= tau go to the
+//           batch's candidate pool as min(row) << 32 | max(row); fjoin_survivors_kernel applies the first-tree rule, gives the rest the canonical
+//           key of (row b, query = f32 row a), judges key <= max_key, counts and pools.
+// Scratch (all per call, released before return): leaf_of is 4 bytes per (stored row, tree) -- 4 N T, 600 MB at 10M rows x 15 trees, not chunked
+// -- and the node -> tree map 4 bytes per node; path 2 per batch of at most max(ZH_FKNN_COL_TILES tiles, the longest leaf) gathered rows 2 d + 28
+// bytes per row, 16 bytes per segment and 8 bytes per candidate slot (at most max(1.25 x the capacity left, 256 per gathered row), never more than
+// the batch's leaf pairs), plus 4 bytes per stored row under a scan order that is not id order; path 1 per panel of at most ZH_FJOIN_PANEL_LINES
+// lines 4 d + 24 bytes per line, 56 bytes per group and 8 bytes per key of at most max(2^25, the longest leaf) keys; both 16 bytes per hit-pool
+// slot (<= the capacity), for the order as much again plus hipCUB's temporary storage, and 24 bytes per pair of staging for the host call.
+#include <algorithm>
+
+#include "zh_internal.h"
+#include "zh_device.h"
+
+typedef _Float16 f16x8g __attribute__((ext_vector_type(8)));
+typedef float f32x4g __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4g __attribute__((ext_vector_type(4)));
+
+// the lanes of `m` (a ballot) get consecutive pool slots: one atomic for the wave (join_wave_slots, restated: zh_join.hip is left alone)
+__device__ __forceinline__ unsigned long long fjoin_wave_slots(unsigned long long *__restrict__ ctr, uint64_t m, uint32_t lane) {
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(ctr, (unsigned long long)__popcll(m));
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
+    return (((unsigned long long)hi << 32) | lo) + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+}
+
+// the first-tree rule: tree t owns the pair (a, b) when no earlier tree holds both rows in one leaf
+__device__ __forceinline__ bool fjoin_owned(const uint32_t *__restrict__ leaf_of, uint32_t T, uint32_t t, uint32_t a, uint32_t b) {
+    const uint32_t *la = leaf_of + (size_t)a * T, *lb = leaf_of + (size_t)b * T;
+    for (uint32_t u = 0; u < t; u++) {
+        const uint32_t x = la[u];
+        if (x != 0xFFFFFFFFu && x == lb[u]) return false;
+    }
+    return true;
+}
+
+// ---- both paths: leaf_of.  A block per node: a leaf of tree t writes its offset for its members; *leaf_pairs += len (len - 1) / 2 ----
+__global__ __launch_bounds__(64) void fjoin_rowleaf_kernel(const int4 *__restrict__ node_pack, const uint32_t *__restrict__ node_tree,
+                                                           const uint32_t *__restrict__ leaf_ids, uint32_t T, uint64_t n_rows, uint32_t node0,
+                                                           uint32_t *__restrict__ leaf_of, unsigned long long *__restrict__ leaf_pairs) {
+    const uint32_t node = node0 + blockIdx.x;
+    const int4 rec = node_pack[node];
+    if (rec.x >= 0) return;  // inner node
+    const uint32_t t = node_tree[node];
+    if (t >= T) return;      // not reachable from a root
+    const uint32_t off = (uint32_t)rec.y, len = (uint32_t)rec.z;
+    for (uint32_t i = threadIdx.x; i < len; i += 64) {
+        const uint64_t r = leaf_ids[(size_t)off + i];
+        if (r < n_rows) leaf_of[(size_t)r * T + t] = off;
+    }
+    if (threadIdx.x == 0 && len >= 2) atomicAdd(leaf_pairs, (unsigned long long)len * (len - 1) / 2);
+}
+
+hipError_t zh_launch_fjoin_rowleaf(const int4 *dNodePack, const uint32_t *dNodeTree, uint32_t n_nodes, const uint32_t *dLeafIds, uint32_t T, uint64_t n_rows,
+                                   uint32_t *dLeafOf, unsigned long long *dLeafPairs, hipStream_t s) {
+    if (!T) return hipSuccess;
+    if (n_rows) {
+        hipError_t e = hipMemsetAsync(dLeafOf, 0xFF, (size_t)n_rows * T * 4, s);  // UINT32_MAX: the row is not in that tree
+        if (e != hipSuccess) return e;
+    }
+    for (uint32_t n0 = 0; n0 < n_nodes; n0 += (1u << 22)) {
+        const uint32_t nb = n_nodes - n0 < (1u << 22) ? n_nodes - n0 : (1u << 22);
+        hipLaunchKernelGGL(fjoin_rowleaf_kernel, dim3(nb), dim3(64), 0, s, dNodePack, dNodeTree, dLeafIds, T, n_rows, n0, dLeafOf, dLeafPairs);
+    }
+    return hipGetLastError();
+}
+
+// ---- path 1: a panel's lines and groups.  Group g belongs to the last piece whose group0 <= g; it holds up to ZH_GROUP_MAX consecutive lines of the
+// piece, which all visit the piece's leaf ----
+__global__ __launch_bounds__(256) void fjoin_groups_kernel(const ZhFjoinPiece *__restrict__ pieces, uint32_t n_pieces, uint32_t n_groups,
+                                                           const uint32_t *__restrict__ leaf_ids, uint64_t n_rows, uint32_t *__restrict__ rows,
+                                                           uint2 *__restrict__ lineLeaf, uint64_t *__restrict__ lineKey, ZhGroup *__restrict__ groups,
+                                                           uint64_t *__restrict__ groupRowOff) {
+    const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= n_groups) return;
+    uint32_t lo = 0, hi = n_pieces;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pieces[mid].group0 <= g) lo = mid; else hi = mid;
+    }
+    const ZhFjoinPiece pc = pieces[lo];
+    const uint32_t gi = g - pc.group0, j0 = gi * ZH_GROUP_MAX, left = pc.nl - j0, gsize = left < ZH_GROUP_MAX ? left : ZH_GROUP_MAX;
+    ZhGroup gr;
+    gr.leaf_off = pc.off; gr.len = pc.len; gr.gsize = gsize; gr.take4 = 0;
+    for (uint32_t m = 0; m < ZH_GROUP_MAX; m++) {
+        const uint32_t j = j0 + (m < gsize ? m : 0u), line = pc.line0 + j;
+        const uint64_t ko = pc.key0 + (uint64_t)j * pc.len;
+        gr.b[m] = line;
+        gr.key_off[m] = ko;
+        if (m < gsize) {
+            const uint32_t row = leaf_ids[(size_t)pc.off + pc.i0 + j];
+            const bool ok = row < n_rows;  // (always, for a forest this library built: a line that is no stored row collects nothing)
+            rows[line] = ok ? row : 0u;
+            lineLeaf[line] = make_uint2(pc.off, ok ? pc.len : 0u);
+            lineKey[line] = ko;
+        }
+    }
+    groups[g] = gr;
+    groupRowOff[g] = pc.flat0 + (uint64_t)gi * pc.len;
+}
+
+hipError_t zh_launch_fjoin_groups(const ZhFjoinPiece *dPieces, uint32_t n_pieces, uint32_t n_groups, const uint32_t *dLeafIds, uint64_t n_rows, uint32_t *dRows,
+                                  uint2 *dLineLeaf, uint64_t *dLineKey, ZhGroup *dGroups, uint64_t *dGroupRowOff, hipStream_t s) {
+    if (!n_pieces || !n_groups) return hipSuccess;
+    hipLaunchKernelGGL(fjoin_groups_kernel, dim3((n_groups + 255) / 256), dim3(256), 0, s, dPieces, n_pieces, n_groups, dLeafIds, n_rows, dRows, dLineLeaf,
+                       dLineKey, dGroups, dGroupRowOff);
+    return hipGetLastError();
+}
+
+// a block per line: the hits among its leaf's keys -- key <= max_key, the member's row number above the line's, the pair owned by tree t
+__global__ __launch_bounds__(256) void fjoin_collect_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ rows,
+                                                            const uint2 *__restrict__ lineLeaf, const uint64_t *__restrict__ lineKey,
+                                                            const uint32_t *__restrict__ leaf_ids, uint64_t n_rows, const uint32_t *__restrict__ leaf_of,
+                                                            uint32_t T, uint32_t t, uint64_t max_key, unsigned long long *__restrict__ ctr,
+                                                            uint64_t *__restrict__ pv, uint64_t *__restrict__ pk, uint64_t cap) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x & 63;
+    const uint32_t a = rows[b];
+    const uint2 lf = lineLeaf[b];
+    const uint64_t ko = lineKey[b];
+    for (uint32_t i0 = 0; i0 < lf.y; i0 += 256) {  // (block-uniform)
+        const uint32_t i = i0 + threadIdx.x;
+        uint64_t key = 0;
+        uint32_t row = 0;
+        bool hit = false;
+        if (i < lf.y) {
+            row = leaf_ids[(size_t)lf.x + i];
+            key = keys[ko + i];
+            hit = row > a && row < n_rows && key <= max_key && fjoin_owned(leaf_of, T, t, a, row);
+        }
+        const uint64_t m = __ballot(hit);
+        if (!m) continue;  // (wave-uniform)
+        const unsigned long long slot = fjoin_wave_slots(ctr, m, lane);  // always: the count stays exact when the pool is full
+        if (hit && slot < cap) {
+            pv[slot] = ((uint64_t)a << 32) | row;
+            pk[slot] = key;
+        }
+    }
+}
+
+hipError_t zh_launch_fjoin_collect(const uint64_t *dKeys, const uint32_t *dRows, const uint2 *dLineLeaf, const uint64_t *dLineKey, uint32_t B,
+                                   const uint32_t *dLeafIds, uint64_t n_rows, const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key,
+                                   unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s) {
+    if (!B) return hipSuccess;
+    hipLaunchKernelGGL(fjoin_collect_kernel, dim3(B), dim3(256), 0, s, dKeys, dRows, dLineLeaf, dLineKey, dLeafIds, n_rows, dLeafOf, T, t, max_key, dHitCtr,
+                       dPoolV, dPoolK, pool_cap);
+    return hipGetLastError();
+}
+
+// ---- path 2 ----
+// The launch geometry of a batch (the host's, fjoin_batch2 in zh_api.hip): a leaf of ct tiles at column tile col0 of the batch gives one segment per
+// held block I0 = 0, 4, 8, ... < ct, whose ceil((ct - I0) / ch) blocks walk the chunks [I0 + ch c, I0 + ch (c + 1)) cut at ct: chunks are counted from
+// the held block's own diagonal, so none lies wholly below it.  Wave I issues ct - I tile products, the leaf ct (ct + 1) / 2.
+// One launch over every segment of a batch.  Block x finds its segment sg (the last whose first_block <= x), then chunk = x - first_block.  CA / meta /
+// qm / crow are the batch's gathered tiles, rowMeta, query views and row-or-masked words (zh_launch_fknn_gather, zh_launch_fknn_cols).
+template <int D, int KINDA>
+__global__ __launch_bounds__(256) void fjoin_mfma_kernel(const ZhFjoinSeg *__restrict__ segs, uint32_t n_segs, uint32_t ch, const u32x4g *__restrict__ CA,
+                                                         const float2 *__restrict__ cmeta, const float4 *__restrict__ cqm, const uint32_t *__restrict__ crow,
+                                                         float Kc, float rho, const uint32_t *__restrict__ tau, uint64_t *__restrict__ cand, uint64_t cap,
+                                                         unsigned long long *__restrict__ ctr) {
+    constexpr int NS = D / 32;        // MFMA steps of a tile (K = 32 each)
+    constexpr int PIECES = NS * 64;   // 16-byte pieces of a tile
+    constexpr int PT = PIECES / 256;  // ... per thread of the block
+    __shared__ u32x4g sB[2][PIECES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, h = lane >> 4;
+    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    uint32_t lo_s = 0, hi_s = n_segs;  // the last segment whose first block is <= blockIdx.x (block-uniform)
+    while (hi_s - lo_s > 1) {
+        const uint32_t mid = (lo_s + hi_s) >> 1;
+        if (segs[mid].first_block <= blockIdx.x) lo_s = mid; else hi_s = mid;
+    }
+    const ZhFjoinSeg sg = segs[lo_s];
+    // tiles of the batch: the leaf's are [col0, Tend); the wave holds I, the block walks [Jb, Je)
+    const uint32_t Tend = sg.col0 + sg.ct, I = sg.col0 + sg.I0 + wid;
+    const uint32_t Jb = sg.col0 + sg.I0 + (blockIdx.x - sg.first_block) * ch;
+    if (Jb >= Tend) return;  // (block-uniform; the host's geometry launches no such block)
+    const uint32_t Je = Jb + ch < Tend ? Jb + ch : Tend;
+    const bool active = I < Tend;  // (wave-uniform; an idle wave of a leaf's last held block still moves tiles and meets the barriers)
+    f16x8g A[NS];
+    uint32_t id[4];
+    float2 meta[4];
+    if (active) {
+        const u32x4g *tp = CA + (size_t)I * PIECES + lane;
+#pragma unroll
+        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8g, tp[64 * st]);
+        // this lane's outputs: rows 4 h + i of the held tile (register i), column c16 = row c16 of tile J
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t p = I * 16 + 4 * h + i;
+            id[i] = crow[p];
+            meta[i] = id[i] != 0xFFFFFFFFu ? cmeta[p] : make_float2(0.f, 0.f);
+        }
+    } else {
+#pragma unroll
+        for (int st = 0; st < NS; st++) A[st] = f16x8g{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 4; i++) { id[i] = 0xFFFFFFFFu; meta[i] = make_float2(0.f, 0.f); }
+    }
+    const uint32_t tq = tau[0];
+    {
+        const u32x4g *src = CA + (size_t)Jb * PIECES + tid;
+#pragma unroll
+        for (int k = 0; k < PT; k++) sB[0][k * 256 + tid] = src[k * 256];
+    }
+    // the column rows' row-or-masked word and qm travel one tile ahead, like the tile itself
+    uint32_t cb_next = crow[Jb * 16 + c16];
+    float4 qb_next = cqm[Jb * 16 + c16];
+    __syncthreads();
+    for (uint32_t J = Jb; J < Je; J++) {
+        const uint32_t cur = (J - Jb) & 1u;
+        const bool more = J + 1 < Je;  // (block-uniform)
+        const uint32_t cb = cb_next;
+        const float4 qb = qb_next;
+        u32x4g pf[PT];
+        if (more) {
+            const u32x4g *src = CA + (size_t)(J + 1) * PIECES + tid;
+#pragma unroll
+            for (int k = 0; k < PT; k++) pf[k] = src[k * 256];
+            cb_next = crow[(J + 1) * 16 + c16];
+            qb_next = cqm[(J + 1) * 16 + c16];
+        }
+        if (active && J >= I) {  // (wave-uniform: in its first chunk wave w skips the w tiles before its own)
+            const u32x4g *bp = &sB[cur][lane];
+            f32x4g acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+            for (int st = 0; st < NS; st++)
+                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8g, bp[64 * st]), acc[st & 3], 0, 0, 0);
+            const f32x4g t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+            const bool diag = J == I;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                bool pass = false;
+                // in a diagonal tile only held row 4 h + i before column row c16; a masked row on either side is no pair
+                if (id[i] != 0xFFFFFFFFu && cb != 0xFFFFFFFFu && (!diag || 4 * h + i < c16))
+                    pass = (uint32_t)approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qb, Kc, rho, 0.f) <= tq;
+                const uint64_t m = __ballot(pass);
+                if (m) {  // (wave-uniform)
+                    const unsigned long long slot = fjoin_wave_slots(ctr, m, lane);  // the counter runs on past the pool
+                    if (pass && slot < cap) {
+                        const uint32_t a = id[i] < cb ? id[i] : cb, b = id[i] < cb ? cb : id[i];
+                        cand[slot] = ((uint64_t)a << 32) | b;
+                    }
+                }
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int k = 0; k < PT; k++) sB[cur ^ 1][k * 256 + tid] = pf[k];
+        }
+        __syncthreads();  // buffer cur ^ 1 was last read in the step before, which every wave left through this barrier
+    }
+}
+
+template <int KINDA>
+static hipError_t launch_fjoin_mfma_kinda(uint32_t d, const ZhFjoinSeg *segs, uint32_t n_segs, uint32_t n_blocks, uint32_t ch, const void *CA, const float2 *cmeta,
+                                          const float4 *cqm, const uint32_t *crow, float Kc, float rho, const uint32_t *dTau, uint64_t *dCand, uint64_t cap,
+                                          unsigned long long *dCtr, hipStream_t s) {
+#define ZH_FJ_CASE(DD)                                                                                                                                  \
+    case DD:                                                                                                                                             \
+        hipLaunchKernelGGL((fjoin_mfma_kernel<DD, KINDA>), dim3(n_blocks), dim3(256), 0, s, segs, n_segs, ch, (const u32x4g *)CA, cmeta, cqm, crow, Kc, rho, \
+                           dTau, dCand, cap, dCtr);                                                                                                      \
+        break
+    switch (d) {
+        ZH_FJ_CASE(256);
+        ZH_FJ_CASE(384);
+        ZH_FJ_CASE(512);
+        ZH_FJ_CASE(768);
+        ZH_FJ_CASE(1024);
+    default: return hipErrorInvalidValue;
+    }
+#undef ZH_FJ_CASE
+    return hipGetLastError();
+}
+
+hipError_t zh_launch_fjoin_mfma(uint32_t d, int metric, int mode, const ZhFjoinSeg *dSegs, uint32_t n_segs, uint32_t n_blocks, uint32_t ch, const void *dCA,
+                                const float2 *dCMeta, const float4 *dCQm, const uint32_t *dCRow, float Kc, float rho, const uint32_t *dTau, uint64_t *dCand,
+                                uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s) {
+    if (!n_segs || !n_blocks) return hipSuccess;
+    if (!ch) return hipErrorInvalidValue;
+    if (metric != ZH_COSINE) return launch_fjoin_mfma_kinda<0>(d, dSegs, n_segs, n_blocks, ch, dCA, dCMeta, dCQm, dCRow, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
+    if (mode == ZH_COSINE_PARITY)
+        return launch_fjoin_mfma_kinda<2>(d, dSegs, n_segs, n_blocks, ch, dCA, dCMeta, dCQm, dCRow, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
+    return launch_fjoin_mfma_kinda<1>(d, dSegs, n_segs, n_blocks, ch, dCA, dCMeta, dCQm, dCRow, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
+}
+
+// The batch's candidates (a << 32 | b, a < b, met in tree t): the first-tree rule, then for those it leaves the canonical key and its judgement
+// exactly as join_survivors_kernel (restated: sharing it would change zh_join.hip) -- the key of STORED row b against the QUERY row a, both read
+// from the f32 table, the cosine's query norm qnorm_kernel's sum of row a.  A wave takes 64 candidates at a time: pair j's sums wait in lane j, so
+// that key_of, the comparison and the pool's atomic run once for all 64.  *keyed += the candidates that got a key.
+template <int D, int KIND>
+__global__ __launch_bounds__(256) void fjoin_survivors_kernel(const float *__restrict__ X, int metric, int param, const uint64_t *__restrict__ cand,
+                                                              const unsigned long long *__restrict__ candCtr, uint64_t cand_cap,
+                                                              const uint32_t *__restrict__ leaf_of, uint32_t T, uint32_t t, uint64_t max_key,
+                                                              unsigned long long *__restrict__ ctr, unsigned long long *__restrict__ keyed,
+                                                              uint64_t *__restrict__ pv, uint64_t *__restrict__ pk, uint64_t cap) {
+    constexpr int NV = RowVec<D>::NV;
+    const uint64_t n = *candCtr;
+    if (n > cand_cap) return;  // (the pool ran over: the batch is answered by path 1)
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
+    for (uint64_t g = wave * 64; g < n; g += n_waves * 64) {
+        const uint32_t m = n - g < 64 ? (uint32_t)(n - g) : 64u;
+        const uint64_t mine = lane < m ? cand[g + lane] : 0ull;
+        const uint32_t my_b = (uint32_t)mine, my_a = (uint32_t)(mine >> 32);
+        const uint64_t own = __ballot(lane < m && fjoin_owned(leaf_of, T, t, my_a, my_b));
+        if (!own) continue;  // (wave-uniform)
+        if (lane == 0) atomicAdd(keyed, (unsigned long long)__popcll(own));
+        float m0 = 0.f, m1 = 0.f, mq = 0.f;
+        for (uint32_t j = 0; j < m; j++) {
+            if (!((own >> j) & 1ull)) continue;  // (wave-uniform)
+            const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)my_b, (int)j), qrow = (uint32_t)__builtin_amdgcn_readlane((int)my_a, (int)j);
+            float4 v[NV], q[NV];
+            load_row<D>(X + (size_t)row * D, lane, v);
+            load_row<D>(X + (size_t)qrow * D, lane, q);
+            float s0 = 0.f, s1 = 0.f, qq = 0.f;
+            row_pair_sums<D, KIND>(v, q, lane, param, s0, s1);
+            if (KIND == K_COS) {
+                float4 c = make_float4(0.f, 0.f, 0.f, 0.f), cq = c;
+#pragma unroll
+                for (int jj = 0; jj < NV; jj++) {
+                    const bool act = (jj < RowVec<D>::NJ) || (lane < (uint32_t)RowVec<D>::REM4);
+                    if (act) { sq4(v[jj], c); sq4(q[jj], cq); }
+                }
+                s1 = wave_sum_canonical((c.x + c.y) + (c.z + c.w));
+                qq = wave_sum_canonical((cq.x + cq.y) + (cq.z + cq.w));
+            }
+            if (lane == j) { m0 = s0; m1 = s1; mq = qq; }
+        }
+        uint64_t key = 0;
+        bool hit = false;
+        if ((own >> lane) & 1ull) {
+            key = key_of(metric, param, m0, m1, mq);
+            hit = key <= max_key;
+        }
+        const uint64_t hm = __ballot(hit);
+        if (hm) {  // (wave-uniform)
+            const unsigned long long slot = fjoin_wave_slots(ctr, hm, lane);
+            if (hit && slot < cap) { pv[slot] = mine; pk[slot] = key; }
+        }
+    }
+}
+
+template <int D>
+static void launch_fjoin_surv_d(const float *dX, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr, uint64_t cand_cap,
+                                const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key, unsigned long long *dHitCtr, unsigned long long *dKeyed,
+                                uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, uint32_t blocks, hipStream_t s) {
+    if (metric == ZH_COSINE)
+        hipLaunchKernelGGL((fjoin_survivors_kernel<D, K_COS>), dim3(blocks), dim3(256), 0, s, dX, metric, mode, dCand, dCandCtr, cand_cap, dLeafOf, T, t, max_key,
+                           dHitCtr, dKeyed, dPoolV, dPoolK, pool_cap);
+    else
+        hipLaunchKernelGGL((fjoin_survivors_kernel<D, K_L2>), dim3(blocks), dim3(256), 0, s, dX, metric, mode, dCand, dCandCtr, cand_cap, dLeafOf, T, t, max_key,
+                           dHitCtr, dKeyed, dPoolV, dPoolK, pool_cap);
+}
+
+hipError_t zh_launch_fjoin_survivors(const float *dX, uint32_t d, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr,
+                                     uint64_t cand_cap, const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key, unsigned long long *dHitCtr,
+                                     unsigned long long *dKeyed, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s) {
+    // the candidate count is known on the device only: enough waves for 64 candidates each up to the pool's size, at most 4096 of them
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (cand_cap + 255) / 256));
+#define ZH_FJ_SURV(DD)                                                                                                                                          \
+    case DD:                                                                                                                                                     \
+        launch_fjoin_surv_d<DD>(dX, metric, mode, dCand, dCandCtr, cand_cap, dLeafOf, T, t, max_key, dHitCtr, dKeyed, dPoolV, dPoolK, pool_cap, blocks, s); \
+        break
+    switch (d) {
+        ZH_FJ_SURV(256);
+        ZH_FJ_SURV(384);
+        ZH_FJ_SURV(512);
+        ZH_FJ_SURV(768);
+        ZH_FJ_SURV(1024);
+    default: return hipErrorInvalidValue;
+    }
+#undef ZH_FJ_SURV
+    return hipGetLastError();
+}

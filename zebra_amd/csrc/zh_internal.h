@@ -456,6 +456,42 @@ hipError_t zh_launch_fknn_store(const uint32_t *dHRow, uint32_t B, uint64_t firs
 // dRedo[(row - first_row) / ZH_FKNN_SLAB] = 1 for every held row of a batch whose lists ran over
 hipError_t zh_launch_fknn_mark(const uint32_t *dHRow, uint32_t B, uint64_t first_row, uint32_t *dRedo, hipStream_t s);
 
+// ---- the forest self-join (zh_fjoin.hip): every pair of leaf-mates whose key is <= one threshold key, each pair once (the first tree that puts
+// the two rows together owns it).  Hit pool, counter and order as the exact self-join's
+#define ZH_FJOIN_PANEL_LINES 16384u  // path 1: lines of one panel at most
+// path 1: members [i0, i0 + nl) of the leaf {off, len} of leaf_ids as lines line0 .. of the panel, in groups group0 .. (ceil(nl / ZH_GROUP_MAX)
+// of them, each sweeping the whole leaf: flat rows from flat0, len per group); line j's keys at key0 + j len
+struct ZhFjoinPiece {
+    uint32_t off, len, i0, nl;
+    uint32_t line0, group0;
+    uint64_t flat0, key0;
+};
+// path 2: held block I0 (tiles I0 .. I0 + 3) of a leaf whose ct tiles start at column tile col0 of the batch; first_block = the launch's blocks
+// before this segment's ceil((ct - I0) / ch)
+struct ZhFjoinSeg {
+    uint32_t col0, ct, I0, first_block;
+};
+// dLeafOf[r * T + t] = the offset into leaf_ids of the leaf of stored row r in tree t, UINT32_MAX for none; *dLeafPairs += the sum over the
+// reachable leaves of len (len - 1) / 2
+hipError_t zh_launch_fjoin_rowleaf(const int4 *dNodePack, const uint32_t *dNodeTree, uint32_t n_nodes, const uint32_t *dLeafIds, uint32_t T, uint64_t n_rows,
+                                   uint32_t *dLeafOf, unsigned long long *dLeafPairs, hipStream_t s);
+// path 1: a panel's lines (dRows, {leaf offset, length} and key offset per line) and its n_groups groups with their flat row offsets
+hipError_t zh_launch_fjoin_groups(const ZhFjoinPiece *dPieces, uint32_t n_pieces, uint32_t n_groups, const uint32_t *dLeafIds, uint64_t n_rows, uint32_t *dRows,
+                                  uint2 *dLineLeaf, uint64_t *dLineKey, ZhGroup *dGroups, uint64_t *dGroupRowOff, hipStream_t s);
+// ... and its hits: the swept keys <= max_key of members above the line's row, for the pairs tree t owns
+hipError_t zh_launch_fjoin_collect(const uint64_t *dKeys, const uint32_t *dRows, const uint2 *dLineLeaf, const uint64_t *dLineKey, uint32_t B,
+                                   const uint32_t *dLeafIds, uint64_t n_rows, const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key,
+                                   unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
+// path 2: every segment of a batch in one launch of n_blocks blocks, chunks of ch tiles, against *dTau (zh_launch_range_tau of the one threshold);
+// pairs with lo <= tau to dCand as min(row) << 32 | max(row); *dCandCtr counts them all
+hipError_t zh_launch_fjoin_mfma(uint32_t d, int metric, int mode, const ZhFjoinSeg *dSegs, uint32_t n_segs, uint32_t n_blocks, uint32_t ch, const void *dCA,
+                                const float2 *dCMeta, const float4 *dCQm, const uint32_t *dCRow, float Kc, float rho, const uint32_t *dTau, uint64_t *dCand,
+                                uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s);
+// ... the first-tree rule, canonical keys and the judgement of its candidates (nothing when *dCandCtr > cand_cap); *dKeyed += those that got a key
+hipError_t zh_launch_fjoin_survivors(const float *dX, uint32_t d, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr,
+                                     uint64_t cand_cap, const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key, unsigned long long *dHitCtr,
+                                     unsigned long long *dKeyed, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
+
 // ---- launchers (zh_score.hip): every sign of a forest built from stored rows, from N row scores per query --------
 // Prefilter (zh_search.hip, "Prefilter"): a batch hashed from row scores picks the rows that can be among a pair's k best from
 // those scores; only they are scored with the reference's arithmetic.  Lists: one per (tree, query), `cap` slots, list (t, b) at

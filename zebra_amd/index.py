@@ -581,6 +581,59 @@ class LSHIndex:
             self.remove(removed)
         return removed
 
+    def self_join_forest(self, radius=None, metric=None, max_key=None, capacity=None):
+        """FOREST self-join: every pair of distinct stored rows (a, b), a < b, that share a leaf in at least one tree (get_forest()'s leaf_ids)
+        and whose key is <= ONE threshold -- `radius` or `max_key`, as self_join -- each pair once however many trees put the two rows together.
+        self_join's keys, ids and order on an approximate candidate set: the answer is the subset of self_join's pairs that are leaf-mates.
+        -> (a u64, b u64, keys u64), ascending by (a, key, b).  One call with a guessed capacity; when the pairs exceed it, one more with the
+        exact total the first call reported.  Needs a built forest."""
+        mk = self._join_key(radius, metric, max_key)
+        cap = int(capacity) if capacity is not None else max(1024, 16 * len(self))
+        total = C.c_uint64(0)
+        for attempt in range(2):
+            a = np.empty(max(cap, 1), np.uint64)
+            b = np.empty(max(cap, 1), np.uint64)
+            keys = np.empty(max(cap, 1), np.uint64)
+            rc = lib().zh_self_join_forest(self._h, mk, metric.metric, metric.mode, cap, _p(a), _p(b), _p(keys), C.byref(total))
+            if rc == _ffi.ZH_ELIMIT and attempt == 0 and total.value > cap:
+                cap = int(total.value)
+                continue
+            check(rc)
+            break
+        n = int(total.value)
+        return a[:n], b[:n], keys[:n]
+
+    def self_join_forest_count(self, radius=None, metric=None, max_key=None):
+        """how many pairs self_join_forest would return (a call with capacity 0: nothing is ordered or written)"""
+        mk = self._join_key(radius, metric, max_key)
+        total = C.c_uint64(0)
+        rc = lib().zh_self_join_forest(self._h, mk, metric.metric, metric.mode, 0, None, None, None, C.byref(total))
+        if rc != _ffi.ZH_ELIMIT:
+            check(rc)
+        return int(total.value)
+
+    def self_join_forest_device(self, max_key, metric, capacity, d_a_ptr, d_b_ptr, d_keys_ptr, d_total_ptr, stream=None):
+        """self_join_forest with a, b, keys (`capacity` each) and the total (one u64) in device memory (raw pointers, e.g. torch .data_ptr()).
+        Pairs beyond the capacity raise ZhError with code ZH_ELIMIT; the total is exact even then."""
+        check(lib().zh_self_join_forest_device(self._h, int(max_key), metric.metric, metric.mode, capacity, d_a_ptr, d_b_ptr, d_keys_ptr, d_total_ptr,
+                                               stream))
+
+    def join_forest_info(self):
+        """what the most recent forest self-join on this index did (zh_self_join_forest_info): rows_live, trees, path, leaf_pairs, pairs,
+        candidates, launches, tiles, redone"""
+        info = _ffi.JoinForestInfo()
+        check(lib().zh_self_join_forest_info(self._h, C.byref(info)))
+        return info.as_dict()
+
+    def deduplicate_within_forest(self, radius, metric):
+        """deduplicate_within's rule over the forest self-join's pairs (self_join_forest at `radius`): near-duplicates that no tree puts into
+        one leaf are not seen -> the removed ids, ascending."""
+        a, b, _ = self.self_join_forest(radius, metric)
+        removed = dedup_rule(a, b)
+        if removed.size:
+            self.remove(removed)
+        return removed
+
     def debug_keep_raw(self, on=True):
         """tests: half-width batches keep a copy of the scan's raw pairs (zh_debug_keep_raw)"""
         check(lib().zh_debug_keep_raw(self._h, 1 if on else 0))
@@ -876,6 +929,15 @@ class Database:
         dist = self._key_numbers(keys)
         return [(self._documents.get(x), self._documents.get(y), float(v)) for x, y, v in zip(a.tolist(), b.tolist(), dist.tolist())]
 
+    def near_duplicates_forest(self, radius):
+        """near_duplicates among the records that share a leaf of the forest (LSHIndex.self_join_forest: exact keys, approximate candidates)
+        -> what near_duplicates returns, for the pairs the forest finds"""
+        if self.index.no_vectors():
+            return []
+        a, b, keys = self.index.self_join_forest(radius, self.metric)
+        dist = self._key_numbers(keys)
+        return [(self._documents.get(x), self._documents.get(y), float(v)) for x, y, v in zip(a.tolist(), b.tolist(), dist.tolist())]
+
     def _key_numbers(self, keys):
         """the number each key holds, as f64 (for the parity cosine key: the similarity)"""
         if self.metric.metric in _F64_KEYED:
@@ -910,6 +972,15 @@ class Database:
     def deduplicate_within(self, radius):
         """LSHIndex.deduplicate_within, then the removed ids' documents go too -> the removed ids"""
         removed = self.index.deduplicate_within(radius, self.metric)
+        for i in removed.tolist():
+            self._documents.pop(i, None)
+        return removed
+
+    def deduplicate_within_forest(self, radius):
+        """LSHIndex.deduplicate_within_forest, then the removed ids' documents go too -> the removed ids"""
+        if self.index.no_vectors():
+            return np.empty(0, np.uint64)
+        removed = self.index.deduplicate_within_forest(radius, self.metric)
         for i in removed.tolist():
             self._documents.pop(i, None)
         return removed

@@ -503,7 +503,7 @@ static void free_forest(zh_index *ix) {
     }
 }
 
-static void exact_release_scratch(zh_index *ix);
+static void release_scratch(zh_index *ix, unsigned families);  // (the exact family's per-call scratch, below)
 extern "C" void zh_index_destroy(zh_index *ix) {
     if (ix)
         for (auto &ln : ix->lanes) {
@@ -528,10 +528,8 @@ extern "C" void zh_index_destroy(zh_index *ix) {
     ix->row_hn2.release(); ix->row_norm.release(); ix->row_half.release(); ix->row_meta.release(); ix->row_rho_dev.release(); ix->row_half128.release();
     ix->scan_perm.release(); ix->row_leaf_p.release();
     ix->dctx.release_all();
-    DevBuf *ws[] = {&ix->wQ, &ix->wOutIds, &ix->wOutKeys, &ix->wOutCounts, &ix->ex_live, &ix->ex_QQ, &ix->ex_keys, &ix->ex_visits, &ix->ex_cbase,
-                    &ix->ex_ckeys, &ix->ex_cids, &ix->ex_run_ids, &ix->ex_run_keys, &ix->ex_run_counts, &ix->ex_Q, &ix->ex_ids, &ix->ex_kout, &ix->ex_counts,
-                    &ix->ex_bits};
-    exact_release_scratch(ix);
+    DevBuf *ws[] = {&ix->wQ, &ix->wOutIds, &ix->wOutKeys, &ix->wOutCounts, &ix->ex_live, &ix->ex_bits};
+    release_scratch(ix, ~0u);  // every family's
     for (DevBuf *b : ws) b->release();
     if (ix->sweep_stream) hipStreamDestroy(ix->sweep_stream);
     if (ix->stream) hipStreamDestroy(ix->stream);
@@ -3448,6 +3446,141 @@ extern "C" int zh_search_batch(zh_index *ix, const float *q, size_t b, size_t k,
 #define ZH_EXACT_BATCH 1024u             // queries per internal batch
 #define ZH_EXACT_KEY_BYTES (size_t(1) << 30)  // key scratch of one row chunk: queries x rows x 8 bytes
 
+// ---- what the families below share: exact, filtered and range search, self-join, k-NN graph, forest k-NN graph, forest self-join ----
+static hipStream_t call_stream(const zh_index *ix, void *stream) { return stream ? (hipStream_t)stream : ix->stream; }
+
+// the score kernels' parameter: the mode, for the metrics that have one
+static int score_param(int metric, int mode) { return (metric == ZH_COSINE || metric == ZH_MINKOWSKI || metric == ZH_PNORM) ? mode : 0; }
+
+// The per-call scratch, each family's buffers listed once.  The guard of a call gives its set back to the driver however the call returns: an idle
+// index holds only the live-row views (ex_live and ex_bits survive every call; zh_index_destroy frees them).  Every family scans with the exact
+// search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's.
+enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64 };  // one bit per list
+enum : unsigned {
+    SCRATCH_EXACT = SCR_EX,
+    SCRATCH_FILTER = SCR_FL | SCRATCH_EXACT,
+    SCRATCH_RANGE = SCR_RG | SCRATCH_EXACT,
+    SCRATCH_JOIN = SCR_JN | SCRATCH_EXACT,
+    SCRATCH_KNN = SCR_KN | SCRATCH_EXACT,
+    SCRATCH_FKNN = SCR_FK | SCRATCH_KNN,
+    SCRATCH_FJOIN = SCR_FJ | SCRATCH_JOIN | SCRATCH_FKNN,
+};
+static void release_scratch(zh_index *ix, unsigned families) {
+    auto drop = [&](unsigned list, std::initializer_list<DevBuf *> bs) {
+        if (families & list)
+            for (DevBuf *b : bs) b->release();
+    };
+    drop(SCR_EX, {&ix->ex_QQ, &ix->ex_keys, &ix->ex_visits, &ix->ex_cbase, &ix->ex_ckeys, &ix->ex_cids, &ix->ex_run_ids, &ix->ex_run_keys, &ix->ex_run_counts,
+                  &ix->ex_Q, &ix->ex_ids, &ix->ex_kout, &ix->ex_counts, &ix->ex_Qh, &ix->ex_qmeta, &ix->ex_tau, &ix->ex_cnt, &ix->ex_lid, &ix->ex_llo,
+                  &ix->ex_lhi, &ix->ex_scr, &ix->ex_over});
+    drop(SCR_FL, {&ix->fl_filter, &ix->fl_bits, &ix->fl_pos, &ix->fl_bcount, &ix->fl_bexcl, &ix->fl_tmp, &ix->fl_list});
+    drop(SCR_RG, {&ix->rg_maxk, &ix->rg_cnt, &ix->rg_ctr, &ix->rg_pv0, &ix->rg_pv1, &ix->rg_pk0, &ix->rg_pk1, &ix->rg_cand, &ix->rg_tmp, &ix->rg_off,
+                  &ix->rg_oids, &ix->rg_okeys});
+    drop(SCR_JN, {&ix->jn_ctr, &ix->jn_maxk, &ix->jn_tau, &ix->jn_pv0, &ix->jn_pv1, &ix->jn_pk0, &ix->jn_pk1, &ix->jn_qm, &ix->jn_cid, &ix->jn_first,
+                  &ix->jn_cand, &ix->jn_rows, &ix->jn_tmp, &ix->jn_oa, &ix->jn_ob, &ix->jn_okeys});
+    drop(SCR_KN, {&ix->kn_qm, &ix->kn_cid, &ix->kn_pos, &ix->kn_A, &ix->kn_pmeta, &ix->kn_pid, &ix->kn_cbase, &ix->kn_pids, &ix->kn_pkeys, &ix->kn_pcounts,
+                  &ix->kn_oids, &ix->kn_okeys, &ix->kn_ocounts});
+    drop(SCR_FK, {&ix->fk_ntree, &ix->fk_rl, &ix->fk_flag, &ix->fk_excl, &ix->fk_tmp, &ix->fk_rows, &ix->fk_ctr, &ix->fk_lens, &ix->fk_takes, &ix->fk_rbase,
+                  &ix->fk_cbase, &ix->fk_groups, &ix->fk_groff, &ix->fk_segs, &ix->fk_colsrc, &ix->fk_crow, &ix->fk_hrow, &ix->fk_held, &ix->fk_CA,
+                  &ix->fk_cmeta, &ix->fk_cqm, &ix->fk_HA, &ix->fk_hmeta, &ix->fk_qrow, &ix->fk_maxk, &ix->fk_redo, &ix->fk_pos});
+    drop(SCR_FJ, {&ix->fj_leafof, &ix->fj_pieces, &ix->fj_linel, &ix->fj_linek, &ix->fj_segs, &ix->fj_cand});
+}
+struct ScratchGuard {
+    zh_index *ix;
+    unsigned families;
+    ~ScratchGuard() { release_scratch(ix, families); }
+};
+
+// what the last call of a family left for its zh_*_info export
+template <typename Info>
+static int get_info(const zh_index *ix, Info zh_index::*slot, Info *out, const char *who) {
+    if (!ix || !out) return fail(ZH_EINVAL, "%s: null argument", who);
+    zh_index *m = const_cast<zh_index *>(ix);
+    std::lock_guard<std::mutex> lk(m->stats_mu);
+    *out = m->*slot;
+    return ZH_OK;
+}
+
+// Path 2's view of the fp16 copy of the rows: made if need be, and read, under blk_mu -- the caller holds it, for as long as it reads scan_perm on
+// the device.  *have = false: no copy (no room for it, or the per-row scales alone) and path 1 answers.
+struct HalfView {
+    const void *Xh = nullptr;
+    const float2 *rowMeta = nullptr;
+    float rho = 0.f;
+    const uint32_t *perm = nullptr;  // position -> row under a row order, else null
+    uint64_t perm_rows = 0;
+};
+static int half_view(zh_index *ix, HalfView *v, bool *have) {
+    bool ok = false;
+    *have = false;
+    int rc = ensure_row_half(ix, &ok);
+    if (rc) return rc;
+    if (!ok || !ix->row_half.p) return ZH_OK;
+    *have = true;
+    v->Xh = ix->row_half.p; v->rowMeta = ix->row_meta.as<float2>(); v->rho = ix->row_rho;
+    v->perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr; v->perm_rows = ix->perm_rows;
+    return ZH_OK;
+}
+
+// Path 2's per-line lists, B lines of cap slots (exact_batch2, knn_panel2, fknn_batch2): lists_ensure sizes them (and the base table, where the
+// caller's final_kernel reads ex_cbase) and fills e's list members, lists_reset empties them on the stream, list_bases writes a base table, and
+// lists_end reads the counts back and waits.  The tau each line starts from is the caller's.
+static int lists_ensure(zh_index *ix, uint32_t B, uint32_t cap, bool cbase, ZhExact2 *e) {
+    int rc;
+    if ((rc = ix->ex_tau.ensure((size_t)B * 4)) || (rc = ix->ex_cnt.ensure((size_t)B * 4)) || (rc = ix->ex_lid.ensure((size_t)B * cap * 4)) ||
+        (rc = ix->ex_llo.ensure((size_t)B * cap * 4)) || (rc = ix->ex_lhi.ensure((size_t)B * cap * 4)) || (rc = ix->ex_scr.ensure((size_t)B * cap * 12)) ||
+        (rc = ix->ex_over.ensure(8)) || (rc = ix->ex_ckeys.ensure((size_t)B * cap * 8)) || (rc = ix->ex_cids.ensure((size_t)B * cap * 4)) ||
+        (cbase && (rc = ix->ex_cbase.ensure(((size_t)B + 1) * 8))))
+        return rc;
+    e->B = B; e->cap = cap;
+    e->tau = ix->ex_tau.as<uint32_t>(); e->cnt = ix->ex_cnt.as<uint32_t>(); e->over = ix->ex_over.as<uint32_t>();
+    e->lid = ix->ex_lid.as<uint32_t>(); e->llo = ix->ex_llo.as<uint32_t>(); e->lhi = ix->ex_lhi.as<uint32_t>();
+    return ZH_OK;
+}
+static int lists_reset(const ZhExact2 &e, hipStream_t s) {
+    HIPCHK(hipMemsetAsync(e.cnt, 0, (size_t)e.B * 4, s));
+    HIPCHK(hipMemsetAsync(e.over, 0, 8, s));  // (word 1: the filtered scan's skipped tiles)
+    return ZH_OK;
+}
+// the base table of B lines: cb[b] = b * cap for its B + 1 entries, copied to dst.  cb is the caller's: it lives until the caller has waited for the stream
+static int list_bases(void *dst, std::vector<uint64_t> &cb, uint32_t cap, hipStream_t s) {
+    for (size_t b = 0; b < cb.size(); b++) cb[b] = (uint64_t)b * cap;
+    HIPCHK(hipMemcpyAsync(dst, cb.data(), cb.size() * 8, hipMemcpyHostToDevice, s));
+    return ZH_OK;
+}
+// *overflowed: a list ran over and the batch's answer is not valid; otherwise the lines' survivors are added to *survivors
+static int lists_end(const ZhExact2 &e, hipStream_t s, bool *overflowed, uint64_t *survivors, uint64_t *tiles_skipped = nullptr) {
+    const uint32_t B = e.B;
+    std::vector<uint32_t> h_cnt((size_t)B + 2);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), e.cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_cnt.data() + B, e.over, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *overflowed = h_cnt[B] != 0;
+    if (tiles_skipped) *tiles_skipped += h_cnt[B + 1];
+    if (!*overflowed)
+        for (uint32_t b = 0; b < B; b++) *survivors += h_cnt[b];
+    return ZH_OK;
+}
+
+// live rows before stored row `row`; the cursor makes a call's ascending questions one walk over h_dead
+struct LiveCursor {
+    uint64_t row = 0, rank = 0;
+};
+static uint64_t live_before(const zh_index *ix, uint64_t row, LiveCursor *c) {
+    if (row < c->row) *c = LiveCursor{};
+    for (; c->row < row; c->row++) c->rank += !(c->row < ix->h_dead.size() && ix->h_dead[c->row]);
+    return c->rank;
+}
+
+// The forest scans' column tiles per chunk: ZH_FKNN_CHUNK, halved while the launch would not fill the device (about 1024 blocks), never under 8.
+// blocks_at(ch) = the launch's blocks at ch tiles per chunk; its last call is the one for the chunk returned.
+template <typename Blocks>
+static uint32_t fill_chunk(Blocks blocks_at) {
+    uint32_t ch = ZH_FKNN_CHUNK;
+    while (blocks_at(ch) < 1024 && ch > 8) ch /= 2;
+    return ch;
+}
+
 // the ascending live rows (path 1) and the live-row bitmap (path 2) on the device (under mu, exclusive), rebuilt when rows were appended or
 // removed since
 static int exact_live_rows(zh_index *ix) {
@@ -3489,7 +3622,7 @@ static int exact_batch(zh_index *ix, const uint32_t *dLive, uint64_t n_live, con
         (rc = ix->ex_run_ids.ensure((size_t)2 * B * k * 8)) || (rc = ix->ex_run_keys.ensure((size_t)2 * B * k * 8)) ||
         (rc = ix->ex_run_counts.ensure((size_t)2 * B * 4)))
         return rc;
-    const int param = metric == ZH_COSINE ? mode : ((metric == ZH_MINKOWSKI || metric == ZH_PNORM) ? mode : 0);
+    const int param = score_param(metric, mode);
     uint64_t *runIds = ix->ex_run_ids.as<uint64_t>(), *runKeys = ix->ex_run_keys.as<uint64_t>();
     uint32_t *runCounts = ix->ex_run_counts.as<uint32_t>();
     HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
@@ -3529,10 +3662,9 @@ struct ExactFilter {
     uint64_t tiles = 0;               // 16-position tiles of the scan that hold one (by position under a row order)
     const uint32_t *dList = nullptr;  // ... ascending, for path 1 (made when path 1 is first needed: filter_list)
     bool path2 = false;               // the path rule chose path 2 and the fp16 copy is there
-    const uint32_t *dPos = nullptr;   // path 2: the bitmap by position, made for this row order:
-    const uint32_t *perm = nullptr;
-    uint64_t perm_rows = 0;
-    std::vector<uint32_t> cum;        // exclusive sums of the allowed rows per block of positions (blocks + 1 entries)
+    const uint32_t *dPos = nullptr;   // path 2: the bitmap by position, made for the row order of this view:
+    HalfView v;
+    std::vector<uint32_t> cum;       // exclusive sums of the allowed rows per block of positions (blocks + 1 entries)
 };
 static int exact_batch2(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts,
                         hipStream_t s, bool *used, bool *overflowed, uint64_t *survivors, uint64_t *launches, const ExactFilter *f = nullptr,
@@ -3541,38 +3673,24 @@ static int exact_batch2(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, i
     const uint32_t d = ix->opt.dim;
     if (k == 0 || !zh_exact_mfma_supported(d, metric) || (f ? f->n_allowed : ix->ex_n_live) < std::max<uint64_t>(k, 8192)) return ZH_OK;
     int rc;
-    const void *Xh;
-    const float2 *rowMeta;
-    const uint32_t *perm;
-    uint64_t perm_rows;
-    float rho;
+    HalfView v;
+    bool have = false;
     {
         std::lock_guard<std::mutex> lb(ix->blk_mu);
-        bool ok = false;
-        if ((rc = ensure_row_half(ix, &ok))) return rc;
-        if (!ok || !ix->row_half.p) return ZH_OK;  // no room for the fp16 copy: path 1
-        Xh = ix->row_half.p; rowMeta = ix->row_meta.as<float2>(); rho = ix->row_rho;
-        perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr; perm_rows = ix->perm_rows;
+        if ((rc = half_view(ix, &v, &have))) return rc;
     }
-    if (f && (perm != f->perm || perm_rows != f->perm_rows)) return ZH_OK;  // (the row order changed since f->dPos was made: path 1)
+    if (!have) return ZH_OK;
+    if (f && (v.perm != f->v.perm || v.perm_rows != f->v.perm_rows)) return ZH_OK;  // (the row order changed since f->dPos was made: path 1)
     const uint32_t cap = 16384 + 8 * k;  // first chunk (<= max(k, 4096) rows, all listed) + a few growth steps' worth of k
-    if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_Qh.ensure((size_t)B * d * 2)) || (rc = ix->ex_qmeta.ensure((size_t)B * 16)) ||
-        (rc = ix->ex_tau.ensure((size_t)B * 4)) || (rc = ix->ex_cnt.ensure((size_t)B * 4)) || (rc = ix->ex_lid.ensure((size_t)B * cap * 4)) ||
-        (rc = ix->ex_llo.ensure((size_t)B * cap * 4)) || (rc = ix->ex_lhi.ensure((size_t)B * cap * 4)) || (rc = ix->ex_scr.ensure((size_t)B * cap * 12)) ||
-        (rc = ix->ex_over.ensure(8)) || (rc = ix->ex_ckeys.ensure((size_t)B * cap * 8)) || (rc = ix->ex_cids.ensure((size_t)B * cap * 4)) ||
-        (rc = ix->ex_cbase.ensure(((size_t)B + 1) * 8)))
-        return rc;
-    ZhExact2 e{Xh, rowMeta, perm, perm_rows, f ? f->dPos : ix->ex_bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B, zh_approx_bound(metric, d, 1), rho,
-               ix->ex_tau.as<uint32_t>(), ix->ex_cnt.as<uint32_t>(), ix->ex_lid.as<uint32_t>(), ix->ex_llo.as<uint32_t>(), ix->ex_lhi.as<uint32_t>(), cap,
-               ix->ex_over.as<uint32_t>()};
+    if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_Qh.ensure((size_t)B * d * 2)) || (rc = ix->ex_qmeta.ensure((size_t)B * 16))) return rc;
+    ZhExact2 e{v.Xh, v.rowMeta, v.perm, v.perm_rows, f ? f->dPos : ix->ex_bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B,
+               zh_approx_bound(metric, d, 1), v.rho};
+    if ((rc = lists_ensure(ix, B, cap, true, &e))) return rc;
+    std::vector<uint64_t> cb((size_t)B + 1);
     HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
     HIPCHK(zh_launch_qhalf(dQ, B, d, ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), 1, s));
     HIPCHK(hipMemsetAsync(e.tau, 0xFF, (size_t)B * 4, s));
-    HIPCHK(hipMemsetAsync(e.cnt, 0, (size_t)B * 4, s));
-    HIPCHK(hipMemsetAsync(e.over, 0, 8, s));  // (word 1: the filtered scan's skipped tiles)
-    std::vector<uint64_t> cb(B + 1);
-    for (uint32_t b = 0; b <= B; b++) cb[b] = (uint64_t)b * cap;
-    HIPCHK(hipMemcpyAsync(ix->ex_cbase.p, cb.data(), cb.size() * 8, hipMemcpyHostToDevice, s));
+    if ((rc = lists_reset(e, s)) || (rc = list_bases(ix->ex_cbase.p, cb, cap, s))) return rc;
     const uint64_t n = ix->n_rows;  // positions of the copy; removed rows are masked by the bitmap
     uint64_t chunk = (std::max<uint64_t>(k, 4096) + 15) / 16 * 16;
     for (uint64_t p0 = 0; p0 < n && !f; p0 += chunk, chunk *= ZH_EXACT_GROWTH) {
@@ -3597,23 +3715,9 @@ static int exact_batch2(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, i
                                          ix->ex_cids.as<uint32_t>(), s));
     HIPCHK(zh_launch_final(ix->ex_cbase.as<uint64_t>(), B, 1, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), ix->opt.id_base, dIds, dKeys,
                            dCounts, nullptr, s));
-    std::vector<uint32_t> h_cnt(B + 2);
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), e.cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h_cnt.data() + B, e.over, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = lists_end(e, s, overflowed, survivors, tiles_skipped))) return rc;  // (cb is this frame's)
     *used = true;
-    *overflowed = h_cnt[B] != 0;
-    if (tiles_skipped) *tiles_skipped += h_cnt[B + 1];
-    if (!*overflowed)
-        for (uint32_t b = 0; b < B; b++) *survivors += h_cnt[b];
     return ZH_OK;
-}
-
-static void exact_release_scratch(zh_index *ix) {  // the per-call scratch goes back to the driver: an idle index holds only the live-row views
-    DevBuf *bs[] = {&ix->ex_QQ, &ix->ex_keys, &ix->ex_visits, &ix->ex_cbase, &ix->ex_ckeys, &ix->ex_cids, &ix->ex_run_ids, &ix->ex_run_keys,
-                    &ix->ex_run_counts, &ix->ex_Q, &ix->ex_ids, &ix->ex_kout, &ix->ex_counts, &ix->ex_Qh, &ix->ex_qmeta, &ix->ex_tau, &ix->ex_cnt,
-                    &ix->ex_lid, &ix->ex_llo, &ix->ex_lhi, &ix->ex_scr, &ix->ex_over};
-    for (DevBuf *b : bs) b->release();
 }
 
 // one internal batch: path 2 where it serves, path 1 otherwise and for a batch whose path-2 lists ran over
@@ -3636,59 +3740,38 @@ static int exact_args(zh_index *ix, const float *q, size_t b, size_t k, int metr
 }
 
 static void exact_record(zh_index *ix, size_t b, zh_exact_info inf) {
-    exact_release_scratch(ix);
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     inf.batch = b;
     inf.rows_live = ix->ex_n_live;
     ix->ex_info = inf;
 }
 
-extern "C" int zh_search_exact_batch_device(zh_index *ix, const float *d_q, size_t b, size_t k, int metric, int mode, uint64_t *d_out_ids,
-                                            uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
-    int rc = exact_args(ix, d_q, b, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_search_exact_batch_device");
-    if (rc) return rc;
-    if (b == 0) return ZH_OK;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
-    const uint32_t d = ix->opt.dim;
-    zh_exact_info inf{};
-    inf.path = 1;
-    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
-        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
-        if ((rc = exact_one(ix, d_q + b0 * d, nb, (uint32_t)k, metric, mode, d_out_ids + b0 * k, d_out_keys + b0 * k, d_out_counts + b0, s, &inf))) {
-            exact_release_scratch(ix);
-            return rc;
-        }
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    exact_record(ix, b, inf);
-    return ZH_OK;
-}
-
-extern "C" int zh_search_exact_batch(zh_index *ix, const float *q, size_t b, size_t k, int metric, int mode, uint64_t *out_ids,
-                                     uint64_t *out_keys, uint32_t *out_counts) {
-    int rc = exact_args(ix, q, b, k, metric, mode, out_ids, out_keys, out_counts, "zh_search_exact_batch");
-    if (rc) return rc;
-    if (b == 0) return ZH_OK;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    const hipStream_t s = ix->stream;
-    const uint32_t d = ix->opt.dim;
-    const size_t nb_max = std::min<size_t>(ZH_EXACT_BATCH, b);
+// the host entry points' staging: one internal batch of queries in, its answer out
+static int exact_stage(zh_index *ix, size_t b, size_t k) {
+    const size_t nb_max = std::min<size_t>(ZH_EXACT_BATCH, b), d = ix->opt.dim;
+    int rc;
     if ((rc = ix->ex_Q.ensure(nb_max * d * 4)) || (rc = ix->ex_ids.ensure(std::max<size_t>(nb_max * k, 1) * 8)) ||
         (rc = ix->ex_kout.ensure(std::max<size_t>(nb_max * k, 1) * 8)) || (rc = ix->ex_counts.ensure(nb_max * 4)))
         return rc;
-    zh_exact_info inf{};
-    inf.path = 1;
+    return ZH_OK;
+}
+
+// The exact and the filtered search's loop over internal batches of at most ZH_EXACT_BATCH queries; one(dQ, nb, dIds, dKeys, dCounts) answers a
+// batch on device pointers.  host: q and the outputs are HOST arrays -- each batch goes through the staging (exact_stage has run) and is waited
+// for; otherwise they are device arrays, waited for once after the last batch.
+template <typename One>
+static int exact_batches(zh_index *ix, const float *q, size_t b, size_t k, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, bool host,
+                         hipStream_t s, One one) {
+    const uint32_t d = ix->opt.dim;
+    int rc;
     for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
         const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
-        HIPCHK(hipMemcpyAsync(ix->ex_Q.p, q + b0 * d, (size_t)nb * d * 4, hipMemcpyHostToDevice, s));
-        if ((rc = exact_one(ix, ix->ex_Q.as<float>(), nb, (uint32_t)k, metric, mode, ix->ex_ids.as<uint64_t>(), ix->ex_kout.as<uint64_t>(),
-                            ix->ex_counts.as<uint32_t>(), s, &inf))) {
-            exact_release_scratch(ix);
-            return rc;
+        if (!host) {
+            if ((rc = one(q + b0 * d, nb, out_ids + b0 * k, out_keys + b0 * k, out_counts + b0))) return rc;
+            continue;
         }
+        HIPCHK(hipMemcpyAsync(ix->ex_Q.p, q + b0 * d, (size_t)nb * d * 4, hipMemcpyHostToDevice, s));
+        if ((rc = one(ix->ex_Q.as<float>(), nb, ix->ex_ids.as<uint64_t>(), ix->ex_kout.as<uint64_t>(), ix->ex_counts.as<uint32_t>()))) return rc;
         if (k) {
             HIPCHK(hipMemcpyAsync(out_ids + b0 * k, ix->ex_ids.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(out_keys + b0 * k, ix->ex_kout.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, s));
@@ -3696,17 +3779,44 @@ extern "C" int zh_search_exact_batch(zh_index *ix, const float *q, size_t b, siz
         HIPCHK(hipMemcpyAsync(out_counts + b0, ix->ex_counts.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
+    if (!host) HIPCHK(hipStreamSynchronize(s));
+    return ZH_OK;
+}
+
+// both entry points once the arguments have been judged (b > 0)
+static int exact_call(zh_index *ix, const float *q, size_t b, size_t k, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts,
+                      bool host, void *stream) {
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    ScratchGuard guard{ix, SCRATCH_EXACT};
+    const hipStream_t s = call_stream(ix, stream);
+    if (host && (rc = exact_stage(ix, b, k))) return rc;
+    zh_exact_info inf{};
+    inf.path = 1;
+    rc = exact_batches(ix, q, b, k, out_ids, out_keys, out_counts, host, s, [&](const float *dQ, uint32_t nb, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
+        return exact_one(ix, dQ, nb, (uint32_t)k, metric, mode, dIds, dKeys, dCounts, s, &inf);
+    });
+    if (rc) return rc;
     exact_record(ix, b, inf);
     return ZH_OK;
 }
 
-extern "C" int zh_search_exact_info(const zh_index *ix, zh_exact_info *out) {
-    if (!ix || !out) return fail(ZH_EINVAL, "zh_search_exact_info: null argument");
-    zh_index *m = const_cast<zh_index *>(ix);
-    std::lock_guard<std::mutex> lk(m->stats_mu);
-    *out = m->ex_info;
-    return ZH_OK;
+extern "C" int zh_search_exact_batch_device(zh_index *ix, const float *d_q, size_t b, size_t k, int metric, int mode, uint64_t *d_out_ids,
+                                            uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
+    int rc = exact_args(ix, d_q, b, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_search_exact_batch_device");
+    if (rc || b == 0) return rc;
+    return exact_call(ix, d_q, b, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, false, stream);
 }
+
+extern "C" int zh_search_exact_batch(zh_index *ix, const float *q, size_t b, size_t k, int metric, int mode, uint64_t *out_ids,
+                                     uint64_t *out_keys, uint32_t *out_counts) {
+    int rc = exact_args(ix, q, b, k, metric, mode, out_ids, out_keys, out_counts, "zh_search_exact_batch");
+    if (rc || b == 0) return rc;
+    return exact_call(ix, q, b, k, metric, mode, out_ids, out_keys, out_counts, true, nullptr);
+}
+
+extern "C" int zh_search_exact_info(const zh_index *ix, zh_exact_info *out) { return get_info(ix, &zh_index::ex_info, out, "zh_search_exact_info"); }
 
 // ------------------------------------------------------------------------------------------------
 // filtered exact search (zh_filter.hip + the exact search's two paths): only the rows a caller's bitmap allows are ranked
@@ -3719,16 +3829,6 @@ extern "C" int zh_search_exact_info(const zh_index *ix, zh_exact_info *out) {
 // path 1 633.3 ms against path 2 109.9 ms = 5.76; a skipped tile 7 - 18 ns against 11.0 ns per loaded row.  A random tenth of the rows leaves
 // few tiles empty and goes to path 1 (64.8 ms against 88.9); a contiguous tenth goes to path 2 (21.2 ms against 64.6).
 #define ZH_FILTER_PATH1_ROW_COST 5.75
-
-static void filter_release_scratch(zh_index *ix) {
-    exact_release_scratch(ix);
-    DevBuf *bs[] = {&ix->fl_filter, &ix->fl_bits, &ix->fl_pos, &ix->fl_bcount, &ix->fl_bexcl, &ix->fl_tmp, &ix->fl_list};
-    for (DevBuf *b : bs) b->release();
-}
-struct FilterScratchGuard {
-    zh_index *ix;
-    ~FilterScratchGuard() { filter_release_scratch(ix); }
-};
 
 // the ascending list of allowed live rows, from the row bitmap and the blocks' exclusive sums filter_prepare left
 static int filter_list(zh_index *ix, ExactFilter *f, hipStream_t s) {
@@ -3766,16 +3866,12 @@ static int filter_prepare(zh_index *ix, const uint32_t *dFilter, uint64_t n_bits
     f->path2 = forced != 1 && k && zh_exact_mfma_supported(ix->opt.dim, metric) && f->n_allowed >= std::max<uint64_t>(k, 8192);
     if (f->path2) {
         std::lock_guard<std::mutex> lb(ix->blk_mu);
-        bool ok = false;
-        if ((rc = ensure_row_half(ix, &ok))) return rc;
-        f->path2 = ok && ix->row_half.p;
-        f->perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr;
-        f->perm_rows = ix->perm_rows;
+        if ((rc = half_view(ix, &f->v, &f->path2))) return rc;
     }
     f->dPos = ix->fl_bits.as<uint32_t>();
-    if (f->path2 && f->perm) {  // position p holds row perm[p]: the mask once per call in that order, counted per block of positions
+    if (f->path2 && f->v.perm) {  // position p holds row perm[p]: the mask once per call in that order, counted per block of positions
         if ((rc = ix->fl_pos.ensure((n + 63) / 64 * 8))) return rc;
-        HIPCHK(zh_launch_filter_permute(ix->fl_bits.as<uint32_t>(), f->perm, f->perm_rows, n, ix->fl_pos.as<uint32_t>(), ix->fl_bcount.as<uint32_t>(),
+        HIPCHK(zh_launch_filter_permute(ix->fl_bits.as<uint32_t>(), f->v.perm, f->v.perm_rows, n, ix->fl_pos.as<uint32_t>(), ix->fl_bcount.as<uint32_t>(),
                                         excl + nb + 1, ix->fl_tmp.as<uint32_t>(), dTiles, s));
         HIPCHK(hipMemcpyAsync(f->cum.data(), excl + nb + 1, (nb + 1) * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(&h_tiles, dTiles, 4, hipMemcpyDeviceToHost, s));
@@ -3829,73 +3925,48 @@ static void filtered_record(zh_index *ix, size_t b, const ExactFilter &f, zh_fil
     ix->fl_info = inf;
 }
 
+// both entry points once the arguments have been judged (b > 0).  host: q, filter and the outputs are HOST arrays
+static int filtered_call(zh_index *ix, const float *q, size_t b, size_t k, int metric, int mode, const uint32_t *filter, uint64_t n_bits, uint64_t *out_ids,
+                         uint64_t *out_keys, uint32_t *out_counts, bool host, void *stream) {
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = filtered_bits_fit(ix, n_bits))) return rc;
+    ScratchGuard guard{ix, SCRATCH_FILTER};
+    const hipStream_t s = call_stream(ix, stream);
+    if (host) {
+        const size_t fwords = (size_t)((n_bits + 31) / 32);
+        if ((rc = exact_stage(ix, b, k)) || (rc = ix->fl_filter.ensure(std::max<size_t>(fwords, 1) * 4))) return rc;
+        if (fwords) HIPCHK(hipMemcpyAsync(ix->fl_filter.p, filter, fwords * 4, hipMemcpyHostToDevice, s));  // the call's only upload besides the queries
+        filter = ix->fl_filter.as<uint32_t>();
+    }
+    ExactFilter f;
+    if ((rc = filter_prepare(ix, filter, n_bits, (uint32_t)k, metric, s, &f))) return rc;
+    zh_filtered_info inf{};
+    inf.path = 1;
+    rc = exact_batches(ix, q, b, k, out_ids, out_keys, out_counts, host, s, [&](const float *dQ, uint32_t nb, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
+        return filtered_one(ix, &f, dQ, nb, (uint32_t)k, metric, mode, dIds, dKeys, dCounts, s, &inf);
+    });
+    if (rc) return rc;
+    filtered_record(ix, b, f, inf);
+    return ZH_OK;
+}
+
 extern "C" int zh_search_exact_filtered_batch_device(zh_index *ix, const float *d_q, size_t b, size_t k, int metric, int mode, const uint32_t *d_filter,
                                                      uint64_t n_bits, uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
     int rc = filtered_args(ix, d_q, b, k, metric, mode, d_filter, n_bits, d_out_ids, d_out_keys, d_out_counts, "zh_search_exact_filtered_batch_device");
-    if (rc) return rc;
-    if (b == 0) return ZH_OK;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = filtered_bits_fit(ix, n_bits))) return rc;
-    FilterScratchGuard guard{ix};
-    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
-    const uint32_t d = ix->opt.dim;
-    ExactFilter f;
-    if ((rc = filter_prepare(ix, d_filter, n_bits, (uint32_t)k, metric, s, &f))) return rc;
-    zh_filtered_info inf{};
-    inf.path = 1;
-    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
-        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
-        if ((rc = filtered_one(ix, &f, d_q + b0 * d, nb, (uint32_t)k, metric, mode, d_out_ids + b0 * k, d_out_keys + b0 * k, d_out_counts + b0, s, &inf)))
-            return rc;
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    filtered_record(ix, b, f, inf);
-    return ZH_OK;
+    if (rc || b == 0) return rc;
+    return filtered_call(ix, d_q, b, k, metric, mode, d_filter, n_bits, d_out_ids, d_out_keys, d_out_counts, false, stream);
 }
 
 extern "C" int zh_search_exact_filtered_batch(zh_index *ix, const float *q, size_t b, size_t k, int metric, int mode, const uint32_t *filter,
                                               uint64_t n_bits, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts) {
     int rc = filtered_args(ix, q, b, k, metric, mode, filter, n_bits, out_ids, out_keys, out_counts, "zh_search_exact_filtered_batch");
-    if (rc) return rc;
-    if (b == 0) return ZH_OK;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = filtered_bits_fit(ix, n_bits))) return rc;
-    FilterScratchGuard guard{ix};
-    const hipStream_t s = ix->stream;
-    const uint32_t d = ix->opt.dim;
-    const size_t nb_max = std::min<size_t>(ZH_EXACT_BATCH, b), fwords = (size_t)((n_bits + 31) / 32);
-    if ((rc = ix->ex_Q.ensure(nb_max * d * 4)) || (rc = ix->ex_ids.ensure(std::max<size_t>(nb_max * k, 1) * 8)) ||
-        (rc = ix->ex_kout.ensure(std::max<size_t>(nb_max * k, 1) * 8)) || (rc = ix->ex_counts.ensure(nb_max * 4)) ||
-        (rc = ix->fl_filter.ensure(std::max<size_t>(fwords, 1) * 4)))
-        return rc;
-    if (fwords) HIPCHK(hipMemcpyAsync(ix->fl_filter.p, filter, fwords * 4, hipMemcpyHostToDevice, s));  // the call's only upload besides the queries
-    ExactFilter f;
-    if ((rc = filter_prepare(ix, ix->fl_filter.as<uint32_t>(), n_bits, (uint32_t)k, metric, s, &f))) return rc;
-    zh_filtered_info inf{};
-    inf.path = 1;
-    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
-        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
-        HIPCHK(hipMemcpyAsync(ix->ex_Q.p, q + b0 * d, (size_t)nb * d * 4, hipMemcpyHostToDevice, s));
-        if ((rc = filtered_one(ix, &f, ix->ex_Q.as<float>(), nb, (uint32_t)k, metric, mode, ix->ex_ids.as<uint64_t>(), ix->ex_kout.as<uint64_t>(),
-                               ix->ex_counts.as<uint32_t>(), s, &inf)))
-            return rc;
-        if (k) {
-            HIPCHK(hipMemcpyAsync(out_ids + b0 * k, ix->ex_ids.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(out_keys + b0 * k, ix->ex_kout.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipMemcpyAsync(out_counts + b0, ix->ex_counts.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    filtered_record(ix, b, f, inf);
-    return ZH_OK;
+    if (rc || b == 0) return rc;
+    return filtered_call(ix, q, b, k, metric, mode, filter, n_bits, out_ids, out_keys, out_counts, true, nullptr);
 }
 
 extern "C" int zh_search_filtered_info(const zh_index *ix, zh_filtered_info *out) {
-    if (!ix || !out) return fail(ZH_EINVAL, "zh_search_filtered_info: null argument");
-    zh_index *m = const_cast<zh_index *>(ix);
-    std::lock_guard<std::mutex> lk(m->stats_mu);
-    *out = m->fl_info;
-    return ZH_OK;
+    return get_info(ix, &zh_index::fl_info, out, "zh_search_filtered_info");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3903,16 +3974,6 @@ extern "C" int zh_search_filtered_info(const zh_index *ix, zh_filtered_info *out
 // ------------------------------------------------------------------------------------------------
 #define ZH_RANGE_CAND_FLOOR 4096u  // path 2: candidate slots per query that are there whatever the capacity (a count-only call still lists candidates)
 
-static void range_release_scratch(zh_index *ix) {
-    exact_release_scratch(ix);
-    DevBuf *bs[] = {&ix->rg_maxk, &ix->rg_cnt, &ix->rg_ctr, &ix->rg_pv0, &ix->rg_pv1, &ix->rg_pk0, &ix->rg_pk1, &ix->rg_cand, &ix->rg_tmp, &ix->rg_off,
-                    &ix->rg_oids, &ix->rg_okeys};
-    for (DevBuf *b : bs) b->release();
-}
-struct RangeScratchGuard {
-    zh_index *ix;
-    ~RangeScratchGuard() { range_release_scratch(ix); }
-};
 struct RangeRun {
     uint64_t capacity = 0;
     uint64_t total = 0;  // hits of the internal batches so far
@@ -3927,7 +3988,7 @@ static int range_batch1(zh_index *ix, const float *dQ, uint32_t B, const uint64_
     const uint64_t rc_rows = std::min<uint64_t>(std::max<uint64_t>(256, ZH_EXACT_KEY_BYTES / 8 / B), n_live);
     int rc;
     if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_keys.ensure((size_t)B * rc_rows * 8))) return rc;
-    const int param = metric == ZH_COSINE ? mode : ((metric == ZH_MINKOWSKI || metric == ZH_PNORM) ? mode : 0);
+    const int param = score_param(metric, mode);
     HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
     HIPCHK(hipMemsetAsync(ix->rg_cnt.p, 0, (size_t)B * 4, s));
     HIPCHK(hipMemsetAsync(ix->rg_ctr.p, 0, 16, s));
@@ -3951,23 +4012,17 @@ static int range_batch2(zh_index *ix, const float *dQ, uint32_t B, const uint64_
     const uint32_t d = ix->opt.dim;
     if (!zh_exact_mfma_supported(d, metric) || ix->ex_n_live < 8192) return ZH_OK;
     int rc;
-    const void *Xh;
-    const float2 *rowMeta;
-    const uint32_t *perm;
-    uint64_t perm_rows;
-    float rho;
+    HalfView v;
+    bool have = false;
     {
         std::lock_guard<std::mutex> lb(ix->blk_mu);
-        bool ok = false;
-        if ((rc = ensure_row_half(ix, &ok))) return rc;
-        if (!ok || !ix->row_half.p) return ZH_OK;  // no room for the fp16 copy: path 1
-        Xh = ix->row_half.p; rowMeta = ix->row_meta.as<float2>(); rho = ix->row_rho;
-        perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr; perm_rows = ix->perm_rows;
+        if ((rc = half_view(ix, &v, &have))) return rc;
     }
+    if (!have) return ZH_OK;
     if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_Qh.ensure((size_t)B * d * 2)) || (rc = ix->ex_qmeta.ensure((size_t)B * 16)) ||
         (rc = ix->ex_tau.ensure((size_t)B * 4)) || (rc = ix->rg_cand.ensure(cand_cap * 8)))
         return rc;
-    ZhExact2 e{Xh, rowMeta, perm, perm_rows, ix->ex_bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B, zh_approx_bound(metric, d, 1), rho,
+    ZhExact2 e{v.Xh, v.rowMeta, v.perm, v.perm_rows, ix->ex_bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B, zh_approx_bound(metric, d, 1), v.rho,
                ix->ex_tau.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     unsigned long long *ctr = ix->rg_ctr.as<unsigned long long>();
     HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
@@ -4067,8 +4122,8 @@ extern "C" int zh_search_range_batch_device(zh_index *ix, const float *d_q, size
     if (rc) return rc;
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    RangeScratchGuard guard{ix};
-    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    ScratchGuard guard{ix, SCRATCH_RANGE};
+    const hipStream_t s = call_stream(ix, stream);
     const uint32_t d = ix->opt.dim;
     RangeRun run;
     run.capacity = capacity;
@@ -4093,7 +4148,7 @@ extern "C" int zh_search_range_batch(zh_index *ix, const float *q, size_t b, con
     if (b == 0) return ZH_OK;
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    RangeScratchGuard guard{ix};
+    ScratchGuard guard{ix, SCRATCH_RANGE};
     const hipStream_t s = ix->stream;
     const uint32_t d = ix->opt.dim;
     const size_t nb_max = std::min<size_t>(ZH_EXACT_BATCH, b);
@@ -4116,30 +4171,13 @@ extern "C" int zh_search_range_batch(zh_index *ix, const float *q, size_t b, con
     return range_finish(ix, b, run, inf, "zh_search_range_batch");
 }
 
-extern "C" int zh_search_range_info(const zh_index *ix, zh_range_info *out) {
-    if (!ix || !out) return fail(ZH_EINVAL, "zh_search_range_info: null argument");
-    zh_index *m = const_cast<zh_index *>(ix);
-    std::lock_guard<std::mutex> lk(m->stats_mu);
-    *out = m->rg_info;
-    return ZH_OK;
-}
+extern "C" int zh_search_range_info(const zh_index *ix, zh_range_info *out) { return get_info(ix, &zh_index::rg_info, out, "zh_search_range_info"); }
 
 // ------------------------------------------------------------------------------------------------
 // exact self-join (zh_join.hip + the exact search's score kernel): every pair of live rows a < b with key(stored b, query a) <= one threshold key,
 // as three arrays ascending by (a, key, b).  DESIGN.md s15
 // ------------------------------------------------------------------------------------------------
 #define ZH_JOIN_CAND_FLOOR 256u  // path 2: candidate slots per held row of a panel that are there whatever the capacity (a count-only call still lists candidates)
-
-static void join_release_scratch(zh_index *ix) {
-    exact_release_scratch(ix);
-    DevBuf *bs[] = {&ix->jn_ctr, &ix->jn_maxk, &ix->jn_tau, &ix->jn_pv0, &ix->jn_pv1, &ix->jn_pk0, &ix->jn_pk1, &ix->jn_qm, &ix->jn_cid, &ix->jn_first,
-                    &ix->jn_cand, &ix->jn_rows, &ix->jn_tmp, &ix->jn_oa, &ix->jn_ob, &ix->jn_okeys};
-    for (DevBuf *b : bs) b->release();
-}
-struct JoinScratchGuard {
-    zh_index *ix;
-    ~JoinScratchGuard() { join_release_scratch(ix); }
-};
 
 // Path 1 for the B <= ZH_EXACT_BATCH query rows dQRows (row numbers, device): gathered into the query buffer, exact_score_kernel's keys of the live
 // rows from position p_from of the ascending live list on (no live row before it is above any of the query rows), join_collect_kernel over them.
@@ -4152,7 +4190,7 @@ static int join_batch1(zh_index *ix, const uint32_t *dQRows, uint32_t B, uint64_
     const uint64_t rc_rows = std::min<uint64_t>(std::max<uint64_t>(256, ZH_EXACT_KEY_BYTES / 8 / B), n_live - p_from);
     int rc;
     if ((rc = ix->ex_Q.ensure((size_t)B * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_keys.ensure((size_t)B * rc_rows * 8))) return rc;
-    const int param = metric == ZH_COSINE ? mode : ((metric == ZH_MINKOWSKI || metric == ZH_PNORM) ? mode : 0);
+    const int param = score_param(metric, mode);
     HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dQRows, B, ix->ex_Q.as<float>(), s));
     HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), B, d, ix->ex_QQ.as<float>(), s));
     for (uint64_t p0 = p_from; p0 < n_live; p0 += rc_rows) {
@@ -4176,19 +4214,13 @@ static int join_path2(zh_index *ix, uint64_t max_key, int metric, int mode, uint
     const uint32_t d = ix->opt.dim;
     if (!zh_exact_mfma_supported(d, metric) || ix->ex_n_live < 8192) return ZH_OK;
     int rc;
-    const void *Xh;
-    const float2 *rowMeta;
-    const uint32_t *perm;
-    uint64_t perm_rows;
-    float rho;
+    HalfView v;
+    bool have = false;
     {
         std::lock_guard<std::mutex> lb(ix->blk_mu);
-        bool ok = false;
-        if ((rc = ensure_row_half(ix, &ok))) return rc;
-        if (!ok || !ix->row_half.p) return ZH_OK;  // no room for the fp16 copy: path 1
-        Xh = ix->row_half.p; rowMeta = ix->row_meta.as<float2>(); rho = ix->row_rho;
-        perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr; perm_rows = ix->perm_rows;
+        if ((rc = half_view(ix, &v, &have))) return rc;
     }
+    if (!have) return ZH_OK;
     const uint64_t n = ix->n_rows, T = (n + 15) / 16, n_pos = T * 16;
     const uint32_t n_ab_max = ZH_JOIN_PANEL_ROWS / 64;
     if ((rc = ix->jn_qm.ensure(n_pos * 16)) || (rc = ix->jn_cid.ensure(n_pos * 4)) || (rc = ix->jn_tau.ensure(4)) || (rc = ix->jn_maxk.ensure(8)) ||
@@ -4197,13 +4229,13 @@ static int join_path2(zh_index *ix, uint64_t max_key, int metric, int mode, uint
     unsigned long long *ctr = ix->jn_ctr.as<unsigned long long>();  // {hits, the panel's candidates, a redone panel's rows}
     HIPCHK(hipMemcpyAsync(ix->jn_maxk.p, &max_key, 8, hipMemcpyHostToDevice, s));
     HIPCHK(zh_launch_range_tau(ix->jn_maxk.as<uint64_t>(), 1, metric, mode, ix->jn_tau.as<uint32_t>(), s));
-    HIPCHK(zh_launch_join_prep(rowMeta, perm, perm_rows, ix->ex_bits.as<uint32_t>(), n, rho, ix->jn_qm.as<float4>(), ix->jn_cid.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_prep(v.rowMeta, v.perm, v.perm_rows, ix->ex_bits.as<uint32_t>(), n, v.rho, ix->jn_qm.as<float4>(), ix->jn_cid.as<uint32_t>(), s));
     HIPCHK(hipStreamSynchronize(s));  // (max_key is the caller's stack)
     *used = true;
     inf->path = 2;
     const float Kc = zh_approx_bound(metric, d, 1);
     std::vector<uint32_t> first(n_ab_max + 1);
-    uint64_t rank_row = 0, rank = 0;  // live rows before row rank_row (id order: a redone panel's first chunk)
+    LiveCursor live;  // (id order: a redone panel's first chunk)
     for (uint64_t P0 = 0; P0 < n; P0 += ZH_JOIN_PANEL_ROWS) {
         const uint64_t P1 = std::min<uint64_t>(n, P0 + ZH_JOIN_PANEL_ROWS), tileA0 = P0 / 16, tileA1 = (P1 + 15) / 16;
         const uint32_t n_ab = (uint32_t)((tileA1 - tileA0 + 3) / 4);
@@ -4213,8 +4245,8 @@ static int join_path2(zh_index *ix, uint64_t max_key, int metric, int mode, uint
         if ((rc = ix->jn_cand.ensure(cand_cap * 8))) return rc;
         HIPCHK(hipMemcpyAsync(ix->jn_first.p, first.data(), ((size_t)n_ab + 1) * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemsetAsync(ctr + 1, 0, 16, s));
-        HIPCHK(zh_launch_join_mfma(d, metric, mode, Xh, rowMeta, ix->jn_qm.as<float4>(), ix->jn_cid.as<uint32_t>(), n, tileA0, ix->jn_first.as<uint32_t>(), n_ab,
-                                   first[n_ab], Kc, rho, ix->jn_tau.as<uint32_t>(), ix->jn_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
+        HIPCHK(zh_launch_join_mfma(d, metric, mode, v.Xh, v.rowMeta, ix->jn_qm.as<float4>(), ix->jn_cid.as<uint32_t>(), n, tileA0, ix->jn_first.as<uint32_t>(), n_ab,
+                                   first[n_ab], Kc, v.rho, ix->jn_tau.as<uint32_t>(), ix->jn_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
         inf->launches++;
         inf->tiles += products;
         HIPCHK(zh_launch_join_survivors(ix->X.as<float>(), d, metric, mode, ix->jn_cand.as<uint64_t>(), ctr + 1, cand_cap, max_key, ctr,
@@ -4228,7 +4260,7 @@ static int join_path2(zh_index *ix, uint64_t max_key, int metric, int mode, uint
             continue;
         }
         inf->redone++;
-        if (perm_rows) {
+        if (v.perm_rows) {
             // Under a row order a panel owns its pairs by POSITION (the lower position lies in it), and path 1 owns pairs by row number: the
             // redo below would count a different set.  So nothing of path 2 is kept: counters and pool rewound, the whole call answered by path 1.
             HIPCHK(hipMemsetAsync(ctr, 0, 32, s));
@@ -4243,8 +4275,7 @@ static int join_path2(zh_index *ix, uint64_t max_key, int metric, int mode, uint
         HIPCHK(hipStreamSynchronize(s));
         // positions are row numbers here: the panel's pairs by position are its pairs by row number, and the live rows before the panel are
         // below every row of it
-        for (; rank_row < P0; rank_row++) rank += !(rank_row < ix->h_dead.size() && ix->h_dead[rank_row]);
-        const uint64_t p_from = rank;
+        const uint64_t p_from = live_before(ix, P0, &live);
         for (uint64_t b0 = 0; b0 < h_ctr[2]; b0 += ZH_EXACT_BATCH) {
             const uint32_t nb = (uint32_t)std::min<uint64_t>(ZH_EXACT_BATCH, h_ctr[2] - b0);
             if ((rc = join_batch1(ix, ix->jn_rows.as<uint32_t>() + b0, nb, p_from, max_key, metric, mode, pool_cap, s, &inf->launches))) return rc;
@@ -4260,6 +4291,44 @@ static int join_args(zh_index *ix, int metric, int mode, uint64_t capacity, cons
                      const char *who) {
     if (!ix || !total || (capacity && (!a || !b || !keys))) return fail(ZH_EINVAL, "%s: null argument", who);
     return check_metric(metric, mode);
+}
+
+// What both joins do once the hits are pooled in jn_pv0 / jn_pk0 and counted: *total = hits, exact whatever the capacity; within it, the pool ordered
+// into outA / outB / outKeys (host_out: HOST arrays, filled through staging; otherwise device arrays) and waited for; the info written; ZH_ELIMIT
+// past the capacity.
+template <typename Info>
+static int join_finish(zh_index *ix, uint64_t hits, uint64_t capacity, uint64_t *outA, uint64_t *outB, uint64_t *outKeys, bool host_out, hipStream_t s,
+                       uint64_t *total, Info inf, Info zh_index::*slot, const char *who) {
+    *total = hits;
+    inf.pairs = hits;
+    const bool over = hits > capacity;
+    int rc;
+    if (!over && hits) {
+        uint64_t *dV[2] = {nullptr, nullptr}, *dK[2] = {nullptr, nullptr};
+        size_t tmp_bytes = 0;
+        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, nullptr, &tmp_bytes, 0, nullptr, nullptr, nullptr, s));
+        if ((rc = ix->jn_pv1.ensure(hits * 8)) || (rc = ix->jn_pk1.ensure(hits * 8)) || (rc = ix->jn_tmp.ensure(tmp_bytes))) return rc;
+        if (host_out && ((rc = ix->jn_oa.ensure(hits * 8)) || (rc = ix->jn_ob.ensure(hits * 8)) || (rc = ix->jn_okeys.ensure(hits * 8)))) return rc;
+        dV[0] = ix->jn_pv0.as<uint64_t>(); dV[1] = ix->jn_pv1.as<uint64_t>();
+        dK[0] = ix->jn_pk0.as<uint64_t>(); dK[1] = ix->jn_pk1.as<uint64_t>();
+        uint64_t *oa = host_out ? ix->jn_oa.as<uint64_t>() : outA, *ob = host_out ? ix->jn_ob.as<uint64_t>() : outB;
+        uint64_t *ok = host_out ? ix->jn_okeys.as<uint64_t>() : outKeys;
+        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, ix->jn_tmp.p, &tmp_bytes, ix->opt.id_base, oa, ob, ok, s));
+        if (host_out) {
+            HIPCHK(hipMemcpyAsync(outA, oa, hits * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(outB, ob, hits * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(outKeys, ok, hits * 8, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        ix->*slot = inf;
+    }
+    if (over)
+        return fail(ZH_ELIMIT, "%s: %llu pairs exceed the capacity of %llu; out_total is exact, call again with that capacity", who,
+                    (unsigned long long)hits, (unsigned long long)capacity);
+    return ZH_OK;
 }
 
 // The call on the index's device (under mu, exclusive; exact_live_rows has run).  host_out: outA / outB / outKeys are HOST arrays, filled through
@@ -4292,35 +4361,7 @@ static int join_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint64
             hits = h;
         }
     }
-    *total = hits;
-    inf.pairs = hits;
-    const bool over = hits > capacity;
-    if (!over && hits) {
-        uint64_t *dV[2] = {nullptr, nullptr}, *dK[2] = {nullptr, nullptr};
-        size_t tmp_bytes = 0;
-        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, nullptr, &tmp_bytes, 0, nullptr, nullptr, nullptr, s));
-        if ((rc = ix->jn_pv1.ensure(hits * 8)) || (rc = ix->jn_pk1.ensure(hits * 8)) || (rc = ix->jn_tmp.ensure(tmp_bytes))) return rc;
-        if (host_out && ((rc = ix->jn_oa.ensure(hits * 8)) || (rc = ix->jn_ob.ensure(hits * 8)) || (rc = ix->jn_okeys.ensure(hits * 8)))) return rc;
-        dV[0] = ix->jn_pv0.as<uint64_t>(); dV[1] = ix->jn_pv1.as<uint64_t>();
-        dK[0] = ix->jn_pk0.as<uint64_t>(); dK[1] = ix->jn_pk1.as<uint64_t>();
-        uint64_t *oa = host_out ? ix->jn_oa.as<uint64_t>() : outA, *ob = host_out ? ix->jn_ob.as<uint64_t>() : outB;
-        uint64_t *ok = host_out ? ix->jn_okeys.as<uint64_t>() : outKeys;
-        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, ix->jn_tmp.p, &tmp_bytes, ix->opt.id_base, oa, ob, ok, s));
-        if (host_out) {
-            HIPCHK(hipMemcpyAsync(outA, oa, hits * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(outB, ob, hits * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(outKeys, ok, hits * 8, hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    {
-        std::lock_guard<std::mutex> lk(ix->stats_mu);
-        ix->jn_info = inf;
-    }
-    if (over)
-        return fail(ZH_ELIMIT, "%s: %llu pairs exceed the capacity of %llu; out_total is exact, call again with that capacity", who,
-                    (unsigned long long)hits, (unsigned long long)capacity);
-    return ZH_OK;
+    return join_finish(ix, hits, capacity, outA, outB, outKeys, host_out, s, total, inf, &zh_index::jn_info, who);
 }
 
 extern "C" int zh_self_join_device(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *d_out_a, uint64_t *d_out_b,
@@ -4329,8 +4370,8 @@ extern "C" int zh_self_join_device(zh_index *ix, uint64_t max_key, int metric, i
     if (rc) return rc;
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    JoinScratchGuard guard{ix};
-    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    ScratchGuard guard{ix, SCRATCH_JOIN};
+    const hipStream_t s = call_stream(ix, stream);
     uint64_t total = 0;
     rc = join_run(ix, max_key, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, false, s, &total, "zh_self_join_device");
     if (rc && rc != ZH_ELIMIT) return rc;
@@ -4346,7 +4387,7 @@ extern "C" int zh_self_join(zh_index *ix, uint64_t max_key, int metric, int mode
     *out_total = 0;
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    JoinScratchGuard guard{ix};
+    ScratchGuard guard{ix, SCRATCH_JOIN};
     uint64_t total = 0;
     rc = join_run(ix, max_key, metric, mode, capacity, out_a, out_b, out_keys, true, ix->stream, &total, "zh_self_join");
     if (rc && rc != ZH_ELIMIT) return rc;
@@ -4354,38 +4395,20 @@ extern "C" int zh_self_join(zh_index *ix, uint64_t max_key, int metric, int mode
     return rc;
 }
 
-extern "C" int zh_self_join_info(const zh_index *ix, zh_join_info *out) {
-    if (!ix || !out) return fail(ZH_EINVAL, "zh_self_join_info: null argument");
-    zh_index *m = const_cast<zh_index *>(ix);
-    std::lock_guard<std::mutex> lk(m->stats_mu);
-    *out = m->jn_info;
-    return ZH_OK;
-}
+extern "C" int zh_self_join_info(const zh_index *ix, zh_join_info *out) { return get_info(ix, &zh_index::jn_info, out, "zh_self_join_info"); }
 
 // ------------------------------------------------------------------------------------------------
 // exact k-NN graph (zh_knn.hip + the exact search's two paths): each live row's k nearest OTHER live rows, slab by slab.  DESIGN.md s16
 // ------------------------------------------------------------------------------------------------
 #define ZH_KNN_HOST_SLAB 65536u  // lines the host call stages at a time
 
-static void knn_release_scratch(zh_index *ix) {
-    exact_release_scratch(ix);
-    DevBuf *bs[] = {&ix->kn_qm, &ix->kn_cid, &ix->kn_pos, &ix->kn_A, &ix->kn_pmeta, &ix->kn_pid, &ix->kn_cbase, &ix->kn_pids, &ix->kn_pkeys, &ix->kn_pcounts,
-                    &ix->kn_oids, &ix->kn_okeys, &ix->kn_ocounts};
-    for (DevBuf *b : bs) b->release();
-}
-struct KnnScratchGuard {
-    zh_index *ix;
-    ~KnnScratchGuard() { knn_release_scratch(ix); }
-};
-
 struct KnnRun {  // what a call settles once, before its slabs
     bool path2 = false;
-    const void *Xh = nullptr;
-    const float2 *rowMeta = nullptr;
+    HalfView v;
     const uint32_t *pos = nullptr;  // row -> position under a row order, else null
-    float rho = 0.f, Kc = 0.f;
+    float Kc = 0.f;
     uint32_t cap = 0;               // list slots per line
-    uint64_t rank_row = 0, rank = 0;  // live rows before stored row rank_row (the slabs of a call ascend)
+    LiveCursor live;                // (the slabs of a call ascend)
 };
 
 // The gate of path 2 and its per-call views: the copy's rows as approx_interval's queries (zh_launch_join_prep), the row -> position map under a
@@ -4396,30 +4419,26 @@ static int knn_setup(zh_index *ix, uint32_t k, int metric, int mode, hipStream_t
     if (env_p && atoi(env_p) == 1) return ZH_OK;
     if (!zh_exact_mfma_supported(d, metric) || ix->ex_n_live < std::max<uint64_t>((uint64_t)k + 1, 8192)) return ZH_OK;
     int rc;
-    const uint32_t *perm;
-    uint64_t perm_rows;
+    HalfView &v = run->v;
+    bool have = false;
     {
         std::lock_guard<std::mutex> lb(ix->blk_mu);
-        bool ok = false;
-        if ((rc = ensure_row_half(ix, &ok))) return rc;
-        if (!ok || !ix->row_half.p) return ZH_OK;  // no copy (no room, or the per-row scales alone): path 1
-        run->Xh = ix->row_half.p; run->rowMeta = ix->row_meta.as<float2>(); run->rho = ix->row_rho;
-        perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr; perm_rows = ix->perm_rows;
+        if ((rc = half_view(ix, &v, &have))) return rc;
     }
+    if (!have) return ZH_OK;
     const uint64_t n = ix->n_rows, n_pos = (n + 15) / 16 * 16;
     run->cap = 16384 + 8 * k;
     const char *env_c = getenv("ZH_KNN_LIST_CAP");
     if (env_c && atoi(env_c) > 0) run->cap = std::min<uint32_t>(run->cap, (uint32_t)atoi(env_c));
     if ((rc = ix->kn_qm.ensure(n_pos * 16)) || (rc = ix->kn_cid.ensure(n_pos * 4)) || (rc = ix->kn_cbase.ensure((ZH_KNN_PANEL_ROWS + 1) * 8))) return rc;
-    HIPCHK(zh_launch_join_prep(run->rowMeta, perm, perm_rows, ix->ex_bits.as<uint32_t>(), n, run->rho, ix->kn_qm.as<float4>(), ix->kn_cid.as<uint32_t>(), s));
-    if (perm_rows) {
+    HIPCHK(zh_launch_join_prep(v.rowMeta, v.perm, v.perm_rows, ix->ex_bits.as<uint32_t>(), n, v.rho, ix->kn_qm.as<float4>(), ix->kn_cid.as<uint32_t>(), s));
+    if (v.perm_rows) {
         if ((rc = ix->kn_pos.ensure(n * 4))) return rc;
         HIPCHK(zh_launch_knn_rowpos(ix->kn_cid.as<uint32_t>(), n_pos, ix->kn_pos.as<uint32_t>(), s));
         run->pos = ix->kn_pos.as<uint32_t>();
     }
     std::vector<uint64_t> cb(ZH_KNN_PANEL_ROWS + 1);
-    for (uint32_t b = 0; b <= ZH_KNN_PANEL_ROWS; b++) cb[b] = (uint64_t)b * run->cap;
-    HIPCHK(hipMemcpyAsync(ix->kn_cbase.p, cb.data(), cb.size() * 8, hipMemcpyHostToDevice, s));
+    if ((rc = list_bases(ix->kn_cbase.p, cb, run->cap, s))) return rc;
     HIPCHK(hipStreamSynchronize(s));  // (cb is this frame's)
     run->Kc = zh_approx_bound(metric, d, 1);
     run->path2 = true;
@@ -4431,22 +4450,16 @@ static int knn_setup(zh_index *ix, uint32_t k, int metric, int mode, hipStream_t
 static int knn_panel2(zh_index *ix, const KnnRun &run, const uint32_t *dRows, uint32_t B, uint32_t k, int metric, int mode, hipStream_t s, bool *overflowed,
                       zh_knn_info *inf) {
     const uint32_t d = ix->opt.dim, cap = run.cap, PT = (B + 15) / 16;
+    ZhExact2 e{run.v.Xh, run.v.rowMeta, nullptr, 0, ix->ex_bits.as<uint32_t>(), nullptr, nullptr, B, run.Kc, run.v.rho};
     int rc;
     if ((rc = ix->kn_A.ensure((size_t)PT * 16 * d * 2)) || (rc = ix->kn_pmeta.ensure((size_t)PT * 16 * 8)) || (rc = ix->kn_pid.ensure((size_t)PT * 16 * 4)) ||
-        (rc = ix->ex_Q.ensure((size_t)B * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_tau.ensure((size_t)B * 4)) ||
-        (rc = ix->ex_cnt.ensure((size_t)B * 4)) || (rc = ix->ex_lid.ensure((size_t)B * cap * 4)) || (rc = ix->ex_llo.ensure((size_t)B * cap * 4)) ||
-        (rc = ix->ex_lhi.ensure((size_t)B * cap * 4)) || (rc = ix->ex_scr.ensure((size_t)B * cap * 12)) || (rc = ix->ex_over.ensure(8)) ||
-        (rc = ix->ex_ckeys.ensure((size_t)B * cap * 8)) || (rc = ix->ex_cids.ensure((size_t)B * cap * 4)))
+        (rc = ix->ex_Q.ensure((size_t)B * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = lists_ensure(ix, B, cap, false, &e)))
         return rc;
-    ZhExact2 e{run.Xh, run.rowMeta, nullptr, 0, ix->ex_bits.as<uint32_t>(), nullptr, nullptr, B, run.Kc, run.rho,
-               ix->ex_tau.as<uint32_t>(), ix->ex_cnt.as<uint32_t>(), ix->ex_lid.as<uint32_t>(), ix->ex_llo.as<uint32_t>(), ix->ex_lhi.as<uint32_t>(), cap,
-               ix->ex_over.as<uint32_t>()};
-    HIPCHK(zh_launch_knn_panel(d, run.Xh, run.rowMeta, run.pos, dRows, B, ix->kn_A.p, ix->kn_pmeta.as<float2>(), ix->kn_pid.as<uint32_t>(), s));
+    HIPCHK(zh_launch_knn_panel(d, run.v.Xh, run.v.rowMeta, run.pos, dRows, B, ix->kn_A.p, ix->kn_pmeta.as<float2>(), ix->kn_pid.as<uint32_t>(), s));
     HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dRows, B, ix->ex_Q.as<float>(), s));
     HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), B, d, ix->ex_QQ.as<float>(), s));
     HIPCHK(hipMemsetAsync(e.tau, 0xFF, (size_t)B * 4, s));
-    HIPCHK(hipMemsetAsync(e.cnt, 0, (size_t)B * 4, s));
-    HIPCHK(hipMemsetAsync(e.over, 0, 8, s));
+    if ((rc = lists_reset(e, s))) return rc;
     const uint64_t n = ix->n_rows;  // positions of the copy; removed rows are masked by the id word
     uint64_t chunk = (std::max<uint64_t>((uint64_t)k + 1, 4096) + 15) / 16 * 16;
     for (uint64_t p0 = 0; p0 < n; p0 += chunk, chunk *= ZH_EXACT_GROWTH) {
@@ -4461,14 +4474,7 @@ static int knn_panel2(zh_index *ix, const KnnRun &run, const uint32_t *dRows, ui
                                          ix->ex_cids.as<uint32_t>(), s));
     HIPCHK(zh_launch_final(ix->kn_cbase.as<uint64_t>(), B, 1, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), ix->opt.id_base,
                            ix->kn_pids.as<uint64_t>(), ix->kn_pkeys.as<uint64_t>(), ix->kn_pcounts.as<uint32_t>(), nullptr, s));
-    std::vector<uint32_t> h_cnt(B + 2);
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), e.cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h_cnt.data() + B, e.over, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    *overflowed = h_cnt[B] != 0;
-    if (!*overflowed)
-        for (uint32_t b = 0; b < B; b++) inf->survivors += h_cnt[b];
-    return ZH_OK;
+    return lists_end(e, s, overflowed, &inf->survivors);
 }
 
 // One slab on device outputs (under mu, exclusive; exact_live_rows and knn_setup have run; k > 0, n > 0): every line filled as "no neighbours", then
@@ -4478,12 +4484,7 @@ static int knn_slab(zh_index *ix, KnnRun *run, uint64_t first_row, uint64_t n, u
     const uint32_t d = ix->opt.dim;
     int rc;
     HIPCHK(zh_launch_exact_empty((uint32_t)n, k, dIds, dKeys, dCounts, s));
-    auto live_before = [&](uint64_t row) {
-        if (row < run->rank_row) { run->rank_row = 0; run->rank = 0; }
-        for (; run->rank_row < row; run->rank_row++) run->rank += !(run->rank_row < ix->h_dead.size() && ix->h_dead[run->rank_row]);
-        return run->rank;
-    };
-    const uint64_t lo = live_before(first_row), hi = live_before(first_row + n);
+    const uint64_t lo = live_before(ix, first_row, &run->live), hi = live_before(ix, first_row + n, &run->live);
     inf->lines += hi - lo;
     if ((rc = ix->kn_pids.ensure((size_t)ZH_KNN_PANEL_ROWS * (k + 1) * 8)) || (rc = ix->kn_pkeys.ensure((size_t)ZH_KNN_PANEL_ROWS * (k + 1) * 8)) ||
         (rc = ix->kn_pcounts.ensure((size_t)ZH_KNN_PANEL_ROWS * 4)))
@@ -4526,6 +4527,15 @@ static int knn_range(zh_index *ix, uint64_t first_row, uint64_t n, const char *w
     return ZH_OK;
 }
 
+// both graphs' host calls: a slab's [m][k] answer from the staging (kn_oids / kn_okeys / kn_ocounts) out to the lines from r0, and waited for
+static int knn_stage_out(zh_index *ix, uint64_t r0, uint64_t m, size_t k, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, hipStream_t s) {
+    HIPCHK(hipMemcpyAsync(out_ids + r0 * k, ix->kn_oids.p, m * k * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_keys + r0 * k, ix->kn_okeys.p, m * k * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_counts + r0, ix->kn_ocounts.p, m * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return ZH_OK;
+}
+
 static void knn_record(zh_index *ix, uint32_t k, zh_knn_info inf) {
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     inf.k = k;
@@ -4540,8 +4550,8 @@ extern "C" int zh_knn_graph_device(zh_index *ix, uint64_t first_row, uint64_t n,
     if (n == 0) return ZH_OK;
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph_device"))) return rc;
-    KnnScratchGuard guard{ix};
-    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    ScratchGuard guard{ix, SCRATCH_KNN};
+    const hipStream_t s = call_stream(ix, stream);
     zh_knn_info inf{};
     inf.path = 1;
     if (k == 0) {
@@ -4564,7 +4574,7 @@ extern "C" int zh_knn_graph(zh_index *ix, uint64_t first_row, uint64_t n, size_t
     if (n == 0) return ZH_OK;
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph"))) return rc;
-    KnnScratchGuard guard{ix};
+    ScratchGuard guard{ix, SCRATCH_KNN};
     const hipStream_t s = ix->stream;
     zh_knn_info inf{};
     inf.path = 1;
@@ -4579,95 +4589,85 @@ extern "C" int zh_knn_graph(zh_index *ix, uint64_t first_row, uint64_t n, size_t
         for (uint64_t r0 = 0; r0 < n; r0 += ZH_KNN_HOST_SLAB) {
             const uint64_t m = std::min<uint64_t>(ZH_KNN_HOST_SLAB, n - r0);
             if ((rc = knn_slab(ix, &run, first_row + r0, m, (uint32_t)k, metric, mode, ix->kn_oids.as<uint64_t>(), ix->kn_okeys.as<uint64_t>(),
-                               ix->kn_ocounts.as<uint32_t>(), s, &inf)))
+                               ix->kn_ocounts.as<uint32_t>(), s, &inf)) ||
+                (rc = knn_stage_out(ix, r0, m, k, out_ids, out_keys, out_counts, s)))
                 return rc;
-            HIPCHK(hipMemcpyAsync(out_ids + r0 * k, ix->kn_oids.p, m * k * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(out_keys + r0 * k, ix->kn_okeys.p, m * k * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(out_counts + r0, ix->kn_ocounts.p, m * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
         }
     }
     knn_record(ix, (uint32_t)k, inf);
     return ZH_OK;
 }
 
-extern "C" int zh_knn_graph_info(const zh_index *ix, zh_knn_info *out) {
-    if (!ix || !out) return fail(ZH_EINVAL, "zh_knn_graph_info: null argument");
-    zh_index *m = const_cast<zh_index *>(ix);
-    std::lock_guard<std::mutex> lk(m->stats_mu);
-    *out = m->kn_info;
-    return ZH_OK;
-}
+extern "C" int zh_knn_graph_info(const zh_index *ix, zh_knn_info *out) { return get_info(ix, &zh_index::kn_info, out, "zh_knn_graph_info"); }
 
 // ------------------------------------------------------------------------------------------------
 // forest k-NN graph (zh_fknn.hip): each row's k nearest rows among its leaf-mates over all trees.  DESIGN.md s17
 // ------------------------------------------------------------------------------------------------
 #define ZH_FKNN_KEY_BUDGET (uint64_t(1) << 25)  // keys one path-1 panel's sweep may write (256 MiB), unless one line's leaves alone hold more
 
-static void fknn_release_scratch(zh_index *ix) {
-    knn_release_scratch(ix);
-    DevBuf *bs[] = {&ix->fk_ntree, &ix->fk_rl, &ix->fk_flag, &ix->fk_excl, &ix->fk_tmp, &ix->fk_rows, &ix->fk_ctr, &ix->fk_lens, &ix->fk_takes, &ix->fk_rbase,
-                    &ix->fk_cbase, &ix->fk_groups, &ix->fk_groff, &ix->fk_segs, &ix->fk_colsrc, &ix->fk_crow, &ix->fk_hrow, &ix->fk_held, &ix->fk_CA,
-                    &ix->fk_cmeta, &ix->fk_cqm, &ix->fk_HA, &ix->fk_hmeta, &ix->fk_qrow, &ix->fk_maxk, &ix->fk_redo, &ix->fk_pos};
-    for (DevBuf *b : bs) b->release();
-}
-struct FknnScratchGuard {
-    zh_index *ix;
-    ~FknnScratchGuard() { fknn_release_scratch(ix); }
-};
-
-struct FknnRun {  // what a call settles once
+struct ForestRun {  // what a call of either forest family settles once
     uint32_t T = 0;
     bool path2 = false;
-    const void *Xh = nullptr;
-    const float2 *rowMeta = nullptr;
+    HalfView v;
     const uint32_t *pos = nullptr;  // row -> position under a row order, else null
-    float rho = 0.f, Kc = 0.f;
-    uint32_t env_cap = 0;           // ZH_FKNN_LIST_CAP (0: not set)
-    std::vector<std::vector<uint2>> leaves;  // per tree the non-empty leaves {offset into leaf_ids, length}, in the host mirror's order (path 2)
+    float Kc = 0.f;
+    std::vector<std::vector<uint2>> leaves;  // per tree the non-empty leaves {offset into leaf_ids, length}, in the host mirror's order
+};
+struct FknnRun : ForestRun {
+    uint32_t env_cap = 0;  // ZH_FKNN_LIST_CAP (0: not set)
 };
 
-// The node -> tree map on the device (both paths' row -> leaf table), the path rule, and path 2's per-call views.
-static int fknn_setup(zh_index *ix, uint32_t k, int metric, int mode, hipStream_t s, FknnRun *run) {
-    const uint32_t d = ix->opt.dim, T = (uint32_t)ix->h_roots.size();
-    const size_t nn = ix->h_plane.size();
-    run->T = T;
-    const char *env_p = getenv("ZH_FKNN_PATH");
-    bool want2 = !(env_p && atoi(env_p) == 1) && zh_exact_mfma_supported(d, metric) && ix->opt.max_node_size >= 64;
-    int rc;
-    if (want2) {
-        std::lock_guard<std::mutex> lb(ix->blk_mu);
-        bool ok = false;
-        if ((rc = ensure_row_half(ix, &ok))) return rc;
-        if (!ok || !ix->row_half.p) want2 = false;  // no copy (no room, or the per-row scales alone): path 1
-        else {
-            run->Xh = ix->row_half.p; run->rowMeta = ix->row_meta.as<float2>(); run->rho = ix->row_rho;
-            if (ix->perm_rows) {
-                if ((rc = ix->fk_pos.ensure(ix->n_rows * 4))) return rc;
-                HIPCHK(zh_launch_fknn_rowpos(ix->scan_perm.as<uint32_t>(), ix->perm_rows, ix->n_rows, ix->fk_pos.as<uint32_t>(), s));
-                HIPCHK(hipStreamSynchronize(s));  // (scan_perm is read under blk_mu only)
-                run->pos = ix->fk_pos.as<uint32_t>();
-            }
-        }
+// The forest families' path rule (env_path: ZH_FKNN_PATH / ZH_FJOIN_PATH, read per call) and path 2's per-call views: the fp16 copy and, under a row
+// order, the row -> position map -- made and waited for inside blk_mu, because scan_perm is read under blk_mu only.
+static int forest_path2(zh_index *ix, const char *env_path, int metric, hipStream_t s, ForestRun *run) {
+    const uint32_t d = ix->opt.dim;
+    run->T = (uint32_t)ix->h_roots.size();
+    const char *env_p = getenv(env_path);
+    if ((env_p && atoi(env_p) == 1) || !zh_exact_mfma_supported(d, metric) || ix->opt.max_node_size < 64) return ZH_OK;
+    std::lock_guard<std::mutex> lb(ix->blk_mu);
+    bool have = false;
+    int rc = half_view(ix, &run->v, &have);
+    if (rc || !have) return rc;
+    if (ix->perm_rows) {
+        if ((rc = ix->fk_pos.ensure(ix->n_rows * 4))) return rc;
+        HIPCHK(zh_launch_fknn_rowpos(ix->scan_perm.as<uint32_t>(), ix->perm_rows, ix->n_rows, ix->fk_pos.as<uint32_t>(), s));
+        HIPCHK(hipStreamSynchronize(s));
+        run->pos = ix->fk_pos.as<uint32_t>();
     }
-    std::vector<uint32_t> node_tree(std::max<size_t>(nn, 1), 0xFFFFFFFFu), st;
-    if (want2) run->leaves.resize(T);
+    run->Kc = zh_approx_bound(metric, d, 1);
+    run->path2 = true;
+    return ZH_OK;
+}
+
+// The host mirror of the forest, walked once -> node_tree[node] = the tree that holds it (0xFFFFFFFF: none) and, where asked for, every tree's
+// non-empty leaves.
+static std::vector<uint32_t> forest_walk(const zh_index *ix, std::vector<std::vector<uint2>> *leaves) {
+    const uint32_t T = (uint32_t)ix->h_roots.size();
+    std::vector<uint32_t> node_tree(std::max<size_t>(ix->h_plane.size(), 1), 0xFFFFFFFFu), st;
+    if (leaves) leaves->resize(T);
     for (uint32_t t = 0; t < T; t++) {
         st.assign(1, ix->h_roots[t]);
         while (!st.empty()) {
             const uint32_t nd = st.back(); st.pop_back();
             node_tree[nd] = t;
             if (ix->h_plane[nd] >= 0) { st.push_back((uint32_t)ix->h_right[nd]); st.push_back((uint32_t)ix->h_left[nd]); }
-            else if (want2 && ix->h_right[nd] > 0) run->leaves[t].push_back(make_uint2((uint32_t)ix->h_left[nd], (uint32_t)ix->h_right[nd]));
+            else if (leaves && ix->h_right[nd] > 0) (*leaves)[t].push_back(make_uint2((uint32_t)ix->h_left[nd], (uint32_t)ix->h_right[nd]));
         }
     }
+    return node_tree;
+}
+
+// The node -> tree map on the device (both paths' row -> leaf table), the path rule, and path 2's per-call views (its leaves among them).
+static int fknn_setup(zh_index *ix, uint32_t k, int metric, int mode, hipStream_t s, FknnRun *run) {
+    int rc;
+    if ((rc = forest_path2(ix, "ZH_FKNN_PATH", metric, s, run))) return rc;
+    const std::vector<uint32_t> node_tree = forest_walk(ix, run->path2 ? &run->leaves : nullptr);
     if ((rc = ix->fk_ntree.ensure(node_tree.size() * 4)) || (rc = ix->fk_ctr.ensure(32))) return rc;
     HIPCHK(hipMemcpyAsync(ix->fk_ntree.p, node_tree.data(), node_tree.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(ix->fk_ctr.p, 0, 32, s));
     HIPCHK(hipStreamSynchronize(s));  // (node_tree is this frame's)
     const char *env_c = getenv("ZH_FKNN_LIST_CAP");
     if (env_c && atoi(env_c) > 0) run->env_cap = (uint32_t)atoi(env_c);
-    if (want2) { run->Kc = zh_approx_bound(metric, d, 1); run->path2 = true; }
     return ZH_OK;
 }
 
@@ -4696,7 +4696,7 @@ static int fknn_panel1(zh_index *ix, const FknnRun &run, uint64_t r0, const uint
     if ((rc = ix->ex_keys.ensure(std::max<size_t>(tot[0], 1) * 8)) || (rc = ix->ex_ckeys.ensure(std::max<size_t>(tot[1], 1) * 8)) ||
         (rc = ix->ex_cids.ensure(std::max<size_t>(tot[1], 1) * 4)))
         return rc;
-    const int param = metric == ZH_COSINE ? mode : ((metric == ZH_MINKOWSKI || metric == ZH_PNORM) ? mode : 0);
+    const int param = score_param(metric, mode);
     HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dRows, B, ix->ex_Q.as<float>(), s));
     HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), B, d, ix->ex_QQ.as<float>(), s));
     HIPCHK(zh_launch_sweep(ix->X.as<float>(), d, ix->ex_Q.as<float>(), ix->ex_QQ.as<float>(), ix->fk_groups.as<ZhGroup>(), ix->fk_groff.as<uint64_t>(), V, nullptr,
@@ -4745,47 +4745,39 @@ static int fknn_batch2(zh_index *ix, const FknnRun &run, std::vector<ZhFknnSeg> 
                        bool first, uint64_t first_row, uint64_t n, uint32_t k, int metric, int mode, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts,
                        hipStream_t s, bool *overflowed, zh_knn_forest_info *inf) {
     const uint32_t d = ix->opt.dim, NT = (uint32_t)colsrc.size(), HB = held_tiles * 16, n_segs = (uint32_t)segs.size();
-    // column tiles per block: ZH_FKNN_CHUNK, fewer while the launch would not fill the device (about 1024 blocks), never under 8
-    uint32_t ch = ZH_FKNN_CHUNK, n_blocks = 0;
-    for (;;) {
+    // column tiles per block, and with them every segment's first block
+    uint32_t n_blocks = 0;
+    const uint32_t ch = fill_chunk([&](uint32_t c) {
         n_blocks = 0;
-        for (ZhFknnSeg &sg : segs) { sg.first_block = n_blocks; n_blocks += (sg.held_tiles + 3) / 4 * ((sg.ct + ch - 1) / ch); }
-        if (n_blocks >= 1024 || ch <= 8) break;
-        ch /= 2;
-    }
+        for (ZhFknnSeg &sg : segs) { sg.first_block = n_blocks; n_blocks += (sg.held_tiles + 3) / 4 * ((sg.ct + c - 1) / c); }
+        return n_blocks;
+    });
     // list slots per line: a line lists at most its leaf-mates (longest - 1 <= lim): only the ceilings and the test switch can make a list run over
     uint32_t cap = std::min<uint32_t>(longest + k, first ? 16384 + 8 * k : 1024 + 4 * k), lim = cap - k;
     if (run.env_cap) { lim = std::min(lim, run.env_cap); cap = lim + k; }
+    ZhExact2 e{run.v.Xh, run.v.rowMeta, nullptr, 0, ix->ex_bits.as<uint32_t>(), nullptr, nullptr, HB, run.Kc, run.v.rho};
     int rc;
     if ((rc = ix->fk_segs.ensure((size_t)n_segs * sizeof(ZhFknnSeg))) || (rc = ix->fk_colsrc.ensure((size_t)NT * 8)) || (rc = ix->fk_crow.ensure((size_t)NT * 64)) ||
         (rc = ix->fk_hrow.ensure((size_t)HB * 4)) || (rc = ix->fk_held.ensure((size_t)n_segs * 4)) || (rc = ix->fk_CA.ensure((size_t)NT * 32 * d)) ||
         (rc = ix->fk_cmeta.ensure((size_t)NT * 128)) || (rc = ix->fk_cqm.ensure((size_t)NT * 256)) || (rc = ix->fk_HA.ensure((size_t)HB * 2 * d)) ||
         (rc = ix->fk_hmeta.ensure((size_t)HB * 8)) || (rc = ix->fk_qrow.ensure((size_t)HB * 4)) || (rc = ix->fk_maxk.ensure((size_t)HB * 8)) ||
-        (rc = ix->ex_Q.ensure((size_t)HB * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)HB * 4)) || (rc = ix->ex_tau.ensure((size_t)HB * 4)) ||
-        (rc = ix->ex_cnt.ensure((size_t)HB * 4)) || (rc = ix->ex_lid.ensure((size_t)HB * cap * 4)) || (rc = ix->ex_llo.ensure((size_t)HB * cap * 4)) ||
-        (rc = ix->ex_lhi.ensure((size_t)HB * cap * 4)) || (rc = ix->ex_scr.ensure((size_t)HB * cap * 12)) || (rc = ix->ex_over.ensure(8)) ||
-        (rc = ix->ex_ckeys.ensure((size_t)HB * cap * 8)) || (rc = ix->ex_cids.ensure((size_t)HB * cap * 4)) || (rc = ix->ex_cbase.ensure(((size_t)HB + 1) * 8)) ||
+        (rc = ix->ex_Q.ensure((size_t)HB * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)HB * 4)) || (rc = lists_ensure(ix, HB, cap, true, &e)) ||
         (rc = ix->kn_pids.ensure((size_t)HB * k * 8)) || (rc = ix->kn_pkeys.ensure((size_t)HB * k * 8)) || (rc = ix->kn_pcounts.ensure((size_t)HB * 4)))
         return rc;
-    ZhExact2 e{run.Xh, run.rowMeta, nullptr, 0, ix->ex_bits.as<uint32_t>(), nullptr, nullptr, HB, run.Kc, run.rho,
-               ix->ex_tau.as<uint32_t>(), ix->ex_cnt.as<uint32_t>(), ix->ex_lid.as<uint32_t>(), ix->ex_llo.as<uint32_t>(), ix->ex_lhi.as<uint32_t>(), cap,
-               ix->ex_over.as<uint32_t>()};
     std::vector<uint64_t> cb((size_t)HB + 1);
-    for (uint32_t b = 0; b <= HB; b++) cb[b] = (uint64_t)b * cap;
     const ZhFknnSeg *dSegs = ix->fk_segs.as<ZhFknnSeg>();
     uint32_t *crow = ix->fk_crow.as<uint32_t>(), *hrow = ix->fk_hrow.as<uint32_t>(), *held = ix->fk_held.as<uint32_t>();
     unsigned long long *ctr = ix->fk_ctr.as<unsigned long long>();
     HIPCHK(hipMemcpyAsync(ix->fk_segs.p, segs.data(), (size_t)n_segs * sizeof(ZhFknnSeg), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(ix->fk_colsrc.p, colsrc.data(), (size_t)NT * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ix->ex_cbase.p, cb.data(), cb.size() * 8, hipMemcpyHostToDevice, s));
+    if ((rc = list_bases(ix->ex_cbase.p, cb, cap, s))) return rc;
     HIPCHK(zh_launch_fknn_cols(ix->fk_colsrc.as<uint2>(), NT, ix->leaf_ids.as<uint32_t>(), ix->n_rows, crow, s));
     HIPCHK(zh_launch_fknn_held(dSegs, n_segs, ix->leaf_ids.as<uint32_t>(), first_row, n, hrow, held, ctr + 1, s));
-    HIPCHK(zh_launch_fknn_gather(d, run.Xh, run.rowMeta, run.pos, crow, NT, run.rho, ix->fk_CA.p, ix->fk_cmeta.as<float2>(), ix->fk_cqm.as<float4>(), s));
-    HIPCHK(zh_launch_fknn_gather(d, run.Xh, run.rowMeta, run.pos, hrow, held_tiles, run.rho, ix->fk_HA.p, ix->fk_hmeta.as<float2>(), nullptr, s));
+    HIPCHK(zh_launch_fknn_gather(d, run.v.Xh, run.v.rowMeta, run.pos, crow, NT, run.v.rho, ix->fk_CA.p, ix->fk_cmeta.as<float2>(), ix->fk_cqm.as<float4>(), s));
+    HIPCHK(zh_launch_fknn_gather(d, run.v.Xh, run.v.rowMeta, run.pos, hrow, held_tiles, run.v.rho, ix->fk_HA.p, ix->fk_hmeta.as<float2>(), nullptr, s));
     HIPCHK(zh_launch_fknn_bound(hrow, HB, first_row, k, dKeys, dCounts, ix->fk_qrow.as<uint32_t>(), ix->fk_maxk.as<uint64_t>(), s));
     HIPCHK(zh_launch_range_tau(ix->fk_maxk.as<uint64_t>(), HB, metric, mode, e.tau, s));
-    HIPCHK(hipMemsetAsync(e.cnt, 0, (size_t)HB * 4, s));
-    HIPCHK(hipMemsetAsync(e.over, 0, 8, s));
+    if ((rc = lists_reset(e, s))) return rc;
     HIPCHK(zh_launch_fknn_mfma(d, metric, mode, dSegs, n_segs, n_blocks, held, ch, ix->fk_CA.p, ix->fk_cqm.as<float4>(), crow, ix->fk_HA.p,
                                ix->fk_hmeta.as<float2>(), hrow, e, lim, s));
     HIPCHK(zh_launch_exact_prune(e, k, ix->ex_scr.as<uint32_t>(), s));
@@ -4798,15 +4790,9 @@ static int fknn_batch2(zh_index *ix, const FknnRun &run, std::vector<ZhFknnSeg> 
                            ix->kn_pids.as<uint64_t>(), ix->kn_pkeys.as<uint64_t>(), ix->kn_pcounts.as<uint32_t>(), nullptr, s));
     HIPCHK(zh_launch_fknn_store(hrow, HB, first_row, ix->opt.id_base, k, ix->kn_pids.as<uint64_t>(), ix->kn_pkeys.as<uint64_t>(), dIds, dKeys, dCounts,
                                 e.over, s));
-    std::vector<uint32_t> h_cnt((size_t)HB + 2);
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), e.cnt, (size_t)HB * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h_cnt.data() + HB, e.over, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));  // (segs, colsrc and cb are the caller's and this frame's)
+    if ((rc = lists_end(e, s, overflowed, &inf->survivors))) return rc;  // (segs, colsrc and cb are the caller's and this frame's)
     inf->launches++;
-    *overflowed = h_cnt[HB] != 0;
     if (*overflowed) HIPCHK(zh_launch_fknn_mark(hrow, HB, first_row, ix->fk_redo.as<uint32_t>(), s));
-    else
-        for (uint32_t b = 0; b < HB; b++) inf->survivors += h_cnt[b];
     return ZH_OK;
 }
 
@@ -4918,8 +4904,8 @@ extern "C" int zh_knn_graph_forest_device(zh_index *ix, uint64_t first_row, uint
     if (n == 0) return ZH_OK;
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph_forest_device"))) return rc;
-    FknnScratchGuard guard{ix};
-    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    ScratchGuard guard{ix, SCRATCH_FKNN};
+    const hipStream_t s = call_stream(ix, stream);
     zh_knn_forest_info inf{};
     inf.path = 1;
     FknnRun run;
@@ -4941,7 +4927,7 @@ extern "C" int zh_knn_graph_forest(zh_index *ix, uint64_t first_row, uint64_t n,
     if (n == 0) return ZH_OK;
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph_forest"))) return rc;
-    FknnScratchGuard guard{ix};
+    ScratchGuard guard{ix, SCRATCH_FKNN};
     const hipStream_t s = ix->stream;
     zh_knn_forest_info inf{};
     inf.path = 1;
@@ -4957,23 +4943,16 @@ extern "C" int zh_knn_graph_forest(zh_index *ix, uint64_t first_row, uint64_t n,
         for (uint64_t r0 = 0; r0 < n; r0 += host_slab) {
             const uint64_t m = std::min(host_slab, n - r0);
             if ((rc = fknn_slab(ix, run, first_row + r0, m, (uint32_t)k, metric, mode, ix->kn_oids.as<uint64_t>(), ix->kn_okeys.as<uint64_t>(),
-                                ix->kn_ocounts.as<uint32_t>(), s, &inf)))
+                                ix->kn_ocounts.as<uint32_t>(), s, &inf)) ||
+                (rc = knn_stage_out(ix, r0, m, k, out_ids, out_keys, out_counts, s)))
                 return rc;
-            HIPCHK(hipMemcpyAsync(out_ids + r0 * k, ix->kn_oids.p, m * k * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(out_keys + r0 * k, ix->kn_okeys.p, m * k * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(out_counts + r0, ix->kn_ocounts.p, m * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
         }
     }
     return fknn_finish(ix, (uint32_t)k, inf, s);
 }
 
 extern "C" int zh_knn_graph_forest_info(const zh_index *ix, zh_knn_forest_info *out) {
-    if (!ix || !out) return fail(ZH_EINVAL, "zh_knn_graph_forest_info: null argument");
-    zh_index *m = const_cast<zh_index *>(ix);
-    std::lock_guard<std::mutex> lk(m->stats_mu);
-    *out = m->fk_info;
-    return ZH_OK;
+    return get_info(ix, &zh_index::fk_info, out, "zh_knn_graph_forest_info");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4981,76 +4960,29 @@ extern "C" int zh_knn_graph_forest_info(const zh_index *ix, zh_knn_forest_info *
 // ------------------------------------------------------------------------------------------------
 #define ZH_FJOIN_CAND_FLOOR 256u  // path 2: candidate slots per gathered row of a batch that are there whatever the capacity
 
-static void fjoin_release_scratch(zh_index *ix) {
-    join_release_scratch(ix);
-    fknn_release_scratch(ix);
-    DevBuf *bs[] = {&ix->fj_leafof, &ix->fj_pieces, &ix->fj_linel, &ix->fj_linek, &ix->fj_segs, &ix->fj_cand};
-    for (DevBuf *b : bs) b->release();
-}
-struct FjoinScratchGuard {
-    zh_index *ix;
-    ~FjoinScratchGuard() { fjoin_release_scratch(ix); }
-};
-
-struct FjoinRun {  // what a call settles once
-    uint32_t T = 0;
+struct FjoinRun : ForestRun {
     int metric = 0, mode = 0;
     uint64_t max_key = 0, pool_cap = 0;
-    bool path2 = false;
-    const void *Xh = nullptr;
-    const float2 *rowMeta = nullptr;
-    const uint32_t *pos = nullptr;  // row -> position under a row order, else null
-    float rho = 0.f, Kc = 0.f;
     bool env_cand = false;          // ZH_FJOIN_CAND_CAP is set ...
     uint64_t env_cand_cap = 0;      // ... to this
-    std::vector<std::vector<uint2>> leaves;  // per tree the non-empty leaves {offset into leaf_ids, length}, in the host mirror's order
 };
 
+// The path rule and path 2's views, every tree's leaves (both paths go by them), the node -> tree map and each row's leaf per tree on the device.
 // jn_ctr: {hits, the batch's candidates, the forest's leaf pairs, candidates that got a key}
 static int fjoin_setup(zh_index *ix, int metric, int mode, hipStream_t s, FjoinRun *run) {
-    const uint32_t d = ix->opt.dim, T = (uint32_t)ix->h_roots.size();
-    const size_t nn = ix->h_plane.size();
-    run->T = T;
-    const char *env_p = getenv("ZH_FJOIN_PATH");
-    bool want2 = !(env_p && atoi(env_p) == 1) && zh_exact_mfma_supported(d, metric) && ix->opt.max_node_size >= 64;
     int rc;
-    if (want2) {
-        std::lock_guard<std::mutex> lb(ix->blk_mu);
-        bool ok = false;
-        if ((rc = ensure_row_half(ix, &ok))) return rc;
-        if (!ok || !ix->row_half.p) want2 = false;  // no copy (no room, or the per-row scales alone): path 1
-        else {
-            run->Xh = ix->row_half.p; run->rowMeta = ix->row_meta.as<float2>(); run->rho = ix->row_rho;
-            if (ix->perm_rows) {
-                if ((rc = ix->fk_pos.ensure(ix->n_rows * 4))) return rc;
-                HIPCHK(zh_launch_fknn_rowpos(ix->scan_perm.as<uint32_t>(), ix->perm_rows, ix->n_rows, ix->fk_pos.as<uint32_t>(), s));
-                HIPCHK(hipStreamSynchronize(s));  // (scan_perm is read under blk_mu only)
-                run->pos = ix->fk_pos.as<uint32_t>();
-            }
-        }
-    }
-    std::vector<uint32_t> node_tree(std::max<size_t>(nn, 1), 0xFFFFFFFFu), st;
-    run->leaves.resize(T);
-    for (uint32_t t = 0; t < T; t++) {
-        st.assign(1, ix->h_roots[t]);
-        while (!st.empty()) {
-            const uint32_t nd = st.back(); st.pop_back();
-            node_tree[nd] = t;
-            if (ix->h_plane[nd] >= 0) { st.push_back((uint32_t)ix->h_right[nd]); st.push_back((uint32_t)ix->h_left[nd]); }
-            else if (ix->h_right[nd] > 0) run->leaves[t].push_back(make_uint2((uint32_t)ix->h_left[nd], (uint32_t)ix->h_right[nd]));
-        }
-    }
+    if ((rc = forest_path2(ix, "ZH_FJOIN_PATH", metric, s, run))) return rc;
+    const std::vector<uint32_t> node_tree = forest_walk(ix, &run->leaves);
     if ((rc = ix->fk_ntree.ensure(node_tree.size() * 4)) || (rc = ix->jn_ctr.ensure(32)) ||
-        (rc = ix->fj_leafof.ensure(std::max<size_t>((size_t)ix->n_rows * T * 4, 4))))
+        (rc = ix->fj_leafof.ensure(std::max<size_t>((size_t)ix->n_rows * run->T * 4, 4))))
         return rc;
     HIPCHK(hipMemcpyAsync(ix->fk_ntree.p, node_tree.data(), node_tree.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(ix->jn_ctr.p, 0, 32, s));
-    HIPCHK(zh_launch_fjoin_rowleaf(ix->node_pack.as<int4>(), ix->fk_ntree.as<uint32_t>(), ix->n_nodes, ix->leaf_ids.as<uint32_t>(), T, ix->n_rows,
+    HIPCHK(zh_launch_fjoin_rowleaf(ix->node_pack.as<int4>(), ix->fk_ntree.as<uint32_t>(), ix->n_nodes, ix->leaf_ids.as<uint32_t>(), run->T, ix->n_rows,
                                    ix->fj_leafof.as<uint32_t>(), ix->jn_ctr.as<unsigned long long>() + 2, s));
     HIPCHK(hipStreamSynchronize(s));  // (node_tree is this frame's)
     const char *env_c = getenv("ZH_FJOIN_CAND_CAP");
     if (env_c && atoll(env_c) > 0) { run->env_cand = true; run->env_cand_cap = (uint64_t)atoll(env_c); }
-    if (want2) { run->Kc = zh_approx_bound(metric, d, 1); run->path2 = true; }
     return ZH_OK;
 }
 
@@ -5064,7 +4996,7 @@ static int fjoin_panel1(zh_index *ix, const FjoinRun &run, uint32_t t, const std
         (rc = ix->fk_groups.ensure((size_t)groups * sizeof(ZhGroup))) || (rc = ix->fk_groff.ensure((size_t)groups * 8)) ||
         (rc = ix->ex_Q.ensure((size_t)lines * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)lines * 4)) || (rc = ix->ex_keys.ensure(std::max<uint64_t>(keys, 1) * 8)))
         return rc;
-    const int param = run.metric == ZH_COSINE ? run.mode : ((run.metric == ZH_MINKOWSKI || run.metric == ZH_PNORM) ? run.mode : 0);
+    const int param = score_param(run.metric, run.mode);
     HIPCHK(hipMemcpyAsync(ix->fj_pieces.p, pieces.data(), pieces.size() * sizeof(ZhFjoinPiece), hipMemcpyHostToDevice, s));
     HIPCHK(zh_launch_fjoin_groups(ix->fj_pieces.as<ZhFjoinPiece>(), (uint32_t)pieces.size(), groups, ix->leaf_ids.as<uint32_t>(), ix->n_rows,
                                   ix->fk_rows.as<uint32_t>(), ix->fj_linel.as<uint2>(), ix->fj_linek.as<uint64_t>(), ix->fk_groups.as<ZhGroup>(),
@@ -5116,18 +5048,16 @@ static int fjoin_leaves1(zh_index *ix, const FjoinRun &run, uint32_t t, const ui
 static int fjoin_batch2(zh_index *ix, const FjoinRun &run, uint32_t t, const std::vector<uint2> &leaves, const std::vector<uint2> &colsrc, hipStream_t s,
                         zh_join_forest_info *inf, uint64_t *hits) {
     const uint32_t d = ix->opt.dim, NT = (uint32_t)colsrc.size();
-    // tiles per chunk: ZH_FKNN_CHUNK, fewer while the launch would not fill the device (about 1024 blocks), never under 8.  A leaf of ct tiles gives one
-    // segment per held block I0 = 0, 4, ... < ct with ceil((ct - I0) / ch) blocks: chunks are counted from the held block's own diagonal
-    uint32_t ch = ZH_FKNN_CHUNK, n_blocks = 0;
-    for (;;) {
-        n_blocks = 0;
+    // tiles per chunk.  A leaf of ct tiles gives one segment per held block I0 = 0, 4, ... < ct with ceil((ct - I0) / ch) blocks: chunks are counted
+    // from the held block's own diagonal
+    const uint32_t ch = fill_chunk([&](uint32_t c) {
+        uint32_t n_blocks = 0;
         for (const uint2 lf : leaves) {
             const uint32_t ct = (lf.y + 15) / 16;
-            for (uint32_t I0 = 0; I0 < ct; I0 += 4) n_blocks += (ct - I0 + ch - 1) / ch;
+            for (uint32_t I0 = 0; I0 < ct; I0 += 4) n_blocks += (ct - I0 + c - 1) / c;
         }
-        if (n_blocks >= 1024 || ch <= 8) break;
-        ch /= 2;
-    }
+        return n_blocks;
+    });
     std::vector<ZhFjoinSeg> segs;
     uint64_t products = 0, batch_pairs = 0;
     uint32_t col0 = 0, blocks = 0;
@@ -5154,10 +5084,10 @@ static int fjoin_batch2(zh_index *ix, const FjoinRun &run, uint32_t t, const std
     HIPCHK(hipMemcpyAsync(ix->fj_segs.p, segs.data(), segs.size() * sizeof(ZhFjoinSeg), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(ix->fk_colsrc.p, colsrc.data(), (size_t)NT * 8, hipMemcpyHostToDevice, s));
     HIPCHK(zh_launch_fknn_cols(ix->fk_colsrc.as<uint2>(), NT, ix->leaf_ids.as<uint32_t>(), ix->n_rows, crow, s));
-    HIPCHK(zh_launch_fknn_gather(d, run.Xh, run.rowMeta, run.pos, crow, NT, run.rho, ix->fk_CA.p, ix->fk_cmeta.as<float2>(), ix->fk_cqm.as<float4>(), s));
+    HIPCHK(zh_launch_fknn_gather(d, run.v.Xh, run.v.rowMeta, run.pos, crow, NT, run.v.rho, ix->fk_CA.p, ix->fk_cmeta.as<float2>(), ix->fk_cqm.as<float4>(), s));
     HIPCHK(hipMemsetAsync(ctr + 1, 0, 8, s));
     HIPCHK(zh_launch_fjoin_mfma(d, run.metric, run.mode, ix->fj_segs.as<ZhFjoinSeg>(), (uint32_t)segs.size(), blocks, ch, ix->fk_CA.p, ix->fk_cmeta.as<float2>(),
-                                ix->fk_cqm.as<float4>(), crow, run.Kc, run.rho, ix->jn_tau.as<uint32_t>(), ix->fj_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
+                                ix->fk_cqm.as<float4>(), crow, run.Kc, run.v.rho, ix->jn_tau.as<uint32_t>(), ix->fj_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
     inf->launches++;
     inf->tiles += products;
     HIPCHK(zh_launch_fjoin_survivors(ix->X.as<float>(), d, run.metric, run.mode, ix->fj_cand.as<uint64_t>(), ctr + 1, cand_cap, ix->fj_leafof.as<uint32_t>(), run.T,
@@ -5232,35 +5162,7 @@ static int fjoin_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint6
         HIPCHK(hipStreamSynchronize(s));
         hits = h_ctr[0];
     }
-    *total = hits;
-    inf.pairs = hits;
-    const bool over = hits > capacity;
-    if (!over && hits) {  // the order and the outputs, as join_run
-        uint64_t *dV[2] = {nullptr, nullptr}, *dK[2] = {nullptr, nullptr};
-        size_t tmp_bytes = 0;
-        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, nullptr, &tmp_bytes, 0, nullptr, nullptr, nullptr, s));
-        if ((rc = ix->jn_pv1.ensure(hits * 8)) || (rc = ix->jn_pk1.ensure(hits * 8)) || (rc = ix->jn_tmp.ensure(tmp_bytes))) return rc;
-        if (host_out && ((rc = ix->jn_oa.ensure(hits * 8)) || (rc = ix->jn_ob.ensure(hits * 8)) || (rc = ix->jn_okeys.ensure(hits * 8)))) return rc;
-        dV[0] = ix->jn_pv0.as<uint64_t>(); dV[1] = ix->jn_pv1.as<uint64_t>();
-        dK[0] = ix->jn_pk0.as<uint64_t>(); dK[1] = ix->jn_pk1.as<uint64_t>();
-        uint64_t *oa = host_out ? ix->jn_oa.as<uint64_t>() : outA, *ob = host_out ? ix->jn_ob.as<uint64_t>() : outB;
-        uint64_t *ok = host_out ? ix->jn_okeys.as<uint64_t>() : outKeys;
-        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, ix->jn_tmp.p, &tmp_bytes, ix->opt.id_base, oa, ob, ok, s));
-        if (host_out) {
-            HIPCHK(hipMemcpyAsync(outA, oa, hits * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(outB, ob, hits * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(outKeys, ok, hits * 8, hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    {
-        std::lock_guard<std::mutex> lk(ix->stats_mu);
-        ix->fj_info = inf;
-    }
-    if (over)
-        return fail(ZH_ELIMIT, "%s: %llu pairs exceed the capacity of %llu; out_total is exact, call again with that capacity", who,
-                    (unsigned long long)hits, (unsigned long long)capacity);
-    return ZH_OK;
+    return join_finish(ix, hits, capacity, outA, outB, outKeys, host_out, s, total, inf, &zh_index::fj_info, who);
 }
 
 // an index without live rows has no pair: total 0 (and the info says so) whatever its trees; otherwise the forest graph's state checks
@@ -5285,8 +5187,8 @@ extern "C" int zh_self_join_forest_device(zh_index *ix, uint64_t max_key, int me
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
     bool empty = false;
     if ((rc = fjoin_state(ix, &empty, "zh_self_join_forest_device"))) return rc;
-    FjoinScratchGuard guard{ix};
-    const hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    ScratchGuard guard{ix, SCRATCH_FJOIN};
+    const hipStream_t s = call_stream(ix, stream);
     uint64_t total = 0;
     if (!empty) {
         rc = fjoin_run(ix, max_key, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, false, s, &total, "zh_self_join_forest_device");
@@ -5306,7 +5208,7 @@ extern "C" int zh_self_join_forest(zh_index *ix, uint64_t max_key, int metric, i
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
     bool empty = false;
     if ((rc = fjoin_state(ix, &empty, "zh_self_join_forest")) || empty) return rc;
-    FjoinScratchGuard guard{ix};
+    ScratchGuard guard{ix, SCRATCH_FJOIN};
     uint64_t total = 0;
     rc = fjoin_run(ix, max_key, metric, mode, capacity, out_a, out_b, out_keys, true, ix->stream, &total, "zh_self_join_forest");
     if (rc && rc != ZH_ELIMIT) return rc;
@@ -5315,11 +5217,7 @@ extern "C" int zh_self_join_forest(zh_index *ix, uint64_t max_key, int metric, i
 }
 
 extern "C" int zh_self_join_forest_info(const zh_index *ix, zh_join_forest_info *out) {
-    if (!ix || !out) return fail(ZH_EINVAL, "zh_self_join_forest_info: null argument");
-    zh_index *m = const_cast<zh_index *>(ix);
-    std::lock_guard<std::mutex> lk(m->stats_mu);
-    *out = m->fj_info;
-    return ZH_OK;
+    return get_info(ix, &zh_index::fj_info, out, "zh_self_join_forest_info");
 }
 
 extern "C" int zh_hash_signs(zh_index *ix, const float *q, size_t b, uint32_t *out_bits, float *out_dots) {

@@ -385,6 +385,35 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_self_join_forest_info(h_.get(), &info));
         return info;
     }
+    // the forest range search (zh_search_range_forest_batch): search_range_batch's hits among the members of the leaves the walk visits for each
+    // query with n = probe (1: the leaf the query hashes to in each tree); exact keys on an approximate candidate set, each hit once.  One call that
+    // counts, one that fetches.  Needs a built forest.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> search_range_forest_batch(const std::vector<Embedding<N>> &queries,
+                                                                                      const std::vector<DistanceUnit> &max_keys, const Met &metric,
+                                                                                      std::uint32_t probe = 1) const {
+        const std::size_t b = queries.size();
+        if (max_keys.size() != b) throw std::invalid_argument("search_range_forest_batch: one threshold key per query");
+        std::vector<std::uint64_t> offsets(b + 1);
+        std::uint64_t total = 0;
+        const int rc = zh_search_range_forest_batch(h_.get(), b ? queries[0].data() : nullptr, b, max_keys.data(), probe, Met::metric, metric.mode(), 0,
+                                                    offsets.data(), nullptr, nullptr, &total);
+        if (rc != ZH_ELIMIT) check(rc);
+        std::vector<Id> ids(total + 1);
+        std::vector<DistanceUnit> keys(total + 1);
+        if (total)
+            check(zh_search_range_forest_batch(h_.get(), queries[0].data(), b, max_keys.data(), probe, Met::metric, metric.mode(), total, offsets.data(),
+                                               ids.data(), keys.data(), &total));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(b);
+        for (std::size_t i = 0; i < b; i++)
+            for (std::uint64_t j = offsets[i]; j < offsets[i + 1]; j++) out[i].emplace_back(ids[j], keys[j]);
+        return out;
+    }
+    zh_range_forest_info range_forest_info() const {
+        zh_range_forest_info info{};
+        check(zh_search_range_forest_info(h_.get(), &info));
+        return info;
+    }
     zh_index *handle() const { return h_.get(); }
 
   private:

@@ -32,6 +32,8 @@
  *   zh_knn_graph_forest[_device]         (new) every row's k nearest rows among its leaf-mates in the forest: exact keys, approximate candidates
  *   zh_self_join_forest[_device]         (new) every pair of leaf-mates whose key is at or below one threshold key, each pair once: exact keys,
  *                                        approximate candidates
+ *   zh_search_range_forest_batch[_device] (new) every member of the leaves the walk visits for a query whose key is at or below the query's
+ *                                        threshold key, as a CSR: exact keys, approximate candidates
  *   zh_index_save / zh_index_load        (new) a snapshot of an index in ONE file of this library's own format (the reference persists through
  *                                        fjall, lsh.rs:62-120, whose files are not read here): rows, removals, forest and the planes' sample rows
  *
@@ -640,6 +642,69 @@ typedef struct zh_join_forest_info {  /* the most recent zh_self_join_forest* ca
     uint32_t redone;      /* path-2 batches whose candidate pool ran over and were answered by path 1 */
 } zh_join_forest_info;
 ZH_API int zh_self_join_forest_info(const zh_index *idx, zh_join_forest_info *out);
+
+/* ---- forest range search (new): all rows within a radius AMONG THE VISITED LEAVES ------------------------------------------------------------
+ * zh_search_range_batch multiplies every query by every live row; this call scores a query only against the leaves the forest's walk visits for
+ * it.  The arguments, the CSR result, the keys, the (key, id) order, id_base, UINT64_MAX = "every candidate" and the capacity contract (ZH_ELIMIT
+ * with *out_total and ALL offsets exact; capacity = 0 with NULL arrays counts only) are zh_search_range_batch's; `probe` comes after max_keys.
+ * Candidate set.  The candidates of query i are every member of every leaf that the reference's walk (tree_result, lsh.rs:290-348: what
+ * zh_search_batch(top_k = probe) performs) visits for that query with n = probe, the union over all trees taken as a set.  A visited leaf
+ * contributes ALL its rows, not only the rows a top-k search would keep of it.  The visit sequence depends on leaf lengths and plane signs only,
+ * never on the metric.  probe = 1 .. ZH_MAX_TOPK; probe = 1 is the leaf the query hashes to in each tree (plus the backups of empty leaves).
+ * Known behaviour of the walk: once probe exceeds the typical leaf length the backups cascade and most of a tree is visited -- at
+ * max_node_size 5, 15 trees and 2000 rows, probe = 10 visits about 5400 leaves per query.  Removed rows are in no leaf and are never hits; rows
+ * appended since the last build are in no leaf and are never hits.
+ * Only the candidate set is approximate: the answer is exactly the subset of zh_search_range_batch's hits that are candidates, bit for bit, for
+ * all 13 metric / mode / power combinations and every dimension, whatever the path, the scan's row order or the run.  A row that several trees or
+ * several visited leaves offer comes once.  On a forest of ONE tree whose root is a leaf the answer is zh_search_range_batch's.
+ * A NULL index, q or max_keys with b > 0, NULL out_offsets / out_total, NULL out_ids / out_keys with capacity > 0, an unknown metric, probe = 0
+ * (ZH_EINVAL) and probe > ZH_MAX_TOPK (ZH_ELIMIT) are refused before any device is touched.  b = 0, an empty index and an index of removed rows
+ * only give all-zero offsets and ZH_OK; an index with live rows and no trees, or with trees an interrupted insert left stale, is ZH_ESTATE, as
+ * for zh_self_join_forest.  Locking as zh_search_range_batch_device; zh_stats_t, every sibling info struct, the cached live-row views and the
+ * search contexts of the LSH search (their running means included) are left alone: zh_search_range_forest_info describes the most recent call.
+ * Internal batches of at most 1024 queries.  The walk runs with the LSH search's own kernels on scratch of this call; its totals reach the host
+ * before the scoring is sized, and an internal batch whose visits hold more than 2^25 rows (256 MiB of path-1 keys) is cut in half, query-wise,
+ * until it fits or is one query.  Each hit once: with leaf_of[row][tree] (as zh_self_join_forest) a pair (query, row) met in a visited leaf of
+ * tree t is kept only if the row's leaf in no earlier tree is among the leaves the query visited there; the lookup is the query's own visit list,
+ * ordered by leaf.  Path 1 (every metric, dimension and leaf shape): the f32 leaf sweep keys every visited row, and the keys at
+ * or below the threshold that pass the rule are hits.  Path 2 (ZH_L2SQ, ZH_L2, ZH_COSINE at dim 256 / 384 / 512 / 768 / 1024, the fp16 row copy
+ * present, zh_options.max_node_size >= 64): the visited leaves, in batches of at most 2048 tiles of 16 rows (or one longer leaf alone), are
+ * gathered once out of the copy and ONE launch per batch multiplies each leaf's row tiles by the 16-query column tiles of that leaf's visitors on
+ * the matrix cores, for an interval per pair; pairs whose interval reaches down to the threshold and that pass the rule are candidates and get
+ * the canonical key (zh_search_range_batch's survivor pass).  Path 2 is leaf-major: it pays where leaves are shared, so an internal batch whose
+ * visited leaves have fewer than 32 visitors on average stays on path 1 (its tile columns would be mostly padding and the gather would move more
+ * bytes than the sweep reads; DESIGN.md s19, measured).  An internal batch whose candidates outgrow their pool is answered by path 1 (`redone`).
+ * ZH_FRANGE_PATH in the environment (read per call): 1 forces path 1, 2 takes path 2 wherever the rule above admits it, whatever the visitor
+ * count; ZH_FRANGE_CAND_CAP=n (read per call; tests) sets the candidate pool's slots per internal batch.
+ * Device scratch is per call and released before return: 4 bytes per (stored row, tree) of leaf_of and 4 bytes per tree node; per internal batch
+ * 16 bytes per tree node, about 1.3 KB per (query, tree) pair, 56 bytes per leaf visit and 14 bytes per (leaf, visitor); path 1 8 bytes per
+ * visited row (at most 2^25 of them, or one query's); path 2 per batch of leaves 2 dim + 12 bytes per gathered row (at most max(32768, the
+ * longest leaf padded to tiles)), 2 dim + 24 bytes per query and 8 bytes per candidate slot (max(1.25 x the capacity left, 4096 per query), never
+ * more than the visited rows); with P = min(capacity left, visited rows) hit slots 32 P bytes of hit pool and sort buffers + the sort's temporary
+ * storage; for the host call 16 bytes per hit of the batch. */
+ZH_API int zh_search_range_forest_batch(zh_index *idx, const float *q, size_t b, const uint64_t *max_keys, uint32_t probe, int metric, int cosine_mode,
+                                        uint64_t capacity, uint64_t *out_offsets, uint64_t *out_ids, uint64_t *out_keys, uint64_t *out_total);
+/* The same with queries, thresholds and every output (out_total included) in device memory; enqueued on `stream` (NULL = the index's own stream),
+ * complete on return. */
+ZH_API int zh_search_range_forest_batch_device(zh_index *idx, const float *d_q, size_t b, const uint64_t *d_max_keys, uint32_t probe, int metric,
+                                               int cosine_mode, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *d_out_ids, uint64_t *d_out_keys,
+                                               uint64_t *d_out_total, void *stream);
+typedef struct zh_range_forest_info {  /* the most recent zh_search_range_forest_* call on this index */
+    uint64_t batch;       /* queries */
+    uint64_t rows_live;   /* live rows of the index */
+    uint32_t trees;       /* trees of the forest */
+    uint32_t probe;       /* the walk's n */
+    uint32_t path;        /* 1: the f32 leaf sweep over the visits; 2: matrix-core intervals leaf by leaf, canonical keys for candidates */
+    uint32_t redone;      /* path-2 internal batches answered by path 1 because the candidate pool ran over */
+    uint64_t visits;      /* leaf visits over all queries and trees, from the walk (it records a visit where it takes rows: no empty leaf) */
+    uint64_t leaf_rows;   /* sum of the visited leaves' lengths over all visits: the work before sharing and de-duplication */
+    uint64_t hits;        /* (row, query) pairs within their query's threshold, each once (exact whatever the capacity) */
+    uint64_t candidates;  /* path 2: pairs that got the canonical key, over the internal batches path 2 completed */
+    uint64_t launches;    /* launches of the scoring kernel (the sweep on path 1, one matrix-core launch per batch of leaves on path 2) */
+    uint64_t tiles;       /* path 2: 16 x 16 tile products issued: per internal batch the sum over visited leaves of ceil(len / 16) x
+                             ceil(visitors / 16); 0 on path 1 */
+} zh_range_forest_info;
+ZH_API int zh_search_range_forest_info(const zh_index *idx, zh_range_forest_info *out);
 
 /* Pipelined form of zh_search_batch_device (new; the reference has one blocking search per query): a context
  * is one in-flight batch with its own scratch.  The context calls do NOT take the index's internal lock (the blocking

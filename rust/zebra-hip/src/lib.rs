@@ -176,6 +176,23 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_range_forest_info {
+        pub batch: u64,
+        pub rows_live: u64,
+        pub trees: u32,
+        pub probe: u32,
+        pub path: u32,
+        pub redone: u32,
+        pub visits: u64,
+        pub leaf_rows: u64,
+        pub hits: u64,
+        pub candidates: u64,
+        pub launches: u64,
+        pub tiles: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_filtered_info {
         pub batch: u64,
         pub rows_live: u64,
@@ -295,6 +312,13 @@ pub mod ffi {
         pub fn zh_self_join_forest_device(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, d_out_a: *mut u64,
                                           d_out_b: *mut u64, d_out_keys: *mut u64, d_out_total: *mut u64, stream: *mut c_void) -> c_int;
         pub fn zh_self_join_forest_info(idx: *const zh_index, out: *mut zh_join_forest_info) -> c_int;
+        pub fn zh_search_range_forest_batch(idx: *mut zh_index, q: *const f32, b: usize, max_keys: *const u64, probe: u32, metric: c_int,
+                                            cosine_mode: c_int, capacity: u64, out_offsets: *mut u64, out_ids: *mut u64, out_keys: *mut u64,
+                                            out_total: *mut u64) -> c_int;
+        pub fn zh_search_range_forest_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, d_max_keys: *const u64, probe: u32, metric: c_int,
+                                                   cosine_mode: c_int, capacity: u64, d_out_offsets: *mut u64, d_out_ids: *mut u64,
+                                                   d_out_keys: *mut u64, d_out_total: *mut u64, stream: *mut c_void) -> c_int;
+        pub fn zh_search_range_forest_info(idx: *const zh_index, out: *mut zh_range_forest_info) -> c_int;
         pub fn zh_search_batch_device(idx: *mut zh_index, d_q: *const f32, b: usize, k: usize, metric: c_int, cosine_mode: c_int,
                                       d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_distance_pair(metric: c_int, cosine_mode: c_int, a: *const f32, b: *const f32, dim: usize, out_key: *mut u64,
@@ -626,6 +650,44 @@ impl<const N: usize> LSHIndex<N> {
             })?;
         }
         Ok((0..b).map(|i| (offsets[i] as usize..offsets[i + 1] as usize).map(|j| (t.of_row[ids[j] as usize], keys[j])).collect()).collect())
+    }
+
+    /// (new) the forest range search (zh_search_range_forest_batch): search_range_batch's hits among the members of the leaves the walk visits for
+    /// each query with n = `probe` (1: the leaf the query hashes to in each tree); exact keys on an approximate candidate set, each hit once.
+    /// One call that counts (capacity 0), one that fetches.  Needs a built forest.
+    pub fn search_range_forest_batch<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        queries: &[Embedding<N>],
+        max_keys: &[DistanceUnit],
+        probe: u32,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<Vec<(Uuid, DistanceUnit)>>> {
+        let b = queries.len();
+        anyhow::ensure!(max_keys.len() == b, "search_range_forest_batch: one threshold key per query");
+        let t = self.ids.read().unwrap();
+        let (mut offsets, mut total) = (vec![0u64; b + 1], 0u64);
+        let rc = unsafe {
+            ffi::zh_search_range_forest_batch(self.hip.0, queries.as_ptr() as *const f32, b, max_keys.as_ptr(), probe, Met::METRIC, metric.param(), 0,
+                                              offsets.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), &mut total)
+        };
+        if rc != -5 {
+            check(rc)?; // (-5 = ZH_ELIMIT: the hits exceed capacity 0; offsets and total are exact)
+        }
+        let (mut ids, mut keys) = (vec![0u64; total as usize + 1], vec![0u64; total as usize + 1]);
+        if total > 0 {
+            check(unsafe {
+                ffi::zh_search_range_forest_batch(self.hip.0, queries.as_ptr() as *const f32, b, max_keys.as_ptr(), probe, Met::METRIC, metric.param(),
+                                                  total, offsets.as_mut_ptr(), ids.as_mut_ptr(), keys.as_mut_ptr(), &mut total)
+            })?;
+        }
+        Ok((0..b).map(|i| (offsets[i] as usize..offsets[i + 1] as usize).map(|j| (t.of_row[ids[j] as usize], keys[j])).collect()).collect())
+    }
+
+    /// what the most recent forest range search did (zh_search_range_forest_info)
+    pub fn range_forest_info(&self) -> anyhow::Result<ffi::zh_range_forest_info> {
+        let mut info = ffi::zh_range_forest_info::default();
+        check(unsafe { ffi::zh_search_range_forest_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// (new) every pair of distinct live vectors (a, b), a before b by row, whose key (stored b against a query equal to a) is <= `max_key`

@@ -136,6 +136,15 @@ class JoinForestInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RangeForestInfo(C.Structure):
+    _fields_ = [("batch", C.c_uint64), ("rows_live", C.c_uint64), ("trees", C.c_uint32), ("probe", C.c_uint32), ("path", C.c_uint32),
+                ("redone", C.c_uint32), ("visits", C.c_uint64), ("leaf_rows", C.c_uint64), ("hits", C.c_uint64), ("candidates", C.c_uint64),
+                ("launches", C.c_uint64), ("tiles", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CompactInfo(C.Structure):
     _fields_ = [("rows_before", C.c_uint64), ("rows_after", C.c_uint64), ("rows_moved", C.c_uint64), ("bytes_moved", C.c_uint64),
                 ("scratch_bytes", C.c_uint64), ("capacity_rows", C.c_uint64), ("copy_bytes_released", C.c_uint64), ("ms", C.c_double)]
@@ -214,6 +223,9 @@ SYMBOLS = [
     ("zh_self_join_forest", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_device", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_info", _i, [_vp, _vp]),
+    ("zh_search_range_forest_batch", _i, [_vp, _vp, _sz, _vp, _u32, _i, _i, _u64, _vp, _vp, _vp, _vp]),
+    ("zh_search_range_forest_batch_device", _i, [_vp, _vp, _sz, _vp, _u32, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
+    ("zh_search_range_forest_info", _i, [_vp, _vp]),
     ("zh_search_ctx_create", _i, [_vp, _vp]),
     ("zh_search_ctx_destroy", None, [_vp]),
     ("zh_search_begin", _i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),

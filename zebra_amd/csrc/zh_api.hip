@@ -287,6 +287,13 @@ struct zh_index {
     // panel's pieces and per-line {leaf, key offset}, path 2's segments and candidate pool
     DevBuf fj_leafof, fj_pieces, fj_linel, fj_linek, fj_segs, fj_cand;
     zh_join_forest_info fj_info{};  // (stats_mu)
+    // the forest range search's per-call scratch beside the range search's and the forest join's (all released before the call returns): the walk's
+    // workspace of one internal batch (what a search context keeps in its w* buffers: pair counts, inline visits, the three bases, totals, per-leaf
+    // counts / fill cursors / group bases, the visit log), its visits and groups, the sorted visit words and their sort partner and temporary
+    // storage, and path 2's leaves
+    DevBuf fr_counts, fr_inline, fr_rowbase, fr_candbase, fr_visitbase, fr_totals, fr_leafcount, fr_leaffill, fr_groupbase, fr_grouprowbase, fr_loghead,
+        fr_logctl, fr_logpool, fr_visits, fr_groups, fr_groupoff, fr_vk0, fr_vk1, fr_vtmp, fr_segs;
+    zh_range_forest_info fr_info{};  // (stats_mu)
 
     bool broken = false;  // an incremental add failed half way: trees are stale until zh_index_build
     bool rows_torn = false;  // ... or a compaction failed after rows had begun to move (set with broken): the TABLE is inconsistent until zh_index_clear
@@ -3446,7 +3453,7 @@ extern "C" int zh_search_batch(zh_index *ix, const float *q, size_t b, size_t k,
 #define ZH_EXACT_BATCH 1024u             // queries per internal batch
 #define ZH_EXACT_KEY_BYTES (size_t(1) << 30)  // key scratch of one row chunk: queries x rows x 8 bytes
 
-// ---- what the families below share: exact, filtered and range search, self-join, k-NN graph, forest k-NN graph, forest self-join ----
+// ---- what the families below share: exact, filtered and range search, self-join, k-NN graph, forest k-NN graph, forest self-join, forest range search ----
 static hipStream_t call_stream(const zh_index *ix, void *stream) { return stream ? (hipStream_t)stream : ix->stream; }
 
 // the score kernels' parameter: the mode, for the metrics that have one
@@ -3454,8 +3461,9 @@ static int score_param(int metric, int mode) { return (metric == ZH_COSINE || me
 
 // The per-call scratch, each family's buffers listed once.  The guard of a call gives its set back to the driver however the call returns: an idle
 // index holds only the live-row views (ex_live and ex_bits survive every call; zh_index_destroy frees them).  Every family scans with the exact
-// search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's.
-enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64 };  // one bit per list
+// search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's, the forest range search with
+// the range search's and the forest join's.
+enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128 };  // one bit per list
 enum : unsigned {
     SCRATCH_EXACT = SCR_EX,
     SCRATCH_FILTER = SCR_FL | SCRATCH_EXACT,
@@ -3464,6 +3472,7 @@ enum : unsigned {
     SCRATCH_KNN = SCR_KN | SCRATCH_EXACT,
     SCRATCH_FKNN = SCR_FK | SCRATCH_KNN,
     SCRATCH_FJOIN = SCR_FJ | SCRATCH_JOIN | SCRATCH_FKNN,
+    SCRATCH_FRANGE = SCR_FR | SCRATCH_RANGE | SCRATCH_FJOIN,
 };
 static void release_scratch(zh_index *ix, unsigned families) {
     auto drop = [&](unsigned list, std::initializer_list<DevBuf *> bs) {
@@ -3484,6 +3493,9 @@ static void release_scratch(zh_index *ix, unsigned families) {
                   &ix->fk_cbase, &ix->fk_groups, &ix->fk_groff, &ix->fk_segs, &ix->fk_colsrc, &ix->fk_crow, &ix->fk_hrow, &ix->fk_held, &ix->fk_CA,
                   &ix->fk_cmeta, &ix->fk_cqm, &ix->fk_HA, &ix->fk_hmeta, &ix->fk_qrow, &ix->fk_maxk, &ix->fk_redo, &ix->fk_pos});
     drop(SCR_FJ, {&ix->fj_leafof, &ix->fj_pieces, &ix->fj_linel, &ix->fj_linek, &ix->fj_segs, &ix->fj_cand});
+    drop(SCR_FR, {&ix->fr_counts, &ix->fr_inline, &ix->fr_rowbase, &ix->fr_candbase, &ix->fr_visitbase, &ix->fr_totals, &ix->fr_leafcount, &ix->fr_leaffill,
+                  &ix->fr_groupbase, &ix->fr_grouprowbase, &ix->fr_loghead, &ix->fr_logctl, &ix->fr_logpool, &ix->fr_visits, &ix->fr_groups, &ix->fr_groupoff,
+                  &ix->fr_vk0, &ix->fr_vk1, &ix->fr_vtmp, &ix->fr_segs});
 }
 struct ScratchGuard {
     zh_index *ix;
@@ -4040,6 +4052,33 @@ static int range_batch2(zh_index *ix, const float *dQ, uint32_t B, const uint64_
     return ZH_OK;
 }
 
+// Both range families, once an internal batch's hits are counted (rg_cnt) and pooled (rg_pv0 / rg_pk0): dOff[0 .. B] = run->total + the exclusive
+// sums of the counts; and, while the capacity holds, the pool ordered by (query, key, id) into dIds / dKeys at run->total (host_out: into staging
+// and from there to the HOST arrays dIds / dKeys).
+static int range_emit(zh_index *ix, uint32_t B, uint64_t hits, uint64_t pool_cap, RangeRun *run, uint64_t *dOff, uint64_t *dIds, uint64_t *dKeys,
+                      bool host_out, hipStream_t s) {
+    int rc;
+    HIPCHK(zh_launch_range_offsets(ix->rg_cnt.as<uint32_t>(), B, run->total, dOff, s));
+    if (!run->over && hits > pool_cap) run->over = true;  // (pool_cap = the capacity left, or every pair there is)
+    if (!run->over && hits) {
+        uint64_t *dV[2] = {nullptr, nullptr}, *dK[2] = {nullptr, nullptr};
+        size_t tmp_bytes = 0;
+        HIPCHK(zh_launch_range_sort(dV, dK, hits, ix->n_rows, B, nullptr, &tmp_bytes, 0, nullptr, nullptr, s));
+        if ((rc = ix->rg_pv1.ensure(hits * 8)) || (rc = ix->rg_pk1.ensure(hits * 8)) || (rc = ix->rg_tmp.ensure(tmp_bytes))) return rc;
+        if (host_out && ((rc = ix->rg_oids.ensure(hits * 8)) || (rc = ix->rg_okeys.ensure(hits * 8)))) return rc;
+        dV[0] = ix->rg_pv0.as<uint64_t>(); dV[1] = ix->rg_pv1.as<uint64_t>();
+        dK[0] = ix->rg_pk0.as<uint64_t>(); dK[1] = ix->rg_pk1.as<uint64_t>();
+        uint64_t *oi = host_out ? ix->rg_oids.as<uint64_t>() : dIds + run->total, *ok = host_out ? ix->rg_okeys.as<uint64_t>() : dKeys + run->total;
+        HIPCHK(zh_launch_range_sort(dV, dK, hits, ix->n_rows, B, ix->rg_tmp.p, &tmp_bytes, ix->opt.id_base, oi, ok, s));
+        if (host_out) {
+            HIPCHK(hipMemcpyAsync(dIds + run->total, oi, hits * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(dKeys + run->total, ok, hits * 8, hipMemcpyDeviceToHost, s));
+        }
+    }
+    run->total += hits;
+    return ZH_OK;
+}
+
 // One internal batch (B <= ZH_EXACT_BATCH) on device pointers: its hits counted and pooled by path 2 where it serves, by path 1 otherwise and
 // when path 2's candidates ran over; dOff[0 .. B] = run->total + the exclusive sums of the counts; and, while the capacity holds, the pool
 // ordered by (query, key, id) into dIds / dKeys at run->total (host_out: into staging and from there to the HOST arrays dIds / dKeys).
@@ -4072,26 +4111,8 @@ static int range_one(zh_index *ix, const float *dQ, uint32_t B, const uint64_t *
             HIPCHK(hipStreamSynchronize(s));
         }
     }
-    const uint64_t hits = h_ctr[0];
-    HIPCHK(zh_launch_range_offsets(ix->rg_cnt.as<uint32_t>(), B, run->total, dOff, s));
-    if (!run->over && hits > pool_cap) run->over = true;  // (pool_cap = the capacity left, or every pair there is)
-    if (!run->over && hits) {
-        uint64_t *dV[2] = {nullptr, nullptr}, *dK[2] = {nullptr, nullptr};
-        size_t tmp_bytes = 0;
-        HIPCHK(zh_launch_range_sort(dV, dK, hits, ix->n_rows, B, nullptr, &tmp_bytes, 0, nullptr, nullptr, s));
-        if ((rc = ix->rg_pv1.ensure(hits * 8)) || (rc = ix->rg_pk1.ensure(hits * 8)) || (rc = ix->rg_tmp.ensure(tmp_bytes))) return rc;
-        if (host_out && ((rc = ix->rg_oids.ensure(hits * 8)) || (rc = ix->rg_okeys.ensure(hits * 8)))) return rc;
-        dV[0] = ix->rg_pv0.as<uint64_t>(); dV[1] = ix->rg_pv1.as<uint64_t>();
-        dK[0] = ix->rg_pk0.as<uint64_t>(); dK[1] = ix->rg_pk1.as<uint64_t>();
-        uint64_t *oi = host_out ? ix->rg_oids.as<uint64_t>() : dIds + run->total, *ok = host_out ? ix->rg_okeys.as<uint64_t>() : dKeys + run->total;
-        HIPCHK(zh_launch_range_sort(dV, dK, hits, ix->n_rows, B, ix->rg_tmp.p, &tmp_bytes, ix->opt.id_base, oi, ok, s));
-        if (host_out) {
-            HIPCHK(hipMemcpyAsync(dIds + run->total, oi, hits * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(dKeys + run->total, ok, hits * 8, hipMemcpyDeviceToHost, s));
-        }
-    }
-    run->total += hits;
-    inf->hits += hits;
+    if ((rc = range_emit(ix, B, h_ctr[0], pool_cap, run, dOff, dIds, dKeys, host_out, s))) return rc;
+    inf->hits += h_ctr[0];
     return ZH_OK;
 }
 
@@ -5218,6 +5239,365 @@ extern "C" int zh_self_join_forest(zh_index *ix, uint64_t max_key, int metric, i
 
 extern "C" int zh_self_join_forest_info(const zh_index *ix, zh_join_forest_info *out) {
     return get_info(ix, &zh_index::fj_info, out, "zh_self_join_forest_info");
+}
+
+// ------------------------------------------------------------------------------------------------
+// forest range search (zh_frange.hip): every member of the leaves the walk visits for a query whose key is <= the query's threshold key, each
+// (query, row) once, as the range search's CSR.  DESIGN.md s19
+// ------------------------------------------------------------------------------------------------
+#define ZH_FRANGE_MIN_VISITORS 32u  // path 2 serves an internal batch whose visited leaves have at least this many visitors on average (s19: it lost at 4 and 15, won at 64)
+
+struct FrangeRun : ForestRun {
+    RangeRun rr;
+    int metric = 0, mode = 0;
+    uint32_t probe = 0;
+    bool force2 = false;        // ZH_FRANGE_PATH=2: path 2 wherever the path rule admits it, whatever the visit gate says
+    bool env_cand = false;      // ZH_FRANGE_CAND_CAP is set ...
+    uint64_t env_cand_cap = 0;  // ... to this
+    size_t log_chunks = 8192;   // the visit log's chunks (ZH_WALK_LOG_CHUNKS, read per call): a batch that logs more walks again, emitting
+    std::vector<uint32_t> node_tree;
+    const uint64_t *vsorted = nullptr;  // the internal batch's sorted visit words
+    zh_range_forest_info inf{};
+};
+
+// The path rule and path 2's views, the node -> tree map on both sides and each row's leaf per tree on the device (the forest join's table).
+static int frange_setup(zh_index *ix, hipStream_t s, FrangeRun *run) {
+    int rc;
+    if ((rc = forest_path2(ix, "ZH_FRANGE_PATH", run->metric, s, run))) return rc;
+    run->node_tree = forest_walk(ix, nullptr);
+    if ((rc = ix->fk_ntree.ensure(run->node_tree.size() * 4)) || (rc = ix->jn_ctr.ensure(32)) ||
+        (rc = ix->fj_leafof.ensure(std::max<size_t>((size_t)ix->n_rows * run->T * 4, 4))))
+        return rc;
+    HIPCHK(hipMemcpyAsync(ix->fk_ntree.p, run->node_tree.data(), run->node_tree.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(ix->jn_ctr.p, 0, 32, s));
+    HIPCHK(zh_launch_fjoin_rowleaf(ix->node_pack.as<int4>(), ix->fk_ntree.as<uint32_t>(), ix->n_nodes, ix->leaf_ids.as<uint32_t>(), run->T, ix->n_rows,
+                                   ix->fj_leafof.as<uint32_t>(), ix->jn_ctr.as<unsigned long long>() + 2, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const char *env_c = getenv("ZH_FRANGE_CAND_CAP"), *env_l = getenv("ZH_WALK_LOG_CHUNKS"), *env_p = getenv("ZH_FRANGE_PATH");
+    run->force2 = env_p && atoi(env_p) == 2;
+    if (env_c && atoll(env_c) > 0) { run->env_cand = true; run->env_cand_cap = (uint64_t)atoll(env_c); }
+    if (env_l && atoll(env_l) > 0) run->log_chunks = (size_t)atoll(env_l);
+    return ZH_OK;
+}
+
+static ZhWalkLog frange_log(const zh_index *ix, const FrangeRun &run) {
+    ZhWalkLog l;
+    l.pool = ix->fr_logpool.as<uint2>();
+    l.capacity = (uint32_t)std::min<size_t>(run.log_chunks, 0xFFFFFFFEu);
+    l.head = ix->fr_loghead.as<uint32_t>();
+    l.ctl = ix->fr_logctl.as<ZhLogCtl>();
+    l.leaf_entries = 0;
+    return l;
+}
+
+// The walk's first half for B queries, as ctx_begin runs it, with n = probe and every sign on demand: counts, scans, *tot on the host.
+static int frange_walk(zh_index *ix, const FrangeRun &run, const float *dQ, uint32_t B, hipStream_t s, ZhTotals *tot) {
+    const uint32_t d = ix->opt.dim;
+    const uint64_t pairs = (uint64_t)B * run.T;
+    const size_t nn = std::max<uint32_t>(ix->n_nodes, 1);
+    if (pairs >= (1ull << 26)) return fail(ZH_ELIMIT, "batch * num_trees >= 2^26");
+    int rc;
+    if ((rc = ix->fr_counts.ensure(pairs * sizeof(ZhPairCounts))) || (rc = ix->fr_inline.ensure(pairs * ZH_INLINE_VISITS * sizeof(ZhVisit))) ||
+        (rc = ix->fr_rowbase.ensure((pairs + 1) * 8)) || (rc = ix->fr_candbase.ensure((pairs + 1) * 8)) || (rc = ix->fr_visitbase.ensure((pairs + 1) * 8)) ||
+        (rc = ix->fr_totals.ensure(sizeof(ZhTotals))) || (rc = ix->fr_leafcount.ensure(nn * 4)) || (rc = ix->fr_leaffill.ensure(nn * 4)) ||
+        (rc = ix->fr_groupbase.ensure(nn * 4)) || (rc = ix->fr_grouprowbase.ensure(nn * 8)) || (rc = ix->fr_loghead.ensure(pairs * 4)) ||
+        (rc = ix->fr_logctl.ensure(sizeof(ZhLogCtl))) || (rc = ix->fr_logpool.ensure(run.log_chunks * ZH_LOG_CHUNK * sizeof(uint2))))
+        return rc;
+    const ZhForestDev f = forest_dev(ix);
+    HIPCHK(zh_launch_batch_init(ix->fr_leafcount.as<uint32_t>(), ix->fr_leaffill.as<uint32_t>(), (uint32_t)nn, ix->fr_logctl.as<ZhLogCtl>(),
+                                ix->fr_totals.as<ZhTotals>(), s));
+    HIPCHK(zh_launch_walk_count(f, dQ, B, d, (int32_t)run.probe, nullptr, 0, 0, ix->fr_counts.as<ZhPairCounts>(), ix->fr_inline.as<ZhVisit>(),
+                                ix->fr_leafcount.as<uint32_t>(), frange_log(ix, run), s));
+    HIPCHK(zh_launch_leaf_scan(f, ix->fr_leafcount.as<uint32_t>(), ix->fr_groupbase.as<uint32_t>(), ix->fr_grouprowbase.as<uint64_t>(),
+                               ix->fr_totals.as<ZhTotals>(), s));
+    HIPCHK(zh_launch_pair_scan(ix->fr_counts.as<ZhPairCounts>(), (uint32_t)pairs, ix->fr_rowbase.as<uint64_t>(), ix->fr_candbase.as<uint64_t>(),
+                               ix->fr_visitbase.as<uint64_t>(), ix->fr_totals.as<ZhTotals>(), ix->fr_logctl.as<ZhLogCtl>(), s));
+    HIPCHK(hipMemcpyAsync(tot, ix->fr_totals.p, sizeof(ZhTotals), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (tot->visits > 0xFFFFFFFull || tot->rows >= (1ull << 36))
+        return fail(ZH_ELIMIT, "more than 2^28 leaf visits or 2^36 visited rows in one batch; use a smaller batch");
+    return ZH_OK;
+}
+
+// ... and its second half, as ctx_finish runs it: the visits placed (or walked again when the log ran over) and the leaf groups joined; then the
+// lookup of visited leaves.
+static int frange_place(zh_index *ix, FrangeRun *run, const float *dQ, uint32_t B, const ZhTotals &tot, hipStream_t s) {
+    const uint32_t d = ix->opt.dim;
+    const uint64_t nv = std::max<uint64_t>(tot.visits, 1), ng = std::max<uint64_t>(tot.groups, 1);
+    int rc;
+    if ((rc = ix->fr_visits.ensure(nv * sizeof(ZhVisit))) || (rc = ix->fr_groups.ensure(ng * sizeof(ZhGroup))) || (rc = ix->fr_groupoff.ensure(ng * 8)) ||
+        (rc = ix->fr_vk0.ensure(nv * 8)) || (rc = ix->fr_vk1.ensure(nv * 8)))
+        return rc;
+    const ZhForestDev f = forest_dev(ix);
+    if (!(tot.flags & 1u))
+        HIPCHK(zh_launch_expand(f, B, ix->fr_counts.as<ZhPairCounts>(), ix->fr_inline.as<ZhVisit>(), ix->fr_rowbase.as<uint64_t>(),
+                                ix->fr_candbase.as<uint64_t>(), ix->fr_visitbase.as<uint64_t>(), ix->fr_visits.as<ZhVisit>(), ix->fr_leafcount.as<uint32_t>(),
+                                ix->fr_leaffill.as<uint32_t>(), ix->fr_groupbase.as<uint32_t>(), ix->fr_grouprowbase.as<uint64_t>(),
+                                ix->fr_groups.as<ZhGroup>(), ix->fr_groupoff.as<uint64_t>(), frange_log(ix, *run), s));
+    else
+        HIPCHK(zh_launch_walk_emit(f, dQ, B, d, (int32_t)run->probe, nullptr, 0, 0, ix->fr_counts.as<ZhPairCounts>(), ix->fr_inline.as<ZhVisit>(),
+                                   ix->fr_rowbase.as<uint64_t>(), ix->fr_candbase.as<uint64_t>(), ix->fr_visitbase.as<uint64_t>(), ix->fr_visits.as<ZhVisit>(),
+                                   ix->fr_leafcount.as<uint32_t>(), ix->fr_leaffill.as<uint32_t>(), ix->fr_groupbase.as<uint32_t>(),
+                                   ix->fr_grouprowbase.as<uint64_t>(), ix->fr_groups.as<ZhGroup>(), ix->fr_groupoff.as<uint64_t>(), s));
+    uint64_t *vk[2] = {ix->fr_vk0.as<uint64_t>(), ix->fr_vk1.as<uint64_t>()};
+    size_t tmp_bytes = 0;
+    HIPCHK(zh_launch_frange_visit_index(nullptr, tot.visits, nullptr, run->T, (uint64_t)B * run->T, vk, nullptr, &tmp_bytes, &run->vsorted, s));
+    if ((rc = ix->fr_vtmp.ensure(tmp_bytes))) return rc;
+    HIPCHK(zh_launch_frange_visit_index(ix->fr_visits.as<ZhVisit>(), tot.visits, ix->fk_ntree.as<uint32_t>(), run->T, (uint64_t)B * run->T, vk, ix->fr_vtmp.p,
+                                        &tmp_bytes, &run->vsorted, s));
+    return ZH_OK;
+}
+
+// path 1 of one internal batch: the f32 leaf sweep over the walk's groups keys every visited row; frange_collect_kernel reads the visits' slices
+static int frange_batch1(zh_index *ix, FrangeRun *run, const float *dQ, uint32_t B, const uint64_t *dMaxK, const ZhTotals &tot, uint64_t pool_cap,
+                         hipStream_t s) {
+    const uint32_t d = ix->opt.dim;
+    int rc;
+    if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_keys.ensure(std::max<uint64_t>(tot.rows, 1) * 8))) return rc;
+    HIPCHK(hipMemsetAsync(ix->rg_cnt.p, 0, (size_t)B * 4, s));
+    HIPCHK(hipMemsetAsync(ix->rg_ctr.p, 0, 16, s));
+    if (!tot.visits) return ZH_OK;
+    HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
+    HIPCHK(zh_launch_sweep(ix->X.as<float>(), d, dQ, ix->ex_QQ.as<float>(), ix->fr_groups.as<ZhGroup>(), ix->fr_groupoff.as<uint64_t>(), tot.groups, nullptr,
+                           ix->leaf_ids.as<uint32_t>(), tot.group_rows, run->metric, score_param(run->metric, run->mode), ix->ex_keys.as<uint64_t>(), s));
+    HIPCHK(zh_launch_frange_collect(ix->fr_visits.as<ZhVisit>(), tot.visits, ix->ex_keys.as<uint64_t>(), ix->leaf_ids.as<uint32_t>(), ix->n_rows,
+                                    ix->fk_ntree.as<uint32_t>(), run->vsorted, ix->fr_visitbase.as<uint64_t>(), ix->fj_leafof.as<uint32_t>(), run->T, dMaxK,
+                                    ix->rg_cnt.as<uint32_t>(), ix->rg_ctr.as<unsigned long long>(), ix->rg_pv0.as<uint64_t>(), ix->rg_pk0.as<uint64_t>(), pool_cap,
+                                    s));
+    run->inf.launches++;
+    return ZH_OK;
+}
+
+// Path 2 of one internal batch: the queries' halves and bounds, the visited leaves listed from the per-leaf visit counts (node order) and scored
+// in batches of at most ZH_FKNN_COL_TILES row tiles (or ONE longer leaf alone) into one candidate pool -- every batch's leaves and tile sources
+// go to the device once, then per batch the gather and ONE launch, nothing waited for in between -- then the range search's survivor pass.
+// *used = false: the visit gate keeps the batch on path 1 (fewer than ZH_FRANGE_MIN_VISITORS visits per visited leaf on average: the tile columns
+// would be mostly padding and the gather would cost more bytes than the f32 sweep reads; ZH_FRANGE_PATH=2 skips the gate).  On return with *used
+// the stream has been waited for and h_ctr = {hits, candidates}; candidates > cand_cap: the pool ran over and nothing was counted.
+static int frange_batch2(zh_index *ix, FrangeRun *run, const float *dQ, uint32_t B, const uint64_t *dMaxK, const ZhTotals &tot, uint64_t pool_cap,
+                         uint64_t cand_cap, hipStream_t s, bool *used, unsigned long long h_ctr[2]) {
+    *used = false;
+    const uint32_t d = ix->opt.dim, nn = ix->n_nodes;
+    int rc;
+    std::vector<uint32_t> h_cnt(nn), h_gb(nn);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), ix->fr_leafcount.p, (size_t)nn * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_gb.data(), ix->fr_groupbase.p, (size_t)nn * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    // the visited leaves (the walk counts visits of non-empty leaves only), cut into batches: batch k = leaves [cut[k].x, cut[k + 1].x), tiles
+    // [cut[k].y, cut[k + 1].y); a leaf's col0 counts from its batch's first tile
+    std::vector<ZhFrangeSeg> segs;
+    std::vector<uint2> colsrc, cut(1, make_uint2(0, 0));
+    uint64_t tiles = 0;
+    uint32_t batch_tiles = 0, most_tiles = 0;
+    for (uint32_t nd = 0; nd < nn; nd++) {
+        if (!h_cnt[nd] || ix->h_plane[nd] >= 0 || ix->h_right[nd] <= 0) continue;
+        const uint32_t off = (uint32_t)ix->h_left[nd], len = (uint32_t)ix->h_right[nd], rt = (len + 15) / 16;
+        if (batch_tiles && batch_tiles + rt > ZH_FKNN_COL_TILES) {
+            cut.push_back(make_uint2((uint32_t)segs.size(), (uint32_t)colsrc.size()));
+            batch_tiles = 0;
+        }
+        segs.push_back(ZhFrangeSeg{batch_tiles, rt, h_gb[nd], h_cnt[nd], run->node_tree[nd], 0, 0, 0});
+        for (uint32_t c = 0; c < rt; c++) colsrc.push_back(make_uint2(off + 16 * c, std::min<uint32_t>(16, len - 16 * c)));
+        batch_tiles += rt;
+        most_tiles = std::max(most_tiles, batch_tiles);
+        tiles += (uint64_t)rt * ((h_cnt[nd] + 15) / 16);
+    }
+    cut.push_back(make_uint2((uint32_t)segs.size(), (uint32_t)colsrc.size()));
+    if (segs.empty() || (!run->force2 && tot.visits < (uint64_t)ZH_FRANGE_MIN_VISITORS * segs.size())) return ZH_OK;
+    // per batch the column tiles per block and every leaf's first block
+    std::vector<uint2> geo(cut.size() - 1);  // {blocks, ch}
+    for (size_t k = 0; k + 1 < cut.size(); k++) {
+        uint32_t n_blocks = 0;
+        const uint32_t ch = fill_chunk([&](uint32_t c) {
+            n_blocks = 0;
+            for (uint32_t l = cut[k].x; l < cut[k + 1].x; l++) {
+                segs[l].first_block = n_blocks;
+                n_blocks += (segs[l].rt + 3) / 4 * (((segs[l].visitors + 15) / 16 + c - 1) / c);
+            }
+            return n_blocks;
+        });
+        geo[k] = make_uint2(n_blocks, ch);
+    }
+    const size_t NT = colsrc.size();
+    if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_Qh.ensure((size_t)B * d * 2)) || (rc = ix->ex_qmeta.ensure((size_t)B * 16)) ||
+        (rc = ix->ex_tau.ensure((size_t)B * 4)) || (rc = ix->rg_cand.ensure(std::max<uint64_t>(cand_cap, 1) * 8)) ||
+        (rc = ix->fr_segs.ensure(segs.size() * sizeof(ZhFrangeSeg))) || (rc = ix->fk_colsrc.ensure(NT * 8)) || (rc = ix->fk_crow.ensure((size_t)most_tiles * 64)) ||
+        (rc = ix->fk_CA.ensure((size_t)most_tiles * 32 * d)) || (rc = ix->fk_cmeta.ensure((size_t)most_tiles * 128)))
+        return rc;
+    unsigned long long *ctr = ix->rg_ctr.as<unsigned long long>();
+    uint32_t *crow = ix->fk_crow.as<uint32_t>();
+    HIPCHK(hipMemcpyAsync(ix->fr_segs.p, segs.data(), segs.size() * sizeof(ZhFrangeSeg), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ix->fk_colsrc.p, colsrc.data(), NT * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
+    HIPCHK(zh_launch_qhalf(dQ, B, d, ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), 1, s));
+    HIPCHK(zh_launch_range_tau(dMaxK, B, run->metric, run->mode, ix->ex_tau.as<uint32_t>(), s));
+    HIPCHK(hipMemsetAsync(ix->rg_cnt.p, 0, (size_t)B * 4, s));
+    HIPCHK(hipMemsetAsync(ctr, 0, 16, s));
+    for (size_t k = 0; k + 1 < cut.size(); k++) {
+        const uint32_t l0 = cut[k].x, nl = cut[k + 1].x - l0, c0 = cut[k].y, nt = cut[k + 1].y - c0;
+        HIPCHK(zh_launch_fknn_cols(ix->fk_colsrc.as<uint2>() + c0, nt, ix->leaf_ids.as<uint32_t>(), ix->n_rows, crow, s));
+        HIPCHK(zh_launch_fknn_gather(d, run->v.Xh, run->v.rowMeta, run->pos, crow, nt, run->v.rho, ix->fk_CA.p, ix->fk_cmeta.as<float2>(), nullptr, s));
+        HIPCHK(zh_launch_frange_mfma(d, run->metric, run->mode, ix->fr_segs.as<ZhFrangeSeg>() + l0, nl, geo[k].x, geo[k].y, zh_group_size(d), ix->fk_CA.p,
+                                     ix->fk_cmeta.as<float2>(), crow, ix->fr_groups.as<ZhGroup>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), run->Kc,
+                                     run->v.rho, ix->ex_tau.as<uint32_t>(), run->vsorted, ix->fr_visitbase.as<uint64_t>(), ix->fj_leafof.as<uint32_t>(),
+                                     run->T, ix->rg_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
+        run->inf.launches++;
+    }
+    run->inf.tiles += tiles;
+    HIPCHK(zh_launch_range_survivors(ix->X.as<float>(), d, dQ, ix->ex_QQ.as<float>(), run->metric, run->mode, ix->rg_cand.as<uint64_t>(), ctr + 1, cand_cap, dMaxK,
+                                     ix->rg_cnt.as<uint32_t>(), ctr, ix->rg_pv0.as<uint64_t>(), ix->rg_pk0.as<uint64_t>(), pool_cap, s));
+    HIPCHK(hipMemcpyAsync(h_ctr, ctr, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // (segs and colsrc are this frame's)
+    *used = true;
+    return ZH_OK;
+}
+
+// B <= ZH_EXACT_BATCH queries on device pointers, as range_one: the walk; a batch whose visits hold more rows than path 1 may key
+// (ZH_FRANGE_KEY_ROWS) is cut in half -- up front where path 1 answers, and where path 2 ran over -- and each half walks for itself; otherwise path
+// 2 where it serves (allow2), path 1 else and when path 2's candidates ran over; then the range search's offsets, order and output.
+static int frange_one(zh_index *ix, FrangeRun *run, const float *dQ, uint32_t B, const uint64_t *dMaxK, uint64_t *dOff, uint64_t *dIds, uint64_t *dKeys,
+                      bool host_out, bool allow2, hipStream_t s) {
+    const uint32_t d = ix->opt.dim;
+    ZhTotals tot{};
+    int rc;
+    if ((rc = frange_walk(ix, *run, dQ, B, s, &tot))) return rc;
+    const bool p2 = allow2 && run->path2, too_long = tot.rows > ZH_FRANGE_KEY_ROWS && B > 1;
+    auto halves = [&](bool a2) -> int {
+        const uint32_t h = B / 2;
+        int r = frange_one(ix, run, dQ, h, dMaxK, dOff, dIds, dKeys, host_out, a2, s);
+        return r ? r : frange_one(ix, run, dQ + (size_t)h * d, B - h, dMaxK + h, dOff + h, dIds, dKeys, host_out, a2, s);
+    };
+    if (!p2 && too_long) return halves(allow2);
+    if ((rc = frange_place(ix, run, dQ, B, tot, s))) return rc;
+    RangeRun *rr = &run->rr;
+    const uint64_t pool_cap = rr->over ? 0 : std::min<uint64_t>(rr->capacity - rr->total, tot.rows);
+    if ((rc = ix->rg_cnt.ensure((size_t)B * 4)) || (rc = ix->rg_ctr.ensure(16)) || (rc = ix->rg_pv0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)) ||
+        (rc = ix->rg_pk0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)))
+        return rc;
+    unsigned long long h_ctr[2] = {0, 0};
+    bool done = false;
+    if (p2 && tot.visits) {
+        uint64_t cand_cap = std::min<uint64_t>(tot.rows, std::max<uint64_t>(pool_cap + pool_cap / 4, (uint64_t)ZH_RANGE_CAND_FLOOR * B));
+        if (run->env_cand) cand_cap = run->env_cand_cap;
+        bool used = false;
+        if ((rc = frange_batch2(ix, run, dQ, B, dMaxK, tot, pool_cap, cand_cap, s, &used, h_ctr))) return rc;
+        if (used) {
+            run->inf.path = 2;
+            if (h_ctr[1] > cand_cap) run->inf.redone++;
+            else { run->inf.candidates += h_ctr[1]; done = true; }
+        }
+        if (!done && too_long) return halves(false);
+    }
+    if (!done) {
+        if ((rc = frange_batch1(ix, run, dQ, B, dMaxK, tot, pool_cap, s))) return rc;
+        HIPCHK(hipMemcpyAsync(h_ctr, ix->rg_ctr.p, 16, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    run->inf.visits += tot.visits;
+    run->inf.leaf_rows += tot.rows;
+    run->inf.hits += h_ctr[0];
+    return range_emit(ix, B, h_ctr[0], pool_cap, rr, dOff, dIds, dKeys, host_out, s);
+}
+
+static int frange_args(zh_index *ix, const float *q, size_t b, const uint64_t *max_keys, uint32_t probe, int metric, int mode, uint64_t capacity,
+                       const void *offsets, const void *ids, const void *keys, const void *total, const char *who) {
+    int rc = range_args(ix, q, b, max_keys, metric, mode, capacity, offsets, ids, keys, total, who);
+    if (rc) return rc;
+    if (!probe) return fail(ZH_EINVAL, "%s: probe must be at least 1", who);
+    if (probe > ZH_MAX_TOPK) return fail(ZH_ELIMIT, "%s: probe %u > ZH_MAX_TOPK (%u)", who, probe, ZH_MAX_TOPK);
+    return ZH_OK;
+}
+
+// what the call starts from: no query, or an index without live rows, answers nothing (*empty; no trees needed), otherwise the forest graph's state checks
+static int frange_begin(zh_index *ix, size_t b, uint32_t probe, int metric, int mode, uint64_t capacity, FrangeRun *run, bool *empty, const char *who) {
+    run->metric = metric; run->mode = mode; run->probe = probe;
+    run->rr.capacity = capacity;
+    run->inf.path = 1;
+    run->inf.probe = probe;
+    run->inf.trees = ix->n_trees;
+    *empty = b == 0 || ix->ex_n_live == 0;
+    return *empty ? ZH_OK : fknn_state(ix, who);
+}
+
+static int frange_finish(zh_index *ix, size_t b, const FrangeRun &run, const char *who) {
+    {
+        zh_range_forest_info inf = run.inf;
+        inf.batch = b;
+        inf.rows_live = ix->ex_n_live;
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        ix->fr_info = inf;
+    }
+    if (run.rr.over)
+        return fail(ZH_ELIMIT, "%s: %llu hits exceed the capacity of %llu; out_total and the offsets are exact, call again with that capacity", who,
+                    (unsigned long long)run.rr.total, (unsigned long long)run.rr.capacity);
+    return ZH_OK;
+}
+
+extern "C" int zh_search_range_forest_batch_device(zh_index *ix, const float *d_q, size_t b, const uint64_t *d_max_keys, uint32_t probe, int metric, int mode,
+                                                   uint64_t capacity, uint64_t *d_out_offsets, uint64_t *d_out_ids, uint64_t *d_out_keys,
+                                                   uint64_t *d_out_total, void *stream) {
+    const char *who = "zh_search_range_forest_batch_device";
+    int rc = frange_args(ix, d_q, b, d_max_keys, probe, metric, mode, capacity, d_out_offsets, d_out_ids, d_out_keys, d_out_total, who);
+    if (rc) return rc;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    FrangeRun run;
+    bool empty = false;
+    if ((rc = frange_begin(ix, b, probe, metric, mode, capacity, &run, &empty, who))) return rc;
+    ScratchGuard guard{ix, SCRATCH_FRANGE};
+    const hipStream_t s = call_stream(ix, stream);
+    const uint32_t d = ix->opt.dim;
+    HIPCHK(hipMemsetAsync(d_out_offsets, 0, (empty ? b + 1 : 1) * 8, s));
+    if (!empty) {
+        if ((rc = frange_setup(ix, s, &run))) return rc;
+        for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
+            const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
+            if ((rc = frange_one(ix, &run, d_q + b0 * d, nb, d_max_keys + b0, d_out_offsets + b0, d_out_ids, d_out_keys, false, true, s))) return rc;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(d_out_total, &run.rr.total, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return frange_finish(ix, b, run, who);
+}
+
+extern "C" int zh_search_range_forest_batch(zh_index *ix, const float *q, size_t b, const uint64_t *max_keys, uint32_t probe, int metric, int mode,
+                                            uint64_t capacity, uint64_t *out_offsets, uint64_t *out_ids, uint64_t *out_keys, uint64_t *out_total) {
+    const char *who = "zh_search_range_forest_batch";
+    int rc = frange_args(ix, q, b, max_keys, probe, metric, mode, capacity, out_offsets, out_ids, out_keys, out_total, who);
+    if (rc) return rc;
+    out_offsets[0] = 0;
+    *out_total = 0;
+    if (b == 0) return ZH_OK;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    FrangeRun run;
+    bool empty = false;
+    if ((rc = frange_begin(ix, b, probe, metric, mode, capacity, &run, &empty, who))) return rc;
+    if (empty) {
+        memset(out_offsets, 0, (b + 1) * 8);
+        return frange_finish(ix, b, run, who);
+    }
+    ScratchGuard guard{ix, SCRATCH_FRANGE};
+    const hipStream_t s = ix->stream;
+    const uint32_t d = ix->opt.dim;
+    const size_t nb_max = std::min<size_t>(ZH_EXACT_BATCH, b);
+    if ((rc = ix->ex_Q.ensure(nb_max * d * 4)) || (rc = ix->rg_maxk.ensure(nb_max * 8)) || (rc = ix->rg_off.ensure((nb_max + 1) * 8))) return rc;
+    if ((rc = frange_setup(ix, s, &run))) return rc;
+    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
+        HIPCHK(hipMemcpyAsync(ix->ex_Q.p, q + b0 * d, (size_t)nb * d * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(ix->rg_maxk.p, max_keys + b0, (size_t)nb * 8, hipMemcpyHostToDevice, s));
+        if ((rc = frange_one(ix, &run, ix->ex_Q.as<float>(), nb, ix->rg_maxk.as<uint64_t>(), ix->rg_off.as<uint64_t>(), out_ids, out_keys, true, true, s)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(out_offsets + b0, ix->rg_off.p, ((size_t)nb + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    *out_total = run.rr.total;
+    return frange_finish(ix, b, run, who);
+}
+
+extern "C" int zh_search_range_forest_info(const zh_index *ix, zh_range_forest_info *out) {
+    return get_info(ix, &zh_index::fr_info, out, "zh_search_range_forest_info");
 }
 
 extern "C" int zh_hash_signs(zh_index *ix, const float *q, size_t b, uint32_t *out_bits, float *out_dots) {

@@ -492,6 +492,31 @@ hipError_t zh_launch_fjoin_survivors(const float *dX, uint32_t d, int metric, in
                                      uint64_t cand_cap, const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key, unsigned long long *dHitCtr,
                                      unsigned long long *dKeyed, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
 
+// ---- the forest range search (zh_frange.hip): every member of the leaves the walk visits for a query whose key is <= the query's threshold key,
+// each (query, row) once (the first tree that offers the row owns the pair).  Hit pool, counters and order as the exact range search's
+#define ZH_FRANGE_KEY_ROWS (uint64_t(1) << 25)  // visited rows (path-1 keys) of one internal batch at most, unless it is one query
+// path 2: one visited leaf of a batch of leaves: its rt row tiles start at tile col0 of the batch's gathered tiles; its visitors are the members of
+// groups group0 .., visitor j = member j % G of group group0 + j / G; first_block = the launch's blocks before this leaf's
+struct ZhFrangeSeg {
+    uint32_t col0, rt, group0, visitors;
+    uint32_t tree, first_block, pad0, pad1;
+};
+// the lookup of visited leaves: (b T + t) << 32 | leaf offset of every visit, sorted -- pair p's slice stays at [visitBase[p], visitBase[p + 1]).
+// dKeys: two buffers of n_visits words; dTmp == nullptr: only *tmp_bytes is set; *dSorted = the buffer that holds the result
+hipError_t zh_launch_frange_visit_index(const ZhVisit *dVisits, uint64_t n_visits, const uint32_t *dNodeTree, uint32_t T, uint64_t n_pairs, uint64_t *dKeys[2],
+                                        void *dTmp, size_t *tmp_bytes, const uint64_t **dSorted, hipStream_t s);
+// path 1: the swept keys (at the visits' row_off) <= the visit's query's threshold that pass the ownership rule, counted and pooled
+hipError_t zh_launch_frange_collect(const ZhVisit *dVisits, uint64_t n_visits, const uint64_t *dKeys, const uint32_t *dLeafIds, uint64_t n_rows,
+                                    const uint32_t *dNodeTree, const uint64_t *dVSorted, const uint64_t *dVisitBase, const uint32_t *dLeafOf, uint32_t T,
+                                    const uint64_t *dMaxKeys, uint32_t *dCnt, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap,
+                                    hipStream_t s);
+// path 2: every leaf of a batch in one launch of n_blocks blocks, column chunks of ch tiles, against dTau (zh_launch_range_tau); pairs with
+// lo <= tau that pass the rule to dCand as query << 32 | row; *dCandCtr counts them all
+hipError_t zh_launch_frange_mfma(uint32_t d, int metric, int mode, const ZhFrangeSeg *dSegs, uint32_t n_segs, uint32_t n_blocks, uint32_t ch, uint32_t group,
+                                 const void *dCA, const float2 *dCMeta, const uint32_t *dCRow, const ZhGroup *dGroups, const void *dQh, const float4 *dQmeta,
+                                 float Kc, float rho, const uint32_t *dTau, const uint64_t *dVSorted, const uint64_t *dVisitBase, const uint32_t *dLeafOf,
+                                 uint32_t T, uint64_t *dCand, uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s);
+
 // ---- launchers (zh_score.hip): every sign of a forest built from stored rows, from N row scores per query --------
 // Prefilter (zh_search.hip, "Prefilter"): a batch hashed from row scores picks the rows that can be among a pair's k best from
 // those scores; only they are scored with the reference's arithmetic.  Lists: one per (tree, query), `cap` slots, list (t, b) at

@@ -472,6 +472,61 @@ class LSHIndex:
         check(lib().zh_search_range_info(self._h, C.byref(info)))
         return info.as_dict()
 
+    def search_range_forest_batch(self, queries, radius=None, metric=None, max_keys=None, probe=1, capacity=None):
+        """FOREST range search: search_range_batch among the members of the leaves the walk visits for each query with n = `probe` (what
+        search_batch(top_k = probe) walks; 1 = the leaf the query hashes to in each tree).  Exact keys, approximate candidates: the answer is
+        the subset of search_range_batch's hits that are members of a visited leaf, each once.  Arguments and result as search_range_batch."""
+        q = _f32(queries, self.dim)
+        b = q.shape[0]
+        mk = self._range_keys(b, radius, metric, max_keys)
+        cap = int(capacity) if capacity is not None else max(1024, 64 * b)
+        offsets = np.zeros(b + 1, np.uint64)
+        total = C.c_uint64(0)
+        for attempt in range(2):
+            ids = np.empty(max(cap, 1), np.uint64)
+            keys = np.empty(max(cap, 1), np.uint64)
+            rc = lib().zh_search_range_forest_batch(self._h, _p(q), b, _p(mk), int(probe), metric.metric, metric.mode, cap, _p(offsets), _p(ids), _p(keys),
+                                                    C.byref(total))
+            if rc == _ffi.ZH_ELIMIT and attempt == 0 and total.value > cap:
+                cap = int(total.value)
+                continue
+            check(rc)
+            break
+        n = int(total.value)
+        return offsets, ids[:n], keys[:n]
+
+    def search_range_forest(self, query, radius=None, metric=None, max_keys=None, probe=1):
+        """the forest hits of one query -> list of (id, distance key), ascending"""
+        _, ids, keys = self.search_range_forest_batch(_f32(query).reshape(1, -1), radius, metric, max_keys, probe)
+        return list(zip(ids.tolist(), keys.tolist()))
+
+    def range_forest_count_batch(self, queries, radius=None, metric=None, max_keys=None, probe=1):
+        """how many hits search_range_forest_batch would return for every query (a call with capacity 0: nothing is ordered or written) -> [b] u64"""
+        q = _f32(queries, self.dim)
+        b = q.shape[0]
+        mk = self._range_keys(b, radius, metric, max_keys)
+        offsets = np.zeros(b + 1, np.uint64)
+        total = C.c_uint64(0)
+        rc = lib().zh_search_range_forest_batch(self._h, _p(q), b, _p(mk), int(probe), metric.metric, metric.mode, 0, _p(offsets), None, None, C.byref(total))
+        if rc != _ffi.ZH_ELIMIT:
+            check(rc)
+        return np.diff(offsets)
+
+    def search_range_forest_batch_device(self, d_q_ptr, b, d_max_keys_ptr, probe, metric, capacity, d_offsets_ptr, d_ids_ptr, d_keys_ptr, d_total_ptr,
+                                         stream=None):
+        """search_range_forest_batch with queries, threshold keys, offsets (b + 1), ids / keys (`capacity` each) and the total (one u64) in
+        device memory (raw pointers, e.g. torch .data_ptr()).  Hits beyond the capacity raise ZhError with code ZH_ELIMIT; the offsets and the
+        total are exact even then."""
+        check(lib().zh_search_range_forest_batch_device(self._h, d_q_ptr, b, d_max_keys_ptr, int(probe), metric.metric, metric.mode, capacity, d_offsets_ptr,
+                                                        d_ids_ptr, d_keys_ptr, d_total_ptr, stream))
+
+    def range_forest_info(self):
+        """what the most recent forest range search on this index did (zh_search_range_forest_info): batch, rows_live, trees, probe, path,
+        redone, visits, leaf_rows, hits, candidates, launches, tiles"""
+        info = _ffi.RangeForestInfo()
+        check(lib().zh_search_range_forest_info(self._h, C.byref(info)))
+        return info.as_dict()
+
     def _join_key(self, radius, metric, max_key):
         if metric is None:
             raise ValueError("the self-join needs a metric")
@@ -920,6 +975,14 @@ class Database:
         if self.index.no_vectors():
             return {}
         offsets, ids, _ = self.index.search_range_batch(vectors, radius, self.metric)
+        return {b: {int(i): self._documents.get(int(i)) for i in ids[int(offsets[b]):int(offsets[b + 1])]} for b in range(offsets.size - 1)}
+
+    def query_vectors_within_forest(self, vectors, radius, probe=1):
+        """query_vectors_within among the records in the leaves the forest's walk visits for each query (LSHIndex.search_range_forest_batch:
+        exact keys, approximate candidates) -> what query_vectors_within returns, for the records the forest finds"""
+        if self.index.no_vectors():
+            return {}
+        offsets, ids, _ = self.index.search_range_forest_batch(vectors, radius, self.metric, probe=probe)
         return {b: {int(i): self._documents.get(int(i)) for i in ids[int(offsets[b]):int(offsets[b + 1])]} for b in range(offsets.size - 1)}
 
     def near_duplicates(self, radius):

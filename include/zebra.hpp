@@ -322,6 +322,26 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_self_join_info(h_.get(), &info));
         return info;
     }
+    // the join between two indexes (zh_cross_join): every pair (live row a of this index, live row b of `other`) whose key (stored row b of
+    // `other` against a query equal to row a) is <= max_key, ascending by (a, key, b); a carries this index's id_base, b other's.  One call that
+    // counts, one that fetches.  `other` must be a different index of the same dim on the same device.
+    template <class Met>
+    std::vector<JoinedPair> cross_join(const LSHIndex &other, DistanceUnit max_key, const Met &metric) const {
+        std::uint64_t total = 0;
+        const int rc = zh_cross_join(h_.get(), other.h_.get(), max_key, Met::metric, metric.mode(), 0, nullptr, nullptr, nullptr, &total);
+        if (rc != ZH_ELIMIT) check(rc);
+        std::vector<Id> a(total + 1), b(total + 1);
+        std::vector<DistanceUnit> keys(total + 1);
+        if (total) check(zh_cross_join(h_.get(), other.h_.get(), max_key, Met::metric, metric.mode(), total, a.data(), b.data(), keys.data(), &total));
+        std::vector<JoinedPair> out(total);
+        for (std::uint64_t i = 0; i < total; i++) out[i] = JoinedPair{a[i], b[i], keys[i]};
+        return out;
+    }
+    zh_cross_info cross_info() const {
+        zh_cross_info info{};
+        check(zh_cross_join_info(h_.get(), &info));
+        return info;
+    }
     // the exact k-NN graph of the slab of stored rows [first_row, first_row + n) (zh_knn_graph): element i = the k nearest OTHER live rows of stored
     // row first_row + i by (key, id), the key that of the neighbour against a query equal to the row; empty for a removed row.  k <= ZH_MAX_TOPK - 1.
     template <class Met>

@@ -28,6 +28,7 @@
  *   zh_search_exact_filtered_batch[_device] (new) the exact top-k among the live rows a caller's bitmap allows
  *   zh_search_range_batch[_device]       (new) every live row whose key is at or below a per-query threshold key, as a CSR
  *   zh_self_join[_device]                (new) every pair of live rows whose key is at or below one threshold key, each pair once
+ *   zh_cross_join[_device]               (new) every pair (live row of one index, live row of another) whose key is at or below one threshold key
  *   zh_knn_graph[_device]                (new) every live row's exact k nearest OTHER live rows, slab by slab
  *   zh_knn_graph_forest[_device]         (new) every row's k nearest rows among its leaf-mates in the forest: exact keys, approximate candidates
  *   zh_self_join_forest[_device]         (new) every pair of leaf-mates whose key is at or below one threshold key, each pair once: exact keys,
@@ -496,6 +497,52 @@ typedef struct zh_join_info {  /* the most recent zh_self_join* call on this ind
     uint64_t tiles;       /* path 2: 16 x 16 tile products issued, from the launch geometry (T (T + 1) / 2 for T tiles: nothing below the diagonal) */
 } zh_join_info;
 ZH_API int zh_self_join_info(const zh_index *idx, zh_join_info *out);
+
+/* Exact JOIN BETWEEN TWO INDEXES (new; the reference has no such call): every pair (live stored row a of index `a`, live stored row b of index
+ * `b`) whose key is <= max_key.  It replaces the loop "zh_index_read_rows of A back to the host, zh_search_range_batch on B 1024 rows at a time":
+ * drop from an incoming batch what the corpus already holds, record linkage between two collections, the pairs between two snapshots.
+ * The key of a pair is the key zh_distance_batch gives for STORED row b of B against a QUERY equal to the f32 values of row a of A: the pairs of
+ * row a are exactly the hits of zh_search_range_batch(B, rows_A[a], max_keys = {max_key}).  That orientation is the definition; nothing relies on
+ * the key being the same with the roles swapped, and zh_cross_join(b, a) is a different call with its own keys and order.  ONE threshold key for
+ * the whole call, a key as for the range search and the self-join; UINT64_MAX returns all live(A) x live(B) pairs.
+ * The result is three parallel arrays out_a, out_b, out_keys of *out_total entries, ascending by (a, key, b); out_a = A's id_base + row,
+ * out_b = B's id_base + row (the two bases may differ).  If the pairs exceed `capacity` the call returns ZH_ELIMIT with *out_total exact --
+ * allocate that many and call again -- and the arrays unspecified.  capacity = 0 with NULL arrays is the supported way to count only.  Either side
+ * empty or without a live row gives *out_total = 0 and ZH_OK; no forest is needed on either side.
+ * Refused with ZH_EINVAL before any device is touched: a NULL index on either side, a == b (use zh_self_join), a NULL out_total, NULL arrays with
+ * capacity > 0, an unknown metric.  Refused with ZH_EINVAL after that: different dim, indexes on different devices.  All 13 metric / mode / power
+ * combinations and every dimension are served.
+ * Locking: the call holds BOTH indexes' internal locks exclusively, taken together without a lock order of the caller's (cross_join(A, B) on one
+ * thread and cross_join(B, A) on another do not deadlock); never concurrent with add / build / remove / clear of either index.  All per-call
+ * scratch and zh_cross_info live on the LEFT index `a`; B lends its rows, its fp16 row copy and its cached live-row views.  zh_stats_t, every
+ * sibling info struct of both indexes and search contexts are left alone.
+ * Two paths, same answers.  Path 1 gathers panels of up to 1024 live rows of A as queries, keys B's live rows against them with the canonical sums
+ * and collects the keys at or below the threshold.  Path 2 (ZH_L2SQ, ZH_L2, ZH_COSINE at dim 256 / 384 / 512 / 768 / 1024, the fp16 row copy
+ * present on BOTH sides, live(A) x live(B) >= 2^25) multiplies tiles of A's fp16 copy by tiles of B's on the matrix cores for an interval per
+ * pair; the pairs whose interval reaches down to the threshold are candidates and only they get the canonical key.  A is scanned in panels of
+ * 16384 positions; a panel whose candidates outgrow their pool is answered by path 1 against all of B (`redone`) -- under any scan order of
+ * either side, since a panel owns its pairs by A row.  ZH_XJOIN_PATH in the environment (read per call): 1 keeps every panel on path 1, 2 takes
+ * path 2 at any size where it is supported.
+ * Device scratch is allocated per call on A's device and released before it returns.  With P = min(capacity, live(A) x live(B)) hit slots: 32 P
+ * bytes of hit pool and sort buffers + the sort's temporary storage; on path 2 20 bytes per stored row of either side and 8 bytes per candidate
+ * slot of one panel (max(1.25 x the capacity left, 256 per row of the panel) of them, never more than the panel's rows x B's stored rows); on
+ * path 1 the panel's rows and up to 1 GiB of key scratch; for the host call 24 bytes per pair as staging. */
+ZH_API int zh_cross_join(zh_index *a, zh_index *b, uint64_t max_key, int metric, int cosine_mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b,
+                         uint64_t *out_keys, uint64_t *out_total);
+/* The same with every output (out_total included) in device memory; enqueued on `stream` (NULL = A's own stream), complete on return. */
+ZH_API int zh_cross_join_device(zh_index *a, zh_index *b, uint64_t max_key, int metric, int cosine_mode, uint64_t capacity, uint64_t *d_out_a,
+                                uint64_t *d_out_b, uint64_t *d_out_keys, uint64_t *d_out_total, void *stream);
+typedef struct zh_cross_info {  /* the most recent zh_cross_join* call with this index on the LEFT */
+    uint64_t rows_live_a; /* live rows of the left index */
+    uint64_t rows_live_b; /* live rows of the right index */
+    uint64_t pairs;       /* pairs within the threshold (exact whatever the capacity) */
+    uint32_t path;        /* 1: canonical sums for every pair; 2: matrix-core intervals, canonical keys for the candidates only */
+    uint32_t redone;      /* path-2 panels of A whose candidate pool ran over and were answered by path 1 instead */
+    uint64_t candidates;  /* path 2: pairs that got the canonical key, over all panels path 2 completed */
+    uint64_t launches;    /* launches of the scan (row chunks of B on path 1, one per panel of A on path 2) */
+    uint64_t tiles;       /* path 2: 16 x 16 tile products issued, from the launch geometry (T_A x T_B: the full rectangle) */
+} zh_cross_info;
+ZH_API int zh_cross_join_info(const zh_index *a, zh_cross_info *out);
 
 /* Exact k-NN GRAPH (new; the reference has no such call): for every live stored row a of the slab [first_row, first_row + n) its exact top-k by
  * (key, id) over every live row EXCEPT a itself.  It replaces the loop "zh_index_read_rows back to the host, zh_search_exact_batch with k + 1,

@@ -134,6 +134,19 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_cross_info {
+        pub rows_live_a: u64,
+        pub rows_live_b: u64,
+        pub pairs: u64,
+        pub path: u32,
+        pub redone: u32,
+        pub candidates: u64,
+        pub launches: u64,
+        pub tiles: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_knn_info {
         pub rows_live: u64,
         pub lines: u64,
@@ -297,6 +310,11 @@ pub mod ffi {
         pub fn zh_self_join_device(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, d_out_a: *mut u64,
                                    d_out_b: *mut u64, d_out_keys: *mut u64, d_out_total: *mut u64, stream: *mut c_void) -> c_int;
         pub fn zh_self_join_info(idx: *const zh_index, out: *mut zh_join_info) -> c_int;
+        pub fn zh_cross_join(a: *mut zh_index, b: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, out_a: *mut u64,
+                             out_b: *mut u64, out_keys: *mut u64, out_total: *mut u64) -> c_int;
+        pub fn zh_cross_join_device(a: *mut zh_index, b: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64,
+                                    d_out_a: *mut u64, d_out_b: *mut u64, d_out_keys: *mut u64, d_out_total: *mut u64, stream: *mut c_void) -> c_int;
+        pub fn zh_cross_join_info(a: *const zh_index, out: *mut zh_cross_info) -> c_int;
         pub fn zh_knn_graph(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int, out_ids: *mut u64,
                             out_keys: *mut u64, out_counts: *mut u32) -> c_int;
         pub fn zh_knn_graph_device(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64,
@@ -714,6 +732,43 @@ impl<const N: usize> LSHIndex<N> {
             })?;
         }
         Ok((0..total as usize).map(|i| (t.of_row[a[i] as usize], t.of_row[b[i] as usize], keys[i])).collect())
+    }
+
+    /// (new) the join between two indexes (zh_cross_join): every pair (live vector a of self, live vector b of `other`) whose key -- that of
+    /// stored b against a query equal to a -- is <= `max_key`, ascending by (a, key, b): one call that counts (capacity 0), one that fetches.
+    /// u64::MAX = every pair of the rectangle.  The library takes both indexes' locks together; `self` and `other` must be different indexes.
+    pub fn cross_join<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        other: &Self,
+        max_key: DistanceUnit,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<(Uuid, Uuid, DistanceUnit)>> {
+        let ta = self.ids.read().unwrap();
+        let tb = other.ids.read().unwrap();
+        let mut total = 0u64;
+        let rc = unsafe {
+            ffi::zh_cross_join(self.hip.0, other.hip.0, max_key, Met::METRIC, metric.param(), 0, std::ptr::null_mut(), std::ptr::null_mut(),
+                               std::ptr::null_mut(), &mut total)
+        };
+        if rc != -5 {
+            check(rc)?;
+        }
+        let n = total as usize + 1;
+        let (mut a, mut b, mut keys) = (vec![0u64; n], vec![0u64; n], vec![0u64; n]);
+        if total > 0 {
+            check(unsafe {
+                ffi::zh_cross_join(self.hip.0, other.hip.0, max_key, Met::METRIC, metric.param(), total, a.as_mut_ptr(), b.as_mut_ptr(),
+                                   keys.as_mut_ptr(), &mut total)
+            })?;
+        }
+        Ok((0..total as usize).map(|i| (ta.of_row[a[i] as usize], tb.of_row[b[i] as usize], keys[i])).collect())
+    }
+
+    /// what the most recent cross_join with this index on the left did (zh_cross_join_info)
+    pub fn cross_info(&self) -> anyhow::Result<ffi::zh_cross_info> {
+        let mut info = ffi::zh_cross_info::default();
+        check(unsafe { ffi::zh_cross_join_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// (new) the exact k-NN graph (zh_knn_graph): per stored vector, in row order, its `k` nearest OTHER live vectors by (key, row), the key that

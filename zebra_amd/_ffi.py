@@ -112,6 +112,14 @@ class JoinInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CrossInfo(C.Structure):
+    _fields_ = [("rows_live_a", C.c_uint64), ("rows_live_b", C.c_uint64), ("pairs", C.c_uint64), ("path", C.c_uint32), ("redone", C.c_uint32),
+                ("candidates", C.c_uint64), ("launches", C.c_uint64), ("tiles", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class KnnInfo(C.Structure):
     _fields_ = [("rows_live", C.c_uint64), ("lines", C.c_uint64), ("k", C.c_uint32), ("path", C.c_uint32), ("redone", C.c_uint32),
                 ("survivors", C.c_uint64), ("launches", C.c_uint64), ("tiles", C.c_uint64)]
@@ -214,6 +222,9 @@ SYMBOLS = [
     ("zh_self_join", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
     ("zh_self_join_device", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("zh_self_join_info", _i, [_vp, _vp]),
+    ("zh_cross_join", _i, [_vp, _vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
+    ("zh_cross_join_device", _i, [_vp, _vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
+    ("zh_cross_join_info", _i, [_vp, _vp]),
     ("zh_knn_graph", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_knn_graph_device", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_knn_graph_info", _i, [_vp, _vp]),

@@ -272,6 +272,12 @@ struct zh_index {
     // and the outputs staged for the host call
     DevBuf jn_ctr, jn_maxk, jn_tau, jn_pv0, jn_pv1, jn_pk0, jn_pk1, jn_qm, jn_cid, jn_first, jn_cand, jn_rows, jn_tmp, jn_oa, jn_ob, jn_okeys;
     zh_join_info jn_info{};  // (stats_mu)
+    // the cross-join's per-call scratch, all on the LEFT index (all released before the call returns): {hit, candidate, panel-row} counters, the
+    // threshold's bound, the hit pool and its sort partner, path 2's per-position views of A (id word; the query view zh_launch_join_prep writes beside
+    // it is not read) and of B (query view, id word), the candidate pool, a redone panel's row list, the sort's temporary storage and the outputs
+    // staged for the host call
+    DevBuf xj_ctr, xj_maxk, xj_tau, xj_pv0, xj_pv1, xj_pk0, xj_pk1, xj_qma, xj_cida, xj_qmb, xj_cidb, xj_cand, xj_rows, xj_tmp, xj_oa, xj_ob, xj_okeys;
+    zh_cross_info xj_info{};  // (stats_mu)
     // the k-NN graph's per-call scratch (all released before the call returns): path 2's per-position views and row -> position map, one panel's
     // tiles, rowMeta and row numbers, the lists' bases, the panel's answer, and the outputs staged for the host call
     DevBuf kn_qm, kn_cid, kn_pos, kn_A, kn_pmeta, kn_pid, kn_cbase, kn_pids, kn_pkeys, kn_pcounts, kn_oids, kn_okeys, kn_ocounts;
@@ -3462,8 +3468,8 @@ static int score_param(int metric, int mode) { return (metric == ZH_COSINE || me
 // The per-call scratch, each family's buffers listed once.  The guard of a call gives its set back to the driver however the call returns: an idle
 // index holds only the live-row views (ex_live and ex_bits survive every call; zh_index_destroy frees them).  Every family scans with the exact
 // search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's, the forest range search with
-// the range search's and the forest join's.
-enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128 };  // one bit per list
+// the range search's and the forest join's, the cross-join (all on its LEFT index) with its own.
+enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256 };  // one bit per list
 enum : unsigned {
     SCRATCH_EXACT = SCR_EX,
     SCRATCH_FILTER = SCR_FL | SCRATCH_EXACT,
@@ -3473,6 +3479,7 @@ enum : unsigned {
     SCRATCH_FKNN = SCR_FK | SCRATCH_KNN,
     SCRATCH_FJOIN = SCR_FJ | SCRATCH_JOIN | SCRATCH_FKNN,
     SCRATCH_FRANGE = SCR_FR | SCRATCH_RANGE | SCRATCH_FJOIN,
+    SCRATCH_XJOIN = SCR_XJ | SCRATCH_EXACT,  // (on the left index)
 };
 static void release_scratch(zh_index *ix, unsigned families) {
     auto drop = [&](unsigned list, std::initializer_list<DevBuf *> bs) {
@@ -3487,6 +3494,8 @@ static void release_scratch(zh_index *ix, unsigned families) {
                   &ix->rg_oids, &ix->rg_okeys});
     drop(SCR_JN, {&ix->jn_ctr, &ix->jn_maxk, &ix->jn_tau, &ix->jn_pv0, &ix->jn_pv1, &ix->jn_pk0, &ix->jn_pk1, &ix->jn_qm, &ix->jn_cid, &ix->jn_first,
                   &ix->jn_cand, &ix->jn_rows, &ix->jn_tmp, &ix->jn_oa, &ix->jn_ob, &ix->jn_okeys});
+    drop(SCR_XJ, {&ix->xj_ctr, &ix->xj_maxk, &ix->xj_tau, &ix->xj_pv0, &ix->xj_pv1, &ix->xj_pk0, &ix->xj_pk1, &ix->xj_qma, &ix->xj_cida, &ix->xj_qmb,
+                  &ix->xj_cidb, &ix->xj_cand, &ix->xj_rows, &ix->xj_tmp, &ix->xj_oa, &ix->xj_ob, &ix->xj_okeys});
     drop(SCR_KN, {&ix->kn_qm, &ix->kn_cid, &ix->kn_pos, &ix->kn_A, &ix->kn_pmeta, &ix->kn_pid, &ix->kn_cbase, &ix->kn_pids, &ix->kn_pkeys, &ix->kn_pcounts,
                   &ix->kn_oids, &ix->kn_okeys, &ix->kn_ocounts});
     drop(SCR_FK, {&ix->fk_ntree, &ix->fk_rl, &ix->fk_flag, &ix->fk_excl, &ix->fk_tmp, &ix->fk_rows, &ix->fk_ctr, &ix->fk_lens, &ix->fk_takes, &ix->fk_rbase,
@@ -4417,6 +4426,242 @@ extern "C" int zh_self_join(zh_index *ix, uint64_t max_key, int metric, int mode
 }
 
 extern "C" int zh_self_join_info(const zh_index *ix, zh_join_info *out) { return get_info(ix, &zh_index::jn_info, out, "zh_self_join_info"); }
+
+// ------------------------------------------------------------------------------------------------
+// exact join between two indexes (zh_xjoin.hip + the exact search's score kernel): every pair (live row a of A, live row b of B) with
+// key(stored b of B, query a of A) <= one threshold key, as three arrays ascending by (a, key, b).  All scratch and the info on A.  DESIGN.md s20
+// ------------------------------------------------------------------------------------------------
+#define ZH_XJOIN_GATE_PAIRS (uint64_t(1) << 25)  // live(A) x live(B) from which path 2 is taken: the pair work at which the self-join switches (8192^2 / 2)
+
+// Path 1 for the B <= ZH_EXACT_BATCH query rows dQRows (row numbers of A, device): gathered out of A's table into A's query buffer,
+// exact_score_kernel's keys of ALL live rows of ib against them, xjoin_collect_kernel over them.  Hits are counted in xj_ctr[0] and pooled while
+// the pool has room.
+static int xjoin_batch1(zh_index *ia, zh_index *ib, const uint32_t *dQRows, uint32_t B, uint64_t max_key, int metric, int mode, uint64_t pool_cap,
+                        hipStream_t s, uint64_t *launches) {
+    const uint32_t d = ia->opt.dim;
+    const uint64_t n_live = ib->ex_n_live;
+    if (!B || !n_live) return ZH_OK;
+    const uint64_t rc_rows = std::min<uint64_t>(std::max<uint64_t>(256, ZH_EXACT_KEY_BYTES / 8 / B), n_live);
+    int rc;
+    if ((rc = ia->ex_Q.ensure((size_t)B * d * 4)) || (rc = ia->ex_QQ.ensure((size_t)B * 4)) || (rc = ia->ex_keys.ensure((size_t)B * rc_rows * 8))) return rc;
+    const int param = score_param(metric, mode);
+    HIPCHK(zh_launch_join_gather(ia->X.as<float>(), d, dQRows, B, ia->ex_Q.as<float>(), s));
+    HIPCHK(zh_launch_qnorm(ia->ex_Q.as<float>(), B, d, ia->ex_QQ.as<float>(), s));
+    for (uint64_t p0 = 0; p0 < n_live; p0 += rc_rows) {
+        const uint32_t nr = (uint32_t)std::min<uint64_t>(rc_rows, n_live - p0);
+        HIPCHK(zh_launch_exact_score(ib->X.as<float>(), d, ib->ex_live.as<uint32_t>(), p0, nr, ia->ex_Q.as<float>(), ia->ex_QQ.as<float>(), B, metric, param,
+                                     ia->ex_keys.as<uint64_t>(), rc_rows, s));
+        HIPCHK(zh_launch_xjoin_collect(ia->ex_keys.as<uint64_t>(), rc_rows, ib->ex_live.as<uint32_t>(), p0, nr, dQRows, B, max_key,
+                                       ia->xj_ctr.as<unsigned long long>(), ia->xj_pv0.as<uint64_t>(), ia->xj_pk0.as<uint64_t>(), pool_cap, s));
+        (*launches)++;
+    }
+    return ZH_OK;
+}
+
+// Path 2 of the whole call: the threshold as a fixed bound, either side's positions through zh_launch_join_prep (A's id word; B's id word and its
+// rows as approx_interval's queries, with B's rho), then panel after panel of ZH_JOIN_PANEL_ROWS positions of A's copy: one matrix-core launch of
+// the panel against all of B's copy, canonical keys and the judgement for its candidates.  A panel whose candidates outgrow the pool (nothing of
+// it was counted) is answered by path 1 from the list of its live rows, against all of B.  That redo is valid under a row order of either side
+// too, unlike the self-join's: a panel owns the pairs (a, b) of the A rows at its positions, whatever those rows' numbers and wherever b sits in
+// B's copy, and path 1 for exactly those A rows against every live b is the same set -- no pair of the rectangle belongs to two panels, none to a
+// panel by anything but its A row, so no whole-call rewind is needed.  *used = false: path 2 does not serve this pair of indexes and path 1
+// answers everything.  *hits = xj_ctr[0] on return with *used.
+static int xjoin_path2(zh_index *ia, zh_index *ib, bool forced, uint64_t max_key, int metric, int mode, uint64_t pool_cap, hipStream_t s, zh_cross_info *inf,
+                       bool *used, uint64_t *hits) {
+    *used = false;
+    const uint32_t d = ia->opt.dim;
+    if (!zh_exact_mfma_supported(d, metric)) return ZH_OK;
+    if (!forced && ia->ex_n_live * ib->ex_n_live < ZH_XJOIN_GATE_PAIRS) return ZH_OK;  // (both counts are below 2^32)
+    int rc;
+    HalfView va, vb;
+    bool have_a = false, have_b = false;
+    {
+        std::lock_guard<std::mutex> lb(ia->blk_mu);
+        if ((rc = half_view(ia, &va, &have_a))) return rc;
+    }
+    if (!have_a) return ZH_OK;
+    {
+        std::lock_guard<std::mutex> lb(ib->blk_mu);
+        if ((rc = half_view(ib, &vb, &have_b))) return rc;  // (a copy made now is complete on return: ensure_row_half waits for ib's stream)
+    }
+    if (!have_b) return ZH_OK;
+    const uint64_t na = ia->n_rows, nb = ib->n_rows, TA = (na + 15) / 16, TB = (nb + 15) / 16;
+    if ((rc = ia->xj_qma.ensure(TA * 16 * 16)) || (rc = ia->xj_cida.ensure(TA * 16 * 4)) || (rc = ia->xj_qmb.ensure(TB * 16 * 16)) ||
+        (rc = ia->xj_cidb.ensure(TB * 16 * 4)) || (rc = ia->xj_tau.ensure(4)) || (rc = ia->xj_maxk.ensure(8)))
+        return rc;
+    unsigned long long *ctr = ia->xj_ctr.as<unsigned long long>();  // {hits, the panel's candidates, a redone panel's rows}
+    HIPCHK(hipMemcpyAsync(ia->xj_maxk.p, &max_key, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(zh_launch_range_tau(ia->xj_maxk.as<uint64_t>(), 1, metric, mode, ia->xj_tau.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_prep(va.rowMeta, va.perm, va.perm_rows, ia->ex_bits.as<uint32_t>(), na, va.rho, ia->xj_qma.as<float4>(), ia->xj_cida.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_prep(vb.rowMeta, vb.perm, vb.perm_rows, ib->ex_bits.as<uint32_t>(), nb, vb.rho, ia->xj_qmb.as<float4>(), ia->xj_cidb.as<uint32_t>(), s));
+    HIPCHK(hipStreamSynchronize(s));  // (max_key is the caller's stack)
+    *used = true;
+    inf->path = 2;
+    const float Kc = zh_approx_bound(metric, d, 1);
+    for (uint64_t P0 = 0; P0 < na; P0 += ZH_JOIN_PANEL_ROWS) {
+        const uint64_t P1 = std::min<uint64_t>(na, P0 + ZH_JOIN_PANEL_ROWS), tileA0 = P0 / 16, tileA1 = (P1 + 15) / 16;
+        uint32_t n_ab = 0, blocks = 0;
+        const uint64_t products = zh_xjoin_geometry(TA, TB, tileA0, tileA1, &n_ab, &blocks);
+        const uint64_t panel_rows = P1 - P0, pairs_bound = panel_rows * nb, pool_left = pool_cap > *hits ? pool_cap - *hits : 0;
+        const uint64_t cand_cap = std::min<uint64_t>(pairs_bound, std::max<uint64_t>(pool_left + pool_left / 4, (uint64_t)ZH_JOIN_CAND_FLOOR * panel_rows));
+        if ((rc = ia->xj_cand.ensure(cand_cap * 8))) return rc;
+        HIPCHK(hipMemsetAsync(ctr + 1, 0, 16, s));
+        HIPCHK(zh_launch_xjoin_mfma(d, metric, mode, va.Xh, va.rowMeta, ia->xj_cida.as<uint32_t>(), na, vb.Xh, ia->xj_qmb.as<float4>(), ia->xj_cidb.as<uint32_t>(),
+                                    nb, tileA0, tileA1, Kc, va.rho, ia->xj_tau.as<uint32_t>(), ia->xj_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
+        inf->launches++;
+        inf->tiles += products;
+        HIPCHK(zh_launch_xjoin_survivors(ia->X.as<float>(), ib->X.as<float>(), d, metric, mode, ia->xj_cand.as<uint64_t>(), ctr + 1, cand_cap, max_key, ctr,
+                                         ia->xj_pv0.as<uint64_t>(), ia->xj_pk0.as<uint64_t>(), pool_cap, s));
+        unsigned long long h_ctr[3] = {0, 0, 0};
+        HIPCHK(hipMemcpyAsync(h_ctr, ctr, 24, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (h_ctr[1] <= cand_cap) {
+            inf->candidates += h_ctr[1];
+            *hits = h_ctr[0];
+            continue;
+        }
+        inf->redone++;
+        if ((rc = ia->xj_rows.ensure(panel_rows * 4))) return rc;
+        HIPCHK(zh_launch_join_panel_rows(ia->xj_cida.as<uint32_t>(), P0, P1, ia->xj_rows.as<uint32_t>(), ctr + 2, s));
+        HIPCHK(hipMemcpyAsync(h_ctr, ctr, 24, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (uint64_t b0 = 0; b0 < h_ctr[2]; b0 += ZH_EXACT_BATCH) {
+            const uint32_t nq = (uint32_t)std::min<uint64_t>(ZH_EXACT_BATCH, h_ctr[2] - b0);
+            if ((rc = xjoin_batch1(ia, ib, ia->xj_rows.as<uint32_t>() + b0, nq, max_key, metric, mode, pool_cap, s, &inf->launches))) return rc;
+        }
+        HIPCHK(hipMemcpyAsync(h_ctr, ctr, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        *hits = h_ctr[0];
+    }
+    return ZH_OK;
+}
+
+// judged before any device is touched (and before either handle is followed)
+static int xjoin_args(const zh_index *ia, const zh_index *ib, int metric, int mode, uint64_t capacity, const void *a, const void *b, const void *keys,
+                      const void *total, const char *who) {
+    if (!ia || !ib) return fail(ZH_EINVAL, "%s: null argument", who);
+    if (ia == ib) return fail(ZH_EINVAL, "%s: the two indexes are the same one; zh_self_join joins an index with itself", who);
+    if (!total || (capacity && (!a || !b || !keys))) return fail(ZH_EINVAL, "%s: null argument", who);
+    return check_metric(metric, mode);
+}
+
+// Both indexes' mu, exclusively (exact_live_rows and half_view re-make caches on either side), taken with std::lock: its try-and-back-off takes the
+// two in no fixed order and holds neither while it waits for the other, so zh_cross_join(A, B) and zh_cross_join(B, A) on two threads cannot
+// deadlock.  Then what can only be judged under the locks.
+struct XjoinLocks {
+    std::unique_lock<std::shared_mutex> la, lb;
+    XjoinLocks(zh_index *ia, zh_index *ib) : la(ia->mu, std::defer_lock), lb(ib->mu, std::defer_lock) { std::lock(la, lb); }
+};
+static int xjoin_state(zh_index *ia, zh_index *ib, const char *who) {
+    if (ia->opt.dim != ib->opt.dim) return fail(ZH_EINVAL, "%s: the indexes have different dim (%u and %u)", who, ia->opt.dim, ib->opt.dim);
+    if (ia->device != ib->device) return fail(ZH_EINVAL, "%s: the indexes live on different devices (%d and %d)", who, ia->device, ib->device);
+    int rc;
+    if ((rc = set_device(ia)) || (rc = exact_live_rows(ia)) || (rc = exact_live_rows(ib))) return rc;
+    return ZH_OK;
+}
+
+// What join_finish does, with the pool on ia, each side's row count and id base, and the info in ia's xj_info.
+static int xjoin_finish(zh_index *ia, zh_index *ib, uint64_t hits, uint64_t capacity, uint64_t *outA, uint64_t *outB, uint64_t *outKeys, bool host_out,
+                        hipStream_t s, uint64_t *total, zh_cross_info inf, const char *who) {
+    *total = hits;
+    inf.pairs = hits;
+    const bool over = hits > capacity;
+    int rc;
+    if (!over && hits) {
+        uint64_t *dV[2] = {nullptr, nullptr}, *dK[2] = {nullptr, nullptr};
+        size_t tmp_bytes = 0;
+        HIPCHK(zh_launch_xjoin_sort(dV, dK, hits, ia->n_rows, ib->n_rows, nullptr, &tmp_bytes, 0, 0, nullptr, nullptr, nullptr, s));
+        if ((rc = ia->xj_pv1.ensure(hits * 8)) || (rc = ia->xj_pk1.ensure(hits * 8)) || (rc = ia->xj_tmp.ensure(tmp_bytes))) return rc;
+        if (host_out && ((rc = ia->xj_oa.ensure(hits * 8)) || (rc = ia->xj_ob.ensure(hits * 8)) || (rc = ia->xj_okeys.ensure(hits * 8)))) return rc;
+        dV[0] = ia->xj_pv0.as<uint64_t>(); dV[1] = ia->xj_pv1.as<uint64_t>();
+        dK[0] = ia->xj_pk0.as<uint64_t>(); dK[1] = ia->xj_pk1.as<uint64_t>();
+        uint64_t *oa = host_out ? ia->xj_oa.as<uint64_t>() : outA, *ob = host_out ? ia->xj_ob.as<uint64_t>() : outB;
+        uint64_t *ok = host_out ? ia->xj_okeys.as<uint64_t>() : outKeys;
+        HIPCHK(zh_launch_xjoin_sort(dV, dK, hits, ia->n_rows, ib->n_rows, ia->xj_tmp.p, &tmp_bytes, ia->opt.id_base, ib->opt.id_base, oa, ob, ok, s));
+        if (host_out) {
+            HIPCHK(hipMemcpyAsync(outA, oa, hits * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(outB, ob, hits * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(outKeys, ok, hits * 8, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    {
+        std::lock_guard<std::mutex> lk(ia->stats_mu);
+        ia->xj_info = inf;
+    }
+    if (over)
+        return fail(ZH_ELIMIT, "%s: %llu pairs exceed the capacity of %llu; out_total is exact, call again with that capacity", who,
+                    (unsigned long long)hits, (unsigned long long)capacity);
+    return ZH_OK;
+}
+
+// The call on the indexes' device (under both mu, exclusive; xjoin_state has run).  host_out as join_run.  ZH_XJOIN_PATH (read per call): 1 keeps
+// everything on path 1, 2 takes path 2 at any size where it is supported.
+static int xjoin_run(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *outA, uint64_t *outB, uint64_t *outKeys,
+                     bool host_out, hipStream_t s, uint64_t *total, const char *who) {
+    zh_cross_info inf{};
+    inf.path = 1;
+    inf.rows_live_a = ia->ex_n_live;
+    inf.rows_live_b = ib->ex_n_live;
+    const uint64_t la = ia->ex_n_live, lb = ib->ex_n_live;
+    uint64_t hits = 0;
+    int rc;
+    if (la && lb) {
+        const uint64_t pool_cap = std::min<uint64_t>(capacity, la * lb);
+        if ((rc = ia->xj_ctr.ensure(32)) || (rc = ia->xj_pv0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)) ||
+            (rc = ia->xj_pk0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)))
+            return rc;
+        HIPCHK(hipMemsetAsync(ia->xj_ctr.p, 0, 32, s));
+        const char *env_p = getenv("ZH_XJOIN_PATH");
+        const int env_path = env_p ? atoi(env_p) : 0;
+        bool used = false;
+        if (env_path != 1 && (rc = xjoin_path2(ia, ib, env_path == 2, max_key, metric, mode, pool_cap, s, &inf, &used, &hits))) return rc;
+        if (!used) {  // panels of A's ascending live list against all of B's
+            for (uint64_t a0 = 0; a0 < la; a0 += ZH_EXACT_BATCH) {
+                const uint32_t B = (uint32_t)std::min<uint64_t>(ZH_EXACT_BATCH, la - a0);
+                if ((rc = xjoin_batch1(ia, ib, ia->ex_live.as<uint32_t>() + a0, B, max_key, metric, mode, pool_cap, s, &inf.launches))) return rc;
+            }
+            unsigned long long h = 0;
+            HIPCHK(hipMemcpyAsync(&h, ia->xj_ctr.p, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            hits = h;
+        }
+    }
+    return xjoin_finish(ia, ib, hits, capacity, outA, outB, outKeys, host_out, s, total, inf, who);
+}
+
+extern "C" int zh_cross_join_device(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *d_out_a,
+                                    uint64_t *d_out_b, uint64_t *d_out_keys, uint64_t *d_out_total, void *stream) {
+    int rc = xjoin_args(ia, ib, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, d_out_total, "zh_cross_join_device");
+    if (rc) return rc;
+    XjoinLocks locks(ia, ib);
+    if ((rc = xjoin_state(ia, ib, "zh_cross_join_device"))) return rc;
+    ScratchGuard guard{ia, SCRATCH_XJOIN};
+    const hipStream_t s = call_stream(ia, stream);
+    uint64_t total = 0;
+    rc = xjoin_run(ia, ib, max_key, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, false, s, &total, "zh_cross_join_device");
+    if (rc && rc != ZH_ELIMIT) return rc;
+    HIPCHK(hipMemcpyAsync(d_out_total, &total, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return rc;
+}
+
+extern "C" int zh_cross_join(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b,
+                             uint64_t *out_keys, uint64_t *out_total) {
+    int rc = xjoin_args(ia, ib, metric, mode, capacity, out_a, out_b, out_keys, out_total, "zh_cross_join");
+    if (rc) return rc;
+    *out_total = 0;
+    XjoinLocks locks(ia, ib);
+    if ((rc = xjoin_state(ia, ib, "zh_cross_join"))) return rc;
+    ScratchGuard guard{ia, SCRATCH_XJOIN};
+    uint64_t total = 0;
+    rc = xjoin_run(ia, ib, max_key, metric, mode, capacity, out_a, out_b, out_keys, true, ia->stream, &total, "zh_cross_join");
+    if (rc && rc != ZH_ELIMIT) return rc;
+    *out_total = total;
+    return rc;
+}
+
+extern "C" int zh_cross_join_info(const zh_index *ia, zh_cross_info *out) { return get_info(ia, &zh_index::xj_info, out, "zh_cross_join_info"); }
 
 // ------------------------------------------------------------------------------------------------
 // exact k-NN graph (zh_knn.hip + the exact search's two paths): each live row's k nearest OTHER live rows, slab by slab.  DESIGN.md s16

@@ -380,6 +380,28 @@ hipError_t zh_launch_join_panel_rows(const uint32_t *dCid, uint64_t p_begin, uin
 hipError_t zh_launch_join_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows, void *dTmp, size_t *tmp_bytes, uint64_t id_base, uint64_t *dOutA,
                                uint64_t *dOutB, uint64_t *dOutKeys, hipStream_t s);
 
+// ---- the exact join between two indexes (zh_xjoin.hip): every pair (live row a of A, live row b of B) with key(stored b, query a) <= one threshold
+// key.  Hit pool and counter as the self-join's, v = a << 32 | b with a a row number of A and b one of B
+// path 1: of the keys [q][p - p0] (zh_launch_exact_score over B's table against rows of A) all those <= max_key
+hipError_t zh_launch_xjoin_collect(const uint64_t *dKeys, uint64_t ld, const uint32_t *dLiveB, uint64_t p0, uint32_t nr, const uint32_t *dQRows, uint32_t B,
+                                   uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
+// path 2: the launch of a panel of held tiles [tileA0, min(tileA1, TA)) of A's copy against all TB tiles of B's: *n_ab held blocks of four tiles,
+// *blocks = n_ab * ceil(TB / ZH_JOIN_CHUNK); returns the 16 x 16 tile products the panel issues
+uint64_t zh_xjoin_geometry(uint64_t TA, uint64_t TB, uint64_t tileA0, uint64_t tileA1, uint32_t *n_ab, uint32_t *blocks);
+// the scan of one panel (tileA0 a multiple of 4; tileA1 one too, or past A's last tile) against *dTau; dCidA / dCidB, dQmB: zh_launch_join_prep of
+// either side; pairs with lo <= tau to dCand as a << 32 | b; *dCandCtr counts all of them (> cand_cap: ran over)
+hipError_t zh_launch_xjoin_mfma(uint32_t d, int metric, int mode, const void *dXhA, const float2 *dRowMetaA, const uint32_t *dCidA, uint64_t n_rows_a,
+                                const void *dXhB, const float4 *dQmB, const uint32_t *dCidB, uint64_t n_rows_b, uint64_t tileA0, uint64_t tileA1, float Kc,
+                                float rhoA, const uint32_t *dTau, uint64_t *dCand, uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s);
+// the candidates' canonical keys (stored row b of dXB, query row a of dXA), judged, counted and appended to the hit pool (nothing when the
+// candidate pool ran over)
+hipError_t zh_launch_xjoin_survivors(const float *dXA, const float *dXB, uint32_t d, int metric, int mode, const uint64_t *dCand,
+                                     const unsigned long long *dCandCtr, uint64_t cand_cap, uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV,
+                                     uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
+// zh_launch_join_sort with each side's row count (the bits sorted) and id base
+hipError_t zh_launch_xjoin_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows_a, uint64_t n_rows_b, void *dTmp, size_t *tmp_bytes,
+                                uint64_t id_base_a, uint64_t id_base_b, uint64_t *dOutA, uint64_t *dOutB, uint64_t *dOutKeys, hipStream_t s);
+
 // ---- the exact k-NN graph (zh_knn.hip): each live row's k nearest other live rows, panel by panel
 #define ZH_KNN_PANEL_ROWS 1024u  // live rows one panel holds (= the exact search's internal batch: every reused launcher sees a batch it already serves)
 #define ZH_KNN_CHUNK 64u         // column tiles one block of the matrix-core scan walks at most

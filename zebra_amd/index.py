@@ -578,6 +578,65 @@ class LSHIndex:
         check(lib().zh_self_join_info(self._h, C.byref(info)))
         return info.as_dict()
 
+    def _cross_other(self, other):
+        if not isinstance(other, LSHIndex):
+            raise TypeError("the join between two indexes takes another LSHIndex")
+        return other._h
+
+    def cross_join(self, other, radius=None, metric=None, max_key=None, capacity=None):
+        """EXACT join between two indexes: every pair (live row a of self, live row b of `other`) whose key is <= ONE threshold -- `radius` or
+        `max_key`, as self_join (2^64-1 = every pair of the rectangle).  The key of a pair is other.search_range_batch's for STORED row b of
+        `other` against a QUERY equal to row a of self; other.cross_join(self) is a different call, with its own keys and order.
+        -> (a u64, b u64, keys u64), ascending by (a, key, b); a carries self's id_base, b other's.  One call with a guessed capacity; when the
+        pairs exceed it, one more with the exact total the first call reported."""
+        mk = self._join_key(radius, metric, max_key)
+        h = self._cross_other(other)
+        cap = int(capacity) if capacity is not None else max(1024, 16 * len(self))
+        total = C.c_uint64(0)
+        for attempt in range(2):
+            a = np.empty(max(cap, 1), np.uint64)
+            b = np.empty(max(cap, 1), np.uint64)
+            keys = np.empty(max(cap, 1), np.uint64)
+            rc = lib().zh_cross_join(self._h, h, mk, metric.metric, metric.mode, cap, _p(a), _p(b), _p(keys), C.byref(total))
+            if rc == _ffi.ZH_ELIMIT and attempt == 0 and total.value > cap:
+                cap = int(total.value)
+                continue
+            check(rc)
+            break
+        n = int(total.value)
+        return a[:n], b[:n], keys[:n]
+
+    def cross_join_count(self, other, radius=None, metric=None, max_key=None):
+        """how many pairs cross_join would return (a call with capacity 0: nothing is ordered or written)"""
+        mk = self._join_key(radius, metric, max_key)
+        total = C.c_uint64(0)
+        rc = lib().zh_cross_join(self._h, self._cross_other(other), mk, metric.metric, metric.mode, 0, None, None, None, C.byref(total))
+        if rc != _ffi.ZH_ELIMIT:
+            check(rc)
+        return int(total.value)
+
+    def cross_join_device(self, other, max_key, metric, capacity, d_a_ptr, d_b_ptr, d_keys_ptr, d_total_ptr, stream=None):
+        """cross_join with a, b, keys (`capacity` each) and the total (one u64) in device memory (raw pointers, e.g. torch .data_ptr()).
+        Pairs beyond the capacity raise ZhError with code ZH_ELIMIT; the total is exact even then."""
+        check(lib().zh_cross_join_device(self._h, self._cross_other(other), int(max_key), metric.metric, metric.mode, capacity, d_a_ptr, d_b_ptr,
+                                         d_keys_ptr, d_total_ptr, stream))
+
+    def cross_info(self):
+        """what the most recent cross_join with this index on the left did (zh_cross_join_info): rows_live_a, rows_live_b, pairs, path, redone,
+        candidates, launches, tiles"""
+        info = _ffi.CrossInfo()
+        check(lib().zh_cross_join_info(self._h, C.byref(info)))
+        return info.as_dict()
+
+    def remove_within(self, other, radius, metric):
+        """drop what the corpus already has: every live row of self that has a live row of `other` within `radius` is removed from self (the
+        distinct a of cross_join's pairs; `other` is left alone) -> the removed ids, ascending"""
+        a, _, _ = self.cross_join(other, radius, metric)
+        removed = matched_rule(a)
+        if removed.size:
+            self.remove(removed)
+        return removed
+
     def knn_graph(self, k, metric, first_row=0, n=None):
         """EXACT k-NN graph of the slab of stored rows [first_row, first_row + n) (default: from first_row to the last stored row): line i holds the
         k nearest OTHER live rows of stored row first_row + i by (key, id) -- the key search_exact_batch gives for that row's f32 values as the
@@ -910,6 +969,12 @@ def dedup_rule(a, b):
     return np.array(sorted(removed), np.uint64)
 
 
+def matched_rule(a):
+    """remove_within's rule on cross_join's left ids: a row of the left index goes when it is in at least one pair -> the distinct a (u64),
+    ascending"""
+    return np.unique(np.asarray(a, dtype=np.uint64))
+
+
 class Database:
     """Database<N, Met, Mod> restricted to the two calls on the hot path: insert_records
     (core.rs:245-254) and query_vectors (core.rs:290-313).  Documents are kept in memory (the lz4
@@ -1000,6 +1065,21 @@ class Database:
         a, b, keys = self.index.self_join_forest(radius, self.metric)
         dist = self._key_numbers(keys)
         return [(self._documents.get(x), self._documents.get(y), float(v)) for x, y, v in zip(a.tolist(), b.tolist(), dist.tolist())]
+
+    def matches(self, other_db, radius):
+        """every pair (record of this database, record of `other_db`) within `radius` (LSHIndex.cross_join: exact; the key is other_db's
+        stored vector against this database's as the query, under this database's metric) -> [(document, other document, distance)], in
+        ascending (id, key, other id) order.  The distance is the number the key holds, as in near_duplicates."""
+        a, b, keys = self.index.cross_join(other_db.index, radius, self.metric)
+        dist = self._key_numbers(keys)
+        return [(self._documents.get(x), other_db._documents.get(y), float(v)) for x, y, v in zip(a.tolist(), b.tolist(), dist.tolist())]
+
+    def remove_within(self, other_db, radius):
+        """LSHIndex.remove_within against other_db's index, then the removed ids' documents go too -> the removed ids"""
+        removed = self.index.remove_within(other_db.index, radius, self.metric)
+        for i in removed.tolist():
+            self._documents.pop(i, None)
+        return removed
 
     def _key_numbers(self, keys):
         """the number each key holds, as f64 (for the parity cosine key: the similarity)"""

@@ -217,6 +217,9 @@ ZH_API int zh_index_clear(zh_index *idx); /* drops vectors AND trees (what lsh.r
 ZH_API int zh_index_add(zh_index *idx, const float *rows, size_t n, uint64_t *out_row_ids);
 /* staged loading for large shards: append without building, then zh_index_build once */
 ZH_API int zh_index_append(zh_index *idx, const float *rows, size_t n, uint64_t *out_row_ids);
+/* The same with the rows already in device memory.  This call takes NO stream: the rows are copied on the index's own (non-blocking) stream and the
+ * call waits for that copy, so d_rows must be COMPLETE before the call -- work still pending on a stream of the caller's that writes d_rows is
+ * ordered against nothing here; wait for it (or for an event of it) first. */
 ZH_API int zh_index_append_device(zh_index *idx, const float *d_rows, size_t n);
 /* append n synthetic rows generated on the device (bit-identical to oracle zo_synth_rows);
  * kind 0 = ~N(0,1), kind 1 = integer-valued "SIFT-style" in [0,255], kind 2 = clustered (128 consecutive rows

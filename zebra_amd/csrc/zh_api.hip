@@ -267,16 +267,15 @@ struct zh_index {
     // pool and its sort partner (v and key), path 2's candidate pool, the sort's temporary storage, offsets and outputs staged for the host call
     DevBuf rg_maxk, rg_cnt, rg_ctr, rg_pv0, rg_pv1, rg_pk0, rg_pk1, rg_cand, rg_tmp, rg_off, rg_oids, rg_okeys;
     zh_range_info rg_info{};  // (stats_mu)
-    // the self-join's per-call scratch (all released before the call returns): {hit, candidate, panel-row} counters, the threshold's bound, the hit
-    // pool and its sort partner, path 2's per-position views, block table and candidate pool, a redone panel's row list, the sort's temporary storage
-    // and the outputs staged for the host call
+    // the joins' per-call scratch (all released before the call returns; the forest join's and the cross-join's too, which hold mu exclusively as the
+    // self-join does; the cross-join's is on its LEFT index): {hit, candidate, panel-row} counters, the threshold's bound, the hit pool and its sort
+    // partner, path 2's per-position views, block table and candidate pool, a redone panel's row list, the sort's temporary storage and the outputs
+    // staged for the host call
     DevBuf jn_ctr, jn_maxk, jn_tau, jn_pv0, jn_pv1, jn_pk0, jn_pk1, jn_qm, jn_cid, jn_first, jn_cand, jn_rows, jn_tmp, jn_oa, jn_ob, jn_okeys;
     zh_join_info jn_info{};  // (stats_mu)
-    // the cross-join's per-call scratch, all on the LEFT index (all released before the call returns): {hit, candidate, panel-row} counters, the
-    // threshold's bound, the hit pool and its sort partner, path 2's per-position views of A (id word; the query view zh_launch_join_prep writes beside
-    // it is not read) and of B (query view, id word), the candidate pool, a redone panel's row list, the sort's temporary storage and the outputs
-    // staged for the host call
-    DevBuf xj_ctr, xj_maxk, xj_tau, xj_pv0, xj_pv1, xj_pk0, xj_pk1, xj_qma, xj_cida, xj_qmb, xj_cidb, xj_cand, xj_rows, xj_tmp, xj_oa, xj_ob, xj_okeys;
+    // what the cross-join holds beside them, on the LEFT index too: path 2's per-position views of A (id word; the query view zh_launch_join_prep
+    // writes beside it is not read) and of B (query view, id word)
+    DevBuf xj_qma, xj_cida, xj_qmb, xj_cidb;
     zh_cross_info xj_info{};  // (stats_mu)
     // the k-NN graph's per-call scratch (all released before the call returns): path 2's per-position views and row -> position map, one panel's
     // tiles, rowMeta and row numbers, the lists' bases, the panel's answer, and the outputs staged for the host call
@@ -3468,7 +3467,7 @@ static int score_param(int metric, int mode) { return (metric == ZH_COSINE || me
 // The per-call scratch, each family's buffers listed once.  The guard of a call gives its set back to the driver however the call returns: an idle
 // index holds only the live-row views (ex_live and ex_bits survive every call; zh_index_destroy frees them).  Every family scans with the exact
 // search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's, the forest range search with
-// the range search's and the forest join's, the cross-join (all on its LEFT index) with its own.
+// the range search's and the forest join's, the cross-join (all on its LEFT index) with the join's and its own views.
 enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256 };  // one bit per list
 enum : unsigned {
     SCRATCH_EXACT = SCR_EX,
@@ -3479,7 +3478,7 @@ enum : unsigned {
     SCRATCH_FKNN = SCR_FK | SCRATCH_KNN,
     SCRATCH_FJOIN = SCR_FJ | SCRATCH_JOIN | SCRATCH_FKNN,
     SCRATCH_FRANGE = SCR_FR | SCRATCH_RANGE | SCRATCH_FJOIN,
-    SCRATCH_XJOIN = SCR_XJ | SCRATCH_EXACT,  // (on the left index)
+    SCRATCH_XJOIN = SCR_XJ | SCRATCH_JOIN,  // (on the left index)
 };
 static void release_scratch(zh_index *ix, unsigned families) {
     auto drop = [&](unsigned list, std::initializer_list<DevBuf *> bs) {
@@ -3494,8 +3493,7 @@ static void release_scratch(zh_index *ix, unsigned families) {
                   &ix->rg_oids, &ix->rg_okeys});
     drop(SCR_JN, {&ix->jn_ctr, &ix->jn_maxk, &ix->jn_tau, &ix->jn_pv0, &ix->jn_pv1, &ix->jn_pk0, &ix->jn_pk1, &ix->jn_qm, &ix->jn_cid, &ix->jn_first,
                   &ix->jn_cand, &ix->jn_rows, &ix->jn_tmp, &ix->jn_oa, &ix->jn_ob, &ix->jn_okeys});
-    drop(SCR_XJ, {&ix->xj_ctr, &ix->xj_maxk, &ix->xj_tau, &ix->xj_pv0, &ix->xj_pv1, &ix->xj_pk0, &ix->xj_pk1, &ix->xj_qma, &ix->xj_cida, &ix->xj_qmb,
-                  &ix->xj_cidb, &ix->xj_cand, &ix->xj_rows, &ix->xj_tmp, &ix->xj_oa, &ix->xj_ob, &ix->xj_okeys});
+    drop(SCR_XJ, {&ix->xj_qma, &ix->xj_cida, &ix->xj_qmb, &ix->xj_cidb});
     drop(SCR_KN, {&ix->kn_qm, &ix->kn_cid, &ix->kn_pos, &ix->kn_A, &ix->kn_pmeta, &ix->kn_pid, &ix->kn_cbase, &ix->kn_pids, &ix->kn_pkeys, &ix->kn_pcounts,
                   &ix->kn_oids, &ix->kn_okeys, &ix->kn_ocounts});
     drop(SCR_FK, {&ix->fk_ntree, &ix->fk_rl, &ix->fk_flag, &ix->fk_excl, &ix->fk_tmp, &ix->fk_rows, &ix->fk_ctr, &ix->fk_lens, &ix->fk_takes, &ix->fk_rbase,
@@ -4209,28 +4207,43 @@ extern "C" int zh_search_range_info(const zh_index *ix, zh_range_info *out) { re
 // ------------------------------------------------------------------------------------------------
 #define ZH_JOIN_CAND_FLOOR 256u  // path 2: candidate slots per held row of a panel that are there whatever the capacity (a count-only call still lists candidates)
 
-// Path 1 for the B <= ZH_EXACT_BATCH query rows dQRows (row numbers, device): gathered into the query buffer, exact_score_kernel's keys of the live
-// rows from position p_from of the ascending live list on (no live row before it is above any of the query rows), join_collect_kernel over them.
-// Hits are counted in jn_ctr[0] and pooled while the pool has room.
-static int join_batch1(zh_index *ix, const uint32_t *dQRows, uint32_t B, uint64_t p_from, uint64_t max_key, int metric, int mode, uint64_t pool_cap,
-                       hipStream_t s, uint64_t *launches) {
-    const uint32_t d = ix->opt.dim;
-    const uint64_t n_live = ix->ex_n_live;
+// Path 1 of the self-join and the cross-join, for the B <= ZH_EXACT_BATCH query rows dQRows (row numbers of iq, device) against the stored rows of
+// `is` (the self-join: iq itself): gathered out of iq's table into iq's query buffer, exact_score_kernel's keys of is's live rows from position
+// p_from of its ascending live list on, pair_collect_kernel over them.  upper (the self-join): only the rows above the query row count, and no live
+// row before p_from is above any of the query rows; the cross-join takes every live row of is.  Hits are counted in iq's jn_ctr[0] and pooled there
+// while the pool has room.
+static int pair_batch1(zh_index *iq, zh_index *is, const uint32_t *dQRows, uint32_t B, uint64_t p_from, bool upper, uint64_t max_key, int metric, int mode,
+                       uint64_t pool_cap, hipStream_t s, uint64_t *launches) {
+    const uint32_t d = iq->opt.dim;
+    const uint64_t n_live = is->ex_n_live;
     if (!B || p_from >= n_live) return ZH_OK;
     const uint64_t rc_rows = std::min<uint64_t>(std::max<uint64_t>(256, ZH_EXACT_KEY_BYTES / 8 / B), n_live - p_from);
     int rc;
-    if ((rc = ix->ex_Q.ensure((size_t)B * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_keys.ensure((size_t)B * rc_rows * 8))) return rc;
+    if ((rc = iq->ex_Q.ensure((size_t)B * d * 4)) || (rc = iq->ex_QQ.ensure((size_t)B * 4)) || (rc = iq->ex_keys.ensure((size_t)B * rc_rows * 8))) return rc;
     const int param = score_param(metric, mode);
-    HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dQRows, B, ix->ex_Q.as<float>(), s));
-    HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), B, d, ix->ex_QQ.as<float>(), s));
+    HIPCHK(zh_launch_join_gather(iq->X.as<float>(), d, dQRows, B, iq->ex_Q.as<float>(), s));
+    HIPCHK(zh_launch_qnorm(iq->ex_Q.as<float>(), B, d, iq->ex_QQ.as<float>(), s));
     for (uint64_t p0 = p_from; p0 < n_live; p0 += rc_rows) {
         const uint32_t nr = (uint32_t)std::min<uint64_t>(rc_rows, n_live - p0);
-        HIPCHK(zh_launch_exact_score(ix->X.as<float>(), d, ix->ex_live.as<uint32_t>(), p0, nr, ix->ex_Q.as<float>(), ix->ex_QQ.as<float>(), B, metric, param,
-                                     ix->ex_keys.as<uint64_t>(), rc_rows, s));
-        HIPCHK(zh_launch_join_collect(ix->ex_keys.as<uint64_t>(), rc_rows, ix->ex_live.as<uint32_t>(), p0, nr, dQRows, B, max_key,
-                                      ix->jn_ctr.as<unsigned long long>(), ix->jn_pv0.as<uint64_t>(), ix->jn_pk0.as<uint64_t>(), pool_cap, s));
+        HIPCHK(zh_launch_exact_score(is->X.as<float>(), d, is->ex_live.as<uint32_t>(), p0, nr, iq->ex_Q.as<float>(), iq->ex_QQ.as<float>(), B, metric, param,
+                                     iq->ex_keys.as<uint64_t>(), rc_rows, s));
+        HIPCHK(zh_launch_pair_collect(iq->ex_keys.as<uint64_t>(), rc_rows, is->ex_live.as<uint32_t>(), p0, nr, dQRows, B, upper, max_key,
+                                      iq->jn_ctr.as<unsigned long long>(), iq->jn_pv0.as<uint64_t>(), iq->jn_pk0.as<uint64_t>(), pool_cap, s));
         (*launches)++;
     }
+    return ZH_OK;
+}
+
+// The tail of a path-2 panel (the forest join: batch of leaves) whose survivors are launched: the first n counters of jn_ctr -- {hits, the panel's
+// candidates, ...} -- are read into h_ctr and waited for.  *kept: the candidates fitted their pool and were judged, *hits = the hits so far.
+// Otherwise nothing of the panel was counted and ++*redone; what answers it instead is the caller's, because it differs: a whole-call rewind under
+// a row order, a panel redo, a leaf redo.
+static int panel_tail(zh_index *ix, uint32_t n, uint64_t cand_cap, hipStream_t s, unsigned long long *h_ctr, uint64_t *hits, uint32_t *redone, bool *kept) {
+    HIPCHK(hipMemcpyAsync(h_ctr, ix->jn_ctr.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *kept = h_ctr[1] <= cand_cap;
+    if (*kept) *hits = h_ctr[0];
+    else (*redone)++;
     return ZH_OK;
 }
 
@@ -4279,17 +4292,15 @@ static int join_path2(zh_index *ix, uint64_t max_key, int metric, int mode, uint
                                    first[n_ab], Kc, v.rho, ix->jn_tau.as<uint32_t>(), ix->jn_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
         inf->launches++;
         inf->tiles += products;
-        HIPCHK(zh_launch_join_survivors(ix->X.as<float>(), d, metric, mode, ix->jn_cand.as<uint64_t>(), ctr + 1, cand_cap, max_key, ctr,
-                                        ix->jn_pv0.as<uint64_t>(), ix->jn_pk0.as<uint64_t>(), pool_cap, s));
+        HIPCHK(zh_launch_pair_survivors(ix->X.as<float>(), ix->X.as<float>(), d, metric, mode, ix->jn_cand.as<uint64_t>(), ctr + 1, cand_cap, nullptr, 0, 0,
+                                        max_key, ctr, nullptr, ix->jn_pv0.as<uint64_t>(), ix->jn_pk0.as<uint64_t>(), pool_cap, s));
         unsigned long long h_ctr[3] = {0, 0, 0};
-        HIPCHK(hipMemcpyAsync(h_ctr, ctr, 24, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (h_ctr[1] <= cand_cap) {
+        bool kept = false;
+        if ((rc = panel_tail(ix, 3, cand_cap, s, h_ctr, hits, &inf->redone, &kept))) return rc;
+        if (kept) {
             inf->candidates += h_ctr[1];
-            *hits = h_ctr[0];
             continue;
         }
-        inf->redone++;
         if (v.perm_rows) {
             // Under a row order a panel owns its pairs by POSITION (the lower position lies in it), and path 1 owns pairs by row number: the
             // redo below would count a different set.  So nothing of path 2 is kept: counters and pool rewound, the whole call answered by path 1.
@@ -4308,7 +4319,7 @@ static int join_path2(zh_index *ix, uint64_t max_key, int metric, int mode, uint
         const uint64_t p_from = live_before(ix, P0, &live);
         for (uint64_t b0 = 0; b0 < h_ctr[2]; b0 += ZH_EXACT_BATCH) {
             const uint32_t nb = (uint32_t)std::min<uint64_t>(ZH_EXACT_BATCH, h_ctr[2] - b0);
-            if ((rc = join_batch1(ix, ix->jn_rows.as<uint32_t>() + b0, nb, p_from, max_key, metric, mode, pool_cap, s, &inf->launches))) return rc;
+            if ((rc = pair_batch1(ix, ix, ix->jn_rows.as<uint32_t>() + b0, nb, p_from, true, max_key, metric, mode, pool_cap, s, &inf->launches))) return rc;
         }
         HIPCHK(hipMemcpyAsync(h_ctr, ctr, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
@@ -4323,12 +4334,13 @@ static int join_args(zh_index *ix, int metric, int mode, uint64_t capacity, cons
     return check_metric(metric, mode);
 }
 
-// What both joins do once the hits are pooled in jn_pv0 / jn_pk0 and counted: *total = hits, exact whatever the capacity; within it, the pool ordered
-// into outA / outB / outKeys (host_out: HOST arrays, filled through staging; otherwise device arrays) and waited for; the info written; ZH_ELIMIT
-// past the capacity.
+// What the three joins do once the hits are pooled in ix's jn_pv0 / jn_pk0 and counted: *total = hits, exact whatever the capacity; within it, the pool
+// ordered into outA / outB / outKeys (host_out: HOST arrays, filled through staging; otherwise device arrays) and waited for; the info written into
+// ix's slot; ZH_ELIMIT past the capacity.  ib = the index the b side's rows are numbered in and whose id base they get: ix itself but for the
+// cross-join.
 template <typename Info>
-static int join_finish(zh_index *ix, uint64_t hits, uint64_t capacity, uint64_t *outA, uint64_t *outB, uint64_t *outKeys, bool host_out, hipStream_t s,
-                       uint64_t *total, Info inf, Info zh_index::*slot, const char *who) {
+static int join_finish(zh_index *ix, const zh_index *ib, uint64_t hits, uint64_t capacity, uint64_t *outA, uint64_t *outB, uint64_t *outKeys, bool host_out,
+                       hipStream_t s, uint64_t *total, Info inf, Info zh_index::*slot, const char *who) {
     *total = hits;
     inf.pairs = hits;
     const bool over = hits > capacity;
@@ -4336,14 +4348,14 @@ static int join_finish(zh_index *ix, uint64_t hits, uint64_t capacity, uint64_t 
     if (!over && hits) {
         uint64_t *dV[2] = {nullptr, nullptr}, *dK[2] = {nullptr, nullptr};
         size_t tmp_bytes = 0;
-        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, nullptr, &tmp_bytes, 0, nullptr, nullptr, nullptr, s));
+        HIPCHK(zh_launch_pair_sort(dV, dK, hits, ix->n_rows, ib->n_rows, nullptr, &tmp_bytes, 0, 0, nullptr, nullptr, nullptr, s));
         if ((rc = ix->jn_pv1.ensure(hits * 8)) || (rc = ix->jn_pk1.ensure(hits * 8)) || (rc = ix->jn_tmp.ensure(tmp_bytes))) return rc;
         if (host_out && ((rc = ix->jn_oa.ensure(hits * 8)) || (rc = ix->jn_ob.ensure(hits * 8)) || (rc = ix->jn_okeys.ensure(hits * 8)))) return rc;
         dV[0] = ix->jn_pv0.as<uint64_t>(); dV[1] = ix->jn_pv1.as<uint64_t>();
         dK[0] = ix->jn_pk0.as<uint64_t>(); dK[1] = ix->jn_pk1.as<uint64_t>();
         uint64_t *oa = host_out ? ix->jn_oa.as<uint64_t>() : outA, *ob = host_out ? ix->jn_ob.as<uint64_t>() : outB;
         uint64_t *ok = host_out ? ix->jn_okeys.as<uint64_t>() : outKeys;
-        HIPCHK(zh_launch_join_sort(dV, dK, hits, ix->n_rows, ix->jn_tmp.p, &tmp_bytes, ix->opt.id_base, oa, ob, ok, s));
+        HIPCHK(zh_launch_pair_sort(dV, dK, hits, ix->n_rows, ib->n_rows, ix->jn_tmp.p, &tmp_bytes, ix->opt.id_base, ib->opt.id_base, oa, ob, ok, s));
         if (host_out) {
             HIPCHK(hipMemcpyAsync(outA, oa, hits * 8, hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(outB, ob, hits * 8, hipMemcpyDeviceToHost, s));
@@ -4383,7 +4395,7 @@ static int join_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint64
         if (!used) {  // panels of the ascending live list: panel [a0, a0 + B) against the live rows from a0 on
             for (uint64_t a0 = 0; a0 + 1 < n_live; a0 += ZH_EXACT_BATCH) {
                 const uint32_t B = (uint32_t)std::min<uint64_t>(ZH_EXACT_BATCH, n_live - a0);
-                if ((rc = join_batch1(ix, ix->ex_live.as<uint32_t>() + a0, B, a0, max_key, metric, mode, pool_cap, s, &inf.launches))) return rc;
+                if ((rc = pair_batch1(ix, ix, ix->ex_live.as<uint32_t>() + a0, B, a0, true, max_key, metric, mode, pool_cap, s, &inf.launches))) return rc;
             }
             unsigned long long h = 0;
             HIPCHK(hipMemcpyAsync(&h, ix->jn_ctr.p, 8, hipMemcpyDeviceToHost, s));
@@ -4391,7 +4403,7 @@ static int join_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint64
             hits = h;
         }
     }
-    return join_finish(ix, hits, capacity, outA, outB, outKeys, host_out, s, total, inf, &zh_index::jn_info, who);
+    return join_finish(ix, ix, hits, capacity, outA, outB, outKeys, host_out, s, total, inf, &zh_index::jn_info, who);
 }
 
 extern "C" int zh_self_join_device(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *d_out_a, uint64_t *d_out_b,
@@ -4428,35 +4440,11 @@ extern "C" int zh_self_join(zh_index *ix, uint64_t max_key, int metric, int mode
 extern "C" int zh_self_join_info(const zh_index *ix, zh_join_info *out) { return get_info(ix, &zh_index::jn_info, out, "zh_self_join_info"); }
 
 // ------------------------------------------------------------------------------------------------
-// exact join between two indexes (zh_xjoin.hip + the exact search's score kernel): every pair (live row a of A, live row b of B) with
-// key(stored b of B, query a of A) <= one threshold key, as three arrays ascending by (a, key, b).  All scratch and the info on A.  DESIGN.md s20
+// exact join between two indexes (zh_xjoin.hip, the self-join's pool and the exact search's score kernel): every pair (live row a of A, live row
+// b of B) with key(stored b of B, query a of A) <= one threshold key, as three arrays ascending by (a, key, b).  All scratch and the info on A.
+// DESIGN.md s20
 // ------------------------------------------------------------------------------------------------
 #define ZH_XJOIN_GATE_PAIRS (uint64_t(1) << 25)  // live(A) x live(B) from which path 2 is taken: the pair work at which the self-join switches (8192^2 / 2)
-
-// Path 1 for the B <= ZH_EXACT_BATCH query rows dQRows (row numbers of A, device): gathered out of A's table into A's query buffer,
-// exact_score_kernel's keys of ALL live rows of ib against them, xjoin_collect_kernel over them.  Hits are counted in xj_ctr[0] and pooled while
-// the pool has room.
-static int xjoin_batch1(zh_index *ia, zh_index *ib, const uint32_t *dQRows, uint32_t B, uint64_t max_key, int metric, int mode, uint64_t pool_cap,
-                        hipStream_t s, uint64_t *launches) {
-    const uint32_t d = ia->opt.dim;
-    const uint64_t n_live = ib->ex_n_live;
-    if (!B || !n_live) return ZH_OK;
-    const uint64_t rc_rows = std::min<uint64_t>(std::max<uint64_t>(256, ZH_EXACT_KEY_BYTES / 8 / B), n_live);
-    int rc;
-    if ((rc = ia->ex_Q.ensure((size_t)B * d * 4)) || (rc = ia->ex_QQ.ensure((size_t)B * 4)) || (rc = ia->ex_keys.ensure((size_t)B * rc_rows * 8))) return rc;
-    const int param = score_param(metric, mode);
-    HIPCHK(zh_launch_join_gather(ia->X.as<float>(), d, dQRows, B, ia->ex_Q.as<float>(), s));
-    HIPCHK(zh_launch_qnorm(ia->ex_Q.as<float>(), B, d, ia->ex_QQ.as<float>(), s));
-    for (uint64_t p0 = 0; p0 < n_live; p0 += rc_rows) {
-        const uint32_t nr = (uint32_t)std::min<uint64_t>(rc_rows, n_live - p0);
-        HIPCHK(zh_launch_exact_score(ib->X.as<float>(), d, ib->ex_live.as<uint32_t>(), p0, nr, ia->ex_Q.as<float>(), ia->ex_QQ.as<float>(), B, metric, param,
-                                     ia->ex_keys.as<uint64_t>(), rc_rows, s));
-        HIPCHK(zh_launch_xjoin_collect(ia->ex_keys.as<uint64_t>(), rc_rows, ib->ex_live.as<uint32_t>(), p0, nr, dQRows, B, max_key,
-                                       ia->xj_ctr.as<unsigned long long>(), ia->xj_pv0.as<uint64_t>(), ia->xj_pk0.as<uint64_t>(), pool_cap, s));
-        (*launches)++;
-    }
-    return ZH_OK;
-}
 
 // Path 2 of the whole call: the threshold as a fixed bound, either side's positions through zh_launch_join_prep (A's id word; B's id word and its
 // rows as approx_interval's queries, with B's rho), then panel after panel of ZH_JOIN_PANEL_ROWS positions of A's copy: one matrix-core launch of
@@ -4465,7 +4453,7 @@ static int xjoin_batch1(zh_index *ia, zh_index *ib, const uint32_t *dQRows, uint
 // too, unlike the self-join's: a panel owns the pairs (a, b) of the A rows at its positions, whatever those rows' numbers and wherever b sits in
 // B's copy, and path 1 for exactly those A rows against every live b is the same set -- no pair of the rectangle belongs to two panels, none to a
 // panel by anything but its A row, so no whole-call rewind is needed.  *used = false: path 2 does not serve this pair of indexes and path 1
-// answers everything.  *hits = xj_ctr[0] on return with *used.
+// answers everything.  *hits = jn_ctr[0] on return with *used.
 static int xjoin_path2(zh_index *ia, zh_index *ib, bool forced, uint64_t max_key, int metric, int mode, uint64_t pool_cap, hipStream_t s, zh_cross_info *inf,
                        bool *used, uint64_t *hits) {
     *used = false;
@@ -4487,11 +4475,11 @@ static int xjoin_path2(zh_index *ia, zh_index *ib, bool forced, uint64_t max_key
     if (!have_b) return ZH_OK;
     const uint64_t na = ia->n_rows, nb = ib->n_rows, TA = (na + 15) / 16, TB = (nb + 15) / 16;
     if ((rc = ia->xj_qma.ensure(TA * 16 * 16)) || (rc = ia->xj_cida.ensure(TA * 16 * 4)) || (rc = ia->xj_qmb.ensure(TB * 16 * 16)) ||
-        (rc = ia->xj_cidb.ensure(TB * 16 * 4)) || (rc = ia->xj_tau.ensure(4)) || (rc = ia->xj_maxk.ensure(8)))
+        (rc = ia->xj_cidb.ensure(TB * 16 * 4)) || (rc = ia->jn_tau.ensure(4)) || (rc = ia->jn_maxk.ensure(8)))
         return rc;
-    unsigned long long *ctr = ia->xj_ctr.as<unsigned long long>();  // {hits, the panel's candidates, a redone panel's rows}
-    HIPCHK(hipMemcpyAsync(ia->xj_maxk.p, &max_key, 8, hipMemcpyHostToDevice, s));
-    HIPCHK(zh_launch_range_tau(ia->xj_maxk.as<uint64_t>(), 1, metric, mode, ia->xj_tau.as<uint32_t>(), s));
+    unsigned long long *ctr = ia->jn_ctr.as<unsigned long long>();  // {hits, the panel's candidates, a redone panel's rows}
+    HIPCHK(hipMemcpyAsync(ia->jn_maxk.p, &max_key, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(zh_launch_range_tau(ia->jn_maxk.as<uint64_t>(), 1, metric, mode, ia->jn_tau.as<uint32_t>(), s));
     HIPCHK(zh_launch_join_prep(va.rowMeta, va.perm, va.perm_rows, ia->ex_bits.as<uint32_t>(), na, va.rho, ia->xj_qma.as<float4>(), ia->xj_cida.as<uint32_t>(), s));
     HIPCHK(zh_launch_join_prep(vb.rowMeta, vb.perm, vb.perm_rows, ib->ex_bits.as<uint32_t>(), nb, vb.rho, ia->xj_qmb.as<float4>(), ia->xj_cidb.as<uint32_t>(), s));
     HIPCHK(hipStreamSynchronize(s));  // (max_key is the caller's stack)
@@ -4504,30 +4492,28 @@ static int xjoin_path2(zh_index *ia, zh_index *ib, bool forced, uint64_t max_key
         const uint64_t products = zh_xjoin_geometry(TA, TB, tileA0, tileA1, &n_ab, &blocks);
         const uint64_t panel_rows = P1 - P0, pairs_bound = panel_rows * nb, pool_left = pool_cap > *hits ? pool_cap - *hits : 0;
         const uint64_t cand_cap = std::min<uint64_t>(pairs_bound, std::max<uint64_t>(pool_left + pool_left / 4, (uint64_t)ZH_JOIN_CAND_FLOOR * panel_rows));
-        if ((rc = ia->xj_cand.ensure(cand_cap * 8))) return rc;
+        if ((rc = ia->jn_cand.ensure(cand_cap * 8))) return rc;
         HIPCHK(hipMemsetAsync(ctr + 1, 0, 16, s));
         HIPCHK(zh_launch_xjoin_mfma(d, metric, mode, va.Xh, va.rowMeta, ia->xj_cida.as<uint32_t>(), na, vb.Xh, ia->xj_qmb.as<float4>(), ia->xj_cidb.as<uint32_t>(),
-                                    nb, tileA0, tileA1, Kc, va.rho, ia->xj_tau.as<uint32_t>(), ia->xj_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
+                                    nb, tileA0, tileA1, Kc, va.rho, ia->jn_tau.as<uint32_t>(), ia->jn_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
         inf->launches++;
         inf->tiles += products;
-        HIPCHK(zh_launch_xjoin_survivors(ia->X.as<float>(), ib->X.as<float>(), d, metric, mode, ia->xj_cand.as<uint64_t>(), ctr + 1, cand_cap, max_key, ctr,
-                                         ia->xj_pv0.as<uint64_t>(), ia->xj_pk0.as<uint64_t>(), pool_cap, s));
+        HIPCHK(zh_launch_pair_survivors(ia->X.as<float>(), ib->X.as<float>(), d, metric, mode, ia->jn_cand.as<uint64_t>(), ctr + 1, cand_cap, nullptr, 0, 0,
+                                        max_key, ctr, nullptr, ia->jn_pv0.as<uint64_t>(), ia->jn_pk0.as<uint64_t>(), pool_cap, s));
         unsigned long long h_ctr[3] = {0, 0, 0};
-        HIPCHK(hipMemcpyAsync(h_ctr, ctr, 24, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (h_ctr[1] <= cand_cap) {
+        bool kept = false;
+        if ((rc = panel_tail(ia, 3, cand_cap, s, h_ctr, hits, &inf->redone, &kept))) return rc;
+        if (kept) {
             inf->candidates += h_ctr[1];
-            *hits = h_ctr[0];
             continue;
         }
-        inf->redone++;
-        if ((rc = ia->xj_rows.ensure(panel_rows * 4))) return rc;
-        HIPCHK(zh_launch_join_panel_rows(ia->xj_cida.as<uint32_t>(), P0, P1, ia->xj_rows.as<uint32_t>(), ctr + 2, s));
+        if ((rc = ia->jn_rows.ensure(panel_rows * 4))) return rc;
+        HIPCHK(zh_launch_join_panel_rows(ia->xj_cida.as<uint32_t>(), P0, P1, ia->jn_rows.as<uint32_t>(), ctr + 2, s));
         HIPCHK(hipMemcpyAsync(h_ctr, ctr, 24, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         for (uint64_t b0 = 0; b0 < h_ctr[2]; b0 += ZH_EXACT_BATCH) {
             const uint32_t nq = (uint32_t)std::min<uint64_t>(ZH_EXACT_BATCH, h_ctr[2] - b0);
-            if ((rc = xjoin_batch1(ia, ib, ia->xj_rows.as<uint32_t>() + b0, nq, max_key, metric, mode, pool_cap, s, &inf->launches))) return rc;
+            if ((rc = pair_batch1(ia, ib, ia->jn_rows.as<uint32_t>() + b0, nq, 0, false, max_key, metric, mode, pool_cap, s, &inf->launches))) return rc;
         }
         HIPCHK(hipMemcpyAsync(h_ctr, ctr, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
@@ -4560,41 +4546,6 @@ static int xjoin_state(zh_index *ia, zh_index *ib, const char *who) {
     return ZH_OK;
 }
 
-// What join_finish does, with the pool on ia, each side's row count and id base, and the info in ia's xj_info.
-static int xjoin_finish(zh_index *ia, zh_index *ib, uint64_t hits, uint64_t capacity, uint64_t *outA, uint64_t *outB, uint64_t *outKeys, bool host_out,
-                        hipStream_t s, uint64_t *total, zh_cross_info inf, const char *who) {
-    *total = hits;
-    inf.pairs = hits;
-    const bool over = hits > capacity;
-    int rc;
-    if (!over && hits) {
-        uint64_t *dV[2] = {nullptr, nullptr}, *dK[2] = {nullptr, nullptr};
-        size_t tmp_bytes = 0;
-        HIPCHK(zh_launch_xjoin_sort(dV, dK, hits, ia->n_rows, ib->n_rows, nullptr, &tmp_bytes, 0, 0, nullptr, nullptr, nullptr, s));
-        if ((rc = ia->xj_pv1.ensure(hits * 8)) || (rc = ia->xj_pk1.ensure(hits * 8)) || (rc = ia->xj_tmp.ensure(tmp_bytes))) return rc;
-        if (host_out && ((rc = ia->xj_oa.ensure(hits * 8)) || (rc = ia->xj_ob.ensure(hits * 8)) || (rc = ia->xj_okeys.ensure(hits * 8)))) return rc;
-        dV[0] = ia->xj_pv0.as<uint64_t>(); dV[1] = ia->xj_pv1.as<uint64_t>();
-        dK[0] = ia->xj_pk0.as<uint64_t>(); dK[1] = ia->xj_pk1.as<uint64_t>();
-        uint64_t *oa = host_out ? ia->xj_oa.as<uint64_t>() : outA, *ob = host_out ? ia->xj_ob.as<uint64_t>() : outB;
-        uint64_t *ok = host_out ? ia->xj_okeys.as<uint64_t>() : outKeys;
-        HIPCHK(zh_launch_xjoin_sort(dV, dK, hits, ia->n_rows, ib->n_rows, ia->xj_tmp.p, &tmp_bytes, ia->opt.id_base, ib->opt.id_base, oa, ob, ok, s));
-        if (host_out) {
-            HIPCHK(hipMemcpyAsync(outA, oa, hits * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(outB, ob, hits * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(outKeys, ok, hits * 8, hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    {
-        std::lock_guard<std::mutex> lk(ia->stats_mu);
-        ia->xj_info = inf;
-    }
-    if (over)
-        return fail(ZH_ELIMIT, "%s: %llu pairs exceed the capacity of %llu; out_total is exact, call again with that capacity", who,
-                    (unsigned long long)hits, (unsigned long long)capacity);
-    return ZH_OK;
-}
-
 // The call on the indexes' device (under both mu, exclusive; xjoin_state has run).  host_out as join_run.  ZH_XJOIN_PATH (read per call): 1 keeps
 // everything on path 1, 2 takes path 2 at any size where it is supported.
 static int xjoin_run(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *outA, uint64_t *outB, uint64_t *outKeys,
@@ -4608,10 +4559,10 @@ static int xjoin_run(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, i
     int rc;
     if (la && lb) {
         const uint64_t pool_cap = std::min<uint64_t>(capacity, la * lb);
-        if ((rc = ia->xj_ctr.ensure(32)) || (rc = ia->xj_pv0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)) ||
-            (rc = ia->xj_pk0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)))
+        if ((rc = ia->jn_ctr.ensure(32)) || (rc = ia->jn_pv0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)) ||
+            (rc = ia->jn_pk0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)))
             return rc;
-        HIPCHK(hipMemsetAsync(ia->xj_ctr.p, 0, 32, s));
+        HIPCHK(hipMemsetAsync(ia->jn_ctr.p, 0, 32, s));
         const char *env_p = getenv("ZH_XJOIN_PATH");
         const int env_path = env_p ? atoi(env_p) : 0;
         bool used = false;
@@ -4619,15 +4570,15 @@ static int xjoin_run(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, i
         if (!used) {  // panels of A's ascending live list against all of B's
             for (uint64_t a0 = 0; a0 < la; a0 += ZH_EXACT_BATCH) {
                 const uint32_t B = (uint32_t)std::min<uint64_t>(ZH_EXACT_BATCH, la - a0);
-                if ((rc = xjoin_batch1(ia, ib, ia->ex_live.as<uint32_t>() + a0, B, max_key, metric, mode, pool_cap, s, &inf.launches))) return rc;
+                if ((rc = pair_batch1(ia, ib, ia->ex_live.as<uint32_t>() + a0, B, 0, false, max_key, metric, mode, pool_cap, s, &inf.launches))) return rc;
             }
             unsigned long long h = 0;
-            HIPCHK(hipMemcpyAsync(&h, ia->xj_ctr.p, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(&h, ia->jn_ctr.p, 8, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             hits = h;
         }
     }
-    return xjoin_finish(ia, ib, hits, capacity, outA, outB, outKeys, host_out, s, total, inf, who);
+    return join_finish(ia, ib, hits, capacity, outA, outB, outKeys, host_out, s, total, inf, &zh_index::xj_info, who);
 }
 
 extern "C" int zh_cross_join_device(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *d_out_a,
@@ -5356,19 +5307,18 @@ static int fjoin_batch2(zh_index *ix, const FjoinRun &run, uint32_t t, const std
                                 ix->fk_cqm.as<float4>(), crow, run.Kc, run.v.rho, ix->jn_tau.as<uint32_t>(), ix->fj_cand.as<uint64_t>(), cand_cap, ctr + 1, s));
     inf->launches++;
     inf->tiles += products;
-    HIPCHK(zh_launch_fjoin_survivors(ix->X.as<float>(), d, run.metric, run.mode, ix->fj_cand.as<uint64_t>(), ctr + 1, cand_cap, ix->fj_leafof.as<uint32_t>(), run.T,
-                                     t, run.max_key, ctr, ctr + 3, ix->jn_pv0.as<uint64_t>(), ix->jn_pk0.as<uint64_t>(), run.pool_cap, s));
+    HIPCHK(zh_launch_pair_survivors(ix->X.as<float>(), ix->X.as<float>(), d, run.metric, run.mode, ix->fj_cand.as<uint64_t>(), ctr + 1, cand_cap,
+                                    ix->fj_leafof.as<uint32_t>(), run.T, t, run.max_key, ctr, ctr + 3, ix->jn_pv0.as<uint64_t>(), ix->jn_pk0.as<uint64_t>(),
+                                    run.pool_cap, s));
     unsigned long long h_ctr[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(h_ctr, ctr, 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));  // (segs and colsrc are this frame's and the caller's)
-    if (h_ctr[1] <= cand_cap) {
+    bool kept = false;
+    if ((rc = panel_tail(ix, 4, cand_cap, s, h_ctr, hits, &inf->redone, &kept))) return rc;  // (it waits: segs and colsrc are this frame's and the caller's)
+    if (kept) {
         inf->candidates = h_ctr[3];
-        *hits = h_ctr[0];
         return ZH_OK;
     }
-    // the pool ran over: nothing of the batch was counted (fjoin_survivors_kernel left at once); ownership does not depend on the path, so path 1
+    // the pool ran over: nothing of the batch was counted (pair_survivors_kernel left at once); ownership does not depend on the path, so path 1
     // over the same leaves counts exactly the batch's pairs
-    inf->redone++;
     if ((rc = fjoin_leaves1(ix, run, t, leaves.data(), leaves.size(), s, inf))) return rc;
     HIPCHK(hipMemcpyAsync(h_ctr, ctr, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -5428,7 +5378,7 @@ static int fjoin_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint6
         HIPCHK(hipStreamSynchronize(s));
         hits = h_ctr[0];
     }
-    return join_finish(ix, hits, capacity, outA, outB, outKeys, host_out, s, total, inf, &zh_index::fj_info, who);
+    return join_finish(ix, ix, hits, capacity, outA, outB, outKeys, host_out, s, total, inf, &zh_index::fj_info, who);
 }
 
 // an index without live rows has no pair: total 0 (and the info says so) whatever its trees; otherwise the forest graph's state checks

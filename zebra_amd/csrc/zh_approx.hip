@@ -29,8 +29,6 @@
 #include "zh_internal.h"
 #include "zh_device.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 // groups per wave by dimension (0: not supported -> exact scan): every lane loads NH = d * G / 512 dwordx4 of halves per pair
 #ifndef ZH_APX_G768
 #define ZH_APX_G768 2   // A/B: 4 = four 16-lane groups at d = 768 (48 row registers per lane)
@@ -440,8 +438,6 @@ void scan_approx_kernel(const float *__restrict__ X, const uint4 *__restrict__ Q
 // 32 products -- any order, any rounding of at most 2 u per operation gives |acc - sum| <= (33 D / 128 + 2) 2 u sum |xh_i h_i|
 // (zh_approx_bound's `ops`; MEASURED on the device, tests/test_gpu_intervals.py: <= 9.2 u where 400-532 u are assumed).  Rows whose scale is
 // out of range (or not finite) hand every pair the interval (-inf, +inf).
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 
 // The fp16 copy of the stored rows, written once (rows appended later: their own slots), in the A operand's own order: per tile of 16
 // rows and MFMA step s one KiB = lane (c, h)'s eight halves {row 16 tile + c, elements 32 s + 4 h + t and 32 s + 16 + 4 h + t}, so that a
@@ -552,7 +548,7 @@ extern "C" __attribute__((visibility("default"))) int zh_debug_scan_prof(uint64_
 #endif
 template <int D, bool F32ROWS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D > 768 ? 2 : ZH_MFMA_WAVES, D > 768 ? 2 : ZH_MFMA_WAVES)))
-void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ Xf, const float2 *__restrict__ rowMeta,
+void scan_mfma_kernel(const u32x4 *__restrict__ Xh, const float *__restrict__ Xf, const float2 *__restrict__ rowMeta,
                                                          const uint4 *__restrict__ Qh, const uint2 *__restrict__ rowLeaf, uint32_t T,
                                                          uint32_t RW, const uint32_t *__restrict__ visitBits,
                                                          const uint4 *__restrict__ nodeVisit, const ZhGroup *__restrict__ groups,
@@ -569,7 +565,7 @@ void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ X
     __shared__ uint64_t tile_list[4][ZH_APX_CAP];  // the same records grouped by tile of 16 columns; before that: the open-addressing table of the column pass (1024 words)
     __shared__ uint32_t col_query[4][ZH_APX_CAP];  // the query of every column (= distinct query of the wave's pairs)
     __shared__ uint32_t tile_start[4][36];         // pairs per tile -> exclusive scan
-    __shared__ f32x4v acc_lds[4][64];              // a tile's 16 x 16 products: [column][row]
+    __shared__ f32x4 acc_lds[4][64];              // a tile's 16 x 16 products: [column][row]
     // stage: a chunk of the tile's query halves, [line][column / 8][column % 8][16-byte piece, swizzled]: CL * 2 KiB per wave -- in pair_list's words, which are
     // done with when the tile loop starts (45 KB of LDS per block instead of 62: three blocks per CU fit)
     __shared__ float2 row_meta[4][16];          // {|x|^2, 1 / sigma_x (NaN: nothing is certain about this row)}
@@ -606,7 +602,7 @@ void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ X
     // ---- the wave's 16 rows: their fp16 copy, already in the A operand's order (row_half_kernel): D / 32 coalesced 1-KiB loads ----
     f16x8 A[NS];
     if constexpr (!F32ROWS) {
-        const u32x4v *tp = Xh + (size_t)(r0 >> 4) * (NS * 64) + lane;
+        const u32x4 *tp = Xh + (size_t)(r0 >> 4) * (NS * 64) + lane;
 #pragma unroll
         for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, __builtin_nontemporal_load(tp + 64 * st));
         if (lane < 16) row_meta[wid][lane] = rowMeta[r0 + (lane < nr ? lane : 0u)];
@@ -624,10 +620,10 @@ void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ X
         const float inv_c = row_meta[wid][c16].y;            // 1 / sigma of row c16 (NaN: unusable -> zeros, as the copy)
         const bool usable_c = inv_c - inv_c == 0.f;
         const float sigma_c = usable_c ? 1.0f / inv_c : 0.f; // (a power of two: exact)
-        f32x4v *xt = reinterpret_cast<f32x4v *>(tile_list[wid]);
-        const f32x4v *X4 = reinterpret_cast<const f32x4v *>(Xf);
+        f32x4 *xt = reinterpret_cast<f32x4 *>(tile_list[wid]);
+        const f32x4 *X4 = reinterpret_cast<const f32x4 *>(Xf);
         const uint32_t g4 = lane >> 4, p16 = lane & 15;
-        auto cvt8 = [&](const f32x4v lo, const f32x4v hi) {
+        auto cvt8 = [&](const f32x4 lo, const f32x4 hi) {
             f16x8 o;
 #pragma unroll
             for (int t = 0; t < 4; t++) {
@@ -636,7 +632,7 @@ void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ X
             }
             return o;
         };
-        f32x4v Rr[4];
+        f32x4 Rr[4];
         auto issue_rows = [&](int kb) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -657,7 +653,7 @@ void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ X
             if (kb + 1 < D / 64) issue_rows(kb + 1);
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++) {
-                const f32x4v lo = xt[c16 * 16 + ((8u * s2 + h) ^ c16)], hi = xt[c16 * 16 + ((8u * s2 + 4u + h) ^ c16)];
+                const f32x4 lo = xt[c16 * 16 + ((8u * s2 + h) ^ c16)], hi = xt[c16 * 16 + ((8u * s2 + 4u + h) ^ c16)];
                 A[2 * kb + s2] = cvt8(lo, hi);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -671,33 +667,33 @@ void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ X
     // path, not L2, set the pace: 6.9 ms per launch (profiles/r04_pmc_scan_mfma.txt, v1).  The lines pass
     // through the wave's own LDS chunk (written as loaded, pieces XOR-swizzled by column so that the fragment reads -- ds_read_b128, lane
     // (c, h) piece 4 (s & 1) + h of column c -- meet no bank twice within their 16-lane groups).
-    u32x4v *stg = reinterpret_cast<u32x4v *>(pair_list[wid]);  // (native vectors: HIP's uint4 struct copies global -> private -> LDS stayed memcpys in scratch memory)
-    const u32x4v *__restrict__ Qv = reinterpret_cast<const u32x4v *>(Qh);
+    u32x4 *stg = reinterpret_cast<u32x4 *>(pair_list[wid]);  // (native vectors: HIP's uint4 struct copies global -> private -> LDS stayed memcpys in scratch memory)
+    const u32x4 *__restrict__ Qv = reinterpret_cast<const u32x4 *>(Qh);
     const uint32_t g8 = lane >> 3, pc = lane & 7;
     const uint32_t swA = (g8 >> 1) & 7u, swB = (4u + (g8 >> 1)) & 7u;          // columns g8 and 8 + g8
     const uint32_t rd0 = (c16 >> 3) * 64u + (c16 & 7u) * 8u + ((h ^ (c16 >> 1)) & 7u);   // even steps: piece h
     const uint32_t rd1 = (c16 >> 3) * 64u + (c16 & 7u) * 8u + (((4u + h) ^ (c16 >> 1)) & 7u);
-    auto issue = [&](uint32_t bA, uint32_t bB, int chunk, u32x4v *dst) {
+    auto issue = [&](uint32_t bA, uint32_t bB, int chunk, u32x4 *dst) {
         if (!ZH_GUARD(bA < nq && bB < nq, 1u)) { bA = 0; bB = 0; }
-        const u32x4v *qa = Qv + (size_t)bA * (D / 8) + (size_t)(chunk * CL * 8) + (pc ^ swA);
-        const u32x4v *qb = Qv + (size_t)bB * (D / 8) + (size_t)(chunk * CL * 8) + (pc ^ swB);
+        const u32x4 *qa = Qv + (size_t)bA * (D / 8) + (size_t)(chunk * CL * 8) + (pc ^ swA);
+        const u32x4 *qb = Qv + (size_t)bB * (D / 8) + (size_t)(chunk * CL * 8) + (pc ^ swB);
 #pragma unroll
         for (int i = 0; i < CL; i++) { dst[2 * i] = qa[8 * i]; dst[2 * i + 1] = qb[8 * i]; }
     };
-    auto to_lds = [&](const u32x4v *src) {
+    auto to_lds = [&](const u32x4 *src) {
 #pragma unroll
         for (int i = 0; i < 2 * CL; i++) stg[64 * i + lane] = src[i];
     };
-    auto mfma_chunk = [&](int chunk, f32x4v *acc) {
+    auto mfma_chunk = [&](int chunk, f32x4 *acc) {
 #pragma unroll
         for (int i = 0; i < 2 * CL; i++) {  // step 2 CL chunk + i: line i / 2 of the chunk
-            const u32x4v v = stg[128 * (i / 2) + ((i & 1) ? rd1 : rd0)];
+            const u32x4 v = stg[128 * (i / 2) + ((i & 1) ? rd1 : rd0)];
             const int st = chunk * 2 * CL + i;
             acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, v), acc[st & 3], 0, 0, 0);
         }
     };
-    auto emit = [&](const f32x4v *acc, uint32_t rl, uint64_t slot, bool valid) {  // column c16 wants row rl: lane (c16, rl >> 2), register rl & 3
-        const f32x4v t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    auto emit = [&](const f32x4 *acc, uint32_t rl, uint64_t slot, bool valid) {  // column c16 wants row rl: lane (c16, rl >> 2), register rl & 3
+        const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
         if (valid && (rl >> 2) == h) {
             const uint32_t i = rl & 3u;
             const float sv = i == 0 ? t[0] : (i == 1 ? t[1] : (i == 2 ? t[2] : t[3]));
@@ -801,12 +797,12 @@ void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ X
         if (colStats && lane == 0 && (wave & 63u) == 0u) { atomicAdd(&colStats[0], nd); atomicAdd(&colStats[1], P); }
         auto col_b = [&](uint32_t t, uint32_t col) { const uint32_t ci = 16 * t + col; return colq[ci < nd ? ci : nd - 1]; };
         uint32_t bA = col_b(0, g8), bB = col_b(0, 8 + g8);
-        u32x4v ra[2 * CL], rb[2 * CL];
+        u32x4 ra[2 * CL], rb[2 * CL];
         issue(bA, bB, 0, ra);
         SP(__builtin_amdgcn_s_waitcnt(0); const uint64_t sp4 = clock64();)
-        f32x4v *al = acc_lds[wid];
+        f32x4 *al = acc_lds[wid];
         for (uint32_t t = 0; t < nt; t++) {
-            f32x4v acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
             for (int c = 0; c < NCH; c += 2) {
                 issue(bA, bB, c + 1, rb);
@@ -860,8 +856,8 @@ void scan_mfma_kernel(const u32x4v *__restrict__ Xh, const float *__restrict__ X
                     const uint32_t bA = visit_b(g8), bB = visit_b(8 + g8);
                     const uint32_t sidx = s0 + c16 < c ? s0 + c16 : c - 1;
                     const ZhGroup *gp = groups + gb + sidx / GRP;
-                    f32x4v acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-                    u32x4v rq[2 * CL];
+                    f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+                    u32x4 rq[2 * CL];
 #pragma unroll
                     for (int cc = 0; cc < NCH; cc++) {
                         issue(bA, bB, cc, rq);
@@ -887,10 +883,10 @@ static hipError_t launch_scan_mfma_d(const float *dX, uint64_t n_rows, const ZhA
         const uint64_t waves = (r_end - r + RW - 1) / RW, blocks = (waves + 3) / 4;
         if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
         if (ap.row_half)
-            hipLaunchKernelGGL((scan_mfma_kernel<D, false>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4v *)ap.row_half, dX, ap.row_meta, (const uint4 *)ap.Qh, dRowLeaf, T, RW,
+            hipLaunchKernelGGL((scan_mfma_kernel<D, false>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4 *)ap.row_half, dX, ap.row_meta, (const uint4 *)ap.Qh, dRowLeaf, T, RW,
                                dVisitBits, dNodeVisit, dGroups, group, r, r_end, ap.iv, ap.ctl + 5, ap.n_queries, ap.iv_cap, ap.ctl + 7);
         else  // no fp16 copy (no room for it): the scan converts the f32 rows itself (rows in id order)
-            hipLaunchKernelGGL((scan_mfma_kernel<D, true>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4v *)nullptr, dX, ap.row_meta, (const uint4 *)ap.Qh, dRowLeaf, T, RW,
+            hipLaunchKernelGGL((scan_mfma_kernel<D, true>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4 *)nullptr, dX, ap.row_meta, (const uint4 *)ap.Qh, dRowLeaf, T, RW,
                                dVisitBits, dNodeVisit, dGroups, group, r, r_end, ap.iv, ap.ctl + 5, ap.n_queries, ap.iv_cap, ap.ctl + 7);
     }
     return hipGetLastError();
@@ -1011,12 +1007,12 @@ __global__ __launch_bounds__(256)
 #if ZH_S128H_WAVES
 __attribute__((amdgpu_waves_per_eu(ZH_S128H_WAVES, ZH_S128H_WAVES)))
 #endif
-void sweep128h_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restrict__ Qh, float inv,
+void sweep128h_kernel(const u32x4 *__restrict__ Xh, const u32x4 *__restrict__ Qh, float inv,
                                                          const ZhGroup *__restrict__ groups, const uint64_t *__restrict__ groupRowOff,
                                                          uint64_t n_groups, const uint32_t *__restrict__ waveGroup,
                                                          const uint32_t *__restrict__ leaf_ids, uint64_t row_begin, uint64_t R_grouped,
                                                          uint64_t *__restrict__ iv) {
-    __shared__ u32x4v rows_lds[4][16 * 16];  // per wave: ONE tile = 16 rows x 16 pieces of 16 bytes, piece p of row R at R * 16 + (p ^ R)
+    __shared__ u32x4 rows_lds[4][16 * 16];  // per wave: ONE tile = 16 rows x 16 pieces of 16 bytes, piece p of row R at R * 16 + (p ^ R)
     const uint32_t lane = threadIdx.x & 63, c16 = lane & 15, h = lane >> 4;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wid;
@@ -1025,7 +1021,7 @@ void sweep128h_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restrict__ 
     uint32_t cnt = (uint32_t)(R_grouped - r0 < 64 ? R_grouped - r0 : 64);
     uint32_t my_g, my_id, my_within, my_off, my_len;
     resolve_flat_rows(r0, cnt, lane, groups, groupRowOff, n_groups, waveGroup, leaf_ids, my_g, my_id, my_within, &my_off, &my_len);
-    u32x4v *tl = rows_lds[wid];
+    u32x4 *tl = rows_lds[wid];
     f16x8 Aq[4];
 #pragma unroll
     for (int st = 0; st < 4; st++) Aq[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
@@ -1033,7 +1029,7 @@ void sweep128h_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restrict__ 
     // a tile's rows, whole: instruction i = the tile's rows 4 i .. 4 i + 3, lane (h, c16) the 16-byte piece c16 of row 4 i + h.  ONE register
     // set: once a tile is written to LDS its registers take the next tile's loads (across chunk boundaries, where the next chunk's rows
     // are known), which travel while this tile is multiplied.
-    u32x4v R[4];
+    u32x4 R[4];
     uint32_t c_rg = 0xFFFFFFFFu, c_hi = 0, c_lo[4] = {0, 0, 0, 0};  // the group record this lane's column last stored through: group, key_off[0..3] (low words; high nibbles | gsize << 16)
     auto issue_tile = [&](uint32_t ids, uint32_t n, uint32_t t) {  // flat rows 16 t .. 16 t + 15 of a chunk of n rows whose ids the lanes hold
 #pragma unroll
@@ -1109,14 +1105,14 @@ void sweep128h_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restrict__ 
                     const uint32_t b = on ? groups[grp].b[c16 & 3u] : 0u;
 #pragma unroll
                     for (int st = 0; st < 4; st++) {
-                        const u32x4v v = Qh[(size_t)b * 16 + 4 * st + h];
+                        const u32x4 v = Qh[(size_t)b * 16 + 4 * st + h];
                         Aq[st] = on ? __builtin_bit_cast(f16x8, v) : f16x8{0, 0, 0, 0, 0, 0, 0, 0};
                     }
                 }
-                f32x4v acc[4];
+                f32x4 acc[4];
 #pragma unroll
-                for (int st = 0; st < 4; st++) acc[st] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[st], Bf[st], f32x4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                const f32x4v dsum = (acc[0] + acc[1]) + (acc[2] + acc[3]);  // [i] = query slot i of group gp + h against stored row c16 of the tile
+                for (int st = 0; st < 4; st++) acc[st] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[st], Bf[st], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                const f32x4 dsum = (acc[0] + acc[1]) + (acc[2] + acc[3]);  // [i] = query slot i of group gp + h against stored row c16 of the tile
                 if (fr < cnt && rg == gp + h) {
                     const uint32_t a2b = __float_as_uint(a2 * inv * inv);
 #pragma unroll
@@ -1152,12 +1148,12 @@ void sweep128h_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restrict__ 
 // chunk's ids, a new group's record: rare) only makes those waits stricter.
 #define ZH_DMA16(src, dst) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src), (__attribute__((address_space(3))) void *)(dst), 16, 0, 0)
 template <int CH>
-__global__ __launch_bounds__(256) void sweep128h_dma_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restrict__ Qh, float inv,
+__global__ __launch_bounds__(256) void sweep128h_dma_kernel(const u32x4 *__restrict__ Xh, const u32x4 *__restrict__ Qh, float inv,
                                                              const ZhGroup *__restrict__ groups, const uint64_t *__restrict__ groupRowOff,
                                                              uint64_t n_groups, const uint32_t *__restrict__ waveGroup,
                                                              const uint32_t *__restrict__ leaf_ids, uint64_t row_begin, uint64_t R_grouped,
                                                              uint64_t *__restrict__ iv) {
-    __shared__ u32x4v rows_lds[4][2][16 * 16];  // per wave: TWO tiles = 16 rows x 16 pieces of 16 bytes, piece p of row R at R * 16 + (p ^ R)
+    __shared__ u32x4 rows_lds[4][2][16 * 16];  // per wave: TWO tiles = 16 rows x 16 pieces of 16 bytes, piece p of row R at R * 16 + (p ^ R)
     __shared__ uint32_t ids_lds[4][64];         // per wave: the next chunk's row ids (requested the same way: no wait of the compiler's for them)
     const uint32_t lane = threadIdx.x & 63, c16 = lane & 15, h = lane >> 4;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1188,7 +1184,7 @@ __global__ __launch_bounds__(256) void sweep128h_dma_kernel(const u32x4v *__rest
             if (!N_known) return;
             I_ids = N_ids; I_cnt = N_cnt; I_t = 0; N_known = false;
         }
-        u32x4v *dst = rows_lds[wid][issued & 1u];
+        u32x4 *dst = rows_lds[wid][issued & 1u];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const uint32_t rr = 4u * i + h, fr = 16u * I_t + rr;
@@ -1232,7 +1228,7 @@ __global__ __launch_bounds__(256) void sweep128h_dma_kernel(const u32x4v *__rest
             f16x8 Bf[4];
             {
                 const uint32_t ta = tile_addr + (consumed & 1u) * 4096u;
-                u32x4v f0, f1, f2, f3;
+                u32x4 f0, f1, f2, f3;
                 asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\ts_waitcnt lgkmcnt(0)"
                              : "=&v"(f0), "=&v"(f1), "=&v"(f2), "=&v"(f3)
                              : "v"(ta + frag_off[0]), "v"(ta + frag_off[1]), "v"(ta + frag_off[2]), "v"(ta + frag_off[3]) : "memory");
@@ -1268,14 +1264,14 @@ __global__ __launch_bounds__(256) void sweep128h_dma_kernel(const u32x4v *__rest
                     const uint32_t b = on ? groups[grp].b[c16 & 3u] : 0u;
 #pragma unroll
                     for (int st = 0; st < 4; st++) {
-                        const u32x4v v = Qh[(size_t)b * 16 + 4 * st + h];
+                        const u32x4 v = Qh[(size_t)b * 16 + 4 * st + h];
                         Aq[st] = on ? __builtin_bit_cast(f16x8, v) : f16x8{0, 0, 0, 0, 0, 0, 0, 0};
                     }
                 }
-                f32x4v acc[4];
+                f32x4 acc[4];
 #pragma unroll
-                for (int st = 0; st < 4; st++) acc[st] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[st], Bf[st], f32x4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                const f32x4v dsum = (acc[0] + acc[1]) + (acc[2] + acc[3]);  // [i] = query slot i of group gp + h against stored row c16 of the tile
+                for (int st = 0; st < 4; st++) acc[st] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[st], Bf[st], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                const f32x4 dsum = (acc[0] + acc[1]) + (acc[2] + acc[3]);  // [i] = query slot i of group gp + h against stored row c16 of the tile
                 if (fr < cnt && rg == gp + h) {
                     const uint32_t a2b = __float_as_uint(a2 * inv * inv);
 #pragma unroll
@@ -1458,7 +1454,7 @@ __device__ __forceinline__ uint32_t row_newbcast(uint32_t v) {  // every lane: t
 }
 // the four row-load instructions of tile T of a chunk whose ids the lanes hold as lane (h, c) = flat row 4 c + h: instruction i = rows 4 (4 T + i) + h
 template <int T>
-__device__ __forceinline__ void issue_lean_tile(const u32x4v *__restrict__ Xh, uint32_t ids, uint32_t c16, u32x4v (&R)[4]) {
+__device__ __forceinline__ void issue_lean_tile(const u32x4 *__restrict__ Xh, uint32_t ids, uint32_t c16, u32x4 (&R)[4]) {
     R[0] = __builtin_nontemporal_load(Xh + (size_t)row_newbcast<4 * T + 0>(ids) * 16 + c16);
     R[1] = __builtin_nontemporal_load(Xh + (size_t)row_newbcast<4 * T + 1>(ids) * 16 + c16);
     R[2] = __builtin_nontemporal_load(Xh + (size_t)row_newbcast<4 * T + 2>(ids) * 16 + c16);
@@ -1490,18 +1486,18 @@ __device__ __forceinline__ bool chunk_segments(uint64_t r0, uint32_t cnt, const 
 // FUSE >= 0 (= approx_interval's KINDA): the FUSED form -- see "the fused sweep" below; FUSE < 0: raw pairs to iv for select_tau_kernel
 template <int CH, int FUSE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FUSE >= 0 ? 4 : ZH_S128L_WAVES, FUSE >= 0 ? 4 : ZH_S128L_WAVES)))
-void sweep128h_lean_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restrict__ Qh, float inv,
+void sweep128h_lean_kernel(const u32x4 *__restrict__ Xh, const u32x4 *__restrict__ Qh, float inv,
                            const ZhGroup *__restrict__ groups, const uint64_t *__restrict__ groupRowOff,
                            uint64_t n_groups, const uint32_t *__restrict__ waveGroup,
                            const uint32_t *__restrict__ leaf_ids, uint64_t row_begin, uint64_t R_grouped,
                            uint64_t *__restrict__ iv, ZhApprox ap, uint32_t k_top, float Kc) {
-    __shared__ u32x4v rows_lds[4][16 * 16];  // per wave: ONE tile = 16 rows x 16 pieces of 16 bytes, piece p of row R at R * 16 + (p ^ R)
+    __shared__ u32x4 rows_lds[4][16 * 16];  // per wave: ONE tile = 16 rows x 16 pieces of 16 bytes, piece p of row R at R * 16 + (p ^ R)
     const uint32_t lane = threadIdx.x & 63, c16 = lane & 15, h = lane >> 4;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wid;
     const uint64_t r_first = row_begin + wave * (64 * CH);
     if (r_first >= R_grouped) return;
-    u32x4v *tl = rows_lds[wid];
+    u32x4 *tl = rows_lds[wid];
     f16x8 Aq[4];
 #pragma unroll
     for (int st = 0; st < 4; st++) Aq[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
@@ -1509,7 +1505,7 @@ void sweep128h_lean_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restri
     const float inv2 = inv * inv;
     const uint32_t diag_src = (((c16 >> 2) << 4) | c16) << 2;  // ds_bpermute address of lane (c16, c16 >> 2): where G[c16][c16] lives
     const bool c_odd = (c16 & 1u) != 0, c_up = (c16 & 2u) != 0;  // which of a lane's four Gram entries sits on the diagonal: register c16 & 3
-    u32x4v R[4];
+    u32x4 R[4];
     // fused form: per slot, the top_k smallest hi of the visit's rows this wave has seen (lane i the i-th; reset when the group changes), and where
     // flat row `lane` of a chunk finds its id (lane (h, c16) holds row 4 c16 + h)
     uint32_t topv[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
@@ -1549,7 +1545,7 @@ void sweep128h_lean_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restri
             const uint32_t b = on ? gr->b[c16 & 3u] : 0u;
 #pragma unroll
             for (int st = 0; st < 4; st++) {
-                const u32x4v v = Qh[(size_t)b * 16 + 4 * st + h];
+                const u32x4 v = Qh[(size_t)b * 16 + 4 * st + h];
                 Aq[st] = on ? __builtin_bit_cast(f16x8, v) : f16x8{0, 0, 0, 0, 0, 0, 0, 0};
             }
         }
@@ -1583,7 +1579,7 @@ void sweep128h_lean_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restri
             for (int st = 0; st < 4; st++) Bf[st] = __builtin_bit_cast(f16x8, tl[c16 * 16 + ((4u * st + h) ^ c16)]);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            f32x4v dsum = {0.f, 0.f, 0.f, 0.f}, gram = {0.f, 0.f, 0.f, 0.f};
+            f32x4 dsum = {0.f, 0.f, 0.f, 0.f}, gram = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int st = 0; st < 4; st++) {
                 dsum = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[st], Bf[st], dsum, 0, 0, 0);
@@ -1649,7 +1645,7 @@ void sweep128h_lean_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restri
 //     + ((c16 >> 1) & 3) of the chunk: a fixed permutation inside each 16 -- ids, key positions and raw runs are addressed through it.
 // inv = 1: the rows are their own values (no table scale); |x|^2 is exact.
 template <int T>
-__device__ __forceinline__ void issue_byte_tile(const u32x4v *__restrict__ Xb, uint32_t ids, uint32_t p8, bool sub, u32x4v (&R)[4]) {
+__device__ __forceinline__ void issue_byte_tile(const u32x4 *__restrict__ Xb, uint32_t ids, uint32_t p8, bool sub, u32x4 (&R)[4]) {
     // (every broadcast with ALL lanes active -- a DPP read of a lane that is switched off returns zero -- and only then the choice)
     const uint32_t e0 = row_newbcast<8 * T + 0>(ids), o0 = row_newbcast<8 * T + 1>(ids), e1 = row_newbcast<8 * T + 2>(ids), o1 = row_newbcast<8 * T + 3>(ids);
     const uint32_t e2 = row_newbcast<8 * T + 4>(ids), o2 = row_newbcast<8 * T + 5>(ids), e3 = row_newbcast<8 * T + 6>(ids), o3 = row_newbcast<8 * T + 7>(ids);
@@ -1664,19 +1660,19 @@ __device__ __forceinline__ void issue_byte_tile(const u32x4v *__restrict__ Xb, u
 #endif
 template <int CH, int FUSE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ZH_S128B_WAVES, ZH_S128B_WAVES)))
-void sweep128b_lean_kernel(const u32x4v *__restrict__ Xb, const u32x4v *__restrict__ Qh,
+void sweep128b_lean_kernel(const u32x4 *__restrict__ Xb, const u32x4 *__restrict__ Qh,
                            const ZhGroup *__restrict__ groups, const uint64_t *__restrict__ groupRowOff,
                            uint64_t n_groups, const uint32_t *__restrict__ waveGroup,
                            const uint32_t *__restrict__ leaf_ids, uint64_t row_begin, uint64_t R_grouped,
                            uint64_t *__restrict__ iv, ZhApprox ap, uint32_t k_top, float Kc) {
-    __shared__ u32x4v rows_lds[4][32 * 8];  // per wave: ONE double tile = 32 image rows x 8 pieces of 16 bytes
+    __shared__ u32x4 rows_lds[4][32 * 8];  // per wave: ONE double tile = 32 image rows x 8 pieces of 16 bytes
     const uint32_t lane = threadIdx.x & 63, c16 = lane & 15, h = lane >> 4, p8 = c16 & 7u;
     const bool sub = (c16 & 8u) != 0;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wid;
     const uint64_t r_first = row_begin + wave * (64 * CH);
     if (r_first >= R_grouped) return;
-    u32x4v *tl = rows_lds[wid];
+    u32x4 *tl = rows_lds[wid];
     f16x8 Aq[4];
 #pragma unroll
     for (int st = 0; st < 4; st++) Aq[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
@@ -1693,7 +1689,7 @@ void sweep128b_lean_kernel(const u32x4v *__restrict__ Xb, const u32x4v *__restri
         wr_at[i] = J * 8 + (p8 ^ ((J >> 1) & 7u));
     }
     const uint32_t rd_sw = (c16 >> 1) & 7u, rd0 = c16 * 8 + ((2u * h) ^ rd_sw), rd1 = c16 * 8 + ((2u * h + 1u) ^ rd_sw);
-    u32x4v R[4];
+    u32x4 R[4];
     uint32_t topv[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
     float pre[4][3] = {{0.f, 0.f, -1.f}, {0.f, 0.f, -1.f}, {0.f, 0.f, -1.f}, {0.f, 0.f, -1.f}};  // (fused_pretest_setup, per group)
     bool carried = false;
@@ -1730,7 +1726,7 @@ void sweep128b_lean_kernel(const u32x4v *__restrict__ Xb, const u32x4v *__restri
             const uint32_t b = on ? gr->b[c16 & 3u] : 0u;
 #pragma unroll
             for (int st = 0; st < 4; st++) {
-                const u32x4v v = Qh[(size_t)b * 16 + 4 * h + st];
+                const u32x4 v = Qh[(size_t)b * 16 + 4 * h + st];
                 Aq[st] = on ? __builtin_bit_cast(f16x8, v) : f16x8{0, 0, 0, 0, 0, 0, 0, 0};
             }
         }
@@ -1751,14 +1747,14 @@ void sweep128b_lean_kernel(const u32x4v *__restrict__ Xb, const u32x4v *__restri
             __builtin_amdgcn_wave_barrier();
             if constexpr (T == 0) issue_byte_tile<1>(Xb, ids, p8, sub, R);
             else if (next_fast) issue_byte_tile<0>(Xb, nxt_ids, p8, sub, R);
-            const u32x4v v00 = tl[rd0], v01 = tl[rd1], v10 = tl[128 + rd0], v11 = tl[128 + rd1];
+            const u32x4 v00 = tl[rd0], v01 = tl[rd1], v10 = tl[128 + rd0], v11 = tl[128 + rd1];
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int m = 0; m < 2; m++) {
-                const u32x4v v0 = m ? v10 : v00, v1 = m ? v11 : v01;
+                const u32x4 v0 = m ? v10 : v00, v1 = m ? v11 : v01;
                 const f16x8 Bf[4] = {bytes8_to_f16(v0[0], v0[1]), bytes8_to_f16(v0[2], v0[3]), bytes8_to_f16(v1[0], v1[1]), bytes8_to_f16(v1[2], v1[3])};
-                f32x4v dsum = {0.f, 0.f, 0.f, 0.f}, gram = {0.f, 0.f, 0.f, 0.f};
+                f32x4 dsum = {0.f, 0.f, 0.f, 0.f}, gram = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int st = 0; st < 4; st++) {
                     dsum = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[st], Bf[st], dsum, 0, 0, 0);
@@ -1809,12 +1805,12 @@ void sweep128b_lean_kernel(const u32x4v *__restrict__ Xb, const u32x4v *__restri
 // works through the ones that are its business; |x^|^2 from the Gram diagonal here too.  BYTES: Xh is row_byte128_kernel's copy (a 16-row tile
 // is two load instructions: image row J = 8 i + 2 h + sub = the tile's row J, the image and the K order as in sweep128b_lean_kernel; inv = 1).
 template <int FUSE, bool BYTES>
-__global__ __launch_bounds__(256) void sweep128h_boundary_kernel(const u32x4v *__restrict__ Xh, const u32x4v *__restrict__ Qh, float inv,
+__global__ __launch_bounds__(256) void sweep128h_boundary_kernel(const u32x4 *__restrict__ Xh, const u32x4 *__restrict__ Qh, float inv,
                                                                   const ZhGroup *__restrict__ groups, const uint64_t *__restrict__ groupRowOff,
                                                                   uint64_t n_groups, const uint32_t *__restrict__ waveGroup,
                                                                   const uint32_t *__restrict__ leaf_ids, uint64_t row_begin, uint64_t R_grouped,
                                                                   uint64_t *__restrict__ iv, ZhApprox ap, uint32_t k_top, float Kc) {
-    __shared__ u32x4v rows_lds[4][16 * 16];
+    __shared__ u32x4 rows_lds[4][16 * 16];
     const uint32_t lane = threadIdx.x & 63, c16 = lane & 15, h = lane >> 4;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wid;
@@ -1832,7 +1828,7 @@ __global__ __launch_bounds__(256) void sweep128h_boundary_kernel(const u32x4v *_
         todo = __ballot(mine);
     }
     if (!todo) return;
-    u32x4v *tl = rows_lds[wid];
+    u32x4 *tl = rows_lds[wid];
     const float inv2 = inv * inv;
     const uint32_t diag_src = (((c16 >> 2) << 4) | c16) << 2;
     const bool c_odd = (c16 & 1u) != 0, c_up = (c16 & 2u) != 0;
@@ -1840,7 +1836,7 @@ __global__ __launch_bounds__(256) void sweep128h_boundary_kernel(const u32x4v *_
 #pragma unroll
     for (int st = 0; st < 4; st++) Aq[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t a_g0 = 0xFFFFFFFFu;  // A holds groups a_g0 .. a_g0 + 3: row m = slot m & 3 of group a_g0 + (m >> 2)
-    u32x4v R[4];
+    u32x4 R[4];
     while (todo) {
         const uint32_t bit = (uint32_t)__builtin_ctzll(todo);
         todo &= todo - 1;
@@ -1906,7 +1902,7 @@ __global__ __launch_bounds__(256) void sweep128h_boundary_kernel(const u32x4v *_
             f16x8 Bf[4];
             if constexpr (BYTES) {
                 const uint32_t sw = (c16 >> 1) & 7u;
-                const u32x4v v0 = tl[c16 * 8 + ((2u * h) ^ sw)], v1 = tl[c16 * 8 + ((2u * h + 1u) ^ sw)];
+                const u32x4 v0 = tl[c16 * 8 + ((2u * h) ^ sw)], v1 = tl[c16 * 8 + ((2u * h + 1u) ^ sw)];
                 Bf[0] = bytes8_to_f16(v0[0], v0[1]); Bf[1] = bytes8_to_f16(v0[2], v0[3]);
                 Bf[2] = bytes8_to_f16(v1[0], v1[1]); Bf[3] = bytes8_to_f16(v1[2], v1[3]);
             } else {
@@ -1918,7 +1914,7 @@ __global__ __launch_bounds__(256) void sweep128h_boundary_kernel(const u32x4v *_
             const uint32_t last = 16 * t + 15 < cnt ? 16 * t + 15 : cnt - 1;
             const uint32_t g_first = (uint32_t)__builtin_amdgcn_readlane((int)my_g, (int)(16 * t));
             const uint32_t g_last = (uint32_t)__builtin_amdgcn_readlane((int)my_g, (int)last);
-            f32x4v gram = {0.f, 0.f, 0.f, 0.f};
+            f32x4 gram = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int st = 0; st < 4; st++) gram = __builtin_amdgcn_mfma_f32_16x16x32_f16(Bf[st], Bf[st], gram, 0, 0, 0);
             const float dg_lo = c_odd ? gram[1] : gram[0], dg_hi = c_odd ? gram[3] : gram[2], dg = c_up ? dg_hi : dg_lo;
@@ -1931,11 +1927,11 @@ __global__ __launch_bounds__(256) void sweep128h_boundary_kernel(const u32x4v *_
                     const uint32_t b = on ? groups[grp].b[c16 & 3u] : 0u;
 #pragma unroll
                     for (int st = 0; st < 4; st++) {
-                        const u32x4v v = Qh[(size_t)b * 16 + (BYTES ? 4 * h + st : 4 * st + h)];
+                        const u32x4 v = Qh[(size_t)b * 16 + (BYTES ? 4 * h + st : 4 * st + h)];
                         Aq[st] = on ? __builtin_bit_cast(f16x8, v) : f16x8{0, 0, 0, 0, 0, 0, 0, 0};
                     }
                 }
-                f32x4v dsum = {0.f, 0.f, 0.f, 0.f};
+                f32x4 dsum = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int st = 0; st < 4; st++) dsum = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[st], Bf[st], dsum, 0, 0, 0);
                 if (fr < cnt && rg == gp + h) {
@@ -2025,16 +2021,16 @@ static void launch_sweep128h_lean(const void *dXh, const void *dQh, float inv, c
         constexpr int CHL = FUSE >= 0 ? (BYTES ? ZH_S128B_CH : ZH_S128F_CH) : ZH_S128L_CH;
         const uint64_t wl = (r_end - r + 64 * CHL - 1) / (64 * CHL);
         if constexpr (BYTES)
-            hipLaunchKernelGGL((sweep128b_lean_kernel<CHL, FUSE>), dim3((uint32_t)((wl + 3) / 4)), dim3(256), 0, s, (const u32x4v *)dXh,
-                               (const u32x4v *)dQh, dGroups, dGroupRowOff, n_groups, dWaveGroup, dLeafIds, r, r_end, dIv, ap, k_top, Kc);
+            hipLaunchKernelGGL((sweep128b_lean_kernel<CHL, FUSE>), dim3((uint32_t)((wl + 3) / 4)), dim3(256), 0, s, (const u32x4 *)dXh,
+                               (const u32x4 *)dQh, dGroups, dGroupRowOff, n_groups, dWaveGroup, dLeafIds, r, r_end, dIv, ap, k_top, Kc);
         else
-            hipLaunchKernelGGL((sweep128h_lean_kernel<CHL, FUSE>), dim3((uint32_t)((wl + 3) / 4)), dim3(256), 0, s, (const u32x4v *)dXh,
-                               (const u32x4v *)dQh, inv, dGroups, dGroupRowOff, n_groups, dWaveGroup, dLeafIds, r, r_end, dIv, ap, k_top, Kc);
+            hipLaunchKernelGGL((sweep128h_lean_kernel<CHL, FUSE>), dim3((uint32_t)((wl + 3) / 4)), dim3(256), 0, s, (const u32x4 *)dXh,
+                               (const u32x4 *)dQh, inv, dGroups, dGroupRowOff, n_groups, dWaveGroup, dLeafIds, r, r_end, dIv, ap, k_top, Kc);
     }
     // the chunks of three or more groups, of the WHOLE batch in one launch (a launch of its own per 25M rows was 0.04-0.06 ms each): a wave
     // looks at 64 chunks.  Chunk boundaries are absolute (every launch above starts on a multiple of 256 rows), so both kernels see the same chunks
     const uint64_t bw = ((R_grouped + 63) / 64 + 63) / 64, bb = (bw + 3) / 4;
-    hipLaunchKernelGGL((sweep128h_boundary_kernel<FUSE, BYTES>), dim3((uint32_t)bb), dim3(256), 0, s, (const u32x4v *)dXh, (const u32x4v *)dQh, inv, dGroups,
+    hipLaunchKernelGGL((sweep128h_boundary_kernel<FUSE, BYTES>), dim3((uint32_t)bb), dim3(256), 0, s, (const u32x4 *)dXh, (const u32x4 *)dQh, inv, dGroups,
                        dGroupRowOff, n_groups, dWaveGroup, dLeafIds, (uint64_t)0, R_grouped, dIv, ap, k_top, Kc);
 }
 // fuse: null = the raw pairs go to dIv for select_tau_kernel / select_emit_kernel; else the FUSED sweep (intervals, bounds and the queries' lists
@@ -2075,10 +2071,10 @@ hipError_t zh_launch_sweep128h(const void *dXh, const void *dQh, float inv, cons
         const uint64_t r_end = r + rows_per_launch < R_grouped ? r + rows_per_launch : R_grouped;
         const uint64_t w = (r_end - r + 64 * CH - 1) / (64 * CH), blocks = (w + 3) / 4;
         if (!dma)
-            hipLaunchKernelGGL((sweep128h_kernel<CH>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4v *)dXh, (const u32x4v *)dQh, inv, dGroups,
+            hipLaunchKernelGGL((sweep128h_kernel<CH>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4 *)dXh, (const u32x4 *)dQh, inv, dGroups,
                                dGroupRowOff, n_groups, dWaveGroup, dLeafIds, r, r_end, dIv);
         else
-            hipLaunchKernelGGL((sweep128h_dma_kernel<CH>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4v *)dXh, (const u32x4v *)dQh, inv, dGroups,
+            hipLaunchKernelGGL((sweep128h_dma_kernel<CH>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4 *)dXh, (const u32x4 *)dQh, inv, dGroups,
                                dGroupRowOff, n_groups, dWaveGroup, dLeafIds, r, r_end, dIv);
     }
     return hipGetLastError();

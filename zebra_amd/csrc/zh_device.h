@@ -1,12 +1,17 @@
 // zh_device.h -- device helpers shared by the kernel translation units (zh_search.hip, zh_approx.hip): the canonical
 // butterflies and sums, key finalisers, row loads, the LDS bitonic sort and the select partition.  Moved verbatim out of
-// zh_search.hip in round 4 so that the half-width scan compiles on its own.
+// zh_search.hip in round 4 so that the half-width scan compiles on its own.  Since then also the matrix-core vector types of
+// every scan and, at the end, the pair pool's helpers (range search, forest range search, the three joins).
 #pragma once
 #include "zh_internal.h"
 
 #define WAVE 64
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+// v_mfma_f32_16x16x32_f16's operands and result, and the 16-byte piece every fp16 tile is moved in
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------
 // small helpers
@@ -243,7 +248,6 @@ struct RowVec {
     static constexpr int NV = NJ + (REM4 ? 1 : 0);
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 template <bool NT>
 __device__ __forceinline__ float4 ld16(const float4 *p) {
     if (NT) {  // streamed once: non-temporal hint (global_load_dwordx4 ... nt)
@@ -522,4 +526,61 @@ __device__ __forceinline__ void resolve_flat_rows(uint64_t r0, uint32_t cnt, uin
     if (my_leaf_off) *my_leaf_off = lo_off;
     if (my_len) *my_len = groups[lo].len;
     my_id = leaf_ids ? leaf_ids[(size_t)lo_off + my_within] : lo_off + my_within;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the pair pool: what range search, forest range search and the three joins share.  A hit is (left << 32 | right, key), appended to ONE pool per
+// call or internal batch and counted whether or not the pool still has room, so the total stays exact when the caller's capacity is too small.
+// ------------------------------------------------------------------------------------------------
+// The lanes of `m` (a ballot) get consecutive pool slots: one atomic for the WAVE, taken by lane 0 (every lane of the wave is active at the call), not
+// one per hit.  The counter runs on past the pool: the caller stores only where slot < cap, and *ctr is the exact count afterwards.
+__device__ __forceinline__ unsigned long long wave_slots(unsigned long long *__restrict__ ctr, uint64_t m, uint32_t lane) {
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(ctr, (unsigned long long)__popcll(m));
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
+    return (((unsigned long long)hi << 32) | lo) + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+}
+
+// the radix sorts' width of a field (host side): bits that hold 0 .. values - 1
+static inline int field_bits(uint64_t values) {
+    int b = 1;
+    while (b < 32 && (1ull << b) < values) b++;
+    return b;
+}
+
+// The canonical sums of STORED row `row` of table XB against QUERY row `qrow` of table XA, both f32 (the survivors kernels: one wave, every lane
+// active).  s0 / s1 are key_of's sums: for the cosine s1 is the stored row's squared norm and, where QQ asks for it, qq the query row's -- both
+// qnorm_kernel's canonical sum.  XA and XB may be one table: both are only read.
+template <int D, int KIND, bool QQ>
+__device__ __forceinline__ void table_pair_sums(const float *__restrict__ XB, uint32_t row, const float *__restrict__ XA, uint32_t qrow, uint32_t lane,
+                                                int param, float &s0, float &s1, float &qq) {
+    constexpr int NV = RowVec<D>::NV;
+    float4 v[NV], q[NV];
+    load_row<D>(XB + (size_t)row * D, lane, v);
+    load_row<D>(XA + (size_t)qrow * D, lane, q);
+    row_pair_sums<D, KIND>(v, q, lane, param, s0, s1);
+    if (KIND == K_COS) {
+        float4 c = make_float4(0.f, 0.f, 0.f, 0.f), cq = c;
+#pragma unroll
+        for (int jj = 0; jj < NV; jj++) {
+            const bool act = (jj < RowVec<D>::NJ) || (lane < (uint32_t)RowVec<D>::REM4);
+            if (act) {
+                sq4(v[jj], c);
+                if (QQ) sq4(q[jj], cq);
+            }
+        }
+        s1 = wave_sum_canonical((c.x + c.y) + (c.z + c.w));
+        if (QQ) qq = wave_sum_canonical((cq.x + cq.y) + (cq.z + cq.w));
+    }
+}
+
+// the forest join's first-tree rule: tree t owns the pair (a, b) when no earlier tree holds both rows in one leaf (leaf_of: zh_fjoin.hip)
+__device__ __forceinline__ bool fjoin_owned(const uint32_t *__restrict__ leaf_of, uint32_t T, uint32_t t, uint32_t a, uint32_t b) {
+    const uint32_t *la = leaf_of + (size_t)a * T, *lb = leaf_of + (size_t)b * T;
+    for (uint32_t u = 0; u < t; u++) {
+        const uint32_t x = la[u];
+        if (x != 0xFFFFFFFFu && x == lb[u]) return false;
+    }
+    return true;
 }

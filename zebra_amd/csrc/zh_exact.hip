@@ -197,18 +197,14 @@ hipError_t zh_launch_exact_empty(uint32_t B, uint32_t k, uint64_t *dIds, uint64_
 // no row tied with the k-th key is ever dropped; the survivors get the canonical key and final_kernel ranks them by (key, id).  A list that runs
 // over raises *over: the host answers that internal batch by path 1.
 // ------------------------------------------------------------------------------------------------
-typedef _Float16 f16x8e __attribute__((ext_vector_type(8)));
-typedef float f32x4e __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4e __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ bool exact_live(const uint32_t *__restrict__ bits, uint32_t id) { return (bits[id >> 5] >> (id & 31)) & 1u; }
 
 // FILT (the filtered search): liveBits is the allowed-and-live bitmap by POSITION (a tile's 16 positions are half a word of it), and a wave whose
 // tile is masked whole returns before it loads anything and counts itself in over[1]
 template <int D, int KINDA, bool FILT>
-__global__ __launch_bounds__(256) void exact_mfma_kernel(const u32x4e *__restrict__ Xh, const float2 *__restrict__ rowMeta,
+__global__ __launch_bounds__(256) void exact_mfma_kernel(const u32x4 *__restrict__ Xh, const float2 *__restrict__ rowMeta,
                                                          const uint32_t *__restrict__ perm, uint64_t perm_rows, const uint32_t *__restrict__ liveBits,
-                                                         uint64_t p_begin, uint64_t p_end, const u32x4e *__restrict__ Qh,
+                                                         uint64_t p_begin, uint64_t p_end, const u32x4 *__restrict__ Qh,
                                                          const float4 *__restrict__ qmeta, uint32_t B, float Kc, float rho,
                                                          const uint32_t *__restrict__ tau, uint32_t *__restrict__ cnt, uint32_t *__restrict__ lid,
                                                          uint32_t *__restrict__ llo, uint32_t *__restrict__ lhi, uint32_t cap, uint32_t *__restrict__ over) {
@@ -224,10 +220,10 @@ __global__ __launch_bounds__(256) void exact_mfma_kernel(const u32x4e *__restric
             return;
         }
     }
-    f16x8e A[NS];
-    const u32x4e *tp = Xh + (size_t)tile * (NS * 64) + lane;
+    f16x8 A[NS];
+    const u32x4 *tp = Xh + (size_t)tile * (NS * 64) + lane;
 #pragma unroll
-    for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8e, __builtin_nontemporal_load(tp + 64 * st));
+    for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, __builtin_nontemporal_load(tp + 64 * st));
     // this lane's outputs: rows 4 h + i of the tile (register i), column c16
     bool valid[4];
     uint32_t id[4];
@@ -242,12 +238,12 @@ __global__ __launch_bounds__(256) void exact_mfma_kernel(const u32x4e *__restric
     }
     for (uint32_t q0 = 0; q0 < B; q0 += 16) {
         const uint32_t b = q0 + c16, bq = b < B ? b : B - 1;
-        const u32x4e *qp = Qh + (size_t)bq * (D / 8) + h;  // step st: piece 4 st + h of the query (qhalf layout 1 = the A operand's k order)
-        f32x4e acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        const u32x4 *qp = Qh + (size_t)bq * (D / 8) + h;  // step st: piece 4 st + h of the query (qhalf layout 1 = the A operand's k order)
+        f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int st = 0; st < NS; st++)
-            acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8e, qp[4 * st]), acc[st & 3], 0, 0, 0);
-        const f32x4e t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+            acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, qp[4 * st]), acc[st & 3], 0, 0, 0);
+        const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
         if (b < B) {
             const float4 qm = qmeta[b];
             const uint32_t tq = tau[b];
@@ -362,8 +358,8 @@ bool zh_exact_mfma_supported(uint32_t d, int metric) {
 template <int D, int KINDA, bool FILT>
 static void launch_mfma_d(const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, hipStream_t s) {
     const uint64_t tiles = (p_end - p_begin + 15) / 16, blocks = (tiles + 3) / 4;
-    hipLaunchKernelGGL((exact_mfma_kernel<D, KINDA, FILT>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4e *)e.Xh, e.rowMeta, e.perm, e.perm_rows,
-                       e.liveBits, p_begin, p_end, (const u32x4e *)e.Qh, e.qmeta, e.B, e.Kc, e.rho, e.tau, e.cnt, e.lid, e.llo, e.lhi, e.cap, e.over);
+    hipLaunchKernelGGL((exact_mfma_kernel<D, KINDA, FILT>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4 *)e.Xh, e.rowMeta, e.perm, e.perm_rows,
+                       e.liveBits, p_begin, p_end, (const u32x4 *)e.Qh, e.qmeta, e.B, e.Kc, e.rho, e.tau, e.cnt, e.lid, e.llo, e.lhi, e.cap, e.over);
 }
 
 template <int KINDA, bool FILT>

@@ -2,7 +2,7 @@
 // number, that are members of the SAME leaf in at least one tree and whose key is <= ONE threshold key, each pair once however many trees put the
 // two rows together.  Key, orientation, order, threshold and output are zh_join.hip's: the key of (a, b) is that of stored row b
 // against a query equal to the f32 row a, hits go to ONE pool per call (v = a << 32 | b and the key) and are counted whether or not the pool has
-// room, zh_launch_join_sort orders the pool by (a, key, b).  What is approximate is the candidate set, never the arithmetic.  DESIGN.md s18.
+// room, zh_launch_pair_sort orders the pool by (a, key, b).  What is approximate is the candidate set, never the arithmetic.  DESIGN.md s18.
 //
 // Each pair once: leaf_of[row][tree] = the offset into leaf_ids of the row's leaf in that tree (UINT32_MAX: the tree does not hold the row), built
 // once per call by fjoin_rowleaf_kernel.  A pair met in tree t is kept only if leaf_of[a][t'] != leaf_of[b][t'] for every t' < t: the FIRST tree
@@ -20,41 +20,16 @@
 //           wave, and walks ONE chunk of the leaf's tiles counted from its own diagonal through two LDS buffers; a gathered tile serves as either
 //           MFMA operand (s15).  The sum is (acc0 + acc1) + (acc2 + acc3), approx_interval's bound zh_approx_bound(metric, d, 1), the held row its
 //           "stored row", the LDS row its "query": s15's argument for two rounded operands applies word for word.  Pairs with lo <= tau go to the
-//           batch's candidate pool as min(row) << 32 | max(row); fjoin_survivors_kernel applies the first-tree rule, gives the rest the canonical
-//           key of (row b, query = f32 row a), judges key <= max_key, counts and pools.
+//           batch's candidate pool as min(row) << 32 | max(row); pair_survivors_kernel (zh_join.hip; OWNED) applies the first-tree rule, gives the
+//           rest the canonical key of (row b, query = f32 row a), judges key <= max_key, counts and pools.
 // Scratch (all per call, released before return): leaf_of is 4 bytes per (stored row, tree) -- 4 N T, 600 MB at 10M rows x 15 trees, not chunked
 // -- and the node -> tree map 4 bytes per node; path 2 per batch of at most max(ZH_FKNN_COL_TILES tiles, the longest leaf) gathered rows 2 d + 28
 // bytes per row, 16 bytes per segment and 8 bytes per candidate slot (at most max(1.25 x the capacity left, 256 per gathered row), never more than
 // the batch's leaf pairs), plus 4 bytes per stored row under a scan order that is not id order; path 1 per panel of at most ZH_FJOIN_PANEL_LINES
 // lines 4 d + 24 bytes per line, 56 bytes per group and 8 bytes per key of at most max(2^25, the longest leaf) keys; both 16 bytes per hit-pool
 // slot (<= the capacity), for the order as much again plus hipCUB's temporary storage, and 24 bytes per pair of staging for the host call.
-#include <algorithm>
-
 #include "zh_internal.h"
 #include "zh_device.h"
-
-typedef _Float16 f16x8g __attribute__((ext_vector_type(8)));
-typedef float f32x4g __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4g __attribute__((ext_vector_type(4)));
-
-// the lanes of `m` (a ballot) get consecutive pool slots: one atomic for the wave (join_wave_slots, restated: zh_join.hip is left alone)
-__device__ __forceinline__ unsigned long long fjoin_wave_slots(unsigned long long *__restrict__ ctr, uint64_t m, uint32_t lane) {
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(ctr, (unsigned long long)__popcll(m));
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
-    return (((unsigned long long)hi << 32) | lo) + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-}
-
-// the first-tree rule: tree t owns the pair (a, b) when no earlier tree holds both rows in one leaf
-__device__ __forceinline__ bool fjoin_owned(const uint32_t *__restrict__ leaf_of, uint32_t T, uint32_t t, uint32_t a, uint32_t b) {
-    const uint32_t *la = leaf_of + (size_t)a * T, *lb = leaf_of + (size_t)b * T;
-    for (uint32_t u = 0; u < t; u++) {
-        const uint32_t x = la[u];
-        if (x != 0xFFFFFFFFu && x == lb[u]) return false;
-    }
-    return true;
-}
 
 // ---- both paths: leaf_of.  A block per node: a leaf of tree t writes its offset for its members; *leaf_pairs += len (len - 1) / 2 ----
 __global__ __launch_bounds__(64) void fjoin_rowleaf_kernel(const int4 *__restrict__ node_pack, const uint32_t *__restrict__ node_tree,
@@ -151,7 +126,7 @@ __global__ __launch_bounds__(256) void fjoin_collect_kernel(const uint64_t *__re
         }
         const uint64_t m = __ballot(hit);
         if (!m) continue;  // (wave-uniform)
-        const unsigned long long slot = fjoin_wave_slots(ctr, m, lane);  // always: the count stays exact when the pool is full
+        const unsigned long long slot = wave_slots(ctr, m, lane);  // always: the count stays exact when the pool is full
         if (hit && slot < cap) {
             pv[slot] = ((uint64_t)a << 32) | row;
             pk[slot] = key;
@@ -175,14 +150,14 @@ hipError_t zh_launch_fjoin_collect(const uint64_t *dKeys, const uint32_t *dRows,
 // One launch over every segment of a batch.  Block x finds its segment sg (the last whose first_block <= x), then chunk = x - first_block.  CA / meta /
 // qm / crow are the batch's gathered tiles, rowMeta, query views and row-or-masked words (zh_launch_fknn_gather, zh_launch_fknn_cols).
 template <int D, int KINDA>
-__global__ __launch_bounds__(256) void fjoin_mfma_kernel(const ZhFjoinSeg *__restrict__ segs, uint32_t n_segs, uint32_t ch, const u32x4g *__restrict__ CA,
+__global__ __launch_bounds__(256) void fjoin_mfma_kernel(const ZhFjoinSeg *__restrict__ segs, uint32_t n_segs, uint32_t ch, const u32x4 *__restrict__ CA,
                                                          const float2 *__restrict__ cmeta, const float4 *__restrict__ cqm, const uint32_t *__restrict__ crow,
                                                          float Kc, float rho, const uint32_t *__restrict__ tau, uint64_t *__restrict__ cand, uint64_t cap,
                                                          unsigned long long *__restrict__ ctr) {
     constexpr int NS = D / 32;        // MFMA steps of a tile (K = 32 each)
     constexpr int PIECES = NS * 64;   // 16-byte pieces of a tile
     constexpr int PT = PIECES / 256;  // ... per thread of the block
-    __shared__ u32x4g sB[2][PIECES];
+    __shared__ u32x4 sB[2][PIECES];
     const uint32_t tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, h = lane >> 4;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     uint32_t lo_s = 0, hi_s = n_segs;  // the last segment whose first block is <= blockIdx.x (block-uniform)
@@ -197,13 +172,13 @@ __global__ __launch_bounds__(256) void fjoin_mfma_kernel(const ZhFjoinSeg *__res
     if (Jb >= Tend) return;  // (block-uniform; the host's geometry launches no such block)
     const uint32_t Je = Jb + ch < Tend ? Jb + ch : Tend;
     const bool active = I < Tend;  // (wave-uniform; an idle wave of a leaf's last held block still moves tiles and meets the barriers)
-    f16x8g A[NS];
+    f16x8 A[NS];
     uint32_t id[4];
     float2 meta[4];
     if (active) {
-        const u32x4g *tp = CA + (size_t)I * PIECES + lane;
+        const u32x4 *tp = CA + (size_t)I * PIECES + lane;
 #pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8g, tp[64 * st]);
+        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, tp[64 * st]);
         // this lane's outputs: rows 4 h + i of the held tile (register i), column c16 = row c16 of tile J
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -213,13 +188,13 @@ __global__ __launch_bounds__(256) void fjoin_mfma_kernel(const ZhFjoinSeg *__res
         }
     } else {
 #pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = f16x8g{0, 0, 0, 0, 0, 0, 0, 0};
+        for (int st = 0; st < NS; st++) A[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int i = 0; i < 4; i++) { id[i] = 0xFFFFFFFFu; meta[i] = make_float2(0.f, 0.f); }
     }
     const uint32_t tq = tau[0];
     {
-        const u32x4g *src = CA + (size_t)Jb * PIECES + tid;
+        const u32x4 *src = CA + (size_t)Jb * PIECES + tid;
 #pragma unroll
         for (int k = 0; k < PT; k++) sB[0][k * 256 + tid] = src[k * 256];
     }
@@ -232,21 +207,21 @@ __global__ __launch_bounds__(256) void fjoin_mfma_kernel(const ZhFjoinSeg *__res
         const bool more = J + 1 < Je;  // (block-uniform)
         const uint32_t cb = cb_next;
         const float4 qb = qb_next;
-        u32x4g pf[PT];
+        u32x4 pf[PT];
         if (more) {
-            const u32x4g *src = CA + (size_t)(J + 1) * PIECES + tid;
+            const u32x4 *src = CA + (size_t)(J + 1) * PIECES + tid;
 #pragma unroll
             for (int k = 0; k < PT; k++) pf[k] = src[k * 256];
             cb_next = crow[(J + 1) * 16 + c16];
             qb_next = cqm[(J + 1) * 16 + c16];
         }
         if (active && J >= I) {  // (wave-uniform: in its first chunk wave w skips the w tiles before its own)
-            const u32x4g *bp = &sB[cur][lane];
-            f32x4g acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            const u32x4 *bp = &sB[cur][lane];
+            f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
             for (int st = 0; st < NS; st++)
-                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8g, bp[64 * st]), acc[st & 3], 0, 0, 0);
-            const f32x4g t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, bp[64 * st]), acc[st & 3], 0, 0, 0);
+            const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
             const bool diag = J == I;
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -256,7 +231,7 @@ __global__ __launch_bounds__(256) void fjoin_mfma_kernel(const ZhFjoinSeg *__res
                     pass = (uint32_t)approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qb, Kc, rho, 0.f) <= tq;
                 const uint64_t m = __ballot(pass);
                 if (m) {  // (wave-uniform)
-                    const unsigned long long slot = fjoin_wave_slots(ctr, m, lane);  // the counter runs on past the pool
+                    const unsigned long long slot = wave_slots(ctr, m, lane);  // the counter runs on past the pool
                     if (pass && slot < cap) {
                         const uint32_t a = id[i] < cb ? id[i] : cb, b = id[i] < cb ? cb : id[i];
                         cand[slot] = ((uint64_t)a << 32) | b;
@@ -278,7 +253,7 @@ static hipError_t launch_fjoin_mfma_kinda(uint32_t d, const ZhFjoinSeg *segs, ui
                                           unsigned long long *dCtr, hipStream_t s) {
 #define ZH_FJ_CASE(DD)                                                                                                                                  \
     case DD:                                                                                                                                             \
-        hipLaunchKernelGGL((fjoin_mfma_kernel<DD, KINDA>), dim3(n_blocks), dim3(256), 0, s, segs, n_segs, ch, (const u32x4g *)CA, cmeta, cqm, crow, Kc, rho, \
+        hipLaunchKernelGGL((fjoin_mfma_kernel<DD, KINDA>), dim3(n_blocks), dim3(256), 0, s, segs, n_segs, ch, (const u32x4 *)CA, cmeta, cqm, crow, Kc, rho, \
                            dTau, dCand, cap, dCtr);                                                                                                      \
         break
     switch (d) {
@@ -302,94 +277,4 @@ hipError_t zh_launch_fjoin_mfma(uint32_t d, int metric, int mode, const ZhFjoinS
     if (mode == ZH_COSINE_PARITY)
         return launch_fjoin_mfma_kinda<2>(d, dSegs, n_segs, n_blocks, ch, dCA, dCMeta, dCQm, dCRow, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
     return launch_fjoin_mfma_kinda<1>(d, dSegs, n_segs, n_blocks, ch, dCA, dCMeta, dCQm, dCRow, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
-}
-
-// The batch's candidates (a << 32 | b, a < b, met in tree t): the first-tree rule, then for those it leaves the canonical key and its judgement
-// exactly as join_survivors_kernel (restated: sharing it would change zh_join.hip) -- the key of STORED row b against the QUERY row a, both read
-// from the f32 table, the cosine's query norm qnorm_kernel's sum of row a.  A wave takes 64 candidates at a time: pair j's sums wait in lane j, so
-// that key_of, the comparison and the pool's atomic run once for all 64.  *keyed += the candidates that got a key.
-template <int D, int KIND>
-__global__ __launch_bounds__(256) void fjoin_survivors_kernel(const float *__restrict__ X, int metric, int param, const uint64_t *__restrict__ cand,
-                                                              const unsigned long long *__restrict__ candCtr, uint64_t cand_cap,
-                                                              const uint32_t *__restrict__ leaf_of, uint32_t T, uint32_t t, uint64_t max_key,
-                                                              unsigned long long *__restrict__ ctr, unsigned long long *__restrict__ keyed,
-                                                              uint64_t *__restrict__ pv, uint64_t *__restrict__ pk, uint64_t cap) {
-    constexpr int NV = RowVec<D>::NV;
-    const uint64_t n = *candCtr;
-    if (n > cand_cap) return;  // (the pool ran over: the batch is answered by path 1)
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
-    for (uint64_t g = wave * 64; g < n; g += n_waves * 64) {
-        const uint32_t m = n - g < 64 ? (uint32_t)(n - g) : 64u;
-        const uint64_t mine = lane < m ? cand[g + lane] : 0ull;
-        const uint32_t my_b = (uint32_t)mine, my_a = (uint32_t)(mine >> 32);
-        const uint64_t own = __ballot(lane < m && fjoin_owned(leaf_of, T, t, my_a, my_b));
-        if (!own) continue;  // (wave-uniform)
-        if (lane == 0) atomicAdd(keyed, (unsigned long long)__popcll(own));
-        float m0 = 0.f, m1 = 0.f, mq = 0.f;
-        for (uint32_t j = 0; j < m; j++) {
-            if (!((own >> j) & 1ull)) continue;  // (wave-uniform)
-            const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)my_b, (int)j), qrow = (uint32_t)__builtin_amdgcn_readlane((int)my_a, (int)j);
-            float4 v[NV], q[NV];
-            load_row<D>(X + (size_t)row * D, lane, v);
-            load_row<D>(X + (size_t)qrow * D, lane, q);
-            float s0 = 0.f, s1 = 0.f, qq = 0.f;
-            row_pair_sums<D, KIND>(v, q, lane, param, s0, s1);
-            if (KIND == K_COS) {
-                float4 c = make_float4(0.f, 0.f, 0.f, 0.f), cq = c;
-#pragma unroll
-                for (int jj = 0; jj < NV; jj++) {
-                    const bool act = (jj < RowVec<D>::NJ) || (lane < (uint32_t)RowVec<D>::REM4);
-                    if (act) { sq4(v[jj], c); sq4(q[jj], cq); }
-                }
-                s1 = wave_sum_canonical((c.x + c.y) + (c.z + c.w));
-                qq = wave_sum_canonical((cq.x + cq.y) + (cq.z + cq.w));
-            }
-            if (lane == j) { m0 = s0; m1 = s1; mq = qq; }
-        }
-        uint64_t key = 0;
-        bool hit = false;
-        if ((own >> lane) & 1ull) {
-            key = key_of(metric, param, m0, m1, mq);
-            hit = key <= max_key;
-        }
-        const uint64_t hm = __ballot(hit);
-        if (hm) {  // (wave-uniform)
-            const unsigned long long slot = fjoin_wave_slots(ctr, hm, lane);
-            if (hit && slot < cap) { pv[slot] = mine; pk[slot] = key; }
-        }
-    }
-}
-
-template <int D>
-static void launch_fjoin_surv_d(const float *dX, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr, uint64_t cand_cap,
-                                const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key, unsigned long long *dHitCtr, unsigned long long *dKeyed,
-                                uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, uint32_t blocks, hipStream_t s) {
-    if (metric == ZH_COSINE)
-        hipLaunchKernelGGL((fjoin_survivors_kernel<D, K_COS>), dim3(blocks), dim3(256), 0, s, dX, metric, mode, dCand, dCandCtr, cand_cap, dLeafOf, T, t, max_key,
-                           dHitCtr, dKeyed, dPoolV, dPoolK, pool_cap);
-    else
-        hipLaunchKernelGGL((fjoin_survivors_kernel<D, K_L2>), dim3(blocks), dim3(256), 0, s, dX, metric, mode, dCand, dCandCtr, cand_cap, dLeafOf, T, t, max_key,
-                           dHitCtr, dKeyed, dPoolV, dPoolK, pool_cap);
-}
-
-hipError_t zh_launch_fjoin_survivors(const float *dX, uint32_t d, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr,
-                                     uint64_t cand_cap, const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key, unsigned long long *dHitCtr,
-                                     unsigned long long *dKeyed, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s) {
-    // the candidate count is known on the device only: enough waves for 64 candidates each up to the pool's size, at most 4096 of them
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (cand_cap + 255) / 256));
-#define ZH_FJ_SURV(DD)                                                                                                                                          \
-    case DD:                                                                                                                                                     \
-        launch_fjoin_surv_d<DD>(dX, metric, mode, dCand, dCandCtr, cand_cap, dLeafOf, T, t, max_key, dHitCtr, dKeyed, dPoolV, dPoolK, pool_cap, blocks, s); \
-        break
-    switch (d) {
-        ZH_FJ_SURV(256);
-        ZH_FJ_SURV(384);
-        ZH_FJ_SURV(512);
-        ZH_FJ_SURV(768);
-        ZH_FJ_SURV(1024);
-    default: return hipErrorInvalidValue;
-    }
-#undef ZH_FJ_SURV
-    return hipGetLastError();
 }

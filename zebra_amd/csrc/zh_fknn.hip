@@ -25,10 +25,6 @@
 #include "zh_internal.h"
 #include "zh_device.h"
 
-typedef _Float16 f16x8f __attribute__((ext_vector_type(8)));
-typedef float f32x4f __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4f __attribute__((ext_vector_type(4)));
-
 // ---- both paths: the row -> leaf table of a sub-slab [r0, r0 + m), its lines and the pairs they stand for ----
 // a block per node: a leaf of tree t writes {offset into leaf_ids, length} for its members that lie in the sub-slab
 __global__ __launch_bounds__(64) void fknn_rowleaf_kernel(const int4 *__restrict__ node_pack, const uint32_t *__restrict__ node_tree,
@@ -214,13 +210,13 @@ __global__ __launch_bounds__(256) void fknn_held_kernel(const ZhFknnSeg *__restr
 // The tiles of a row list (n_tiles * 16 rows, UINT32_MAX = no row: zero and masked) out of the fp16 copy, in the MFMA operand's own order (the copy's own
 // bits), as knn_panel_kernel: a tile is NS * 64 pieces of 16 bytes, piece 64 st + 16 h + line; thread t writes piece t.  Per row its rowMeta and, when
 // qm is asked for, the row as approx_interval's query (join_prep_kernel's values).
-__global__ __launch_bounds__(256) void fknn_gather_kernel(const u32x4f *__restrict__ Xh, const float2 *__restrict__ rowMeta, const uint32_t *__restrict__ pos,
-                                                          const uint32_t *__restrict__ rows, uint32_t n_tiles, uint32_t pieces, float rho, u32x4f *__restrict__ A,
+__global__ __launch_bounds__(256) void fknn_gather_kernel(const u32x4 *__restrict__ Xh, const float2 *__restrict__ rowMeta, const uint32_t *__restrict__ pos,
+                                                          const uint32_t *__restrict__ rows, uint32_t n_tiles, uint32_t pieces, float rho, u32x4 *__restrict__ A,
                                                           float2 *__restrict__ meta, float4 *__restrict__ qm) {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (uint64_t)n_tiles * pieces) return;
     const uint32_t tile = (uint32_t)(t / pieces), w = (uint32_t)(t % pieces), b = tile * 16 + (w & 15);
-    u32x4f v = {0u, 0u, 0u, 0u};
+    u32x4 v = {0u, 0u, 0u, 0u};
     float2 rm = make_float2(0.f, 0.f);
     float4 o = make_float4(NAN, NAN, NAN, NAN);
     const uint32_t row = rows[b];
@@ -260,8 +256,8 @@ hipError_t zh_launch_fknn_gather(uint32_t d, const void *dXh, const float2 *dRow
     if (!n_tiles) return hipSuccess;
     const uint32_t pieces = d / 32 * 64;
     const uint64_t n = (uint64_t)n_tiles * pieces;
-    hipLaunchKernelGGL(fknn_gather_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const u32x4f *)dXh, dRowMeta, dPos, dRows, n_tiles, pieces, rho,
-                       (u32x4f *)dA, dMeta, dQm);
+    hipLaunchKernelGGL(fknn_gather_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const u32x4 *)dXh, dRowMeta, dPos, dRows, n_tiles, pieces, rho,
+                       (u32x4 *)dA, dMeta, dQm);
     return hipGetLastError();
 }
 
@@ -294,15 +290,15 @@ hipError_t zh_launch_fknn_bound(const uint32_t *dHRow, uint32_t B, uint64_t firs
 // whose held tiles are past the segment's held rows (held[seg], counted on the device) leaves at once.
 template <int D, int KINDA>
 __global__ __launch_bounds__(256) void fknn_mfma_kernel(const ZhFknnSeg *__restrict__ segs, uint32_t n_segs, const uint32_t *__restrict__ held, uint32_t ch,
-                                                        const u32x4f *__restrict__ CA, const float4 *__restrict__ cqm, const uint32_t *__restrict__ crow,
-                                                        const u32x4f *__restrict__ HA, const float2 *__restrict__ hmeta, const uint32_t *__restrict__ hrow,
+                                                        const u32x4 *__restrict__ CA, const float4 *__restrict__ cqm, const uint32_t *__restrict__ crow,
+                                                        const u32x4 *__restrict__ HA, const float2 *__restrict__ hmeta, const uint32_t *__restrict__ hrow,
                                                         float Kc, float rho, const uint32_t *__restrict__ tau, uint32_t *__restrict__ cnt,
                                                         uint32_t *__restrict__ lid, uint32_t *__restrict__ llo, uint32_t *__restrict__ lhi, uint32_t cap,
                                                         uint32_t lim, uint32_t *__restrict__ over) {
     constexpr int NS = D / 32;        // MFMA steps of a tile (K = 32 each)
     constexpr int PIECES = NS * 64;   // 16-byte pieces of a tile
     constexpr int PT_ = PIECES / 256; // ... per thread of the block
-    __shared__ u32x4f sB[2][PIECES];
+    __shared__ u32x4 sB[2][PIECES];
     const uint32_t tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, h = lane >> 4;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     uint32_t lo_s = 0, hi_s = n_segs;  // the last segment whose first block is <= blockIdx.x (block-uniform)
@@ -318,13 +314,13 @@ __global__ __launch_bounds__(256) void fknn_mfma_kernel(const ZhFknnSeg *__restr
     const uint32_t Jb = sg.col0 + chunk * ch, Jend = sg.col0 + sg.ct, Je = Jb + ch < Jend ? Jb + ch : Jend;
     if (Jb >= Je) return;  // (block-uniform; the host's geometry launches no such block)
     const bool active = I < ht;  // (wave-uniform; an idle wave still moves tiles and meets the barriers)
-    f16x8f A[NS];
+    f16x8 A[NS];
     uint32_t id[4], line[4], tq[4];
     float2 meta[4];
     if (active) {
-        const u32x4f *tp = HA + ((size_t)(sg.line0 >> 4) + I) * PIECES + lane;
+        const u32x4 *tp = HA + ((size_t)(sg.line0 >> 4) + I) * PIECES + lane;
 #pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8f, tp[64 * st]);
+        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, tp[64 * st]);
         // this lane's outputs: lines 4 h + i of the held tile (register i), column c16 = row c16 of tile J
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -336,12 +332,12 @@ __global__ __launch_bounds__(256) void fknn_mfma_kernel(const ZhFknnSeg *__restr
         }
     } else {
 #pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = f16x8f{0, 0, 0, 0, 0, 0, 0, 0};
+        for (int st = 0; st < NS; st++) A[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int i = 0; i < 4; i++) { id[i] = 0xFFFFFFFFu; line[i] = 0; tq[i] = 0; meta[i] = make_float2(0.f, 0.f); }
     }
     {
-        const u32x4f *src = CA + (size_t)Jb * PIECES + tid;
+        const u32x4 *src = CA + (size_t)Jb * PIECES + tid;
 #pragma unroll
         for (int k = 0; k < PT_; k++) sB[0][k * 256 + tid] = src[k * 256];
     }
@@ -354,21 +350,21 @@ __global__ __launch_bounds__(256) void fknn_mfma_kernel(const ZhFknnSeg *__restr
         const bool more = J + 1 < Je;  // (block-uniform)
         const uint32_t cb = cb_next;
         const float4 qb = qb_next;
-        u32x4f pf[PT_];
+        u32x4 pf[PT_];
         if (more) {
-            const u32x4f *src = CA + (size_t)(J + 1) * PIECES + tid;
+            const u32x4 *src = CA + (size_t)(J + 1) * PIECES + tid;
 #pragma unroll
             for (int k = 0; k < PT_; k++) pf[k] = src[k * 256];
             cb_next = crow[(J + 1) * 16 + c16];
             qb_next = cqm[(J + 1) * 16 + c16];
         }
         if (active) {  // (wave-uniform)
-            const u32x4f *bp = &sB[cur][lane];
-            f32x4f acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            const u32x4 *bp = &sB[cur][lane];
+            f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
             for (int st = 0; st < NS; st++)
-                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8f, bp[64 * st]), acc[st & 3], 0, 0, 0);
-            const f32x4f t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, bp[64 * st]), acc[st & 3], 0, 0, 0);
+            const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 bool pass = false;
@@ -411,8 +407,8 @@ static hipError_t launch_fknn_mfma_kinda(uint32_t d, const ZhFknnSeg *segs, uint
                                          uint32_t lim, hipStream_t s) {
 #define ZH_FK_CASE(DD)                                                                                                                                     \
     case DD:                                                                                                                                                \
-        hipLaunchKernelGGL((fknn_mfma_kernel<DD, KINDA>), dim3(n_blocks), dim3(256), 0, s, segs, n_segs, held, ch, (const u32x4f *)CA, cqm, crow,              \
-                           (const u32x4f *)HA, hmeta, hrow, e.Kc, e.rho, e.tau, e.cnt, e.lid, e.llo, e.lhi, e.cap, lim, e.over);                            \
+        hipLaunchKernelGGL((fknn_mfma_kernel<DD, KINDA>), dim3(n_blocks), dim3(256), 0, s, segs, n_segs, held, ch, (const u32x4 *)CA, cqm, crow,              \
+                           (const u32x4 *)HA, hmeta, hrow, e.Kc, e.rho, e.tau, e.cnt, e.lid, e.llo, e.lhi, e.cap, lim, e.over);                            \
         break
     switch (d) {
         ZH_FK_CASE(256);

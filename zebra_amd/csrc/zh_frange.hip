@@ -43,19 +43,6 @@
 #include "zh_internal.h"
 #include "zh_device.h"
 
-typedef _Float16 f16x8q __attribute__((ext_vector_type(8)));
-typedef float f32x4q __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4q __attribute__((ext_vector_type(4)));
-
-// the lanes of `m` (a ballot) get consecutive pool slots: one atomic for the wave (range_wave_slots, restated: zh_range.hip is left alone)
-__device__ __forceinline__ unsigned long long frange_wave_slots(unsigned long long *__restrict__ ctr, uint64_t m, uint32_t lane) {
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(ctr, (unsigned long long)__popcll(m));
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
-    return (((unsigned long long)hi << 32) | lo) + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-}
-
 // ---- both paths: the lookup of visited leaves.  vkey[i] = (b T + t) << 32 | leaf offset of visit i, then sorted ----
 __global__ __launch_bounds__(256) void frange_vkeys_kernel(const ZhVisit *__restrict__ visits, uint64_t n, const uint32_t *__restrict__ node_tree, uint32_t T,
                                                            uint64_t *__restrict__ vkey) {
@@ -65,16 +52,10 @@ __global__ __launch_bounds__(256) void frange_vkeys_kernel(const ZhVisit *__rest
     vkey[i] = ((uint64_t)(v.b * T + node_tree[v.node]) << 32) | v.leaf_off;
 }
 
-static int frange_bits(uint64_t values) {  // bits that hold 0 .. values - 1
-    int b = 1;
-    while (b < 32 && (1ull << b) < values) b++;
-    return b;
-}
-
 hipError_t zh_launch_frange_visit_index(const ZhVisit *dVisits, uint64_t n_visits, const uint32_t *dNodeTree, uint32_t T, uint64_t n_pairs, uint64_t *dKeys[2],
                                         void *dTmp, size_t *tmp_bytes, const uint64_t **dSorted, hipStream_t s) {
     hipcub::DoubleBuffer<uint64_t> k(dKeys[0], dKeys[1]);
-    const int end_bit = 32 + frange_bits(n_pairs);
+    const int end_bit = 32 + field_bits(n_pairs);
     hipError_t e;
     if (!dTmp) {
         size_t a = 0;
@@ -136,7 +117,7 @@ __global__ __launch_bounds__(256) void frange_collect_kernel(const ZhVisit *__re
         const uint64_t m = __ballot(hit);
         if (!m) continue;  // (wave-uniform)
         if (lane == 0) atomicAdd(&cnt[v.b], (uint32_t)__popcll(m));  // always: the count stays exact when the pool is full
-        const unsigned long long slot = frange_wave_slots(ctr, m, lane);
+        const unsigned long long slot = wave_slots(ctr, m, lane);
         if (hit && slot < cap) {
             pv[slot] = ((uint64_t)v.b << 32) | row;
             pk[slot] = key;
@@ -161,8 +142,8 @@ hipError_t zh_launch_frange_collect(const ZhVisit *dVisits, uint64_t n_visits, c
 // past the leaf's last row tile leaves at once.
 template <int D, int KINDA>
 __global__ __launch_bounds__(256) void frange_mfma_kernel(const ZhFrangeSeg *__restrict__ segs, uint32_t n_segs, uint32_t ch, uint32_t G,
-                                                          const u32x4q *__restrict__ CA, const float2 *__restrict__ cmeta, const uint32_t *__restrict__ crow,
-                                                          const ZhGroup *__restrict__ groups, const u32x4q *__restrict__ Qh, const float4 *__restrict__ qmeta,
+                                                          const u32x4 *__restrict__ CA, const float2 *__restrict__ cmeta, const uint32_t *__restrict__ crow,
+                                                          const ZhGroup *__restrict__ groups, const u32x4 *__restrict__ Qh, const float4 *__restrict__ qmeta,
                                                           float Kc, float rho, const uint32_t *__restrict__ tau, const uint64_t *__restrict__ vsorted,
                                                           const uint64_t *__restrict__ visitBase, const uint32_t *__restrict__ leaf_of, uint32_t T,
                                                           uint64_t *__restrict__ cand, uint64_t cap, unsigned long long *__restrict__ ctr) {
@@ -180,10 +161,10 @@ __global__ __launch_bounds__(256) void frange_mfma_kernel(const ZhFrangeSeg *__r
     if (rtile >= sg.rt) return;  // (wave-uniform)
     const uint32_t Jb = (k % nch) * ch, Je = Jb + ch < vt ? Jb + ch : vt;
     const uint32_t I = sg.col0 + rtile;
-    f16x8q A[NS];
-    const u32x4q *tp = CA + (size_t)I * (NS * 64) + lane;
+    f16x8 A[NS];
+    const u32x4 *tp = CA + (size_t)I * (NS * 64) + lane;
 #pragma unroll
-    for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8q, tp[64 * st]);
+    for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, tp[64 * st]);
     // this lane's outputs: rows 4 h + i of the tile (register i), column c16 = visitor 16 J + c16
     uint32_t id[4];
     float2 meta[4];
@@ -198,12 +179,12 @@ __global__ __launch_bounds__(256) void frange_mfma_kernel(const ZhFrangeSeg *__r
         const bool col = j < sg.visitors;
         const uint32_t jj = col ? j : sg.visitors - 1;  // (a padding column repeats the leaf's last visitor and passes nothing)
         const uint32_t b = groups[sg.group0 + jj / G].b[jj % G];
-        const u32x4q *qp = Qh + (size_t)b * (D / 8) + h;  // step st: piece 4 st + h of the query (qhalf layout 1 = the A operand's k order)
-        f32x4q acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        const u32x4 *qp = Qh + (size_t)b * (D / 8) + h;  // step st: piece 4 st + h of the query (qhalf layout 1 = the A operand's k order)
+        f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int st = 0; st < NS; st++)
-            acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8q, qp[4 * st]), acc[st & 3], 0, 0, 0);
-        const f32x4q tt = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+            acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, qp[4 * st]), acc[st & 3], 0, 0, 0);
+        const f32x4 tt = (acc[0] + acc[1]) + (acc[2] + acc[3]);
         const float4 qm = qmeta[b];
         const uint32_t tq = tau[b];
 #pragma unroll
@@ -214,7 +195,7 @@ __global__ __launch_bounds__(256) void frange_mfma_kernel(const ZhFrangeSeg *__r
             if (pass) pass = frange_owned(vsorted, visitBase, leaf_of, T, sg.tree, b, id[i]);
             const uint64_t m = __ballot(pass);
             if (m) {  // (wave-uniform)
-                const unsigned long long slot = frange_wave_slots(ctr, m, lane);  // the counter runs on past the pool
+                const unsigned long long slot = wave_slots(ctr, m, lane);  // the counter runs on past the pool
                 if (pass && slot < cap) cand[slot] = ((uint64_t)b << 32) | id[i];
             }
         }
@@ -228,8 +209,8 @@ static hipError_t launch_frange_mfma_kinda(uint32_t d, const ZhFrangeSeg *segs, 
                                            uint32_t T, uint64_t *dCand, uint64_t cap, unsigned long long *dCtr, hipStream_t s) {
 #define ZH_FR_CASE(DD)                                                                                                                                   \
     case DD:                                                                                                                                              \
-        hipLaunchKernelGGL((frange_mfma_kernel<DD, KINDA>), dim3(n_blocks), dim3(256), 0, s, segs, n_segs, ch, G, (const u32x4q *)CA, cmeta, crow, groups, \
-                           (const u32x4q *)Qh, qmeta, Kc, rho, dTau, vsorted, visitBase, leafOf, T, dCand, cap, dCtr);                                       \
+        hipLaunchKernelGGL((frange_mfma_kernel<DD, KINDA>), dim3(n_blocks), dim3(256), 0, s, segs, n_segs, ch, G, (const u32x4 *)CA, cmeta, crow, groups, \
+                           (const u32x4 *)Qh, qmeta, Kc, rho, dTau, vsorted, visitBase, leafOf, T, dCand, cap, dCtr);                                       \
         break
     switch (d) {
         ZH_FR_CASE(256);

@@ -343,20 +343,27 @@ hipError_t zh_launch_range_survivors(const float *dX, uint32_t d, const float *d
                                      unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
 // dOff[i] = base + hits of the queries before i, i <= B (B <= 1024)
 hipError_t zh_launch_range_offsets(const uint32_t *dCnt, uint32_t B, uint64_t base, uint64_t *dOff, hipStream_t s);
-// the pool's n entries ordered by (query, key, row) and written out as ids (id_base + row) and keys; dV / dK: the pool and a second buffer of the
-// same size each.  dTmp == nullptr: only *tmp_bytes is set, to what the sorts of n entries need
+// every pool's order: n entries of (v, k) by (the high field of v, k, the low field of v), the fields holding hi_values / lo_values values; skip_high
+// leaves the last of the three passes out.  dV / dK: the pool and a second buffer of the same size each; *v_out / *k_out = where the result is.
+// dTmp == nullptr: only *tmp_bytes is set, to what the sorts of n entries need
+hipError_t zh_launch_pool_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t lo_values, uint64_t hi_values, bool skip_high, void *dTmp,
+                               size_t *tmp_bytes, const uint64_t **v_out, const uint64_t **k_out, hipStream_t s);
+// ... of the pool of an internal batch, by (query, key, row), written out as ids (id_base + row) and keys; dTmp == nullptr as above
 hipError_t zh_launch_range_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows, uint32_t B, void *dTmp, size_t *tmp_bytes, uint64_t id_base,
                                 uint64_t *dOutIds, uint64_t *dOutKeys, hipStream_t s);
 
 // ---- the exact self-join (zh_join.hip): every pair of live rows a < b with key(stored b, query a) <= one threshold key.  A hit pool is two u64
-// arrays, v = a << 32 | b (row numbers) and the key; *dHitCtr counts every hit whether or not the pool has room
+// arrays, v = a << 32 | b (row numbers) and the key; *dHitCtr counts every hit whether or not the pool has room.  The launchers named `pair` serve
+// the join between two indexes and the forest join too: two tables, row counts and id bases, which the self-join passes as the same one twice
 #define ZH_JOIN_CHUNK 64u          // tiles J one block of the matrix-core scan walks
 #define ZH_JOIN_PANEL_ROWS 16384u  // positions of the copy one launch holds (256 blocks of four tiles); a panel is the unit path 1 redoes
 // path 1: dQ[b] = the f32 row dRows[b]
 hipError_t zh_launch_join_gather(const float *dX, uint32_t d, const uint32_t *dRows, uint32_t B, float *dQ, hipStream_t s);
-// ... and of the keys [b][p - p0] (zh_launch_exact_score) those <= max_key whose row dLive[p] is above the query row dQRows[b]
-hipError_t zh_launch_join_collect(const uint64_t *dKeys, uint64_t ld, const uint32_t *dLive, uint64_t p0, uint32_t nr, const uint32_t *dQRows, uint32_t B,
-                                  uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
+// ... and of the keys [b][p - p0] (zh_launch_exact_score) those <= max_key -- upper: whose row dLive[p] is above the query row dQRows[b] (the
+// self-join); otherwise all of them (the full rectangle of two indexes)
+hipError_t zh_launch_pair_collect(const uint64_t *dKeys, uint64_t ld, const uint32_t *dLive, uint64_t p0, uint32_t nr, const uint32_t *dQRows, uint32_t B,
+                                  bool upper, uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap,
+                                  hipStream_t s);
 // path 2: per position of the fp16 copy (ceil(n_rows / 16) * 16 of them) dQm = the row as approx_interval's query, dCid = its row number or
 // UINT32_MAX (removed, or past the table)
 hipError_t zh_launch_join_prep(const float2 *dRowMeta, const uint32_t *dPerm, uint64_t perm_rows, const uint32_t *dLiveBits, uint64_t n_rows, float rho,
@@ -369,22 +376,21 @@ uint64_t zh_join_geometry(uint64_t T, uint64_t tileA0, uint64_t tileA1, uint32_t
 hipError_t zh_launch_join_mfma(uint32_t d, int metric, int mode, const void *dXh, const float2 *dRowMeta, const float4 *dQm, const uint32_t *dCid,
                                uint64_t n_rows, uint64_t tileA0, const uint32_t *dFirst, uint32_t n_ab, uint32_t blocks, float Kc, float rho,
                                const uint32_t *dTau, uint64_t *dCand, uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s);
-// the candidates' canonical keys, judged, counted and appended to the hit pool (nothing when the candidate pool ran over)
-hipError_t zh_launch_join_survivors(const float *dX, uint32_t d, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr,
-                                    uint64_t cand_cap, uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap,
+// the candidates' canonical keys (stored row b of dXB, query row a of dXA), judged, counted and appended to the hit pool (nothing when the
+// candidate pool ran over).  dLeafOf != nullptr (the forest join, candidates met in tree t): the first-tree rule first; *dKeyed += those that got a key
+hipError_t zh_launch_pair_survivors(const float *dXA, const float *dXB, uint32_t d, int metric, int mode, const uint64_t *dCand,
+                                    const unsigned long long *dCandCtr, uint64_t cand_cap, const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key,
+                                    unsigned long long *dHitCtr, unsigned long long *dKeyed, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap,
                                     hipStream_t s);
 // dList = the live rows at positions [p_begin, p_end), any order; *dCount += their number
 hipError_t zh_launch_join_panel_rows(const uint32_t *dCid, uint64_t p_begin, uint64_t p_end, uint32_t *dList, unsigned long long *dCount, hipStream_t s);
-// the pool's n entries ordered by (a, key, b) and written out as ids (id_base + row) and keys; dV / dK: the pool and a second buffer of the same size
-// each.  dTmp == nullptr: only *tmp_bytes is set, to what the sorts of n entries need
-hipError_t zh_launch_join_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows, void *dTmp, size_t *tmp_bytes, uint64_t id_base, uint64_t *dOutA,
-                               uint64_t *dOutB, uint64_t *dOutKeys, hipStream_t s);
+// the pool's n entries ordered by (a, key, b) and written out as ids (each side's id base + row) and keys; n_rows_a / n_rows_b: the row numbers the
+// two fields of v hold.  dV / dK, dTmp == nullptr: as zh_launch_pool_sort
+hipError_t zh_launch_pair_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows_a, uint64_t n_rows_b, void *dTmp, size_t *tmp_bytes,
+                               uint64_t id_base_a, uint64_t id_base_b, uint64_t *dOutA, uint64_t *dOutB, uint64_t *dOutKeys, hipStream_t s);
 
 // ---- the exact join between two indexes (zh_xjoin.hip): every pair (live row a of A, live row b of B) with key(stored b, query a) <= one threshold
-// key.  Hit pool and counter as the self-join's, v = a << 32 | b with a a row number of A and b one of B
-// path 1: of the keys [q][p - p0] (zh_launch_exact_score over B's table against rows of A) all those <= max_key
-hipError_t zh_launch_xjoin_collect(const uint64_t *dKeys, uint64_t ld, const uint32_t *dLiveB, uint64_t p0, uint32_t nr, const uint32_t *dQRows, uint32_t B,
-                                   uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
+// key.  Hit pool, counter and their launchers are the self-join's, v = a << 32 | b with a a row number of A and b one of B
 // path 2: the launch of a panel of held tiles [tileA0, min(tileA1, TA)) of A's copy against all TB tiles of B's: *n_ab held blocks of four tiles,
 // *blocks = n_ab * ceil(TB / ZH_JOIN_CHUNK); returns the 16 x 16 tile products the panel issues
 uint64_t zh_xjoin_geometry(uint64_t TA, uint64_t TB, uint64_t tileA0, uint64_t tileA1, uint32_t *n_ab, uint32_t *blocks);
@@ -393,14 +399,6 @@ uint64_t zh_xjoin_geometry(uint64_t TA, uint64_t TB, uint64_t tileA0, uint64_t t
 hipError_t zh_launch_xjoin_mfma(uint32_t d, int metric, int mode, const void *dXhA, const float2 *dRowMetaA, const uint32_t *dCidA, uint64_t n_rows_a,
                                 const void *dXhB, const float4 *dQmB, const uint32_t *dCidB, uint64_t n_rows_b, uint64_t tileA0, uint64_t tileA1, float Kc,
                                 float rhoA, const uint32_t *dTau, uint64_t *dCand, uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s);
-// the candidates' canonical keys (stored row b of dXB, query row a of dXA), judged, counted and appended to the hit pool (nothing when the
-// candidate pool ran over)
-hipError_t zh_launch_xjoin_survivors(const float *dXA, const float *dXB, uint32_t d, int metric, int mode, const uint64_t *dCand,
-                                     const unsigned long long *dCandCtr, uint64_t cand_cap, uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV,
-                                     uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
-// zh_launch_join_sort with each side's row count (the bits sorted) and id base
-hipError_t zh_launch_xjoin_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows_a, uint64_t n_rows_b, void *dTmp, size_t *tmp_bytes,
-                                uint64_t id_base_a, uint64_t id_base_b, uint64_t *dOutA, uint64_t *dOutB, uint64_t *dOutKeys, hipStream_t s);
 
 // ---- the exact k-NN graph (zh_knn.hip): each live row's k nearest other live rows, panel by panel
 #define ZH_KNN_PANEL_ROWS 1024u  // live rows one panel holds (= the exact search's internal batch: every reused launcher sees a batch it already serves)
@@ -509,10 +507,6 @@ hipError_t zh_launch_fjoin_collect(const uint64_t *dKeys, const uint32_t *dRows,
 hipError_t zh_launch_fjoin_mfma(uint32_t d, int metric, int mode, const ZhFjoinSeg *dSegs, uint32_t n_segs, uint32_t n_blocks, uint32_t ch, const void *dCA,
                                 const float2 *dCMeta, const float4 *dCQm, const uint32_t *dCRow, float Kc, float rho, const uint32_t *dTau, uint64_t *dCand,
                                 uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s);
-// ... the first-tree rule, canonical keys and the judgement of its candidates (nothing when *dCandCtr > cand_cap); *dKeyed += those that got a key
-hipError_t zh_launch_fjoin_survivors(const float *dX, uint32_t d, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr,
-                                     uint64_t cand_cap, const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key, unsigned long long *dHitCtr,
-                                     unsigned long long *dKeyed, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s);
 
 // ---- the forest range search (zh_frange.hip): every member of the leaves the walk visits for a query whose key is <= the query's threshold key,
 // each (query, row) once (the first tree that offers the row owns the pair).  Hit pool, counters and order as the exact range search's

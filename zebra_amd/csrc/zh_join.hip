@@ -5,9 +5,10 @@
 //
 // A hit is (a, b, key).  Both paths append hits to ONE pool per call -- v = a << 32 | b and the key, two u64 arrays -- and count them in *ctr whether
 // or not the pool still has room: the total stays exact when the caller's capacity is too small (or 0: count only).  A pool slot is taken with one
-// atomic per WAVE (range_wave_slots's pattern, restated here: zh_range.hip is left alone).
+// atomic per WAVE (wave_slots, zh_device.h).  The pool's kernels -- collect, survivors, the order -- are written once here and serve the join
+// between two indexes (zh_xjoin.hip) and the forest join (zh_fjoin.hip) too: the self-join passes its one table, row count and id base twice.
 //   path 1  a panel of up to 1024 live rows is gathered device-to-device into a query buffer (join_gather_kernel), exact_score_kernel (zh_exact.hip)
-//           keys the row chunks from the panel's first row on into the key scratch [query][position], join_collect_kernel takes the keys <= max_key
+//           keys the row chunks from the panel's first row on into the key scratch [query][position], pair_collect_kernel takes the keys <= max_key
 //           whose row number is greater than the query row's.
 //   path 2  join_mfma_kernel: BOTH operands of v_mfma_f32_16x16x32_f16 are tiles of the index's fp16 row copy (the A and the B operand have the same
 //           per-lane layout: lane l holds line l % 16, k-chunk l / 16), so a 16 x 16 block of the table's Gram matrix needs no conversion, and only
@@ -18,33 +19,18 @@
 //           (acc0 + acc1) + (acc2 + acc3) as in range_mfma_kernel: zh_approx_bound(metric, d, 1) stays the accumulation bound.  approx_interval
 //           (unchanged) gives the pair's interval: the held row is its "stored row", the LDS row its "query", whose qm = {scale, |x|^2, an upper
 //           bound of |x|, dq = rho times that bound rounded up} comes from the row's rowMeta entry (join_prep_kernel).  Pairs with lo <= tau go to a
-//           candidate pool as min(id) << 32 | max(id) (positions are not ids under a row order); join_survivors_kernel gives every candidate the
+//           candidate pool as min(id) << 32 | max(id) (positions are not ids under a row order); pair_survivors_kernel gives every candidate the
 //           canonical key of (row b, query = f32 row a), both rows read from the f32 table, judges key <= max_key, counts and compacts.
 // Then, while the capacity holds, the pool is ordered by (a, key, b) with three stable LSD radix sorts (b bits, then the key, then the a bits;
-// rocPRIM through hipCUB) and join_emit_kernel writes the three arrays.
+// rocPRIM through hipCUB) and pair_emit_kernel writes the three arrays.
 // Scratch (all per call, released before return): path 2 holds 20 bytes per position (qm and the id-or-masked word), 8 bytes per candidate slot of
 // one panel (at most max(1.25 x the capacity left, 256 per held row) and never more than the panel's pairs) and a block table of 4 bytes per 64 held
 // rows; path 1 the exact search's query buffer and key scratch (<= 1 GiB); both 16 bytes per hit-pool slot (<= the capacity), and for the order as
 // much again plus hipCUB's temporary storage, and 24 bytes per hit of staging for the host call.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 
 #include "zh_internal.h"
 #include "zh_device.h"
-
-typedef _Float16 f16x8j __attribute__((ext_vector_type(8)));
-typedef float f32x4j __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4j __attribute__((ext_vector_type(4)));
-
-// the lanes of `m` (a ballot) get consecutive pool slots: one atomic for the wave, taken by lane 0 (every lane of the wave is active at the call)
-__device__ __forceinline__ unsigned long long join_wave_slots(unsigned long long *__restrict__ ctr, uint64_t m, uint32_t lane) {
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(ctr, (unsigned long long)__popcll(m));
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
-    return (((unsigned long long)hi << 32) | lo) + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-}
 
 // ---- path 1: the panel's rows as queries.  One wave per row ----
 __global__ __launch_bounds__(256) void join_gather_kernel(const float *__restrict__ X, uint32_t d, const uint32_t *__restrict__ rows, uint32_t B,
@@ -62,8 +48,10 @@ hipError_t zh_launch_join_gather(const float *dX, uint32_t d, const uint32_t *dR
     return hipGetLastError();
 }
 
-// the hits of a keyed row chunk: key <= max_key and the stored row's number above the query row's.  grid (ceil(nr / 256), B)
-__global__ __launch_bounds__(256) void join_collect_kernel(const uint64_t *__restrict__ keys, uint64_t ld, const uint32_t *__restrict__ live, uint64_t p0,
+// the hits of a keyed row chunk: key <= max_key and, UPPER (the self-join's triangle), the stored row's number above the query row's; the join
+// between two indexes takes the full rectangle.  grid (ceil(nr / 256), B)
+template <bool UPPER>
+__global__ __launch_bounds__(256) void pair_collect_kernel(const uint64_t *__restrict__ keys, uint64_t ld, const uint32_t *__restrict__ live, uint64_t p0,
                                                            uint32_t nr, const uint32_t *__restrict__ qrows, uint64_t max_key,
                                                            unsigned long long *__restrict__ ctr, uint64_t *__restrict__ pv, uint64_t *__restrict__ pk,
                                                            uint64_t cap) {
@@ -76,22 +64,23 @@ __global__ __launch_bounds__(256) void join_collect_kernel(const uint64_t *__res
     if (rl < nr) {
         row = live[p0 + rl];
         key = keys[(size_t)b * ld + rl];
-        hit = row > a && key <= max_key;
+        hit = (!UPPER || row > a) && key <= max_key;
     }
     const uint64_t m = __ballot(hit);
     if (!m) return;  // (wave-uniform)
-    const unsigned long long slot = join_wave_slots(ctr, m, lane);  // always: the count stays exact when the pool is full
+    const unsigned long long slot = wave_slots(ctr, m, lane);  // always: the count stays exact when the pool is full
     if (hit && slot < cap) {
         pv[slot] = ((uint64_t)a << 32) | row;
         pk[slot] = key;
     }
 }
 
-hipError_t zh_launch_join_collect(const uint64_t *dKeys, uint64_t ld, const uint32_t *dLive, uint64_t p0, uint32_t nr, const uint32_t *dQRows, uint32_t B,
-                                  uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s) {
+hipError_t zh_launch_pair_collect(const uint64_t *dKeys, uint64_t ld, const uint32_t *dLive, uint64_t p0, uint32_t nr, const uint32_t *dQRows, uint32_t B,
+                                  bool upper, uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap,
+                                  hipStream_t s) {
     if (!nr || !B) return hipSuccess;
-    hipLaunchKernelGGL(join_collect_kernel, dim3((nr + 255) / 256, B), dim3(256), 0, s, dKeys, ld, dLive, p0, nr, dQRows, max_key, dHitCtr, dPoolV, dPoolK,
-                       pool_cap);
+    const auto kernel = upper ? pair_collect_kernel<true> : pair_collect_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((nr + 255) / 256, B), dim3(256), 0, s, dKeys, ld, dLive, p0, nr, dQRows, max_key, dHitCtr, dPoolV, dPoolK, pool_cap);
     return hipGetLastError();
 }
 
@@ -148,14 +137,14 @@ uint64_t zh_join_geometry(uint64_t T, uint64_t tileA0, uint64_t tileA1, uint32_t
 }
 
 template <int D, int KINDA>
-__global__ __launch_bounds__(256) void join_mfma_kernel(const u32x4j *__restrict__ Xh, const float2 *__restrict__ rowMeta, const float4 *__restrict__ qm,
+__global__ __launch_bounds__(256) void join_mfma_kernel(const u32x4 *__restrict__ Xh, const float2 *__restrict__ rowMeta, const float4 *__restrict__ qm,
                                                         const uint32_t *__restrict__ cid, uint64_t T, uint64_t tileA0, const uint32_t *__restrict__ first,
                                                         uint32_t n_ab, float Kc, float rho, const uint32_t *__restrict__ tau, uint64_t *__restrict__ cand,
                                                         uint64_t cap, unsigned long long *__restrict__ ctr) {
     constexpr int NS = D / 32;        // MFMA steps of a tile (K = 32 each) = its KiB
     constexpr int PIECES = NS * 64;   // 16-byte pieces of a tile
     constexpr int PT = PIECES / 256;  // ... per thread of the block
-    __shared__ u32x4j sB[2][PIECES];
+    __shared__ u32x4 sB[2][PIECES];
     const uint32_t tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, h = lane >> 4;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     // the held block: the last ab with first[ab] <= blockIdx.x (block-uniform)
@@ -167,13 +156,13 @@ __global__ __launch_bounds__(256) void join_mfma_kernel(const u32x4j *__restrict
     const uint64_t I0 = tileA0 + 4ull * lo, I = I0 + wid;
     const uint64_t Jb = I0 + (uint64_t)(blockIdx.x - first[lo]) * ZH_JOIN_CHUNK, Je = Jb + ZH_JOIN_CHUNK < T ? Jb + ZH_JOIN_CHUNK : T;
     const bool active = I < T;  // (wave-uniform; an idle wave of the table's last block still moves tiles and meets the barriers)
-    f16x8j A[NS];
+    f16x8 A[NS];
     uint32_t id[4];
     float2 meta[4];
     if (active) {
-        const u32x4j *tp = Xh + (size_t)I * PIECES + lane;
+        const u32x4 *tp = Xh + (size_t)I * PIECES + lane;
 #pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8j, tp[64 * st]);
+        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, tp[64 * st]);
         // this lane's outputs: rows 4 h + i of the held tile (register i), column c16 = row c16 of tile J
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -183,13 +172,13 @@ __global__ __launch_bounds__(256) void join_mfma_kernel(const u32x4j *__restrict
         }
     } else {
 #pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = f16x8j{0, 0, 0, 0, 0, 0, 0, 0};
+        for (int st = 0; st < NS; st++) A[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int i = 0; i < 4; i++) { id[i] = 0xFFFFFFFFu; meta[i] = make_float2(0.f, 0.f); }
     }
     const uint32_t tq = tau[0];
     {
-        const u32x4j *src = Xh + (size_t)Jb * PIECES + tid;
+        const u32x4 *src = Xh + (size_t)Jb * PIECES + tid;
 #pragma unroll
         for (int k = 0; k < PT; k++) sB[0][k * 256 + tid] = src[k * 256];
     }
@@ -202,21 +191,21 @@ __global__ __launch_bounds__(256) void join_mfma_kernel(const u32x4j *__restrict
         const bool more = J + 1 < Je;  // (block-uniform)
         const uint32_t cb = cb_next;
         const float4 qb = qb_next;
-        u32x4j pf[PT];
+        u32x4 pf[PT];
         if (more) {
-            const u32x4j *src = Xh + (size_t)(J + 1) * PIECES + tid;
+            const u32x4 *src = Xh + (size_t)(J + 1) * PIECES + tid;
 #pragma unroll
             for (int k = 0; k < PT; k++) pf[k] = src[k * 256];
             cb_next = cid[(J + 1) * 16 + c16];
             qb_next = qm[(J + 1) * 16 + c16];
         }
         if (active && J >= I) {  // (wave-uniform)
-            const u32x4j *bp = &sB[cur][lane];
-            f32x4j acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            const u32x4 *bp = &sB[cur][lane];
+            f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
             for (int st = 0; st < NS; st++)
-                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8j, bp[64 * st]), acc[st & 3], 0, 0, 0);
-            const f32x4j t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, bp[64 * st]), acc[st & 3], 0, 0, 0);
+            const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
             const bool diag = J == I;
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -226,7 +215,7 @@ __global__ __launch_bounds__(256) void join_mfma_kernel(const u32x4j *__restrict
                     pass = (uint32_t)approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qb, Kc, rho, 0.f) <= tq;
                 const uint64_t m = __ballot(pass);
                 if (m) {  // (wave-uniform)
-                    const unsigned long long slot = join_wave_slots(ctr, m, lane);
+                    const unsigned long long slot = wave_slots(ctr, m, lane);
                     if (pass && slot < cap) {
                         const uint32_t a = id[i] < cb ? id[i] : cb, b = id[i] < cb ? cb : id[i];
                         cand[slot] = ((uint64_t)a << 32) | b;
@@ -248,7 +237,7 @@ static hipError_t launch_join_mfma_kinda(uint32_t d, const void *Xh, const float
                                          uint64_t cap, unsigned long long *dCtr, hipStream_t s) {
 #define ZH_JN_CASE(DD)                                                                                                                                 \
     case DD:                                                                                                                                            \
-        hipLaunchKernelGGL((join_mfma_kernel<DD, KINDA>), dim3(blocks), dim3(256), 0, s, (const u32x4j *)Xh, rowMeta, qm, cid, T, tileA0, dFirst, n_ab, Kc, rho, \
+        hipLaunchKernelGGL((join_mfma_kernel<DD, KINDA>), dim3(blocks), dim3(256), 0, s, (const u32x4 *)Xh, rowMeta, qm, cid, T, tileA0, dFirst, n_ab, Kc, rho, \
                            dTau, dCand, cap, dCtr);                                                                                                     \
         break
     switch (d) {
@@ -275,84 +264,93 @@ hipError_t zh_launch_join_mfma(uint32_t d, int metric, int mode, const void *dXh
     return launch_join_mfma_kinda<1>(d, dXh, dRowMeta, dQm, dCid, T, tileA0, dFirst, n_ab, blocks, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
 }
 
-// The candidates' canonical keys, in the manner of range_survivors_kernel -- and their judgement.  A candidate is a << 32 | b, a < b: the key is that
-// of STORED row b against the QUERY row a, both read from the f32 table; the cosine's query norm is qnorm_kernel's sum (the canonical one) of row a.
-// A wave takes 64 candidates at a time: pair j's sums wait in lane j, so that key_of, the comparison and the pool's atomic run once for all 64.
-template <int D, int KIND>
-__global__ __launch_bounds__(256) void join_survivors_kernel(const float *__restrict__ X, int metric, int param, const uint64_t *__restrict__ cand,
-                                                             const unsigned long long *__restrict__ candCtr, uint64_t cand_cap, uint64_t max_key,
-                                                             unsigned long long *__restrict__ ctr, uint64_t *__restrict__ pv, uint64_t *__restrict__ pk,
-                                                             uint64_t cap) {
-    constexpr int NV = RowVec<D>::NV;
+// The candidates' canonical keys, in the manner of range_survivors_kernel -- and their judgement, for the three joins.  A candidate is a << 32 | b:
+// the key is that of STORED row b of table XB against the QUERY row a of table XA, both f32 tables; the cosine's query norm is qnorm_kernel's sum
+// (the canonical one) of row a.  The self-join and the forest join pass their one table twice: XA and XB are only read, so that two __restrict__
+// pointers alias there breaks no promise.  A wave takes 64 candidates at a time: pair j's sums wait in lane j, so that key_of, the comparison and
+// the pool's atomic run once for all 64.  OWNED (the forest join, candidates met in tree t): the first-tree rule comes first, only the pairs it
+// leaves get a key and *keyed += their number; the plain kernel reads none of leaf_of, T, t and keyed.  TWO = false (XA == XB, the launcher sees
+// to it): both rows' addresses come from ONE per-lane base -- the second base is a register pair, which at d = 768 (cosine) and in the OWNED
+// kernel at d >= 512 is the step from 6 waves per SIMD to 5.
+template <int D, int KIND, bool OWNED, bool TWO>
+__global__ __launch_bounds__(256) void pair_survivors_kernel(const float *__restrict__ XA, const float *__restrict__ XB, int metric, int param,
+                                                             const uint64_t *__restrict__ cand, const unsigned long long *__restrict__ candCtr,
+                                                             uint64_t cand_cap, const uint32_t *__restrict__ leaf_of, uint32_t T, uint32_t t, uint64_t max_key,
+                                                             unsigned long long *__restrict__ ctr, unsigned long long *__restrict__ keyed,
+                                                             uint64_t *__restrict__ pv, uint64_t *__restrict__ pk, uint64_t cap) {
     const uint64_t n = *candCtr;
-    if (n > cand_cap) return;  // (the pool ran over: the panel is answered by path 1)
+    if (n > cand_cap) return;  // (the pool ran over: the panel or batch is answered by path 1)
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
     for (uint64_t g = wave * 64; g < n; g += n_waves * 64) {
         const uint32_t m = n - g < 64 ? (uint32_t)(n - g) : 64u;
         const uint64_t mine = lane < m ? cand[g + lane] : 0ull;
         const uint32_t my_b = (uint32_t)mine, my_a = (uint32_t)(mine >> 32);
+        uint64_t own = 0;
+        if constexpr (OWNED) {
+            own = __ballot(lane < m && fjoin_owned(leaf_of, T, t, my_a, my_b));
+            if (!own) continue;  // (wave-uniform)
+            if (lane == 0) atomicAdd(keyed, (unsigned long long)__popcll(own));
+        }
         float m0 = 0.f, m1 = 0.f, mq = 0.f;
         for (uint32_t j = 0; j < m; j++) {
-            const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)my_b, (int)j), qrow = (uint32_t)__builtin_amdgcn_readlane((int)my_a, (int)j);
-            float4 v[NV], q[NV];
-            load_row<D>(X + (size_t)row * D, lane, v);
-            load_row<D>(X + (size_t)qrow * D, lane, q);
-            float s0 = 0.f, s1 = 0.f, qq = 0.f;
-            row_pair_sums<D, KIND>(v, q, lane, param, s0, s1);
-            if (KIND == K_COS) {
-                float4 c = make_float4(0.f, 0.f, 0.f, 0.f), cq = c;
-#pragma unroll
-                for (int jj = 0; jj < NV; jj++) {
-                    const bool act = (jj < RowVec<D>::NJ) || (lane < (uint32_t)RowVec<D>::REM4);
-                    if (act) { sq4(v[jj], c); sq4(q[jj], cq); }
-                }
-                s1 = wave_sum_canonical((c.x + c.y) + (c.z + c.w));
-                qq = wave_sum_canonical((cq.x + cq.y) + (cq.z + cq.w));
+            if constexpr (OWNED) {
+                if (!((own >> j) & 1ull)) continue;  // (wave-uniform)
             }
+            const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)my_b, (int)j), qrow = (uint32_t)__builtin_amdgcn_readlane((int)my_a, (int)j);
+            float s0 = 0.f, s1 = 0.f, qq = 0.f;
+            table_pair_sums<D, KIND, true>(TWO ? XB : XA, row, XA, qrow, lane, param, s0, s1, qq);
             if (lane == j) { m0 = s0; m1 = s1; mq = qq; }
         }
         uint64_t key = 0;
         bool hit = false;
-        if (lane < m) {
+        if (OWNED ? (bool)((own >> lane) & 1ull) : lane < m) {
             key = key_of(metric, param, m0, m1, mq);
             hit = key <= max_key;
         }
         const uint64_t hm = __ballot(hit);
         if (hm) {  // (wave-uniform)
-            const unsigned long long slot = join_wave_slots(ctr, hm, lane);
+            const unsigned long long slot = wave_slots(ctr, hm, lane);
             if (hit && slot < cap) { pv[slot] = mine; pk[slot] = key; }
         }
     }
 }
 
-template <int D>
-static void launch_join_surv_d(const float *dX, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr, uint64_t cand_cap,
-                               uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, uint32_t blocks,
-                               hipStream_t s) {
-    if (metric == ZH_COSINE)
-        hipLaunchKernelGGL((join_survivors_kernel<D, K_COS>), dim3(blocks), dim3(256), 0, s, dX, metric, mode, dCand, dCandCtr, cand_cap, max_key, dHitCtr, dPoolV,
-                           dPoolK, pool_cap);
-    else
-        hipLaunchKernelGGL((join_survivors_kernel<D, K_L2>), dim3(blocks), dim3(256), 0, s, dX, metric, mode, dCand, dCandCtr, cand_cap, max_key, dHitCtr, dPoolV,
-                           dPoolK, pool_cap);
-}
-
-hipError_t zh_launch_join_survivors(const float *dX, uint32_t d, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr,
-                                    uint64_t cand_cap, uint64_t max_key, unsigned long long *dHitCtr, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap,
-                                    hipStream_t s) {
+// dLeafOf == nullptr: the plain kernel (T, t and dKeyed are not read); the forest join has one table
+template <int D, int KIND>
+static void launch_pair_surv(const float *dXA, const float *dXB, int metric, int mode, const uint64_t *dCand, const unsigned long long *dCandCtr,
+                             uint64_t cand_cap, const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key, unsigned long long *dHitCtr,
+                             unsigned long long *dKeyed, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap, hipStream_t s) {
     // the candidate count is known on the device only: enough waves for 64 candidates each up to the pool's size, at most 4096 of them
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (cand_cap + 255) / 256));
-#define ZH_JN_SURV(DD) case DD: launch_join_surv_d<DD>(dX, metric, mode, dCand, dCandCtr, cand_cap, max_key, dHitCtr, dPoolV, dPoolK, pool_cap, blocks, s); break
+    const auto kernel = dLeafOf      ? pair_survivors_kernel<D, KIND, true, false>
+                        : dXA == dXB ? pair_survivors_kernel<D, KIND, false, false>
+                                     : pair_survivors_kernel<D, KIND, false, true>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, dXA, dXB, metric, mode, dCand, dCandCtr, cand_cap, dLeafOf, T, t, max_key, dHitCtr, dKeyed, dPoolV,
+                       dPoolK, pool_cap);
+}
+
+hipError_t zh_launch_pair_survivors(const float *dXA, const float *dXB, uint32_t d, int metric, int mode, const uint64_t *dCand,
+                                    const unsigned long long *dCandCtr, uint64_t cand_cap, const uint32_t *dLeafOf, uint32_t T, uint32_t t, uint64_t max_key,
+                                    unsigned long long *dHitCtr, unsigned long long *dKeyed, uint64_t *dPoolV, uint64_t *dPoolK, uint64_t pool_cap,
+                                    hipStream_t s) {
+    if (dLeafOf && dXA != dXB) return hipErrorInvalidValue;
+#define ZH_PAIR_SURV(DD)                                                                                                                                   \
+    case DD:                                                                                                                                                \
+        if (metric == ZH_COSINE)                                                                                                                            \
+            launch_pair_surv<DD, K_COS>(dXA, dXB, metric, mode, dCand, dCandCtr, cand_cap, dLeafOf, T, t, max_key, dHitCtr, dKeyed, dPoolV, dPoolK, pool_cap, s); \
+        else                                                                                                                                                \
+            launch_pair_surv<DD, K_L2>(dXA, dXB, metric, mode, dCand, dCandCtr, cand_cap, dLeafOf, T, t, max_key, dHitCtr, dKeyed, dPoolV, dPoolK, pool_cap, s);  \
+        break
     switch (d) {
-        ZH_JN_SURV(256);
-        ZH_JN_SURV(384);
-        ZH_JN_SURV(512);
-        ZH_JN_SURV(768);
-        ZH_JN_SURV(1024);
+        ZH_PAIR_SURV(256);
+        ZH_PAIR_SURV(384);
+        ZH_PAIR_SURV(512);
+        ZH_PAIR_SURV(768);
+        ZH_PAIR_SURV(1024);
     default: return hipErrorInvalidValue;
     }
-#undef ZH_JN_SURV
+#undef ZH_PAIR_SURV
     return hipGetLastError();
 }
 
@@ -365,7 +363,7 @@ __global__ __launch_bounds__(256) void join_panel_rows_kernel(const uint32_t *__
     const bool on = id != 0xFFFFFFFFu;
     const uint64_t m = __ballot(on);
     if (!m) return;  // (wave-uniform)
-    const unsigned long long slot = join_wave_slots(count, m, lane);
+    const unsigned long long slot = wave_slots(count, m, lane);
     if (on) list[slot] = id;
 }
 
@@ -375,41 +373,21 @@ hipError_t zh_launch_join_panel_rows(const uint32_t *dCid, uint64_t p_begin, uin
     return hipGetLastError();
 }
 
-// ---- both paths: the order.  Three stable LSD sorts of the pool: by the b bits of v, by the key, by the a bits of v -> (a, key, b) ----
-__global__ __launch_bounds__(256) void join_emit_kernel(const uint64_t *__restrict__ v, const uint64_t *__restrict__ k, uint64_t n, uint64_t id_base,
-                                                        uint64_t *__restrict__ out_a, uint64_t *__restrict__ out_b, uint64_t *__restrict__ keys) {
+// ---- both paths: the order (a, key, b): zh_launch_pool_sort (zh_range.hip) over the b bits, the key and the a bits of the pool, then the emit ----
+__global__ __launch_bounds__(256) void pair_emit_kernel(const uint64_t *__restrict__ v, const uint64_t *__restrict__ k, uint64_t n, uint64_t id_base_a,
+                                                        uint64_t id_base_b, uint64_t *__restrict__ out_a, uint64_t *__restrict__ out_b,
+                                                        uint64_t *__restrict__ keys) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) { out_a[i] = id_base + (v[i] >> 32); out_b[i] = id_base + (v[i] & 0xFFFFFFFFull); keys[i] = k[i]; }
+    if (i < n) { out_a[i] = id_base_a + (v[i] >> 32); out_b[i] = id_base_b + (v[i] & 0xFFFFFFFFull); keys[i] = k[i]; }
 }
 
-static int join_bits(uint64_t values) {  // bits that hold 0 .. values - 1
-    int b = 1;
-    while (b < 32 && (1ull << b) < values) b++;
-    return b;
-}
-
-// dTmp == nullptr: *tmp_bytes = what the three sorts of n entries need at most
-hipError_t zh_launch_join_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows, void *dTmp, size_t *tmp_bytes, uint64_t id_base, uint64_t *dOutA,
-                               uint64_t *dOutB, uint64_t *dOutKeys, hipStream_t s) {
-    hipcub::DoubleBuffer<uint64_t> v(dV[0], dV[1]), k(dK[0], dK[1]);
-    const int rb = join_bits(n_rows);
-    hipError_t e;
-    if (!dTmp) {
-        size_t a = 0, b = 0, c = 0;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, a, v, k, n, 0, rb, s)) != hipSuccess) return e;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, b, k, v, n, 0, 64, s)) != hipSuccess) return e;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, c, v, k, n, 32, 32 + rb, s)) != hipSuccess) return e;
-        *tmp_bytes = std::max<size_t>(std::max(a, b), std::max<size_t>(c, 1));
-        return hipSuccess;
-    }
-    if (!n) return hipSuccess;
-    size_t bytes = *tmp_bytes;
-    if ((e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, v, k, n, 0, rb, s)) != hipSuccess) return e;
-    bytes = *tmp_bytes;
-    if ((e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, k, v, n, 0, 64, s)) != hipSuccess) return e;
-    bytes = *tmp_bytes;
-    if ((e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, v, k, n, 32, 32 + rb, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(join_emit_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const uint64_t *)v.Current(), (const uint64_t *)k.Current(), n,
-                       id_base, dOutA, dOutB, dOutKeys);
+// the pool of a join ordered by (a, key, b) and written out: the b bits of v hold n_rows_b values, the a bits n_rows_a; each side has its id base
+hipError_t zh_launch_pair_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows_a, uint64_t n_rows_b, void *dTmp, size_t *tmp_bytes,
+                               uint64_t id_base_a, uint64_t id_base_b, uint64_t *dOutA, uint64_t *dOutB, uint64_t *dOutKeys, hipStream_t s) {
+    if (dTmp && !n) return hipSuccess;
+    const uint64_t *v = nullptr, *k = nullptr;
+    const hipError_t e = zh_launch_pool_sort(dV, dK, n, n_rows_b, n_rows_a, false, dTmp, tmp_bytes, &v, &k, s);
+    if (e != hipSuccess || !dTmp) return e;
+    hipLaunchKernelGGL(pair_emit_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, v, k, n, id_base_a, id_base_b, dOutA, dOutB, dOutKeys);
     return hipGetLastError();
 }

@@ -29,10 +29,6 @@
 #include "zh_internal.h"
 #include "zh_device.h"
 
-typedef _Float16 f16x8k __attribute__((ext_vector_type(8)));
-typedef float f32x4k __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4k __attribute__((ext_vector_type(4)));
-
 // under a row order: pos[row] = the position of live row `row` in the copy (cid: join_prep_kernel's id-or-masked word per position)
 __global__ __launch_bounds__(256) void knn_rowpos_kernel(const uint32_t *__restrict__ cid, uint64_t n_pos, uint32_t *__restrict__ pos) {
     const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -50,13 +46,13 @@ hipError_t zh_launch_knn_rowpos(const uint32_t *dCid, uint64_t n_pos, uint32_t *
 // The panel's tiles: line b (live row rows[b], b < B) of panel tile b / 16 gets the 16-byte pieces of its position in the copy.  A tile is NS * 64
 // pieces, piece 64 st + 16 h + line: thread t of the grid writes piece t of the panel's tiles (line = t % 16 runs fastest: the stores are
 // contiguous, and so are the loads where the panel's rows are).  Lines past B (the last tile's tail) are zero and masked (pid = UINT32_MAX).
-__global__ __launch_bounds__(256) void knn_panel_kernel(const u32x4k *__restrict__ Xh, const float2 *__restrict__ rowMeta, const uint32_t *__restrict__ pos,
-                                                        const uint32_t *__restrict__ rows, uint32_t B, uint32_t PT, uint32_t pieces, u32x4k *__restrict__ A,
+__global__ __launch_bounds__(256) void knn_panel_kernel(const u32x4 *__restrict__ Xh, const float2 *__restrict__ rowMeta, const uint32_t *__restrict__ pos,
+                                                        const uint32_t *__restrict__ rows, uint32_t B, uint32_t PT, uint32_t pieces, u32x4 *__restrict__ A,
                                                         float2 *__restrict__ pmeta, uint32_t *__restrict__ pid) {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (uint64_t)PT * pieces) return;
     const uint32_t tile = (uint32_t)(t / pieces), w = (uint32_t)(t % pieces), b = tile * 16 + (w & 15);
-    u32x4k v = {0u, 0u, 0u, 0u};
+    u32x4 v = {0u, 0u, 0u, 0u};
     uint32_t row = 0xFFFFFFFFu;
     float2 rm = make_float2(0.f, 0.f);
     if (b < B) {
@@ -74,34 +70,34 @@ hipError_t zh_launch_knn_panel(uint32_t d, const void *dXh, const float2 *dRowMe
     if (!B) return hipSuccess;
     const uint32_t PT = (B + 15) / 16, pieces = d / 32 * 64;
     const uint64_t n = (uint64_t)PT * pieces;
-    hipLaunchKernelGGL(knn_panel_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const u32x4k *)dXh, dRowMeta, dPos, dRows, B, PT, pieces,
-                       (u32x4k *)dA, dPMeta, dPid);
+    hipLaunchKernelGGL(knn_panel_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const u32x4 *)dXh, dRowMeta, dPos, dRows, B, PT, pieces,
+                       (u32x4 *)dA, dPMeta, dPid);
     return hipGetLastError();
 }
 
 // grid (chunks of `ch` column tiles of [Jt0, Jt1), held blocks of four panel tiles)
 template <int D, int KINDA>
-__global__ __launch_bounds__(256) void knn_mfma_kernel(const u32x4k *__restrict__ Xh, const float4 *__restrict__ qm, const uint32_t *__restrict__ cid,
-                                                       uint64_t Jt0, uint64_t Jt1, uint32_t ch, const u32x4k *__restrict__ PA,
+__global__ __launch_bounds__(256) void knn_mfma_kernel(const u32x4 *__restrict__ Xh, const float4 *__restrict__ qm, const uint32_t *__restrict__ cid,
+                                                       uint64_t Jt0, uint64_t Jt1, uint32_t ch, const u32x4 *__restrict__ PA,
                                                        const float2 *__restrict__ pmeta, const uint32_t *__restrict__ pid, uint32_t PT, float Kc, float rho,
                                                        const uint32_t *__restrict__ tau, uint32_t *__restrict__ cnt, uint32_t *__restrict__ lid,
                                                        uint32_t *__restrict__ llo, uint32_t *__restrict__ lhi, uint32_t cap, uint32_t *__restrict__ over) {
     constexpr int NS = D / 32;        // MFMA steps of a tile (K = 32 each) = its KiB
     constexpr int PIECES = NS * 64;   // 16-byte pieces of a tile
     constexpr int PT_ = PIECES / 256; // ... per thread of the block
-    __shared__ u32x4k sB[2][PIECES];
+    __shared__ u32x4 sB[2][PIECES];
     const uint32_t tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, h = lane >> 4;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const uint32_t I = blockIdx.y * 4 + wid;  // the wave's panel tile
     const uint64_t Jb = Jt0 + (uint64_t)blockIdx.x * ch, Je = Jb + ch < Jt1 ? Jb + ch : Jt1;
     const bool active = I < PT;  // (wave-uniform; an idle wave of the panel's last block still moves tiles and meets the barriers)
-    f16x8k A[NS];
+    f16x8 A[NS];
     uint32_t id[4], line[4], tq[4];
     float2 meta[4];
     if (active) {
-        const u32x4k *tp = PA + (size_t)I * PIECES + lane;
+        const u32x4 *tp = PA + (size_t)I * PIECES + lane;
 #pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8k, tp[64 * st]);
+        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, tp[64 * st]);
         // this lane's outputs: lines 4 h + i of the held tile (register i), column c16 = row c16 of tile J
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -113,12 +109,12 @@ __global__ __launch_bounds__(256) void knn_mfma_kernel(const u32x4k *__restrict_
         }
     } else {
 #pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = f16x8k{0, 0, 0, 0, 0, 0, 0, 0};
+        for (int st = 0; st < NS; st++) A[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int i = 0; i < 4; i++) { id[i] = 0xFFFFFFFFu; line[i] = 0; tq[i] = 0; meta[i] = make_float2(0.f, 0.f); }
     }
     {
-        const u32x4k *src = Xh + (size_t)Jb * PIECES + tid;
+        const u32x4 *src = Xh + (size_t)Jb * PIECES + tid;
 #pragma unroll
         for (int k = 0; k < PT_; k++) sB[0][k * 256 + tid] = src[k * 256];
     }
@@ -131,21 +127,21 @@ __global__ __launch_bounds__(256) void knn_mfma_kernel(const u32x4k *__restrict_
         const bool more = J + 1 < Je;  // (block-uniform)
         const uint32_t cb = cb_next;
         const float4 qb = qb_next;
-        u32x4k pf[PT_];
+        u32x4 pf[PT_];
         if (more) {
-            const u32x4k *src = Xh + (size_t)(J + 1) * PIECES + tid;
+            const u32x4 *src = Xh + (size_t)(J + 1) * PIECES + tid;
 #pragma unroll
             for (int k = 0; k < PT_; k++) pf[k] = src[k * 256];
             cb_next = cid[(J + 1) * 16 + c16];
             qb_next = qm[(J + 1) * 16 + c16];
         }
         if (active) {  // (wave-uniform)
-            const u32x4k *bp = &sB[cur][lane];
-            f32x4k acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            const u32x4 *bp = &sB[cur][lane];
+            f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
             for (int st = 0; st < NS; st++)
-                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8k, bp[64 * st]), acc[st & 3], 0, 0, 0);
-            const f32x4k t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, bp[64 * st]), acc[st & 3], 0, 0, 0);
+            const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 bool pass = false;
@@ -195,7 +191,7 @@ static hipError_t launch_knn_mfma_kinda(uint32_t d, const ZhExact2 &e, const flo
     const dim3 grid((uint32_t)((Jt1 - Jt0 + ch - 1) / ch), n_ab);
 #define ZH_KN_CASE(DD)                                                                                                                                     \
     case DD:                                                                                                                                                \
-        hipLaunchKernelGGL((knn_mfma_kernel<DD, KINDA>), grid, dim3(256), 0, s, (const u32x4k *)e.Xh, qm, cid, Jt0, Jt1, ch, (const u32x4k *)dA, pmeta, pid, PT, \
+        hipLaunchKernelGGL((knn_mfma_kernel<DD, KINDA>), grid, dim3(256), 0, s, (const u32x4 *)e.Xh, qm, cid, Jt0, Jt1, ch, (const u32x4 *)dA, pmeta, pid, PT, \
                            e.Kc, e.rho, e.tau, e.cnt, e.lid, e.llo, e.lhi, e.cap, e.over);                                                                  \
         break
     switch (d) {

@@ -15,19 +15,6 @@
 #include "zh_internal.h"
 #include "zh_device.h"
 
-typedef _Float16 f16x8r __attribute__((ext_vector_type(8)));
-typedef float f32x4r __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4r __attribute__((ext_vector_type(4)));
-
-// the lanes of `m` (a ballot) get consecutive pool slots: one atomic for the wave, taken by lane 0 (every lane of the wave is active at the call)
-__device__ __forceinline__ unsigned long long range_wave_slots(unsigned long long *__restrict__ ctr, uint64_t m, uint32_t lane) {
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(ctr, (unsigned long long)__popcll(m));
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
-    return (((unsigned long long)hi << 32) | lo) + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-}
-
 // ---- path 1: the hits of a keyed row chunk.  grid (ceil(nr / 256), B): a wave reads 64 consecutive positions of ONE query ----
 __global__ __launch_bounds__(256) void range_collect_kernel(const uint64_t *__restrict__ keys, uint64_t ld, const uint32_t *__restrict__ live, uint64_t p0,
                                                             uint32_t nr, const uint64_t *__restrict__ maxk, uint32_t *__restrict__ cnt,
@@ -44,7 +31,7 @@ __global__ __launch_bounds__(256) void range_collect_kernel(const uint64_t *__re
     const uint64_t m = __ballot(hit);
     if (!m) return;  // (wave-uniform)
     if (lane == 0) atomicAdd(&cnt[b], (uint32_t)__popcll(m));  // always: the count stays exact when the pool is full
-    const unsigned long long slot = range_wave_slots(ctr, m, lane);
+    const unsigned long long slot = wave_slots(ctr, m, lane);
     if (hit && slot < cap) {
         pv[slot] = ((uint64_t)b << 32) | live[p0 + rl];
         pk[slot] = key;
@@ -98,9 +85,9 @@ hipError_t zh_launch_range_tau(const uint64_t *dMaxKeys, uint32_t B, int metric,
 // No per-query cap and no prune pass: tau never moves, so one launch covers the table.  *ctr counts every candidate; past cap they are not stored and
 // the host answers the batch by path 1.
 template <int D, int KINDA>
-__global__ __launch_bounds__(256) void range_mfma_kernel(const u32x4r *__restrict__ Xh, const float2 *__restrict__ rowMeta, const uint32_t *__restrict__ perm,
+__global__ __launch_bounds__(256) void range_mfma_kernel(const u32x4 *__restrict__ Xh, const float2 *__restrict__ rowMeta, const uint32_t *__restrict__ perm,
                                                          uint64_t perm_rows, const uint32_t *__restrict__ liveBits, uint64_t p_begin, uint64_t p_end,
-                                                         const u32x4r *__restrict__ Qh, const float4 *__restrict__ qmeta, uint32_t B, float Kc, float rho,
+                                                         const u32x4 *__restrict__ Qh, const float4 *__restrict__ qmeta, uint32_t B, float Kc, float rho,
                                                          const uint32_t *__restrict__ tau, uint64_t *__restrict__ cand, uint64_t cap,
                                                          unsigned long long *__restrict__ ctr) {
     constexpr int NS = D / 32;  // MFMA steps of a tile (K = 32 each)
@@ -109,10 +96,10 @@ __global__ __launch_bounds__(256) void range_mfma_kernel(const u32x4r *__restric
     const uint64_t tile = p_begin / 16 + (uint64_t)blockIdx.x * 4 + wid;
     const uint64_t p0 = tile * 16;
     if (p0 >= p_end) return;
-    f16x8r A[NS];
-    const u32x4r *tp = Xh + (size_t)tile * (NS * 64) + lane;
+    f16x8 A[NS];
+    const u32x4 *tp = Xh + (size_t)tile * (NS * 64) + lane;
 #pragma unroll
-    for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8r, __builtin_nontemporal_load(tp + 64 * st));
+    for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, __builtin_nontemporal_load(tp + 64 * st));
     // this lane's outputs: rows 4 h + i of the tile (register i), column c16
     bool valid[4];
     uint32_t id[4];
@@ -127,12 +114,12 @@ __global__ __launch_bounds__(256) void range_mfma_kernel(const u32x4r *__restric
     }
     for (uint32_t q0 = 0; q0 < B; q0 += 16) {
         const uint32_t b = q0 + c16, bq = b < B ? b : B - 1;
-        const u32x4r *qp = Qh + (size_t)bq * (D / 8) + h;  // step st: piece 4 st + h of the query (qhalf layout 1 = the A operand's k order)
-        f32x4r acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        const u32x4 *qp = Qh + (size_t)bq * (D / 8) + h;  // step st: piece 4 st + h of the query (qhalf layout 1 = the A operand's k order)
+        f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int st = 0; st < NS; st++)
-            acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8r, qp[4 * st]), acc[st & 3], 0, 0, 0);
-        const f32x4r t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+            acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, qp[4 * st]), acc[st & 3], 0, 0, 0);
+        const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
         const float4 qm = qmeta[bq];
         const uint32_t tq = tau[bq];
 #pragma unroll
@@ -141,7 +128,7 @@ __global__ __launch_bounds__(256) void range_mfma_kernel(const u32x4r *__restric
             if (b < B && valid[i]) pass = (uint32_t)approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qm, Kc, rho, 0.f) <= tq;
             const uint64_t m = __ballot(pass);
             if (m) {  // (wave-uniform)
-                const unsigned long long slot = range_wave_slots(ctr, m, lane);
+                const unsigned long long slot = wave_slots(ctr, m, lane);
                 if (pass && slot < cap) cand[slot] = ((uint64_t)b << 32) | id[i];
             }
         }
@@ -154,8 +141,8 @@ static hipError_t launch_range_mfma_kinda(uint32_t d, const ZhExact2 &e, uint64_
     const uint64_t tiles = (p_end - p_begin + 15) / 16, blocks = (tiles + 3) / 4;
 #define ZH_RG_CASE(DD)                                                                                                                              \
     case DD:                                                                                                                                         \
-        hipLaunchKernelGGL((range_mfma_kernel<DD, KINDA>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4r *)e.Xh, e.rowMeta, e.perm, e.perm_rows, \
-                           e.liveBits, p_begin, p_end, (const u32x4r *)e.Qh, e.qmeta, e.B, e.Kc, e.rho, (const uint32_t *)e.tau, dCand, cap, dCtr);     \
+        hipLaunchKernelGGL((range_mfma_kernel<DD, KINDA>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4 *)e.Xh, e.rowMeta, e.perm, e.perm_rows, \
+                           e.liveBits, p_begin, p_end, (const u32x4 *)e.Qh, e.qmeta, e.B, e.Kc, e.rho, (const uint32_t *)e.tau, dCand, cap, dCtr);     \
         break
     switch (d) {
         ZH_RG_CASE(256);
@@ -186,7 +173,6 @@ __global__ __launch_bounds__(256) void range_survivors_kernel(const float *__res
                                                               uint64_t cand_cap, const uint64_t *__restrict__ maxk, uint32_t *__restrict__ cnt,
                                                               unsigned long long *__restrict__ ctr, uint64_t *__restrict__ pv, uint64_t *__restrict__ pk,
                                                               uint64_t cap) {
-    constexpr int NV = RowVec<D>::NV;
     const uint64_t n = *candCtr;
     if (n > cand_cap) return;  // (the pool ran over: the batch is answered by path 1)
     const uint32_t lane = threadIdx.x & 63;
@@ -198,20 +184,8 @@ __global__ __launch_bounds__(256) void range_survivors_kernel(const float *__res
         float m0 = 0.f, m1 = 0.f;
         for (uint32_t j = 0; j < m; j++) {
             const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)my_row, (int)j), b = (uint32_t)__builtin_amdgcn_readlane((int)my_b, (int)j);
-            float4 v[NV], q[NV];
-            load_row<D>(X + (size_t)row * D, lane, v);
-            load_row<D>(Q + (size_t)b * D, lane, q);
-            float s0 = 0.f, s1 = 0.f;
-            row_pair_sums<D, KIND>(v, q, lane, param, s0, s1);
-            if (KIND == K_COS) {
-                float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int jj = 0; jj < NV; jj++) {
-                    const bool act = (jj < RowVec<D>::NJ) || (lane < (uint32_t)RowVec<D>::REM4);
-                    if (act) sq4(v[jj], c);
-                }
-                s1 = wave_sum_canonical((c.x + c.y) + (c.z + c.w));
-            }
+            float s0 = 0.f, s1 = 0.f, qq = 0.f;
+            table_pair_sums<D, KIND, false>(X, row, Q, b, lane, param, s0, s1, qq);  // (the query's norm is QQ's, below)
             if (lane == j) { m0 = s0; m1 = s1; }
         }
         uint64_t key = 0;
@@ -222,7 +196,7 @@ __global__ __launch_bounds__(256) void range_survivors_kernel(const float *__res
         }
         const uint64_t hm = __ballot(hit);
         if (hm) {  // (wave-uniform)
-            const unsigned long long slot = range_wave_slots(ctr, hm, lane);
+            const unsigned long long slot = wave_slots(ctr, hm, lane);
             if (hit) {
                 atomicAdd(&cnt[my_b], 1u);
                 if (slot < cap) { pv[slot] = mine; pk[slot] = key; }
@@ -284,41 +258,46 @@ hipError_t zh_launch_range_offsets(const uint32_t *dCnt, uint32_t B, uint64_t ba
     return hipGetLastError();
 }
 
-// ---- both paths: the order.  Three stable LSD sorts of the pool: by the row bits of v, by the key, by the query bits of v -> (query, key, row) ----
+// ---- both paths: the order, for every pool of this library (the joins' too: zh_join.hip).  Three stable LSD sorts of (v, k): by the low field of
+// v (lo_values of them), by the key, by the high field of v (hi_values of them; skip_high: there is one value only and the pass is left out)
+// -> (high, key, low).  *v_out / *k_out = the ordered arrays.  dTmp == nullptr: *tmp_bytes = what the three sorts of n entries need at most ----
+hipError_t zh_launch_pool_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t lo_values, uint64_t hi_values, bool skip_high, void *dTmp,
+                               size_t *tmp_bytes, const uint64_t **v_out, const uint64_t **k_out, hipStream_t s) {
+    hipcub::DoubleBuffer<uint64_t> v(dV[0], dV[1]), k(dK[0], dK[1]);
+    const int lb = field_bits(lo_values), hb = field_bits(hi_values);
+    hipError_t e;
+    if (!dTmp) {
+        size_t a = 0, b = 0, c = 0;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, a, v, k, n, 0, lb, s)) != hipSuccess) return e;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, b, k, v, n, 0, 64, s)) != hipSuccess) return e;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, c, v, k, n, 32, 32 + hb, s)) != hipSuccess) return e;
+        *tmp_bytes = std::max<size_t>(std::max(a, b), std::max<size_t>(c, 1));
+        return hipSuccess;
+    }
+    size_t bytes = *tmp_bytes;
+    if ((e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, v, k, n, 0, lb, s)) != hipSuccess) return e;
+    bytes = *tmp_bytes;
+    if ((e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, k, v, n, 0, 64, s)) != hipSuccess) return e;
+    bytes = *tmp_bytes;
+    if (!skip_high && (e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, v, k, n, 32, 32 + hb, s)) != hipSuccess) return e;
+    *v_out = v.Current();
+    *k_out = k.Current();
+    return hipSuccess;
+}
+
 __global__ __launch_bounds__(256) void range_emit_kernel(const uint64_t *__restrict__ v, const uint64_t *__restrict__ k, uint64_t n, uint64_t id_base,
                                                          uint64_t *__restrict__ ids, uint64_t *__restrict__ keys) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) { ids[i] = id_base + (v[i] & 0xFFFFFFFFull); keys[i] = k[i]; }
 }
 
-static int range_bits(uint64_t values) {  // bits that hold 0 .. values - 1
-    int b = 1;
-    while (b < 32 && (1ull << b) < values) b++;
-    return b;
-}
-
-// dTmp == nullptr: *tmp_bytes = what the three sorts of n entries need at most
+// the pool of an internal batch ordered by (query, key, row) and written out; B == 1 has one query value and no third pass
 hipError_t zh_launch_range_sort(uint64_t *dV[2], uint64_t *dK[2], uint64_t n, uint64_t n_rows, uint32_t B, void *dTmp, size_t *tmp_bytes, uint64_t id_base,
                                 uint64_t *dOutIds, uint64_t *dOutKeys, hipStream_t s) {
-    hipcub::DoubleBuffer<uint64_t> v(dV[0], dV[1]), k(dK[0], dK[1]);
-    const int rb = range_bits(n_rows), qb = range_bits(B);
-    hipError_t e;
-    if (!dTmp) {
-        size_t a = 0, b = 0, c = 0;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, a, v, k, n, 0, rb, s)) != hipSuccess) return e;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, b, k, v, n, 0, 64, s)) != hipSuccess) return e;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, c, v, k, n, 32, 32 + qb, s)) != hipSuccess) return e;
-        *tmp_bytes = std::max<size_t>(std::max(a, b), std::max<size_t>(c, 1));
-        return hipSuccess;
-    }
-    if (!n) return hipSuccess;
-    size_t bytes = *tmp_bytes;
-    if ((e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, v, k, n, 0, rb, s)) != hipSuccess) return e;
-    bytes = *tmp_bytes;
-    if ((e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, k, v, n, 0, 64, s)) != hipSuccess) return e;
-    bytes = *tmp_bytes;
-    if (B > 1 && (e = hipcub::DeviceRadixSort::SortPairs(dTmp, bytes, v, k, n, 32, 32 + qb, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(range_emit_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const uint64_t *)v.Current(), (const uint64_t *)k.Current(), n,
-                       id_base, dOutIds, dOutKeys);
+    if (dTmp && !n) return hipSuccess;
+    const uint64_t *v = nullptr, *k = nullptr;
+    const hipError_t e = zh_launch_pool_sort(dV, dK, n, n_rows, B, B <= 1, dTmp, tmp_bytes, &v, &k, s);
+    if (e != hipSuccess || !dTmp) return e;
+    hipLaunchKernelGGL(range_emit_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, v, k, n, id_base, dOutIds, dOutKeys);
     return hipGetLastError();
 }

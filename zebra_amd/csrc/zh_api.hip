@@ -4144,59 +4144,79 @@ static int range_finish(zh_index *ix, size_t b, const RangeRun &run, zh_range_in
     return ZH_OK;
 }
 
-extern "C" int zh_search_range_batch_device(zh_index *ix, const float *d_q, size_t b, const uint64_t *d_max_keys, int metric, int mode, uint64_t capacity,
-                                            uint64_t *d_out_offsets, uint64_t *d_out_ids, uint64_t *d_out_keys, uint64_t *d_out_total, void *stream) {
-    int rc = range_args(ix, d_q, b, d_max_keys, metric, mode, capacity, d_out_offsets, d_out_ids, d_out_keys, d_out_total, "zh_search_range_batch_device");
-    if (rc) return rc;
+// Both range families' loop over internal batches of at most ZH_EXACT_BATCH queries; one(dQ, nb, dMaxK, dOff) answers a batch on device pointers
+// (range_one / frange_one: nb + 1 offsets at dOff).  host: q, max_keys and out_offsets are HOST arrays -- each batch goes through the staging
+// (ex_Q, rg_maxk, rg_off) and is waited for; otherwise they are device arrays and the caller waits once, after the total (put_total).
+template <typename One>
+static int range_batches(zh_index *ix, const float *q, size_t b, const uint64_t *max_keys, uint64_t *out_offsets, bool host, hipStream_t s, One one) {
+    const size_t nb_max = std::min<size_t>(ZH_EXACT_BATCH, b), d = ix->opt.dim;
+    int rc;
+    if (host && ((rc = ix->ex_Q.ensure(nb_max * d * 4)) || (rc = ix->rg_maxk.ensure(nb_max * 8)) || (rc = ix->rg_off.ensure((nb_max + 1) * 8)))) return rc;
+    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
+        if (!host) {
+            if ((rc = one(q + b0 * d, nb, max_keys + b0, out_offsets + b0))) return rc;
+            continue;
+        }
+        HIPCHK(hipMemcpyAsync(ix->ex_Q.p, q + b0 * d, (size_t)nb * d * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(ix->rg_maxk.p, max_keys + b0, (size_t)nb * 8, hipMemcpyHostToDevice, s));
+        if ((rc = one(ix->ex_Q.as<float>(), nb, ix->rg_maxk.as<uint64_t>(), ix->rg_off.as<uint64_t>()))) return rc;
+        HIPCHK(hipMemcpyAsync(out_offsets + b0, ix->rg_off.p, ((size_t)nb + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return ZH_OK;
+}
+
+// A call's total to its caller: *out_total on the host; otherwise over the stream into device memory, and the call's one wait (`total` is this
+// frame's until then).
+static int put_total(uint64_t total, uint64_t *out_total, bool host, hipStream_t s) {
+    if (host) {
+        *out_total = total;
+        return ZH_OK;
+    }
+    HIPCHK(hipMemcpyAsync(out_total, &total, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return ZH_OK;
+}
+
+// both entry points once the arguments have been judged.  host: b > 0, and the caller has zeroed out_offsets[0] and the total; the device call
+// comes here with b == 0 too and zeroes them on its stream
+static int range_call(zh_index *ix, const float *q, size_t b, const uint64_t *max_keys, int metric, int mode, uint64_t capacity, uint64_t *out_offsets,
+                      uint64_t *out_ids, uint64_t *out_keys, uint64_t *out_total, bool host, void *stream, const char *who) {
     std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
     ScratchGuard guard{ix, SCRATCH_RANGE};
     const hipStream_t s = call_stream(ix, stream);
-    const uint32_t d = ix->opt.dim;
     RangeRun run;
     run.capacity = capacity;
     zh_range_info inf{};
     inf.path = 1;
-    HIPCHK(hipMemsetAsync(d_out_offsets, 0, 8, s));
-    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
-        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
-        if ((rc = range_one(ix, d_q + b0 * d, nb, d_max_keys + b0, metric, mode, &run, d_out_offsets + b0, d_out_ids, d_out_keys, false, s, &inf))) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(d_out_total, &run.total, 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return range_finish(ix, b, run, inf, "zh_search_range_batch_device");
+    if (!host) HIPCHK(hipMemsetAsync(out_offsets, 0, 8, s));
+    rc = range_batches(ix, q, b, max_keys, out_offsets, host, s, [&](const float *dQ, uint32_t nb, const uint64_t *dMaxK, uint64_t *dOff) {
+        return range_one(ix, dQ, nb, dMaxK, metric, mode, &run, dOff, out_ids, out_keys, host, s, &inf);
+    });
+    if (rc || (rc = put_total(run.total, out_total, host, s))) return rc;
+    return range_finish(ix, b, run, inf, who);
+}
+
+extern "C" int zh_search_range_batch_device(zh_index *ix, const float *d_q, size_t b, const uint64_t *d_max_keys, int metric, int mode, uint64_t capacity,
+                                            uint64_t *d_out_offsets, uint64_t *d_out_ids, uint64_t *d_out_keys, uint64_t *d_out_total, void *stream) {
+    const char *who = "zh_search_range_batch_device";
+    int rc = range_args(ix, d_q, b, d_max_keys, metric, mode, capacity, d_out_offsets, d_out_ids, d_out_keys, d_out_total, who);
+    if (rc) return rc;
+    return range_call(ix, d_q, b, d_max_keys, metric, mode, capacity, d_out_offsets, d_out_ids, d_out_keys, d_out_total, false, stream, who);
 }
 
 extern "C" int zh_search_range_batch(zh_index *ix, const float *q, size_t b, const uint64_t *max_keys, int metric, int mode, uint64_t capacity,
                                      uint64_t *out_offsets, uint64_t *out_ids, uint64_t *out_keys, uint64_t *out_total) {
-    int rc = range_args(ix, q, b, max_keys, metric, mode, capacity, out_offsets, out_ids, out_keys, out_total, "zh_search_range_batch");
+    const char *who = "zh_search_range_batch";
+    int rc = range_args(ix, q, b, max_keys, metric, mode, capacity, out_offsets, out_ids, out_keys, out_total, who);
     if (rc) return rc;
     out_offsets[0] = 0;
     *out_total = 0;
     if (b == 0) return ZH_OK;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    ScratchGuard guard{ix, SCRATCH_RANGE};
-    const hipStream_t s = ix->stream;
-    const uint32_t d = ix->opt.dim;
-    const size_t nb_max = std::min<size_t>(ZH_EXACT_BATCH, b);
-    if ((rc = ix->ex_Q.ensure(nb_max * d * 4)) || (rc = ix->rg_maxk.ensure(nb_max * 8)) || (rc = ix->rg_off.ensure((nb_max + 1) * 8))) return rc;
-    RangeRun run;
-    run.capacity = capacity;
-    zh_range_info inf{};
-    inf.path = 1;
-    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
-        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
-        HIPCHK(hipMemcpyAsync(ix->ex_Q.p, q + b0 * d, (size_t)nb * d * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(ix->rg_maxk.p, max_keys + b0, (size_t)nb * 8, hipMemcpyHostToDevice, s));
-        if ((rc = range_one(ix, ix->ex_Q.as<float>(), nb, ix->rg_maxk.as<uint64_t>(), metric, mode, &run, ix->rg_off.as<uint64_t>(), out_ids, out_keys, true,
-                            s, &inf)))
-            return rc;
-        HIPCHK(hipMemcpyAsync(out_offsets + b0, ix->rg_off.p, ((size_t)nb + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    *out_total = run.total;
-    return range_finish(ix, b, run, inf, "zh_search_range_batch");
+    return range_call(ix, q, b, max_keys, metric, mode, capacity, out_offsets, out_ids, out_keys, out_total, true, nullptr, who);
 }
 
 extern "C" int zh_search_range_info(const zh_index *ix, zh_range_info *out) { return get_info(ix, &zh_index::rg_info, out, "zh_search_range_info"); }
@@ -4373,6 +4393,13 @@ static int join_finish(zh_index *ix, const zh_index *ib, uint64_t hits, uint64_t
     return ZH_OK;
 }
 
+// How the three joins' entry points end, rc being their *_run's: past the capacity (ZH_ELIMIT) the total still goes to the caller, as put_total does it.
+static int join_total(int rc, uint64_t total, uint64_t *out_total, bool host, hipStream_t s) {
+    if (rc && rc != ZH_ELIMIT) return rc;
+    const int rt = put_total(total, out_total, host, s);
+    return rt ? rt : rc;
+}
+
 // The call on the index's device (under mu, exclusive; exact_live_rows has run).  host_out: outA / outB / outKeys are HOST arrays, filled through
 // staging; otherwise device arrays.  *total = the pairs, exact whatever the capacity.
 static int join_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *outA, uint64_t *outB, uint64_t *outKeys, bool host_out,
@@ -4406,20 +4433,24 @@ static int join_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint64
     return join_finish(ix, ix, hits, capacity, outA, outB, outKeys, host_out, s, total, inf, &zh_index::jn_info, who);
 }
 
-extern "C" int zh_self_join_device(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *d_out_a, uint64_t *d_out_b,
-                                   uint64_t *d_out_keys, uint64_t *d_out_total, void *stream) {
-    int rc = join_args(ix, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, d_out_total, "zh_self_join_device");
-    if (rc) return rc;
+// both entry points once the arguments have been judged (host: the caller has zeroed the total)
+static int join_call(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b, uint64_t *out_keys,
+                     uint64_t *out_total, bool host, void *stream, const char *who) {
     std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
     ScratchGuard guard{ix, SCRATCH_JOIN};
     const hipStream_t s = call_stream(ix, stream);
     uint64_t total = 0;
-    rc = join_run(ix, max_key, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, false, s, &total, "zh_self_join_device");
-    if (rc && rc != ZH_ELIMIT) return rc;
-    HIPCHK(hipMemcpyAsync(d_out_total, &total, 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return rc;
+    rc = join_run(ix, max_key, metric, mode, capacity, out_a, out_b, out_keys, host, s, &total, who);
+    return join_total(rc, total, out_total, host, s);
+}
+
+extern "C" int zh_self_join_device(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *d_out_a, uint64_t *d_out_b,
+                                   uint64_t *d_out_keys, uint64_t *d_out_total, void *stream) {
+    int rc = join_args(ix, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, d_out_total, "zh_self_join_device");
+    if (rc) return rc;
+    return join_call(ix, max_key, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, d_out_total, false, stream, "zh_self_join_device");
 }
 
 extern "C" int zh_self_join(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b, uint64_t *out_keys,
@@ -4427,14 +4458,7 @@ extern "C" int zh_self_join(zh_index *ix, uint64_t max_key, int metric, int mode
     int rc = join_args(ix, metric, mode, capacity, out_a, out_b, out_keys, out_total, "zh_self_join");
     if (rc) return rc;
     *out_total = 0;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    ScratchGuard guard{ix, SCRATCH_JOIN};
-    uint64_t total = 0;
-    rc = join_run(ix, max_key, metric, mode, capacity, out_a, out_b, out_keys, true, ix->stream, &total, "zh_self_join");
-    if (rc && rc != ZH_ELIMIT) return rc;
-    *out_total = total;
-    return rc;
+    return join_call(ix, max_key, metric, mode, capacity, out_a, out_b, out_keys, out_total, true, nullptr, "zh_self_join");
 }
 
 extern "C" int zh_self_join_info(const zh_index *ix, zh_join_info *out) { return get_info(ix, &zh_index::jn_info, out, "zh_self_join_info"); }
@@ -4581,20 +4605,24 @@ static int xjoin_run(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, i
     return join_finish(ia, ib, hits, capacity, outA, outB, outKeys, host_out, s, total, inf, &zh_index::xj_info, who);
 }
 
+// both entry points once the arguments have been judged (host: the caller has zeroed the total)
+static int xjoin_call(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b,
+                      uint64_t *out_keys, uint64_t *out_total, bool host, void *stream, const char *who) {
+    XjoinLocks locks(ia, ib);
+    int rc = xjoin_state(ia, ib, who);
+    if (rc) return rc;
+    ScratchGuard guard{ia, SCRATCH_XJOIN};
+    const hipStream_t s = call_stream(ia, stream);
+    uint64_t total = 0;
+    rc = xjoin_run(ia, ib, max_key, metric, mode, capacity, out_a, out_b, out_keys, host, s, &total, who);
+    return join_total(rc, total, out_total, host, s);
+}
+
 extern "C" int zh_cross_join_device(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *d_out_a,
                                     uint64_t *d_out_b, uint64_t *d_out_keys, uint64_t *d_out_total, void *stream) {
     int rc = xjoin_args(ia, ib, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, d_out_total, "zh_cross_join_device");
     if (rc) return rc;
-    XjoinLocks locks(ia, ib);
-    if ((rc = xjoin_state(ia, ib, "zh_cross_join_device"))) return rc;
-    ScratchGuard guard{ia, SCRATCH_XJOIN};
-    const hipStream_t s = call_stream(ia, stream);
-    uint64_t total = 0;
-    rc = xjoin_run(ia, ib, max_key, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, false, s, &total, "zh_cross_join_device");
-    if (rc && rc != ZH_ELIMIT) return rc;
-    HIPCHK(hipMemcpyAsync(d_out_total, &total, 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return rc;
+    return xjoin_call(ia, ib, max_key, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, d_out_total, false, stream, "zh_cross_join_device");
 }
 
 extern "C" int zh_cross_join(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b,
@@ -4602,14 +4630,7 @@ extern "C" int zh_cross_join(zh_index *ia, zh_index *ib, uint64_t max_key, int m
     int rc = xjoin_args(ia, ib, metric, mode, capacity, out_a, out_b, out_keys, out_total, "zh_cross_join");
     if (rc) return rc;
     *out_total = 0;
-    XjoinLocks locks(ia, ib);
-    if ((rc = xjoin_state(ia, ib, "zh_cross_join"))) return rc;
-    ScratchGuard guard{ia, SCRATCH_XJOIN};
-    uint64_t total = 0;
-    rc = xjoin_run(ia, ib, max_key, metric, mode, capacity, out_a, out_b, out_keys, true, ia->stream, &total, "zh_cross_join");
-    if (rc && rc != ZH_ELIMIT) return rc;
-    *out_total = total;
-    return rc;
+    return xjoin_call(ia, ib, max_key, metric, mode, capacity, out_a, out_b, out_keys, out_total, true, nullptr, "zh_cross_join");
 }
 
 extern "C" int zh_cross_join_info(const zh_index *ia, zh_cross_info *out) { return get_info(ia, &zh_index::xj_info, out, "zh_cross_join_info"); }
@@ -4760,59 +4781,78 @@ static void knn_record(zh_index *ix, uint32_t k, zh_knn_info inf) {
     ix->kn_info = inf;
 }
 
-extern "C" int zh_knn_graph_device(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys,
-                                   uint32_t *d_out_counts, void *stream) {
-    int rc = knn_args(ix, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_device");
-    if (rc) return rc;
-    if (n == 0) return ZH_OK;
+// Both graphs' loop over slabs of lines (k > 0, n > 0); slab(r0, m, dIds, dKeys, dCounts) answers the lines of the rows [r0, r0 + m) on device
+// pointers (knn_slab / fknn_slab).  host: the outputs are HOST arrays -- host_slab lines at a time go through the staging (kn_oids, kn_okeys,
+// kn_ocounts) and are waited for (knn_stage_out); otherwise ONE slab over the whole range, straight into the caller's device arrays, and one wait.
+template <typename Slab>
+static int knn_slabs(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, uint64_t host_slab,
+                     bool host, hipStream_t s, Slab slab) {
+    int rc;
+    if (!host) {
+        if ((rc = slab(first_row, n, out_ids, out_keys, out_counts))) return rc;
+        HIPCHK(hipStreamSynchronize(s));
+        return ZH_OK;
+    }
+    const uint64_t m_max = std::min(n, host_slab);
+    if ((rc = ix->kn_oids.ensure(m_max * k * 8)) || (rc = ix->kn_okeys.ensure(m_max * k * 8)) || (rc = ix->kn_ocounts.ensure(m_max * 4))) return rc;
+    for (uint64_t r0 = 0; r0 < n; r0 += host_slab) {
+        const uint64_t m = std::min(host_slab, n - r0);
+        if ((rc = slab(first_row + r0, m, ix->kn_oids.as<uint64_t>(), ix->kn_okeys.as<uint64_t>(), ix->kn_ocounts.as<uint32_t>())) ||
+            (rc = knn_stage_out(ix, r0, m, k, out_ids, out_keys, out_counts, s)))
+            return rc;
+    }
+    return ZH_OK;
+}
+
+// both graphs with k == 0: the counts alone are the answer
+static int knn_no_neighbours(uint64_t n, uint32_t *out_counts, bool host, hipStream_t s) {
+    if (host) {
+        memset(out_counts, 0, n * 4);
+        return ZH_OK;
+    }
+    HIPCHK(hipMemsetAsync(out_counts, 0, n * 4, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return ZH_OK;
+}
+
+// both entry points once the arguments have been judged (n > 0)
+static int knn_call(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts,
+                    bool host, void *stream, const char *who) {
     std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph_device"))) return rc;
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, who))) return rc;
     ScratchGuard guard{ix, SCRATCH_KNN};
     const hipStream_t s = call_stream(ix, stream);
     zh_knn_info inf{};
     inf.path = 1;
     if (k == 0) {
-        HIPCHK(hipMemsetAsync(d_out_counts, 0, n * 4, s));
+        if ((rc = knn_no_neighbours(n, out_counts, host, s))) return rc;
     } else {
         KnnRun run;
         if ((rc = knn_setup(ix, (uint32_t)k, metric, mode, s, &run))) return rc;
         if (run.path2) inf.path = 2;
-        if ((rc = knn_slab(ix, &run, first_row, n, (uint32_t)k, metric, mode, d_out_ids, d_out_keys, d_out_counts, s, &inf))) return rc;
+        rc = knn_slabs(ix, first_row, n, k, out_ids, out_keys, out_counts, ZH_KNN_HOST_SLAB, host, s,
+                       [&](uint64_t r0, uint64_t m, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
+                           return knn_slab(ix, &run, r0, m, (uint32_t)k, metric, mode, dIds, dKeys, dCounts, s, &inf);
+                       });
+        if (rc) return rc;
     }
-    HIPCHK(hipStreamSynchronize(s));
     knn_record(ix, (uint32_t)k, inf);
     return ZH_OK;
+}
+
+extern "C" int zh_knn_graph_device(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys,
+                                   uint32_t *d_out_counts, void *stream) {
+    int rc = knn_args(ix, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_device");
+    if (rc || n == 0) return rc;
+    return knn_call(ix, first_row, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, false, stream, "zh_knn_graph_device");
 }
 
 extern "C" int zh_knn_graph(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys,
                             uint32_t *out_counts) {
     int rc = knn_args(ix, n, k, metric, mode, out_ids, out_keys, out_counts, "zh_knn_graph");
-    if (rc) return rc;
-    if (n == 0) return ZH_OK;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph"))) return rc;
-    ScratchGuard guard{ix, SCRATCH_KNN};
-    const hipStream_t s = ix->stream;
-    zh_knn_info inf{};
-    inf.path = 1;
-    if (k == 0) {
-        memset(out_counts, 0, n * 4);
-    } else {
-        KnnRun run;
-        if ((rc = knn_setup(ix, (uint32_t)k, metric, mode, s, &run))) return rc;
-        if (run.path2) inf.path = 2;
-        const uint64_t m_max = std::min<uint64_t>(n, ZH_KNN_HOST_SLAB);
-        if ((rc = ix->kn_oids.ensure(m_max * k * 8)) || (rc = ix->kn_okeys.ensure(m_max * k * 8)) || (rc = ix->kn_ocounts.ensure(m_max * 4))) return rc;
-        for (uint64_t r0 = 0; r0 < n; r0 += ZH_KNN_HOST_SLAB) {
-            const uint64_t m = std::min<uint64_t>(ZH_KNN_HOST_SLAB, n - r0);
-            if ((rc = knn_slab(ix, &run, first_row + r0, m, (uint32_t)k, metric, mode, ix->kn_oids.as<uint64_t>(), ix->kn_okeys.as<uint64_t>(),
-                               ix->kn_ocounts.as<uint32_t>(), s, &inf)) ||
-                (rc = knn_stage_out(ix, r0, m, k, out_ids, out_keys, out_counts, s)))
-                return rc;
-        }
-    }
-    knn_record(ix, (uint32_t)k, inf);
-    return ZH_OK;
+    if (rc || n == 0) return rc;
+    return knn_call(ix, first_row, n, k, metric, mode, out_ids, out_keys, out_counts, true, nullptr, "zh_knn_graph");
 }
 
 extern "C" int zh_knn_graph_info(const zh_index *ix, zh_knn_info *out) { return get_info(ix, &zh_index::kn_info, out, "zh_knn_graph_info"); }
@@ -5114,58 +5154,45 @@ static int fknn_state(zh_index *ix, const char *who) {
     return ZH_OK;
 }
 
-extern "C" int zh_knn_graph_forest_device(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *d_out_ids,
-                                          uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
-    int rc = fknn_args(ix, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_forest_device");
-    if (rc) return rc;
-    if (n == 0) return ZH_OK;
+// both entry points once the arguments have been judged (n > 0)
+static int fknn_call(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts,
+                     bool host, void *stream, const char *who) {
     std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph_forest_device"))) return rc;
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, who))) return rc;
     ScratchGuard guard{ix, SCRATCH_FKNN};
     const hipStream_t s = call_stream(ix, stream);
     zh_knn_forest_info inf{};
     inf.path = 1;
-    FknnRun run;
     if (k == 0) {
-        HIPCHK(hipMemsetAsync(d_out_counts, 0, n * 4, s));
+        if ((rc = knn_no_neighbours(n, out_counts, host, s))) return rc;
     } else {
-        if ((rc = fknn_state(ix, "zh_knn_graph_forest_device")) || (rc = fknn_setup(ix, (uint32_t)k, metric, mode, s, &run))) return rc;
+        FknnRun run;
+        if ((rc = fknn_state(ix, who)) || (rc = fknn_setup(ix, (uint32_t)k, metric, mode, s, &run))) return rc;
         if (run.path2) inf.path = 2;
-        if ((rc = fknn_slab(ix, run, first_row, n, (uint32_t)k, metric, mode, d_out_ids, d_out_keys, d_out_counts, s, &inf))) return rc;
+        // the staged sub-slab: large, because path 2 serves a slab at the cost of every leaf that holds one of its rows
+        const uint64_t host_slab = std::max<uint64_t>(ZH_FKNN_SLAB, (uint64_t(1) << 25) / k / ZH_FKNN_SLAB * ZH_FKNN_SLAB);
+        rc = knn_slabs(ix, first_row, n, k, out_ids, out_keys, out_counts, host_slab, host, s,
+                       [&](uint64_t r0, uint64_t m, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
+                           return fknn_slab(ix, run, r0, m, (uint32_t)k, metric, mode, dIds, dKeys, dCounts, s, &inf);
+                       });
+        if (rc) return rc;
     }
-    HIPCHK(hipStreamSynchronize(s));
     return fknn_finish(ix, (uint32_t)k, inf, s);
+}
+
+extern "C" int zh_knn_graph_forest_device(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *d_out_ids,
+                                          uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
+    int rc = fknn_args(ix, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_forest_device");
+    if (rc || n == 0) return rc;
+    return fknn_call(ix, first_row, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, false, stream, "zh_knn_graph_forest_device");
 }
 
 extern "C" int zh_knn_graph_forest(zh_index *ix, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys,
                                    uint32_t *out_counts) {
     int rc = fknn_args(ix, n, k, metric, mode, out_ids, out_keys, out_counts, "zh_knn_graph_forest");
-    if (rc) return rc;
-    if (n == 0) return ZH_OK;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, "zh_knn_graph_forest"))) return rc;
-    ScratchGuard guard{ix, SCRATCH_FKNN};
-    const hipStream_t s = ix->stream;
-    zh_knn_forest_info inf{};
-    inf.path = 1;
-    FknnRun run;
-    if (k == 0) {
-        memset(out_counts, 0, n * 4);
-    } else {
-        if ((rc = fknn_state(ix, "zh_knn_graph_forest")) || (rc = fknn_setup(ix, (uint32_t)k, metric, mode, s, &run))) return rc;
-        if (run.path2) inf.path = 2;
-        // the staged sub-slab: large, because path 2 serves a slab at the cost of every leaf that holds one of its rows
-        const uint64_t host_slab = std::max<uint64_t>(ZH_FKNN_SLAB, (uint64_t(1) << 25) / k / ZH_FKNN_SLAB * ZH_FKNN_SLAB), m_max = std::min(n, host_slab);
-        if ((rc = ix->kn_oids.ensure(m_max * k * 8)) || (rc = ix->kn_okeys.ensure(m_max * k * 8)) || (rc = ix->kn_ocounts.ensure(m_max * 4))) return rc;
-        for (uint64_t r0 = 0; r0 < n; r0 += host_slab) {
-            const uint64_t m = std::min(host_slab, n - r0);
-            if ((rc = fknn_slab(ix, run, first_row + r0, m, (uint32_t)k, metric, mode, ix->kn_oids.as<uint64_t>(), ix->kn_okeys.as<uint64_t>(),
-                                ix->kn_ocounts.as<uint32_t>(), s, &inf)) ||
-                (rc = knn_stage_out(ix, r0, m, k, out_ids, out_keys, out_counts, s)))
-                return rc;
-        }
-    }
-    return fknn_finish(ix, (uint32_t)k, inf, s);
+    if (rc || n == 0) return rc;
+    return fknn_call(ix, first_row, n, k, metric, mode, out_ids, out_keys, out_counts, true, nullptr, "zh_knn_graph_forest");
 }
 
 extern "C" int zh_knn_graph_forest_info(const zh_index *ix, zh_knn_forest_info *out) {
@@ -5395,24 +5422,27 @@ static int fjoin_state(zh_index *ix, bool *empty, const char *who) {
     return fknn_state(ix, who);
 }
 
+// both entry points once the arguments have been judged (host: the caller has zeroed the total, so an empty index ends the host call at once; the
+// device call still writes its total of 0 on the stream)
+static int fjoin_call(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b, uint64_t *out_keys,
+                      uint64_t *out_total, bool host, void *stream, const char *who) {
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    bool empty = false;
+    if ((rc = fjoin_state(ix, &empty, who)) || (empty && host)) return rc;
+    ScratchGuard guard{ix, SCRATCH_FJOIN};
+    const hipStream_t s = call_stream(ix, stream);
+    uint64_t total = 0;
+    if (!empty) rc = fjoin_run(ix, max_key, metric, mode, capacity, out_a, out_b, out_keys, host, s, &total, who);
+    return join_total(rc, total, out_total, host, s);
+}
+
 extern "C" int zh_self_join_forest_device(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *d_out_a, uint64_t *d_out_b,
                                           uint64_t *d_out_keys, uint64_t *d_out_total, void *stream) {
     int rc = join_args(ix, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, d_out_total, "zh_self_join_forest_device");
     if (rc) return rc;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    bool empty = false;
-    if ((rc = fjoin_state(ix, &empty, "zh_self_join_forest_device"))) return rc;
-    ScratchGuard guard{ix, SCRATCH_FJOIN};
-    const hipStream_t s = call_stream(ix, stream);
-    uint64_t total = 0;
-    if (!empty) {
-        rc = fjoin_run(ix, max_key, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, false, s, &total, "zh_self_join_forest_device");
-        if (rc && rc != ZH_ELIMIT) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(d_out_total, &total, 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return rc;
+    return fjoin_call(ix, max_key, metric, mode, capacity, d_out_a, d_out_b, d_out_keys, d_out_total, false, stream, "zh_self_join_forest_device");
 }
 
 extern "C" int zh_self_join_forest(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t capacity, uint64_t *out_a, uint64_t *out_b, uint64_t *out_keys,
@@ -5420,16 +5450,7 @@ extern "C" int zh_self_join_forest(zh_index *ix, uint64_t max_key, int metric, i
     int rc = join_args(ix, metric, mode, capacity, out_a, out_b, out_keys, out_total, "zh_self_join_forest");
     if (rc) return rc;
     *out_total = 0;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    bool empty = false;
-    if ((rc = fjoin_state(ix, &empty, "zh_self_join_forest")) || empty) return rc;
-    ScratchGuard guard{ix, SCRATCH_FJOIN};
-    uint64_t total = 0;
-    rc = fjoin_run(ix, max_key, metric, mode, capacity, out_a, out_b, out_keys, true, ix->stream, &total, "zh_self_join_forest");
-    if (rc && rc != ZH_ELIMIT) return rc;
-    *out_total = total;
-    return rc;
+    return fjoin_call(ix, max_key, metric, mode, capacity, out_a, out_b, out_keys, out_total, true, nullptr, "zh_self_join_forest");
 }
 
 extern "C" int zh_self_join_forest_info(const zh_index *ix, zh_join_forest_info *out) {
@@ -5728,31 +5749,41 @@ static int frange_finish(zh_index *ix, size_t b, const FrangeRun &run, const cha
     return ZH_OK;
 }
 
+// Both entry points once the arguments have been judged, as range_call.  An empty call (no query -- the device call's alone -- or no live row) asks
+// for no trees and takes no batch: the host call zeroes its b + 1 offsets and ends without scratch, the device call zeroes them on its stream.
+static int frange_call(zh_index *ix, const float *q, size_t b, const uint64_t *max_keys, uint32_t probe, int metric, int mode, uint64_t capacity,
+                       uint64_t *out_offsets, uint64_t *out_ids, uint64_t *out_keys, uint64_t *out_total, bool host, void *stream, const char *who) {
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    FrangeRun run;
+    bool empty = false;
+    if ((rc = frange_begin(ix, b, probe, metric, mode, capacity, &run, &empty, who))) return rc;
+    if (empty && host) {
+        memset(out_offsets, 0, (b + 1) * 8);
+        return frange_finish(ix, b, run, who);
+    }
+    ScratchGuard guard{ix, SCRATCH_FRANGE};
+    const hipStream_t s = call_stream(ix, stream);
+    if (!host) HIPCHK(hipMemsetAsync(out_offsets, 0, (empty ? b + 1 : 1) * 8, s));
+    if (!empty) {
+        if ((rc = frange_setup(ix, s, &run))) return rc;
+        rc = range_batches(ix, q, b, max_keys, out_offsets, host, s, [&](const float *dQ, uint32_t nb, const uint64_t *dMaxK, uint64_t *dOff) {
+            return frange_one(ix, &run, dQ, nb, dMaxK, dOff, out_ids, out_keys, host, true, s);
+        });
+        if (rc) return rc;
+    }
+    if ((rc = put_total(run.rr.total, out_total, host, s))) return rc;
+    return frange_finish(ix, b, run, who);
+}
+
 extern "C" int zh_search_range_forest_batch_device(zh_index *ix, const float *d_q, size_t b, const uint64_t *d_max_keys, uint32_t probe, int metric, int mode,
                                                    uint64_t capacity, uint64_t *d_out_offsets, uint64_t *d_out_ids, uint64_t *d_out_keys,
                                                    uint64_t *d_out_total, void *stream) {
     const char *who = "zh_search_range_forest_batch_device";
     int rc = frange_args(ix, d_q, b, d_max_keys, probe, metric, mode, capacity, d_out_offsets, d_out_ids, d_out_keys, d_out_total, who);
     if (rc) return rc;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    FrangeRun run;
-    bool empty = false;
-    if ((rc = frange_begin(ix, b, probe, metric, mode, capacity, &run, &empty, who))) return rc;
-    ScratchGuard guard{ix, SCRATCH_FRANGE};
-    const hipStream_t s = call_stream(ix, stream);
-    const uint32_t d = ix->opt.dim;
-    HIPCHK(hipMemsetAsync(d_out_offsets, 0, (empty ? b + 1 : 1) * 8, s));
-    if (!empty) {
-        if ((rc = frange_setup(ix, s, &run))) return rc;
-        for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
-            const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
-            if ((rc = frange_one(ix, &run, d_q + b0 * d, nb, d_max_keys + b0, d_out_offsets + b0, d_out_ids, d_out_keys, false, true, s))) return rc;
-        }
-    }
-    HIPCHK(hipMemcpyAsync(d_out_total, &run.rr.total, 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return frange_finish(ix, b, run, who);
+    return frange_call(ix, d_q, b, d_max_keys, probe, metric, mode, capacity, d_out_offsets, d_out_ids, d_out_keys, d_out_total, false, stream, who);
 }
 
 extern "C" int zh_search_range_forest_batch(zh_index *ix, const float *q, size_t b, const uint64_t *max_keys, uint32_t probe, int metric, int mode,
@@ -5763,32 +5794,7 @@ extern "C" int zh_search_range_forest_batch(zh_index *ix, const float *q, size_t
     out_offsets[0] = 0;
     *out_total = 0;
     if (b == 0) return ZH_OK;
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
-    FrangeRun run;
-    bool empty = false;
-    if ((rc = frange_begin(ix, b, probe, metric, mode, capacity, &run, &empty, who))) return rc;
-    if (empty) {
-        memset(out_offsets, 0, (b + 1) * 8);
-        return frange_finish(ix, b, run, who);
-    }
-    ScratchGuard guard{ix, SCRATCH_FRANGE};
-    const hipStream_t s = ix->stream;
-    const uint32_t d = ix->opt.dim;
-    const size_t nb_max = std::min<size_t>(ZH_EXACT_BATCH, b);
-    if ((rc = ix->ex_Q.ensure(nb_max * d * 4)) || (rc = ix->rg_maxk.ensure(nb_max * 8)) || (rc = ix->rg_off.ensure((nb_max + 1) * 8))) return rc;
-    if ((rc = frange_setup(ix, s, &run))) return rc;
-    for (size_t b0 = 0; b0 < b; b0 += ZH_EXACT_BATCH) {
-        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_EXACT_BATCH, b - b0);
-        HIPCHK(hipMemcpyAsync(ix->ex_Q.p, q + b0 * d, (size_t)nb * d * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(ix->rg_maxk.p, max_keys + b0, (size_t)nb * 8, hipMemcpyHostToDevice, s));
-        if ((rc = frange_one(ix, &run, ix->ex_Q.as<float>(), nb, ix->rg_maxk.as<uint64_t>(), ix->rg_off.as<uint64_t>(), out_ids, out_keys, true, true, s)))
-            return rc;
-        HIPCHK(hipMemcpyAsync(out_offsets + b0, ix->rg_off.p, ((size_t)nb + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    *out_total = run.rr.total;
-    return frange_finish(ix, b, run, who);
+    return frange_call(ix, q, b, max_keys, probe, metric, mode, capacity, out_offsets, out_ids, out_keys, out_total, true, nullptr, who);
 }
 
 extern "C" int zh_search_range_forest_info(const zh_index *ix, zh_range_forest_info *out) {

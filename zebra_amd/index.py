@@ -23,6 +23,30 @@ def _f32(a, d=None):
     return a
 
 
+def _with_capacity(cap, n_arrays, call):
+    """the range searches' and the joins' host calls: call(cap, arrays, total) -> rc with `n_arrays` u64 output arrays of a guessed capacity; when
+    the hits exceed it (ZH_ELIMIT), ONE more call with the exact total the first one reported -> the arrays, cut to the total"""
+    total = C.c_uint64(0)
+    for attempt in range(2):
+        out = [np.empty(max(cap, 1), np.uint64) for _ in range(n_arrays)]
+        rc = call(cap, out, total)
+        if rc == _ffi.ZH_ELIMIT and attempt == 0 and total.value > cap:
+            cap = int(total.value)
+            continue
+        check(rc)
+        break
+    return tuple(a[:int(total.value)] for a in out)
+
+
+def _count(call):
+    """the same calls with capacity 0 (nothing is ordered or written): call(total) -> rc, and ZH_ELIMIT is the ordinary answer -> the total"""
+    total = C.c_uint64(0)
+    rc = call(total)
+    if rc != _ffi.ZH_ELIMIT:
+        check(rc)
+    return int(total.value)
+
+
 # ---------------------------------------------------------------------------- src/distance.rs
 class _Metric:
     """space::Metric<Embedding<N>> with Unit = u64 (src/distance.rs:19-21)."""
@@ -355,11 +379,15 @@ class LSHIndex:
         check(lib().zh_search_exact_batch_device(self._h, d_q_ptr, b, top_k, metric.metric, metric.mode, d_ids_ptr,
                                                  d_keys_ptr, d_counts_ptr, stream))
 
+    def _info(self, struct, entry):
+        """what the most recent call of a family on this index did: its zh_*_info export as a dict"""
+        info = struct()
+        check(entry(self._h, C.byref(info)))
+        return info.as_dict()
+
     def exact_info(self):
         """what the most recent exact search on this index did (zh_search_exact_info): batch, rows_live, path, redone, survivors, launches"""
-        info = _ffi.ExactInfo()
-        check(lib().zh_search_exact_info(self._h, C.byref(info)))
-        return info.as_dict()
+        return self._info(_ffi.ExactInfo, lib().zh_search_exact_info)
 
     def filter_bitmap(self, allowed):
         """a filter for the filtered searches from a boolean mask over the stored rows (length up to stored_rows(); rows past it are not
@@ -405,9 +433,7 @@ class LSHIndex:
     def filtered_info(self):
         """what the most recent filtered exact search on this index did (zh_search_filtered_info): batch, rows_live, rows_allowed, path,
         redone, survivors, launches, tiles_skipped"""
-        info = _ffi.FilteredInfo()
-        check(lib().zh_search_filtered_info(self._h, C.byref(info)))
-        return info.as_dict()
+        return self._info(_ffi.FilteredInfo, lib().zh_search_filtered_info)
 
     def _range_keys(self, b, radius, metric, max_keys):
         if (radius is None) == (max_keys is None):
@@ -429,18 +455,9 @@ class LSHIndex:
         mk = self._range_keys(b, radius, metric, max_keys)
         cap = int(capacity) if capacity is not None else max(1024, 64 * b)
         offsets = np.zeros(b + 1, np.uint64)
-        total = C.c_uint64(0)
-        for attempt in range(2):
-            ids = np.empty(max(cap, 1), np.uint64)
-            keys = np.empty(max(cap, 1), np.uint64)
-            rc = lib().zh_search_range_batch(self._h, _p(q), b, _p(mk), metric.metric, metric.mode, cap, _p(offsets), _p(ids), _p(keys), C.byref(total))
-            if rc == _ffi.ZH_ELIMIT and attempt == 0 and total.value > cap:
-                cap = int(total.value)
-                continue
-            check(rc)
-            break
-        n = int(total.value)
-        return offsets, ids[:n], keys[:n]
+        return (offsets,) + _with_capacity(cap, 2, lambda cap, o, total: lib().zh_search_range_batch(
+            self._h, _p(q), b, _p(mk), metric.metric, metric.mode, cap, _p(offsets), _p(o[0]), _p(o[1]), C.byref(total)))
+
 
     def search_range(self, query, radius=None, metric=None, max_keys=None):
         """the hits of one query -> list of (id, distance key), ascending"""
@@ -453,10 +470,9 @@ class LSHIndex:
         b = q.shape[0]
         mk = self._range_keys(b, radius, metric, max_keys)
         offsets = np.zeros(b + 1, np.uint64)
-        total = C.c_uint64(0)
-        rc = lib().zh_search_range_batch(self._h, _p(q), b, _p(mk), metric.metric, metric.mode, 0, _p(offsets), None, None, C.byref(total))
-        if rc != _ffi.ZH_ELIMIT:
-            check(rc)
+        _count(lambda total: lib().zh_search_range_batch(
+            self._h, _p(q), b, _p(mk), metric.metric, metric.mode, 0, _p(offsets), None, None, C.byref(total)))
+
         return np.diff(offsets)
 
     def search_range_batch_device(self, d_q_ptr, b, d_max_keys_ptr, metric, capacity, d_offsets_ptr, d_ids_ptr, d_keys_ptr, d_total_ptr, stream=None):
@@ -468,9 +484,7 @@ class LSHIndex:
 
     def range_info(self):
         """what the most recent range search on this index did (zh_search_range_info): batch, rows_live, hits, path, redone, candidates, launches"""
-        info = _ffi.RangeInfo()
-        check(lib().zh_search_range_info(self._h, C.byref(info)))
-        return info.as_dict()
+        return self._info(_ffi.RangeInfo, lib().zh_search_range_info)
 
     def search_range_forest_batch(self, queries, radius=None, metric=None, max_keys=None, probe=1, capacity=None):
         """FOREST range search: search_range_batch among the members of the leaves the walk visits for each query with n = `probe` (what
@@ -481,19 +495,9 @@ class LSHIndex:
         mk = self._range_keys(b, radius, metric, max_keys)
         cap = int(capacity) if capacity is not None else max(1024, 64 * b)
         offsets = np.zeros(b + 1, np.uint64)
-        total = C.c_uint64(0)
-        for attempt in range(2):
-            ids = np.empty(max(cap, 1), np.uint64)
-            keys = np.empty(max(cap, 1), np.uint64)
-            rc = lib().zh_search_range_forest_batch(self._h, _p(q), b, _p(mk), int(probe), metric.metric, metric.mode, cap, _p(offsets), _p(ids), _p(keys),
-                                                    C.byref(total))
-            if rc == _ffi.ZH_ELIMIT and attempt == 0 and total.value > cap:
-                cap = int(total.value)
-                continue
-            check(rc)
-            break
-        n = int(total.value)
-        return offsets, ids[:n], keys[:n]
+        return (offsets,) + _with_capacity(cap, 2, lambda cap, o, total: lib().zh_search_range_forest_batch(
+            self._h, _p(q), b, _p(mk), int(probe), metric.metric, metric.mode, cap, _p(offsets), _p(o[0]), _p(o[1]), C.byref(total)))
+
 
     def search_range_forest(self, query, radius=None, metric=None, max_keys=None, probe=1):
         """the forest hits of one query -> list of (id, distance key), ascending"""
@@ -506,10 +510,9 @@ class LSHIndex:
         b = q.shape[0]
         mk = self._range_keys(b, radius, metric, max_keys)
         offsets = np.zeros(b + 1, np.uint64)
-        total = C.c_uint64(0)
-        rc = lib().zh_search_range_forest_batch(self._h, _p(q), b, _p(mk), int(probe), metric.metric, metric.mode, 0, _p(offsets), None, None, C.byref(total))
-        if rc != _ffi.ZH_ELIMIT:
-            check(rc)
+        _count(lambda total: lib().zh_search_range_forest_batch(
+            self._h, _p(q), b, _p(mk), int(probe), metric.metric, metric.mode, 0, _p(offsets), None, None, C.byref(total)))
+
         return np.diff(offsets)
 
     def search_range_forest_batch_device(self, d_q_ptr, b, d_max_keys_ptr, probe, metric, capacity, d_offsets_ptr, d_ids_ptr, d_keys_ptr, d_total_ptr,
@@ -523,9 +526,7 @@ class LSHIndex:
     def range_forest_info(self):
         """what the most recent forest range search on this index did (zh_search_range_forest_info): batch, rows_live, trees, probe, path,
         redone, visits, leaf_rows, hits, candidates, launches, tiles"""
-        info = _ffi.RangeForestInfo()
-        check(lib().zh_search_range_forest_info(self._h, C.byref(info)))
-        return info.as_dict()
+        return self._info(_ffi.RangeForestInfo, lib().zh_search_range_forest_info)
 
     def _join_key(self, radius, metric, max_key):
         if metric is None:
@@ -544,28 +545,16 @@ class LSHIndex:
         exceed it, one more with the exact total the first call reported."""
         mk = self._join_key(radius, metric, max_key)
         cap = int(capacity) if capacity is not None else max(1024, 16 * len(self))
-        total = C.c_uint64(0)
-        for attempt in range(2):
-            a = np.empty(max(cap, 1), np.uint64)
-            b = np.empty(max(cap, 1), np.uint64)
-            keys = np.empty(max(cap, 1), np.uint64)
-            rc = lib().zh_self_join(self._h, mk, metric.metric, metric.mode, cap, _p(a), _p(b), _p(keys), C.byref(total))
-            if rc == _ffi.ZH_ELIMIT and attempt == 0 and total.value > cap:
-                cap = int(total.value)
-                continue
-            check(rc)
-            break
-        n = int(total.value)
-        return a[:n], b[:n], keys[:n]
+        return _with_capacity(cap, 3, lambda cap, o, total: lib().zh_self_join(
+            self._h, mk, metric.metric, metric.mode, cap, _p(o[0]), _p(o[1]), _p(o[2]), C.byref(total)))
+
 
     def self_join_count(self, radius=None, metric=None, max_key=None):
         """how many pairs self_join would return (a call with capacity 0: nothing is ordered or written)"""
         mk = self._join_key(radius, metric, max_key)
-        total = C.c_uint64(0)
-        rc = lib().zh_self_join(self._h, mk, metric.metric, metric.mode, 0, None, None, None, C.byref(total))
-        if rc != _ffi.ZH_ELIMIT:
-            check(rc)
-        return int(total.value)
+        return _count(lambda total: lib().zh_self_join(
+            self._h, mk, metric.metric, metric.mode, 0, None, None, None, C.byref(total)))
+
 
     def self_join_device(self, max_key, metric, capacity, d_a_ptr, d_b_ptr, d_keys_ptr, d_total_ptr, stream=None):
         """self_join with a, b, keys (`capacity` each) and the total (one u64) in device memory (raw pointers, e.g. torch .data_ptr()).
@@ -574,9 +563,7 @@ class LSHIndex:
 
     def join_info(self):
         """what the most recent self-join on this index did (zh_self_join_info): rows_live, pairs, path, redone, candidates, launches, tiles"""
-        info = _ffi.JoinInfo()
-        check(lib().zh_self_join_info(self._h, C.byref(info)))
-        return info.as_dict()
+        return self._info(_ffi.JoinInfo, lib().zh_self_join_info)
 
     def _cross_other(self, other):
         if not isinstance(other, LSHIndex):
@@ -592,28 +579,16 @@ class LSHIndex:
         mk = self._join_key(radius, metric, max_key)
         h = self._cross_other(other)
         cap = int(capacity) if capacity is not None else max(1024, 16 * len(self))
-        total = C.c_uint64(0)
-        for attempt in range(2):
-            a = np.empty(max(cap, 1), np.uint64)
-            b = np.empty(max(cap, 1), np.uint64)
-            keys = np.empty(max(cap, 1), np.uint64)
-            rc = lib().zh_cross_join(self._h, h, mk, metric.metric, metric.mode, cap, _p(a), _p(b), _p(keys), C.byref(total))
-            if rc == _ffi.ZH_ELIMIT and attempt == 0 and total.value > cap:
-                cap = int(total.value)
-                continue
-            check(rc)
-            break
-        n = int(total.value)
-        return a[:n], b[:n], keys[:n]
+        return _with_capacity(cap, 3, lambda cap, o, total: lib().zh_cross_join(
+            self._h, h, mk, metric.metric, metric.mode, cap, _p(o[0]), _p(o[1]), _p(o[2]), C.byref(total)))
+
 
     def cross_join_count(self, other, radius=None, metric=None, max_key=None):
         """how many pairs cross_join would return (a call with capacity 0: nothing is ordered or written)"""
         mk = self._join_key(radius, metric, max_key)
-        total = C.c_uint64(0)
-        rc = lib().zh_cross_join(self._h, self._cross_other(other), mk, metric.metric, metric.mode, 0, None, None, None, C.byref(total))
-        if rc != _ffi.ZH_ELIMIT:
-            check(rc)
-        return int(total.value)
+        return _count(lambda total: lib().zh_cross_join(
+            self._h, self._cross_other(other), mk, metric.metric, metric.mode, 0, None, None, None, C.byref(total)))
+
 
     def cross_join_device(self, other, max_key, metric, capacity, d_a_ptr, d_b_ptr, d_keys_ptr, d_total_ptr, stream=None):
         """cross_join with a, b, keys (`capacity` each) and the total (one u64) in device memory (raw pointers, e.g. torch .data_ptr()).
@@ -624,9 +599,7 @@ class LSHIndex:
     def cross_info(self):
         """what the most recent cross_join with this index on the left did (zh_cross_join_info): rows_live_a, rows_live_b, pairs, path, redone,
         candidates, launches, tiles"""
-        info = _ffi.CrossInfo()
-        check(lib().zh_cross_join_info(self._h, C.byref(info)))
-        return info.as_dict()
+        return self._info(_ffi.CrossInfo, lib().zh_cross_join_info)
 
     def remove_within(self, other, radius, metric):
         """drop what the corpus already has: every live row of self that has a live row of `other` within `radius` is removed from self (the
@@ -642,12 +615,16 @@ class LSHIndex:
         k nearest OTHER live rows of stored row first_row + i by (key, id) -- the key search_exact_batch gives for that row's f32 values as the
         query; only the row itself is excluded, a bit-identical duplicate is a neighbour.  -> (ids [n,k] u64, keys [n,k] u64, counts [n] u32);
         counts = min(k, live rows - 1), 0 for a removed row; entries past the count are 2^64-1."""
+        return self._graph(lib().zh_knn_graph, k, metric, first_row, n)
+
+    def _graph(self, entry, k, metric, first_row, n):
+        """either graph's host call over the slab [first_row, first_row + n) (n None: to the last stored row)"""
         stored = self.stored_rows()
         n = max(stored - first_row, 0) if n is None else int(n)
         ids = np.empty((n, k), np.uint64)
         keys = np.empty((n, k), np.uint64)
         counts = np.zeros(n, np.uint32)
-        check(lib().zh_knn_graph(self._h, int(first_row), n, k, metric.metric, metric.mode, _p(ids), _p(keys), _p(counts)))
+        check(entry(self._h, int(first_row), n, k, metric.metric, metric.mode, _p(ids), _p(keys), _p(counts)))
         return ids, keys, counts
 
     def knn_graph_device(self, k, metric, first_row, n, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream=None):
@@ -656,9 +633,7 @@ class LSHIndex:
 
     def knn_info(self):
         """what the most recent k-NN graph call on this index did (zh_knn_graph_info): rows_live, lines, k, path, redone, survivors, launches, tiles"""
-        info = _ffi.KnnInfo()
-        check(lib().zh_knn_graph_info(self._h, C.byref(info)))
-        return info.as_dict()
+        return self._info(_ffi.KnnInfo, lib().zh_knn_graph_info)
 
     def knn_graph_forest(self, k, metric, first_row=0, n=None):
         """FOREST k-NN graph of the slab of stored rows [first_row, first_row + n) (default: from first_row to the last stored row): line i holds the
@@ -666,13 +641,7 @@ class LSHIndex:
         excluded -- knn_graph's keys, ids and layout, exact arithmetic on an approximate candidate set.  -> (ids [n,k] u64, keys [n,k] u64,
         counts [n] u32); counts = min(k, leaf-mates), 0 for a removed row and for a row no tree holds (appended since the last build); entries
         past the count are 2^64-1.  Needs a built forest."""
-        stored = self.stored_rows()
-        n = max(stored - first_row, 0) if n is None else int(n)
-        ids = np.empty((n, k), np.uint64)
-        keys = np.empty((n, k), np.uint64)
-        counts = np.zeros(n, np.uint32)
-        check(lib().zh_knn_graph_forest(self._h, int(first_row), n, k, metric.metric, metric.mode, _p(ids), _p(keys), _p(counts)))
-        return ids, keys, counts
+        return self._graph(lib().zh_knn_graph_forest, k, metric, first_row, n)
 
     def knn_graph_forest_device(self, k, metric, first_row, n, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream=None):
         """knn_graph_forest with the outputs ([n,k] u64 twice, [n] u32) already in device memory (raw pointers, e.g. torch .data_ptr())."""
@@ -682,9 +651,7 @@ class LSHIndex:
     def knn_forest_info(self):
         """what the most recent forest k-NN graph call on this index did (zh_knn_graph_forest_info): rows_live, lines, k, path, trees, pairs,
         survivors, redone, launches, tiles"""
-        info = _ffi.KnnForestInfo()
-        check(lib().zh_knn_graph_forest_info(self._h, C.byref(info)))
-        return info.as_dict()
+        return self._info(_ffi.KnnForestInfo, lib().zh_knn_graph_forest_info)
 
     def deduplicate_within(self, radius, metric):
         """near-duplicate removal: rows are taken in ascending id, and row b is removed exactly when some KEPT row a < b forms a joined pair
@@ -703,28 +670,16 @@ class LSHIndex:
         exact total the first call reported.  Needs a built forest."""
         mk = self._join_key(radius, metric, max_key)
         cap = int(capacity) if capacity is not None else max(1024, 16 * len(self))
-        total = C.c_uint64(0)
-        for attempt in range(2):
-            a = np.empty(max(cap, 1), np.uint64)
-            b = np.empty(max(cap, 1), np.uint64)
-            keys = np.empty(max(cap, 1), np.uint64)
-            rc = lib().zh_self_join_forest(self._h, mk, metric.metric, metric.mode, cap, _p(a), _p(b), _p(keys), C.byref(total))
-            if rc == _ffi.ZH_ELIMIT and attempt == 0 and total.value > cap:
-                cap = int(total.value)
-                continue
-            check(rc)
-            break
-        n = int(total.value)
-        return a[:n], b[:n], keys[:n]
+        return _with_capacity(cap, 3, lambda cap, o, total: lib().zh_self_join_forest(
+            self._h, mk, metric.metric, metric.mode, cap, _p(o[0]), _p(o[1]), _p(o[2]), C.byref(total)))
+
 
     def self_join_forest_count(self, radius=None, metric=None, max_key=None):
         """how many pairs self_join_forest would return (a call with capacity 0: nothing is ordered or written)"""
         mk = self._join_key(radius, metric, max_key)
-        total = C.c_uint64(0)
-        rc = lib().zh_self_join_forest(self._h, mk, metric.metric, metric.mode, 0, None, None, None, C.byref(total))
-        if rc != _ffi.ZH_ELIMIT:
-            check(rc)
-        return int(total.value)
+        return _count(lambda total: lib().zh_self_join_forest(
+            self._h, mk, metric.metric, metric.mode, 0, None, None, None, C.byref(total)))
+
 
     def self_join_forest_device(self, max_key, metric, capacity, d_a_ptr, d_b_ptr, d_keys_ptr, d_total_ptr, stream=None):
         """self_join_forest with a, b, keys (`capacity` each) and the total (one u64) in device memory (raw pointers, e.g. torch .data_ptr()).
@@ -735,9 +690,7 @@ class LSHIndex:
     def join_forest_info(self):
         """what the most recent forest self-join on this index did (zh_self_join_forest_info): rows_live, trees, path, leaf_pairs, pairs,
         candidates, launches, tiles, redone"""
-        info = _ffi.JoinForestInfo()
-        check(lib().zh_self_join_forest_info(self._h, C.byref(info)))
-        return info.as_dict()
+        return self._info(_ffi.JoinForestInfo, lib().zh_self_join_forest_info)
 
     def deduplicate_within_forest(self, radius, metric):
         """deduplicate_within's rule over the forest self-join's pairs (self_join_forest at `radius`): near-duplicates that no tree puts into

@@ -611,3 +611,32 @@ def test_database_near_duplicates_forest(za):
     assert set(got) <= set(exact) and len(exact) == 4  # rows 3 .. 7 and their copies, 7 removed
     removed = db.deduplicate_within_forest(1e-3)
     assert removed.tolist() == sorted(set(ref[1].tolist())) and all(int(i) not in db._documents for i in removed)
+
+
+@pytest.mark.parametrize("name", ["l2sq", "cos_corrected"])
+def test_walk_edges_a_chunk_of_one_tile_and_idle_waves(za, monkeypatch, name):
+    """the held-tile walk (zh_device.h) at its edges, against the family fuzz's reference: one tree whose root is a leaf of 1040 rows = 65 tiles.
+    So small a launch walks chunks of 8 tiles (fill_chunk), counted from each held block's diagonal: the blocks from tile 0, 8, ... walk eight
+    full chunks (even: the last tile in the second LDS buffer) and a chunk of ONE tile (odd, no prefetch at all), the others end in chunks of
+    5 tiles; in every first chunk waves 1 to 3 skip the tiles before their diagonal; the last held block holds one tile: three idle waves.
+    Near-duplicates are planted so that the one-tile chunk and the last block's diagonal tile both have pairs"""
+    from tests import family_cases as fc
+    n = 1040
+    spec = fc.metric_spec(name)
+    m = za.L2SquaredDistance() if name == "l2sq" else za.CosineDistance(parity=False)
+    X = zo.synth_rows(n, DB).copy()
+    X[1030], X[1039] = X[5] * np.float32(1.0 + 2.0**-12), X[1025] * np.float32(1.0 + 2.0**-12)
+    rows, alive = np.arange(n), np.ones(n, bool)
+    K = fc.key_matrix(spec, X, X)
+    upper = rows[None, :] > rows[:, None]
+    mk = fc.quantile_threshold(K, upper, 3000, n * (n - 1) / 2)
+    ref = fc.join_ref(K, rows, alive, alive, mk, 0, 0, True)
+    assert ((ref[0] == 5) & (ref[1] == 1030)).any() and ((ref[0] == 1025) & (ref[1] == 1039)).any() and ref[0].size >= 3000
+    ix = za.LSHIndex(DB, za.LSHIndexOptions(16384, 1), device=0)
+    ix.add(X)
+    on_path(monkeypatch, 2)
+    got = ix.self_join_forest(metric=m, max_key=mk)
+    info = expect_info(ix, 2, n * (n - 1) // 2, ref[0].size, 1, n)
+    assert info["tiles"] == 65 * 66 // 2 and info["launches"] == 1, info
+    same(got, ref)
+    ix.close()

@@ -535,3 +535,30 @@ def test_database_knn_graph_forest(za):
         rid, rkey = ref[a]
         assert [d for d, _ in graph[docs[a]]] == [docs[int(i)] for i in rid[:3]]
         assert [v for _, v in graph[docs[a]]] == zo.key_to_float(rkey[:3]).tolist()
+
+
+@pytest.mark.parametrize("name", ["l2sq", "cos_corrected"])
+def test_walk_edges_a_chunk_of_one_tile_and_idle_waves(za, monkeypatch, name):
+    """the held-tile walk (zh_device.h) at its edges, against the family fuzz's reference: one tree whose root is a leaf of 1040 rows = 65 column
+    tiles, a slab of 17 lines = two held tiles, the second with one line: two waves of the one held block that has lines are idle.  So small a
+    launch walks chunks of 8 column tiles (fill_chunk): eight full chunks (even: the last tile in the second LDS buffer) and a chunk of ONE
+    tile (odd, no prefetch at all).  A near-duplicate of a line is planted in that last tile"""
+    from tests import family_cases as fc
+    n, k, first = 1040, 10, 500
+    spec = fc.metric_spec(name)
+    m = za.L2SquaredDistance() if name == "l2sq" else za.CosineDistance(parity=False)
+    X = zo.synth_rows(n, DB).copy()
+    X[1033] = X[first + 16] * np.float32(1.0 + 2.0**-12)
+    slab = np.arange(first, first + 17)
+    ref = fc.graph_ref(fc.key_matrix(spec, X, X[slab]), slab, np.ones(n, bool), k, 0, mates=np.ones((17, n), bool))
+    assert ref[0][16, 0] == 1033
+    ix = za.LSHIndex(DB, za.LSHIndexOptions(16384, 1), device=0)
+    ix.add(X)
+    monkeypatch.delenv("ZH_FKNN_PATH", raising=False)
+    monkeypatch.delenv("ZH_FKNN_LIST_CAP", raising=False)
+    got = ix.knn_graph_forest(k, m, first, 17)
+    info = ix.knn_forest_info()
+    assert info["path"] == 2 and info["redone"] == 0 and info["lines"] == 17 and info["trees"] == 1 and info["tiles"] == 2 * 65, info
+    for g, r, what in zip(got, ref, ("ids", "keys", "counts")):
+        assert g.shape == r.shape and (g == r).all(), what
+    ix.close()

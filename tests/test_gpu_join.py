@@ -537,3 +537,33 @@ def test_full_triangle(za):
     got = ix.self_join(metric=m, max_key=ALL)
     assert got[0].size == L * (L - 1) // 2
     same(got, pairs_from(rows.tolist(), oracle_rows(X, rows, rows.tolist(), om, omode), ALL))
+
+
+@pytest.mark.parametrize("name", ["l2sq", "cos_corrected"])
+def test_walk_edges_a_chunk_of_one_tile_and_idle_waves(za, monkeypatch, name):
+    """the held-tile walk (zh_device.h) at its edges, against the family fuzz's reference: 8200 rows are 513 = 8 x 64 + 1 tiles, so the first
+    held block walks eight full chunks of ZH_JOIN_CHUNK = 64 tiles (even: the last tile in the second LDS buffer) and a chunk of ONE tile (odd,
+    no prefetch at all), the later blocks' last chunks have 61, 57, ... tiles, in every first chunk waves 1 to 3 skip the tiles before their
+    diagonal, and the last held block holds one tile of 8 rows: three idle waves.  Near-duplicates are planted so that the one-tile chunk and
+    the last block's diagonal tile both have pairs"""
+    from tests import family_cases as fc
+    n = 8200
+    spec = fc.metric_spec(name)
+    m = za.L2SquaredDistance() if name == "l2sq" else za.CosineDistance(parity=False)
+    X = wide_rows(D2)[:n].copy()
+    X[8195], X[8199] = X[20] * np.float32(1.0 + 2.0**-12), X[8193] * np.float32(1.0 + 2.0**-12)
+    sample = np.array([0, 20, 33, 63, 64, 250, 4097, 8191, 8192, 8193, 8198])
+    alive = np.ones(n, bool)
+    K = fc.key_matrix(spec, X, X[sample])
+    upper = np.arange(n)[None, :] > sample[:, None]
+    mk = fc.quantile_threshold(K, upper, 3000, n * (n - 1) / 2)
+    ref = fc.join_ref(K, sample, alive, alive, mk, 0, 0, True)
+    assert ((ref[0] == 20) & (ref[1] == 8195)).any() and ((ref[0] == 8193) & (ref[1] == 8199)).any()
+    ix = za.LSHIndex(D2, za.LSHIndexOptions(64, 4), device=0)
+    ix.append(X)
+    monkeypatch.delenv("ZH_JOIN_PATH", raising=False)
+    got = ix.self_join(metric=m, max_key=mk)
+    info = ix.join_info()
+    assert info["path"] == 2 and info["redone"] == 0 and info["tiles"] == 513 * 514 // 2 and info["launches"] == 1, info
+    assert (got[0] < got[1]).all() and info["pairs"] == got[0].size
+    same(fc.restrict(got, sample, 0), ref)

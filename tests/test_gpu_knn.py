@@ -401,3 +401,28 @@ def test_database_knn_graph(za):
     for a, (rid, rkey) in zip(live.tolist(), ref):
         assert [d for d, _ in graph[docs[a]]] == [docs[int(i)] for i in rid]
         assert [v for _, v in graph[docs[a]]] == zo.key_to_float(rkey).tolist()
+
+
+@pytest.mark.parametrize("name", ["l2sq", "cos_corrected"])
+def test_walk_edges_a_chunk_of_one_tile_and_idle_waves(za, monkeypatch, name):
+    """the held-tile walk (zh_device.h) at its edges, against the family fuzz's reference: a slab of 17 lines is two held tiles, the second with
+    one line -- two waves of the one held block are idle; a short launch walks chunks of 8 column tiles (zh_knn_chunk), and of 8200 rows the
+    second launch takes tiles 256 .. 512, 257 = 32 x 8 + 1 of them: full chunks (even: the last tile in the second LDS buffer) and a chunk of
+    ONE tile (odd, no prefetch at all).  A near-duplicate of a line is planted in that last tile"""
+    from tests import family_cases as fc
+    n, k, first = 8200, 10, 4000
+    spec = fc.metric_spec(name)
+    m = za.L2SquaredDistance() if name == "l2sq" else za.CosineDistance(parity=False)
+    X = wide_rows(D2)[:n].copy()
+    X[8197] = X[first + 16] * np.float32(1.0 + 2.0**-12)
+    slab = np.arange(first, first + 17)
+    ref = fc.graph_ref(fc.key_matrix(spec, X, X[slab]), slab, np.ones(n, bool), k, 0)
+    assert ref[0][16, 0] == 8197
+    ix = za.LSHIndex(D2, za.LSHIndexOptions(64, 4), device=0)
+    ix.append(X)
+    monkeypatch.delenv("ZH_KNN_PATH", raising=False)
+    got = ix.knn_graph(k, m, first, 17)
+    info = ix.knn_info()
+    assert info["path"] == 2 and info["redone"] == 0 and info["lines"] == 17 and info["launches"] == 2 and info["tiles"] == 2 * 513, info
+    for g, r, what in zip(got, ref, ("ids", "keys", "counts")):
+        assert g.shape == r.shape and (g == r).all(), what

@@ -646,3 +646,27 @@ def test_loaded_snapshot_of_b_answers_as_b(za, monkeypatch, tmp_path):
         same(ia.cross_join(loaded, metric=m, max_key=mk), ref)
         assert ia.cross_info()["path"] == int(p)
         same(loaded.cross_join(ia, metric=m, max_key=mk), ib.cross_join(ia, metric=m, max_key=mk))
+
+
+@pytest.mark.parametrize("name", ["l2sq", "cos_corrected"])
+def test_walk_edges_a_chunk_of_one_tile_and_idle_waves(za, monkeypatch, name):
+    """the held-tile walk (zh_device.h) at its edges, against the family fuzz's reference: B of 1040 rows is 65 column tiles -- a full chunk of
+    ZH_JOIN_CHUNK = 64 (an even number: its last tile lies in the second LDS buffer) and a chunk of ONE tile (odd, no prefetch at all); A of 17
+    rows is two held tiles, the second with one row: two waves of the one held block are idle.  Near-duplicates are planted so that the
+    one-tile chunk and the one-row tile both have pairs"""
+    from tests import family_cases as fc
+    spec = fc.metric_spec(name)
+    m = za.L2SquaredDistance() if name == "l2sq" else za.CosineDistance(parity=False)
+    XB = zo.synth_rows(1040, D2)
+    XA = zo.synth_rows(17, D2, row0=10**6).copy()
+    XA[3], XA[16] = XB[1030] * np.float32(1.0 + 2.0**-12), XB[70] * np.float32(1.0 + 2.0**-12)
+    K = fc.key_matrix(spec, XB, XA)
+    mk = fc.quantile_threshold(K, np.ones(K.shape, bool), 300, K.size)
+    ref = fc.join_ref(K, np.arange(17), np.ones(17, bool), np.ones(1040, bool), mk, 0, 0, False)
+    assert ((ref[0] == 3) & (ref[1] == 1030)).any() and ((ref[0] == 16) & (ref[1] == 70)).any() and ref[0].size >= 300
+    ia, ib = make(za, XA), make(za, XB)
+    monkeypatch.setenv("ZH_XJOIN_PATH", "2")
+    got = ia.cross_join(ib, metric=m, max_key=mk)
+    info = ia.cross_info()
+    assert info["path"] == 2 and info["redone"] == 0 and info["tiles"] == 2 * 65 and info["pairs"] == ref[0].size, info
+    same(got, ref)

@@ -2,7 +2,16 @@
 // butterflies and sums, key finalisers, row loads, the LDS bitonic sort and the select partition.  Moved verbatim out of
 // zh_search.hip in round 4 so that the half-width scan compiles on its own.  Since then also the matrix-core vector types of
 // every scan and, at the end, the pair pool's helpers (range search, forest range search, the three joins).
+//
+// Last, what the matrix-core scans of the exact and forest families (path 2) share.  tile_dot is their tile product -- the
+// summation order zh_approx_bound(metric, d, 1) is valid for (exact_mfma_kernel alone writes it out: zh_exact.hip says why).  held_tile / held_walk are the three joins' and the two graphs' scheme, written once:
+// a wave holds a 16-row tile in registers and the block walks a chunk of column tiles through two LDS buffers, one tile ahead; what becomes of a
+// 16 x 16 block of sums is a sink's business -- PoolSink appends the pairs with lo <= tau to a candidate pool (the joins; with or without the
+// upper-triangle rule), ListSink to the held line's own (row, lo, hi) list (the graphs).  A kernel is its geometry, a sink and one call of the walk.
+// zh_mfma_dispatch is the host's one switch over the dimensions and interval kinds these scans are built for.
 #pragma once
+#include <type_traits>
+
 #include "zh_internal.h"
 
 #define WAVE 64
@@ -583,4 +592,236 @@ __device__ __forceinline__ bool fjoin_owned(const uint32_t *__restrict__ leaf_of
         if (x != 0xFFFFFFFFu && x == lb[u]) return false;
     }
     return true;
+}
+
+// one candidate per lane of `pass` into a pool: slots by wave_slots (every lane of the wave is active at the call), stored while the pool has room
+__device__ __forceinline__ void pool_push(unsigned long long *__restrict__ ctr, uint64_t *__restrict__ cand, uint64_t cap, bool pass, uint64_t v,
+                                          uint32_t lane) {
+    const uint64_t m = __ballot(pass);
+    if (m) {  // (wave-uniform)
+        const unsigned long long slot = wave_slots(ctr, m, lane);  // the counter runs on past the pool
+        if (pass && slot < cap) cand[slot] = v;
+    }
+}
+
+// the last i < n with at(i) <= x (at ascending, at(0) <= x): a block's entry in a table of first blocks
+template <class AT>
+__device__ __forceinline__ uint32_t last_le(uint32_t n, uint32_t x, AT at) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (at(mid) <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the matrix-core family scans (path 2 of the exact and forest families)
+// ------------------------------------------------------------------------------------------------
+// A tile is 16 rows of an fp16 copy in the MFMA operand's own order: D / 32 steps of 64 pieces of 16 bytes, lane l's piece of step st at 64 st + l.
+// NT: the tile is streamed once (exact and range search)
+template <int D, bool NT = false>
+__device__ __forceinline__ void tile_load(f16x8 (&A)[D / 32], const u32x4 *__restrict__ X, size_t tile, uint32_t lane) {
+    const u32x4 *tp = X + tile * (D * 2) + lane;
+#pragma unroll
+    for (int st = 0; st < D / 32; st++) {
+        if constexpr (NT) A[st] = __builtin_bit_cast(f16x8, __builtin_nontemporal_load(tp + 64 * st));
+        else A[st] = __builtin_bit_cast(f16x8, tp[64 * st]);
+    }
+}
+
+// The 16 x 16 block of dot products of tile A (registers) and a tile whose piece of step st lies at bp[STRIDE * st]: 64 for a tile in operand order
+// (LDS), 4 for a query's halves (qhalf layout 1).  Four accumulators, step st into acc[st & 3], then (acc0 + acc1) + (acc2 + acc3): the summation
+// order of scan_mfma_kernel and the ONLY one zh_approx_bound(metric, d, 1) bounds -- every interval of the family scans rests on this order.
+// [i] sums one of the lane's four elements where it is used, all() the four at once: the same additions in the same order.  Which of the two a
+// scan takes decides only how the compiler schedules it: with all() the scans that read the other operand from global memory (range, forest range)
+// need fewer registers, reach a higher occupancy and wait for every load before its product -- range search at d = 768 lost 20 % that way,
+// measured.  exact_mfma_kernel (zh_exact.hip) keeps its own copy of these lines: at d = 1024 either form cost its filtered scan 27 %.
+struct TileSums {
+    f32x4 acc[4];
+    __device__ __forceinline__ float operator[](int i) const { return (acc[0][i] + acc[1][i]) + (acc[2][i] + acc[3][i]); }
+    __device__ __forceinline__ f32x4 all() const { return (acc[0] + acc[1]) + (acc[2] + acc[3]); }
+};
+template <int NS, int STRIDE>
+__device__ __forceinline__ TileSums tile_dot(const f16x8 (&A)[NS], const u32x4 *bp) {
+    TileSums t = {{{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}};
+#pragma unroll
+    for (int st = 0; st < NS; st++)
+        t.acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, bp[STRIDE * st]), t.acc[st & 3], 0, 0, 0);
+    return t;
+}
+
+// The held-tile walk (the three joins and the two graphs).  A block's four waves hold one tile each in registers -- a wave without one (`active`
+// false, wave-uniform) holds zeros, still moves tiles and meets every barrier -- and walk the column tiles [Jb, Je) of a table (CA: the tiles, crow:
+// a row-or-masked word per position, cqm: approx_interval's view of the row as a query) through two LDS buffers of 32 d bytes: tile J + 1, its crow
+// and its cqm are fetched while tile J is multiplied, one barrier per tile.  LDS holds a tile as global memory does, so each of ds_read_b128's four
+// 16-lane groups reads 16 distinct 16-byte slots: no conflict, no padding.  TI: the type tile numbers and positions are computed in.
+template <int D>
+__device__ __forceinline__ void held_tile(f16x8 (&A)[D / 32], const u32x4 *__restrict__ X, size_t tile, bool active, uint32_t lane) {
+    if (active) tile_load<D>(A, X, tile, lane);
+    else {
+#pragma unroll
+        for (int st = 0; st < D / 32; st++) A[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+}
+// sink.wants(J): does this wave multiply tile J (wave-uniform); sink(J, t, cb, qb): lane l's four sums t[i] = held row 4 (l / 16) + i against column
+// row l % 16 of tile J, whose crow and cqm are cb and qb
+template <int D, typename TI, class SINK>
+__device__ __forceinline__ void held_walk(const f16x8 (&A)[D / 32], bool active, const u32x4 *__restrict__ CA, const uint32_t *__restrict__ crow,
+                                          const float4 *__restrict__ cqm, TI Jb, TI Je, const SINK &sink) {
+    constexpr int NS = D / 32;        // MFMA steps of a tile (K = 32 each) = its KiB
+    constexpr int PIECES = NS * 64;   // 16-byte pieces of a tile
+    constexpr int PT = PIECES / 256;  // ... per thread of the block
+    __shared__ u32x4 sB[2][PIECES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, c16 = lane & 15;
+    {
+        const u32x4 *src = CA + (size_t)Jb * PIECES + tid;
+#pragma unroll
+        for (int k = 0; k < PT; k++) sB[0][k * 256 + tid] = src[k * 256];
+    }
+    // the column rows' row-or-masked word and qm travel one tile ahead, like the tile itself: nothing of tile J is fetched in its compute phase
+    uint32_t cb_next = crow[Jb * 16 + c16];
+    float4 qb_next = cqm[Jb * 16 + c16];
+    __syncthreads();
+    for (TI J = Jb; J < Je; J++) {
+        const uint32_t cur = (uint32_t)(J - Jb) & 1u;
+        const bool more = J + 1 < Je;  // (block-uniform)
+        const uint32_t cb = cb_next;
+        const float4 qb = qb_next;
+        u32x4 pf[PT];
+        if (more) {
+            const u32x4 *src = CA + (size_t)(J + 1) * PIECES + tid;
+#pragma unroll
+            for (int k = 0; k < PT; k++) pf[k] = src[k * 256];
+            cb_next = crow[(J + 1) * 16 + c16];
+            qb_next = cqm[(J + 1) * 16 + c16];
+        }
+        if (active && sink.wants(J)) sink(J, tile_dot<NS, 64>(A, &sB[cur][lane]).all(), cb, qb);  // (wave-uniform)
+        if (more) {
+#pragma unroll
+            for (int k = 0; k < PT; k++) sB[cur ^ 1][k * 256 + tid] = pf[k];
+        }
+        __syncthreads();  // buffer cur ^ 1 was last read in the step before, which every wave left through this barrier
+    }
+}
+
+// The pool sink (the joins): a pair with lo <= tau goes to the candidate pool, left << 32 | right; a masked row on either side is no pair.  UPPER
+// (one table against itself): only tiles on or above the wave's diagonal, in the diagonal tile only held row 4 h + i before column row c16, and the
+// pair as min << 32 | max (positions are not ids under a row order); else the full rectangle, held << 32 | column.
+template <int KINDA, bool UPPER, typename TI>
+struct PoolSink {
+    uint32_t lane;
+    TI I;  // the wave's held tile
+    uint32_t tq;
+    float Kc, rho;
+    uint64_t *__restrict__ cand;
+    uint64_t cap;
+    unsigned long long *__restrict__ ctr;
+    uint32_t id[4];  // this lane's held rows 4 h + i: the row-or-masked word and rowMeta
+    float2 meta[4];
+    __device__ __forceinline__ void hold(bool active, const uint32_t *__restrict__ rows, const float2 *__restrict__ rmeta) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            id[i] = 0xFFFFFFFFu;
+            meta[i] = make_float2(0.f, 0.f);
+            if (active) {
+                const TI p = I * 16 + 4 * (lane >> 4) + i;
+                id[i] = rows[p];
+                if (id[i] != 0xFFFFFFFFu) meta[i] = rmeta[p];
+            }
+        }
+    }
+    __device__ __forceinline__ bool wants(TI J) const { return !UPPER || J >= I; }
+    __device__ __forceinline__ void operator()(TI J, const f32x4 t, uint32_t cb, const float4 qb) const {
+        const uint32_t c16 = lane & 15, h = lane >> 4;
+        const bool diag = UPPER && J == I;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            bool pass = false;
+            if (id[i] != 0xFFFFFFFFu && cb != 0xFFFFFFFFu && (!diag || 4 * h + i < c16))
+                pass = (uint32_t)approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qb, Kc, rho, 0.f) <= tq;
+            const bool swap = UPPER && cb < id[i];
+            pool_push(ctr, cand, cap, pass, ((uint64_t)(swap ? cb : id[i]) << 32) | (swap ? id[i] : cb), lane);
+        }
+    }
+};
+
+// The list sink (the graphs): every held line has its own tau, count and (row, lo, hi) list -- ZhExact2's layout, `cap` slots a line of which `lim`
+// may be filled.  Self is the column with the line's own row number; a masked row on either side is no pair.  The 16 lanes of a k-group h share
+// the line: one atomic for the group, taken by its first passing lane.  A list that runs over raises *over.
+template <int KINDA>
+struct ListSink {
+    uint32_t lane;
+    float Kc, rho;
+    uint32_t *__restrict__ cnt, *__restrict__ lid, *__restrict__ llo, *__restrict__ lhi;
+    uint32_t cap, lim;
+    uint32_t *__restrict__ over;
+    uint32_t id[4], line[4], tq[4];  // this lane's held lines line0 + 4 h + i
+    float2 meta[4];
+    __device__ __forceinline__ void hold(bool active, uint32_t line0, const uint32_t *__restrict__ rows, const float2 *__restrict__ rmeta,
+                                         const uint32_t *__restrict__ tau) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            id[i] = 0xFFFFFFFFu; line[i] = 0; tq[i] = 0; meta[i] = make_float2(0.f, 0.f);
+            if (active) {
+                line[i] = line0 + 4 * (lane >> 4) + i;
+                id[i] = rows[line[i]];
+                if (id[i] != 0xFFFFFFFFu) { meta[i] = rmeta[line[i]]; tq[i] = tau[line[i]]; }
+            }
+        }
+    }
+    template <typename TI>
+    __device__ __forceinline__ bool wants(TI) const { return true; }
+    template <typename TI>
+    __device__ __forceinline__ void operator()(TI, const f32x4 t, uint32_t cb, const float4 qb) const {
+        const uint32_t c16 = lane & 15, h = lane >> 4;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            bool pass = false;
+            uint32_t lo = 0, hi = 0;
+            if (id[i] != 0xFFFFFFFFu && cb != 0xFFFFFFFFu && cb != id[i]) {
+                const uint64_t iv = approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qb, Kc, rho, 0.f);
+                lo = (uint32_t)iv; hi = (uint32_t)(iv >> 32);
+                pass = lo <= tq[i];
+            }
+            const uint64_t m = __ballot(pass);
+            if (m) {  // (wave-uniform)
+                const uint32_t gm = (uint32_t)(m >> (16 * h)) & 0xFFFFu;
+                const uint32_t leader = gm ? (uint32_t)__builtin_ctz(gm) : 0u;
+                uint32_t base = 0;
+                if (pass && c16 == leader) base = atomicAdd(&cnt[line[i]], (uint32_t)__popc(gm));
+                base = (uint32_t)__shfl((int)base, (int)(16 * h + leader), 64);
+                if (pass) {
+                    const uint32_t slot = base + (uint32_t)__popc(gm & ((1u << c16) - 1u));
+                    if (slot < lim) {
+                        const size_t o = (size_t)line[i] * cap + slot;
+                        lid[o] = cb; llo[o] = lo; lhi[o] = hi;
+                    } else
+                        atomicOr(over, 1u);
+                }
+            }
+        }
+    }
+};
+
+// ---- host side: the ONE list of dimensions the family scans are built for, and their launch dispatch ----
+template <int... DS>
+struct ZhDims {};
+typedef ZhDims<256, 384, 512, 768, 1024> ZhMfmaDims;
+// f(D, KINDA) (integral constants) for the d of the list; false: d is not in it
+template <int KINDA, class F, int... DS>
+static inline bool zh_mfma_dispatch_d(uint32_t d, F &f, ZhDims<DS...>) {
+    return ((d == (uint32_t)DS && (f(std::integral_constant<int, DS>{}, std::integral_constant<int, KINDA>{}), true)) || ...);
+}
+static inline bool zh_mfma_dim(uint32_t d) {
+    auto none = [](auto, auto) {};
+    return zh_mfma_dispatch_d<0>(d, none, ZhMfmaDims{});
+}
+// f launches the <D, KINDA> instantiation of a family's scan; KINDA = approx_interval's: 0 the L2 metrics, 1 the cosine, 2 its parity key
+template <class F>
+static inline hipError_t zh_mfma_dispatch(uint32_t d, int metric, int mode, F f) {
+    const bool known = metric != ZH_COSINE          ? zh_mfma_dispatch_d<0>(d, f, ZhMfmaDims{})
+                       : mode == ZH_COSINE_PARITY ? zh_mfma_dispatch_d<2>(d, f, ZhMfmaDims{})
+                                                  : zh_mfma_dispatch_d<1>(d, f, ZhMfmaDims{});
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }

@@ -16,10 +16,10 @@
 //           fjoin_collect_kernel takes the keys <= max_key whose row number is above the line's and that pass the first-tree rule.
 //   path 2  a batch of one tree's leaves, each padded to whole tiles by masked rows, is gathered ONCE out of the fp16 copy (zh_fknn.hip's cols /
 //           gather kernels).  fjoin_mfma_kernel is join_mfma_kernel's triangle over MANY leaves in one launch: a block finds its segment (a leaf's
-//           four held tiles from I0) by binary search over the segments' first blocks, holds tiles I0 .. I0 + 3 of that leaf in registers, one per
-//           wave, and walks ONE chunk of the leaf's tiles counted from its own diagonal through two LDS buffers; a gathered tile serves as either
-//           MFMA operand (s15).  The sum is (acc0 + acc1) + (acc2 + acc3), approx_interval's bound zh_approx_bound(metric, d, 1), the held row its
-//           "stored row", the LDS row its "query": s15's argument for two rounded operands applies word for word.  Pairs with lo <= tau go to the
+//           four held tiles from I0) by binary search over the segments' first blocks, holds tiles I0 .. I0 + 3 of that leaf, one per wave, and
+//           walks ONE chunk of the leaf's tiles counted from its own diagonal (the held-tile walk with the pool sink's upper-triangle rule,
+//           DESIGN.md s15a); a gathered tile serves as either MFMA operand (s15).  The held row is approx_interval's "stored row", the LDS row
+//           its "query": s15's argument for two rounded operands applies word for word.  Pairs with lo <= tau go to the
 //           batch's candidate pool as min(row) << 32 | max(row); pair_survivors_kernel (zh_join.hip; OWNED) applies the first-tree rule, gives the
 //           rest the canonical key of (row b, query = f32 row a), judges key <= max_key, counts and pools.
 // Scratch (all per call, released before return): leaf_of is 4 bytes per (stored row, tree) -- 4 N T, 600 MB at 10M rows x 15 trees, not chunked
@@ -70,12 +70,7 @@ __global__ __launch_bounds__(256) void fjoin_groups_kernel(const ZhFjoinPiece *_
                                                            uint64_t *__restrict__ groupRowOff) {
     const uint32_t g = blockIdx.x * 256 + threadIdx.x;
     if (g >= n_groups) return;
-    uint32_t lo = 0, hi = n_pieces;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (pieces[mid].group0 <= g) lo = mid; else hi = mid;
-    }
-    const ZhFjoinPiece pc = pieces[lo];
+    const ZhFjoinPiece pc = pieces[last_le(n_pieces, g, [&](uint32_t i) { return pieces[i].group0; })];
     const uint32_t gi = g - pc.group0, j0 = gi * ZH_GROUP_MAX, left = pc.nl - j0, gsize = left < ZH_GROUP_MAX ? left : ZH_GROUP_MAX;
     ZhGroup gr;
     gr.leaf_off = pc.off; gr.len = pc.len; gr.gsize = gsize; gr.take4 = 0;
@@ -154,118 +149,20 @@ __global__ __launch_bounds__(256) void fjoin_mfma_kernel(const ZhFjoinSeg *__res
                                                          const float2 *__restrict__ cmeta, const float4 *__restrict__ cqm, const uint32_t *__restrict__ crow,
                                                          float Kc, float rho, const uint32_t *__restrict__ tau, uint64_t *__restrict__ cand, uint64_t cap,
                                                          unsigned long long *__restrict__ ctr) {
-    constexpr int NS = D / 32;        // MFMA steps of a tile (K = 32 each)
-    constexpr int PIECES = NS * 64;   // 16-byte pieces of a tile
-    constexpr int PT = PIECES / 256;  // ... per thread of the block
-    __shared__ u32x4 sB[2][PIECES];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, h = lane >> 4;
-    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-    uint32_t lo_s = 0, hi_s = n_segs;  // the last segment whose first block is <= blockIdx.x (block-uniform)
-    while (hi_s - lo_s > 1) {
-        const uint32_t mid = (lo_s + hi_s) >> 1;
-        if (segs[mid].first_block <= blockIdx.x) lo_s = mid; else hi_s = mid;
-    }
-    const ZhFjoinSeg sg = segs[lo_s];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const ZhFjoinSeg sg = segs[last_le(n_segs, blockIdx.x, [&](uint32_t i) { return segs[i].first_block; })];  // (block-uniform)
     // tiles of the batch: the leaf's are [col0, Tend); the wave holds I, the block walks [Jb, Je)
     const uint32_t Tend = sg.col0 + sg.ct, I = sg.col0 + sg.I0 + wid;
     const uint32_t Jb = sg.col0 + sg.I0 + (blockIdx.x - sg.first_block) * ch;
     if (Jb >= Tend) return;  // (block-uniform; the host's geometry launches no such block)
     const uint32_t Je = Jb + ch < Tend ? Jb + ch : Tend;
-    const bool active = I < Tend;  // (wave-uniform; an idle wave of a leaf's last held block still moves tiles and meets the barriers)
-    f16x8 A[NS];
-    uint32_t id[4];
-    float2 meta[4];
-    if (active) {
-        const u32x4 *tp = CA + (size_t)I * PIECES + lane;
-#pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, tp[64 * st]);
-        // this lane's outputs: rows 4 h + i of the held tile (register i), column c16 = row c16 of tile J
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t p = I * 16 + 4 * h + i;
-            id[i] = crow[p];
-            meta[i] = id[i] != 0xFFFFFFFFu ? cmeta[p] : make_float2(0.f, 0.f);
-        }
-    } else {
-#pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 4; i++) { id[i] = 0xFFFFFFFFu; meta[i] = make_float2(0.f, 0.f); }
-    }
-    const uint32_t tq = tau[0];
-    {
-        const u32x4 *src = CA + (size_t)Jb * PIECES + tid;
-#pragma unroll
-        for (int k = 0; k < PT; k++) sB[0][k * 256 + tid] = src[k * 256];
-    }
-    // the column rows' row-or-masked word and qm travel one tile ahead, like the tile itself
-    uint32_t cb_next = crow[Jb * 16 + c16];
-    float4 qb_next = cqm[Jb * 16 + c16];
-    __syncthreads();
-    for (uint32_t J = Jb; J < Je; J++) {
-        const uint32_t cur = (J - Jb) & 1u;
-        const bool more = J + 1 < Je;  // (block-uniform)
-        const uint32_t cb = cb_next;
-        const float4 qb = qb_next;
-        u32x4 pf[PT];
-        if (more) {
-            const u32x4 *src = CA + (size_t)(J + 1) * PIECES + tid;
-#pragma unroll
-            for (int k = 0; k < PT; k++) pf[k] = src[k * 256];
-            cb_next = crow[(J + 1) * 16 + c16];
-            qb_next = cqm[(J + 1) * 16 + c16];
-        }
-        if (active && J >= I) {  // (wave-uniform: in its first chunk wave w skips the w tiles before its own)
-            const u32x4 *bp = &sB[cur][lane];
-            f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-            for (int st = 0; st < NS; st++)
-                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, bp[64 * st]), acc[st & 3], 0, 0, 0);
-            const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-            const bool diag = J == I;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                bool pass = false;
-                // in a diagonal tile only held row 4 h + i before column row c16; a masked row on either side is no pair
-                if (id[i] != 0xFFFFFFFFu && cb != 0xFFFFFFFFu && (!diag || 4 * h + i < c16))
-                    pass = (uint32_t)approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qb, Kc, rho, 0.f) <= tq;
-                const uint64_t m = __ballot(pass);
-                if (m) {  // (wave-uniform)
-                    const unsigned long long slot = wave_slots(ctr, m, lane);  // the counter runs on past the pool
-                    if (pass && slot < cap) {
-                        const uint32_t a = id[i] < cb ? id[i] : cb, b = id[i] < cb ? cb : id[i];
-                        cand[slot] = ((uint64_t)a << 32) | b;
-                    }
-                }
-            }
-        }
-        if (more) {
-#pragma unroll
-            for (int k = 0; k < PT; k++) sB[cur ^ 1][k * 256 + tid] = pf[k];
-        }
-        __syncthreads();  // buffer cur ^ 1 was last read in the step before, which every wave left through this barrier
-    }
-}
-
-template <int KINDA>
-static hipError_t launch_fjoin_mfma_kinda(uint32_t d, const ZhFjoinSeg *segs, uint32_t n_segs, uint32_t n_blocks, uint32_t ch, const void *CA, const float2 *cmeta,
-                                          const float4 *cqm, const uint32_t *crow, float Kc, float rho, const uint32_t *dTau, uint64_t *dCand, uint64_t cap,
-                                          unsigned long long *dCtr, hipStream_t s) {
-#define ZH_FJ_CASE(DD)                                                                                                                                  \
-    case DD:                                                                                                                                             \
-        hipLaunchKernelGGL((fjoin_mfma_kernel<DD, KINDA>), dim3(n_blocks), dim3(256), 0, s, segs, n_segs, ch, (const u32x4 *)CA, cmeta, cqm, crow, Kc, rho, \
-                           dTau, dCand, cap, dCtr);                                                                                                      \
-        break
-    switch (d) {
-        ZH_FJ_CASE(256);
-        ZH_FJ_CASE(384);
-        ZH_FJ_CASE(512);
-        ZH_FJ_CASE(768);
-        ZH_FJ_CASE(1024);
-    default: return hipErrorInvalidValue;
-    }
-#undef ZH_FJ_CASE
-    return hipGetLastError();
+    const bool active = I < Tend;  // (wave-uniform: a leaf's last held block may hold fewer than four tiles)
+    f16x8 A[D / 32];
+    held_tile<D>(A, CA, (size_t)I, active, lane);
+    PoolSink<KINDA, true, uint32_t> sink{lane, I, tau[0], Kc, rho, cand, cap, ctr};
+    sink.hold(active, crow, cmeta);
+    held_walk<D>(A, active, CA, crow, cqm, Jb, Je, sink);  // (in its first chunk wave w skips the w tiles before its own)
 }
 
 hipError_t zh_launch_fjoin_mfma(uint32_t d, int metric, int mode, const ZhFjoinSeg *dSegs, uint32_t n_segs, uint32_t n_blocks, uint32_t ch, const void *dCA,
@@ -273,8 +170,8 @@ hipError_t zh_launch_fjoin_mfma(uint32_t d, int metric, int mode, const ZhFjoinS
                                 uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s) {
     if (!n_segs || !n_blocks) return hipSuccess;
     if (!ch) return hipErrorInvalidValue;
-    if (metric != ZH_COSINE) return launch_fjoin_mfma_kinda<0>(d, dSegs, n_segs, n_blocks, ch, dCA, dCMeta, dCQm, dCRow, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
-    if (mode == ZH_COSINE_PARITY)
-        return launch_fjoin_mfma_kinda<2>(d, dSegs, n_segs, n_blocks, ch, dCA, dCMeta, dCQm, dCRow, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
-    return launch_fjoin_mfma_kinda<1>(d, dSegs, n_segs, n_blocks, ch, dCA, dCMeta, dCQm, dCRow, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
+    return zh_mfma_dispatch(d, metric, mode, [&](auto D, auto K) {
+        hipLaunchKernelGGL((fjoin_mfma_kernel<D, K>), dim3(n_blocks), dim3(256), 0, s, dSegs, n_segs, ch, (const u32x4 *)dCA, dCMeta, dCQm, dCRow, Kc, rho, dTau,
+                           dCand, cand_cap, dCandCtr);
+    });
 }

@@ -13,9 +13,9 @@
 //           (a leaf padded to whole tiles), fknn_held_kernel compacts each segment's members that lie in the slab into its held rows (stable: the
 //           leaf's order) and counts them, fknn_gather_kernel copies either list's tiles out of the copy by row number (through the row ->
 //           position map under a scan order) into the MFMA operand's order with rowMeta and the row as approx_interval's query.  fknn_mfma_kernel
-//           is knn_mfma_kernel's scheme over MANY leaves in one launch: a block finds its segment in the batch's block table, holds up to four
-//           tiles of that segment's held rows in registers and walks a chunk of the segment's column tiles through two LDS buffers -- the same
-//           (acc0 + acc1) + (acc2 + acc3) sum, approx_interval, per-line tau and (row, lo, hi) list.  A line's tau starts from its running answer
+//           is knn_mfma_kernel's scheme (the held-tile walk with the list sink) over MANY leaves in one launch: a block finds
+//           its segment in the batch's block table, holds up to four tiles of that segment's held rows and walks a chunk of the segment's
+//           column tiles.  A line's tau starts from its running answer
 //           (the k-th key after the earlier trees, through range_tau_kernel; all ones while it holds fewer than k) and is lowered by
 //           exact_prune_kernel from THIS tree's list alone, whose rows are distinct.  The survivors get the canonical key, the running answer is
 //           appended to them (fknn_seed_kernel), final_kernel ranks both with duplicates dropped by id, fknn_store_kernel writes the line back.
@@ -295,131 +295,22 @@ __global__ __launch_bounds__(256) void fknn_mfma_kernel(const ZhFknnSeg *__restr
                                                         float Kc, float rho, const uint32_t *__restrict__ tau, uint32_t *__restrict__ cnt,
                                                         uint32_t *__restrict__ lid, uint32_t *__restrict__ llo, uint32_t *__restrict__ lhi, uint32_t cap,
                                                         uint32_t lim, uint32_t *__restrict__ over) {
-    constexpr int NS = D / 32;        // MFMA steps of a tile (K = 32 each)
-    constexpr int PIECES = NS * 64;   // 16-byte pieces of a tile
-    constexpr int PT_ = PIECES / 256; // ... per thread of the block
-    __shared__ u32x4 sB[2][PIECES];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, h = lane >> 4;
-    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-    uint32_t lo_s = 0, hi_s = n_segs;  // the last segment whose first block is <= blockIdx.x (block-uniform)
-    while (hi_s - lo_s > 1) {
-        const uint32_t mid = (lo_s + hi_s) >> 1;
-        if (segs[mid].first_block <= blockIdx.x) lo_s = mid; else hi_s = mid;
-    }
-    const ZhFknnSeg sg = segs[lo_s];
-    const uint32_t n_held = held[lo_s], ht = (n_held + 15) / 16, n_hb = (sg.held_tiles + 3) / 4;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t seg = last_le(n_segs, blockIdx.x, [&](uint32_t i) { return segs[i].first_block; });  // (block-uniform)
+    const ZhFknnSeg sg = segs[seg];
+    const uint32_t n_held = held[seg], ht = (n_held + 15) / 16, n_hb = (sg.held_tiles + 3) / 4;
     const uint32_t lb = blockIdx.x - sg.first_block, hb = lb % n_hb, chunk = lb / n_hb;
     if (4 * hb >= ht) return;  // (block-uniform) no held row of the slab here
     const uint32_t I = 4 * hb + wid;   // the wave's held tile of the segment
     const uint32_t Jb = sg.col0 + chunk * ch, Jend = sg.col0 + sg.ct, Je = Jb + ch < Jend ? Jb + ch : Jend;
     if (Jb >= Je) return;  // (block-uniform; the host's geometry launches no such block)
-    const bool active = I < ht;  // (wave-uniform; an idle wave still moves tiles and meets the barriers)
-    f16x8 A[NS];
-    uint32_t id[4], line[4], tq[4];
-    float2 meta[4];
-    if (active) {
-        const u32x4 *tp = HA + ((size_t)(sg.line0 >> 4) + I) * PIECES + lane;
-#pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, tp[64 * st]);
-        // this lane's outputs: lines 4 h + i of the held tile (register i), column c16 = row c16 of tile J
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            line[i] = sg.line0 + I * 16 + 4 * h + i;
-            id[i] = hrow[line[i]];
-            const bool on = id[i] != 0xFFFFFFFFu;
-            meta[i] = on ? hmeta[line[i]] : make_float2(0.f, 0.f);
-            tq[i] = on ? tau[line[i]] : 0u;
-        }
-    } else {
-#pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 4; i++) { id[i] = 0xFFFFFFFFu; line[i] = 0; tq[i] = 0; meta[i] = make_float2(0.f, 0.f); }
-    }
-    {
-        const u32x4 *src = CA + (size_t)Jb * PIECES + tid;
-#pragma unroll
-        for (int k = 0; k < PT_; k++) sB[0][k * 256 + tid] = src[k * 256];
-    }
-    // the column rows' row-or-masked word and qm travel one tile ahead, like the tile itself
-    uint32_t cb_next = crow[Jb * 16 + c16];
-    float4 qb_next = cqm[Jb * 16 + c16];
-    __syncthreads();
-    for (uint32_t J = Jb; J < Je; J++) {
-        const uint32_t cur = (J - Jb) & 1u;
-        const bool more = J + 1 < Je;  // (block-uniform)
-        const uint32_t cb = cb_next;
-        const float4 qb = qb_next;
-        u32x4 pf[PT_];
-        if (more) {
-            const u32x4 *src = CA + (size_t)(J + 1) * PIECES + tid;
-#pragma unroll
-            for (int k = 0; k < PT_; k++) pf[k] = src[k * 256];
-            cb_next = crow[(J + 1) * 16 + c16];
-            qb_next = cqm[(J + 1) * 16 + c16];
-        }
-        if (active) {  // (wave-uniform)
-            const u32x4 *bp = &sB[cur][lane];
-            f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-            for (int st = 0; st < NS; st++)
-                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, bp[64 * st]), acc[st & 3], 0, 0, 0);
-            const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                bool pass = false;
-                uint32_t lo = 0, hi = 0;
-                // self is the column with the line's own row number; a masked row on either side is no pair
-                if (id[i] != 0xFFFFFFFFu && cb != 0xFFFFFFFFu && cb != id[i]) {
-                    const uint64_t iv = approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qb, Kc, rho, 0.f);
-                    lo = (uint32_t)iv; hi = (uint32_t)(iv >> 32);
-                    pass = lo <= tq[i];
-                }
-                const uint64_t m = __ballot(pass);
-                if (m) {  // (wave-uniform)  the 16 lanes of a k-group h share the line: one atomic for the group, taken by its first passing lane
-                    const uint32_t gm = (uint32_t)(m >> (16 * h)) & 0xFFFFu;
-                    const uint32_t leader = gm ? (uint32_t)__builtin_ctz(gm) : 0u;
-                    uint32_t base = 0;
-                    if (pass && c16 == leader) base = atomicAdd(&cnt[line[i]], (uint32_t)__popc(gm));
-                    base = (uint32_t)__shfl((int)base, (int)(16 * h + leader), 64);
-                    if (pass) {
-                        const uint32_t slot = base + (uint32_t)__popc(gm & ((1u << c16) - 1u));
-                        if (slot < lim) {
-                            const size_t o = (size_t)line[i] * cap + slot;
-                            lid[o] = cb; llo[o] = lo; lhi[o] = hi;
-                        } else
-                            atomicOr(over, 1u);
-                    }
-                }
-            }
-        }
-        if (more) {
-#pragma unroll
-            for (int k = 0; k < PT_; k++) sB[cur ^ 1][k * 256 + tid] = pf[k];
-        }
-        __syncthreads();  // buffer cur ^ 1 was last read in the step before, which every wave left through this barrier
-    }
-}
-
-template <int KINDA>
-static hipError_t launch_fknn_mfma_kinda(uint32_t d, const ZhFknnSeg *segs, uint32_t n_segs, uint32_t n_blocks, const uint32_t *held, uint32_t ch, const void *CA,
-                                         const float4 *cqm, const uint32_t *crow, const void *HA, const float2 *hmeta, const uint32_t *hrow, const ZhExact2 &e,
-                                         uint32_t lim, hipStream_t s) {
-#define ZH_FK_CASE(DD)                                                                                                                                     \
-    case DD:                                                                                                                                                \
-        hipLaunchKernelGGL((fknn_mfma_kernel<DD, KINDA>), dim3(n_blocks), dim3(256), 0, s, segs, n_segs, held, ch, (const u32x4 *)CA, cqm, crow,              \
-                           (const u32x4 *)HA, hmeta, hrow, e.Kc, e.rho, e.tau, e.cnt, e.lid, e.llo, e.lhi, e.cap, lim, e.over);                            \
-        break
-    switch (d) {
-        ZH_FK_CASE(256);
-        ZH_FK_CASE(384);
-        ZH_FK_CASE(512);
-        ZH_FK_CASE(768);
-        ZH_FK_CASE(1024);
-    default: return hipErrorInvalidValue;
-    }
-#undef ZH_FK_CASE
-    return hipGetLastError();
+    const bool active = I < ht;  // (wave-uniform)
+    f16x8 A[D / 32];
+    held_tile<D>(A, HA, (size_t)(sg.line0 >> 4) + I, active, lane);
+    ListSink<KINDA> sink{lane, Kc, rho, cnt, lid, llo, lhi, cap, lim, over};
+    sink.hold(active, sg.line0 + I * 16, hrow, hmeta, tau);
+    held_walk<D>(A, active, CA, crow, cqm, Jb, Je, sink);
 }
 
 hipError_t zh_launch_fknn_mfma(uint32_t d, int metric, int mode, const ZhFknnSeg *dSegs, uint32_t n_segs, uint32_t n_blocks, const uint32_t *dHeld, uint32_t ch,
@@ -427,9 +318,10 @@ hipError_t zh_launch_fknn_mfma(uint32_t d, int metric, int mode, const ZhFknnSeg
                                const ZhExact2 &e, uint32_t lim, hipStream_t s) {
     if (!n_segs || !n_blocks) return hipSuccess;
     if (!ch || lim > e.cap) return hipErrorInvalidValue;
-    if (metric != ZH_COSINE) return launch_fknn_mfma_kinda<0>(d, dSegs, n_segs, n_blocks, dHeld, ch, dCA, dCQm, dCRow, dHA, dHMeta, dHRow, e, lim, s);
-    if (mode == ZH_COSINE_PARITY) return launch_fknn_mfma_kinda<2>(d, dSegs, n_segs, n_blocks, dHeld, ch, dCA, dCQm, dCRow, dHA, dHMeta, dHRow, e, lim, s);
-    return launch_fknn_mfma_kinda<1>(d, dSegs, n_segs, n_blocks, dHeld, ch, dCA, dCQm, dCRow, dHA, dHMeta, dHRow, e, lim, s);
+    return zh_mfma_dispatch(d, metric, mode, [&](auto D, auto K) {
+        hipLaunchKernelGGL((fknn_mfma_kernel<D, K>), dim3(n_blocks), dim3(256), 0, s, dSegs, n_segs, dHeld, ch, (const u32x4 *)dCA, dCQm, dCRow, (const u32x4 *)dHA,
+                           dHMeta, dHRow, e.Kc, e.rho, e.tau, e.cnt, e.lid, e.llo, e.lhi, e.cap, lim, e.over);
+    });
 }
 
 // a wave per held line b: its running answer (the line's count entries of the outputs) goes behind its cnt[b] survivors in the candidate slots

@@ -24,7 +24,7 @@
 //           at most ZH_FKNN_COL_TILES row tiles are gathered ONCE from the fp16 copy (zh_fknn.hip's cols / gather kernels: operand order, rowMeta,
 //           position map under a row order).  frange_mfma_kernel: a block holds four 16-row tiles of one leaf in registers, one per wave, and walks
 //           a chunk of the leaf's 16-visitor column tiles, the queries' halves read from zh_launch_qhalf's copy exactly as range_mfma_kernel does:
-//           a leaf's rows are read once per 16 visitors (once per chunk, in fact).  The sum is (acc0 + acc1) + (acc2 + acc3), the bound
+//           a leaf's rows are read once per 16 visitors (once per chunk, in fact).  The sum is tile_dot's (zh_device.h), the bound
 //           zh_approx_bound(metric, d, 1), so approx_interval and the s14 argument "key <= max_key implies lo <= tau_q" apply unchanged.  A pair
 //           with lo <= tau_q that passes the ownership rule goes to the candidate pool as query << 32 | row; nothing is stored per scored pair.
 //           zh_launch_range_survivors then gives the candidates the canonical key, judges, counts and pools, as it is.
@@ -147,24 +147,16 @@ __global__ __launch_bounds__(256) void frange_mfma_kernel(const ZhFrangeSeg *__r
                                                           float Kc, float rho, const uint32_t *__restrict__ tau, const uint64_t *__restrict__ vsorted,
                                                           const uint64_t *__restrict__ visitBase, const uint32_t *__restrict__ leaf_of, uint32_t T,
                                                           uint64_t *__restrict__ cand, uint64_t cap, unsigned long long *__restrict__ ctr) {
-    constexpr int NS = D / 32;  // MFMA steps of a tile (K = 32 each)
     const uint32_t lane = threadIdx.x & 63, c16 = lane & 15, h = lane >> 4;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    uint32_t lo_s = 0, hi_s = n_segs;  // the last leaf whose first block is <= blockIdx.x (block-uniform)
-    while (hi_s - lo_s > 1) {
-        const uint32_t mid = (lo_s + hi_s) >> 1;
-        if (segs[mid].first_block <= blockIdx.x) lo_s = mid; else hi_s = mid;
-    }
-    const ZhFrangeSeg sg = segs[lo_s];
+    const ZhFrangeSeg sg = segs[last_le(n_segs, blockIdx.x, [&](uint32_t i) { return segs[i].first_block; })];  // the block's leaf (block-uniform)
     const uint32_t vt = (sg.visitors + 15) / 16, nch = (vt + ch - 1) / ch, k = blockIdx.x - sg.first_block;
     const uint32_t rtile = 4 * (k / nch) + wid;
     if (rtile >= sg.rt) return;  // (wave-uniform)
     const uint32_t Jb = (k % nch) * ch, Je = Jb + ch < vt ? Jb + ch : vt;
     const uint32_t I = sg.col0 + rtile;
-    f16x8 A[NS];
-    const u32x4 *tp = CA + (size_t)I * (NS * 64) + lane;
-#pragma unroll
-    for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, tp[64 * st]);
+    f16x8 A[D / 32];
+    tile_load<D>(A, CA, (size_t)I, lane);
     // this lane's outputs: rows 4 h + i of the tile (register i), column c16 = visitor 16 J + c16
     uint32_t id[4];
     float2 meta[4];
@@ -180,11 +172,7 @@ __global__ __launch_bounds__(256) void frange_mfma_kernel(const ZhFrangeSeg *__r
         const uint32_t jj = col ? j : sg.visitors - 1;  // (a padding column repeats the leaf's last visitor and passes nothing)
         const uint32_t b = groups[sg.group0 + jj / G].b[jj % G];
         const u32x4 *qp = Qh + (size_t)b * (D / 8) + h;  // step st: piece 4 st + h of the query (qhalf layout 1 = the A operand's k order)
-        f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int st = 0; st < NS; st++)
-            acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, qp[4 * st]), acc[st & 3], 0, 0, 0);
-        const f32x4 tt = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        const TileSums tt = tile_dot<D / 32, 4>(A, qp);
         const float4 qm = qmeta[b];
         const uint32_t tq = tau[b];
 #pragma unroll
@@ -193,35 +181,9 @@ __global__ __launch_bounds__(256) void frange_mfma_kernel(const ZhFrangeSeg *__r
             if (col && id[i] != 0xFFFFFFFFu) pass = (uint32_t)approx_interval<KINDA>(tt[i] * meta[i].y, meta[i].x, qm, Kc, rho, 0.f) <= tq;
             if (!__ballot(pass)) continue;  // (wave-uniform)
             if (pass) pass = frange_owned(vsorted, visitBase, leaf_of, T, sg.tree, b, id[i]);
-            const uint64_t m = __ballot(pass);
-            if (m) {  // (wave-uniform)
-                const unsigned long long slot = wave_slots(ctr, m, lane);  // the counter runs on past the pool
-                if (pass && slot < cap) cand[slot] = ((uint64_t)b << 32) | id[i];
-            }
+            pool_push(ctr, cand, cap, pass, ((uint64_t)b << 32) | id[i], lane);
         }
     }
-}
-
-template <int KINDA>
-static hipError_t launch_frange_mfma_kinda(uint32_t d, const ZhFrangeSeg *segs, uint32_t n_segs, uint32_t n_blocks, uint32_t ch, uint32_t G, const void *CA,
-                                           const float2 *cmeta, const uint32_t *crow, const ZhGroup *groups, const void *Qh, const float4 *qmeta, float Kc,
-                                           float rho, const uint32_t *dTau, const uint64_t *vsorted, const uint64_t *visitBase, const uint32_t *leafOf,
-                                           uint32_t T, uint64_t *dCand, uint64_t cap, unsigned long long *dCtr, hipStream_t s) {
-#define ZH_FR_CASE(DD)                                                                                                                                   \
-    case DD:                                                                                                                                              \
-        hipLaunchKernelGGL((frange_mfma_kernel<DD, KINDA>), dim3(n_blocks), dim3(256), 0, s, segs, n_segs, ch, G, (const u32x4 *)CA, cmeta, crow, groups, \
-                           (const u32x4 *)Qh, qmeta, Kc, rho, dTau, vsorted, visitBase, leafOf, T, dCand, cap, dCtr);                                       \
-        break
-    switch (d) {
-        ZH_FR_CASE(256);
-        ZH_FR_CASE(384);
-        ZH_FR_CASE(512);
-        ZH_FR_CASE(768);
-        ZH_FR_CASE(1024);
-    default: return hipErrorInvalidValue;
-    }
-#undef ZH_FR_CASE
-    return hipGetLastError();
 }
 
 hipError_t zh_launch_frange_mfma(uint32_t d, int metric, int mode, const ZhFrangeSeg *dSegs, uint32_t n_segs, uint32_t n_blocks, uint32_t ch, uint32_t group,
@@ -230,12 +192,8 @@ hipError_t zh_launch_frange_mfma(uint32_t d, int metric, int mode, const ZhFrang
                                  uint32_t T, uint64_t *dCand, uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s) {
     if (!n_segs || !n_blocks) return hipSuccess;
     if (!ch || !group) return hipErrorInvalidValue;
-    if (metric != ZH_COSINE)
-        return launch_frange_mfma_kinda<0>(d, dSegs, n_segs, n_blocks, ch, group, dCA, dCMeta, dCRow, dGroups, dQh, dQmeta, Kc, rho, dTau, dVSorted, dVisitBase,
-                                           dLeafOf, T, dCand, cand_cap, dCandCtr, s);
-    if (mode == ZH_COSINE_PARITY)
-        return launch_frange_mfma_kinda<2>(d, dSegs, n_segs, n_blocks, ch, group, dCA, dCMeta, dCRow, dGroups, dQh, dQmeta, Kc, rho, dTau, dVSorted, dVisitBase,
-                                           dLeafOf, T, dCand, cand_cap, dCandCtr, s);
-    return launch_frange_mfma_kinda<1>(d, dSegs, n_segs, n_blocks, ch, group, dCA, dCMeta, dCRow, dGroups, dQh, dQmeta, Kc, rho, dTau, dVSorted, dVisitBase,
-                                       dLeafOf, T, dCand, cand_cap, dCandCtr, s);
+    return zh_mfma_dispatch(d, metric, mode, [&](auto D, auto K) {
+        hipLaunchKernelGGL((frange_mfma_kernel<D, K>), dim3(n_blocks), dim3(256), 0, s, dSegs, n_segs, ch, group, (const u32x4 *)dCA, dCMeta, dCRow, dGroups,
+                           (const u32x4 *)dQh, dQmeta, Kc, rho, dTau, dVSorted, dVisitBase, dLeafOf, T, dCand, cand_cap, dCandCtr);
+    });
 }

@@ -12,15 +12,12 @@
 //           whose row number is greater than the query row's.
 //   path 2  join_mfma_kernel: BOTH operands of v_mfma_f32_16x16x32_f16 are tiles of the index's fp16 row copy (the A and the B operand have the same
 //           per-lane layout: lane l holds line l % 16, k-chunk l / 16), so a 16 x 16 block of the table's Gram matrix needs no conversion, and only
-//           the blocks on or above the diagonal are computed.  A wave holds its 16-row tile I in registers; the four waves of a block hold four
-//           consecutive tiles and share every tile J >= I through LDS (two buffers of 32 d bytes: 64 KiB at d = 1024), so a tile crosses L2 -> CU
-//           once per 64 held rows.  LDS holds a tile exactly as global memory does -- lane l reads the 16 bytes at 16 l of a 1-KiB step, which puts
-//           each of ds_read_b128's four 16-lane groups on 16 distinct 16-byte slots of the 256-byte bank row: no conflict, no padding.  The sum is
-//           (acc0 + acc1) + (acc2 + acc3) as in range_mfma_kernel: zh_approx_bound(metric, d, 1) stays the accumulation bound.  approx_interval
-//           (unchanged) gives the pair's interval: the held row is its "stored row", the LDS row its "query", whose qm = {scale, |x|^2, an upper
-//           bound of |x|, dq = rho times that bound rounded up} comes from the row's rowMeta entry (join_prep_kernel).  Pairs with lo <= tau go to a
-//           candidate pool as min(id) << 32 | max(id) (positions are not ids under a row order); pair_survivors_kernel gives every candidate the
-//           canonical key of (row b, query = f32 row a), both rows read from the f32 table, judges key <= max_key, counts and compacts.
+//           the blocks on or above the diagonal are computed: the held-tile walk of zh_device.h with the pool sink's
+//           upper-triangle rule, so a tile crosses L2 -> CU once per 64 held rows.  approx_interval (unchanged) gives the pair's interval: the
+//           held row is its "stored row", the LDS row its "query", whose qm = {scale, |x|^2, an upper bound of |x|, dq = rho times that bound
+//           rounded up} comes from the row's rowMeta entry (join_prep_kernel).  Pairs with lo <= tau go to a candidate pool as
+//           min(id) << 32 | max(id); pair_survivors_kernel gives every candidate the canonical key of (row b, query = f32 row a), both rows
+//           read from the f32 table, judges key <= max_key, counts and compacts.
 // Then, while the capacity holds, the pool is ordered by (a, key, b) with three stable LSD radix sorts (b bits, then the key, then the a bits;
 // rocPRIM through hipCUB) and pair_emit_kernel writes the three arrays.
 // Scratch (all per call, released before return): path 2 holds 20 bytes per position (qm and the id-or-masked word), 8 bytes per candidate slot of
@@ -141,115 +138,17 @@ __global__ __launch_bounds__(256) void join_mfma_kernel(const u32x4 *__restrict_
                                                         const uint32_t *__restrict__ cid, uint64_t T, uint64_t tileA0, const uint32_t *__restrict__ first,
                                                         uint32_t n_ab, float Kc, float rho, const uint32_t *__restrict__ tau, uint64_t *__restrict__ cand,
                                                         uint64_t cap, unsigned long long *__restrict__ ctr) {
-    constexpr int NS = D / 32;        // MFMA steps of a tile (K = 32 each) = its KiB
-    constexpr int PIECES = NS * 64;   // 16-byte pieces of a tile
-    constexpr int PT = PIECES / 256;  // ... per thread of the block
-    __shared__ u32x4 sB[2][PIECES];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, h = lane >> 4;
-    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-    // the held block: the last ab with first[ab] <= blockIdx.x (block-uniform)
-    uint32_t lo = 0, hi = n_ab;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (first[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    const uint64_t I0 = tileA0 + 4ull * lo, I = I0 + wid;
-    const uint64_t Jb = I0 + (uint64_t)(blockIdx.x - first[lo]) * ZH_JOIN_CHUNK, Je = Jb + ZH_JOIN_CHUNK < T ? Jb + ZH_JOIN_CHUNK : T;
-    const bool active = I < T;  // (wave-uniform; an idle wave of the table's last block still moves tiles and meets the barriers)
-    f16x8 A[NS];
-    uint32_t id[4];
-    float2 meta[4];
-    if (active) {
-        const u32x4 *tp = Xh + (size_t)I * PIECES + lane;
-#pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, tp[64 * st]);
-        // this lane's outputs: rows 4 h + i of the held tile (register i), column c16 = row c16 of tile J
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint64_t p = I * 16 + 4 * h + i;
-            id[i] = cid[p];
-            meta[i] = id[i] != 0xFFFFFFFFu ? rowMeta[p] : make_float2(0.f, 0.f);
-        }
-    } else {
-#pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 4; i++) { id[i] = 0xFFFFFFFFu; meta[i] = make_float2(0.f, 0.f); }
-    }
-    const uint32_t tq = tau[0];
-    {
-        const u32x4 *src = Xh + (size_t)Jb * PIECES + tid;
-#pragma unroll
-        for (int k = 0; k < PT; k++) sB[0][k * 256 + tid] = src[k * 256];
-    }
-    // the column rows' id-or-masked word and qm travel one tile ahead, like the tile itself: nothing of tile J is fetched in its compute phase
-    uint32_t cb_next = cid[Jb * 16 + c16];
-    float4 qb_next = qm[Jb * 16 + c16];
-    __syncthreads();
-    for (uint64_t J = Jb; J < Je; J++) {
-        const uint32_t cur = (uint32_t)(J - Jb) & 1u;
-        const bool more = J + 1 < Je;  // (block-uniform)
-        const uint32_t cb = cb_next;
-        const float4 qb = qb_next;
-        u32x4 pf[PT];
-        if (more) {
-            const u32x4 *src = Xh + (size_t)(J + 1) * PIECES + tid;
-#pragma unroll
-            for (int k = 0; k < PT; k++) pf[k] = src[k * 256];
-            cb_next = cid[(J + 1) * 16 + c16];
-            qb_next = qm[(J + 1) * 16 + c16];
-        }
-        if (active && J >= I) {  // (wave-uniform)
-            const u32x4 *bp = &sB[cur][lane];
-            f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-            for (int st = 0; st < NS; st++)
-                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, bp[64 * st]), acc[st & 3], 0, 0, 0);
-            const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-            const bool diag = J == I;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                bool pass = false;
-                // in a diagonal tile only p_a < p_b: held row 4 h + i before column row c16
-                if (id[i] != 0xFFFFFFFFu && cb != 0xFFFFFFFFu && (!diag || 4 * h + i < c16))
-                    pass = (uint32_t)approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qb, Kc, rho, 0.f) <= tq;
-                const uint64_t m = __ballot(pass);
-                if (m) {  // (wave-uniform)
-                    const unsigned long long slot = wave_slots(ctr, m, lane);
-                    if (pass && slot < cap) {
-                        const uint32_t a = id[i] < cb ? id[i] : cb, b = id[i] < cb ? cb : id[i];
-                        cand[slot] = ((uint64_t)a << 32) | b;
-                    }
-                }
-            }
-        }
-        if (more) {
-#pragma unroll
-            for (int k = 0; k < PT; k++) sB[cur ^ 1][k * 256 + tid] = pf[k];
-        }
-        __syncthreads();  // buffer cur ^ 1 was last read in the step before, which every wave left through this barrier
-    }
-}
-
-template <int KINDA>
-static hipError_t launch_join_mfma_kinda(uint32_t d, const void *Xh, const float2 *rowMeta, const float4 *qm, const uint32_t *cid, uint64_t T, uint64_t tileA0,
-                                         const uint32_t *dFirst, uint32_t n_ab, uint32_t blocks, float Kc, float rho, const uint32_t *dTau, uint64_t *dCand,
-                                         uint64_t cap, unsigned long long *dCtr, hipStream_t s) {
-#define ZH_JN_CASE(DD)                                                                                                                                 \
-    case DD:                                                                                                                                            \
-        hipLaunchKernelGGL((join_mfma_kernel<DD, KINDA>), dim3(blocks), dim3(256), 0, s, (const u32x4 *)Xh, rowMeta, qm, cid, T, tileA0, dFirst, n_ab, Kc, rho, \
-                           dTau, dCand, cap, dCtr);                                                                                                     \
-        break
-    switch (d) {
-        ZH_JN_CASE(256);
-        ZH_JN_CASE(384);
-        ZH_JN_CASE(512);
-        ZH_JN_CASE(768);
-        ZH_JN_CASE(1024);
-    default: return hipErrorInvalidValue;
-    }
-#undef ZH_JN_CASE
-    return hipGetLastError();
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t ab = last_le(n_ab, blockIdx.x, [&](uint32_t i) { return first[i]; });  // the held block (block-uniform)
+    const uint64_t I0 = tileA0 + 4ull * ab, I = I0 + wid;
+    const uint64_t Jb = I0 + (uint64_t)(blockIdx.x - first[ab]) * ZH_JOIN_CHUNK, Je = Jb + ZH_JOIN_CHUNK < T ? Jb + ZH_JOIN_CHUNK : T;
+    const bool active = I < T;  // (wave-uniform: the table's last block may hold fewer than four tiles)
+    f16x8 A[D / 32];
+    held_tile<D>(A, Xh, (size_t)I, active, lane);
+    PoolSink<KINDA, true, uint64_t> sink{lane, I, tau[0], Kc, rho, cand, cap, ctr};
+    sink.hold(active, cid, rowMeta);
+    held_walk<D>(A, active, Xh, cid, qm, Jb, Je, sink);  // (a wave skips the tiles J < I of the first chunk)
 }
 
 hipError_t zh_launch_join_mfma(uint32_t d, int metric, int mode, const void *dXh, const float2 *dRowMeta, const float4 *dQm, const uint32_t *dCid,
@@ -258,10 +157,10 @@ hipError_t zh_launch_join_mfma(uint32_t d, int metric, int mode, const void *dXh
     const uint64_t T = (n_rows + 15) / 16;
     if (!blocks || !n_ab) return hipSuccess;
     if (tileA0 % 4 || tileA0 >= T) return hipErrorInvalidValue;
-    if (metric != ZH_COSINE) return launch_join_mfma_kinda<0>(d, dXh, dRowMeta, dQm, dCid, T, tileA0, dFirst, n_ab, blocks, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
-    if (mode == ZH_COSINE_PARITY)
-        return launch_join_mfma_kinda<2>(d, dXh, dRowMeta, dQm, dCid, T, tileA0, dFirst, n_ab, blocks, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
-    return launch_join_mfma_kinda<1>(d, dXh, dRowMeta, dQm, dCid, T, tileA0, dFirst, n_ab, blocks, Kc, rho, dTau, dCand, cand_cap, dCandCtr, s);
+    return zh_mfma_dispatch(d, metric, mode, [&](auto D, auto K) {
+        hipLaunchKernelGGL((join_mfma_kernel<D, K>), dim3(blocks), dim3(256), 0, s, (const u32x4 *)dXh, dRowMeta, dQm, dCid, T, tileA0, dFirst, n_ab, Kc, rho,
+                           dTau, dCand, cand_cap, dCandCtr);
+    });
 }
 
 // The candidates' canonical keys, in the manner of range_survivors_kernel -- and their judgement, for the three joins.  A candidate is a << 32 | b:

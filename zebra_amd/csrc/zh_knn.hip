@@ -8,14 +8,11 @@
 //           over the live list, knn_emit_kernel writes each line's first k entries that are not the line's own id.  Right whatever self's key is:
 //           if self is among the k + 1 it is taken out, if it is not the first k never held it.
 //   path 2  knn_panel_kernel gathers the panel's tiles out of the fp16 row copy into scratch, in the MFMA operand's own order (the copy's own bits:
-//           its measured rho holds), with their rowMeta and row numbers.  knn_mfma_kernel is join_mfma_kernel's scheme over the full rectangle: a
-//           block's four waves hold four consecutive panel tiles in registers and walk a chunk of column tiles of the copy through two LDS buffers
-//           of 32 d bytes (the next tile, its qm and its id are fetched while the current one is multiplied; one barrier per tile; LDS holds a tile
-//           as global memory does, so ds_read_b128's four 16-lane groups each hit 16 distinct 16-byte slots: no conflict).  The sum is
-//           (acc0 + acc1) + (acc2 + acc3): zh_approx_bound(metric, d, 1) stays the bound.  The held row is approx_interval's "stored row", the
-//           column its "query" (qm from join_prep_kernel); self is excluded by row number, a masked row on either side is skipped.  Every held
-//           row has its own tau, count and (row, lo, hi) list -- ZhExact2's layout with B = the panel's lines; a pair is listed when
-//           lo <= tau[line], a list that runs over raises the flag.  The columns come in the exact search's schedule (max(k + 1, 4096) positions,
+//           its measured rho holds), with their rowMeta and row numbers.  knn_mfma_kernel is the held-tile walk of zh_device.h
+//           with the list sink: a block's four waves hold four consecutive panel tiles and walk a chunk of column tiles of the copy.  The held
+//           row is approx_interval's "stored row", the column its "query" (qm from join_prep_kernel); self is excluded by row number, a masked
+//           row on either side is skipped.  Every held row has its own tau, count and (row, lo, hi) list -- ZhExact2's layout with B = the
+//           panel's lines.  The columns come in the exact search's schedule (max(k + 1, 4096) positions,
 //           then ZH_EXACT_GROWTH times as many each launch) with exact_prune_kernel after each launch; then qnorm_kernel on the gathered f32
 //           panel, exact_survivor_keys_kernel, final_kernel -- all unchanged -- and knn_emit_kernel puts the lines at their places.  A panel
 //           whose flag is raised is answered by path 1.
@@ -82,100 +79,16 @@ __global__ __launch_bounds__(256) void knn_mfma_kernel(const u32x4 *__restrict__
                                                        const float2 *__restrict__ pmeta, const uint32_t *__restrict__ pid, uint32_t PT, float Kc, float rho,
                                                        const uint32_t *__restrict__ tau, uint32_t *__restrict__ cnt, uint32_t *__restrict__ lid,
                                                        uint32_t *__restrict__ llo, uint32_t *__restrict__ lhi, uint32_t cap, uint32_t *__restrict__ over) {
-    constexpr int NS = D / 32;        // MFMA steps of a tile (K = 32 each) = its KiB
-    constexpr int PIECES = NS * 64;   // 16-byte pieces of a tile
-    constexpr int PT_ = PIECES / 256; // ... per thread of the block
-    __shared__ u32x4 sB[2][PIECES];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, h = lane >> 4;
-    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t I = blockIdx.y * 4 + wid;  // the wave's panel tile
     const uint64_t Jb = Jt0 + (uint64_t)blockIdx.x * ch, Je = Jb + ch < Jt1 ? Jb + ch : Jt1;
-    const bool active = I < PT;  // (wave-uniform; an idle wave of the panel's last block still moves tiles and meets the barriers)
-    f16x8 A[NS];
-    uint32_t id[4], line[4], tq[4];
-    float2 meta[4];
-    if (active) {
-        const u32x4 *tp = PA + (size_t)I * PIECES + lane;
-#pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, tp[64 * st]);
-        // this lane's outputs: lines 4 h + i of the held tile (register i), column c16 = row c16 of tile J
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            line[i] = I * 16 + 4 * h + i;
-            id[i] = pid[line[i]];
-            const bool on = id[i] != 0xFFFFFFFFu;
-            meta[i] = on ? pmeta[line[i]] : make_float2(0.f, 0.f);
-            tq[i] = on ? tau[line[i]] : 0u;
-        }
-    } else {
-#pragma unroll
-        for (int st = 0; st < NS; st++) A[st] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 4; i++) { id[i] = 0xFFFFFFFFu; line[i] = 0; tq[i] = 0; meta[i] = make_float2(0.f, 0.f); }
-    }
-    {
-        const u32x4 *src = Xh + (size_t)Jb * PIECES + tid;
-#pragma unroll
-        for (int k = 0; k < PT_; k++) sB[0][k * 256 + tid] = src[k * 256];
-    }
-    // the column rows' id-or-masked word and qm travel one tile ahead, like the tile itself: nothing of tile J is fetched in its compute phase
-    uint32_t cb_next = cid[Jb * 16 + c16];
-    float4 qb_next = qm[Jb * 16 + c16];
-    __syncthreads();
-    for (uint64_t J = Jb; J < Je; J++) {
-        const uint32_t cur = (uint32_t)(J - Jb) & 1u;
-        const bool more = J + 1 < Je;  // (block-uniform)
-        const uint32_t cb = cb_next;
-        const float4 qb = qb_next;
-        u32x4 pf[PT_];
-        if (more) {
-            const u32x4 *src = Xh + (size_t)(J + 1) * PIECES + tid;
-#pragma unroll
-            for (int k = 0; k < PT_; k++) pf[k] = src[k * 256];
-            cb_next = cid[(J + 1) * 16 + c16];
-            qb_next = qm[(J + 1) * 16 + c16];
-        }
-        if (active) {  // (wave-uniform)
-            const u32x4 *bp = &sB[cur][lane];
-            f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-            for (int st = 0; st < NS; st++)
-                acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, bp[64 * st]), acc[st & 3], 0, 0, 0);
-            const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                bool pass = false;
-                uint32_t lo = 0, hi = 0;
-                // self is the column with the line's own row number; a masked row on either side is no pair
-                if (id[i] != 0xFFFFFFFFu && cb != 0xFFFFFFFFu && cb != id[i]) {
-                    const uint64_t iv = approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qb, Kc, rho, 0.f);
-                    lo = (uint32_t)iv; hi = (uint32_t)(iv >> 32);
-                    pass = lo <= tq[i];
-                }
-                const uint64_t m = __ballot(pass);
-                if (m) {  // (wave-uniform)  the 16 lanes of a k-group h share the line: one atomic for the group, taken by its first passing lane
-                    const uint32_t gm = (uint32_t)(m >> (16 * h)) & 0xFFFFu;
-                    const uint32_t leader = gm ? (uint32_t)__builtin_ctz(gm) : 0u;
-                    uint32_t base = 0;
-                    if (pass && c16 == leader) base = atomicAdd(&cnt[line[i]], (uint32_t)__popc(gm));
-                    base = (uint32_t)__shfl((int)base, (int)(16 * h + leader), 64);
-                    if (pass) {
-                        const uint32_t slot = base + (uint32_t)__popc(gm & ((1u << c16) - 1u));
-                        if (slot < cap) {
-                            const size_t o = (size_t)line[i] * cap + slot;
-                            lid[o] = cb; llo[o] = lo; lhi[o] = hi;
-                        } else
-                            atomicOr(over, 1u);
-                    }
-                }
-            }
-        }
-        if (more) {
-#pragma unroll
-            for (int k = 0; k < PT_; k++) sB[cur ^ 1][k * 256 + tid] = pf[k];
-        }
-        __syncthreads();  // buffer cur ^ 1 was last read in the step before, which every wave left through this barrier
-    }
+    const bool active = I < PT;  // (wave-uniform: the panel's last block may hold fewer than four tiles)
+    f16x8 A[D / 32];
+    held_tile<D>(A, PA, (size_t)I, active, lane);
+    ListSink<KINDA> sink{lane, Kc, rho, cnt, lid, llo, lhi, cap, cap, over};
+    sink.hold(active, I * 16, pid, pmeta, tau);
+    held_walk<D>(A, active, Xh, cid, qm, Jb, Je, sink);
 }
 
 // column tiles a block walks: ZH_KNN_CHUNK, fewer in a short launch so that it still fills the device (about 1024 blocks), never under 8
@@ -184,36 +97,17 @@ uint32_t zh_knn_chunk(uint64_t tiles, uint32_t n_ab) {
     return (uint32_t)std::min<uint64_t>(ZH_KNN_CHUNK, std::max<uint64_t>(8, c));
 }
 
-template <int KINDA>
-static hipError_t launch_knn_mfma_kinda(uint32_t d, const ZhExact2 &e, const float4 *qm, const uint32_t *cid, uint64_t Jt0, uint64_t Jt1, const void *dA,
-                                        const float2 *pmeta, const uint32_t *pid, hipStream_t s) {
-    const uint32_t PT = (e.B + 15) / 16, n_ab = (PT + 3) / 4, ch = zh_knn_chunk(Jt1 - Jt0, n_ab);
-    const dim3 grid((uint32_t)((Jt1 - Jt0 + ch - 1) / ch), n_ab);
-#define ZH_KN_CASE(DD)                                                                                                                                     \
-    case DD:                                                                                                                                                \
-        hipLaunchKernelGGL((knn_mfma_kernel<DD, KINDA>), grid, dim3(256), 0, s, (const u32x4 *)e.Xh, qm, cid, Jt0, Jt1, ch, (const u32x4 *)dA, pmeta, pid, PT, \
-                           e.Kc, e.rho, e.tau, e.cnt, e.lid, e.llo, e.lhi, e.cap, e.over);                                                                  \
-        break
-    switch (d) {
-        ZH_KN_CASE(256);
-        ZH_KN_CASE(384);
-        ZH_KN_CASE(512);
-        ZH_KN_CASE(768);
-        ZH_KN_CASE(1024);
-    default: return hipErrorInvalidValue;
-    }
-#undef ZH_KN_CASE
-    return hipGetLastError();
-}
-
 hipError_t zh_launch_knn_mfma(uint32_t d, int metric, int mode, const ZhExact2 &e, const float4 *dQm, const uint32_t *dCid, uint64_t p_begin, uint64_t p_end,
                               const void *dA, const float2 *dPMeta, const uint32_t *dPid, hipStream_t s) {
     if (p_begin >= p_end || !e.B) return hipSuccess;
     if (p_begin % 16 || e.B > ZH_KNN_PANEL_ROWS) return hipErrorInvalidValue;
     const uint64_t Jt0 = p_begin / 16, Jt1 = (p_end + 15) / 16;
-    if (metric != ZH_COSINE) return launch_knn_mfma_kinda<0>(d, e, dQm, dCid, Jt0, Jt1, dA, dPMeta, dPid, s);
-    if (mode == ZH_COSINE_PARITY) return launch_knn_mfma_kinda<2>(d, e, dQm, dCid, Jt0, Jt1, dA, dPMeta, dPid, s);
-    return launch_knn_mfma_kinda<1>(d, e, dQm, dCid, Jt0, Jt1, dA, dPMeta, dPid, s);
+    const uint32_t PT = (e.B + 15) / 16, n_ab = (PT + 3) / 4, ch = zh_knn_chunk(Jt1 - Jt0, n_ab);
+    const dim3 grid((uint32_t)((Jt1 - Jt0 + ch - 1) / ch), n_ab);
+    return zh_mfma_dispatch(d, metric, mode, [&](auto D, auto K) {
+        hipLaunchKernelGGL((knn_mfma_kernel<D, K>), grid, dim3(256), 0, s, (const u32x4 *)e.Xh, dQm, dCid, Jt0, Jt1, ch, (const u32x4 *)dA, dPMeta, dPid, PT, e.Kc,
+                           e.rho, e.tau, e.cnt, e.lid, e.llo, e.lhi, e.cap, e.over);
+    });
 }
 
 // A panel's answer to its lines' places: a wave per line b.  in_*: [B][w] as final_kernel wrote them (ids = id_base + row, ascending by (key, id),

@@ -90,16 +90,13 @@ __global__ __launch_bounds__(256) void range_mfma_kernel(const u32x4 *__restrict
                                                          const u32x4 *__restrict__ Qh, const float4 *__restrict__ qmeta, uint32_t B, float Kc, float rho,
                                                          const uint32_t *__restrict__ tau, uint64_t *__restrict__ cand, uint64_t cap,
                                                          unsigned long long *__restrict__ ctr) {
-    constexpr int NS = D / 32;  // MFMA steps of a tile (K = 32 each)
     const uint32_t lane = threadIdx.x & 63, c16 = lane & 15, h = lane >> 4;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t tile = p_begin / 16 + (uint64_t)blockIdx.x * 4 + wid;
     const uint64_t p0 = tile * 16;
     if (p0 >= p_end) return;
-    f16x8 A[NS];
-    const u32x4 *tp = Xh + (size_t)tile * (NS * 64) + lane;
-#pragma unroll
-    for (int st = 0; st < NS; st++) A[st] = __builtin_bit_cast(f16x8, __builtin_nontemporal_load(tp + 64 * st));
+    f16x8 A[D / 32];
+    tile_load<D, true>(A, Xh, (size_t)tile, lane);
     // this lane's outputs: rows 4 h + i of the tile (register i), column c16
     bool valid[4];
     uint32_t id[4];
@@ -115,54 +112,27 @@ __global__ __launch_bounds__(256) void range_mfma_kernel(const u32x4 *__restrict
     for (uint32_t q0 = 0; q0 < B; q0 += 16) {
         const uint32_t b = q0 + c16, bq = b < B ? b : B - 1;
         const u32x4 *qp = Qh + (size_t)bq * (D / 8) + h;  // step st: piece 4 st + h of the query (qhalf layout 1 = the A operand's k order)
-        f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int st = 0; st < NS; st++)
-            acc[st & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[st], __builtin_bit_cast(f16x8, qp[4 * st]), acc[st & 3], 0, 0, 0);
-        const f32x4 t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        const TileSums t = tile_dot<D / 32, 4>(A, qp);
         const float4 qm = qmeta[bq];
         const uint32_t tq = tau[bq];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             bool pass = false;
             if (b < B && valid[i]) pass = (uint32_t)approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qm, Kc, rho, 0.f) <= tq;
-            const uint64_t m = __ballot(pass);
-            if (m) {  // (wave-uniform)
-                const unsigned long long slot = wave_slots(ctr, m, lane);
-                if (pass && slot < cap) cand[slot] = ((uint64_t)b << 32) | id[i];
-            }
+            pool_push(ctr, cand, cap, pass, ((uint64_t)b << 32) | id[i], lane);
         }
     }
-}
-
-template <int KINDA>
-static hipError_t launch_range_mfma_kinda(uint32_t d, const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, uint64_t *dCand, uint64_t cap,
-                                          unsigned long long *dCtr, hipStream_t s) {
-    const uint64_t tiles = (p_end - p_begin + 15) / 16, blocks = (tiles + 3) / 4;
-#define ZH_RG_CASE(DD)                                                                                                                              \
-    case DD:                                                                                                                                         \
-        hipLaunchKernelGGL((range_mfma_kernel<DD, KINDA>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4 *)e.Xh, e.rowMeta, e.perm, e.perm_rows, \
-                           e.liveBits, p_begin, p_end, (const u32x4 *)e.Qh, e.qmeta, e.B, e.Kc, e.rho, (const uint32_t *)e.tau, dCand, cap, dCtr);     \
-        break
-    switch (d) {
-        ZH_RG_CASE(256);
-        ZH_RG_CASE(384);
-        ZH_RG_CASE(512);
-        ZH_RG_CASE(768);
-        ZH_RG_CASE(1024);
-    default: return hipErrorInvalidValue;
-    }
-#undef ZH_RG_CASE
-    return hipGetLastError();
 }
 
 hipError_t zh_launch_range_mfma(uint32_t d, int metric, int mode, const ZhExact2 &e, uint64_t p_begin, uint64_t p_end, uint64_t *dCand, uint64_t cand_cap,
                                 unsigned long long *dCandCtr, hipStream_t s) {
     if (p_begin >= p_end || !e.B) return hipSuccess;
     if (p_begin % 16) return hipErrorInvalidValue;
-    if (metric != ZH_COSINE) return launch_range_mfma_kinda<0>(d, e, p_begin, p_end, dCand, cand_cap, dCandCtr, s);
-    if (mode == ZH_COSINE_PARITY) return launch_range_mfma_kinda<2>(d, e, p_begin, p_end, dCand, cand_cap, dCandCtr, s);
-    return launch_range_mfma_kinda<1>(d, e, p_begin, p_end, dCand, cand_cap, dCandCtr, s);
+    const uint64_t tiles = (p_end - p_begin + 15) / 16, blocks = (tiles + 3) / 4;
+    return zh_mfma_dispatch(d, metric, mode, [&](auto D, auto K) {
+        hipLaunchKernelGGL((range_mfma_kernel<D, K>), dim3((uint32_t)blocks), dim3(256), 0, s, (const u32x4 *)e.Xh, e.rowMeta, e.perm, e.perm_rows, e.liveBits,
+                           p_begin, p_end, (const u32x4 *)e.Qh, e.qmeta, e.B, e.Kc, e.rho, (const uint32_t *)e.tau, dCand, cand_cap, dCandCtr);
+    });
 }
 
 // The candidates' canonical keys, in the manner of exact_survivor_keys_kernel -- and their judgement.  A wave takes 64 candidates at a time: pair j's

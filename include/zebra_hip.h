@@ -975,6 +975,38 @@ ZH_API int zh_debug_keep_raw(zh_index *idx, int on);
  * upper estimate of |q|, upper estimate of |q - h / sigma_q|} (NaN: nothing certain about the query) */
 ZH_API int zh_debug_scan_pairs(zh_index *idx, zh_search_ctx *ctx, zh_debug_scan_info *info, zh_debug_pair *out, size_t cap, float *qmeta);
 
+/* ---- test / debug access: the intervals of the joins' and the graphs' matrix-core scans, pair by pair -------------------
+ * zh_self_join, zh_cross_join, zh_knn_graph, zh_knn_graph_forest and zh_self_join_forest (their path 2) never compute the key of most pairs: a
+ * 16 x 16 block of dot products of two tiles of the fp16 row copies gives every pair an interval, the "query" of the pair being a STORED row of
+ * the copy (its rounding assumed from the copy's rho, not measured), and only pairs whose interval reaches the threshold get the canonical key.
+ * The answers are the reference's only if every interval contains the key.  zh_debug_walk_pairs lets a test check that pair by pair
+ * (tests/test_gpu_pair_intervals.py): it runs the same held-tile walk -- the same tile product, LDS double buffer, per-position views and interval
+ * arithmetic -- with a sink that RECORDS instead of judging, over the rectangle
+ *     held positions [first_pos, first_pos + n_pos) of `left`'s copy  x  every position of `right`'s copy (16 * ceil(stored rows / 16) of them),
+ * one record per pair, at (held_pos - first_pos) * info->col_positions + col_pos.  `right` == `left`: the self-join's and the graphs' view; another
+ * index: the cross join's (the held side takes left's rho, right's rho goes into the column rows' query view).  A position is a place in the
+ * copy: row number = position unless the copy is in a row order.  held_row / col_row = the row number at the position, UINT32_MAX for a removed row
+ * and for the tail of the last tile (masked: the product scans make no pair of it; lo / hi / raw_s of such a record mean nothing).  lo / hi: as
+ * zh_debug_pair's, (0, ~0) = nothing certain.  raw_s = the block's sum for the pair times the held row's 1 / sigma, i.e. x^ . y^ / sigma_x with the
+ * column row still scaled.  first_pos must be a multiple of 64, n_pos at most 1024, the slab inside the copy; dim and metric those the
+ * matrix-core scans serve (else ZH_EINVAL).  out == NULL with cap 0: only *info.  cap < info->pairs: ZH_ELIMIT, *info is set and nothing is
+ * stored.  Not a product path: both indexes are locked for the call, the records are staged in device memory and copied out. */
+typedef struct zh_debug_walk_pair {
+    uint32_t held_pos, col_pos;  /* positions in left's / right's copy */
+    uint32_t held_row, col_row;  /* local row numbers (without id_base), or UINT32_MAX: masked */
+    uint32_t lo, hi;             /* the interval, sortable f32 */
+    float raw_s;
+} zh_debug_walk_pair;
+typedef struct zh_debug_walk_info {
+    uint64_t pairs;              /* records of the rectangle = held_positions * col_positions */
+    uint64_t held_positions, col_positions;
+    float bound_const;           /* zh_approx_bound of the family scans */
+    float rho_left, rho_right;   /* the two copies' measured relative rounding error */
+    uint32_t order_left, order_right; /* 1: that copy is in a row order (positions are not row numbers) */
+} zh_debug_walk_info;
+ZH_API int zh_debug_walk_pairs(zh_index *left, zh_index *right, int metric, int cosine_mode, uint64_t first_pos, uint64_t n_pos,
+                               zh_debug_walk_info *info, zh_debug_walk_pair *out, size_t cap);
+
 /* ---- instrumentation ------------------------------------------------------------------------ */
 ZH_API int zh_set_profiling(zh_index *idx, int level); /* 0 off, 1 per-stage hipEvent timing, 2 + unique-row count */
 ZH_API int zh_stats(zh_index *idx, zh_stats_t *out);

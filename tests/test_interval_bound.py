@@ -95,6 +95,16 @@ def row_half(x, sigma=None):
     return h, inv, rho
 
 
+def row_as_query(a2, inv_sigma, rho):
+    """row_as_query (zh_device.h; join_prep_kernel, fknn_gather_kernel): a STORED row of the fp16 copy as approx_interval's query, from its rowMeta
+    {f32 |x|^2, 1 / sigma} and the table's rho -> {1 / sigma, |x|^2, nq, dq}: dq is ASSUMED (rho * nq, rounded up), where qhalf measures it.  A scale
+    outside 2^-104 .. 2^76 or a norm that is no finite number: four NaNs -- nothing certain"""
+    if not (F(2.0 ** -104) <= inv_sigma <= F(2.0 ** 76)) or not np.isfinite(a2):
+        return F(np.nan), F(np.nan), F(np.nan), F(np.nan)
+    nq = F(F(np.sqrt(a2)) * F(1.0 + 1e-5))
+    return F(inv_sigma), F(a2), nq, F(F(F(rho) * nq) * F(1.0000005))
+
+
 def bound(metric_cos, d, kind):
     c0 = (d + 255) // 256 + 8.0
     ops = (2 * 33.0 + 2.0 + 40.0) if kind == 2 else ((33.0 * (d // 128) + 2.0) if kind else 0.0)
@@ -188,3 +198,72 @@ def test_intervals_contain_the_reference_key(d, kind):
                         assert lo <= key <= hi, ("cos", d, kind, i, order, lo, key, hi)
                         checked += 1
     assert checked > 150
+
+
+def test_row_as_query_usability():
+    """the view's own tests: the accepted scales are 2^-104 .. 2^76 inclusive, the norm any finite number (0 too: approx_interval judges it)"""
+    for inv, a2, ok in ((F(2.0 ** -104), F(1), True), (F(2.0 ** 76), F(1), True), (F(2.0 ** -105), F(1), False), (F(2.0 ** 77), F(1), False),
+                        (F(1), F(0), True), (F(1), F(np.inf), False), (F(1), F(np.nan), False), (F(np.nan), F(1), False)):
+        v = row_as_query(a2, inv, F(2.0 ** -12))
+        assert np.isfinite(v).all() == ok and np.isnan(v).all() == (not ok), (inv, a2, v)
+    inv, a2, nq, dq = row_as_query(F(9), F(0.5), F(2.0 ** -12))
+    assert (inv, a2) == (F(0.5), F(9)) and nq >= 3 and dq >= np.float64(F(2.0 ** -12)) * np.float64(nq)   # dq is rounded UP
+
+
+def misses_of_row_pairs(X, Y, d, rho_held, rho_col, drop=False):
+    """Every pair (held row X[i], column row Y[j]) of the joins' and the graphs' matrix-core scans, restated: both operands are row_half copies, the
+    column row is approx_interval's query through row_as_query with ITS table's rho, the held row is the stored row with its own table's.  The pool
+    stores a pair without orientation: the interval must contain the reference's key of (stored Y[j], query X[i]) and of (stored X[i], query Y[j]).
+    drop: the rounding terms left out (dq = 0, rho = 0) -> (intervals checked, [those that miss a key])"""
+    n = X.shape[0]
+    HX, HY = [row_half(x) for x in X], [row_half(y) for y in Y]
+    miss, checked = [], 0
+    for i, x in enumerate(X):
+        xh, inv_x, _ = HX[i]
+        a2 = f32_sum((x * x).astype(F), "pairwise")
+        for j in (i, (i + 5) % n):
+            y = Y[j]
+            yh, inv_y, _ = HY[j]
+            inv_q, b2, nq, dq = row_as_query(f32_sum((y * y).astype(F), "pairwise"), inv_y, F(0) if drop else rho_col)
+            rho = F(0) if drop else rho_held
+            if not np.isfinite(inv_q):
+                continue  # (nothing certain)
+            l2 = [np.float64(zo.distance_sums(*p)[3]) for p in ((x, y), (y, x))]
+            cos = [np.array([zo.distance(zo.COSINE, zo.CORRECTED, *p)], np.uint64).view(np.float64)[0] for p in ((x, y), (y, x))]
+            for order in ("blocks32", "down", "7"):
+                s = F(f32_sum((xh.astype(F) * yh.astype(F)).astype(F), order) * inv_x)
+                if not (np.isfinite(s) and np.isfinite(a2) and np.isfinite(b2)):
+                    continue  # (the device hands such a pair the interval (-inf, +inf))
+                lo, hi = interval_l2(s, a2, inv_q, b2, nq, dq, bound(False, d, 1), rho, F(0))
+                if np.isfinite(lo) and np.isfinite(hi) and F(a2 + b2) < F(1e37):
+                    checked += 1
+                    if not all(lo <= k <= hi for k in l2):
+                        miss.append(("l2", i, j, order, lo, l2, hi))
+                if a2 > 0 and b2 > 0:
+                    lo, hi = interval_cos(s, a2, inv_q, b2, dq, bound(True, d, 1), rho, F(0))
+                    if np.isfinite(lo) and np.isfinite(hi) and F(np.sqrt(a2)) > F(1e-12) and F(np.sqrt(b2)) > F(1e-12):
+                        checked += 1
+                        if not all(lo <= k <= hi for k in cos):
+                            miss.append(("cos", i, j, order, lo, cos, hi))
+    return checked, miss
+
+
+@pytest.mark.parametrize("d", [256, 768])
+def test_row_as_query_intervals_contain_the_reference_key(d):
+    """The row-as-query view of path 2 of the join, cross join, k-NN graph, forest graph and forest join: one table (one rho on
+    both sides) and two tables with different rho in both directions -- the held side takes its own table's, the column's goes into dq.  The
+    negative control shows the inputs are not tame: without the rounding terms the same pairs miss."""
+    n = 24
+    X, Y = rows_and_queries(3000 + d, d, n)
+    rho_x = max(row_half(x)[2] for x in X)
+    rho_y = max(row_half(y)[2] for y in Y)
+    assert rho_x > 0 and rho_y > 0 and rho_x != rho_y
+    for what, (A, B, rho_held, rho_col) in {"one table": (X, Y, max(rho_x, rho_y), max(rho_x, rho_y)), "X held, Y columns": (X, Y, rho_x, rho_y),
+                                            "Y held, X columns": (Y, X, rho_y, rho_x)}.items():
+        checked, miss = misses_of_row_pairs(A, B, d, rho_held, rho_col)
+        assert checked > 250, (what, checked)
+        assert not miss, (what, d, len(miss), checked, miss[0])
+    if d == 256:
+        checked, miss = misses_of_row_pairs(X, Y, d, rho_x, rho_y, drop=True)
+        print(f"negative control, d = {d}: {len(miss)} of {checked} intervals miss without dq and rho")
+        assert checked > 250 and len(miss) >= 1, "the inputs are too tame: intervals without the rounding terms still contain every key"

@@ -80,6 +80,19 @@ class DebugScanInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DebugWalkPair(C.Structure):
+    _fields_ = [("held_pos", C.c_uint32), ("col_pos", C.c_uint32), ("held_row", C.c_uint32), ("col_row", C.c_uint32), ("lo", C.c_uint32),
+                ("hi", C.c_uint32), ("raw_s", C.c_float)]
+
+
+class DebugWalkInfo(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("held_positions", C.c_uint64), ("col_positions", C.c_uint64), ("bound_const", C.c_float),
+                ("rho_left", C.c_float), ("rho_right", C.c_float), ("order_left", C.c_uint32), ("order_right", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class ExactInfo(C.Structure):
     _fields_ = [("batch", C.c_uint64), ("rows_live", C.c_uint64), ("path", C.c_uint32), ("redone", C.c_uint32), ("survivors", C.c_uint64),
                 ("launches", C.c_uint64)]
@@ -277,6 +290,7 @@ SYMBOLS = [
     ("zh_ref_header_encode", _i, [_vp, _vp, _vp, _sz, _vp]),
     ("zh_debug_keep_raw", _i, [_vp, _i]),
     ("zh_debug_scan_pairs", _i, [_vp, _vp, _vp, _vp, _sz, _vp]),
+    ("zh_debug_walk_pairs", _i, [_vp, _vp, _i, _i, _u64, _u64, _vp, _vp, _sz]),
     ("zh_set_profiling", _i, [_vp, _i]),
     ("zh_stats", _i, [_vp, _vp]),
     ("zh_stats_reset", _i, [_vp]),

@@ -4635,6 +4635,66 @@ extern "C" int zh_cross_join(zh_index *ia, zh_index *ib, uint64_t max_key, int m
 
 extern "C" int zh_cross_join_info(const zh_index *ia, zh_cross_info *out) { return get_info(ia, &zh_index::xj_info, out, "zh_cross_join_info"); }
 
+// ---- test / debug access (include/zebra_hip.h): the held-tile walk's interval of every pair of a slab of `ia`'s positions x all of `ib`'s, through
+// the inputs path 2 of the joins prepares and by the host functions it prepares them with -- the copy's view, zh_launch_join_prep per side,
+// zh_approx_bound(metric, d, 1), the held side's rho -- and the walk itself under a recording sink (zh_walkdbg.hip).  ia == ib: the self-join's view
+extern "C" int zh_debug_walk_pairs(zh_index *ia, zh_index *ib, int metric, int mode, uint64_t first_pos, uint64_t n_pos, zh_debug_walk_info *info,
+                                   zh_debug_walk_pair *out, size_t cap) {
+    if (!ia || !ib || !info || (cap && !out)) return fail(ZH_EINVAL, "zh_debug_walk_pairs: null argument");
+    int rc = check_metric(metric, mode);
+    if (rc) return rc;
+    std::unique_lock<std::shared_mutex> la(ia->mu, std::defer_lock), lb(ib->mu, std::defer_lock);
+    if (ia == ib) la.lock();
+    else std::lock(la, lb);
+    memset(info, 0, sizeof(*info));
+    const uint32_t d = ia->opt.dim;
+    if (ib->opt.dim != d) return fail(ZH_EINVAL, "zh_debug_walk_pairs: the indexes have different dim (%u and %u)", d, ib->opt.dim);
+    if (ia->device != ib->device) return fail(ZH_EINVAL, "zh_debug_walk_pairs: the indexes live on different devices (%d and %d)", ia->device, ib->device);
+    if (!zh_exact_mfma_supported(d, metric)) return fail(ZH_EINVAL, "zh_debug_walk_pairs: no matrix-core scan for dim %u, metric %d", d, metric);
+    if ((rc = set_device(ia)) || (rc = exact_live_rows(ia)) || (ib != ia && (rc = exact_live_rows(ib)))) return rc;
+    HalfView va, vb;
+    bool have_a = false, have_b = false;
+    {
+        std::lock_guard<std::mutex> lk(ia->blk_mu);
+        if ((rc = half_view(ia, &va, &have_a))) return rc;
+    }
+    if (ib == ia) { vb = va; have_b = have_a; }
+    else {
+        std::lock_guard<std::mutex> lk(ib->blk_mu);
+        if ((rc = half_view(ib, &vb, &have_b))) return rc;  // (complete on return: ensure_row_half waits for ib's stream)
+    }
+    if (!have_a || !have_b) return fail(ZH_ESTATE, "zh_debug_walk_pairs: an index has no fp16 copy of its rows");
+    const uint64_t na = ia->n_rows, nb = ib->n_rows, TA = (na + 15) / 16, TB = (nb + 15) / 16;
+    if (first_pos % 64 || !n_pos || n_pos > ZH_DEBUG_WALK_ROWS || first_pos + n_pos > TA * 16)
+        return fail(ZH_EINVAL, "zh_debug_walk_pairs: a slab starts on a multiple of 64 positions, holds 1 .. %u and ends inside the copy (%llu positions)",
+                    ZH_DEBUG_WALK_ROWS, (unsigned long long)(TA * 16));
+    const float Kc = zh_approx_bound(metric, d, 1);
+    info->held_positions = n_pos; info->col_positions = TB * 16; info->pairs = n_pos * TB * 16;
+    info->bound_const = Kc; info->rho_left = va.rho; info->rho_right = vb.rho;
+    info->order_left = va.perm ? 1u : 0u; info->order_right = vb.perm ? 1u : 0u;
+    if (!out && !cap) return ZH_OK;
+    if (cap < info->pairs) return fail(ZH_ELIMIT, "zh_debug_walk_pairs: %llu pairs, room for %zu", (unsigned long long)info->pairs, cap);
+    if (!info->pairs) return ZH_OK;
+    struct Scratch {
+        DevBuf qma, cida, qmb, cidb, rec;
+        ~Scratch() { qma.release(); cida.release(); qmb.release(); cidb.release(); rec.release(); }
+    } w;
+    const size_t rec_bytes = (size_t)info->pairs * sizeof(zh_debug_walk_pair);
+    if ((rc = w.qma.ensure(TA * 16 * 16)) || (rc = w.cida.ensure(TA * 16 * 4)) || (rc = w.rec.ensure(rec_bytes))) return rc;
+    if (ib != ia && ((rc = w.qmb.ensure(TB * 16 * 16)) || (rc = w.cidb.ensure(TB * 16 * 4)))) return rc;
+    const hipStream_t s = ia->stream;
+    HIPCHK(zh_launch_join_prep(va.rowMeta, va.perm, va.perm_rows, ia->ex_bits.as<uint32_t>(), na, va.rho, w.qma.as<float4>(), w.cida.as<uint32_t>(), s));
+    if (ib != ia)
+        HIPCHK(zh_launch_join_prep(vb.rowMeta, vb.perm, vb.perm_rows, ib->ex_bits.as<uint32_t>(), nb, vb.rho, w.qmb.as<float4>(), w.cidb.as<uint32_t>(), s));
+    const DevBuf &qmB = ib != ia ? w.qmb : w.qma, &cidB = ib != ia ? w.cidb : w.cida;
+    HIPCHK(hipMemsetAsync(w.rec.p, 0xFF, rec_bytes, s));  // (a record the walk did not write: positions all ones)
+    HIPCHK(zh_launch_walk_debug(d, metric, mode, va.Xh, va.rowMeta, w.cida.as<uint32_t>(), na, vb.Xh, qmB.as<float4>(), cidB.as<uint32_t>(), nb, first_pos,
+                                first_pos + n_pos, Kc, va.rho, w.rec.as<zh_debug_walk_pair>(), info->pairs, s));
+    HIPCHK(hipMemcpyAsync(out, w.rec.p, rec_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return ZH_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // exact k-NN graph (zh_knn.hip + the exact search's two paths): each live row's k nearest OTHER live rows, slab by slab.  DESIGN.md s16
 // ------------------------------------------------------------------------------------------------

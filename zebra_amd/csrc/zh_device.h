@@ -509,6 +509,20 @@ __device__ __forceinline__ uint64_t approx_interval(float s, float a2, const flo
     return ((uint64_t)hi_s << 32) | lo_s;
 }
 
+// A STORED row of the fp16 copy as approx_interval's query (the joins and the graphs: join_prep_kernel, fknn_gather_kernel): rm = the row's rowMeta
+// {f32 |x|^2, 1 / sigma}, rho the copy's -> {1 / sigma, |x|^2, nq >= |x|, dq >= |x - x'|}, x' the copy's row: l2_E's comment gives |x - x'| <= rho |x|
+// for every usable row of the copy, so dq = rho * nq rounded up (two roundings of 2^-24 each, under the factor's 2^-21).  The tests are
+// qhalf_kernel's: a scale outside 2^-104 .. 2^76 (an exponent outside -90 .. 90), a row that is not usable or a norm that is no finite number
+// leaves all four NaN -- nothing certain, every pair of the row a candidate.
+__device__ __forceinline__ float4 row_as_query(const float2 rm, float rho) {
+    float4 o = make_float4(NAN, NAN, NAN, NAN);
+    if (rm.y >= 4.930380657631324e-32f && rm.y <= 7.555786372591432e+22f && (rm.x - rm.x == 0.f)) {  // 2^-104, 2^76
+        const float nq = sqrtf(rm.x) * (1.0f + 1e-5f);
+        o = make_float4(rm.y, rm.x, nq, (rho * nq) * 1.0000005f);
+    }
+    return o;
+}
+
 // ---- the leaf-major sweeps' view of a batch: flat rows = the rows of group 0, then group 1, ... (moved out of zh_search.hip) ----
 // lane i of a sweep wave -> (group, stored row, position in the group) of flat row r0 + i.  With the wave-start table the
 // search is confined to the <= 64 groups the wave's 64 rows can span (every group has at least one row), and skipped when
@@ -800,6 +814,42 @@ struct ListSink {
                         atomicOr(over, 1u);
                 }
             }
+        }
+    }
+};
+
+// The record sink (test / debug: zh_debug_walk_pairs, zh_walkdbg.hip; no product path): EVERY pair of the rectangle held positions [p0, p1) x the
+// walked column positions leaves one record at (held position - p0) * ncol + column position -- the positions, either side's row-or-masked word,
+// the interval as the two product sinks would form it (the same call of approx_interval on the same operands; they form it for unmasked pairs
+// only) and the sum it was formed from.  Nothing is stored at or past `cap`.
+template <int KINDA, typename TI>
+struct RecordSink : PoolSink<KINDA, false, TI> {  // the held rows' words and rowMeta by the pool sink's own hold(); its pool stays null
+    using PoolSink<KINDA, false, TI>::lane;
+    using PoolSink<KINDA, false, TI>::I;
+    using PoolSink<KINDA, false, TI>::Kc;
+    using PoolSink<KINDA, false, TI>::rho;
+    using PoolSink<KINDA, false, TI>::id;
+    using PoolSink<KINDA, false, TI>::meta;
+    zh_debug_walk_pair *__restrict__ out;
+    uint64_t cap, p0, p1, ncol;
+    __device__ __forceinline__ RecordSink(uint32_t lane_, TI I_, float Kc_, float rho_, zh_debug_walk_pair *out_, uint64_t cap_, uint64_t p0_, uint64_t p1_,
+                                          uint64_t ncol_)
+        : PoolSink<KINDA, false, TI>{lane_, I_, 0u, Kc_, rho_, nullptr, 0, nullptr}, out(out_), cap(cap_), p0(p0_), p1(p1_), ncol(ncol_) {}
+    __device__ __forceinline__ bool wants(TI) const { return true; }
+    __device__ __forceinline__ void operator()(TI J, const f32x4 t, uint32_t cb, const float4 qb) const {
+        const uint32_t c16 = lane & 15, h = lane >> 4;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint64_t hp = (uint64_t)I * 16 + 4 * h + i, cp = (uint64_t)J * 16 + c16;
+            if (hp < p0 || hp >= p1 || cp >= ncol) continue;
+            const uint64_t slot = (hp - p0) * ncol + cp;
+            if (slot >= cap) continue;
+            const float s = t[i] * meta[i].y;
+            const uint64_t iv = approx_interval<KINDA>(s, meta[i].x, qb, Kc, rho, 0.f);
+            zh_debug_walk_pair r;
+            r.held_pos = (uint32_t)hp; r.col_pos = (uint32_t)cp; r.held_row = id[i]; r.col_row = cb;
+            r.lo = (uint32_t)iv; r.hi = (uint32_t)(iv >> 32); r.raw_s = s;
+            out[slot] = r;
         }
     }
 };

@@ -225,10 +225,7 @@ __global__ __launch_bounds__(256) void fknn_gather_kernel(const u32x4 *__restric
         v = Xh[(p >> 4) * pieces + (w & ~15u) + (p & 15)];
         if (w < 16) {
             rm = rowMeta[p];
-            if (rm.y >= 4.930380657631324e-32f && rm.y <= 7.555786372591432e+22f && (rm.x - rm.x == 0.f)) {  // 2^-104, 2^76
-                const float nq = sqrtf(rm.x) * (1.0f + 1e-5f);
-                o = make_float4(rm.y, rm.x, nq, (rho * nq) * 1.0000005f);
-            }
+            o = row_as_query(rm, rho);
         }
     }
     A[t] = v;

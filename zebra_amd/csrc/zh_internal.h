@@ -400,6 +400,14 @@ hipError_t zh_launch_xjoin_mfma(uint32_t d, int metric, int mode, const void *dX
                                 const void *dXhB, const float4 *dQmB, const uint32_t *dCidB, uint64_t n_rows_b, uint64_t tileA0, uint64_t tileA1, float Kc,
                                 float rhoA, const uint32_t *dTau, uint64_t *dCand, uint64_t cand_cap, unsigned long long *dCandCtr, hipStream_t s);
 
+// ---- test / debug (zh_walkdbg.hip): the held-tile walk's interval of every pair of held positions [p0, p1) of A's copy (p0 a multiple of 64,
+// p1 <= 16 ceil(n_rows_a / 16), at most ZH_DEBUG_WALK_ROWS of them) x all positions of B's; record (p - p0) * 16 ceil(n_rows_b / 16) + column position,
+// stored where that is below `cap`.  dCidA / dCidB, dQmB: zh_launch_join_prep of either side
+#define ZH_DEBUG_WALK_ROWS 1024u
+hipError_t zh_launch_walk_debug(uint32_t d, int metric, int mode, const void *dXhA, const float2 *dRowMetaA, const uint32_t *dCidA, uint64_t n_rows_a,
+                                const void *dXhB, const float4 *dQmB, const uint32_t *dCidB, uint64_t n_rows_b, uint64_t p0, uint64_t p1, float Kc, float rhoA,
+                                zh_debug_walk_pair *dOut, uint64_t cap, hipStream_t s);
+
 // ---- the exact k-NN graph (zh_knn.hip): each live row's k nearest other live rows, panel by panel
 #define ZH_KNN_PANEL_ROWS 1024u  // live rows one panel holds (= the exact search's internal batch: every reused launcher sees a batch it already serves)
 #define ZH_KNN_CHUNK 64u         // column tiles one block of the matrix-core scan walks at most

@@ -82,10 +82,9 @@ hipError_t zh_launch_pair_collect(const uint64_t *dKeys, uint64_t ld, const uint
 }
 
 // ---- path 2: what the scan reads per POSITION of the copy (ceil(n / 16) * 16 of them).  cid = the row's number, or UINT32_MAX for a removed row
-// and for the tail of the last tile.  qm = approx_interval's view of the row as a query: {1 / sigma, f32 |x|^2, nq >= |x|, dq >= |x - x'|}, x' the
-// copy's row: l2_E's comment gives |x - x'| <= rho |x| for every usable row of the copy, so dq = rho * nq rounded up.  The tests are qhalf_kernel's:
-// a scale outside 2^-104 .. 2^76 (an exponent outside -90 .. 90), a row that is not usable or a norm that is no finite number leaves all four NaN --
-// nothing certain, every pair of the row a candidate. ----
+// and for the tail of the last tile.  qm = approx_interval's view of the row as a query (row_as_query, zh_device.h): {1 / sigma, f32 |x|^2,
+// nq >= |x|, dq >= |x - x'|}, x' the copy's row; all four NaN -- nothing certain, every pair of the row a candidate -- for a row that is not usable,
+// a scale outside 2^-104 .. 2^76 or a norm that is no finite number. ----
 __global__ __launch_bounds__(256) void join_prep_kernel(const float2 *__restrict__ rowMeta, const uint32_t *__restrict__ perm, uint64_t perm_rows,
                                                         const uint32_t *__restrict__ liveBits, uint64_t n_rows, uint64_t n_pos, float rho,
                                                         float4 *__restrict__ qm, uint32_t *__restrict__ cid) {
@@ -96,11 +95,7 @@ __global__ __launch_bounds__(256) void join_prep_kernel(const float2 *__restrict
     if (p < n_rows) {
         const uint32_t r = perm && p < perm_rows ? perm[p] : (uint32_t)p;
         if ((liveBits[r >> 5] >> (r & 31)) & 1u) id = r;
-        const float2 rm = rowMeta[p];
-        if (rm.y >= 4.930380657631324e-32f && rm.y <= 7.555786372591432e+22f && (rm.x - rm.x == 0.f)) {  // 2^-104, 2^76
-            const float nq = sqrtf(rm.x) * (1.0f + 1e-5f);
-            o = make_float4(rm.y, rm.x, nq, (rho * nq) * 1.0000005f);  // (two roundings of 2^-24 each, under the factor's 2^-21)
-        }
+        o = row_as_query(rowMeta[p], rho);
     }
     qm[p] = o;
     cid[p] = id;

@@ -719,6 +719,22 @@ class LSHIndex:
             check(lib().zh_debug_scan_pairs(self._h, h, C.byref(info), pairs.ctypes.data_as(C.c_void_p), pairs.shape[0], qmeta.ctypes.data_as(C.c_void_p)))
         return info.as_dict(), pairs, qmeta
 
+    def debug_walk_pairs(self, metric, first_pos, n_pos, right=None):
+        """tests: the interval of EVERY pair of the rectangle held positions [first_pos, first_pos + n_pos) of this index's fp16 copy x every
+        position of `right`'s (None: this index itself -- the self-join's and the graphs' view; another index: the cross join's), as the joins'
+        and the graphs' matrix-core scans form it -> (info dict, structured array of zh_debug_walk_pair, record (held_pos - first_pos) *
+        col_positions + col_pos); zh_debug_walk_pairs"""
+        info = _ffi.DebugWalkInfo()
+        rh = self._h if right is None else right._h
+        check(lib().zh_debug_walk_pairs(self._h, rh, metric.metric, metric.mode, int(first_pos), int(n_pos), C.byref(info), None, 0))
+        dt = np.dtype([("held_pos", "<u4"), ("col_pos", "<u4"), ("held_row", "<u4"), ("col_row", "<u4"), ("lo", "<u4"), ("hi", "<u4"), ("raw_s", "<f4")])
+        assert dt.itemsize == C.sizeof(_ffi.DebugWalkPair)
+        pairs = np.zeros(int(info.pairs), dt)
+        if info.pairs:
+            check(lib().zh_debug_walk_pairs(self._h, rh, metric.metric, metric.mode, int(first_pos), int(n_pos), C.byref(info),
+                                            pairs.ctypes.data_as(C.c_void_p), pairs.shape[0]))
+        return info.as_dict(), pairs
+
     def read_rows(self, first, n):
         """KeyValue::embedding (lsh.rs:107-119) for a run of rows."""
         out = np.empty((n, self.dim), np.float32)

@@ -386,6 +386,44 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_knn_graph_forest_info(h_.get(), &info));
         return info;
     }
+    // One refinement round over a graph of ALL stored rows (zh_knn_graph_refine): in_ids [stored rows][in_k] in the outputs' id space, in_counts
+    // [stored rows] -- what knn_graph / knn_graph_forest give for the whole table, flattened.  Element i = the first k by (key, id) of stored row
+    // first_row + i's neighbours and their neighbours, the row itself excluded; entries that are out of range, removed or repeated are ignored.
+    // k <= ZH_MAX_TOPK - 1, in_k <= ZH_REFINE_MAX_IN_K.  No forest needed.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> knn_graph_refine(const std::vector<Id> &in_ids, const std::vector<std::uint32_t> &in_counts,
+                                                                           std::size_t in_k, std::size_t k, const Met &metric, std::uint64_t first_row,
+                                                                           std::uint64_t n) const {
+        const std::uint64_t stored = zh_index_stored_rows(h_.get());
+        if (in_counts.size() != stored || in_ids.size() != stored * in_k) throw std::invalid_argument("knn_graph_refine: the graph must cover every stored row");
+        std::vector<Id> ids(n * k + 1);
+        std::vector<DistanceUnit> keys(n * k + 1);
+        std::vector<std::uint32_t> counts(n + 1);
+        check(zh_knn_graph_refine(h_.get(), in_ids.data(), in_counts.data(), in_k, first_row, n, k, Met::metric, metric.mode(), ids.data(), keys.data(),
+                                  counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(n);
+        for (std::uint64_t i = 0; i < n; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * k + j], keys[i * k + j]);
+        return out;
+    }
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> knn_graph_refine(const std::vector<Id> &in_ids, const std::vector<std::uint32_t> &in_counts,
+                                                                           std::size_t in_k, std::size_t k, const Met &metric) const {
+        return knn_graph_refine(in_ids, in_counts, in_k, k, metric, 0, zh_index_stored_rows(h_.get()));
+    }
+    // the same with the graph and the outputs in device memory, enqueued on `stream` (nullptr: the index's own), complete on return
+    template <class Met>
+    void knn_graph_refine_device(const Id *d_in_ids, const std::uint32_t *d_in_counts, std::size_t in_k, std::uint64_t first_row, std::uint64_t n,
+                                 std::size_t k, const Met &metric, Id *d_out_ids, DistanceUnit *d_out_keys, std::uint32_t *d_out_counts,
+                                 void *stream = nullptr) const {
+        check(zh_knn_graph_refine_device(h_.get(), d_in_ids, d_in_counts, in_k, first_row, n, k, Met::metric, metric.mode(), d_out_ids, d_out_keys,
+                                         d_out_counts, stream));
+    }
+    zh_knn_refine_info knn_refine_info() const {
+        zh_knn_refine_info info{};
+        check(zh_knn_graph_refine_info(h_.get(), &info));
+        return info;
+    }
     // the forest self-join (zh_self_join_forest): self_join's pairs among the rows that share a leaf in at least one tree, each pair once; exact
     // keys on an approximate candidate set.  One call that counts, one that fetches.  Needs a built forest.
     template <class Met>

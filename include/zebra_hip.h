@@ -31,6 +31,8 @@
  *   zh_cross_join[_device]               (new) every pair (live row of one index, live row of another) whose key is at or below one threshold key
  *   zh_knn_graph[_device]                (new) every live row's exact k nearest OTHER live rows, slab by slab
  *   zh_knn_graph_forest[_device]         (new) every row's k nearest rows among its leaf-mates in the forest: exact keys, approximate candidates
+ *   zh_knn_graph_refine[_device]         (new) one NN-descent join round over a caller's graph: every row's neighbours and their neighbours, ranked
+ *                                        by the exact key
  *   zh_self_join_forest[_device]         (new) every pair of leaf-mates whose key is at or below one threshold key, each pair once: exact keys,
  *                                        approximate candidates
  *   zh_search_range_forest_batch[_device] (new) every member of the leaves the walk visits for a query whose key is at or below the query's
@@ -637,6 +639,56 @@ typedef struct zh_knn_forest_info {  /* the most recent zh_knn_graph_forest* cal
     uint64_t tiles;       /* path 2: 16 x 16 tile products issued, from the launch geometry (held tiles in use x the leaf's column tiles); 0 on path 1 */
 } zh_knn_forest_info;
 ZH_API int zh_knn_graph_forest_info(const zh_index *idx, zh_knn_forest_info *out);
+
+/* ---- k-NN graph refinement (new): rank each row's neighbours' neighbours -------------------------------------------------------------------
+ * One join round of NN-descent over a graph the caller already has: the forest graph's recall is limited by what the leaves hold, and the
+ * neighbours of a row's neighbours are where the missing rows usually are.  The INPUT is a graph over ALL stored rows of the index: in_ids
+ * [stored rows][in_k] in the id space of the outputs (id_base + row), in_counts [stored rows] -- what zh_knn_graph or zh_knn_graph_forest
+ * returns for the whole table with k = in_k.  Keys are not taken: every returned key is computed here.
+ *   N'(x) = the SET of rows named by the first min(in_counts[x], in_k) entries of line x that are live stored rows of this index.  An entry
+ *           outside [id_base, id_base + stored rows) (UINT64_MAX included) is ignored, not an error; an entry that names a removed row is
+ *           ignored: no candidate, not expanded; duplicates inside a line count once; order inside a line means nothing.  A graph made before
+ *           a later zh_index_remove therefore stays valid; after zh_index_compact, re-keying it with the id map is the caller's job.
+ *   C(a)  = ( N'(a)  union  N'(u) for every u in N'(a) ) minus a.  Only the row with the same row number is excluded; bit-identical
+ *           duplicates are ordinary neighbours, as for zh_knn_graph.
+ * The outputs have zh_knn_graph's layout and slab meaning: line i belongs to stored row a = first_row + i and holds the first k of C(a) by
+ * (key, id), the key being zh_distance_batch's for stored row b against a query equal to the f32 values of row a; out_counts[i] =
+ * min(k, |C(a)|), tails UINT64_MAX in both arrays, a removed a has count 0.  Ids, keys and counts are bit for bit what this definition gives,
+ * for all 13 metric / mode / power combinations and every dimension, whatever the order or repetition of the input entries, the slabs or the
+ * run.  No forest is needed: an index filled by zh_index_append and never built is served.
+ * What follows from the definition:
+ *   - N'(a) is a subset of C(a), so position by position the answer's (key, id) is never above that of the input line re-keyed;
+ *   - refining the exact graph with k <= in_k returns the exact graph's first k;
+ *   - on a table of at most in_k + 1 live rows with complete lists the answer is zh_knn_graph's.
+ * Limits: k <= ZH_MAX_TOPK - 1 and in_k <= ZH_REFINE_MAX_IN_K (a line then gathers at most 64 + 64^2 = 4160 entries), else ZH_ELIMIT; in_k = 0
+ * with n > 0 is ZH_EINVAL.  Judged before any device is touched, in this order of kinds: a null index (even for n = 0), null input or output
+ * pointers of a request with n > 0, an unknown metric, the two limits, in_k = 0.  Then: first_row + n > stored rows is ZH_EINVAL, n = 0 is
+ * ZH_OK, k = 0 zeroes the counts and touches nothing else.  Locking as zh_knn_graph_device; zh_stats_t, every sibling info struct and the
+ * cached live-row views are left alone: zh_knn_graph_refine_info describes the most recent call.
+ * The input is turned once per call into a table of u32 row numbers with everything invalid, removed or repeated masked (the host entry
+ * streams in_ids through two pinned buffers of at most 64 MiB, ZH_REFINE_CHUNK_BYTES in the environment lowers that for tests), then a block
+ * per live line gathers, sorts and de-duplicates its candidates in LDS, keys them with the canonical sums and sorts them by (key, id).
+ * Device scratch is per call and released before return: 4 in_k + 4 bytes per stored row (the table and the counts), one chunk of the u64
+ * input for the host entry, per sub-slab of 65536 lines 4 dim + 4 bytes per live line, and for the host call 16 k + 4 bytes per line of a
+ * staged slab of at most max(65536, 2^25 / k) lines.  DESIGN.md s21. */
+#define ZH_REFINE_MAX_IN_K 64u
+ZH_API int zh_knn_graph_refine(zh_index *idx, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, uint64_t first_row, uint64_t n, size_t k,
+                               int metric, int cosine_mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts);
+/* The same with the graph and every output in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_knn_graph_refine_device(zh_index *idx, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, uint64_t first_row, uint64_t n,
+                                      size_t k, int metric, int cosine_mode, uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts,
+                                      void *stream);
+typedef struct zh_knn_refine_info {  /* the most recent zh_knn_graph_refine* call on this index */
+    uint64_t rows_live;   /* live rows of the index */
+    uint64_t lines;       /* live rows of the slab */
+    uint32_t in_k;
+    uint32_t k;
+    uint64_t listed;      /* entries gathered before de-duplication: the sum over the lines a of |N'(a)| + the sum over u in N'(a) of |N'(u)| */
+    uint64_t keyed;       /* the sum of |C(a)|: the pairs that got a key */
+    uint64_t updates;     /* output entries whose row is not in the line's own N'(a): NN-descent's convergence signal, 0 at a fixed point */
+    uint64_t launches;    /* launches of the line kernel: one per sub-slab of 65536 stored rows that holds a live row */
+} zh_knn_refine_info;
+ZH_API int zh_knn_graph_refine_info(const zh_index *idx, zh_knn_refine_info *out);
 
 /* ---- forest self-join (new): all near-duplicate pairs AMONG LEAF-MATES ---------------------------------------------------------------------
  * zh_self_join multiplies every tile of the table by every tile at or above it; this call multiplies a leaf only by itself.  Arguments, key,

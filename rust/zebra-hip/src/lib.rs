@@ -175,6 +175,19 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_knn_refine_info {
+        pub rows_live: u64,
+        pub lines: u64,
+        pub in_k: u32,
+        pub k: u32,
+        pub listed: u64,
+        pub keyed: u64,
+        pub updates: u64,
+        pub launches: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_join_forest_info {
         pub rows_live: u64,
         pub trees: u32,
@@ -325,6 +338,12 @@ pub mod ffi {
         pub fn zh_knn_graph_forest_device(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int,
                                           d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_knn_graph_forest_info(idx: *const zh_index, out: *mut zh_knn_forest_info) -> c_int;
+        pub fn zh_knn_graph_refine(idx: *mut zh_index, in_ids: *const u64, in_counts: *const u32, in_k: usize, first_row: u64, n: u64, k: usize,
+                                   metric: c_int, cosine_mode: c_int, out_ids: *mut u64, out_keys: *mut u64, out_counts: *mut u32) -> c_int;
+        pub fn zh_knn_graph_refine_device(idx: *mut zh_index, d_in_ids: *const u64, d_in_counts: *const u32, in_k: usize, first_row: u64, n: u64,
+                                          k: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64, d_out_keys: *mut u64,
+                                          d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_knn_graph_refine_info(idx: *const zh_index, out: *mut zh_knn_refine_info) -> c_int;
         pub fn zh_self_join_forest(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, out_a: *mut u64,
                                    out_b: *mut u64, out_keys: *mut u64, out_total: *mut u64) -> c_int;
         pub fn zh_self_join_forest_device(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, d_out_a: *mut u64,
@@ -824,6 +843,51 @@ impl<const N: usize> LSHIndex<N> {
             first += n;
         }
         Ok(out)
+    }
+
+    /// (new) the refined forest k-NN graph (zh_knn_graph_forest, then zh_knn_graph_refine): the forest graph of the whole table in row numbers,
+    /// then up to `rounds` join rounds -- each vector's neighbours and their neighbours, ranked by the exact key -- each round's output the next
+    /// round's input, stopping early once a round changes nothing (`updates` == 0).  knn_graph's shape.
+    pub fn knn_graph_refined<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        k: usize,
+        rounds: usize,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<(Uuid, Vec<(Uuid, DistanceUnit)>)>> {
+        let t = self.ids.read().unwrap();
+        let stored = t.of_row.len();
+        let (mut ids, mut keys, mut counts) = (vec![0u64; stored * k + 1], vec![0u64; stored * k + 1], vec![0u32; stored + 1]);
+        if stored > 0 {
+            check(unsafe {
+                ffi::zh_knn_graph_forest(self.hip.0, 0, stored as u64, k, Met::METRIC, metric.param(), ids.as_mut_ptr(), keys.as_mut_ptr(),
+                                         counts.as_mut_ptr())
+            })?;
+        }
+        let (mut rids, mut rcounts) = (vec![0u64; stored * k + 1], vec![0u32; stored + 1]);
+        for _ in 0..rounds {
+            if stored == 0 || k == 0 {
+                break;
+            }
+            check(unsafe {
+                ffi::zh_knn_graph_refine(self.hip.0, ids.as_ptr(), counts.as_ptr(), k, 0, stored as u64, k, Met::METRIC, metric.param(),
+                                         rids.as_mut_ptr(), keys.as_mut_ptr(), rcounts.as_mut_ptr())
+            })?;
+            std::mem::swap(&mut ids, &mut rids);
+            std::mem::swap(&mut counts, &mut rcounts);
+            if self.knn_refine_info()?.updates == 0 {
+                break;
+            }
+        }
+        Ok((0..stored)
+            .map(|i| (t.of_row[i], (0..counts[i] as usize).map(|j| (t.of_row[ids[i * k + j] as usize], keys[i * k + j])).collect()))
+            .collect())
+    }
+
+    /// what the most recent graph refinement call did (zh_knn_graph_refine_info)
+    pub fn knn_refine_info(&self) -> anyhow::Result<ffi::zh_knn_refine_info> {
+        let mut info = ffi::zh_knn_refine_info::default();
+        check(unsafe { ffi::zh_knn_graph_refine_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// (new) the forest self-join (zh_self_join_forest): self_join's pairs among the vectors that share a leaf in at least one tree, each pair

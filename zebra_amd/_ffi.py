@@ -149,6 +149,14 @@ class KnnForestInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KnnRefineInfo(C.Structure):
+    _fields_ = [("rows_live", C.c_uint64), ("lines", C.c_uint64), ("in_k", C.c_uint32), ("k", C.c_uint32), ("listed", C.c_uint64),
+                ("keyed", C.c_uint64), ("updates", C.c_uint64), ("launches", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class JoinForestInfo(C.Structure):
     _fields_ = [("rows_live", C.c_uint64), ("trees", C.c_uint32), ("path", C.c_uint32), ("leaf_pairs", C.c_uint64), ("pairs", C.c_uint64),
                 ("candidates", C.c_uint64), ("launches", C.c_uint64), ("tiles", C.c_uint64), ("redone", C.c_uint32)]
@@ -244,6 +252,9 @@ SYMBOLS = [
     ("zh_knn_graph_forest", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_knn_graph_forest_device", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_knn_graph_forest_info", _i, [_vp, _vp]),
+    ("zh_knn_graph_refine", _i, [_vp, _vp, _vp, _sz, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
+    ("zh_knn_graph_refine_device", _i, [_vp, _vp, _vp, _sz, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    ("zh_knn_graph_refine_info", _i, [_vp, _vp]),
     ("zh_self_join_forest", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_device", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_info", _i, [_vp, _vp]),

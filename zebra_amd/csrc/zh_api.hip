@@ -288,6 +288,10 @@ struct zh_index {
     DevBuf fk_ntree, fk_rl, fk_flag, fk_excl, fk_tmp, fk_rows, fk_ctr, fk_lens, fk_takes, fk_rbase, fk_cbase, fk_groups, fk_groff, fk_segs, fk_colsrc, fk_crow,
         fk_hrow, fk_held, fk_CA, fk_cmeta, fk_cqm, fk_HA, fk_hmeta, fk_qrow, fk_maxk, fk_redo, fk_pos;
     zh_knn_forest_info fk_info{};  // (stats_mu)
+    // the graph refinement's per-call scratch beside the graph's staging and the exact search's query rows (all released before the call returns):
+    // the table of row numbers, the lines' counts, one chunk of the host call's u64 input, {listed, keyed, updates}
+    DevBuf rf_tab, rf_cnt, rf_stage, rf_ctr;
+    zh_knn_refine_info rf_info{};  // (stats_mu)
     // the forest self-join's per-call scratch beside the self-join's and the forest graph's (all released before the call returns): leaf_of, a path-1
     // panel's pieces and per-line {leaf, key offset}, path 2's segments and candidate pool
     DevBuf fj_leafof, fj_pieces, fj_linel, fj_linek, fj_segs, fj_cand;
@@ -3468,7 +3472,7 @@ static int score_param(int metric, int mode) { return (metric == ZH_COSINE || me
 // index holds only the live-row views (ex_live and ex_bits survive every call; zh_index_destroy frees them).  Every family scans with the exact
 // search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's, the forest range search with
 // the range search's and the forest join's, the cross-join (all on its LEFT index) with the join's and its own views.
-enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256 };  // one bit per list
+enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512 };  // one bit per list
 enum : unsigned {
     SCRATCH_EXACT = SCR_EX,
     SCRATCH_FILTER = SCR_FL | SCRATCH_EXACT,
@@ -3476,6 +3480,7 @@ enum : unsigned {
     SCRATCH_JOIN = SCR_JN | SCRATCH_EXACT,
     SCRATCH_KNN = SCR_KN | SCRATCH_EXACT,
     SCRATCH_FKNN = SCR_FK | SCRATCH_KNN,
+    SCRATCH_REFINE = SCR_RF | SCRATCH_KNN,
     SCRATCH_FJOIN = SCR_FJ | SCRATCH_JOIN | SCRATCH_FKNN,
     SCRATCH_FRANGE = SCR_FR | SCRATCH_RANGE | SCRATCH_FJOIN,
     SCRATCH_XJOIN = SCR_XJ | SCRATCH_JOIN,  // (on the left index)
@@ -3499,6 +3504,7 @@ static void release_scratch(zh_index *ix, unsigned families) {
     drop(SCR_FK, {&ix->fk_ntree, &ix->fk_rl, &ix->fk_flag, &ix->fk_excl, &ix->fk_tmp, &ix->fk_rows, &ix->fk_ctr, &ix->fk_lens, &ix->fk_takes, &ix->fk_rbase,
                   &ix->fk_cbase, &ix->fk_groups, &ix->fk_groff, &ix->fk_segs, &ix->fk_colsrc, &ix->fk_crow, &ix->fk_hrow, &ix->fk_held, &ix->fk_CA,
                   &ix->fk_cmeta, &ix->fk_cqm, &ix->fk_HA, &ix->fk_hmeta, &ix->fk_qrow, &ix->fk_maxk, &ix->fk_redo, &ix->fk_pos});
+    drop(SCR_RF, {&ix->rf_tab, &ix->rf_cnt, &ix->rf_stage, &ix->rf_ctr});
     drop(SCR_FJ, {&ix->fj_leafof, &ix->fj_pieces, &ix->fj_linel, &ix->fj_linek, &ix->fj_segs, &ix->fj_cand});
     drop(SCR_FR, {&ix->fr_counts, &ix->fr_inline, &ix->fr_rowbase, &ix->fr_candbase, &ix->fr_visitbase, &ix->fr_totals, &ix->fr_leafcount, &ix->fr_leaffill,
                   &ix->fr_groupbase, &ix->fr_grouprowbase, &ix->fr_loghead, &ix->fr_logctl, &ix->fr_logpool, &ix->fr_visits, &ix->fr_groups, &ix->fr_groupoff,
@@ -5257,6 +5263,157 @@ extern "C" int zh_knn_graph_forest(zh_index *ix, uint64_t first_row, uint64_t n,
 
 extern "C" int zh_knn_graph_forest_info(const zh_index *ix, zh_knn_forest_info *out) {
     return get_info(ix, &zh_index::fk_info, out, "zh_knn_graph_forest_info");
+}
+
+// ------------------------------------------------------------------------------------------------
+// k-NN graph refinement (zh_refine.hip): each live row's neighbours and their neighbours, ranked by the canonical key.  DESIGN.md s21
+// ------------------------------------------------------------------------------------------------
+// bytes of the u64 input one pinned buffer holds (the host entry): 64 MiB, ZH_REFINE_CHUNK_BYTES in the environment lowers it (read per call; tests)
+static uint64_t refine_chunk_bytes() {
+    uint64_t chunk = 64ull << 20;
+    if (const char *e = getenv("ZH_REFINE_CHUNK_BYTES")) {
+        const long long v = atoll(e);
+        if (v >= 8) chunk = std::min<uint64_t>((uint64_t)v, chunk);
+    }
+    return chunk;
+}
+
+struct RefinePins {  // two pinned buffers and an event each: released whatever way the call ends, after the stream has drained
+    void *pin[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipStream_t s = nullptr;
+    ~RefinePins() {
+        if (pin[0] || pin[1]) hipStreamSynchronize(s);
+        for (int i = 0; i < 2; i++) {
+            if (pin[i]) hipHostFree(pin[i]);
+            if (ev[i]) hipEventDestroy(ev[i]);
+        }
+    }
+};
+
+// The caller's graph -> rf_tab, the table of row numbers (zh_launch_refine_rows), once per call.  host: in_ids / in_counts are HOST arrays -- the ids
+// go chunk by chunk (whole lines) through two pinned buffers and one device chunk, never as a whole u64 copy on the device.
+static int refine_table(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, bool host, hipStream_t s) {
+    const uint64_t N = ix->n_rows, id_base = ix->opt.id_base;
+    int rc;
+    if ((rc = ix->rf_tab.ensure(std::max<size_t>((size_t)N * in_k * 4, 4))) || (rc = ix->rf_ctr.ensure(24))) return rc;
+    HIPCHK(hipMemsetAsync(ix->rf_ctr.p, 0, 24, s));
+    if (!N) return ZH_OK;
+    const uint32_t *dBits = ix->ex_bits.as<uint32_t>();
+    if (!host) {
+        HIPCHK(zh_launch_refine_rows(in_ids, in_counts, dBits, id_base, N, in_k, 0, N, ix->rf_tab.as<uint32_t>(), s));
+        return ZH_OK;
+    }
+    const uint64_t line_bytes = (uint64_t)in_k * 8, chunk_lines = std::min<uint64_t>(N, std::max<uint64_t>(1, refine_chunk_bytes() / line_bytes));
+    if ((rc = ix->rf_cnt.ensure((size_t)N * 4)) || (rc = ix->rf_stage.ensure(chunk_lines * line_bytes))) return rc;
+    HIPCHK(hipMemcpyAsync(ix->rf_cnt.p, in_counts, (size_t)N * 4, hipMemcpyHostToDevice, s));
+    RefinePins pp;
+    pp.s = s;
+    for (int i = 0; i < 2 && (i == 0 || chunk_lines < N); i++) {
+        hipError_t e = hipHostMalloc(&pp.pin[i], chunk_lines * line_bytes, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(ZH_ENOMEM, "hipHostMalloc(%llu): %s", (unsigned long long)(chunk_lines * line_bytes), hipGetErrorString(e));
+        HIPCHK(hipEventCreateWithFlags(&pp.ev[i], hipEventDisableTiming));
+    }
+    uint64_t i = 0;
+    for (uint64_t l0 = 0; l0 < N; l0 += chunk_lines, i++) {
+        const uint64_t nl = std::min(chunk_lines, N - l0);
+        const int b = (int)(i & 1);
+        if (i >= 2) HIPCHK(hipEventSynchronize(pp.ev[b]));  // the copy out of this buffer two chunks ago is done
+        memcpy(pp.pin[b], in_ids + l0 * in_k, nl * line_bytes);
+        HIPCHK(hipMemcpyAsync(ix->rf_stage.p, pp.pin[b], nl * line_bytes, hipMemcpyHostToDevice, s));  // (behind the kernel that read the chunk before)
+        HIPCHK(hipEventRecord(pp.ev[b], s));
+        HIPCHK(zh_launch_refine_rows(ix->rf_stage.as<uint64_t>(), ix->rf_cnt.as<uint32_t>(), dBits, id_base, N, in_k, l0, nl, ix->rf_tab.as<uint32_t>(), s));
+    }
+    return ZH_OK;
+}
+
+// One slab on device outputs (under mu, exclusive; exact_live_rows and refine_table have run; k > 0, n > 0): every line filled as "no neighbours",
+// then sub-slab by sub-slab the live lines (a stretch of ex_live), their f32 rows as the query side, their norms, and a block per line.
+static int refine_slab(zh_index *ix, LiveCursor *live, uint32_t in_k, uint64_t first_row, uint64_t n, uint32_t k, int metric, int mode, uint64_t *dIds,
+                       uint64_t *dKeys, uint32_t *dCounts, hipStream_t s, zh_knn_refine_info *inf) {
+    const uint32_t d = ix->opt.dim;
+    int rc;
+    HIPCHK(zh_launch_exact_empty((uint32_t)n, k, dIds, dKeys, dCounts, s));
+    for (uint64_t r0 = first_row; r0 < first_row + n; r0 += ZH_REFINE_SLAB) {
+        const uint64_t m = std::min<uint64_t>(ZH_REFINE_SLAB, first_row + n - r0);
+        const uint64_t lo = live_before(ix, r0, live), hi = live_before(ix, r0 + m, live);
+        const uint32_t B = (uint32_t)(hi - lo);
+        if (!B) continue;
+        const uint32_t *dRows = ix->ex_live.as<uint32_t>() + lo;
+        if ((rc = ix->ex_Q.ensure((size_t)B * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)B * 4))) return rc;
+        HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dRows, B, ix->ex_Q.as<float>(), s));
+        HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), B, d, ix->ex_QQ.as<float>(), s));
+        HIPCHK(zh_launch_refine_lines(ix->X.as<float>(), d, ix->rf_tab.as<uint32_t>(), in_k, dRows, B, ix->ex_Q.as<float>(), ix->ex_QQ.as<float>(), metric,
+                                      score_param(metric, mode), ix->opt.id_base, first_row, k, dIds, dKeys, dCounts, ix->rf_ctr.as<unsigned long long>(), s));
+        inf->lines += B;
+        inf->launches++;
+    }
+    return ZH_OK;
+}
+
+// judged before any device is touched, in this order of kinds: null index (even for n = 0), null inputs or outputs of a non-empty request, the
+// metric, the two limits, in_k = 0
+static int refine_args(zh_index *ix, const void *in_ids, const void *in_counts, size_t in_k, uint64_t n, size_t k, int metric, int mode, const void *ids,
+                       const void *keys, const void *counts, const char *who) {
+    if (!ix || (n && (!in_ids || !in_counts || !counts || (k && (!ids || !keys))))) return fail(ZH_EINVAL, "%s: null argument", who);
+    const int rc = check_metric(metric, mode);
+    if (rc) return rc;
+    if (k > ZH_MAX_TOPK - 1) return fail(ZH_ELIMIT, "%s: k %zu > ZH_MAX_TOPK - 1 (%u)", who, k, ZH_MAX_TOPK - 1);
+    if (in_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: in_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, ZH_REFINE_MAX_IN_K);
+    if (n && !in_k) return fail(ZH_EINVAL, "%s: in_k is 0", who);
+    return ZH_OK;
+}
+
+// both entry points once the arguments have been judged (n > 0)
+static int refine_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, uint64_t first_row, uint64_t n, size_t k, int metric,
+                       int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, bool host, void *stream, const char *who) {
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, who))) return rc;
+    ScratchGuard guard{ix, SCRATCH_REFINE};
+    const hipStream_t s = call_stream(ix, stream);
+    zh_knn_refine_info inf{};
+    unsigned long long ctr[3] = {0, 0, 0};
+    if (k == 0) {
+        if ((rc = knn_no_neighbours(n, out_counts, host, s))) return rc;
+    } else {
+        if ((rc = refine_table(ix, in_ids, in_counts, in_k, host, s))) return rc;
+        LiveCursor live;
+        const uint64_t host_slab = std::max<uint64_t>(ZH_REFINE_SLAB, (uint64_t(1) << 25) / k / ZH_REFINE_SLAB * ZH_REFINE_SLAB);
+        rc = knn_slabs(ix, first_row, n, k, out_ids, out_keys, out_counts, host_slab, host, s,
+                       [&](uint64_t r0, uint64_t m, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
+                           return refine_slab(ix, &live, in_k, r0, m, (uint32_t)k, metric, mode, dIds, dKeys, dCounts, s, &inf);
+                       });
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(ctr, ix->rf_ctr.p, 24, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    inf.rows_live = ix->ex_n_live;
+    inf.in_k = in_k;
+    inf.k = (uint32_t)k;
+    inf.listed = ctr[0]; inf.keyed = ctr[1]; inf.updates = ctr[2];
+    std::lock_guard<std::mutex> ls(ix->stats_mu);
+    ix->rf_info = inf;
+    return ZH_OK;
+}
+
+extern "C" int zh_knn_graph_refine_device(zh_index *ix, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, uint64_t first_row, uint64_t n,
+                                          size_t k, int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
+    int rc = refine_args(ix, d_in_ids, d_in_counts, in_k, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_refine_device");
+    if (rc || n == 0) return rc;
+    return refine_call(ix, d_in_ids, d_in_counts, (uint32_t)in_k, first_row, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, false, stream,
+                       "zh_knn_graph_refine_device");
+}
+
+extern "C" int zh_knn_graph_refine(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, uint64_t first_row, uint64_t n, size_t k,
+                                   int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts) {
+    int rc = refine_args(ix, in_ids, in_counts, in_k, n, k, metric, mode, out_ids, out_keys, out_counts, "zh_knn_graph_refine");
+    if (rc || n == 0) return rc;
+    return refine_call(ix, in_ids, in_counts, (uint32_t)in_k, first_row, n, k, metric, mode, out_ids, out_keys, out_counts, true, nullptr, "zh_knn_graph_refine");
+}
+
+extern "C" int zh_knn_graph_refine_info(const zh_index *ix, zh_knn_refine_info *out) {
+    return get_info(ix, &zh_index::rf_info, out, "zh_knn_graph_refine_info");
 }
 
 // ------------------------------------------------------------------------------------------------

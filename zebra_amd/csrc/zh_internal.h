@@ -484,6 +484,20 @@ hipError_t zh_launch_fknn_store(const uint32_t *dHRow, uint32_t B, uint64_t firs
 // dRedo[(row - first_row) / ZH_FKNN_SLAB] = 1 for every held row of a batch whose lists ran over
 hipError_t zh_launch_fknn_mark(const uint32_t *dHRow, uint32_t B, uint64_t first_row, uint32_t *dRedo, hipStream_t s);
 
+// ---- k-NN graph refinement (zh_refine.hip): each live row's neighbours and their neighbours, ranked by the canonical key
+#define ZH_REFINE_SLAB 65536u      // stored rows of a sub-slab: one launch of the line kernel
+#define ZH_REFINE_CAP_SMALL 2048u  // candidate slots of the small instantiation of the line kernel (in_k + in_k^2 <= 2048: in_k <= 44) ...
+#define ZH_REFINE_CAP_LARGE 8192u  // ... and of the large one (in_k <= ZH_REFINE_MAX_IN_K)
+// lines [l0, l0 + nl) of the input graph (dIn holds THEIR in_k entries each, from its start) into the table dTab [stored rows][in_k] of row numbers:
+// UINT32_MAX for an entry past the line's count, outside [id_base, id_base + n_rows), not live by dBits, or equal to an earlier entry of its line
+hipError_t zh_launch_refine_rows(const uint64_t *dIn, const uint32_t *dCounts, const uint32_t *dBits, uint64_t id_base, uint64_t n_rows, uint32_t in_k,
+                                 uint64_t l0, uint64_t nl, uint32_t *dTab, hipStream_t s);
+// a block per line b (row dRows[b], its f32 values dQ[b], its squared norm dQQ[b]): the first k of C(row) by (key, id) to line row - first_row of the
+// outputs; dCtr[0] += listed, dCtr[1] += keyed, dCtr[2] += updates
+hipError_t zh_launch_refine_lines(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, const uint32_t *dRows, uint32_t B, const float *dQ,
+                                  const float *dQQ, int metric, int param, uint64_t id_base, uint64_t first_row, uint32_t k, uint64_t *dOutIds,
+                                  uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s);
+
 // ---- the forest self-join (zh_fjoin.hip): every pair of leaf-mates whose key is <= one threshold key, each pair once (the first tree that puts
 // the two rows together owns it).  Hit pool, counter and order as the exact self-join's
 #define ZH_FJOIN_PANEL_LINES 16384u  // path 1: lines of one panel at most

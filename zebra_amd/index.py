@@ -653,6 +653,47 @@ class LSHIndex:
         survivors, redone, launches, tiles"""
         return self._info(_ffi.KnnForestInfo, lib().zh_knn_graph_forest_info)
 
+    def knn_graph_refine(self, graph, k, metric, first_row=0, n=None, rounds=1):
+        """one join round of NN-descent over a graph of ALL stored rows: `graph` is (ids [stored rows, in_k] u64, counts [stored rows] u32) or the
+        3-tuple knn_graph / knn_graph_forest return (its keys are not read: every returned key is computed here).  Line i of the answer holds the
+        first k by (key, id) of stored row first_row + i's neighbours and their neighbours, the row itself excluded; entries that are out of range,
+        removed or repeated in a line are ignored.  rounds > 1 (the whole table only) feeds each round's output to the next and stops early
+        once a round changes nothing (knn_refine_info()['updates'] == 0).  -> (ids [n,k] u64, keys [n,k] u64, counts [n] u32), knn_graph's
+        layout.  No forest needed."""
+        in_ids, in_counts = (graph[0], graph[-1])
+        in_ids = np.ascontiguousarray(in_ids, np.uint64)
+        in_counts = np.ascontiguousarray(in_counts, np.uint32)
+        stored = self.stored_rows()
+        if in_ids.ndim != 2 or in_counts.ndim != 1 or in_ids.shape[0] != stored or in_counts.shape[0] != stored:
+            raise _ffi.ZhError(_ffi.ZH_EINVAL, "knn_graph_refine: the graph must cover the %d stored rows: ids [%d, in_k], counts [%d]" % (stored, stored, stored))
+        rounds = int(rounds)
+        if rounds < 1:
+            raise _ffi.ZhError(_ffi.ZH_EINVAL, "knn_graph_refine: rounds must be at least 1")
+        n = max(stored - first_row, 0) if n is None else int(n)
+        if rounds > 1 and (first_row != 0 or n != stored):
+            raise _ffi.ZhError(_ffi.ZH_EINVAL, "knn_graph_refine: rounds > 1 needs the whole table (a round's output is the next round's input)")
+        for _ in range(rounds):
+            ids = np.empty((n, k), np.uint64)
+            keys = np.empty((n, k), np.uint64)
+            counts = np.zeros(n, np.uint32)
+            check(lib().zh_knn_graph_refine(self._h, _p(in_ids), _p(in_counts), in_ids.shape[1], int(first_row), n, k, metric.metric, metric.mode,
+                                            _p(ids), _p(keys), _p(counts)))
+            if rounds > 1 and (k == 0 or self.knn_refine_info()["updates"] == 0):
+                break
+            in_ids, in_counts = ids, counts
+        return ids, keys, counts
+
+    def knn_graph_refine_device(self, d_in_ids_ptr, d_in_counts_ptr, in_k, k, metric, first_row, n, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream=None):
+        """one round of knn_graph_refine with the graph ([stored rows, in_k] u64, [stored rows] u32) and the outputs ([n,k] u64 twice, [n] u32)
+        already in device memory (raw pointers, e.g. torch .data_ptr())."""
+        check(lib().zh_knn_graph_refine_device(self._h, d_in_ids_ptr, d_in_counts_ptr, int(in_k), int(first_row), int(n), k, metric.metric, metric.mode,
+                                               d_ids_ptr, d_keys_ptr, d_counts_ptr, stream))
+
+    def knn_refine_info(self):
+        """what the most recent graph refinement call on this index did (zh_knn_graph_refine_info): rows_live, lines, in_k, k, listed, keyed,
+        updates, launches"""
+        return self._info(_ffi.KnnRefineInfo, lib().zh_knn_graph_refine_info)
+
     def deduplicate_within(self, radius, metric):
         """near-duplicate removal: rows are taken in ascending id, and row b is removed exactly when some KEPT row a < b forms a joined pair
         with it (self_join at `radius`).  Decided on the host from the sorted pair list, then passed to remove -> the removed ids, ascending."""
@@ -1069,6 +1110,14 @@ class Database:
         if self.index.no_vectors():
             return {}
         return self._graph_documents(*self.index.knn_graph_forest(k, self.metric))
+
+    def knn_graph_refined(self, k, rounds=1):
+        """knn_graph_forest, then `rounds` rounds of LSHIndex.knn_graph_refine (each row's neighbours' neighbours, until a round changes
+        nothing) -> what knn_graph returns"""
+        if self.index.no_vectors():
+            return {}
+        graph = self.index.knn_graph_forest(k, self.metric)
+        return self._graph_documents(*self.index.knn_graph_refine(graph, k, self.metric, rounds=rounds))
 
     def _graph_documents(self, ids, keys, counts):
         dist = self._key_numbers(np.ascontiguousarray(keys)).reshape(keys.shape)

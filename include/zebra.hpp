@@ -424,6 +424,64 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_knn_graph_refine_info(h_.get(), &info));
         return info;
     }
+    // The same round with up to rev_k sampled reverse neighbours of every row -- the rows that name it, picked by a hash of the pair -- and THEIR
+    // lines among the candidates (zh_knn_graph_refine_rev).  in_k + rev_k <= ZH_REFINE_MAX_IN_K; rev_k = 0 is knn_graph_refine bit for bit.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> knn_graph_refine_rev(const std::vector<Id> &in_ids, const std::vector<std::uint32_t> &in_counts,
+                                                                               std::size_t in_k, std::size_t rev_k, std::size_t k, const Met &metric,
+                                                                               std::uint64_t first_row, std::uint64_t n) const {
+        const std::uint64_t stored = zh_index_stored_rows(h_.get());
+        if (in_counts.size() != stored || in_ids.size() != stored * in_k)
+            throw std::invalid_argument("knn_graph_refine_rev: the graph must cover every stored row");
+        std::vector<Id> ids(n * k + 1);
+        std::vector<DistanceUnit> keys(n * k + 1);
+        std::vector<std::uint32_t> counts(n + 1);
+        check(zh_knn_graph_refine_rev(h_.get(), in_ids.data(), in_counts.data(), in_k, rev_k, first_row, n, k, Met::metric, metric.mode(), ids.data(),
+                                      keys.data(), counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(n);
+        for (std::uint64_t i = 0; i < n; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * k + j], keys[i * k + j]);
+        return out;
+    }
+    template <class Met>
+    void knn_graph_refine_rev_device(const Id *d_in_ids, const std::uint32_t *d_in_counts, std::size_t in_k, std::size_t rev_k, std::uint64_t first_row,
+                                     std::uint64_t n, std::size_t k, const Met &metric, Id *d_out_ids, DistanceUnit *d_out_keys,
+                                     std::uint32_t *d_out_counts, void *stream = nullptr) const {
+        check(zh_knn_graph_refine_rev_device(h_.get(), d_in_ids, d_in_counts, in_k, rev_k, first_row, n, k, Met::metric, metric.mode(), d_out_ids,
+                                             d_out_keys, d_out_counts, stream));
+    }
+    zh_knn_refine_rev_info knn_refine_rev_info() const {
+        zh_knn_refine_rev_info info{};
+        check(zh_knn_graph_refine_rev_info(h_.get(), &info));
+        return info;
+    }
+    // The capped reverse graph on its own (zh_knn_graph_reverse): element i = up to rev_k of the live rows that name stored row first_row + i and
+    // that its own line does not name, in (hash, row) order; degree[i] = its uncapped in-degree.  No metric, no keys, no forest.
+    struct ReverseGraph {
+        std::vector<std::vector<Id>> lines;
+        std::vector<std::uint32_t> degree;
+    };
+    ReverseGraph knn_graph_reverse(const std::vector<Id> &in_ids, const std::vector<std::uint32_t> &in_counts, std::size_t in_k, std::size_t rev_k,
+                                   std::uint64_t first_row, std::uint64_t n) const {
+        const std::uint64_t stored = zh_index_stored_rows(h_.get());
+        if (in_counts.size() != stored || in_ids.size() != stored * in_k) throw std::invalid_argument("knn_graph_reverse: the graph must cover every stored row");
+        std::vector<Id> ids(n * rev_k + 1);
+        std::vector<std::uint32_t> counts(n + 1);
+        ReverseGraph out{std::vector<std::vector<Id>>(n), std::vector<std::uint32_t>(n + 1)};
+        check(zh_knn_graph_reverse(h_.get(), in_ids.data(), in_counts.data(), in_k, rev_k, first_row, n, ids.data(), counts.data(), out.degree.data()));
+        out.degree.resize(n);
+        for (std::uint64_t i = 0; i < n; i++) out.lines[i].assign(ids.begin() + i * rev_k, ids.begin() + i * rev_k + counts[i]);
+        return out;
+    }
+    void knn_graph_reverse_device(const Id *d_in_ids, const std::uint32_t *d_in_counts, std::size_t in_k, std::size_t rev_k, std::uint64_t first_row,
+                                  std::uint64_t n, Id *d_out_ids, std::uint32_t *d_out_counts, std::uint32_t *d_out_degree, void *stream = nullptr) const {
+        check(zh_knn_graph_reverse_device(h_.get(), d_in_ids, d_in_counts, in_k, rev_k, first_row, n, d_out_ids, d_out_counts, d_out_degree, stream));
+    }
+    zh_knn_reverse_info knn_reverse_info() const {
+        zh_knn_reverse_info info{};
+        check(zh_knn_graph_reverse_info(h_.get(), &info));
+        return info;
+    }
     // the forest self-join (zh_self_join_forest): self_join's pairs among the rows that share a leaf in at least one tree, each pair once; exact
     // keys on an approximate candidate set.  One call that counts, one that fetches.  Needs a built forest.
     template <class Met>

@@ -33,6 +33,9 @@
  *   zh_knn_graph_forest[_device]         (new) every row's k nearest rows among its leaf-mates in the forest: exact keys, approximate candidates
  *   zh_knn_graph_refine[_device]         (new) one NN-descent join round over a caller's graph: every row's neighbours and their neighbours, ranked
  *                                        by the exact key
+ *   zh_knn_graph_reverse[_device]        (new) the capped reverse graph: for every row a deterministic sample of the rows that name it, and its
+ *                                        in-degree
+ *   zh_knn_graph_refine_rev[_device]     (new) zh_knn_graph_refine over each row's neighbours AND sampled reverse neighbours
  *   zh_self_join_forest[_device]         (new) every pair of leaf-mates whose key is at or below one threshold key, each pair once: exact keys,
  *                                        approximate candidates
  *   zh_search_range_forest_batch[_device] (new) every member of the leaves the walk visits for a query whose key is at or below the query's
@@ -689,6 +692,70 @@ typedef struct zh_knn_refine_info {  /* the most recent zh_knn_graph_refine* cal
     uint64_t launches;    /* launches of the line kernel: one per sub-slab of 65536 stored rows that holds a live row */
 } zh_knn_refine_info;
 ZH_API int zh_knn_graph_refine_info(const zh_index *idx, zh_knn_refine_info *out);
+
+/* ---- reverse neighbours (new): the capped transposed graph, alone and inside the refinement -------------------------------------------------
+ * zh_knn_graph_refine ranks what a row's line names and what those lines name, never the rows that name IT: half of an NN-descent join.  With
+ * N'(x) as defined above (the same rules for out-of-range, removed and repeated entries):
+ *   In(x)   = { u live, u != x : x in N'(u) }, deg(x) = |In(x)| -- 0 for a removed x, which N' never names.
+ *   h(u, x) = fmix32((u + 0x9E3779B9 * (x + 1)) mod 2^32) on the 32-bit row numbers, fmix32 murmur3's finaliser (h ^= h >> 16; h *= 0x85EBCA6B;
+ *             h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16).  h(0,0) = 0x92CA2F0E, h(12345,678) = 0x44199268.
+ *   R'(x)   = the first min(rev_k, |In(x) - N'(x)|) members of In(x) - N'(x), ascending by (h(u, x), u): mutual neighbours are left out (the line
+ *             holds them), and the pick is a deterministic pseudo-random sample -- no seed, no dependence on the order of entries, the run or
+ *             the slab.
+ *   B(x)    = N'(x) union R'(x);   C_r(a) = ( B(a)  union  B(u) for every u in B(a) ) minus a.
+ * zh_knn_graph_reverse: the input is the graph over ALL stored rows as for zh_knn_graph_refine; the slab selects output lines only.  Line i
+ * belongs to x = first_row + i: out_ids [n][rev_k] holds R'(x) as id_base + row in (h, u) order with tails UINT64_MAX, out_counts[i] = |R'(x)|,
+ * out_degree[i] = deg(x), the uncapped in-degree (the hubness score).  No metric and no keys are involved.  Limits: in_k and rev_k at most
+ * ZH_REFINE_MAX_IN_K, else ZH_ELIMIT; 0 for either with n > 0 is ZH_EINVAL.  Judged before any device is touched, in this order of kinds: a
+ * null index (even for n = 0), null pointers of a request with n > 0, the two limits (in_k, rev_k), in_k = 0, rev_k = 0.  Then first_row + n >
+ * stored rows is ZH_EINVAL and n = 0 is ZH_OK.  Locking, stream semantics and "no forest needed" as zh_knn_graph_refine.
+ * zh_knn_graph_refine_rev: zh_knn_graph_refine's arguments with rev_k behind in_k, and its answer, layout, keys, slabs and counts with C_r(a)
+ * in place of C(a).  in_k + rev_k <= ZH_REFINE_MAX_IN_K, else ZH_ELIMIT (judged right after in_k's own limit); rev_k = 0 is allowed and is
+ * zh_knn_graph_refine bit for bit (edges, kept and max_degree are then 0: nothing is transposed).  `updates` counts the answer's entries that
+ * are not in N'(a) -- the FORWARD line -- so it stays the convergence signal, 0 at a fixed point.  C(a) is a subset of C_r(a): position by
+ * position the answer's (key, id) is never above zh_knn_graph_refine's; refining the exact graph with k <= in_k still returns its first k.
+ * The transposition runs on the refinement's table of row numbers: a pass of vector atomics counts the in-degrees, a scan makes 64-bit offsets,
+ * a scatter fills the in-neighbours (their order inside a row's segment is not deterministic, the selection does not depend on it), a wave per
+ * line -- a block for a line of more than 1024 in-neighbours -- keeps the rev_k smallest (h, u).  Device scratch is per call and released
+ * before return: beside zh_knn_graph_refine's, per stored row 4 in_k (the in-neighbours) + 16 (in-degree, cursor, offset) + in_k / 256 + 1
+ * bytes, for the fused call 4 (in_k + rev_k) more (the union table), and for zh_knn_graph_reverse's host call 8 rev_k + 8 bytes per line of a
+ * staged piece of at most max(65536, 2^25 / rev_k) lines.  DESIGN.md s22. */
+ZH_API int zh_knn_graph_reverse(zh_index *idx, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, size_t rev_k, uint64_t first_row, uint64_t n,
+                                uint64_t *out_ids, uint32_t *out_counts, uint32_t *out_degree);
+ZH_API int zh_knn_graph_reverse_device(zh_index *idx, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, size_t rev_k, uint64_t first_row,
+                                       uint64_t n, uint64_t *d_out_ids, uint32_t *d_out_counts, uint32_t *d_out_degree, void *stream);
+typedef struct zh_knn_reverse_info {  /* the most recent zh_knn_graph_reverse* call on this index */
+    uint64_t rows_live;   /* live rows of the index */
+    uint64_t lines;       /* live rows of the slab */
+    uint32_t in_k;
+    uint32_t rev_k;
+    uint64_t edges;       /* the sum of deg(x) over ALL stored rows */
+    uint64_t kept;        /* the sum of |R'(x)| over the slab */
+    uint64_t max_degree;  /* the largest deg(x) over ALL stored rows */
+    uint64_t launches;    /* launches of the two selection kernels: per staged piece one per 2^24 lines and one for the heavy lines */
+} zh_knn_reverse_info;
+ZH_API int zh_knn_graph_reverse_info(const zh_index *idx, zh_knn_reverse_info *out);
+
+ZH_API int zh_knn_graph_refine_rev(zh_index *idx, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, size_t rev_k, uint64_t first_row, uint64_t n,
+                                   size_t k, int metric, int cosine_mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts);
+ZH_API int zh_knn_graph_refine_rev_device(zh_index *idx, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, size_t rev_k, uint64_t first_row,
+                                          uint64_t n, size_t k, int metric, int cosine_mode, uint64_t *d_out_ids, uint64_t *d_out_keys,
+                                          uint32_t *d_out_counts, void *stream);
+typedef struct zh_knn_refine_rev_info {  /* the most recent zh_knn_graph_refine_rev* call on this index; the first eight fields are zh_knn_refine_info's */
+    uint64_t rows_live;
+    uint64_t lines;
+    uint32_t in_k;
+    uint32_t k;
+    uint64_t listed;      /* the sum over the lines a of |B(a)| + the sum over u in B(a) of |B(u)| */
+    uint64_t keyed;       /* the sum of |C_r(a)| */
+    uint64_t updates;     /* output entries whose row is not in the FORWARD line N'(a) */
+    uint64_t launches;    /* launches of the line kernel */
+    uint64_t rev_k;
+    uint64_t edges;       /* the sum of deg(x) over ALL stored rows; 0 when rev_k = 0 */
+    uint64_t kept;        /* the sum of |R'(x)| over the slab */
+    uint64_t max_degree;  /* the largest deg(x) over ALL stored rows */
+} zh_knn_refine_rev_info;
+ZH_API int zh_knn_graph_refine_rev_info(const zh_index *idx, zh_knn_refine_rev_info *out);
 
 /* ---- forest self-join (new): all near-duplicate pairs AMONG LEAF-MATES ---------------------------------------------------------------------
  * zh_self_join multiplies every tile of the table by every tile at or above it; this call multiplies a leaf only by itself.  Arguments, key,

@@ -188,6 +188,36 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_knn_reverse_info {
+        pub rows_live: u64,
+        pub lines: u64,
+        pub in_k: u32,
+        pub rev_k: u32,
+        pub edges: u64,
+        pub kept: u64,
+        pub max_degree: u64,
+        pub launches: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
+    pub struct zh_knn_refine_rev_info {
+        pub rows_live: u64,
+        pub lines: u64,
+        pub in_k: u32,
+        pub k: u32,
+        pub listed: u64,
+        pub keyed: u64,
+        pub updates: u64,
+        pub launches: u64,
+        pub rev_k: u64,
+        pub edges: u64,
+        pub kept: u64,
+        pub max_degree: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_join_forest_info {
         pub rows_live: u64,
         pub trees: u32,
@@ -344,6 +374,17 @@ pub mod ffi {
                                           k: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64, d_out_keys: *mut u64,
                                           d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_knn_graph_refine_info(idx: *const zh_index, out: *mut zh_knn_refine_info) -> c_int;
+        pub fn zh_knn_graph_reverse(idx: *mut zh_index, in_ids: *const u64, in_counts: *const u32, in_k: usize, rev_k: usize, first_row: u64, n: u64,
+                                    out_ids: *mut u64, out_counts: *mut u32, out_degree: *mut u32) -> c_int;
+        pub fn zh_knn_graph_reverse_device(idx: *mut zh_index, d_in_ids: *const u64, d_in_counts: *const u32, in_k: usize, rev_k: usize, first_row: u64,
+                                           n: u64, d_out_ids: *mut u64, d_out_counts: *mut u32, d_out_degree: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_knn_graph_reverse_info(idx: *const zh_index, out: *mut zh_knn_reverse_info) -> c_int;
+        pub fn zh_knn_graph_refine_rev(idx: *mut zh_index, in_ids: *const u64, in_counts: *const u32, in_k: usize, rev_k: usize, first_row: u64, n: u64,
+                                       k: usize, metric: c_int, cosine_mode: c_int, out_ids: *mut u64, out_keys: *mut u64, out_counts: *mut u32) -> c_int;
+        pub fn zh_knn_graph_refine_rev_device(idx: *mut zh_index, d_in_ids: *const u64, d_in_counts: *const u32, in_k: usize, rev_k: usize,
+                                              first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64,
+                                              d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_knn_graph_refine_rev_info(idx: *const zh_index, out: *mut zh_knn_refine_rev_info) -> c_int;
         pub fn zh_self_join_forest(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, out_a: *mut u64,
                                    out_b: *mut u64, out_keys: *mut u64, out_total: *mut u64) -> c_int;
         pub fn zh_self_join_forest_device(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, d_out_a: *mut u64,
@@ -854,6 +895,19 @@ impl<const N: usize> LSHIndex<N> {
         rounds: usize,
         metric: &Met,
     ) -> anyhow::Result<Vec<(Uuid, Vec<(Uuid, DistanceUnit)>)>> {
+        self.knn_graph_refined_rev(k, rounds, 0, metric)
+    }
+
+    /// (new) knn_graph_refined with up to `reverse` sampled reverse neighbours of every vector -- the vectors that name it, picked by a hash of
+    /// the pair -- and THEIR lists among each round's candidates (zh_knn_graph_refine_rev; k + reverse <= 64).  reverse == 0 is
+    /// knn_graph_refined's call and path exactly.
+    pub fn knn_graph_refined_rev<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        k: usize,
+        rounds: usize,
+        reverse: usize,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<(Uuid, Vec<(Uuid, DistanceUnit)>)>> {
         let t = self.ids.read().unwrap();
         let stored = t.of_row.len();
         let (mut ids, mut keys, mut counts) = (vec![0u64; stored * k + 1], vec![0u64; stored * k + 1], vec![0u32; stored + 1]);
@@ -868,13 +922,22 @@ impl<const N: usize> LSHIndex<N> {
             if stored == 0 || k == 0 {
                 break;
             }
-            check(unsafe {
-                ffi::zh_knn_graph_refine(self.hip.0, ids.as_ptr(), counts.as_ptr(), k, 0, stored as u64, k, Met::METRIC, metric.param(),
-                                         rids.as_mut_ptr(), keys.as_mut_ptr(), rcounts.as_mut_ptr())
-            })?;
+            let updates = if reverse == 0 {
+                check(unsafe {
+                    ffi::zh_knn_graph_refine(self.hip.0, ids.as_ptr(), counts.as_ptr(), k, 0, stored as u64, k, Met::METRIC, metric.param(),
+                                             rids.as_mut_ptr(), keys.as_mut_ptr(), rcounts.as_mut_ptr())
+                })?;
+                self.knn_refine_info()?.updates
+            } else {
+                check(unsafe {
+                    ffi::zh_knn_graph_refine_rev(self.hip.0, ids.as_ptr(), counts.as_ptr(), k, reverse, 0, stored as u64, k, Met::METRIC,
+                                                 metric.param(), rids.as_mut_ptr(), keys.as_mut_ptr(), rcounts.as_mut_ptr())
+                })?;
+                self.knn_refine_rev_info()?.updates
+            };
             std::mem::swap(&mut ids, &mut rids);
             std::mem::swap(&mut counts, &mut rcounts);
-            if self.knn_refine_info()?.updates == 0 {
+            if updates == 0 {
                 break;
             }
         }
@@ -887,6 +950,45 @@ impl<const N: usize> LSHIndex<N> {
     pub fn knn_refine_info(&self) -> anyhow::Result<ffi::zh_knn_refine_info> {
         let mut info = ffi::zh_knn_refine_info::default();
         check(unsafe { ffi::zh_knn_graph_refine_info(self.hip.0, &mut info) })?;
+        Ok(info)
+    }
+
+    /// what the most recent refinement with reverse neighbours did (zh_knn_graph_refine_rev_info)
+    pub fn knn_refine_rev_info(&self) -> anyhow::Result<ffi::zh_knn_refine_rev_info> {
+        let mut info = ffi::zh_knn_refine_rev_info::default();
+        check(unsafe { ffi::zh_knn_graph_refine_rev_info(self.hip.0, &mut info) })?;
+        Ok(info)
+    }
+
+    /// (new) every vector's in-degree in the forest k-NN graph (zh_knn_graph_forest, then zh_knn_graph_reverse): how many other vectors name it
+    /// among their k leaf-mate neighbours -- the hubness score
+    pub fn knn_in_degrees<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        k: usize,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<(Uuid, u32)>> {
+        let t = self.ids.read().unwrap();
+        let stored = t.of_row.len();
+        if stored == 0 || k == 0 {
+            return Ok(Vec::new());
+        }
+        let (mut ids, mut keys, mut counts) = (vec![0u64; stored * k + 1], vec![0u64; stored * k + 1], vec![0u32; stored + 1]);
+        check(unsafe {
+            ffi::zh_knn_graph_forest(self.hip.0, 0, stored as u64, k, Met::METRIC, metric.param(), ids.as_mut_ptr(), keys.as_mut_ptr(),
+                                     counts.as_mut_ptr())
+        })?;
+        let (mut rids, mut rcounts, mut degree) = (vec![0u64; stored + 1], vec![0u32; stored + 1], vec![0u32; stored + 1]);
+        check(unsafe {
+            ffi::zh_knn_graph_reverse(self.hip.0, ids.as_ptr(), counts.as_ptr(), k, 1, 0, stored as u64, rids.as_mut_ptr(), rcounts.as_mut_ptr(),
+                                      degree.as_mut_ptr())
+        })?;
+        Ok((0..stored).map(|i| (t.of_row[i], degree[i])).collect())
+    }
+
+    /// what the most recent zh_knn_graph_reverse call did (zh_knn_graph_reverse_info)
+    pub fn knn_reverse_info(&self) -> anyhow::Result<ffi::zh_knn_reverse_info> {
+        let mut info = ffi::zh_knn_reverse_info::default();
+        check(unsafe { ffi::zh_knn_graph_reverse_info(self.hip.0, &mut info) })?;
         Ok(info)
     }
 

@@ -157,6 +157,21 @@ class KnnRefineInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KnnReverseInfo(C.Structure):
+    _fields_ = [("rows_live", C.c_uint64), ("lines", C.c_uint64), ("in_k", C.c_uint32), ("rev_k", C.c_uint32), ("edges", C.c_uint64),
+                ("kept", C.c_uint64), ("max_degree", C.c_uint64), ("launches", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class KnnRefineRevInfo(C.Structure):
+    _fields_ = KnnRefineInfo._fields_ + [("rev_k", C.c_uint64), ("edges", C.c_uint64), ("kept", C.c_uint64), ("max_degree", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class JoinForestInfo(C.Structure):
     _fields_ = [("rows_live", C.c_uint64), ("trees", C.c_uint32), ("path", C.c_uint32), ("leaf_pairs", C.c_uint64), ("pairs", C.c_uint64),
                 ("candidates", C.c_uint64), ("launches", C.c_uint64), ("tiles", C.c_uint64), ("redone", C.c_uint32)]
@@ -255,6 +270,12 @@ SYMBOLS = [
     ("zh_knn_graph_refine", _i, [_vp, _vp, _vp, _sz, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_knn_graph_refine_device", _i, [_vp, _vp, _vp, _sz, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_knn_graph_refine_info", _i, [_vp, _vp]),
+    ("zh_knn_graph_reverse", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _vp, _vp, _vp]),
+    ("zh_knn_graph_reverse_device", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _vp, _vp, _vp, _vp]),
+    ("zh_knn_graph_reverse_info", _i, [_vp, _vp]),
+    ("zh_knn_graph_refine_rev", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
+    ("zh_knn_graph_refine_rev_device", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    ("zh_knn_graph_refine_rev_info", _i, [_vp, _vp]),
     ("zh_self_join_forest", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_device", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_info", _i, [_vp, _vp]),

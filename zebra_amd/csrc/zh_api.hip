@@ -292,6 +292,11 @@ struct zh_index {
     // the table of row numbers, the lines' counts, one chunk of the host call's u64 input, {listed, keyed, updates}
     DevBuf rf_tab, rf_cnt, rf_stage, rf_ctr;
     zh_knn_refine_info rf_info{};  // (stats_mu)
+    // the capped reverse graph's per-call scratch beside the refinement's (all released before the call returns): in-degrees, fill cursors, 64-bit
+    // offsets, the scan's block sums, the in-neighbours, the heavy lines, the union table, {edges, max degree, kept, heavy lines}, the host call's staging
+    DevBuf rv_deg, rv_cur, rv_off, rv_sums, rv_csr, rv_heavy, rv_uni, rv_ctr, rv_oids, rv_ocounts, rv_odeg;
+    zh_knn_reverse_info rv_info{};          // (stats_mu)
+    zh_knn_refine_rev_info rfr_info{};      // (stats_mu)
     // the forest self-join's per-call scratch beside the self-join's and the forest graph's (all released before the call returns): leaf_of, a path-1
     // panel's pieces and per-line {leaf, key offset}, path 2's segments and candidate pool
     DevBuf fj_leafof, fj_pieces, fj_linel, fj_linek, fj_segs, fj_cand;
@@ -3472,7 +3477,7 @@ static int score_param(int metric, int mode) { return (metric == ZH_COSINE || me
 // index holds only the live-row views (ex_live and ex_bits survive every call; zh_index_destroy frees them).  Every family scans with the exact
 // search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's, the forest range search with
 // the range search's and the forest join's, the cross-join (all on its LEFT index) with the join's and its own views.
-enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512 };  // one bit per list
+enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024 };  // one bit per list
 enum : unsigned {
     SCRATCH_EXACT = SCR_EX,
     SCRATCH_FILTER = SCR_FL | SCRATCH_EXACT,
@@ -3481,6 +3486,7 @@ enum : unsigned {
     SCRATCH_KNN = SCR_KN | SCRATCH_EXACT,
     SCRATCH_FKNN = SCR_FK | SCRATCH_KNN,
     SCRATCH_REFINE = SCR_RF | SCRATCH_KNN,
+    SCRATCH_REVERSE = SCR_RV | SCRATCH_REFINE,
     SCRATCH_FJOIN = SCR_FJ | SCRATCH_JOIN | SCRATCH_FKNN,
     SCRATCH_FRANGE = SCR_FR | SCRATCH_RANGE | SCRATCH_FJOIN,
     SCRATCH_XJOIN = SCR_XJ | SCRATCH_JOIN,  // (on the left index)
@@ -3505,6 +3511,8 @@ static void release_scratch(zh_index *ix, unsigned families) {
                   &ix->fk_cbase, &ix->fk_groups, &ix->fk_groff, &ix->fk_segs, &ix->fk_colsrc, &ix->fk_crow, &ix->fk_hrow, &ix->fk_held, &ix->fk_CA,
                   &ix->fk_cmeta, &ix->fk_cqm, &ix->fk_HA, &ix->fk_hmeta, &ix->fk_qrow, &ix->fk_maxk, &ix->fk_redo, &ix->fk_pos});
     drop(SCR_RF, {&ix->rf_tab, &ix->rf_cnt, &ix->rf_stage, &ix->rf_ctr});
+    drop(SCR_RV, {&ix->rv_deg, &ix->rv_cur, &ix->rv_off, &ix->rv_sums, &ix->rv_csr, &ix->rv_heavy, &ix->rv_uni, &ix->rv_ctr, &ix->rv_oids, &ix->rv_ocounts,
+                  &ix->rv_odeg});
     drop(SCR_FJ, {&ix->fj_leafof, &ix->fj_pieces, &ix->fj_linel, &ix->fj_linek, &ix->fj_segs, &ix->fj_cand});
     drop(SCR_FR, {&ix->fr_counts, &ix->fr_inline, &ix->fr_rowbase, &ix->fr_candbase, &ix->fr_visitbase, &ix->fr_totals, &ix->fr_leafcount, &ix->fr_leaffill,
                   &ix->fr_groupbase, &ix->fr_grouprowbase, &ix->fr_loghead, &ix->fr_logctl, &ix->fr_logpool, &ix->fr_visits, &ix->fr_groups, &ix->fr_groupoff,
@@ -5327,9 +5335,10 @@ static int refine_table(zh_index *ix, const uint64_t *in_ids, const uint32_t *in
     return ZH_OK;
 }
 
-// One slab on device outputs (under mu, exclusive; exact_live_rows and refine_table have run; k > 0, n > 0): every line filled as "no neighbours",
+// One slab on device outputs (under mu, exclusive; exact_live_rows and refine_table have run; k > 0, n > 0; dTab's lines are in_k wide, the first
+// fwd_k of them the caller's own: rf_tab at in_k twice, or the union table): every line filled as "no neighbours",
 // then sub-slab by sub-slab the live lines (a stretch of ex_live), their f32 rows as the query side, their norms, and a block per line.
-static int refine_slab(zh_index *ix, LiveCursor *live, uint32_t in_k, uint64_t first_row, uint64_t n, uint32_t k, int metric, int mode, uint64_t *dIds,
+static int refine_slab(zh_index *ix, LiveCursor *live, const uint32_t *dTab, uint32_t in_k, uint32_t fwd_k, uint64_t first_row, uint64_t n, uint32_t k, int metric, int mode, uint64_t *dIds,
                        uint64_t *dKeys, uint32_t *dCounts, hipStream_t s, zh_knn_refine_info *inf) {
     const uint32_t d = ix->opt.dim;
     int rc;
@@ -5343,7 +5352,7 @@ static int refine_slab(zh_index *ix, LiveCursor *live, uint32_t in_k, uint64_t f
         if ((rc = ix->ex_Q.ensure((size_t)B * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)B * 4))) return rc;
         HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dRows, B, ix->ex_Q.as<float>(), s));
         HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), B, d, ix->ex_QQ.as<float>(), s));
-        HIPCHK(zh_launch_refine_lines(ix->X.as<float>(), d, ix->rf_tab.as<uint32_t>(), in_k, dRows, B, ix->ex_Q.as<float>(), ix->ex_QQ.as<float>(), metric,
+        HIPCHK(zh_launch_refine_lines(ix->X.as<float>(), d, dTab, in_k, fwd_k, dRows, B, ix->ex_Q.as<float>(), ix->ex_QQ.as<float>(), metric,
                                       score_param(metric, mode), ix->opt.id_base, first_row, k, dIds, dKeys, dCounts, ix->rf_ctr.as<unsigned long long>(), s));
         inf->lines += B;
         inf->launches++;
@@ -5364,25 +5373,61 @@ static int refine_args(zh_index *ix, const void *in_ids, const void *in_counts, 
     return ZH_OK;
 }
 
-// both entry points once the arguments have been judged (n > 0)
-static int refine_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, uint64_t first_row, uint64_t n, size_t k, int metric,
-                       int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, bool host, void *stream, const char *who) {
+// The in-neighbours of every stored row out of rf_tab (refine_table has run; n_rows > 0): rv_deg, rv_off, rv_csr; rv_ctr = {edges, max in-degree, 0, 0}
+static int reverse_csr(zh_index *ix, uint32_t in_k, hipStream_t s) {
+    const uint64_t N = ix->n_rows;
+    int rc;
+    if ((rc = ix->rv_deg.ensure((size_t)N * 4)) || (rc = ix->rv_cur.ensure((size_t)N * 4)) || (rc = ix->rv_off.ensure((size_t)(N + 1) * 8)) ||
+        (rc = ix->rv_sums.ensure((size_t)(N / 4096 + 1) * 8)) || (rc = ix->rv_csr.ensure((size_t)N * in_k * 4)) ||
+        (rc = ix->rv_heavy.ensure((size_t)(N * in_k / ZH_REVERSE_HEAVY + 1) * 4)) || (rc = ix->rv_ctr.ensure(32)))
+        return rc;
+    HIPCHK(hipMemsetAsync(ix->rv_ctr.p, 0, 32, s));
+    HIPCHK(zh_launch_reverse_csr(ix->rf_tab.as<uint32_t>(), ix->ex_bits.as<uint32_t>(), N, in_k, ix->rv_deg.as<uint32_t>(), ix->rv_cur.as<uint32_t>(), ix->rv_off.as<uint64_t>(),
+                                 ix->rv_sums.as<uint64_t>(), ix->rv_csr.as<uint32_t>(), ix->rv_ctr.as<unsigned long long>(), s));
+    return ZH_OK;
+}
+
+// R'(x) of the lines [x0, x0 + nx) (reverse_csr has run): into the union table rv_uni (uni) and / or, for the lines of [first_row, first_row + n), as
+// ids, counts and in-degrees on device pointers; rv_ctr[2] += the slab's kept entries
+static int reverse_select(zh_index *ix, uint32_t in_k, uint32_t rev_k, uint64_t x0, uint64_t nx, uint64_t first_row, uint64_t n, bool uni, uint64_t *dIds,
+                          uint32_t *dCounts, uint32_t *dDegree, hipStream_t s, uint64_t *launches) {
+    HIPCHK(zh_launch_reverse_select(ix->rf_tab.as<uint32_t>(), in_k, rev_k, ix->rv_off.as<uint64_t>(), ix->rv_csr.as<uint32_t>(), ix->n_rows, x0, nx, first_row, n,
+                                    ix->opt.id_base, uni ? ix->rv_uni.as<uint32_t>() : nullptr, dIds, dCounts, dDegree, ix->rv_heavy.as<uint32_t>(),
+                                    ix->rv_ctr.as<unsigned long long>(), s));
+    *launches += (nx + (1ull << 24) - 1) / (1ull << 24) + 1;
+    return ZH_OK;
+}
+
+// both entry points of both refinements once the arguments have been judged (n > 0).  rev: zh_knn_graph_refine_rev*, which with rev_k > 0 ranks over
+// the union table (N'(x) then R'(x), in_k + rev_k wide) and always records rfr_info; zh_knn_graph_refine* records rf_info
+static int refine_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, uint32_t rev_k, bool rev, uint64_t first_row, uint64_t n,
+                       size_t k, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, bool host, void *stream, const char *who) {
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     int rc;
     if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, who))) return rc;
-    ScratchGuard guard{ix, SCRATCH_REFINE};
+    ScratchGuard guard{ix, rev ? SCRATCH_REVERSE : SCRATCH_REFINE};
     const hipStream_t s = call_stream(ix, stream);
     zh_knn_refine_info inf{};
-    unsigned long long ctr[3] = {0, 0, 0};
+    unsigned long long ctr[3] = {0, 0, 0}, rctr[4] = {0, 0, 0, 0};
+    uint64_t rev_launches = 0;
     if (k == 0) {
         if ((rc = knn_no_neighbours(n, out_counts, host, s))) return rc;
     } else {
         if ((rc = refine_table(ix, in_ids, in_counts, in_k, host, s))) return rc;
+        const uint32_t *dTab = ix->rf_tab.as<uint32_t>();
+        const uint32_t width = in_k + rev_k;
+        if (rev_k) {
+            if ((rc = ix->rv_uni.ensure((size_t)ix->n_rows * width * 4)) || (rc = reverse_csr(ix, in_k, s)) ||
+                (rc = reverse_select(ix, in_k, rev_k, 0, ix->n_rows, first_row, n, true, nullptr, nullptr, nullptr, s, &rev_launches)))
+                return rc;
+            HIPCHK(hipMemcpyAsync(rctr, ix->rv_ctr.p, 32, hipMemcpyDeviceToHost, s));  // (waited for with the slabs)
+            dTab = ix->rv_uni.as<uint32_t>();
+        }
         LiveCursor live;
         const uint64_t host_slab = std::max<uint64_t>(ZH_REFINE_SLAB, (uint64_t(1) << 25) / k / ZH_REFINE_SLAB * ZH_REFINE_SLAB);
         rc = knn_slabs(ix, first_row, n, k, out_ids, out_keys, out_counts, host_slab, host, s,
                        [&](uint64_t r0, uint64_t m, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
-                           return refine_slab(ix, &live, in_k, r0, m, (uint32_t)k, metric, mode, dIds, dKeys, dCounts, s, &inf);
+                           return refine_slab(ix, &live, dTab, width, in_k, r0, m, (uint32_t)k, metric, mode, dIds, dKeys, dCounts, s, &inf);
                        });
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(ctr, ix->rf_ctr.p, 24, hipMemcpyDeviceToHost, s));
@@ -5393,7 +5438,15 @@ static int refine_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_
     inf.k = (uint32_t)k;
     inf.listed = ctr[0]; inf.keyed = ctr[1]; inf.updates = ctr[2];
     std::lock_guard<std::mutex> ls(ix->stats_mu);
-    ix->rf_info = inf;
+    if (!rev) {
+        ix->rf_info = inf;
+        return ZH_OK;
+    }
+    zh_knn_refine_rev_info r{};
+    r.rows_live = inf.rows_live; r.lines = inf.lines; r.in_k = inf.in_k; r.k = inf.k;
+    r.listed = inf.listed; r.keyed = inf.keyed; r.updates = inf.updates; r.launches = inf.launches;
+    r.rev_k = rev_k; r.edges = rctr[0]; r.kept = rctr[2]; r.max_degree = rctr[1];
+    ix->rfr_info = r;
     return ZH_OK;
 }
 
@@ -5401,7 +5454,7 @@ extern "C" int zh_knn_graph_refine_device(zh_index *ix, const uint64_t *d_in_ids
                                           size_t k, int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
     int rc = refine_args(ix, d_in_ids, d_in_counts, in_k, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_refine_device");
     if (rc || n == 0) return rc;
-    return refine_call(ix, d_in_ids, d_in_counts, (uint32_t)in_k, first_row, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, false, stream,
+    return refine_call(ix, d_in_ids, d_in_counts, (uint32_t)in_k, 0, false, first_row, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, false, stream,
                        "zh_knn_graph_refine_device");
 }
 
@@ -5409,11 +5462,121 @@ extern "C" int zh_knn_graph_refine(zh_index *ix, const uint64_t *in_ids, const u
                                    int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts) {
     int rc = refine_args(ix, in_ids, in_counts, in_k, n, k, metric, mode, out_ids, out_keys, out_counts, "zh_knn_graph_refine");
     if (rc || n == 0) return rc;
-    return refine_call(ix, in_ids, in_counts, (uint32_t)in_k, first_row, n, k, metric, mode, out_ids, out_keys, out_counts, true, nullptr, "zh_knn_graph_refine");
+    return refine_call(ix, in_ids, in_counts, (uint32_t)in_k, 0, false, first_row, n, k, metric, mode, out_ids, out_keys, out_counts, true, nullptr,
+                       "zh_knn_graph_refine");
 }
 
 extern "C" int zh_knn_graph_refine_info(const zh_index *ix, zh_knn_refine_info *out) {
     return get_info(ix, &zh_index::rf_info, out, "zh_knn_graph_refine_info");
+}
+
+// ------------------------------------------------------------------------------------------------
+// reverse neighbours (zh_reverse.hip): the capped transposed graph on its own, and the refinement over N'(x) union R'(x).  DESIGN.md s22
+// ------------------------------------------------------------------------------------------------
+// zh_knn_graph_refine_rev*: refine_args' order with the limit of the sum behind in_k's
+static int refine_rev_args(zh_index *ix, const void *in_ids, const void *in_counts, size_t in_k, size_t rev_k, uint64_t n, size_t k, int metric, int mode,
+                           const void *ids, const void *keys, const void *counts, const char *who) {
+    if (!ix || (n && (!in_ids || !in_counts || !counts || (k && (!ids || !keys))))) return fail(ZH_EINVAL, "%s: null argument", who);
+    const int rc = check_metric(metric, mode);
+    if (rc) return rc;
+    if (k > ZH_MAX_TOPK - 1) return fail(ZH_ELIMIT, "%s: k %zu > ZH_MAX_TOPK - 1 (%u)", who, k, ZH_MAX_TOPK - 1);
+    if (in_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: in_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, ZH_REFINE_MAX_IN_K);
+    if (rev_k > ZH_REFINE_MAX_IN_K - in_k) return fail(ZH_ELIMIT, "%s: in_k %zu + rev_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, rev_k, ZH_REFINE_MAX_IN_K);
+    if (n && !in_k) return fail(ZH_EINVAL, "%s: in_k is 0", who);
+    return ZH_OK;
+}
+
+extern "C" int zh_knn_graph_refine_rev_device(zh_index *ix, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, size_t rev_k, uint64_t first_row,
+                                              uint64_t n, size_t k, int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts,
+                                              void *stream) {
+    int rc = refine_rev_args(ix, d_in_ids, d_in_counts, in_k, rev_k, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_refine_rev_device");
+    if (rc || n == 0) return rc;
+    return refine_call(ix, d_in_ids, d_in_counts, (uint32_t)in_k, (uint32_t)rev_k, true, first_row, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, false,
+                       stream, "zh_knn_graph_refine_rev_device");
+}
+
+extern "C" int zh_knn_graph_refine_rev(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, size_t rev_k, uint64_t first_row, uint64_t n,
+                                       size_t k, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts) {
+    int rc = refine_rev_args(ix, in_ids, in_counts, in_k, rev_k, n, k, metric, mode, out_ids, out_keys, out_counts, "zh_knn_graph_refine_rev");
+    if (rc || n == 0) return rc;
+    return refine_call(ix, in_ids, in_counts, (uint32_t)in_k, (uint32_t)rev_k, true, first_row, n, k, metric, mode, out_ids, out_keys, out_counts, true, nullptr,
+                       "zh_knn_graph_refine_rev");
+}
+
+extern "C" int zh_knn_graph_refine_rev_info(const zh_index *ix, zh_knn_refine_rev_info *out) {
+    return get_info(ix, &zh_index::rfr_info, out, "zh_knn_graph_refine_rev_info");
+}
+
+// judged before any device is touched, in this order of kinds: null index (even for n = 0), null inputs or outputs of a non-empty request, the two
+// limits, in_k = 0, rev_k = 0
+static int reverse_args(zh_index *ix, const void *in_ids, const void *in_counts, size_t in_k, size_t rev_k, uint64_t n, const void *ids, const void *counts,
+                        const void *degree, const char *who) {
+    if (!ix || (n && (!in_ids || !in_counts || !ids || !counts || !degree))) return fail(ZH_EINVAL, "%s: null argument", who);
+    if (in_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: in_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, ZH_REFINE_MAX_IN_K);
+    if (rev_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: rev_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, rev_k, ZH_REFINE_MAX_IN_K);
+    if (n && !in_k) return fail(ZH_EINVAL, "%s: in_k is 0", who);
+    if (n && !rev_k) return fail(ZH_EINVAL, "%s: rev_k is 0", who);
+    return ZH_OK;
+}
+
+// both entry points once the arguments have been judged (n > 0).  host: the outputs are HOST arrays and go piece by piece through the staging
+static int reverse_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, uint32_t rev_k, uint64_t first_row, uint64_t n,
+                        uint64_t *out_ids, uint32_t *out_counts, uint32_t *out_degree, bool host, void *stream, const char *who) {
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, who))) return rc;
+    ScratchGuard guard{ix, SCRATCH_REVERSE};
+    const hipStream_t s = call_stream(ix, stream);
+    zh_knn_reverse_info inf{};
+    unsigned long long rctr[4] = {0, 0, 0, 0};
+    if ((rc = refine_table(ix, in_ids, in_counts, in_k, host, s)) || (rc = reverse_csr(ix, in_k, s))) return rc;
+    if (!host) {
+        if ((rc = reverse_select(ix, in_k, rev_k, first_row, n, first_row, n, false, out_ids, out_counts, out_degree, s, &inf.launches))) return rc;
+    } else {
+        const uint64_t piece = std::min<uint64_t>(n, std::max<uint64_t>(ZH_REFINE_SLAB, (uint64_t(1) << 25) / rev_k));
+        if ((rc = ix->rv_oids.ensure(piece * rev_k * 8)) || (rc = ix->rv_ocounts.ensure(piece * 4)) || (rc = ix->rv_odeg.ensure(piece * 4))) return rc;
+        for (uint64_t r0 = 0; r0 < n; r0 += piece) {
+            const uint64_t m = std::min(piece, n - r0);
+            if ((rc = reverse_select(ix, in_k, rev_k, first_row + r0, m, first_row + r0, m, false, ix->rv_oids.as<uint64_t>(), ix->rv_ocounts.as<uint32_t>(),
+                                     ix->rv_odeg.as<uint32_t>(), s, &inf.launches)))
+                return rc;
+            HIPCHK(hipMemcpyAsync(out_ids + r0 * rev_k, ix->rv_oids.p, m * rev_k * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_counts + r0, ix->rv_ocounts.p, m * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_degree + r0, ix->rv_odeg.p, m * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+    }
+    HIPCHK(hipMemcpyAsync(rctr, ix->rv_ctr.p, 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    LiveCursor live;
+    inf.rows_live = ix->ex_n_live;
+    inf.lines = live_before(ix, first_row + n, &live) - live_before(ix, first_row, &live);
+    inf.in_k = in_k;
+    inf.rev_k = rev_k;
+    inf.edges = rctr[0]; inf.kept = rctr[2]; inf.max_degree = rctr[1];
+    std::lock_guard<std::mutex> ls(ix->stats_mu);
+    ix->rv_info = inf;
+    return ZH_OK;
+}
+
+extern "C" int zh_knn_graph_reverse_device(zh_index *ix, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, size_t rev_k, uint64_t first_row,
+                                           uint64_t n, uint64_t *d_out_ids, uint32_t *d_out_counts, uint32_t *d_out_degree, void *stream) {
+    int rc = reverse_args(ix, d_in_ids, d_in_counts, in_k, rev_k, n, d_out_ids, d_out_counts, d_out_degree, "zh_knn_graph_reverse_device");
+    if (rc || n == 0) return rc;
+    return reverse_call(ix, d_in_ids, d_in_counts, (uint32_t)in_k, (uint32_t)rev_k, first_row, n, d_out_ids, d_out_counts, d_out_degree, false, stream,
+                        "zh_knn_graph_reverse_device");
+}
+
+extern "C" int zh_knn_graph_reverse(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, size_t rev_k, uint64_t first_row, uint64_t n,
+                                    uint64_t *out_ids, uint32_t *out_counts, uint32_t *out_degree) {
+    int rc = reverse_args(ix, in_ids, in_counts, in_k, rev_k, n, out_ids, out_counts, out_degree, "zh_knn_graph_reverse");
+    if (rc || n == 0) return rc;
+    return reverse_call(ix, in_ids, in_counts, (uint32_t)in_k, (uint32_t)rev_k, first_row, n, out_ids, out_counts, out_degree, true, nullptr,
+                        "zh_knn_graph_reverse");
+}
+
+extern "C" int zh_knn_graph_reverse_info(const zh_index *ix, zh_knn_reverse_info *out) {
+    return get_info(ix, &zh_index::rv_info, out, "zh_knn_graph_reverse_info");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -493,10 +493,26 @@ hipError_t zh_launch_fknn_mark(const uint32_t *dHRow, uint32_t B, uint64_t first
 hipError_t zh_launch_refine_rows(const uint64_t *dIn, const uint32_t *dCounts, const uint32_t *dBits, uint64_t id_base, uint64_t n_rows, uint32_t in_k,
                                  uint64_t l0, uint64_t nl, uint32_t *dTab, hipStream_t s);
 // a block per line b (row dRows[b], its f32 values dQ[b], its squared norm dQQ[b]): the first k of C(row) by (key, id) to line row - first_row of the
-// outputs; dCtr[0] += listed, dCtr[1] += keyed, dCtr[2] += updates
-hipError_t zh_launch_refine_lines(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, const uint32_t *dRows, uint32_t B, const float *dQ,
-                                  const float *dQQ, int metric, int param, uint64_t id_base, uint64_t first_row, uint32_t k, uint64_t *dOutIds,
-                                  uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s);
+// outputs; dCtr[0] += listed, dCtr[1] += keyed, dCtr[2] += updates.  dTab's lines are in_k wide; `updates` counts against their first fwd_k entries
+// (the caller's own line: in_k for zh_knn_graph_refine, the forward part of the union table for zh_knn_graph_refine_rev)
+hipError_t zh_launch_refine_lines(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, uint32_t fwd_k, const uint32_t *dRows, uint32_t B,
+                                  const float *dQ, const float *dQQ, int metric, int param, uint64_t id_base, uint64_t first_row, uint32_t k,
+                                  uint64_t *dOutIds, uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s);
+
+// ---- the capped reverse graph (zh_reverse.hip) over zh_launch_refine_rows' table: In(x) = the rows u != x, live by dBits, whose line names x
+#define ZH_REVERSE_HEAVY 1024u  // in-degree above which a block of four waves, not one wave, selects a line's reverse neighbours
+// dDeg[x] = |In(x)|, dOff[x] = the in-degrees before x (n_rows + 1 entries, the last one the edge count), dCsr[dOff[x] ..] = In(x) in no
+// particular order; dCtr[0] = edges, dCtr[1] = max in-degree (dCtr zeroed by the caller).  dCur: n_rows words, dSums: n_rows / 4096 + 1 u64,
+// dCsr: n_rows * in_k words at most
+hipError_t zh_launch_reverse_csr(const uint32_t *dTab, const uint32_t *dBits, uint64_t n_rows, uint32_t in_k, uint32_t *dDeg, uint32_t *dCur, uint64_t *dOff, uint64_t *dSums,
+                                 uint32_t *dCsr, unsigned long long *dCtr, hipStream_t s);
+// R'(x) of the lines x0 .. x0 + nx: the first rev_k of In(x) - N'(x) by (h(u, x), u).  dUni (or null): line x of the union table [n_rows][in_k +
+// rev_k] = N'(x)'s line, then R'(x), UINT32_MAX tails.  dOutIds (or null; then the next two as well): for x in [first_row, first_row + n) line x -
+// first_row of [n][rev_k] ids, counts and in-degrees.  dCtr[2] += |R'(x)| over that slab; dCtr[3] and dHeavy (n_rows * in_k / ZH_REVERSE_HEAVY + 1
+// words) are the call's list of heavy lines
+hipError_t zh_launch_reverse_select(const uint32_t *dTab, uint32_t in_k, uint32_t rev_k, const uint64_t *dOff, const uint32_t *dCsr, uint64_t n_rows, uint64_t x0,
+                                    uint64_t nx, uint64_t first_row, uint64_t n, uint64_t id_base, uint32_t *dUni, uint64_t *dOutIds, uint32_t *dOutCounts,
+                                    uint32_t *dOutDegree, uint32_t *dHeavy, unsigned long long *dCtr, hipStream_t s);
 
 // ---- the forest self-join (zh_fjoin.hip): every pair of leaf-mates whose key is <= one threshold key, each pair once (the first tree that puts
 // the two rows together owns it).  Hit pool, counter and order as the exact self-join's

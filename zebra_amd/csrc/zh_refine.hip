@@ -9,7 +9,8 @@
 //                        a dropped, ids sorted, adjacent equals compacted -> U distinct rows; (b) the four waves stride over them with the line's
 //                        row in registers, ZH_REFINE_INFLIGHT candidate rows in flight per wave, exact_key's arithmetic (zh_approx.hip), keys to LDS;
 //                        (c) block_bitonic_sort by (key, id), the first min(k, U) written with id_base, tails and the count; `updates` = written
-//                        rows that N'(a) does not hold.
+//                        rows that N'(a) does not hold.  The table may be zh_reverse.hip's union table (N'(x) then the kept reverse
+//                        neighbours, in_k + rev_k wide): in_k is then that width, and N'(a) the line's first fwd_k entries.
 #include "zh_internal.h"
 #include "zh_device.h"
 
@@ -103,7 +104,7 @@ __device__ __forceinline__ uint64_t refine_key(const float4 *v, const float *__r
 
 template <int D, int KIND, int CAP>
 __global__ __launch_bounds__(256) void refine_line_kernel(const float *__restrict__ X, uint32_t d, const uint32_t *__restrict__ tab, uint32_t in_k,
-                                                          const uint32_t *__restrict__ rows, const float *__restrict__ Q, const float *__restrict__ QQ,
+                                                          uint32_t fwd_k, const uint32_t *__restrict__ rows, const float *__restrict__ Q, const float *__restrict__ QQ,
                                                           int metric, int param, uint64_t id_base, uint64_t first_row, uint32_t k,
                                                           uint64_t *__restrict__ out_ids, uint64_t *__restrict__ out_keys, uint32_t *__restrict__ out_counts,
                                                           unsigned long long *__restrict__ ctr) {
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256) void refine_line_kernel(const float *__restric
             const uint32_t r = s_id[i];
             id = id_base + r; key = s_key[i];
             bool old = false;
-            for (uint32_t j = 0; j < in_k; j++) old = old || s_own[j] == r;
+            for (uint32_t j = 0; j < fwd_k; j++) old = old || s_own[j] == r;
             mine += old ? 0u : 1u;
         }
         out_ids[o + i] = id; out_keys[o + i] = key;
@@ -211,25 +212,25 @@ __global__ __launch_bounds__(256) void refine_line_kernel(const float *__restric
 }
 
 template <int D, int KIND>
-static hipError_t launch_lines_d(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, const uint32_t *dRows, uint32_t B, const float *dQ,
+static hipError_t launch_lines_d(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, uint32_t fwd_k, const uint32_t *dRows, uint32_t B, const float *dQ,
                                  const float *dQQ, int metric, int param, uint64_t id_base, uint64_t first_row, uint32_t k, uint64_t *dOutIds,
                                  uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s) {
     if (in_k + in_k * in_k <= ZH_REFINE_CAP_SMALL)
-        hipLaunchKernelGGL((refine_line_kernel<D, KIND, ZH_REFINE_CAP_SMALL>), dim3(B), dim3(256), 0, s, dX, d, dTab, in_k, dRows, dQ, dQQ, metric, param, id_base,
+        hipLaunchKernelGGL((refine_line_kernel<D, KIND, ZH_REFINE_CAP_SMALL>), dim3(B), dim3(256), 0, s, dX, d, dTab, in_k, fwd_k, dRows, dQ, dQQ, metric, param, id_base,
                            first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr);
     else
-        hipLaunchKernelGGL((refine_line_kernel<D, KIND, ZH_REFINE_CAP_LARGE>), dim3(B), dim3(256), 0, s, dX, d, dTab, in_k, dRows, dQ, dQQ, metric, param, id_base,
+        hipLaunchKernelGGL((refine_line_kernel<D, KIND, ZH_REFINE_CAP_LARGE>), dim3(B), dim3(256), 0, s, dX, d, dTab, in_k, fwd_k, dRows, dQ, dQQ, metric, param, id_base,
                            first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr);
     return hipGetLastError();
 }
 
 // the dimensions zh_launch_exact_score specialises: 128 / 384 / 768 for every kind, 256 / 512 / 1024 as well for the two simsimd kinds
 template <int KIND>
-static hipError_t launch_lines_kind(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, const uint32_t *dRows, uint32_t B, const float *dQ,
+static hipError_t launch_lines_kind(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, uint32_t fwd_k, const uint32_t *dRows, uint32_t B, const float *dQ,
                                     const float *dQQ, int metric, int param, uint64_t id_base, uint64_t first_row, uint32_t k, uint64_t *dOutIds,
                                     uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s) {
 #define ZH_RF_CASE(DD) \
-    case DD: return launch_lines_d<DD, KIND>(dX, d, dTab, in_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s)
+    case DD: return launch_lines_d<DD, KIND>(dX, d, dTab, in_k, fwd_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s)
     if constexpr (KIND == K_L2 || KIND == K_COS) {
         switch (d) {
             ZH_RF_CASE(256);
@@ -245,16 +246,16 @@ static hipError_t launch_lines_kind(const float *dX, uint32_t d, const uint32_t 
     default: break;
     }
 #undef ZH_RF_CASE
-    return launch_lines_d<0, KIND>(dX, d, dTab, in_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s);
+    return launch_lines_d<0, KIND>(dX, d, dTab, in_k, fwd_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s);
 }
 
-hipError_t zh_launch_refine_lines(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, const uint32_t *dRows, uint32_t B, const float *dQ,
+hipError_t zh_launch_refine_lines(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, uint32_t fwd_k, const uint32_t *dRows, uint32_t B, const float *dQ,
                                   const float *dQQ, int metric, int param, uint64_t id_base, uint64_t first_row, uint32_t k, uint64_t *dOutIds,
                                   uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s) {
     if (!B) return hipSuccess;
-    if (!in_k || in_k > ZH_REFINE_MAX_IN_K || in_k + in_k * in_k > ZH_REFINE_CAP_LARGE || !k) return hipErrorInvalidValue;
+    if (!in_k || in_k > ZH_REFINE_MAX_IN_K || in_k + in_k * in_k > ZH_REFINE_CAP_LARGE || fwd_k > in_k || !k) return hipErrorInvalidValue;
 #define ZH_RF_KIND(K) \
-    case K: return launch_lines_kind<K>(dX, d, dTab, in_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s)
+    case K: return launch_lines_kind<K>(dX, d, dTab, in_k, fwd_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s)
     switch (zh_kind_of(metric)) {
         ZH_RF_KIND(K_COS);
         ZH_RF_KIND(K_MAX);
@@ -265,7 +266,7 @@ hipError_t zh_launch_refine_lines(const float *dX, uint32_t d, const uint32_t *d
         ZH_RF_KIND(K_P4);
         ZH_RF_KIND(K_HAMM);
         ZH_RF_KIND(K_PP);
-    default: return launch_lines_kind<K_L2>(dX, d, dTab, in_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s);
+    default: return launch_lines_kind<K_L2>(dX, d, dTab, in_k, fwd_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s);
     }
 #undef ZH_RF_KIND
 }

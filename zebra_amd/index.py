@@ -653,13 +653,15 @@ class LSHIndex:
         survivors, redone, launches, tiles"""
         return self._info(_ffi.KnnForestInfo, lib().zh_knn_graph_forest_info)
 
-    def knn_graph_refine(self, graph, k, metric, first_row=0, n=None, rounds=1):
+    def knn_graph_refine(self, graph, k, metric, first_row=0, n=None, rounds=1, reverse=0):
         """one join round of NN-descent over a graph of ALL stored rows: `graph` is (ids [stored rows, in_k] u64, counts [stored rows] u32) or the
         3-tuple knn_graph / knn_graph_forest return (its keys are not read: every returned key is computed here).  Line i of the answer holds the
         first k by (key, id) of stored row first_row + i's neighbours and their neighbours, the row itself excluded; entries that are out of range,
         removed or repeated in a line are ignored.  rounds > 1 (the whole table only) feeds each round's output to the next and stops early
         once a round changes nothing (knn_refine_info()['updates'] == 0).  -> (ids [n,k] u64, keys [n,k] u64, counts [n] u32), knn_graph's
-        layout.  No forest needed."""
+        layout.  No forest needed.  reverse > 0: every round also ranks up to `reverse` sampled reverse neighbours of each row (the rows that
+        name it, knn_graph_reverse) and THEIR lists -- zh_knn_graph_refine_rev, in_k + reverse <= 64; knn_refine_rev_info() then describes the
+        call, and its 'updates' is the early stop.  reverse = 0 is today's call and path exactly."""
         in_ids, in_counts = (graph[0], graph[-1])
         in_ids = np.ascontiguousarray(in_ids, np.uint64)
         in_counts = np.ascontiguousarray(in_counts, np.uint32)
@@ -676,9 +678,15 @@ class LSHIndex:
             ids = np.empty((n, k), np.uint64)
             keys = np.empty((n, k), np.uint64)
             counts = np.zeros(n, np.uint32)
-            check(lib().zh_knn_graph_refine(self._h, _p(in_ids), _p(in_counts), in_ids.shape[1], int(first_row), n, k, metric.metric, metric.mode,
-                                            _p(ids), _p(keys), _p(counts)))
-            if rounds > 1 and (k == 0 or self.knn_refine_info()["updates"] == 0):
+            if reverse:
+                check(lib().zh_knn_graph_refine_rev(self._h, _p(in_ids), _p(in_counts), in_ids.shape[1], int(reverse), int(first_row), n, k, metric.metric,
+                                                    metric.mode, _p(ids), _p(keys), _p(counts)))
+                info = self.knn_refine_rev_info
+            else:
+                check(lib().zh_knn_graph_refine(self._h, _p(in_ids), _p(in_counts), in_ids.shape[1], int(first_row), n, k, metric.metric, metric.mode,
+                                                _p(ids), _p(keys), _p(counts)))
+                info = self.knn_refine_info
+            if rounds > 1 and (k == 0 or info()["updates"] == 0):
                 break
             in_ids, in_counts = ids, counts
         return ids, keys, counts
@@ -693,6 +701,43 @@ class LSHIndex:
         """what the most recent graph refinement call on this index did (zh_knn_graph_refine_info): rows_live, lines, in_k, k, listed, keyed,
         updates, launches"""
         return self._info(_ffi.KnnRefineInfo, lib().zh_knn_graph_refine_info)
+
+    def knn_graph_refine_rev_device(self, d_in_ids_ptr, d_in_counts_ptr, in_k, rev_k, k, metric, first_row, n, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream=None):
+        """knn_graph_refine_device with up to rev_k sampled reverse neighbours per row in the candidate set (rev_k = 0: the same answer)"""
+        check(lib().zh_knn_graph_refine_rev_device(self._h, d_in_ids_ptr, d_in_counts_ptr, int(in_k), int(rev_k), int(first_row), int(n), k, metric.metric,
+                                                   metric.mode, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream))
+
+    def knn_refine_rev_info(self):
+        """what the most recent knn_graph_refine(reverse > 0) / knn_graph_refine_rev_device call did (zh_knn_graph_refine_rev_info):
+        knn_refine_info's fields, then rev_k, edges, kept, max_degree"""
+        return self._info(_ffi.KnnRefineRevInfo, lib().zh_knn_graph_refine_rev_info)
+
+    def knn_graph_reverse(self, graph, rev_k, first_row=0, n=None):
+        """the capped reverse graph of a graph of ALL stored rows (`graph` as for knn_graph_refine): line i holds up to rev_k of the live rows that
+        name stored row first_row + i and that its own line does not name -- a deterministic pseudo-random sample by a hash of the pair, the same
+        whatever the order of entries, the run or the slab -> (ids [n, rev_k] u64 with tails 2^64-1, counts [n] u32, degree [n] u32: the uncapped
+        in-degree, the hubness score).  No metric, no keys, no forest."""
+        in_ids = np.ascontiguousarray(graph[0], np.uint64)
+        in_counts = np.ascontiguousarray(graph[-1], np.uint32)
+        stored = self.stored_rows()
+        if in_ids.ndim != 2 or in_counts.ndim != 1 or in_ids.shape[0] != stored or in_counts.shape[0] != stored:
+            raise _ffi.ZhError(_ffi.ZH_EINVAL, "knn_graph_reverse: the graph must cover the %d stored rows: ids [%d, in_k], counts [%d]" % (stored, stored, stored))
+        n = max(stored - first_row, 0) if n is None else int(n)
+        ids = np.empty((n, rev_k), np.uint64)
+        counts = np.zeros(n, np.uint32)
+        degree = np.zeros(n, np.uint32)
+        check(lib().zh_knn_graph_reverse(self._h, _p(in_ids), _p(in_counts), in_ids.shape[1], int(rev_k), int(first_row), n, _p(ids), _p(counts), _p(degree)))
+        return ids, counts, degree
+
+    def knn_graph_reverse_device(self, d_in_ids_ptr, d_in_counts_ptr, in_k, rev_k, first_row, n, d_ids_ptr, d_counts_ptr, d_degree_ptr, stream=None):
+        """knn_graph_reverse with the graph and the outputs ([n, rev_k] u64, [n] u32 twice) already in device memory (raw pointers)"""
+        check(lib().zh_knn_graph_reverse_device(self._h, d_in_ids_ptr, d_in_counts_ptr, int(in_k), int(rev_k), int(first_row), int(n), d_ids_ptr, d_counts_ptr,
+                                                d_degree_ptr, stream))
+
+    def knn_reverse_info(self):
+        """what the most recent knn_graph_reverse call on this index did (zh_knn_graph_reverse_info): rows_live, lines, in_k, rev_k, edges, kept,
+        max_degree, launches"""
+        return self._info(_ffi.KnnReverseInfo, lib().zh_knn_graph_reverse_info)
 
     def deduplicate_within(self, radius, metric):
         """near-duplicate removal: rows are taken in ascending id, and row b is removed exactly when some KEPT row a < b forms a joined pair
@@ -1111,13 +1156,13 @@ class Database:
             return {}
         return self._graph_documents(*self.index.knn_graph_forest(k, self.metric))
 
-    def knn_graph_refined(self, k, rounds=1):
+    def knn_graph_refined(self, k, rounds=1, reverse=0):
         """knn_graph_forest, then `rounds` rounds of LSHIndex.knn_graph_refine (each row's neighbours' neighbours, until a round changes
-        nothing) -> what knn_graph returns"""
+        nothing; reverse > 0: with that many sampled reverse neighbours per row as well) -> what knn_graph returns"""
         if self.index.no_vectors():
             return {}
         graph = self.index.knn_graph_forest(k, self.metric)
-        return self._graph_documents(*self.index.knn_graph_refine(graph, k, self.metric, rounds=rounds))
+        return self._graph_documents(*self.index.knn_graph_refine(graph, k, self.metric, rounds=rounds, reverse=reverse))
 
     def _graph_documents(self, ids, keys, counts):
         dist = self._key_numbers(np.ascontiguousarray(keys)).reshape(keys.shape)

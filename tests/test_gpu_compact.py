@@ -321,6 +321,80 @@ def test_forest_d128_leaf_half(za, monkeypatch, kind):
     cx.close()
 
 
+def small_leaf_lifecycle(za, seed):
+    """The small-leaf regime's views -- row norms, per-plane norms, leaf meta, the blocked walk view -- are built, then the rows under them are
+    removed, moved (compact) and replaced (clear + a refill to the same count).  After every search: the oracle on the index's own forest, and a
+    twin that never held the views (built fresh over the same stored rows, the same forest injected: no sample rows, so no row scores, no norms,
+    no leaf meta, and a first batch, so no blocked view).  -> (hash_from_scores, prefiltered) of every search, in order"""
+    n, d, M, T, B, k = 3000, 64, 5, 4, 24, 10
+    m = za.L2SquaredDistance()
+    X = zo.synth_rows(n, d, seed=0x5EB2CC00)
+    Q = zo.synth_queries(B, d, n, seed_rows=0x5EB2CC00)
+    ix = za.LSHIndex(d, za.LSHIndexOptions(M, T), device=0)
+    ix.add(X)  # (a forest of the library's own: the planes' sample rows are known)
+    ix.set_hash_mode("scores")
+    seen = []
+
+    def search(rows, queries, what):
+        fa = ix.get_forest()
+        ids, keys, counts = ix.search_batch(queries, k, m)
+        st = ix.stats()
+        seen.append((int(st["hash_from_scores"]), int(st["prefiltered"])))
+        tw = za.LSHIndex(d, za.LSHIndexOptions(M, T), device=0)
+        tw.append(rows)
+        tw.set_forest(fa)
+        ti, tk, tc = tw.search_batch(queries, k, m)
+        tw.close()
+        oi, ok, oc = zo.Forest.from_arrays(rows, M, fa).search_batch(queries, k, zo.L2SQ, 0)
+        assert (counts == oc).all() and (counts == tc).all(), what
+        for b in range(B):
+            c = int(oc[b])
+            assert (ids[b, :c] == oi[b, :c]).all() and (keys[b, :c] == ok[b, :c]).all(), (what, "oracle", b)
+            assert (ids[b, :c] == ti[b, :c]).all() and (keys[b, :c] == tk[b, :c]).all(), (what, "twin", b)
+
+    for it in range(4):  # (the blocked view is built from the third batch on; the prefilter needs the norms and the leaf meta)
+        search(X, Q, ("built", it))
+    alive = pattern("random10", n, np.random.default_rng(seed))
+    gone = np.flatnonzero(~alive).astype(np.uint64)
+    assert len(ix.remove(gone)) == len(gone)
+    search(X, Q, "removed")  # (the removed rows are still stored; no leaf lists them)
+    new_ids, info = ix.compact()
+    assert (new_ids == expected_map(alive)).all() and info["rows_after"] == int(alive.sum())
+    for it in range(4):
+        search(X[alive], Q, ("compacted", it))
+    ix.clear()
+    X2 = zo.synth_rows(n, d, seed=0x5EB2CC01)  # different rows, the same count
+    assert X2.tobytes() != X.tobytes()
+    ix.add(X2)
+    Q2 = zo.synth_queries(B, d, n, seed_rows=0x5EB2CC01)
+    for it in range(4):
+        search(X2, Q2, ("refilled", it))
+    ix.close()
+    return seen
+
+
+# (hash_from_scores, prefiltered) of the thirteen searches as the library reported them before the index's derived views were gathered into one
+# record each: four on the built index, one after the removal, four after the compaction, four after clear + refill.  After the compaction the
+# value depends on whether some plane's sample row was among the removed rows (then the index has no row scores until its forest is rebuilt).
+# At this shape the ~4,800 planes name most of the 3,000 rows as samples: removal seeds 0 .. 5 all lose one, so that is the one case listed.
+SMALL_LEAF_SEEN = {
+    0: [(1, 1)] * 5 + [(0, 0)] * 4 + [(1, 1)] * 4,
+}
+
+
+@pytest.mark.parametrize("seed", sorted(SMALL_LEAF_SEEN))
+@pytest.mark.parametrize("view", [None, "inner"])
+def test_small_leaf_views_across_compact_and_refill(za, monkeypatch, view, seed):
+    chunking(monkeypatch, None)
+    if view:
+        monkeypatch.setenv("ZH_WALK_BLOCKS", view)
+    else:
+        monkeypatch.delenv("ZH_WALK_BLOCKS", raising=False)
+    seen = small_leaf_lifecycle(za, seed)
+    print("small-leaf lifecycle, view %s seed %d: %s" % (view, seed, seen))
+    assert seen == SMALL_LEAF_SEEN[seed]
+
+
 # ------------------------------------------------------------------------------------------------------------------ 4. exact search
 def test_exact_all_metrics_after_compaction(za, monkeypatch):
     chunking(monkeypatch, 64)

@@ -196,68 +196,124 @@ struct zh_index {
     std::vector<uint32_t> h_leaf_ids;          // host mirror of leaf_ids, materialised by the first incremental add
     std::vector<uint8_t> h_dead;               // rows removed by zh_index_remove (their vectors stay in X)
     uint64_t n_dead = 0;
-    std::vector<uint32_t> h_live;              // ascending live rows, for hyperplane sampling once rows were removed
-    uint64_t h_live_rows = ~0ull;              // n_rows / n_dead / dead_gen h_live was built for
-    uint64_t h_live_dead = ~0ull;
-    uint64_t h_live_gen = ~0ull;
     // Caches derived from the stored rows are keyed on a generation as well as on a count: clear() followed by a refill to the
-    // same count must not find them valid.  rows_gen: bumped whenever the CONTENT of rows [0, n_rows) may have changed (clear);
-    // dead_gen: whenever the set of removed rows changed (remove, clear).
+    // same count must not find them valid.  rows_gen: bumped whenever the CONTENT of rows [0, n_rows) may have changed (clear, compact);
+    // dead_gen: whenever the set of removed rows changed (remove, clear, compact).  Both start at 1: a stamp of generation 0 names no table.
     uint64_t rows_gen = 1, dead_gen = 1;
     uint32_t max_leaf_len = 0;
-    // blocked view of the forest (ZhBlocksDev) for all-dense walks: built on first use, dropped whenever the trees change
-    DevBuf blk_recs, blk_upper, blk_roots;
-    uint32_t n_blocks = 0, n_upper = 0;
-    bool blocks_valid = false;
-    bool blocks_inner = false;  // the view holds blocks of INNER nodes only (round 5; ZhBlocksDev::inner_only)
-    size_t blk_recs_b = 0;      // ... whose records' second halves start at this index of blk_recs
     std::mutex blk_mu;
-    // row -> (leaf, position) per tree for the table-scan sweep (zh_launch_row_leaf): built on first use, dropped with the trees
-    DevBuf row_leaf;
-    bool row_leaf_valid = false, row_leaf_failed = false;
-    // Both derived views cost host time per build (a traversal of every node: ~0.35 s for the 13M nodes of a 1M-row forest at the
-    // default leaf size), so a forest that changes between searches (insert, search, insert, ...) keeps the pointer walk / the
-    // leaf-major sweep: the views are built once the forest has served a few batches unchanged.
-    std::atomic<uint32_t> batches_since_change{0};
+
+    // ---------------------------------------------------------------------------------------------------------------------------------------
+    // Derived views of the rows and the forest: built lazily, one record each -- its buffers, its state, the ONE place its "is it current" test
+    // is written, and how it is marked and dropped.  What every mutation does to every view is the event routines below the struct
+    // (views_trees_dropped ...; the table is in DESIGN.md s4): nothing else assigns a view's state.
+    // The rule for the state: whatever the per-batch choices and the two halves of a batch read WITHOUT a lock (ctx_begin, ctx_finish, choose_scan,
+    // use_approx, use_approx_leaf, mfma_wanted, use_score_hash, use_prefilter, launch_score_hash) is a std::atomic -- another context may be
+    // building the view under blk_mu at that moment.  The buffers themselves are only touched under blk_mu (or under `mu` held exclusively).
+    // ---------------------------------------------------------------------------------------------------------------------------------------
+    struct Stamp {  // "built for which rows": their count and the generation of their content (or, for the live-row lists, of the removed set)
+        std::atomic<uint64_t> rows{0}, gen{0};
+        bool is(uint64_t r, uint64_t g) const { return rows == r && gen == g; }
+        void set(uint64_t r, uint64_t g) { rows = r; gen = g; }
+    };
+    // blocked view of the forest (ZhBlocksDev) for all-dense walks: built on first use, not valid once the trees change
+    struct BlocksView {
+        DevBuf recs, upper, roots;
+        std::atomic<uint32_t> n_blocks{0}, n_upper{0};
+        std::atomic<bool> valid{false};
+        std::atomic<bool> inner{false};   // the view holds blocks of INNER nodes only (round 5; ZhBlocksDev::inner_only)
+        std::atomic<size_t> recs_b{0};    // ... whose records' second halves start at this index of recs
+        void mark_built(uint32_t blocks, uint32_t uppers, bool inner_only, size_t second_halves) {
+            n_blocks = blocks; n_upper = uppers; inner = inner_only; recs_b = second_halves; valid = true;
+        }
+        void invalidate() { valid = false; }  // (the buffers stay for the next build)
+        void drop() { recs.release(); upper.release(); roots.release(); n_blocks = 0; n_upper = 0; inner = false; recs_b = 0; valid = false; }
+    } blocks;
+    // row -> (leaf, position) per tree for the table-scan sweep (zh_launch_row_leaf): built on first use, for the trees and the stored rows of that
+    // moment (rows appended since are in no tree yet, but must not be scanned past it); a failed allocation is remembered until the trees change
+    struct RowLeafView {
+        DevBuf table;
+        std::atomic<bool> valid{false}, failed{false};
+        std::atomic<uint64_t> rows{0};  // stored rows the table was built for (read only where valid)
+        uint64_t version = 0;           // counts the builds (never reset): ScanOrder's gathered copy names the one it was made from
+        bool current(const zh_index *ix) const { return valid && rows == ix->n_rows; }
+        void mark_built(uint64_t n) { valid = true; rows = n; version++; }
+        void mark_failed() { failed = true; }
+        void invalidate() { valid = false; failed = false; }  // (the trees changed: the table is stale, and a failed allocation gets another try)
+        void drop() { table.release(); invalidate(); }
+    } row_leaf;
     // the MFMA table scan's view of the stored rows (zh_launch_row_half): their fp16 copy in the A operand's order (2 * d bytes per row), per
-    // row {|x|^2, 1 / scale}, and the largest relative rounding error of any row; for rows [0, scale_rows) of generation scale_gen,
-    // extended when rows are appended; a failed allocation is remembered until the rows change (the VALU kernel serves the index)
-    DevBuf row_half, row_meta, row_rho_dev;
-    // (the flags and generations below are read without a lock by the per-batch choices -- mfma_wanted, choose_scan, use_approx_leaf -- while another
-    // context may be inside ensure_row_half / ensure_row_half128 under blk_mu: atomics; the buffers themselves are only touched under blk_mu)
-    std::atomic<bool> row_half_failed{false};
-    // d = 128, leaf by leaf at half width (sweep128h_kernel): a row-major fp16 copy under ONE power-of-two scale (2^(14 - h128_ex)), same life cycle
-    DevBuf row_half128;
-    std::atomic<uint64_t> h128_rows{0}, h128_gen{0};
-    int h128_ex = 0;
-    float h128_rho = 0.f;
-    std::atomic<bool> h128_failed{false};
-    // ... or, for a table of integers 0 .. 255 (SIFT descriptors), an EXACT copy of 128 bytes per row in the same buffer (row_byte128_kernel):
-    // h128_bytes = the current copy is that one; h128_not_bytes = some stored row is known not to qualify (until the rows are replaced)
-    bool h128_bytes = false, h128_not_bytes = false;
-    std::atomic<uint64_t> scale_rows{0}, scale_gen{0};
-    float row_rho = 0.f;
+    // row {|x|^2, 1 / scale}, and the largest relative rounding error of any row; for the rows `at` names, extended when rows are appended; a
+    // failed allocation is remembered until the rows change (the VALU kernel serves the index).  tiles released and meta kept: the per-row scales
+    // alone (scan_mfma_kernel<D, true> converts the f32 rows itself).  rho_dev: the builders' few words of device scratch (RowHalf128View's too).
+    struct RowHalfView {
+        DevBuf tiles, meta, rho_dev;
+        Stamp at;
+        std::atomic<bool> failed{false};
+        std::atomic<float> rho{0.f};
+        bool current(const zh_index *ix) const { return at.is(ix->n_rows, ix->rows_gen); }   // made -- or found impossible -- for the rows stored now
+        bool known_failed(const zh_index *ix) const { return failed && current(ix); }
+        void mark_built(const zh_index *ix, float r) { rho = r; at.set(ix->n_rows, ix->rows_gen); }
+        void mark_failed(const zh_index *ix) { failed = true; at.set(ix->n_rows, ix->rows_gen); }
+        void retry() { failed = false; }
+        void remake() { at.gen = 0; }  // (the copy is made again from row 0 by the next batch that wants it; `rows` and the buffers stay)
+        void drop() { at.set(0, 0); rho = 0.f; tiles.release(); meta.release(); failed = false; }  // (rho_dev goes with the index)
+    } half;
     // Round 5 (VERDICT r4 #4b): the matrix-core scan's OWN view of the rows -- the fp16 tiles, their {|x|^2, 1 / scale} and the row -> leaf entries --
-    // is kept sorted by (leaf in tree 0, leaf in tree 1, leaf in tree 2, id): position p holds row scan_perm[p] (zh_order.hip).  The scan never needs
+    // is kept sorted by (leaf in tree 0, leaf in tree 1, leaf in tree 2, id): position p holds row perm[p] (zh_order.hip).  The scan never needs
     // a row's id (its outputs go to key slots that the row -> leaf entries name), so nothing else changes; a wave's 16 rows then share tree 0's leaf --
     // its visitors are ONE tile column each for all 16 -- and, on data with structure, most other trees' too, whatever order the rows were inserted
     // in.  Made with the copy, from the row -> leaf table; rows appended later keep position = id; the f32 rows and every other kernel stay in id
-    // order.  row_leaf_p = the row -> leaf table gathered into that order (for row_leaf generation row_leaf_p_gen).
-    DevBuf scan_perm, row_leaf_p;
-    bool row_order_off = false;
-    uint32_t order_keys = 0;   // trees whose leaves the kept order sorts by (0: id order)
-    double order_worth = 0;    // share of (adjacent positions, tree) combinations in the same leaf under the kept order
-    uint64_t perm_rows = 0, row_leaf_gen = 0, row_leaf_p_gen = 0, perm_gen = 0, row_leaf_p_perm = 0;
-    uint64_t row_leaf_rows = 0;  // stored rows the table was built for (rows appended since are in no tree yet, but must not be scanned past it)
+    // order.  row_leaf_p = the row -> leaf table gathered into that order: for build p_table of RowLeafView and order p_order.  All under blk_mu.
+    struct ScanOrder {
+        DevBuf perm, row_leaf_p;
+        bool off = false;       // given up for lack of room: id order until the trees or the table are replaced
+        uint32_t keys = 0;      // trees whose leaves the kept order sorts by (0: id order)
+        double worth = 0;       // share of (adjacent positions, tree) combinations in the same leaf under the kept order
+        uint64_t rows = 0;      // rows the order covers (0: id order -- it won, there is no table, the order is off, or there was no room for the sort)
+        uint64_t version = 0;   // counts the orders made and given up (never reset)
+        uint64_t p_table = 0, p_order = 0;
+        bool table_current(const RowLeafView &rl) const { return p_table == rl.version && p_order == version; }
+        void mark_table(const RowLeafView &rl) { p_table = rl.version; p_order = version; }
+        void begin() { rows = 0; version++; keys = 0; }  // (id order, until mark_built says otherwise)
+        void mark_built(uint32_t k, double w, uint64_t n) { keys = k; worth = w; if (k) rows = n; }
+        void no_room_for_table() { rows = 0; }
+        void switch_off() { off = true; }
+        void allow() { off = false; }
+        bool used() const { return rows || keys; }
+        void drop() { rows = 0; version++; perm.release(); row_leaf_p.release(); }  // (keys, worth and off stay: DESIGN.md s4, "kept as found")
+    } order;
+    // d = 128, leaf by leaf at half width (sweep128h_kernel): a row-major fp16 copy under ONE power-of-two scale (2^(14 - ex)), same life cycle as
+    // RowHalfView's ... or, for a table of integers 0 .. 255 (SIFT descriptors), an EXACT copy of 128 bytes per row in the same buffer
+    // (row_byte128_kernel): bytes = the current copy is that one; not_bytes = some stored row is known not to qualify (until the rows are replaced)
+    struct RowHalf128View {
+        DevBuf copy;
+        Stamp at;
+        std::atomic<int> ex{0};
+        std::atomic<float> rho{0.f};
+        std::atomic<bool> failed{false};
+        bool bytes = false, not_bytes = false;  // (blk_mu)
+        bool current(const zh_index *ix) const { return at.is(ix->n_rows, ix->rows_gen); }
+        bool known_failed(const zh_index *ix) const { return failed && current(ix); }
+        uint64_t extend_from(const zh_index *ix, bool as_bytes) const {  // first row a copy of that kind still lacks (0: made from scratch)
+            return at.gen == ix->rows_gen && at.rows <= ix->n_rows && bytes == as_bytes ? at.rows.load() : 0;
+        }
+        void set_scale(int e) { ex = e; }  // (of a copy of halves about to be made from the first row)
+        void mark_bytes(const zh_index *ix) { bytes = true; rho = 0.f; ex = 14; at.set(ix->n_rows, ix->rows_gen); }
+        void mark_halves(const zh_index *ix, float r) { rho = r; bytes = false; at.set(ix->n_rows, ix->rows_gen); }
+        void mark_failed(const zh_index *ix) { failed = true; bytes = false; at.set(ix->n_rows, ix->rows_gen); }
+        void retry() { failed = false; }
+        void found_not_bytes() { not_bytes = true; bytes = false; at.gen = 0; }  // the copy of halves, from the first row, now and from now on
+        void drop() { at.set(0, 0); rho = 0.f; copy.release(); failed = false; bytes = false; }  // (not_bytes and ex stay: see the events)
+    } half128;
 
     // the blocking entry points run on this context (under `mu`); staging buffers of the host-pointer variant
     zh_search_ctx dctx;
     DevBuf wQ, wOutIds, wOutKeys, wOutCounts;
-    // the exact search (zh_search_exact_*, zh_exact.hip): scratch of its own, so that pipelined search contexts are never touched; the
-    // ascending live rows on the device for (ex_live_rows, ex_live_gen) = (n_rows, dead_gen) -- removed rows are never scored
-    DevBuf ex_live, ex_bits, ex_QQ, ex_keys, ex_visits, ex_cbase, ex_ckeys, ex_cids, ex_run_ids, ex_run_keys, ex_run_counts, ex_Q, ex_ids, ex_kout, ex_counts,
+    // the exact search (zh_search_exact_*, zh_exact.hip): scratch of its own, so that pipelined search contexts are never touched (its live rows
+    // on the device: LiveRowsDev below)
+    DevBuf ex_QQ, ex_keys, ex_visits, ex_cbase, ex_ckeys, ex_cids, ex_run_ids, ex_run_keys, ex_run_counts, ex_Q, ex_ids, ex_kout, ex_counts,
         ex_Qh, ex_qmeta, ex_tau, ex_cnt, ex_lid, ex_llo, ex_lhi, ex_scr, ex_over;
-    uint64_t ex_live_rows = ~0ull, ex_live_gen = ~0ull, ex_n_live = 0;
     zh_exact_info ex_info{};  // (stats_mu)
     // the filtered exact search's per-call scratch (all released before the call returns): the caller's filter, allowed AND live by row and by
     // position of the scan's row order, the blocks' counts and their exclusive sums, the ascending list of allowed live rows
@@ -314,35 +370,94 @@ struct zh_index {
     int dense_levels = -1;
     bool debug_keep_raw = false;  // zh_debug_keep_raw
     std::atomic<int> sweep_mode{0};  // zh_set_sweep_mode (atomic: set by one thread while pipelined contexts read it per batch): 0 cost model (prefilter where the batch has row scores), 1 leaf-major, 2 table scan (exact), 3 = 0, 4 table scan with half-width queries wherever it applies, 5 = 4 with the VALU kernel only (no fp16 copy of the rows)
-    // a batch whose half-width scan ran over was redone by the f32 scan: both scans paid.  Data whose keys are dense around the cut (the
-    // parity cosine key on iid rows in 20k-row leaves: thousands of rows per query inside the bound) would do so batch after batch:
-    // after the first such batch -- or one whose lists came close -- the per-query lists get 8192 slots instead of 4096 (a final
-    // kernel with twice the LDS); after the second the index keeps the f32 scan until its trees change
-    std::atomic<uint32_t> approx_strikes{0};
-    // the matrix-core scan on f32 rows (no fp16 copy) rounds the rows as well: wider intervals, longer lists.  Lists that run over at 8192 slots send the
-    // index back to the VALU half-width scan (which rounds the queries only) instead of all the way to the f32 scan
-    std::atomic<bool> mfma_f32_off{false};
-    // ... and a FUSED d = 128 sweep whose lists ran over (it hands on what the bounds known at the time cannot rule out: more than the select pass's exact
-    // per-visit bounds would) goes back to the unfused half-width sweep first, not to the f32 sweep
-    std::atomic<bool> fused_off{false};
     int hash_mode = 0;   // zh_set_hash_mode: 0 chosen per batch, 1 one dot product per plane, 2 row scores where the forest allows
     // the two sample rows of every plane (build_hyperplane, lsh.rs:197-225), kept for forests this library built or grew: the
     // row-score hash derives signs from them.  An injected forest (zh_index_set_forest) has arbitrary planes: not valid.
-    DevBuf plane_samples;
-    bool samples_valid = false;
-    DevBuf row_hn2, row_norm;  // |r|^2 / 2 and |r| of the stored rows, for the first norm_rows rows of generation norm_gen
-    uint64_t norm_rows = 0, norm_gen = 0;
-    DevBuf plane_hab;          // the same per PLANE (its two sample rows), for the first hab_planes planes at (hab_rows, hab_gen)
-    uint32_t hab_planes = 0;
-    uint64_t hab_rows = 0, hab_gen = 0;
-    // {|r|^2/2, |r|} of the row in every slot of leaf_ids, for the prefilter: built on first use from the norms of (meta_rows,
-    // meta_gen), dropped with the trees
-    DevBuf leaf_meta;
-    bool leaf_meta_valid = false;
-    uint64_t meta_rows = 0, meta_gen = 0;
-    // batches in a row that the prefilter handed back to the sweep (a list ran over: rows the bound cannot tell apart, many long
-    // leaves): after two the forest is swept until it changes -- such data would pay for both every batch
-    std::atomic<uint32_t> prefilter_strikes{0};
+    struct PlaneSamples {
+        DevBuf pairs;
+        std::atomic<bool> valid{false};
+        void mark(bool known) { valid = known; }
+        void drop() { pairs.release(); valid = false; }
+    } samples;
+    // |r|^2 / 2 and |r| of the stored rows
+    struct RowNorms {
+        DevBuf hn2, norm;
+        Stamp at;
+        bool current(const zh_index *ix) const { return at.is(ix->n_rows, ix->rows_gen); }  // (rows added, or replaced, since they were taken?)
+        void mark_built(const zh_index *ix) { at.set(ix->n_rows, ix->rows_gen); }
+        void drop() { at.set(0, 0); hn2.release(); norm.release(); }
+    } norms;
+    // ... the same per PLANE (its two sample rows): for the first `planes` planes, from the norms of stamp `of`
+    struct PlaneNorms {
+        DevBuf hab;
+        std::atomic<uint32_t> planes{0};
+        Stamp of;
+        bool current(const zh_index *ix) const { return planes == ix->n_planes && of.is(ix->norms.at.rows, ix->norms.at.gen); }  // (planes added, or the norms retaken?)
+        void mark_built(const zh_index *ix) { planes = ix->n_planes; of.set(ix->norms.at.rows, ix->norms.at.gen); }
+        void forget() { planes = 0; of.set(0, 0); }  // (the buffer stays for the next build)
+        void drop() { hab.release(); forget(); }
+    } plane_norms;
+    // {|r|^2/2, |r|} of the row in every slot of leaf_ids, for the prefilter: built on first use from the norms of stamp `of`, for the trees of
+    // that moment
+    struct LeafMeta {
+        DevBuf slots;
+        std::atomic<bool> valid{false};
+        Stamp of;
+        bool current(const zh_index *ix) const { return valid && of.is(ix->norms.at.rows, ix->norms.at.gen); }
+        void mark_built(const zh_index *ix) { valid = true; of.set(ix->norms.at.rows, ix->norms.at.gen); }
+        void invalidate() { valid = false; }  // (the buffer stays for the next build)
+        void drop() { slots.release(); valid = false; }
+    } leaf_meta;
+    // ascending live rows on the host, for hyperplane sampling once rows were removed: for (n_rows, dead_gen) and n_dead (under mu, exclusive)
+    struct LiveRowsHost {
+        std::vector<uint32_t> rows;
+        Stamp at;
+        uint64_t dead = 0;
+        bool current(const zh_index *ix) const { return at.is(ix->n_rows, ix->dead_gen) && dead == ix->n_dead; }
+        void mark_built(const zh_index *ix) { at.set(ix->n_rows, ix->dead_gen); dead = ix->n_dead; }
+        void drop() { rows.clear(); rows.shrink_to_fit(); at.set(0, 0); dead = 0; }
+    } live_host;
+    // ... and on the device, as a list (path 1) and as a bitmap (path 2), for the exact family -- removed rows are never scored: for
+    // (n_rows, dead_gen) (under mu, exclusive).  They survive every call; remove, clear and append leave the buffers to be refilled.
+    struct LiveRowsDev {
+        DevBuf rows, bits;
+        Stamp at;
+        uint64_t n_live = 0;  // (read only after exact_live_rows made the lists current)
+        bool current(const zh_index *ix) const { return at.is(ix->n_rows, ix->dead_gen); }
+        void mark_built(const zh_index *ix, uint64_t n) { n_live = n; at.set(ix->n_rows, ix->dead_gen); }
+        void drop() { at.set(0, 0); rows.release(); bits.release(); }
+    } live_dev;
+    // What the index remembers of paths that did not pay on its data, and how long its forest has stood.
+    struct Fallbacks {
+        // Both derived views of the forest cost host time per build (a traversal of every node: ~0.35 s for the 13M nodes of a 1M-row forest at the
+        // default leaf size), so a forest that changes between searches (insert, search, insert, ...) keeps the pointer walk / the
+        // leaf-major sweep: the views are built once the forest has served a few batches unchanged.
+        std::atomic<uint32_t> batches_since_change{0};
+        // batches in a row that the prefilter handed back to the sweep (a list ran over: rows the bound cannot tell apart, many long
+        // leaves): after two the forest is swept until it changes -- such data would pay for both every batch
+        std::atomic<uint32_t> prefilter_strikes{0};
+        // a batch whose half-width scan ran over was redone by the f32 scan: both scans paid.  Data whose keys are dense around the cut (the
+        // parity cosine key on iid rows in 20k-row leaves: thousands of rows per query inside the bound) would do so batch after batch:
+        // after the first such batch -- or one whose lists came close -- the per-query lists get 8192 slots instead of 4096 (a final
+        // kernel with twice the LDS); after the second the index keeps the f32 scan until its trees change
+        std::atomic<uint32_t> approx_strikes{0};
+        // the matrix-core scan on f32 rows (no fp16 copy) rounds the rows as well: wider intervals, longer lists.  Lists that run over at 8192 slots send the
+        // index back to the VALU half-width scan (which rounds the queries only) instead of all the way to the f32 scan
+        std::atomic<bool> mfma_f32_off{false};
+        // ... and a FUSED d = 128 sweep whose lists ran over (it hands on what the bounds known at the time cannot rule out: more than the select pass's exact
+        // per-visit bounds would) goes back to the unfused half-width sweep first, not to the f32 sweep
+        std::atomic<bool> fused_off{false};
+        void prefilter_ran_over() { prefilter_strikes.fetch_add(1); }
+        void prefilter_held() { prefilter_strikes = 0; }
+        void approx_ran_over(bool mfma_on_f32_rows, bool fused_leaf) {
+            if (mfma_on_f32_rows && approx_strikes.load() >= 1) mfma_f32_off = true;  // (8192-slot lists ran over: the VALU scan next)
+            else if (fused_leaf && !fused_off) fused_off = true;                     // (the fused sweep's lists ran over: the select pass next)
+            else approx_strikes.fetch_add(1);
+        }
+        void approx_nearly_ran_over() { approx_strikes.fetch_add(1); }
+        void new_trees() { prefilter_strikes = 0; approx_strikes = 0; mfma_f32_off = false; fused_off = false; }  // (they were measured on the old ones)
+        void trees_settle_again() { batches_since_change = 0; }
+    } fb;
     bool scan_unsafe = false;  // an injected forest lists a row twice in one tree: rowLeaf holds one slot per (row, tree) -> leaf-major only
     double visits_per_pair = 0;  // leaf visits per (query, tree) pair, running mean over the batches so far (stats_mu)
     int profiling = 0;
@@ -393,6 +508,77 @@ struct zh_index {
     size_t clast = 0;       // callers served by the previous round
     Lane lanes[1];
 };
+
+// ------------------------------------------------------------------------------------------------
+// What each mutation of the index does to its derived views: one routine per event, every view it touches named in it (DESIGN.md s4 has the
+// same as a table).  The callers hold `mu` exclusively.  A view that is not named keeps its state through the event.
+// ------------------------------------------------------------------------------------------------
+// the fp16 copies' device bytes (zh_stats, zh_compact_info): the tiles and per-row scales, the d = 128 copy, the scan's row order and its view
+// of row -> leaf (under blk_mu)
+static uint64_t row_copy_bytes(const zh_index *ix) {
+    return ix->half.tiles.cap + ix->half.meta.cap + ix->half128.copy.cap + ix->order.perm.cap + ix->order.row_leaf_p.cap;
+}
+
+// The trees are gone (before a build, a set_forest, a load; clear; destroy).
+static void views_trees_dropped(zh_index *ix) {
+    ix->blocks.drop();
+    ix->leaf_meta.drop();
+    ix->fb.new_trees();  // (batches_since_change is not reset here: upload_nodes, which every new forest goes through, does it)
+    ix->row_leaf.drop();
+    {
+        // the matrix-core scan's row order was measured on THIS forest's leaves: the next half-width batch re-makes the copy in the new forest's
+        // order, and an order given up for lack of room gets another chance.  A copy in id order is as good under the next forest.
+        std::lock_guard<std::mutex> lb(ix->blk_mu);
+        if (ix->order.used()) ix->half.remake();
+        ix->order.allow();
+    }
+    ix->samples.drop();
+    ix->plane_norms.drop();
+}
+
+// The trees changed in place or were just uploaded (build, set_forest, load, every incremental add and remove: the tail of upload_nodes).  The
+// views' buffers stay -- the next build of each reuses them.
+static void views_trees_changed(zh_index *ix) {
+    ix->blocks.invalidate();
+    ix->leaf_meta.invalidate();
+    ix->fb.new_trees();
+    ix->row_leaf.invalidate();
+    ix->fb.trees_settle_again();  // (the forest's views wait until it has served a few batches unchanged)
+}
+
+// The table was emptied (zh_index_clear, after views_trees_dropped and after rows_gen and dead_gen were bumped): everything derived from the
+// rows that were just dropped.  (The row norms and the sampler's live rows were once keyed on counts alone: a refill to the same count found
+// them "valid".)  LiveRowsDev is not named: dead_gen moved, so its stamp is stale, and its buffers are refilled in place.
+static void views_table_emptied(zh_index *ix) {
+    ix->norms.drop();
+    std::lock_guard<std::mutex> lb(ix->blk_mu);  // (the fp16 copies' state is blk_mu's: zh_stats reads it under that lock)
+    ix->half.drop();
+    ix->order.drop();
+    ix->order.allow();  // (a new table gets a new chance at the scan's row order)
+    ix->half128.drop();
+    ix->half128.not_bytes = false;  // (the row that was not of bytes went with the others)
+    ix->live_host.drop();
+}
+
+// The rows moved (zh_index_compact, after rows_gen and dead_gen were bumped): the trees stand, with their leaf ids renumbered.  lost_sample: some
+// plane's sample row was among the removed.  -> the device bytes of the fp16 copies that were released.
+static uint64_t views_rows_moved(zh_index *ix, bool lost_sample) {
+    ix->live_host.drop();
+    ix->live_dev.drop();  // (the buffers too: they were sized by the old row count; re-made by the next exact search)
+    ix->norms.drop();
+    ix->plane_norms.forget();
+    if (lost_sample) ix->samples.mark(false);  // (no row scores for that plane's sign until the forest is rebuilt)
+    ix->leaf_meta.drop();
+    ix->row_leaf.drop();
+    ix->row_leaf.rows = 0;
+    std::lock_guard<std::mutex> lb(ix->blk_mu);  // (the fp16 copies' state is blk_mu's: zh_stats reads it under that lock)
+    ix->blocks.invalidate();
+    const uint64_t released = row_copy_bytes(ix);
+    ix->half.drop();
+    ix->order.drop();    // (order.off stays: DESIGN.md s4, "kept as found")
+    ix->half128.drop();  // (not_bytes stays: a table with a row that is not of bytes still has one, or lost it and finds out when the copy is next made)
+    return released;
+}
 
 static const char *const k_torn_msg = "an earlier zh_index_compact failed after rows had begun to move: the stored rows are inconsistent; "
                                       "zh_index_clear the index and store them again";
@@ -499,19 +685,8 @@ extern "C" int zh_index_create(const zh_options *opt, zh_index **out) {
 static void free_forest(zh_index *ix) {
     ix->node_plane.release(); ix->node_left.release(); ix->node_right.release(); ix->node_pack.release(); ix->roots.release();
     ix->planes.release(); ix->consts.release(); ix->leaf_ids.release();
-    ix->blk_recs.release(); ix->blk_upper.release(); ix->blk_roots.release();
-    ix->n_blocks = 0; ix->blocks_valid = false;
-    ix->leaf_meta.release(); ix->leaf_meta_valid = false; ix->prefilter_strikes = 0; ix->approx_strikes = 0; ix->mfma_f32_off = false; ix->fused_off = false;
-    ix->row_leaf.release(); ix->row_leaf_valid = false; ix->row_leaf_failed = false; ix->scan_unsafe = false;
-    {
-        // the matrix-core scan's row order was measured on THIS forest's leaves: the next half-width batch re-makes the copy in the new forest's
-        // order, and an order given up for lack of room gets another chance
-        std::lock_guard<std::mutex> lb(ix->blk_mu);
-        if (ix->perm_rows || ix->order_keys) ix->scale_gen = 0;
-        ix->row_order_off = false;
-    }
-    ix->plane_samples.release(); ix->samples_valid = false;
-    ix->plane_hab.release(); ix->hab_planes = 0; ix->hab_rows = 0; ix->hab_gen = 0;
+    views_trees_dropped(ix);
+    ix->scan_unsafe = false;  // (a property of the forest that is going, not of a view: set_forest and load say what the next one is)
     ix->n_nodes = ix->n_planes = ix->n_trees = 0;
     ix->n_leaf_ids = 0;
     ix->h_plane.clear(); ix->h_left.clear(); ix->h_right.clear(); ix->h_roots.clear();
@@ -546,10 +721,9 @@ extern "C" void zh_index_destroy(zh_index *ix) {
     if (ix->sweep_stream) hipStreamSynchronize(ix->sweep_stream);
     free_forest(ix);
     ix->X.release();
-    ix->row_hn2.release(); ix->row_norm.release(); ix->row_half.release(); ix->row_meta.release(); ix->row_rho_dev.release(); ix->row_half128.release();
-    ix->scan_perm.release(); ix->row_leaf_p.release();
+    ix->norms.drop(); ix->half.drop(); ix->half.rho_dev.release(); ix->half128.drop(); ix->order.drop(); ix->live_dev.drop();
     ix->dctx.release_all();
-    DevBuf *ws[] = {&ix->wQ, &ix->wOutIds, &ix->wOutKeys, &ix->wOutCounts, &ix->ex_live, &ix->ex_bits};
+    DevBuf *ws[] = {&ix->wQ, &ix->wOutIds, &ix->wOutKeys, &ix->wOutCounts};
     release_scratch(ix, ~0u);  // every family's
     for (DevBuf *b : ws) b->release();
     if (ix->sweep_stream) hipStreamDestroy(ix->sweep_stream);
@@ -568,18 +742,8 @@ extern "C" int zh_index_clear(zh_index *ix) {
     ix->n_rows = 0;
     ix->h_dead.clear();
     ix->n_dead = 0;
-    // everything derived from the rows that were just dropped: the row norms of the row-score hash, the live-row list of
-    // the hyperplane sampler (both were keyed on counts alone: a refill to the same count found them "valid")
     ix->rows_gen++; ix->dead_gen++;
-    ix->norm_rows = 0; ix->norm_gen = 0;
-    ix->row_hn2.release(); ix->row_norm.release();
-    std::lock_guard<std::mutex> lb(ix->blk_mu);  // (the fp16 copies' state is blk_mu's: zh_stats reads it under that lock)
-    ix->scale_rows = 0; ix->scale_gen = 0; ix->row_rho = 0.f; ix->row_half.release(); ix->row_meta.release(); ix->row_half_failed = false;
-    ix->perm_rows = 0; ix->perm_gen++; ix->scan_perm.release(); ix->row_leaf_p.release(); ix->row_order_off = false;  // (a new table gets a new chance at the scan's row order)
-    ix->h128_rows = 0; ix->h128_gen = 0; ix->h128_rho = 0.f; ix->row_half128.release(); ix->h128_failed = false;
-    ix->h128_bytes = false; ix->h128_not_bytes = false;
-    ix->h_live.clear(); ix->h_live.shrink_to_fit();
-    ix->h_live_rows = ix->h_live_dead = ix->h_live_gen = ~0ull;
+    views_table_emptied(ix);
     return ZH_OK;
 }
 
@@ -687,10 +851,7 @@ static int upload_nodes(zh_index *ix) {
     HIPCHK(hipStreamSynchronize(ix->stream));
     ix->n_nodes = (uint32_t)nn;
     ix->n_trees = (uint32_t)ix->h_roots.size();
-    ix->blocks_valid = false;  // the trees changed
-    ix->leaf_meta_valid = false; ix->prefilter_strikes = 0; ix->approx_strikes = 0; ix->mfma_f32_off = false; ix->fused_off = false;
-    ix->row_leaf_valid = false; ix->row_leaf_failed = false;
-    ix->batches_since_change = 0;
+    views_trees_changed(ix);
     ix->max_leaf_len = 0;
     for (size_t i = 0; i < nn; i++)
         if (ix->h_plane[i] < 0) ix->max_leaf_len = std::max(ix->max_leaf_len, (uint32_t)ix->h_right[i]);
@@ -864,17 +1025,18 @@ static void sample_pair(uint64_t seed, uint32_t tree, uint64_t path, uint64_t n_
 // defines a plane.  Returns the live count (< 2: default zero vectors, lsh.rs:203-220).  Same mapping as the oracle's.
 static uint64_t sample_live_pair(zh_index *ix, uint32_t tree, uint64_t path, uint64_t n_sample, uint64_t *si, uint64_t *sj) {
     if (ix->n_dead == 0) { sample_pair(ix->opt.seed, tree, path, n_sample, si, sj); return n_sample; }
-    if (ix->h_live_rows != ix->n_rows || ix->h_live_dead != ix->n_dead || ix->h_live_gen != ix->dead_gen) {
-        ix->h_live.clear();
-        ix->h_live.reserve(ix->n_rows - ix->n_dead);
+    std::vector<uint32_t> &live = ix->live_host.rows;
+    if (!ix->live_host.current(ix)) {
+        live.clear();
+        live.reserve(ix->n_rows - ix->n_dead);
         for (uint64_t r = 0; r < ix->n_rows; r++)
-            if (!(r < ix->h_dead.size() && ix->h_dead[r])) ix->h_live.push_back((uint32_t)r);
-        ix->h_live_rows = ix->n_rows; ix->h_live_dead = ix->n_dead; ix->h_live_gen = ix->dead_gen;
+            if (!(r < ix->h_dead.size() && ix->h_dead[r])) live.push_back((uint32_t)r);
+        ix->live_host.mark_built(ix);
     }
-    const uint64_t n_live = (uint64_t)(std::lower_bound(ix->h_live.begin(), ix->h_live.end(), n_sample,
-                                                        [](uint32_t a, uint64_t b) { return (uint64_t)a < b; }) - ix->h_live.begin());
+    const uint64_t n_live = (uint64_t)(std::lower_bound(live.begin(), live.end(), n_sample,
+                                                        [](uint32_t a, uint64_t b) { return (uint64_t)a < b; }) - live.begin());
     sample_pair(ix->opt.seed, tree, path, n_live, si, sj);
-    if (n_live) { *si = ix->h_live[*si]; *sj = ix->h_live[*sj]; }
+    if (n_live) { *si = live[*si]; *sj = live[*sj]; }
     return n_live;
 }
 
@@ -942,8 +1104,8 @@ static int grow_segments(zh_index *ix, uint32_t *d_perm, uint64_t perm_len, std:
             for (uint32_t i = 0; i < na; i++)
                 hs[i] = make_uint2(hn[i].sample_a == ~0ull ? 0xFFFFFFFFu : (uint32_t)hn[i].sample_a,
                                    hn[i].sample_b == ~0ull ? 0xFFFFFFFFu : (uint32_t)hn[i].sample_b);
-            if ((rc = ix->plane_samples.ensure((size_t)(n_planes + na) * sizeof(uint2), true, s))) return rc;
-            HIPCHK(hipMemcpy(ix->plane_samples.as<uint2>() + n_planes, hs.data(), na * sizeof(uint2), hipMemcpyHostToDevice));
+            if ((rc = ix->samples.pairs.ensure((size_t)(n_planes + na) * sizeof(uint2), true, s))) return rc;
+            HIPCHK(hipMemcpy(ix->samples.pairs.as<uint2>() + n_planes, hs.data(), na * sizeof(uint2), hipMemcpyHostToDevice));
         }
         hipError_t e = hipMemcpyAsync(dNodes.p, hn.data(), na * sizeof(ZhBuildNode), hipMemcpyHostToDevice, s);
         if (e == hipSuccess && nc) e = hipMemcpyAsync(dChunks.p, hc.data(), nc * sizeof(ZhBuildChunk), hipMemcpyHostToDevice, s);
@@ -1018,7 +1180,7 @@ static int build_forest_locked(zh_index *ix) {
         if ((rc = ix->planes.ensure(4 * (size_t)ix->opt.dim)) || (rc = ix->consts.ensure(4))) { perm.release(); free_forest(ix); return rc; }
     }
     ix->n_planes = n_planes;
-    ix->samples_valid = true;  // every plane of this forest was made from two stored rows, recorded in plane_samples
+    ix->samples.mark(true);  // every plane of this forest was made from two stored rows, recorded in samples.pairs
     ix->leaf_ids = perm;  // perm is the concatenation of all leaves
     perm.p = nullptr; perm.cap = 0;
     ix->n_leaf_ids = total;
@@ -1431,8 +1593,8 @@ extern "C" int zh_index_compact(zh_index *ix, uint64_t *out_new_ids, size_t cap,
         }
     }
     if (e == hipSuccess) e = zh_launch_renumber_ids(ix->leaf_ids.as<uint32_t>(), ix->n_leaf_ids, dMap, N, s);
-    const bool had_samples = ix->samples_valid && ix->n_planes && ix->plane_samples.cap >= (size_t)ix->n_planes * sizeof(uint2);
-    if (e == hipSuccess && had_samples) e = zh_launch_renumber_samples(ix->plane_samples.as<uint2>(), ix->n_planes, dMap, N, dFlag.as<uint32_t>(), s);
+    const bool had_samples = ix->samples.valid && ix->n_planes && ix->samples.pairs.cap >= (size_t)ix->n_planes * sizeof(uint2);
+    if (e == hipSuccess && had_samples) e = zh_launch_renumber_samples(ix->samples.pairs.as<uint2>(), ix->n_planes, dMap, N, dFlag.as<uint32_t>(), s);
     if (e == hipSuccess) e = hipEventRecord(ev1, s);
     uint32_t lost_sample = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&lost_sample, dFlag.p, 4, hipMemcpyDeviceToHost, s);
@@ -1459,25 +1621,7 @@ extern "C" int zh_index_compact(zh_index *ix, uint64_t *out_new_ids, size_t cap,
     ix->h_dead.clear();
     ix->n_dead = 0;
     ix->rows_gen++; ix->dead_gen++;
-    ix->h_live.clear(); ix->h_live.shrink_to_fit();
-    ix->h_live_rows = ix->h_live_dead = ix->h_live_gen = ~0ull;
-    ix->ex_live_rows = ix->ex_live_gen = ~0ull;
-    ix->ex_live.release(); ix->ex_bits.release();  // (sized by the old row count; re-made by the next exact search)
-    ix->norm_rows = 0; ix->norm_gen = 0;
-    ix->row_hn2.release(); ix->row_norm.release();
-    ix->hab_planes = 0; ix->hab_rows = 0; ix->hab_gen = 0;
-    if (lost_sample) ix->samples_valid = false;  // (a plane's sample row is gone: no row scores for its sign until the forest is rebuilt)
-    ix->leaf_meta.release(); ix->leaf_meta_valid = false;
-    ix->row_leaf.release(); ix->row_leaf_valid = false; ix->row_leaf_failed = false; ix->row_leaf_rows = 0;
-    {
-        std::lock_guard<std::mutex> lb(ix->blk_mu);  // (the fp16 copies' state is blk_mu's: zh_stats reads it under that lock)
-        ix->blocks_valid = false;
-        ci.copy_bytes_released = ix->row_half.cap + ix->row_meta.cap + ix->row_half128.cap + ix->scan_perm.cap + ix->row_leaf_p.cap;
-        ix->scale_rows = 0; ix->scale_gen = 0; ix->row_rho = 0.f; ix->row_half.release(); ix->row_meta.release(); ix->row_half_failed = false;
-        ix->perm_rows = 0; ix->perm_gen++; ix->scan_perm.release(); ix->row_leaf_p.release();
-        ix->h128_rows = 0; ix->h128_gen = 0; ix->h128_rho = 0.f; ix->row_half128.release(); ix->h128_failed = false;
-        ix->h128_bytes = false;  // (h128_not_bytes stays: a table with a row that is not of bytes still has one, or lost it and finds out when the copy is next made)
-    }
+    ci.copy_bytes_released = views_rows_moved(ix, lost_sample != 0);
     if (info) *info = ci;
     return ZH_OK;
 }
@@ -1515,7 +1659,7 @@ extern "C" int zh_index_save(zh_index *ix, const char *path, zh_snapshot_info *i
     f.version = ZH_SNAPSHOT_VERSION; f.dim = d; f.max_node_size = ix->opt.max_node_size; f.num_trees_option = ix->opt.num_trees;
     f.seed = ix->opt.seed; f.id_base = ix->opt.id_base; f.stored_rows = N; f.live_rows = N - ix->n_dead;
     f.n_trees = ix->n_trees; f.n_nodes = ix->n_nodes; f.n_planes = np; f.n_leaf_ids = ix->n_leaf_ids;
-    f.flags = (ix->samples_valid ? 1u : 0u) | (ix->scan_unsafe ? 2u : 0u);
+    f.flags = (ix->samples.valid ? 1u : 0u) | (ix->scan_unsafe ? 2u : 0u);
     h.max_leaf_len = ix->max_leaf_len;
     h.n_levels = (uint32_t)ix->planes_below_level.size();
     if (h.n_levels > ZH_SNAP_MAX_LEVELS) return fail(ZH_ELIMIT, "zh_index_save: %u forest levels", h.n_levels);
@@ -1533,8 +1677,8 @@ extern "C" int zh_index_save(zh_index *ix, const char *path, zh_snapshot_info *i
     }
     if (!hl.empty()) HIPCHK(hipMemcpy(hl.data(), ix->leaf_ids.p, hl.size() * 4, hipMemcpyDeviceToHost));
     if (!hs.empty()) {
-        if (ix->plane_samples.cap < hs.size() * 4) return fail(ZH_ESTATE, "zh_index_save: the planes' sample rows are incomplete");
-        HIPCHK(hipMemcpy(hs.data(), ix->plane_samples.p, hs.size() * 4, hipMemcpyDeviceToHost));
+        if (ix->samples.pairs.cap < hs.size() * 4) return fail(ZH_ESTATE, "zh_index_save: the planes' sample rows are incomplete");
+        HIPCHK(hipMemcpy(hs.data(), ix->samples.pairs.p, hs.size() * 4, hipMemcpyDeviceToHost));
     }
     const void *small[ZH_SNAP_MAX_SECTIONS] = {};
     small[ZH_SEC_REMOVED] = removed.data(); small[ZH_SEC_NODE_PLANE] = ix->h_plane.data(); small[ZH_SEC_NODE_LEFT] = ix->h_left.data();
@@ -1640,14 +1784,14 @@ static int load_forest(zh_index *ix, int fd, const ZhSnapHeader &h) {
     }
     if (f.n_leaf_ids) HIPCHK(hipMemcpyAsync(ix->leaf_ids.p, leaf_ids.data(), leaf_ids.size() * 4, hipMemcpyHostToDevice, ix->stream));
     if (f.flags & 1u) {
-        if ((rc = ix->plane_samples.ensure((size_t)std::max(np, 1u) * sizeof(uint2)))) return rc;
-        if (np) HIPCHK(hipMemcpyAsync(ix->plane_samples.p, samples.data(), samples.size() * 4, hipMemcpyHostToDevice, ix->stream));
+        if ((rc = ix->samples.pairs.ensure((size_t)std::max(np, 1u) * sizeof(uint2)))) return rc;
+        if (np) HIPCHK(hipMemcpyAsync(ix->samples.pairs.p, samples.data(), samples.size() * 4, hipMemcpyHostToDevice, ix->stream));
     }
     HIPCHK(hipStreamSynchronize(ix->stream));
     ix->n_planes = np;
     ix->n_leaf_ids = f.n_leaf_ids;
     ix->planes_below_level.swap(levels);
-    ix->samples_valid = (f.flags & 1u) != 0;
+    ix->samples.mark((f.flags & 1u) != 0);
     rc = upload_nodes(ix);
     ix->scan_unsafe = (f.flags & 2u) != 0 || fc.dup_in_tree;
     return rc;
@@ -1738,9 +1882,9 @@ extern "C" int zh_stats(zh_index *ix, zh_stats_t *out) {
         *out = ix->stats;
     }
     std::lock_guard<std::mutex> lk(ix->blk_mu);  // (the copies are made and dropped under it)
-    out->row_copy_bytes = ix->row_half.cap + ix->row_meta.cap + ix->row_half128.cap + ix->scan_perm.cap + ix->row_leaf_p.cap;  // (+ the scan's row order and its view of row -> leaf)
-    out->scan_order_keys = ix->perm_rows ? ix->order_keys : 0;
-    out->scan_order_share_permille = (uint64_t)(ix->order_worth * 1000.0 + 0.5);
+    out->row_copy_bytes = row_copy_bytes(ix);
+    out->scan_order_keys = ix->order.rows ? ix->order.keys : 0;
+    out->scan_order_share_permille = (uint64_t)(ix->order.worth * 1000.0 + 0.5);
     return ZH_OK;
 }
 extern "C" int zh_stats_reset(zh_index *ix) {
@@ -1748,6 +1892,31 @@ extern "C" int zh_stats_reset(zh_index *ix) {
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     memset(&ix->stats, 0, sizeof ix->stats);
     return ZH_OK;
+}
+
+// The host mirror of the forest in pre-order, tree after tree: visit(node, its tree) (iterative: trees may be 60 levels deep).
+template <typename Visit>
+static void forest_preorder(const zh_index *ix, Visit visit) {
+    std::vector<uint32_t> st;
+    for (uint32_t t = 0; t < (uint32_t)ix->h_roots.size(); t++) {
+        st.assign(1, ix->h_roots[t]);
+        while (!st.empty()) {
+            const uint32_t n = st.back(); st.pop_back();
+            visit(n, t);
+            if (ix->h_plane[n] >= 0) { st.push_back((uint32_t)ix->h_right[n]); st.push_back((uint32_t)ix->h_left[n]); }
+        }
+    }
+}
+
+// ... walked once -> node_tree[node] = the tree that holds it (0xFFFFFFFF: none) and, where asked for, every tree's non-empty leaves.
+static std::vector<uint32_t> forest_walk(const zh_index *ix, std::vector<std::vector<uint2>> *leaves) {
+    std::vector<uint32_t> node_tree(std::max<size_t>(ix->h_plane.size(), 1), 0xFFFFFFFFu);
+    if (leaves) leaves->resize(ix->h_roots.size());
+    forest_preorder(ix, [&](uint32_t nd, uint32_t t) {
+        node_tree[nd] = t;
+        if (leaves && ix->h_plane[nd] < 0 && ix->h_right[nd] > 0) (*leaves)[t].push_back(make_uint2((uint32_t)ix->h_left[nd], (uint32_t)ix->h_right[nd]));
+    });
+    return node_tree;
 }
 
 // Blocked view of the forest (zh_internal.h, ZhBlocksDev): every maximal subtree of at most ZH_BLOCK_NODES nodes becomes
@@ -1760,32 +1929,71 @@ extern "C" int zh_stats_reset(zh_index *ix) {
 // Twice the tree nodes per block: half the blocks, half the upper nodes, and the walk's dependent round trips with them (1M x 384 at the
 // reference's default options: 346k blocks / 346k upper nodes -> see tests/probes/refdefault_shape.py).  A leaf hanging directly off an upper node
 // (or a tree that is one leaf) is a block of zero inner nodes: record {-1, 0, offset, length} {node id, 0, 0, 0}.
-static int build_blocks_inner(zh_index *ix) {
+//
+// the size of every subtree, by the measure its kind of block is limited in: all of its nodes, or its inner nodes only (the pre-order, then a
+// reverse pass: children before parents)
+static std::vector<uint32_t> subtree_sizes(const zh_index *ix, bool inner_only) {
     const size_t nn = ix->h_plane.size();
-    const uint32_t T = (uint32_t)ix->h_roots.size();
-    std::vector<uint32_t> isize(nn, 0), order, st;
+    std::vector<uint32_t> size(nn, 0), order;
     order.reserve(nn);
-    for (uint32_t t = 0; t < T; t++) {  // pre-order of every tree; inner-node counts of the subtrees in a reverse pass
-        const size_t o0 = order.size();
-        st.assign(1, ix->h_roots[t]);
-        while (!st.empty()) {
-            const uint32_t n = st.back(); st.pop_back();
-            order.push_back(n);
-            if (ix->h_plane[n] >= 0) { st.push_back((uint32_t)ix->h_right[n]); st.push_back((uint32_t)ix->h_left[n]); }
-        }
-        for (size_t i = order.size(); i-- > o0;) {
-            const uint32_t n = order[i];
-            isize[n] = ix->h_plane[n] >= 0 ? 1 + isize[(uint32_t)ix->h_left[n]] + isize[(uint32_t)ix->h_right[n]] : 0;
+    forest_preorder(ix, [&](uint32_t n, uint32_t) { order.push_back(n); });
+    for (size_t i = order.size(); i-- > 0;) {
+        const uint32_t n = order[i];
+        const bool inner = ix->h_plane[n] >= 0;
+        size[n] = (inner_only ? (inner ? 1u : 0u) : 1u) + (inner ? size[(uint32_t)ix->h_left[n]] + size[(uint32_t)ix->h_right[n]] : 0u);
+    }
+    return size;
+}
+
+// Every maximal subtree of at most `limit` (by `size`) becomes a block -- emit_block(root) writes its records and returns its ref -- and the
+// nodes above them get pointer records: upper nodes get dense ids in the order they are met; a child's ref is final once the child has been
+// classified.
+template <typename Emit>
+static void place_blocks(const zh_index *ix, const std::vector<uint32_t> &size, uint32_t limit, Emit emit_block, std::vector<int4> &upper,
+                         std::vector<int2> &roots) {
+    std::vector<std::pair<uint32_t, uint32_t>> todo;  // (node, its upper id)
+    for (uint32_t t = 0; t < (uint32_t)ix->h_roots.size(); t++) {
+        const uint32_t rt = ix->h_roots[t];
+        if (size[rt] <= limit) { roots[t] = make_int2(emit_block(rt), 0); continue; }
+        roots[t] = make_int2((int32_t)(upper.size() / 2), ix->h_plane[rt]);
+        upper.push_back(make_int4(0, 0, 0, 0)); upper.push_back(make_int4(0, 0, 0, 0));
+        todo.assign(1, {rt, (uint32_t)(upper.size() / 2 - 1)});
+        while (!todo.empty()) {
+            const auto [n, uid] = todo.back(); todo.pop_back();
+            const uint32_t ch[2] = {(uint32_t)ix->h_left[n], (uint32_t)ix->h_right[n]};
+            int32_t ref[2], cpl[2];
+            for (int e = 0; e < 2; e++) {
+                if (size[ch[e]] <= limit) { ref[e] = emit_block(ch[e]); cpl[e] = 0; }
+                else {
+                    ref[e] = (int32_t)(upper.size() / 2); cpl[e] = ix->h_plane[ch[e]];
+                    upper.push_back(make_int4(0, 0, 0, 0)); upper.push_back(make_int4(0, 0, 0, 0));
+                    todo.push_back({ch[e], (uint32_t)ref[e]});
+                }
+            }
+            upper[2 * (size_t)uid] = make_int4(ix->h_plane[n], ref[0], ref[1], 0);
+            upper[2 * (size_t)uid + 1] = make_int4(cpl[0], cpl[1], 0, 0);
         }
     }
-    std::vector<int4> recs, recsB, upper;  // recs / recsB: the first / second int4 of every inner node's record (two arrays: a wave's two loads of a
-                                           // block are 1 KiB contiguous each -- interleaved 32-byte records made a block load 3404 cycles against 1795)
+}
+
+static int build_blocks(zh_index *ix) {
+    // ZH_WALK_BLOCKS=inner (read when a forest's view is built): the round-5 blocks of inner nodes only.  Measured and NOT the default: half the
+    // blocks and upper nodes, 27 % fewer block entries and 31 % fewer upper steps per pair -- and the same 8.5 ms per batch (DESIGN.md s9,
+    // profiles/r05_walk_prof.txt): the walk's time is its instruction stream and the exact sign chains, not its round trips.
+    const char *bv = getenv("ZH_WALK_BLOCKS");
+    const bool inner_only = bv && bv[0] == 'i';
+    const size_t nn = ix->h_plane.size();
+    const uint32_t T = (uint32_t)ix->h_roots.size();
+    const std::vector<uint32_t> size = subtree_sizes(ix, inner_only);
+    std::vector<int4> recs, recsB, upper;  // inner only: recs / recsB = the first / second int4 of every inner node's record (two arrays: a wave's two loads
+                                           // of a block are 1 KiB contiguous each -- interleaved 32-byte records made a block load 3404 cycles against 1795)
     std::vector<int2> roots(std::max<uint32_t>(T, 1), make_int2(0, 0));
-    recs.reserve(nn / 2 + ZH_BLOCK_NODES);
-    recsB.reserve(nn / 2 + ZH_BLOCK_NODES);
-    std::vector<uint32_t> nodes;
+    recs.reserve((inner_only ? nn / 2 : nn) + ZH_BLOCK_NODES);
+    if (inner_only) recsB.reserve(nn / 2 + ZH_BLOCK_NODES);
+    std::vector<uint32_t> nodes, st;
     uint32_t n_blocks = 0;
-    auto emit_block = [&](uint32_t root) -> int32_t {  // the subtree's INNER nodes in pre-order; a ref is -(first 32-byte record + 1)
+    auto emit_inner = [&](uint32_t root) -> int32_t {  // the subtree's INNER nodes in pre-order; a ref is -(first 32-byte record + 1)
+        const std::vector<uint32_t> &isize = size;
         const size_t base = recs.size();
         n_blocks++;
         if (ix->h_plane[root] < 0) {  // a leaf by itself
@@ -1813,82 +2021,7 @@ static int build_blocks_inner(zh_index *ix) {
         }
         return -(int32_t)base - 1;
     };
-    std::vector<std::pair<uint32_t, uint32_t>> todo;  // (node, its upper id)
-    for (uint32_t t = 0; t < T; t++) {
-        const uint32_t rt = ix->h_roots[t];
-        if (isize[rt] <= ZH_BLOCK_INNER) { roots[t] = make_int2(emit_block(rt), 0); continue; }
-        roots[t] = make_int2((int32_t)(upper.size() / 2), ix->h_plane[rt]);
-        upper.push_back(make_int4(0, 0, 0, 0)); upper.push_back(make_int4(0, 0, 0, 0));
-        todo.assign(1, {rt, (uint32_t)(upper.size() / 2 - 1)});
-        while (!todo.empty()) {
-            const auto [n, uid] = todo.back(); todo.pop_back();
-            const uint32_t ch[2] = {(uint32_t)ix->h_left[n], (uint32_t)ix->h_right[n]};
-            int32_t ref[2], cpl[2];
-            for (int e = 0; e < 2; e++) {
-                if (isize[ch[e]] <= ZH_BLOCK_INNER) { ref[e] = emit_block(ch[e]); cpl[e] = 0; }
-                else {
-                    ref[e] = (int32_t)(upper.size() / 2); cpl[e] = ix->h_plane[ch[e]];
-                    upper.push_back(make_int4(0, 0, 0, 0)); upper.push_back(make_int4(0, 0, 0, 0));
-                    todo.push_back({ch[e], (uint32_t)ref[e]});
-                }
-            }
-            upper[2 * (size_t)uid] = make_int4(ix->h_plane[n], ref[0], ref[1], 0);
-            upper[2 * (size_t)uid + 1] = make_int4(cpl[0], cpl[1], 0, 0);
-        }
-    }
-    if (recs.size() > 0x7FFFFFF0ull || upper.size() > 0x7FFFFFF0ull) return fail(ZH_ELIMIT, "forest too large for the blocked view");
-    recs.resize(recs.size() + ZH_BLOCK_NODES, make_int4(-1, 0, 0, 0));  // a wave always reads 64 records
-    recsB.resize(recs.size(), make_int4(0, 0, 0, 0));
-    const size_t n_inner_recs = recs.size();
-    recs.insert(recs.end(), recsB.begin(), recsB.end());  // one buffer: [first halves][second halves]
-    std::vector<int4>().swap(recsB);
-    if (upper.empty()) upper.assign(2, make_int4(0, 0, 0, 0));
-    int rc;
-    if ((rc = ix->blk_recs.ensure(recs.size() * sizeof(int4)))) return rc;
-    if ((rc = ix->blk_upper.ensure(upper.size() * sizeof(int4)))) return rc;
-    if ((rc = ix->blk_roots.ensure(roots.size() * sizeof(int2)))) return rc;
-    HIPCHK(hipMemcpy(ix->blk_recs.p, recs.data(), recs.size() * sizeof(int4), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ix->blk_upper.p, upper.data(), upper.size() * sizeof(int4), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ix->blk_roots.p, roots.data(), roots.size() * sizeof(int2), hipMemcpyHostToDevice));
-    ix->n_blocks = n_blocks;
-    ix->n_upper = (uint32_t)(upper.size() / 2);
-    ix->blocks_valid = true;
-    ix->blocks_inner = true;
-    ix->blk_recs_b = n_inner_recs;
-    return ZH_OK;
-}
-
-static int build_blocks(zh_index *ix) {
-    // ZH_WALK_BLOCKS=inner (read when a forest's view is built): the round-5 blocks of inner nodes only.  Measured and NOT the default: half the
-    // blocks and upper nodes, 27 % fewer block entries and 31 % fewer upper steps per pair -- and the same 8.5 ms per batch (DESIGN.md s9,
-    // profiles/r05_walk_prof.txt): the walk's time is its instruction stream and the exact sign chains, not its round trips.
-    const char *bv = getenv("ZH_WALK_BLOCKS");
-    if (bv && bv[0] == 'i') return build_blocks_inner(ix);
-    ix->blocks_inner = false;
-    const size_t nn = ix->h_plane.size();
-    const uint32_t T = (uint32_t)ix->h_roots.size();
-    std::vector<uint32_t> size(nn, 0), order;
-    order.reserve(nn);
-    std::vector<uint32_t> st;
-    for (uint32_t t = 0; t < T; t++) {  // pre-order of every tree; subtree sizes in a reverse pass
-        const size_t o0 = order.size();
-        st.assign(1, ix->h_roots[t]);
-        while (!st.empty()) {
-            const uint32_t n = st.back(); st.pop_back();
-            order.push_back(n);
-            if (ix->h_plane[n] >= 0) { st.push_back((uint32_t)ix->h_right[n]); st.push_back((uint32_t)ix->h_left[n]); }
-        }
-        for (size_t i = order.size(); i-- > o0;) {
-            const uint32_t n = order[i];
-            size[n] = 1 + (ix->h_plane[n] >= 0 ? size[(uint32_t)ix->h_left[n]] + size[(uint32_t)ix->h_right[n]] : 0);
-        }
-    }
-    std::vector<int4> recs, upper;
-    std::vector<int2> roots(std::max<uint32_t>(T, 1), make_int2(0, 0));
-    recs.reserve(nn + ZH_BLOCK_NODES);
-    std::vector<uint32_t> nodes;
-    uint32_t n_blocks = 0;
-    auto emit_block = [&](uint32_t root) -> int32_t {  // nodes of the subtree in pre-order, children as local indices
+    auto emit_whole = [&](uint32_t root) -> int32_t {  // nodes of the subtree in pre-order, children as local indices
         const size_t base = recs.size();
         nodes.clear();
         st.assign(1, root);
@@ -1909,96 +2042,65 @@ static int build_blocks(zh_index *ix) {
         n_blocks++;
         return -(int32_t)base - 1;
     };
-    // upper nodes get dense ids in the order they are met; a child's ref is final once the child has been classified
-    std::vector<uint32_t> up;
-    std::vector<std::pair<uint32_t, uint32_t>> todo;  // (node, its upper id)
-    for (uint32_t t = 0; t < T; t++) {
-        const uint32_t rt = ix->h_roots[t];
-        if (size[rt] <= ZH_BLOCK_NODES) { roots[t] = make_int2(emit_block(rt), 0); continue; }
-        roots[t] = make_int2((int32_t)(upper.size() / 2), ix->h_plane[rt]);
-        upper.push_back(make_int4(0, 0, 0, 0)); upper.push_back(make_int4(0, 0, 0, 0));
-        todo.assign(1, {rt, (uint32_t)(upper.size() / 2 - 1)});
-        while (!todo.empty()) {
-            const auto [n, uid] = todo.back(); todo.pop_back();
-            const uint32_t ch[2] = {(uint32_t)ix->h_left[n], (uint32_t)ix->h_right[n]};
-            int32_t ref[2], cpl[2];
-            for (int e = 0; e < 2; e++) {
-                if (size[ch[e]] <= ZH_BLOCK_NODES) { ref[e] = emit_block(ch[e]); cpl[e] = 0; }
-                else {
-                    ref[e] = (int32_t)(upper.size() / 2); cpl[e] = ix->h_plane[ch[e]];
-                    upper.push_back(make_int4(0, 0, 0, 0)); upper.push_back(make_int4(0, 0, 0, 0));
-                    todo.push_back({ch[e], (uint32_t)ref[e]});
-                }
-            }
-            upper[2 * (size_t)uid] = make_int4(ix->h_plane[n], ref[0], ref[1], 0);
-            upper[2 * (size_t)uid + 1] = make_int4(cpl[0], cpl[1], 0, 0);
-        }
-    }
+    if (inner_only) place_blocks(ix, size, ZH_BLOCK_INNER, emit_inner, upper, roots);
+    else place_blocks(ix, size, ZH_BLOCK_NODES, emit_whole, upper, roots);
     if (recs.size() > 0x7FFFFFF0ull || upper.size() > 0x7FFFFFF0ull) return fail(ZH_ELIMIT, "forest too large for the blocked view");
-    const size_t n_recs = recs.size();
-    recs.resize(n_recs + ZH_BLOCK_NODES, make_int4(-1, 0, 0, 0));  // a wave always reads 64 records
+    recs.resize(recs.size() + ZH_BLOCK_NODES, make_int4(-1, 0, 0, 0));  // a wave always reads 64 records
+    const size_t second_halves = inner_only ? recs.size() : 0;
+    if (inner_only) {
+        recsB.resize(recs.size(), make_int4(0, 0, 0, 0));
+        recs.insert(recs.end(), recsB.begin(), recsB.end());  // one buffer: [first halves][second halves]
+        std::vector<int4>().swap(recsB);
+    }
     if (upper.empty()) upper.assign(2, make_int4(0, 0, 0, 0));
+    zh_index::BlocksView &v = ix->blocks;
     int rc;
-    if ((rc = ix->blk_recs.ensure(recs.size() * sizeof(int4)))) return rc;
-    if ((rc = ix->blk_upper.ensure(upper.size() * sizeof(int4)))) return rc;
-    if ((rc = ix->blk_roots.ensure(roots.size() * sizeof(int2)))) return rc;
-    HIPCHK(hipMemcpy(ix->blk_recs.p, recs.data(), recs.size() * sizeof(int4), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ix->blk_upper.p, upper.data(), upper.size() * sizeof(int4), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ix->blk_roots.p, roots.data(), roots.size() * sizeof(int2), hipMemcpyHostToDevice));
-    ix->n_blocks = n_blocks;
-    ix->n_upper = (uint32_t)(upper.size() / 2);
-    ix->blocks_valid = true;
+    if ((rc = v.recs.ensure(recs.size() * sizeof(int4)))) return rc;
+    if ((rc = v.upper.ensure(upper.size() * sizeof(int4)))) return rc;
+    if ((rc = v.roots.ensure(roots.size() * sizeof(int2)))) return rc;
+    HIPCHK(hipMemcpy(v.recs.p, recs.data(), recs.size() * sizeof(int4), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(v.upper.p, upper.data(), upper.size() * sizeof(int4), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(v.roots.p, roots.data(), roots.size() * sizeof(int2), hipMemcpyHostToDevice));
+    v.mark_built(n_blocks, (uint32_t)(upper.size() / 2), inner_only, second_halves);
     return ZH_OK;
 }
 
 // row -> {leaf node, position in the leaf} for every tree (the table-scan sweep's view of the forest): host pass for the
-// node -> tree map (iterative, as build_blocks), then one kernel over the leaves.  A failed allocation is remembered: the
+// node -> tree map (forest_walk), then one kernel over the leaves.  A failed allocation is remembered: the
 // leaf-major sweep serves the index until the trees change.
 static int build_row_leaf(zh_index *ix) {
     const size_t nn = ix->h_plane.size();
     const uint32_t T = (uint32_t)ix->h_roots.size();
-    if (ix->row_leaf.ensure(std::max<uint64_t>(ix->n_rows * T, 1) * sizeof(uint2)) != ZH_OK) { ix->row_leaf_failed = true; return ZH_OK; }
-    std::vector<uint32_t> node_tree(std::max<size_t>(nn, 1), 0xFFFFFFFFu), st;
-    for (uint32_t t = 0; t < T; t++) {
-        st.assign(1, ix->h_roots[t]);
-        while (!st.empty()) {
-            const uint32_t n = st.back(); st.pop_back();
-            node_tree[n] = t;
-            if (ix->h_plane[n] >= 0) { st.push_back((uint32_t)ix->h_right[n]); st.push_back((uint32_t)ix->h_left[n]); }
-        }
-    }
+    if (ix->row_leaf.table.ensure(std::max<uint64_t>(ix->n_rows * T, 1) * sizeof(uint2)) != ZH_OK) { ix->row_leaf.mark_failed(); return ZH_OK; }
+    const std::vector<uint32_t> node_tree = forest_walk(ix, nullptr);
     DevBuf dTree;
     int rc = dTree.ensure(node_tree.size() * 4);
-    if (rc) { ix->row_leaf_failed = true; return ZH_OK; }
+    if (rc) { ix->row_leaf.mark_failed(); return ZH_OK; }
     hipError_t e = hipMemcpy(dTree.p, node_tree.data(), node_tree.size() * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess)
         e = zh_launch_row_leaf(ix->node_pack.as<int4>(), dTree.as<uint32_t>(), (uint32_t)nn, ix->leaf_ids.as<uint32_t>(), T, ix->n_rows,
-                               ix->row_leaf.as<uint2>(), ix->stream);
+                               ix->row_leaf.table.as<uint2>(), ix->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
     dTree.release();
     if (e != hipSuccess) return fail(ZH_EHIP, "row -> leaf table: %s", hipGetErrorString(e));
-    ix->row_leaf_valid = true;
-    ix->row_leaf_rows = ix->n_rows;
-    ix->row_leaf_gen++;
+    ix->row_leaf.mark_built(ix->n_rows);
     return ZH_OK;
 }
 
 // the matrix-core scan's row order (under blk_mu; zh_order.hip), from the row -> leaf table, which must be valid for the stored rows.  Candidates:
 // id order (rows inserted cluster by cluster are best left alone), sorted by (leaf in tree 0, leaf in tree 1, id), and by three trees' leaves; each
 // is MEASURED -- (adjacent positions, tree) combinations that share a leaf = visitors a tile fetches once -- and the best one kept.
-// perm_rows = 0: id order (it won, there is no table, the order is switched off, or there is no room for the sort).  ZH_ROW_ORDER=0|2|3 forces one.
+// order.rows = 0: id order (it won, there is no table, the order is switched off, or there is no room for the sort).  ZH_ROW_ORDER=0|2|3 forces one.
 static int build_scan_perm(zh_index *ix) {
     const char *env_o = getenv("ZH_ROW_ORDER");  // (read when a copy is made: tests and A/B switch it)
     const int forced = env_o ? atoi(env_o) : -1;
-    ix->perm_rows = 0;
-    ix->perm_gen++;
-    ix->order_keys = 0;
-    if (forced == 0 || ix->row_order_off || !ix->row_leaf_valid || ix->row_leaf_rows != ix->n_rows || ix->n_rows < 32 || ix->n_rows > 0x7FFFFFF0ull) return ZH_OK;
+    ix->order.begin();
+    if (forced == 0 || ix->order.off || !ix->row_leaf.current(ix) || ix->n_rows < 32 || ix->n_rows > 0x7FFFFFF0ull) return ZH_OK;
     size_t mem_free = 0, mem_total = 0;  // the sort's scratch: ~28 bytes per row, released before the copy is made
     if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess || mem_free < ix->n_rows * 48 + mem_total / 16) return ZH_OK;
     DevBuf cand, dsum;
-    if (ix->scan_perm.ensure(ix->n_rows * 4) || cand.ensure(ix->n_rows * 4) || dsum.ensure(8)) { cand.release(); dsum.release(); return ZH_OK; }
-    const uint2 *rl = ix->row_leaf.as<uint2>();
+    if (ix->order.perm.ensure(ix->n_rows * 4) || cand.ensure(ix->n_rows * 4) || dsum.ensure(8)) { cand.release(); dsum.release(); return ZH_OK; }
+    const uint2 *rl = ix->row_leaf.table.as<uint2>();
     const uint32_t T = ix->n_trees;
     auto worth = [&](const uint32_t *perm, unsigned long long *out) -> hipError_t {
         hipError_t e = zh_launch_order_agreement(rl, perm, ix->n_rows, T, dsum.as<unsigned long long>(), ix->stream);
@@ -2015,19 +2117,17 @@ static int build_scan_perm(zh_index *ix) {
         if ((e = worth(cand.as<uint32_t>(), &w)) != hipSuccess) break;
         if (forced > 0 || w > best + best / 50) {  // (an order must be worth 2 % more than what there is)
             best = w; best_keys = keys;
-            e = hipMemcpyAsync(ix->scan_perm.p, cand.p, ix->n_rows * 4, hipMemcpyDeviceToDevice, ix->stream);
+            e = hipMemcpyAsync(ix->order.perm.p, cand.p, ix->n_rows * 4, hipMemcpyDeviceToDevice, ix->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
         }
     }
     cand.release(); dsum.release();
     if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return ZH_OK; }
     if (e != hipSuccess) return fail(ZH_EHIP, "row order of the scan: %s", hipGetErrorString(e));
-    ix->order_keys = best_keys;
-    ix->order_worth = (double)best / ((double)(ix->n_rows - 1) * T);
-    if (best_keys) ix->perm_rows = ix->n_rows;
+    ix->order.mark_built(best_keys, (double)best / ((double)(ix->n_rows - 1) * T), ix->n_rows);
     return ZH_OK;
 }
-// The scan's inputs (row_half / row_meta, row_leaf_p, row_half128) are rewritten IN PLACE when rows were appended, the forest changed or the row
+// The scan's inputs (half.tiles / half.meta, order.row_leaf_p, half128.copy) are rewritten IN PLACE when rows were appended, the forest changed or the row
 // order is given up.  blk_mu orders the host threads that do it, not the GPU work of other contexts: a scan another pipelined context queued on the
 // shared sweep stream (or its own) before this batch got here would read half-rewritten tiles.  Rewrites are rare (the first batch after an add /
 // a rebuild): wait for everything the device has queued, then rewrite.  
@@ -2037,36 +2137,34 @@ static int quiesce_before_rewrite() {
 }
 // the row -> leaf table in the scan's row order (under blk_mu; row_leaf must be valid)
 static int ensure_row_leaf_p(zh_index *ix) {
-    if (!ix->perm_rows) return ZH_OK;
-    if (ix->row_leaf_p_gen == ix->row_leaf_gen && ix->row_leaf_p_perm == ix->perm_gen) return ZH_OK;
+    if (!ix->order.rows) return ZH_OK;
+    if (ix->order.table_current(ix->row_leaf)) return ZH_OK;
     const uint32_t T = ix->n_trees;
     // the same headroom rule as the copies themselves: a sixteenth of the device stays free for the batches' scratch
     const uint64_t want_p = std::max<uint64_t>(ix->n_rows * T, 1) * sizeof(uint2);
     size_t mem_free = 0, mem_total = 0;
-    if (want_p > ix->row_leaf_p.cap && (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess || mem_free < want_p + mem_total / 16)) { ix->perm_rows = 0; return ZH_OK; }
+    if (want_p > ix->order.row_leaf_p.cap && (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess || mem_free < want_p + mem_total / 16)) { ix->order.no_room_for_table(); return ZH_OK; }
     int rc = quiesce_before_rewrite();
     if (rc) return rc;
-    rc = ix->row_leaf_p.ensure(want_p);
-    if (rc) { ix->perm_rows = 0; return ZH_OK; }  // (no room: the scan reads the table in id order -- but its tiles are in tree-0 order: the copy is remade)
-    hipError_t e = zh_launch_permute_row_leaf(ix->row_leaf.as<uint2>(), ix->scan_perm.as<uint32_t>(), ix->perm_rows, ix->n_rows, T, ix->row_leaf_p.as<uint2>(), ix->stream);
+    rc = ix->order.row_leaf_p.ensure(want_p);
+    if (rc) { ix->order.no_room_for_table(); return ZH_OK; }  // (no room: the scan reads the table in id order -- but its tiles are in tree-0 order: the copy is remade)
+    hipError_t e = zh_launch_permute_row_leaf(ix->row_leaf.table.as<uint2>(), ix->order.perm.as<uint32_t>(), ix->order.rows, ix->n_rows, T, ix->order.row_leaf_p.as<uint2>(), ix->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
     if (e != hipSuccess) return fail(ZH_EHIP, "row -> leaf table in the scan's order: %s", hipGetErrorString(e));
-    ix->row_leaf_p_gen = ix->row_leaf_gen;
-    ix->row_leaf_p_perm = ix->perm_gen;
+    ix->order.mark_table(ix->row_leaf);
     return ZH_OK;
 }
 
 // The fp16 copy of the stored rows for the MFMA table scan (under blk_mu): rows appended since the last call only.  false: no room for it.
 static int ensure_row_half(zh_index *ix, bool *ok) {
     *ok = false;
-    if (ix->row_half_failed && ix->scale_gen == ix->rows_gen && ix->scale_rows == ix->n_rows) return ZH_OK;
-    if (!ix->row_half_failed && ix->scale_gen == ix->rows_gen && ix->scale_rows == ix->n_rows) { *ok = true; return ZH_OK; }
+    if (ix->half.current(ix)) { *ok = !ix->half.failed; return ZH_OK; }
     const uint64_t d = ix->opt.dim, tiles = (ix->n_rows + 15) / 16;
-    ix->row_half_failed = false;
+    ix->half.retry();
     // room for it?  (a copy that grows is allocated anew before the old one is freed; a sixteenth of the device stays free for the batches' scratch)
     size_t mem_free = 0, mem_total = 0;
     const uint64_t want = std::max<uint64_t>(tiles, 1) * 16 * (d * 2 + sizeof(float2));
-    const bool room = want <= ix->row_half.cap + ix->row_meta.cap ||
+    const bool room = want <= ix->half.tiles.cap + ix->half.meta.cap ||
                       (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_free >= want + want / 2 + mem_total / 16);
     // No room for the copy (64M x 768 on one GPU: 196 GB of rows + 98 GB), or ZH_ROW_HALF_META_ONLY=1 (tests; read per call): the per-row scales and
     // norms alone (8 bytes per row) -- scan_mfma_kernel<D, true> then converts the f32 rows itself, to the bits the copy would hold (round 6: the
@@ -2075,59 +2173,55 @@ static int ensure_row_half(zh_index *ix, bool *ok) {
     const bool meta_only = !room || (mo_e && mo_e[0] == '1');
     if (meta_only) {
         const uint64_t want_meta = std::max<uint64_t>(tiles, 1) * 16 * sizeof(float2);
-        const bool room_meta = want_meta <= ix->row_meta.cap || (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_free >= want_meta + mem_total / 16);
-        ix->row_half.release();
-        if (!room_meta || ix->row_meta.ensure(want_meta, false, ix->stream) != ZH_OK || ix->row_rho_dev.ensure(4) != ZH_OK) {
-            ix->row_meta.release();
-            ix->row_half_failed = true;
-            ix->scale_rows = ix->n_rows; ix->scale_gen = ix->rows_gen;
+        const bool room_meta = want_meta <= ix->half.meta.cap || (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_free >= want_meta + mem_total / 16);
+        ix->half.tiles.release();
+        if (!room_meta || ix->half.meta.ensure(want_meta, false, ix->stream) != ZH_OK || ix->half.rho_dev.ensure(4) != ZH_OK) {
+            ix->half.meta.release();
+            ix->half.mark_failed(ix);
             return ZH_OK;
         }
         int rcq = quiesce_before_rewrite();
         if (rcq) return rcq;
-        ix->perm_rows = 0; ix->perm_gen++; ix->order_keys = 0;  // (the f32 rows are in id order)
-        HIPCHK(hipMemsetAsync(ix->row_rho_dev.p, 0, 4, ix->stream));
-        HIPCHK(zh_launch_row_half(ix->X.as<float>(), 0, ix->n_rows, (uint32_t)d, nullptr, ix->row_meta.as<float2>(), ix->row_rho_dev.as<uint32_t>(), nullptr, 0, ix->stream));
+        ix->order.begin();  // (the f32 rows are in id order)
+        HIPCHK(hipMemsetAsync(ix->half.rho_dev.p, 0, 4, ix->stream));
+        HIPCHK(zh_launch_row_half(ix->X.as<float>(), 0, ix->n_rows, (uint32_t)d, nullptr, ix->half.meta.as<float2>(), ix->half.rho_dev.as<uint32_t>(), nullptr, 0, ix->stream));
         float rho_m = 0.f;
-        HIPCHK(hipMemcpyAsync(&rho_m, ix->row_rho_dev.p, 4, hipMemcpyDeviceToHost, ix->stream));
+        HIPCHK(hipMemcpyAsync(&rho_m, ix->half.rho_dev.p, 4, hipMemcpyDeviceToHost, ix->stream));
         HIPCHK(hipStreamSynchronize(ix->stream));
-        ix->row_rho = rho_m;
-        ix->scale_rows = ix->n_rows; ix->scale_gen = ix->rows_gen;
+        ix->half.mark_built(ix, rho_m);
         *ok = true;
         return ZH_OK;
     }
-    // a copy that was released (the meta-only state, or no room at all) holds none of the rows scale_rows speaks of: made again from row 0
-    const bool had_copy = ix->row_half.p && ix->row_meta.p;
-    if (ix->row_half.ensure(std::max<uint64_t>(tiles, 1) * 16 * d * 2, true, ix->stream) != ZH_OK ||
-        ix->row_meta.ensure(std::max<uint64_t>(tiles, 1) * 16 * sizeof(float2), true, ix->stream) != ZH_OK || ix->row_rho_dev.ensure(4) != ZH_OK) {
-        ix->row_half.release(); ix->row_meta.release();
-        ix->row_half_failed = true;
-        ix->scale_rows = ix->n_rows; ix->scale_gen = ix->rows_gen;
+    // a copy that was released (the meta-only state, or no room at all) holds none of the rows its stamp speaks of: made again from row 0
+    const bool had_copy = ix->half.tiles.p && ix->half.meta.p;
+    if (ix->half.tiles.ensure(std::max<uint64_t>(tiles, 1) * 16 * d * 2, true, ix->stream) != ZH_OK ||
+        ix->half.meta.ensure(std::max<uint64_t>(tiles, 1) * 16 * sizeof(float2), true, ix->stream) != ZH_OK || ix->half.rho_dev.ensure(4) != ZH_OK) {
+        ix->half.tiles.release(); ix->half.meta.release();
+        ix->half.mark_failed(ix);
         return ZH_OK;
     }
-    uint64_t from = ix->scale_rows;
+    uint64_t from = ix->half.at.rows;
     {
         const int rcq = quiesce_before_rewrite();
         if (rcq) return rcq;
     }
     // rows appended since the order was made keep position = id and share no tile with their leaf mates: once they are a quarter of the table
     // the copy is made again, in an order measured on all of it
-    const bool stale_order = ix->perm_rows && ix->n_rows - ix->perm_rows > ix->perm_rows / 4;
-    if (!had_copy || ix->scale_gen != ix->rows_gen || from > ix->n_rows || stale_order) {
+    const bool stale_order = ix->order.rows && ix->n_rows - ix->order.rows > ix->order.rows / 4;
+    if (!had_copy || ix->half.at.gen != ix->rows_gen || from > ix->n_rows || stale_order) {
         from = 0;
-        HIPCHK(hipMemsetAsync(ix->row_rho_dev.p, 0, 4, ix->stream));
+        HIPCHK(hipMemsetAsync(ix->half.rho_dev.p, 0, 4, ix->stream));
     }
     if (from == 0) {  // a copy made from scratch: in tree-0 leaf order where the forest allows (rows appended later keep position = id)
         int rcp = build_scan_perm(ix);
         if (rcp) return rcp;
     }
-    HIPCHK(zh_launch_row_half(ix->X.as<float>(), from, ix->n_rows - from, (uint32_t)d, ix->row_half.p, ix->row_meta.as<float2>(),
-                              ix->row_rho_dev.as<uint32_t>(), ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr, ix->perm_rows, ix->stream));
+    HIPCHK(zh_launch_row_half(ix->X.as<float>(), from, ix->n_rows - from, (uint32_t)d, ix->half.tiles.p, ix->half.meta.as<float2>(),
+                              ix->half.rho_dev.as<uint32_t>(), ix->order.rows ? ix->order.perm.as<uint32_t>() : nullptr, ix->order.rows, ix->stream));
     float rho = 0.f;
-    HIPCHK(hipMemcpyAsync(&rho, ix->row_rho_dev.p, 4, hipMemcpyDeviceToHost, ix->stream));
+    HIPCHK(hipMemcpyAsync(&rho, ix->half.rho_dev.p, 4, hipMemcpyDeviceToHost, ix->stream));
     HIPCHK(hipStreamSynchronize(ix->stream));
-    ix->row_rho = rho;
-    ix->scale_rows = ix->n_rows; ix->scale_gen = ix->rows_gen;
+    ix->half.mark_built(ix, rho);
     *ok = true;
     return ZH_OK;
 }
@@ -2138,41 +2232,38 @@ static int ensure_row_half(zh_index *ix, bool *ok) {
 // caller that wants the other kind than the one present (tests switching kernels) gets the copy re-made.
 static int ensure_row_half128(zh_index *ix, bool *ok, bool want_bytes) {
     *ok = false;
-    const bool bytes = want_bytes && !ix->h128_not_bytes;
-    const bool current = ix->h128_gen == ix->rows_gen && ix->h128_rows == ix->n_rows;
-    if (current && (ix->h128_failed || ix->h128_bytes == bytes)) { *ok = !ix->h128_failed; return ZH_OK; }
-    ix->h128_failed = false;
+    zh_index::RowHalf128View &v = ix->half128;
+    const bool bytes = want_bytes && !v.not_bytes;
+    if (v.current(ix) && (v.failed || v.bytes == bytes)) { *ok = !v.failed; return ZH_OK; }
+    v.retry();
     size_t mem_free = 0, mem_total = 0;
     const uint64_t want = std::max<uint64_t>(ix->n_rows, 1) * (bytes ? 128 : 256);
-    const bool room = want <= ix->row_half128.cap || (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_free >= want + want / 2 + mem_total / 16);
-    if (!room || ix->row_half128.ensure(want, true, ix->stream) != ZH_OK || ix->row_rho_dev.ensure(12) != ZH_OK) {
-        ix->row_half128.release();
-        ix->h128_failed = true; ix->h128_bytes = false;
-        ix->h128_rows = ix->n_rows; ix->h128_gen = ix->rows_gen;
+    const bool room = want <= ix->half128.copy.cap || (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_free >= want + want / 2 + mem_total / 16);
+    if (!room || ix->half128.copy.ensure(want, true, ix->stream) != ZH_OK || ix->half.rho_dev.ensure(12) != ZH_OK) {
+        ix->half128.copy.release();
+        v.mark_failed(ix);
         return ZH_OK;
     }
-    uint64_t from = (ix->h128_gen == ix->rows_gen && ix->h128_rows <= ix->n_rows && ix->h128_bytes == bytes) ? ix->h128_rows.load() : 0;
+    uint64_t from = v.extend_from(ix, bytes);
     {
         const int rcq = quiesce_before_rewrite();
         if (rcq) return rcq;
     }
     if (bytes) {
-        uint32_t *dflag = ix->row_rho_dev.as<uint32_t>() + 2, flag = 0;
+        uint32_t *dflag = ix->half.rho_dev.as<uint32_t>() + 2, flag = 0;
         HIPCHK(hipMemsetAsync(dflag, 0, 4, ix->stream));
-        HIPCHK(zh_launch_row_byte128(ix->X.as<float>(), from, ix->n_rows - from, ix->row_half128.p, dflag, ix->stream));
+        HIPCHK(zh_launch_row_byte128(ix->X.as<float>(), from, ix->n_rows - from, ix->half128.copy.p, dflag, ix->stream));
         HIPCHK(hipMemcpyAsync(&flag, dflag, 4, hipMemcpyDeviceToHost, ix->stream));
         HIPCHK(hipStreamSynchronize(ix->stream));
         if (!flag) {
-            ix->h128_bytes = true; ix->h128_rho = 0.f; ix->h128_ex = 14;
-            ix->h128_rows = ix->n_rows; ix->h128_gen = ix->rows_gen;
+            v.mark_bytes(ix);
             *ok = true;
             return ZH_OK;
         }
-        ix->h128_not_bytes = true;  // some row is not a row of bytes: the copy of halves, from the first row, now and from now on
-        ix->h128_bytes = false; ix->h128_gen = 0;
+        v.found_not_bytes();  // some row is not a row of bytes: the copy of halves, from the first row, now and from now on
         return ensure_row_half128(ix, ok, false);
     }
-    uint32_t *dmax = ix->row_rho_dev.as<uint32_t>() + 1;
+    uint32_t *dmax = ix->half.rho_dev.as<uint32_t>() + 1;
     for (int pass = 0; pass < 2; pass++) {
         uint32_t mbits = 0;
         HIPCHK(hipMemsetAsync(dmax, 0, 4, ix->stream));
@@ -2184,19 +2275,17 @@ static int ensure_row_half128(zh_index *ix, bool *ok, bool want_bytes) {
         int ex = 14;
         if (m > 0.f) (void)frexpf(m, &ex);
         ex = std::min(std::max(ex, -100), 100);
-        if (from == 0) { ix->h128_ex = ex; break; }
-        if (ex <= ix->h128_ex) break;
+        if (from == 0) { v.set_scale(ex); break; }
+        if (ex <= v.ex) break;
         from = 0;  // the appended rows do not fit the scale: the whole copy again, under theirs
     }
-    if (from == 0) HIPCHK(hipMemsetAsync(ix->row_rho_dev.p, 0, 4, ix->stream));
-    HIPCHK(zh_launch_row_half128(ix->X.as<float>(), from, ix->n_rows - from, ldexpf(1.f, 14 - ix->h128_ex), ix->row_half128.p,
-                                 ix->row_rho_dev.as<uint32_t>(), ix->stream));
+    if (from == 0) HIPCHK(hipMemsetAsync(ix->half.rho_dev.p, 0, 4, ix->stream));
+    HIPCHK(zh_launch_row_half128(ix->X.as<float>(), from, ix->n_rows - from, ldexpf(1.f, 14 - v.ex), ix->half128.copy.p,
+                                 ix->half.rho_dev.as<uint32_t>(), ix->stream));
     float rho = 0.f;
-    HIPCHK(hipMemcpyAsync(&rho, ix->row_rho_dev.p, 4, hipMemcpyDeviceToHost, ix->stream));
+    HIPCHK(hipMemcpyAsync(&rho, ix->half.rho_dev.p, 4, hipMemcpyDeviceToHost, ix->stream));
     HIPCHK(hipStreamSynchronize(ix->stream));
-    ix->h128_rho = from == 0 ? rho : std::max(rho, ix->h128_rho);
-    ix->h128_bytes = false;
-    ix->h128_rows = ix->n_rows; ix->h128_gen = ix->rows_gen;
+    v.mark_halves(ix, from == 0 ? rho : std::max(rho, v.rho.load()));
     *ok = true;
     return ZH_OK;
 }
@@ -2210,19 +2299,23 @@ static bool use_approx(const zh_index *ix, const ZhTotals &tot, size_t B, size_t
 // The half-width scan on the matrix cores (scan_mfma_kernel) where it has a kernel and the index can keep an fp16 copy of its rows
 // (+50 % of the row table; ensure_row_half): mode 5 keeps the VALU kernel, which reads the f32 rows.
 static bool mfma_wanted(const zh_index *ix) {
-    return ix->sweep_mode != 5 && zh_scan_mfma_supported(ix->opt.dim, ix->n_trees) && !ix->mfma_f32_off &&
-           !(ix->row_half_failed && ix->scale_gen == ix->rows_gen && ix->scale_rows == ix->n_rows);
+    return ix->sweep_mode != 5 && zh_scan_mfma_supported(ix->opt.dim, ix->n_trees) && !ix->fb.mfma_f32_off && !ix->half.known_failed(ix);
+}
+// the sweep a batch is asked for: zh_set_sweep_mode where it names one (0 and 3 leave the choice open), else ZH_SWEEP_MODE=leaf|scan|approx (read
+// once); 5 asks for what 4 does (only mfma_wanted tells them apart).  0: chosen per batch
+static int asked_sweep_mode(const zh_index *ix) {
+    static const int forced = [] { const char *e = getenv("ZH_SWEEP_MODE"); return !e ? 0 : (e[0] == 's' ? 2 : (e[0] == 'a' ? 4 : 1)); }();
+    const int sm_ = ix->sweep_mode.load();
+    const int mode = sm_ == 3 ? forced : (sm_ ? sm_ : forced);
+    return mode == 5 ? 4 : mode;
 }
 static bool choose_scan(const zh_index *ix, const ZhTotals &tot, int metric, size_t B, size_t k) {
-    static const int forced = [] { const char *e = getenv("ZH_SWEEP_MODE"); return !e ? 0 : (e[0] == 's' ? 2 : (e[0] == 'a' ? 4 : 1)); }();
     const uint32_t d = ix->opt.dim, T = ix->n_trees;
-    const int sm_ = ix->sweep_mode.load();
-    int mode = sm_ == 3 ? forced : (sm_ ? sm_ : forced);
-    if (mode == 5) mode = 4;
+    int mode = asked_sweep_mode(ix);
     if (mode == 6) mode = 1;
-    if (mode == 1 || !zh_scan_sweep_supported(d, T, metric) || ix->row_leaf_failed || ix->scan_unsafe) return false;
+    if (mode == 1 || !zh_scan_sweep_supported(d, T, metric) || ix->row_leaf.failed || ix->scan_unsafe) return false;
     if (mode == 2 || mode == 4) return true;
-    if (!ix->row_leaf_valid && ix->batches_since_change.load() < 3) return false;  // (the row -> leaf table is built for a forest that stays)
+    if (!ix->row_leaf.valid && ix->fb.batches_since_change.load() < 3) return false;  // (the row -> leaf table is built for a forest that stays)
     const double row_b = 4.0 * d;
     const double t_leaf = (double)tot.group_rows * row_b / (d >= 256 ? 6.0e12 : 5.5e12);
     // with half-width queries (zh_approx.hip) a pair pulls 2 d bytes through the vector L1 instead of 4 d: measured 0.157 ns per pair at
@@ -2242,10 +2335,7 @@ static bool choose_scan(const zh_index *ix, const ZhTotals &tot, int metric, siz
 // product determines, the dimensions its groups divide, batches in the few-visits-per-pair regime (long leaves) whose candidate
 // lists fit the per-query sort.  ZH_SWEEP_MODE=scan / zh_set_sweep_mode(2) keep the f32 scan; =approx / mode 4 say so explicitly.
 static bool use_approx(const zh_index *ix, const ZhTotals &tot, size_t B, size_t k, int metric) {
-    static const int forced = [] { const char *e = getenv("ZH_SWEEP_MODE"); return !e ? 0 : (e[0] == 's' ? 2 : (e[0] == 'a' ? 4 : 1)); }();
-    const int sm_ = ix->sweep_mode.load();
-    int mode = sm_ == 3 ? forced : (sm_ ? sm_ : forced);
-    if (mode == 5) mode = 4;
+    const int mode = asked_sweep_mode(ix);
     if (mode == 2 || mode == 1 || mode == 6) return false;
     if (!zh_scan_approx_supported(ix->opt.dim, ix->n_trees, metric) || k > 256 || B == 0 || B >= (1u << 24)) return false;  // (24 bits of a packed pair record)
     if (tot.takes > 2048ull * B || tot.visits > 8ull * B * ix->n_trees) return false;
@@ -2253,7 +2343,7 @@ static bool use_approx(const zh_index *ix, const ZhTotals &tot, size_t B, size_t
     // the scan (3.28 against 3.42 ms per launch) and pays more than that for the interval stages: from ~5 pairs per stored row on
     // (the matrix-core kernel reads half the row bytes as well and multiplies for nothing: measured from d = 256 and ~2 pairs per stored row on)
     const bool mfma = mfma_wanted(ix);
-    if (mode != 4 && (ix->approx_strikes.load() >= 2 || !(mfma ? ix->opt.dim >= 256 : zh_approx_pays(ix->opt.dim)) ||
+    if (mode != 4 && (ix->fb.approx_strikes.load() >= 2 || !(mfma ? ix->opt.dim >= 256 : zh_approx_pays(ix->opt.dim)) ||
                       tot.rows < (mfma ? 2 : 5) * ix->n_rows))
         return false;
     return true;
@@ -2267,8 +2357,8 @@ static bool use_approx_leaf(const zh_index *ix, const ZhTotals &tot, size_t B, s
     if (ix->opt.dim != 128 || !zh_sweep_has_predicate(128, metric)) return false;
     if (ix->sweep_mode != 6 && (env_sweep || (ix->sweep_mode != 0 && ix->sweep_mode != 3))) return false;
     if (k > 256 || B == 0 || B >= (1u << 24) || tot.takes > 2048ull * B || tot.visits > 8ull * B * ix->n_trees) return false;
-    if (ix->h128_failed && ix->h128_gen == ix->rows_gen && ix->h128_rows == ix->n_rows) return false;
-    if (ix->sweep_mode != 6 && (ix->approx_strikes.load() >= 2 || tot.group_rows < (4u << 20))) return false;
+    if (ix->half128.known_failed(ix)) return false;
+    if (ix->sweep_mode != 6 && (ix->fb.approx_strikes.load() >= 2 || tot.group_rows < (4u << 20))) return false;
     return true;
 }
 
@@ -2321,7 +2411,7 @@ static uint32_t choose_dense_planes(zh_index *ix, size_t B, size_t k) {
 static bool use_score_hash(const zh_index *ix, size_t B, uint32_t P_dense) {
     static const int forced = [] { const char *e = getenv("ZH_HASH_MODE"); return !e ? 0 : (e[0] == 's' ? 2 : 1); }();
     const int mode = ix->hash_mode ? ix->hash_mode : forced;
-    if (mode == 1 || !ix->samples_valid || ix->n_planes == 0 || P_dense < ix->n_planes) return false;
+    if (mode == 1 || !ix->samples.valid || ix->n_planes == 0 || P_dense < ix->n_planes) return false;
     const size_t Bp = (B + 3) & ~(size_t)3;  // (the kernels take queries four at a time: the batch is padded with zero queries)
     if ((uint64_t)ix->n_rows * Bp * 4 > (12ull << 30) || ix->n_rows > 0xFFFFFFF0ull) return false;  // the score table of ONE context (288 GB of HBM)
     if (mode == 2) return true;
@@ -2336,23 +2426,23 @@ static int launch_score_hash(zh_search_ctx *c, const float *dQ, size_t B, bool l
     zh_index *ix = c->ix;
     const uint32_t d = ix->opt.dim;
     int rc;
-    if (ix->norm_rows != ix->n_rows || ix->norm_gen != ix->rows_gen) {  // rows were added (or replaced: clear) since the norms were taken
+    if (!ix->norms.current(ix)) {  // rows were added (or replaced: clear) since the norms were taken
         std::lock_guard<std::mutex> lk(ix->blk_mu);
-        if (ix->norm_rows != ix->n_rows || ix->norm_gen != ix->rows_gen) {
-            if ((rc = ix->row_hn2.ensure(ix->n_rows * 4)) || (rc = ix->row_norm.ensure(ix->n_rows * 4))) return rc;
-            HIPCHK(zh_launch_row_norms(ix->X.as<float>(), ix->n_rows, d, ix->row_hn2.as<float>(), ix->row_norm.as<float>(), ix->stream));
+        if (!ix->norms.current(ix)) {
+            if ((rc = ix->norms.hn2.ensure(ix->n_rows * 4)) || (rc = ix->norms.norm.ensure(ix->n_rows * 4))) return rc;
+            HIPCHK(zh_launch_row_norms(ix->X.as<float>(), ix->n_rows, d, ix->norms.hn2.as<float>(), ix->norms.norm.as<float>(), ix->stream));
             HIPCHK(hipStreamSynchronize(ix->stream));
-            ix->norm_rows = ix->n_rows; ix->norm_gen = ix->rows_gen;
+            ix->norms.mark_built(ix);
         }
     }
-    if (ix->hab_planes != ix->n_planes || ix->hab_rows != ix->norm_rows || ix->hab_gen != ix->norm_gen) {  // planes were added, or the norms retaken
+    if (!ix->plane_norms.current(ix)) {  // planes were added, or the norms retaken
         std::lock_guard<std::mutex> lk(ix->blk_mu);
-        if (ix->hab_planes != ix->n_planes || ix->hab_rows != ix->norm_rows || ix->hab_gen != ix->norm_gen) {
-            if ((rc = ix->plane_hab.ensure(std::max<size_t>(ix->n_planes, 1) * sizeof(float4)))) return rc;
-            HIPCHK(zh_launch_plane_hab(ix->plane_samples.as<uint2>(), ix->n_planes, ix->row_hn2.as<float>(), ix->row_norm.as<float>(),
-                                       ix->plane_hab.as<float4>(), ix->stream));
+        if (!ix->plane_norms.current(ix)) {
+            if ((rc = ix->plane_norms.hab.ensure(std::max<size_t>(ix->n_planes, 1) * sizeof(float4)))) return rc;
+            HIPCHK(zh_launch_plane_hab(ix->samples.pairs.as<uint2>(), ix->n_planes, ix->norms.hn2.as<float>(), ix->norms.norm.as<float>(),
+                                       ix->plane_norms.hab.as<float4>(), ix->stream));
             HIPCHK(hipStreamSynchronize(ix->stream));
-            ix->hab_planes = ix->n_planes; ix->hab_rows = ix->norm_rows; ix->hab_gen = ix->norm_gen;
+            ix->plane_norms.mark_built(ix);
         }
     }
     if (B % 4) {  // pad the batch with zero queries to a multiple of four (their signs are computed and never read)
@@ -2385,8 +2475,8 @@ static int launch_score_hash(zh_search_ctx *c, const float *dQ, size_t B, bool l
                                     c->wScore.as<float>(), s));
     HIPCHK(zh_launch_row_norms(dQ, B, d, nullptr, c->wQnorm.as<float>(), s));
     ZhTotals *tot = c->wTotals.as<ZhTotals>();
-    HIPCHK(zh_launch_score_signs(c->wScore.as<float>(), (uint32_t)B, ix->plane_samples.as<uint2>(), ix->n_planes, ix->row_hn2.as<float>(),
-                                 ix->row_norm.as<float>(), ix->plane_hab.as<float4>(), c->wQnorm.as<float>(), dQ, d, ix->planes.as<float>(), ix->consts.as<float>(),
+    HIPCHK(zh_launch_score_signs(c->wScore.as<float>(), (uint32_t)B, ix->samples.pairs.as<uint2>(), ix->n_planes, ix->norms.hn2.as<float>(),
+                                 ix->norms.norm.as<float>(), ix->plane_norms.hab.as<float4>(), c->wQnorm.as<float>(), dQ, d, ix->planes.as<float>(), ix->consts.as<float>(),
                                  c->wBits.as<uint32_t>(), c->wpq, c->wFixList.as<uint2>(), fix_cap, &tot->hash_fixups,
                                  lazy ? c->wUnc.as<uint32_t>() : nullptr, s));
     return ZH_OK;
@@ -2398,7 +2488,7 @@ int ctx_wait(zh_search_ctx *c);
 // determine, leaves short enough for the per-lane selection, and forests this library built (a row is in one leaf per tree).
 static bool use_prefilter(const zh_index *ix, const zh_search_ctx *c, size_t k, int metric) {
     // (mode 3 keeps trying past two strikes -- a caller who knows the overflows are rare -- but not past eight in a row: every one is a batch computed twice)
-    const uint32_t strikes = ix->prefilter_strikes.load();
+    const uint32_t strikes = ix->fb.prefilter_strikes.load();
     if (!c->score_hash || c->prefilter_off_once || c->stream_ordered || (strikes >= 2 && ix->sweep_mode != 3) || strikes >= 8) return false;
     static const bool env_sweep = getenv("ZH_SWEEP_MODE") != nullptr;
     if ((ix->sweep_mode != 0 && ix->sweep_mode != 3) || (env_sweep && ix->sweep_mode != 3)) return false;  // a sweep was asked for
@@ -2410,11 +2500,11 @@ static bool use_prefilter(const zh_index *ix, const zh_search_ctx *c, size_t k, 
 
 static int build_leaf_meta(zh_index *ix) {  // under blk_mu; the norms are those launch_score_hash just validated
     int rc;
-    if ((rc = ix->leaf_meta.ensure(ix->n_leaf_ids * sizeof(float4)))) return rc;
-    HIPCHK(zh_launch_leaf_meta(ix->leaf_ids.as<uint32_t>(), ix->n_leaf_ids, ix->row_hn2.as<float>(), ix->row_norm.as<float>(),
-                               ix->leaf_meta.as<float4>(), ix->stream));
+    if ((rc = ix->leaf_meta.slots.ensure(ix->n_leaf_ids * sizeof(float4)))) return rc;
+    HIPCHK(zh_launch_leaf_meta(ix->leaf_ids.as<uint32_t>(), ix->n_leaf_ids, ix->norms.hn2.as<float>(), ix->norms.norm.as<float>(),
+                               ix->leaf_meta.slots.as<float4>(), ix->stream));
     HIPCHK(hipStreamSynchronize(ix->stream));
-    ix->leaf_meta_valid = true; ix->meta_rows = ix->norm_rows; ix->meta_gen = ix->norm_gen;
+    ix->leaf_meta.mark_built(ix);
     return ZH_OK;
 }
 
@@ -2451,10 +2541,10 @@ static int ctx_begin(zh_search_ctx *c, const float *const *dQs, size_t nwin, siz
     const uint64_t pairs = (uint64_t)B * T;
     if (pairs >= (1ull << 26)) { c->state = 0; return fail(ZH_ELIMIT, "batch * num_trees >= 2^26"); }
     c->P_dense = choose_dense_planes(ix, B, k);
-    const uint32_t seen = ix->batches_since_change.fetch_add(1);
-    if (c->P_dense >= ix->n_planes && ix->n_planes && !ix->blocks_valid && seen >= 2) {  // the forest has been stable for a few batches
+    const uint32_t seen = ix->fb.batches_since_change.fetch_add(1);
+    if (c->P_dense >= ix->n_planes && ix->n_planes && !ix->blocks.valid && seen >= 2) {  // the forest has been stable for a few batches
         std::lock_guard<std::mutex> lk(ix->blk_mu);
-        if (!ix->blocks_valid && (rc = build_blocks(ix))) { c->state = 0; return rc; }
+        if (!ix->blocks.valid && (rc = build_blocks(ix))) { c->state = 0; return rc; }
     }
     c->wpq = (c->P_dense + 255) / 256 * 8;  // sign words per query, a multiple of eight: score_signs_kernel stores whole 32-byte sectors
     const size_t nn = std::max<uint32_t>(ix->n_nodes, 1);
@@ -2500,7 +2590,7 @@ static int ctx_begin(zh_search_ctx *c, const float *const *dQs, size_t nwin, siz
     ZhForestDev f = forest_dev(ix);
     HIPCHK(hipEventRecord(c->ev[0], s));
     if (metric == ZH_COSINE) HIPCHK(zh_launch_qnorm(dQ, (uint32_t)B, d, c->wQQ.as<float>(), s));
-    const bool blocked = c->P_dense >= ix->n_planes && ix->n_planes && ix->blocks_valid;
+    const bool blocked = c->P_dense >= ix->n_planes && ix->n_planes && ix->blocks.valid;
     c->lazy_fix = c->score_hash && blocked && ((B + 3) & ~(size_t)3) != 4 && d % 4 == 0;  // (plane_above_wave's shape)
     if (c->lazy_fix && (rc = c->wUnc.ensure(std::max<size_t>((size_t)B * c->wpq * 4, 4)))) return rc;
     if (c->score_hash) {
@@ -2510,9 +2600,9 @@ static int ctx_begin(zh_search_ctx *c, const float *const *dQs, size_t nwin, siz
     HIPCHK(hipEventRecord(c->ev[1], s));
     if (blocked) {
         ZhBlocksDev bd;
-        bd.recs = ix->blk_recs.as<int4>(); bd.upper = ix->blk_upper.as<int4>(); bd.root = ix->blk_roots.as<int2>();
-        bd.n_blocks = ix->n_blocks; bd.n_upper = ix->n_upper; bd.inner_only = ix->blocks_inner ? 1u : 0u;
-        bd.recs_b = ix->blocks_inner ? bd.recs + ix->blk_recs_b : nullptr;
+        bd.recs = ix->blocks.recs.as<int4>(); bd.upper = ix->blocks.upper.as<int4>(); bd.root = ix->blocks.roots.as<int2>();
+        bd.n_blocks = ix->blocks.n_blocks; bd.n_upper = ix->blocks.n_upper; bd.inner_only = ix->blocks.inner ? 1u : 0u;
+        bd.recs_b = ix->blocks.inner ? bd.recs + ix->blocks.recs_b.load() : nullptr;
         HIPCHK(zh_launch_walk_blocked(f, bd, (uint32_t)B, (int32_t)k, c->wBits.as<uint32_t>(), c->wpq, c->wCounts.as<ZhPairCounts>(),
                                       c->wInline.as<ZhVisit>(), leaf_count, walk_log(c), c->lazy_fix ? c->wUnc.as<uint32_t>() : nullptr, dQ, d, s));
     } else
@@ -2539,9 +2629,9 @@ static int finish_prefilter(zh_search_ctx *c, uint64_t *dOutIds, uint64_t *dOutK
     const size_t B = c->B, k = c->k, nwin = c->nwin, bwin = c->bwin;
     hipStream_t s = c->s;
     int rc;
-    if (!ix->leaf_meta_valid || ix->meta_rows != ix->norm_rows || ix->meta_gen != ix->norm_gen) {
+    if (!ix->leaf_meta.current(ix)) {
         std::lock_guard<std::mutex> lk(ix->blk_mu);
-        if ((!ix->leaf_meta_valid || ix->meta_rows != ix->norm_rows || ix->meta_gen != ix->norm_gen) && (rc = build_leaf_meta(ix))) return rc;
+        if (!ix->leaf_meta.current(ix) && (rc = build_leaf_meta(ix))) return rc;
     }
     const char *cap_e = getenv("ZH_PREFILTER_CAP");  // tests: lists that run over (read per batch)
     const uint32_t cap_env = cap_e ? (uint32_t)atoi(cap_e) : 0u;
@@ -2556,7 +2646,7 @@ static int finish_prefilter(zh_search_ctx *c, uint64_t *dOutIds, uint64_t *dOutK
         return rc;
     HIPCHK(hipMemsetAsync(c->wPfCtl.p, 0, 16, s));
     ZhPrefilter pf;
-    pf.S = c->wScore.as<float>(); pf.Bp = c->score_Bp; pf.leaf_meta = ix->leaf_meta.as<float4>(); pf.qnorm = c->wQnorm.as<float>();
+    pf.S = c->wScore.as<float>(); pf.Bp = c->score_Bp; pf.leaf_meta = ix->leaf_meta.slots.as<float4>(); pf.qnorm = c->wQnorm.as<float>();
     pf.rows = c->wPfRows.as<uint32_t>(); pf.counts = c->wPfCounts.as<uint32_t>(); pf.tau = reinterpret_cast<float *>(pf.counts + lists); pf.cap = cap;
     pf.amb = c->wPfAmb.as<uint4>(); pf.amb_cap = amb_cap; pf.ctl = c->wPfCtl.as<uint32_t>();
     ZhForestDev f = forest_dev(ix);
@@ -2670,10 +2760,10 @@ static int ctx_finish(zh_search_ctx *c, uint64_t *const *outIds, uint64_t *const
         }
     }
     c->scan = choose_scan(ix, tot, c->metric, B, k);
-    if (c->scan && (!ix->row_leaf_valid || ix->row_leaf_rows != ix->n_rows)) {  // first table scan since the trees (or the row count) changed
+    if (c->scan && !ix->row_leaf.current(ix)) {  // first table scan since the trees (or the row count) changed
         std::lock_guard<std::mutex> lk(ix->blk_mu);
-        if ((!ix->row_leaf_valid || ix->row_leaf_rows != ix->n_rows) && !ix->row_leaf_failed && (rc = build_row_leaf(ix))) return rc;
-        if (!ix->row_leaf_valid || ix->row_leaf_rows != ix->n_rows) c->scan = false;
+        if (!ix->row_leaf.current(ix) && !ix->row_leaf.failed && (rc = build_row_leaf(ix))) return rc;
+        if (!ix->row_leaf.current(ix)) c->scan = false;
     }
     if (c->scan) {
         const size_t nn = std::max<uint32_t>(ix->n_nodes, 1);
@@ -2695,28 +2785,28 @@ static int ctx_finish(zh_search_ctx *c, uint64_t *const *outIds, uint64_t *const
         std::lock_guard<std::mutex> lk(ix->blk_mu);
         if ((rc = ensure_row_half128(ix, &ok, want_bytes))) return rc;
         c->approx = c->approx_leaf = ok;
-        c->approx_bytes = ok && ix->h128_bytes;
+        c->approx_bytes = ok && ix->half128.bytes;
     }
     ZhApprox ap{};
     // the scan on the matrix cores, from an fp16 copy of the stored rows (+50 % of the row table, made on first use); no room for it, or mode 5:
     // the VALU kernel on the f32 rows
     bool mfma = c->approx && !c->approx_leaf && mfma_wanted(ix) && B < (1u << 23) - 1;  // (the column pass packs query + 1 into 23 bits of an LDS word)
-    const uint2 *scan_row_leaf = ix->row_leaf.as<uint2>();
+    const uint2 *scan_row_leaf = ix->row_leaf.table.as<uint2>();
     if (mfma) {
         std::lock_guard<std::mutex> lk(ix->blk_mu);
         if ((rc = ensure_row_half(ix, &mfma))) return rc;
-        if (mfma && ix->perm_rows) {
+        if (mfma && ix->order.rows) {
             if ((rc = ensure_row_leaf_p(ix))) return rc;
-            if (!ix->perm_rows) {  // no room for the table in the scan's order: the copy again, in id order, and no further attempt
-                ix->row_order_off = true;
-                ix->scale_gen = 0;
+            if (!ix->order.rows) {  // no room for the table in the scan's order: the copy again, in id order, and no further attempt
+                ix->order.switch_off();
+                ix->half.remake();
                 if ((rc = ensure_row_half(ix, &mfma))) return rc;
             } else
-                scan_row_leaf = ix->row_leaf_p.as<uint2>();
+                scan_row_leaf = ix->order.row_leaf_p.as<uint2>();
         }
     }
     c->approx_mfma = mfma;
-    c->approx_f32rows = mfma && ix->row_half.p == nullptr;
+    c->approx_f32rows = mfma && ix->half.tiles.p == nullptr;
     if (c->approx) {
         // per query: what final_interval_kernel's sort holds (48 KB per query of HBM).  A visit hands on the rows its intervals cannot
         // rule out: a few more than `take` -- or dozens more where the keys are dense around the cut: the parity cosine key on iid
@@ -2725,7 +2815,7 @@ static int ctx_finish(zh_search_ctx *c, uint64_t *const *outIds, uint64_t *const
         const char *cap_e = getenv("ZH_APX_CAPS");  // tests: "capq,ex_cap,ex_rows" -- lists and tables that run over (read per batch)
         unsigned e_capq = 0, e_excap = 0, e_exrows = 0;
         if (cap_e) sscanf(cap_e, "%u,%u,%u", &e_capq, &e_excap, &e_exrows);
-        const uint32_t capq = e_capq ? std::min(e_capq, 8192u) : (ix->approx_strikes.load() ? 8192u : 4096u);
+        const uint32_t capq = e_capq ? std::min(e_capq, 8192u) : (ix->fb.approx_strikes.load() ? 8192u : 4096u);
         const uint32_t ex_cap = e_excap ? e_excap : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096, tot.visits / 4 + 1024), 1u << 24);
         const uint32_t ex_rows = e_exrows ? e_exrows : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1u << 20, tot.rows / 16), 1u << 26);
         if ((rc = c->wQh.ensure(B * d * 2)) || (rc = c->wQmeta.ensure(B * sizeof(float4))) || (rc = c->wApList.ensure((size_t)B * capq * 12)) ||
@@ -2739,9 +2829,9 @@ static int ctx_finish(zh_search_ctx *c, uint64_t *const *outIds, uint64_t *const
         ap.ex_keys = c->wApExKeys.as<uint64_t>(); ap.ex_ckeys = ap.ex_keys + ex_rows; ap.ex_cids = reinterpret_cast<uint32_t *>(ap.ex_ckeys + ex_rows);
         ap.ex_rows_cap = ex_rows; ap.ctl = c->wApCtl.as<uint32_t>();
         ap.n_queries = (uint32_t)B; ap.iv_cap = tot.rows;
-        ap.mfma = mfma ? 1u : 0u; ap.row_half = mfma ? ix->row_half.p : nullptr; ap.row_meta = mfma ? ix->row_meta.as<float2>() : nullptr;  // (row_half null with mfma: the scan converts the f32 rows itself)
-        ap.row_rho = mfma ? ix->row_rho : 0.f;
-        if (c->approx_leaf) { ap.mfma = 2u; ap.row_rho = ap.rho_norm = c->approx_bytes ? 0.f : ix->h128_rho; }
+        ap.mfma = mfma ? 1u : 0u; ap.row_half = mfma ? ix->half.tiles.p : nullptr; ap.row_meta = mfma ? ix->half.meta.as<float2>() : nullptr;  // (row_half null with mfma: the scan converts the f32 rows itself)
+        ap.row_rho = mfma ? ix->half.rho.load() : 0.f;
+        if (c->approx_leaf) { ap.mfma = 2u; ap.row_rho = ap.rho_norm = c->approx_bytes ? 0.f : ix->half128.rho.load(); }
         // (a row of bytes: |x|^2 <= 128 * 255^2 exactly, approx_interval's nx = sqrtf of it * (1 + 1e-5) < 2885.1; ZH_S128H_PRETEST=0, read per batch: tests)
         const char *pte = getenv("ZH_S128H_PRETEST");
         ap.nx_max = c->approx_leaf && c->approx_bytes && !(pte && pte[0] == '0') ? 2885.1f : 0.f;
@@ -2764,18 +2854,18 @@ static int ctx_finish(zh_search_ctx *c, uint64_t *const *outIds, uint64_t *const
     if (c->approx_leaf && k <= 64 && !ix->debug_keep_raw) {
         const char *fe = getenv("ZH_S128H_FUSED"), *ke = getenv("ZH_S128H_KERNEL"), *de = getenv("ZH_S128H_DMA");
         const bool lean = !(ke && ke[0] == 'r') && !(de && de[0] == '1');
-        c->approx_fused = lean && (fe ? fe[0] == '1' : (!ix->fused_off && tot.rows >= 1024 * std::max<uint64_t>(tot.visits, 1)));
+        c->approx_fused = lean && (fe ? fe[0] == '1' : (!ix->fb.fused_off && tot.rows >= 1024 * std::max<uint64_t>(tot.visits, 1)));
     }
     const int kinda = c->metric != ZH_COSINE ? 0 : (c->mode == ZH_COSINE_PARITY ? 2 : 1);
     if (c->approx_leaf)
-        HIPCHK(zh_launch_sweep128h(ix->row_half128.p, c->wQh.p, ldexpf(1.f, ix->h128_ex - 14), c->wGroups.as<ZhGroup>(), c->wGroupRowOff.as<uint64_t>(),
+        HIPCHK(zh_launch_sweep128h(ix->half128.copy.p, c->wQh.p, ldexpf(1.f, ix->half128.ex - 14), c->wGroups.as<ZhGroup>(), c->wGroupRowOff.as<uint64_t>(),
                                    tot.groups, c->wWaveGroup.as<uint32_t>(), f.leaf_ids, tot.group_rows, c->wKeys.as<uint64_t>(), hs,
                                    c->approx_fused ? &ap : nullptr, kinda, (uint32_t)k, zh_approx_bound(c->metric, d, 2), c->approx_bytes));
     else if (c->approx)
-        HIPCHK(zh_launch_scan_approx(ix->X.as<float>(), d, ix->n_rows, ap, mfma ? scan_row_leaf : ix->row_leaf.as<uint2>(), T, c->wVisitBits.as<uint32_t>(),
+        HIPCHK(zh_launch_scan_approx(ix->X.as<float>(), d, ix->n_rows, ap, mfma ? scan_row_leaf : ix->row_leaf.table.as<uint2>(), T, c->wVisitBits.as<uint32_t>(),
                                      c->wNodeVisit.as<uint4>(), c->wGroups.as<ZhGroup>(), f.group, c->metric, c->mode, hs));
     else if (c->scan)
-        HIPCHK(zh_launch_scan_sweep(ix->X.as<float>(), d, ix->n_rows, c->dQ, c->wQQ.as<float>(), ix->row_leaf.as<uint2>(), T,
+        HIPCHK(zh_launch_scan_sweep(ix->X.as<float>(), d, ix->n_rows, c->dQ, c->wQQ.as<float>(), ix->row_leaf.table.as<uint2>(), T,
                                     c->wVisitBits.as<uint32_t>(), c->wNodeVisit.as<uint4>(), c->wGroups.as<ZhGroup>(), f.group,
                                     c->metric, c->mode, c->wKeys.as<uint64_t>(), nullptr, hs));
     else
@@ -2809,7 +2899,7 @@ static int ctx_finish(zh_search_ctx *c, uint64_t *const *outIds, uint64_t *const
             HIPCHK(zh_launch_sweep(ix->X.as<float>(), d, c->dQ, c->wQQ.as<float>(), c->wGroups.as<ZhGroup>(), c->wGroupRowOff.as<uint64_t>(), tot.groups,
                                    c->wWaveGroup.as<uint32_t>(), f.leaf_ids, tot.group_rows, c->metric, c->mode, c->wKeys.as<uint64_t>(), s, run_if));
         else
-            HIPCHK(zh_launch_scan_sweep(ix->X.as<float>(), d, ix->n_rows, c->dQ, c->wQQ.as<float>(), ix->row_leaf.as<uint2>(), T,
+            HIPCHK(zh_launch_scan_sweep(ix->X.as<float>(), d, ix->n_rows, c->dQ, c->wQQ.as<float>(), ix->row_leaf.table.as<uint2>(), T,
                                         c->wVisitBits.as<uint32_t>(), c->wNodeVisit.as<uint4>(), c->wGroups.as<ZhGroup>(), f.group,
                                         c->metric, c->mode, c->wKeys.as<uint64_t>(), run_if, s));
     }
@@ -2844,7 +2934,7 @@ int ctx_wait(zh_search_ctx *c) {
             ix->stats.prefilter_fallbacks_accum++;
             ix->stats.prefilter_last_overflow = pf_flags;
         }
-        ix->prefilter_strikes.fetch_add(1);
+        ix->fb.prefilter_ran_over();
         const std::vector<const float *> q = c->sv_q;
         const std::vector<uint64_t *> ids = c->sv_ids, keys = c->sv_keys;
         const std::vector<uint32_t *> counts = c->sv_counts;
@@ -2855,7 +2945,7 @@ int ctx_wait(zh_search_ctx *c) {
         if (rc) return rc;
         return ctx_wait(c);
     }
-    if (pf) ix->prefilter_strikes = 0;
+    if (pf) ix->fb.prefilter_held();
     const ZhTotals tot = c->tot;
     uint64_t uniq = 0;
     if (ix->profiling >= 2 && tot.visits && !pf) {  // R_unique: rows of the distinct leaves touched by the batch
@@ -2895,11 +2985,9 @@ int ctx_wait(zh_search_ctx *c) {
     if (apx && c->h_ap[1]) {
         st.approx_fallbacks_accum++;
         st.approx_last_overflow = c->h_ap[1];
-        if (c->approx_mfma && c->approx_f32rows && ix->approx_strikes.load() >= 1) ix->mfma_f32_off = true;  // (8192-slot lists ran over: the VALU scan next)
-        else if (c->approx_leaf && c->approx_fused && !ix->fused_off) ix->fused_off = true;                     // (the fused sweep's lists ran over: the select pass next)
-        else ix->approx_strikes.fetch_add(1);
-    } else if (apx && (uint64_t)c->h_ap[4] > (uint64_t)c->B * (ix->approx_strikes.load() ? 5600 : 2800))  // lists 70 % full on average: some query's will run over
-        ix->approx_strikes.fetch_add(1);
+        ix->fb.approx_ran_over(c->approx_mfma && c->approx_f32rows, c->approx_leaf && c->approx_fused);
+    } else if (apx && (uint64_t)c->h_ap[4] > (uint64_t)c->B * (ix->fb.approx_strikes.load() ? 5600 : 2800))  // lists 70 % full on average: some query's will run over
+        ix->fb.approx_nearly_ran_over();
     st.prefiltered = pf ? 1 : 0;
     st.prefilter_exact_visits = pf_amb;
     st.prefilter_exact_rows = pf_exact;
@@ -3474,7 +3562,7 @@ static hipStream_t call_stream(const zh_index *ix, void *stream) { return stream
 static int score_param(int metric, int mode) { return (metric == ZH_COSINE || metric == ZH_MINKOWSKI || metric == ZH_PNORM) ? mode : 0; }
 
 // The per-call scratch, each family's buffers listed once.  The guard of a call gives its set back to the driver however the call returns: an idle
-// index holds only the live-row views (ex_live and ex_bits survive every call; zh_index_destroy frees them).  Every family scans with the exact
+// index holds only the live-row views (live_dev's list and bitmap survive every call; zh_index_destroy frees them).  Every family scans with the exact
 // search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's, the forest range search with
 // the range search's and the forest join's, the cross-join (all on its LEFT index) with the join's and its own views.
 enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024 };  // one bit per list
@@ -3534,7 +3622,7 @@ static int get_info(const zh_index *ix, Info zh_index::*slot, Info *out, const c
     return ZH_OK;
 }
 
-// Path 2's view of the fp16 copy of the rows: made if need be, and read, under blk_mu -- the caller holds it, for as long as it reads scan_perm on
+// Path 2's view of the fp16 copy of the rows: made if need be, and read, under blk_mu -- the caller holds it, for as long as it reads order.perm on
 // the device.  *have = false: no copy (no room for it, or the per-row scales alone) and path 1 answers.
 struct HalfView {
     const void *Xh = nullptr;
@@ -3548,10 +3636,10 @@ static int half_view(zh_index *ix, HalfView *v, bool *have) {
     *have = false;
     int rc = ensure_row_half(ix, &ok);
     if (rc) return rc;
-    if (!ok || !ix->row_half.p) return ZH_OK;
+    if (!ok || !ix->half.tiles.p) return ZH_OK;
     *have = true;
-    v->Xh = ix->row_half.p; v->rowMeta = ix->row_meta.as<float2>(); v->rho = ix->row_rho;
-    v->perm = ix->perm_rows ? ix->scan_perm.as<uint32_t>() : nullptr; v->perm_rows = ix->perm_rows;
+    v->Xh = ix->half.tiles.p; v->rowMeta = ix->half.meta.as<float2>(); v->rho = ix->half.rho;
+    v->perm = ix->order.rows ? ix->order.perm.as<uint32_t>() : nullptr; v->perm_rows = ix->order.rows;
     return ZH_OK;
 }
 
@@ -3618,21 +3706,19 @@ static uint32_t fill_chunk(Blocks blocks_at) {
 // removed since
 static int exact_live_rows(zh_index *ix) {
     if (ix->rows_torn) return fail(ZH_ESTATE, "%s", k_torn_msg);
-    if (ix->ex_live_rows == ix->n_rows && ix->ex_live_gen == ix->dead_gen) return ZH_OK;
+    if (ix->live_dev.current(ix)) return ZH_OK;
     std::vector<uint32_t> live;
     live.reserve(ix->n_rows - ix->n_dead);
     for (uint64_t r = 0; r < ix->n_rows; r++)
         if (!(r < ix->h_dead.size() && ix->h_dead[r])) live.push_back((uint32_t)r);
-    int rc = ix->ex_live.ensure(std::max<size_t>(live.size(), 1) * 4);
+    int rc = ix->live_dev.rows.ensure(std::max<size_t>(live.size(), 1) * 4);
     if (rc) return rc;
-    if (!live.empty()) HIPCHK(hipMemcpy(ix->ex_live.p, live.data(), live.size() * 4, hipMemcpyHostToDevice));
+    if (!live.empty()) HIPCHK(hipMemcpy(ix->live_dev.rows.p, live.data(), live.size() * 4, hipMemcpyHostToDevice));
     std::vector<uint32_t> bits((ix->n_rows + 31) / 32 + 1, 0u);
     for (uint32_t r : live) bits[r >> 5] |= 1u << (r & 31);
-    if ((rc = ix->ex_bits.ensure(bits.size() * 4))) return rc;
-    HIPCHK(hipMemcpy(ix->ex_bits.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
-    ix->ex_n_live = live.size();
-    ix->ex_live_rows = ix->n_rows;
-    ix->ex_live_gen = ix->dead_gen;
+    if ((rc = ix->live_dev.bits.ensure(bits.size() * 4))) return rc;
+    HIPCHK(hipMemcpy(ix->live_dev.bits.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
+    ix->live_dev.mark_built(ix, live.size());
     return ZH_OK;
 }
 
@@ -3704,7 +3790,7 @@ static int exact_batch2(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, i
                         uint64_t *tiles_skipped = nullptr) {
     *used = false; *overflowed = false;
     const uint32_t d = ix->opt.dim;
-    if (k == 0 || !zh_exact_mfma_supported(d, metric) || (f ? f->n_allowed : ix->ex_n_live) < std::max<uint64_t>(k, 8192)) return ZH_OK;
+    if (k == 0 || !zh_exact_mfma_supported(d, metric) || (f ? f->n_allowed : ix->live_dev.n_live) < std::max<uint64_t>(k, 8192)) return ZH_OK;
     int rc;
     HalfView v;
     bool have = false;
@@ -3716,7 +3802,7 @@ static int exact_batch2(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, i
     if (f && (v.perm != f->v.perm || v.perm_rows != f->v.perm_rows)) return ZH_OK;  // (the row order changed since f->dPos was made: path 1)
     const uint32_t cap = 16384 + 8 * k;  // first chunk (<= max(k, 4096) rows, all listed) + a few growth steps' worth of k
     if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_Qh.ensure((size_t)B * d * 2)) || (rc = ix->ex_qmeta.ensure((size_t)B * 16))) return rc;
-    ZhExact2 e{v.Xh, v.rowMeta, v.perm, v.perm_rows, f ? f->dPos : ix->ex_bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B,
+    ZhExact2 e{v.Xh, v.rowMeta, v.perm, v.perm_rows, f ? f->dPos : ix->live_dev.bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B,
                zh_approx_bound(metric, d, 1), v.rho};
     if ((rc = lists_ensure(ix, B, cap, true, &e))) return rc;
     std::vector<uint64_t> cb((size_t)B + 1);
@@ -3762,7 +3848,7 @@ static int exact_one(zh_index *ix, const float *dQ, uint32_t B, uint32_t k, int 
     if (used) inf->path = 2;
     if (used && !overflowed) return ZH_OK;
     if (overflowed) inf->redone++;
-    return exact_batch(ix, ix->ex_live.as<uint32_t>(), ix->ex_n_live, dQ, B, k, metric, mode, dIds, dKeys, dCounts, s, &inf->launches);
+    return exact_batch(ix, ix->live_dev.rows.as<uint32_t>(), ix->live_dev.n_live, dQ, B, k, metric, mode, dIds, dKeys, dCounts, s, &inf->launches);
 }
 
 static int exact_args(zh_index *ix, const float *q, size_t b, size_t k, int metric, int mode, const void *ids, const void *keys,
@@ -3775,7 +3861,7 @@ static int exact_args(zh_index *ix, const float *q, size_t b, size_t k, int metr
 static void exact_record(zh_index *ix, size_t b, zh_exact_info inf) {
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     inf.batch = b;
-    inf.rows_live = ix->ex_n_live;
+    inf.rows_live = ix->live_dev.n_live;
     ix->ex_info = inf;
 }
 
@@ -3886,7 +3972,7 @@ static int filter_prepare(zh_index *ix, const uint32_t *dFilter, uint64_t n_bits
         return rc;
     uint32_t *excl = ix->fl_bexcl.as<uint32_t>();  // [0, nb]: by row; [nb + 1, 2 nb + 1]: by position under a row order; then the tile count
     uint32_t *dTiles = excl + 2 * (nb + 1), h_tiles = 0;
-    HIPCHK(zh_launch_filter_and(dFilter, n_bits, ix->ex_bits.as<uint32_t>(), n, ix->fl_bits.as<uint32_t>(), ix->fl_bcount.as<uint32_t>(), excl,
+    HIPCHK(zh_launch_filter_and(dFilter, n_bits, ix->live_dev.bits.as<uint32_t>(), n, ix->fl_bits.as<uint32_t>(), ix->fl_bcount.as<uint32_t>(), excl,
                                 ix->fl_tmp.as<uint32_t>(), dTiles, s));
     f->cum.resize(nb + 1);
     HIPCHK(hipMemcpyAsync(f->cum.data(), excl, (nb + 1) * 4, hipMemcpyDeviceToHost, s));
@@ -3953,7 +4039,7 @@ static int filtered_bits_fit(zh_index *ix, uint64_t n_bits) {
 static void filtered_record(zh_index *ix, size_t b, const ExactFilter &f, zh_filtered_info inf) {
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     inf.batch = b;
-    inf.rows_live = ix->ex_n_live;
+    inf.rows_live = ix->live_dev.n_live;
     inf.rows_allowed = f.n_allowed;
     ix->fl_info = inf;
 }
@@ -4017,7 +4103,7 @@ struct RangeRun {
 static int range_batch1(zh_index *ix, const float *dQ, uint32_t B, const uint64_t *dMaxK, int metric, int mode, uint64_t pool_cap, hipStream_t s,
                         uint64_t *launches) {
     const uint32_t d = ix->opt.dim;
-    const uint64_t n_live = ix->ex_n_live;
+    const uint64_t n_live = ix->live_dev.n_live;
     const uint64_t rc_rows = std::min<uint64_t>(std::max<uint64_t>(256, ZH_EXACT_KEY_BYTES / 8 / B), n_live);
     int rc;
     if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_keys.ensure((size_t)B * rc_rows * 8))) return rc;
@@ -4027,9 +4113,9 @@ static int range_batch1(zh_index *ix, const float *dQ, uint32_t B, const uint64_
     HIPCHK(hipMemsetAsync(ix->rg_ctr.p, 0, 16, s));
     for (uint64_t p0 = 0; p0 < n_live; p0 += rc_rows) {
         const uint32_t nr = (uint32_t)std::min<uint64_t>(rc_rows, n_live - p0);
-        HIPCHK(zh_launch_exact_score(ix->X.as<float>(), d, ix->ex_live.as<uint32_t>(), p0, nr, dQ, ix->ex_QQ.as<float>(), B, metric, param,
+        HIPCHK(zh_launch_exact_score(ix->X.as<float>(), d, ix->live_dev.rows.as<uint32_t>(), p0, nr, dQ, ix->ex_QQ.as<float>(), B, metric, param,
                                      ix->ex_keys.as<uint64_t>(), rc_rows, s));
-        HIPCHK(zh_launch_range_collect(ix->ex_keys.as<uint64_t>(), rc_rows, ix->ex_live.as<uint32_t>(), p0, nr, B, dMaxK, ix->rg_cnt.as<uint32_t>(),
+        HIPCHK(zh_launch_range_collect(ix->ex_keys.as<uint64_t>(), rc_rows, ix->live_dev.rows.as<uint32_t>(), p0, nr, B, dMaxK, ix->rg_cnt.as<uint32_t>(),
                                        ix->rg_ctr.as<unsigned long long>(), ix->rg_pv0.as<uint64_t>(), ix->rg_pk0.as<uint64_t>(), pool_cap, s));
         (*launches)++;
     }
@@ -4043,7 +4129,7 @@ static int range_batch2(zh_index *ix, const float *dQ, uint32_t B, const uint64_
                         hipStream_t s, bool *used, unsigned long long h_ctr[2], uint64_t *launches) {
     *used = false;
     const uint32_t d = ix->opt.dim;
-    if (!zh_exact_mfma_supported(d, metric) || ix->ex_n_live < 8192) return ZH_OK;
+    if (!zh_exact_mfma_supported(d, metric) || ix->live_dev.n_live < 8192) return ZH_OK;
     int rc;
     HalfView v;
     bool have = false;
@@ -4055,7 +4141,7 @@ static int range_batch2(zh_index *ix, const float *dQ, uint32_t B, const uint64_
     if ((rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = ix->ex_Qh.ensure((size_t)B * d * 2)) || (rc = ix->ex_qmeta.ensure((size_t)B * 16)) ||
         (rc = ix->ex_tau.ensure((size_t)B * 4)) || (rc = ix->rg_cand.ensure(cand_cap * 8)))
         return rc;
-    ZhExact2 e{v.Xh, v.rowMeta, v.perm, v.perm_rows, ix->ex_bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B, zh_approx_bound(metric, d, 1), v.rho,
+    ZhExact2 e{v.Xh, v.rowMeta, v.perm, v.perm_rows, ix->live_dev.bits.as<uint32_t>(), ix->ex_Qh.p, ix->ex_qmeta.as<float4>(), B, zh_approx_bound(metric, d, 1), v.rho,
                ix->ex_tau.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     unsigned long long *ctr = ix->rg_ctr.as<unsigned long long>();
     HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
@@ -4105,7 +4191,7 @@ static int range_emit(zh_index *ix, uint32_t B, uint64_t hits, uint64_t pool_cap
 // ordered by (query, key, id) into dIds / dKeys at run->total (host_out: into staging and from there to the HOST arrays dIds / dKeys).
 static int range_one(zh_index *ix, const float *dQ, uint32_t B, const uint64_t *dMaxK, int metric, int mode, RangeRun *run, uint64_t *dOff,
                      uint64_t *dIds, uint64_t *dKeys, bool host_out, hipStream_t s, zh_range_info *inf) {
-    const uint64_t n_live = ix->ex_n_live, pairs = (uint64_t)B * n_live;
+    const uint64_t n_live = ix->live_dev.n_live, pairs = (uint64_t)B * n_live;
     const uint64_t pool_cap = run->over ? 0 : std::min<uint64_t>(run->capacity - run->total, pairs);
     int rc;
     if ((rc = ix->rg_cnt.ensure((size_t)B * 4)) || (rc = ix->rg_ctr.ensure(16)) || (rc = ix->rg_pv0.ensure(std::max<uint64_t>(pool_cap, 1) * 8)) ||
@@ -4149,7 +4235,7 @@ static int range_finish(zh_index *ix, size_t b, const RangeRun &run, zh_range_in
     {
         std::lock_guard<std::mutex> lk(ix->stats_mu);
         inf.batch = b;
-        inf.rows_live = ix->ex_n_live;
+        inf.rows_live = ix->live_dev.n_live;
         ix->rg_info = inf;
     }
     if (run.over)
@@ -4249,7 +4335,7 @@ extern "C" int zh_search_range_info(const zh_index *ix, zh_range_info *out) { re
 static int pair_batch1(zh_index *iq, zh_index *is, const uint32_t *dQRows, uint32_t B, uint64_t p_from, bool upper, uint64_t max_key, int metric, int mode,
                        uint64_t pool_cap, hipStream_t s, uint64_t *launches) {
     const uint32_t d = iq->opt.dim;
-    const uint64_t n_live = is->ex_n_live;
+    const uint64_t n_live = is->live_dev.n_live;
     if (!B || p_from >= n_live) return ZH_OK;
     const uint64_t rc_rows = std::min<uint64_t>(std::max<uint64_t>(256, ZH_EXACT_KEY_BYTES / 8 / B), n_live - p_from);
     int rc;
@@ -4259,9 +4345,9 @@ static int pair_batch1(zh_index *iq, zh_index *is, const uint32_t *dQRows, uint3
     HIPCHK(zh_launch_qnorm(iq->ex_Q.as<float>(), B, d, iq->ex_QQ.as<float>(), s));
     for (uint64_t p0 = p_from; p0 < n_live; p0 += rc_rows) {
         const uint32_t nr = (uint32_t)std::min<uint64_t>(rc_rows, n_live - p0);
-        HIPCHK(zh_launch_exact_score(is->X.as<float>(), d, is->ex_live.as<uint32_t>(), p0, nr, iq->ex_Q.as<float>(), iq->ex_QQ.as<float>(), B, metric, param,
+        HIPCHK(zh_launch_exact_score(is->X.as<float>(), d, is->live_dev.rows.as<uint32_t>(), p0, nr, iq->ex_Q.as<float>(), iq->ex_QQ.as<float>(), B, metric, param,
                                      iq->ex_keys.as<uint64_t>(), rc_rows, s));
-        HIPCHK(zh_launch_pair_collect(iq->ex_keys.as<uint64_t>(), rc_rows, is->ex_live.as<uint32_t>(), p0, nr, dQRows, B, upper, max_key,
+        HIPCHK(zh_launch_pair_collect(iq->ex_keys.as<uint64_t>(), rc_rows, is->live_dev.rows.as<uint32_t>(), p0, nr, dQRows, B, upper, max_key,
                                       iq->jn_ctr.as<unsigned long long>(), iq->jn_pv0.as<uint64_t>(), iq->jn_pk0.as<uint64_t>(), pool_cap, s));
         (*launches)++;
     }
@@ -4289,7 +4375,7 @@ static int panel_tail(zh_index *ix, uint32_t n, uint64_t cand_cap, hipStream_t s
 static int join_path2(zh_index *ix, uint64_t max_key, int metric, int mode, uint64_t pool_cap, hipStream_t s, zh_join_info *inf, bool *used, uint64_t *hits) {
     *used = false;
     const uint32_t d = ix->opt.dim;
-    if (!zh_exact_mfma_supported(d, metric) || ix->ex_n_live < 8192) return ZH_OK;
+    if (!zh_exact_mfma_supported(d, metric) || ix->live_dev.n_live < 8192) return ZH_OK;
     int rc;
     HalfView v;
     bool have = false;
@@ -4306,7 +4392,7 @@ static int join_path2(zh_index *ix, uint64_t max_key, int metric, int mode, uint
     unsigned long long *ctr = ix->jn_ctr.as<unsigned long long>();  // {hits, the panel's candidates, a redone panel's rows}
     HIPCHK(hipMemcpyAsync(ix->jn_maxk.p, &max_key, 8, hipMemcpyHostToDevice, s));
     HIPCHK(zh_launch_range_tau(ix->jn_maxk.as<uint64_t>(), 1, metric, mode, ix->jn_tau.as<uint32_t>(), s));
-    HIPCHK(zh_launch_join_prep(v.rowMeta, v.perm, v.perm_rows, ix->ex_bits.as<uint32_t>(), n, v.rho, ix->jn_qm.as<float4>(), ix->jn_cid.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_prep(v.rowMeta, v.perm, v.perm_rows, ix->live_dev.bits.as<uint32_t>(), n, v.rho, ix->jn_qm.as<float4>(), ix->jn_cid.as<uint32_t>(), s));
     HIPCHK(hipStreamSynchronize(s));  // (max_key is the caller's stack)
     *used = true;
     inf->path = 2;
@@ -4420,8 +4506,8 @@ static int join_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint64
                     hipStream_t s, uint64_t *total, const char *who) {
     zh_join_info inf{};
     inf.path = 1;
-    inf.rows_live = ix->ex_n_live;
-    const uint64_t n_live = ix->ex_n_live;
+    inf.rows_live = ix->live_dev.n_live;
+    const uint64_t n_live = ix->live_dev.n_live;
     uint64_t hits = 0;
     int rc;
     if (n_live >= 2) {
@@ -4436,7 +4522,7 @@ static int join_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint64
         if (!used) {  // panels of the ascending live list: panel [a0, a0 + B) against the live rows from a0 on
             for (uint64_t a0 = 0; a0 + 1 < n_live; a0 += ZH_EXACT_BATCH) {
                 const uint32_t B = (uint32_t)std::min<uint64_t>(ZH_EXACT_BATCH, n_live - a0);
-                if ((rc = pair_batch1(ix, ix, ix->ex_live.as<uint32_t>() + a0, B, a0, true, max_key, metric, mode, pool_cap, s, &inf.launches))) return rc;
+                if ((rc = pair_batch1(ix, ix, ix->live_dev.rows.as<uint32_t>() + a0, B, a0, true, max_key, metric, mode, pool_cap, s, &inf.launches))) return rc;
             }
             unsigned long long h = 0;
             HIPCHK(hipMemcpyAsync(&h, ix->jn_ctr.p, 8, hipMemcpyDeviceToHost, s));
@@ -4497,7 +4583,7 @@ static int xjoin_path2(zh_index *ia, zh_index *ib, bool forced, uint64_t max_key
     *used = false;
     const uint32_t d = ia->opt.dim;
     if (!zh_exact_mfma_supported(d, metric)) return ZH_OK;
-    if (!forced && ia->ex_n_live * ib->ex_n_live < ZH_XJOIN_GATE_PAIRS) return ZH_OK;  // (both counts are below 2^32)
+    if (!forced && ia->live_dev.n_live * ib->live_dev.n_live < ZH_XJOIN_GATE_PAIRS) return ZH_OK;  // (both counts are below 2^32)
     int rc;
     HalfView va, vb;
     bool have_a = false, have_b = false;
@@ -4518,8 +4604,8 @@ static int xjoin_path2(zh_index *ia, zh_index *ib, bool forced, uint64_t max_key
     unsigned long long *ctr = ia->jn_ctr.as<unsigned long long>();  // {hits, the panel's candidates, a redone panel's rows}
     HIPCHK(hipMemcpyAsync(ia->jn_maxk.p, &max_key, 8, hipMemcpyHostToDevice, s));
     HIPCHK(zh_launch_range_tau(ia->jn_maxk.as<uint64_t>(), 1, metric, mode, ia->jn_tau.as<uint32_t>(), s));
-    HIPCHK(zh_launch_join_prep(va.rowMeta, va.perm, va.perm_rows, ia->ex_bits.as<uint32_t>(), na, va.rho, ia->xj_qma.as<float4>(), ia->xj_cida.as<uint32_t>(), s));
-    HIPCHK(zh_launch_join_prep(vb.rowMeta, vb.perm, vb.perm_rows, ib->ex_bits.as<uint32_t>(), nb, vb.rho, ia->xj_qmb.as<float4>(), ia->xj_cidb.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_prep(va.rowMeta, va.perm, va.perm_rows, ia->live_dev.bits.as<uint32_t>(), na, va.rho, ia->xj_qma.as<float4>(), ia->xj_cida.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_prep(vb.rowMeta, vb.perm, vb.perm_rows, ib->live_dev.bits.as<uint32_t>(), nb, vb.rho, ia->xj_qmb.as<float4>(), ia->xj_cidb.as<uint32_t>(), s));
     HIPCHK(hipStreamSynchronize(s));  // (max_key is the caller's stack)
     *used = true;
     inf->path = 2;
@@ -4590,9 +4676,9 @@ static int xjoin_run(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, i
                      bool host_out, hipStream_t s, uint64_t *total, const char *who) {
     zh_cross_info inf{};
     inf.path = 1;
-    inf.rows_live_a = ia->ex_n_live;
-    inf.rows_live_b = ib->ex_n_live;
-    const uint64_t la = ia->ex_n_live, lb = ib->ex_n_live;
+    inf.rows_live_a = ia->live_dev.n_live;
+    inf.rows_live_b = ib->live_dev.n_live;
+    const uint64_t la = ia->live_dev.n_live, lb = ib->live_dev.n_live;
     uint64_t hits = 0;
     int rc;
     if (la && lb) {
@@ -4608,7 +4694,7 @@ static int xjoin_run(zh_index *ia, zh_index *ib, uint64_t max_key, int metric, i
         if (!used) {  // panels of A's ascending live list against all of B's
             for (uint64_t a0 = 0; a0 < la; a0 += ZH_EXACT_BATCH) {
                 const uint32_t B = (uint32_t)std::min<uint64_t>(ZH_EXACT_BATCH, la - a0);
-                if ((rc = pair_batch1(ia, ib, ia->ex_live.as<uint32_t>() + a0, B, 0, false, max_key, metric, mode, pool_cap, s, &inf.launches))) return rc;
+                if ((rc = pair_batch1(ia, ib, ia->live_dev.rows.as<uint32_t>() + a0, B, 0, false, max_key, metric, mode, pool_cap, s, &inf.launches))) return rc;
             }
             unsigned long long h = 0;
             HIPCHK(hipMemcpyAsync(&h, ia->jn_ctr.p, 8, hipMemcpyDeviceToHost, s));
@@ -4697,9 +4783,9 @@ extern "C" int zh_debug_walk_pairs(zh_index *ia, zh_index *ib, int metric, int m
     if ((rc = w.qma.ensure(TA * 16 * 16)) || (rc = w.cida.ensure(TA * 16 * 4)) || (rc = w.rec.ensure(rec_bytes))) return rc;
     if (ib != ia && ((rc = w.qmb.ensure(TB * 16 * 16)) || (rc = w.cidb.ensure(TB * 16 * 4)))) return rc;
     const hipStream_t s = ia->stream;
-    HIPCHK(zh_launch_join_prep(va.rowMeta, va.perm, va.perm_rows, ia->ex_bits.as<uint32_t>(), na, va.rho, w.qma.as<float4>(), w.cida.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_prep(va.rowMeta, va.perm, va.perm_rows, ia->live_dev.bits.as<uint32_t>(), na, va.rho, w.qma.as<float4>(), w.cida.as<uint32_t>(), s));
     if (ib != ia)
-        HIPCHK(zh_launch_join_prep(vb.rowMeta, vb.perm, vb.perm_rows, ib->ex_bits.as<uint32_t>(), nb, vb.rho, w.qmb.as<float4>(), w.cidb.as<uint32_t>(), s));
+        HIPCHK(zh_launch_join_prep(vb.rowMeta, vb.perm, vb.perm_rows, ib->live_dev.bits.as<uint32_t>(), nb, vb.rho, w.qmb.as<float4>(), w.cidb.as<uint32_t>(), s));
     const DevBuf &qmB = ib != ia ? w.qmb : w.qma, &cidB = ib != ia ? w.cidb : w.cida;
     HIPCHK(hipMemsetAsync(w.rec.p, 0xFF, rec_bytes, s));  // (a record the walk did not write: positions all ones)
     HIPCHK(zh_launch_walk_debug(d, metric, mode, va.Xh, va.rowMeta, w.cida.as<uint32_t>(), na, vb.Xh, qmB.as<float4>(), cidB.as<uint32_t>(), nb, first_pos,
@@ -4729,7 +4815,7 @@ static int knn_setup(zh_index *ix, uint32_t k, int metric, int mode, hipStream_t
     const uint32_t d = ix->opt.dim;
     const char *env_p = getenv("ZH_KNN_PATH");
     if (env_p && atoi(env_p) == 1) return ZH_OK;
-    if (!zh_exact_mfma_supported(d, metric) || ix->ex_n_live < std::max<uint64_t>((uint64_t)k + 1, 8192)) return ZH_OK;
+    if (!zh_exact_mfma_supported(d, metric) || ix->live_dev.n_live < std::max<uint64_t>((uint64_t)k + 1, 8192)) return ZH_OK;
     int rc;
     HalfView &v = run->v;
     bool have = false;
@@ -4743,7 +4829,7 @@ static int knn_setup(zh_index *ix, uint32_t k, int metric, int mode, hipStream_t
     const char *env_c = getenv("ZH_KNN_LIST_CAP");
     if (env_c && atoi(env_c) > 0) run->cap = std::min<uint32_t>(run->cap, (uint32_t)atoi(env_c));
     if ((rc = ix->kn_qm.ensure(n_pos * 16)) || (rc = ix->kn_cid.ensure(n_pos * 4)) || (rc = ix->kn_cbase.ensure((ZH_KNN_PANEL_ROWS + 1) * 8))) return rc;
-    HIPCHK(zh_launch_join_prep(v.rowMeta, v.perm, v.perm_rows, ix->ex_bits.as<uint32_t>(), n, v.rho, ix->kn_qm.as<float4>(), ix->kn_cid.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_prep(v.rowMeta, v.perm, v.perm_rows, ix->live_dev.bits.as<uint32_t>(), n, v.rho, ix->kn_qm.as<float4>(), ix->kn_cid.as<uint32_t>(), s));
     if (v.perm_rows) {
         if ((rc = ix->kn_pos.ensure(n * 4))) return rc;
         HIPCHK(zh_launch_knn_rowpos(ix->kn_cid.as<uint32_t>(), n_pos, ix->kn_pos.as<uint32_t>(), s));
@@ -4762,7 +4848,7 @@ static int knn_setup(zh_index *ix, uint32_t k, int metric, int mode, hipStream_t
 static int knn_panel2(zh_index *ix, const KnnRun &run, const uint32_t *dRows, uint32_t B, uint32_t k, int metric, int mode, hipStream_t s, bool *overflowed,
                       zh_knn_info *inf) {
     const uint32_t d = ix->opt.dim, cap = run.cap, PT = (B + 15) / 16;
-    ZhExact2 e{run.v.Xh, run.v.rowMeta, nullptr, 0, ix->ex_bits.as<uint32_t>(), nullptr, nullptr, B, run.Kc, run.v.rho};
+    ZhExact2 e{run.v.Xh, run.v.rowMeta, nullptr, 0, ix->live_dev.bits.as<uint32_t>(), nullptr, nullptr, B, run.Kc, run.v.rho};
     int rc;
     if ((rc = ix->kn_A.ensure((size_t)PT * 16 * d * 2)) || (rc = ix->kn_pmeta.ensure((size_t)PT * 16 * 8)) || (rc = ix->kn_pid.ensure((size_t)PT * 16 * 4)) ||
         (rc = ix->ex_Q.ensure((size_t)B * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)B * 4)) || (rc = lists_ensure(ix, B, cap, false, &e)))
@@ -4803,7 +4889,7 @@ static int knn_slab(zh_index *ix, KnnRun *run, uint64_t first_row, uint64_t n, u
         return rc;
     for (uint64_t a0 = lo; a0 < hi; a0 += ZH_KNN_PANEL_ROWS) {
         const uint32_t B = (uint32_t)std::min<uint64_t>(ZH_KNN_PANEL_ROWS, hi - a0);
-        const uint32_t *dRows = ix->ex_live.as<uint32_t>() + a0;
+        const uint32_t *dRows = ix->live_dev.rows.as<uint32_t>() + a0;
         if (run->path2) {
             bool overflowed = false;
             if ((rc = knn_panel2(ix, *run, dRows, B, k, metric, mode, s, &overflowed, inf))) return rc;
@@ -4817,7 +4903,7 @@ static int knn_slab(zh_index *ix, KnnRun *run, uint64_t first_row, uint64_t n, u
         // path 1: the panel as queries, k + 1 over the live list, self taken out of each line
         if ((rc = ix->ex_Q.ensure((size_t)B * d * 4))) return rc;
         HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dRows, B, ix->ex_Q.as<float>(), s));
-        if ((rc = exact_batch(ix, ix->ex_live.as<uint32_t>(), ix->ex_n_live, ix->ex_Q.as<float>(), B, k + 1, metric, mode, ix->kn_pids.as<uint64_t>(),
+        if ((rc = exact_batch(ix, ix->live_dev.rows.as<uint32_t>(), ix->live_dev.n_live, ix->ex_Q.as<float>(), B, k + 1, metric, mode, ix->kn_pids.as<uint64_t>(),
                               ix->kn_pkeys.as<uint64_t>(), ix->kn_pcounts.as<uint32_t>(), s, &inf->launches)))
             return rc;
         HIPCHK(zh_launch_knn_emit(ix->kn_pids.as<uint64_t>(), ix->kn_pkeys.as<uint64_t>(), ix->kn_pcounts.as<uint32_t>(), k + 1, dRows, B, ix->opt.id_base,
@@ -4851,7 +4937,7 @@ static int knn_stage_out(zh_index *ix, uint64_t r0, uint64_t m, size_t k, uint64
 static void knn_record(zh_index *ix, uint32_t k, zh_knn_info inf) {
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     inf.k = k;
-    inf.rows_live = ix->ex_n_live;
+    inf.rows_live = ix->live_dev.n_live;
     ix->kn_info = inf;
 }
 
@@ -4949,7 +5035,7 @@ struct FknnRun : ForestRun {
 };
 
 // The forest families' path rule (env_path: ZH_FKNN_PATH / ZH_FJOIN_PATH, read per call) and path 2's per-call views: the fp16 copy and, under a row
-// order, the row -> position map -- made and waited for inside blk_mu, because scan_perm is read under blk_mu only.
+// order, the row -> position map -- made and waited for inside blk_mu, because order.perm is read under blk_mu only.
 static int forest_path2(zh_index *ix, const char *env_path, int metric, hipStream_t s, ForestRun *run) {
     const uint32_t d = ix->opt.dim;
     run->T = (uint32_t)ix->h_roots.size();
@@ -4959,33 +5045,15 @@ static int forest_path2(zh_index *ix, const char *env_path, int metric, hipStrea
     bool have = false;
     int rc = half_view(ix, &run->v, &have);
     if (rc || !have) return rc;
-    if (ix->perm_rows) {
+    if (ix->order.rows) {
         if ((rc = ix->fk_pos.ensure(ix->n_rows * 4))) return rc;
-        HIPCHK(zh_launch_fknn_rowpos(ix->scan_perm.as<uint32_t>(), ix->perm_rows, ix->n_rows, ix->fk_pos.as<uint32_t>(), s));
+        HIPCHK(zh_launch_fknn_rowpos(ix->order.perm.as<uint32_t>(), ix->order.rows, ix->n_rows, ix->fk_pos.as<uint32_t>(), s));
         HIPCHK(hipStreamSynchronize(s));
         run->pos = ix->fk_pos.as<uint32_t>();
     }
     run->Kc = zh_approx_bound(metric, d, 1);
     run->path2 = true;
     return ZH_OK;
-}
-
-// The host mirror of the forest, walked once -> node_tree[node] = the tree that holds it (0xFFFFFFFF: none) and, where asked for, every tree's
-// non-empty leaves.
-static std::vector<uint32_t> forest_walk(const zh_index *ix, std::vector<std::vector<uint2>> *leaves) {
-    const uint32_t T = (uint32_t)ix->h_roots.size();
-    std::vector<uint32_t> node_tree(std::max<size_t>(ix->h_plane.size(), 1), 0xFFFFFFFFu), st;
-    if (leaves) leaves->resize(T);
-    for (uint32_t t = 0; t < T; t++) {
-        st.assign(1, ix->h_roots[t]);
-        while (!st.empty()) {
-            const uint32_t nd = st.back(); st.pop_back();
-            node_tree[nd] = t;
-            if (ix->h_plane[nd] >= 0) { st.push_back((uint32_t)ix->h_right[nd]); st.push_back((uint32_t)ix->h_left[nd]); }
-            else if (leaves && ix->h_right[nd] > 0) (*leaves)[t].push_back(make_uint2((uint32_t)ix->h_left[nd], (uint32_t)ix->h_right[nd]));
-        }
-    }
-    return node_tree;
 }
 
 // The node -> tree map on the device (both paths' row -> leaf table), the path rule, and path 2's per-call views (its leaves among them).
@@ -5086,7 +5154,7 @@ static int fknn_batch2(zh_index *ix, const FknnRun &run, std::vector<ZhFknnSeg> 
     // list slots per line: a line lists at most its leaf-mates (longest - 1 <= lim): only the ceilings and the test switch can make a list run over
     uint32_t cap = std::min<uint32_t>(longest + k, first ? 16384 + 8 * k : 1024 + 4 * k), lim = cap - k;
     if (run.env_cap) { lim = std::min(lim, run.env_cap); cap = lim + k; }
-    ZhExact2 e{run.v.Xh, run.v.rowMeta, nullptr, 0, ix->ex_bits.as<uint32_t>(), nullptr, nullptr, HB, run.Kc, run.v.rho};
+    ZhExact2 e{run.v.Xh, run.v.rowMeta, nullptr, 0, ix->live_dev.bits.as<uint32_t>(), nullptr, nullptr, HB, run.Kc, run.v.rho};
     int rc;
     if ((rc = ix->fk_segs.ensure((size_t)n_segs * sizeof(ZhFknnSeg))) || (rc = ix->fk_colsrc.ensure((size_t)NT * 8)) || (rc = ix->fk_crow.ensure((size_t)NT * 64)) ||
         (rc = ix->fk_hrow.ensure((size_t)HB * 4)) || (rc = ix->fk_held.ensure((size_t)n_segs * 4)) || (rc = ix->fk_CA.ensure((size_t)NT * 32 * d)) ||
@@ -5203,7 +5271,7 @@ static int fknn_finish(zh_index *ix, uint32_t k, zh_knn_forest_info inf, hipStre
         HIPCHK(hipStreamSynchronize(s));
     }
     inf.k = k;
-    inf.rows_live = ix->ex_n_live;
+    inf.rows_live = ix->live_dev.n_live;
     inf.trees = ix->n_trees;
     inf.pairs = ctr[0];
     inf.tiles = ctr[1];
@@ -5307,7 +5375,7 @@ static int refine_table(zh_index *ix, const uint64_t *in_ids, const uint32_t *in
     if ((rc = ix->rf_tab.ensure(std::max<size_t>((size_t)N * in_k * 4, 4))) || (rc = ix->rf_ctr.ensure(24))) return rc;
     HIPCHK(hipMemsetAsync(ix->rf_ctr.p, 0, 24, s));
     if (!N) return ZH_OK;
-    const uint32_t *dBits = ix->ex_bits.as<uint32_t>();
+    const uint32_t *dBits = ix->live_dev.bits.as<uint32_t>();
     if (!host) {
         HIPCHK(zh_launch_refine_rows(in_ids, in_counts, dBits, id_base, N, in_k, 0, N, ix->rf_tab.as<uint32_t>(), s));
         return ZH_OK;
@@ -5337,7 +5405,7 @@ static int refine_table(zh_index *ix, const uint64_t *in_ids, const uint32_t *in
 
 // One slab on device outputs (under mu, exclusive; exact_live_rows and refine_table have run; k > 0, n > 0; dTab's lines are in_k wide, the first
 // fwd_k of them the caller's own: rf_tab at in_k twice, or the union table): every line filled as "no neighbours",
-// then sub-slab by sub-slab the live lines (a stretch of ex_live), their f32 rows as the query side, their norms, and a block per line.
+// then sub-slab by sub-slab the live lines (a stretch of live_dev.rows), their f32 rows as the query side, their norms, and a block per line.
 static int refine_slab(zh_index *ix, LiveCursor *live, const uint32_t *dTab, uint32_t in_k, uint32_t fwd_k, uint64_t first_row, uint64_t n, uint32_t k, int metric, int mode, uint64_t *dIds,
                        uint64_t *dKeys, uint32_t *dCounts, hipStream_t s, zh_knn_refine_info *inf) {
     const uint32_t d = ix->opt.dim;
@@ -5348,7 +5416,7 @@ static int refine_slab(zh_index *ix, LiveCursor *live, const uint32_t *dTab, uin
         const uint64_t lo = live_before(ix, r0, live), hi = live_before(ix, r0 + m, live);
         const uint32_t B = (uint32_t)(hi - lo);
         if (!B) continue;
-        const uint32_t *dRows = ix->ex_live.as<uint32_t>() + lo;
+        const uint32_t *dRows = ix->live_dev.rows.as<uint32_t>() + lo;
         if ((rc = ix->ex_Q.ensure((size_t)B * d * 4)) || (rc = ix->ex_QQ.ensure((size_t)B * 4))) return rc;
         HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dRows, B, ix->ex_Q.as<float>(), s));
         HIPCHK(zh_launch_qnorm(ix->ex_Q.as<float>(), B, d, ix->ex_QQ.as<float>(), s));
@@ -5382,7 +5450,7 @@ static int reverse_csr(zh_index *ix, uint32_t in_k, hipStream_t s) {
         (rc = ix->rv_heavy.ensure((size_t)(N * in_k / ZH_REVERSE_HEAVY + 1) * 4)) || (rc = ix->rv_ctr.ensure(32)))
         return rc;
     HIPCHK(hipMemsetAsync(ix->rv_ctr.p, 0, 32, s));
-    HIPCHK(zh_launch_reverse_csr(ix->rf_tab.as<uint32_t>(), ix->ex_bits.as<uint32_t>(), N, in_k, ix->rv_deg.as<uint32_t>(), ix->rv_cur.as<uint32_t>(), ix->rv_off.as<uint64_t>(),
+    HIPCHK(zh_launch_reverse_csr(ix->rf_tab.as<uint32_t>(), ix->live_dev.bits.as<uint32_t>(), N, in_k, ix->rv_deg.as<uint32_t>(), ix->rv_cur.as<uint32_t>(), ix->rv_off.as<uint64_t>(),
                                  ix->rv_sums.as<uint64_t>(), ix->rv_csr.as<uint32_t>(), ix->rv_ctr.as<unsigned long long>(), s));
     return ZH_OK;
 }
@@ -5433,7 +5501,7 @@ static int refine_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_
         HIPCHK(hipMemcpyAsync(ctr, ix->rf_ctr.p, 24, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
-    inf.rows_live = ix->ex_n_live;
+    inf.rows_live = ix->live_dev.n_live;
     inf.in_k = in_k;
     inf.k = (uint32_t)k;
     inf.listed = ctr[0]; inf.keyed = ctr[1]; inf.updates = ctr[2];
@@ -5549,7 +5617,7 @@ static int reverse_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in
     HIPCHK(hipMemcpyAsync(rctr, ix->rv_ctr.p, 32, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     LiveCursor live;
-    inf.rows_live = ix->ex_n_live;
+    inf.rows_live = ix->live_dev.n_live;
     inf.lines = live_before(ix, first_row + n, &live) - live_before(ix, first_row, &live);
     inf.in_k = in_k;
     inf.rev_k = rev_k;
@@ -5755,7 +5823,7 @@ static int fjoin_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint6
                      hipStream_t s, uint64_t *total, const char *who) {
     zh_join_forest_info inf{};
     inf.path = 1;
-    inf.rows_live = ix->ex_n_live;
+    inf.rows_live = ix->live_dev.n_live;
     inf.trees = ix->n_trees;
     FjoinRun run;
     run.metric = metric; run.mode = mode; run.max_key = max_key;
@@ -5790,7 +5858,7 @@ static int fjoin_run(zh_index *ix, uint64_t max_key, int metric, int mode, uint6
 
 // an index without live rows has no pair: total 0 (and the info says so) whatever its trees; otherwise the forest graph's state checks
 static int fjoin_state(zh_index *ix, bool *empty, const char *who) {
-    *empty = ix->ex_n_live == 0;
+    *empty = ix->live_dev.n_live == 0;
     if (*empty) {
         zh_join_forest_info inf{};
         inf.path = 1;
@@ -6111,7 +6179,7 @@ static int frange_begin(zh_index *ix, size_t b, uint32_t probe, int metric, int 
     run->inf.path = 1;
     run->inf.probe = probe;
     run->inf.trees = ix->n_trees;
-    *empty = b == 0 || ix->ex_n_live == 0;
+    *empty = b == 0 || ix->live_dev.n_live == 0;
     return *empty ? ZH_OK : fknn_state(ix, who);
 }
 
@@ -6119,7 +6187,7 @@ static int frange_finish(zh_index *ix, size_t b, const FrangeRun &run, const cha
     {
         zh_range_forest_info inf = run.inf;
         inf.batch = b;
-        inf.rows_live = ix->ex_n_live;
+        inf.rows_live = ix->live_dev.n_live;
         std::lock_guard<std::mutex> lk(ix->stats_mu);
         ix->fr_info = inf;
     }

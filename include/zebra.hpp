@@ -455,6 +455,38 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_knn_graph_refine_rev_info(h_.get(), &info));
         return info;
     }
+    // NN-descent on the device (zh_knn_graph_descent): up to `rounds` rounds of knn_graph_refine_rev over the whole table in one call that keeps the
+    // graph on the device and, from the second round on, keys only what a new entry of a line brings up -- the loop's answer bit for bit, early
+    // stop at the first round without updates included.  1 <= rounds <= 32, k >= 1, in_k + rev_k and k + rev_k <= ZH_REFINE_MAX_IN_K.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> knn_graph_descent(const std::vector<Id> &in_ids, const std::vector<std::uint32_t> &in_counts,
+                                                                            std::size_t in_k, std::size_t rev_k, std::size_t k, std::size_t rounds,
+                                                                            const Met &metric) const {
+        const std::uint64_t stored = zh_index_stored_rows(h_.get());
+        if (in_counts.size() != stored || in_ids.size() != stored * in_k)
+            throw std::invalid_argument("knn_graph_descent: the graph must cover every stored row");
+        std::vector<Id> ids(stored * k + 1);
+        std::vector<DistanceUnit> keys(stored * k + 1);
+        std::vector<std::uint32_t> counts(stored + 1);
+        const Id none = 0;
+        check(zh_knn_graph_descent(h_.get(), stored ? in_ids.data() : &none, stored ? in_counts.data() : counts.data(), in_k, rev_k, k, rounds, Met::metric,
+                                   metric.mode(), ids.data(), keys.data(), counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(stored);
+        for (std::uint64_t i = 0; i < stored; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * k + j], keys[i * k + j]);
+        return out;
+    }
+    template <class Met>
+    void knn_graph_descent_device(const Id *d_in_ids, const std::uint32_t *d_in_counts, std::size_t in_k, std::size_t rev_k, std::size_t k, std::size_t rounds,
+                                  const Met &metric, Id *d_out_ids, DistanceUnit *d_out_keys, std::uint32_t *d_out_counts, void *stream = nullptr) const {
+        check(zh_knn_graph_descent_device(h_.get(), d_in_ids, d_in_counts, in_k, rev_k, k, rounds, Met::metric, metric.mode(), d_out_ids, d_out_keys,
+                                          d_out_counts, stream));
+    }
+    zh_knn_descent_info knn_descent_info() const {
+        zh_knn_descent_info info{};
+        check(zh_knn_graph_descent_info(h_.get(), &info));
+        return info;
+    }
     // The capped reverse graph on its own (zh_knn_graph_reverse): element i = up to rev_k of the live rows that name stored row first_row + i and
     // that its own line does not name, in (hash, row) order; degree[i] = its uncapped in-degree.  No metric, no keys, no forest.
     struct ReverseGraph {

@@ -36,6 +36,8 @@
  *   zh_knn_graph_reverse[_device]        (new) the capped reverse graph: for every row a deterministic sample of the rows that name it, and its
  *                                        in-degree
  *   zh_knn_graph_refine_rev[_device]     (new) zh_knn_graph_refine over each row's neighbours AND sampled reverse neighbours
+ *   zh_knn_graph_descent[_device]        (new) the rounds of zh_knn_graph_refine_rev in one call on the device, keying from the second round on
+ *                                        only what a new entry brings up: the loop's answer bit for bit
  *   zh_self_join_forest[_device]         (new) every pair of leaf-mates whose key is at or below one threshold key, each pair once: exact keys,
  *                                        approximate candidates
  *   zh_search_range_forest_batch[_device] (new) every member of the leaves the walk visits for a query whose key is at or below the query's
@@ -756,6 +758,58 @@ typedef struct zh_knn_refine_rev_info {  /* the most recent zh_knn_graph_refine_
     uint64_t max_degree;  /* the largest deg(x) over ALL stored rows */
 } zh_knn_refine_rev_info;
 ZH_API int zh_knn_graph_refine_rev_info(const zh_index *idx, zh_knn_refine_rev_info *out);
+
+/* ---- NN-descent (new): incremental rounds on the device, to a fixed point --------------------------------------------------------------------
+ * A loop over zh_knn_graph_refine_rev keys every pair again in every round and moves the graph through the host between rounds.  This call runs
+ * the rounds in one go, keeps the graph on the device, and from the second round on keys only what a NEW entry of a line brings up.  Nothing
+ * about the answer is approximate: let G_0 be the caller's graph (all stored rows, in_k wide, judged as zh_knn_graph_refine judges it) and G_r
+ * what zh_knn_graph_refine_rev(G_{r-1}, in_k_r, rev_k, k) returns for the whole table, in_k_1 = in_k and in_k_r = k afterwards (rev_k = 0:
+ * zh_knn_graph_refine).  The call returns G_rounds, or G_r for the first r whose `updates` is 0 -- ids, keys, tails, counts, a removed row's
+ * empty line and the meaning of `updates` (answer entries that the FORWARD input line does not hold) are that call's, bit for bit.
+ * Which candidates round r + 1 >= 2 keys (this fixes `keyed`): U_r(x) is the line it ranks over -- N'(G_r)(x), then the kept reverse neighbours
+ * R'(x) of G_r.  An entry of U_r(x) is OLD if U_{r-1}(x) holds it, NEW otherwise; every entry of U_0 is new.  For a live row a, S(a) is the set
+ * of rows c != a, c not in N'(G_r)(a), such that c is a new entry of U_r(a), or c is in U_r(b) for a new entry b of U_r(a), or c is a new entry
+ * of U_r(b) for an old entry b of U_r(a).  The line of a is the first k by (key, id) of S(a) together with N'(G_r)(a), whose entries carry the
+ * keys round r wrote (a key is a pure function of the pair).  A line with empty S(a) is inactive: copied, nothing keyed, no updates.  What only
+ * old hops reach was a candidate of round r and lost to k rows that are candidates again, so the line equals the full round's.  This needs one k
+ * for all rounds and the same live rows throughout: the call holds the index's exclusive lock.
+ * Whole table only; outputs [stored rows][k] u64 twice and [stored rows] u32.  Judged before any device is touched, in this order of kinds: a
+ * null index, null pointers, an unknown metric, rounds outside 1 .. ZH_DESCENT_MAX_ROUNDS (ZH_EINVAL), k = 0 (ZH_EINVAL), in_k + rev_k or
+ * k + rev_k above ZH_REFINE_MAX_IN_K (ZH_ELIMIT), in_k = 0 (ZH_EINVAL).  An empty table is ZH_OK with nothing written.  Any metric, any
+ * dimension, no forest needed.  Locking and stream semantics as zh_knn_graph_refine_device; the sibling info structs are left alone.
+ * Round 1 is zh_knn_graph_refine_rev's kernels; its ids become u32 row numbers once, and no u64 id leaves the device until the end.  Every later
+ * round: (rev_k > 0: transpose and select as zh_knn_graph_reverse,) a wave per line flags its new entries, a wave per live line counts what it
+ * would gather and copies a line that gathers nothing, a block per remaining line gathers, de-duplicates, keys and merges with the carried
+ * forward line into the OTHER table; one readback of the round's counters decides the early stop.  Device scratch is per call and released
+ * before return: beside zh_knn_graph_refine_rev's (with max(in_k, k) for in_k), per stored row 24 k (two u32 tables and two key arrays), 8 (the
+ * new-mask), 4 (the squared norms) and, with rev_k > 0, 4 (max(in_k, k) + rev_k) for the second union table; 4 bytes per live row for the list
+ * of active lines; round 1's ids and the host entry's answer go through a staged piece of at most max(65536, 2^25 / k) lines of 16 k + 4 bytes.
+ * ZH_ENOMEM leaves nothing allocated.  DESIGN.md s23. */
+#define ZH_DESCENT_MAX_ROUNDS 32u
+ZH_API int zh_knn_graph_descent(zh_index *idx, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, size_t rev_k, size_t k, size_t rounds,
+                                int metric, int cosine_mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts);
+/* The same with the graph and every output in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_knn_graph_descent_device(zh_index *idx, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, size_t rev_k, size_t k,
+                                       size_t rounds, int metric, int cosine_mode, uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts,
+                                       void *stream);
+typedef struct zh_knn_descent_info {  /* the most recent zh_knn_graph_descent* call on this index */
+    uint64_t rows_live;     /* live rows of the index */
+    uint32_t in_k;
+    uint32_t rev_k;
+    uint32_t k;
+    uint32_t rounds;        /* asked for */
+    uint32_t rounds_run;    /* run: the first round without updates, or `rounds` */
+    uint64_t launches;      /* kernel launches of the call's own passes and of the line kernels */
+    uint64_t listed;        /* entries gathered before de-duplication, summed over the rounds run */
+    uint64_t keyed;         /* pairs that got a key, summed over the rounds run */
+    uint64_t lines_active;  /* the sum of active_round */
+    uint64_t updates;       /* of the last round run */
+    uint64_t large_lines;   /* lines that ran in the large instantiation of a line kernel, over all rounds */
+    uint64_t keyed_round[32];    /* per round run: the sum of |S(a)| (round 1: of |C_r(a)|) */
+    uint64_t updates_round[32];  /* per round run */
+    uint64_t active_round[32];   /* per round run: lines with a non-empty S(a); [0] = the live rows */
+} zh_knn_descent_info;
+ZH_API int zh_knn_graph_descent_info(const zh_index *idx, zh_knn_descent_info *out);
 
 /* ---- forest self-join (new): all near-duplicate pairs AMONG LEAF-MATES ---------------------------------------------------------------------
  * zh_self_join multiplies every tile of the table by every tile at or above it; this call multiplies a leaf only by itself.  Arguments, key,

@@ -218,6 +218,26 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_knn_descent_info {
+        pub rows_live: u64,
+        pub in_k: u32,
+        pub rev_k: u32,
+        pub k: u32,
+        pub rounds: u32,
+        pub rounds_run: u32,
+        pub launches: u64,
+        pub listed: u64,
+        pub keyed: u64,
+        pub lines_active: u64,
+        pub updates: u64,
+        pub large_lines: u64,
+        pub keyed_round: [u64; 32],
+        pub updates_round: [u64; 32],
+        pub active_round: [u64; 32],
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_join_forest_info {
         pub rows_live: u64,
         pub trees: u32,
@@ -385,6 +405,12 @@ pub mod ffi {
                                               first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64,
                                               d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_knn_graph_refine_rev_info(idx: *const zh_index, out: *mut zh_knn_refine_rev_info) -> c_int;
+        pub fn zh_knn_graph_descent(idx: *mut zh_index, in_ids: *const u64, in_counts: *const u32, in_k: usize, rev_k: usize, k: usize, rounds: usize,
+                                    metric: c_int, cosine_mode: c_int, out_ids: *mut u64, out_keys: *mut u64, out_counts: *mut u32) -> c_int;
+        pub fn zh_knn_graph_descent_device(idx: *mut zh_index, d_in_ids: *const u64, d_in_counts: *const u32, in_k: usize, rev_k: usize, k: usize,
+                                           rounds: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64, d_out_keys: *mut u64,
+                                           d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_knn_graph_descent_info(idx: *const zh_index, out: *mut zh_knn_descent_info) -> c_int;
         pub fn zh_self_join_forest(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, out_a: *mut u64,
                                    out_b: *mut u64, out_keys: *mut u64, out_total: *mut u64) -> c_int;
         pub fn zh_self_join_forest_device(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, d_out_a: *mut u64,
@@ -944,6 +970,41 @@ impl<const N: usize> LSHIndex<N> {
         Ok((0..stored)
             .map(|i| (t.of_row[i], (0..counts[i] as usize).map(|j| (t.of_row[ids[i * k + j] as usize], keys[i * k + j])).collect()))
             .collect())
+    }
+
+    /// (new) knn_graph_refined_rev's answer from ONE call that runs the rounds on the device and, from the second round on, keys only what a new
+    /// entry of a line brings up (zh_knn_graph_descent; 1 <= rounds <= 32, 1 <= k, k + reverse <= 64)
+    pub fn knn_graph_descent<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        k: usize,
+        rounds: usize,
+        reverse: usize,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<(Uuid, Vec<(Uuid, DistanceUnit)>)>> {
+        let t = self.ids.read().unwrap();
+        let stored = t.of_row.len();
+        let (mut ids, mut keys, mut counts) = (vec![0u64; stored * k + 1], vec![0u64; stored * k + 1], vec![0u32; stored + 1]);
+        let (mut rids, mut rcounts) = (vec![0u64; stored * k + 1], vec![0u32; stored + 1]);
+        if stored > 0 {
+            check(unsafe {
+                ffi::zh_knn_graph_forest(self.hip.0, 0, stored as u64, k, Met::METRIC, metric.param(), ids.as_mut_ptr(), keys.as_mut_ptr(),
+                                         counts.as_mut_ptr())
+            })?;
+            check(unsafe {
+                ffi::zh_knn_graph_descent(self.hip.0, ids.as_ptr(), counts.as_ptr(), k, reverse, k, rounds, Met::METRIC, metric.param(),
+                                          rids.as_mut_ptr(), keys.as_mut_ptr(), rcounts.as_mut_ptr())
+            })?;
+        }
+        Ok((0..stored)
+            .map(|i| (t.of_row[i], (0..rcounts[i] as usize).map(|j| (t.of_row[rids[i * k + j] as usize], keys[i * k + j])).collect()))
+            .collect())
+    }
+
+    /// what the most recent zh_knn_graph_descent call did, round by round (zh_knn_graph_descent_info)
+    pub fn knn_descent_info(&self) -> anyhow::Result<ffi::zh_knn_descent_info> {
+        let mut info = ffi::zh_knn_descent_info::default();
+        check(unsafe { ffi::zh_knn_graph_descent_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// what the most recent graph refinement call did (zh_knn_graph_refine_info)

@@ -172,6 +172,20 @@ class KnnRefineRevInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KnnDescentInfo(C.Structure):
+    _fields_ = [("rows_live", C.c_uint64), ("in_k", C.c_uint32), ("rev_k", C.c_uint32), ("k", C.c_uint32), ("rounds", C.c_uint32),
+                ("rounds_run", C.c_uint32), ("launches", C.c_uint64), ("listed", C.c_uint64), ("keyed", C.c_uint64), ("lines_active", C.c_uint64),
+                ("updates", C.c_uint64), ("large_lines", C.c_uint64), ("keyed_round", C.c_uint64 * 32), ("updates_round", C.c_uint64 * 32),
+                ("active_round", C.c_uint64 * 32)]
+
+    def as_dict(self):
+        """the per-round arrays as lists of rounds_run entries"""
+        out = {k: getattr(self, k) for k, _ in self._fields_}
+        for k in ("keyed_round", "updates_round", "active_round"):
+            out[k] = list(out[k])[:self.rounds_run]
+        return out
+
+
 class JoinForestInfo(C.Structure):
     _fields_ = [("rows_live", C.c_uint64), ("trees", C.c_uint32), ("path", C.c_uint32), ("leaf_pairs", C.c_uint64), ("pairs", C.c_uint64),
                 ("candidates", C.c_uint64), ("launches", C.c_uint64), ("tiles", C.c_uint64), ("redone", C.c_uint32)]
@@ -276,6 +290,9 @@ SYMBOLS = [
     ("zh_knn_graph_refine_rev", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_knn_graph_refine_rev_device", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_knn_graph_refine_rev_info", _i, [_vp, _vp]),
+    ("zh_knn_graph_descent", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp]),
+    ("zh_knn_graph_descent_device", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    ("zh_knn_graph_descent_info", _i, [_vp, _vp]),
     ("zh_self_join_forest", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_device", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_info", _i, [_vp, _vp]),

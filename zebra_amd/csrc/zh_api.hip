@@ -353,6 +353,10 @@ struct zh_index {
     DevBuf rv_deg, rv_cur, rv_off, rv_sums, rv_csr, rv_heavy, rv_uni, rv_ctr, rv_oids, rv_ocounts, rv_odeg;
     zh_knn_reverse_info rv_info{};          // (stats_mu)
     zh_knn_refine_rev_info rfr_info{};      // (stats_mu)
+    // NN-descent's per-call scratch beside the reverse graph's (all released before the call returns): the two forward tables of row numbers and
+    // their keys, the two union tables, the new-mask of every line, the list of active lines, every stored row's squared norm, a round's counters
+    DevBuf nd_tab[2], nd_key[2], nd_uni[2], nd_mask, nd_list, nd_qq, nd_ctr;
+    zh_knn_descent_info nd_info{};          // (stats_mu)
     // the forest self-join's per-call scratch beside the self-join's and the forest graph's (all released before the call returns): leaf_of, a path-1
     // panel's pieces and per-line {leaf, key offset}, path 2's segments and candidate pool
     DevBuf fj_leafof, fj_pieces, fj_linel, fj_linek, fj_segs, fj_cand;
@@ -3565,7 +3569,7 @@ static int score_param(int metric, int mode) { return (metric == ZH_COSINE || me
 // index holds only the live-row views (live_dev's list and bitmap survive every call; zh_index_destroy frees them).  Every family scans with the exact
 // search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's, the forest range search with
 // the range search's and the forest join's, the cross-join (all on its LEFT index) with the join's and its own views.
-enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024 };  // one bit per list
+enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024, SCR_ND = 2048 };  // one bit per list
 enum : unsigned {
     SCRATCH_EXACT = SCR_EX,
     SCRATCH_FILTER = SCR_FL | SCRATCH_EXACT,
@@ -3575,6 +3579,7 @@ enum : unsigned {
     SCRATCH_FKNN = SCR_FK | SCRATCH_KNN,
     SCRATCH_REFINE = SCR_RF | SCRATCH_KNN,
     SCRATCH_REVERSE = SCR_RV | SCRATCH_REFINE,
+    SCRATCH_DESCENT = SCR_ND | SCRATCH_REVERSE,
     SCRATCH_FJOIN = SCR_FJ | SCRATCH_JOIN | SCRATCH_FKNN,
     SCRATCH_FRANGE = SCR_FR | SCRATCH_RANGE | SCRATCH_FJOIN,
     SCRATCH_XJOIN = SCR_XJ | SCRATCH_JOIN,  // (on the left index)
@@ -3601,6 +3606,8 @@ static void release_scratch(zh_index *ix, unsigned families) {
     drop(SCR_RF, {&ix->rf_tab, &ix->rf_cnt, &ix->rf_stage, &ix->rf_ctr});
     drop(SCR_RV, {&ix->rv_deg, &ix->rv_cur, &ix->rv_off, &ix->rv_sums, &ix->rv_csr, &ix->rv_heavy, &ix->rv_uni, &ix->rv_ctr, &ix->rv_oids, &ix->rv_ocounts,
                   &ix->rv_odeg});
+    drop(SCR_ND, {&ix->nd_tab[0], &ix->nd_tab[1], &ix->nd_key[0], &ix->nd_key[1], &ix->nd_uni[0], &ix->nd_uni[1], &ix->nd_mask, &ix->nd_list, &ix->nd_qq,
+                  &ix->nd_ctr});
     drop(SCR_FJ, {&ix->fj_leafof, &ix->fj_pieces, &ix->fj_linel, &ix->fj_linek, &ix->fj_segs, &ix->fj_cand});
     drop(SCR_FR, {&ix->fr_counts, &ix->fr_inline, &ix->fr_rowbase, &ix->fr_candbase, &ix->fr_visitbase, &ix->fr_totals, &ix->fr_leafcount, &ix->fr_leaffill,
                   &ix->fr_groupbase, &ix->fr_grouprowbase, &ix->fr_loghead, &ix->fr_logctl, &ix->fr_logpool, &ix->fr_visits, &ix->fr_groups, &ix->fr_groupoff,
@@ -5573,6 +5580,195 @@ extern "C" int zh_knn_graph_refine_rev(zh_index *ix, const uint64_t *in_ids, con
 
 extern "C" int zh_knn_graph_refine_rev_info(const zh_index *ix, zh_knn_refine_rev_info *out) {
     return get_info(ix, &zh_index::rfr_info, out, "zh_knn_graph_refine_rev_info");
+}
+
+// ------------------------------------------------------------------------------------------------
+// NN-descent (zh_nnd.hip): the refinement's rounds on the device, keying from round 2 on only what a new entry brings up.  DESIGN.md s23
+// ------------------------------------------------------------------------------------------------
+// refine_rev_args' order with the rounds and k = 0 behind the metric, and k + rev_k's limit behind in_k + rev_k's.  Whole table: the pointers are
+// judged whatever the table holds
+static int descent_args(zh_index *ix, const void *in_ids, const void *in_counts, size_t in_k, size_t rev_k, size_t k, size_t rounds, int metric, int mode,
+                        const void *ids, const void *keys, const void *counts, const char *who) {
+    if (!ix || !in_ids || !in_counts || !ids || !keys || !counts) return fail(ZH_EINVAL, "%s: null argument", who);
+    const int rc = check_metric(metric, mode);
+    if (rc) return rc;
+    if (rounds < 1 || rounds > ZH_DESCENT_MAX_ROUNDS) return fail(ZH_EINVAL, "%s: rounds %zu outside 1 .. %u", who, rounds, ZH_DESCENT_MAX_ROUNDS);
+    if (!k) return fail(ZH_EINVAL, "%s: k is 0", who);
+    if (in_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: in_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, ZH_REFINE_MAX_IN_K);
+    if (rev_k > ZH_REFINE_MAX_IN_K - in_k) return fail(ZH_ELIMIT, "%s: in_k %zu + rev_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, rev_k, ZH_REFINE_MAX_IN_K);
+    if (k > ZH_REFINE_MAX_IN_K || rev_k > ZH_REFINE_MAX_IN_K - k)
+        return fail(ZH_ELIMIT, "%s: k %zu + rev_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, k, rev_k, ZH_REFINE_MAX_IN_K);
+    if (!in_k) return fail(ZH_EINVAL, "%s: in_k is 0", who);
+    return ZH_OK;
+}
+
+// U(x) of a forward table dTab (w wide): N'(x), then R'(x) -- the transposition and the selection of zh_knn_graph_reverse into dUni (w + rev_k wide)
+static int descent_union(zh_index *ix, const uint32_t *dTab, uint32_t w, uint32_t rev_k, uint32_t *dUni, hipStream_t s, uint64_t *launches) {
+    const uint64_t N = ix->n_rows;
+    HIPCHK(hipMemsetAsync(ix->rv_ctr.p, 0, 32, s));
+    HIPCHK(zh_launch_reverse_csr(dTab, ix->live_dev.bits.as<uint32_t>(), N, w, ix->rv_deg.as<uint32_t>(), ix->rv_cur.as<uint32_t>(), ix->rv_off.as<uint64_t>(),
+                                 ix->rv_sums.as<uint64_t>(), ix->rv_csr.as<uint32_t>(), ix->rv_ctr.as<unsigned long long>(), s));
+    HIPCHK(zh_launch_reverse_select(dTab, w, rev_k, ix->rv_off.as<uint64_t>(), ix->rv_csr.as<uint32_t>(), N, 0, N, 0, N, ix->opt.id_base, dUni, nullptr, nullptr,
+                                    nullptr, ix->rv_heavy.as<uint32_t>(), ix->rv_ctr.as<unsigned long long>(), s));
+    *launches += 5 + 2 * ((N * w + (1ull << 30) - 1) >> 30) + ((N + (1ull << 24) - 1) >> 24);
+    return ZH_OK;
+}
+
+// both entry points once the arguments have been judged
+static int descent_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, uint32_t rev_k, uint32_t k, uint32_t rounds, int metric,
+                        int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, bool host, void *stream, const char *who) {
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    const uint64_t N = ix->n_rows, n_live = ix->live_dev.n_live;
+    if (!N) return ZH_OK;
+    ScratchGuard guard{ix, SCRATCH_DESCENT};
+    const hipStream_t s = call_stream(ix, stream);
+    const uint32_t d = ix->opt.dim, w1 = in_k + rev_k, w = k + rev_k, wmax = std::max(in_k, k);
+    const int param = score_param(metric, mode);
+    zh_knn_descent_info inf{};
+    inf.rows_live = n_live; inf.in_k = in_k; inf.rev_k = rev_k; inf.k = k; inf.rounds = rounds;
+    unsigned long long ctr[ZH_NND_CTRS] = {0, 0, 0, 0, 0, 0};
+    const auto first_round = [&](uint64_t lines, uint64_t launches) {  // what round 1 leaves in the info (ctr: rf_ctr's three words)
+        inf.launches += launches;
+        if (w1 + w1 * w1 > ZH_REFINE_CAP_SMALL) inf.large_lines += lines;
+        inf.listed = ctr[0]; inf.keyed = ctr[1]; inf.updates = ctr[2]; inf.lines_active = n_live;
+        inf.keyed_round[0] = ctr[1]; inf.updates_round[0] = ctr[2]; inf.active_round[0] = n_live;
+        inf.rounds_run = 1;
+    };
+    if (rounds == 1) {  // one round is zh_knn_graph_refine_rev and nothing else: its passes, straight into the caller's arrays, no state of the call's own
+        if ((rc = refine_table(ix, in_ids, in_counts, in_k, host, s))) return rc;
+        const uint32_t *dTab = ix->rf_tab.as<uint32_t>();
+        if (rev_k) {
+            if ((rc = ix->rv_uni.ensure((size_t)N * w1 * 4)) || (rc = reverse_csr(ix, in_k, s)) ||
+                (rc = reverse_select(ix, in_k, rev_k, 0, N, 0, N, true, nullptr, nullptr, nullptr, s, &inf.launches)))
+                return rc;
+            dTab = ix->rv_uni.as<uint32_t>();
+        }
+        LiveCursor live;
+        zh_knn_refine_info one{};
+        const uint64_t host_slab = std::max<uint64_t>(ZH_REFINE_SLAB, (uint64_t(1) << 25) / k / ZH_REFINE_SLAB * ZH_REFINE_SLAB);
+        rc = knn_slabs(ix, 0, N, k, out_ids, out_keys, out_counts, host_slab, host, s, [&](uint64_t r0, uint64_t m, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
+            return refine_slab(ix, &live, dTab, w1, in_k, r0, m, k, metric, mode, dIds, dKeys, dCounts, s, &one);
+        });
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(ctr, ix->rf_ctr.p, 24, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        first_round(one.lines, one.launches);
+        std::lock_guard<std::mutex> ls(ix->stats_mu);
+        ix->nd_info = inf;
+        return ZH_OK;
+    }
+    // ---- the call's state: everything a later round reads is there before the first one starts, so that ZH_ENOMEM comes before any work
+    for (int i = 0; i < 2; i++)
+        if ((rc = ix->nd_tab[i].ensure((size_t)N * k * 4)) || (rc = ix->nd_key[i].ensure((size_t)N * k * 8)) ||
+            (rev_k && (rc = ix->nd_uni[i].ensure((size_t)N * (wmax + rev_k) * 4))))
+            return rc;
+    if ((rc = ix->nd_mask.ensure((size_t)N * 8)) || (rc = ix->nd_list.ensure(std::max<size_t>((size_t)n_live * 4, 4))) || (rc = ix->nd_qq.ensure((size_t)N * 4)) ||
+        (rc = ix->nd_ctr.ensure(ZH_NND_CTRS * 8)))
+        return rc;
+    if (rev_k &&
+        ((rc = ix->rv_deg.ensure((size_t)N * 4)) || (rc = ix->rv_cur.ensure((size_t)N * 4)) || (rc = ix->rv_off.ensure((size_t)(N + 1) * 8)) ||
+         (rc = ix->rv_sums.ensure((size_t)(N / 4096 + 1) * 8)) || (rc = ix->rv_csr.ensure((size_t)N * wmax * 4)) ||
+         (rc = ix->rv_heavy.ensure((size_t)(N * wmax / ZH_REVERSE_HEAVY + 1) * 4)) || (rc = ix->rv_ctr.ensure(32))))
+        return rc;
+    const uint64_t piece = std::min<uint64_t>(N, std::max<uint64_t>(ZH_REFINE_SLAB, (uint64_t(1) << 25) / k / ZH_REFINE_SLAB * ZH_REFINE_SLAB));
+    if ((rc = ix->kn_oids.ensure(piece * k * 8)) || (rc = ix->kn_ocounts.ensure(piece * 4)) || (host && (rc = ix->kn_okeys.ensure(piece * k * 8)))) return rc;
+    uint32_t *tab[2] = {ix->nd_tab[0].as<uint32_t>(), ix->nd_tab[1].as<uint32_t>()};
+    uint64_t *key[2] = {ix->nd_key[0].as<uint64_t>(), ix->nd_key[1].as<uint64_t>()};
+    uint32_t *uni[2] = {ix->nd_uni[0].as<uint32_t>(), ix->nd_uni[1].as<uint32_t>()};
+    unsigned long long *dCtr = ix->nd_ctr.as<unsigned long long>();
+    for (int i = 0; i < 2; i++) {  // (a removed row's line is never written again: empty in both tables)
+        HIPCHK(hipMemsetAsync(tab[i], 0xFF, (size_t)N * k * 4, s));
+        HIPCHK(hipMemsetAsync(key[i], 0xFF, (size_t)N * k * 8, s));
+    }
+    if (metric == ZH_COSINE)
+        for (uint64_t r0 = 0; r0 < N; r0 += 1ull << 30)
+            HIPCHK(zh_launch_qnorm(ix->X.as<float>() + r0 * d, (uint32_t)std::min<uint64_t>(1ull << 30, N - r0), d, ix->nd_qq.as<float>() + r0, s));
+    // ---- round 1: zh_knn_graph_refine_rev's passes; the keys go straight to key[0], the ids piece by piece through the staging into tab[0]
+    if ((rc = refine_table(ix, in_ids, in_counts, in_k, host, s))) return rc;
+    const uint32_t *Uprev = ix->rf_tab.as<uint32_t>();  // U_0, w1 wide
+    if (rev_k) {
+        if ((rc = descent_union(ix, ix->rf_tab.as<uint32_t>(), in_k, rev_k, uni[0], s, &inf.launches))) return rc;
+        Uprev = uni[0];
+    }
+    zh_knn_refine_info one{};
+    {
+        LiveCursor live;
+        for (uint64_t r0 = 0; r0 < N; r0 += piece) {
+            const uint64_t m = std::min(piece, N - r0);
+            if ((rc = refine_slab(ix, &live, Uprev, w1, in_k, r0, m, k, metric, mode, ix->kn_oids.as<uint64_t>(), key[0] + r0 * k, ix->kn_ocounts.as<uint32_t>(), s,
+                                  &one)))
+                return rc;
+            HIPCHK(zh_launch_nnd_rows(ix->kn_oids.as<uint64_t>(), ix->opt.id_base, m, k, tab[0] + r0 * k, s));
+            inf.launches++;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(ctr, ix->rf_ctr.p, 24, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    first_round(one.lines, one.launches);
+    // ---- rounds 2 ..: G_r is tab[(r - 1) & 1] with key[(r - 1) & 1], U_r is that table or uni[r & 1]; the round writes the other pair
+    uint32_t wp = w1;
+    for (uint32_t r = 1; r < rounds && inf.updates; r++) {
+        const int c = (int)((r - 1) & 1), nx = (int)(r & 1);
+        const uint32_t *Ucur = tab[c];
+        if (rev_k) {
+            if ((rc = descent_union(ix, tab[c], k, rev_k, uni[r & 1], s, &inf.launches))) return rc;
+            Ucur = uni[r & 1];
+        }
+        HIPCHK(hipMemsetAsync(dCtr, 0, ZH_NND_CTRS * 8, s));
+        HIPCHK(zh_launch_nnd_flag(Uprev, wp, Ucur, w, N, ix->nd_mask.as<uint64_t>(), s));
+        HIPCHK(zh_launch_nnd_plan(Ucur, w, k, ix->nd_mask.as<uint64_t>(), ix->live_dev.rows.as<uint32_t>(), n_live, key[c], tab[nx], key[nx],
+                                  ix->nd_list.as<uint32_t>(), dCtr, s));
+        HIPCHK(zh_launch_nnd_lines(ix->X.as<float>(), d, Ucur, w, k, ix->nd_mask.as<uint64_t>(), key[c], ix->nd_qq.as<float>(), ix->nd_list.as<uint32_t>(), n_live,
+                                   metric, param, tab[nx], key[nx], dCtr, s));
+        inf.launches += 2 * ((N + (1ull << 24) - 1) >> 24) + (w + w * w > ZH_REFINE_CAP_SMALL ? 2 : 1);
+        HIPCHK(hipMemcpyAsync(ctr, dCtr, ZH_NND_CTRS * 8, hipMemcpyDeviceToHost, s));  // the round's one readback: it decides the early stop
+        HIPCHK(hipStreamSynchronize(s));
+        inf.listed += ctr[0]; inf.keyed += ctr[1]; inf.updates = ctr[2]; inf.lines_active += ctr[3]; inf.large_lines += ctr[5];
+        inf.keyed_round[r] = ctr[1]; inf.updates_round[r] = ctr[2]; inf.active_round[r] = ctr[3];
+        inf.rounds_run = r + 1;
+        Uprev = Ucur;
+        wp = w;
+    }
+    // ---- the answer: G_{rounds_run}
+    const int f = (int)((inf.rounds_run - 1) & 1);
+    if (!host) {
+        HIPCHK(zh_launch_nnd_emit(tab[f], key[f], k, ix->opt.id_base, N, out_ids, out_keys, out_counts, s));
+        HIPCHK(hipStreamSynchronize(s));
+        inf.launches += (N + (1ull << 24) - 1) >> 24;
+    } else {
+        for (uint64_t r0 = 0; r0 < N; r0 += piece) {
+            const uint64_t m = std::min(piece, N - r0);
+            HIPCHK(zh_launch_nnd_emit(tab[f] + r0 * k, key[f] + r0 * k, k, ix->opt.id_base, m, ix->kn_oids.as<uint64_t>(), ix->kn_okeys.as<uint64_t>(),
+                                      ix->kn_ocounts.as<uint32_t>(), s));
+            if ((rc = knn_stage_out(ix, r0, m, k, out_ids, out_keys, out_counts, s))) return rc;
+            inf.launches++;
+        }
+    }
+    std::lock_guard<std::mutex> ls(ix->stats_mu);
+    ix->nd_info = inf;
+    return ZH_OK;
+}
+
+extern "C" int zh_knn_graph_descent_device(zh_index *ix, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, size_t rev_k, size_t k, size_t rounds,
+                                           int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
+    int rc = descent_args(ix, d_in_ids, d_in_counts, in_k, rev_k, k, rounds, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_descent_device");
+    if (rc) return rc;
+    return descent_call(ix, d_in_ids, d_in_counts, (uint32_t)in_k, (uint32_t)rev_k, (uint32_t)k, (uint32_t)rounds, metric, mode, d_out_ids, d_out_keys, d_out_counts,
+                        false, stream, "zh_knn_graph_descent_device");
+}
+
+extern "C" int zh_knn_graph_descent(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, size_t rev_k, size_t k, size_t rounds, int metric,
+                                    int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts) {
+    int rc = descent_args(ix, in_ids, in_counts, in_k, rev_k, k, rounds, metric, mode, out_ids, out_keys, out_counts, "zh_knn_graph_descent");
+    if (rc) return rc;
+    return descent_call(ix, in_ids, in_counts, (uint32_t)in_k, (uint32_t)rev_k, (uint32_t)k, (uint32_t)rounds, metric, mode, out_ids, out_keys, out_counts, true,
+                        nullptr, "zh_knn_graph_descent");
+}
+
+extern "C" int zh_knn_graph_descent_info(const zh_index *ix, zh_knn_descent_info *out) {
+    return get_info(ix, &zh_index::nd_info, out, "zh_knn_graph_descent_info");
 }
 
 // judged before any device is touched, in this order of kinds: null index (even for n = 0), null inputs or outputs of a non-empty request, the two

@@ -514,6 +514,26 @@ hipError_t zh_launch_reverse_select(const uint32_t *dTab, uint32_t in_k, uint32_
                                     uint64_t nx, uint64_t first_row, uint64_t n, uint64_t id_base, uint32_t *dUni, uint64_t *dOutIds, uint32_t *dOutCounts,
                                     uint32_t *dOutDegree, uint32_t *dHeavy, unsigned long long *dCtr, hipStream_t s);
 
+// ---- NN-descent's incremental rounds (zh_nnd.hip) over u32 tables of row numbers: the forward table [stored rows][k] with its keys [stored rows][k],
+// and the table a round ranks over, dU [stored rows][w] (the forward table itself, w = k, or zh_launch_reverse_select's union table, w = k + rev_k)
+#define ZH_NND_CTRS 6u  // a round's counters: listed, keyed, updates, active lines, lines on the list's front (small), lines on its back (large)
+// lines of u64 ids (2^64 - 1 tails, id_base + row otherwise: a round's own output) -> row numbers, UINT32_MAX tails
+hipError_t zh_launch_nnd_rows(const uint64_t *dIds, uint64_t id_base, uint64_t nl, uint32_t k, uint32_t *dTab, hipStream_t s);
+// and back at the end: ids with id_base, keys, 2^64 - 1 tails in both, counts
+hipError_t zh_launch_nnd_emit(const uint32_t *dTab, const uint64_t *dKeys, uint32_t k, uint64_t id_base, uint64_t nl, uint64_t *dOutIds, uint64_t *dOutKeys,
+                              uint32_t *dOutCounts, hipStream_t s);
+// dMask[x] bit j = entry j of dCur's line x (wc wide) is a row that dPrev's line x (wp wide) does not hold
+hipError_t zh_launch_nnd_flag(const uint32_t *dPrev, uint32_t wp, const uint32_t *dCur, uint32_t wc, uint64_t n_rows, uint64_t *dMask, hipStream_t s);
+// per live row (dRows, n_live of them): a line that gathers nothing is copied to dTabNext / dKeysNext, any other goes on dList (n_live words) -- from
+// the front (dCtr[4]) if its raw gather count is <= ZH_REFINE_CAP_SMALL, from the back (dCtr[5]) if not
+hipError_t zh_launch_nnd_plan(const uint32_t *dU, uint32_t w, uint32_t k, const uint64_t *dMask, const uint32_t *dRows, uint64_t n_live, const uint64_t *dKeys,
+                              uint32_t *dTabNext, uint64_t *dKeysNext, uint32_t *dList, unsigned long long *dCtr, hipStream_t s);
+// the listed lines: the first k by (key, id) of the keyed candidates and the forward line to dTabNext / dKeysNext; dCtr[0..3] += listed, keyed,
+// updates, lines that keyed something.  dQQ: the squared norm of every stored row (read for the cosine kinds only)
+hipError_t zh_launch_nnd_lines(const float *dX, uint32_t d, const uint32_t *dU, uint32_t w, uint32_t k, const uint64_t *dMask, const uint64_t *dKeys, const float *dQQ,
+                               const uint32_t *dList, uint64_t n_live, int metric, int param, uint32_t *dTabNext, uint64_t *dKeysNext, unsigned long long *dCtr,
+                               hipStream_t s);
+
 // ---- the forest self-join (zh_fjoin.hip): every pair of leaf-mates whose key is <= one threshold key, each pair once (the first tree that puts
 // the two rows together owns it).  Hit pool, counter and order as the exact self-join's
 #define ZH_FJOIN_PANEL_LINES 16384u  // path 1: lines of one panel at most

@@ -11,14 +11,7 @@
 //                        (c) block_bitonic_sort by (key, id), the first min(k, U) written with id_base, tails and the count; `updates` = written
 //                        rows that N'(a) does not hold.  The table may be zh_reverse.hip's union table (N'(x) then the kept reverse
 //                        neighbours, in_k + rev_k wide): in_k is then that width, and N'(a) the line's first fwd_k entries.
-#include "zh_internal.h"
-#include "zh_device.h"
-
-#ifndef ZH_REFINE_INFLIGHT
-#define ZH_REFINE_INFLIGHT 4  // candidate rows a wave has in flight (build-time knob)
-#endif
-
-#define RF_NONE 0xFFFFFFFFu
+#include "zh_refine_dev.h"  // refine_key, block_bitonic_sort_u32, block_sum_u32, RF_NONE, ZH_REFINE_INFLIGHT: shared with zh_nnd.hip
 
 // a wave per line, lane j its entry j (in_k <= 64)
 __global__ __launch_bounds__(256) void refine_rows_kernel(const uint64_t *__restrict__ in, const uint32_t *__restrict__ counts,
@@ -52,54 +45,6 @@ hipError_t zh_launch_refine_rows(const uint64_t *dIn, const uint32_t *dCounts, c
                            dTab);
     }
     return hipGetLastError();
-}
-
-// ascending LDS bitonic sort of n u32 words, n a power of two
-__device__ __forceinline__ void block_bitonic_sort_u32(uint32_t *sv, uint32_t n) {
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t size = 2; size <= n; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            for (uint32_t i = tid; i < (n >> 1); i += 256) {
-                const uint32_t lo = ((i & ~(stride - 1)) << 1) | (i & (stride - 1)), hi = lo + stride;
-                const bool asc = (lo & size) == 0;
-                const uint32_t a = sv[lo], b = sv[hi];
-                if ((a > b) == asc) { sv[lo] = b; sv[hi] = a; }
-            }
-        }
-    }
-    __syncthreads();
-}
-
-// the sum of v over the block's 256 threads, for every thread (red: 4 words; the barrier before it also closes what the caller did to LDS)
-__device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t *red) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the key of one candidate row, loaded (D > 0: v, the canonical lane layout) or still in memory (D == 0), against the line's row: exact_key's arithmetic
-template <int D, int KIND>
-__device__ __forceinline__ uint64_t refine_key(const float4 *v, const float *__restrict__ xrow, const float *__restrict__ q, const float4 *qreg, float qq,
-                                               uint32_t d, uint32_t lane, int metric, int param) {
-    float s0 = 0.f, s1 = 0.f;
-    if constexpr (D > 0) {
-        constexpr int NV = RowVec<D>::NV;
-        row_pair_sums<D, KIND>(v, qreg, lane, param, s0, s1);
-        if (KIND == K_COS) {
-            float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int j = 0; j < NV; j++) {
-                const bool act = (j < RowVec<D>::NJ) || (lane < (uint32_t)RowVec<D>::REM4);
-                if (act) sq4(v[j], c);
-            }
-            s1 = wave_sum_canonical((c.x + c.y) + (c.z + c.w));
-        }
-    } else
-        lane_sums_generic<KIND>(xrow, q, d, lane, param, s0, s1);
-    return key_of(metric, param, s0, s1, qq);
 }
 
 template <int D, int KIND, int CAP>

@@ -712,6 +712,37 @@ class LSHIndex:
         knn_refine_info's fields, then rev_k, edges, kept, max_degree"""
         return self._info(_ffi.KnnRefineRevInfo, lib().zh_knn_graph_refine_rev_info)
 
+    def knn_graph_descent(self, graph, k, metric, rounds=8, reverse=0):
+        """NN-descent over a graph of ALL stored rows (`graph` as for knn_graph_refine): up to `rounds` rounds of knn_graph_refine(reverse=reverse)
+        in ONE call that keeps the graph on the device and, from the second round on, keys only the candidates a NEW entry of a line brings up.
+        The answer is bit for bit knn_graph_refine(graph, k, metric, rounds=rounds, reverse=reverse)'s, early stop at the first round without
+        updates included; knn_descent_info() describes the call round by round.  Whole table only, 1 <= rounds <= 32, k >= 1,
+        in_k + reverse <= 64 and k + reverse <= 64.  -> (ids [stored rows, k] u64, keys [stored rows, k] u64, counts [stored rows] u32)."""
+        in_ids = np.ascontiguousarray(graph[0], np.uint64)
+        in_counts = np.ascontiguousarray(graph[-1], np.uint32)
+        stored = self.stored_rows()
+        if in_ids.ndim != 2 or in_counts.ndim != 1 or in_ids.shape[0] != stored or in_counts.shape[0] != stored:
+            raise _ffi.ZhError(_ffi.ZH_EINVAL, "knn_graph_descent: the graph must cover the %d stored rows: ids [%d, in_k], counts [%d]" % (stored, stored, stored))
+        k = int(k)
+        ids = np.empty((stored, max(k, 0)), np.uint64)
+        keys = np.empty((stored, max(k, 0)), np.uint64)
+        counts = np.zeros(stored, np.uint32)
+        check(lib().zh_knn_graph_descent(self._h, _p(in_ids), _p(in_counts), in_ids.shape[1], int(reverse), k, int(rounds), metric.metric, metric.mode,
+                                         _p(ids), _p(keys), _p(counts)))
+        return ids, keys, counts
+
+    def knn_graph_descent_device(self, d_in_ids_ptr, d_in_counts_ptr, in_k, rev_k, k, rounds, metric, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream=None):
+        """knn_graph_descent with the graph ([stored rows, in_k] u64, [stored rows] u32) and the outputs ([stored rows, k] u64 twice,
+        [stored rows] u32) already in device memory (raw pointers, e.g. torch .data_ptr())."""
+        check(lib().zh_knn_graph_descent_device(self._h, d_in_ids_ptr, d_in_counts_ptr, int(in_k), int(rev_k), int(k), int(rounds), metric.metric, metric.mode,
+                                                d_ids_ptr, d_keys_ptr, d_counts_ptr, stream))
+
+    def knn_descent_info(self):
+        """what the most recent knn_graph_descent call on this index did (zh_knn_graph_descent_info): rows_live, in_k, rev_k, k, rounds, rounds_run,
+        launches, listed, keyed, lines_active (sums over the rounds run), updates (of the last round run), large_lines, and per round run the
+        lists keyed_round, updates_round and active_round"""
+        return self._info(_ffi.KnnDescentInfo, lib().zh_knn_graph_descent_info)
+
     def knn_graph_reverse(self, graph, rev_k, first_row=0, n=None):
         """the capped reverse graph of a graph of ALL stored rows (`graph` as for knn_graph_refine): line i holds up to rev_k of the live rows that
         name stored row first_row + i and that its own line does not name -- a deterministic pseudo-random sample by a hash of the pair, the same
@@ -1163,6 +1194,14 @@ class Database:
             return {}
         graph = self.index.knn_graph_forest(k, self.metric)
         return self._graph_documents(*self.index.knn_graph_refine(graph, k, self.metric, rounds=rounds, reverse=reverse))
+
+    def knn_graph_descent(self, k, rounds=8, reverse=0):
+        """knn_graph_forest, then LSHIndex.knn_graph_descent: the rounds of knn_graph_refined in one call on the device, keying only what is new
+        from the second round on -- the same answer -> what knn_graph returns"""
+        if self.index.no_vectors():
+            return {}
+        graph = self.index.knn_graph_forest(k, self.metric)
+        return self._graph_documents(*self.index.knn_graph_descent(graph, k, self.metric, rounds=rounds, reverse=reverse))
 
     def _graph_documents(self, ids, keys, counts):
         dist = self._key_numbers(np.ascontiguousarray(keys)).reshape(keys.shape)

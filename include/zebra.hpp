@@ -487,6 +487,65 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_knn_graph_descent_info(h_.get(), &info));
         return info;
     }
+    // Graph search (zh_index_set_graph, zh_search_graph_batch): a k-NN graph over the first g_rows stored rows kept on the device (4 g_rows g_k bytes)
+    // through append, add, remove, deduplicate, build and set_forest; replaced by a second set_graph, dropped by drop_graph, compact (once rows
+    // move) and clear, never saved.  in_ids [g_rows * g_k] / in_counts [g_rows] as knn_graph_refine takes them.
+    void set_graph(const std::vector<Id> &in_ids, const std::vector<std::uint32_t> &in_counts, std::size_t g_k) {
+        const std::uint64_t g_rows = in_counts.size();
+        if (in_ids.size() != g_rows * g_k) throw std::invalid_argument("set_graph: in_ids holds g_k entries per line of in_counts");
+        check(zh_index_set_graph(h_.get(), g_rows ? in_ids.data() : nullptr, g_rows ? in_counts.data() : nullptr, g_rows, g_k));
+    }
+    void set_graph_device(const Id *d_in_ids, const std::uint32_t *d_in_counts, std::uint64_t g_rows, std::size_t g_k, void *stream = nullptr) {
+        check(zh_index_set_graph_device(h_.get(), d_in_ids, d_in_counts, g_rows, g_k, stream));
+    }
+    void drop_graph() { check(zh_index_drop_graph(h_.get())); }
+    zh_graph_info graph_info() const {
+        zh_graph_info info{};
+        check(zh_index_graph_info(h_.get(), &info));
+        return info;
+    }
+    // beam search over the attached graph under search_exact_batch's keys: seeds holds n_seed ids per query (invalid, removed and repeated ones are
+    // ignored); the beam keeps the `beam` best rows met, an iteration expands its first `width` unexpanded ones, until none is left or max_iters
+    // (0: no cap) iterations ran.  1 <= top_k <= beam <= ZH_GRAPH_MAX_BEAM, width * g_k <= 256, n_seed <= ZH_GRAPH_MAX_SEEDS.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> search_graph_batch(const std::vector<Embedding<N>> &queries, const std::vector<Id> &seeds,
+                                                                               std::size_t n_seed, std::size_t top_k, const Met &metric,
+                                                                               std::size_t beam = 64, std::size_t width = 1,
+                                                                               std::size_t max_iters = 0) const {
+        const std::size_t b = queries.size();
+        if (seeds.size() != b * n_seed) throw std::invalid_argument("search_graph_batch: seeds holds n_seed ids per query");
+        std::vector<Id> ids(b * top_k + 1);
+        std::vector<DistanceUnit> keys(b * top_k + 1);
+        std::vector<std::uint32_t> counts(b + 1);
+        check(zh_search_graph_batch(h_.get(), b ? queries[0].data() : nullptr, b, seeds.data(), n_seed, top_k, beam, width, max_iters, Met::metric,
+                                    metric.mode(), ids.data(), keys.data(), counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(b);
+        for (std::size_t i = 0; i < b; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * top_k + j], keys[i * top_k + j]);
+        return out;
+    }
+    // ... with the same strided rows of the attached graph as every query's seeds: id_base + j * g_rows / n_seed
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> search_graph_batch(const std::vector<Embedding<N>> &queries, std::size_t top_k, const Met &metric,
+                                                                               std::size_t beam = 64, std::size_t width = 1, std::size_t max_iters = 0,
+                                                                               std::size_t n_seed = 32) const {
+        const std::uint64_t g_rows = graph_info().g_rows, base = zh_index_id_base(h_.get());
+        std::vector<Id> seeds(queries.size() * n_seed);
+        for (std::size_t i = 0; i < seeds.size(); i++) seeds[i] = base + (i % n_seed) * g_rows / n_seed;
+        return search_graph_batch(queries, seeds, n_seed, top_k, metric, beam, width, max_iters);
+    }
+    template <class Met>
+    void search_graph_batch_device(const float *d_queries, std::size_t b, const Id *d_seeds, std::size_t n_seed, std::size_t top_k, std::size_t beam,
+                                   std::size_t width, std::size_t max_iters, const Met &metric, Id *d_out_ids, DistanceUnit *d_out_keys,
+                                   std::uint32_t *d_out_counts, void *stream = nullptr) const {
+        check(zh_search_graph_batch_device(h_.get(), d_queries, b, d_seeds, n_seed, top_k, beam, width, max_iters, Met::metric, metric.mode(), d_out_ids,
+                                           d_out_keys, d_out_counts, stream));
+    }
+    zh_graph_search_info search_graph_info() const {
+        zh_graph_search_info info{};
+        check(zh_search_graph_info(h_.get(), &info));
+        return info;
+    }
     // The capped reverse graph on its own (zh_knn_graph_reverse): element i = up to rev_k of the live rows that name stored row first_row + i and
     // that its own line does not name, in (hash, row) order; degree[i] = its uncapped in-degree.  No metric, no keys, no forest.
     struct ReverseGraph {
@@ -589,7 +648,8 @@ class Database {
     void deduplicate() {
         for (Id i : index.deduplicate()) documents_.erase(i);
     }
-    // (new) compact the index and re-key the documents with the old -> new id map
+    // (new) compact the index and re-key the documents with the old -> new id map.  Rows move, so the database is left WITHOUT a graph
+    // (build_graph again before query_vectors_graph) -- unless nothing was removed and nothing moved.
     void compact() {
         const Id base = zh_index_id_base(index.handle());
         const std::vector<Id> new_ids = index.compact();
@@ -612,6 +672,37 @@ class Database {
         std::map<std::size_t, std::map<Id, std::string>> results;
         if (index.no_vectors()) return results;  // core.rs:295-297
         const auto nb = index.search_batch(vectors, number_of_results, metric_);
+        for (std::size_t i = 0; i < nb.size(); i++) {
+            auto &m = results[i];
+            for (auto &p : nb[i]) {
+                auto it = documents_.find(p.first);
+                m[p.first] = it == documents_.end() ? std::string() : it->second;
+            }
+        }
+        return results;
+    }
+
+    // (new) make the graph query_vectors_graph walks and attach it: the forest graph, NN-descent, LSHIndex::set_graph.  Needs trees.
+    zh_graph_info build_graph(std::size_t k = 32, std::size_t rounds = 8, std::size_t reverse = 0) {
+        const std::uint64_t stored = zh_index_stored_rows(index.handle());
+        if (!stored) return index.graph_info();
+        std::vector<Id> fids(stored * k), fkeys(stored * k), ids(stored * k), keys(stored * k);
+        std::vector<std::uint32_t> fcounts(stored), counts(stored);
+        auto ok = [](int rc) { if (rc != ZH_OK) throw std::runtime_error(zh_last_error()); };
+        ok(zh_knn_graph_forest(index.handle(), 0, stored, k, Met::metric, metric_.mode(), fids.data(), fkeys.data(), fcounts.data()));
+        ok(zh_knn_graph_descent(index.handle(), fids.data(), fcounts.data(), k, reverse, k, rounds, Met::metric, metric_.mode(), ids.data(), keys.data(),
+                                counts.data()));
+        index.set_graph(ids, counts, k);
+        return index.graph_info();
+    }
+    // (new) query_vectors answered by LSHIndex::search_graph_batch over the attached graph, strided seeds
+    std::map<std::size_t, std::map<Id, std::string>> query_vectors_graph(const std::vector<Embedding<N>> &vectors, std::size_t number_of_results,
+                                                                         std::size_t beam = 64, std::size_t width = 1, std::size_t max_iters = 0,
+                                                                         std::size_t n_seed = 32) const {
+        std::map<std::size_t, std::map<Id, std::string>> results;
+        if (index.no_vectors()) return results;
+        const auto nb = index.search_graph_batch(vectors, number_of_results, metric_, beam < number_of_results ? number_of_results : beam, width, max_iters,
+                                                 n_seed);
         for (std::size_t i = 0; i < nb.size(); i++) {
             auto &m = results[i];
             for (auto &p : nb[i]) {

@@ -38,6 +38,9 @@
  *   zh_knn_graph_refine_rev[_device]     (new) zh_knn_graph_refine over each row's neighbours AND sampled reverse neighbours
  *   zh_knn_graph_descent[_device]        (new) the rounds of zh_knn_graph_refine_rev in one call on the device, keying from the second round on
  *                                        only what a new entry brings up: the loop's answer bit for bit
+ *   zh_index_set_graph[_device] / zh_index_drop_graph / zh_index_graph_info  (new) a k-NN graph over the stored rows, kept on the device between calls
+ *   zh_search_graph_batch[_device]       (new) beam search over that graph: a best-first walk from caller-given seeds, exact keys, an approximate
+ *                                        visited set
  *   zh_self_join_forest[_device]         (new) every pair of leaf-mates whose key is at or below one threshold key, each pair once: exact keys,
  *                                        approximate candidates
  *   zh_search_range_forest_batch[_device] (new) every member of the leaves the walk visits for a query whose key is at or below the query's
@@ -810,6 +813,75 @@ typedef struct zh_knn_descent_info {  /* the most recent zh_knn_graph_descent* c
     uint64_t active_round[32];   /* per round run: lines with a non-empty S(a); [0] = the live rows */
 } zh_knn_descent_info;
 ZH_API int zh_knn_graph_descent_info(const zh_index *idx, zh_knn_descent_info *out);
+
+/* ---- graph search (new): beam search over a k-NN graph kept on the index --------------------------------------------------------------------
+ * The graph calls above make a graph and hand it back; these calls keep one on the index and answer queries by walking it.  What is approximate
+ * is the set of rows that get a key, never the arithmetic: key(r) below is zh_distance_batch's key of stored row r against the query --
+ * zh_search_exact_batch's key, bit for bit, for every metric, mode, power and dimension.
+ * The attached graph.  zh_index_set_graph[_device](idx, in_ids, in_counts, g_rows, g_k) takes a graph over the first g_rows stored rows (g_rows <=
+ * stored rows; the usual case is all of them), in_ids [g_rows][g_k] u64 in the id space id_base + row and in_counts [g_rows] u32, exactly as
+ * zh_knn_graph_refine takes them, and keeps it on the device as the table of u32 row numbers that call makes: entries past the line's count,
+ * outside [id_base, id_base + stored rows) (2^64-1 included), naming a removed row or repeated inside their line are masked.  N'(p) at search time
+ * is the LIVE rows among line p's unmasked entries, judged against the live rows of the moment of the search: a zh_index_remove after the attach
+ * needs no re-attach, a removed row is no candidate and is never expanded, and a row p >= g_rows (appended since the attach) has an empty line.
+ * A second set_graph replaces the first; zh_index_drop_graph releases it (ZH_OK with none attached); zh_index_graph_info reports it.  The graph
+ * survives append, add, remove, deduplicate, build and set_forest -- rows keep their numbers -- and is dropped by zh_index_compact (rows move) and
+ * zh_index_clear.  It is never part of a snapshot: a loaded index has none.  The host entry streams the ids through the pinned chunks of
+ * zh_knn_graph_refine's host entry (ZH_REFINE_CHUNK_BYTES).  Judged before any device is touched, in this order: a null index, null arrays with
+ * g_rows > 0, g_k = 0 (ZH_EINVAL), g_k > ZH_REFINE_MAX_IN_K (ZH_ELIMIT); under the index's lock: g_rows above the stored rows (ZH_EINVAL), a
+ * table of 2^31 rows or more (ZH_ELIMIT: the search keeps a flag beside a row number in one word).  Attach and drop take the lock as a mutation
+ * does.  Device memory: 4 g_rows g_k bytes kept; per call, released before return, the host entry's 4 g_rows bytes of counts and one chunk of ids.
+ * The search.  For each of the b queries (queries [b][dim] f32, seeds [b][n_seed] u64 in the id space):
+ *   1. S(q) = the live stored rows the query's seeds name; a seed that is out of range, removed or repeated is ignored, a seed >= g_rows is
+ *      allowed.  The beam B = the first `beam` of S(q) by (key, id), every entry unexpanded.
+ *   2. Iteration t = 0, 1, ... stops when t == max_iters (max_iters = 0: no cap) or when B has no unexpanded entry.  Otherwise P = the first
+ *      `width` unexpanded entries of B in (key, id) order, marked expanded; cand = the union of N'(p) for p in P, each row once, minus the rows
+ *      in B now (the members of P included); cand is keyed, and B becomes the first `beam` of B union cand by (key, id), flags travelling with
+ *      their rows.
+ *   3. The answer is the first top_k of B in zh_search_exact_batch's layout: out_ids / out_keys [b][top_k], out_counts [b] = min(top_k, |B|),
+ *      2^64-1 tails in both arrays, ids carry id_base.  A query with no valid seed has count 0.
+ * A row that was keyed and fell out of B can be keyed again; that never changes B (a row only leaves, or fails to enter, a FULL beam, and a full
+ * beam's last (key, id) never rises), so answer and iteration count are those of the textbook rule "minus every row keyed so far" -- only
+ * `keyed` is larger.  There is no visited set.
+ * Limits: 1 <= top_k <= beam <= ZH_GRAPH_MAX_BEAM, 1 <= width with width * g_k <= 256, 1 <= n_seed <= ZH_GRAPH_MAX_SEEDS, max_iters <=
+ * ZH_GRAPH_MAX_ITERS.  Judged before any device is touched, in this order of kinds: a null index, null pointers of a request with b > 0, an
+ * unknown metric, a zero top_k, beam, width or n_seed (ZH_EINVAL), then the limits (ZH_ELIMIT: beam, top_k > beam, n_seed, width > 256,
+ * max_iters); under the lock: no attached graph (ZH_ESTATE), width * g_k > 256 (ZH_ELIMIT).  b = 0 is ZH_OK.  Locking and stream semantics
+ * as zh_search_exact_batch_device.  One 256-thread block per query, launches of at most ZH_GRAPH_BATCH queries.  Device scratch is per call and
+ * released before return: 4 bytes per query of an internal batch (the cosine norms), 40 bytes of counters, and for the host entry the staged
+ * batch: per query 4 dim + 8 n_seed + 16 top_k + 4 bytes.  zh_stats_t and every sibling info struct are left alone.  DESIGN.md s24. */
+#define ZH_GRAPH_MAX_BEAM 256u
+#define ZH_GRAPH_MAX_SEEDS 64u
+#define ZH_GRAPH_MAX_ITERS 65535u
+#define ZH_GRAPH_BATCH 16384u  /* queries of one launch */
+ZH_API int zh_index_set_graph(zh_index *idx, const uint64_t *in_ids, const uint32_t *in_counts, uint64_t g_rows, size_t g_k);
+/* The same with the graph in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_index_set_graph_device(zh_index *idx, const uint64_t *d_in_ids, const uint32_t *d_in_counts, uint64_t g_rows, size_t g_k, void *stream);
+ZH_API int zh_index_drop_graph(zh_index *idx);
+typedef struct zh_graph_info {  /* the graph attached to this index now */
+    uint32_t attached;  /* 1: a graph is attached */
+    uint32_t g_k;       /* its line width */
+    uint64_t g_rows;    /* its lines */
+    uint64_t bytes;     /* device bytes it holds */
+} zh_graph_info;
+ZH_API int zh_index_graph_info(const zh_index *idx, zh_graph_info *out);
+ZH_API int zh_search_graph_batch(zh_index *idx, const float *queries, size_t b, const uint64_t *seeds, size_t n_seed, size_t top_k, size_t beam,
+                                 size_t width, size_t max_iters, int metric, int cosine_mode, uint64_t *out_ids, uint64_t *out_keys,
+                                 uint32_t *out_counts);
+/* The same with queries, seeds and every output in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_search_graph_batch_device(zh_index *idx, const float *d_queries, size_t b, const uint64_t *d_seeds, size_t n_seed, size_t top_k,
+                                        size_t beam, size_t width, size_t max_iters, int metric, int cosine_mode, uint64_t *d_out_ids,
+                                        uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream);
+typedef struct zh_graph_search_info {  /* the most recent zh_search_graph_batch* call on this index; every field a sum over the batch */
+    uint64_t queries;
+    uint64_t seeds;       /* valid seeds: the sum of |S(q)| */
+    uint64_t iterations;
+    uint64_t expanded;    /* the sum of |P| */
+    uint64_t keyed;       /* |S(q)| plus every |cand| */
+    uint64_t capped;      /* queries stopped by max_iters with an unexpanded entry left */
+    uint64_t launches;    /* launches of the search kernel: ceil(b / ZH_GRAPH_BATCH) */
+} zh_graph_search_info;
+ZH_API int zh_search_graph_info(const zh_index *idx, zh_graph_search_info *out);
 
 /* ---- forest self-join (new): all near-duplicate pairs AMONG LEAF-MATES ---------------------------------------------------------------------
  * zh_self_join multiplies every tile of the table by every tile at or above it; this call multiplies a leaf only by itself.  Arguments, key,

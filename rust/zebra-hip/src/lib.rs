@@ -238,6 +238,27 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_graph_info {
+        pub attached: u32,
+        pub g_k: u32,
+        pub g_rows: u64,
+        pub bytes: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
+    pub struct zh_graph_search_info {
+        pub queries: u64,
+        pub seeds: u64,
+        pub iterations: u64,
+        pub expanded: u64,
+        pub keyed: u64,
+        pub capped: u64,
+        pub launches: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_join_forest_info {
         pub rows_live: u64,
         pub trees: u32,
@@ -411,6 +432,18 @@ pub mod ffi {
                                            rounds: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64, d_out_keys: *mut u64,
                                            d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_knn_graph_descent_info(idx: *const zh_index, out: *mut zh_knn_descent_info) -> c_int;
+        pub fn zh_index_set_graph(idx: *mut zh_index, in_ids: *const u64, in_counts: *const u32, g_rows: u64, g_k: usize) -> c_int;
+        pub fn zh_index_set_graph_device(idx: *mut zh_index, d_in_ids: *const u64, d_in_counts: *const u32, g_rows: u64, g_k: usize,
+                                         stream: *mut c_void) -> c_int;
+        pub fn zh_index_drop_graph(idx: *mut zh_index) -> c_int;
+        pub fn zh_index_graph_info(idx: *const zh_index, out: *mut zh_graph_info) -> c_int;
+        pub fn zh_search_graph_batch(idx: *mut zh_index, queries: *const f32, b: usize, seeds: *const u64, n_seed: usize, top_k: usize, beam: usize,
+                                     width: usize, max_iters: usize, metric: c_int, cosine_mode: c_int, out_ids: *mut u64, out_keys: *mut u64,
+                                     out_counts: *mut u32) -> c_int;
+        pub fn zh_search_graph_batch_device(idx: *mut zh_index, d_queries: *const f32, b: usize, d_seeds: *const u64, n_seed: usize, top_k: usize,
+                                            beam: usize, width: usize, max_iters: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64,
+                                            d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_search_graph_info(idx: *const zh_index, out: *mut zh_graph_search_info) -> c_int;
         pub fn zh_self_join_forest(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, out_a: *mut u64,
                                    out_b: *mut u64, out_keys: *mut u64, out_total: *mut u64) -> c_int;
         pub fn zh_self_join_forest_device(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, d_out_a: *mut u64,
@@ -998,6 +1031,79 @@ impl<const N: usize> LSHIndex<N> {
         Ok((0..stored)
             .map(|i| (t.of_row[i], (0..rcounts[i] as usize).map(|j| (t.of_row[rids[i * k + j] as usize], keys[i * k + j])).collect()))
             .collect())
+    }
+
+    /// (new) make the graph `search_graph_batch` walks and keep it on the device: the forest graph, NN-descent (knn_graph_descent's calls), then
+    /// zh_index_set_graph over every stored row.  Vectors added later are found only as seeds until the next build_graph; removed ones are
+    /// skipped at once; compact() and clear() drop the graph
+    pub fn build_graph<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        k: usize,
+        rounds: usize,
+        reverse: usize,
+        metric: &Met,
+    ) -> anyhow::Result<ffi::zh_graph_info> {
+        let t = self.ids.read().unwrap();
+        let stored = t.of_row.len();
+        let (mut ids, mut keys, mut counts) = (vec![0u64; stored * k + 1], vec![0u64; stored * k + 1], vec![0u32; stored + 1]);
+        let (mut rids, mut rcounts) = (vec![0u64; stored * k + 1], vec![0u32; stored + 1]);
+        if stored > 0 {
+            check(unsafe {
+                ffi::zh_knn_graph_forest(self.hip.0, 0, stored as u64, k, Met::METRIC, metric.param(), ids.as_mut_ptr(), keys.as_mut_ptr(),
+                                         counts.as_mut_ptr())
+            })?;
+            check(unsafe {
+                ffi::zh_knn_graph_descent(self.hip.0, ids.as_ptr(), counts.as_ptr(), k, reverse, k, rounds, Met::METRIC, metric.param(),
+                                          rids.as_mut_ptr(), keys.as_mut_ptr(), rcounts.as_mut_ptr())
+            })?;
+        }
+        check(unsafe { ffi::zh_index_set_graph(self.hip.0, rids.as_ptr(), rcounts.as_ptr(), stored as u64, k) })?;
+        self.graph_info()
+    }
+
+    /// (new) release the attached graph (zh_index_drop_graph)
+    pub fn drop_graph(&self) -> anyhow::Result<()> {
+        check(unsafe { ffi::zh_index_drop_graph(self.hip.0) })
+    }
+
+    /// (new) the attached graph (zh_index_graph_info)
+    pub fn graph_info(&self) -> anyhow::Result<ffi::zh_graph_info> {
+        let mut info = ffi::zh_graph_info::default();
+        check(unsafe { ffi::zh_index_graph_info(self.hip.0, &mut info) })?;
+        Ok(info)
+    }
+
+    /// (new) beam search over the attached graph under search_exact_batch's keys (zh_search_graph_batch): every query starts from the same n_seed
+    /// strided rows of the graph; the beam keeps the `beam` best vectors met, an iteration expands its first `width` unexpanded ones, until none
+    /// is left or max_iters (0: no cap) iterations ran.  1 <= top_k <= beam <= 256, width * k <= 256, n_seed <= 64
+    #[allow(clippy::too_many_arguments)]
+    pub fn search_graph_batch<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        queries: &[Embedding<N>],
+        top_k: usize,
+        beam: usize,
+        width: usize,
+        max_iters: usize,
+        n_seed: usize,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<Vec<(Uuid, DistanceUnit)>>> {
+        let b = queries.len();
+        let g_rows = self.graph_info()?.g_rows;
+        let seeds: Vec<u64> = (0..b * n_seed).map(|i| ((i % n_seed) as u64) * g_rows / n_seed.max(1) as u64).collect();
+        let (mut ids, mut keys, mut counts) = (vec![0u64; b * top_k + 1], vec![0u64; b * top_k + 1], vec![0u32; b + 1]);
+        check(unsafe {
+            ffi::zh_search_graph_batch(self.hip.0, queries.as_ptr() as *const f32, b, seeds.as_ptr(), n_seed, top_k, beam, width, max_iters,
+                                       Met::METRIC, metric.param(), ids.as_mut_ptr(), keys.as_mut_ptr(), counts.as_mut_ptr())
+        })?;
+        let t = self.ids.read().unwrap();
+        Ok((0..b).map(|i| (0..counts[i] as usize).map(|j| (t.of_row[ids[i * top_k + j] as usize], keys[i * top_k + j])).collect()).collect())
+    }
+
+    /// what the most recent zh_search_graph_batch call did, summed over its queries (zh_search_graph_info)
+    pub fn search_graph_info(&self) -> anyhow::Result<ffi::zh_graph_search_info> {
+        let mut info = ffi::zh_graph_search_info::default();
+        check(unsafe { ffi::zh_search_graph_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// what the most recent zh_knn_graph_descent call did, round by round (zh_knn_graph_descent_info)

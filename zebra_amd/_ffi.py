@@ -186,6 +186,24 @@ class KnnDescentInfo(C.Structure):
         return out
 
 
+class GraphInfo(C.Structure):
+    _fields_ = [("attached", C.c_uint32), ("g_k", C.c_uint32), ("g_rows", C.c_uint64), ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SearchGraphInfo(C.Structure):
+    _fields_ = [("queries", C.c_uint64), ("seeds", C.c_uint64), ("iterations", C.c_uint64), ("expanded", C.c_uint64), ("keyed", C.c_uint64),
+                ("capped", C.c_uint64), ("launches", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+GRAPH_MAX_BEAM, GRAPH_MAX_SEEDS, GRAPH_MAX_ITERS, GRAPH_BATCH = 256, 64, 65535, 16384  # ZH_GRAPH_*
+
+
 class JoinForestInfo(C.Structure):
     _fields_ = [("rows_live", C.c_uint64), ("trees", C.c_uint32), ("path", C.c_uint32), ("leaf_pairs", C.c_uint64), ("pairs", C.c_uint64),
                 ("candidates", C.c_uint64), ("launches", C.c_uint64), ("tiles", C.c_uint64), ("redone", C.c_uint32)]
@@ -293,6 +311,13 @@ SYMBOLS = [
     ("zh_knn_graph_descent", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_knn_graph_descent_device", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_knn_graph_descent_info", _i, [_vp, _vp]),
+    ("zh_index_set_graph", _i, [_vp, _vp, _vp, _u64, _sz]),
+    ("zh_index_set_graph_device", _i, [_vp, _vp, _vp, _u64, _sz, _vp]),
+    ("zh_index_drop_graph", _i, [_vp]),
+    ("zh_index_graph_info", _i, [_vp, _vp]),
+    ("zh_search_graph_batch", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp]),
+    ("zh_search_graph_batch_device", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    ("zh_search_graph_info", _i, [_vp, _vp]),
     ("zh_self_join_forest", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_device", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_info", _i, [_vp, _vp]),

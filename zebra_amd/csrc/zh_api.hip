@@ -431,6 +431,22 @@ struct zh_index {
         void mark_built(const zh_index *ix, uint64_t n) { n_live = n; at.set(ix->n_rows, ix->dead_gen); }
         void drop() { at.set(0, 0); rows.release(); bits.release(); }
     } live_dev;
+    // The k-NN graph a caller attached for graph search (zh_index_set_graph, zh_gsearch.hip): zh_launch_refine_rows' table of u32 row numbers,
+    // [g_rows][g_k], for the row numbering of the moment of the attach.  Not derived from anything the index holds: nothing re-makes it, an event
+    // that renumbers or drops the rows drops it, every other event leaves it (rows keep their numbers; the search judges liveness itself).
+    // Under mu: written exclusively, read by the search under the same lock and by zh_index_graph_info under the shared one.
+    struct GraphView {
+        DevBuf tab;
+        bool attached = false;
+        uint64_t rows = 0;
+        uint32_t k = 0;
+        void mark_attached(uint64_t g_rows, uint32_t g_k) { attached = true; rows = g_rows; k = g_k; }
+        void drop() { tab.release(); attached = false; rows = 0; k = 0; }
+    } graph;
+    // graph search's per-call scratch (all released before the call returns): the queries' squared norms, {seeds, iterations, expanded, keyed,
+    // capped}, and the host entry's staged batch: queries, seeds, ids, keys, counts
+    DevBuf gs_QQ, gs_ctr, gs_Q, gs_seeds, gs_oids, gs_okeys, gs_ocounts;
+    zh_graph_search_info gs_info{};  // (stats_mu)
     // What the index remembers of paths that did not pay on its data, and how long its forest has stood.
     struct Fallbacks {
         // Both derived views of the forest cost host time per build (a traversal of every node: ~0.35 s for the 13M nodes of a 1M-row forest at the
@@ -555,6 +571,7 @@ static void views_trees_changed(zh_index *ix) {
 // them "valid".)  LiveRowsDev is not named: dead_gen moved, so its stamp is stale, and its buffers are refilled in place.
 static void views_table_emptied(zh_index *ix) {
     ix->norms.drop();
+    ix->graph.drop();  // (its lines name rows that are gone)
     std::lock_guard<std::mutex> lb(ix->blk_mu);  // (the fp16 copies' state is blk_mu's: zh_stats reads it under that lock)
     ix->half.drop();
     ix->order.drop();
@@ -569,6 +586,7 @@ static void views_table_emptied(zh_index *ix) {
 static uint64_t views_rows_moved(zh_index *ix, bool lost_sample) {
     ix->live_host.drop();
     ix->live_dev.drop();  // (the buffers too: they were sized by the old row count; re-made by the next exact search)
+    ix->graph.drop();     // (its lines hold the old row numbers: the caller attaches a graph of the new ones)
     ix->norms.drop();
     ix->plane_norms.forget();
     if (lost_sample) ix->samples.mark(false);  // (no row scores for that plane's sign until the forest is rebuilt)
@@ -726,6 +744,7 @@ extern "C" void zh_index_destroy(zh_index *ix) {
     free_forest(ix);
     ix->X.release();
     ix->norms.drop(); ix->half.drop(); ix->half.rho_dev.release(); ix->half128.drop(); ix->order.drop(); ix->live_dev.drop();
+    ix->graph.drop();
     ix->dctx.release_all();
     DevBuf *ws[] = {&ix->wQ, &ix->wOutIds, &ix->wOutKeys, &ix->wOutCounts};
     release_scratch(ix, ~0u);  // every family's
@@ -3569,7 +3588,7 @@ static int score_param(int metric, int mode) { return (metric == ZH_COSINE || me
 // index holds only the live-row views (live_dev's list and bitmap survive every call; zh_index_destroy frees them).  Every family scans with the exact
 // search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's, the forest range search with
 // the range search's and the forest join's, the cross-join (all on its LEFT index) with the join's and its own views.
-enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024, SCR_ND = 2048 };  // one bit per list
+enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024, SCR_ND = 2048, SCR_GS = 4096 };  // one bit per list
 enum : unsigned {
     SCRATCH_EXACT = SCR_EX,
     SCRATCH_FILTER = SCR_FL | SCRATCH_EXACT,
@@ -3580,6 +3599,8 @@ enum : unsigned {
     SCRATCH_REFINE = SCR_RF | SCRATCH_KNN,
     SCRATCH_REVERSE = SCR_RV | SCRATCH_REFINE,
     SCRATCH_DESCENT = SCR_ND | SCRATCH_REVERSE,
+    SCRATCH_GRAPH_ATTACH = SCR_RF,  // (the host entry's counts and staged chunk of ids)
+    SCRATCH_GSEARCH = SCR_GS,
     SCRATCH_FJOIN = SCR_FJ | SCRATCH_JOIN | SCRATCH_FKNN,
     SCRATCH_FRANGE = SCR_FR | SCRATCH_RANGE | SCRATCH_FJOIN,
     SCRATCH_XJOIN = SCR_XJ | SCRATCH_JOIN,  // (on the left index)
@@ -3608,6 +3629,7 @@ static void release_scratch(zh_index *ix, unsigned families) {
                   &ix->rv_odeg});
     drop(SCR_ND, {&ix->nd_tab[0], &ix->nd_tab[1], &ix->nd_key[0], &ix->nd_key[1], &ix->nd_uni[0], &ix->nd_uni[1], &ix->nd_mask, &ix->nd_list, &ix->nd_qq,
                   &ix->nd_ctr});
+    drop(SCR_GS, {&ix->gs_QQ, &ix->gs_ctr, &ix->gs_Q, &ix->gs_seeds, &ix->gs_oids, &ix->gs_okeys, &ix->gs_ocounts});
     drop(SCR_FJ, {&ix->fj_leafof, &ix->fj_pieces, &ix->fj_linel, &ix->fj_linek, &ix->fj_segs, &ix->fj_cand});
     drop(SCR_FR, {&ix->fr_counts, &ix->fr_inline, &ix->fr_rowbase, &ix->fr_candbase, &ix->fr_visitbase, &ix->fr_totals, &ix->fr_leafcount, &ix->fr_leaffill,
                   &ix->fr_groupbase, &ix->fr_grouprowbase, &ix->fr_loghead, &ix->fr_logctl, &ix->fr_logpool, &ix->fr_visits, &ix->fr_groups, &ix->fr_groupoff,
@@ -5376,15 +5398,20 @@ struct RefinePins {  // two pinned buffers and an event each: released whatever 
 
 // The caller's graph -> rf_tab, the table of row numbers (zh_launch_refine_rows), once per call.  host: in_ids / in_counts are HOST arrays -- the ids
 // go chunk by chunk (whole lines) through two pinned buffers and one device chunk, never as a whole u64 copy on the device.
-static int refine_table(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, bool host, hipStream_t s) {
-    const uint64_t N = ix->n_rows, id_base = ix->opt.id_base;
+// dst (zh_index_set_graph): the first `lines` lines only, into that table instead of rf_tab; entries are still judged against all stored rows.
+static int refine_table(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, bool host, hipStream_t s, uint32_t *dst = nullptr,
+                        uint64_t lines = 0) {
+    const uint64_t stored = ix->n_rows, N = dst ? lines : stored, id_base = ix->opt.id_base;
     int rc;
-    if ((rc = ix->rf_tab.ensure(std::max<size_t>((size_t)N * in_k * 4, 4))) || (rc = ix->rf_ctr.ensure(24))) return rc;
-    HIPCHK(hipMemsetAsync(ix->rf_ctr.p, 0, 24, s));
+    if (!dst) {
+        if ((rc = ix->rf_tab.ensure(std::max<size_t>((size_t)N * in_k * 4, 4))) || (rc = ix->rf_ctr.ensure(24))) return rc;
+        HIPCHK(hipMemsetAsync(ix->rf_ctr.p, 0, 24, s));
+        dst = ix->rf_tab.as<uint32_t>();
+    }
     if (!N) return ZH_OK;
     const uint32_t *dBits = ix->live_dev.bits.as<uint32_t>();
     if (!host) {
-        HIPCHK(zh_launch_refine_rows(in_ids, in_counts, dBits, id_base, N, in_k, 0, N, ix->rf_tab.as<uint32_t>(), s));
+        HIPCHK(zh_launch_refine_rows(in_ids, in_counts, dBits, id_base, stored, in_k, 0, N, dst, s));
         return ZH_OK;
     }
     const uint64_t line_bytes = (uint64_t)in_k * 8, chunk_lines = std::min<uint64_t>(N, std::max<uint64_t>(1, refine_chunk_bytes() / line_bytes));
@@ -5405,7 +5432,7 @@ static int refine_table(zh_index *ix, const uint64_t *in_ids, const uint32_t *in
         memcpy(pp.pin[b], in_ids + l0 * in_k, nl * line_bytes);
         HIPCHK(hipMemcpyAsync(ix->rf_stage.p, pp.pin[b], nl * line_bytes, hipMemcpyHostToDevice, s));  // (behind the kernel that read the chunk before)
         HIPCHK(hipEventRecord(pp.ev[b], s));
-        HIPCHK(zh_launch_refine_rows(ix->rf_stage.as<uint64_t>(), ix->rf_cnt.as<uint32_t>(), dBits, id_base, N, in_k, l0, nl, ix->rf_tab.as<uint32_t>(), s));
+        HIPCHK(zh_launch_refine_rows(ix->rf_stage.as<uint64_t>(), ix->rf_cnt.as<uint32_t>(), dBits, id_base, stored, in_k, l0, nl, dst, s));
     }
     return ZH_OK;
 }
@@ -5769,6 +5796,160 @@ extern "C" int zh_knn_graph_descent(zh_index *ix, const uint64_t *in_ids, const 
 
 extern "C" int zh_knn_graph_descent_info(const zh_index *ix, zh_knn_descent_info *out) {
     return get_info(ix, &zh_index::nd_info, out, "zh_knn_graph_descent_info");
+}
+
+// ------------------------------------------------------------------------------------------------
+// graph search (zh_gsearch.hip): a k-NN graph kept on the index (GraphView) and the beam search over it.  DESIGN.md s24
+// ------------------------------------------------------------------------------------------------
+// both attach entry points.  Judged before any device is touched: null index, null arrays of a non-empty graph, g_k = 0, g_k's limit; under the
+// lock: g_rows against the stored rows, the table against 2^31 rows.  The new table is made beside the old one: a failure leaves what was attached.
+static int graph_attach(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint64_t g_rows, size_t g_k, bool host, void *stream, const char *who) {
+    if (!ix || (g_rows && (!in_ids || !in_counts))) return fail(ZH_EINVAL, "%s: null argument", who);
+    if (!g_k) return fail(ZH_EINVAL, "%s: g_k is 0", who);
+    if (g_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: g_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, g_k, ZH_REFINE_MAX_IN_K);
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix))) return rc;
+    if (g_rows > ix->n_rows) return fail(ZH_EINVAL, "%s: g_rows %llu > the %llu stored rows", who, (unsigned long long)g_rows, (unsigned long long)ix->n_rows);
+    if (ix->n_rows >= (1ull << 31)) return fail(ZH_ELIMIT, "%s: %llu stored rows; graph search serves tables below 2^31 rows", who, (unsigned long long)ix->n_rows);
+    ScratchGuard guard{ix, SCRATCH_GRAPH_ATTACH};
+    const hipStream_t s = call_stream(ix, stream);
+    DevBuf tab;
+    if ((rc = tab.ensure(std::max<size_t>((size_t)g_rows * g_k * 4, 4)))) return rc;
+    rc = refine_table(ix, in_ids, in_counts, (uint32_t)g_k, host, s, tab.as<uint32_t>(), g_rows);
+    if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = fail(ZH_EHIP, "%s: the table of row numbers failed", who);
+    if (rc) { tab.release(); return rc; }
+    ix->graph.drop();
+    ix->graph.tab = tab;
+    ix->graph.mark_attached(g_rows, (uint32_t)g_k);
+    return ZH_OK;
+}
+
+extern "C" int zh_index_set_graph(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint64_t g_rows, size_t g_k) {
+    return graph_attach(ix, in_ids, in_counts, g_rows, g_k, true, nullptr, "zh_index_set_graph");
+}
+
+extern "C" int zh_index_set_graph_device(zh_index *ix, const uint64_t *d_in_ids, const uint32_t *d_in_counts, uint64_t g_rows, size_t g_k, void *stream) {
+    return graph_attach(ix, d_in_ids, d_in_counts, g_rows, g_k, false, stream, "zh_index_set_graph_device");
+}
+
+extern "C" int zh_index_drop_graph(zh_index *ix) {
+    if (!ix) return fail(ZH_EINVAL, "zh_index_drop_graph: null argument");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc = set_device(ix);
+    if (rc) return rc;
+    if (ix->graph.attached) HIPCHK(hipDeviceSynchronize());  // (nothing of an earlier call on a caller's stream is left reading the table)
+    ix->graph.drop();
+    return ZH_OK;
+}
+
+extern "C" int zh_index_graph_info(const zh_index *ix, zh_graph_info *out) {
+    if (!ix || !out) return fail(ZH_EINVAL, "zh_index_graph_info: null argument");
+    zh_index *m = const_cast<zh_index *>(ix);
+    std::shared_lock<std::shared_mutex> lk(m->mu);
+    zh_graph_info g{};
+    g.attached = m->graph.attached ? 1u : 0u;
+    g.g_k = m->graph.k;
+    g.g_rows = m->graph.rows;
+    g.bytes = m->graph.attached ? m->graph.tab.cap : 0;
+    *out = g;
+    return ZH_OK;
+}
+
+// judged before any device is touched, in this order of kinds: null index (even for b = 0), null pointers of a non-empty request, the metric, a zero
+// top_k / beam / width / n_seed, then the limits: beam, top_k against beam, n_seed, width (against 256: g_k is only known under the lock), max_iters
+static int gsearch_args(zh_index *ix, const void *q, size_t b, const void *seeds, size_t n_seed, size_t top_k, size_t beam, size_t width, size_t max_iters,
+                        int metric, int mode, const void *ids, const void *keys, const void *counts, const char *who) {
+    if (!ix || (b && (!q || !seeds || !ids || !keys || !counts))) return fail(ZH_EINVAL, "%s: null argument", who);
+    const int rc = check_metric(metric, mode);
+    if (rc) return rc;
+    if (!top_k) return fail(ZH_EINVAL, "%s: top_k is 0", who);
+    if (!beam) return fail(ZH_EINVAL, "%s: beam is 0", who);
+    if (!width) return fail(ZH_EINVAL, "%s: width is 0", who);
+    if (!n_seed) return fail(ZH_EINVAL, "%s: n_seed is 0", who);
+    if (beam > ZH_GRAPH_MAX_BEAM) return fail(ZH_ELIMIT, "%s: beam %zu > ZH_GRAPH_MAX_BEAM (%u)", who, beam, ZH_GRAPH_MAX_BEAM);
+    if (top_k > beam) return fail(ZH_ELIMIT, "%s: top_k %zu > beam %zu", who, top_k, beam);
+    if (n_seed > ZH_GRAPH_MAX_SEEDS) return fail(ZH_ELIMIT, "%s: n_seed %zu > ZH_GRAPH_MAX_SEEDS (%u)", who, n_seed, ZH_GRAPH_MAX_SEEDS);
+    if (width > 256) return fail(ZH_ELIMIT, "%s: width %zu > 256", who, width);
+    if (max_iters > ZH_GRAPH_MAX_ITERS) return fail(ZH_ELIMIT, "%s: max_iters %zu > ZH_GRAPH_MAX_ITERS (%u)", who, max_iters, ZH_GRAPH_MAX_ITERS);
+    return ZH_OK;
+}
+
+// both entry points once the arguments have been judged (b > 0).  host: q, seeds and the outputs are HOST arrays -- each internal batch goes through
+// the staging and is waited for; otherwise they are device arrays, waited for once after the last batch.
+static int gsearch_call(zh_index *ix, const float *q, size_t b, const uint64_t *seeds, uint32_t n_seed, uint32_t top_k, uint32_t beam, uint32_t width,
+                        uint32_t max_iters, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, bool host, void *stream,
+                        const char *who) {
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix))) return rc;
+    if (!ix->graph.attached) return fail(ZH_ESTATE, "%s: no graph is attached to the index (zh_index_set_graph)", who);
+    const uint32_t g_k = ix->graph.k, d = ix->opt.dim;
+    if ((uint64_t)width * g_k > 256) return fail(ZH_ELIMIT, "%s: width %u * g_k %u > 256", who, width, g_k);
+    if (ix->n_rows >= (1ull << 31)) return fail(ZH_ELIMIT, "%s: %llu stored rows; graph search serves tables below 2^31 rows", who, (unsigned long long)ix->n_rows);
+    if ((rc = exact_live_rows(ix))) return rc;
+    ScratchGuard guard{ix, SCRATCH_GSEARCH};
+    const hipStream_t s = call_stream(ix, stream);
+    const size_t nb_max = std::min<size_t>(ZH_GRAPH_BATCH, b);
+    if ((rc = ix->gs_QQ.ensure(nb_max * 4)) || (rc = ix->gs_ctr.ensure(40))) return rc;
+    if (host && ((rc = ix->gs_Q.ensure(nb_max * d * 4)) || (rc = ix->gs_seeds.ensure(nb_max * n_seed * 8)) || (rc = ix->gs_oids.ensure(nb_max * top_k * 8)) ||
+                 (rc = ix->gs_okeys.ensure(nb_max * top_k * 8)) || (rc = ix->gs_ocounts.ensure(nb_max * 4))))
+        return rc;
+    HIPCHK(hipMemsetAsync(ix->gs_ctr.p, 0, 40, s));
+    zh_graph_search_info inf{};
+    for (size_t b0 = 0; b0 < b; b0 += ZH_GRAPH_BATCH) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(ZH_GRAPH_BATCH, b - b0);
+        const float *dQ = q + b0 * d;
+        const uint64_t *dSeeds = seeds + b0 * n_seed;
+        uint64_t *dIds = out_ids + b0 * top_k, *dKeys = out_keys + b0 * top_k;
+        uint32_t *dCounts = out_counts + b0;
+        if (host) {
+            HIPCHK(hipMemcpyAsync(ix->gs_Q.p, dQ, (size_t)nb * d * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(ix->gs_seeds.p, dSeeds, (size_t)nb * n_seed * 8, hipMemcpyHostToDevice, s));
+            dQ = ix->gs_Q.as<float>(); dSeeds = ix->gs_seeds.as<uint64_t>();
+            dIds = ix->gs_oids.as<uint64_t>(); dKeys = ix->gs_okeys.as<uint64_t>(); dCounts = ix->gs_ocounts.as<uint32_t>();
+        }
+        if (metric == ZH_COSINE) HIPCHK(zh_launch_qnorm(dQ, nb, d, ix->gs_QQ.as<float>(), s));  // (the exact search's norm of the query)
+        HIPCHK(zh_launch_gsearch(ix->X.as<float>(), d, ix->n_rows, ix->graph.tab.as<uint32_t>(), ix->graph.rows, g_k, ix->live_dev.bits.as<uint32_t>(), dQ,
+                                 ix->gs_QQ.as<float>(), dSeeds, n_seed, nb, ix->opt.id_base, top_k, beam, width, max_iters, metric, score_param(metric, mode), dIds,
+                                 dKeys, dCounts, ix->gs_ctr.as<unsigned long long>(), s));
+        inf.launches++;
+        if (host) {
+            HIPCHK(hipMemcpyAsync(out_ids + b0 * top_k, dIds, (size_t)nb * top_k * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_keys + b0 * top_k, dKeys, (size_t)nb * top_k * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_counts + b0, dCounts, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+    }
+    unsigned long long ctr[5] = {0, 0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(ctr, ix->gs_ctr.p, 40, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    inf.queries = b;
+    inf.seeds = ctr[0]; inf.iterations = ctr[1]; inf.expanded = ctr[2]; inf.keyed = ctr[3]; inf.capped = ctr[4];
+    std::lock_guard<std::mutex> ls(ix->stats_mu);
+    ix->gs_info = inf;
+    return ZH_OK;
+}
+
+extern "C" int zh_search_graph_batch_device(zh_index *ix, const float *d_q, size_t b, const uint64_t *d_seeds, size_t n_seed, size_t top_k, size_t beam,
+                                            size_t width, size_t max_iters, int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys,
+                                            uint32_t *d_out_counts, void *stream) {
+    int rc = gsearch_args(ix, d_q, b, d_seeds, n_seed, top_k, beam, width, max_iters, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_search_graph_batch_device");
+    if (rc || b == 0) return rc;
+    return gsearch_call(ix, d_q, b, d_seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, d_out_ids,
+                        d_out_keys, d_out_counts, false, stream, "zh_search_graph_batch_device");
+}
+
+extern "C" int zh_search_graph_batch(zh_index *ix, const float *q, size_t b, const uint64_t *seeds, size_t n_seed, size_t top_k, size_t beam, size_t width,
+                                     size_t max_iters, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts) {
+    int rc = gsearch_args(ix, q, b, seeds, n_seed, top_k, beam, width, max_iters, metric, mode, out_ids, out_keys, out_counts, "zh_search_graph_batch");
+    if (rc || b == 0) return rc;
+    return gsearch_call(ix, q, b, seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, out_ids, out_keys,
+                        out_counts, true, nullptr, "zh_search_graph_batch");
+}
+
+extern "C" int zh_search_graph_info(const zh_index *ix, zh_graph_search_info *out) {
+    return get_info(ix, &zh_index::gs_info, out, "zh_search_graph_info");
 }
 
 // judged before any device is touched, in this order of kinds: null index (even for n = 0), null inputs or outputs of a non-empty request, the two

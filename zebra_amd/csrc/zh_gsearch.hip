@@ -1,0 +1,244 @@
+// zh_gsearch.hip -- graph search (zh_search_graph_batch, driver in zh_api.hip): a best-first walk over the k-NN graph an index keeps
+// (zh_index_set_graph: zh_launch_refine_rows' table of u32 row numbers, [g_rows][g_k], UINT32_MAX for a masked entry).  Per query:
+//   the beam B = the first `beam` of the query's valid seeds by (key, id), every entry unexpanded; then, while B has an unexpanded entry (and the
+//   iteration cap is not reached): P = its first `width` unexpanded entries, marked expanded; cand = the live rows their lines name, each once,
+//   minus the rows in B now; B = the first `beam` of B union cand by (key, id).  The answer is the first top_k of B.
+// Keys, ids, tails and counts as zh_exact.hip: what is approximate is the set of rows that get a key, never the arithmetic.  DESIGN.md s24.
+//
+//   gsearch_kernel   a 256-thread block per query, nothing per candidate leaves the block.  The query sits in registers (load_row's lane layout; the
+//                    generic kernel reads it from memory), the beam in LDS: slots [0, 256) hold B sorted by (key, row), the id word is row << 1 |
+//                    expanded; slots [256, 512) hold an iteration's candidates.  An iteration: (1) a ballot / prefix pass over the beam's flags picks
+//                    P; (2) thread e reads entry e % g_k of parent e / g_k's line and tests it against the live bitmap; (3) it is dropped if an
+//                    EARLIER parent's line holds it (a line holds no row twice: zh_launch_refine_rows) or the beam does -- a broadcast scan of the
+//                    beam's id words, every lane reading the same LDS address; (4) the survivors are compacted; (5) the four waves key them,
+//                    ZH_REFINE_INFLIGHT rows in flight per wave (refine_line_kernel's step (b), refine_key's arithmetic); (6) every beam entry
+//                    and every candidate finds its place in the union by counting: the candidates below it (one broadcast pass over the at most
+//                    256 of them) plus, for a candidate, the beam entries below it (a binary search of the sorted beam) -- all (key, row) pairs are
+//                    distinct, so the counts are a permutation; what lands below `beam` is written there.  No sort: eight barriers an iteration.
+#include "zh_refine_dev.h"  // refine_key, RF_NONE, ZH_REFINE_INFLIGHT: the key of a gathered row against a row held in registers
+
+#define GS_SLOTS ZH_GRAPH_MAX_BEAM  // beam slots, and candidate slots behind them (width * g_k <= 256, seeds <= 64)
+static_assert(GS_SLOTS == 256, "one thread per beam slot and per candidate slot");
+
+// (key, row) below (key, row)
+__device__ __forceinline__ bool gs_less(uint64_t ka, uint32_t ra, uint64_t kb, uint32_t rb) { return ka < kb || (ka == kb && ra < rb); }
+
+template <int D, int KIND>
+__global__ __launch_bounds__(256) void gsearch_kernel(const float *__restrict__ X, uint32_t d, uint64_t n_rows, const uint32_t *__restrict__ tab, uint64_t g_rows,
+                                                      uint32_t g_k, const uint32_t *__restrict__ bits, const float *__restrict__ Q, const float *__restrict__ QQ,
+                                                      const uint64_t *__restrict__ seeds, uint32_t n_seed, uint64_t id_base, uint32_t top_k, uint32_t beam,
+                                                      uint32_t width, uint32_t max_iters, int metric, int param, uint64_t *__restrict__ out_ids,
+                                                      uint64_t *__restrict__ out_keys, uint32_t *__restrict__ out_counts, unsigned long long *__restrict__ ctr) {
+    constexpr int R = ZH_REFINE_INFLIGHT;
+    __shared__ uint64_t s_key[2 * GS_SLOTS];
+    __shared__ uint32_t s_id[2 * GS_SLOTS];
+    __shared__ uint32_t s_raw[GS_SLOTS], s_par[GS_SLOTS], s_wc[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const size_t b = blockIdx.x;
+    const float *q = Q + b * d;
+    const float qq = KIND == K_COS ? QQ[b] : 0.f;
+    float4 qreg[D > 0 ? RowVec<(D > 0 ? D : 256)>::NV : 1];
+    if constexpr (D > 0) load_row<D>(q, lane, qreg);
+    uint64_t *ckey = s_key + GS_SLOTS;
+    uint32_t *cid = s_id + GS_SLOTS;
+    uint32_t nb = 0;  // |B| (block-uniform)
+    uint32_t n_seeds = 0, n_iter = 0, n_exp = 0, n_keyed = 0, capped = 0;
+
+    // thread tid's candidate row v (RF_NONE: none) joins the beam: steps (4) to (6).  -> the candidates keyed.  (Every thread calls it.)
+    auto absorb = [&](uint32_t v) -> uint32_t {
+        // (4) compaction: a wave's survivors by ballot, the waves' counts through LDS
+        const unsigned long long m = __ballot(v != RF_NONE);
+        if (lane == 0) s_wc[wv] = (uint32_t)__popcll(m);
+        __syncthreads();
+        const uint32_t c0 = s_wc[0], c1 = s_wc[1], c2 = s_wc[2], c3 = s_wc[3];
+        const uint32_t U = (c0 + c1) + (c2 + c3);
+        if (v != RF_NONE) cid[(wv > 0 ? c0 : 0u) + (wv > 1 ? c1 : 0u) + (wv > 2 ? c2 : 0u) + (uint32_t)__popcll(m & ((1ull << lane) - 1))] = v << 1;
+        __syncthreads();
+        if (!U) return 0;  // (block-uniform)
+        // (5) the keys: wave wv takes candidates 4 R t + 4 c + wv, c < R at a time
+        if constexpr (D > 0) {
+            constexpr int NV = RowVec<D>::NV;
+            for (uint32_t i0 = wv; i0 < U; i0 += 4 * R) {
+                float4 x[R][NV];
+#pragma unroll
+                for (int c = 0; c < R; c++) {
+                    const uint32_t i = i0 + 4 * c < U ? i0 + 4 * c : U - 1;  // (a slot past the list loads the last row again: straight-line loads)
+                    load_row<D>(X + (size_t)((uint32_t)__builtin_amdgcn_readfirstlane((int)cid[i]) >> 1) * D, lane, x[c]);
+                }
+#pragma unroll
+                for (int c = 0; c < R; c++) {
+                    const uint64_t key = refine_key<D, KIND>(x[c], nullptr, q, qreg, qq, d, lane, metric, param);
+                    if (lane == 0 && i0 + 4 * c < U) ckey[i0 + 4 * c] = key;
+                }
+            }
+        } else {
+            for (uint32_t i = wv; i < U; i += 4) {
+                const uint64_t key = refine_key<0, KIND>(nullptr, X + (size_t)(cid[i] >> 1) * d, q, nullptr, qq, d, lane, metric, param);
+                if (lane == 0) ckey[i] = key;
+            }
+        }
+        __syncthreads();
+        // (6) places in the union: beam entry tid and candidate tid each count what lies below them
+        const bool hb = tid < nb, hc = tid < U;
+        const uint64_t kb = hb ? s_key[tid] : 0, kc = hc ? ckey[tid] : 0;
+        const uint32_t ib = hb ? s_id[tid] : 0, ic = hc ? cid[tid] : 0;
+        uint32_t pb = tid, pc = 0;
+        for (uint32_t j = 0; j < U; j++) {  // (every lane reads the same words: LDS broadcasts)
+            const uint64_t kj = ckey[j];
+            const uint32_t rj = cid[j] >> 1;
+            pb += gs_less(kj, rj, kb, ib >> 1) ? 1u : 0u;
+            pc += gs_less(kj, rj, kc, ic >> 1) ? 1u : 0u;
+        }
+        if (hc) {  // the beam entries below the candidate: the first of the sorted beam that is not
+            uint32_t lo = 0, hi = nb;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (gs_less(s_key[mid], s_id[mid] >> 1, kc, ic >> 1)) lo = mid + 1;
+                else hi = mid;
+            }
+            pc += lo;
+        }
+        __syncthreads();  // (the beam is read: its slots are written next)
+        if (hb && pb < beam) { s_key[pb] = kb; s_id[pb] = ib; }
+        if (hc && pc < beam) { s_key[pc] = kc; s_id[pc] = ic; }
+        nb = nb + U < beam ? nb + U : beam;
+        __syncthreads();
+        return U;
+    };
+
+    // ---- the seeds: S(q) = the live stored rows they name, each once
+    {
+        uint32_t v = RF_NONE;
+        if (tid < n_seed) {
+            const uint64_t r = seeds[b * n_seed + tid] - id_base;  // (an id below id_base wraps past every row number)
+            if (r < n_rows && ((bits[r >> 5] >> (r & 31)) & 1u)) v = (uint32_t)r;
+        }
+        s_raw[tid] = v;
+        __syncthreads();
+        if (v != RF_NONE)
+            for (uint32_t j = 0; j < tid; j++)
+                if (s_raw[j] == v) { v = RF_NONE; break; }
+        n_seeds = absorb(v);
+        n_keyed = n_seeds;
+    }
+    // ---- the iterations
+    for (; n_iter <= n_rows; n_iter++) {  // (a row is expanded at most once, DESIGN.md s24: the bound is never the reason the loop ends)
+        // (1) P: the first `width` unexpanded entries of the sorted beam
+        const bool un = tid < nb && !(s_id[tid] & 1u);
+        const unsigned long long m = __ballot(un);
+        if (lane == 0) s_wc[wv] = (uint32_t)__popcll(m);
+        __syncthreads();
+        const uint32_t c0 = s_wc[0], c1 = s_wc[1], c2 = s_wc[2], c3 = s_wc[3];
+        const uint32_t left = (c0 + c1) + (c2 + c3);
+        if (!left) break;  // (block-uniform)
+        if (max_iters && n_iter == max_iters) { capped = 1; break; }
+        const uint32_t rank = (wv > 0 ? c0 : 0u) + (wv > 1 ? c1 : 0u) + (wv > 2 ? c2 : 0u) + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+        if (un && rank < width) {
+            s_par[rank] = s_id[tid] >> 1;
+            s_id[tid] |= 1u;
+        }
+        const uint32_t np = left < width ? left : width;
+        __syncthreads();
+        n_exp += np;
+        // (2) the parents' lines: thread e holds entry e % g_k of parent e / g_k (np * g_k <= 256: the host's check)
+        uint32_t v = RF_NONE;
+        const uint32_t pe = tid / g_k;
+        if (pe < np) {
+            const uint32_t p = s_par[pe];
+            if (p < g_rows) v = tab[(size_t)p * g_k + (tid - pe * g_k)];  // (a row appended since the attach has an empty line)
+            if (v != RF_NONE && !((bits[v >> 5] >> (v & 31)) & 1u)) v = RF_NONE;  // (removed since the attach)
+        }
+        s_raw[tid] = v;
+        __syncthreads();
+        // (3) once each, and not in the beam
+        if (v != RF_NONE) {
+            const uint32_t before = pe * g_k;  // (the entries of earlier parents' lines)
+            for (uint32_t j = 0; j < before; j++)
+                if (s_raw[j] == v) { v = RF_NONE; break; }
+        }
+        {
+            bool in_beam = false;
+            for (uint32_t j = 0; j < nb; j++) in_beam = in_beam || (s_id[j] >> 1) == v;  // (broadcast reads; v = RF_NONE matches no row below 2^31)
+            if (in_beam) v = RF_NONE;
+        }
+        n_keyed += absorb(v);  // (its first barrier closes the reads of the beam's id words)
+    }
+    // ---- the answer: the first top_k of B
+    const uint32_t have = nb < top_k ? nb : top_k;
+    for (uint32_t i = tid; i < top_k; i += 256) {
+        out_ids[b * top_k + i] = i < have ? id_base + (s_id[i] >> 1) : ~0ull;
+        out_keys[b * top_k + i] = i < have ? s_key[i] : ~0ull;
+    }
+    if (tid == 0) {
+        out_counts[b] = have;
+        if (n_seeds) atomicAdd(&ctr[0], (unsigned long long)n_seeds);
+        if (n_iter) atomicAdd(&ctr[1], (unsigned long long)n_iter);
+        if (n_exp) atomicAdd(&ctr[2], (unsigned long long)n_exp);
+        if (n_keyed) atomicAdd(&ctr[3], (unsigned long long)n_keyed);
+        if (capped) atomicAdd(&ctr[4], 1ull);
+    }
+}
+
+#define GS_ARGS_DECL \
+    const float *dX, uint32_t d, uint64_t n_rows, const uint32_t *dTab, uint64_t g_rows, uint32_t g_k, const uint32_t *dBits, const float *dQ, const float *dQQ, \
+    const uint64_t *dSeeds, uint32_t n_seed, uint32_t B, uint64_t id_base, uint32_t top_k, uint32_t beam, uint32_t width, uint32_t max_iters, int metric, \
+    int param, uint64_t *dOutIds, uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s
+
+template <int D, int KIND>
+static hipError_t launch_gsearch_d(GS_ARGS_DECL) {
+    hipLaunchKernelGGL((gsearch_kernel<D, KIND>), dim3(B), dim3(256), 0, s, dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ, dSeeds, n_seed, id_base, top_k, beam,
+                       width, max_iters, metric, param, dOutIds, dOutKeys, dOutCounts, dCtr);
+    return hipGetLastError();
+}
+
+// the dimensions zh_launch_refine_lines specialises: 128 / 384 / 768 for every kind, 256 / 512 / 1024 as well for the two simsimd kinds
+template <int KIND>
+static hipError_t launch_gsearch_kind(GS_ARGS_DECL) {
+#define ZH_GS_CASE(DD) \
+    case DD: \
+        return launch_gsearch_d<DD, KIND>(dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ, dSeeds, n_seed, B, id_base, top_k, beam, width, max_iters, metric, param, \
+                                          dOutIds, dOutKeys, dOutCounts, dCtr, s)
+    if constexpr (KIND == K_L2 || KIND == K_COS) {
+        switch (d) {
+            ZH_GS_CASE(256);
+            ZH_GS_CASE(512);
+            ZH_GS_CASE(1024);
+        default: break;
+        }
+    }
+    switch (d) {
+        ZH_GS_CASE(128);
+        ZH_GS_CASE(384);
+        ZH_GS_CASE(768);
+    default: break;
+    }
+#undef ZH_GS_CASE
+    return launch_gsearch_d<0, KIND>(dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ, dSeeds, n_seed, B, id_base, top_k, beam, width, max_iters, metric, param,
+                                     dOutIds, dOutKeys, dOutCounts, dCtr, s);
+}
+
+hipError_t zh_launch_gsearch(GS_ARGS_DECL) {
+    if (!B) return hipSuccess;
+    if (!g_k || g_k > ZH_REFINE_MAX_IN_K || !width || (uint64_t)width * g_k > GS_SLOTS || !n_seed || n_seed > ZH_GRAPH_MAX_SEEDS || !top_k || top_k > beam ||
+        beam > ZH_GRAPH_MAX_BEAM || n_rows >= (1ull << 31))
+        return hipErrorInvalidValue;
+#define ZH_GS_KIND(K) \
+    case K: \
+        return launch_gsearch_kind<K>(dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ, dSeeds, n_seed, B, id_base, top_k, beam, width, max_iters, metric, param, \
+                                      dOutIds, dOutKeys, dOutCounts, dCtr, s)
+    switch (zh_kind_of(metric)) {
+        ZH_GS_KIND(K_COS);
+        ZH_GS_KIND(K_MAX);
+        ZH_GS_KIND(K_CANB);
+        ZH_GS_KIND(K_BRAY);
+        ZH_GS_KIND(K_ABS);
+        ZH_GS_KIND(K_P3);
+        ZH_GS_KIND(K_P4);
+        ZH_GS_KIND(K_HAMM);
+        ZH_GS_KIND(K_PP);
+    default:
+        return launch_gsearch_kind<K_L2>(dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ, dSeeds, n_seed, B, id_base, top_k, beam, width, max_iters, metric, param,
+                                         dOutIds, dOutKeys, dOutCounts, dCtr, s);
+    }
+#undef ZH_GS_KIND
+}

@@ -534,6 +534,14 @@ hipError_t zh_launch_nnd_lines(const float *dX, uint32_t d, const uint32_t *dU, 
                                const uint32_t *dList, uint64_t n_live, int metric, int param, uint32_t *dTabNext, uint64_t *dKeysNext, unsigned long long *dCtr,
                                hipStream_t s);
 
+// ---- graph search (zh_gsearch.hip): beam search over the index's attached graph, dTab = zh_launch_refine_rows' table [g_rows][g_k].  A block per
+// query: seeds [B][n_seed] ids, the first top_k of the final beam to the outputs (zh_search_exact_batch's layout); dCtr[0..4] += valid seeds,
+// iterations, expanded, keyed, capped queries.  n_rows < 2^31, width * g_k <= 256
+hipError_t zh_launch_gsearch(const float *dX, uint32_t d, uint64_t n_rows, const uint32_t *dTab, uint64_t g_rows, uint32_t g_k, const uint32_t *dBits,
+                             const float *dQ, const float *dQQ, const uint64_t *dSeeds, uint32_t n_seed, uint32_t B, uint64_t id_base, uint32_t top_k,
+                             uint32_t beam, uint32_t width, uint32_t max_iters, int metric, int param, uint64_t *dOutIds, uint64_t *dOutKeys,
+                             uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s);
+
 // ---- the forest self-join (zh_fjoin.hip): every pair of leaf-mates whose key is <= one threshold key, each pair once (the first tree that puts
 // the two rows together owns it).  Hit pool, counter and order as the exact self-join's
 #define ZH_FJOIN_PANEL_LINES 16384u  // path 1: lines of one panel at most

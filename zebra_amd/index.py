@@ -743,6 +743,87 @@ class LSHIndex:
         lists keyed_round, updates_round and active_round"""
         return self._info(_ffi.KnnDescentInfo, lib().zh_knn_graph_descent_info)
 
+    def set_graph(self, graph, rows=None):
+        """attach a k-NN graph for search_graph_batch (zh_index_set_graph): `graph` is (ids [g_rows, g_k] u64, counts [g_rows] u32) or the 3-tuple
+        a graph call returns (its keys are not read), over the first g_rows = `rows` stored rows (default: as many as the arrays hold; at most
+        stored_rows()), ids in the id space id_base + row.  Entries past a line's count, out of range, removed or repeated in their line are
+        ignored.  The index keeps the graph on the device (4 g_rows g_k bytes) through append, add, remove, deduplicate, build and set_forest;
+        a second set_graph replaces it; compact() (once it moves rows) and clear() drop it, and a snapshot never holds it."""
+        in_ids = np.ascontiguousarray(graph[0], np.uint64)
+        in_counts = np.ascontiguousarray(graph[-1], np.uint32)
+        if in_ids.ndim != 2 or in_counts.ndim != 1:
+            raise _ffi.ZhError(_ffi.ZH_EINVAL, "set_graph: the graph is ids [g_rows, g_k] and counts [g_rows]")
+        g_rows = in_ids.shape[0] if rows is None else int(rows)
+        if g_rows < 0 or g_rows > in_ids.shape[0] or g_rows > in_counts.shape[0]:
+            raise _ffi.ZhError(_ffi.ZH_EINVAL, "set_graph: rows %d, but the arrays hold %d and %d lines" % (g_rows, in_ids.shape[0], in_counts.shape[0]))
+        check(lib().zh_index_set_graph(self._h, _p(in_ids), _p(in_counts), g_rows, in_ids.shape[1]))
+
+    def set_graph_device(self, d_in_ids_ptr, d_in_counts_ptr, g_rows, g_k, stream=None):
+        """set_graph with the graph ([g_rows, g_k] u64, [g_rows] u32) already in device memory (raw pointers, e.g. torch .data_ptr())"""
+        check(lib().zh_index_set_graph_device(self._h, d_in_ids_ptr, d_in_counts_ptr, int(g_rows), int(g_k), stream))
+
+    def drop_graph(self):
+        """release the attached graph (zh_index_drop_graph); nothing happens without one"""
+        check(lib().zh_index_drop_graph(self._h))
+
+    def graph_info(self):
+        """the attached graph (zh_index_graph_info): attached (0 / 1), g_k, g_rows, bytes"""
+        return self._info(_ffi.GraphInfo, lib().zh_index_graph_info)
+
+    def _graph_seeds(self, seeds, q, metric, n_seed):
+        """the [b, n_seed] u64 seed ids of search_graph_batch"""
+        b = q.shape[0]
+        if seeds is None:  # the same strided rows of the attached graph for every query
+            g_rows, n_seed = self.graph_info()["g_rows"], int(n_seed)
+            row = np.array([j * g_rows // n_seed for j in range(n_seed)], np.uint64) + np.uint64(self.id_base)
+            return np.ascontiguousarray(np.broadcast_to(row, (b, n_seed)))
+        if isinstance(seeds, str):
+            if seeds != "lsh":
+                raise ValueError("seeds is None, 'lsh' or an array of ids")
+            return np.ascontiguousarray(self.search_batch(q, int(n_seed), metric)[0])  # (tails are 2^64-1: ignored as out of range)
+        a = np.asarray(seeds).astype(np.uint64, copy=False)
+        if a.ndim == 1:
+            a = np.broadcast_to(a, (b, a.shape[0]))
+        if a.ndim != 2 or a.shape[0] != b:
+            raise _ffi.ZhError(_ffi.ZH_EINVAL, "search_graph_batch: seeds is [n_seed] or [%d, n_seed]" % b)
+        return np.ascontiguousarray(a)
+
+    def search_graph_batch(self, queries, top_k, metric, beam=64, width=1, max_iters=0, seeds=None, n_seed=32):
+        """beam search over the attached graph (set_graph; zh_search_graph_batch) under search_exact_batch's keys: from each query's seeds, the
+        beam holds the `beam` best rows met so far; an iteration expands the first `width` unexpanded ones (their lines' live rows are keyed
+        and merged in) until none is left or `max_iters` (0: no cap) iterations ran -> (ids [b,k] u64, keys [b,k] u64, counts [b] u32), the
+        first top_k of the beam, entries past counts[i] 2^64-1.  seeds: None = the same n_seed strided rows id_base + j * g_rows // n_seed for
+        every query; "lsh" = search_batch(queries, n_seed, metric)'s ids (needs trees); an array [b, n_seed] of ids, or [n_seed] for every
+        query.  Seeds that are out of range, removed or repeated are ignored; a query without a valid seed has count 0.
+        1 <= top_k <= beam <= 256, width * g_k <= 256, 1 <= n_seed <= 64, max_iters <= 65535.  search_graph_info() describes the call."""
+        q = _f32(queries, self.dim)
+        b = q.shape[0]
+        sd = self._graph_seeds(seeds, q, metric, n_seed)
+        top_k = int(top_k)
+        ids = np.empty((b, max(top_k, 0)), np.uint64)
+        keys = np.empty((b, max(top_k, 0)), np.uint64)
+        counts = np.zeros(b, np.uint32)
+        check(lib().zh_search_graph_batch(self._h, _p(q), b, _p(sd), sd.shape[1], top_k, int(beam), int(width), int(max_iters), metric.metric, metric.mode,
+                                          _p(ids), _p(keys), _p(counts)))
+        return ids, keys, counts
+
+    def search_graph(self, query, top_k, metric, **kw):
+        """search_graph_batch of one query -> list of (id, distance key), ascending"""
+        ids, keys, counts = self.search_graph_batch(_f32(query).reshape(1, -1), top_k, metric, **kw)
+        n = int(counts[0])
+        return list(zip(ids[0, :n].tolist(), keys[0, :n].tolist()))
+
+    def search_graph_batch_device(self, d_q_ptr, b, d_seeds_ptr, n_seed, top_k, metric, d_ids_ptr, d_keys_ptr, d_counts_ptr, beam=64, width=1, max_iters=0,
+                                  stream=None):
+        """search_graph_batch with queries ([b, dim] f32), seeds ([b, n_seed] u64) and results already in device memory (raw pointers)"""
+        check(lib().zh_search_graph_batch_device(self._h, d_q_ptr, int(b), d_seeds_ptr, int(n_seed), int(top_k), int(beam), int(width), int(max_iters),
+                                                 metric.metric, metric.mode, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream))
+
+    def search_graph_info(self):
+        """what the most recent search_graph_batch call on this index did (zh_search_graph_info), summed over its queries: queries, seeds (valid
+        ones), iterations, expanded, keyed, capped (stopped by max_iters with an unexpanded entry left), launches"""
+        return self._info(_ffi.SearchGraphInfo, lib().zh_search_graph_info)
+
     def knn_graph_reverse(self, graph, rev_k, first_row=0, n=None):
         """the capped reverse graph of a graph of ALL stored rows (`graph` as for knn_graph_refine): line i holds up to rev_k of the live rows that
         name stored row first_row + i and that its own line does not name -- a deterministic pseudo-random sample by a hash of the pair, the same
@@ -1088,7 +1169,8 @@ class Database:
             self._documents.pop(i, None)
 
     def compact(self):
-        """reclaim the device memory of removed vectors (LSHIndex.compact) and re-key the documents with the old -> new id map"""
+        """reclaim the device memory of removed vectors (LSHIndex.compact) and re-key the documents with the old -> new id map.  Rows move, so the
+        database is left WITHOUT a graph (build_graph again before query_vectors_graph) -- unless nothing was removed and nothing moved."""
         new_ids, info = self.index.compact()
         base, gone = self.index.id_base, np.uint64(0xFFFFFFFFFFFFFFFF)
         docs = {}
@@ -1202,6 +1284,24 @@ class Database:
             return {}
         graph = self.index.knn_graph_forest(k, self.metric)
         return self._graph_documents(*self.index.knn_graph_descent(graph, k, self.metric, rounds=rounds, reverse=reverse))
+
+    def build_graph(self, k=32, rounds=8, reverse=0):
+        """make the graph query_vectors_graph walks and attach it to the index: knn_graph_forest(k), LSHIndex.knn_graph_descent(rounds, reverse),
+        LSHIndex.set_graph.  Needs trees.  Records added later are found only as seeds until the graph is built again; removed ones are skipped
+        at once.  -> LSHIndex.graph_info()"""
+        if self.index.no_vectors():
+            return self.index.graph_info()
+        graph = self.index.knn_graph_forest(k, self.metric)
+        self.index.set_graph(self.index.knn_graph_descent(graph, k, self.metric, rounds=rounds, reverse=reverse))
+        return self.index.graph_info()
+
+    def query_vectors_graph(self, vectors, number_of_results, beam=64, **kw):
+        """query_vectors answered by LSHIndex.search_graph_batch over the graph build_graph attached (beam, width, max_iters, seeds, n_seed as
+        there; beam is raised to number_of_results) -> {query index: {id: document}}"""
+        if self.index.no_vectors():
+            return {}
+        ids, _, counts = self.index.search_graph_batch(vectors, number_of_results, self.metric, beam=max(int(beam), int(number_of_results)), **kw)
+        return {b: {int(i): self._documents.get(int(i)) for i in ids[b, :counts[b]]} for b in range(ids.shape[0])}
 
     def _graph_documents(self, ids, keys, counts):
         dist = self._key_numbers(np.ascontiguousarray(keys)).reshape(keys.shape)

@@ -12,7 +12,7 @@ Per setting it prints the arms' median and range, keyed_round beside the loop's 
 exact graph round by round; the descent's answer after r rounds is asserted equal, id for id, to the device loop's round r, so the recall is the
 same in both arms by construction.
 
-    python tests/probes/descent_probe.py [rows] [kind] [rounds,..] [reverse,..] [sections]   (default 1048576 0 3,8 0,8 times)"""
+    python tests/probes/descent_probe.py [rows] [kind] [rounds,..] [reverse,..] [sections] [library]   (default 1048576 0 3,8 0,8 times, the built library)"""
 import json
 import os
 import sys
@@ -125,6 +125,9 @@ def main(n, kind, rounds_list, rev_list, sections):
 
 if __name__ == "__main__":
     a = sys.argv[1:]
+    if len(a) > 5:
+        from zebra_amd import _ffi
+        _ffi.LIB_PATH = os.path.abspath(a[5])
     ints = lambda s: [int(x) for x in s.split(",")]  # noqa: E731
     main(int(a[0]) if len(a) > 0 else 1_048_576, int(a[1]) if len(a) > 1 else 0, ints(a[2]) if len(a) > 2 else [3, 8], ints(a[3]) if len(a) > 3 else [0, 8],
          set((a[4] if len(a) > 4 else "times").split(",")))

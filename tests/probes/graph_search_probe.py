@@ -14,7 +14,7 @@ the same table with the exact 32-NN graph, 16 queries -- what a visited set woul
 forest graph's, the descent's and the attach's time (device entries).
 The index is created before any torch GEMM (INTEGRATION section 9's order effect): nothing here runs one.
 
-    python tests/probes/graph_search_probe.py [rows] [kind] [sections]   (default 1048576 0 times,rules)"""
+    python tests/probes/graph_search_probe.py [rows] [kind] [sections] [library]   (default 1048576 0 times,rules, the built library)"""
 import json
 import os
 import sys
@@ -134,4 +134,7 @@ def main(n, kind, sections, sample=4096):
 
 if __name__ == "__main__":
     a = sys.argv[1:]
+    if len(a) > 3:
+        from zebra_amd import _ffi
+        _ffi.LIB_PATH = os.path.abspath(a[3])
     main(int(a[0]) if len(a) > 0 else 1_048_576, int(a[1]) if len(a) > 1 else 0, set((a[2] if len(a) > 2 else "times,rules").split(",")))

@@ -5462,41 +5462,97 @@ static int refine_slab(zh_index *ix, LiveCursor *live, const uint32_t *dTab, uin
     return ZH_OK;
 }
 
-// judged before any device is touched, in this order of kinds: null index (even for n = 0), null inputs or outputs of a non-empty request, the
-// metric, the two limits, in_k = 0
-static int refine_args(zh_index *ix, const void *in_ids, const void *in_counts, size_t in_k, uint64_t n, size_t k, int metric, int mode, const void *ids,
-                       const void *keys, const void *counts, const char *who) {
+// rows a staged piece of a round's output holds (the host entries): 2^25 entries, in whole sub-slabs
+static uint64_t refine_host_slab(size_t k) { return std::max<uint64_t>(ZH_REFINE_SLAB, (uint64_t(1) << 25) / k / ZH_REFINE_SLAB * ZH_REFINE_SLAB); }
+
+// every refinement entry, with rev_k = 0 for the plain ones (the limit of the sum then cannot fire behind in_k's).  Judged before any device is
+// touched, in this order of kinds: null index (even for n = 0), null inputs or outputs of a non-empty request, the metric, the limits (k, in_k,
+// in_k + rev_k), in_k = 0
+static int refine_rev_args(zh_index *ix, const void *in_ids, const void *in_counts, size_t in_k, size_t rev_k, uint64_t n, size_t k, int metric, int mode,
+                           const void *ids, const void *keys, const void *counts, const char *who) {
     if (!ix || (n && (!in_ids || !in_counts || !counts || (k && (!ids || !keys))))) return fail(ZH_EINVAL, "%s: null argument", who);
     const int rc = check_metric(metric, mode);
     if (rc) return rc;
     if (k > ZH_MAX_TOPK - 1) return fail(ZH_ELIMIT, "%s: k %zu > ZH_MAX_TOPK - 1 (%u)", who, k, ZH_MAX_TOPK - 1);
     if (in_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: in_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, ZH_REFINE_MAX_IN_K);
+    if (rev_k > ZH_REFINE_MAX_IN_K - in_k) return fail(ZH_ELIMIT, "%s: in_k %zu + rev_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, rev_k, ZH_REFINE_MAX_IN_K);
     if (n && !in_k) return fail(ZH_EINVAL, "%s: in_k is 0", who);
     return ZH_OK;
 }
 
-// The in-neighbours of every stored row out of rf_tab (refine_table has run; n_rows > 0): rv_deg, rv_off, rv_csr; rv_ctr = {edges, max in-degree, 0, 0}
-static int reverse_csr(zh_index *ix, uint32_t in_k, hipStream_t s) {
+// the transposition's buffers for forward tables up to w wide
+static int reverse_ensure(zh_index *ix, uint32_t w) {
     const uint64_t N = ix->n_rows;
     int rc;
     if ((rc = ix->rv_deg.ensure((size_t)N * 4)) || (rc = ix->rv_cur.ensure((size_t)N * 4)) || (rc = ix->rv_off.ensure((size_t)(N + 1) * 8)) ||
-        (rc = ix->rv_sums.ensure((size_t)(N / 4096 + 1) * 8)) || (rc = ix->rv_csr.ensure((size_t)N * in_k * 4)) ||
-        (rc = ix->rv_heavy.ensure((size_t)(N * in_k / ZH_REVERSE_HEAVY + 1) * 4)) || (rc = ix->rv_ctr.ensure(32)))
+        (rc = ix->rv_sums.ensure((size_t)(N / 4096 + 1) * 8)) || (rc = ix->rv_csr.ensure((size_t)N * w * 4)) ||
+        (rc = ix->rv_heavy.ensure((size_t)(N * w / ZH_REVERSE_HEAVY + 1) * 4)) || (rc = ix->rv_ctr.ensure(32)))
         return rc;
-    HIPCHK(hipMemsetAsync(ix->rv_ctr.p, 0, 32, s));
-    HIPCHK(zh_launch_reverse_csr(ix->rf_tab.as<uint32_t>(), ix->live_dev.bits.as<uint32_t>(), N, in_k, ix->rv_deg.as<uint32_t>(), ix->rv_cur.as<uint32_t>(), ix->rv_off.as<uint64_t>(),
-                                 ix->rv_sums.as<uint64_t>(), ix->rv_csr.as<uint32_t>(), ix->rv_ctr.as<unsigned long long>(), s));
     return ZH_OK;
 }
 
-// R'(x) of the lines [x0, x0 + nx) (reverse_csr has run): into the union table rv_uni (uni) and / or, for the lines of [first_row, first_row + n), as
-// ids, counts and in-degrees on device pointers; rv_ctr[2] += the slab's kept entries
-static int reverse_select(zh_index *ix, uint32_t in_k, uint32_t rev_k, uint64_t x0, uint64_t nx, uint64_t first_row, uint64_t n, bool uni, uint64_t *dIds,
-                          uint32_t *dCounts, uint32_t *dDegree, hipStream_t s, uint64_t *launches) {
-    HIPCHK(zh_launch_reverse_select(ix->rf_tab.as<uint32_t>(), in_k, rev_k, ix->rv_off.as<uint64_t>(), ix->rv_csr.as<uint32_t>(), ix->n_rows, x0, nx, first_row, n,
-                                    ix->opt.id_base, uni ? ix->rv_uni.as<uint32_t>() : nullptr, dIds, dCounts, dDegree, ix->rv_heavy.as<uint32_t>(),
-                                    ix->rv_ctr.as<unsigned long long>(), s));
-    *launches += (nx + (1ull << 24) - 1) / (1ull << 24) + 1;
+// The in-neighbours of every stored row out of the forward table dTab, w wide (n_rows > 0): rv_deg, rv_off, rv_csr; rv_ctr = {edges, max in-degree, 0, 0}
+static int reverse_csr(zh_index *ix, const uint32_t *dTab, uint32_t w, hipStream_t s) {
+    int rc;
+    if ((rc = reverse_ensure(ix, w))) return rc;
+    HIPCHK(hipMemsetAsync(ix->rv_ctr.p, 0, 32, s));
+    HIPCHK(zh_launch_reverse_csr(dTab, ix->live_dev.bits.as<uint32_t>(), ix->n_rows, w, ix->rv_deg.as<uint32_t>(), ix->rv_cur.as<uint32_t>(), ix->rv_off.as<uint64_t>(),
+                                 ix->rv_sums.as<uint64_t>(), ix->rv_csr.as<uint32_t>(), ix->rv_ctr.as<unsigned long long>(), s));
+    return ZH_OK;
+}
+// what the multi-round descent adds to `launches` for a transposition beside its selection's count: with that count (which has the heavy-line
+// launch in it) the figure the field has always had, 5 + 2 ceil(N w / 2^30) + ceil(N / 2^24).  The one-round calls never counted these passes.
+static uint64_t reverse_csr_launches(uint64_t N, uint32_t w) { return 4 + 2 * ((N * w + (1ull << 30) - 1) >> 30); }
+
+// R'(x) of the lines [x0, x0 + nx) of dTab (reverse_csr has run over it): behind N'(x) into the union table dUni (or null) and / or, for the lines of
+// [first_row, first_row + n), as ids, counts and in-degrees on device pointers; rv_ctr[2] += the slab's kept entries; *launches += the selection's
+static int reverse_select(zh_index *ix, const uint32_t *dTab, uint32_t w, uint32_t rev_k, uint64_t x0, uint64_t nx, uint64_t first_row, uint64_t n, uint32_t *dUni,
+                          uint64_t *dIds, uint32_t *dCounts, uint32_t *dDegree, hipStream_t s, uint64_t *launches) {
+    HIPCHK(zh_launch_reverse_select(dTab, w, rev_k, ix->rv_off.as<uint64_t>(), ix->rv_csr.as<uint32_t>(), ix->n_rows, x0, nx, first_row, n, ix->opt.id_base, dUni, dIds,
+                                    dCounts, dDegree, ix->rv_heavy.as<uint32_t>(), ix->rv_ctr.as<unsigned long long>(), s));
+    *launches += zh_line_launches(nx) + 1;
+    return ZH_OK;
+}
+
+// U(x) of a forward table dTab (w wide): N'(x), then R'(x) -- the transposition and the selection over every stored row into dUni (w + rev_k wide);
+// rv_ctr's `kept` counts the lines of [first_row, first_row + n)
+static int reverse_union(zh_index *ix, const uint32_t *dTab, uint32_t w, uint32_t rev_k, uint64_t first_row, uint64_t n, uint32_t *dUni, hipStream_t s,
+                         uint64_t *launches) {
+    int rc;
+    if ((rc = reverse_csr(ix, dTab, w, s))) return rc;
+    return reverse_select(ix, dTab, w, rev_k, 0, ix->n_rows, first_row, n, dUni, nullptr, nullptr, nullptr, s, launches);
+}
+
+// what a first round ranks over: the caller's graph as rf_tab (refine_table), or with rev_k its union table in dUni (in_k + rev_k wide)
+static int refine_first_table(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, uint32_t rev_k, uint64_t first_row, uint64_t n, bool host,
+                              hipStream_t s, uint32_t *dUni, const uint32_t **dTab, uint64_t *rev_launches) {
+    int rc;
+    if ((rc = refine_table(ix, in_ids, in_counts, in_k, host, s))) return rc;
+    *dTab = ix->rf_tab.as<uint32_t>();
+    if (!rev_k) return ZH_OK;
+    if ((rc = reverse_union(ix, *dTab, in_k, rev_k, first_row, n, dUni, s, rev_launches))) return rc;
+    *dTab = dUni;
+    return ZH_OK;
+}
+
+// A refinement round into the caller's arrays (k > 0, n > 0; under mu, exact_live_rows has run): the table, with rev_k the union (rv_uni), the slabs,
+// then the counters -- ctr: rf_ctr's listed / keyed / updates; rctr (or null): rv_ctr -- and the wait for all of it
+static int refine_round(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, uint32_t rev_k, uint64_t first_row, uint64_t n, uint32_t k,
+                        int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, bool host, hipStream_t s, zh_knn_refine_info *inf,
+                        unsigned long long *ctr, unsigned long long *rctr, uint64_t *rev_launches) {
+    int rc;
+    const uint32_t *dTab = nullptr;
+    if (rev_k && (rc = ix->rv_uni.ensure((size_t)ix->n_rows * (in_k + rev_k) * 4))) return rc;
+    if ((rc = refine_first_table(ix, in_ids, in_counts, in_k, rev_k, first_row, n, host, s, ix->rv_uni.as<uint32_t>(), &dTab, rev_launches))) return rc;
+    if (rev_k && rctr) HIPCHK(hipMemcpyAsync(rctr, ix->rv_ctr.p, 32, hipMemcpyDeviceToHost, s));  // (waited for with the slabs)
+    LiveCursor live;
+    rc = knn_slabs(ix, first_row, n, k, out_ids, out_keys, out_counts, refine_host_slab(k), host, s,
+                   [&](uint64_t r0, uint64_t m, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
+                       return refine_slab(ix, &live, dTab, in_k + rev_k, in_k, r0, m, k, metric, mode, dIds, dKeys, dCounts, s, inf);
+                   });
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ctr, ix->rf_ctr.p, 24, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return ZH_OK;
 }
 
@@ -5511,30 +5567,12 @@ static int refine_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_
     const hipStream_t s = call_stream(ix, stream);
     zh_knn_refine_info inf{};
     unsigned long long ctr[3] = {0, 0, 0}, rctr[4] = {0, 0, 0, 0};
-    uint64_t rev_launches = 0;
-    if (k == 0) {
-        if ((rc = knn_no_neighbours(n, out_counts, host, s))) return rc;
-    } else {
-        if ((rc = refine_table(ix, in_ids, in_counts, in_k, host, s))) return rc;
-        const uint32_t *dTab = ix->rf_tab.as<uint32_t>();
-        const uint32_t width = in_k + rev_k;
-        if (rev_k) {
-            if ((rc = ix->rv_uni.ensure((size_t)ix->n_rows * width * 4)) || (rc = reverse_csr(ix, in_k, s)) ||
-                (rc = reverse_select(ix, in_k, rev_k, 0, ix->n_rows, first_row, n, true, nullptr, nullptr, nullptr, s, &rev_launches)))
-                return rc;
-            HIPCHK(hipMemcpyAsync(rctr, ix->rv_ctr.p, 32, hipMemcpyDeviceToHost, s));  // (waited for with the slabs)
-            dTab = ix->rv_uni.as<uint32_t>();
-        }
-        LiveCursor live;
-        const uint64_t host_slab = std::max<uint64_t>(ZH_REFINE_SLAB, (uint64_t(1) << 25) / k / ZH_REFINE_SLAB * ZH_REFINE_SLAB);
-        rc = knn_slabs(ix, first_row, n, k, out_ids, out_keys, out_counts, host_slab, host, s,
-                       [&](uint64_t r0, uint64_t m, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
-                           return refine_slab(ix, &live, dTab, width, in_k, r0, m, (uint32_t)k, metric, mode, dIds, dKeys, dCounts, s, &inf);
-                       });
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(ctr, ix->rf_ctr.p, 24, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
+    uint64_t rev_launches = 0;  // (the fused call's `launches` are the line kernel's)
+    if (k == 0) rc = knn_no_neighbours(n, out_counts, host, s);
+    else
+        rc = refine_round(ix, in_ids, in_counts, in_k, rev_k, first_row, n, (uint32_t)k, metric, mode, out_ids, out_keys, out_counts, host, s, &inf, ctr, rctr,
+                          &rev_launches);
+    if (rc) return rc;
     inf.rows_live = ix->live_dev.n_live;
     inf.in_k = in_k;
     inf.k = (uint32_t)k;
@@ -5554,7 +5592,7 @@ static int refine_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_
 
 extern "C" int zh_knn_graph_refine_device(zh_index *ix, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, uint64_t first_row, uint64_t n,
                                           size_t k, int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
-    int rc = refine_args(ix, d_in_ids, d_in_counts, in_k, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_refine_device");
+    int rc = refine_rev_args(ix, d_in_ids, d_in_counts, in_k, 0, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_refine_device");
     if (rc || n == 0) return rc;
     return refine_call(ix, d_in_ids, d_in_counts, (uint32_t)in_k, 0, false, first_row, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, false, stream,
                        "zh_knn_graph_refine_device");
@@ -5562,7 +5600,7 @@ extern "C" int zh_knn_graph_refine_device(zh_index *ix, const uint64_t *d_in_ids
 
 extern "C" int zh_knn_graph_refine(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, uint64_t first_row, uint64_t n, size_t k,
                                    int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts) {
-    int rc = refine_args(ix, in_ids, in_counts, in_k, n, k, metric, mode, out_ids, out_keys, out_counts, "zh_knn_graph_refine");
+    int rc = refine_rev_args(ix, in_ids, in_counts, in_k, 0, n, k, metric, mode, out_ids, out_keys, out_counts, "zh_knn_graph_refine");
     if (rc || n == 0) return rc;
     return refine_call(ix, in_ids, in_counts, (uint32_t)in_k, 0, false, first_row, n, k, metric, mode, out_ids, out_keys, out_counts, true, nullptr,
                        "zh_knn_graph_refine");
@@ -5575,19 +5613,6 @@ extern "C" int zh_knn_graph_refine_info(const zh_index *ix, zh_knn_refine_info *
 // ------------------------------------------------------------------------------------------------
 // reverse neighbours (zh_reverse.hip): the capped transposed graph on its own, and the refinement over N'(x) union R'(x).  DESIGN.md s22
 // ------------------------------------------------------------------------------------------------
-// zh_knn_graph_refine_rev*: refine_args' order with the limit of the sum behind in_k's
-static int refine_rev_args(zh_index *ix, const void *in_ids, const void *in_counts, size_t in_k, size_t rev_k, uint64_t n, size_t k, int metric, int mode,
-                           const void *ids, const void *keys, const void *counts, const char *who) {
-    if (!ix || (n && (!in_ids || !in_counts || !counts || (k && (!ids || !keys))))) return fail(ZH_EINVAL, "%s: null argument", who);
-    const int rc = check_metric(metric, mode);
-    if (rc) return rc;
-    if (k > ZH_MAX_TOPK - 1) return fail(ZH_ELIMIT, "%s: k %zu > ZH_MAX_TOPK - 1 (%u)", who, k, ZH_MAX_TOPK - 1);
-    if (in_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: in_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, ZH_REFINE_MAX_IN_K);
-    if (rev_k > ZH_REFINE_MAX_IN_K - in_k) return fail(ZH_ELIMIT, "%s: in_k %zu + rev_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, rev_k, ZH_REFINE_MAX_IN_K);
-    if (n && !in_k) return fail(ZH_EINVAL, "%s: in_k is 0", who);
-    return ZH_OK;
-}
-
 extern "C" int zh_knn_graph_refine_rev_device(zh_index *ix, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, size_t rev_k, uint64_t first_row,
                                               uint64_t n, size_t k, int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts,
                                               void *stream) {
@@ -5609,6 +5634,80 @@ extern "C" int zh_knn_graph_refine_rev_info(const zh_index *ix, zh_knn_refine_re
     return get_info(ix, &zh_index::rfr_info, out, "zh_knn_graph_refine_rev_info");
 }
 
+// judged before any device is touched, in this order of kinds: null index (even for n = 0), null inputs or outputs of a non-empty request, the two
+// limits, in_k = 0, rev_k = 0
+static int reverse_args(zh_index *ix, const void *in_ids, const void *in_counts, size_t in_k, size_t rev_k, uint64_t n, const void *ids, const void *counts,
+                        const void *degree, const char *who) {
+    if (!ix || (n && (!in_ids || !in_counts || !ids || !counts || !degree))) return fail(ZH_EINVAL, "%s: null argument", who);
+    if (in_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: in_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, ZH_REFINE_MAX_IN_K);
+    if (rev_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: rev_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, rev_k, ZH_REFINE_MAX_IN_K);
+    if (n && !in_k) return fail(ZH_EINVAL, "%s: in_k is 0", who);
+    if (n && !rev_k) return fail(ZH_EINVAL, "%s: rev_k is 0", who);
+    return ZH_OK;
+}
+
+// both entry points once the arguments have been judged (n > 0).  host: the outputs are HOST arrays and go piece by piece through the staging
+static int reverse_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, uint32_t rev_k, uint64_t first_row, uint64_t n,
+                        uint64_t *out_ids, uint32_t *out_counts, uint32_t *out_degree, bool host, void *stream, const char *who) {
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, who))) return rc;
+    ScratchGuard guard{ix, SCRATCH_REVERSE};
+    const hipStream_t s = call_stream(ix, stream);
+    zh_knn_reverse_info inf{};
+    unsigned long long rctr[4] = {0, 0, 0, 0};
+    if ((rc = refine_table(ix, in_ids, in_counts, in_k, host, s))) return rc;
+    const uint32_t *dTab = ix->rf_tab.as<uint32_t>();
+    if ((rc = reverse_csr(ix, dTab, in_k, s))) return rc;
+    if (!host) {
+        if ((rc = reverse_select(ix, dTab, in_k, rev_k, first_row, n, first_row, n, nullptr, out_ids, out_counts, out_degree, s, &inf.launches))) return rc;
+    } else {
+        const uint64_t piece = std::min<uint64_t>(n, std::max<uint64_t>(ZH_REFINE_SLAB, (uint64_t(1) << 25) / rev_k));
+        if ((rc = ix->rv_oids.ensure(piece * rev_k * 8)) || (rc = ix->rv_ocounts.ensure(piece * 4)) || (rc = ix->rv_odeg.ensure(piece * 4))) return rc;
+        for (uint64_t r0 = 0; r0 < n; r0 += piece) {
+            const uint64_t m = std::min(piece, n - r0);
+            if ((rc = reverse_select(ix, dTab, in_k, rev_k, first_row + r0, m, first_row + r0, m, nullptr, ix->rv_oids.as<uint64_t>(), ix->rv_ocounts.as<uint32_t>(),
+                                     ix->rv_odeg.as<uint32_t>(), s, &inf.launches)))
+                return rc;
+            HIPCHK(hipMemcpyAsync(out_ids + r0 * rev_k, ix->rv_oids.p, m * rev_k * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_counts + r0, ix->rv_ocounts.p, m * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_degree + r0, ix->rv_odeg.p, m * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+    }
+    HIPCHK(hipMemcpyAsync(rctr, ix->rv_ctr.p, 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    LiveCursor live;
+    inf.rows_live = ix->live_dev.n_live;
+    inf.lines = live_before(ix, first_row + n, &live) - live_before(ix, first_row, &live);
+    inf.in_k = in_k;
+    inf.rev_k = rev_k;
+    inf.edges = rctr[0]; inf.kept = rctr[2]; inf.max_degree = rctr[1];
+    std::lock_guard<std::mutex> ls(ix->stats_mu);
+    ix->rv_info = inf;
+    return ZH_OK;
+}
+
+extern "C" int zh_knn_graph_reverse_device(zh_index *ix, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, size_t rev_k, uint64_t first_row,
+                                           uint64_t n, uint64_t *d_out_ids, uint32_t *d_out_counts, uint32_t *d_out_degree, void *stream) {
+    int rc = reverse_args(ix, d_in_ids, d_in_counts, in_k, rev_k, n, d_out_ids, d_out_counts, d_out_degree, "zh_knn_graph_reverse_device");
+    if (rc || n == 0) return rc;
+    return reverse_call(ix, d_in_ids, d_in_counts, (uint32_t)in_k, (uint32_t)rev_k, first_row, n, d_out_ids, d_out_counts, d_out_degree, false, stream,
+                        "zh_knn_graph_reverse_device");
+}
+
+extern "C" int zh_knn_graph_reverse(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, size_t rev_k, uint64_t first_row, uint64_t n,
+                                    uint64_t *out_ids, uint32_t *out_counts, uint32_t *out_degree) {
+    int rc = reverse_args(ix, in_ids, in_counts, in_k, rev_k, n, out_ids, out_counts, out_degree, "zh_knn_graph_reverse");
+    if (rc || n == 0) return rc;
+    return reverse_call(ix, in_ids, in_counts, (uint32_t)in_k, (uint32_t)rev_k, first_row, n, out_ids, out_counts, out_degree, true, nullptr,
+                        "zh_knn_graph_reverse");
+}
+
+extern "C" int zh_knn_graph_reverse_info(const zh_index *ix, zh_knn_reverse_info *out) {
+    return get_info(ix, &zh_index::rv_info, out, "zh_knn_graph_reverse_info");
+}
+
 // ------------------------------------------------------------------------------------------------
 // NN-descent (zh_nnd.hip): the refinement's rounds on the device, keying from round 2 on only what a new entry brings up.  DESIGN.md s23
 // ------------------------------------------------------------------------------------------------
@@ -5626,18 +5725,6 @@ static int descent_args(zh_index *ix, const void *in_ids, const void *in_counts,
     if (k > ZH_REFINE_MAX_IN_K || rev_k > ZH_REFINE_MAX_IN_K - k)
         return fail(ZH_ELIMIT, "%s: k %zu + rev_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, k, rev_k, ZH_REFINE_MAX_IN_K);
     if (!in_k) return fail(ZH_EINVAL, "%s: in_k is 0", who);
-    return ZH_OK;
-}
-
-// U(x) of a forward table dTab (w wide): N'(x), then R'(x) -- the transposition and the selection of zh_knn_graph_reverse into dUni (w + rev_k wide)
-static int descent_union(zh_index *ix, const uint32_t *dTab, uint32_t w, uint32_t rev_k, uint32_t *dUni, hipStream_t s, uint64_t *launches) {
-    const uint64_t N = ix->n_rows;
-    HIPCHK(hipMemsetAsync(ix->rv_ctr.p, 0, 32, s));
-    HIPCHK(zh_launch_reverse_csr(dTab, ix->live_dev.bits.as<uint32_t>(), N, w, ix->rv_deg.as<uint32_t>(), ix->rv_cur.as<uint32_t>(), ix->rv_off.as<uint64_t>(),
-                                 ix->rv_sums.as<uint64_t>(), ix->rv_csr.as<uint32_t>(), ix->rv_ctr.as<unsigned long long>(), s));
-    HIPCHK(zh_launch_reverse_select(dTab, w, rev_k, ix->rv_off.as<uint64_t>(), ix->rv_csr.as<uint32_t>(), N, 0, N, 0, N, ix->opt.id_base, dUni, nullptr, nullptr,
-                                    nullptr, ix->rv_heavy.as<uint32_t>(), ix->rv_ctr.as<unsigned long long>(), s));
-    *launches += 5 + 2 * ((N * w + (1ull << 30) - 1) >> 30) + ((N + (1ull << 24) - 1) >> 24);
     return ZH_OK;
 }
 
@@ -5663,24 +5750,10 @@ static int descent_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in
         inf.keyed_round[0] = ctr[1]; inf.updates_round[0] = ctr[2]; inf.active_round[0] = n_live;
         inf.rounds_run = 1;
     };
+    zh_knn_refine_info one{};
     if (rounds == 1) {  // one round is zh_knn_graph_refine_rev and nothing else: its passes, straight into the caller's arrays, no state of the call's own
-        if ((rc = refine_table(ix, in_ids, in_counts, in_k, host, s))) return rc;
-        const uint32_t *dTab = ix->rf_tab.as<uint32_t>();
-        if (rev_k) {
-            if ((rc = ix->rv_uni.ensure((size_t)N * w1 * 4)) || (rc = reverse_csr(ix, in_k, s)) ||
-                (rc = reverse_select(ix, in_k, rev_k, 0, N, 0, N, true, nullptr, nullptr, nullptr, s, &inf.launches)))
-                return rc;
-            dTab = ix->rv_uni.as<uint32_t>();
-        }
-        LiveCursor live;
-        zh_knn_refine_info one{};
-        const uint64_t host_slab = std::max<uint64_t>(ZH_REFINE_SLAB, (uint64_t(1) << 25) / k / ZH_REFINE_SLAB * ZH_REFINE_SLAB);
-        rc = knn_slabs(ix, 0, N, k, out_ids, out_keys, out_counts, host_slab, host, s, [&](uint64_t r0, uint64_t m, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
-            return refine_slab(ix, &live, dTab, w1, in_k, r0, m, k, metric, mode, dIds, dKeys, dCounts, s, &one);
-        });
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(ctr, ix->rf_ctr.p, 24, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
+        if ((rc = refine_round(ix, in_ids, in_counts, in_k, rev_k, 0, N, k, metric, mode, out_ids, out_keys, out_counts, host, s, &one, ctr, nullptr, &inf.launches)))
+            return rc;
         first_round(one.lines, one.launches);
         std::lock_guard<std::mutex> ls(ix->stats_mu);
         ix->nd_info = inf;
@@ -5694,12 +5767,8 @@ static int descent_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in
     if ((rc = ix->nd_mask.ensure((size_t)N * 8)) || (rc = ix->nd_list.ensure(std::max<size_t>((size_t)n_live * 4, 4))) || (rc = ix->nd_qq.ensure((size_t)N * 4)) ||
         (rc = ix->nd_ctr.ensure(ZH_NND_CTRS * 8)))
         return rc;
-    if (rev_k &&
-        ((rc = ix->rv_deg.ensure((size_t)N * 4)) || (rc = ix->rv_cur.ensure((size_t)N * 4)) || (rc = ix->rv_off.ensure((size_t)(N + 1) * 8)) ||
-         (rc = ix->rv_sums.ensure((size_t)(N / 4096 + 1) * 8)) || (rc = ix->rv_csr.ensure((size_t)N * wmax * 4)) ||
-         (rc = ix->rv_heavy.ensure((size_t)(N * wmax / ZH_REVERSE_HEAVY + 1) * 4)) || (rc = ix->rv_ctr.ensure(32))))
-        return rc;
-    const uint64_t piece = std::min<uint64_t>(N, std::max<uint64_t>(ZH_REFINE_SLAB, (uint64_t(1) << 25) / k / ZH_REFINE_SLAB * ZH_REFINE_SLAB));
+    if (rev_k && (rc = reverse_ensure(ix, wmax))) return rc;
+    const uint64_t piece = std::min<uint64_t>(N, refine_host_slab(k));
     if ((rc = ix->kn_oids.ensure(piece * k * 8)) || (rc = ix->kn_ocounts.ensure(piece * 4)) || (host && (rc = ix->kn_okeys.ensure(piece * k * 8)))) return rc;
     uint32_t *tab[2] = {ix->nd_tab[0].as<uint32_t>(), ix->nd_tab[1].as<uint32_t>()};
     uint64_t *key[2] = {ix->nd_key[0].as<uint64_t>(), ix->nd_key[1].as<uint64_t>()};
@@ -5713,13 +5782,9 @@ static int descent_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in
         for (uint64_t r0 = 0; r0 < N; r0 += 1ull << 30)
             HIPCHK(zh_launch_qnorm(ix->X.as<float>() + r0 * d, (uint32_t)std::min<uint64_t>(1ull << 30, N - r0), d, ix->nd_qq.as<float>() + r0, s));
     // ---- round 1: zh_knn_graph_refine_rev's passes; the keys go straight to key[0], the ids piece by piece through the staging into tab[0]
-    if ((rc = refine_table(ix, in_ids, in_counts, in_k, host, s))) return rc;
-    const uint32_t *Uprev = ix->rf_tab.as<uint32_t>();  // U_0, w1 wide
-    if (rev_k) {
-        if ((rc = descent_union(ix, ix->rf_tab.as<uint32_t>(), in_k, rev_k, uni[0], s, &inf.launches))) return rc;
-        Uprev = uni[0];
-    }
-    zh_knn_refine_info one{};
+    const uint32_t *Uprev = nullptr;  // U_0, w1 wide
+    if ((rc = refine_first_table(ix, in_ids, in_counts, in_k, rev_k, 0, N, host, s, uni[0], &Uprev, &inf.launches))) return rc;
+    if (rev_k) inf.launches += reverse_csr_launches(N, in_k);
     {
         LiveCursor live;
         for (uint64_t r0 = 0; r0 < N; r0 += piece) {
@@ -5740,7 +5805,8 @@ static int descent_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in
         const int c = (int)((r - 1) & 1), nx = (int)(r & 1);
         const uint32_t *Ucur = tab[c];
         if (rev_k) {
-            if ((rc = descent_union(ix, tab[c], k, rev_k, uni[r & 1], s, &inf.launches))) return rc;
+            if ((rc = reverse_union(ix, tab[c], k, rev_k, 0, N, uni[r & 1], s, &inf.launches))) return rc;
+            inf.launches += reverse_csr_launches(N, k);
             Ucur = uni[r & 1];
         }
         HIPCHK(hipMemsetAsync(dCtr, 0, ZH_NND_CTRS * 8, s));
@@ -5749,7 +5815,7 @@ static int descent_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in
                                   ix->nd_list.as<uint32_t>(), dCtr, s));
         HIPCHK(zh_launch_nnd_lines(ix->X.as<float>(), d, Ucur, w, k, ix->nd_mask.as<uint64_t>(), key[c], ix->nd_qq.as<float>(), ix->nd_list.as<uint32_t>(), n_live,
                                    metric, param, tab[nx], key[nx], dCtr, s));
-        inf.launches += 2 * ((N + (1ull << 24) - 1) >> 24) + (w + w * w > ZH_REFINE_CAP_SMALL ? 2 : 1);
+        inf.launches += 2 * zh_line_launches(N) + (w + w * w > ZH_REFINE_CAP_SMALL ? 2 : 1);
         HIPCHK(hipMemcpyAsync(ctr, dCtr, ZH_NND_CTRS * 8, hipMemcpyDeviceToHost, s));  // the round's one readback: it decides the early stop
         HIPCHK(hipStreamSynchronize(s));
         inf.listed += ctr[0]; inf.keyed += ctr[1]; inf.updates = ctr[2]; inf.lines_active += ctr[3]; inf.large_lines += ctr[5];
@@ -5763,7 +5829,7 @@ static int descent_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in
     if (!host) {
         HIPCHK(zh_launch_nnd_emit(tab[f], key[f], k, ix->opt.id_base, N, out_ids, out_keys, out_counts, s));
         HIPCHK(hipStreamSynchronize(s));
-        inf.launches += (N + (1ull << 24) - 1) >> 24;
+        inf.launches += zh_line_launches(N);
     } else {
         for (uint64_t r0 = 0; r0 < N; r0 += piece) {
             const uint64_t m = std::min(piece, N - r0);
@@ -5950,78 +6016,6 @@ extern "C" int zh_search_graph_batch(zh_index *ix, const float *q, size_t b, con
 
 extern "C" int zh_search_graph_info(const zh_index *ix, zh_graph_search_info *out) {
     return get_info(ix, &zh_index::gs_info, out, "zh_search_graph_info");
-}
-
-// judged before any device is touched, in this order of kinds: null index (even for n = 0), null inputs or outputs of a non-empty request, the two
-// limits, in_k = 0, rev_k = 0
-static int reverse_args(zh_index *ix, const void *in_ids, const void *in_counts, size_t in_k, size_t rev_k, uint64_t n, const void *ids, const void *counts,
-                        const void *degree, const char *who) {
-    if (!ix || (n && (!in_ids || !in_counts || !ids || !counts || !degree))) return fail(ZH_EINVAL, "%s: null argument", who);
-    if (in_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: in_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, ZH_REFINE_MAX_IN_K);
-    if (rev_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: rev_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, rev_k, ZH_REFINE_MAX_IN_K);
-    if (n && !in_k) return fail(ZH_EINVAL, "%s: in_k is 0", who);
-    if (n && !rev_k) return fail(ZH_EINVAL, "%s: rev_k is 0", who);
-    return ZH_OK;
-}
-
-// both entry points once the arguments have been judged (n > 0).  host: the outputs are HOST arrays and go piece by piece through the staging
-static int reverse_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, uint32_t rev_k, uint64_t first_row, uint64_t n,
-                        uint64_t *out_ids, uint32_t *out_counts, uint32_t *out_degree, bool host, void *stream, const char *who) {
-    std::unique_lock<std::shared_mutex> lk(ix->mu);
-    int rc;
-    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, who))) return rc;
-    ScratchGuard guard{ix, SCRATCH_REVERSE};
-    const hipStream_t s = call_stream(ix, stream);
-    zh_knn_reverse_info inf{};
-    unsigned long long rctr[4] = {0, 0, 0, 0};
-    if ((rc = refine_table(ix, in_ids, in_counts, in_k, host, s)) || (rc = reverse_csr(ix, in_k, s))) return rc;
-    if (!host) {
-        if ((rc = reverse_select(ix, in_k, rev_k, first_row, n, first_row, n, false, out_ids, out_counts, out_degree, s, &inf.launches))) return rc;
-    } else {
-        const uint64_t piece = std::min<uint64_t>(n, std::max<uint64_t>(ZH_REFINE_SLAB, (uint64_t(1) << 25) / rev_k));
-        if ((rc = ix->rv_oids.ensure(piece * rev_k * 8)) || (rc = ix->rv_ocounts.ensure(piece * 4)) || (rc = ix->rv_odeg.ensure(piece * 4))) return rc;
-        for (uint64_t r0 = 0; r0 < n; r0 += piece) {
-            const uint64_t m = std::min(piece, n - r0);
-            if ((rc = reverse_select(ix, in_k, rev_k, first_row + r0, m, first_row + r0, m, false, ix->rv_oids.as<uint64_t>(), ix->rv_ocounts.as<uint32_t>(),
-                                     ix->rv_odeg.as<uint32_t>(), s, &inf.launches)))
-                return rc;
-            HIPCHK(hipMemcpyAsync(out_ids + r0 * rev_k, ix->rv_oids.p, m * rev_k * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(out_counts + r0, ix->rv_ocounts.p, m * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(out_degree + r0, ix->rv_odeg.p, m * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-        }
-    }
-    HIPCHK(hipMemcpyAsync(rctr, ix->rv_ctr.p, 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    LiveCursor live;
-    inf.rows_live = ix->live_dev.n_live;
-    inf.lines = live_before(ix, first_row + n, &live) - live_before(ix, first_row, &live);
-    inf.in_k = in_k;
-    inf.rev_k = rev_k;
-    inf.edges = rctr[0]; inf.kept = rctr[2]; inf.max_degree = rctr[1];
-    std::lock_guard<std::mutex> ls(ix->stats_mu);
-    ix->rv_info = inf;
-    return ZH_OK;
-}
-
-extern "C" int zh_knn_graph_reverse_device(zh_index *ix, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, size_t rev_k, uint64_t first_row,
-                                           uint64_t n, uint64_t *d_out_ids, uint32_t *d_out_counts, uint32_t *d_out_degree, void *stream) {
-    int rc = reverse_args(ix, d_in_ids, d_in_counts, in_k, rev_k, n, d_out_ids, d_out_counts, d_out_degree, "zh_knn_graph_reverse_device");
-    if (rc || n == 0) return rc;
-    return reverse_call(ix, d_in_ids, d_in_counts, (uint32_t)in_k, (uint32_t)rev_k, first_row, n, d_out_ids, d_out_counts, d_out_degree, false, stream,
-                        "zh_knn_graph_reverse_device");
-}
-
-extern "C" int zh_knn_graph_reverse(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, size_t rev_k, uint64_t first_row, uint64_t n,
-                                    uint64_t *out_ids, uint32_t *out_counts, uint32_t *out_degree) {
-    int rc = reverse_args(ix, in_ids, in_counts, in_k, rev_k, n, out_ids, out_counts, out_degree, "zh_knn_graph_reverse");
-    if (rc || n == 0) return rc;
-    return reverse_call(ix, in_ids, in_counts, (uint32_t)in_k, (uint32_t)rev_k, first_row, n, out_ids, out_counts, out_degree, true, nullptr,
-                        "zh_knn_graph_reverse");
-}
-
-extern "C" int zh_knn_graph_reverse_info(const zh_index *ix, zh_knn_reverse_info *out) {
-    return get_info(ix, &zh_index::rv_info, out, "zh_knn_graph_reverse_info");
 }
 
 // ------------------------------------------------------------------------------------------------

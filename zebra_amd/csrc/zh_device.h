@@ -88,6 +88,43 @@ __host__ __device__ inline int zh_kind_of(int metric) {
     }
 }
 
+// The host's one table of the canonical-row kernels' instantiations (exact_score_kernel, refine_line_kernel, nnd_line_kernel, gsearch_kernel): ten
+// kinds; d = 128 / 384 / 768 specialised for every kind, 256 / 512 / 1024 as well for the two simsimd kinds; any other d is the generic 0.
+// -> f(kind, dim), both std::integral_constant<int, ..>, so that a generic lambda names its kernel with them.
+template <int KIND, class F>
+inline hipError_t zh_dispatch_dim(uint32_t d, F &f) {
+    using K = std::integral_constant<int, KIND>;
+    if constexpr (KIND == K_L2 || KIND == K_COS) {
+        switch (d) {
+        case 256: return f(K{}, std::integral_constant<int, 256>{});
+        case 512: return f(K{}, std::integral_constant<int, 512>{});
+        case 1024: return f(K{}, std::integral_constant<int, 1024>{});
+        default: break;
+        }
+    }
+    switch (d) {
+    case 128: return f(K{}, std::integral_constant<int, 128>{});
+    case 384: return f(K{}, std::integral_constant<int, 384>{});
+    case 768: return f(K{}, std::integral_constant<int, 768>{});
+    default: return f(K{}, std::integral_constant<int, 0>{});
+    }
+}
+template <class F>
+inline hipError_t zh_dispatch_kind_dim(int metric, uint32_t d, F f) {
+    switch (zh_kind_of(metric)) {
+    case K_COS: return zh_dispatch_dim<K_COS>(d, f);
+    case K_MAX: return zh_dispatch_dim<K_MAX>(d, f);
+    case K_CANB: return zh_dispatch_dim<K_CANB>(d, f);
+    case K_BRAY: return zh_dispatch_dim<K_BRAY>(d, f);
+    case K_ABS: return zh_dispatch_dim<K_ABS>(d, f);
+    case K_P3: return zh_dispatch_dim<K_P3>(d, f);
+    case K_P4: return zh_dispatch_dim<K_P4>(d, f);
+    case K_HAMM: return zh_dispatch_dim<K_HAMM>(d, f);
+    case K_PP: return zh_dispatch_dim<K_PP>(d, f);
+    default: return zh_dispatch_dim<K_L2>(d, f);
+    }
+}
+
 __device__ __forceinline__ float powi_f32(float a, int b) {  // compiler-rt __powisf2 (Rust f32::powi)
     const bool recip = b < 0;
     float r = 1.0f;

@@ -90,55 +90,18 @@ __global__ __launch_bounds__(256) void exact_score_generic_kernel(const float *_
     }
 }
 
-template <int D, int KIND>
-static hipError_t launch_score_d(const float *dX, const uint32_t *dLive, uint64_t p0, uint32_t nr, const float *dQ, const float *dQQ,
-                                 uint32_t B, int metric, int param, uint64_t *dKeys, uint64_t ld, hipStream_t s) {
-    const uint32_t blocks = (nr + 4 * EXR - 1) / (4 * EXR);
-    hipLaunchKernelGGL((exact_score_kernel<D, KIND>), dim3(blocks), dim3(256), 0, s, dX, dLive, p0, nr, dQ, dQQ, B, metric, param, dKeys, ld);
-    return hipGetLastError();
-}
-
-template <int KIND>
-static hipError_t launch_score_kind(const float *dX, uint32_t d, const uint32_t *dLive, uint64_t p0, uint32_t nr, const float *dQ,
-                                    const float *dQQ, uint32_t B, int metric, int param, uint64_t *dKeys, uint64_t ld, hipStream_t s) {
-#define ZH_EX_CASE(DD) case DD: return launch_score_d<DD, KIND>(dX, dLive, p0, nr, dQ, dQQ, B, metric, param, dKeys, ld, s)
-    if constexpr (KIND == K_L2 || KIND == K_COS) {
-        switch (d) {
-            ZH_EX_CASE(256);
-            ZH_EX_CASE(512);
-            ZH_EX_CASE(1024);
-        default: break;
-        }
-    }
-    switch (d) {
-        ZH_EX_CASE(128);
-        ZH_EX_CASE(384);
-        ZH_EX_CASE(768);
-    default: break;
-    }
-#undef ZH_EX_CASE
-    hipLaunchKernelGGL(exact_score_generic_kernel<KIND>, dim3((nr + 3) / 4), dim3(256), 0, s, dX, d, dLive, p0, nr, dQ, dQQ, B, metric, param,
-                       dKeys, ld);
-    return hipGetLastError();
-}
-
 hipError_t zh_launch_exact_score(const float *dX, uint32_t d, const uint32_t *dLive, uint64_t p0, uint32_t nr, const float *dQ,
                                  const float *dQQ, uint32_t B, int metric, int param, uint64_t *dKeys, uint64_t ld, hipStream_t s) {
     if (!nr || !B) return hipSuccess;
-#define ZH_EX_KIND(K) case K: return launch_score_kind<K>(dX, d, dLive, p0, nr, dQ, dQQ, B, metric, param, dKeys, ld, s)
-    switch (zh_kind_of(metric)) {
-        ZH_EX_KIND(K_COS);
-        ZH_EX_KIND(K_MAX);
-        ZH_EX_KIND(K_CANB);
-        ZH_EX_KIND(K_BRAY);
-        ZH_EX_KIND(K_ABS);
-        ZH_EX_KIND(K_P3);
-        ZH_EX_KIND(K_P4);
-        ZH_EX_KIND(K_HAMM);
-        ZH_EX_KIND(K_PP);
-    default: return launch_score_kind<K_L2>(dX, d, dLive, p0, nr, dQ, dQQ, B, metric, param, dKeys, ld, s);
-    }
-#undef ZH_EX_KIND
+    return zh_dispatch_kind_dim(metric, d, [&](auto kind, auto dim) {
+        constexpr int KIND = decltype(kind)::value, D = decltype(dim)::value;
+        if constexpr (D > 0)
+            hipLaunchKernelGGL((exact_score_kernel<D, KIND>), dim3((nr + 4 * EXR - 1) / (4 * EXR)), dim3(256), 0, s, dX, dLive, p0, nr, dQ, dQQ, B, metric, param,
+                               dKeys, ld);
+        else
+            hipLaunchKernelGGL(exact_score_generic_kernel<KIND>, dim3((nr + 3) / 4), dim3(256), 0, s, dX, d, dLive, p0, nr, dQ, dQQ, B, metric, param, dKeys, ld);
+        return hipGetLastError();
+    });
 }
 
 // One "visit" per (query, sub-chunk of L positions): select_kernel keeps its take = min(k, len) smallest (key, id), final_kernel

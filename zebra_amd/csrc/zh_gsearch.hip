@@ -15,7 +15,10 @@
 //                    and every candidate finds its place in the union by counting: the candidates below it (one broadcast pass over the at most
 //                    256 of them) plus, for a candidate, the beam entries below it (a binary search of the sorted beam) -- all (key, row) pairs are
 //                    distinct, so the counts are a permutation; what lands below `beam` is written there.  No sort: eight barriers an iteration.
-#include "zh_refine_dev.h"  // refine_key, RF_NONE, ZH_REFINE_INFLIGHT: the key of a gathered row against a row held in registers
+// Step (5) is refine_key_list's loop (zh_refine_dev.h) written out here, with >> 1 on the id word: shared, gsearch_kernel<1024, K_COS> lost an
+// occupancy step or the width-4 searches 1 to 2 % of their speed, depending on the row a slot past the list reloads.  The key itself
+// is the shared refine_key.
+#include "zh_refine_dev.h"  // refine_key, RowRegs, RF_NONE, ZH_REFINE_INFLIGHT: the key of a gathered row against a row held in registers
 
 #define GS_SLOTS ZH_GRAPH_MAX_BEAM  // beam slots, and candidate slots behind them (width * g_k <= 256, seeds <= 64)
 static_assert(GS_SLOTS == 256, "one thread per beam slot and per candidate slot");
@@ -37,7 +40,7 @@ __global__ __launch_bounds__(256) void gsearch_kernel(const float *__restrict__ 
     const size_t b = blockIdx.x;
     const float *q = Q + b * d;
     const float qq = KIND == K_COS ? QQ[b] : 0.f;
-    float4 qreg[D > 0 ? RowVec<(D > 0 ? D : 256)>::NV : 1];
+    RowRegs<D> qreg;
     if constexpr (D > 0) load_row<D>(q, lane, qreg);
     uint64_t *ckey = s_key + GS_SLOTS;
     uint32_t *cid = s_id + GS_SLOTS;
@@ -179,66 +182,17 @@ __global__ __launch_bounds__(256) void gsearch_kernel(const float *__restrict__ 
     }
 }
 
-#define GS_ARGS_DECL \
-    const float *dX, uint32_t d, uint64_t n_rows, const uint32_t *dTab, uint64_t g_rows, uint32_t g_k, const uint32_t *dBits, const float *dQ, const float *dQQ, \
-    const uint64_t *dSeeds, uint32_t n_seed, uint32_t B, uint64_t id_base, uint32_t top_k, uint32_t beam, uint32_t width, uint32_t max_iters, int metric, \
-    int param, uint64_t *dOutIds, uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s
-
-template <int D, int KIND>
-static hipError_t launch_gsearch_d(GS_ARGS_DECL) {
-    hipLaunchKernelGGL((gsearch_kernel<D, KIND>), dim3(B), dim3(256), 0, s, dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ, dSeeds, n_seed, id_base, top_k, beam,
-                       width, max_iters, metric, param, dOutIds, dOutKeys, dOutCounts, dCtr);
-    return hipGetLastError();
-}
-
-// the dimensions zh_launch_refine_lines specialises: 128 / 384 / 768 for every kind, 256 / 512 / 1024 as well for the two simsimd kinds
-template <int KIND>
-static hipError_t launch_gsearch_kind(GS_ARGS_DECL) {
-#define ZH_GS_CASE(DD) \
-    case DD: \
-        return launch_gsearch_d<DD, KIND>(dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ, dSeeds, n_seed, B, id_base, top_k, beam, width, max_iters, metric, param, \
-                                          dOutIds, dOutKeys, dOutCounts, dCtr, s)
-    if constexpr (KIND == K_L2 || KIND == K_COS) {
-        switch (d) {
-            ZH_GS_CASE(256);
-            ZH_GS_CASE(512);
-            ZH_GS_CASE(1024);
-        default: break;
-        }
-    }
-    switch (d) {
-        ZH_GS_CASE(128);
-        ZH_GS_CASE(384);
-        ZH_GS_CASE(768);
-    default: break;
-    }
-#undef ZH_GS_CASE
-    return launch_gsearch_d<0, KIND>(dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ, dSeeds, n_seed, B, id_base, top_k, beam, width, max_iters, metric, param,
-                                     dOutIds, dOutKeys, dOutCounts, dCtr, s);
-}
-
-hipError_t zh_launch_gsearch(GS_ARGS_DECL) {
+hipError_t zh_launch_gsearch(const float *dX, uint32_t d, uint64_t n_rows, const uint32_t *dTab, uint64_t g_rows, uint32_t g_k, const uint32_t *dBits,
+                             const float *dQ, const float *dQQ, const uint64_t *dSeeds, uint32_t n_seed, uint32_t B, uint64_t id_base, uint32_t top_k,
+                             uint32_t beam, uint32_t width, uint32_t max_iters, int metric, int param, uint64_t *dOutIds, uint64_t *dOutKeys,
+                             uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s) {
     if (!B) return hipSuccess;
     if (!g_k || g_k > ZH_REFINE_MAX_IN_K || !width || (uint64_t)width * g_k > GS_SLOTS || !n_seed || n_seed > ZH_GRAPH_MAX_SEEDS || !top_k || top_k > beam ||
         beam > ZH_GRAPH_MAX_BEAM || n_rows >= (1ull << 31))
         return hipErrorInvalidValue;
-#define ZH_GS_KIND(K) \
-    case K: \
-        return launch_gsearch_kind<K>(dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ, dSeeds, n_seed, B, id_base, top_k, beam, width, max_iters, metric, param, \
-                                      dOutIds, dOutKeys, dOutCounts, dCtr, s)
-    switch (zh_kind_of(metric)) {
-        ZH_GS_KIND(K_COS);
-        ZH_GS_KIND(K_MAX);
-        ZH_GS_KIND(K_CANB);
-        ZH_GS_KIND(K_BRAY);
-        ZH_GS_KIND(K_ABS);
-        ZH_GS_KIND(K_P3);
-        ZH_GS_KIND(K_P4);
-        ZH_GS_KIND(K_HAMM);
-        ZH_GS_KIND(K_PP);
-    default:
-        return launch_gsearch_kind<K_L2>(dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ, dSeeds, n_seed, B, id_base, top_k, beam, width, max_iters, metric, param,
-                                         dOutIds, dOutKeys, dOutCounts, dCtr, s);
-    }
-#undef ZH_GS_KIND
+    return zh_dispatch_kind_dim(metric, d, [&](auto kind, auto dim) {
+        hipLaunchKernelGGL((gsearch_kernel<decltype(dim)::value, decltype(kind)::value>), dim3(B), dim3(256), 0, s, dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ,
+                           dSeeds, n_seed, id_base, top_k, beam, width, max_iters, metric, param, dOutIds, dOutKeys, dOutCounts, dCtr);
+        return hipGetLastError();
+    });
 }

@@ -488,6 +488,16 @@ hipError_t zh_launch_fknn_mark(const uint32_t *dHRow, uint32_t B, uint64_t first
 #define ZH_REFINE_SLAB 65536u      // stored rows of a sub-slab: one launch of the line kernel
 #define ZH_REFINE_CAP_SMALL 2048u  // candidate slots of the small instantiation of the line kernel (in_k + in_k^2 <= 2048: in_k <= 44) ...
 #define ZH_REFINE_CAP_LARGE 8192u  // ... and of the large one (in_k <= ZH_REFINE_MAX_IN_K)
+// The graph family's wave-per-line kernels (a 256-thread block serves 4 lines) take at most ZH_LINES_PER_LAUNCH lines a launch: 2^30 threads.
+#define ZH_LINES_PER_LAUNCH (1ull << 24)
+inline uint64_t zh_line_launches(uint64_t n) { return (n + ZH_LINES_PER_LAUNCH - 1) / ZH_LINES_PER_LAUNCH; }  // launches that n lines take
+template <class F>
+inline void zh_for_line_pieces(uint64_t n, F f) {  // f(b0, m, blocks): the lines [b0, b0 + m) in one launch of `blocks` blocks
+    for (uint64_t b0 = 0; b0 < n; b0 += ZH_LINES_PER_LAUNCH) {
+        const uint64_t m = n - b0 < ZH_LINES_PER_LAUNCH ? n - b0 : ZH_LINES_PER_LAUNCH;
+        f(b0, m, (uint32_t)((m + 3) / 4));
+    }
+}
 // lines [l0, l0 + nl) of the input graph (dIn holds THEIR in_k entries each, from its start) into the table dTab [stored rows][in_k] of row numbers:
 // UINT32_MAX for an entry past the line's count, outside [id_base, id_base + n_rows), not live by dBits, or equal to an earlier entry of its line
 hipError_t zh_launch_refine_rows(const uint64_t *dIn, const uint32_t *dCounts, const uint32_t *dBits, uint64_t id_base, uint64_t n_rows, uint32_t in_k,

@@ -13,10 +13,13 @@
 //   nnd_plan_kernel   a wave per live line: the exact raw gather count (per own entry: 1 + w if new, popcount(mask(e)) if old); 0 -> the line is
 //                     copied across; otherwise its row goes on the list -- from the front if the count fits ZH_REFINE_CAP_SMALL, from the back if not
 //   nnd_line_kernel   256-thread blocks striding over one half of the list (the counts are read on the device: no readback before the launch),
-//                     refine_line_kernel's stages: gather into LDS, sort, compact the distinct rows that the forward line does not hold, key them
-//                     (refine_key: the SAME arithmetic), sort by (key, id), merge the best 64 with the forward line in a 128-slot sort, write the
-//                     first k row numbers and keys to the OTHER table (never in place: other blocks read this round's lines meanwhile)
+//                     refine_line_kernel's stages: gather into LDS, sort, compact the distinct rows that the forward line does not hold
+//                     (refine_compact, the drop bitmap its predicate), key them (refine_key_list: the SAME routine, so the same arithmetic), sort
+//                     by (key, id), merge the best 64 with the forward line in a 128-slot sort, write the first k row numbers and keys to the
+//                     OTHER table (never in place: other blocks read this round's lines meanwhile)
 //   nnd_emit_kernel   at the end: row numbers -> ids with id_base, tails 2^64 - 1, counts
+// The wave-per-line kernels are launched ZH_LINES_PER_LAUNCH lines at a time (zh_for_line_pieces); nnd_line_kernel's instantiation is
+// zh_dispatch_kind_dim's (zh_device.h).  DESIGN.md s25.
 #include "zh_refine_dev.h"
 
 // a wave per line, lane j its entry j (k <= 64)
@@ -89,7 +92,6 @@ __global__ __launch_bounds__(256) void nnd_line_kernel(const float *__restrict__
                                                        const uint64_t *__restrict__ mask, const uint64_t *__restrict__ keys, const float *__restrict__ QQ,
                                                        const uint32_t *__restrict__ list, uint64_t n_live, int metric, int param,
                                                        uint32_t *__restrict__ tab_next, uint64_t *__restrict__ keys_next, unsigned long long *__restrict__ ctr) {
-    constexpr int R = ZH_REFINE_INFLIGHT;
     constexpr bool LARGE = CAP > ZH_REFINE_CAP_SMALL;
     __shared__ uint64_t s_key[CAP];
     __shared__ uint32_t s_id[CAP];
@@ -156,60 +158,14 @@ __global__ __launch_bounds__(256) void nnd_line_kernel(const float *__restrict__
             }
         }
         __syncthreads();
-        // the first entry of every row number that is not marked, compacted to the front (refine_line_kernel's scan)
-        constexpr uint32_t PER = CAP / 256;
-        uint32_t *tmp = reinterpret_cast<uint32_t *>(s_key);  // (the keys come later)
-        mine = 0;
-        for (uint32_t j = 0; j < PER; j++) {
-            const uint32_t i = tid * PER + j;
-            if (i < np2 && s_id[i] != RF_NONE && (i == 0 || s_id[i] != s_id[i - 1]) && !((s_drop[i >> 5] >> (i & 31)) & 1u)) mine++;
-        }
-        s_scan[tid] = mine;
-        __syncthreads();
-        for (uint32_t o = 1; o < 256; o <<= 1) {
-            const uint32_t t = tid >= o ? s_scan[tid - o] : 0;
-            __syncthreads();
-            s_scan[tid] += t;
-            __syncthreads();
-        }
-        const uint32_t S = s_scan[255];
-        uint32_t rank = s_scan[tid] - mine;
-        for (uint32_t j = 0; j < PER; j++) {
-            const uint32_t i = tid * PER + j;
-            if (i < np2 && s_id[i] != RF_NONE && (i == 0 || s_id[i] != s_id[i - 1]) && !((s_drop[i >> 5] >> (i & 31)) & 1u)) tmp[rank++] = s_id[i];
-        }
-        __syncthreads();
-        const uint32_t up2 = next_pow2(S);  // (<= np2 <= CAP)
-        for (uint32_t i = tid; i < up2; i += 256) s_id[i] = i < S ? tmp[i] : RF_NONE;
-        __syncthreads();  // (tmp is read: its words become the keys)
-        for (uint32_t i = S + tid; i < up2; i += 256) s_key[i] = ~0ull;
+        // the first entry of every row number that is not marked, compacted to the front
+        const uint32_t S = refine_compact<CAP>(s_id, s_key, s_scan, np2, [&](uint32_t i) { return !((s_drop[i >> 5] >> (i & 31)) & 1u); }), up2 = next_pow2(S);
         // ---- (b) the keys of S(a): wave wv takes candidates 4 R t + 4 c + wv, c < R at a time
         if (S) {  // (block-uniform)
             const float *q = X + (size_t)a * d;
-            const float qq = KIND == K_COS ? QQ[a] : 0.f;
-            if constexpr (D > 0) {
-                constexpr int NV = RowVec<D>::NV;
-                float4 qreg[NV];
-                load_row<D>(q, lane, qreg);
-                for (uint32_t i0 = wv; i0 < S; i0 += 4 * R) {
-                    float4 v[R][NV];
-#pragma unroll
-                    for (int c = 0; c < R; c++) {
-                        const uint32_t i = i0 + 4 * c < S ? i0 + 4 * c : S - 1;  // (a slot past the list loads the last row again: straight-line loads)
-                        load_row<D>(X + (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_id[i]) * D, lane, v[c]);
-                    }
-#pragma unroll
-                    for (int c = 0; c < R; c++) {
-                        const uint64_t key = refine_key<D, KIND>(v[c], nullptr, q, qreg, qq, d, lane, metric, param);
-                        if (lane == 0 && i0 + 4 * c < S) s_key[i0 + 4 * c] = key;
-                    }
-                }
-            } else {
-                for (uint32_t i = wv; i < S; i += 4) {
-                    const uint64_t key = refine_key<0, KIND>(nullptr, X + (size_t)s_id[i] * d, q, nullptr, qq, d, lane, metric, param);
-                    if (lane == 0) s_key[i] = key;
-                }
-            }
+            RowRegs<D> qreg;
+            if constexpr (D > 0) load_row<D>(q, lane, qreg);
+            refine_key_list<D, KIND>(X, d, s_id, S, q, qreg, KIND == K_COS ? QQ[a] : 0.f, lane, wv, metric, param, s_key);
             // ---- (c) rank by (key, id); the slots from S to up2 hold (all ones, UINT32_MAX) and stay last
             block_bitonic_sort<uint32_t>(s_key, s_id, up2);
         }
@@ -244,117 +200,55 @@ __global__ __launch_bounds__(256) void nnd_line_kernel(const float *__restrict__
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launchers
-#define NND_STEP (1ull << 24)  // lines of one launch of a wave-per-line kernel: 2^30 threads
-
 hipError_t zh_launch_nnd_rows(const uint64_t *dIds, uint64_t id_base, uint64_t nl, uint32_t k, uint32_t *dTab, hipStream_t s) {
     if (!k || k > ZH_REFINE_MAX_IN_K) return hipErrorInvalidValue;
-    for (uint64_t b0 = 0; b0 < nl; b0 += NND_STEP) {
-        const uint64_t m = std::min<uint64_t>(NND_STEP, nl - b0);
-        hipLaunchKernelGGL(nnd_rows_kernel, dim3((uint32_t)((m + 3) / 4)), dim3(256), 0, s, dIds + b0 * k, id_base, m, k, dTab + b0 * k);
-    }
+    zh_for_line_pieces(nl, [&](uint64_t b0, uint64_t m, uint32_t blocks) {
+        hipLaunchKernelGGL(nnd_rows_kernel, dim3(blocks), dim3(256), 0, s, dIds + b0 * k, id_base, m, k, dTab + b0 * k);
+    });
     return hipGetLastError();
 }
 
 hipError_t zh_launch_nnd_emit(const uint32_t *dTab, const uint64_t *dKeys, uint32_t k, uint64_t id_base, uint64_t nl, uint64_t *dOutIds, uint64_t *dOutKeys,
                               uint32_t *dOutCounts, hipStream_t s) {
     if (!k || k > ZH_REFINE_MAX_IN_K) return hipErrorInvalidValue;
-    for (uint64_t b0 = 0; b0 < nl; b0 += NND_STEP) {
-        const uint64_t m = std::min<uint64_t>(NND_STEP, nl - b0);
-        hipLaunchKernelGGL(nnd_emit_kernel, dim3((uint32_t)((m + 3) / 4)), dim3(256), 0, s, dTab + b0 * k, dKeys + b0 * k, k, id_base, m, dOutIds + b0 * k,
-                           dOutKeys + b0 * k, dOutCounts + b0);
-    }
+    zh_for_line_pieces(nl, [&](uint64_t b0, uint64_t m, uint32_t blocks) {
+        hipLaunchKernelGGL(nnd_emit_kernel, dim3(blocks), dim3(256), 0, s, dTab + b0 * k, dKeys + b0 * k, k, id_base, m, dOutIds + b0 * k, dOutKeys + b0 * k,
+                           dOutCounts + b0);
+    });
     return hipGetLastError();
 }
 
 hipError_t zh_launch_nnd_flag(const uint32_t *dPrev, uint32_t wp, const uint32_t *dCur, uint32_t wc, uint64_t n_rows, uint64_t *dMask, hipStream_t s) {
     if (!wp || wp > ZH_REFINE_MAX_IN_K || !wc || wc > ZH_REFINE_MAX_IN_K) return hipErrorInvalidValue;
-    for (uint64_t b0 = 0; b0 < n_rows; b0 += NND_STEP) {
-        const uint64_t m = std::min<uint64_t>(NND_STEP, n_rows - b0);
-        hipLaunchKernelGGL(nnd_flag_kernel, dim3((uint32_t)((m + 3) / 4)), dim3(256), 0, s, dPrev, wp, dCur, wc, b0, m, dMask);
-    }
+    zh_for_line_pieces(n_rows, [&](uint64_t b0, uint64_t m, uint32_t blocks) {
+        hipLaunchKernelGGL(nnd_flag_kernel, dim3(blocks), dim3(256), 0, s, dPrev, wp, dCur, wc, b0, m, dMask);
+    });
     return hipGetLastError();
 }
 
 hipError_t zh_launch_nnd_plan(const uint32_t *dU, uint32_t w, uint32_t k, const uint64_t *dMask, const uint32_t *dRows, uint64_t n_live, const uint64_t *dKeys,
                               uint32_t *dTabNext, uint64_t *dKeysNext, uint32_t *dList, unsigned long long *dCtr, hipStream_t s) {
     if (!k || k > w || w > ZH_REFINE_MAX_IN_K) return hipErrorInvalidValue;
-    for (uint64_t b0 = 0; b0 < n_live; b0 += NND_STEP) {
-        const uint64_t m = std::min<uint64_t>(NND_STEP, n_live - b0);
-        hipLaunchKernelGGL(nnd_plan_kernel, dim3((uint32_t)((m + 3) / 4)), dim3(256), 0, s, dU, w, k, dMask, dRows, b0, m, n_live, dKeys, dTabNext, dKeysNext, dList,
-                           dCtr);
-    }
+    zh_for_line_pieces(n_live, [&](uint64_t b0, uint64_t m, uint32_t blocks) {
+        hipLaunchKernelGGL(nnd_plan_kernel, dim3(blocks), dim3(256), 0, s, dU, w, k, dMask, dRows, b0, m, n_live, dKeys, dTabNext, dKeysNext, dList, dCtr);
+    });
     return hipGetLastError();
 }
-
-struct NndArgs {
-    const float *X;
-    uint32_t d;
-    const uint32_t *U;
-    uint32_t w, k;
-    const uint64_t *mask, *keys;
-    const float *QQ;
-    const uint32_t *list;
-    uint64_t n_live;
-    int metric, param;
-    uint32_t *tab_next;
-    uint64_t *keys_next;
-    unsigned long long *ctr;
-};
 
 // both halves of the list, each by its instantiation; a half that is empty costs blocks that read one counter and leave
-template <int D, int KIND>
-static hipError_t launch_nnd_d(const NndArgs &g, hipStream_t s) {
-    const uint32_t small = (uint32_t)std::min<uint64_t>(g.n_live, 4096), large = (uint32_t)std::min<uint64_t>(g.n_live, 1024);
-    hipLaunchKernelGGL((nnd_line_kernel<D, KIND, ZH_REFINE_CAP_SMALL>), dim3(small), dim3(256), 0, s, g.X, g.d, g.U, g.w, g.k, g.mask, g.keys, g.QQ, g.list, g.n_live,
-                       g.metric, g.param, g.tab_next, g.keys_next, g.ctr);
-    if (g.w + g.w * g.w > ZH_REFINE_CAP_SMALL)  // (otherwise no line's count passes the small one's slots, and the back of the list is empty)
-        hipLaunchKernelGGL((nnd_line_kernel<D, KIND, ZH_REFINE_CAP_LARGE>), dim3(large), dim3(256), 0, s, g.X, g.d, g.U, g.w, g.k, g.mask, g.keys, g.QQ, g.list,
-                           g.n_live, g.metric, g.param, g.tab_next, g.keys_next, g.ctr);
-    return hipGetLastError();
-}
-
-// zh_refine.hip's launch_lines_kind: 128 / 384 / 768 for every kind, 256 / 512 / 1024 as well for the two simsimd kinds
-template <int KIND>
-static hipError_t launch_nnd_kind(const NndArgs &g, hipStream_t s) {
-#define ZH_ND_CASE(DD) \
-    case DD: return launch_nnd_d<DD, KIND>(g, s)
-    if constexpr (KIND == K_L2 || KIND == K_COS) {
-        switch (g.d) {
-            ZH_ND_CASE(256);
-            ZH_ND_CASE(512);
-            ZH_ND_CASE(1024);
-        default: break;
-        }
-    }
-    switch (g.d) {
-        ZH_ND_CASE(128);
-        ZH_ND_CASE(384);
-        ZH_ND_CASE(768);
-    default: break;
-    }
-#undef ZH_ND_CASE
-    return launch_nnd_d<0, KIND>(g, s);
-}
-
 hipError_t zh_launch_nnd_lines(const float *dX, uint32_t d, const uint32_t *dU, uint32_t w, uint32_t k, const uint64_t *dMask, const uint64_t *dKeys, const float *dQQ,
                                const uint32_t *dList, uint64_t n_live, int metric, int param, uint32_t *dTabNext, uint64_t *dKeysNext, unsigned long long *dCtr,
                                hipStream_t s) {
     if (!n_live) return hipSuccess;
     if (!k || k > w || w > ZH_REFINE_MAX_IN_K || w + w * w > ZH_REFINE_CAP_LARGE) return hipErrorInvalidValue;
-    const NndArgs g{dX, d, dU, w, k, dMask, dKeys, dQQ, dList, n_live, metric, param, dTabNext, dKeysNext, dCtr};
-#define ZH_ND_KIND(K) \
-    case K: return launch_nnd_kind<K>(g, s)
-    switch (zh_kind_of(metric)) {
-        ZH_ND_KIND(K_COS);
-        ZH_ND_KIND(K_MAX);
-        ZH_ND_KIND(K_CANB);
-        ZH_ND_KIND(K_BRAY);
-        ZH_ND_KIND(K_ABS);
-        ZH_ND_KIND(K_P3);
-        ZH_ND_KIND(K_P4);
-        ZH_ND_KIND(K_HAMM);
-        ZH_ND_KIND(K_PP);
-    default: return launch_nnd_kind<K_L2>(g, s);
-    }
-#undef ZH_ND_KIND
+    const uint32_t small = (uint32_t)std::min<uint64_t>(n_live, 4096), large = (uint32_t)std::min<uint64_t>(n_live, 1024);
+    return zh_dispatch_kind_dim(metric, d, [&](auto kind, auto dim) {
+        constexpr int KIND = decltype(kind)::value, D = decltype(dim)::value;
+        hipLaunchKernelGGL((nnd_line_kernel<D, KIND, ZH_REFINE_CAP_SMALL>), dim3(small), dim3(256), 0, s, dX, d, dU, w, k, dMask, dKeys, dQQ, dList, n_live, metric, param,
+                           dTabNext, dKeysNext, dCtr);
+        if (w + w * w > ZH_REFINE_CAP_SMALL)  // (otherwise no line's count passes the small one's slots, and the back of the list is empty)
+            hipLaunchKernelGGL((nnd_line_kernel<D, KIND, ZH_REFINE_CAP_LARGE>), dim3(large), dim3(256), 0, s, dX, d, dU, w, k, dMask, dKeys, dQQ, dList, n_live, metric,
+                               param, dTabNext, dKeysNext, dCtr);
+        return hipGetLastError();
+    });
 }

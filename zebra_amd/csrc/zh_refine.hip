@@ -11,7 +11,9 @@
 //                        (c) block_bitonic_sort by (key, id), the first min(k, U) written with id_base, tails and the count; `updates` = written
 //                        rows that N'(a) does not hold.  The table may be zh_reverse.hip's union table (N'(x) then the kept reverse
 //                        neighbours, in_k + rev_k wide): in_k is then that width, and N'(a) the line's first fwd_k entries.
-#include "zh_refine_dev.h"  // refine_key, block_bitonic_sort_u32, block_sum_u32, RF_NONE, ZH_REFINE_INFLIGHT: shared with zh_nnd.hip
+// The compaction of (a) and the keying stage (b) are zh_refine_dev.h's refine_compact and refine_key_list, shared with nnd_line_kernel; which
+// instantiation a call gets is zh_dispatch_kind_dim's table (zh_device.h).  DESIGN.md s25.
+#include "zh_refine_dev.h"  // refine_key_list, refine_compact, block_bitonic_sort_u32, block_sum_u32, RF_NONE, ZH_REFINE_INFLIGHT
 
 // a wave per line, lane j its entry j (in_k <= 64)
 __global__ __launch_bounds__(256) void refine_rows_kernel(const uint64_t *__restrict__ in, const uint32_t *__restrict__ counts,
@@ -38,12 +40,9 @@ __global__ __launch_bounds__(256) void refine_rows_kernel(const uint64_t *__rest
 hipError_t zh_launch_refine_rows(const uint64_t *dIn, const uint32_t *dCounts, const uint32_t *dBits, uint64_t id_base, uint64_t n_rows, uint32_t in_k,
                                  uint64_t l0, uint64_t nl, uint32_t *dTab, hipStream_t s) {
     if (!in_k || in_k > ZH_REFINE_MAX_IN_K) return hipErrorInvalidValue;
-    const uint64_t step = 1ull << 24;  // lines of one launch: 2^30 threads
-    for (uint64_t b0 = 0; b0 < nl; b0 += step) {
-        const uint64_t m = nl - b0 < step ? nl - b0 : step;
-        hipLaunchKernelGGL(refine_rows_kernel, dim3((uint32_t)((m + 3) / 4)), dim3(256), 0, s, dIn + b0 * in_k, dCounts, dBits, id_base, n_rows, in_k, l0 + b0, m,
-                           dTab);
-    }
+    zh_for_line_pieces(nl, [&](uint64_t b0, uint64_t m, uint32_t blocks) {
+        hipLaunchKernelGGL(refine_rows_kernel, dim3(blocks), dim3(256), 0, s, dIn + b0 * in_k, dCounts, dBits, id_base, n_rows, in_k, l0 + b0, m, dTab);
+    });
     return hipGetLastError();
 }
 
@@ -53,7 +52,6 @@ __global__ __launch_bounds__(256) void refine_line_kernel(const float *__restric
                                                           int metric, int param, uint64_t id_base, uint64_t first_row, uint32_t k,
                                                           uint64_t *__restrict__ out_ids, uint64_t *__restrict__ out_keys, uint32_t *__restrict__ out_counts,
                                                           unsigned long long *__restrict__ ctr) {
-    constexpr int R = ZH_REFINE_INFLIGHT;
     __shared__ uint64_t s_key[CAP];
     __shared__ uint32_t s_id[CAP];
     __shared__ uint32_t s_own[ZH_REFINE_MAX_IN_K], s_scan[256], s_red[4];
@@ -76,60 +74,14 @@ __global__ __launch_bounds__(256) void refine_line_kernel(const float *__restric
     }
     const uint32_t listed = block_sum_u32(mine, s_red);
     block_bitonic_sort_u32(s_id, np2);
-    // the first entry of every row number, compacted to the front: a thread counts its stretch, the stretches' exclusive sums, then the ranks
-    constexpr uint32_t PER = CAP / 256;
-    uint32_t *tmp = reinterpret_cast<uint32_t *>(s_key);  // (the keys come later)
-    mine = 0;
-    for (uint32_t j = 0; j < PER; j++) {
-        const uint32_t i = tid * PER + j;
-        if (i < np2 && s_id[i] != RF_NONE && (i == 0 || s_id[i] != s_id[i - 1])) mine++;
-    }
-    s_scan[tid] = mine;
-    __syncthreads();
-    for (uint32_t o = 1; o < 256; o <<= 1) {
-        const uint32_t t = tid >= o ? s_scan[tid - o] : 0;
-        __syncthreads();
-        s_scan[tid] += t;
-        __syncthreads();
-    }
-    const uint32_t U = s_scan[255];
-    uint32_t rank = s_scan[tid] - mine;
-    for (uint32_t j = 0; j < PER; j++) {
-        const uint32_t i = tid * PER + j;
-        if (i < np2 && s_id[i] != RF_NONE && (i == 0 || s_id[i] != s_id[i - 1])) tmp[rank++] = s_id[i];
-    }
-    __syncthreads();
-    const uint32_t up2 = next_pow2(U);  // (<= np2 <= CAP)
-    for (uint32_t i = tid; i < up2; i += 256) s_id[i] = i < U ? tmp[i] : RF_NONE;
-    __syncthreads();  // (tmp is read: its words become the keys)
-    for (uint32_t i = U + tid; i < up2; i += 256) s_key[i] = ~0ull;
+    // the first entry of every row number, compacted to the front
+    const uint32_t U = refine_compact<CAP>(s_id, s_key, s_scan, np2, [](uint32_t) { return true; }), up2 = next_pow2(U);
     // ---- (b) the keys: wave wv takes candidates 4 R t + 4 c + wv, c < R at a time
     if (U) {  // (block-uniform)
         const float *q = Q + (size_t)b * d;
-        const float qq = KIND == K_COS ? QQ[b] : 0.f;
-        if constexpr (D > 0) {
-            constexpr int NV = RowVec<D>::NV;
-            float4 qreg[NV];
-            load_row<D>(q, lane, qreg);
-            for (uint32_t i0 = wv; i0 < U; i0 += 4 * R) {
-                float4 v[R][NV];
-#pragma unroll
-                for (int c = 0; c < R; c++) {
-                    const uint32_t i = i0 + 4 * c < U ? i0 + 4 * c : U - 1;  // (a slot past the list loads the last row again: straight-line loads)
-                    load_row<D>(X + (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_id[i]) * D, lane, v[c]);
-                }
-#pragma unroll
-                for (int c = 0; c < R; c++) {
-                    const uint64_t key = refine_key<D, KIND>(v[c], nullptr, q, qreg, qq, d, lane, metric, param);
-                    if (lane == 0 && i0 + 4 * c < U) s_key[i0 + 4 * c] = key;
-                }
-            }
-        } else {
-            for (uint32_t i = wv; i < U; i += 4) {
-                const uint64_t key = refine_key<0, KIND>(nullptr, X + (size_t)s_id[i] * d, q, nullptr, qq, d, lane, metric, param);
-                if (lane == 0) s_key[i] = key;
-            }
-        }
+        RowRegs<D> qreg;
+        if constexpr (D > 0) load_row<D>(q, lane, qreg);
+        refine_key_list<D, KIND>(X, d, s_id, U, q, qreg, KIND == K_COS ? QQ[b] : 0.f, lane, wv, metric, param, s_key);
     }
     // ---- (c) rank by (key, id); the slots from U to up2 hold (all ones, UINT32_MAX) and stay last
     block_bitonic_sort<uint32_t>(s_key, s_id, up2);
@@ -156,62 +108,19 @@ __global__ __launch_bounds__(256) void refine_line_kernel(const float *__restric
     }
 }
 
-template <int D, int KIND>
-static hipError_t launch_lines_d(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, uint32_t fwd_k, const uint32_t *dRows, uint32_t B, const float *dQ,
-                                 const float *dQQ, int metric, int param, uint64_t id_base, uint64_t first_row, uint32_t k, uint64_t *dOutIds,
-                                 uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s) {
-    if (in_k + in_k * in_k <= ZH_REFINE_CAP_SMALL)
-        hipLaunchKernelGGL((refine_line_kernel<D, KIND, ZH_REFINE_CAP_SMALL>), dim3(B), dim3(256), 0, s, dX, d, dTab, in_k, fwd_k, dRows, dQ, dQQ, metric, param, id_base,
-                           first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr);
-    else
-        hipLaunchKernelGGL((refine_line_kernel<D, KIND, ZH_REFINE_CAP_LARGE>), dim3(B), dim3(256), 0, s, dX, d, dTab, in_k, fwd_k, dRows, dQ, dQQ, metric, param, id_base,
-                           first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr);
-    return hipGetLastError();
-}
-
-// the dimensions zh_launch_exact_score specialises: 128 / 384 / 768 for every kind, 256 / 512 / 1024 as well for the two simsimd kinds
-template <int KIND>
-static hipError_t launch_lines_kind(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, uint32_t fwd_k, const uint32_t *dRows, uint32_t B, const float *dQ,
-                                    const float *dQQ, int metric, int param, uint64_t id_base, uint64_t first_row, uint32_t k, uint64_t *dOutIds,
-                                    uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s) {
-#define ZH_RF_CASE(DD) \
-    case DD: return launch_lines_d<DD, KIND>(dX, d, dTab, in_k, fwd_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s)
-    if constexpr (KIND == K_L2 || KIND == K_COS) {
-        switch (d) {
-            ZH_RF_CASE(256);
-            ZH_RF_CASE(512);
-            ZH_RF_CASE(1024);
-        default: break;
-        }
-    }
-    switch (d) {
-        ZH_RF_CASE(128);
-        ZH_RF_CASE(384);
-        ZH_RF_CASE(768);
-    default: break;
-    }
-#undef ZH_RF_CASE
-    return launch_lines_d<0, KIND>(dX, d, dTab, in_k, fwd_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s);
-}
-
 hipError_t zh_launch_refine_lines(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t in_k, uint32_t fwd_k, const uint32_t *dRows, uint32_t B, const float *dQ,
                                   const float *dQQ, int metric, int param, uint64_t id_base, uint64_t first_row, uint32_t k, uint64_t *dOutIds,
                                   uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s) {
     if (!B) return hipSuccess;
     if (!in_k || in_k > ZH_REFINE_MAX_IN_K || in_k + in_k * in_k > ZH_REFINE_CAP_LARGE || fwd_k > in_k || !k) return hipErrorInvalidValue;
-#define ZH_RF_KIND(K) \
-    case K: return launch_lines_kind<K>(dX, d, dTab, in_k, fwd_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s)
-    switch (zh_kind_of(metric)) {
-        ZH_RF_KIND(K_COS);
-        ZH_RF_KIND(K_MAX);
-        ZH_RF_KIND(K_CANB);
-        ZH_RF_KIND(K_BRAY);
-        ZH_RF_KIND(K_ABS);
-        ZH_RF_KIND(K_P3);
-        ZH_RF_KIND(K_P4);
-        ZH_RF_KIND(K_HAMM);
-        ZH_RF_KIND(K_PP);
-    default: return launch_lines_kind<K_L2>(dX, d, dTab, in_k, fwd_k, dRows, B, dQ, dQQ, metric, param, id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr, s);
-    }
-#undef ZH_RF_KIND
+    return zh_dispatch_kind_dim(metric, d, [&](auto kind, auto dim) {
+        constexpr int KIND = decltype(kind)::value, D = decltype(dim)::value;
+        if (in_k + in_k * in_k <= ZH_REFINE_CAP_SMALL)
+            hipLaunchKernelGGL((refine_line_kernel<D, KIND, ZH_REFINE_CAP_SMALL>), dim3(B), dim3(256), 0, s, dX, d, dTab, in_k, fwd_k, dRows, dQ, dQQ, metric, param,
+                               id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr);
+        else
+            hipLaunchKernelGGL((refine_line_kernel<D, KIND, ZH_REFINE_CAP_LARGE>), dim3(B), dim3(256), 0, s, dX, d, dTab, in_k, fwd_k, dRows, dQ, dQQ, metric, param,
+                               id_base, first_row, k, dOutIds, dOutKeys, dOutCounts, dCtr);
+        return hipGetLastError();
+    });
 }

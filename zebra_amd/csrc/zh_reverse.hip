@@ -288,11 +288,9 @@ hipError_t zh_launch_reverse_select(const uint32_t *dTab, uint32_t in_k, uint32_
     hipError_t e;
     if ((e = hipMemsetAsync(&dCtr[3], 0, 8, s)) != hipSuccess) return e;
     const RevOut o{dUni, dOutIds, dOutCounts, dOutDegree, first_row, n, id_base};
-    const uint64_t step = 1ull << 24;  // lines of one launch: 2^30 threads
-    for (uint64_t b0 = 0; b0 < nx; b0 += step) {
-        const uint64_t m = std::min(step, nx - b0);
-        hipLaunchKernelGGL(rev_select_kernel, dim3((uint32_t)((m + 3) / 4)), dim3(256), 0, s, dTab, in_k, rev_k, dOff, dCsr, x0 + b0, m, o, dHeavy, dCtr);
-    }
+    zh_for_line_pieces(nx, [&](uint64_t b0, uint64_t m, uint32_t blocks) {
+        hipLaunchKernelGGL(rev_select_kernel, dim3(blocks), dim3(256), 0, s, dTab, in_k, rev_k, dOff, dCsr, x0 + b0, m, o, dHeavy, dCtr);
+    });
     const uint64_t cap = std::min(nx, n_rows * in_k / ZH_REVERSE_HEAVY) + 1;  // (the list's lines share the table's n_rows in_k entries)
     hipLaunchKernelGGL(rev_select_heavy_kernel, dim3((uint32_t)std::min<uint64_t>(cap, 2048)), dim3(256), 0, s, dTab, in_k, rev_k, dOff, dCsr, o, dHeavy, dCtr);
     return hipGetLastError();

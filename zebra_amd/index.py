@@ -653,6 +653,21 @@ class LSHIndex:
         survivors, redone, launches, tiles"""
         return self._info(_ffi.KnnForestInfo, lib().zh_knn_graph_forest_info)
 
+    def _graph_arrays(self, graph, who, cover=True):
+        """an input graph -- (ids, counts) or a graph call's 3-tuple -- as contiguous (in_ids u64 [lines, in_k], in_counts u32 [lines]) and the
+        number of stored rows; cover: the lines must be the stored rows (otherwise the rows are not asked for: None)"""
+        in_ids = np.ascontiguousarray(graph[0], np.uint64)
+        in_counts = np.ascontiguousarray(graph[-1], np.uint32)
+        shaped = in_ids.ndim == 2 and in_counts.ndim == 1
+        if not cover:
+            if not shaped:
+                raise _ffi.ZhError(_ffi.ZH_EINVAL, "%s: the graph is ids [g_rows, g_k] and counts [g_rows]" % who)
+            return in_ids, in_counts, None
+        stored = self.stored_rows()
+        if not shaped or in_ids.shape[0] != stored or in_counts.shape[0] != stored:
+            raise _ffi.ZhError(_ffi.ZH_EINVAL, "%s: the graph must cover the %d stored rows: ids [%d, in_k], counts [%d]" % (who, stored, stored, stored))
+        return in_ids, in_counts, stored
+
     def knn_graph_refine(self, graph, k, metric, first_row=0, n=None, rounds=1, reverse=0):
         """one join round of NN-descent over a graph of ALL stored rows: `graph` is (ids [stored rows, in_k] u64, counts [stored rows] u32) or the
         3-tuple knn_graph / knn_graph_forest return (its keys are not read: every returned key is computed here).  Line i of the answer holds the
@@ -662,12 +677,7 @@ class LSHIndex:
         layout.  No forest needed.  reverse > 0: every round also ranks up to `reverse` sampled reverse neighbours of each row (the rows that
         name it, knn_graph_reverse) and THEIR lists -- zh_knn_graph_refine_rev, in_k + reverse <= 64; knn_refine_rev_info() then describes the
         call, and its 'updates' is the early stop.  reverse = 0 is today's call and path exactly."""
-        in_ids, in_counts = (graph[0], graph[-1])
-        in_ids = np.ascontiguousarray(in_ids, np.uint64)
-        in_counts = np.ascontiguousarray(in_counts, np.uint32)
-        stored = self.stored_rows()
-        if in_ids.ndim != 2 or in_counts.ndim != 1 or in_ids.shape[0] != stored or in_counts.shape[0] != stored:
-            raise _ffi.ZhError(_ffi.ZH_EINVAL, "knn_graph_refine: the graph must cover the %d stored rows: ids [%d, in_k], counts [%d]" % (stored, stored, stored))
+        in_ids, in_counts, stored = self._graph_arrays(graph, "knn_graph_refine")
         rounds = int(rounds)
         if rounds < 1:
             raise _ffi.ZhError(_ffi.ZH_EINVAL, "knn_graph_refine: rounds must be at least 1")
@@ -718,11 +728,7 @@ class LSHIndex:
         The answer is bit for bit knn_graph_refine(graph, k, metric, rounds=rounds, reverse=reverse)'s, early stop at the first round without
         updates included; knn_descent_info() describes the call round by round.  Whole table only, 1 <= rounds <= 32, k >= 1,
         in_k + reverse <= 64 and k + reverse <= 64.  -> (ids [stored rows, k] u64, keys [stored rows, k] u64, counts [stored rows] u32)."""
-        in_ids = np.ascontiguousarray(graph[0], np.uint64)
-        in_counts = np.ascontiguousarray(graph[-1], np.uint32)
-        stored = self.stored_rows()
-        if in_ids.ndim != 2 or in_counts.ndim != 1 or in_ids.shape[0] != stored or in_counts.shape[0] != stored:
-            raise _ffi.ZhError(_ffi.ZH_EINVAL, "knn_graph_descent: the graph must cover the %d stored rows: ids [%d, in_k], counts [%d]" % (stored, stored, stored))
+        in_ids, in_counts, stored = self._graph_arrays(graph, "knn_graph_descent")
         k = int(k)
         ids = np.empty((stored, max(k, 0)), np.uint64)
         keys = np.empty((stored, max(k, 0)), np.uint64)
@@ -749,10 +755,7 @@ class LSHIndex:
         stored_rows()), ids in the id space id_base + row.  Entries past a line's count, out of range, removed or repeated in their line are
         ignored.  The index keeps the graph on the device (4 g_rows g_k bytes) through append, add, remove, deduplicate, build and set_forest;
         a second set_graph replaces it; compact() (once it moves rows) and clear() drop it, and a snapshot never holds it."""
-        in_ids = np.ascontiguousarray(graph[0], np.uint64)
-        in_counts = np.ascontiguousarray(graph[-1], np.uint32)
-        if in_ids.ndim != 2 or in_counts.ndim != 1:
-            raise _ffi.ZhError(_ffi.ZH_EINVAL, "set_graph: the graph is ids [g_rows, g_k] and counts [g_rows]")
+        in_ids, in_counts, _ = self._graph_arrays(graph, "set_graph", cover=False)
         g_rows = in_ids.shape[0] if rows is None else int(rows)
         if g_rows < 0 or g_rows > in_ids.shape[0] or g_rows > in_counts.shape[0]:
             raise _ffi.ZhError(_ffi.ZH_EINVAL, "set_graph: rows %d, but the arrays hold %d and %d lines" % (g_rows, in_ids.shape[0], in_counts.shape[0]))
@@ -829,11 +832,7 @@ class LSHIndex:
         name stored row first_row + i and that its own line does not name -- a deterministic pseudo-random sample by a hash of the pair, the same
         whatever the order of entries, the run or the slab -> (ids [n, rev_k] u64 with tails 2^64-1, counts [n] u32, degree [n] u32: the uncapped
         in-degree, the hubness score).  No metric, no keys, no forest."""
-        in_ids = np.ascontiguousarray(graph[0], np.uint64)
-        in_counts = np.ascontiguousarray(graph[-1], np.uint32)
-        stored = self.stored_rows()
-        if in_ids.ndim != 2 or in_counts.ndim != 1 or in_ids.shape[0] != stored or in_counts.shape[0] != stored:
-            raise _ffi.ZhError(_ffi.ZH_EINVAL, "knn_graph_reverse: the graph must cover the %d stored rows: ids [%d, in_k], counts [%d]" % (stored, stored, stored))
+        in_ids, in_counts, stored = self._graph_arrays(graph, "knn_graph_reverse")
         n = max(stored - first_row, 0) if n is None else int(n)
         ids = np.empty((n, rev_k), np.uint64)
         counts = np.zeros(n, np.uint32)

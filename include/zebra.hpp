@@ -546,6 +546,41 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_search_graph_info(h_.get(), &info));
         return info;
     }
+    // Filtered graph search (zh_search_graph_filtered_batch): search_graph_batch's walk -- it goes through every live row -- answered with the first
+    // top_k by (key, id) of the rows it keyed that `filter_words` allows (bit r & 31 of word r >> 5 = stored row r; n_bits <= stored_rows(), rows at
+    // and past it are not allowed).  With every row allowed it is search_graph_batch's answer.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> search_graph_filtered_batch(const std::vector<Embedding<N>> &queries, const std::vector<Id> &seeds,
+                                                                                        std::size_t n_seed, std::size_t top_k, const Met &metric,
+                                                                                        const std::vector<std::uint32_t> &filter_words, std::uint64_t n_bits,
+                                                                                        std::size_t beam = 64, std::size_t width = 1,
+                                                                                        std::size_t max_iters = 0) const {
+        const std::size_t b = queries.size();
+        if (seeds.size() != b * n_seed) throw std::invalid_argument("search_graph_filtered_batch: seeds holds n_seed ids per query");
+        if (filter_words.size() < (n_bits + 31) / 32) throw std::invalid_argument("search_graph_filtered_batch: filter_words holds n_bits bits");
+        std::vector<Id> ids(b * top_k + 1);
+        std::vector<DistanceUnit> keys(b * top_k + 1);
+        std::vector<std::uint32_t> counts(b + 1);
+        check(zh_search_graph_filtered_batch(h_.get(), b ? queries[0].data() : nullptr, b, seeds.data(), n_seed, top_k, beam, width, max_iters, Met::metric,
+                                             metric.mode(), n_bits ? filter_words.data() : nullptr, n_bits, ids.data(), keys.data(), counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(b);
+        for (std::size_t i = 0; i < b; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * top_k + j], keys[i * top_k + j]);
+        return out;
+    }
+    template <class Met>
+    void search_graph_filtered_batch_device(const float *d_queries, std::size_t b, const Id *d_seeds, std::size_t n_seed, std::size_t top_k, std::size_t beam,
+                                            std::size_t width, std::size_t max_iters, const Met &metric, const std::uint32_t *d_filter_words,
+                                            std::uint64_t n_bits, Id *d_out_ids, DistanceUnit *d_out_keys, std::uint32_t *d_out_counts,
+                                            void *stream = nullptr) const {
+        check(zh_search_graph_filtered_batch_device(h_.get(), d_queries, b, d_seeds, n_seed, top_k, beam, width, max_iters, Met::metric, metric.mode(),
+                                                    d_filter_words, n_bits, d_out_ids, d_out_keys, d_out_counts, stream));
+    }
+    zh_graph_filtered_info search_graph_filtered_info() const {
+        zh_graph_filtered_info info{};
+        check(zh_search_graph_filtered_info(h_.get(), &info));
+        return info;
+    }
     // The capped reverse graph on its own (zh_knn_graph_reverse): element i = up to rev_k of the live rows that name stored row first_row + i and
     // that its own line does not name, in (hash, row) order; degree[i] = its uncapped in-degree.  No metric, no keys, no forest.
     struct ReverseGraph {

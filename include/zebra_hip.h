@@ -41,6 +41,7 @@
  *   zh_index_set_graph[_device] / zh_index_drop_graph / zh_index_graph_info  (new) a k-NN graph over the stored rows, kept on the device between calls
  *   zh_search_graph_batch[_device]       (new) beam search over that graph: a best-first walk from caller-given seeds, exact keys, an approximate
  *                                        visited set
+ *   zh_search_graph_filtered_batch[_device] (new) the same walk, answered from the rows a caller's bitmap allows among those it keyed
  *   zh_self_join_forest[_device]         (new) every pair of leaf-mates whose key is at or below one threshold key, each pair once: exact keys,
  *                                        approximate candidates
  *   zh_search_range_forest_batch[_device] (new) every member of the leaves the walk visits for a query whose key is at or below the query's
@@ -882,6 +883,50 @@ typedef struct zh_graph_search_info {  /* the most recent zh_search_graph_batch*
     uint64_t launches;    /* launches of the search kernel: ceil(b / ZH_GRAPH_BATCH) */
 } zh_graph_search_info;
 ZH_API int zh_search_graph_info(const zh_index *idx, zh_graph_search_info *out);
+
+/* Filtered graph search (new): zh_search_graph_batch's walk, answered from the rows a bitmap allows.  The arguments are zh_search_graph_batch's
+ * plus filter_words / n_bits, which follow zh_search_exact_filtered_batch's convention to the letter: bit r & 31 of filter_words[r >> 5] set =
+ * stored row r may be returned; rows at and past n_bits are not allowed; bits of the last word past n_bits are ignored; n_bits >
+ * zh_index_stored_rows is ZH_EINVAL; a NULL filter with n_bits > 0 is ZH_EINVAL; one filter serves the batch.
+ * THE WALK DOES NOT SEE THE FILTER: S(q), B, P, cand, the flags, the stop rule and max_iters are zh_search_graph_batch's, and navigation goes
+ * through every live row, allowed or not.  Let K(q) be the rows that ever get a key: S(q) and every iteration's cand.  The answer is the first
+ * top_k by (key, id) of the rows of K(q) that are allowed and live at the time of the search, in zh_search_exact_batch's layout: out_counts[q] =
+ * min(top_k, allowed rows in K(q)), entries past it UINT64_MAX, ids carry id_base, every key is zh_distance_batch's.  A row appended since the
+ * attach can be a seed and is returned if the mask covers it; a row removed since the attach is neither walked nor returned.  With every stored
+ * row allowed the ids, keys and counts are zh_search_graph_batch's bit for bit (B is always the first `beam` of K(q), and top_k <= beam).
+ * n_bits = 0, or a filter that allows nothing, gives counts of 0 with the walk still run.
+ * The block keeps a second list R beside the beam, the first top_k allowed rows met so far sorted by (key, id): an iteration's candidates whose
+ * bit in the allowed-AND-live bitmap is set are merged into it, minus the rows R holds now.  There is no visited set, so an allowed row can be
+ * offered again: it is either in R (dropped by that test), or it lost to a full R whose last entry never rises and loses again -- the beam's
+ * argument, one list further.
+ * Limits and judgement order are zh_search_graph_batch's, top_k <= beam included; the NULL filter is judged with the null pointers (before any
+ * device is touched, for any b); n_bits against the stored rows is judged under the lock, after ZH_ESTATE and the width * g_k check.  b = 0 is
+ * ZH_OK.  Locking and stream semantics as zh_search_graph_batch_device.  The filter pass (allowed AND live, counted) runs once per call on the
+ * call's stream; nothing of it comes back to the host before the launches.  Device scratch is per call and released before return:
+ * zh_search_graph_batch's (56 bytes of counters for its 40), the allowed-AND-live bitmap (stored rows / 8 bytes) with 8 bytes per 8192 stored
+ * rows of block counts, and for the host entry the staged filter (n_bits / 8 bytes).  zh_search_graph_info, zh_stats_t and every sibling info
+ * struct are left alone: zh_search_graph_filtered_info describes the most recent filtered call. */
+ZH_API int zh_search_graph_filtered_batch(zh_index *idx, const float *queries, size_t b, const uint64_t *seeds, size_t n_seed, size_t top_k,
+                                          size_t beam, size_t width, size_t max_iters, int metric, int cosine_mode, const uint32_t *filter_words,
+                                          uint64_t n_bits, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts);
+/* The same with queries, seeds, filter and every output in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_search_graph_filtered_batch_device(zh_index *idx, const float *d_queries, size_t b, const uint64_t *d_seeds, size_t n_seed,
+                                                 size_t top_k, size_t beam, size_t width, size_t max_iters, int metric, int cosine_mode,
+                                                 const uint32_t *d_filter_words, uint64_t n_bits, uint64_t *d_out_ids, uint64_t *d_out_keys,
+                                                 uint32_t *d_out_counts, void *stream);
+typedef struct zh_graph_filtered_info {  /* the most recent zh_search_graph_filtered_batch* call on this index */
+    uint64_t queries;       /* the first seven: zh_graph_search_info's, and equal to the unfiltered call's at the same arguments */
+    uint64_t seeds;
+    uint64_t iterations;
+    uint64_t expanded;
+    uint64_t keyed;
+    uint64_t capped;
+    uint64_t launches;
+    uint64_t rows_allowed;  /* rows both allowed and live: the filter pass's count */
+    uint64_t offered;       /* the allowed rows among S(q) and every cand, summed over the batch, repeats included */
+    uint64_t returned;      /* the sum of out_counts */
+} zh_graph_filtered_info;
+ZH_API int zh_search_graph_filtered_info(const zh_index *idx, zh_graph_filtered_info *out);
 
 /* ---- forest self-join (new): all near-duplicate pairs AMONG LEAF-MATES ---------------------------------------------------------------------
  * zh_self_join multiplies every tile of the table by every tile at or above it; this call multiplies a leaf only by itself.  Arguments, key,

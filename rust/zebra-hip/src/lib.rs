@@ -259,6 +259,21 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_graph_filtered_info {
+        pub queries: u64,
+        pub seeds: u64,
+        pub iterations: u64,
+        pub expanded: u64,
+        pub keyed: u64,
+        pub capped: u64,
+        pub launches: u64,
+        pub rows_allowed: u64,
+        pub offered: u64,
+        pub returned: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_join_forest_info {
         pub rows_live: u64,
         pub trees: u32,
@@ -444,6 +459,15 @@ pub mod ffi {
                                             beam: usize, width: usize, max_iters: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64,
                                             d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_search_graph_info(idx: *const zh_index, out: *mut zh_graph_search_info) -> c_int;
+        pub fn zh_search_graph_filtered_batch(idx: *mut zh_index, queries: *const f32, b: usize, seeds: *const u64, n_seed: usize, top_k: usize,
+                                              beam: usize, width: usize, max_iters: usize, metric: c_int, cosine_mode: c_int,
+                                              filter_words: *const u32, n_bits: u64, out_ids: *mut u64, out_keys: *mut u64,
+                                              out_counts: *mut u32) -> c_int;
+        pub fn zh_search_graph_filtered_batch_device(idx: *mut zh_index, d_queries: *const f32, b: usize, d_seeds: *const u64, n_seed: usize,
+                                                     top_k: usize, beam: usize, width: usize, max_iters: usize, metric: c_int, cosine_mode: c_int,
+                                                     d_filter_words: *const u32, n_bits: u64, d_out_ids: *mut u64, d_out_keys: *mut u64,
+                                                     d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_search_graph_filtered_info(idx: *const zh_index, out: *mut zh_graph_filtered_info) -> c_int;
         pub fn zh_self_join_forest(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, out_a: *mut u64,
                                    out_b: *mut u64, out_keys: *mut u64, out_total: *mut u64) -> c_int;
         pub fn zh_self_join_forest_device(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, d_out_a: *mut u64,
@@ -1097,6 +1121,46 @@ impl<const N: usize> LSHIndex<N> {
         })?;
         let t = self.ids.read().unwrap();
         Ok((0..b).map(|i| (0..counts[i] as usize).map(|j| (t.of_row[ids[i * top_k + j] as usize], keys[i * top_k + j])).collect()).collect())
+    }
+
+    /// (new) search_graph_batch's walk -- through every live vector -- answered with the nearest of the vectors it keyed that `allowed` names
+    /// (zh_search_graph_filtered_batch).  Unknown Uuids allow nothing; removed vectors are neither walked nor returned.  With every vector
+    /// allowed it is search_graph_batch's answer
+    #[allow(clippy::too_many_arguments)]
+    pub fn search_graph_filtered_batch<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        queries: &[Embedding<N>],
+        top_k: usize,
+        beam: usize,
+        width: usize,
+        max_iters: usize,
+        n_seed: usize,
+        metric: &Met,
+        allowed: &[Uuid],
+    ) -> anyhow::Result<Vec<Vec<(Uuid, DistanceUnit)>>> {
+        let b = queries.len();
+        let g_rows = self.graph_info()?.g_rows;
+        let seeds: Vec<u64> = (0..b * n_seed).map(|i| ((i % n_seed) as u64) * g_rows / n_seed.max(1) as u64).collect();
+        let t = self.ids.read().unwrap();
+        let n_bits = unsafe { ffi::zh_index_stored_rows(self.hip.0) };
+        let mut words = vec![0u32; ((n_bits + 31) / 32) as usize];
+        for row in allowed.iter().filter_map(|u| t.row_of.get(u).copied()).filter(|r| *r < n_bits) {
+            words[(row >> 5) as usize] |= 1u32 << (row & 31);
+        }
+        let (mut ids, mut keys, mut counts) = (vec![0u64; b * top_k + 1], vec![0u64; b * top_k + 1], vec![0u32; b + 1]);
+        check(unsafe {
+            ffi::zh_search_graph_filtered_batch(self.hip.0, queries.as_ptr() as *const f32, b, seeds.as_ptr(), n_seed, top_k, beam, width, max_iters,
+                                                Met::METRIC, metric.param(), if n_bits > 0 { words.as_ptr() } else { std::ptr::null() }, n_bits,
+                                                ids.as_mut_ptr(), keys.as_mut_ptr(), counts.as_mut_ptr())
+        })?;
+        Ok((0..b).map(|i| (0..counts[i] as usize).map(|j| (t.of_row[ids[i * top_k + j] as usize], keys[i * top_k + j])).collect()).collect())
+    }
+
+    /// what the most recent zh_search_graph_filtered_batch call did (zh_search_graph_filtered_info)
+    pub fn search_graph_filtered_info(&self) -> anyhow::Result<ffi::zh_graph_filtered_info> {
+        let mut info = ffi::zh_graph_filtered_info::default();
+        check(unsafe { ffi::zh_search_graph_filtered_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// what the most recent zh_search_graph_batch call did, summed over its queries (zh_search_graph_info)

@@ -201,6 +201,13 @@ class SearchGraphInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SearchGraphFilteredInfo(C.Structure):
+    _fields_ = SearchGraphInfo._fields_ + [("rows_allowed", C.c_uint64), ("offered", C.c_uint64), ("returned", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 GRAPH_MAX_BEAM, GRAPH_MAX_SEEDS, GRAPH_MAX_ITERS, GRAPH_BATCH = 256, 64, 65535, 16384  # ZH_GRAPH_*
 
 
@@ -318,6 +325,9 @@ SYMBOLS = [
     ("zh_search_graph_batch", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_search_graph_batch_device", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_search_graph_info", _i, [_vp, _vp]),
+    ("zh_search_graph_filtered_batch", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _u64, _vp, _vp, _vp]),
+    ("zh_search_graph_filtered_batch_device", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _u64, _vp, _vp, _vp, _vp]),
+    ("zh_search_graph_filtered_info", _i, [_vp, _vp]),
     ("zh_self_join_forest", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_device", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_info", _i, [_vp, _vp]),

@@ -447,6 +447,7 @@ struct zh_index {
     // capped}, and the host entry's staged batch: queries, seeds, ids, keys, counts
     DevBuf gs_QQ, gs_ctr, gs_Q, gs_seeds, gs_oids, gs_okeys, gs_ocounts;
     zh_graph_search_info gs_info{};  // (stats_mu)
+    zh_graph_filtered_info gf_info{};  // (stats_mu)
     // What the index remembers of paths that did not pay on its data, and how long its forest has stood.
     struct Fallbacks {
         // Both derived views of the forest cost host time per build (a traversal of every node: ~0.35 s for the 13M nodes of a 1M-row forest at the
@@ -3601,6 +3602,7 @@ enum : unsigned {
     SCRATCH_DESCENT = SCR_ND | SCRATCH_REVERSE,
     SCRATCH_GRAPH_ATTACH = SCR_RF,  // (the host entry's counts and staged chunk of ids)
     SCRATCH_GSEARCH = SCR_GS,
+    SCRATCH_GSEARCH_FILTERED = SCR_GS | SCR_FL,  // (the filter pass writes the filtered exact search's buffers)
     SCRATCH_FJOIN = SCR_FJ | SCRATCH_JOIN | SCRATCH_FKNN,
     SCRATCH_FRANGE = SCR_FR | SCRATCH_RANGE | SCRATCH_FJOIN,
     SCRATCH_XJOIN = SCR_XJ | SCRATCH_JOIN,  // (on the left index)
@@ -5924,9 +5926,11 @@ extern "C" int zh_index_graph_info(const zh_index *ix, zh_graph_info *out) {
 
 // judged before any device is touched, in this order of kinds: null index (even for b = 0), null pointers of a non-empty request, the metric, a zero
 // top_k / beam / width / n_seed, then the limits: beam, top_k against beam, n_seed, width (against 256: g_k is only known under the lock), max_iters
+// (the filtered entries: a null filter that speaks for rows is one of the null pointers, whatever b; the unfiltered ones pass null and 0)
 static int gsearch_args(zh_index *ix, const void *q, size_t b, const void *seeds, size_t n_seed, size_t top_k, size_t beam, size_t width, size_t max_iters,
-                        int metric, int mode, const void *ids, const void *keys, const void *counts, const char *who) {
+                        int metric, int mode, const void *filter, uint64_t n_bits, const void *ids, const void *keys, const void *counts, const char *who) {
     if (!ix || (b && (!q || !seeds || !ids || !keys || !counts))) return fail(ZH_EINVAL, "%s: null argument", who);
+    if (n_bits && !filter) return fail(ZH_EINVAL, "%s: null filter for %llu rows", who, (unsigned long long)n_bits);
     const int rc = check_metric(metric, mode);
     if (rc) return rc;
     if (!top_k) return fail(ZH_EINVAL, "%s: top_k is 0", who);
@@ -5941,11 +5945,17 @@ static int gsearch_args(zh_index *ix, const void *q, size_t b, const void *seeds
     return ZH_OK;
 }
 
-// both entry points once the arguments have been judged (b > 0).  host: q, seeds and the outputs are HOST arrays -- each internal batch goes through
-// the staging and is waited for; otherwise they are device arrays, waited for once after the last batch.
+// all four entry points once the arguments have been judged (b > 0).  host: q, seeds, the filter and the outputs are HOST arrays -- each internal batch
+// goes through the staging and is waited for; otherwise they are device arrays, waited for once after the last batch.  flt (the filtered entries):
+// the caller's bitmap; the filter pass runs once, on the call's stream, into the filtered exact search's buffers, and its count comes back with the
+// counters.  Without flt nothing of that is touched.
+struct GsearchFilter {
+    const uint32_t *words;
+    uint64_t n_bits;
+};
 static int gsearch_call(zh_index *ix, const float *q, size_t b, const uint64_t *seeds, uint32_t n_seed, uint32_t top_k, uint32_t beam, uint32_t width,
-                        uint32_t max_iters, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, bool host, void *stream,
-                        const char *who) {
+                        uint32_t max_iters, int metric, int mode, const GsearchFilter *flt, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, bool host,
+                        void *stream, const char *who) {
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     int rc;
     if ((rc = set_device(ix))) return rc;
@@ -5953,16 +5963,36 @@ static int gsearch_call(zh_index *ix, const float *q, size_t b, const uint64_t *
     const uint32_t g_k = ix->graph.k, d = ix->opt.dim;
     if ((uint64_t)width * g_k > 256) return fail(ZH_ELIMIT, "%s: width %u * g_k %u > 256", who, width, g_k);
     if (ix->n_rows >= (1ull << 31)) return fail(ZH_ELIMIT, "%s: %llu stored rows; graph search serves tables below 2^31 rows", who, (unsigned long long)ix->n_rows);
+    if (flt && (rc = filtered_bits_fit(ix, flt->n_bits))) return rc;
     if ((rc = exact_live_rows(ix))) return rc;
-    ScratchGuard guard{ix, SCRATCH_GSEARCH};
+    ScratchGuard guard{ix, flt ? SCRATCH_GSEARCH_FILTERED : SCRATCH_GSEARCH};
     const hipStream_t s = call_stream(ix, stream);
-    const size_t nb_max = std::min<size_t>(ZH_GRAPH_BATCH, b);
-    if ((rc = ix->gs_QQ.ensure(nb_max * 4)) || (rc = ix->gs_ctr.ensure(40))) return rc;
+    const size_t nb_max = std::min<size_t>(ZH_GRAPH_BATCH, b), ctr_bytes = flt ? 56 : 40;  // (zh_launch_gsearch's five counters, seven under a filter)
+    if ((rc = ix->gs_QQ.ensure(nb_max * 4)) || (rc = ix->gs_ctr.ensure(ctr_bytes))) return rc;
     if (host && ((rc = ix->gs_Q.ensure(nb_max * d * 4)) || (rc = ix->gs_seeds.ensure(nb_max * n_seed * 8)) || (rc = ix->gs_oids.ensure(nb_max * top_k * 8)) ||
                  (rc = ix->gs_okeys.ensure(nb_max * top_k * 8)) || (rc = ix->gs_ocounts.ensure(nb_max * 4))))
         return rc;
-    HIPCHK(hipMemsetAsync(ix->gs_ctr.p, 0, 40, s));
-    zh_graph_search_info inf{};
+    HIPCHK(hipMemsetAsync(ix->gs_ctr.p, 0, ctr_bytes, s));
+    const uint32_t *dAllow = nullptr, *dAllowed = nullptr;  // the allowed-AND-live bitmap; its count
+    if (flt) {
+        const uint64_t n = ix->n_rows;
+        const size_t fblocks = (size_t)((n + ZH_FILTER_BLOCK_ROWS - 1) / ZH_FILTER_BLOCK_ROWS), fwords = (size_t)((flt->n_bits + 31) / 32);
+        if ((rc = ix->fl_bits.ensure(std::max<size_t>((n + 63) / 64 * 8, 8))) || (rc = ix->fl_bcount.ensure(std::max<size_t>(fblocks, 1) * 4)) ||
+            (rc = ix->fl_bexcl.ensure((fblocks + 2) * 4)) || (rc = ix->fl_tmp.ensure((fblocks / 1024 + 2) * 4)))
+            return rc;
+        const uint32_t *dFilter = flt->words;
+        if (host) {
+            if ((rc = ix->fl_filter.ensure(std::max<size_t>(fwords, 1) * 4))) return rc;
+            if (fwords) HIPCHK(hipMemcpyAsync(ix->fl_filter.p, flt->words, fwords * 4, hipMemcpyHostToDevice, s));
+            dFilter = ix->fl_filter.as<uint32_t>();
+        }
+        uint32_t *excl = ix->fl_bexcl.as<uint32_t>();  // [0, fblocks]: the blocks' exclusive sums, the last one the count; then the tile count (not read)
+        HIPCHK(zh_launch_filter_and(dFilter, flt->n_bits, ix->live_dev.bits.as<uint32_t>(), n, ix->fl_bits.as<uint32_t>(), ix->fl_bcount.as<uint32_t>(), excl,
+                                    ix->fl_tmp.as<uint32_t>(), excl + fblocks + 1, s));
+        dAllow = ix->fl_bits.as<uint32_t>();
+        dAllowed = excl + fblocks;
+    }
+    zh_graph_filtered_info inf{};
     for (size_t b0 = 0; b0 < b; b0 += ZH_GRAPH_BATCH) {
         const uint32_t nb = (uint32_t)std::min<size_t>(ZH_GRAPH_BATCH, b - b0);
         const float *dQ = q + b0 * d;
@@ -5976,7 +6006,7 @@ static int gsearch_call(zh_index *ix, const float *q, size_t b, const uint64_t *
             dIds = ix->gs_oids.as<uint64_t>(); dKeys = ix->gs_okeys.as<uint64_t>(); dCounts = ix->gs_ocounts.as<uint32_t>();
         }
         if (metric == ZH_COSINE) HIPCHK(zh_launch_qnorm(dQ, nb, d, ix->gs_QQ.as<float>(), s));  // (the exact search's norm of the query)
-        HIPCHK(zh_launch_gsearch(ix->X.as<float>(), d, ix->n_rows, ix->graph.tab.as<uint32_t>(), ix->graph.rows, g_k, ix->live_dev.bits.as<uint32_t>(), dQ,
+        HIPCHK(zh_launch_gsearch(ix->X.as<float>(), d, ix->n_rows, ix->graph.tab.as<uint32_t>(), ix->graph.rows, g_k, ix->live_dev.bits.as<uint32_t>(), dAllow, dQ,
                                  ix->gs_QQ.as<float>(), dSeeds, n_seed, nb, ix->opt.id_base, top_k, beam, width, max_iters, metric, score_param(metric, mode), dIds,
                                  dKeys, dCounts, ix->gs_ctr.as<unsigned long long>(), s));
         inf.launches++;
@@ -5987,35 +6017,73 @@ static int gsearch_call(zh_index *ix, const float *q, size_t b, const uint64_t *
             HIPCHK(hipStreamSynchronize(s));
         }
     }
-    unsigned long long ctr[5] = {0, 0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(ctr, ix->gs_ctr.p, 40, hipMemcpyDeviceToHost, s));
+    unsigned long long ctr[7] = {0, 0, 0, 0, 0, 0, 0};
+    uint32_t allowed = 0;
+    HIPCHK(hipMemcpyAsync(ctr, ix->gs_ctr.p, ctr_bytes, hipMemcpyDeviceToHost, s));
+    if (flt) HIPCHK(hipMemcpyAsync(&allowed, dAllowed, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     inf.queries = b;
     inf.seeds = ctr[0]; inf.iterations = ctr[1]; inf.expanded = ctr[2]; inf.keyed = ctr[3]; inf.capped = ctr[4];
+    inf.rows_allowed = allowed; inf.offered = ctr[5]; inf.returned = ctr[6];
     std::lock_guard<std::mutex> ls(ix->stats_mu);
-    ix->gs_info = inf;
+    if (flt) {
+        ix->gf_info = inf;
+    } else {
+        zh_graph_search_info g{};
+        g.queries = inf.queries; g.seeds = inf.seeds; g.iterations = inf.iterations; g.expanded = inf.expanded; g.keyed = inf.keyed; g.capped = inf.capped;
+        g.launches = inf.launches;
+        ix->gs_info = g;
+    }
     return ZH_OK;
 }
 
 extern "C" int zh_search_graph_batch_device(zh_index *ix, const float *d_q, size_t b, const uint64_t *d_seeds, size_t n_seed, size_t top_k, size_t beam,
                                             size_t width, size_t max_iters, int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys,
                                             uint32_t *d_out_counts, void *stream) {
-    int rc = gsearch_args(ix, d_q, b, d_seeds, n_seed, top_k, beam, width, max_iters, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_search_graph_batch_device");
+    int rc = gsearch_args(ix, d_q, b, d_seeds, n_seed, top_k, beam, width, max_iters, metric, mode, nullptr, 0, d_out_ids, d_out_keys, d_out_counts,
+                          "zh_search_graph_batch_device");
     if (rc || b == 0) return rc;
-    return gsearch_call(ix, d_q, b, d_seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, d_out_ids,
-                        d_out_keys, d_out_counts, false, stream, "zh_search_graph_batch_device");
+    return gsearch_call(ix, d_q, b, d_seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, nullptr,
+                        d_out_ids, d_out_keys, d_out_counts, false, stream, "zh_search_graph_batch_device");
 }
 
 extern "C" int zh_search_graph_batch(zh_index *ix, const float *q, size_t b, const uint64_t *seeds, size_t n_seed, size_t top_k, size_t beam, size_t width,
                                      size_t max_iters, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts) {
-    int rc = gsearch_args(ix, q, b, seeds, n_seed, top_k, beam, width, max_iters, metric, mode, out_ids, out_keys, out_counts, "zh_search_graph_batch");
+    int rc = gsearch_args(ix, q, b, seeds, n_seed, top_k, beam, width, max_iters, metric, mode, nullptr, 0, out_ids, out_keys, out_counts, "zh_search_graph_batch");
     if (rc || b == 0) return rc;
-    return gsearch_call(ix, q, b, seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, out_ids, out_keys,
-                        out_counts, true, nullptr, "zh_search_graph_batch");
+    return gsearch_call(ix, q, b, seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, nullptr, out_ids,
+                        out_keys, out_counts, true, nullptr, "zh_search_graph_batch");
 }
 
 extern "C" int zh_search_graph_info(const zh_index *ix, zh_graph_search_info *out) {
     return get_info(ix, &zh_index::gs_info, out, "zh_search_graph_info");
+}
+
+// filtered graph search: the same walk, answered from the allowed rows it keyed.  DESIGN.md s26
+extern "C" int zh_search_graph_filtered_batch_device(zh_index *ix, const float *d_q, size_t b, const uint64_t *d_seeds, size_t n_seed, size_t top_k, size_t beam,
+                                                     size_t width, size_t max_iters, int metric, int mode, const uint32_t *d_filter, uint64_t n_bits,
+                                                     uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
+    const char *who = "zh_search_graph_filtered_batch_device";
+    int rc = gsearch_args(ix, d_q, b, d_seeds, n_seed, top_k, beam, width, max_iters, metric, mode, d_filter, n_bits, d_out_ids, d_out_keys, d_out_counts, who);
+    if (rc || b == 0) return rc;
+    const GsearchFilter flt{d_filter, n_bits};
+    return gsearch_call(ix, d_q, b, d_seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, &flt, d_out_ids,
+                        d_out_keys, d_out_counts, false, stream, who);
+}
+
+extern "C" int zh_search_graph_filtered_batch(zh_index *ix, const float *q, size_t b, const uint64_t *seeds, size_t n_seed, size_t top_k, size_t beam, size_t width,
+                                              size_t max_iters, int metric, int mode, const uint32_t *filter, uint64_t n_bits, uint64_t *out_ids,
+                                              uint64_t *out_keys, uint32_t *out_counts) {
+    const char *who = "zh_search_graph_filtered_batch";
+    int rc = gsearch_args(ix, q, b, seeds, n_seed, top_k, beam, width, max_iters, metric, mode, filter, n_bits, out_ids, out_keys, out_counts, who);
+    if (rc || b == 0) return rc;
+    const GsearchFilter flt{filter, n_bits};
+    return gsearch_call(ix, q, b, seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, &flt, out_ids,
+                        out_keys, out_counts, true, nullptr, who);
+}
+
+extern "C" int zh_search_graph_filtered_info(const zh_index *ix, zh_graph_filtered_info *out) {
+    return get_info(ix, &zh_index::gf_info, out, "zh_search_graph_filtered_info");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -18,6 +18,14 @@
 // Step (5) is refine_key_list's loop (zh_refine_dev.h) written out here, with >> 1 on the id word: shared, gsearch_kernel<1024, K_COS> lost an
 // occupancy step or the width-4 searches 1 to 2 % of their speed, depending on the row a slot past the list reloads.  The key itself
 // is the shared refine_key.
+//
+//   gsearch_filtered_kernel   zh_search_graph_filtered_batch: the same block body (gsearch_block<D, KIND, FILT>) with a second list R in
+//                    LDS, the first top_k by (key, row) of the rows keyed so far that the call's allowed-AND-live bitmap allows.  The walk does not see
+//                    the filter.  Inside absorb, once the keys are in ckey: (F1) a candidate whose bit is set passes unless R holds it now -- a
+//                    broadcast scan of R's at most top_k id words -- and says so in bit 0 of its candidate word; (F2) step (6)'s pass over the
+//                    candidates also counts the passing ones below each entry of R and below each candidate, and a passing candidate adds the
+//                    entries of R below it by a binary search; (F3) what lands below top_k is written.  One barrier more an iteration.  A row keyed
+//                    again is in R (dropped) or lost to a full R whose last entry never rises (loses again): R is exact.  The answer is R.
 #include "zh_refine_dev.h"  // refine_key, RowRegs, RF_NONE, ZH_REFINE_INFLIGHT: the key of a gathered row against a row held in registers
 
 #define GS_SLOTS ZH_GRAPH_MAX_BEAM  // beam slots, and candidate slots behind them (width * g_k <= 256, seeds <= 64)
@@ -26,16 +34,20 @@ static_assert(GS_SLOTS == 256, "one thread per beam slot and per candidate slot"
 // (key, row) below (key, row)
 __device__ __forceinline__ bool gs_less(uint64_t ka, uint32_t ra, uint64_t kb, uint32_t rb) { return ka < kb || (ka == kb && ra < rb); }
 
-template <int D, int KIND>
-__global__ __launch_bounds__(256) void gsearch_kernel(const float *__restrict__ X, uint32_t d, uint64_t n_rows, const uint32_t *__restrict__ tab, uint64_t g_rows,
-                                                      uint32_t g_k, const uint32_t *__restrict__ bits, const float *__restrict__ Q, const float *__restrict__ QQ,
-                                                      const uint64_t *__restrict__ seeds, uint32_t n_seed, uint64_t id_base, uint32_t top_k, uint32_t beam,
-                                                      uint32_t width, uint32_t max_iters, int metric, int param, uint64_t *__restrict__ out_ids,
-                                                      uint64_t *__restrict__ out_keys, uint32_t *__restrict__ out_counts, unsigned long long *__restrict__ ctr) {
+// the block of both kernels.  FILT: the second list (allow: the allowed-AND-live bitmap of the call's filter pass; null without)
+template <int D, int KIND, bool FILT>
+__device__ __forceinline__ void gsearch_block(const float *__restrict__ X, uint32_t d, uint64_t n_rows, const uint32_t *__restrict__ tab, uint64_t g_rows, uint32_t g_k,
+                                              const uint32_t *__restrict__ bits, const uint32_t *__restrict__ allow, const float *__restrict__ Q,
+                                              const float *__restrict__ QQ, const uint64_t *__restrict__ seeds, uint32_t n_seed, uint64_t id_base, uint32_t top_k,
+                                              uint32_t beam, uint32_t width, uint32_t max_iters, int metric, int param, uint64_t *__restrict__ out_ids,
+                                              uint64_t *__restrict__ out_keys, uint32_t *__restrict__ out_counts, unsigned long long *__restrict__ ctr) {
     constexpr int R = ZH_REFINE_INFLIGHT;
     __shared__ uint64_t s_key[2 * GS_SLOTS];
     __shared__ uint32_t s_id[2 * GS_SLOTS];
     __shared__ uint32_t s_raw[GS_SLOTS], s_par[GS_SLOTS], s_wc[4];
+    __shared__ uint64_t r_key[FILT ? GS_SLOTS : 1];  // the second list: the first top_k allowed rows met so far, sorted by (key, row)
+    __shared__ uint32_t r_id[FILT ? GS_SLOTS : 1];   // (plain row numbers)
+    uint32_t nr = 0, n_off = 0;  // |R| (block-uniform); the allowed rows this WAVE's lanes saw offered (wave-uniform)
     const uint32_t tid = threadIdx.x, lane = tid & 63, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const size_t b = blockIdx.x;
     const float *q = Q + b * d;
@@ -86,11 +98,45 @@ __global__ __launch_bounds__(256) void gsearch_kernel(const float *__restrict__ 
         const uint64_t kb = hb ? s_key[tid] : 0, kc = hc ? ckey[tid] : 0;
         const uint32_t ib = hb ? s_id[tid] : 0, ic = hc ? cid[tid] : 0;
         uint32_t pb = tid, pc = 0;
+        // (F1) candidate tid is offered to R if its bit in the allowed-AND-live bitmap is set, and passes unless R holds it now
+        const bool hr = FILT && tid < nr;
+        uint64_t kr = 0;
+        uint32_t ir = 0, pr = tid, pcr = 0, n_pass = 0;
+        bool pass = false;
+        if constexpr (FILT) {
+            if (hr) { kr = r_key[tid]; ir = r_id[tid]; }
+            const uint32_t rc = ic >> 1;
+            const bool offered = hc && ((allow[rc >> 5] >> (rc & 31)) & 1u);
+            n_off += (uint32_t)__popcll(__ballot(offered));
+            bool in_r = false;
+            for (uint32_t j = 0; j < nr; j++) in_r = in_r || r_id[j] == rc;  // (broadcast reads)
+            pass = offered && !in_r;
+            if (pass) cid[tid] = ic | 1u;  // (a candidate's flag bit is free until it joins the beam, which it does as ic)
+            __syncthreads();
+        }
         for (uint32_t j = 0; j < U; j++) {  // (every lane reads the same words: LDS broadcasts)
             const uint64_t kj = ckey[j];
-            const uint32_t rj = cid[j] >> 1;
+            const uint32_t wj = cid[j], rj = wj >> 1;
             pb += gs_less(kj, rj, kb, ib >> 1) ? 1u : 0u;
-            pc += gs_less(kj, rj, kc, ic >> 1) ? 1u : 0u;
+            const uint32_t below_c = gs_less(kj, rj, kc, ic >> 1) ? 1u : 0u;
+            pc += below_c;
+            if constexpr (FILT) {  // (F2) the same count among the passing candidates, for R's entries and for the candidate
+                const uint32_t fj = wj & 1u;
+                n_pass += fj;
+                pr += gs_less(kj, rj, kr, ir) ? fj : 0u;
+                pcr += below_c & fj;
+            }
+        }
+        if constexpr (FILT) {
+            if (pass) {  // the entries of R below the candidate
+                uint32_t lo = 0, hi = nr;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (gs_less(r_key[mid], r_id[mid], kc, ic >> 1)) lo = mid + 1;
+                    else hi = mid;
+                }
+                pcr += lo;
+            }
         }
         if (hc) {  // the beam entries below the candidate: the first of the sorted beam that is not
             uint32_t lo = 0, hi = nb;
@@ -105,6 +151,11 @@ __global__ __launch_bounds__(256) void gsearch_kernel(const float *__restrict__ 
         if (hb && pb < beam) { s_key[pb] = kb; s_id[pb] = ib; }
         if (hc && pc < beam) { s_key[pc] = kc; s_id[pc] = ic; }
         nb = nb + U < beam ? nb + U : beam;
+        if constexpr (FILT) {  // (F3) what lands below top_k is written (the barrier above closed the reads of R too)
+            if (hr && pr < top_k) { r_key[pr] = kr; r_id[pr] = ir; }
+            if (pass && pcr < top_k) { r_key[pcr] = kc; r_id[pcr] = ic >> 1; }
+            nr = nr + n_pass < top_k ? nr + n_pass : top_k;
+        }
         __syncthreads();
         return U;
     };
@@ -166,11 +217,20 @@ __global__ __launch_bounds__(256) void gsearch_kernel(const float *__restrict__ 
         }
         n_keyed += absorb(v);  // (its first barrier closes the reads of the beam's id words)
     }
-    // ---- the answer: the first top_k of B
-    const uint32_t have = nb < top_k ? nb : top_k;
+    // ---- the answer: the first top_k of B; under a filter, R
+    const uint32_t have = FILT ? nr : nb < top_k ? nb : top_k;
     for (uint32_t i = tid; i < top_k; i += 256) {
-        out_ids[b * top_k + i] = i < have ? id_base + (s_id[i] >> 1) : ~0ull;
-        out_keys[b * top_k + i] = i < have ? s_key[i] : ~0ull;
+        if constexpr (FILT) {
+            out_ids[b * top_k + i] = i < have ? id_base + r_id[i] : ~0ull;
+            out_keys[b * top_k + i] = i < have ? r_key[i] : ~0ull;
+        } else {
+            out_ids[b * top_k + i] = i < have ? id_base + (s_id[i] >> 1) : ~0ull;
+            out_keys[b * top_k + i] = i < have ? s_key[i] : ~0ull;
+        }
+    }
+    if constexpr (FILT) {
+        if (lane == 0 && n_off) atomicAdd(&ctr[5], (unsigned long long)n_off);
+        if (tid == 0 && have) atomicAdd(&ctr[6], (unsigned long long)have);
     }
     if (tid == 0) {
         out_counts[b] = have;
@@ -182,8 +242,30 @@ __global__ __launch_bounds__(256) void gsearch_kernel(const float *__restrict__ 
     }
 }
 
+template <int D, int KIND>
+__global__ __launch_bounds__(256) void gsearch_kernel(const float *__restrict__ X, uint32_t d, uint64_t n_rows, const uint32_t *__restrict__ tab, uint64_t g_rows,
+                                                      uint32_t g_k, const uint32_t *__restrict__ bits, const float *__restrict__ Q, const float *__restrict__ QQ,
+                                                      const uint64_t *__restrict__ seeds, uint32_t n_seed, uint64_t id_base, uint32_t top_k, uint32_t beam,
+                                                      uint32_t width, uint32_t max_iters, int metric, int param, uint64_t *__restrict__ out_ids,
+                                                      uint64_t *__restrict__ out_keys, uint32_t *__restrict__ out_counts, unsigned long long *__restrict__ ctr) {
+    gsearch_block<D, KIND, false>(X, d, n_rows, tab, g_rows, g_k, bits, nullptr, Q, QQ, seeds, n_seed, id_base, top_k, beam, width, max_iters, metric, param, out_ids,
+                                  out_keys, out_counts, ctr);
+}
+
+// the same walk, answering from R: allow = allowed AND live (zh_launch_filter_and's bitmap), ctr[5] = offered, ctr[6] = returned
+template <int D, int KIND>
+__global__ __launch_bounds__(256) void gsearch_filtered_kernel(const float *__restrict__ X, uint32_t d, uint64_t n_rows, const uint32_t *__restrict__ tab,
+                                                               uint64_t g_rows, uint32_t g_k, const uint32_t *__restrict__ bits, const uint32_t *__restrict__ allow,
+                                                               const float *__restrict__ Q, const float *__restrict__ QQ, const uint64_t *__restrict__ seeds,
+                                                               uint32_t n_seed, uint64_t id_base, uint32_t top_k, uint32_t beam, uint32_t width, uint32_t max_iters,
+                                                               int metric, int param, uint64_t *__restrict__ out_ids, uint64_t *__restrict__ out_keys,
+                                                               uint32_t *__restrict__ out_counts, unsigned long long *__restrict__ ctr) {
+    gsearch_block<D, KIND, true>(X, d, n_rows, tab, g_rows, g_k, bits, allow, Q, QQ, seeds, n_seed, id_base, top_k, beam, width, max_iters, metric, param, out_ids,
+                                 out_keys, out_counts, ctr);
+}
+
 hipError_t zh_launch_gsearch(const float *dX, uint32_t d, uint64_t n_rows, const uint32_t *dTab, uint64_t g_rows, uint32_t g_k, const uint32_t *dBits,
-                             const float *dQ, const float *dQQ, const uint64_t *dSeeds, uint32_t n_seed, uint32_t B, uint64_t id_base, uint32_t top_k,
+                             const uint32_t *dAllow, const float *dQ, const float *dQQ, const uint64_t *dSeeds, uint32_t n_seed, uint32_t B, uint64_t id_base, uint32_t top_k,
                              uint32_t beam, uint32_t width, uint32_t max_iters, int metric, int param, uint64_t *dOutIds, uint64_t *dOutKeys,
                              uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s) {
     if (!B) return hipSuccess;
@@ -191,8 +273,12 @@ hipError_t zh_launch_gsearch(const float *dX, uint32_t d, uint64_t n_rows, const
         beam > ZH_GRAPH_MAX_BEAM || n_rows >= (1ull << 31))
         return hipErrorInvalidValue;
     return zh_dispatch_kind_dim(metric, d, [&](auto kind, auto dim) {
-        hipLaunchKernelGGL((gsearch_kernel<decltype(dim)::value, decltype(kind)::value>), dim3(B), dim3(256), 0, s, dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ, dQQ,
-                           dSeeds, n_seed, id_base, top_k, beam, width, max_iters, metric, param, dOutIds, dOutKeys, dOutCounts, dCtr);
+        if (dAllow)
+            hipLaunchKernelGGL((gsearch_filtered_kernel<decltype(dim)::value, decltype(kind)::value>), dim3(B), dim3(256), 0, s, dX, d, n_rows, dTab, g_rows, g_k,
+                               dBits, dAllow, dQ, dQQ, dSeeds, n_seed, id_base, top_k, beam, width, max_iters, metric, param, dOutIds, dOutKeys, dOutCounts, dCtr);
+        else
+            hipLaunchKernelGGL((gsearch_kernel<decltype(dim)::value, decltype(kind)::value>), dim3(B), dim3(256), 0, s, dX, d, n_rows, dTab, g_rows, g_k, dBits, dQ,
+                               dQQ, dSeeds, n_seed, id_base, top_k, beam, width, max_iters, metric, param, dOutIds, dOutKeys, dOutCounts, dCtr);
         return hipGetLastError();
     });
 }

@@ -546,9 +546,11 @@ hipError_t zh_launch_nnd_lines(const float *dX, uint32_t d, const uint32_t *dU, 
 
 // ---- graph search (zh_gsearch.hip): beam search over the index's attached graph, dTab = zh_launch_refine_rows' table [g_rows][g_k].  A block per
 // query: seeds [B][n_seed] ids, the first top_k of the final beam to the outputs (zh_search_exact_batch's layout); dCtr[0..4] += valid seeds,
-// iterations, expanded, keyed, capped queries.  n_rows < 2^31, width * g_k <= 256
+// iterations, expanded, keyed, capped queries.  n_rows < 2^31, width * g_k <= 256.  dAllow (zh_search_graph_filtered_batch; null: none) is the
+// allowed-AND-live bitmap zh_launch_filter_and made: the walk is the same, the outputs are the first top_k of the ALLOWED rows that got a key, and
+// dCtr[5..6] += allowed rows offered (repeats included), entries returned
 hipError_t zh_launch_gsearch(const float *dX, uint32_t d, uint64_t n_rows, const uint32_t *dTab, uint64_t g_rows, uint32_t g_k, const uint32_t *dBits,
-                             const float *dQ, const float *dQQ, const uint64_t *dSeeds, uint32_t n_seed, uint32_t B, uint64_t id_base, uint32_t top_k,
+                             const uint32_t *dAllow, const float *dQ, const float *dQQ, const uint64_t *dSeeds, uint32_t n_seed, uint32_t B, uint64_t id_base, uint32_t top_k,
                              uint32_t beam, uint32_t width, uint32_t max_iters, int metric, int param, uint64_t *dOutIds, uint64_t *dOutKeys,
                              uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s);
 

@@ -827,6 +827,53 @@ class LSHIndex:
         ones), iterations, expanded, keyed, capped (stopped by max_iters with an unexpanded entry left), launches"""
         return self._info(_ffi.SearchGraphInfo, lib().zh_search_graph_info)
 
+    def _allowed_seeds(self, words, n_bits, b, n_seed):
+        """seeds="allowed": n_seed rows strided over the mask's set positions, rows[j * len(rows) // n_seed], the same for every query; a mask
+        with fewer set positions than n_seed gives every one of them, padded with repeats (which the kernel ignores)"""
+        n_seed = int(n_seed)
+        rows = np.flatnonzero(np.unpackbits(words.view(np.uint8), bitorder="little")[:n_bits])
+        if rows.size == 0:
+            row = np.full(max(n_seed, 0), 2 ** 64 - 1, np.uint64)  # (out of range: no seed)
+        elif rows.size < n_seed:
+            row = rows[np.arange(n_seed) % rows.size].astype(np.uint64) + np.uint64(self.id_base)
+        else:
+            row = rows[[j * rows.size // n_seed for j in range(n_seed)]].astype(np.uint64) + np.uint64(self.id_base)
+        return np.ascontiguousarray(np.broadcast_to(row, (b, row.size)))
+
+    def search_graph_filtered_batch(self, queries, top_k, metric, allowed, beam=64, width=1, max_iters=0, seeds=None, n_seed=32):
+        """search_graph_batch's walk, answered from the rows `allowed` names (whatever filter_bitmap takes; zh_search_graph_filtered_batch): the
+        walk does not see the filter and goes through every live row; the answer is the first top_k by (key, id) of the allowed live rows among
+        those that got a key -> (ids [b,k] u64, keys [b,k] u64, counts [b] u32), entries past counts[i] 2^64-1.  With every row allowed it is
+        search_graph_batch's answer.  seeds as in search_graph_batch, and "allowed" = n_seed rows strided over the mask's set positions, the same
+        for every query.  Limits as search_graph_batch.  search_graph_filtered_info() describes the call."""
+        q = _f32(queries, self.dim)
+        b = q.shape[0]
+        words, n_bits = self.filter_bitmap(allowed)
+        if isinstance(seeds, str) and seeds == "allowed":
+            sd = self._allowed_seeds(words, n_bits, b, n_seed)
+        else:
+            sd = self._graph_seeds(seeds, q, metric, n_seed)
+        top_k = int(top_k)
+        ids = np.empty((b, max(top_k, 0)), np.uint64)
+        keys = np.empty((b, max(top_k, 0)), np.uint64)
+        counts = np.zeros(b, np.uint32)
+        check(lib().zh_search_graph_filtered_batch(self._h, _p(q), b, _p(sd), sd.shape[1], top_k, int(beam), int(width), int(max_iters), metric.metric,
+                                                   metric.mode, _p(words) if n_bits else None, n_bits, _p(ids), _p(keys), _p(counts)))
+        return ids, keys, counts
+
+    def search_graph_filtered_batch_device(self, d_q_ptr, b, d_seeds_ptr, n_seed, top_k, metric, d_filter_ptr, n_bits, d_ids_ptr, d_keys_ptr, d_counts_ptr,
+                                           beam=64, width=1, max_iters=0, stream=None):
+        """search_graph_filtered_batch with queries, seeds, the filter's u32 words (filter_bitmap's layout) and results already in device memory"""
+        check(lib().zh_search_graph_filtered_batch_device(self._h, d_q_ptr, int(b), d_seeds_ptr, int(n_seed), int(top_k), int(beam), int(width),
+                                                          int(max_iters), metric.metric, metric.mode, d_filter_ptr, int(n_bits), d_ids_ptr, d_keys_ptr,
+                                                          d_counts_ptr, stream))
+
+    def search_graph_filtered_info(self):
+        """what the most recent search_graph_filtered_batch call on this index did (zh_search_graph_filtered_info): search_graph_info's seven
+        fields (equal to the unfiltered call's at the same arguments), rows_allowed (allowed and live), offered (allowed rows among the seeds
+        and every iteration's candidates, repeats included), returned (the sum of counts)"""
+        return self._info(_ffi.SearchGraphFilteredInfo, lib().zh_search_graph_filtered_info)
+
     def knn_graph_reverse(self, graph, rev_k, first_row=0, n=None):
         """the capped reverse graph of a graph of ALL stored rows (`graph` as for knn_graph_refine): line i holds up to rev_k of the live rows that
         name stored row first_row + i and that its own line does not name -- a deterministic pseudo-random sample by a hash of the pair, the same
@@ -1300,6 +1347,16 @@ class Database:
         if self.index.no_vectors():
             return {}
         ids, _, counts = self.index.search_graph_batch(vectors, number_of_results, self.metric, beam=max(int(beam), int(number_of_results)), **kw)
+        return {b: {int(i): self._documents.get(int(i)) for i in ids[b, :counts[b]]} for b in range(ids.shape[0])}
+
+    def query_vectors_graph_where(self, vectors, number_of_results, predicate, beam=64, **kw):
+        """query_vectors_graph among the records whose document satisfies predicate(document) (LSHIndex.search_graph_filtered_batch: the walk
+        goes through every record, the answer holds only those; seeds="allowed" starts it from them) -> what query_vectors_graph returns"""
+        if self.index.no_vectors():
+            return {}
+        allowed = np.fromiter((i for i, doc in self._documents.items() if predicate(doc)), np.uint64)
+        ids, _, counts = self.index.search_graph_filtered_batch(vectors, number_of_results, self.metric, allowed,
+                                                                beam=max(int(beam), int(number_of_results)), **kw)
         return {b: {int(i): self._documents.get(int(i)) for i in ids[b, :counts[b]]} for b in range(ids.shape[0])}
 
     def _graph_documents(self, ids, keys, counts):

@@ -25,12 +25,12 @@ CASES = {1: (1500, "block", 0, 32, 32, 0), 2: (1500, "hub", 7, 5, 8, 8), 3: (120
 ORACLE_METRIC = {0: (zo.L2SQ, 0), 7: (zo.MANHATTAN, 0)}  # the oracle's side of those metric indexes
 
 
-def union_lines(graph, in_k, rev_k, live, id_base):
-    """-> (N, U): N'(x) and U(x) = N'(x) union R'(x) of every stored row, ascending int64 row numbers"""
+def union_lines(graph, in_k, rev_k, live, id_base, row0=0):
+    """-> (N, U): N'(x) and U(x) = N'(x) union R'(x) of every stored row, ascending int64 row numbers (row0: reverse_cases.reverse_sets')"""
     N = rc.neighbour_sets(graph[0], graph[-1], in_k, live, id_base)
     if not rev_k:
         return N, N
-    R = rv.reverse_sets(N, rv.in_neighbours(N, live), rev_k)
+    R = rv.reverse_sets(N, rv.in_neighbours(N, live), rev_k, row0)
     return N, rv.union_sets(N, R)
 
 
@@ -62,10 +62,10 @@ def incremental_round(U_old, N, U, k, live, id_base, K):
     return (ids, keys, counts), info
 
 
-def descent(X, graph, in_k, rev_k, k, rounds, live, id_base, om, omode, K=None):
+def descent(X, graph, in_k, rev_k, k, rounds, live, id_base, om, omode, K=None, row0=0):
     """-> (answer, info, full, inc): the call's (ids, keys, counts); info = {rounds_run, listed_round, keyed_round, updates_round, active_round,
     full_keyed_round} (lists of rounds_run entries; full_keyed_round is what a loop over full rounds keys); full[r] and inc[r] the full and the
-    incremental answer of round r + 1 (inc[0] is full[0]: round 1 IS the full round)"""
+    incremental answer of round r + 1 (inc[0] is full[0]: round 1 IS the full round).  row0: reverse_cases.reverse_sets'"""
     live = np.asarray(live, bool)
     if K is None:
         K = rc.key_rows(X, om, omode, np.flatnonzero(live).tolist())
@@ -73,8 +73,8 @@ def descent(X, graph, in_k, rev_k, k, rounds, live, id_base, om, omode, K=None):
     full, inc = [], []
     g, w, U_old = (graph[0], graph[-1]), in_k, None
     for r in range(rounds):
-        ref, rinfo = rv.reference_rev(X, g, w, rev_k, k, live, id_base, om, omode, K=K)
-        N, U = union_lines(g, w, rev_k, live, id_base)
+        ref, rinfo = rv.reference_rev(X, g, w, rev_k, k, live, id_base, om, omode, K=K, row0=row0)
+        N, U = union_lines(g, w, rev_k, live, id_base, row0)
         if r == 0:
             got, ginfo = ref, {"listed": rinfo["listed"], "keyed": rinfo["keyed"], "updates": rinfo["updates"], "active": int(live.sum())}
         else:

@@ -45,12 +45,13 @@ def in_neighbours(N, live):
     return [src[cuts[x]:cuts[x + 1]] for x in range(n)]
 
 
-def reverse_sets(N, In, rev_k):
-    """R'(x) of every stored row in (h, u) order"""
+def reverse_sets(N, In, rev_k, row0=0):
+    """R'(x) of every stored row in (h, u) order.  row0: the table's row 0 is stored row row0 of a larger table whose hash is wanted -- h is taken
+    of row0 + u, row0 + x (tests/seam_cases.py's group-local references)"""
     out = []
     for x, (s, r) in enumerate(zip(N, In)):
         c = r[~np.isin(r, s)]
-        o = np.lexsort((c, h(c, x)))
+        o = np.lexsort((c, h(c + row0, x + row0)))
         out.append(c[o][:rev_k])
     return out
 
@@ -60,11 +61,11 @@ def union_sets(N, R):
     return [np.union1d(s, r) for s, r in zip(N, R)]
 
 
-def candidates_rev(in_ids, in_counts, in_k, rev_k, live, id_base):
-    """-> (C_r, listed, keyed, N, In, R): refine_cases.candidates() with B in place of N'; In and R as above"""
+def candidates_rev(in_ids, in_counts, in_k, rev_k, live, id_base, row0=0):
+    """-> (C_r, listed, keyed, N, In, R): refine_cases.candidates() with B in place of N'; In and R as above (row0: reverse_sets')"""
     N = rc.neighbour_sets(in_ids, in_counts, in_k, live, id_base)
     In = in_neighbours(N, live)
-    R = reverse_sets(N, In, rev_k)
+    R = reverse_sets(N, In, rev_k, row0)
     B = union_sets(N, R)
     n = len(N)
     sizes = np.array([s.size for s in B], np.int64)
@@ -80,14 +81,14 @@ def candidates_rev(in_ids, in_counts, in_k, rev_k, live, id_base):
     return C, listed, keyed, N, In, R
 
 
-def reference_reverse(graph, in_k, rev_k, live, id_base, first_row=0, n=None):
-    """zh_knn_graph_reverse's whole answer: (ids [n, rev_k], counts [n], degree [n]) and {lines, edges, kept, max_degree}"""
+def reference_reverse(graph, in_k, rev_k, live, id_base, first_row=0, n=None, row0=0):
+    """zh_knn_graph_reverse's whole answer: (ids [n, rev_k], counts [n], degree [n]) and {lines, edges, kept, max_degree} (row0: reverse_sets')"""
     in_ids, in_counts = graph[0], graph[-1]
     stored = in_ids.shape[0]
     n = stored - first_row if n is None else n
     N = rc.neighbour_sets(in_ids, in_counts, in_k, live, id_base)
     In = in_neighbours(N, live)
-    R = reverse_sets(N, In, rev_k)
+    R = reverse_sets(N, In, rev_k, row0)
     ids, counts, degree = np.full((n, rev_k), NONE, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
     for i in range(n):
         r = R[first_row + i]
@@ -98,13 +99,13 @@ def reference_reverse(graph, in_k, rev_k, live, id_base, first_row=0, n=None):
     return (ids, counts, degree), info
 
 
-def reference_rev(X, graph, in_k, rev_k, k, live, id_base, om, omode, first_row=0, n=None, K=None):
+def reference_rev(X, graph, in_k, rev_k, k, live, id_base, om, omode, first_row=0, n=None, K=None, row0=0):
     """zh_knn_graph_refine_rev's whole answer: refine_cases.reference() with C_r(a) in place of C(a); `updates` counts against N'(a), and the
-    info gains rev_k, edges, kept (over the slab) and max_degree -- all three 0 when rev_k = 0, where nothing is transposed"""
+    info gains rev_k, edges, kept (over the slab) and max_degree -- all three 0 when rev_k = 0, where nothing is transposed (row0: reverse_sets')"""
     in_ids, in_counts = graph[0], graph[-1]
     stored = in_ids.shape[0]
     n = stored - first_row if n is None else n
-    C, listed, keyed, N, In, R = candidates_rev(in_ids, in_counts, in_k, rev_k, live, id_base)
+    C, listed, keyed, N, In, R = candidates_rev(in_ids, in_counts, in_k, rev_k, live, id_base, row0)
     slab = [a for a in range(first_row, first_row + n) if live[a]]
     ranked = rc.ranked(X, C, slab, om, omode, id_base, K)
     ids, keys, counts = np.full((n, k), NONE, np.uint64), np.full((n, k), NONE, np.uint64), np.zeros(n, np.uint32)

@@ -26,12 +26,20 @@ products (not the oracle's arithmetic; the ratio is far from 1): L2 squared 11.5
 against false alarms: every assertion is an equality, so a row that wrongly qualified fails the test.  The filtered search under the selective mask
 and the three forest families need no such condition: their references take every allowed row / every leaf-mate (from ix.get_forest()).
 
+THE GRAPH FAMILY (section 7; zh_knn_graph_refine, _refine_rev, _reverse, _descent, zh_index_set_graph with zh_search_graph_batch and
+zh_search_graph_filtered_batch) needs no such condition: its input graph is tests/seam_cases.py's group-local one over the 128-row clusters --
+line 128 c + j of a probe cluster names 128 c + (j + o_t) mod 128, t < 8, every other line has count 0 -- so every answer on a probe cluster is
+the family's numpy reference on the 128 regenerated rows, and a read that wraps to a low row finds an empty line, another cluster's line or another
+row's values where the reference has the right ones.  The graph goes in as a HOST array of 268 MB, which takes the host entries' 64 MiB pinned
+chunks (8 388 608 entries each) through their loop at its real size; the section leaves the table as it found it (no removals, no graph attached).
+
 NOT COVERED, so that the gap stays visible: the exact self-join (zh_join.hip) -- quadratic, about 50 s at this size, and it has no slab form --
 and snapshots of a 17 GB table.  Nor does this table reach an offset counted in 16-byte vectors (the fp16 copy's u32x4e units): that one stays
 below 2^32 until 33.5M rows of d = 1024.
 
 The module takes half a minute on one MI355X (the slowest tests, 5 to 6 s each: the forest self-join's f32 leaf sweep over 1.76e10 leaf pairs,
-and the forest graph's matrix-core path, which visits every leaf of the forest for a slab of 32 lines).  Run alone, give it a limit of its own:
+and the forest graph's matrix-core path, which visits every leaf of the forest for a slab of 32 lines; the graph family's section adds 4 s: a
+descent over the whole table 0.3 to 0.4 s a case, the slab refinements 0.2 s a case with their four 268 MB uploads, the searches 0.1 s).  Run alone, give it a limit of its own:
 timeout 600 pytest -m gpu tests/test_gpu_large_table.py"""
 import concurrent.futures
 import functools
@@ -451,7 +459,137 @@ def test_forest_self_join_paths_agree(za, table, forest, monkeypatch):
         assert g.dtype == np.uint64 and g.shape == p.shape and (g == p).all()
 
 
-# ---------------------------------------------------------------- 7. compaction (last: it changes the table)
+# ---------------------------------------------------------------- 7. the graph family
+G_K = 8  # in_k = g_k of the cluster-local graph
+
+
+@functools.lru_cache(maxsize=None)
+def cluster_graph():
+    """(the table as seam_cases sees it, the graph on the host: lines of the probe clusters full, every other line count 0)"""
+    from tests import seam_cases as sc
+    tb = sc.Table(N, D, 0, kind=KIND, group=CL)
+    ids, counts = np.full((N, G_K), NONE, np.uint64), np.zeros(N, np.uint32)
+    for c in PROBE_CLUSTERS:
+        ids[CL * c:CL * c + CL], counts[CL * c:CL * c + CL] = sc.graph(N, G_K, 0, CL * c, CL * c + CL, group=CL)
+    # five chunks of the host entries' pinned staging (the size is the library's: tests/test_seam_reference.py); the info counts no chunks
+    assert -(-ids.nbytes // sc.REFINE_CHUNK_BYTES) == 5 and sc.REFINE_CHUNK_BYTES // 8 == 8388608
+    for b in BOUNDARIES:  # probe rows on both sides of every boundary
+        assert counts[b - 1] == G_K and counts[b] == G_K and (ids[b - 1] < b).all() and (ids[b] >= b).all()
+    ids.setflags(write=False); counts.setflags(write=False)
+    return tb, (ids, counts)
+
+
+def graph_slabs():
+    """the 256 lines around each boundary and the last probe cluster: (first row, lines)"""
+    return [(b - CL, 2 * CL) for b in BOUNDARIES] + [(CL * PROBE_CLUSTERS[-1], CL)]
+
+
+def cluster_lines(graph, c):
+    return graph[0][CL * c:CL * c + CL], graph[1][CL * c:CL * c + CL]
+
+
+def same_lines(got, ref, what):
+    for g, r, name in zip(got, ref, ("first", "second", "third")):
+        assert g.dtype == r.dtype and g.shape == r.shape and (g == r).all(), (what, name, np.argwhere(g != r)[:3].tolist())
+
+
+@pytest.mark.parametrize("rev_k", [0, 4])
+@pytest.mark.parametrize("name", METRICS)
+def test_graph_refinement_slabs(za, table, monkeypatch, name, rev_k):
+    from tests import seam_cases as sc
+    on_path(monkeypatch, None, 0)
+    m, om, omode = metric_of(za, name)
+    tb, graph = cluster_graph()
+    k = 16
+    for first, n in graph_slabs():
+        got = table.knn_graph_refine(graph, k, m, first, n, reverse=rev_k)
+        info = table.knn_refine_rev_info() if rev_k else table.knn_refine_info()
+        assert info["rows_live"] == N and info["lines"] == n and info["in_k"] == G_K and info["k"] == k and info["launches"] == 1, info
+        assert info["keyed"] > n * G_K and (got[2] == k).all()
+        for c in range(first // CL, (first + n) // CL):
+            ref, _ = sc.local_refine(tb, *cluster_lines(graph, c), c, k, om, omode, rev_k)
+            same_lines(tuple(a[CL * c - first:CL * c - first + CL] for a in got), ref, (name, rev_k, c))
+
+
+def test_graph_reverse_slabs(table):
+    from tests import seam_cases as sc
+    tb, graph = cluster_graph()
+    rev_k = 4
+    for first, n in graph_slabs():
+        got = table.knn_graph_reverse(graph, rev_k, first, n)
+        info = table.knn_reverse_info()
+        assert info["rows_live"] == N and info["lines"] == n and info["edges"] == len(PROBE_CLUSTERS) * CL * G_K and info["max_degree"] == G_K, info
+        assert info["kept"] == int(got[1].sum()) > 0 and (got[2] == G_K).all()
+        for c in range(first // CL, (first + n) // CL):
+            ref, _ = sc.local_reverse(tb, *cluster_lines(graph, c), c, rev_k)
+            same_lines(tuple(a[CL * c - first:CL * c - first + CL] for a in got), ref, ("reverse", c))
+
+
+@pytest.mark.parametrize("rev_k", [0, 4])
+@pytest.mark.parametrize("name", METRICS)
+def test_graph_descent_whole_table(za, table, monkeypatch, name, rev_k):
+    """the whole table on the device entry: the probe clusters' lines against the local reference, every other count 0"""
+    import torch
+    from tests import seam_cases as sc
+    on_path(monkeypatch, None, 0)
+    m, om, omode = metric_of(za, name)
+    tb, graph = cluster_graph()
+    k, rounds = 8, 3
+    d_ids, d_counts = torch.from_numpy(graph[0].view(np.int64).copy()).cuda(), torch.from_numpy(graph[1].view(np.int32).copy()).cuda()
+    out = [torch.full((N, k), 0x5A5A5A5A, dtype=torch.int64, device="cuda"), torch.full((N, k), 0x5A5A5A5A, dtype=torch.int64, device="cuda"),
+           torch.full((N,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")]
+    torch.cuda.synchronize()
+    table.knn_graph_descent_device(d_ids.data_ptr(), d_counts.data_ptr(), G_K, rev_k, k, rounds, m, *[o.data_ptr() for o in out])
+    info = table.knn_descent_info()
+    assert info["rows_live"] == N and info["rounds_run"] >= 2 and info["active_round"][0] == N, info
+    total = 0
+    for c in PROBE_CLUSTERS:
+        got = (out[0][CL * c:CL * c + CL].cpu().numpy().view(np.uint64), out[1][CL * c:CL * c + CL].cpu().numpy().view(np.uint64),
+               out[2][CL * c:CL * c + CL].cpu().numpy().view(np.uint32))
+        same_lines(got, sc.local_descent(tb, *cluster_lines(graph, c), c, rev_k, k, info["rounds_run"], om, omode), (name, rev_k, c))
+        total += int(got[2].sum())
+    assert int(out[2].sum(dtype=torch.int64)) == total == len(PROBE_CLUSTERS) * CL * k
+    assert int((out[0] != -1).sum()) == total and int((out[1] != -1).sum()) == total  # (every other line: no neighbours)
+    del d_ids, d_counts, out
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("name", METRICS)
+def test_graph_search_and_filtered_search(za, table, monkeypatch, name):
+    """the module's 16 probe queries, each seeded inside its cluster; the filter allows the even rows"""
+    from tests import seam_cases as sc
+    on_path(monkeypatch, None, 0)
+    m, om, omode = metric_of(za, name)
+    tb, graph = cluster_graph()
+    Q, cl = probe_queries()
+    top_k, beam, n_seed = 10, 64, 4
+    seeds = np.array([[CL * c + (29 * i + 41 * t + 3) % CL for t in range(n_seed)] for i, c in enumerate(cl.tolist())], np.uint64)
+    even = np.arange(N) % 2 == 0
+    table.set_graph(graph)
+    try:
+        assert table.graph_info()["attached"] == 1 and table.graph_info()["g_rows"] == N and table.graph_info()["g_k"] == G_K
+        for allowed in (None, even):
+            if allowed is None:
+                got = table.search_graph_batch(Q, top_k, m, beam=beam, seeds=seeds)
+                info = table.search_graph_info()
+            else:
+                got = table.search_graph_filtered_batch(Q, top_k, m, allowed, beam=beam, seeds=seeds)
+                info = table.search_graph_filtered_info()
+            fields = ("seeds", "iterations", "expanded", "keyed") + (() if allowed is None else ("offered", "returned"))
+            total = {f: 0 for f in fields}
+            for i, c in enumerate(cl.tolist()):
+                ref, rinfo = sc.local_search(tb, *cluster_lines(graph, c), c, Q[i:i + 1], seeds[i:i + 1], top_k, beam, 1, 0, om, omode, allowed)
+                same_lines(tuple(a[i:i + 1] for a in got), ref, (name, allowed is not None, i))
+                for f in fields:
+                    total[f] += rinfo[f]
+            assert {f: info[f] for f in fields} == total and info["queries"] == len(cl) and info["launches"] == 1, (info, total)
+            assert (got[2] == top_k).all()
+    finally:
+        table.drop_graph()
+    assert table.graph_info()["attached"] == 0
+
+
+# ---------------------------------------------------------------- 8. compaction (last: it changes the table)
 def test_compaction(za, table, monkeypatch):
     on_path(monkeypatch, None, 0)
     m = metric_of(za, "l2sq")[0]

@@ -581,6 +581,49 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_search_graph_filtered_info(h_.get(), &info));
         return info;
     }
+    // Extending the attached graph (zh_index_extend_graph): lines for the rows stored since the attach -- each found by search_graph_batch's walk over
+    // the table before its chunk of `batch` rows, seeds holding n_seed ids per new row -- and the old lines those name re-ranked to name them.  Rows of
+    // one chunk never name each other (batch = 1 is the sequential rule).  g_k <= beam, 1 <= batch <= ZH_GRAPH_EXTEND_MAX_BATCH.
+    template <class Met>
+    zh_graph_extend_info extend_graph(const std::vector<Id> &seeds, std::size_t n_seed, const Met &metric, std::size_t beam = 64, std::size_t width = 1,
+                                      std::size_t max_iters = 0, std::size_t batch = ZH_GRAPH_EXTEND_MAX_BATCH) {
+        const std::uint64_t n_new = n_seed ? seeds.size() / n_seed : 0;
+        if (seeds.size() != n_new * n_seed) throw std::invalid_argument("extend_graph: seeds holds n_seed ids per new row");
+        check(zh_index_extend_graph(h_.get(), n_new ? seeds.data() : nullptr, n_new, n_seed, beam, width, max_iters, batch, Met::metric, metric.mode()));
+        return extend_graph_info();
+    }
+    // ... with the same strided rows of the graph before the call as every new row's seeds: id_base + j * g_rows / n_seed
+    template <class Met>
+    zh_graph_extend_info extend_graph(const Met &metric, std::size_t beam = 64, std::size_t width = 1, std::size_t max_iters = 0, std::size_t n_seed = 32,
+                                      std::size_t batch = ZH_GRAPH_EXTEND_MAX_BATCH) {
+        const std::uint64_t g_rows = graph_info().g_rows, stored = zh_index_stored_rows(h_.get()), base = zh_index_id_base(h_.get());
+        std::vector<Id> seeds((stored > g_rows ? stored - g_rows : 0) * n_seed);
+        for (std::size_t i = 0; i < seeds.size(); i++) seeds[i] = base + (i % n_seed) * g_rows / n_seed;
+        return extend_graph(seeds, n_seed, metric, beam, width, max_iters, batch);
+    }
+    template <class Met>
+    void extend_graph_device(const Id *d_seeds, std::uint64_t n_new, std::size_t n_seed, std::size_t beam, std::size_t width, std::size_t max_iters,
+                             std::size_t batch, const Met &metric, void *stream = nullptr) {
+        check(zh_index_extend_graph_device(h_.get(), d_seeds, n_new, n_seed, beam, width, max_iters, batch, Met::metric, metric.mode(), stream));
+    }
+    zh_graph_extend_info extend_graph_info() const {
+        zh_graph_extend_info info{};
+        check(zh_index_extend_graph_info(h_.get(), &info));
+        return info;
+    }
+    // The attached table read back (zh_index_get_graph) as set_graph takes it: ids [n * g_k] with 2^64-1 tails, counts [n]
+    std::pair<std::vector<Id>, std::vector<std::uint32_t>> get_graph(std::uint64_t first_row, std::uint64_t n) const {
+        const std::size_t g_k = graph_info().g_k;
+        std::vector<Id> ids(n * g_k + 1);
+        std::vector<std::uint32_t> counts(n + 1);
+        check(zh_index_get_graph(h_.get(), first_row, n, ids.data(), counts.data()));
+        ids.resize(n * g_k);
+        counts.resize(n);
+        return {std::move(ids), std::move(counts)};
+    }
+    void get_graph_device(std::uint64_t first_row, std::uint64_t n, Id *d_out_ids, std::uint32_t *d_out_counts, void *stream = nullptr) const {
+        check(zh_index_get_graph_device(h_.get(), first_row, n, d_out_ids, d_out_counts, stream));
+    }
     // The capped reverse graph on its own (zh_knn_graph_reverse): element i = up to rev_k of the live rows that name stored row first_row + i and
     // that its own line does not name, in (hash, row) order; degree[i] = its uncapped in-degree.  No metric, no keys, no forest.
     struct ReverseGraph {

@@ -42,6 +42,9 @@
  *   zh_search_graph_batch[_device]       (new) beam search over that graph: a best-first walk from caller-given seeds, exact keys, an approximate
  *                                        visited set
  *   zh_search_graph_filtered_batch[_device] (new) the same walk, answered from the rows a caller's bitmap allows among those it keyed
+ *   zh_index_extend_graph[_device]       (new) lines for the rows stored since the attach, found by that walk, and the old lines they should be in
+ *                                        re-ranked to name them: the attached graph follows add / append without a rebuild
+ *   zh_index_get_graph[_device]          (new) the attached table read back as ids and counts
  *   zh_self_join_forest[_device]         (new) every pair of leaf-mates whose key is at or below one threshold key, each pair once: exact keys,
  *                                        approximate candidates
  *   zh_search_range_forest_batch[_device] (new) every member of the leaves the walk visits for a query whose key is at or below the query's
@@ -824,7 +827,8 @@ ZH_API int zh_knn_graph_descent_info(const zh_index *idx, zh_knn_descent_info *o
  * zh_knn_graph_refine takes them, and keeps it on the device as the table of u32 row numbers that call makes: entries past the line's count,
  * outside [id_base, id_base + stored rows) (2^64-1 included), naming a removed row or repeated inside their line are masked.  N'(p) at search time
  * is the LIVE rows among line p's unmasked entries, judged against the live rows of the moment of the search: a zh_index_remove after the attach
- * needs no re-attach, a removed row is no candidate and is never expanded, and a row p >= g_rows (appended since the attach) has an empty line.
+ * needs no re-attach, a removed row is no candidate and is never expanded, and a row p >= g_rows (appended since the attach) has an empty line
+ * until zh_index_extend_graph gives it one.
  * A second set_graph replaces the first; zh_index_drop_graph releases it (ZH_OK with none attached); zh_index_graph_info reports it.  The graph
  * survives append, add, remove, deduplicate, build and set_forest -- rows keep their numbers -- and is dropped by zh_index_compact (rows move) and
  * zh_index_clear.  It is never part of a snapshot: a loaded index has none.  The host entry streams the ids through the pinned chunks of
@@ -927,6 +931,61 @@ typedef struct zh_graph_filtered_info {  /* the most recent zh_search_graph_filt
     uint64_t returned;      /* the sum of out_counts */
 } zh_graph_filtered_info;
 ZH_API int zh_search_graph_filtered_info(const zh_index *idx, zh_graph_filtered_info *out);
+
+/* Extending the attached graph (new): lines for the rows stored since the attach, and reverse edges to them.  G = the rows the attached table
+ * covers (zh_graph_info.g_rows), N = the stored rows at the time of the call, g_k = the table's width.  The new rows G .. N-1 are taken in chunks
+ * of `batch` consecutive stored rows: chunk c is [lo, hi), lo = G + c batch, hi = min(N, lo + batch).  While chunk c is processed the table covers
+ * [0, lo): the earlier chunks' lines and every change they made to older lines included.  A chunk has two steps.
+ *   1. Search.  For every live row a of [lo, hi): zh_search_graph_batch's walk, bit for bit, with stored row a as the query, the [lo][g_k] table,
+ *      liveness as of now, and the caller's n_seed seeds for a (seeds [n_new][n_seed], line a - G) -- but a seed naming a row >= lo is ignored: such
+ *      a row has no line yet.  That covers a itself and the rows of its chunk, and no line names a row >= lo, so a line never holds its own row.
+ *      line(a) = the first min(g_k, |B|) rows of the final beam in (key, id) order.  A removed row of the chunk gets an empty line.
+ *   2. Reverse edges.  For every live row r < lo let R(r) = the live rows a of the chunk whose line(a) holds r.  If R(r) is empty, line r is left
+ *      untouched word for word: masked entries and entries naming rows removed since the attach stay.  Otherwise line r becomes the first g_k of
+ *      L'(r) union R(r) by (key_r(x), x), the rest UINT32_MAX: L'(r) = the kept entries of line r that are live now, key_r(x) = the key
+ *      zh_search_exact_batch gives stored row x against a query equal to stored row r (zh_knn_graph's orientation).
+ * ROWS OF ONE CHUNK NEVER NAME EACH OTHER, and a chunk's old rows are re-ranked against that chunk only: the price of walking a chunk's rows in
+ * parallel.  batch = 1 is the fully sequential rule.  zh_index_get_graph, a round of zh_knn_graph_descent over it and zh_index_set_graph close
+ * what is left.  The metric is the caller's, as for the search: the graph records none.
+ * Limits: 1 <= g_k <= beam <= ZH_GRAPH_MAX_BEAM (the walk's top_k is g_k), width * g_k <= 256, 1 <= n_seed <= ZH_GRAPH_MAX_SEEDS, max_iters <=
+ * ZH_GRAPH_MAX_ITERS, 1 <= batch <= ZH_GRAPH_EXTEND_MAX_BATCH (a re-ranked line then holds at most 64 + 1024 candidates).  Judged before any
+ * device is touched, in this order: a null index, null seeds with n_new > 0, an unknown metric, a zero beam, width, n_seed or batch (ZH_EINVAL),
+ * then the limits (ZH_ELIMIT: beam, n_seed, width > 256, max_iters, batch); under the lock: no attached graph (ZH_ESTATE), g_k > beam, width * g_k
+ * > 256, a table of 2^31 rows or more (ZH_ELIMIT), n_new != N - G (ZH_EINVAL: the table changed between the caller's sizing and the call).  N == G
+ * (and n_new == 0) is ZH_OK with nothing done.  The new [N][g_k] table is made beside the old one -- a copy, then the chunks -- and swapped in at
+ * the end: a failed call leaves what was attached.  Afterwards zh_graph_info.g_rows = N, and every rule of the attached graph above holds for the
+ * extended one as it is.  The call takes the lock as a mutation does; the device entry takes seeds in device memory and is enqueued on `stream`
+ * (NULL = the index's own), complete on return.  Device scratch is per call and released before return: the walk's staged chunk (per row of a
+ * chunk 4 dim + 8 n_seed + 16 g_k + 8 bytes), 16 bytes per stored row of in-degrees, cursors and offsets, 4 bytes per stored row of norms
+ * (cosine), 8 batch g_k bytes of edges and touched rows, and for the host entry the staged seeds.  DESIGN.md s27. */
+#define ZH_GRAPH_EXTEND_MAX_BATCH 1024u
+ZH_API int zh_index_extend_graph(zh_index *idx, const uint64_t *seeds, uint64_t n_new, size_t n_seed, size_t beam, size_t width, size_t max_iters,
+                                 size_t batch, int metric, int cosine_mode);
+ZH_API int zh_index_extend_graph_device(zh_index *idx, const uint64_t *d_seeds, uint64_t n_new, size_t n_seed, size_t beam, size_t width,
+                                        size_t max_iters, size_t batch, int metric, int cosine_mode, void *stream);
+typedef struct zh_graph_extend_info {  /* the most recent zh_index_extend_graph* call on this index */
+    uint64_t rows_added;       /* live new rows: each got a line */
+    uint64_t rows_removed;     /* new rows that were removed already: each got an empty line */
+    uint64_t chunks;
+    uint64_t seeds;            /* the next five: zh_graph_search_info's, summed over the walks of the live new rows */
+    uint64_t iterations;
+    uint64_t expanded;
+    uint64_t keyed;
+    uint64_t capped;
+    uint64_t reverse_rows;     /* old rows re-ranked, summed over the chunks */
+    uint64_t reverse_offered;  /* the sum of |R(r)| */
+    uint64_t reverse_kept;     /* chunk rows that ended inside a re-ranked line */
+    uint64_t launches;         /* launches of the walk and of the re-ranking kernel */
+} zh_graph_extend_info;
+ZH_API int zh_index_extend_graph_info(const zh_index *idx, zh_graph_extend_info *out);
+/* Reading the attached table (new).  Line i of out_ids [n][g_k] holds the kept entries of line first_row + i in table order, compacted to the front
+ * as id_base + row; out_counts[i] is their number and the tail is 2^64-1.  Entries are as stored: a row removed since the attach is still listed
+ * (the search and zh_knn_graph_refine skip it themselves).  zh_index_set_graph of the answer attaches the same kept entries in the same order,
+ * less those naming rows removed since (which it masks, and which no walk saw): every search answers alike, and a table of compact lines (every line
+ * the extension wrote is one) without such entries comes back word for word.  A null index, null outputs with n > 0 (ZH_EINVAL); under
+ * the lock: no graph (ZH_ESTATE), first_row + n > g_rows (ZH_EINVAL).  n = 0 is ZH_OK.  The host entry stages slabs of 2^18 lines. */
+ZH_API int zh_index_get_graph(zh_index *idx, uint64_t first_row, uint64_t n, uint64_t *out_ids, uint32_t *out_counts);
+ZH_API int zh_index_get_graph_device(zh_index *idx, uint64_t first_row, uint64_t n, uint64_t *d_out_ids, uint32_t *d_out_counts, void *stream);
 
 /* ---- forest self-join (new): all near-duplicate pairs AMONG LEAF-MATES ---------------------------------------------------------------------
  * zh_self_join multiplies every tile of the table by every tile at or above it; this call multiplies a leaf only by itself.  Arguments, key,

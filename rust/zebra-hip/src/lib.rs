@@ -274,6 +274,23 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_graph_extend_info {
+        pub rows_added: u64,
+        pub rows_removed: u64,
+        pub chunks: u64,
+        pub seeds: u64,
+        pub iterations: u64,
+        pub expanded: u64,
+        pub keyed: u64,
+        pub capped: u64,
+        pub reverse_rows: u64,
+        pub reverse_offered: u64,
+        pub reverse_kept: u64,
+        pub launches: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_join_forest_info {
         pub rows_live: u64,
         pub trees: u32,
@@ -468,6 +485,14 @@ pub mod ffi {
                                                      d_filter_words: *const u32, n_bits: u64, d_out_ids: *mut u64, d_out_keys: *mut u64,
                                                      d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_search_graph_filtered_info(idx: *const zh_index, out: *mut zh_graph_filtered_info) -> c_int;
+        pub fn zh_index_extend_graph(idx: *mut zh_index, seeds: *const u64, n_new: u64, n_seed: usize, beam: usize, width: usize, max_iters: usize,
+                                     batch: usize, metric: c_int, cosine_mode: c_int) -> c_int;
+        pub fn zh_index_extend_graph_device(idx: *mut zh_index, d_seeds: *const u64, n_new: u64, n_seed: usize, beam: usize, width: usize,
+                                            max_iters: usize, batch: usize, metric: c_int, cosine_mode: c_int, stream: *mut c_void) -> c_int;
+        pub fn zh_index_extend_graph_info(idx: *const zh_index, out: *mut zh_graph_extend_info) -> c_int;
+        pub fn zh_index_get_graph(idx: *mut zh_index, first_row: u64, n: u64, out_ids: *mut u64, out_counts: *mut u32) -> c_int;
+        pub fn zh_index_get_graph_device(idx: *mut zh_index, first_row: u64, n: u64, d_out_ids: *mut u64, d_out_counts: *mut u32,
+                                         stream: *mut c_void) -> c_int;
         pub fn zh_self_join_forest(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, out_a: *mut u64,
                                    out_b: *mut u64, out_keys: *mut u64, out_total: *mut u64) -> c_int;
         pub fn zh_self_join_forest_device(idx: *mut zh_index, max_key: u64, metric: c_int, cosine_mode: c_int, capacity: u64, d_out_a: *mut u64,
@@ -1058,7 +1083,7 @@ impl<const N: usize> LSHIndex<N> {
     }
 
     /// (new) make the graph `search_graph_batch` walks and keep it on the device: the forest graph, NN-descent (knn_graph_descent's calls), then
-    /// zh_index_set_graph over every stored row.  Vectors added later are found only as seeds until the next build_graph; removed ones are
+    /// zh_index_set_graph over every stored row.  Vectors added later are found only as seeds until extend_graph (or the next build_graph); removed ones are
     /// skipped at once; compact() and clear() drop the graph
     pub fn build_graph<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
         &self,
@@ -1083,6 +1108,41 @@ impl<const N: usize> LSHIndex<N> {
         }
         check(unsafe { ffi::zh_index_set_graph(self.hip.0, rids.as_ptr(), rcounts.as_ptr(), stored as u64, k) })?;
         self.graph_info()
+    }
+
+    /// (new) lines for the vectors added since build_graph (or the last extend_graph), and the old lines re-ranked to name them
+    /// (zh_index_extend_graph): every new vector starts its walk from the same n_seed strided rows of the graph before the call; the new rows go in
+    /// chunks of `batch` (<= 1024), and the rows of one chunk never name each other.  k <= beam
+    #[allow(clippy::too_many_arguments)]
+    pub fn extend_graph<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        beam: usize,
+        width: usize,
+        max_iters: usize,
+        n_seed: usize,
+        batch: usize,
+        metric: &Met,
+    ) -> anyhow::Result<ffi::zh_graph_extend_info> {
+        let _t = self.ids.read().unwrap();
+        let g_rows = self.graph_info()?.g_rows;
+        let n_new = unsafe { ffi::zh_index_stored_rows(self.hip.0) }.saturating_sub(g_rows);
+        let seeds: Vec<u64> = (0..n_new as usize * n_seed).map(|i| ((i % n_seed) as u64) * g_rows / n_seed.max(1) as u64).collect();
+        check(unsafe {
+            ffi::zh_index_extend_graph(self.hip.0, if n_new > 0 { seeds.as_ptr() } else { std::ptr::null() }, n_new, n_seed, beam, width, max_iters, batch,
+                                       Met::METRIC, metric.param())
+        })?;
+        let mut info = ffi::zh_graph_extend_info::default();
+        check(unsafe { ffi::zh_index_extend_graph_info(self.hip.0, &mut info) })?;
+        Ok(info)
+    }
+
+    /// (new) the attached table read back as rows (zh_index_get_graph): per stored row of the graph the rows its line names, in table order
+    pub fn get_graph(&self) -> anyhow::Result<Vec<Vec<u64>>> {
+        let g = self.graph_info()?;
+        let (n, k) = (g.g_rows as usize, g.g_k as usize);
+        let (mut ids, mut counts) = (vec![0u64; n * k + 1], vec![0u32; n + 1]);
+        check(unsafe { ffi::zh_index_get_graph(self.hip.0, 0, n as u64, ids.as_mut_ptr(), counts.as_mut_ptr()) })?;
+        Ok((0..n).map(|i| ids[i * k..i * k + counts[i] as usize].to_vec()).collect())
     }
 
     /// (new) release the attached graph (zh_index_drop_graph)

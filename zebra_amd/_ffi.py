@@ -209,6 +209,16 @@ class SearchGraphFilteredInfo(C.Structure):
 
 
 GRAPH_MAX_BEAM, GRAPH_MAX_SEEDS, GRAPH_MAX_ITERS, GRAPH_BATCH = 256, 64, 65535, 16384  # ZH_GRAPH_*
+GRAPH_EXTEND_MAX_BATCH = 1024  # ZH_GRAPH_EXTEND_MAX_BATCH
+
+
+class GraphExtendInfo(C.Structure):
+    _fields_ = [("rows_added", C.c_uint64), ("rows_removed", C.c_uint64), ("chunks", C.c_uint64), ("seeds", C.c_uint64), ("iterations", C.c_uint64),
+                ("expanded", C.c_uint64), ("keyed", C.c_uint64), ("capped", C.c_uint64), ("reverse_rows", C.c_uint64), ("reverse_offered", C.c_uint64),
+                ("reverse_kept", C.c_uint64), ("launches", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class JoinForestInfo(C.Structure):
@@ -328,6 +338,11 @@ SYMBOLS = [
     ("zh_search_graph_filtered_batch", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _u64, _vp, _vp, _vp]),
     ("zh_search_graph_filtered_batch_device", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _u64, _vp, _vp, _vp, _vp]),
     ("zh_search_graph_filtered_info", _i, [_vp, _vp]),
+    ("zh_index_extend_graph", _i, [_vp, _vp, _u64, _sz, _sz, _sz, _sz, _sz, _i, _i]),
+    ("zh_index_extend_graph_device", _i, [_vp, _vp, _u64, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp]),
+    ("zh_index_extend_graph_info", _i, [_vp, _vp]),
+    ("zh_index_get_graph", _i, [_vp, _u64, _u64, _vp, _vp]),
+    ("zh_index_get_graph_device", _i, [_vp, _u64, _u64, _vp, _vp, _vp]),
     ("zh_self_join_forest", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_device", _i, [_vp, _u64, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("zh_self_join_forest_info", _i, [_vp, _vp]),

@@ -448,6 +448,12 @@ struct zh_index {
     DevBuf gs_QQ, gs_ctr, gs_Q, gs_seeds, gs_oids, gs_okeys, gs_ocounts;
     zh_graph_search_info gs_info{};  // (stats_mu)
     zh_graph_filtered_info gf_info{};  // (stats_mu)
+    // the graph extension's per-call scratch beside graph search's (all released before the call returns): a chunk's gathered seed lines and the
+    // walk's answer for it, every stored row's squared norm, in-degrees, fill cursors, 64-bit offsets and the scan's block sums over the rows before
+    // the chunk, the chunk's transposed edges, the touched rows, {the walk's five counters, touched rows of the chunk, rows re-ranked, offered, kept,
+    // the transposition's two}; zh_index_get_graph's host entry stages through graph search's gs_oids / gs_ocounts
+    DevBuf ge_seeds, ge_ids, ge_keys, ge_counts, ge_qq, ge_deg, ge_cur, ge_off, ge_sums, ge_csr, ge_touched, ge_ctr;
+    zh_graph_extend_info ge_info{};  // (stats_mu)
     // What the index remembers of paths that did not pay on its data, and how long its forest has stood.
     struct Fallbacks {
         // Both derived views of the forest cost host time per build (a traversal of every node: ~0.35 s for the 13M nodes of a 1M-row forest at the
@@ -3589,7 +3595,7 @@ static int score_param(int metric, int mode) { return (metric == ZH_COSINE || me
 // index holds only the live-row views (live_dev's list and bitmap survive every call; zh_index_destroy frees them).  Every family scans with the exact
 // search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's, the forest range search with
 // the range search's and the forest join's, the cross-join (all on its LEFT index) with the join's and its own views.
-enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024, SCR_ND = 2048, SCR_GS = 4096 };  // one bit per list
+enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024, SCR_ND = 2048, SCR_GS = 4096, SCR_GE = 8192 };  // one bit per list
 enum : unsigned {
     SCRATCH_EXACT = SCR_EX,
     SCRATCH_FILTER = SCR_FL | SCRATCH_EXACT,
@@ -3603,6 +3609,7 @@ enum : unsigned {
     SCRATCH_GRAPH_ATTACH = SCR_RF,  // (the host entry's counts and staged chunk of ids)
     SCRATCH_GSEARCH = SCR_GS,
     SCRATCH_GSEARCH_FILTERED = SCR_GS | SCR_FL,  // (the filter pass writes the filtered exact search's buffers)
+    SCRATCH_GEXTEND = SCR_GE | SCR_GS,  // (the walk's staged queries, their norms and the host entry's seeds are graph search's)
     SCRATCH_FJOIN = SCR_FJ | SCRATCH_JOIN | SCRATCH_FKNN,
     SCRATCH_FRANGE = SCR_FR | SCRATCH_RANGE | SCRATCH_FJOIN,
     SCRATCH_XJOIN = SCR_XJ | SCRATCH_JOIN,  // (on the left index)
@@ -3632,6 +3639,8 @@ static void release_scratch(zh_index *ix, unsigned families) {
     drop(SCR_ND, {&ix->nd_tab[0], &ix->nd_tab[1], &ix->nd_key[0], &ix->nd_key[1], &ix->nd_uni[0], &ix->nd_uni[1], &ix->nd_mask, &ix->nd_list, &ix->nd_qq,
                   &ix->nd_ctr});
     drop(SCR_GS, {&ix->gs_QQ, &ix->gs_ctr, &ix->gs_Q, &ix->gs_seeds, &ix->gs_oids, &ix->gs_okeys, &ix->gs_ocounts});
+    drop(SCR_GE, {&ix->ge_seeds, &ix->ge_ids, &ix->ge_keys, &ix->ge_counts, &ix->ge_qq, &ix->ge_deg, &ix->ge_cur, &ix->ge_off, &ix->ge_sums, &ix->ge_csr,
+                  &ix->ge_touched, &ix->ge_ctr});
     drop(SCR_FJ, {&ix->fj_leafof, &ix->fj_pieces, &ix->fj_linel, &ix->fj_linek, &ix->fj_segs, &ix->fj_cand});
     drop(SCR_FR, {&ix->fr_counts, &ix->fr_inline, &ix->fr_rowbase, &ix->fr_candbase, &ix->fr_visitbase, &ix->fr_totals, &ix->fr_leafcount, &ix->fr_leaffill,
                   &ix->fr_groupbase, &ix->fr_grouprowbase, &ix->fr_loghead, &ix->fr_logctl, &ix->fr_logpool, &ix->fr_visits, &ix->fr_groups, &ix->fr_groupoff,
@@ -6084,6 +6093,190 @@ extern "C" int zh_search_graph_filtered_batch(zh_index *ix, const float *q, size
 
 extern "C" int zh_search_graph_filtered_info(const zh_index *ix, zh_graph_filtered_info *out) {
     return get_info(ix, &zh_index::gf_info, out, "zh_search_graph_filtered_info");
+}
+
+// ------------------------------------------------------------------------------------------------
+// extending the attached graph over the rows stored since the attach, and reading the table back (zh_gextend.hip).  DESIGN.md s27
+// ------------------------------------------------------------------------------------------------
+// judged before any device is touched, in this order of kinds: null index, null seeds of new rows, the metric, a zero beam / width / n_seed / batch,
+// then the limits: beam, n_seed, width (against 256: g_k is only known under the lock), max_iters, batch
+static int gextend_args(zh_index *ix, const void *seeds, uint64_t n_new, size_t n_seed, size_t beam, size_t width, size_t max_iters, size_t batch, int metric,
+                        int mode, const char *who) {
+    if (!ix || (n_new && !seeds)) return fail(ZH_EINVAL, "%s: null argument", who);
+    const int rc = check_metric(metric, mode);
+    if (rc) return rc;
+    if (!beam) return fail(ZH_EINVAL, "%s: beam is 0", who);
+    if (!width) return fail(ZH_EINVAL, "%s: width is 0", who);
+    if (!n_seed) return fail(ZH_EINVAL, "%s: n_seed is 0", who);
+    if (!batch) return fail(ZH_EINVAL, "%s: batch is 0", who);
+    if (beam > ZH_GRAPH_MAX_BEAM) return fail(ZH_ELIMIT, "%s: beam %zu > ZH_GRAPH_MAX_BEAM (%u)", who, beam, ZH_GRAPH_MAX_BEAM);
+    if (n_seed > ZH_GRAPH_MAX_SEEDS) return fail(ZH_ELIMIT, "%s: n_seed %zu > ZH_GRAPH_MAX_SEEDS (%u)", who, n_seed, ZH_GRAPH_MAX_SEEDS);
+    if (width > 256) return fail(ZH_ELIMIT, "%s: width %zu > 256", who, width);
+    if (max_iters > ZH_GRAPH_MAX_ITERS) return fail(ZH_ELIMIT, "%s: max_iters %zu > ZH_GRAPH_MAX_ITERS (%u)", who, max_iters, ZH_GRAPH_MAX_ITERS);
+    if (batch > ZH_GRAPH_EXTEND_MAX_BATCH) return fail(ZH_ELIMIT, "%s: batch %zu > ZH_GRAPH_EXTEND_MAX_BATCH (%u)", who, batch, ZH_GRAPH_EXTEND_MAX_BATCH);
+    return ZH_OK;
+}
+
+// The chunks (under mu, exclusive; exact_live_rows has run; N > G): tab [N][g_k] receives the old table, then chunk by chunk the new lines and the
+// re-ranked old ones.  dSeeds: the [N - G][n_seed] seeds on the device.  Everything is enqueued on s and nothing is waited for but the counters.
+static int gextend_chunks(zh_index *ix, uint32_t *tab, const uint64_t *dSeeds, uint32_t n_seed, uint32_t beam, uint32_t width, uint32_t max_iters, uint32_t batch,
+                          int metric, int mode, hipStream_t s, zh_graph_extend_info *inf) {
+    const uint64_t G = ix->graph.rows, N = ix->n_rows;
+    const uint32_t g_k = ix->graph.k, d = ix->opt.dim;
+    const int param = score_param(metric, mode);
+    const size_t nb_max = (size_t)std::min<uint64_t>(batch, N - G), edges = nb_max * g_k;
+    int rc;
+    if ((rc = ix->gs_Q.ensure(nb_max * d * 4)) || (rc = ix->gs_QQ.ensure(nb_max * 4)) || (rc = ix->ge_seeds.ensure(nb_max * n_seed * 8)) ||
+        (rc = ix->ge_ids.ensure(edges * 8)) || (rc = ix->ge_keys.ensure(edges * 8)) || (rc = ix->ge_counts.ensure(nb_max * 4)) || (rc = ix->ge_deg.ensure(N * 4)) ||
+        (rc = ix->ge_cur.ensure(N * 4)) || (rc = ix->ge_off.ensure((N + 1) * 8)) || (rc = ix->ge_sums.ensure((N / 4096 + 1) * 8)) || (rc = ix->ge_csr.ensure(edges * 4)) ||
+        (rc = ix->ge_touched.ensure(edges * 4)) || (rc = ix->ge_ctr.ensure(88)))
+        return rc;
+    unsigned long long *dCtr = ix->ge_ctr.as<unsigned long long>();  // [0..4] the walk's, [5] a chunk's touched rows, [6..8] re-ranked / offered / kept, [9..10] the transposition's
+    HIPCHK(hipMemsetAsync(dCtr, 0, 88, s));
+    if (G) HIPCHK(hipMemcpyAsync(tab, ix->graph.tab.p, (size_t)G * g_k * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemsetAsync(tab + (size_t)G * g_k, 0xFF, (size_t)(N - G) * g_k * 4, s));  // (a removed new row's line stays empty)
+    if (metric == ZH_COSINE) {  // every stored row's squared norm: a re-ranked row's, as zh_launch_qnorm gives it to the exact search
+        if ((rc = ix->ge_qq.ensure(N * 4))) return rc;
+        for (uint64_t r0 = 0; r0 < N; r0 += 1ull << 30)
+            HIPCHK(zh_launch_qnorm(ix->X.as<float>() + r0 * d, (uint32_t)std::min<uint64_t>(1ull << 30, N - r0), d, ix->ge_qq.as<float>() + r0, s));
+    }
+    const uint32_t *dBits = ix->live_dev.bits.as<uint32_t>();
+    LiveCursor live;
+    for (uint64_t lo = G; lo < N; lo += batch) {
+        const uint64_t hi = std::min<uint64_t>(N, lo + batch), l0 = live_before(ix, lo, &live), l1 = live_before(ix, hi, &live);
+        const uint32_t B = (uint32_t)(l1 - l0);
+        inf->chunks++;
+        inf->rows_added += B;
+        inf->rows_removed += (hi - lo) - B;
+        if (!B) continue;
+        const uint32_t *dRows = ix->live_dev.rows.as<uint32_t>() + l0;
+        // ---- step 1: the chunk's live rows as queries of the walk over [0, lo)
+        HIPCHK(zh_launch_join_gather(ix->X.as<float>(), d, dRows, B, ix->gs_Q.as<float>(), s));
+        HIPCHK(zh_launch_gext_seeds(dSeeds, dRows, B, G, n_seed, ix->ge_seeds.as<uint64_t>(), s));
+        if (metric == ZH_COSINE) HIPCHK(zh_launch_qnorm(ix->gs_Q.as<float>(), B, d, ix->gs_QQ.as<float>(), s));
+        HIPCHK(zh_launch_gsearch(ix->X.as<float>(), d, lo, tab, lo, g_k, dBits, nullptr, ix->gs_Q.as<float>(), ix->gs_QQ.as<float>(), ix->ge_seeds.as<uint64_t>(), n_seed,
+                                 B, ix->opt.id_base, g_k, beam, width, max_iters, metric, param, ix->ge_ids.as<uint64_t>(), ix->ge_keys.as<uint64_t>(),
+                                 ix->ge_counts.as<uint32_t>(), dCtr, s));
+        HIPCHK(zh_launch_gext_lines(ix->ge_ids.as<uint64_t>(), ix->ge_counts.as<uint32_t>(), dRows, B, g_k, ix->opt.id_base, tab, s));
+        inf->launches++;
+        if (!lo) continue;  // (no row before the chunk: every line of it is empty)
+        // ---- step 2: the chunk's lines transposed over [0, lo), the rows they name re-ranked
+        HIPCHK(hipMemsetAsync(dCtr + 5, 0, 8, s));
+        HIPCHK(zh_launch_reverse_csr_lines(tab, dBits, lo, g_k, lo, hi - lo, ix->ge_deg.as<uint32_t>(), ix->ge_cur.as<uint32_t>(), ix->ge_off.as<uint64_t>(),
+                                           ix->ge_sums.as<uint64_t>(), ix->ge_csr.as<uint32_t>(), dCtr + 9, s));
+        HIPCHK(zh_launch_gext_rerank(ix->X.as<float>(), d, tab, g_k, lo, (uint32_t)(hi - lo), dBits, ix->ge_qq.as<float>(), ix->ge_off.as<uint64_t>(),
+                                     ix->ge_csr.as<uint32_t>(), ix->ge_touched.as<uint32_t>(), metric, param, dCtr + 5, s));
+        inf->launches++;
+    }
+    unsigned long long ctr[9];
+    HIPCHK(hipMemcpyAsync(ctr, dCtr, sizeof ctr, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    inf->seeds = ctr[0]; inf->iterations = ctr[1]; inf->expanded = ctr[2]; inf->keyed = ctr[3]; inf->capped = ctr[4];
+    inf->reverse_rows = ctr[6]; inf->reverse_offered = ctr[7]; inf->reverse_kept = ctr[8];
+    return ZH_OK;
+}
+
+// both entry points once the arguments have been judged.  host: seeds is a HOST array, staged whole
+static int gextend_call(zh_index *ix, const uint64_t *seeds, uint64_t n_new, uint32_t n_seed, uint32_t beam, uint32_t width, uint32_t max_iters, uint32_t batch,
+                        int metric, int mode, bool host, void *stream, const char *who) {
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix))) return rc;
+    if (!ix->graph.attached) return fail(ZH_ESTATE, "%s: no graph is attached to the index (zh_index_set_graph)", who);
+    const uint64_t G = ix->graph.rows, N = ix->n_rows;
+    const uint32_t g_k = ix->graph.k;
+    if (g_k > beam) return fail(ZH_ELIMIT, "%s: g_k %u > beam %u", who, g_k, beam);
+    if ((uint64_t)width * g_k > 256) return fail(ZH_ELIMIT, "%s: width %u * g_k %u > 256", who, width, g_k);
+    if (N >= (1ull << 31)) return fail(ZH_ELIMIT, "%s: %llu stored rows; graph search serves tables below 2^31 rows", who, (unsigned long long)N);
+    if (n_new != N - G)
+        return fail(ZH_EINVAL, "%s: n_new %llu, but %llu rows were stored since the graph's %llu", who, (unsigned long long)n_new, (unsigned long long)(N - G),
+                    (unsigned long long)G);
+    zh_graph_extend_info inf{};
+    if (N > G) {
+        if ((rc = exact_live_rows(ix))) return rc;
+        ScratchGuard guard{ix, SCRATCH_GEXTEND};
+        const hipStream_t s = call_stream(ix, stream);
+        DevBuf tab;
+        if ((rc = tab.ensure((size_t)N * g_k * 4))) return rc;
+        const uint64_t *dSeeds = seeds;
+        if (host && !(rc = ix->gs_seeds.ensure((size_t)n_new * n_seed * 8))) {
+            if (hipMemcpyAsync(ix->gs_seeds.p, seeds, (size_t)n_new * n_seed * 8, hipMemcpyHostToDevice, s) != hipSuccess) rc = fail(ZH_EHIP, "%s: the seeds' copy failed", who);
+            dSeeds = ix->gs_seeds.as<uint64_t>();
+        }
+        if (!rc) rc = gextend_chunks(ix, tab.as<uint32_t>(), dSeeds, n_seed, beam, width, max_iters, batch, metric, mode, s, &inf);
+        if (rc) {  // what was attached stays
+            hipStreamSynchronize(s);
+            tab.release();
+            return rc;
+        }
+        ix->graph.drop();
+        ix->graph.tab = tab;
+        ix->graph.mark_attached(N, g_k);
+    }
+    std::lock_guard<std::mutex> ls(ix->stats_mu);
+    ix->ge_info = inf;
+    return ZH_OK;
+}
+
+extern "C" int zh_index_extend_graph_device(zh_index *ix, const uint64_t *d_seeds, uint64_t n_new, size_t n_seed, size_t beam, size_t width, size_t max_iters,
+                                            size_t batch, int metric, int mode, void *stream) {
+    const char *who = "zh_index_extend_graph_device";
+    int rc = gextend_args(ix, d_seeds, n_new, n_seed, beam, width, max_iters, batch, metric, mode, who);
+    if (rc) return rc;
+    return gextend_call(ix, d_seeds, n_new, (uint32_t)n_seed, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, (uint32_t)batch, metric, mode, false, stream, who);
+}
+
+extern "C" int zh_index_extend_graph(zh_index *ix, const uint64_t *seeds, uint64_t n_new, size_t n_seed, size_t beam, size_t width, size_t max_iters, size_t batch,
+                                     int metric, int mode) {
+    const char *who = "zh_index_extend_graph";
+    int rc = gextend_args(ix, seeds, n_new, n_seed, beam, width, max_iters, batch, metric, mode, who);
+    if (rc) return rc;
+    return gextend_call(ix, seeds, n_new, (uint32_t)n_seed, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, (uint32_t)batch, metric, mode, true, nullptr, who);
+}
+
+extern "C" int zh_index_extend_graph_info(const zh_index *ix, zh_graph_extend_info *out) {
+    return get_info(ix, &zh_index::ge_info, out, "zh_index_extend_graph_info");
+}
+
+#define ZH_GRAPH_READ_SLAB (1ull << 18)  // lines the host entry of zh_index_get_graph stages at a time
+// both read-back entry points.  host: the outputs are HOST arrays, answered slab by slab through graph search's staging
+static int graph_read(zh_index *ix, uint64_t first_row, uint64_t n, uint64_t *out_ids, uint32_t *out_counts, bool host, void *stream, const char *who) {
+    if (!ix || (n && (!out_ids || !out_counts))) return fail(ZH_EINVAL, "%s: null argument", who);
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix))) return rc;
+    if (!ix->graph.attached) return fail(ZH_ESTATE, "%s: no graph is attached to the index (zh_index_set_graph)", who);
+    if (first_row > ix->graph.rows || n > ix->graph.rows - first_row)
+        return fail(ZH_EINVAL, "%s: lines [%llu, %llu + %llu) of a graph of %llu", who, (unsigned long long)first_row, (unsigned long long)first_row,
+                    (unsigned long long)n, (unsigned long long)ix->graph.rows);
+    if (!n) return ZH_OK;
+    const uint32_t g_k = ix->graph.k;
+    const hipStream_t s = call_stream(ix, stream);
+    const uint32_t *tab = ix->graph.tab.as<uint32_t>();
+    if (!host) {
+        HIPCHK(zh_launch_gext_read(tab, g_k, first_row, n, ix->opt.id_base, out_ids, out_counts, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return ZH_OK;
+    }
+    ScratchGuard guard{ix, SCRATCH_GSEARCH};
+    const uint64_t slab = std::min<uint64_t>(n, ZH_GRAPH_READ_SLAB);
+    if ((rc = ix->gs_oids.ensure((size_t)slab * g_k * 8)) || (rc = ix->gs_ocounts.ensure((size_t)slab * 4))) return rc;
+    for (uint64_t r0 = 0; r0 < n; r0 += slab) {
+        const uint64_t m = std::min(slab, n - r0);
+        HIPCHK(zh_launch_gext_read(tab, g_k, first_row + r0, m, ix->opt.id_base, ix->gs_oids.as<uint64_t>(), ix->gs_ocounts.as<uint32_t>(), s));
+        HIPCHK(hipMemcpyAsync(out_ids + r0 * g_k, ix->gs_oids.p, (size_t)m * g_k * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out_counts + r0, ix->gs_ocounts.p, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return ZH_OK;
+}
+
+extern "C" int zh_index_get_graph(zh_index *ix, uint64_t first_row, uint64_t n, uint64_t *out_ids, uint32_t *out_counts) {
+    return graph_read(ix, first_row, n, out_ids, out_counts, true, nullptr, "zh_index_get_graph");
+}
+
+extern "C" int zh_index_get_graph_device(zh_index *ix, uint64_t first_row, uint64_t n, uint64_t *d_out_ids, uint32_t *d_out_counts, void *stream) {
+    return graph_read(ix, first_row, n, d_out_ids, d_out_counts, false, stream, "zh_index_get_graph_device");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -516,6 +516,9 @@ hipError_t zh_launch_refine_lines(const float *dX, uint32_t d, const uint32_t *d
 // dCsr: n_rows * in_k words at most
 hipError_t zh_launch_reverse_csr(const uint32_t *dTab, const uint32_t *dBits, uint64_t n_rows, uint32_t in_k, uint32_t *dDeg, uint32_t *dCur, uint64_t *dOff, uint64_t *dSums,
                                  uint32_t *dCsr, unsigned long long *dCtr, hipStream_t s);
+// the same over the lines [r0, r0 + n_lines) only, which name rows of [0, n_rows): dDeg / dCur / dOff as above, dCsr: n_lines * in_k words at most
+hipError_t zh_launch_reverse_csr_lines(const uint32_t *dTab, const uint32_t *dBits, uint64_t n_rows, uint32_t in_k, uint64_t r0, uint64_t n_lines, uint32_t *dDeg,
+                                       uint32_t *dCur, uint64_t *dOff, uint64_t *dSums, uint32_t *dCsr, unsigned long long *dCtr, hipStream_t s);
 // R'(x) of the lines x0 .. x0 + nx: the first rev_k of In(x) - N'(x) by (h(u, x), u).  dUni (or null): line x of the union table [n_rows][in_k +
 // rev_k] = N'(x)'s line, then R'(x), UINT32_MAX tails.  dOutIds (or null; then the next two as well): for x in [first_row, first_row + n) line x -
 // first_row of [n][rev_k] ids, counts and in-degrees.  dCtr[2] += |R'(x)| over that slab; dCtr[3] and dHeavy (n_rows * in_k / ZH_REVERSE_HEAVY + 1
@@ -553,6 +556,20 @@ hipError_t zh_launch_gsearch(const float *dX, uint32_t d, uint64_t n_rows, const
                              const uint32_t *dAllow, const float *dQ, const float *dQQ, const uint64_t *dSeeds, uint32_t n_seed, uint32_t B, uint64_t id_base, uint32_t top_k,
                              uint32_t beam, uint32_t width, uint32_t max_iters, int metric, int param, uint64_t *dOutIds, uint64_t *dOutKeys,
                              uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s);
+
+// ---- the graph extension and read-back (zh_gextend.hip): dRows = the B live rows of a chunk [lo, hi) of new lines, ascending
+// the seed lines of those rows out of the caller's [new rows][n_seed] (row g0 is its line 0), one behind the other
+hipError_t zh_launch_gext_seeds(const uint64_t *dSeeds, const uint32_t *dRows, uint32_t B, uint64_t g0, uint32_t n_seed, uint64_t *dOut, hipStream_t s);
+// the walk's answer [B][g_k] (ids with id_base, counts) -> lines dRows[b] of the table, UINT32_MAX past the count
+hipError_t zh_launch_gext_lines(const uint64_t *dIds, const uint32_t *dCounts, const uint32_t *dRows, uint32_t B, uint32_t g_k, uint64_t id_base, uint32_t *dTab,
+                                hipStream_t s);
+// every row r < lo that a line of [lo, lo + n_chunk) names (dOff / dCsr: zh_launch_reverse_csr_lines of those lines) re-ranked in place against
+// itself: the first g_k of its kept live entries and R(r) by (key, row).  dQQ: the squared norm of every stored row (cosine only).  dTouched:
+// min(n_chunk g_k, lo) words.  dCtr[0] (zeroed by the caller) = the rows re-ranked; dCtr[1..3] += the same, the sum of |R(r)|, chunk rows written
+hipError_t zh_launch_gext_rerank(const float *dX, uint32_t d, uint32_t *dTab, uint32_t g_k, uint64_t lo, uint32_t n_chunk, const uint32_t *dBits, const float *dQQ,
+                                 const uint64_t *dOff, const uint32_t *dCsr, uint32_t *dTouched, int metric, int param, unsigned long long *dCtr, hipStream_t s);
+// lines [x0, x0 + nl) of the table as ids: the kept entries in table order at the front (id_base + row), 2^64 - 1 behind them, and their counts
+hipError_t zh_launch_gext_read(const uint32_t *dTab, uint32_t g_k, uint64_t x0, uint64_t nl, uint64_t id_base, uint64_t *dOutIds, uint32_t *dOutCounts, hipStream_t s);
 
 // ---- the forest self-join (zh_fjoin.hip): every pair of leaf-mates whose key is <= one threshold key, each pair once (the first tree that puts
 // the two rows together owns it).  Hit pool, counter and order as the exact self-join's

@@ -131,26 +131,33 @@ __global__ __launch_bounds__(256) void rev_offsets_kernel(const uint32_t *__rest
     }
 }
 
-hipError_t zh_launch_reverse_csr(const uint32_t *dTab, const uint32_t *dBits, uint64_t n_rows, uint32_t in_k, uint32_t *dDeg, uint32_t *dCur, uint64_t *dOff, uint64_t *dSums,
-                                 uint32_t *dCsr, unsigned long long *dCtr, hipStream_t s) {
+// the lines [r0, r0 + n_lines) of the table transposed over the rows [0, n_rows) they name (zh_launch_reverse_csr: every line; the graph extension: a
+// chunk of new lines over the rows before it)
+hipError_t zh_launch_reverse_csr_lines(const uint32_t *dTab, const uint32_t *dBits, uint64_t n_rows, uint32_t in_k, uint64_t r0, uint64_t n_lines, uint32_t *dDeg,
+                                       uint32_t *dCur, uint64_t *dOff, uint64_t *dSums, uint32_t *dCsr, unsigned long long *dCtr, hipStream_t s) {
     if (!n_rows) return hipSuccess;
-    if (!in_k || in_k > ZH_REFINE_MAX_IN_K || n_rows >= RV_NONE) return hipErrorInvalidValue;
+    if (!in_k || in_k > ZH_REFINE_MAX_IN_K || n_rows >= RV_NONE || r0 + n_lines >= RV_NONE) return hipErrorInvalidValue;
     hipError_t e;
     if ((e = hipMemsetAsync(dDeg, 0, n_rows * 4, s)) != hipSuccess || (e = hipMemsetAsync(dCur, 0, n_rows * 4, s)) != hipSuccess) return e;
     const uint64_t step = (1ull << 30) / in_k;  // lines of one launch: at most 2^30 threads
-    for (uint64_t r0 = 0; r0 < n_rows; r0 += step) {
-        const uint32_t m = (uint32_t)(std::min(step, n_rows - r0) * in_k);
-        hipLaunchKernelGGL(rev_edges_kernel<false>, dim3((m + 255) / 256), dim3(256), 0, s, dTab, dBits, in_k, r0, m, dDeg, nullptr, nullptr);
+    for (uint64_t l0 = 0; l0 < n_lines; l0 += step) {
+        const uint32_t m = (uint32_t)(std::min(step, n_lines - l0) * in_k);
+        hipLaunchKernelGGL(rev_edges_kernel<false>, dim3((m + 255) / 256), dim3(256), 0, s, dTab, dBits, in_k, r0 + l0, m, dDeg, nullptr, nullptr);
     }
     const uint64_t nb = (n_rows + RV_SCAN_ROWS - 1) / RV_SCAN_ROWS;  // (< 2^20)
     hipLaunchKernelGGL(rev_sums_kernel, dim3((uint32_t)nb), dim3(256), 0, s, dDeg, n_rows, dSums, dCtr);
     hipLaunchKernelGGL(rev_scan_sums_kernel, dim3(1), dim3(256), 0, s, dSums, nb, dOff + n_rows, dCtr);
     hipLaunchKernelGGL(rev_offsets_kernel, dim3((uint32_t)nb), dim3(256), 0, s, dDeg, n_rows, dSums, dOff);
-    for (uint64_t r0 = 0; r0 < n_rows; r0 += step) {
-        const uint32_t m = (uint32_t)(std::min(step, n_rows - r0) * in_k);
-        hipLaunchKernelGGL(rev_edges_kernel<true>, dim3((m + 255) / 256), dim3(256), 0, s, dTab, dBits, in_k, r0, m, dCur, dOff, dCsr);
+    for (uint64_t l0 = 0; l0 < n_lines; l0 += step) {
+        const uint32_t m = (uint32_t)(std::min(step, n_lines - l0) * in_k);
+        hipLaunchKernelGGL(rev_edges_kernel<true>, dim3((m + 255) / 256), dim3(256), 0, s, dTab, dBits, in_k, r0 + l0, m, dCur, dOff, dCsr);
     }
     return hipGetLastError();
+}
+
+hipError_t zh_launch_reverse_csr(const uint32_t *dTab, const uint32_t *dBits, uint64_t n_rows, uint32_t in_k, uint32_t *dDeg, uint32_t *dCur, uint64_t *dOff, uint64_t *dSums,
+                                 uint32_t *dCsr, unsigned long long *dCtr, hipStream_t s) {
+    return zh_launch_reverse_csr_lines(dTab, dBits, n_rows, in_k, 0, n_rows, dDeg, dCur, dOff, dSums, dCsr, dCtr, s);
 }
 
 __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, uint32_t src) {

@@ -874,6 +874,65 @@ class LSHIndex:
         and every iteration's candidates, repeats included), returned (the sum of counts)"""
         return self._info(_ffi.SearchGraphFilteredInfo, lib().zh_search_graph_filtered_info)
 
+    def extend_graph(self, metric, beam=64, width=1, max_iters=0, seeds=None, n_seed=32, batch=1024):
+        """give the rows stored since set_graph lines of their own and let the old lines name them (zh_index_extend_graph): the new rows go in
+        chunks of `batch` stored rows; each live row of a chunk is a query of search_graph_batch's walk over the table as it stands before the
+        chunk (top_k = g_k, so g_k <= beam), its line the first g_k of the final beam; then every old row that one of those lines names is
+        re-ranked over its live entries and the chunk rows that name it, under the key of that old row as the query.  Rows of one chunk never
+        name each other (batch=1 is the sequential rule); get_graph, a knn_graph_descent round and set_graph close what is left.  seeds: None =
+        the strided rows id_base + j * G // n_seed of the graph before the call for every new row; "lsh" = search_batch of the new rows read
+        back (needs trees; a seed naming a row without a line yet is ignored by the rule); an array [new rows, n_seed] of ids, or [n_seed] for
+        every row.  1 <= batch <= 1024, the other limits as search_graph_batch.  -> extend_graph_info()"""
+        g_rows = self.graph_info()["g_rows"]
+        n_new = max(self.stored_rows() - g_rows, 0)
+        n_seed = int(n_seed)
+        if seeds is None:
+            row = np.array([j * g_rows // n_seed for j in range(n_seed)] if n_seed > 0 else [], np.uint64) + np.uint64(self.id_base)
+            sd = np.ascontiguousarray(np.broadcast_to(row, (n_new, row.size)))
+        elif isinstance(seeds, str):
+            if seeds != "lsh":
+                raise ValueError("seeds is None, 'lsh' or an array of ids")
+            sd = np.empty((n_new, n_seed), np.uint64)
+            for r0 in range(0, n_new, 65536):  # (tails are 2^64-1: ignored as out of range)
+                m = min(65536, n_new - r0)
+                sd[r0:r0 + m] = self.search_batch(self.read_rows(g_rows + r0, m), n_seed, metric)[0]
+        else:
+            a = np.asarray(seeds).astype(np.uint64, copy=False)
+            if a.ndim == 1:
+                a = np.broadcast_to(a, (n_new, a.shape[0]))
+            if a.ndim != 2 or a.shape[0] != n_new:
+                raise _ffi.ZhError(_ffi.ZH_EINVAL, "extend_graph: seeds is [n_seed] or [%d, n_seed]" % n_new)
+            sd = np.ascontiguousarray(a)
+        check(lib().zh_index_extend_graph(self._h, _p(sd) if n_new else None, n_new, sd.shape[1], int(beam), int(width), int(max_iters), int(batch),
+                                          metric.metric, metric.mode))
+        return self.extend_graph_info()
+
+    def extend_graph_device(self, d_seeds_ptr, n_new, n_seed, metric, beam=64, width=1, max_iters=0, batch=1024, stream=None):
+        """extend_graph with the seeds ([n_new, n_seed] u64, n_new = the rows stored since the attach) already in device memory (raw pointer)"""
+        check(lib().zh_index_extend_graph_device(self._h, d_seeds_ptr, int(n_new), int(n_seed), int(beam), int(width), int(max_iters), int(batch),
+                                                 metric.metric, metric.mode, stream))
+
+    def extend_graph_info(self):
+        """what the most recent extend_graph call on this index did (zh_index_extend_graph_info): rows_added (live new rows), rows_removed (new
+        rows with an empty line), chunks, the walks' seeds, iterations, expanded, keyed and capped, reverse_rows (old rows re-ranked, summed over
+        the chunks), reverse_offered (new rows offered to them), reverse_kept (new rows that ended inside a re-ranked line), launches"""
+        return self._info(_ffi.GraphExtendInfo, lib().zh_index_extend_graph_info)
+
+    def get_graph(self, first_row=0, n=None):
+        """the attached graph's lines [first_row, first_row + n) (default: to its last line) as set_graph takes them (zh_index_get_graph): the kept
+        entries of each line in table order as ids, 2^64-1 behind them -> (ids [n, g_k] u64, counts [n] u32).  A row removed since the attach
+        is still listed."""
+        g = self.graph_info()
+        n = max(g["g_rows"] - int(first_row), 0) if n is None else int(n)
+        ids = np.empty((n, g["g_k"]), np.uint64)
+        counts = np.zeros(n, np.uint32)
+        check(lib().zh_index_get_graph(self._h, int(first_row), n, _p(ids) if n else None, _p(counts) if n else None))
+        return ids, counts
+
+    def get_graph_device(self, first_row, n, d_ids_ptr, d_counts_ptr, stream=None):
+        """get_graph with the outputs ([n, g_k] u64, [n] u32) already in device memory (raw pointers)"""
+        check(lib().zh_index_get_graph_device(self._h, int(first_row), int(n), d_ids_ptr, d_counts_ptr, stream))
+
     def knn_graph_reverse(self, graph, rev_k, first_row=0, n=None):
         """the capped reverse graph of a graph of ALL stored rows (`graph` as for knn_graph_refine): line i holds up to rev_k of the live rows that
         name stored row first_row + i and that its own line does not name -- a deterministic pseudo-random sample by a hash of the pair, the same
@@ -1333,13 +1392,22 @@ class Database:
 
     def build_graph(self, k=32, rounds=8, reverse=0):
         """make the graph query_vectors_graph walks and attach it to the index: knn_graph_forest(k), LSHIndex.knn_graph_descent(rounds, reverse),
-        LSHIndex.set_graph.  Needs trees.  Records added later are found only as seeds until the graph is built again; removed ones are skipped
-        at once.  -> LSHIndex.graph_info()"""
+        LSHIndex.set_graph.  Needs trees.  Records added later are found only as seeds until extend_graph gives them lines (or the graph is built
+        again); removed ones are skipped at once.  -> LSHIndex.graph_info()"""
         if self.index.no_vectors():
             return self.index.graph_info()
         graph = self.index.knn_graph_forest(k, self.metric)
         self.index.set_graph(self.index.knn_graph_descent(graph, k, self.metric, rounds=rounds, reverse=reverse))
         return self.index.graph_info()
+
+    def extend_graph(self, beam=64, **kw):
+        """lines for the records added since build_graph (or the last extend_graph), and the old lines re-ranked to name them:
+        LSHIndex.extend_graph under the database's metric (width, max_iters, seeds, n_seed, batch as there; beam is raised to the graph's
+        width).  Far cheaper than build_graph while the added records are few; see the README for where the rebuild takes over.
+        -> LSHIndex.extend_graph_info()"""
+        if self.index.no_vectors() or not self.index.graph_info()["attached"]:
+            return self.index.extend_graph_info()
+        return self.index.extend_graph(self.metric, beam=max(int(beam), self.index.graph_info()["g_k"]), **kw)
 
     def query_vectors_graph(self, vectors, number_of_results, beam=64, **kw):
         """query_vectors answered by LSHIndex.search_graph_batch over the graph build_graph attached (beam, width, max_iters, seeds, n_seed as

@@ -581,6 +581,42 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_search_graph_filtered_info(h_.get(), &info));
         return info;
     }
+    // Filter-steered graph search (zh_search_graph_steered_batch): a walk that sees the filter.  The beam only ever holds rows `filter_words` allows
+    // (search_graph_filtered_batch's bitmap) -- seeds that are not allowed are ignored -- and an iteration's candidates are the allowed entries of the
+    // parents' lines and, with hops = 2, those of the lines of the disallowed live rows the parents name, in line order, at most 256 an iteration.
+    // With every row allowed it is search_graph_batch's answer.  hops is 1 or 2.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> search_graph_steered_batch(const std::vector<Embedding<N>> &queries, const std::vector<Id> &seeds,
+                                                                                       std::size_t n_seed, std::size_t top_k, const Met &metric,
+                                                                                       const std::vector<std::uint32_t> &filter_words, std::uint64_t n_bits,
+                                                                                       int hops = 2, std::size_t beam = 64, std::size_t width = 1,
+                                                                                       std::size_t max_iters = 0) const {
+        const std::size_t b = queries.size();
+        if (seeds.size() != b * n_seed) throw std::invalid_argument("search_graph_steered_batch: seeds holds n_seed ids per query");
+        if (filter_words.size() < (n_bits + 31) / 32) throw std::invalid_argument("search_graph_steered_batch: filter_words holds n_bits bits");
+        std::vector<Id> ids(b * top_k + 1);
+        std::vector<DistanceUnit> keys(b * top_k + 1);
+        std::vector<std::uint32_t> counts(b + 1);
+        check(zh_search_graph_steered_batch(h_.get(), b ? queries[0].data() : nullptr, b, seeds.data(), n_seed, top_k, beam, width, max_iters, Met::metric,
+                                            metric.mode(), n_bits ? filter_words.data() : nullptr, n_bits, hops, ids.data(), keys.data(), counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(b);
+        for (std::size_t i = 0; i < b; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * top_k + j], keys[i * top_k + j]);
+        return out;
+    }
+    template <class Met>
+    void search_graph_steered_batch_device(const float *d_queries, std::size_t b, const Id *d_seeds, std::size_t n_seed, std::size_t top_k, std::size_t beam,
+                                           std::size_t width, std::size_t max_iters, const Met &metric, const std::uint32_t *d_filter_words,
+                                           std::uint64_t n_bits, int hops, Id *d_out_ids, DistanceUnit *d_out_keys, std::uint32_t *d_out_counts,
+                                           void *stream = nullptr) const {
+        check(zh_search_graph_steered_batch_device(h_.get(), d_queries, b, d_seeds, n_seed, top_k, beam, width, max_iters, Met::metric, metric.mode(),
+                                                   d_filter_words, n_bits, hops, d_out_ids, d_out_keys, d_out_counts, stream));
+    }
+    zh_graph_steered_info search_graph_steered_info() const {
+        zh_graph_steered_info info{};
+        check(zh_search_graph_steered_info(h_.get(), &info));
+        return info;
+    }
     // Extending the attached graph (zh_index_extend_graph): lines for the rows stored since the attach -- each found by search_graph_batch's walk over
     // the table before its chunk of `batch` rows, seeds holding n_seed ids per new row -- and the old lines those name re-ranked to name them.  Rows of
     // one chunk never name each other (batch = 1 is the sequential rule).  g_k <= beam, 1 <= batch <= ZH_GRAPH_EXTEND_MAX_BATCH.

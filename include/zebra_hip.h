@@ -42,6 +42,7 @@
  *   zh_search_graph_batch[_device]       (new) beam search over that graph: a best-first walk from caller-given seeds, exact keys, an approximate
  *                                        visited set
  *   zh_search_graph_filtered_batch[_device] (new) the same walk, answered from the rows a caller's bitmap allows among those it keyed
+ *   zh_search_graph_steered_batch[_device] (new) a walk that sees the bitmap: the beam holds allowed rows only, disallowed rows are hopped over
  *   zh_index_extend_graph[_device]       (new) lines for the rows stored since the attach, found by that walk, and the old lines they should be in
  *                                        re-ranked to name them: the attached graph follows add / append without a rebuild
  *   zh_index_get_graph[_device]          (new) the attached table read back as ids and counts
@@ -931,6 +932,57 @@ typedef struct zh_graph_filtered_info {  /* the most recent zh_search_graph_filt
     uint64_t returned;      /* the sum of out_counts */
 } zh_graph_filtered_info;
 ZH_API int zh_search_graph_filtered_info(const zh_index *idx, zh_graph_filtered_info *out);
+
+/* Filter-steered graph search (new): a walk that sees the filter.  The arguments are zh_search_graph_filtered_batch's, in the same positions, plus
+ * `hops` (1 or 2) directly after n_bits; the filter convention is the same to the letter (bit r & 31 of filter_words[r >> 5]; rows at and past
+ * n_bits are not allowed; spare bits of the last word are ignored; n_bits > zh_index_stored_rows is ZH_EINVAL; a NULL filter with n_bits > 0 is
+ * ZH_EINVAL; one filter serves the batch).  A = the rows both allowed and live at the time of the search; a KEPT entry of a line is one the
+ * attached table does not mask.  Per query:
+ *   1. S(q) = the rows of A the seeds name: a seed that is out of range, removed, NOT ALLOWED or repeated is ignored; a seed >= g_rows is fine.
+ *      B = the first `beam` of S(q) by (key, id), every entry unexpanded.  B only ever holds rows of A.
+ *   2. Iteration t stops as zh_search_graph_batch's (t == max_iters with max_iters != 0, or no unexpanded entry).  Otherwise P = the first `width`
+ *      unexpanded entries of B, marked expanded, and the emission sequence E is built in this order.  First hop: for the parents in P's order, and
+ *      per parent its line's kept entries n in table order (a parent >= g_rows has an empty line): n in A is emitted (a DIRECT row); otherwise, if
+ *      hops == 2 and n is live, n joins the bridge list H, in this order, each row once; a removed n is skipped.  Second hop (hops == 2): for the
+ *      bridges of H in order, and per bridge its line's kept entries m in table order (a bridge >= g_rows has none): m in A is emitted.
+ *      cand = E with every repeat after a row's first emission dropped and every row in B now dropped, TRUNCATED TO ITS FIRST 256 ROWS
+ *      (ZH_GRAPH_MAX_CAND); width * g_k <= 256, so direct rows are never truncated.  cand is keyed and B = the first `beam` of B union cand by
+ *      (key, id), flags travelling with their rows.
+ *   3. The answer is the first top_k of B in zh_search_exact_batch's layout: out_counts[q] = min(top_k, |B|), tails UINT64_MAX, ids carry id_base,
+ *      every key is zh_distance_batch's.
+ * B is still the first `beam` of a superset of itself, so an expanded row that leaves never returns and the walk ends within `stored rows`
+ * iterations.  Truncation makes cand depend on B: zh_search_graph_batch's visited-set equivalence does NOT carry over; the definition above is the
+ * definition.  With every stored row allowed the ids, keys, counts and the seven walk figures are zh_search_graph_batch's, for either `hops`.
+ * n_bits = 0, or a filter that allows nothing, gives counts of 0 and no seed, with the kernel still launched.
+ * Limits and judgement order are zh_search_graph_filtered_batch's; hops other than 1 or 2 is ZH_EINVAL, judged last of the scalar limits (after
+ * max_iters) and before any device is touched.  No attached graph is ZH_ESTATE.  b = 0 is ZH_OK.  Locking, stream semantics, the filter pass and
+ * device scratch as zh_search_graph_filtered_batch (80 bytes of counters for its 56).  zh_search_graph_info, zh_search_graph_filtered_info,
+ * zh_stats_t and every sibling info struct are left alone.  DESIGN.md s28. */
+#define ZH_GRAPH_MAX_CAND 256u  /* the rows one iteration can key */
+ZH_API int zh_search_graph_steered_batch(zh_index *idx, const float *queries, size_t b, const uint64_t *seeds, size_t n_seed, size_t top_k,
+                                         size_t beam, size_t width, size_t max_iters, int metric, int cosine_mode, const uint32_t *filter_words,
+                                         uint64_t n_bits, int hops, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts);
+/* The same with queries, seeds, filter and every output in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_search_graph_steered_batch_device(zh_index *idx, const float *d_queries, size_t b, const uint64_t *d_seeds, size_t n_seed,
+                                                size_t top_k, size_t beam, size_t width, size_t max_iters, int metric, int cosine_mode,
+                                                const uint32_t *d_filter_words, uint64_t n_bits, int hops, uint64_t *d_out_ids, uint64_t *d_out_keys,
+                                                uint32_t *d_out_counts, void *stream);
+typedef struct zh_graph_steered_info {  /* the most recent zh_search_graph_steered_batch* call on this index; sums over the batch */
+    uint64_t queries;       /* the first seven: zh_graph_search_info's meanings under this walk */
+    uint64_t seeds;         /* the sum of |S(q)| */
+    uint64_t iterations;
+    uint64_t expanded;
+    uint64_t keyed;         /* seeds + direct + via_bridge */
+    uint64_t capped;
+    uint64_t launches;
+    uint64_t rows_allowed;  /* rows both allowed and live: the filter pass's count */
+    uint64_t direct;        /* first-hop members of every cand */
+    uint64_t via_bridge;    /* second-hop members of every cand */
+    uint64_t bridges;       /* the sum over iterations of |H|, read or not */
+    uint64_t cand_full;     /* iterations whose |cand| == ZH_GRAPH_MAX_CAND */
+    uint64_t returned;      /* the sum of out_counts */
+} zh_graph_steered_info;
+ZH_API int zh_search_graph_steered_info(const zh_index *idx, zh_graph_steered_info *out);
 
 /* Extending the attached graph (new): lines for the rows stored since the attach, and reverse edges to them.  G = the rows the attached table
  * covers (zh_graph_info.g_rows), N = the stored rows at the time of the call, g_k = the table's width.  The new rows G .. N-1 are taken in chunks

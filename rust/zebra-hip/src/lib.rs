@@ -274,6 +274,24 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_graph_steered_info {
+        pub queries: u64,
+        pub seeds: u64,
+        pub iterations: u64,
+        pub expanded: u64,
+        pub keyed: u64,
+        pub capped: u64,
+        pub launches: u64,
+        pub rows_allowed: u64,
+        pub direct: u64,
+        pub via_bridge: u64,
+        pub bridges: u64,
+        pub cand_full: u64,
+        pub returned: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_graph_extend_info {
         pub rows_added: u64,
         pub rows_removed: u64,
@@ -485,6 +503,15 @@ pub mod ffi {
                                                      d_filter_words: *const u32, n_bits: u64, d_out_ids: *mut u64, d_out_keys: *mut u64,
                                                      d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_search_graph_filtered_info(idx: *const zh_index, out: *mut zh_graph_filtered_info) -> c_int;
+        pub fn zh_search_graph_steered_batch(idx: *mut zh_index, queries: *const f32, b: usize, seeds: *const u64, n_seed: usize, top_k: usize,
+                                             beam: usize, width: usize, max_iters: usize, metric: c_int, cosine_mode: c_int,
+                                             filter_words: *const u32, n_bits: u64, hops: c_int, out_ids: *mut u64, out_keys: *mut u64,
+                                             out_counts: *mut u32) -> c_int;
+        pub fn zh_search_graph_steered_batch_device(idx: *mut zh_index, d_queries: *const f32, b: usize, d_seeds: *const u64, n_seed: usize,
+                                                    top_k: usize, beam: usize, width: usize, max_iters: usize, metric: c_int, cosine_mode: c_int,
+                                                    d_filter_words: *const u32, n_bits: u64, hops: c_int, d_out_ids: *mut u64,
+                                                    d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_search_graph_steered_info(idx: *const zh_index, out: *mut zh_graph_steered_info) -> c_int;
         pub fn zh_index_extend_graph(idx: *mut zh_index, seeds: *const u64, n_new: u64, n_seed: usize, beam: usize, width: usize, max_iters: usize,
                                      batch: usize, metric: c_int, cosine_mode: c_int) -> c_int;
         pub fn zh_index_extend_graph_device(idx: *mut zh_index, d_seeds: *const u64, n_new: u64, n_seed: usize, beam: usize, width: usize,
@@ -1214,6 +1241,51 @@ impl<const N: usize> LSHIndex<N> {
                                                 ids.as_mut_ptr(), keys.as_mut_ptr(), counts.as_mut_ptr())
         })?;
         Ok((0..b).map(|i| (0..counts[i] as usize).map(|j| (t.of_row[ids[i * top_k + j] as usize], keys[i * top_k + j])).collect()).collect())
+    }
+
+    /// (new) a walk that sees the filter (zh_search_graph_steered_batch): the beam holds only vectors `allowed` names; with hops = 2 a vector
+    /// that is not allowed is hopped over -- the allowed entries of its line are candidates, at most 256 an iteration.  The seeds are n_seed
+    /// rows strided over the allowed ones (a seed that is not allowed would be ignored).  hops is 1 or 2.  With every vector allowed it is
+    /// search_graph_batch's answer
+    #[allow(clippy::too_many_arguments)]
+    pub fn search_graph_steered_batch<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        queries: &[Embedding<N>],
+        top_k: usize,
+        beam: usize,
+        width: usize,
+        max_iters: usize,
+        n_seed: usize,
+        metric: &Met,
+        allowed: &[Uuid],
+        hops: i32,
+    ) -> anyhow::Result<Vec<Vec<(Uuid, DistanceUnit)>>> {
+        let b = queries.len();
+        let t = self.ids.read().unwrap();
+        let n_bits = unsafe { ffi::zh_index_stored_rows(self.hip.0) };
+        let mut words = vec![0u32; ((n_bits + 31) / 32) as usize];
+        let mut rows: Vec<u64> = allowed.iter().filter_map(|u| t.row_of.get(u).copied()).filter(|r| *r < n_bits).collect();
+        rows.sort_unstable();
+        rows.dedup();
+        for row in rows.iter() {
+            words[(row >> 5) as usize] |= 1u32 << (row & 31);
+        }
+        let line: Vec<u64> = (0..n_seed).map(|j| if rows.is_empty() { u64::MAX } else { rows[(j * rows.len() / n_seed.max(1)) % rows.len()] }).collect();
+        let seeds: Vec<u64> = (0..b * n_seed).map(|i| line[i % n_seed]).collect();
+        let (mut ids, mut keys, mut counts) = (vec![0u64; b * top_k + 1], vec![0u64; b * top_k + 1], vec![0u32; b + 1]);
+        check(unsafe {
+            ffi::zh_search_graph_steered_batch(self.hip.0, queries.as_ptr() as *const f32, b, seeds.as_ptr(), n_seed, top_k, beam, width, max_iters,
+                                               Met::METRIC, metric.param(), if n_bits > 0 { words.as_ptr() } else { std::ptr::null() }, n_bits,
+                                               hops, ids.as_mut_ptr(), keys.as_mut_ptr(), counts.as_mut_ptr())
+        })?;
+        Ok((0..b).map(|i| (0..counts[i] as usize).map(|j| (t.of_row[ids[i * top_k + j] as usize], keys[i * top_k + j])).collect()).collect())
+    }
+
+    /// what the most recent zh_search_graph_steered_batch call did (zh_search_graph_steered_info)
+    pub fn search_graph_steered_info(&self) -> anyhow::Result<ffi::zh_graph_steered_info> {
+        let mut info = ffi::zh_graph_steered_info::default();
+        check(unsafe { ffi::zh_search_graph_steered_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// what the most recent zh_search_graph_filtered_batch call did (zh_search_graph_filtered_info)

@@ -208,7 +208,16 @@ class SearchGraphFilteredInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SearchGraphSteeredInfo(C.Structure):
+    _fields_ = SearchGraphInfo._fields_ + [("rows_allowed", C.c_uint64), ("direct", C.c_uint64), ("via_bridge", C.c_uint64), ("bridges", C.c_uint64),
+                                           ("cand_full", C.c_uint64), ("returned", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 GRAPH_MAX_BEAM, GRAPH_MAX_SEEDS, GRAPH_MAX_ITERS, GRAPH_BATCH = 256, 64, 65535, 16384  # ZH_GRAPH_*
+GRAPH_MAX_CAND = 256  # ZH_GRAPH_MAX_CAND
 GRAPH_EXTEND_MAX_BATCH = 1024  # ZH_GRAPH_EXTEND_MAX_BATCH
 
 
@@ -338,6 +347,9 @@ SYMBOLS = [
     ("zh_search_graph_filtered_batch", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _u64, _vp, _vp, _vp]),
     ("zh_search_graph_filtered_batch_device", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _u64, _vp, _vp, _vp, _vp]),
     ("zh_search_graph_filtered_info", _i, [_vp, _vp]),
+    ("zh_search_graph_steered_batch", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _u64, _i, _vp, _vp, _vp]),
+    ("zh_search_graph_steered_batch_device", _i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp, _u64, _i, _vp, _vp, _vp, _vp]),
+    ("zh_search_graph_steered_info", _i, [_vp, _vp]),
     ("zh_index_extend_graph", _i, [_vp, _vp, _u64, _sz, _sz, _sz, _sz, _sz, _i, _i]),
     ("zh_index_extend_graph_device", _i, [_vp, _vp, _u64, _sz, _sz, _sz, _sz, _sz, _i, _i, _vp]),
     ("zh_index_extend_graph_info", _i, [_vp, _vp]),

@@ -448,6 +448,7 @@ struct zh_index {
     DevBuf gs_QQ, gs_ctr, gs_Q, gs_seeds, gs_oids, gs_okeys, gs_ocounts;
     zh_graph_search_info gs_info{};  // (stats_mu)
     zh_graph_filtered_info gf_info{};  // (stats_mu)
+    zh_graph_steered_info gt_info{};  // (stats_mu)
     // the graph extension's per-call scratch beside graph search's (all released before the call returns): a chunk's gathered seed lines and the
     // walk's answer for it, every stored row's squared norm, in-degrees, fill cursors, 64-bit offsets and the scan's block sums over the rows before
     // the chunk, the chunk's transposed edges, the touched rows, {the walk's five counters, touched rows of the chunk, rows re-ranked, offered, kept,
@@ -5935,9 +5936,11 @@ extern "C" int zh_index_graph_info(const zh_index *ix, zh_graph_info *out) {
 
 // judged before any device is touched, in this order of kinds: null index (even for b = 0), null pointers of a non-empty request, the metric, a zero
 // top_k / beam / width / n_seed, then the limits: beam, top_k against beam, n_seed, width (against 256: g_k is only known under the lock), max_iters
-// (the filtered entries: a null filter that speaks for rows is one of the null pointers, whatever b; the unfiltered ones pass null and 0)
+// (the filtered entries: a null filter that speaks for rows is one of the null pointers, whatever b; the unfiltered ones pass null and 0), and last,
+// for the steered entries, hops (ZH_EINVAL unless 1 or 2; the others pass 1)
 static int gsearch_args(zh_index *ix, const void *q, size_t b, const void *seeds, size_t n_seed, size_t top_k, size_t beam, size_t width, size_t max_iters,
-                        int metric, int mode, const void *filter, uint64_t n_bits, const void *ids, const void *keys, const void *counts, const char *who) {
+                        int metric, int mode, const void *filter, uint64_t n_bits, const void *ids, const void *keys, const void *counts, const char *who,
+                        int hops = 1) {
     if (!ix || (b && (!q || !seeds || !ids || !keys || !counts))) return fail(ZH_EINVAL, "%s: null argument", who);
     if (n_bits && !filter) return fail(ZH_EINVAL, "%s: null filter for %llu rows", who, (unsigned long long)n_bits);
     const int rc = check_metric(metric, mode);
@@ -5951,16 +5954,19 @@ static int gsearch_args(zh_index *ix, const void *q, size_t b, const void *seeds
     if (n_seed > ZH_GRAPH_MAX_SEEDS) return fail(ZH_ELIMIT, "%s: n_seed %zu > ZH_GRAPH_MAX_SEEDS (%u)", who, n_seed, ZH_GRAPH_MAX_SEEDS);
     if (width > 256) return fail(ZH_ELIMIT, "%s: width %zu > 256", who, width);
     if (max_iters > ZH_GRAPH_MAX_ITERS) return fail(ZH_ELIMIT, "%s: max_iters %zu > ZH_GRAPH_MAX_ITERS (%u)", who, max_iters, ZH_GRAPH_MAX_ITERS);
+    if (hops != 1 && hops != 2) return fail(ZH_EINVAL, "%s: hops %d is neither 1 nor 2", who, hops);
     return ZH_OK;
 }
 
-// all four entry points once the arguments have been judged (b > 0).  host: q, seeds, the filter and the outputs are HOST arrays -- each internal batch
+// all six entry points once the arguments have been judged (b > 0).  host: q, seeds, the filter and the outputs are HOST arrays -- each internal batch
 // goes through the staging and is waited for; otherwise they are device arrays, waited for once after the last batch.  flt (the filtered entries):
 // the caller's bitmap; the filter pass runs once, on the call's stream, into the filtered exact search's buffers, and its count comes back with the
-// counters.  Without flt nothing of that is touched.
+// counters.  Without flt nothing of that is touched.  flt->hops (the steered entries): the walk itself reads the pass's bitmap, 1 or 2 hops wide;
+// 0 is the blind walk answered from the allowed rows.
 struct GsearchFilter {
     const uint32_t *words;
     uint64_t n_bits;
+    uint32_t hops;
 };
 static int gsearch_call(zh_index *ix, const float *q, size_t b, const uint64_t *seeds, uint32_t n_seed, uint32_t top_k, uint32_t beam, uint32_t width,
                         uint32_t max_iters, int metric, int mode, const GsearchFilter *flt, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, bool host,
@@ -5976,7 +5982,8 @@ static int gsearch_call(zh_index *ix, const float *q, size_t b, const uint64_t *
     if ((rc = exact_live_rows(ix))) return rc;
     ScratchGuard guard{ix, flt ? SCRATCH_GSEARCH_FILTERED : SCRATCH_GSEARCH};
     const hipStream_t s = call_stream(ix, stream);
-    const size_t nb_max = std::min<size_t>(ZH_GRAPH_BATCH, b), ctr_bytes = flt ? 56 : 40;  // (zh_launch_gsearch's five counters, seven under a filter)
+    const bool steer = flt && flt->hops;
+    const size_t nb_max = std::min<size_t>(ZH_GRAPH_BATCH, b), ctr_bytes = steer ? 80 : flt ? 56 : 40;  // (five counters, seven under a filter, ten steered)
     if ((rc = ix->gs_QQ.ensure(nb_max * 4)) || (rc = ix->gs_ctr.ensure(ctr_bytes))) return rc;
     if (host && ((rc = ix->gs_Q.ensure(nb_max * d * 4)) || (rc = ix->gs_seeds.ensure(nb_max * n_seed * 8)) || (rc = ix->gs_oids.ensure(nb_max * top_k * 8)) ||
                  (rc = ix->gs_okeys.ensure(nb_max * top_k * 8)) || (rc = ix->gs_ocounts.ensure(nb_max * 4))))
@@ -6002,6 +6009,7 @@ static int gsearch_call(zh_index *ix, const float *q, size_t b, const uint64_t *
         dAllowed = excl + fblocks;
     }
     zh_graph_filtered_info inf{};
+    const int param = score_param(metric, mode);
     for (size_t b0 = 0; b0 < b; b0 += ZH_GRAPH_BATCH) {
         const uint32_t nb = (uint32_t)std::min<size_t>(ZH_GRAPH_BATCH, b - b0);
         const float *dQ = q + b0 * d;
@@ -6015,9 +6023,14 @@ static int gsearch_call(zh_index *ix, const float *q, size_t b, const uint64_t *
             dIds = ix->gs_oids.as<uint64_t>(); dKeys = ix->gs_okeys.as<uint64_t>(); dCounts = ix->gs_ocounts.as<uint32_t>();
         }
         if (metric == ZH_COSINE) HIPCHK(zh_launch_qnorm(dQ, nb, d, ix->gs_QQ.as<float>(), s));  // (the exact search's norm of the query)
-        HIPCHK(zh_launch_gsearch(ix->X.as<float>(), d, ix->n_rows, ix->graph.tab.as<uint32_t>(), ix->graph.rows, g_k, ix->live_dev.bits.as<uint32_t>(), dAllow, dQ,
-                                 ix->gs_QQ.as<float>(), dSeeds, n_seed, nb, ix->opt.id_base, top_k, beam, width, max_iters, metric, score_param(metric, mode), dIds,
-                                 dKeys, dCounts, ix->gs_ctr.as<unsigned long long>(), s));
+        if (steer)
+            HIPCHK(zh_launch_gsearch_steered(ix->X.as<float>(), d, ix->n_rows, ix->graph.tab.as<uint32_t>(), ix->graph.rows, g_k, ix->live_dev.bits.as<uint32_t>(),
+                                             dAllow, dQ, ix->gs_QQ.as<float>(), dSeeds, n_seed, nb, ix->opt.id_base, top_k, beam, width, max_iters, flt->hops, metric,
+                                             param, dIds, dKeys, dCounts, ix->gs_ctr.as<unsigned long long>(), s));
+        else
+            HIPCHK(zh_launch_gsearch(ix->X.as<float>(), d, ix->n_rows, ix->graph.tab.as<uint32_t>(), ix->graph.rows, g_k, ix->live_dev.bits.as<uint32_t>(), dAllow,
+                                     dQ, ix->gs_QQ.as<float>(), dSeeds, n_seed, nb, ix->opt.id_base, top_k, beam, width, max_iters, metric, param, dIds, dKeys,
+                                     dCounts, ix->gs_ctr.as<unsigned long long>(), s));
         inf.launches++;
         if (host) {
             HIPCHK(hipMemcpyAsync(out_ids + b0 * top_k, dIds, (size_t)nb * top_k * 8, hipMemcpyDeviceToHost, s));
@@ -6026,7 +6039,7 @@ static int gsearch_call(zh_index *ix, const float *q, size_t b, const uint64_t *
             HIPCHK(hipStreamSynchronize(s));
         }
     }
-    unsigned long long ctr[7] = {0, 0, 0, 0, 0, 0, 0};
+    unsigned long long ctr[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t allowed = 0;
     HIPCHK(hipMemcpyAsync(ctr, ix->gs_ctr.p, ctr_bytes, hipMemcpyDeviceToHost, s));
     if (flt) HIPCHK(hipMemcpyAsync(&allowed, dAllowed, 4, hipMemcpyDeviceToHost, s));
@@ -6035,7 +6048,13 @@ static int gsearch_call(zh_index *ix, const float *q, size_t b, const uint64_t *
     inf.seeds = ctr[0]; inf.iterations = ctr[1]; inf.expanded = ctr[2]; inf.keyed = ctr[3]; inf.capped = ctr[4];
     inf.rows_allowed = allowed; inf.offered = ctr[5]; inf.returned = ctr[6];
     std::lock_guard<std::mutex> ls(ix->stats_mu);
-    if (flt) {
+    if (steer) {
+        zh_graph_steered_info g{};
+        g.queries = inf.queries; g.seeds = inf.seeds; g.iterations = inf.iterations; g.expanded = inf.expanded; g.keyed = inf.keyed; g.capped = inf.capped;
+        g.launches = inf.launches; g.rows_allowed = allowed;
+        g.direct = ctr[5]; g.via_bridge = ctr[6]; g.bridges = ctr[7]; g.cand_full = ctr[8]; g.returned = ctr[9];
+        ix->gt_info = g;
+    } else if (flt) {
         ix->gf_info = inf;
     } else {
         zh_graph_search_info g{};
@@ -6075,7 +6094,7 @@ extern "C" int zh_search_graph_filtered_batch_device(zh_index *ix, const float *
     const char *who = "zh_search_graph_filtered_batch_device";
     int rc = gsearch_args(ix, d_q, b, d_seeds, n_seed, top_k, beam, width, max_iters, metric, mode, d_filter, n_bits, d_out_ids, d_out_keys, d_out_counts, who);
     if (rc || b == 0) return rc;
-    const GsearchFilter flt{d_filter, n_bits};
+    const GsearchFilter flt{d_filter, n_bits, 0};
     return gsearch_call(ix, d_q, b, d_seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, &flt, d_out_ids,
                         d_out_keys, d_out_counts, false, stream, who);
 }
@@ -6086,13 +6105,40 @@ extern "C" int zh_search_graph_filtered_batch(zh_index *ix, const float *q, size
     const char *who = "zh_search_graph_filtered_batch";
     int rc = gsearch_args(ix, q, b, seeds, n_seed, top_k, beam, width, max_iters, metric, mode, filter, n_bits, out_ids, out_keys, out_counts, who);
     if (rc || b == 0) return rc;
-    const GsearchFilter flt{filter, n_bits};
+    const GsearchFilter flt{filter, n_bits, 0};
     return gsearch_call(ix, q, b, seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, &flt, out_ids,
                         out_keys, out_counts, true, nullptr, who);
 }
 
 extern "C" int zh_search_graph_filtered_info(const zh_index *ix, zh_graph_filtered_info *out) {
     return get_info(ix, &zh_index::gf_info, out, "zh_search_graph_filtered_info");
+}
+
+// filter-steered graph search: the walk keeps to the allowed rows and hops over the others.  DESIGN.md s28
+extern "C" int zh_search_graph_steered_batch_device(zh_index *ix, const float *d_q, size_t b, const uint64_t *d_seeds, size_t n_seed, size_t top_k, size_t beam,
+                                                    size_t width, size_t max_iters, int metric, int mode, const uint32_t *d_filter, uint64_t n_bits, int hops,
+                                                    uint64_t *d_out_ids, uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
+    const char *who = "zh_search_graph_steered_batch_device";
+    int rc = gsearch_args(ix, d_q, b, d_seeds, n_seed, top_k, beam, width, max_iters, metric, mode, d_filter, n_bits, d_out_ids, d_out_keys, d_out_counts, who, hops);
+    if (rc || b == 0) return rc;
+    const GsearchFilter flt{d_filter, n_bits, (uint32_t)hops};
+    return gsearch_call(ix, d_q, b, d_seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, &flt, d_out_ids,
+                        d_out_keys, d_out_counts, false, stream, who);
+}
+
+extern "C" int zh_search_graph_steered_batch(zh_index *ix, const float *q, size_t b, const uint64_t *seeds, size_t n_seed, size_t top_k, size_t beam, size_t width,
+                                             size_t max_iters, int metric, int mode, const uint32_t *filter, uint64_t n_bits, int hops, uint64_t *out_ids,
+                                             uint64_t *out_keys, uint32_t *out_counts) {
+    const char *who = "zh_search_graph_steered_batch";
+    int rc = gsearch_args(ix, q, b, seeds, n_seed, top_k, beam, width, max_iters, metric, mode, filter, n_bits, out_ids, out_keys, out_counts, who, hops);
+    if (rc || b == 0) return rc;
+    const GsearchFilter flt{filter, n_bits, (uint32_t)hops};
+    return gsearch_call(ix, q, b, seeds, (uint32_t)n_seed, (uint32_t)top_k, (uint32_t)beam, (uint32_t)width, (uint32_t)max_iters, metric, mode, &flt, out_ids,
+                        out_keys, out_counts, true, nullptr, who);
+}
+
+extern "C" int zh_search_graph_steered_info(const zh_index *ix, zh_graph_steered_info *out) {
+    return get_info(ix, &zh_index::gt_info, out, "zh_search_graph_steered_info");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -556,6 +556,13 @@ hipError_t zh_launch_gsearch(const float *dX, uint32_t d, uint64_t n_rows, const
                              const uint32_t *dAllow, const float *dQ, const float *dQQ, const uint64_t *dSeeds, uint32_t n_seed, uint32_t B, uint64_t id_base, uint32_t top_k,
                              uint32_t beam, uint32_t width, uint32_t max_iters, int metric, int param, uint64_t *dOutIds, uint64_t *dOutKeys,
                              uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s);
+// the steered walk (zh_search_graph_steered_batch): the beam holds rows of dAllow (never null) only; hops == 2 reaches them through the lines of the
+// disallowed live rows a parent's line names.  The outputs are the first top_k of the final beam; dCtr[0..4] as above, dCtr[5..9] += direct rows,
+// rows reached over a bridge, bridges, iterations whose candidate list was full (256), entries returned
+hipError_t zh_launch_gsearch_steered(const float *dX, uint32_t d, uint64_t n_rows, const uint32_t *dTab, uint64_t g_rows, uint32_t g_k, const uint32_t *dBits,
+                                     const uint32_t *dAllow, const float *dQ, const float *dQQ, const uint64_t *dSeeds, uint32_t n_seed, uint32_t B, uint64_t id_base,
+                                     uint32_t top_k, uint32_t beam, uint32_t width, uint32_t max_iters, uint32_t hops, int metric, int param, uint64_t *dOutIds,
+                                     uint64_t *dOutKeys, uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s);
 
 // ---- the graph extension and read-back (zh_gextend.hip): dRows = the B live rows of a chunk [lo, hi) of new lines, ascending
 // the seed lines of those rows out of the caller's [new rows][n_seed] (row g0 is its line 0), one behind the other

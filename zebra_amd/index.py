@@ -874,6 +874,45 @@ class LSHIndex:
         and every iteration's candidates, repeats included), returned (the sum of counts)"""
         return self._info(_ffi.SearchGraphFilteredInfo, lib().zh_search_graph_filtered_info)
 
+    def search_graph_steered_batch(self, queries, top_k, metric, allowed, hops=2, beam=64, width=1, max_iters=0, seeds="allowed", n_seed=32):
+        """a walk over the attached graph that sees the filter (zh_search_graph_steered_batch): the beam only ever holds rows `allowed` names
+        (whatever filter_bitmap takes) that are live.  An iteration expands the first `width` unexpanded beam entries: an allowed live entry of
+        a parent's line is a candidate; with hops=2 a disallowed live entry is a bridge, and the allowed live entries of the bridges' lines are
+        candidates too, in line order behind the direct ones; at most 256 candidates an iteration, the rest of the bridges' entries dropped.
+        -> (ids [b,k] u64, keys [b,k] u64, counts [b] u32), the first top_k of the beam, entries past counts[i] 2^64-1.  With every row allowed
+        it is search_graph_batch's answer.  seeds: "allowed" (the default) = n_seed rows strided over the mask's set positions, the same for
+        every query; None, "lsh" and arrays as in search_graph_filtered_batch -- but seeds that are NOT ALLOWED are ignored here, like removed,
+        repeated and out-of-range ones.  hops is 1 or 2; the other limits as search_graph_batch.  search_graph_steered_info() describes the
+        call."""
+        q = _f32(queries, self.dim)
+        b = q.shape[0]
+        words, n_bits = self.filter_bitmap(allowed)
+        if isinstance(seeds, str) and seeds == "allowed":
+            sd = self._allowed_seeds(words, n_bits, b, n_seed)
+        else:
+            sd = self._graph_seeds(seeds, q, metric, n_seed)
+        top_k = int(top_k)
+        ids = np.empty((b, max(top_k, 0)), np.uint64)
+        keys = np.empty((b, max(top_k, 0)), np.uint64)
+        counts = np.zeros(b, np.uint32)
+        check(lib().zh_search_graph_steered_batch(self._h, _p(q), b, _p(sd), sd.shape[1], top_k, int(beam), int(width), int(max_iters), metric.metric,
+                                                  metric.mode, _p(words) if n_bits else None, n_bits, int(hops), _p(ids), _p(keys), _p(counts)))
+        return ids, keys, counts
+
+    def search_graph_steered_batch_device(self, d_q_ptr, b, d_seeds_ptr, n_seed, top_k, metric, d_filter_ptr, n_bits, d_ids_ptr, d_keys_ptr, d_counts_ptr,
+                                          hops=2, beam=64, width=1, max_iters=0, stream=None):
+        """search_graph_steered_batch with queries, seeds, the filter's u32 words (filter_bitmap's layout) and results already in device memory"""
+        check(lib().zh_search_graph_steered_batch_device(self._h, d_q_ptr, int(b), d_seeds_ptr, int(n_seed), int(top_k), int(beam), int(width),
+                                                         int(max_iters), metric.metric, metric.mode, d_filter_ptr, int(n_bits), int(hops), d_ids_ptr,
+                                                         d_keys_ptr, d_counts_ptr, stream))
+
+    def search_graph_steered_info(self):
+        """what the most recent search_graph_steered_batch call on this index did (zh_search_graph_steered_info): search_graph_info's seven
+        fields under this walk, rows_allowed (allowed and live), direct and via_bridge (candidates a parent's line named / a bridge's line
+        named: keyed = seeds + direct + via_bridge), bridges (disallowed live rows hopped over, summed over the iterations), cand_full
+        (iterations that filled all 256 candidate slots), returned (the sum of counts)"""
+        return self._info(_ffi.SearchGraphSteeredInfo, lib().zh_search_graph_steered_info)
+
     def extend_graph(self, metric, beam=64, width=1, max_iters=0, seeds=None, n_seed=32, batch=1024):
         """give the rows stored since set_graph lines of their own and let the old lines name them (zh_index_extend_graph): the new rows go in
         chunks of `batch` stored rows; each live row of a chunk is a query of search_graph_batch's walk over the table as it stands before the
@@ -1417,14 +1456,20 @@ class Database:
         ids, _, counts = self.index.search_graph_batch(vectors, number_of_results, self.metric, beam=max(int(beam), int(number_of_results)), **kw)
         return {b: {int(i): self._documents.get(int(i)) for i in ids[b, :counts[b]]} for b in range(ids.shape[0])}
 
-    def query_vectors_graph_where(self, vectors, number_of_results, predicate, beam=64, **kw):
-        """query_vectors_graph among the records whose document satisfies predicate(document) (LSHIndex.search_graph_filtered_batch: the walk
-        goes through every record, the answer holds only those; seeds="allowed" starts it from them) -> what query_vectors_graph returns"""
+    def query_vectors_graph_where(self, vectors, number_of_results, predicate, beam=64, hops=0, **kw):
+        """query_vectors_graph among the records whose document satisfies predicate(document).  hops=0: LSHIndex.search_graph_filtered_batch
+        (the walk goes through every record, the answer holds only those; seeds="allowed" starts it from them); hops=1 or 2:
+        LSHIndex.search_graph_steered_batch (the walk keeps to those records and, with 2, hops over the others: the call for a selective
+        predicate) -> what query_vectors_graph returns"""
         if self.index.no_vectors():
             return {}
         allowed = np.fromiter((i for i, doc in self._documents.items() if predicate(doc)), np.uint64)
-        ids, _, counts = self.index.search_graph_filtered_batch(vectors, number_of_results, self.metric, allowed,
-                                                                beam=max(int(beam), int(number_of_results)), **kw)
+        if hops:
+            ids, _, counts = self.index.search_graph_steered_batch(vectors, number_of_results, self.metric, allowed, hops=hops,
+                                                                   beam=max(int(beam), int(number_of_results)), **kw)
+        else:
+            ids, _, counts = self.index.search_graph_filtered_batch(vectors, number_of_results, self.metric, allowed,
+                                                                    beam=max(int(beam), int(number_of_results)), **kw)
         return {b: {int(i): self._documents.get(int(i)) for i in ids[b, :counts[b]]} for b in range(ids.shape[0])}
 
     def _graph_documents(self, ids, keys, counts):

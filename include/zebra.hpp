@@ -455,6 +455,44 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_knn_graph_refine_rev_info(h_.get(), &info));
         return info;
     }
+    // The occlusion rule of the graph indexes over a graph of ALL stored rows (zh_knn_graph_prune; the graph as knn_graph_refine_rev takes it): element
+    // i = the candidates of stored row first_row + i -- its line and up to rev_k sampled reverse neighbours, the row itself excluded -- in (key, id)
+    // order, each kept unless one kept before it is closer to it than the row is (its key against that kept row strictly below its key against the
+    // row), at most `degree` of them; fill: a line that came short takes the first dropped candidates.  degree and in_k + rev_k <= ZH_REFINE_MAX_IN_K.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> knn_graph_prune(const std::vector<Id> &in_ids, const std::vector<std::uint32_t> &in_counts,
+                                                                          std::size_t in_k, std::size_t rev_k, std::size_t degree, bool fill, const Met &metric,
+                                                                          std::uint64_t first_row, std::uint64_t n) const {
+        const std::uint64_t stored = zh_index_stored_rows(h_.get());
+        if (in_counts.size() != stored || in_ids.size() != stored * in_k) throw std::invalid_argument("knn_graph_prune: the graph must cover every stored row");
+        std::vector<Id> ids(n * degree + 1);
+        std::vector<DistanceUnit> keys(n * degree + 1);
+        std::vector<std::uint32_t> counts(n + 1);
+        check(zh_knn_graph_prune(h_.get(), in_ids.data(), in_counts.data(), in_k, rev_k, first_row, n, degree, fill ? 1 : 0, Met::metric, metric.mode(),
+                                 ids.data(), keys.data(), counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(n);
+        for (std::uint64_t i = 0; i < n; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * degree + j], keys[i * degree + j]);
+        return out;
+    }
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> knn_graph_prune(const std::vector<Id> &in_ids, const std::vector<std::uint32_t> &in_counts,
+                                                                          std::size_t in_k, std::size_t rev_k, std::size_t degree, bool fill,
+                                                                          const Met &metric) const {
+        return knn_graph_prune(in_ids, in_counts, in_k, rev_k, degree, fill, metric, 0, zh_index_stored_rows(h_.get()));
+    }
+    template <class Met>
+    void knn_graph_prune_device(const Id *d_in_ids, const std::uint32_t *d_in_counts, std::size_t in_k, std::size_t rev_k, std::uint64_t first_row,
+                                std::uint64_t n, std::size_t degree, bool fill, const Met &metric, Id *d_out_ids, DistanceUnit *d_out_keys,
+                                std::uint32_t *d_out_counts, void *stream = nullptr) const {
+        check(zh_knn_graph_prune_device(h_.get(), d_in_ids, d_in_counts, in_k, rev_k, first_row, n, degree, fill ? 1 : 0, Met::metric, metric.mode(),
+                                        d_out_ids, d_out_keys, d_out_counts, stream));
+    }
+    zh_knn_prune_info knn_prune_info() const {
+        zh_knn_prune_info info{};
+        check(zh_knn_graph_prune_info(h_.get(), &info));
+        return info;
+    }
     // NN-descent on the device (zh_knn_graph_descent): up to `rounds` rounds of knn_graph_refine_rev over the whole table in one call that keeps the
     // graph on the device and, from the second round on, keys only what a new entry of a line brings up -- the loop's answer bit for bit, early
     // stop at the first round without updates included.  1 <= rounds <= 32, k >= 1, in_k + rev_k and k + rev_k <= ZH_REFINE_MAX_IN_K.

@@ -38,6 +38,8 @@
  *   zh_knn_graph_refine_rev[_device]     (new) zh_knn_graph_refine over each row's neighbours AND sampled reverse neighbours
  *   zh_knn_graph_descent[_device]        (new) the rounds of zh_knn_graph_refine_rev in one call on the device, keying from the second round on
  *                                        only what a new entry brings up: the loop's answer bit for bit
+ *   zh_knn_graph_prune[_device]          (new) the occlusion rule of the graph indexes over a caller's graph: a line keeps a neighbour only if no
+ *                                        neighbour kept before it is closer to it than the row itself
  *   zh_index_set_graph[_device] / zh_index_drop_graph / zh_index_graph_info  (new) a k-NN graph over the stored rows, kept on the device between calls
  *   zh_search_graph_batch[_device]       (new) beam search over that graph: a best-first walk from caller-given seeds, exact keys, an approximate
  *                                        visited set
@@ -766,6 +768,61 @@ typedef struct zh_knn_refine_rev_info {  /* the most recent zh_knn_graph_refine_
     uint64_t max_degree;  /* the largest deg(x) over ALL stored rows */
 } zh_knn_refine_rev_info;
 ZH_API int zh_knn_graph_refine_rev_info(const zh_index *idx, zh_knn_refine_rev_info *out);
+
+/* ---- k-NN graph pruning (new): keep only a line's unoccluded neighbours ---------------------------------------------------------------------
+ * A k-NN line names the k nearest rows, and most of them lie in the same direction as an earlier one.  HNSW, NSG and Vamana drop a neighbour
+ * that is closer to an already kept neighbour than to the row itself; this call is that rule, written in keys.  The INPUT is a graph over ALL
+ * stored rows exactly as zh_knn_graph_refine_rev takes it; N'(x) and R'(x) are that call's and zh_knn_graph_reverse's sets, word for word
+ * (out-of-range, removed and repeated entries are ignored; R'(x) is zh_knn_graph_reverse's line at rev_k, empty for rev_k = 0).
+ *   P(a)     = ( N'(a) union R'(a) ) minus a.  Only the row with a's own row number is excluded; bit-identical duplicates are ordinary candidates.
+ *   key_q(x) = zh_distance_batch's key of stored row x against a query equal to the f32 values of stored row q: zh_knn_graph's orientation.
+ *   Order P(a) by (key_a(c), id): c_1 .. c_m.  Walk that order with S = O = (), and stop as soon as |S| == degree.  Candidate c is OCCLUDED and
+ *   goes to O if some p already in S has key_p(c) < key_a(c) -- on the u64 keys, unsigned and strict, so a tie does not occlude; otherwise c
+ *   goes to S.  If fill != 0 and |S| < degree, the first degree - |S| members of O, in their order, join S (HNSW's "keep pruned connections").
+ * Line i of the slab, for row a = first_row + i, is S ordered by (key_a, id): out_ids [n][degree] as id_base + row, out_keys the keys key_a,
+ * out_counts[i] = |S|, tails UINT64_MAX in both arrays, a removed a has count 0: zh_knn_graph's layout and slab meaning at k = degree.  Ids,
+ * keys and counts are bit for bit what this definition gives, for all 13 metric / mode / power combinations and every dimension, whatever the
+ * order or repetition of the input entries, the slabs or the run.  Under the parity cosine key (ZH_COSINE_PARITY), whose value is the
+ * SIMILARITY, the rule is still the unsigned order of the keys, as for zh_search_range_batch: "closer" there means the smaller key, and the
+ * line that comes out is what that key's own ranking calls unoccluded.  No forest is needed.
+ * What follows from the definition:
+ *   - c_1 is always kept;
+ *   - with fill and degree >= |P(a)| the line is P(a) re-keyed;
+ *   - with fill = 0 and rev_k = 0 pruning is idempotent: pruning the output at the same degree returns it;
+ *   - for a row a inside a block of identical rows its duplicates never occlude each other (key_p(c) == key_a(c): a tie);
+ *   - for a row outside such a block the first duplicate occludes the rest (key_p(c) is the key of a row against itself).
+ * Limits: degree, in_k and in_k + rev_k at most ZH_REFINE_MAX_IN_K, else ZH_ELIMIT.  Judged before any device is touched, in this order: a null
+ * index (even for n = 0), null input or output pointers of a request with n > 0, an unknown metric, degree's limit, in_k's, in_k + rev_k's,
+ * in_k = 0 with n > 0 (ZH_EINVAL), a fill other than 0 or 1 (ZH_EINVAL).  Then: first_row + n > stored rows is ZH_EINVAL, n = 0 is ZH_OK,
+ * degree = 0 zeroes the counts and touches nothing else.  Locking and stream semantics as zh_knn_graph_refine_device; zh_stats_t, every sibling
+ * info struct, the cached live-row views and the attached graph are left alone: zh_knn_graph_prune_info describes the most recent call.
+ * A block per live line orders its at most 64 candidates by key_a in LDS, then runs the walk as greedy rounds: the next surviving candidate is
+ * kept, becomes the query, and the survivors behind it are keyed against it -- at most degree rounds, nothing per pair leaves the block.
+ * Device scratch is per call and released before return: zh_knn_graph_refine_rev's tables, 4 bytes per stored row for the cosine kinds (the
+ * rows' norms: computed over ALL stored rows in EVERY call, as the table of row numbers is, whatever the slab -- a caller that prunes slab by
+ * slab pays both passes per slab, so few large slabs are cheaper than many small ones), and for the host call 16 degree + 4 bytes per line of a staged slab of at most max(65536, 2^25 / degree) lines.  DESIGN.md s29. */
+ZH_API int zh_knn_graph_prune(zh_index *idx, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, size_t rev_k, uint64_t first_row, uint64_t n,
+                              size_t degree, int fill, int metric, int cosine_mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts);
+/* The same with the graph and every output in device memory; enqueued on `stream` (NULL = the index's own stream), complete on return. */
+ZH_API int zh_knn_graph_prune_device(zh_index *idx, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, size_t rev_k, uint64_t first_row,
+                                     uint64_t n, size_t degree, int fill, int metric, int cosine_mode, uint64_t *d_out_ids, uint64_t *d_out_keys,
+                                     uint32_t *d_out_counts, void *stream);
+typedef struct zh_knn_prune_info {  /* the most recent zh_knn_graph_prune* call on this index */
+    uint64_t rows_live;   /* live rows of the index */
+    uint64_t lines;       /* live rows of the slab */
+    uint64_t in_k;
+    uint64_t rev_k;
+    uint64_t degree;
+    uint64_t fill;
+    uint64_t candidates;  /* the sum of |P(a)| */
+    uint64_t kept;        /* the sum of |S| before filling */
+    uint64_t occluded;    /* the sum of |O|: candidates the walk examined and dropped */
+    uint64_t filled;      /* entries of O that joined a short line */
+    uint64_t cut;         /* lines that stopped at `degree` with candidates still unexamined */
+    uint64_t keyed;       /* keys computed: candidates <= keyed <= candidates + the sum of |P(a)| (|P(a)| - 1); depends on the schedule */
+    uint64_t launches;    /* launches of the line kernel: one per sub-slab of 65536 stored rows that holds a live row */
+} zh_knn_prune_info;
+ZH_API int zh_knn_graph_prune_info(const zh_index *idx, zh_knn_prune_info *out);
 
 /* ---- NN-descent (new): incremental rounds on the device, to a fixed point --------------------------------------------------------------------
  * A loop over zh_knn_graph_refine_rev keys every pair again in every round and moves the graph through the host between rounds.  This call runs

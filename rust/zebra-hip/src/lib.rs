@@ -218,6 +218,24 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_knn_prune_info {
+        pub rows_live: u64,
+        pub lines: u64,
+        pub in_k: u64,
+        pub rev_k: u64,
+        pub degree: u64,
+        pub fill: u64,
+        pub candidates: u64,
+        pub kept: u64,
+        pub occluded: u64,
+        pub filled: u64,
+        pub cut: u64,
+        pub keyed: u64,
+        pub launches: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_knn_descent_info {
         pub rows_live: u64,
         pub in_k: u32,
@@ -476,6 +494,13 @@ pub mod ffi {
                                               first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64,
                                               d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_knn_graph_refine_rev_info(idx: *const zh_index, out: *mut zh_knn_refine_rev_info) -> c_int;
+        pub fn zh_knn_graph_prune(idx: *mut zh_index, in_ids: *const u64, in_counts: *const u32, in_k: usize, rev_k: usize, first_row: u64, n: u64,
+                                  degree: usize, fill: c_int, metric: c_int, cosine_mode: c_int, out_ids: *mut u64, out_keys: *mut u64,
+                                  out_counts: *mut u32) -> c_int;
+        pub fn zh_knn_graph_prune_device(idx: *mut zh_index, d_in_ids: *const u64, d_in_counts: *const u32, in_k: usize, rev_k: usize,
+                                         first_row: u64, n: u64, degree: usize, fill: c_int, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64,
+                                         d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_knn_graph_prune_info(idx: *const zh_index, out: *mut zh_knn_prune_info) -> c_int;
         pub fn zh_knn_graph_descent(idx: *mut zh_index, in_ids: *const u64, in_counts: *const u32, in_k: usize, rev_k: usize, k: usize, rounds: usize,
                                     metric: c_int, cosine_mode: c_int, out_ids: *mut u64, out_keys: *mut u64, out_counts: *mut u32) -> c_int;
         pub fn zh_knn_graph_descent_device(idx: *mut zh_index, d_in_ids: *const u64, d_in_counts: *const u32, in_k: usize, rev_k: usize, k: usize,
@@ -1107,6 +1132,49 @@ impl<const N: usize> LSHIndex<N> {
         Ok((0..stored)
             .map(|i| (t.of_row[i], (0..rcounts[i] as usize).map(|j| (t.of_row[rids[i * k + j] as usize], keys[i * k + j])).collect()))
             .collect())
+    }
+
+    /// (new) knn_graph_descent's graph pruned by the occlusion rule of the graph indexes (zh_knn_graph_prune): of each vector's k neighbours and
+    /// up to `reverse` sampled reverse neighbours, in (key, id) order, one is kept unless a neighbour kept before it is closer to it than the
+    /// vector itself; at most `degree` are kept, and with `fill` a line that came short takes the first dropped ones.  degree, k + reverse <= 64
+    pub fn knn_graph_pruned<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        k: usize,
+        rounds: usize,
+        reverse: usize,
+        degree: usize,
+        fill: bool,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<(Uuid, Vec<(Uuid, DistanceUnit)>)>> {
+        let t = self.ids.read().unwrap();
+        let stored = t.of_row.len();
+        let (mut ids, mut keys, mut counts) = (vec![0u64; stored * k + 1], vec![0u64; stored * k + 1], vec![0u32; stored + 1]);
+        let (mut rids, mut rcounts) = (vec![0u64; stored * k + 1], vec![0u32; stored + 1]);
+        let (mut pids, mut pkeys, mut pcounts) = (vec![0u64; stored * degree + 1], vec![0u64; stored * degree + 1], vec![0u32; stored + 1]);
+        if stored > 0 {
+            check(unsafe {
+                ffi::zh_knn_graph_forest(self.hip.0, 0, stored as u64, k, Met::METRIC, metric.param(), ids.as_mut_ptr(), keys.as_mut_ptr(),
+                                         counts.as_mut_ptr())
+            })?;
+            check(unsafe {
+                ffi::zh_knn_graph_descent(self.hip.0, ids.as_ptr(), counts.as_ptr(), k, reverse, k, rounds, Met::METRIC, metric.param(),
+                                          rids.as_mut_ptr(), keys.as_mut_ptr(), rcounts.as_mut_ptr())
+            })?;
+            check(unsafe {
+                ffi::zh_knn_graph_prune(self.hip.0, rids.as_ptr(), rcounts.as_ptr(), k, reverse, 0, stored as u64, degree, fill as c_int, Met::METRIC,
+                                        metric.param(), pids.as_mut_ptr(), pkeys.as_mut_ptr(), pcounts.as_mut_ptr())
+            })?;
+        }
+        Ok((0..stored)
+            .map(|i| (t.of_row[i], (0..pcounts[i] as usize).map(|j| (t.of_row[pids[i * degree + j] as usize], pkeys[i * degree + j])).collect()))
+            .collect())
+    }
+
+    /// what the most recent pruning call did (zh_knn_graph_prune_info)
+    pub fn knn_prune_info(&self) -> anyhow::Result<ffi::zh_knn_prune_info> {
+        let mut info = ffi::zh_knn_prune_info::default();
+        check(unsafe { ffi::zh_knn_graph_prune_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// (new) make the graph `search_graph_batch` walks and keep it on the device: the forest graph, NN-descent (knn_graph_descent's calls), then

@@ -186,6 +186,14 @@ class KnnDescentInfo(C.Structure):
         return out
 
 
+class KnnPruneInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("rows_live", "lines", "in_k", "rev_k", "degree", "fill", "candidates", "kept", "occluded", "filled", "cut",
+                                          "keyed", "launches")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class GraphInfo(C.Structure):
     _fields_ = [("attached", C.c_uint32), ("g_k", C.c_uint32), ("g_rows", C.c_uint64), ("bytes", C.c_uint64)]
 
@@ -334,6 +342,9 @@ SYMBOLS = [
     ("zh_knn_graph_refine_rev", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_knn_graph_refine_rev_device", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_knn_graph_refine_rev_info", _i, [_vp, _vp]),
+    ("zh_knn_graph_prune", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _sz, _i, _i, _i, _vp, _vp, _vp]),
+    ("zh_knn_graph_prune_device", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _sz, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    ("zh_knn_graph_prune_info", _i, [_vp, _vp]),
     ("zh_knn_graph_descent", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_knn_graph_descent_device", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_knn_graph_descent_info", _i, [_vp, _vp]),

@@ -357,6 +357,10 @@ struct zh_index {
     // their keys, the two union tables, the new-mask of every line, the list of active lines, every stored row's squared norm, a round's counters
     DevBuf nd_tab[2], nd_key[2], nd_uni[2], nd_mask, nd_list, nd_qq, nd_ctr;
     zh_knn_descent_info nd_info{};          // (stats_mu)
+    // the graph pruning's per-call scratch beside the reverse graph's (all released before the call returns): every stored row's squared norm,
+    // {candidates, kept, occluded, filled, cut, keyed}
+    DevBuf pr_qq, pr_ctr;
+    zh_knn_prune_info pr_info{};            // (stats_mu)
     // the forest self-join's per-call scratch beside the self-join's and the forest graph's (all released before the call returns): leaf_of, a path-1
     // panel's pieces and per-line {leaf, key offset}, path 2's segments and candidate pool
     DevBuf fj_leafof, fj_pieces, fj_linel, fj_linek, fj_segs, fj_cand;
@@ -3596,7 +3600,7 @@ static int score_param(int metric, int mode) { return (metric == ZH_COSINE || me
 // index holds only the live-row views (live_dev's list and bitmap survive every call; zh_index_destroy frees them).  Every family scans with the exact
 // search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's, the forest range search with
 // the range search's and the forest join's, the cross-join (all on its LEFT index) with the join's and its own views.
-enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024, SCR_ND = 2048, SCR_GS = 4096, SCR_GE = 8192 };  // one bit per list
+enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024, SCR_ND = 2048, SCR_GS = 4096, SCR_GE = 8192, SCR_PR = 16384 };  // one bit per list
 enum : unsigned {
     SCRATCH_EXACT = SCR_EX,
     SCRATCH_FILTER = SCR_FL | SCRATCH_EXACT,
@@ -3607,6 +3611,7 @@ enum : unsigned {
     SCRATCH_REFINE = SCR_RF | SCRATCH_KNN,
     SCRATCH_REVERSE = SCR_RV | SCRATCH_REFINE,
     SCRATCH_DESCENT = SCR_ND | SCRATCH_REVERSE,
+    SCRATCH_PRUNE = SCR_PR | SCRATCH_REVERSE,
     SCRATCH_GRAPH_ATTACH = SCR_RF,  // (the host entry's counts and staged chunk of ids)
     SCRATCH_GSEARCH = SCR_GS,
     SCRATCH_GSEARCH_FILTERED = SCR_GS | SCR_FL,  // (the filter pass writes the filtered exact search's buffers)
@@ -3639,6 +3644,7 @@ static void release_scratch(zh_index *ix, unsigned families) {
                   &ix->rv_odeg});
     drop(SCR_ND, {&ix->nd_tab[0], &ix->nd_tab[1], &ix->nd_key[0], &ix->nd_key[1], &ix->nd_uni[0], &ix->nd_uni[1], &ix->nd_mask, &ix->nd_list, &ix->nd_qq,
                   &ix->nd_ctr});
+    drop(SCR_PR, {&ix->pr_qq, &ix->pr_ctr});
     drop(SCR_GS, {&ix->gs_QQ, &ix->gs_ctr, &ix->gs_Q, &ix->gs_seeds, &ix->gs_oids, &ix->gs_okeys, &ix->gs_ocounts});
     drop(SCR_GE, {&ix->ge_seeds, &ix->ge_ids, &ix->ge_keys, &ix->ge_counts, &ix->ge_qq, &ix->ge_deg, &ix->ge_cur, &ix->ge_off, &ix->ge_sums, &ix->ge_csr,
                   &ix->ge_touched, &ix->ge_ctr});
@@ -5718,6 +5724,107 @@ extern "C" int zh_knn_graph_reverse(zh_index *ix, const uint64_t *in_ids, const 
 
 extern "C" int zh_knn_graph_reverse_info(const zh_index *ix, zh_knn_reverse_info *out) {
     return get_info(ix, &zh_index::rv_info, out, "zh_knn_graph_reverse_info");
+}
+
+// ------------------------------------------------------------------------------------------------
+// k-NN graph pruning (zh_prune.hip): each live row's unoccluded neighbours out of its line, with rev_k out of N'(a) union R'(a).  DESIGN.md s29
+// ------------------------------------------------------------------------------------------------
+// refine_rev_args' kinds in its order, `degree` where k stands and `fill` behind in_k = 0.  Judged before any device is touched
+static int prune_args(zh_index *ix, const void *in_ids, const void *in_counts, size_t in_k, size_t rev_k, uint64_t n, size_t degree, int fill, int metric, int mode,
+                      const void *ids, const void *keys, const void *counts, const char *who) {
+    if (!ix || (n && (!in_ids || !in_counts || !counts || (degree && (!ids || !keys))))) return fail(ZH_EINVAL, "%s: null argument", who);
+    const int rc = check_metric(metric, mode);
+    if (rc) return rc;
+    if (degree > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: degree %zu > ZH_REFINE_MAX_IN_K (%u)", who, degree, ZH_REFINE_MAX_IN_K);
+    if (in_k > ZH_REFINE_MAX_IN_K) return fail(ZH_ELIMIT, "%s: in_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, ZH_REFINE_MAX_IN_K);
+    if (rev_k > ZH_REFINE_MAX_IN_K - in_k) return fail(ZH_ELIMIT, "%s: in_k %zu + rev_k %zu > ZH_REFINE_MAX_IN_K (%u)", who, in_k, rev_k, ZH_REFINE_MAX_IN_K);
+    if (n && !in_k) return fail(ZH_EINVAL, "%s: in_k is 0", who);
+    if (fill != 0 && fill != 1) return fail(ZH_EINVAL, "%s: fill %d is neither 0 nor 1", who, fill);
+    return ZH_OK;
+}
+
+// One slab on device outputs (under mu, exclusive; exact_live_rows and refine_first_table have run; degree > 0, n > 0; dTab's lines are w wide):
+// every line filled as "no neighbours", then refine_slab's sub-slabs, a block per live line.  The line's row and the kept rows that become the
+// query are read where they are stored, their norms out of pr_qq: nothing is gathered.
+static int prune_slab(zh_index *ix, LiveCursor *live, const uint32_t *dTab, uint32_t w, uint64_t first_row, uint64_t n, uint32_t degree, uint32_t fill, int metric,
+                      int mode, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts, hipStream_t s, zh_knn_prune_info *inf) {
+    HIPCHK(zh_launch_exact_empty((uint32_t)n, degree, dIds, dKeys, dCounts, s));
+    for (uint64_t r0 = first_row; r0 < first_row + n; r0 += ZH_REFINE_SLAB) {
+        const uint64_t m = std::min<uint64_t>(ZH_REFINE_SLAB, first_row + n - r0);
+        const uint64_t lo = live_before(ix, r0, live), hi = live_before(ix, r0 + m, live);
+        const uint32_t B = (uint32_t)(hi - lo);
+        if (!B) continue;
+        HIPCHK(zh_launch_prune_lines(ix->X.as<float>(), ix->opt.dim, dTab, w, ix->live_dev.rows.as<uint32_t>() + lo, B, ix->pr_qq.as<float>(), metric,
+                                     score_param(metric, mode), ix->opt.id_base, first_row, degree, fill, dIds, dKeys, dCounts,
+                                     ix->pr_ctr.as<unsigned long long>(), s));
+        inf->lines += B;
+        inf->launches++;
+    }
+    return ZH_OK;
+}
+
+// both entry points once the arguments have been judged (n > 0)
+static int prune_call(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, uint32_t in_k, uint32_t rev_k, uint64_t first_row, uint64_t n, uint32_t degree,
+                      uint32_t fill, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts, bool host, void *stream, const char *who) {
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    int rc;
+    if ((rc = set_device(ix)) || (rc = exact_live_rows(ix)) || (rc = knn_range(ix, first_row, n, who))) return rc;
+    ScratchGuard guard{ix, SCRATCH_PRUNE};
+    const hipStream_t s = call_stream(ix, stream);
+    zh_knn_prune_info inf{};
+    unsigned long long ctr[6] = {0, 0, 0, 0, 0, 0};
+    if (degree == 0) {
+        if ((rc = knn_no_neighbours(n, out_counts, host, s))) return rc;
+    } else {
+        const uint64_t N = ix->n_rows;
+        const uint32_t d = ix->opt.dim;
+        const uint32_t *dTab = nullptr;
+        uint64_t rev_launches = 0;  // (`launches` are the line kernel's)
+        if (rev_k && (rc = ix->rv_uni.ensure((size_t)N * (in_k + rev_k) * 4))) return rc;
+        if ((rc = refine_first_table(ix, in_ids, in_counts, in_k, rev_k, first_row, n, host, s, ix->rv_uni.as<uint32_t>(), &dTab, &rev_launches))) return rc;
+        if ((rc = ix->pr_ctr.ensure(48))) return rc;
+        HIPCHK(hipMemsetAsync(ix->pr_ctr.p, 0, 48, s));
+        if (metric == ZH_COSINE) {  // every stored row's squared norm: a kept row's as the query, as zh_launch_qnorm gives it to the exact search
+            if ((rc = ix->pr_qq.ensure((size_t)N * 4))) return rc;
+            for (uint64_t r0 = 0; r0 < N; r0 += 1ull << 30)
+                HIPCHK(zh_launch_qnorm(ix->X.as<float>() + r0 * d, (uint32_t)std::min<uint64_t>(1ull << 30, N - r0), d, ix->pr_qq.as<float>() + r0, s));
+        }
+        LiveCursor live;
+        rc = knn_slabs(ix, first_row, n, degree, out_ids, out_keys, out_counts, refine_host_slab(degree), host, s,
+                       [&](uint64_t r0, uint64_t m, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
+                           return prune_slab(ix, &live, dTab, in_k + rev_k, r0, m, degree, fill, metric, mode, dIds, dKeys, dCounts, s, &inf);
+                       });
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(ctr, ix->pr_ctr.p, 48, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    inf.rows_live = ix->live_dev.n_live;
+    inf.in_k = in_k; inf.rev_k = rev_k; inf.degree = degree; inf.fill = fill;
+    inf.candidates = ctr[0]; inf.kept = ctr[1]; inf.occluded = ctr[2]; inf.filled = ctr[3]; inf.cut = ctr[4]; inf.keyed = ctr[5];
+    std::lock_guard<std::mutex> ls(ix->stats_mu);
+    ix->pr_info = inf;
+    return ZH_OK;
+}
+
+extern "C" int zh_knn_graph_prune_device(zh_index *ix, const uint64_t *d_in_ids, const uint32_t *d_in_counts, size_t in_k, size_t rev_k, uint64_t first_row,
+                                         uint64_t n, size_t degree, int fill, int metric, int mode, uint64_t *d_out_ids, uint64_t *d_out_keys,
+                                         uint32_t *d_out_counts, void *stream) {
+    int rc = prune_args(ix, d_in_ids, d_in_counts, in_k, rev_k, n, degree, fill, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_knn_graph_prune_device");
+    if (rc || n == 0) return rc;
+    return prune_call(ix, d_in_ids, d_in_counts, (uint32_t)in_k, (uint32_t)rev_k, first_row, n, (uint32_t)degree, (uint32_t)fill, metric, mode, d_out_ids,
+                      d_out_keys, d_out_counts, false, stream, "zh_knn_graph_prune_device");
+}
+
+extern "C" int zh_knn_graph_prune(zh_index *ix, const uint64_t *in_ids, const uint32_t *in_counts, size_t in_k, size_t rev_k, uint64_t first_row, uint64_t n,
+                                  size_t degree, int fill, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys, uint32_t *out_counts) {
+    int rc = prune_args(ix, in_ids, in_counts, in_k, rev_k, n, degree, fill, metric, mode, out_ids, out_keys, out_counts, "zh_knn_graph_prune");
+    if (rc || n == 0) return rc;
+    return prune_call(ix, in_ids, in_counts, (uint32_t)in_k, (uint32_t)rev_k, first_row, n, (uint32_t)degree, (uint32_t)fill, metric, mode, out_ids, out_keys,
+                      out_counts, true, nullptr, "zh_knn_graph_prune");
+}
+
+extern "C" int zh_knn_graph_prune_info(const zh_index *ix, zh_knn_prune_info *out) {
+    return get_info(ix, &zh_index::pr_info, out, "zh_knn_graph_prune_info");
 }
 
 // ------------------------------------------------------------------------------------------------

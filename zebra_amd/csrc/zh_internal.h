@@ -578,6 +578,14 @@ hipError_t zh_launch_gext_rerank(const float *dX, uint32_t d, uint32_t *dTab, ui
 // lines [x0, x0 + nl) of the table as ids: the kept entries in table order at the front (id_base + row), 2^64 - 1 behind them, and their counts
 hipError_t zh_launch_gext_read(const uint32_t *dTab, uint32_t g_k, uint64_t x0, uint64_t nl, uint64_t id_base, uint64_t *dOutIds, uint32_t *dOutCounts, hipStream_t s);
 
+// ---- k-NN graph pruning (zh_prune.hip): a block per line b (row dRows[b]) of dTab, w <= ZH_REFINE_MAX_IN_K wide (zh_launch_refine_rows' table or
+// zh_launch_reverse_select's union table): the unoccluded candidates in (key, id) order, at most `degree` of them, with fill the first occluded
+// ones behind a short line, to line row - first_row of the [..][degree] outputs.  dQQ: the squared norm of every stored row (cosine only).
+// dCtr[0..5] += candidates, kept, occluded, filled, lines cut at degree, keyed
+hipError_t zh_launch_prune_lines(const float *dX, uint32_t d, const uint32_t *dTab, uint32_t w, const uint32_t *dRows, uint32_t B, const float *dQQ, int metric,
+                                 int param, uint64_t id_base, uint64_t first_row, uint32_t degree, uint32_t fill, uint64_t *dOutIds, uint64_t *dOutKeys,
+                                 uint32_t *dOutCounts, unsigned long long *dCtr, hipStream_t s);
+
 // ---- the forest self-join (zh_fjoin.hip): every pair of leaf-mates whose key is <= one threshold key, each pair once (the first tree that puts
 // the two rows together owns it).  Hit pool, counter and order as the exact self-join's
 #define ZH_FJOIN_PANEL_LINES 16384u  // path 1: lines of one panel at most

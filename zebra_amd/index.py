@@ -749,6 +749,42 @@ class LSHIndex:
         lists keyed_round, updates_round and active_round"""
         return self._info(_ffi.KnnDescentInfo, lib().zh_knn_graph_descent_info)
 
+    def knn_graph_prune(self, graph, degree, metric, reverse=0, fill=False, first_row=0, n=None):
+        """the occlusion rule of the graph indexes over a graph of ALL stored rows (`graph` as for knn_graph_refine; zh_knn_graph_prune): the
+        candidates of stored row a = first_row + i are the live rows its line names and, with reverse > 0, up to `reverse` sampled reverse
+        neighbours (knn_graph_reverse's line), a itself excluded.  In (key, id) order under the key of row a as the query, a candidate is kept
+        unless a candidate kept before it is closer to it than a is -- its key against that kept row as the query is strictly below its key
+        against a -- until `degree` are kept; fill=True then makes up a short line with the first dropped candidates.  -> (ids [n, degree] u64,
+        keys [n, degree] u64, counts [n] u32), knn_graph's layout, each line ordered by (key, id).  degree and in_k + reverse at most 64.  No
+        forest needed; knn_prune_info() describes the call."""
+        in_ids, in_counts, stored = self._graph_arrays(graph, "knn_graph_prune")
+        n = max(stored - first_row, 0) if n is None else int(n)
+        degree = int(degree)
+        ids = np.empty((n, max(degree, 0)), np.uint64)
+        keys = np.empty((n, max(degree, 0)), np.uint64)
+        counts = np.zeros(n, np.uint32)
+        check(lib().zh_knn_graph_prune(self._h, _p(in_ids), _p(in_counts), in_ids.shape[1], int(reverse), int(first_row), n, degree, int(fill),
+                                       metric.metric, metric.mode, _p(ids), _p(keys), _p(counts)))
+        return ids, keys, counts
+
+    def knn_graph_prune_device(self, d_in_ids_ptr, d_in_counts_ptr, in_k, rev_k, degree, fill, metric, first_row, n, d_ids_ptr, d_keys_ptr, d_counts_ptr,
+                               stream=None):
+        """knn_graph_prune with the graph ([stored rows, in_k] u64, [stored rows] u32) and the outputs ([n, degree] u64 twice, [n] u32) already
+        in device memory (raw pointers, e.g. torch .data_ptr())."""
+        check(lib().zh_knn_graph_prune_device(self._h, d_in_ids_ptr, d_in_counts_ptr, int(in_k), int(rev_k), int(first_row), int(n), int(degree), int(fill),
+                                              metric.metric, metric.mode, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream))
+
+    def knn_prune_info(self):
+        """what the most recent knn_graph_prune call on this index did (zh_knn_graph_prune_info): rows_live, lines, in_k, rev_k, degree, fill,
+        candidates, kept (before filling), occluded, filled, cut (lines that stopped at degree with candidates unexamined), keyed, launches"""
+        return self._info(_ffi.KnnPruneInfo, lib().zh_knn_graph_prune_info)
+
+    def prune_graph(self, degree, metric, reverse=0, fill=False):
+        """prune the ATTACHED graph in place of itself: get_graph -> knn_graph_prune -> set_graph, a composition of those three calls through the
+        host and nothing more.  The graph must cover every stored row (extend_graph first if rows were added).  -> graph_info()"""
+        self.set_graph(self.knn_graph_prune(self.get_graph(), degree, metric, reverse=reverse, fill=fill))
+        return self.graph_info()
+
     def set_graph(self, graph, rows=None):
         """attach a k-NN graph for search_graph_batch (zh_index_set_graph): `graph` is (ids [g_rows, g_k] u64, counts [g_rows] u32) or the 3-tuple
         a graph call returns (its keys are not read), over the first g_rows = `rows` stored rows (default: as many as the arrays hold; at most
@@ -1429,14 +1465,18 @@ class Database:
         graph = self.index.knn_graph_forest(k, self.metric)
         return self._graph_documents(*self.index.knn_graph_descent(graph, k, self.metric, rounds=rounds, reverse=reverse))
 
-    def build_graph(self, k=32, rounds=8, reverse=0):
+    def build_graph(self, k=32, rounds=8, reverse=0, prune=0, prune_reverse=0, fill=False):
         """make the graph query_vectors_graph walks and attach it to the index: knn_graph_forest(k), LSHIndex.knn_graph_descent(rounds, reverse),
-        LSHIndex.set_graph.  Needs trees.  Records added later are found only as seeds until extend_graph gives them lines (or the graph is built
+        LSHIndex.set_graph.  prune > 0: LSHIndex.knn_graph_prune(degree=prune, reverse=prune_reverse, fill=fill) between the descent and the
+        attach; prune = 0 is the call without it.  Needs trees.  Records added later are found only as seeds until extend_graph gives them lines (or the graph is built
         again); removed ones are skipped at once.  -> LSHIndex.graph_info()"""
         if self.index.no_vectors():
             return self.index.graph_info()
         graph = self.index.knn_graph_forest(k, self.metric)
-        self.index.set_graph(self.index.knn_graph_descent(graph, k, self.metric, rounds=rounds, reverse=reverse))
+        graph = self.index.knn_graph_descent(graph, k, self.metric, rounds=rounds, reverse=reverse)
+        if prune:
+            graph = self.index.knn_graph_prune(graph, prune, self.metric, reverse=prune_reverse, fill=fill)
+        self.index.set_graph(graph)
         return self.index.graph_info()
 
     def extend_graph(self, beam=64, **kw):

@@ -364,6 +364,31 @@ class LSHIndex {  // Clone in the crate shares the store (lsh.rs:144-148): copie
         check(zh_knn_graph_info(h_.get(), &info));
         return info;
     }
+    // the k-NN join between two indexes over the slab of this index's stored rows [first_row, first_row + n) (zh_cross_knn): element i = the k
+    // nearest live rows of `other` to stored row first_row + i by (key, id), the key that of other's stored row against a query equal to the row
+    // (other.search_exact's answer); ids carry other's id_base; empty for a removed row.  `other` must be a different index of the same dim on the
+    // same device.  k <= ZH_MAX_TOPK.
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> cross_knn(const LSHIndex &other, std::size_t k, const Met &metric, std::uint64_t first_row,
+                                                                    std::uint64_t n) const {
+        std::vector<Id> ids(n * k + 1);
+        std::vector<DistanceUnit> keys(n * k + 1);
+        std::vector<std::uint32_t> counts(n + 1);
+        check(zh_cross_knn(h_.get(), other.h_.get(), first_row, n, k, Met::metric, metric.mode(), ids.data(), keys.data(), counts.data()));
+        std::vector<std::vector<std::pair<Id, DistanceUnit>>> out(n);
+        for (std::uint64_t i = 0; i < n; i++)
+            for (std::uint32_t j = 0; j < counts[i]; j++) out[i].emplace_back(ids[i * k + j], keys[i * k + j]);
+        return out;
+    }
+    template <class Met>
+    std::vector<std::vector<std::pair<Id, DistanceUnit>>> cross_knn(const LSHIndex &other, std::size_t k, const Met &metric) const {
+        return cross_knn(other, k, metric, 0, zh_index_stored_rows(h_.get()));
+    }
+    zh_xknn_info cross_knn_info() const {
+        zh_xknn_info info{};
+        check(zh_cross_knn_info(h_.get(), &info));
+        return info;
+    }
     // the forest k-NN graph of the slab (zh_knn_graph_forest): knn_graph's shape, the candidates of a row being the rows that share a leaf with it
     // in some tree; empty for a removed row and for a row no tree holds.  Needs a built forest.
     template <class Met>

@@ -30,6 +30,7 @@
  *   zh_self_join[_device]                (new) every pair of live rows whose key is at or below one threshold key, each pair once
  *   zh_cross_join[_device]               (new) every pair (live row of one index, live row of another) whose key is at or below one threshold key
  *   zh_knn_graph[_device]                (new) every live row's exact k nearest OTHER live rows, slab by slab
+ *   zh_cross_knn[_device]                (new) every live row of one index's exact k nearest live rows of ANOTHER index, slab by slab
  *   zh_knn_graph_forest[_device]         (new) every row's k nearest rows among its leaf-mates in the forest: exact keys, approximate candidates
  *   zh_knn_graph_refine[_device]         (new) one NN-descent join round over a caller's graph: every row's neighbours and their neighbours, ranked
  *                                        by the exact key
@@ -607,6 +608,54 @@ typedef struct zh_knn_info {  /* the most recent zh_knn_graph* call on this inde
 } zh_knn_info;
 /* What the host loop that zh_knn_graph replaces could only count by hand. */
 ZH_API int zh_knn_graph_info(const zh_index *idx, zh_knn_info *out);
+
+/* Exact k-NN JOIN BETWEEN TWO INDEXES (new; the reference has no such call): for every live stored row a of the slab [first_row, first_row + n) of
+ * index `a` its exact top-k by (key, id) over every live row of index `b`.  It replaces the loop "zh_index_read_rows of A back to the host,
+ * zh_search_exact_batch on B 1024 rows at a time": link an incoming batch to its k nearest corpus rows, k-NN classification and label transfer,
+ * ground truth for what a graph walk found, without a radius the caller does not know.
+ * Lines.  Output line i belongs to STORED row first_row + i of A, 0 <= i < n: out_ids / out_keys are [n][k] u64, out_counts [n] u32.  A slab
+ * interface for zh_knn_graph's reason.  first_row + n > A's stored rows is ZH_EINVAL; n = 0 is ZH_OK.
+ * Neighbours.  The key of (a, b) is the key zh_distance_batch gives for STORED row b of B against a QUERY equal to the f32 values of row a of A:
+ * the line of a is zh_search_exact_batch(B, rows_A[a], k) bit for bit -- ids (B's id_base + row), keys, (key, id) order.  That orientation is the
+ * definition; zh_cross_knn(b, a) is a different call.  Nothing is excluded: a row of B that is bit-identical to row a is an ordinary neighbour.
+ * Counts and tails.  out_counts[i] = min(k, live rows of B) for a live row of A, 0 for a removed one; entries past the count are UINT64_MAX in both
+ * arrays.  An empty B, or one without a live row, gives count 0 everywhere with ZH_OK.
+ * Limits.  k = 0 zeroes the counts and touches nothing else; k > ZH_MAX_TOPK is ZH_ELIMIT (no slot has to be spared here, unlike zh_knn_graph).
+ * Refused before any device is touched and before either handle is followed: a NULL index on either side, a == b (ZH_EINVAL; use zh_knn_graph),
+ * NULL outputs for a non-empty request, an unknown metric, the k limit.  Refused with ZH_EINVAL under the locks: different dim, indexes on
+ * different devices.  All 13 metric / mode / power combinations and every dimension are served.
+ * Locking: BOTH indexes' internal locks, exclusively, taken together as for zh_cross_join (cross_knn(A, B) on one thread and cross_knn(B, A) on
+ * another do not deadlock); never concurrent with add / build / remove / clear of either index.  All per-call scratch and zh_xknn_info live
+ * on the LEFT index `a`; B lends its f32 rows, its fp16 row copy and rowMeta, its live bitmap and its live list.  zh_stats_t, every sibling info
+ * struct of BOTH indexes, the search contexts and the contents of the cached live-row views are left alone.
+ * The work goes panel by panel (up to 1024 live rows of A's slab, ascending).  Two paths, same answers.  Path 1 gathers the panel out of A's f32
+ * table as queries and lets the exact search's path 1 rank B's live list against it with k.  Path 2 (ZH_L2SQ, ZH_L2, ZH_COSINE at dim 256 / 384 /
+ * 512 / 768 / 1024, the fp16 row copy present on BOTH sides, B with at least max(k, 8192) live rows) gathers the panel's tiles out of A's fp16 copy
+ * and multiplies them by every tile of B's on the matrix cores for an interval per pair, with a falling bound per line as in the exact search;
+ * only the survivors get the canonical key.  A panel whose candidate list runs over is answered by path 1 (`redone`).  ZH_XKNN_PATH in the
+ * environment (read per call): 1 keeps every panel on path 1, 2 takes path 2 wherever it is supported and B has at least k live rows;
+ * ZH_XKNN_LIST_CAP=n (read per call; tests) lowers the list capacity.
+ * Device scratch is allocated per call on A's device and released before it returns: on path 2 20 bytes per stored row of B, 4 per stored row of A
+ * under a scan order of A that is not id order, and per panel of P <= 1024 lines P (6 dim + 12) bytes of rows and 36 P (16384 + 8 k) bytes of
+ * lists; on path 1 the panel's rows and up to 1 GiB of key scratch; both 16 P k bytes of panel answer; for the host call 16 k + 4 bytes per line
+ * of a sub-slab of 65536 lines. */
+ZH_API int zh_cross_knn(zh_index *a, zh_index *b, uint64_t first_row, uint64_t n, size_t k, int metric, int cosine_mode, uint64_t *out_ids,
+                        uint64_t *out_keys, uint32_t *out_counts);
+/* The same with every output in device memory; enqueued on `stream` (NULL = A's own stream), complete on return. */
+ZH_API int zh_cross_knn_device(zh_index *a, zh_index *b, uint64_t first_row, uint64_t n, size_t k, int metric, int cosine_mode, uint64_t *d_out_ids,
+                               uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream);
+typedef struct zh_xknn_info {  /* the most recent zh_cross_knn* call with this index on the LEFT */
+    uint64_t rows_live_a; /* live rows of the left index */
+    uint64_t rows_live_b; /* live rows of the right index */
+    uint64_t lines;       /* live rows of A answered (the slab's live rows) */
+    uint32_t k;
+    uint32_t path;        /* 1: the exact search's path 1 over B's live list; 2: matrix-core intervals, canonical keys for the survivors only */
+    uint32_t redone;      /* path 2: panels whose list ran over and that path 1 answered again */
+    uint64_t survivors;   /* path 2: pairs that got the canonical key, over the panels path 2 completed */
+    uint64_t launches;    /* launches of the scan (row chunks of B on path 1, column chunks of B on path 2) */
+    uint64_t tiles;       /* path 2: 16 x 16 tile products issued, from the launch geometry (panel tiles of A x column tiles of B) */
+} zh_xknn_info;
+ZH_API int zh_cross_knn_info(const zh_index *a, zh_xknn_info *out);
 
 /* ---- forest k-NN graph (new): each stored row's k nearest rows AMONG ITS LEAF-MATES -------------------------------------------------------
  * zh_knn_graph multiplies every row by every row; this call multiplies a row only by the rows the random-projection forest puts beside it.

@@ -160,6 +160,20 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Default, Clone, Copy)]
+    pub struct zh_xknn_info {
+        pub rows_live_a: u64,
+        pub rows_live_b: u64,
+        pub lines: u64,
+        pub k: u32,
+        pub path: u32,
+        pub redone: u32,
+        pub survivors: u64,
+        pub launches: u64,
+        pub tiles: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Default, Clone, Copy)]
     pub struct zh_knn_forest_info {
         pub rows_live: u64,
         pub lines: u64,
@@ -472,6 +486,11 @@ pub mod ffi {
         pub fn zh_knn_graph_device(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int, d_out_ids: *mut u64,
                                    d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
         pub fn zh_knn_graph_info(idx: *const zh_index, out: *mut zh_knn_info) -> c_int;
+        pub fn zh_cross_knn(a: *mut zh_index, b: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int,
+                            out_ids: *mut u64, out_keys: *mut u64, out_counts: *mut u32) -> c_int;
+        pub fn zh_cross_knn_device(a: *mut zh_index, b: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int,
+                                   d_out_ids: *mut u64, d_out_keys: *mut u64, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
+        pub fn zh_cross_knn_info(a: *const zh_index, out: *mut zh_xknn_info) -> c_int;
         pub fn zh_knn_graph_forest(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int, out_ids: *mut u64,
                                    out_keys: *mut u64, out_counts: *mut u32) -> c_int;
         pub fn zh_knn_graph_forest_device(idx: *mut zh_index, first_row: u64, n: u64, k: usize, metric: c_int, cosine_mode: c_int,
@@ -1016,6 +1035,44 @@ impl<const N: usize> LSHIndex<N> {
             first += n;
         }
         Ok(out)
+    }
+
+    /// (new) the k-NN join between two indexes (zh_cross_knn): per stored vector of self, in row order, its `k` nearest live vectors of `other`
+    /// by (key, row) -- the key that of other's stored vector against a query equal to the vector, other's exact search bit for bit; nothing is
+    /// excluded; a removed vector's list is empty.  Fetched in slabs of 65536 rows.  `self` and `other` must be different indexes.
+    pub fn cross_knn<Met: Metric<Embedding<N>, Unit = DistanceUnit> + HipMetric + Send + Sync>(
+        &self,
+        other: &Self,
+        k: usize,
+        metric: &Met,
+    ) -> anyhow::Result<Vec<(Uuid, Vec<(Uuid, DistanceUnit)>)>> {
+        const SLAB: u64 = 65536;
+        let ta = self.ids.read().unwrap();
+        let tb = other.ids.read().unwrap();
+        let stored = ta.of_row.len() as u64;
+        let mut out = Vec::with_capacity(stored as usize);
+        let (mut ids, mut keys, mut counts) = (vec![0u64; SLAB as usize * k + 1], vec![0u64; SLAB as usize * k + 1], vec![0u32; SLAB as usize]);
+        let mut first = 0u64;
+        while first < stored {
+            let n = SLAB.min(stored - first);
+            check(unsafe {
+                ffi::zh_cross_knn(self.hip.0, other.hip.0, first, n, k, Met::METRIC, metric.param(), ids.as_mut_ptr(), keys.as_mut_ptr(),
+                                  counts.as_mut_ptr())
+            })?;
+            for i in 0..n as usize {
+                let line = (0..counts[i] as usize).map(|j| (tb.of_row[ids[i * k + j] as usize], keys[i * k + j])).collect();
+                out.push((ta.of_row[first as usize + i], line));
+            }
+            first += n;
+        }
+        Ok(out)
+    }
+
+    /// what the most recent cross_knn with this index on the left did (zh_cross_knn_info)
+    pub fn cross_knn_info(&self) -> anyhow::Result<ffi::zh_xknn_info> {
+        let mut info = ffi::zh_xknn_info::default();
+        check(unsafe { ffi::zh_cross_knn_info(self.hip.0, &mut info) })?;
+        Ok(info)
     }
 
     /// (new) the forest k-NN graph (zh_knn_graph_forest): knn_graph's shape, a vector's candidates being the vectors that share a leaf with it in

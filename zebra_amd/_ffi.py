@@ -141,6 +141,14 @@ class KnnInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CrossKnnInfo(C.Structure):
+    _fields_ = [("rows_live_a", C.c_uint64), ("rows_live_b", C.c_uint64), ("lines", C.c_uint64), ("k", C.c_uint32), ("path", C.c_uint32),
+                ("redone", C.c_uint32), ("survivors", C.c_uint64), ("launches", C.c_uint64), ("tiles", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class KnnForestInfo(C.Structure):
     _fields_ = [("rows_live", C.c_uint64), ("lines", C.c_uint64), ("k", C.c_uint32), ("path", C.c_uint32), ("trees", C.c_uint32),
                 ("pairs", C.c_uint64), ("survivors", C.c_uint64), ("redone", C.c_uint32), ("launches", C.c_uint64), ("tiles", C.c_uint64)]
@@ -330,6 +338,9 @@ SYMBOLS = [
     ("zh_knn_graph", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_knn_graph_device", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_knn_graph_info", _i, [_vp, _vp]),
+    ("zh_cross_knn", _i, [_vp, _vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
+    ("zh_cross_knn_device", _i, [_vp, _vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    ("zh_cross_knn_info", _i, [_vp, _vp]),
     ("zh_knn_graph_forest", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp]),
     ("zh_knn_graph_forest_device", _i, [_vp, _u64, _u64, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     ("zh_knn_graph_forest_info", _i, [_vp, _vp]),

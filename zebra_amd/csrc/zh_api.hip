@@ -337,6 +337,9 @@ struct zh_index {
     // tiles, rowMeta and row numbers, the lists' bases, the panel's answer, and the outputs staged for the host call
     DevBuf kn_qm, kn_cid, kn_pos, kn_A, kn_pmeta, kn_pid, kn_cbase, kn_pids, kn_pkeys, kn_pcounts, kn_oids, kn_okeys, kn_ocounts;
     zh_knn_info kn_info{};  // (stats_mu)
+    // what the k-NN join between two indexes holds beside the graph's, on the LEFT index: path 2's per-position views of B (query view, id word)
+    DevBuf xk_qmb, xk_cidb;
+    zh_xknn_info xk_info{};  // (stats_mu)
     // the forest k-NN graph's per-call scratch (all released before the call returns): the node -> tree map, a sub-slab's row -> leaf table, line
     // flags, their exclusive sums and the lines, {pairs, tiles} counters, a path-1 panel's visit sizes, bases, groups and their row offsets, and
     // path 2's batch: segments, column sources, column and held rows, held counts, both sides' tiles, rowMeta and queries, the lines' rows and
@@ -3600,7 +3603,7 @@ static int score_param(int metric, int mode) { return (metric == ZH_COSINE || me
 // index holds only the live-row views (live_dev's list and bitmap survive every call; zh_index_destroy frees them).  Every family scans with the exact
 // search's buffers, the forest graph with the graph's as well, the forest join with the join's and the forest graph's, the forest range search with
 // the range search's and the forest join's, the cross-join (all on its LEFT index) with the join's and its own views.
-enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024, SCR_ND = 2048, SCR_GS = 4096, SCR_GE = 8192, SCR_PR = 16384 };  // one bit per list
+enum : unsigned { SCR_EX = 1, SCR_FL = 2, SCR_RG = 4, SCR_JN = 8, SCR_KN = 16, SCR_FK = 32, SCR_FJ = 64, SCR_FR = 128, SCR_XJ = 256, SCR_RF = 512, SCR_RV = 1024, SCR_ND = 2048, SCR_GS = 4096, SCR_GE = 8192, SCR_PR = 16384, SCR_XK = 32768 };  // one bit per list
 enum : unsigned {
     SCRATCH_EXACT = SCR_EX,
     SCRATCH_FILTER = SCR_FL | SCRATCH_EXACT,
@@ -3619,6 +3622,7 @@ enum : unsigned {
     SCRATCH_FJOIN = SCR_FJ | SCRATCH_JOIN | SCRATCH_FKNN,
     SCRATCH_FRANGE = SCR_FR | SCRATCH_RANGE | SCRATCH_FJOIN,
     SCRATCH_XJOIN = SCR_XJ | SCRATCH_JOIN,  // (on the left index)
+    SCRATCH_XKNN = SCR_XK | SCRATCH_KNN,    // (on the left index)
 };
 static void release_scratch(zh_index *ix, unsigned families) {
     auto drop = [&](unsigned list, std::initializer_list<DevBuf *> bs) {
@@ -3634,6 +3638,7 @@ static void release_scratch(zh_index *ix, unsigned families) {
     drop(SCR_JN, {&ix->jn_ctr, &ix->jn_maxk, &ix->jn_tau, &ix->jn_pv0, &ix->jn_pv1, &ix->jn_pk0, &ix->jn_pk1, &ix->jn_qm, &ix->jn_cid, &ix->jn_first,
                   &ix->jn_cand, &ix->jn_rows, &ix->jn_tmp, &ix->jn_oa, &ix->jn_ob, &ix->jn_okeys});
     drop(SCR_XJ, {&ix->xj_qma, &ix->xj_cida, &ix->xj_qmb, &ix->xj_cidb});
+    drop(SCR_XK, {&ix->xk_qmb, &ix->xk_cidb});
     drop(SCR_KN, {&ix->kn_qm, &ix->kn_cid, &ix->kn_pos, &ix->kn_A, &ix->kn_pmeta, &ix->kn_pid, &ix->kn_cbase, &ix->kn_pids, &ix->kn_pkeys, &ix->kn_pcounts,
                   &ix->kn_oids, &ix->kn_okeys, &ix->kn_ocounts});
     drop(SCR_FK, {&ix->fk_ntree, &ix->fk_rl, &ix->fk_flag, &ix->fk_excl, &ix->fk_tmp, &ix->fk_rows, &ix->fk_ctr, &ix->fk_lens, &ix->fk_takes, &ix->fk_rbase,
@@ -3772,9 +3777,11 @@ static int exact_live_rows(zh_index *ix) {
 // one internal batch (B <= ZH_EXACT_BATCH) on device pointers, enqueued on s.  Row chunk after row chunk: keys of all queries into the
 // scratch, each query's top_k of every sub-chunk of L positions (select_kernel), a query's sub-chunks merged (final_kernel), the chunk's
 // answer merged into the running one (the caller's outputs) -- merge_wave_kernel / final_kernel<true>.
+// st (the k-NN join between two indexes): the index whose table and id base the rows dLive are of, all scratch staying on ix; null: ix itself.
 static int exact_batch(zh_index *ix, const uint32_t *dLive, uint64_t n_live, const float *dQ, uint32_t B, uint32_t k, int metric, int mode,
-                       uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts, hipStream_t s, uint64_t *launches) {
+                       uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts, hipStream_t s, uint64_t *launches, const zh_index *st = nullptr) {
     const uint32_t d = ix->opt.dim;
+    if (!st) st = ix;
     if (k == 0) { HIPCHK(hipMemsetAsync(dCounts, 0, (size_t)B * 4, s)); return ZH_OK; }
     if (n_live == 0) { HIPCHK(zh_launch_exact_empty(B, k, dIds, dKeys, dCounts, s)); return ZH_OK; }
     const uint32_t L = k <= 512 ? 2048u : 4096u, kk = std::min(k, L);
@@ -3794,16 +3801,16 @@ static int exact_batch(zh_index *ix, const uint32_t *dLive, uint64_t n_live, con
     HIPCHK(zh_launch_qnorm(dQ, B, d, ix->ex_QQ.as<float>(), s));
     for (uint64_t p0 = 0; p0 < n_live; p0 += rc_rows) {
         const uint32_t nr = (uint32_t)std::min<uint64_t>(rc_rows, n_live - p0), nsub = (nr + L - 1) / L;
-        HIPCHK(zh_launch_exact_score(ix->X.as<float>(), d, dLive, p0, nr, dQ, ix->ex_QQ.as<float>(), B, metric, param, ix->ex_keys.as<uint64_t>(),
+        HIPCHK(zh_launch_exact_score(st->X.as<float>(), d, dLive, p0, nr, dQ, ix->ex_QQ.as<float>(), B, metric, param, ix->ex_keys.as<uint64_t>(),
                                      rc_rows, s));
         HIPCHK(zh_launch_exact_visits(B, nsub, nr, L, k, p0, rc_rows, ix->ex_visits.as<ZhVisit>(), ix->ex_cbase.as<uint64_t>(), s));
         HIPCHK(zh_launch_select(ix->ex_visits.as<ZhVisit>(), (uint64_t)B * nsub, dLive, ix->ex_keys.as<uint64_t>(), ix->ex_ckeys.as<uint64_t>(),
                                 ix->ex_cids.as<uint32_t>(), L, nullptr, s));
         if (p0 == 0) {
-            HIPCHK(zh_launch_final(ix->ex_cbase.as<uint64_t>(), B, nsub, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), ix->opt.id_base,
+            HIPCHK(zh_launch_final(ix->ex_cbase.as<uint64_t>(), B, nsub, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), st->opt.id_base,
                                    dIds, dKeys, dCounts, nullptr, s));
         } else {  // this chunk's answer into slot 1, the running one (the outputs) into slot 0, both merged back into the outputs
-            HIPCHK(zh_launch_final(ix->ex_cbase.as<uint64_t>(), B, nsub, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), ix->opt.id_base,
+            HIPCHK(zh_launch_final(ix->ex_cbase.as<uint64_t>(), B, nsub, k, ix->ex_ckeys.as<uint64_t>(), ix->ex_cids.as<uint32_t>(), st->opt.id_base,
                                    runIds + (size_t)B * k, runKeys + (size_t)B * k, runCounts + B, nullptr, s));
             HIPCHK(hipMemcpyAsync(runIds, dIds, (size_t)B * k * 8, hipMemcpyDeviceToDevice, s));
             HIPCHK(hipMemcpyAsync(runKeys, dKeys, (size_t)B * k * 8, hipMemcpyDeviceToDevice, s));
@@ -5063,6 +5070,188 @@ extern "C" int zh_knn_graph(zh_index *ix, uint64_t first_row, uint64_t n, size_t
 }
 
 extern "C" int zh_knn_graph_info(const zh_index *ix, zh_knn_info *out) { return get_info(ix, &zh_index::kn_info, out, "zh_knn_graph_info"); }
+
+// ------------------------------------------------------------------------------------------------
+// exact k-NN join between two indexes (zh_xknn.hip, the graph's panels and the exact search's two paths): each live row of A's k nearest live rows
+// of B, slab by slab of A.  All scratch and the info on A.  DESIGN.md s30
+// ------------------------------------------------------------------------------------------------
+struct XknnRun {  // what a call settles once, before its slabs
+    bool path2 = false;
+    HalfView va, vb;
+    const uint32_t *posA = nullptr;  // row -> position of A under A's row order, else null
+    float Kc = 0.f;
+    uint32_t cap = 0;                // list slots per line
+    LiveCursor live;                 // (the slabs of a call ascend)
+};
+
+// The gate of path 2 and its per-call views: B's positions as approx_interval's queries with B's rho (zh_launch_join_prep), A's row -> position map
+// under a row order of A, the lists' bases.  ZH_XKNN_PATH (read per call): 1 keeps everything on path 1, 2 takes path 2 wherever it is supported
+// and B has at least k live rows.
+static int xknn_setup(zh_index *ia, zh_index *ib, uint32_t k, int metric, int mode, hipStream_t s, XknnRun *run) {
+    const uint32_t d = ia->opt.dim;
+    const char *env_p = getenv("ZH_XKNN_PATH");
+    const int env_path = env_p ? atoi(env_p) : 0;
+    if (env_path == 1 || !zh_exact_mfma_supported(d, metric)) return ZH_OK;
+    const uint64_t lb = ib->live_dev.n_live;
+    if (!lb || lb < (env_path == 2 ? (uint64_t)k : std::max<uint64_t>(k, 8192))) return ZH_OK;
+    int rc;
+    bool have_a = false, have_b = false;
+    {
+        std::lock_guard<std::mutex> lk(ia->blk_mu);
+        if ((rc = half_view(ia, &run->va, &have_a))) return rc;
+    }
+    if (!have_a) return ZH_OK;
+    {
+        std::lock_guard<std::mutex> lk(ib->blk_mu);
+        if ((rc = half_view(ib, &run->vb, &have_b))) return rc;  // (a copy made now is complete on return: ensure_row_half waits for ib's stream)
+    }
+    if (!have_b) return ZH_OK;
+    const uint64_t na = ia->n_rows, nb = ib->n_rows, nb_pos = (nb + 15) / 16 * 16;
+    run->cap = 16384 + 8 * k;
+    const char *env_c = getenv("ZH_XKNN_LIST_CAP");
+    if (env_c && atoi(env_c) > 0) run->cap = std::min<uint32_t>(run->cap, (uint32_t)atoi(env_c));
+    if ((rc = ia->xk_qmb.ensure(nb_pos * 16)) || (rc = ia->xk_cidb.ensure(nb_pos * 4)) || (rc = ia->kn_cbase.ensure((ZH_KNN_PANEL_ROWS + 1) * 8))) return rc;
+    const HalfView &vb = run->vb;
+    HIPCHK(zh_launch_join_prep(vb.rowMeta, vb.perm, vb.perm_rows, ib->live_dev.bits.as<uint32_t>(), nb, vb.rho, ia->xk_qmb.as<float4>(), ia->xk_cidb.as<uint32_t>(), s));
+    if (run->va.perm_rows) {
+        if ((rc = ia->kn_pos.ensure(na * 4))) return rc;
+        HIPCHK(zh_launch_fknn_rowpos(run->va.perm, run->va.perm_rows, na, ia->kn_pos.as<uint32_t>(), s));
+        run->posA = ia->kn_pos.as<uint32_t>();
+    }
+    std::vector<uint64_t> cb(ZH_KNN_PANEL_ROWS + 1);
+    if ((rc = list_bases(ia->kn_cbase.p, cb, run->cap, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));  // (cb is this frame's)
+    run->Kc = zh_approx_bound(metric, d, 1);
+    run->path2 = true;
+    return ZH_OK;
+}
+
+// Path 2 of one panel (the B live rows dRows of A, ascending): its answer [B][k] into ia's kn_pids / kn_pkeys / kn_pcounts.  *overflowed: a line's
+// list ran over and the answer is not valid (the caller answers the panel by path 1).  The held side is A (its copy's bits, rowMeta and rho), the
+// columns are B's; the survivors' keys are those of (stored row of B's table, query = the gathered f32 row of A): the contract's orientation.
+static int xknn_panel2(zh_index *ia, zh_index *ib, const XknnRun &run, const uint32_t *dRows, uint32_t B, uint32_t k, int metric, int mode, hipStream_t s,
+                       bool *overflowed, zh_xknn_info *inf) {
+    const uint32_t d = ia->opt.dim, cap = run.cap, PT = (B + 15) / 16;
+    ZhExact2 e{run.vb.Xh, run.vb.rowMeta, nullptr, 0, ib->live_dev.bits.as<uint32_t>(), nullptr, nullptr, B, run.Kc, run.va.rho};
+    int rc;
+    if ((rc = ia->kn_A.ensure((size_t)PT * 16 * d * 2)) || (rc = ia->kn_pmeta.ensure((size_t)PT * 16 * 8)) || (rc = ia->kn_pid.ensure((size_t)PT * 16 * 4)) ||
+        (rc = ia->ex_Q.ensure((size_t)B * d * 4)) || (rc = ia->ex_QQ.ensure((size_t)B * 4)) || (rc = lists_ensure(ia, B, cap, false, &e)))
+        return rc;
+    HIPCHK(zh_launch_knn_panel(d, run.va.Xh, run.va.rowMeta, run.posA, dRows, B, ia->kn_A.p, ia->kn_pmeta.as<float2>(), ia->kn_pid.as<uint32_t>(), s));
+    HIPCHK(zh_launch_join_gather(ia->X.as<float>(), d, dRows, B, ia->ex_Q.as<float>(), s));
+    HIPCHK(zh_launch_qnorm(ia->ex_Q.as<float>(), B, d, ia->ex_QQ.as<float>(), s));
+    HIPCHK(hipMemsetAsync(e.tau, 0xFF, (size_t)B * 4, s));
+    if ((rc = lists_reset(e, s))) return rc;
+    const uint64_t n = ib->n_rows;  // positions of B's copy; removed rows are masked by the id word
+    uint64_t chunk = (std::max<uint64_t>(k, 4096) + 15) / 16 * 16;
+    for (uint64_t p0 = 0; p0 < n; p0 += chunk, chunk *= ZH_EXACT_GROWTH) {
+        const uint64_t p1 = std::min(n, p0 + chunk);
+        HIPCHK(zh_launch_xknn_mfma(d, metric, mode, e, ia->xk_qmb.as<float4>(), ia->xk_cidb.as<uint32_t>(), p0, p1, ia->kn_A.p, ia->kn_pmeta.as<float2>(),
+                                   ia->kn_pid.as<uint32_t>(), s));
+        HIPCHK(zh_launch_exact_prune(e, k, ia->ex_scr.as<uint32_t>(), s));
+        inf->launches++;
+        inf->tiles += (uint64_t)PT * ((p1 + 15) / 16 - p0 / 16);
+    }
+    HIPCHK(zh_launch_exact_survivor_keys(ib->X.as<float>(), d, ia->ex_Q.as<float>(), ia->ex_QQ.as<float>(), metric, mode, e, ia->ex_ckeys.as<uint64_t>(),
+                                         ia->ex_cids.as<uint32_t>(), s));
+    HIPCHK(zh_launch_final(ia->kn_cbase.as<uint64_t>(), B, 1, k, ia->ex_ckeys.as<uint64_t>(), ia->ex_cids.as<uint32_t>(), ib->opt.id_base,
+                           ia->kn_pids.as<uint64_t>(), ia->kn_pkeys.as<uint64_t>(), ia->kn_pcounts.as<uint32_t>(), nullptr, s));
+    return lists_end(e, s, overflowed, &inf->survivors);
+}
+
+// One slab of A on device outputs (under both mu, exclusive; xjoin_state and xknn_setup have run; k > 0, n > 0): every line filled as "no
+// neighbours", then panel after panel of the slab's live rows.  A B without a live row leaves it at that.
+static int xknn_slab(zh_index *ia, zh_index *ib, XknnRun *run, uint64_t first_row, uint64_t n, uint32_t k, int metric, int mode, uint64_t *dIds,
+                     uint64_t *dKeys, uint32_t *dCounts, hipStream_t s, zh_xknn_info *inf) {
+    const uint32_t d = ia->opt.dim;
+    int rc;
+    HIPCHK(zh_launch_exact_empty((uint32_t)n, k, dIds, dKeys, dCounts, s));
+    const uint64_t lo = live_before(ia, first_row, &run->live), hi = live_before(ia, first_row + n, &run->live);
+    inf->lines += hi - lo;
+    if (!ib->live_dev.n_live) return ZH_OK;
+    if ((rc = ia->kn_pids.ensure((size_t)ZH_KNN_PANEL_ROWS * k * 8)) || (rc = ia->kn_pkeys.ensure((size_t)ZH_KNN_PANEL_ROWS * k * 8)) ||
+        (rc = ia->kn_pcounts.ensure((size_t)ZH_KNN_PANEL_ROWS * 4)))
+        return rc;
+    for (uint64_t a0 = lo; a0 < hi; a0 += ZH_KNN_PANEL_ROWS) {
+        const uint32_t B = (uint32_t)std::min<uint64_t>(ZH_KNN_PANEL_ROWS, hi - a0);
+        const uint32_t *dRows = ia->live_dev.rows.as<uint32_t>() + a0;
+        bool answered = false;
+        if (run->path2) {
+            bool overflowed = false;
+            if ((rc = xknn_panel2(ia, ib, *run, dRows, B, k, metric, mode, s, &overflowed, inf))) return rc;
+            answered = !overflowed;
+            if (overflowed) inf->redone++;
+        }
+        if (!answered) {  // path 1: the panel as queries, k over B's live list
+            if ((rc = ia->ex_Q.ensure((size_t)B * d * 4))) return rc;
+            HIPCHK(zh_launch_join_gather(ia->X.as<float>(), d, dRows, B, ia->ex_Q.as<float>(), s));
+            if ((rc = exact_batch(ia, ib->live_dev.rows.as<uint32_t>(), ib->live_dev.n_live, ia->ex_Q.as<float>(), B, k, metric, mode, ia->kn_pids.as<uint64_t>(),
+                                  ia->kn_pkeys.as<uint64_t>(), ia->kn_pcounts.as<uint32_t>(), s, &inf->launches, ib)))
+                return rc;
+        }
+        HIPCHK(zh_launch_xknn_emit(ia->kn_pids.as<uint64_t>(), ia->kn_pkeys.as<uint64_t>(), ia->kn_pcounts.as<uint32_t>(), dRows, B, first_row, k, dIds, dKeys,
+                                   dCounts, s));
+    }
+    return ZH_OK;
+}
+
+// judged before any device is touched (and before either handle is followed)
+static int xknn_args(const zh_index *ia, const zh_index *ib, uint64_t n, size_t k, int metric, int mode, const void *ids, const void *keys, const void *counts,
+                     const char *who) {
+    if (!ia || !ib) return fail(ZH_EINVAL, "%s: null argument", who);
+    if (ia == ib) return fail(ZH_EINVAL, "%s: the two indexes are the same one; zh_knn_graph ranks an index's rows against its own", who);
+    if (n && (!counts || (k && (!ids || !keys)))) return fail(ZH_EINVAL, "%s: null argument", who);
+    int rc = check_metric(metric, mode);
+    if (rc) return rc;
+    if (k > ZH_MAX_TOPK) return fail(ZH_ELIMIT, "%s: k %zu > ZH_MAX_TOPK (%u)", who, k, ZH_MAX_TOPK);
+    return ZH_OK;
+}
+
+// both entry points once the arguments have been judged (n > 0)
+static int xknn_call(zh_index *ia, zh_index *ib, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys,
+                     uint32_t *out_counts, bool host, void *stream, const char *who) {
+    XjoinLocks locks(ia, ib);
+    int rc;
+    if ((rc = xjoin_state(ia, ib, who)) || (rc = knn_range(ia, first_row, n, who))) return rc;
+    ScratchGuard guard{ia, SCRATCH_XKNN};
+    const hipStream_t s = call_stream(ia, stream);
+    zh_xknn_info inf{};
+    inf.path = 1;
+    if (k == 0) {
+        if ((rc = knn_no_neighbours(n, out_counts, host, s))) return rc;
+    } else {
+        XknnRun run;
+        if ((rc = xknn_setup(ia, ib, (uint32_t)k, metric, mode, s, &run))) return rc;
+        if (run.path2) inf.path = 2;
+        rc = knn_slabs(ia, first_row, n, k, out_ids, out_keys, out_counts, ZH_KNN_HOST_SLAB, host, s,
+                       [&](uint64_t r0, uint64_t m, uint64_t *dIds, uint64_t *dKeys, uint32_t *dCounts) {
+                           return xknn_slab(ia, ib, &run, r0, m, (uint32_t)k, metric, mode, dIds, dKeys, dCounts, s, &inf);
+                       });
+        if (rc) return rc;
+    }
+    std::lock_guard<std::mutex> lk(ia->stats_mu);
+    inf.k = (uint32_t)k;
+    inf.rows_live_a = ia->live_dev.n_live;
+    inf.rows_live_b = ib->live_dev.n_live;
+    ia->xk_info = inf;
+    return ZH_OK;
+}
+
+extern "C" int zh_cross_knn_device(zh_index *ia, zh_index *ib, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *d_out_ids,
+                                   uint64_t *d_out_keys, uint32_t *d_out_counts, void *stream) {
+    int rc = xknn_args(ia, ib, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, "zh_cross_knn_device");
+    if (rc || n == 0) return rc;
+    return xknn_call(ia, ib, first_row, n, k, metric, mode, d_out_ids, d_out_keys, d_out_counts, false, stream, "zh_cross_knn_device");
+}
+
+extern "C" int zh_cross_knn(zh_index *ia, zh_index *ib, uint64_t first_row, uint64_t n, size_t k, int metric, int mode, uint64_t *out_ids, uint64_t *out_keys,
+                            uint32_t *out_counts) {
+    int rc = xknn_args(ia, ib, n, k, metric, mode, out_ids, out_keys, out_counts, "zh_cross_knn");
+    if (rc || n == 0) return rc;
+    return xknn_call(ia, ib, first_row, n, k, metric, mode, out_ids, out_keys, out_counts, true, nullptr, "zh_cross_knn");
+}
+
+extern "C" int zh_cross_knn_info(const zh_index *ia, zh_xknn_info *out) { return get_info(ia, &zh_index::xk_info, out, "zh_cross_knn_info"); }
 
 // ------------------------------------------------------------------------------------------------
 // forest k-NN graph (zh_fknn.hip): each row's k nearest rows among its leaf-mates over all trees.  DESIGN.md s17

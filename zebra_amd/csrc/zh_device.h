@@ -799,8 +799,9 @@ struct PoolSink {
 
 // The list sink (the graphs): every held line has its own tau, count and (row, lo, hi) list -- ZhExact2's layout, `cap` slots a line of which `lim`
 // may be filled.  Self is the column with the line's own row number; a masked row on either side is no pair.  The 16 lanes of a k-group h share
-// the line: one atomic for the group, taken by its first passing lane.  A list that runs over raises *over.
-template <int KINDA>
+// the line: one atomic for the group, taken by its first passing lane.  A list that runs over raises *over.  SELF = false (the k-NN join between two
+// indexes: the two sides' row numbers are unrelated) skips no column for its number.
+template <int KINDA, bool SELF = true>
 struct ListSink {
     uint32_t lane;
     float Kc, rho;
@@ -830,7 +831,7 @@ struct ListSink {
         for (int i = 0; i < 4; i++) {
             bool pass = false;
             uint32_t lo = 0, hi = 0;
-            if (id[i] != 0xFFFFFFFFu && cb != 0xFFFFFFFFu && cb != id[i]) {
+            if (id[i] != 0xFFFFFFFFu && cb != 0xFFFFFFFFu && (!SELF || cb != id[i])) {
                 const uint64_t iv = approx_interval<KINDA>(t[i] * meta[i].y, meta[i].x, qb, Kc, rho, 0.f);
                 lo = (uint32_t)iv; hi = (uint32_t)(iv >> 32);
                 pass = lo <= tq[i];

@@ -428,6 +428,16 @@ hipError_t zh_launch_knn_mfma(uint32_t d, int metric, int mode, const ZhExact2 &
 hipError_t zh_launch_knn_emit(const uint64_t *dInIds, const uint64_t *dInKeys, const uint32_t *dInCounts, uint32_t w, const uint32_t *dRows, uint32_t B,
                               uint64_t id_base, uint64_t first_row, uint32_t k, uint64_t *dOutIds, uint64_t *dOutKeys, uint32_t *dOutCounts, hipStream_t s);
 
+// ---- the exact k-NN join between two indexes (zh_xknn.hip): each live row of A's k nearest live rows of B, panel by panel of A.  Panels, their
+// gather (zh_launch_knn_panel over A's copy), chunks and lists are the graph's
+// the scan of the panel (e.B lines of A; the lists per LINE) against positions [p_begin, p_end) of B's copy (e.Xh); dQmB / dCidB: zh_launch_join_prep
+// of B; no column is skipped for its number.  Of e it reads Xh (B's copy), B, Kc, rho (A's) and the lists
+hipError_t zh_launch_xknn_mfma(uint32_t d, int metric, int mode, const ZhExact2 &e, const float4 *dQmB, const uint32_t *dCidB, uint64_t p_begin, uint64_t p_end,
+                               const void *dA, const float2 *dPMeta, const uint32_t *dPid, hipStream_t s);
+// a panel's answer [B][k] (zh_launch_final's) to the lines' places: line dRows[b] - first_row gets the first min(count, k) entries as they are
+hipError_t zh_launch_xknn_emit(const uint64_t *dInIds, const uint64_t *dInKeys, const uint32_t *dInCounts, const uint32_t *dRows, uint32_t B,
+                               uint64_t first_row, uint32_t k, uint64_t *dOutIds, uint64_t *dOutKeys, uint32_t *dOutCounts, hipStream_t s);
+
 // ---- the forest k-NN graph (zh_fknn.hip): each row's k nearest rows among its leaf-mates over all trees
 #define ZH_FKNN_SLAB 65536u       // lines of a sub-slab: the unit of the row -> leaf table, of path 1 and of a redo
 #define ZH_FKNN_HELD_ROWS 4096u   // path 2: members of one leaf a segment holds at most; held lines of a batch (256 tiles)

@@ -601,6 +601,25 @@ class LSHIndex:
         candidates, launches, tiles"""
         return self._info(_ffi.CrossInfo, lib().zh_cross_join_info)
 
+    def cross_knn(self, other, k, metric, first_row=0, n=None):
+        """EXACT k-NN join between two indexes over the slab of self's stored rows [first_row, first_row + n) (default: to the last stored row):
+        line i holds the k nearest live rows of `other` to stored row first_row + i of self by (key, id) -- other.search_exact_batch's answer for
+        that row's f32 values as the query, bit for bit; nothing is excluded.  other.cross_knn(self) is a different call.
+        -> (ids [n,k] u64 with other's id_base, keys [n,k] u64, counts [n] u32); counts = min(k, live rows of other), 0 for a removed row of
+        self; entries past the count are 2^64-1."""
+        h = self._cross_other(other)
+        return self._graph(lambda me, *rest: lib().zh_cross_knn(me, h, *rest), k, metric, first_row, n)
+
+    def cross_knn_device(self, other, k, metric, first_row, n, d_ids_ptr, d_keys_ptr, d_counts_ptr, stream=None):
+        """cross_knn with the outputs ([n,k] u64 twice, [n] u32) already in device memory (raw pointers, e.g. torch .data_ptr())."""
+        check(lib().zh_cross_knn_device(self._h, self._cross_other(other), int(first_row), int(n), k, metric.metric, metric.mode, d_ids_ptr,
+                                        d_keys_ptr, d_counts_ptr, stream))
+
+    def cross_knn_info(self):
+        """what the most recent cross_knn with this index on the left did (zh_cross_knn_info): rows_live_a, rows_live_b, lines, k, path, redone,
+        survivors, launches, tiles"""
+        return self._info(_ffi.CrossKnnInfo, lib().zh_cross_knn_info)
+
     def remove_within(self, other, radius, metric):
         """drop what the corpus already has: every live row of self that has a live row of `other` within `radius` is removed from self (the
         distinct a of cross_join's pairs; `other` is left alone) -> the removed ids, ascending"""
@@ -1422,6 +1441,14 @@ class Database:
         dist = self._key_numbers(keys)
         return [(self._documents.get(x), other_db._documents.get(y), float(v)) for x, y, v in zip(a.tolist(), b.tolist(), dist.tolist())]
 
+    def nearest_in(self, other_db, k):
+        """every record's k nearest records of `other_db` (LSHIndex.cross_knn: exact; the key is other_db's stored vector against this
+        database's as the query, under this database's metric) -> {document: [(other document, distance), ...]}, nearest first, one entry per
+        live record.  The distance is the number the key holds, as in near_duplicates."""
+        if self.index.no_vectors():
+            return {}
+        return self._graph_documents(*self.index.cross_knn(other_db.index, k, self.metric), neighbours=other_db._documents)
+
     def remove_within(self, other_db, radius):
         """LSHIndex.remove_within against other_db's index, then the removed ids' documents go too -> the removed ids"""
         removed = self.index.remove_within(other_db.index, radius, self.metric)
@@ -1512,7 +1539,9 @@ class Database:
                                                                     beam=max(int(beam), int(number_of_results)), **kw)
         return {b: {int(i): self._documents.get(int(i)) for i in ids[b, :counts[b]]} for b in range(ids.shape[0])}
 
-    def _graph_documents(self, ids, keys, counts):
+    def _graph_documents(self, ids, keys, counts, neighbours=None):
+        """lines of this database's rows as documents; neighbours: the documents the ids name (default: this database's own)"""
+        neighbours = self._documents if neighbours is None else neighbours
         dist = self._key_numbers(np.ascontiguousarray(keys)).reshape(keys.shape)
         base = self.index.id_base
         out = {}
@@ -1520,7 +1549,7 @@ class Database:
             if (base + r) not in self._documents:
                 continue  # a removed row's line
             c = int(counts[r])
-            out[self._documents[base + r]] = [(self._documents.get(i), float(v)) for i, v in zip(ids[r, :c].tolist(), dist[r, :c].tolist())]
+            out[self._documents[base + r]] = [(neighbours.get(i), float(v)) for i, v in zip(ids[r, :c].tolist(), dist[r, :c].tolist())]
         return out
 
     def deduplicate_within(self, radius):

@@ -1,7 +1,10 @@
-"""The kind x dimension table of the canonical-row kernels (zh_dispatch_kind_dim: exact_score_kernel, refine_line_kernel, nnd_line_kernel,
-gsearch_kernel), walked once: d = 128 / 384 / 768 have a specialised instantiation for every kind, 256 / 512 / 1024 for L2 and cosine only, so that
-Manhattan takes the generic row loop there.  A dimension that reached another dimension's instantiation, or a kind another kind's, changes keys:
-everything below is compared bit for bit -- integer keys under the order contract, no tolerance.
+"""A sample of the kind x dimension table of the canonical-row kernels (zh_dispatch_kind_dim): three kinds of the ten -- L2 squared, parity cosine,
+Manhattan -- at the six specialised dimensions, through four of the eight kernels on the table (exact_score_kernel, refine_line_kernel,
+nnd_line_kernel, gsearch_kernel; the module was written before prune, extend and the filtered and steered search joined the dispatch).  d = 128 /
+384 / 768 have a specialised instantiation for every kind, 256 / 512 / 1024 for L2 and cosine only, so that Manhattan takes the generic row loop
+there.  The full walk -- every kind at every D, the generic loop at odd and neighbouring dimensions, all eight kernels -- is
+tests/test_gpu_dispatch_table.py.  A dimension that reached another dimension's instantiation, or a kind another kind's, changes keys: everything
+below is compared bit for bit -- integer keys under the order contract, no tolerance.
 
 One 300-row table per d (refine_cases.table with its 40 identical rows, refine_cases.removed_rows removed), the ring graph at in_k = 8."""
 import numpy as np

@@ -88,8 +88,9 @@ __host__ __device__ inline int zh_kind_of(int metric) {
     }
 }
 
-// The host's one table of the canonical-row kernels' instantiations (exact_score_kernel, refine_line_kernel, nnd_line_kernel, gsearch_kernel): ten
-// kinds; d = 128 / 384 / 768 specialised for every kind, 256 / 512 / 1024 as well for the two simsimd kinds; any other d is the generic 0.
+// The host's one table of the canonical-row kernels' instantiations (exact_score_kernel, refine_line_kernel, nnd_line_kernel, prune_line_kernel,
+// gsearch_kernel, gsearch_filtered_kernel, gsearch_steered_kernel, gext_rerank_kernel): ten kinds; d = 128 / 384 / 768 specialised for every kind,
+// 256 / 512 / 1024 as well for the two simsimd kinds; any other d is the generic 0.  tests/test_gpu_dispatch_table.py walks all of it.
 // -> f(kind, dim), both std::integral_constant<int, ..>, so that a generic lambda names its kernel with them.
 template <int KIND, class F>
 inline hipError_t zh_dispatch_dim(uint32_t d, F &f) {
